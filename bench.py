@@ -14,11 +14,17 @@ the decompress of its step and the compress of the next one (two output buffers 
 timed region.  At N = 8 every rank receives 7 x 0.73 GiB per step, so the step time is the larger of the codec
 time and the all-gather time.
 
-The default single-GPU run (no workload flags) also measures the other configurations BASELINE.json names, each at full size and
-bit-exact, and files them under "extra_configs" of the same line (the headline keys are unchanged): synthetic text at level 1
+A plain run sets up, warms up, times --steps steps and prints the line; nothing else.  `--full` adds what the headline does
+not need: the CPU baseline of the oracle (cpu_baseline), the N > 1 steps without the gather (value_no_gather), and, on the
+default single-GPU workload (no workload flags), the other configurations BASELINE.json names, each at full size and
+bit-exact, filed under "extra_configs" of the same line (the headline keys are unchanged): synthetic text at level 1
 (1 GiB, and 10 MiB = a dickens-sized call), the mixed corpus at level 5 (configs[2]), decompress-only of oracle-built level-5
 frames (configs[4]: 4 GiB of 1 MiB frames, and one single 256 MiB frame).  Every entry carries value, stage_ms (one kernel per
 stage), roofline and cpu_baseline; `--no-extra` skips them (tools/profile_round.sh profiles one workload per run).
+
+`--dump-outputs DIR` writes what the last timed step handed its caller (rank 0) as DIR/<name>.npy: the compressed frames
+(roundtrip only), their size, and the decompressed bytes, as float32 byte values — all of an output up to DUMP_SAMPLE bytes,
+else a fixed, seeded sample of DUMP_SAMPLE positions.  The inputs are seeded, so two builds can be compared output for output.
 
 Prints ONE JSON line on rank 0.
 """
@@ -35,6 +41,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 HBM_PEAK_GBPS = 8000.0          # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.29 TB/s measured float4 copy)
+DUMP_SAMPLE = 6_000_000         # bytes kept per dumped output: two outputs of 24 MB each stay under 64 MB in all
 
 
 def make_zipf(n, seed, device):
@@ -101,6 +108,23 @@ def roofline(stages, alg_bytes, workload, n, t_comp_ms=None):
     if t_comp_ms:       # north_star's wording: input bytes read per second by the whole COMPRESS side over the HBM peak
         r["hbm_read_frac_compress"] = round(n / (t_comp_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 5)
     return r
+
+
+def dump_outputs(directory, sizes, outputs):
+    """sizes: name -> number (saved as a float64 scalar); outputs: name -> uint8 device tensor, saved as float32 byte values,
+    whole up to DUMP_SAMPLE bytes, else at DUMP_SAMPLE sorted positions drawn from a generator seeded by the output's name."""
+    import zlib
+    import numpy as np
+    import torch
+    os.makedirs(directory, exist_ok=True)
+    for name, v in sizes.items():
+        np.save(os.path.join(directory, name + ".npy"), np.array(v, dtype=np.float64))
+    for name, t in outputs.items():
+        if t.numel() > DUMP_SAMPLE:
+            gen = torch.Generator().manual_seed(zlib.crc32(name.encode()))
+            idx = torch.randint(0, t.numel(), (DUMP_SAMPLE,), generator=gen).sort().values
+            t = t[idx.to(t.device)]
+        np.save(os.path.join(directory, name + ".npy"), t.cpu().numpy().astype(np.float32))
 
 
 def stage_times(lib, ctx, getter):
@@ -246,6 +270,8 @@ def run_decompress(env, args):
     elapsed = env.max_over_ranks(time.perf_counter() - t0)
     ok = env.all_ok(bool(torch.equal(want, back)))
     d.Dispose()
+    if args.dump_outputs and env.rank == 0:
+        dump_outputs(args.dump_outputs, {"decompressed_size": n}, {"decompressed": back})
     line = None
     if env.rank == 0:
         K = args.steps
@@ -264,7 +290,7 @@ def run_decompress(env, args):
             "stage_ms": {k: round(v, 4) for k, v in dec_ms.items()},
             "roofline": roofline(dec_ms, (1.0 + ratio) * n, workload, n),
         }
-        if env.world == 1 and not args.no_cpu_baseline:
+        if env.world == 1 and args.full and not args.no_cpu_baseline:
             import oracle_lib as o
             if args.frames == "oracle":         # whole frames of the same blob, up to the sample size (at least one)
                 k = max(1, min(args.cpu_sample_mib << 20, unique) // frame_bytes)
@@ -349,9 +375,12 @@ def run_roundtrip(env, args):
         last = dsts[(step_no - 1) % len(dsts)]
         ok = ok and bool(torch.equal(gathered[:cs], last[:cs]))
     ok = env.all_ok(ok)
-    # N > 1: the collective-free number beside the gathered one (K more steps, outside the contract's timed region)
+    if args.dump_outputs and rank == 0:
+        last = dsts[(step_no - 1) % len(dsts)]
+        dump_outputs(args.dump_outputs, {"compressed_size": cs, "decompressed_size": n}, {"compressed": last[:cs], "decompressed": back})
+    # N > 1, --full: the collective-free number beside the gathered one (K more steps, outside the contract's timed region)
     elapsed_ng = None
-    if comm is not None:
+    if comm is not None and args.full:
         env.sync()
         t0 = time.perf_counter()
         for _ in range(args.steps):
@@ -380,7 +409,7 @@ def run_roundtrip(env, args):
             "stage_ms": {k: round(v, 4) for k, v in allk.items()},
             "roofline": roofline(allk, (1.0 + ratio) * n, workload, n, t_comp),      # (1 + r) bytes per input byte, both directions
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             m = min(args.cpu_sample_mib << 20, n)
             sample = src[:m].cpu().numpy().tobytes()
             threads = max(1, min(16, len(os.sched_getaffinity(0)))) if args.cpu_all_cores else 1
@@ -426,11 +455,15 @@ def main():
     ap.add_argument("--gather-method", default="p2p", choices=["p2p", "padded"], help="N>1: exact-size grouped send/recv, or one padded all-gather + compaction")
     ap.add_argument("--cpu-sample-mib", type=int, default=256)
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="only the headline workload (the default single-GPU run also measures EXTRA_CONFIGS)")
+    ap.add_argument("--no-extra", action="store_true", help="--full: only the headline workload (a --full single-GPU run of the default workload also measures EXTRA_CONFIGS)")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need: the CPU baseline, value_no_gather (N > 1), EXTRA_CONFIGS")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed as DIR/<name>.npy (rank 0)")
     ap.add_argument("--parser", type=int, default=0, help="0 = region parse of dense chunks (default), 1 = tile loop only (ZSTDMI_CCtx_setParser)")
     ap.add_argument("--history", type=int, default=None, help="cross-chunk history in KiB per block (0 = independent 64 KiB frames; default: by level, "
                     "i.e. off at levels 1-2, 32 at levels >= 3)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     args.cpu_all_cores = True
     defaults = ap.parse_args([])
     workload_flags = ("size_mib", "input", "mode", "frames", "frame_mib", "unique_mib", "level", "parser", "history")
@@ -456,7 +489,7 @@ def main():
     env = Env(lib, z, torch, dist, dev, rank, world, local)
 
     line, ok = (run_decompress if args.mode == "decompress" else run_roundtrip)(env, args)
-    if world == 1 and is_default_workload and not args.no_extra:
+    if world == 1 and is_default_workload and args.full and not args.no_extra:
         import copy
         extras = []
         for name, over in EXTRA_CONFIGS:
@@ -464,6 +497,7 @@ def main():
             for k, v in over.items():
                 setattr(a, k, v)
             a.cpu_all_cores = False
+            a.dump_outputs = None
             t0 = time.perf_counter()
             try:
                 e, eok = (run_decompress if a.mode == "decompress" else run_roundtrip)(env, a)

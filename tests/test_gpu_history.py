@@ -89,19 +89,10 @@ def test_fast_strategy_with_far_history_beats_independent_chunks(gpu_lib, oracle
     block's first tiles have not overwritten it (what a global-memory table would buy).  The slack below is measured + 1 %."""
     if kind == "text":
         data = datagen.gen("text", 4 << 20, 6)
-    else:
-        import glob
-        data = b""
-        for f in sorted(glob.glob("/usr/lib/python3/dist-packages/**/*.py", recursive=True)):
-            try:
-                data += open(f, "rb").read()
-            except OSError:
-                pass
-            if len(data) >= (4 << 20):
-                break
-        data = data[:4 << 20]
-        if len(data) < (1 << 20):
-            pytest.skip("no Python sources on this box")
+    else:                   # 4 MiB of CPython's standard library sources (tests/golden/make_pysrc.py)
+        import hashlib, lzma, os
+        data = lzma.decompress(open(os.path.join(os.path.dirname(__file__), "golden", "pysrc_4m.xz"), "rb").read())
+        assert hashlib.sha256(data).hexdigest() == "4f4ad9c5e67f2b925dd24bc2d5d8ee185144c219368872e49f61095d8de5244d"
     with z.Compressor(1) as c, z.Decompressor() as d:
         plain = len(c.Wrap(data))
         set_history(gpu_lib, c, 32 << 10)

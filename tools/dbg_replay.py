@@ -1,7 +1,8 @@
 """Development aid: replay the sequences + literals of every chunk of one input (ZSTDMI_debugGetChunk) the way the decoder
 would and report the first inconsistency.  usage: dbg_replay.py <kind> <size> [seed]"""
 import sys, os, ctypes
-sys.path.insert(0, "/root/repo"); sys.path.insert(0, "/root/repo/tests")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import torch; torch.cuda.init()
 import datagen, zstdsharp_amd as z
 from zstdsharp_amd import _ffi

@@ -1,5 +1,5 @@
 #!/bin/bash
-# Round profiles: for every workload of the default bench line (headline + extra_configs), the three rocprofv3 passes of
+# Round profiles: for every workload of the `bench.py --full` line (headline + extra_configs), the three rocprofv3 passes of
 # tools/profile_round.sh (kernel stats, FETCH_SIZE, WRITE_SIZE; one workload per process).  Run on the GPU box through gpurun; then
 # copy gpurun_out/prof/<tag>_* into profiles/.
 set -e
