@@ -32,9 +32,13 @@ typedef struct ZSTD_DCtx_s ZSTD_DCtx;
 enum {
     ZSTD_c_compressionLevel = 100, ZSTD_c_windowLog = 101, ZSTD_c_hashLog = 102, ZSTD_c_chainLog = 103,
     ZSTD_c_searchLog = 104, ZSTD_c_minMatch = 105, ZSTD_c_targetLength = 106, ZSTD_c_strategy = 107,
+    ZSTD_c_enableLongDistanceMatching = 160, ZSTD_c_ldmHashLog = 161, ZSTD_c_ldmMinMatch = 162, ZSTD_c_ldmBucketSizeLog = 163,
+    ZSTD_c_ldmHashRateLog = 164,
     ZSTD_c_contentSizeFlag = 200, ZSTD_c_checksumFlag = 201, ZSTD_c_dictIDFlag = 202, ZSTD_c_nbWorkers = 400,
     ZSTD_d_windowLogMax = 100
 };
+/* U/ZSTD_paramSwitch_e.cs: the values of ZSTD_c_enableLongDistanceMatching */
+enum { ZSTD_ps_auto = 0, ZSTD_ps_enable = 1, ZSTD_ps_disable = 2 };
 
 /* ---- compression context: S/Compressor.cs:32,60,138 -> U/ZstdCompress.cs:24-27, 43-62, 137-160 ---- */
 ZSTD_CCtx* ZSTD_createCCtx(void);
@@ -43,7 +47,17 @@ size_t     ZSTD_freeCCtx(ZSTD_CCtx* cctx);                                   /* 
  * with a probing step and raw literals, as U/ZstdCompress.cs:7915-7920 + U/ZstdCompressInternal.cs:146-173), checksumFlag,
  * dictIDFlag, strategy (1..9, mapped onto the three finders) and targetLength are honoured; windowLog >= 16, contentSizeFlag = 1,
  * nbWorkers = 0, and for hashLog / minMatch / chainLog / searchLog the value the kernels implement (13; 6 or 5; the level's
- * own) are accepted; anything else within bounds returns parameter_unsupported — nothing is silently ignored. */
+ * own) are accepted; anything else within bounds returns parameter_unsupported — nothing is silently ignored.
+ * Long-distance matching (U/ZstdLdm.cs, U/ZstdCompress.cs:560-595, 1106-1160): ZSTD_c_enableLongDistanceMatching = ZSTD_ps_enable
+ * adds matches at any distance inside a window (ZSTD_c_windowLog, default 2^27 under LDM, shrunk to the input) to what the block
+ * finders find.  A frame then holds min(window, 512 MiB, one pass) of content; windows below 2^17 and inputs of one block
+ * (<= 64 KiB) are written as without LDM.  ldmHashLog (6..30), ldmMinMatch (4..4096), ldmBucketSizeLog (1..8) and ldmHashRateLog
+ * (0..25) follow ZSTD_ldm_adjustParameters when 0; ldmHashRateLog 1..4 returns parameter_unsupported (the split workspace holds at
+ * most one split per 16 bytes), and a derived one below 5 is raised to 5.  ZSTD_ps_auto (the default) and ZSTD_ps_disable write
+ * exactly what a context that never set the switch writes: the reference's auto rule (on for btopt and above at windowLog >= 27,
+ * U/ZstdCompress.cs:276-284) is deliberately not adopted, so that no level's output changes.  ZSTD_compressCCtx ignores the switch
+ * (level-only parameters, as the reference).  With a dictionary loaded, an LDM call of more than one block returns
+ * parameter_unsupported from ZSTD_compress2; ZSTD_compressStream2 finds LDM matches inside each 16 MiB batch, not across batches. */
 size_t     ZSTD_CCtx_setParameter(ZSTD_CCtx* cctx, int param, int value);
 size_t     ZSTD_CCtx_getParameter(const ZSTD_CCtx* cctx, int param, int* value);
 /* S/Compressor.cs:43-56 (dictionary load) -> U/ZstdCompress.cs:1286-1330, 5465-5503.  RAW-CONTENT dictionaries (any bytes

@@ -5,6 +5,13 @@ from . import _ffi
 from .errors import DST_SIZE_TOO_SMALL, ensure_zstd_success
 
 ZSTD_c_compressionLevel = 100
+# long-distance matching (include/zstd_mi355x.h): the switch takes ZSTD_ps_*; the others 0 = from the window
+ZSTD_c_enableLongDistanceMatching = 160
+ZSTD_c_ldmHashLog = 161
+ZSTD_c_ldmMinMatch = 162
+ZSTD_c_ldmBucketSizeLog = 163
+ZSTD_c_ldmHashRateLog = 164
+ZSTD_ps_auto, ZSTD_ps_enable, ZSTD_ps_disable = 0, 1, 2
 
 
 def _as_buffer(data):

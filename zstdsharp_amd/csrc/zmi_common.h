@@ -160,6 +160,10 @@ struct StageHook {
     void operator()(const char* name) const { if (fn) fn(self, name); }
 };
 
+// Long-distance matching (ldm.hip) as a call resolves it (ZSTD_ldm_adjustParameters, U/ZstdLdm.cs:187-212)
+struct LdmLaunch { u32 minMatch, hashLog, bucketLog, hashRateLog; };
+constexpr u32 kLdmMinHashRateLog = 5;      // the split workspace keeps at most one split per 16 bytes: denser split rates are refused
+
 // error codes: U/ZSTD_ErrorCode.cs
 enum : u32 {
     kErrGeneric = 1, kErrPrefixUnknown = 10, kErrVersionUnsupported = 12, kErrFrameParameterUnsupported = 14,

@@ -31,6 +31,13 @@ void launch_scan_sizes(const ChunkMeta* meta, u32 nChunks, u64* offsets, u64* to
 void launch_gather(const u8* src, u64 srcSize, const u8* slots, const ChunkMeta* meta, const u64* offsets, u8* dst, u64 dstCapacity,
                    u32 nChunks, u32 chunkBytes, hipStream_t stream);
 void launch_xxh64(const u8* src, u64 srcSize, ChunkMeta* meta, u32 nChunks, u32 chunkBytes, u32 frameBlocks, hipStream_t stream);
+// long-distance matching (ldm.hip)
+size_t ldm_small_bytes(u64 n);
+size_t ldm_big_bytes(u64 nSplits);
+void launch_ldm_count(const u8* src, u64 n, u64 frameSpan, const LdmLaunch& p, u8* small, hipStream_t stream);
+u32* ldm_total_word(u8* small, u64 n);
+void launch_ldm_rest(const u8* src, u64 n, u32 nChunks, u32 chunkBytes, u64 frameSpan, const LdmLaunch& p, u32 nSplits, u8* small, u8* big,
+                     Seq* seqs, u8* lits, ChunkMeta* meta, hipStream_t stream, StageHook hook);
 // decoder (decode_walk.hip, decode_lit.hip, decode_seq.hip)
 size_t decode_walk_workspace_bytes(u64 srcSize);
 void launch_frame_walk_count(const u8* src, u64 srcSize, u32 maxFrames, u32* status, u8* walkWs, hipStream_t stream);
@@ -134,9 +141,11 @@ struct ZSTD_CCtx_s {
     int level = 3;              // ZSTD_CLEVEL_DEFAULT
     int checksumFlag = 0, contentSizeFlag = 1, dictIDFlag = 1;
     int windowLog = 0, hashLog = 0, chainLog = 0, searchLog = 0, minMatch = 0, targetLength = 0, strategy = 0;
+    int ldm = 0, ldmHashLog = 0, ldmMinMatch = 0, ldmBucketSizeLog = 0, ldmHashRateLog = 0;     // ZSTD_c_enableLongDistanceMatching .. (0 = auto / from the window)
     int device = 0; bool deviceOk = false;
     hipStream_t ownStream = nullptr, stream = nullptr;
     DevBuf seqs, lits, meta, tables, slots, offsets, total, cand, probe, stageSrc, stageDst;
+    DevBuf ldmSmall, ldmBig;    // long-distance matching's workspace (allocated by the first call that runs it)
     u32 lastChunks = 0;         // chunks of the last pass (debug hook)
     const u8* lastSrc = nullptr; u32 lastChunkBytes = 0;     // its source (debug hook: chunks without sequences keep their literals there)
     u32 passChunks = 16384;     // chunks per pass: 1 GiB of input bounds the HBM workspace to ~4.2 GiB
@@ -233,12 +242,14 @@ static size_t dctx_bind(ZSTD_DCtx* d)
 struct CallParams {
     int level = 3, checksumFlag = 0, contentSizeFlag = 1, dictIDFlag = 1, strategy = 0, targetLength = 0, windowLog = 0, searchLog = 0;
     int minMatch = 0, chainLog = 0;     // accepted by the setters only at the value the kernels implement for the level/strategy in force THEN: checked again per call
+    int ldm = 0, ldmHashLog = 0, ldmMinMatch = 0, ldmBucketSizeLog = 0, ldmHashRateLog = 0;     // (ZSTD_compressCCtx: all 0, as the reference's level-only parameters)
     bool useDict = true;
 };
 static CallParams sticky_params(const ZSTD_CCtx* c)
 {
     CallParams p; p.level = c->level; p.checksumFlag = c->checksumFlag; p.contentSizeFlag = c->contentSizeFlag; p.dictIDFlag = c->dictIDFlag;
     p.strategy = c->strategy; p.targetLength = c->targetLength; p.windowLog = c->windowLog; p.searchLog = c->searchLog; p.minMatch = c->minMatch; p.chainLog = c->chainLog; p.useDict = true;
+    p.ldm = c->ldm; p.ldmHashLog = c->ldmHashLog; p.ldmMinMatch = c->ldmMinMatch; p.ldmBucketSizeLog = c->ldmBucketSizeLog; p.ldmHashRateLog = c->ldmHashRateLog;
     return p;
 }
 
@@ -309,9 +320,54 @@ static size_t cctx_sync_dictionary(ZSTD_CCtx* c)
 // How a range of paramSize bytes is cut into blocks and frames (a function of the parameters, the loaded dictionary and that size):
 // bytes of dictionary in front of every chunk, bytes per block, blocks per frame (0 = every block a frame of its own), and what
 // the level resolves to for it.
-struct Framing { u32 prefixLen, chunkBytes, frameBlocks; Resolved rs; u32 indepWindowLog = 0; size_t span() const { return (size_t)chunkBytes * (frameBlocks ? frameBlocks : 1u); } };
+struct Framing { u32 prefixLen, chunkBytes, frameBlocks; Resolved rs; u32 indepWindowLog = 0; bool ldm = false; LdmLaunch ldmP = {};
+                 size_t span() const { return (size_t)chunkBytes * (frameBlocks ? frameBlocks : 1u); } };
+
+// Long-distance matching (ZSTD_c_enableLongDistanceMatching = ZSTD_ps_enable): on for a call of more than one block whose window is
+// at least 2^17 (below, frames are no longer than the block finders' own reach and there is nothing for it to find).  The window is
+// ZSTD_c_windowLog, or 2^27 (U/ZstdCompress.cs:2166-2171), shrunk to the input as ZSTD_adjustCParams does; the LDM parameters
+// left at 0 follow from it as ZSTD_ldm_adjustParameters derives them (U/ZstdLdm.cs:187-212).  ZSTD_ps_auto and ZSTD_ps_disable
+// are off: the reference's auto rule (btopt and above with windowLog >= 27) is not adopted, so no level's output changes.
+constexpr int kLdmDefaultWindowLog = 27;
+constexpr u64 kLdmMaxFrame = (u64)512 << 20;        // every offset stays below the decoder's 2^29 record limit (kRecOffMax)
+static int ldm_window_log(const CallParams& cp) { return cp.windowLog ? cp.windowLog : kLdmDefaultWindowLog; }
+static bool ldm_active(const CallParams& cp, size_t paramSize) { return cp.ldm == 1 && paramSize > kChunkSize && ldm_window_log(cp) >= 17; }
+static LdmLaunch ldm_resolve(const CallParams& cp, size_t paramSize)
+{
+    u32 wl = (u32)ldm_window_log(cp);
+    u32 need = 10; while (need < 31 && ((u64)1 << need) < paramSize) ++need;
+    if (wl > need) wl = need;
+    LdmLaunch p;
+    p.minMatch = cp.ldmMinMatch ? (u32)cp.ldmMinMatch : 64u;
+    p.hashLog = cp.ldmHashLog ? (u32)cp.ldmHashLog : (wl > 13 ? wl - 7 : 6u);
+    p.bucketLog = cp.ldmBucketSizeLog ? (u32)cp.ldmBucketSizeLog : 3u;
+    if (p.bucketLog > p.hashLog) p.bucketLog = p.hashLog;
+    p.hashRateLog = cp.ldmHashRateLog ? (u32)cp.ldmHashRateLog : (wl > p.hashLog ? wl - p.hashLog : 0u);
+    if (p.hashRateLog < kLdmMinHashRateLog) p.hashRateLog = kLdmMinHashRateLog;      // (a derived value; a set one below it was refused)
+    return p;
+}
+
 static Framing resolve_framing(const ZSTD_CCtx* c, const CallParams& cp, size_t paramSize)
 {
+    if (ldm_active(cp, paramSize)) {
+        // Under LDM a frame is a window: min(2^windowLog, 512 MiB, the pass) of content (ldm.hip matches never leave their frame, so
+        // no offset exceeds what the frame declares).  Blocks and history are those the level's windowLog > 16 path picks: full
+        // 64 KiB blocks with far candidates at the fast strategy, 64 KiB - 16/32 KiB blocks behind LDS history above it.
+        Framing f; f.prefixLen = 0; f.indepWindowLog = 0; f.ldm = true; f.ldmP = ldm_resolve(cp, paramSize);
+        const u32 wl = (u32)ldm_window_log(cp);
+        const u64 win = ((u64)1 << wl) < kLdmMaxFrame ? ((u64)1 << wl) : kLdmMaxFrame;
+        const Resolved rf = resolve_call(cp, paramSize < win ? paramSize : (size_t)win, (u32)(win < ((u64)1 << 31) ? win : ((u64)1 << 31)));
+        u32 chunkBytes = kChunkSize;
+        if (rf.finder != 0) {
+            const int hb = c->historyBytes > 0 ? c->historyBytes : (rf.cp.strategy == kStratDfast ? (16 << 10) : (32 << 10));
+            chunkBytes = kChunkSize - (round_tile((size_t)hb) > (48u << 10) ? (48u << 10) : round_tile((size_t)hb));
+        }
+        u32 frameBlocks = (u32)(win / chunkBytes);
+        if (frameBlocks > c->passChunks) frameBlocks = c->passChunks;
+        if (frameBlocks < 2) frameBlocks = 2;
+        f.chunkBytes = chunkBytes; f.frameBlocks = frameBlocks; f.rs = rf;
+        return f;
+    }
     const u32 prefixLen = cp.useDict ? dict_prefix_len(c, paramSize) : 0u;
     u32 chunkBytes = kChunkSize - round_tile(prefixLen);
     // ZSTD_c_windowLog 10 .. 15: independent frames of 1 << windowLog bytes (the reference cuts blocks at the window size and lets
@@ -397,6 +453,7 @@ static size_t compress_range(ZSTD_CCtx* c, const CallParams& cp, u8* d_dst, size
     const u8* prefix = prefixLen ? (const u8*)c->dict.p + (c->dictHost.size() - prefixLen) : nullptr;
     const u64 totalChunks = (srcSize + chunkBytes - 1) / chunkBytes;
     u32 passChunks = (u32)(totalChunks < c->passChunks ? totalChunks : c->passChunks);
+    if (fr.ldm) { const u32 most = (u32)(((u64)1 << 31) / chunkBytes) / frameBlocks * frameBlocks; if (passChunks > most) passChunks = most; }    // (ldm.hip: u32 offsets in a pass)
     if (frameBlocks && passChunks < totalChunks) { passChunks -= passChunks % frameBlocks; if (!passChunks) passChunks = frameBlocks; }     // frames never straddle passes
     if (!cctx_workspace(c, passChunks)) return ZERR(kErrMemoryAllocation);
     const bool regionParse = rs.minStrideLog == 0 && !(rs.finder == 0 && frameBlocks && chunkBytes >= kChunkSize) && c->parser == 0;   // (not the far-candidate finder)
@@ -418,6 +475,19 @@ static size_t compress_range(ZSTD_CCtx* c, const CallParams& cp, u8* d_dst, size
         c->timer.begin(s);
         launch_lz(rs.finder, src, n, nChunks, seqs, lits, meta, prefix, prefixLen, chunkBytes, dictIdBytes | (cp.contentSizeFlag ? 0u : 0x100u) | (hdrWindow << 12), rs.minStrideLog, lzFrameBlocks, regionParse ? (u16*)c->cand.p : nullptr, hcChains ? (u16*)((u8*)c->cand.p + cand_plane_bytes(passChunks)) : nullptr,
                   regionParse ? (u32*)((u8*)c->cand.p + cand_plane_bytes(passChunks) * (hcChains ? 2 : 1)) : nullptr, hcDepth, s, c->timer.hook(), (u32*)(total + 4));      // (the claim counter: a word of `total`'s 64 bytes)
+        if (fr.ldm) {       // long-distance matches into the finder's sequence store (ldm.hip); the splits are counted first to size the workspace
+            const u64 span = (u64)frameBlocks * chunkBytes;
+            if (!c->ldmSmall.ensure(ldm_small_bytes(n))) return ZERR(kErrMemoryAllocation);
+            launch_ldm_count(src, n, span, fr.ldmP, (u8*)c->ldmSmall.p, s);
+            u32 nSplits = 0;
+            if (hipMemcpyAsync(&nSplits, ldm_total_word((u8*)c->ldmSmall.p, n), sizeof(u32), hipMemcpyDeviceToHost, s) != hipSuccess) return ZERR(kErrGeneric);
+            if (hipStreamSynchronize(s) != hipSuccess) { (void)hipGetLastError(); return ZERR(kErrGeneric); }
+            c->timer.mark("ldm_count", s);
+            if (nSplits) {
+                if (!c->ldmBig.ensure(ldm_big_bytes(nSplits))) return ZERR(kErrMemoryAllocation);
+                launch_ldm_rest(src, n, nChunks, chunkBytes, span, fr.ldmP, nSplits, (u8*)c->ldmSmall.p, (u8*)c->ldmBig.p, seqs, lits, meta, s, c->timer.hook());
+            }
+        }
         launch_huf_build(lits, meta, tables, slots, nChunks, rs.rawLiterals, src, chunkBytes, s, c->timer.hook());
         if (cp.checksumFlag) { launch_xxh64(src, n, meta, nChunks, chunkBytes, frameBlocks, s);             c->timer.mark("xxh64", s); }
         launch_seq_encode(seqs, meta, slots, nChunks, strategy, (cp.checksumFlag ? 1u : 0u) | (cp.contentSizeFlag ? 0u : 2u) | (hdrWindow << 8), 1, dictID, dictIdBytes, initReps, frameBlocks, chunkBytes, n, s);   c->timer.mark("seq_encode", s);
@@ -464,6 +534,7 @@ static size_t probe_group_bytes(ZSTD_CCtx* c, const CallParams& cp, size_t srcSi
     err = 0;
     // (a caller-set targetLength keeps the level's own path: at the fast strategy it means raw literals, which the sparse ranges must not inherit)
     if (!(srcSize >= (4u << 20) && c->historyBytes < 0 && cp.strategy == 0 && cp.windowLog == 0 && cp.searchLog == 0 && cp.targetLength == 0)) return 0;
+    if (ldm_active(cp, srcSize)) return 0;          // (one range: LDM frames are windows)
     if (cp.useDict) { err = cctx_sync_dictionary(c); if (isErr(err)) return 0; err = 0; }
     if (cp.useDict && dict_prefix_len(c, srcSize)) return 0;
     if (resolve_call(cp, srcSize, kChunkSize).cp.strategy <= kStratFast) return 0;
@@ -503,6 +574,12 @@ static void plan_ranges(const std::vector<u32>& counts, size_t group, size_t src
         out.push_back(r);
         g = e;
     }
+}
+// LDM together with a dictionary: the dictionary's framing (a prefix in front of independent 64 KiB frames) cannot hold a window-sized frame
+static size_t check_ldm_dict(const ZSTD_CCtx* c, const CallParams& cp, size_t srcSize)
+{
+    if (ldm_active(cp, srcSize) && cp.useDict && (c->dictFormatted || c->dictHost.size() >= 8)) return ZERR(kErrParameterUnsupported);
+    return 0;
 }
 static size_t check_call_params(const CallParams& cp)
 {
@@ -588,6 +665,7 @@ static size_t compress_device(ZSTD_CCtx* c, const CallParams& cp, u8* d_dst, siz
 {
     bool first = true;
     { const size_t e = check_call_params(cp); if (isErr(e)) return e; }
+    { const size_t e = check_ldm_dict(c, cp, srcSize); if (isErr(e)) return e; }
     size_t err = 0;
     const size_t group = probe_group_bytes(c, cp, srcSize, err);
     if (isErr(err)) return err;
@@ -615,7 +693,7 @@ size_t ZSTD_freeCCtx(ZSTD_CCtx* c)
         (void)hipSetDevice(c->device);
         if (c->ownStream) (void)hipStreamSynchronize(c->ownStream);
         c->seqs.release(); c->lits.release(); c->meta.release(); c->tables.release(); c->slots.release(); c->cand.release(); c->probe.release();
-        c->gatherIn.release(); c->gatherOut.release(); c->offsets.release(); c->total.release(); c->stageSrc.release(); c->stageDst.release(); c->dict.release(); c->dictFullDev.release(); c->dictInfoDev.release();
+        c->gatherIn.release(); c->gatherOut.release(); c->ldmSmall.release(); c->ldmBig.release(); c->offsets.release(); c->total.release(); c->stageSrc.release(); c->stageDst.release(); c->dict.release(); c->dictFullDev.release(); c->dictInfoDev.release();
         c->timer.destroy();
         if (c->ownStream) (void)hipStreamDestroy(c->ownStream);
     }
@@ -669,6 +747,23 @@ size_t ZSTD_CCtx_setParameter(ZSTD_CCtx* c, int param, int value)
     case ZSTD_c_searchLog:       // attempts per position of the greedy/lazy search = 1 << searchLog (used from 2 to 5: 4 .. 32 attempts)
         if (value != 0 && (value < 1 || value > 30)) return ZERR(kErrParameterOutOfBound);
         c->searchLog = value; return (size_t)value;
+    // Long-distance matching (ldm.hip; bounds: ZSTD_cParam_getBounds, U/ZstdCompress.cs:560-595).  0 = from the window.
+    case ZSTD_c_enableLongDistanceMatching:     // ZSTD_ps_auto (0) and ZSTD_ps_disable (2): off; ZSTD_ps_enable (1): on
+        if (value < 0 || value > 2) return ZERR(kErrParameterOutOfBound);
+        c->ldm = value; return (size_t)value;
+    case ZSTD_c_ldmHashLog:
+        if (value != 0 && (value < 6 || value > 30)) return ZERR(kErrParameterOutOfBound);
+        c->ldmHashLog = value; return (size_t)value;
+    case ZSTD_c_ldmMinMatch:
+        if (value != 0 && (value < 4 || value > 4096)) return ZERR(kErrParameterOutOfBound);
+        c->ldmMinMatch = value; return (size_t)value;
+    case ZSTD_c_ldmBucketSizeLog:
+        if (value != 0 && (value < 1 || value > 8)) return ZERR(kErrParameterOutOfBound);
+        c->ldmBucketSizeLog = value; return (size_t)value;
+    case ZSTD_c_ldmHashRateLog:                 // 1 .. kLdmMinHashRateLog - 1: a split every 2 .. 16 bytes, more than the workspace holds
+        if (value < 0 || value > 25) return ZERR(kErrParameterOutOfBound);
+        if (value != 0 && value < (int)kLdmMinHashRateLog) return ZERR(kErrParameterUnsupported);
+        c->ldmHashRateLog = value; return (size_t)value;
     default: return ZERR(kErrParameterUnsupported);
     }
 }
@@ -689,6 +784,11 @@ size_t ZSTD_CCtx_getParameter(const ZSTD_CCtx* c, int param, int* value)
     case ZSTD_c_minMatch: *value = c->minMatch; return 0;
     case ZSTD_c_targetLength: *value = c->targetLength; return 0;
     case ZSTD_c_strategy: *value = c->strategy; return 0;
+    case ZSTD_c_enableLongDistanceMatching: *value = c->ldm; return 0;
+    case ZSTD_c_ldmHashLog: *value = c->ldmHashLog; return 0;
+    case ZSTD_c_ldmMinMatch: *value = c->ldmMinMatch; return 0;
+    case ZSTD_c_ldmBucketSizeLog: *value = c->ldmBucketSizeLog; return 0;
+    case ZSTD_c_ldmHashRateLog: *value = c->ldmHashRateLog; return 0;
     default: return ZERR(kErrParameterUnsupported);
     }
 }
@@ -1164,6 +1264,7 @@ static size_t copy_any(void* dst, const void* src, size_t n, hipStream_t s)
 static size_t compress_multi(ZSTD_CCtx* c, const CallParams& cp, void* dst, size_t dstCapacity, const void* src, size_t srcSize)
 {
     { const size_t e = check_call_params(cp); if (isErr(e)) return e; }
+    { const size_t e = check_ldm_dict(c, cp, srcSize); if (isErr(e)) return e; }
     const size_t W = c->workers.size();
     bool ok = true;
     // the workers run with the parent's settings and dictionary
