@@ -99,10 +99,43 @@ size_t     ZSTD_decompressDCtx(ZSTD_DCtx* dctx, void* dst, size_t dstCapacity, c
 /* ---- errors: S/ThrowHelper.cs:12-13 -> U/ErrorPrivate.cs:10-24, 35-120 ---- */
 unsigned    ZSTD_isError(size_t code);
 const char* ZSTD_getErrorName(size_t code);
-/* S/ThrowHelper.cs:18-24 (EnsureZdictSuccess) -> U/Zdict.cs:11-19.  The trainer itself (ZDICT_trainFromBuffer, S/DictBuilder.cs)
- * is outside this library: a shim that keeps DictBuilder.cs routes that one call to the managed implementation. */
+/* S/ThrowHelper.cs:18-24 (EnsureZdictSuccess) -> U/Zdict.cs:11-19 */
 unsigned    ZDICT_isError(size_t code);
 const char* ZDICT_getErrorName(size_t code);
+
+/* ---- dictionary training: S/DictBuilder.cs -> U/Zdict.cs, U/Fastcover.cs, U/Cover.cs (dict_train.hip) ----
+ * The fastCover trainer on the GPU.  Host pointers in, host dictionary out; the work runs on device 0 (where a fresh ZSTD_CCtx
+ * binds) on a stream of the call's own, and everything is freed before return.  Calls from any number of threads are safe and
+ * give identical bytes.  The dictionary CONTENT for given (k, d, f, accel, splitPoint) is byte-identical to the reference's.
+ * The entropy tables and the k choice are not: their statistics and scores come from this library's compressor (each sample
+ * compressed alone against the candidate, in one batch), not from the reference's CPU parser.  Arguments are checked in the reference's order before the device is touched.
+ * Refused with parameter_unsupported: f > 24 (every candidate needs its own 2^f-entry u32 frequency copy in HBM), shrinkDict = 1, and
+ * training sets above 4 GiB - 8 KiB (positions are 32-bit).
+ * nbThreads is accepted and ignored.  Not provided: the COVER (non-fast) trainer, the legacy trainer and
+ * ZDICT_addEntropyTablesFromBuffer. */
+typedef struct { int compressionLevel; unsigned notificationLevel; unsigned dictID; } ZDICT_params_t;        /* U/ZDICT_params_t.cs */
+typedef struct {                                                                                              /* U/ZDICT_cover_params_t.cs */
+    unsigned k; unsigned d; unsigned steps; unsigned nbThreads; double splitPoint;
+    unsigned shrinkDict; unsigned shrinkDictMaxRegression; ZDICT_params_t zParams;
+} ZDICT_cover_params_t;
+typedef struct {                                                                                              /* U/ZDICT_fastCover_params_t.cs */
+    unsigned k; unsigned d; unsigned f; unsigned steps; unsigned nbThreads; double splitPoint;
+    unsigned accel; unsigned shrinkDict; unsigned shrinkDictMaxRegression; ZDICT_params_t zParams;
+} ZDICT_fastCover_params_t;
+/* U/Zdict.cs:591-600: ZDICT_optimizeTrainFromBuffer_fastCover with d = 8, steps = 4 (k in {50, 537, 1024, 1511, 1998}), f = 20,
+ * accel = 1, compressionLevel 3 */
+size_t ZDICT_trainFromBuffer(void* dictBuffer, size_t dictBufferCapacity, const void* samplesBuffer, const size_t* samplesSizes,
+                             unsigned nbSamples);
+/* U/Fastcover.cs:449-505: one (k, d); splitPoint is forced to 1.0 */
+size_t ZDICT_trainFromBuffer_fastCover(void* dictBuffer, size_t dictBufferCapacity, const void* samplesBuffer, const size_t* samplesSizes,
+                                       unsigned nbSamples, ZDICT_fastCover_params_t parameters);
+/* U/Fastcover.cs:525-715: every candidate k (and d = 6 and 8 when d = 0) side by side, the smallest total compressed size of the test
+ * samples wins (the first k of equal totals); *parameters receives the chosen ones */
+size_t ZDICT_optimizeTrainFromBuffer_fastCover(void* dictBuffer, size_t dictBufferCapacity, const void* samplesBuffer,
+                                               const size_t* samplesSizes, unsigned nbSamples, ZDICT_fastCover_params_t* parameters);
+/* U/Zdict.cs:458-533: header + entropy tables + content (truncated at its end to fit, padded when under 8 bytes) */
+size_t ZDICT_finalizeDictionary(void* dstDictBuffer, size_t maxDictSize, const void* dictContent, size_t dictContentSize,
+                                const void* samplesBuffer, const size_t* samplesSizes, unsigned nbSamples, ZDICT_params_t parameters);
 unsigned    ZSTD_versionNumber(void);        /* 10501, as U/ZstdCommon.cs:11-21 */
 const char* ZSTD_versionString(void);
 
@@ -201,6 +234,9 @@ size_t ZSTDMI_debugEntropyBlock(ZSTD_CCtx* cctx, void* dst, size_t dstCapacity, 
 /* the entropy stage of ONE chunk whose ChunkMeta is taken as given, WITHOUT the host's range checks, over a seqStore filled with the
  * byte `fill`: what a faulty match finder would hand over.  The kernels must bound every size themselves (meta_checked, the
  * bitstream room): returns the bytes the chunk's frame would take, never faults.  tests/test_gpu_boundary.py */
+/* the dictionary trainer's batch: n samples (concatenated in src, host memory) each compressed as ZSTD_compress2 would compress it
+ * alone with the context's parameters and dictionary, in one pass through the pipeline; outSizes[i] = sample i's compressed size */
+size_t ZSTDMI_debugCompressSamples(ZSTD_CCtx* cctx, const void* src, const size_t* sizes, size_t n, size_t* outSizes);
 size_t ZSTDMI_debugPoisonedChunk(ZSTD_CCtx* cctx, unsigned nbSeq, unsigned litSize, unsigned srcSize, unsigned fill);
 
 #ifdef __cplusplus

@@ -7,7 +7,8 @@ error behaviour, over the C ABI in include/zstd_mi355x.h.
 from .errors import ZstdException, ZSTD_ErrorCode
 from .compressor import Compressor
 from .decompressor import Decompressor
+from .dictbuilder import DictBuilder
 from . import _ffi
 from .streams import CompressionStream, DecompressionStream, EndOfStreamException
 
-__all__ = ["Compressor", "Decompressor", "CompressionStream", "DecompressionStream", "EndOfStreamException", "ZstdException", "ZSTD_ErrorCode", "_ffi"]
+__all__ = ["Compressor", "Decompressor", "DictBuilder", "CompressionStream", "DecompressionStream", "EndOfStreamException", "ZstdException", "ZSTD_ErrorCode", "_ffi"]

@@ -12,6 +12,21 @@ LIB_PATH = os.path.join(_HERE, "libzstd_mi355x.so")
 c_size_t, c_void_p, c_int, c_uint, c_ull = ctypes.c_size_t, ctypes.c_void_p, ctypes.c_int, ctypes.c_uint, ctypes.c_ulonglong
 
 
+class ZDICT_params_t(ctypes.Structure):
+    _fields_ = [("compressionLevel", c_int), ("notificationLevel", c_uint), ("dictID", c_uint)]
+
+
+class ZDICT_fastCover_params_t(ctypes.Structure):
+    _fields_ = [("k", c_uint), ("d", c_uint), ("f", c_uint), ("steps", c_uint), ("nbThreads", c_uint),
+                ("splitPoint", ctypes.c_double), ("accel", c_uint), ("shrinkDict", c_uint),
+                ("shrinkDictMaxRegression", c_uint), ("zParams", ZDICT_params_t)]
+
+
+class ZDICT_cover_params_t(ctypes.Structure):
+    _fields_ = [("k", c_uint), ("d", c_uint), ("steps", c_uint), ("nbThreads", c_uint), ("splitPoint", ctypes.c_double),
+                ("shrinkDict", c_uint), ("shrinkDictMaxRegression", c_uint), ("zParams", ZDICT_params_t)]
+
+
 class ZSTDMI_Seq(ctypes.Structure):
     _fields_ = [("offBase", ctypes.c_uint32), ("litLength", ctypes.c_uint16), ("mlBase", ctypes.c_uint16)]
 
@@ -50,6 +65,13 @@ SIGNATURES = {
     "ZSTD_DStreamOutSize": (c_size_t, []),
     "ZDICT_isError": (c_uint, [c_size_t]),
     "ZDICT_getErrorName": (ctypes.c_char_p, [c_size_t]),
+    "ZDICT_trainFromBuffer": (c_size_t, [c_void_p, c_size_t, c_void_p, ctypes.POINTER(c_size_t), c_uint]),
+    "ZDICT_trainFromBuffer_fastCover": (c_size_t, [c_void_p, c_size_t, c_void_p, ctypes.POINTER(c_size_t), c_uint,
+                                                   ZDICT_fastCover_params_t]),
+    "ZDICT_optimizeTrainFromBuffer_fastCover": (c_size_t, [c_void_p, c_size_t, c_void_p, ctypes.POINTER(c_size_t), c_uint,
+                                                           ctypes.POINTER(ZDICT_fastCover_params_t)]),
+    "ZDICT_finalizeDictionary": (c_size_t, [c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, ctypes.POINTER(c_size_t), c_uint,
+                                            ZDICT_params_t]),
     "ZSTDMI_deviceCount": (c_int, []),
     "ZSTDMI_CCtx_setDevice": (c_size_t, [c_void_p, c_int]),
     "ZSTDMI_DCtx_setDevice": (c_size_t, [c_void_p, c_int]),
@@ -73,6 +95,7 @@ SIGNATURES = {
     "ZSTDMI_DCtx_getStageTimes": (c_int, [c_void_p, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_char_p), c_int]),
     "ZSTDMI_debugGetChunk": (c_size_t, [c_void_p, c_size_t, ctypes.POINTER(ZSTDMI_Seq), c_size_t, ctypes.POINTER(c_size_t),
                                         c_void_p, c_size_t, ctypes.POINTER(c_size_t)]),
+    "ZSTDMI_debugCompressSamples": (c_size_t, [c_void_p, c_void_p, ctypes.POINTER(c_size_t), c_size_t, ctypes.POINTER(c_size_t)]),
     "ZSTDMI_debugPoisonedChunk": (c_size_t, [c_void_p, c_uint, c_uint, c_uint, c_uint]),
     "ZSTDMI_debugEntropyBlock": (c_size_t, [c_void_p, c_void_p, c_size_t, ctypes.POINTER(ZSTDMI_Seq), c_size_t,
                                             c_void_p, c_size_t, c_size_t]),

@@ -789,4 +789,87 @@ void launch_huf_encode(const u8* lits, const ChunkMeta* meta, const HufTable* ta
     hipLaunchKernelGGL(huf_encode_kernel, dim3(nChunks), dim3(256), 0, stream, lits, meta, tables, slots, dst, offsets, dstCapacity, src, chunkBytes);
 }
 
+// ---- the entropy tables of a trained dictionary (ZDICT_analyzeEntropy, U/Zdict.cs:174-408), one wave ----
+// In: the statistics (every count >= 1): [0, 256) literals, [256, 292) LL codes, [292, 345) ML codes, [345, 345 + offcodeMax]
+// offset codes.  Out: Huffman table description (maxNbBits 11, the ZDICT_flatLit retry when the build returns 8), the offset /
+// match-length / literal-length FSE descriptions (logs 8 / 9 / 9, low-probability counts, the offset one written with
+// maxSymbolValue 30), and the repcodes {1, 4, 8}.  *outSize = bytes written,
+// 0 when the literal table cannot be described (HUF_writeCTable fails), 0xFFFFFFFF when the tables exceed `cap`.
+__global__ __launch_bounds__(64) void dict_entropy_kernel(const u32* __restrict__ stats, u32 offcodeMax, u8* __restrict__ out, u32 cap,
+                                                          u32* __restrict__ outSize)
+{
+    __shared__ HufTreeLds L;
+    __shared__ u32 cnt[256];
+    __shared__ u8 hdr[512];
+    const u32 lane = threadIdx.x;
+    for (u32 k = 0; k < 4; ++k) cnt[k * 64 + lane] = stats[k * 64 + lane];
+    wave_lds_sync();
+    u32 huffLog = 0, ws = 0;
+    for (u32 attempt = 0; attempt < 2; ++attempt) {
+        if (lane == 0) {                                    // HUF_sort: counts in descending order (ties in symbol order)
+            Node z; z.count = 0; z.parent = 0; z.byte = 0; z.nbBits = 0;
+            for (u32 i = 0; i < 513; i++) L.nodes[i] = z;
+            for (u32 s = 0; s < 256; s++) {
+                Node nd; nd.count = cnt[s]; nd.parent = 0; nd.byte = (u8)s; nd.nbBits = 0;
+                int j = (int)s;
+                while (j > 0 && L.nodes[j].count < nd.count) { L.nodes[j + 1] = L.nodes[j]; j--; }
+                L.nodes[j + 1] = nd;
+            }
+        }
+        if (lane < 13) L.wcount[lane] = 0;
+        wave_lds_sync();
+        Node* huffNode = L.nodes + 1;
+        if (lane == 0) { int root = 0; L.sh[kShNonNull] = (u32)huf_build_tree(huffNode, 255, &root); L.sh[kShRoot] = (u32)root; }
+        wave_lds_sync();
+        const u32 nonNull = L.sh[kShNonNull], root = L.sh[kShRoot];
+        for (u32 k = 0; k < 4; ++k) {
+            const u32 pos = k * 64 + lane;
+            if (pos <= nonNull) { u32 node = pos, d = 0; while (node != root) { node = huffNode[node].parent; d++; } huffNode[pos].nbBits = (u8)d; }
+        }
+        wave_lds_sync();
+        const u32 hl = uniform(huf_set_max_height_wave(L, huffNode, nonNull, 11));
+        wave_lds_sync();
+        if (hl == 8 && attempt == 0) {                      // ZDICT_flatLit: a flat distribution HUF_writeCTable can describe
+            for (u32 k = 0; k < 4; ++k) { const u32 s = k * 64 + lane; cnt[s] = s == 0 ? 4u : (s == 253 || s == 254) ? 1u : 2u; }
+            wave_lds_sync();
+            continue;
+        }
+        for (u32 k = 0; k < 4; ++k) { const u32 pos = k * 64 + lane; L.nbBits[huffNode[pos].byte] = huffNode[pos].nbBits; }
+        wave_lds_sync();
+        for (u32 k = 0; k < 4; ++k) {
+            const u32 s = k * 64 + lane;
+            if (s < 255) { const u32 nb = L.nbBits[s]; const u32 wt = nb ? hl + 1 - nb : 0; L.weights[s] = (u8)wt; atomicAdd(&L.wcount[wt], 1u); }
+        }
+        wave_lds_sync();
+        ws = huf_compress_weights_wave(L, hdr + 1, 255, lane);
+        huffLog = hl;
+        break;
+    }
+    if (lane != 0) return;
+    if (!huffLog || !(ws > 1 && ws < 255 / 2)) { *outSize = 0; return; }
+    hdr[0] = (u8)ws;
+    u32 pos = ws + 1;
+    u32 count[53]; s16 norm[53]; u32 total = 0;
+    // offset codes 0..offcodeMax, written up to maxSymbolValue 30
+    for (u32 s = 0; s < 53; s++) { count[s] = s <= offcodeMax ? stats[345 + s] : 0u; norm[s] = 0; total += count[s]; }
+    fse_normalize_count(norm, 8, count, total, offcodeMax, 1);
+    pos += fse_write_ncount(hdr + pos, norm, 30, 8);
+    total = 0; for (u32 s = 0; s < 53; s++) { count[s] = stats[292 + s]; total += count[s]; }
+    fse_normalize_count(norm, 9, count, total, 52, 1);
+    pos += fse_write_ncount(hdr + pos, norm, 52, 9);
+    total = 0; for (u32 s = 0; s < 36; s++) { count[s] = stats[256 + s]; total += count[s]; }
+    fse_normalize_count(norm, 9, count, total, 35, 1);
+    pos += fse_write_ncount(hdr + pos, norm, 35, 9);
+    if (pos + 12 > cap) { *outSize = 0xFFFFFFFFu; return; }
+    writeLE32(hdr + pos, 1); writeLE32(hdr + pos + 4, 4); writeLE32(hdr + pos + 8, 8);
+    pos += 12;
+    for (u32 i = 0; i < pos; i++) out[i] = hdr[i];
+    *outSize = pos;
+}
+
+void launch_dict_entropy(const u32* stats, u32 offcodeMax, u8* out, u32 cap, u32* outSize, hipStream_t stream)
+{
+    hipLaunchKernelGGL(dict_entropy_kernel, dim3(1), dim3(64), 0, stream, stats, offcodeMax, out, cap, outSize);
+}
+
 } // namespace zmi

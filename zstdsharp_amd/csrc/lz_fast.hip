@@ -801,7 +801,7 @@ __global__ __launch_bounds__(1024) void lz_kernel(const u8* __restrict__ src, u6
                                                   ChunkMeta* __restrict__ meta,
                                                   const u8* __restrict__ prefixArg, const u32 prefixLenArg, const u32 chunkBytes,
                                                   const u32 fhExtra, const u32 minStrideLog, const u32 frameBlocksArg, u16* __restrict__ candAll, u16* __restrict__ chainAll, u32* __restrict__ regionList, const u32 nChunks,
-                                                  u32* __restrict__ claimCtr)
+                                                  u32* __restrict__ claimCtr, const u32* __restrict__ chunkLens)
 {
     extern __shared__ __attribute__((aligned(16))) u8 ldsRaw[];
     LzLds& L = *reinterpret_cast<LzLds*>(ldsRaw);
@@ -841,7 +841,9 @@ __global__ __launch_bounds__(1024) void lz_kernel(const u8* __restrict__ src, u6
     if (DICT && frameBlocks && !indep) { const u64 back = (u64)bf * cb; prefixLen = back < hist ? (u32)back : hist; prefix = in - prefixLen; }
     if (DICT && indep && bf) prefixLen = 0;
     const u32 lowLimit = DICT ? hist - prefixLen : 0u;
-    const u32 nData = (u32)((srcSize - base) < cb ? (srcSize - base) : cb);
+    // chunkLens (optional, dictionary instantiations): chunk c holds chunkLens[c] <= cb bytes at c * cb (a batch of independent
+    // inputs, each staged at a chunk boundary: the trainer's per-sample compression); null = the call's input cut every cb bytes
+    const u32 nData = (DICT && chunkLens) ? chunkLens[c] : (u32)((srcSize - base) < cb ? (srcSize - base) : cb);
     const u32 n = hist + nData;                            // end of the data in LDS
 #ifdef ZMI_LZ_STAMPS
     unsigned long long stampAcc[14] = {0,0,0,0,0,0,0,0,0,0,0,0,0,0}; unsigned long long stampLast = __builtin_amdgcn_s_memtime();
@@ -1525,7 +1527,8 @@ __global__ __launch_bounds__(1024) void lz_kernel(const u8* __restrict__ src, u6
 template <int MODE, bool DICT>
 __global__ __launch_bounds__(1024) void lz_region_kernel(const u8* __restrict__ src, u64 srcSize, Seq* __restrict__ seqs, u8* __restrict__ lits,
                                                          ChunkMeta* __restrict__ meta, u16* __restrict__ candAll, u16* __restrict__ chainAll, const u32* __restrict__ regionList,
-                                                         const u8* __restrict__ prefixArg, const u32 prefixLenArg, const u32 chunkBytes, const u32 frameBlocksArg, const u32 hcDepth)
+                                                         const u8* __restrict__ prefixArg, const u32 prefixLenArg, const u32 chunkBytes, const u32 frameBlocksArg, const u32 hcDepth,
+                                                         const u32* __restrict__ chunkLens)
 {
     const u32 frameBlocks = frameBlocksArg & 0x7FFFFFFFu;
     const bool indep = (frameBlocksArg >> 31) != 0;
@@ -1547,7 +1550,7 @@ __global__ __launch_bounds__(1024) void lz_region_kernel(const u8* __restrict__ 
     if (DICT && frameBlocks && !indep) { const u64 back = (u64)bf * cb; prefixLen = back < hist ? (u32)back : hist; prefix = in - prefixLen; }
     if (DICT && indep && bf) prefixLen = 0;
     const u32 lowLimit = DICT ? hist - prefixLen : 0u;
-    const u32 nData = (u32)((srcSize - base) < cb ? (srcSize - base) : cb);
+    const u32 nData = (DICT && chunkLens) ? chunkLens[c] : (u32)((srcSize - base) < cb ? (srcSize - base) : cb);
     const u32 n = hist + nData;
     {   // the image [lowLimit, n): history (or dictionary tail) + block.  Cross-chunk history is one contiguous piece of the input
         const bool onePiece = !DICT || (frameBlocks != 0 && !indep);
@@ -1676,7 +1679,8 @@ extern "C" void ZSTDMI_debugReadLzStamps(unsigned long long* out16, int reset)
 
 template <int MODE, int SHORT, bool DICT, bool FAR = false>
 static void launch_one(const u8* src, u64 srcSize, u32 nChunks, Seq* seqs, u8* lits, ChunkMeta* meta, const u8* prefix, u32 prefixLen,
-                       u32 chunkBytes, u32 fhExtra, u32 minStrideLog, u32 frameBlocks, u16* cand, u16* chain, u32* regionList, u32 hcDepth, hipStream_t stream, StageHook hook, u32* claimCtr)
+                       u32 chunkBytes, u32 fhExtra, u32 minStrideLog, u32 frameBlocks, u16* cand, u16* chain, u32* regionList, u32 hcDepth, hipStream_t stream, StageHook hook, u32* claimCtr,
+                       const u32* chunkLens)
 {
     // the region parse of dense chunks: a second kernel behind a work list (see lz_region_kernel), inlined for the others
     constexpr bool kSplit = (MODE == 0 && !DICT && !FAR) || MODE == 2;
@@ -1697,11 +1701,11 @@ static void launch_one(const u8* src, u64 srcSize, u32 nChunks, Seq* seqs, u8* l
     if (claim) (void)hipMemsetAsync(claimCtr, 0, sizeof(u32), stream);
     const u32 grid = claim ? cuCount[dev & 63] : nChunks;
     hipLaunchKernelGGL((lz_kernel<MODE, SHORT, DICT, FAR>), dim3(grid), dim3(kTile), sizeof(LzLds), stream, src, srcSize, seqs, lits, meta, prefix, prefixLen, chunkBytes, fhExtra, minStrideLog, frameBlocks, cand, cand ? chain : nullptr, cand ? regionList : nullptr, nChunks,
-                       claim ? claimCtr : nullptr);
+                       claim ? claimCtr : nullptr, chunkLens);
     hook("lz_fast");
     if constexpr (kSplit) if (cand) {                      // the dense chunks' rest: 256 workgroups (one per CU) walk the list
         hipLaunchKernelGGL((lz_region_kernel<MODE, DICT>), dim3(nChunks < 256 ? nChunks : 256), dim3(kTile), sizeof(LzLds), stream, src, srcSize, seqs, lits, meta, cand, chain, regionList,
-                           prefix, prefixLen, chunkBytes, frameBlocks, hcDepth);
+                           prefix, prefixLen, chunkBytes, frameBlocks, hcDepth, chunkLens);
         hook("lz_region");
     }
 }
@@ -1714,24 +1718,25 @@ static void launch_one(const u8* src, u64 srcSize, u32 nChunks, Seq* seqs, u8* l
 // frames of chunkBytes each (ZSTD_c_windowLog 10 .. 15: a frame is its own window), on the same instantiation with an empty history.
 // cand / regionList (null: off): workspace of the region parse, 65536 u16 per chunk and 1 + nChunks u32.
 void launch_lz(u32 finder, const u8* src, u64 srcSize, u32 nChunks, Seq* seqs, u8* lits, ChunkMeta* meta, const u8* prefix, u32 prefixLen,
-               u32 chunkBytes, u32 fhExtra, u32 minStrideLog, u32 frameBlocks, u16* cand, u16* chain, u32* regionList, u32 hcDepth, hipStream_t stream, StageHook hook, u32* claimCtr)
+               u32 chunkBytes, u32 fhExtra, u32 minStrideLog, u32 frameBlocks, u16* cand, u16* chain, u32* regionList, u32 hcDepth, hipStream_t stream, StageHook hook, u32* claimCtr,
+               const u32* chunkLens)
 {
     if (chunkBytes >= kChunkSize && frameBlocks && finder == 0) {       // fast strategy with cross-chunk history: full 64 KiB blocks, far candidates
-        launch_one<0, 5, false, true>(src, srcSize, nChunks, seqs, lits, meta, nullptr, 0, kChunkSize, fhExtra, minStrideLog, frameBlocks, nullptr, nullptr, nullptr, 0, stream, hook, claimCtr);
+        launch_one<0, 5, false, true>(src, srcSize, nChunks, seqs, lits, meta, nullptr, 0, kChunkSize, fhExtra, minStrideLog, frameBlocks, nullptr, nullptr, nullptr, 0, stream, hook, claimCtr, nullptr);
         return;
     }
     if (chunkBytes >= kChunkSize) {
         switch (finder) {
-        case 0:  launch_one<0, 5, false>(src, srcSize, nChunks, seqs, lits, meta, nullptr, 0, kChunkSize, fhExtra, minStrideLog, 0, cand, chain, regionList, hcDepth, stream, hook, claimCtr); break;
-        case 1:  launch_one<1, 5, false>(src, srcSize, nChunks, seqs, lits, meta, nullptr, 0, kChunkSize, fhExtra, minStrideLog, 0, cand, chain, regionList, hcDepth, stream, hook, claimCtr); break;
-        default: launch_one<2, 5, false>(src, srcSize, nChunks, seqs, lits, meta, nullptr, 0, kChunkSize, fhExtra, minStrideLog, 0, cand, chain, regionList, hcDepth, stream, hook, claimCtr); break;
+        case 0:  launch_one<0, 5, false>(src, srcSize, nChunks, seqs, lits, meta, nullptr, 0, kChunkSize, fhExtra, minStrideLog, 0, cand, chain, regionList, hcDepth, stream, hook, claimCtr, chunkLens); break;
+        case 1:  launch_one<1, 5, false>(src, srcSize, nChunks, seqs, lits, meta, nullptr, 0, kChunkSize, fhExtra, minStrideLog, 0, cand, chain, regionList, hcDepth, stream, hook, claimCtr, chunkLens); break;
+        default: launch_one<2, 5, false>(src, srcSize, nChunks, seqs, lits, meta, nullptr, 0, kChunkSize, fhExtra, minStrideLog, 0, cand, chain, regionList, hcDepth, stream, hook, claimCtr, chunkLens); break;
         }
         return;
     }
     switch (finder) {
-    case 0:  launch_one<0, 5, true>(src, srcSize, nChunks, seqs, lits, meta, prefix, prefixLen, chunkBytes, fhExtra, minStrideLog, frameBlocks, cand, chain, regionList, hcDepth, stream, hook, claimCtr); break;
-    case 1:  launch_one<1, 5, true>(src, srcSize, nChunks, seqs, lits, meta, prefix, prefixLen, chunkBytes, fhExtra, minStrideLog, frameBlocks, cand, chain, regionList, hcDepth, stream, hook, claimCtr); break;
-    default: launch_one<2, 5, true>(src, srcSize, nChunks, seqs, lits, meta, prefix, prefixLen, chunkBytes, fhExtra, minStrideLog, frameBlocks, cand, chain, regionList, hcDepth, stream, hook, claimCtr); break;
+    case 0:  launch_one<0, 5, true>(src, srcSize, nChunks, seqs, lits, meta, prefix, prefixLen, chunkBytes, fhExtra, minStrideLog, frameBlocks, cand, chain, regionList, hcDepth, stream, hook, claimCtr, chunkLens); break;
+    case 1:  launch_one<1, 5, true>(src, srcSize, nChunks, seqs, lits, meta, prefix, prefixLen, chunkBytes, fhExtra, minStrideLog, frameBlocks, cand, chain, regionList, hcDepth, stream, hook, claimCtr, chunkLens); break;
+    default: launch_one<2, 5, true>(src, srcSize, nChunks, seqs, lits, meta, prefix, prefixLen, chunkBytes, fhExtra, minStrideLog, frameBlocks, cand, chain, regionList, hcDepth, stream, hook, claimCtr, chunkLens); break;
     }
 }
 

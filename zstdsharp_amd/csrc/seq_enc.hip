@@ -425,4 +425,48 @@ extern "C" void ZSTDMI_debugReadSeqEncStamps(unsigned long long* out16, int rese
 }
 #endif
 
+// ---- statistics of compressed blocks (ZDICT_countEStats, U/Zdict.cs:21-120): one workgroup per chunk ----
+// stats: [0, 256) literal bytes, [256, 292) LL codes, [292, 345) ML codes, [345, 377) offset codes.  Only chunks whose block came out
+// compressed count (the reference's cSize != 0 rule); the sequences are read after seq_encode, as the block codes them.
+__global__ __launch_bounds__(256) void seq_stats_kernel(const Seq* __restrict__ seqs, const u8* __restrict__ lits, const ChunkMeta* __restrict__ meta,
+                                                        u32 nChunks, const u8* __restrict__ src, u32 chunkBytes, u32* __restrict__ stats)
+{
+    __shared__ u32 h[377];
+    const u32 c = blockIdx.x, tid = threadIdx.x;
+    const ChunkMeta m = meta_checked(meta[c]);
+    if (m.blockType != 2) return;
+    for (u32 i = tid; i < 377; i += 256) h[i] = 0;
+    __syncthreads();
+    const u8* __restrict__ lit = m.litFromSrc ? src + (u64)c * chunkBytes : lits + (u64)c * kLitStride;
+    for (u32 i = tid; i < m.litSize; i += 256) atomicAdd(&h[lit[i]], 1u);
+    const Seq* __restrict__ sq = seqs + (u64)c * kMaxSeq;
+    for (u32 i = tid; i < m.nbSeq; i += 256) {
+        const Seq q = sq[i];
+        atomicAdd(&h[256 + ll_code(q.litLength)], 1u);
+        atomicAdd(&h[292 + ml_code(q.mlBase)], 1u);
+        atomicAdd(&h[345 + highbit32(q.offBase)], 1u);
+    }
+    __syncthreads();
+    for (u32 i = tid; i < 377; i += 256) if (h[i]) atomicAdd(&stats[i], h[i]);
+}
+
+// the inputs of a batch of independent samples, each at its own chunk boundary: chunk c = bytes [from[c], from[c] + len[c]) of src
+__global__ __launch_bounds__(256) void sample_scatter_kernel(const u8* __restrict__ src, const u64* __restrict__ from, const u32* __restrict__ len,
+                                                             u8* __restrict__ stage, u32 chunkBytes)
+{
+    const u32 c = blockIdx.x;
+    const u8* __restrict__ in = src + from[c];
+    u8* __restrict__ out = stage + (u64)c * chunkBytes;
+    for (u32 i = threadIdx.x; i < len[c]; i += 256) out[i] = in[i];
+}
+
+void launch_seq_stats(const Seq* seqs, const u8* lits, const ChunkMeta* meta, u32 nChunks, const u8* src, u32 chunkBytes, u32* stats, hipStream_t stream)
+{
+    hipLaunchKernelGGL(seq_stats_kernel, dim3(nChunks), dim3(256), 0, stream, seqs, lits, meta, nChunks, src, chunkBytes, stats);
+}
+void launch_sample_scatter(const u8* src, const u64* from, const u32* len, u8* stage, u32 nChunks, u32 chunkBytes, hipStream_t stream)
+{
+    hipLaunchKernelGGL(sample_scatter_kernel, dim3(nChunks), dim3(256), 0, stream, src, from, len, stage, chunkBytes);
+}
+
 } // namespace zmi

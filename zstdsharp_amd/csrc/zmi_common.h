@@ -168,7 +168,7 @@ constexpr u32 kLdmMinHashRateLog = 5;      // the split workspace keeps at most 
 enum : u32 {
     kErrGeneric = 1, kErrPrefixUnknown = 10, kErrVersionUnsupported = 12, kErrFrameParameterUnsupported = 14,
     kErrWindowTooLarge = 16, kErrCorruption = 20, kErrChecksumWrong = 22, kErrDictionaryCorrupted = 30,
-    kErrDictionaryWrong = 32, kErrParameterUnsupported = 40, kErrParameterOutOfBound = 42,
+    kErrDictionaryWrong = 32, kErrDictionaryCreationFailed = 34, kErrParameterUnsupported = 40, kErrParameterOutOfBound = 42,
     kErrTableLogTooLarge = 44, kErrMaxSymbolValueTooLarge = 46, kErrMaxSymbolValueTooSmall = 48,
     kErrStageWrong = 60, kErrInitMissing = 62, kErrMemoryAllocation = 64, kErrWorkSpaceTooSmall = 66,
     kErrDstSizeTooSmall = 70, kErrSrcSizeWrong = 72, kErrDstBufferNull = 74, kErrMaxCode = 120

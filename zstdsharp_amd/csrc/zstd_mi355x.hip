@@ -19,7 +19,8 @@
 namespace zmi {
 // kernels (lz_fast.hip, huf_enc.hip, seq_enc.hip, frame.hip, decode.hip)
 void launch_lz(u32 finder, const u8* src, u64 srcSize, u32 nChunks, Seq* seqs, u8* lits, ChunkMeta* meta, const u8* prefix, u32 prefixLen,
-               u32 chunkBytes, u32 fhExtra, u32 minStrideLog, u32 frameBlocks, u16* cand, u16* chain, u32* regionList, u32 hcDepth, hipStream_t stream, StageHook hook, u32* claimCtr);
+               u32 chunkBytes, u32 fhExtra, u32 minStrideLog, u32 frameBlocks, u16* cand, u16* chain, u32* regionList, u32 hcDepth, hipStream_t stream, StageHook hook, u32* claimCtr,
+               const u32* chunkLens = nullptr);
 void launch_lz_probe(const u8* src, u64 srcSize, u64 front, u64 groupBytes, u32 nGroups, u32 tilesPerGroup, u32* out, hipStream_t stream);
 void launch_huf_build(const u8* lits, ChunkMeta* meta, HufTable* tables, u8* slots, u32 nChunks, u32 rawLiterals, const u8* src, u32 chunkBytes,
                       hipStream_t stream, StageHook hook);
@@ -44,6 +45,8 @@ void launch_frame_walk_count(const u8* src, u64 srcSize, u32 maxFrames, u32* sta
 void launch_frame_walk_emit(const u8* src, u64 srcSize, FrameDesc* frames, BlockDesc* blocks, u8* walkWs, hipStream_t stream);
 void launch_frame_walk_serial(const u8* src, u64 srcSize, FrameDesc* frames, BlockDesc* blocks, u32 maxFrames, u32* status, u32 dictID, u32 emit,
                               hipStream_t stream);
+void launch_seq_stats(const Seq* seqs, const u8* lits, const ChunkMeta* meta, u32 nChunks, const u8* src, u32 chunkBytes, u32* stats, hipStream_t stream);
+void launch_sample_scatter(const u8* src, const u64* from, const u32* len, u8* stage, u32 nChunks, u32 chunkBytes, hipStream_t stream);
 void launch_dict_parse(const u8* dict, u32 dictSize, DictInfo* out, hipStream_t stream);
 void launch_block_prepass(const u8* src, FrameDesc* frames, BlockDesc* blocks, u32 nFrames, u32 nBlocks, u32 haveDict, u32 earlyLiterals, u32* status, hipStream_t stream);
 void launch_seq_decode(const u8* src, const FrameDesc* frames, BlockDesc* blocks, u32 nBlocks, SeqRec* recs, u32* status,
@@ -1718,3 +1721,107 @@ unsigned long long ZSTD_getFrameContentSize(const void* src, size_t srcSize)
 }
 
 } // extern "C"
+
+// ---- a batch of independent samples, each compressed as ZSTD_compress2 would compress it alone against the loaded dictionary ----
+// (the dictionary trainer's inner loop, dict_train.hip).  Samples of one framing class (same dictionary prefix, chunk size and
+// resolved parameters) go through the pipeline together: each chunk of a sample is staged at its own chunk boundary and the finder
+// takes its length from a per-chunk table (launch_lz's chunkLens); the sizes come from the chunks' ChunkMeta, nothing is gathered.
+// A sample the class model does not cover (empty, no dictionary prefix, multi-block frames, LDM, checksums) is compressed alone.
+// outSizes[i] = the compressed size of sample i (or its error).  stats (optional, host, 377 u32): literal / LL / ML / offset code
+// counts of the compressed blocks are added to it (seq_stats_kernel).
+namespace zmi {
+size_t compress_samples(ZSTD_CCtx* c, const u8* src, const u64* offs, const size_t* sizes, size_t n, size_t* outSizes, u32* stats)
+{
+    size_t e = cctx_bind(c); if (isErr(e)) return e;
+    const CallParams cp = sticky_params(c);
+    e = cctx_sync_dictionary(c); if (isErr(e)) return e;
+    hipStream_t s = c->stream;
+    struct Group { Framing fr; std::vector<size_t> members; };
+    std::vector<Group> groups;
+    std::vector<u8> tmp;
+    u64 maxEnd = 0;
+    for (size_t i = 0; i < n; i++) {
+        const size_t S = sizes[i];
+        const Framing fr = S ? resolve_framing(c, cp, S) : Framing{};
+        if (!S || !fr.prefixLen || fr.frameBlocks || fr.indepWindowLog || fr.ldm || cp.checksumFlag || c->workers.size() > 1) {
+            tmp.resize(ZSTD_compressBound(S));
+            outSizes[i] = compress_any(c, cp, tmp.data(), tmp.size(), src + offs[i], S);
+            continue;
+        }
+        outSizes[i] = 0;
+        maxEnd = offs[i] + S > maxEnd ? offs[i] + S : maxEnd;
+        Group* g = nullptr;
+        for (auto& x : groups)
+            if (x.fr.prefixLen == fr.prefixLen && x.fr.chunkBytes == fr.chunkBytes && !memcmp(&x.fr.rs, &fr.rs, sizeof(Resolved))) { g = &x; break; }
+        if (!g) { groups.push_back(Group{fr, {}}); g = &groups.back(); }
+        g->members.push_back(i);
+    }
+    if (groups.empty()) return 0;
+    DevBuf dSrc, dStage, dFrom, dLen, dStats;
+    if (!dSrc.ensure(maxEnd + 16) || !dStats.ensure(377 * 4)) return ZERR(kErrMemoryAllocation);
+    bool ok = hipMemcpyAsync(dSrc.p, src, maxEnd, hipMemcpyHostToDevice, s) == hipSuccess && hipMemsetAsync(dStats.p, 0, 377 * 4, s) == hipSuccess;
+    const bool fmtDict = c->dictFormatted;
+    const u32 dictID = fmtDict ? c->info.dictID : 0u;
+    const u32 dictIdBytes = (dictID && cp.dictIDFlag) ? (dictID < 256 ? 1u : dictID < 65536 ? 2u : 4u) : 0u;
+    const u32 plainReps[3] = { 1, 4, 8 };
+    const u32* const initReps = fmtDict ? c->info.rep : plainReps;
+    for (const Group& g : groups) {
+        if (!ok) break;
+        const u32 cb = g.fr.chunkBytes, prefixLen = g.fr.prefixLen;
+        const Resolved rs = g.fr.rs;
+        const u8* prefix = (const u8*)c->dict.p + (c->dictHost.size() - prefixLen);
+        std::vector<u64> from; std::vector<u32> len; std::vector<size_t> owner;
+        for (size_t i : g.members)
+            for (u64 o = 0; o < sizes[i]; o += cb) { from.push_back(offs[i] + o); len.push_back((u32)(sizes[i] - o < cb ? sizes[i] - o : cb)); owner.push_back(i); }
+        const u32 pass = c->passChunks < 16384 ? c->passChunks : 16384;
+        const bool regionParse = rs.minStrideLog == 0 && c->parser == 0;
+        const bool hcChains = regionParse && rs.finder >= 2;
+        u32 hcDepth = rs.cp.searchLog < 2 ? 4u : rs.cp.searchLog > 5 ? 32u : 1u << rs.cp.searchLog;
+        if (hcDepth > 8 && rs.cp.strategy <= 4 && cp.searchLog == 0) hcDepth = 8;
+        const u32 strategy = rs.cp.strategy < kStratGreedy ? rs.cp.strategy : (u32)kStratGreedy;
+        std::vector<ChunkMeta> hm;
+        for (size_t c0 = 0; c0 < from.size() && ok; c0 += pass) {
+            const u32 nCh = (u32)(from.size() - c0 < pass ? from.size() - c0 : pass);
+            if (!cctx_workspace(c, nCh) || (regionParse && !cctx_cand_workspace(c, nCh, hcChains)) || !dStage.ensure((u64)nCh * cb + 64) ||
+                !dFrom.ensure((u64)nCh * 8) || !dLen.ensure((u64)nCh * 4)) return ZERR(kErrMemoryAllocation);
+            ok = hipMemcpyAsync(dFrom.p, from.data() + c0, (u64)nCh * 8, hipMemcpyHostToDevice, s) == hipSuccess &&
+                 hipMemcpyAsync(dLen.p, len.data() + c0, (u64)nCh * 4, hipMemcpyHostToDevice, s) == hipSuccess;
+            if (!ok) break;
+            const u8* stage = (const u8*)dStage.p;
+            launch_sample_scatter((const u8*)dSrc.p, (const u64*)dFrom.p, (const u32*)dLen.p, (u8*)dStage.p, nCh, cb, s);
+            Seq* seqs = (Seq*)c->seqs.p; u8* lits = (u8*)c->lits.p; ChunkMeta* meta = (ChunkMeta*)c->meta.p;
+            HufTable* tables = (HufTable*)c->tables.p; u8* slots = (u8*)c->slots.p; u64* total = (u64*)c->total.p;
+            const u64 stagedBytes = (u64)nCh * cb;
+            launch_lz(rs.finder, stage, stagedBytes, nCh, seqs, lits, meta, prefix, prefixLen, cb, dictIdBytes | (cp.contentSizeFlag ? 0u : 0x100u), rs.minStrideLog, 0,
+                      regionParse ? (u16*)c->cand.p : nullptr, hcChains ? (u16*)((u8*)c->cand.p + cand_plane_bytes(nCh)) : nullptr,
+                      regionParse ? (u32*)((u8*)c->cand.p + cand_plane_bytes(nCh) * (hcChains ? 2 : 1)) : nullptr, hcDepth, s, StageHook{}, (u32*)(total + 4),
+                      (const u32*)dLen.p);
+            launch_huf_build(lits, meta, tables, slots, nCh, rs.rawLiterals, stage, cb, s, StageHook{});
+            launch_seq_encode(seqs, meta, slots, nCh, strategy, cp.contentSizeFlag ? 0u : 2u, 1, dictID, dictIdBytes, initReps, 0, cb, stagedBytes, s);
+            if (stats) launch_seq_stats(seqs, lits, meta, nCh, stage, cb, (u32*)dStats.p, s);
+            hm.resize(nCh);
+            ok = hipMemcpyAsync(hm.data(), meta, (u64)nCh * sizeof(ChunkMeta), hipMemcpyDeviceToHost, s) == hipSuccess &&
+                 hipStreamSynchronize(s) == hipSuccess;
+            if (!ok) break;
+            for (u32 k = 0; k < nCh; k++) outSizes[owner[c0 + k]] += hm[k].outSize;
+        }
+    }
+    std::vector<u32> h(377);
+    if (ok) ok = hipMemcpyAsync(h.data(), dStats.p, 377 * 4, hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
+    if (!ok) { (void)hipGetLastError(); return ZERR(kErrGeneric); }
+    if (stats) for (u32 i = 0; i < 377; i++) stats[i] += h[i];
+    c->lastChunks = 0;                                  // (ZSTDMI_debugGetChunk: no ordinary call to look at)
+    return 0;
+}
+} // namespace zmi
+
+extern "C" size_t ZSTDMI_debugCompressSamples(ZSTD_CCtx* c, const void* src, const size_t* sizes, size_t n, size_t* outSizes)
+{
+    if (!c || (n && (!sizes || !outSizes))) return ZERR(kErrGeneric);
+    return guarded([&] {
+        std::vector<u64> offs(n);
+        u64 o = 0; for (size_t i = 0; i < n; i++) { offs[i] = o; o += sizes[i]; }
+        if (o && !src) return ZERR(kErrSrcSizeWrong);
+        return compress_samples(c, (const u8*)src, offs.data(), sizes, n, outSizes, nullptr);
+    });
+}
