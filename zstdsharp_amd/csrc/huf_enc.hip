@@ -1,12 +1,16 @@
 // huf_enc.hip — literals section of a block on gfx950.
 //
-//   huf_hist_kernel   : one 256-thread workgroup per chunk.  Four waves build the four per-stream byte histograms in
-//                       LDS (HIST_count, U/Hist.cs:67-166; 16-byte loads, parity-split copies, the hottest byte
-//                       counted by ballot), take the compressible / RLE / raw verdict of HUF_compress_internal
-//                       (U/HufCompress.cs:1360-1543) and run HUF_sort (:520-680: parallel bucket placement, the log2
-//                       buckets quick-sorted on separate lanes exactly as the reference does).  Sorted leaves and
-//                       histograms go to the next kernel through the chunk's output slot.
-//   huf_tree_kernel   : one wave per chunk (5 KiB of LDS, ~28 chunks per CU).  The serial constructions, exactly as
+//   huf_hist_kernel   : the counting phase alone, one wave per stream of a chunk (HIST_count, U/Hist.cs:67-166).  A wave
+//                       owns 16 KiB of LDS: 256 symbols x 64 BYTE counters, one per lane, so no two lanes ever add to
+//                       the same counter — skew costs nothing and nothing is lost; one ds_add_u32 without return per
+//                       input byte.  A byte counter holds 255, so the table is summed (v_sad_u8) into 32-bit
+//                       registers and zeroed again after at most 8 x 16 bytes per lane.  Hands the four per-stream
+//                       histograms and the two sample maxima of HUF_compress_internal's pre-check to the next kernel
+//                       through the chunk's output slot.
+//   huf_tree_kernel   : one wave per chunk (5.4 KiB of LDS, ~29 chunks per CU), four symbols per lane.  First the
+//                       compressible / RLE / raw verdict of HUF_compress_internal (U/HufCompress.cs:1360-1543) and
+//                       HUF_sort (:520-680: parallel bucket placement, the log2 buckets quick-sorted on separate lanes
+//                       exactly as the reference does), then the serial constructions, exactly as
 //                       the reference: HUF_buildTree / HUF_setMaxHeight / HUF_buildCTableFromTree (:377-823), the tree
 //                       description (HUF_writeCTable_wksp + HUF_compressWeights, :40-235) and every raw / RLE /
 //                       compressed decision of ZSTD_compressLiterals (U/ZstdCompressLiterals.cs:86-185).  Because
@@ -35,14 +39,12 @@ struct Node { u32 count; u16 parent; u8 byte; u8 nbBits; };
 
 // hand-off from huf_hist_kernel to huf_tree_kernel, kept in the chunk's output slot (overwritten later by huf_encode)
 struct HufWork {
-    u32 leafCount[256];         // HUF_sort's result: counts in descending order ...
-    u8  leafByte[256];          // ... and their symbols
     u16 hist[4][256];           // per-stream histograms
-    u32 flags[4];               // compressible?, maxSymbolValue, RLE?, RLE byte
+    u32 sampleMax[2];           // largest count of the first / last 4 KiB (written only when the pre-check applies)
 };
 static_assert(sizeof(HufWork) <= kSlotStride, "hand-off fits the slot");
 
-struct HufTreeLds {
+struct alignas(16) HufTreeLds {
     Node nodes[513];
     u8  nbBits[256];
     u8  weights[256];
@@ -50,21 +52,22 @@ struct HufTreeLds {
     u32 valPerRank[13];
     u32 rankLast[14];
     u32 sh[8];
+    u32 sortPad[90];            // makes room for HufSortLds, which otherwise lies over members that are dead while HUF_sort runs
 };
+// HUF_sort's scratch: lives from nodes[258] to the end of HufTreeLds (the node queue, the code lengths and the weight tables
+// are written only after the sort).  The placement keys are dead before the first quicksort pushes.
+struct HufSortLds {
+    union {
+        u32 keys[256];          // huf_get_index(count) << 8 | 255 - symbol (0 above maxSymbolValue)
+        s16 qsStack[26][64];    // one explicit quicksort stack per log2 bucket (buckets are sorted by separate lanes); values -1..256
+    };
+    u16 rankGe[32];             // [t] = symbols whose index is >= 164 + t: bucket 165 + b spans [rankGe[b + 1], rankGe[b])
+};
+constexpr u32 kSortScratchNode = 258;
+static_assert(kSortScratchNode * sizeof(Node) % 16 == 0, "keys are read 16 bytes at a time");
+static_assert(kSortScratchNode * sizeof(Node) + sizeof(HufSortLds) <= sizeof(HufTreeLds), "HUF_sort's scratch fits the tree's storage");
 
-struct HufBuildLds {
-    u32 hist[4][2][256];         // two copies per wave (more copies cost more in residency than they save in same-address atomics: DESIGN 5)
-    u32 sample[2][256];
-    u32 count[256];
-    Node nodes[513];
-    u16 rankBase[192], rankCurr[192];
-    u32 sampleMax[2];
-    u32 redMaxSV[4], redLargest[4];
-    u8  sortIdx[256];
-    s16 qsStack[26][64];        // one explicit quicksort stack per log2 bucket (buckets are sorted by separate lanes); values -1..256
-    u32 sh[8];                  // decisions shared by the workgroup: see enum below
-};
-enum { kShCompressed = 0, kShMaxSV, kShRle, kShRleByte, kShHuffLog, kShNonNull, kShRoot, kShHSize };
+enum { kShHuffLog = 4, kShNonNull, kShRoot, kShHSize };
 
 // ---- HUF_sort (U/HufCompress.cs:520-680): bucket sort by count, quicksort inside the log2 buckets ----
 __device__ __forceinline__ u32 huf_get_index(u32 count) { return count < 165 ? count : highbit32(count) + 158; }
@@ -108,11 +111,10 @@ __device__ inline void huf_quick_sort(Node* a, int low0, int high0, s16* stack)
 }
 
 // the log2 buckets (extents computed by the kernel's parallel placement) are sorted on separate lanes
-__device__ inline void huf_sort_bucket(HufBuildLds& L, u32 b /* 0..25 */)
+__device__ inline void huf_sort_bucket(Node* nodes, HufSortLds& S, u32 b /* 0..25 */)
 {
-    const u32 n = 165 + b;
-    const u32 bucketSize = L.rankCurr[n] - L.rankBase[n], bucketStart = L.rankBase[n];
-    if (bucketSize > 1) huf_quick_sort(L.nodes + 1 + bucketStart, 0, (int)bucketSize - 1, L.qsStack[b]);
+    const u32 bucketStart = S.rankGe[b + 1], bucketSize = S.rankGe[b] - bucketStart;
+    if (bucketSize > 1) huf_quick_sort(nodes + 1 + bucketStart, 0, (int)bucketSize - 1, S.qsStack[b]);
 }
 
 // ---- HUF_buildTree (U/HufCompress.cs:689-738) ----
@@ -317,166 +319,159 @@ __device__ inline u32 huf_compress_weights_wave(HufTreeLds& L, u8* dst, u32 wtSi
 
 __device__ __forceinline__ u32 min_gain(u32 srcSize) { return (srcSize >> 6) + 2; }   // ZSTD_minGain, strategies < btultra
 
-// Front half: everything that is parallel over the literals or over the 256 symbols.  Hands the sorted leaves, the four
-// per-stream histograms and the verdicts to huf_tree_kernel through the chunk's (still unused) output slot.
-__global__ __launch_bounds__(256) void huf_hist_kernel(const u8* __restrict__ lits, const ChunkMeta* __restrict__ meta,
-                                                       u8* __restrict__ slots, const u32 rawLiterals, const u8* __restrict__ src, const u32 chunkBytes)
+// ---- counting phase: lane-private byte counters ----
+// The wave's table holds 256 symbols x 16 dwords; lane l counts in byte (l >> 4) of dword sym * 16 + (l & 15).  A counter byte
+// has one writer, so an add never meets another lane's on its address, and by banks (dword mod 32, inside a 32-lane half)
+// only lanes l and l + 16 can meet: 2-way at most, whatever the data.
+constexpr u32 kHistBatch = 8;            // 16-byte loads in flight per lane, and per lane between two flushes (4: 0.357 ms per GiB of Zipf bytes against 0.331)
+static_assert(kHistBatch * 16 + 2 <= 255, "a byte counter takes a batch plus one head and one tail byte");
+constexpr u32 kHistItemsPerWave = 8;     // (chunk, stream) items per wave of a large call (1 GiB of Zipf bytes: 1 item 0.320 ms, 4 0.320, 8 0.331, 32 0.341; text 0.149 / 0.137 / 0.139 / 0.136)
+constexpr u32 kHistMinGrid = 2 * 9 * 256;   // a small call gets a wave per item: two rounds of 9 waves (16 KiB each) on 256 CUs
+
+struct HufHistLds { u32 ctr[256 * 16]; };
+
+__device__ __forceinline__ void hist_wave_sync() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); }
+__device__ __forceinline__ void hist_add(u32* slot0 /* &ctr[lane & 15] */, u32 sym, u32 inc)
 {
-    __shared__ HufBuildLds L;
-    const u32 c = blockIdx.x, tid = threadIdx.x, lane = lane_id(), wave = wave_id();
-    const ChunkMeta m0 = meta_checked(meta[c]);
-    const u32 litSize = m0.litSize, nbSeqIn = m0.nbSeq;
-    HufWork* __restrict__ W = reinterpret_cast<HufWork*>(slots + (u64)c * kSlotStride);
-    // (a chunk without sequences never copied its literals: they are its source bytes, lz_fast.hip)
-    const u8* __restrict__ lit = m0.litFromSrc ? src + (u64)c * chunkBytes : lits + (u64)c * kLitStride;
+    (void)__hip_atomic_fetch_add(slot0 + sym * 16, inc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);     // ds_add_u32, no return
+}
+// adds the table to acc[k] (symbol k * 64 + lane) and leaves it zeroed
+__device__ __forceinline__ void hist_flush(HufHistLds& L, u32 lane, u32 (&acc)[4])
+{
+    hist_wave_sync();
+    const uint4* t4 = reinterpret_cast<const uint4*>(L.ctr);
+#pragma unroll
+    for (u32 k = 0; k < 4; ++k) {
+#pragma unroll
+        for (u32 j = 0; j < 4; ++j) {
+            // ds_read_b128 serves 16 lanes at a time over 64 banks; symbols are 16 dwords apart, so lanes that agree in
+            // (lane & 3) start at different quarters of their symbols
+            const uint4 x = t4[(k * 64 + lane) * 4 + ((j + (lane >> 2)) & 3u)];
+            acc[k] = __builtin_amdgcn_sad_u8(x.x, 0u, acc[k]); acc[k] = __builtin_amdgcn_sad_u8(x.y, 0u, acc[k]);
+            acc[k] = __builtin_amdgcn_sad_u8(x.z, 0u, acc[k]); acc[k] = __builtin_amdgcn_sad_u8(x.w, 0u, acc[k]);
+        }
+    }
+    hist_wave_sync();
+    uint4* z4 = reinterpret_cast<uint4*>(L.ctr);
+#pragma unroll
+    for (u32 i = 0; i < 16; ++i) z4[i * 64 + lane] = make_uint4(0u, 0u, 0u, 0u);
+    hist_wave_sync();
+}
+// counts lit[r0, r1) into acc; the table is zero before and after
+__device__ __forceinline__ void hist_count_range(HufHistLds& L, const u8* __restrict__ lit, u32 r0, u32 r1, u32 lane, u32 (&acc)[4])
+{
+    u32* const slot0 = L.ctr + (lane & 15u);
+    const u32 inc = 1u << (8u * (lane >> 4));
+    // 16 bytes per lane per load (aligned: the literal buffer is, a caller's source need not be); the pieces in front of and
+    // behind the aligned part are shorter than 16 bytes: one byte per lane
+    u32 a0 = r0 + ((0u - (u32)(uintptr_t)(lit + r0)) & 15u); if (a0 > r1) a0 = r1;
+    if (r0 + lane < a0) hist_add(slot0, lit[r0 + lane], inc);
+    const u32 nVec = (r1 - a0) >> 4;
+    const u32 t0 = a0 + (nVec << 4);
+    if (t0 + lane < r1) hist_add(slot0, lit[t0 + lane], inc);
+    const uint4* v4 = reinterpret_cast<const uint4*>(lit + a0);
+    auto count16 = [&](const uint4 v) {
+        const u32 d[4] = { v.x, v.y, v.z, v.w };
+#pragma unroll
+        for (u32 k = 0; k < 4; ++k) {
+#pragma unroll
+            for (u32 b = 0; b < 4; ++b) hist_add(slot0, (d[k] >> (8 * b)) & 0xFFu, inc);
+        }
+    };
+    // (the loads are unconditional — past the end they re-read the range's first piece —: behind a branch the compiler
+    //  waits for every load in flight instead of the oldest; the next batch is on its way while this one is counted and flushed)
+    uint4 q[kHistBatch];
+    if (nVec) {
+#pragma unroll
+        for (u32 k = 0; k < kHistBatch; ++k) { const u32 ix = lane + 64 * k; q[k] = v4[ix < nVec ? ix : 0u]; }
+    }
+    for (u32 i = lane; i < nVec + lane; i += 64 * kHistBatch) {       // (uniform trip count)
+#pragma unroll
+        for (u32 k = 0; k < kHistBatch; ++k) {
+            const uint4 v = q[k];
+            const u32 nx = i + 64 * k + 64 * kHistBatch;
+            q[k] = v4[nx < nVec ? nx : 0u];
+            if (i + 64 * k < nVec) count16(v);
+        }
+        hist_flush(L, lane, acc);
+    }
+    if (!nVec) hist_flush(L, lane, acc);
+}
+
+// Front half: the four per-stream histograms (they also size the four streams) and the sample maxima.  One wave per workgroup;
+// a wave takes (chunk, stream) items blockIdx.x, blockIdx.x + gridDim.x, ...
+__global__ __launch_bounds__(64) void huf_hist_kernel(const u8* __restrict__ lits, const ChunkMeta* __restrict__ meta,
+                                                      u8* __restrict__ slots, const u32 rawLiterals, const u8* __restrict__ src, const u32 chunkBytes,
+                                                      const u32 nItems)
+{
+    __shared__ HufHistLds L;
+    const u32 lane = threadIdx.x;
 #ifdef ZMI_LZ_STAMPS
-    unsigned long long stampAcc[10] = {0,0,0,0,0,0,0,0,0,0}; unsigned long long stampLast = __builtin_amdgcn_s_memtime();
+    const u32 tid = lane; unsigned long long stampAcc[10] = {0,0,0,0,0,0,0,0,0,0}; unsigned long long stampLast = __builtin_amdgcn_s_memtime();
 #endif
-
-    // ZSTD_compressLiterals: <= 63 literals are stored raw (no previous table in a one-block frame)
-    // (rawLiterals: literal compression is off — the fast strategy with a step, i.e. negative levels; U/ZstdCompressInternal.cs:146-173)
-    if (litSize <= 63 || rawLiterals) return;  // huf_tree_kernel stores them raw
-    for (u32 i = tid; i < 8 * 256; i += 256) (&L.hist[0][0][0])[i] = 0;
-    for (u32 i = tid; i < 2 * 256; i += 256) (&L.sample[0][0])[i] = 0;
-    for (u32 i = tid; i < 513; i += 256) { Node z; z.count = 0; z.parent = 0; z.byte = 0; z.nbBits = 0; L.nodes[i] = z; }
-    __syncthreads();
-    const u32 seg = (litSize + 3) / 4;
-    {   // wave w counts segment w (these are also the per-stream histograms that size the four streams)
-        const u32 s0 = wave * seg, s1 = (s0 + seg < litSize) ? s0 + seg : litSize;
-        u32* H = L.hist[wave][lane & 1];      // two copies per wave, by lane parity: halves same-address atomic serialisation
-        if (s0 < s1) {
-            // 16 bytes per lane per load (aligned: the literal buffer is, a caller's source need not be): a byte-per-lane loop is
-            // bound by one global-load latency per 64 bytes
-            u32 a0 = s0 + ((0u - (u32)(uintptr_t)(lit + s0)) & 15u); if (a0 > s1) a0 = s1;
-            if (s0 + lane < a0) atomicAdd(&H[lit[s0 + lane]], 1u);
-            const u32 nVec = (s1 - a0) >> 4;
-            const uint4* v4 = reinterpret_cast<const uint4*>(lit + a0);
-            // Skewed data serialises the atomics of the lanes that hold the most frequent byte.  Guess that byte from 64
-            // samples and count it with a ballot instead (scalar add, no LDS traffic); everything else takes the atomic.
-            u32 hot = 256, hotCnt = 0;
-            if (nVec >= 64) {
-                const u32 b0 = v4[lane].x & 0xFFu;
-                u32 best = 0;
-#pragma unroll
-                for (u32 k = 0; k < 8; ++k) {
-                    const u32 cand = read_lane(b0, k * 8);
-                    const u32 cn = popc64(ballot(b0 == cand));
-                    if (cn > best) { best = cn; hot = cand; }
-                }
-                if (best < 6) hot = 256;
-            }
-            // (four loads in flight per lane: a wave's 16 atomics per load are far shorter than the load's way from HBM, and 32 waves
-            //  per CU do not cover it — the loop used to wait out every load: 0.73 ms per GiB of Zipf bytes against 0.13 for reading them)
-            auto count16 = [&](const uint4 v) {
-                const u32 d[4] = { v.x, v.y, v.z, v.w };
-#pragma unroll
-                for (u32 k = 0; k < 4; ++k) {
-#pragma unroll
-                    for (u32 b = 0; b < 4; ++b) {
-                        const u32 sym = (d[k] >> (8 * b)) & 0xFFu;
-                        const bool isHot = sym == hot;
-                        hotCnt += popc64(ballot(isHot));
-                        if (!isHot) atomicAdd(&H[sym], 1u);
-                    }
-                }
-            };
-            //  (the loads are unconditional — past the end they re-read the segment's first piece —: behind a branch the compiler
-            //   waits for every load in flight instead of the oldest)
-            uint4 q[4];
-#pragma unroll
-            for (u32 k = 0; k < 4; ++k) { const u32 ix = lane + 64 * k; q[k] = v4[ix < nVec ? ix : 0u]; }
-            for (u32 i = lane; i < nVec; i += 256) {
-#pragma unroll
-                for (u32 k = 0; k < 4; ++k) {
-                    const uint4 v = q[k];
-                    const u32 nx = i + 64 * k + 256;
-                    q[k] = v4[nx < nVec ? nx : 0u];
-                    if (i + 64 * k < nVec) count16(v);
-                }
-            }
-            if (lane == 0 && hot < 256) atomicAdd(&H[hot], hotCnt);
-            const u32 t0 = a0 + (nVec << 4);
-            if (t0 + lane < s1) atomicAdd(&H[lit[t0 + lane]], 1u);
-        }
-    }
-    const u32 suspect = (nbSeqIn == 0) || (litSize / nbSeqIn >= 20);
-    const bool doSample = suspect && litSize >= 4096 * 10;
-    if (doSample && wave < 2) {       // HUF_compress_internal's 2 x 4 KiB pre-check (U/HufCompress.cs:1412-1446)
-        const u8* sp = wave == 0 ? lit : lit + litSize - 4096;
-        for (u32 i = lane; i < 4096; i += 64) atomicAdd(&L.sample[wave][sp[i]], 1u);
-    }
-    __syncthreads();
     {
-        u32 tot = 0;
+        uint4* z4 = reinterpret_cast<uint4*>(L.ctr);
 #pragma unroll
-        for (u32 w = 0; w < 4; ++w) { const u32 v = L.hist[w][0][tid] + L.hist[w][1][tid]; W->hist[w][tid] = (u16)v; tot += v; }
-        L.count[tid] = tot;
+        for (u32 i = 0; i < 16; ++i) z4[i * 64 + lane] = make_uint4(0u, 0u, 0u, 0u);
     }
-    if (doSample && wave < 2) {
-        u32 mx = 0;
-        for (u32 i = lane; i < 256; i += 64) { const u32 v = L.sample[wave][i]; mx = v > mx ? v : mx; }
-        mx = wave_max(mx);
-        if (lane == 0) L.sampleMax[wave] = mx;
-    }
-    __syncthreads();
-
-    ZMI_HSTAMP(0);
-    {   // compressible at all?  (HUF_compress_internal, U/HufCompress.cs:1412-1462) — every thread reaches the same verdict
-        const u32 cnt = L.count[tid];
-        const u64 nz = ballot(cnt != 0);
-        const u32 wmx = wave_max(cnt);
-        if (lane == 0) { L.redMaxSV[wave] = nz ? wave * 64 + 63 - (u32)__builtin_clzll(nz) : 0; L.redLargest[wave] = wmx; }
-        __syncthreads();
-        u32 maxSV0 = 0, largest = 0;
-        for (u32 w = 0; w < 4; ++w) { maxSV0 = L.redMaxSV[w] > maxSV0 ? L.redMaxSV[w] : maxSV0; largest = L.redLargest[w] > largest ? L.redLargest[w] : largest; }
-        u32 compressed = 1, rle = 0;
-        if (doSample && L.sampleMax[0] + L.sampleMax[1] <= ((2 * 4096) >> 7) + 4) { compressed = 0; maxSV0 = 255; }
-        else if (largest == litSize) { rle = 1; compressed = 0; }
-        else if (largest <= (litSize >> 7) + 4) compressed = 0;
-        if (tid == 0) { L.sh[kShCompressed] = compressed; L.sh[kShMaxSV] = maxSV0; L.sh[kShRle] = rle; L.sh[kShRleByte] = rle ? lit[0] : 0; }
-        if (compressed) {
-            // HUF_sort's bucket placement (U/HufCompress.cs:635-680) without the serial counters: a symbol lands behind
-            // every symbol of a higher bucket and behind the lower-numbered symbols of its own bucket
-            const u32 idx = huf_get_index(cnt);
-            L.sortIdx[tid] = (u8)idx;
-            __syncthreads();
-            if (tid <= maxSV0) {
-                u32 pos = 0;
-                for (u32 mS = 0; mS <= maxSV0; ++mS) { const u32 im = L.sortIdx[mS]; pos += (im > idx) || (im == idx && mS < tid); }
-                Node nd; nd.count = cnt; nd.parent = 0; nd.byte = (u8)tid; nd.nbBits = 0;
-                L.nodes[1 + pos] = nd;
-            }
-            if (tid < 26) {            // extent of log2 bucket n (symbols whose index is n-1), for huf_sort_bucket
-                const u32 nB = 165 + tid; u32 start = 0, size = 0;
-                for (u32 mS = 0; mS <= maxSV0; ++mS) { const u32 im = L.sortIdx[mS]; start += im >= nB; size += im == nB - 1; }
-                L.rankBase[nB] = (u16)start; L.rankCurr[nB] = (u16)(start + size);
-            }
+    hist_wave_sync();
+    for (u32 item = blockIdx.x; item < nItems; item += gridDim.x) {
+        const u32 c = item >> 2, w = item & 3u;
+        const ChunkMeta m0 = meta_checked(meta[c]);
+        const u32 litSize = m0.litSize, nbSeqIn = m0.nbSeq;
+        // ZSTD_compressLiterals: <= 63 literals are stored raw (no previous table in a one-block frame)
+        // (rawLiterals: literal compression is off — the fast strategy with a step, i.e. negative levels; U/ZstdCompressInternal.cs:146-173)
+        if (litSize <= 63 || rawLiterals) continue;   // huf_tree_kernel stores them raw
+        HufWork* __restrict__ W = reinterpret_cast<HufWork*>(slots + (u64)c * kSlotStride);
+        // (a chunk without sequences never copied its literals: they are its source bytes, lz_fast.hip)
+        const u8* __restrict__ lit = m0.litFromSrc ? src + (u64)c * chunkBytes : lits + (u64)c * kLitStride;
+        const u32 seg = (litSize + 3) / 4;
+        u32 s0 = w * seg; if (s0 > litSize) s0 = litSize;
+        const u32 s1 = (s0 + seg < litSize) ? s0 + seg : litSize;
+        // HUF_compress_internal's 2 x 4 KiB pre-check (U/HufCompress.cs:1412-1446) looks at the first 4 KiB of stream 0 and the
+        // last 4 KiB of stream 3 (a stream is >= 10 KiB here): those are counted as a range of their own and read off at the flush
+        const u32 suspect = (nbSeqIn == 0) || (litSize / nbSeqIn >= 20);
+        const bool doSample = suspect && litSize >= 4096 * 10;
+        u32 mid = s1;
+        if (doSample && w == 0) mid = s0 + 4096;
+        if (doSample && w == 3) mid = s1 - 4096;
+        u32 acc[4] = { 0, 0, 0, 0 }, part[4] = { 0, 0, 0, 0 };
+        if (s0 < mid) hist_count_range(L, lit, s0, mid, lane, acc);
+#pragma unroll
+        for (u32 k = 0; k < 4; ++k) part[k] = acc[k];
+        if (mid < s1) hist_count_range(L, lit, mid, s1, lane, acc);
+#pragma unroll
+        for (u32 k = 0; k < 4; ++k) W->hist[w][k * 64 + lane] = (u16)acc[k];
+        if (doSample && (w == 0 || w == 3)) {
+            u32 mx = 0;
+#pragma unroll
+            for (u32 k = 0; k < 4; ++k) { const u32 v = w == 0 ? part[k] : acc[k] - part[k]; mx = v > mx ? v : mx; }
+            mx = wave_max(mx);
+            if (lane == 0) W->sampleMax[w ? 1 : 0] = mx;
         }
     }
-    ZMI_HSTAMP(1);
-    __syncthreads();
-    if (L.sh[kShCompressed]) {
-        if (tid < 26) huf_sort_bucket(L, tid);                 // HUF_sort's per-bucket quicksorts, one bucket per lane
-        __syncthreads();
-        W->leafCount[tid] = L.nodes[1 + tid].count; W->leafByte[tid] = L.nodes[1 + tid].byte;
-    }
-    if (tid < 4) W->flags[tid] = L.sh[tid];                    // compressed, maxSV, rle, rleByte
-    ZMI_HSTAMP(2);
+    ZMI_HSTAMP(0);
 #ifdef ZMI_LZ_STAMPS
-    if (tid == 0) for (int i = 0; i < 3; i++) atomicAdd(&g_hufStamps[i], stampAcc[i]);
+    if (tid == 0) atomicAdd(&g_hufStamps[0], stampAcc[0]);
 #endif
 }
 
-// Back half: the serial constructions (HUF_buildTree, HUF_setMaxHeight, HUF_compressWeights) and the decisions.  One
-// wave per chunk and ~6 KiB of LDS, so that ~25 chunks per CU hide each other's LDS latency; per-symbol steps run
-// four symbols per lane.
+// Back half: the verdict and HUF_sort (parallel over the 256 symbols, four per lane), then the serial constructions
+// (HUF_buildTree, HUF_setMaxHeight, HUF_compressWeights) and the decisions.  One wave per chunk and 5.4 KiB of LDS, so
+// that ~29 chunks per CU hide each other's LDS latency.
 __global__ __launch_bounds__(64) void huf_tree_kernel(ChunkMeta* __restrict__ meta, HufTable* __restrict__ tables, const u8* __restrict__ slots,
                                                       const u32 rawLiterals)
 {
     __shared__ HufTreeLds L;
     const u32 c = blockIdx.x, lane = threadIdx.x, tid = lane;
-    ChunkMeta m = meta_checked(meta[c]);
+    // (the record is written back field by field: a whole-struct copy kept across the kernel went through scratch memory)
+    const ChunkMeta m = meta_checked(meta[c]);
+    ChunkMeta* const mOut = meta + c;
     const u32 litSize = m.litSize;
+    auto store_section = [&](u32 litMode, u32 lhSz, u32 sectionSize) {      // + what meta_checked settled
+        mOut->srcSize = m.srcSize; mOut->nbSeq = m.nbSeq; mOut->litSize = m.litSize; mOut->fhSize = m.fhSize;
+        mOut->litMode = litMode; mOut->lhSize = lhSz; mOut->litSectionSize = sectionSize;
+    };
     const u32 lhSizeRaw = 1 + (litSize > 31) + (litSize > 4095);
     const HufWork* __restrict__ W = reinterpret_cast<const HufWork*>(slots + (u64)c * kSlotStride);
 #ifdef ZMI_LZ_STAMPS
@@ -484,26 +479,92 @@ __global__ __launch_bounds__(64) void huf_tree_kernel(ChunkMeta* __restrict__ me
 #endif
     // ZSTD_compressLiterals: <= 63 literals are stored raw (no previous table in a one-block frame)
     if (litSize <= 63 || rawLiterals) {        // (or ZSTD_noCompressLiterals because literal compression is disabled, U/ZstdCompressLiterals.cs:99-101)
-        if (tid == 0) { m.litMode = kLitRaw; m.lhSize = lhSizeRaw; m.litSectionSize = lhSizeRaw + litSize; meta[c] = m; }
+        if (tid == 0) store_section(kLitRaw, lhSizeRaw, lhSizeRaw + litSize);
         return;
     }
     const u32 lhSize = 3 + (litSize >= 1024) + (litSize >= 16384);
     const u32 single = litSize < 256;
     HufTable* T = tables + c;
-    const u32 shCompressed = W->flags[0], maxSV = W->flags[1], shRle = W->flags[2], shRleByte = W->flags[3];
+    u32 hst[4][4], cnt[4];          // [stream][k]: symbol k * 64 + lane
+#pragma unroll
+    for (u32 k = 0; k < 4; ++k) {
+        cnt[k] = 0;
+#pragma unroll
+        for (u32 w = 0; w < 4; ++w) { hst[w][k] = W->hist[w][k * 64 + lane]; cnt[k] += hst[w][k]; }
+    }
+    u32 shCompressed = 1, maxSV = 0, shRle = 0, shRleByte = 0;
+    {   // compressible at all?  (HUF_compress_internal, U/HufCompress.cs:1412-1462) — uniform
+        u32 largest = cnt[0];
+#pragma unroll
+        for (u32 k = 0; k < 4; ++k) {
+            const u64 nz = ballot(cnt[k] != 0);
+            if (nz) maxSV = k * 64 + 63 - (u32)__builtin_clzll(nz);
+            largest = cnt[k] > largest ? cnt[k] : largest;
+        }
+        largest = wave_max(largest);
+        const u32 suspect = (m.nbSeq == 0) || (litSize / m.nbSeq >= 20);
+        const bool doSample = suspect && litSize >= 4096 * 10;
+        if (doSample && W->sampleMax[0] + W->sampleMax[1] <= ((2 * 4096) >> 7) + 4) { shCompressed = 0; maxSV = 255; }
+        else if (largest == litSize) {             // one symbol: it is the RLE byte
+            shRle = 1; shCompressed = 0;
+#pragma unroll
+            for (u32 k = 0; k < 4; ++k) { const u64 b = ballot(cnt[k] == litSize); if (b) shRleByte = k * 64 + ctz64(b); }
+        }
+        else if (largest <= (litSize >> 7) + 4) shCompressed = 0;
+    }
     u32 huffLog = 0;
     u32 streamBits[4] = { 0, 0, 0, 0 };
     if (shCompressed) {
+        HufSortLds& S = *reinterpret_cast<HufSortLds*>(&L.nodes[kSortScratchNode]);
+        // HUF_sort's bucket placement (U/HufCompress.cs:635-680) without the serial counters: a symbol lands behind
+        // every symbol of a higher bucket and behind the lower-numbered symbols of its own bucket — behind every symbol
+        // with a larger key
+        u32 idx[4], key[4], pos[4];
+#pragma unroll
+        for (u32 k = 0; k < 4; ++k) {
+            const u32 sIdx = k * 64 + lane;
+            idx[k] = huf_get_index(cnt[k]);
+            key[k] = sIdx <= maxSV ? (idx[k] << 8) | (255u - sIdx) : 0u;
+            S.keys[sIdx] = key[k];
+            pos[k] = 0;
+        }
+        for (u32 i = lane; i < kSortScratchNode; i += 64) { Node z; z.count = 0; z.parent = 0; z.byte = 0; z.nbBits = 0; L.nodes[i] = z; }
+        // extents of the log2 buckets, for huf_sort_bucket: lane t keeps the number of symbols whose index is >= 164 + t
+        u32 ge = 0;
+#pragma unroll
+        for (u32 t = 0; t < 27; ++t) {
+            const u32 n = popc64(ballot(idx[0] >= 164 + t)) + popc64(ballot(idx[1] >= 164 + t)) + popc64(ballot(idx[2] >= 164 + t)) + popc64(ballot(idx[3] >= 164 + t));
+            if (lane == t) ge = n;
+        }
+        wave_lds_sync();
+        {
+            const uint4* k4 = reinterpret_cast<const uint4*>(S.keys);
+            const u32 nQuad = (maxSV >> 2) + 1;
+            for (u32 i = 0; i < nQuad; ++i) {          // (every lane reads the same four keys)
+                const uint4 o = k4[i];
+#pragma unroll
+                for (u32 k = 0; k < 4; ++k) pos[k] += (u32)(o.x > key[k]) + (u32)(o.y > key[k]) + (u32)(o.z > key[k]) + (u32)(o.w > key[k]);
+            }
+        }
+        wave_lds_sync();                               // (the keys are read: their storage becomes the quicksort stacks)
+#pragma unroll
+        for (u32 k = 0; k < 4; ++k) {
+            const u32 sIdx = k * 64 + lane;
+            if (sIdx <= maxSV) { Node nd; nd.count = cnt[k]; nd.parent = 0; nd.byte = (u8)sIdx; nd.nbBits = 0; L.nodes[1 + pos[k]] = nd; }
+        }
+        if (lane < 27) S.rankGe[lane] = (u16)ge;
+        wave_lds_sync();
+        ZMI_HSTAMP(1);
+        if (lane < 26) huf_sort_bucket(L.nodes, S, lane);      // HUF_sort's per-bucket quicksorts, one bucket per lane
+        wave_lds_sync();
+        ZMI_HSTAMP(2);
 #pragma unroll
         for (u32 k = 0; k < 4; ++k) {
             const u32 pos = k * 64 + lane;
-            Node nd; nd.count = W->leafCount[pos]; nd.parent = 0; nd.byte = W->leafByte[pos]; nd.nbBits = 0;
-            L.nodes[1 + pos] = nd;
             Node z; z.count = 0; z.parent = 0; z.byte = 0; z.nbBits = 0;
             L.nodes[257 + pos] = z;
             L.nbBits[pos] = 0;
         }
-        if (lane == 0) { Node z; z.count = 0; z.parent = 0; z.byte = 0; z.nbBits = 0; L.nodes[0] = z; }
         if (lane < 13) L.wcount[lane] = 0;
         wave_lds_sync();
         Node* huffNode = L.nodes + 1;
@@ -569,7 +630,7 @@ __global__ __launch_bounds__(64) void huf_tree_kernel(ChunkMeta* __restrict__ me
             for (u32 w = 0; w < 4; ++w) {
                 u32 bits = 0;
 #pragma unroll
-                for (u32 k = 0; k < 4; ++k) bits += (u32)W->hist[w][k * 64 + lane] * nb[k];
+                for (u32 k = 0; k < 4; ++k) bits += hst[w][k] * nb[k];
                 streamBits[w] = wave_sum(bits);
             }
         }
@@ -617,18 +678,17 @@ __global__ __launch_bounds__(64) void huf_tree_kernel(ChunkMeta* __restrict__ me
         if (compressed && cLitSize >= litSize - min_gain(litSize)) compressed = false;     // ZSTD_compressLiterals
     }
     if (compressed) {
-        m.litMode = kLitCompressed; m.litSingle = single; m.lhSize = lhSize; m.hufHdrSize = hSize;
-        m.streamSize[0] = streamSize[0]; m.streamSize[1] = streamSize[1]; m.streamSize[2] = streamSize[2]; m.streamSize[3] = streamSize[3];
-        m.litSectionSize = lhSize + cLitSize;
+        store_section(kLitCompressed, lhSize, lhSize + cLitSize);
+        mOut->litSingle = single; mOut->hufHdrSize = hSize;
+        mOut->streamSize[0] = streamSize[0]; mOut->streamSize[1] = streamSize[1]; mOut->streamSize[2] = streamSize[2]; mOut->streamSize[3] = streamSize[3];
     } else if (rle) {
-        m.litMode = kLitRle; m.lhSize = lhSizeRaw; m.litSectionSize = lhSizeRaw + 1; m.rleByte = shRleByte;
+        store_section(kLitRle, lhSizeRaw, lhSizeRaw + 1); mOut->rleByte = shRleByte;
     } else {
-        m.litMode = kLitRaw; m.lhSize = lhSizeRaw; m.litSectionSize = lhSizeRaw + litSize;
+        store_section(kLitRaw, lhSizeRaw, lhSizeRaw + litSize);
     }
-    meta[c] = m;
     ZMI_HSTAMP(7);
 #ifdef ZMI_LZ_STAMPS
-    for (int i = 3; i < 10; i++) atomicAdd(&g_hufStamps[i], stampAcc[i]);
+    for (int i = 1; i < 10; i++) atomicAdd(&g_hufStamps[i], stampAcc[i]);
 #endif
 }
 
@@ -778,7 +838,10 @@ __global__ __launch_bounds__(256) void huf_encode_kernel(const u8* __restrict__ 
 void launch_huf_build(const u8* lits, ChunkMeta* meta, HufTable* tables, u8* slots, u32 nChunks, u32 rawLiterals, const u8* src, u32 chunkBytes,
                       hipStream_t stream, StageHook hook)
 {
-    hipLaunchKernelGGL(huf_hist_kernel, dim3(nChunks), dim3(256), 0, stream, lits, meta, slots, rawLiterals, src, chunkBytes);
+    // a throughput kernel: a wave per (chunk, stream) item while that keeps every CU's share short, several items per wave beyond
+    const u32 nItems = 4 * nChunks, perWave = (nItems + kHistItemsPerWave - 1) / kHistItemsPerWave;
+    const u32 grid = nItems <= kHistMinGrid ? nItems : (perWave > kHistMinGrid ? perWave : kHistMinGrid);
+    hipLaunchKernelGGL(huf_hist_kernel, dim3(grid), dim3(64), 0, stream, lits, meta, slots, rawLiterals, src, chunkBytes, nItems);
     hook("huf_hist");
     hipLaunchKernelGGL(huf_tree_kernel, dim3(nChunks), dim3(64), 0, stream, meta, tables, slots, rawLiterals);
     hook("huf_tree");
