@@ -216,6 +216,37 @@ int ZSTDMI_debugLastWalkSerial(const ZSTD_DCtx* dctx);
 size_t ZSTDMI_compressDevice(ZSTD_CCtx* cctx, void* d_dst, size_t dstCapacity, const void* d_src, size_t srcSize);
 size_t ZSTDMI_decompressDevice(ZSTD_DCtx* dctx, void* d_dst, size_t dstCapacity, const void* d_src, size_t srcSize);
 
+/* Many small buffers in one call: n independent entries, entry i from srcs[i] (srcSizes[i] bytes) to dsts[i] (dstCapacities[i] bytes).
+ * The five arrays are host memory; srcs[i] and dsts[i] are device pointers as for ZSTDMI_compressDevice / ZSTDMI_decompressDevice,
+ * anywhere in HBM, at any alignment, in any order; destinations must not overlap each other or any source.  Both calls return 0 when
+ * they ran (n == 0: at once, without touching the device), or the error of the whole call: init_missing without a device,
+ * memory_allocation, GENERIC for a NULL context or a NULL array with n > 0, parameter_unsupported on a context with several device
+ * workers (ZSTDMI_*_setDevices).  dstSizes[i] = the bytes written for entry i, or its error (dstSize_tooSmall, corruption_detected
+ * ...): size, error code and the bytes at dsts[i] are exactly those of the single device call on that entry alone, on the same
+ * context with the same sticky parameters and dictionary — a compressed entry is a complete stream that decodes on its own.  One
+ * entry's failure changes nothing of another's, nothing is written at or beyond dsts[i] + dstCapacities[i], and the context is left as
+ * it was found.
+ * Compress.  Entries of one block (1 byte up to 64 KiB; behind a dictionary 64 KiB minus the dictionary's last 60 KiB rounded up to
+ * 4 KiB) — at every level, with or without a dictionary, checksum or content size, LDM enabled or not — share ONE pass through the
+ * pipeline per class of resolved parameters (the cParams tiers at 16 KiB, 128 KiB and 256 KiB), ZSTDMI_CCtx_setPassChunks blocks at
+ * most: a gather kernel stages them from the pointer array, the kernels of the single call run once over all of them, and a placement
+ * kernel sends each result straight to its destination; the sizes come back in one copy per pass.  So do entries of several blocks
+ * that are independent 64 KiB frames (behind a dictionary, or with ZSTDMI_CCtx_setHistory(0)) below 4 MiB.  Everything else — empty
+ * entries, multi-block frames, LDM above one block, ZSTD_c_windowLog 10 .. 15 above one window, 4 MiB and more — is handed to the
+ * single-call path one entry at a time, after the batched passes, in entry order.
+ * Decompress.  One lane per entry walks that entry's frames exactly as the single call's serial walk does (every frame, skippable
+ * frames, trailing bytes, a dictID that is not the loaded one); the frames and blocks of all entries then go through the decoder ONCE,
+ * with as many host synchronisations as a single call makes.  An entry's error is its first failing block's first error.  Entries
+ * that hold a frame without a content size, and entries of more than 4 MiB compressed, are decoded by the single-call path one at a
+ * time afterwards. */
+size_t ZSTDMI_compressBatch(ZSTD_CCtx* cctx, const void* const* srcs, const size_t* srcSizes, size_t n,
+                            void* const* dsts, const size_t* dstCapacities, size_t* dstSizes);
+size_t ZSTDMI_decompressBatch(ZSTD_DCtx* dctx, const void* const* srcs, const size_t* srcSizes, size_t n,
+                              void* const* dsts, const size_t* dstCapacities, size_t* dstSizes);
+/* diagnostics: entries of the last batch call that did NOT take the batched pass (handed to the single-call path); -1 without a context */
+int ZSTDMI_debugLastBatchAlone(const ZSTD_CCtx* cctx);
+int ZSTDMI_debugLastBatchAloneD(const ZSTD_DCtx* dctx);
+
 /* per-stage HIP-event timing of the LAST call (enable first).  Fills up to `cap` entries, returns the count. */
 size_t ZSTDMI_CCtx_setProfiling(ZSTD_CCtx* cctx, int enable);
 size_t ZSTDMI_DCtx_setProfiling(ZSTD_DCtx* dctx, int enable);

@@ -1,0 +1,107 @@
+"""Batched calls against a loop of single calls (run on the GPU box): 256 MiB of device-resident entries of 4 KiB, 16 KiB and 64 KiB
+(65 536, 16 384 and 4096 entries), text and Zipf bytes at levels 1 and 3, and 4 KiB text records at level 3 with
+tests/golden/trained_16k.dict.  Per point, compress and decompress:
+  (a) loop   : one ZSTDMI_compressDevice / ZSTDMI_decompressDevice call per entry (timed on the first 4096 entries, scaled to all)
+  (b) batch  : one ZSTDMI_compressBatch / ZSTDMI_decompressBatch call
+  (c) concat : one single call on the concatenation — a different product (the entries are not decodable on their own), the ceiling
+  (d) the batch call's stage times (ZSTDMI_*_getStageTimes)
+Best of 3 after a warm-up call of the same shape; the host clock stops after the call's final synchronise (every call ends with one).
+The input is 16 MiB of generated data repeated (entries are independent, so the repeats are nobody's match).
+python tools/batch_time.py [MiB]"""
+import ctypes, sys, os, time
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
+import numpy as np, torch
+torch.zeros(1, device="cuda")
+import zstdsharp_amd as z, datagen
+lib = z._ffi.load()
+MiB = 1 << 20
+total = (int(sys.argv[1]) if len(sys.argv) > 1 else 256) * MiB
+SAMPLE = 4096
+DICT = open(os.path.join(ROOT, "tests", "golden", "trained_16k.dict"), "rb").read()
+
+
+def stage_times(get, ctx):
+    ms = (ctypes.c_float * 24)(); names = (ctypes.c_char_p * 24)()
+    k = get(ctx, ms, names, 24)
+    return " ".join(f"{names[i].decode()} {float(ms[i]):.2f}" for i in range(k))
+
+
+def best_of(f, reps=3):
+    f()                                     # warm-up: same shape, workspaces allocated
+    best = 1e9
+    for _ in range(reps):
+        torch.cuda.synchronize(); t0 = time.perf_counter()
+        f()
+        best = min(best, time.perf_counter() - t0)
+    return best
+
+
+def ptrs(base, offs):
+    return (ctypes.c_void_p * len(offs))(*[base + o for o in offs])
+
+
+def sizes(vals):
+    return (ctypes.c_size_t * len(vals))(*vals)
+
+
+def ok(r):
+    assert not lib.ZSTD_isError(r), lib.ZSTD_getErrorName(r)
+    return r
+
+
+data = {k: torch.from_numpy(np.frombuffer(datagen.gen(k, 16 * MiB, 5), dtype=np.uint8).copy()).cuda().repeat(total // (16 * MiB)) for k in ("text", "zipf")}
+points = [(kind, size, level, None) for size in (4096, 16384, 65536) for kind in ("text", "zipf") for level in (1, 3)] + [("text", 4096, 3, DICT)]
+print(f"{total // MiB} MiB per point; ms per call of all entries (GB/s of content)", flush=True)
+for kind, size, level, dic in points:
+    src = data[kind]
+    n = total // size
+    cap = lib.ZSTD_compressBound(size)
+    dst = torch.empty(n * cap + total // 64 + MiB, dtype=torch.uint8, device="cuda")
+    out = torch.empty(total, dtype=torch.uint8, device="cuda")
+    c, d = lib.ZSTD_createCCtx(), lib.ZSTD_createDCtx()
+    lib.ZSTD_CCtx_setParameter(c, 100, level)
+    if dic:
+        ok(lib.ZSTD_CCtx_loadDictionary(c, dic, len(dic))); ok(lib.ZSTD_DCtx_loadDictionary(d, dic, len(dic)))
+    s_ptr, d_ptr, o_ptr = ptrs(src.data_ptr(), [i * size for i in range(n)]), ptrs(dst.data_ptr(), [i * cap for i in range(n)]), ptrs(out.data_ptr(), [i * size for i in range(n)])
+    s_sz, d_cap, got, back = sizes([size] * n), sizes([cap] * n), (ctypes.c_size_t * n)(), (ctypes.c_size_t * n)()
+    # (b) batch
+    lib.ZSTDMI_CCtx_setProfiling(c, 1); lib.ZSTDMI_DCtx_setProfiling(d, 1)
+    cb = best_of(lambda: ok(lib.ZSTDMI_compressBatch(c, s_ptr, s_sz, n, d_ptr, d_cap, got)))
+    assert not any(lib.ZSTD_isError(g) for g in got) and lib.ZSTDMI_debugLastBatchAlone(c) == 0
+    cst = stage_times(lib.ZSTDMI_CCtx_getStageTimes, c)
+    db = best_of(lambda: ok(lib.ZSTDMI_decompressBatch(d, d_ptr, got, n, o_ptr, s_sz, back)))
+    assert all(b == size for b in back) and lib.ZSTDMI_debugLastBatchAloneD(d) == 0 and bool(torch.equal(out, src))
+    dst_t = stage_times(lib.ZSTDMI_DCtx_getStageTimes, d)
+    lib.ZSTDMI_CCtx_setProfiling(c, 0); lib.ZSTDMI_DCtx_setProfiling(d, 0)
+    comp_bytes = sum(got)
+    # (a) the loop of single calls, on a sample
+    m = min(n, SAMPLE)
+
+    def loop_c():
+        for i in range(m):
+            lib.ZSTDMI_compressDevice(c, d_ptr[i], cap, s_ptr[i], size)
+
+    def loop_d():
+        for i in range(m):
+            lib.ZSTDMI_decompressDevice(d, o_ptr[i], size, d_ptr[i], got[i])
+
+    ca = best_of(loop_c, 3) * n / m
+    da = best_of(loop_d, 3) * n / m
+    # (c) one call on the concatenation (without the dictionary's small-input framing it is simply another stream)
+    whole = [0]
+
+    def concat_c():
+        whole[0] = ok(lib.ZSTDMI_compressDevice(c, dst.data_ptr(), dst.numel(), src.data_ptr(), total))
+
+    cc = best_of(concat_c)
+    dc = best_of(lambda: ok(lib.ZSTDMI_decompressDevice(d, out.data_ptr(), total, dst.data_ptr(), whole[0])))
+    gbs = lambda t: total / t / 1e9
+    name = f"{kind} {size // 1024:2d} KiB L{level}{' dict' if dic else ''}"
+    print(f"| {name:22s} | {n:6d} | {comp_bytes / total:.3f} | {ca * 1e3:8.1f} ({gbs(ca):6.2f}) | {cb * 1e3:7.2f} ({gbs(cb):6.1f}) | {cc * 1e3:7.2f} ({gbs(cc):6.1f}) "
+          f"| {da * 1e3:8.1f} ({gbs(da):6.2f}) | {db * 1e3:7.2f} ({gbs(db):6.1f}) | {dc * 1e3:7.2f} ({gbs(dc):6.1f}) |", flush=True)
+    print(f"    compress stages ms: {cst}\n    decompress stages ms: {dst_t}", flush=True)
+    assert cb < ca and db < da, "the batch call must beat the loop of single calls"
+    lib.ZSTD_freeCCtx(c); lib.ZSTD_freeDCtx(d)
+    del dst, out
+    torch.cuda.empty_cache()

@@ -9,6 +9,7 @@ from .compressor import Compressor
 from .decompressor import Decompressor
 from .dictbuilder import DictBuilder
 from . import _ffi
+from .batch import compress_batch, decompress_batch
 from .streams import CompressionStream, DecompressionStream, EndOfStreamException
 
-__all__ = ["Compressor", "Decompressor", "DictBuilder", "CompressionStream", "DecompressionStream", "EndOfStreamException", "ZstdException", "ZSTD_ErrorCode", "_ffi"]
+__all__ = ["Compressor", "Decompressor", "DictBuilder", "CompressionStream", "DecompressionStream", "EndOfStreamException", "ZstdException", "ZSTD_ErrorCode", "compress_batch", "decompress_batch", "_ffi"]

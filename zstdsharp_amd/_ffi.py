@@ -89,6 +89,12 @@ SIGNATURES = {
     "ZSTDMI_CCtx_setParser": (c_size_t, [c_void_p, c_uint]),
     "ZSTDMI_compressDevice": (c_size_t, [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t]),
     "ZSTDMI_decompressDevice": (c_size_t, [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t]),
+    "ZSTDMI_compressBatch": (c_size_t, [c_void_p, ctypes.POINTER(c_void_p), ctypes.POINTER(c_size_t), c_size_t,
+                                        ctypes.POINTER(c_void_p), ctypes.POINTER(c_size_t), ctypes.POINTER(c_size_t)]),
+    "ZSTDMI_decompressBatch": (c_size_t, [c_void_p, ctypes.POINTER(c_void_p), ctypes.POINTER(c_size_t), c_size_t,
+                                          ctypes.POINTER(c_void_p), ctypes.POINTER(c_size_t), ctypes.POINTER(c_size_t)]),
+    "ZSTDMI_debugLastBatchAlone": (c_int, [c_void_p]),
+    "ZSTDMI_debugLastBatchAloneD": (c_int, [c_void_p]),
     "ZSTDMI_CCtx_setProfiling": (c_size_t, [c_void_p, c_int]),
     "ZSTDMI_DCtx_setProfiling": (c_size_t, [c_void_p, c_int]),
     "ZSTDMI_CCtx_getStageTimes": (c_int, [c_void_p, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_char_p), c_int]),

@@ -1,0 +1,95 @@
+"""Many small buffers in one call (ZSTDMI_compressBatch / ZSTDMI_decompressBatch, include/zstd_mi355x.h): every item is compressed as
+Compressor.Wrap would compress it alone — a complete stream that decodes on its own — and decoded as Decompressor.Unwrap would decode
+it, but the items share one pass through the GPU pipeline.
+
+torch is imported inside the functions: the package imports without it.
+"""
+import ctypes
+
+from . import _ffi
+from .errors import ZstdException, get_error_code, is_error
+
+
+def _pointer_array(values):
+    return (ctypes.c_void_p * len(values))(*values)
+
+
+def _size_array(values):
+    return (ctypes.c_size_t * len(values))(*values)
+
+
+def _gather(torch, items):
+    """-> (tensors?, device, sizes, source pointers, keepalive)"""
+    tensors = all(isinstance(x, torch.Tensor) for x in items)
+    if tensors:
+        for i, t in enumerate(items):
+            if not (t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous()):
+                raise TypeError(f"item {i}: expected a contiguous CUDA uint8 tensor")
+        return True, items[0].device, [t.numel() for t in items], [t.data_ptr() if t.numel() else None for t in items], items
+    if any(isinstance(x, torch.Tensor) for x in items):
+        raise TypeError("items must be all tensors or all bytes-like")
+    views = [memoryview(x).cast("B") for x in items]
+    sizes = [len(v) for v in views]
+    device = torch.device("cuda", torch.cuda.current_device())
+    flat = torch.frombuffer(bytearray(b"".join(views)) or bytearray(1), dtype=torch.uint8).to(device)      # one upload
+    srcs, at = [], 0
+    for s in sizes:
+        srcs.append(flat.data_ptr() + at if s else None)
+        at += s
+    return False, device, sizes, srcs, flat
+
+
+def _run(torch, lib, call, ctx, device, srcs, sizes, caps, tensors):
+    n = len(sizes)
+    starts, at = [], 0
+    for c in caps:
+        starts.append(at)
+        at += c
+    out = torch.empty(max(at, 1), dtype=torch.uint8, device=device)
+    got = (ctypes.c_size_t * n)()
+    torch.cuda.synchronize(device)          # the library runs on a stream of its own
+    r = call(ctx, _pointer_array(srcs), _size_array(sizes), n, _pointer_array([out.data_ptr() + s for s in starts]), _size_array(caps), got)
+    if is_error(r):
+        raise ZstdException(get_error_code(r), lib.ZSTD_getErrorName(r).decode())
+    for i in range(n):
+        if is_error(got[i]):
+            raise ZstdException(get_error_code(got[i]), f"item {i}: {lib.ZSTD_getErrorName(got[i]).decode()}")
+    if tensors:
+        return [out[starts[i]:starts[i] + got[i]] for i in range(n)]
+    host = out.cpu().numpy().tobytes()
+    return [host[starts[i]:starts[i] + got[i]] for i in range(n)]
+
+
+def decompress_batch(decompressor, items, sizes):
+    """items as for compress_batch, each a complete compressed stream; sizes[i] = room for item i's content (its decompressed size, or
+    more).  -> a list of CUDA uint8 tensors or of bytes.  Uses the decompressor's dictionary.  An item that fails — damaged, or larger
+    than sizes[i] — raises ZstdException naming its index."""
+    import torch
+    decompressor._ensure_not_disposed()
+    lib = decompressor._lib
+    items, sizes = list(items), [int(x) for x in sizes]
+    if len(items) != len(sizes):
+        raise ValueError("one size per item")
+    if not items:
+        return []
+    tensors, device, src_sizes, srcs, keep = _gather(torch, items)
+    out = _run(torch, lib, lib.ZSTDMI_decompressBatch, decompressor.dctx, device, srcs, src_sizes, sizes, tensors)
+    del keep
+    return out
+
+
+def compress_batch(compressor, items):
+    """items: a list of torch CUDA uint8 tensors (-> a list of CUDA uint8 tensors, views of one buffer) or of bytes-like objects
+    (uploaded in one copy -> a list of bytes).  Uses the compressor's level, parameters and dictionary.  An item that fails raises
+    ZstdException naming its index."""
+    import torch
+    compressor._ensure_not_disposed()
+    lib = compressor._lib
+    items = list(items)
+    n = len(items)
+    if n == 0:
+        return []
+    tensors, device, sizes, srcs, keep = _gather(torch, items)
+    out = _run(torch, lib, lib.ZSTDMI_compressBatch, compressor.cctx, device, srcs, sizes, [lib.ZSTD_compressBound(x) for x in sizes], tensors)
+    del keep
+    return out

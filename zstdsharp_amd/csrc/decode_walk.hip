@@ -234,6 +234,119 @@ __global__ __launch_bounds__(256) void walk_emit_kernel(const u8* __restrict__ s
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// batch walk (ZSTDMI_decompressBatch): one lane per entry runs the exact serial walk over that entry alone — every frame, skippable
+// frames, trailing garbage, a dictID that is not the loaded one — in count-then-emit form like the walks above
+// ------------------------------------------------------------------------------------------------
+// count: what frame_walk_serial_kernel's counting pass and the host's checks behind it make of the entry
+__global__ __launch_bounds__(64) void batch_walk_count_kernel(const u8* __restrict__ src, const BatchEntryIn* __restrict__ in, BatchEntryOut* __restrict__ out, u32 nEntries,
+                                                              u32 dictID, u64 aloneAbove)
+{
+    const u32 e = blockIdx.x * 64 + threadIdx.x;
+    if (e >= nEntries) return;
+    const BatchEntryIn E = in[e];
+    BatchEntryOut r = {};
+    if (E.srcSize > aloneAbove) { r.state = kBatchAlone; out[e] = r; return; }
+    const u64 end = E.srcOff + E.srcSize;
+    const u32 maxFrames = (u32)((E.srcSize / 9 + 1) < (1u << 26) ? (E.srcSize / 9 + 1) : (1u << 26));
+    u64 pos = E.srcOff, content = 0, nBlocks = 0; u32 n = 0, err = 0, nUnsized = 0;
+    while (end - pos >= 5) {
+        ChainOut o;
+        const u32 st = chain_step(src, end, pos, o);
+        if (st == 1) { pos = o.next; continue; }
+        if (st) { err = (st == kErrPrefixUnknown && n > 0) ? (u32)kErrSrcSizeWrong : st; break; }
+        if (o.dictID && o.dictID != dictID) { err = kErrDictionaryWrong; break; }
+        if (n >= maxFrames || nBlocks + o.nbBlocks > 0xFFFFFFF0ull) { err = kErrMemoryAllocation; break; }
+        n++; nUnsized += o.unsized; nBlocks += o.nbBlocks;
+        content += o.content; pos = o.next;
+    }
+    if (!err && pos != end) err = kErrSrcSizeWrong;
+    if (err) { r.state = kBatchDone; r.result = (u64)0 - (u64)err; }
+    else if (nUnsized) r.state = kBatchAlone;
+    else if (content > E.dstCap) { r.state = kBatchDone; r.result = (u64)0 - (u64)kErrDstSizeTooSmall; }
+    else { r.state = kBatchDecode; r.result = content; r.nFrames = n; r.nBlocks = (u32)nBlocks; }
+    out[e] = r;
+}
+
+// scan (single workgroup): every decoded entry's first frame, first block and literal-scratch offset; the totals go to the status
+// words the single call's walk fills (a total beyond the lists' index range: memory_allocation for the whole call)
+__global__ __launch_bounds__(256) void batch_scan_kernel(BatchEntryOut* __restrict__ out, u32 nEntries, u32* __restrict__ status)
+{
+    __shared__ u64 shF[4], shB[4], shC[4];
+    const u32 tid = threadIdx.x, lane = lane_id(), wave = wave_id();
+    u64 carryF = 0, carryB = 0, carryC = 0;
+    for (u32 base = 0; base < nEntries; base += 256) {
+        const u32 i = base + tid;
+        u64 f = 0, b = 0, c = 0;
+        if (i < nEntries && out[i].state == kBatchDecode) { f = out[i].nFrames; b = out[i].nBlocks; c = out[i].result; }
+        u64 fi = f, bi = b, ci = c;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const u64 tf = __shfl_up(fi, d), tb = __shfl_up(bi, d), tc = __shfl_up(ci, d);
+            if ((int)lane >= d) { fi += tf; bi += tb; ci += tc; }
+        }
+        if (lane == 63) { shF[wave] = fi; shB[wave] = bi; shC[wave] = ci; }
+        __syncthreads();
+        u64 bf = carryF, bb = carryB, bc = carryC, af = 0, ab = 0, ac = 0;
+        for (u32 w = 0; w < 4; ++w) { if (w < wave) { bf += shF[w]; bb += shB[w]; bc += shC[w]; } af += shF[w]; ab += shB[w]; ac += shC[w]; }
+        if (i < nEntries) { out[i].firstFrame = (u32)(bf + fi - f); out[i].firstBlock = (u32)(bb + bi - b); out[i].scratchOff = bc + ci - c; }
+        carryF += af; carryB += ab; carryC += ac;
+        __syncthreads();
+    }
+    if (tid == 0) {
+        const bool tooMany = carryF > (1u << 26) || carryB > 0xFFFFFFF0ull;
+        status[kStFrames] = tooMany ? 0u : (u32)carryF; status[kStBlocks] = tooMany ? 0u : (u32)carryB; status[kStErr] = tooMany ? (u32)kErrMemoryAllocation : 0u;
+        status[kStTotalLo] = (u32)carryC; status[kStTotalHi] = (u32)(carryC >> 32); status[kStUnsized] = 0; status[kStUsable] = 0;
+    }
+}
+
+// emit: the same walk again, into the lists.  A frame's content goes to the entry's destination plus the frame's place inside the
+// entry; its literal scratch is the scratch prefix sum (in a single call both are the same number; here they are not)
+__global__ __launch_bounds__(64) void batch_walk_emit_kernel(const u8* __restrict__ src, const BatchEntryIn* __restrict__ in, const BatchEntryOut* __restrict__ out, u32 nEntries,
+                                                             FrameDesc* __restrict__ frames, BlockDesc* __restrict__ blocks)
+{
+    const u32 e = blockIdx.x * 64 + threadIdx.x;
+    if (e >= nEntries) return;
+    const BatchEntryOut R = out[e];
+    if (R.state != kBatchDecode) return;
+    const BatchEntryIn E = in[e];
+    const u64 end = E.srcOff + E.srcSize;
+    u64 pos = E.srcOff, dstOff = E.dstOff, scr = R.scratchOff; u32 idx = R.firstFrame, blk = R.firstBlock;
+    while (end - pos >= 5 && idx < R.firstFrame + R.nFrames) {
+        ChainOut o;
+        const u32 st = emit_frame(src, end, pos, o, idx, blk, dstOff, frames, blocks);
+        if (st >= 2) return;                                   // cannot happen: the counting pass walked the same bytes
+        if (st == 0) { frames[idx].scratchOff = scr; idx++; blk += o.nbBlocks; dstOff += o.content; scr += o.content; }
+        pos = o.next;
+    }
+}
+
+// fold: an entry's error is the smallest key of its blocks — its first failing block's first error, what the single call reports
+__global__ __launch_bounds__(64) void batch_fold_kernel(BatchEntryOut* __restrict__ out, u32 nEntries, const u64* __restrict__ keys)
+{
+    const u32 e = blockIdx.x * 64 + threadIdx.x;
+    if (e >= nEntries) return;
+    if (out[e].state != kBatchDecode) return;
+    const u32 first = out[e].firstBlock, nb = out[e].nBlocks;
+    u64 key = ~0ull;
+    for (u32 k = 0; k < nb; ++k) { const u64 v = keys[first + k]; key = v < key ? v : key; }
+    if (key != ~0ull) out[e].result = (u64)0 - (key & 0xFFFFull);
+}
+
+void launch_batch_walk_count(const u8* src, const BatchEntryIn* in, BatchEntryOut* out, u32 nEntries, u32 dictID, u64 aloneAbove, u32* status, hipStream_t stream)
+{
+    hipLaunchKernelGGL(batch_walk_count_kernel, dim3((nEntries + 63) / 64), dim3(64), 0, stream, src, in, out, nEntries, dictID, aloneAbove);
+    hipLaunchKernelGGL(batch_scan_kernel, dim3(1), dim3(256), 0, stream, out, nEntries, status);
+}
+void launch_batch_walk_emit(const u8* src, const BatchEntryIn* in, const BatchEntryOut* out, u32 nEntries, FrameDesc* frames, BlockDesc* blocks, hipStream_t stream)
+{
+    hipLaunchKernelGGL(batch_walk_emit_kernel, dim3((nEntries + 63) / 64), dim3(64), 0, stream, src, in, out, nEntries, frames, blocks);
+}
+void launch_batch_fold(BatchEntryOut* out, u32 nEntries, const u64* keys, hipStream_t stream)
+{
+    hipLaunchKernelGGL(batch_fold_kernel, dim3((nEntries + 63) / 64), dim3(64), 0, stream, out, nEntries, keys);
+}
+
 size_t decode_walk_workspace_bytes(u64 srcSize)
 {
     const u64 nSeg = (srcSize + (1ull << kSegLog) - 1) >> kSegLog;

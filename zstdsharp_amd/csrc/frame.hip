@@ -70,6 +70,33 @@ __global__ __launch_bounds__(256) void gather_kernel(const u8* __restrict__ src,
     if (tail && tid < 4) d[m.outSize - 4 + tid] = (u8)(m.checksum >> (8 * tid));
 }
 
+// ---- a batch of independent inputs (ZSTDMI_compressBatch; the trainer's samples): staging and placement ----
+// stage: chunk c = bytes [from[c], from[c] + len[c]) — any address in HBM, any alignment — to its own chunk boundary c * chunkBytes
+__global__ __launch_bounds__(256) void batch_stage_kernel(const u64* __restrict__ from, const u32* __restrict__ len, u8* __restrict__ stage, u32 chunkBytes)
+{
+    const u32 c = blockIdx.x;
+    copy_bytes(stage + (u64)c * chunkBytes, reinterpret_cast<const u8*>((uintptr_t)from[c]), len[c], threadIdx.x, 256);
+}
+
+// place (instead of scan_sizes): entry e owns the chunks [entFirst[e], entFirst[e + 1]); its frames lie one behind the other from
+// entDst[e], an offset from the one base pointer huf_encode and gather are given.  An entry whose frames exceed entCap[e] gets
+// dstSize_tooSmall and its chunks the offset `span` (the end of everything the base pointer may reach), which fails both kernels'
+// capacity comparison: nothing of it is written.  One lane per entry.
+__global__ __launch_bounds__(256) void batch_place_kernel(const ChunkMeta* __restrict__ meta, u32 nEntries, const u32* __restrict__ entFirst,
+                                                          const u64* __restrict__ entDst, const u64* __restrict__ entCap, u64 span,
+                                                          u64* __restrict__ offsets, u64* __restrict__ entSize)
+{
+    const u32 e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= nEntries) return;
+    const u32 c0 = entFirst[e], c1 = entFirst[e + 1];
+    u64 sum = 0;
+    for (u32 c = c0; c < c1; ++c) sum += meta[c].outSize;
+    const bool fits = sum <= entCap[e];
+    u64 at = entDst[e];
+    for (u32 c = c0; c < c1; ++c) { offsets[c] = fits ? at : span; at += meta[c].outSize; }
+    entSize[e] = fits ? sum : (u64)0 - (u64)kErrDstSizeTooSmall;
+}
+
 // ---- XXH64 (seed 0): 4 lanes per chunk, one per accumulator ----
 constexpr u64 P1 = 0x9E3779B185EBCA87ULL, P2 = 0xC2B2AE3D27D4EB4FULL, P3 = 0x165667B19E3779F9ULL,
               P4 = 0x85EBCA77C2B2AE63ULL, P5 = 0x27D4EB2F165667C5ULL;
@@ -78,15 +105,16 @@ __device__ __forceinline__ u64 xxh_round(u64 acc, u64 in) { acc += in * P2; acc 
 __device__ __forceinline__ u64 xxh_merge(u64 acc, u64 v) { acc ^= xxh_round(0, v); return acc * P1 + P4; }
 
 // (one frame = frameBlocks chunks of chunkBytes; the checksum is filed with the frame's last block, which carries it)
+// chunkLens (optional; single-block frames only): chunk c holds chunkLens[c] bytes at c * chunkBytes (a batch of independent inputs)
 __global__ __launch_bounds__(256) void xxh64_kernel(const u8* __restrict__ src, u64 srcSize, ChunkMeta* __restrict__ meta, u32 nChunks, u32 chunkBytes,
-                                                    u32 frameBlocks)
+                                                    u32 frameBlocks, const u32* __restrict__ chunkLens)
 {
     const u32 t = blockIdx.x * 256 + threadIdx.x;
     const u32 f = t >> 2, j = t & 3;
     if ((u64)f * frameBlocks >= nChunks) return;           // whole groups of 4 lanes leave together
     const u64 frameBytes = (u64)frameBlocks * chunkBytes;
     const u64 base = (u64)f * frameBytes;
-    const u32 n = (u32)((srcSize - base) < frameBytes ? (srcSize - base) : frameBytes);
+    const u32 n = chunkLens ? chunkLens[f] : (u32)((srcSize - base) < frameBytes ? (srcSize - base) : frameBytes);
     const u32 c = (f + 1) * frameBlocks <= nChunks ? (f + 1) * frameBlocks - 1 : nChunks - 1;
     const u8* p = src + base;
     u64 h;
@@ -118,11 +146,21 @@ void launch_gather(const u8* src, u64 srcSize, const u8* slots, const ChunkMeta*
 {
     hipLaunchKernelGGL(gather_kernel, dim3(nChunks), dim3(256), 0, stream, src, srcSize, slots, meta, offsets, dst, dstCapacity, chunkBytes);
 }
-void launch_xxh64(const u8* src, u64 srcSize, ChunkMeta* meta, u32 nChunks, u32 chunkBytes, u32 frameBlocks, hipStream_t stream)
+void launch_xxh64(const u8* src, u64 srcSize, ChunkMeta* meta, u32 nChunks, u32 chunkBytes, u32 frameBlocks, hipStream_t stream, const u32* chunkLens)
 {
     if (!frameBlocks) frameBlocks = 1;
+    if (frameBlocks != 1) chunkLens = nullptr;
     const u32 nFrames = (nChunks + frameBlocks - 1) / frameBlocks;
-    hipLaunchKernelGGL(xxh64_kernel, dim3((nFrames * 4 + 255) / 256), dim3(256), 0, stream, src, srcSize, meta, nChunks, chunkBytes, frameBlocks);
+    hipLaunchKernelGGL(xxh64_kernel, dim3((nFrames * 4 + 255) / 256), dim3(256), 0, stream, src, srcSize, meta, nChunks, chunkBytes, frameBlocks, chunkLens);
+}
+void launch_batch_stage(const u64* from, const u32* len, u8* stage, u32 nChunks, u32 chunkBytes, hipStream_t stream)
+{
+    hipLaunchKernelGGL(batch_stage_kernel, dim3(nChunks), dim3(256), 0, stream, from, len, stage, chunkBytes);
+}
+void launch_batch_place(const ChunkMeta* meta, u32 nEntries, const u32* entFirst, const u64* entDst, const u64* entCap, u64 span, u64* offsets, u64* entSize,
+                        hipStream_t stream)
+{
+    hipLaunchKernelGGL(batch_place_kernel, dim3((nEntries + 255) / 256), dim3(256), 0, stream, meta, nEntries, entFirst, entDst, entCap, span, offsets, entSize);
 }
 
 } // namespace zmi

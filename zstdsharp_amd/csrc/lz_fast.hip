@@ -841,9 +841,9 @@ __global__ __launch_bounds__(1024) void lz_kernel(const u8* __restrict__ src, u6
     if (DICT && frameBlocks && !indep) { const u64 back = (u64)bf * cb; prefixLen = back < hist ? (u32)back : hist; prefix = in - prefixLen; }
     if (DICT && indep && bf) prefixLen = 0;
     const u32 lowLimit = DICT ? hist - prefixLen : 0u;
-    // chunkLens (optional, dictionary instantiations): chunk c holds chunkLens[c] <= cb bytes at c * cb (a batch of independent
-    // inputs, each staged at a chunk boundary: the trainer's per-sample compression); null = the call's input cut every cb bytes
-    const u32 nData = (DICT && chunkLens) ? chunkLens[c] : (u32)((srcSize - base) < cb ? (srcSize - base) : cb);
+    // chunkLens (optional): chunk c holds chunkLens[c] <= cb bytes at c * cb (a batch of independent inputs, each staged at a
+    // chunk boundary: ZSTDMI_compressBatch, the trainer's per-sample compression); null = the call's input cut every cb bytes
+    const u32 nData = chunkLens ? chunkLens[c] : (u32)((srcSize - base) < cb ? (srcSize - base) : cb);
     const u32 n = hist + nData;                            // end of the data in LDS
 #ifdef ZMI_LZ_STAMPS
     unsigned long long stampAcc[14] = {0,0,0,0,0,0,0,0,0,0,0,0,0,0}; unsigned long long stampLast = __builtin_amdgcn_s_memtime();
@@ -911,7 +911,8 @@ __global__ __launch_bounds__(1024) void lz_kernel(const u8* __restrict__ src, u6
     if (kPrefetch) {
         const u32 cN = cNext;
         const u8* __restrict__ inN = src + (u64)cN * kChunkSize;
-        if (cN < nChunks && srcSize - (u64)cN * kChunkSize >= kChunkSize && (((uintptr_t)inN) & 15) == 0) {      // uniform
+        // (a batch's short chunk is staged directly: the zero fill behind its data must not meet the prefetched stores)
+        if (cN < nChunks && srcSize - (u64)cN * kChunkSize >= kChunkSize && (((uintptr_t)inN) & 15) == 0 && (!chunkLens || chunkLens[cN] >= kChunkSize)) {      // uniform
             const uint4* n4 = reinterpret_cast<const uint4*>(inN);
             pf0 = n4[tid]; pf1 = n4[tid + kTile]; pf2 = n4[tid + 2 * kTile]; pf3 = n4[tid + 3 * kTile];
             pfValid = true;
@@ -1550,7 +1551,7 @@ __global__ __launch_bounds__(1024) void lz_region_kernel(const u8* __restrict__ 
     if (DICT && frameBlocks && !indep) { const u64 back = (u64)bf * cb; prefixLen = back < hist ? (u32)back : hist; prefix = in - prefixLen; }
     if (DICT && indep && bf) prefixLen = 0;
     const u32 lowLimit = DICT ? hist - prefixLen : 0u;
-    const u32 nData = (DICT && chunkLens) ? chunkLens[c] : (u32)((srcSize - base) < cb ? (srcSize - base) : cb);
+    const u32 nData = chunkLens ? chunkLens[c] : (u32)((srcSize - base) < cb ? (srcSize - base) : cb);
     const u32 n = hist + nData;
     {   // the image [lowLimit, n): history (or dictionary tail) + block.  Cross-chunk history is one contiguous piece of the input
         const bool onePiece = !DICT || (frameBlocks != 0 && !indep);

@@ -450,23 +450,9 @@ __global__ __launch_bounds__(256) void seq_stats_kernel(const Seq* __restrict__ 
     for (u32 i = tid; i < 377; i += 256) if (h[i]) atomicAdd(&stats[i], h[i]);
 }
 
-// the inputs of a batch of independent samples, each at its own chunk boundary: chunk c = bytes [from[c], from[c] + len[c]) of src
-__global__ __launch_bounds__(256) void sample_scatter_kernel(const u8* __restrict__ src, const u64* __restrict__ from, const u32* __restrict__ len,
-                                                             u8* __restrict__ stage, u32 chunkBytes)
-{
-    const u32 c = blockIdx.x;
-    const u8* __restrict__ in = src + from[c];
-    u8* __restrict__ out = stage + (u64)c * chunkBytes;
-    for (u32 i = threadIdx.x; i < len[c]; i += 256) out[i] = in[i];
-}
-
 void launch_seq_stats(const Seq* seqs, const u8* lits, const ChunkMeta* meta, u32 nChunks, const u8* src, u32 chunkBytes, u32* stats, hipStream_t stream)
 {
     hipLaunchKernelGGL(seq_stats_kernel, dim3(nChunks), dim3(256), 0, stream, seqs, lits, meta, nChunks, src, chunkBytes, stats);
-}
-void launch_sample_scatter(const u8* src, const u64* from, const u32* len, u8* stage, u32 nChunks, u32 chunkBytes, hipStream_t stream)
-{
-    hipLaunchKernelGGL(sample_scatter_kernel, dim3(nChunks), dim3(256), 0, stream, src, from, len, stage, chunkBytes);
 }
 
 } // namespace zmi

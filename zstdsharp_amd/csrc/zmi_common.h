@@ -142,9 +142,23 @@ struct BlockDesc {
 struct SeqRec { u32 lo, hi; };
 constexpr u32 kRecOffMax = (1u << 29) - 1;
 
+// A batch of independent entries (ZSTDMI_decompressBatch): what the host says of entry e, and what the batch walk finds in it.
+// Offsets are relative to one base pointer each for sources and destinations (the lowest of the call); the lists of all entries
+// are one FrameDesc / BlockDesc array, entry e's frames and blocks side by side from firstFrame / firstBlock.
+struct BatchEntryIn { u64 srcOff, srcSize, dstOff, dstCap; };
+enum : u32 { kBatchDecode = 0, kBatchDone = 1, kBatchAlone = 2 };
+struct BatchEntryOut {
+    u64 result;         // the entry's answer: its content size, or an error in the size_t convention (kBatchAlone: not yet known)
+    u64 scratchOff;     // literal scratch of its first frame (prefix sum of the content sizes over the entries that are decoded)
+    u32 firstFrame, firstBlock, nFrames, nBlocks;
+    u32 state;          // kBatchDecode: its frames are in the lists; kBatchDone: `result` is final (header-stage error, dstSize_tooSmall);
+    u32 pad;            // kBatchAlone: the single-call path decodes it afterwards (a frame without a content size, a very large entry)
+};
+
 // status words shared by the decoder's kernels and the host
 enum : u32 { kStFrames = 0, kStErr = 1, kStTotalLo = 2, kStTotalHi = 3, kStUsable = 4, kStUnsized = 5, kStBlocks = 6, kStSeqLo = 8, kStSeqHi = 9,
              kStErrKeyLo = 10, kStErrKeyHi = 11, kStActualLo = 12, kStActualHi = 13,
+             kStBlockKeysLo = 7, kStBlockKeysHi = 15,   // a batch call: address of one error key per block (report_error files there too); 0 = none
              kStOriginFrames = 14,      // frames the origin path took (origin_select_kernel)
              kStOriginLo = 16, kStOriginHi = 17,        // entries of the origin array handed out so far (u64)
              kStOriginChanged = 18,     // .. 18 + kOriginRounds: round r of the pointer jumping changed something

@@ -14,6 +14,9 @@ __device__ __forceinline__ void report_error(u32* status, u64 blockIdx, u32 stag
 {
     const unsigned long long key = ((unsigned long long)blockIdx << 24) | ((unsigned long long)stage << 16) | err;
     atomicMin(reinterpret_cast<unsigned long long*>(status + kStErrKeyLo), key);
+    // a batch call keeps a key per block beside the global one: an entry's error is the smallest key of ITS blocks (batch_fold_kernel)
+    const unsigned long long perBlock = (unsigned long long)status[kStBlockKeysLo] | ((unsigned long long)status[kStBlockKeysHi] << 32);
+    if (perBlock) atomicMin(reinterpret_cast<unsigned long long*>(perBlock) + blockIdx, key);
 }
 
 struct FrameHeader { u64 contentSize; u64 windowSize; u32 headerSize; u32 checksum; u32 dictID; u32 err; };

@@ -12,6 +12,7 @@
 #include <mutex>
 #include <thread>
 #include <new>
+#include <functional>
 #include "zmi_common.h"
 #include "zmi_cparams.h"
 #include "../../include/zstd_mi355x.h"
@@ -31,7 +32,10 @@ void launch_seq_encode(Seq* seqs, ChunkMeta* meta, u8* slots, u32 nChunks, u32 s
 void launch_scan_sizes(const ChunkMeta* meta, u32 nChunks, u64* offsets, u64* total, hipStream_t stream);
 void launch_gather(const u8* src, u64 srcSize, const u8* slots, const ChunkMeta* meta, const u64* offsets, u8* dst, u64 dstCapacity,
                    u32 nChunks, u32 chunkBytes, hipStream_t stream);
-void launch_xxh64(const u8* src, u64 srcSize, ChunkMeta* meta, u32 nChunks, u32 chunkBytes, u32 frameBlocks, hipStream_t stream);
+void launch_xxh64(const u8* src, u64 srcSize, ChunkMeta* meta, u32 nChunks, u32 chunkBytes, u32 frameBlocks, hipStream_t stream, const u32* chunkLens = nullptr);
+void launch_batch_stage(const u64* from, const u32* len, u8* stage, u32 nChunks, u32 chunkBytes, hipStream_t stream);
+void launch_batch_place(const ChunkMeta* meta, u32 nEntries, const u32* entFirst, const u64* entDst, const u64* entCap, u64 span, u64* offsets, u64* entSize,
+                        hipStream_t stream);
 // long-distance matching (ldm.hip)
 size_t ldm_small_bytes(u64 n);
 size_t ldm_big_bytes(u64 nSplits);
@@ -45,8 +49,10 @@ void launch_frame_walk_count(const u8* src, u64 srcSize, u32 maxFrames, u32* sta
 void launch_frame_walk_emit(const u8* src, u64 srcSize, FrameDesc* frames, BlockDesc* blocks, u8* walkWs, hipStream_t stream);
 void launch_frame_walk_serial(const u8* src, u64 srcSize, FrameDesc* frames, BlockDesc* blocks, u32 maxFrames, u32* status, u32 dictID, u32 emit,
                               hipStream_t stream);
+void launch_batch_walk_count(const u8* src, const BatchEntryIn* in, BatchEntryOut* out, u32 nEntries, u32 dictID, u64 aloneAbove, u32* status, hipStream_t stream);
+void launch_batch_walk_emit(const u8* src, const BatchEntryIn* in, const BatchEntryOut* out, u32 nEntries, FrameDesc* frames, BlockDesc* blocks, hipStream_t stream);
+void launch_batch_fold(BatchEntryOut* out, u32 nEntries, const u64* keys, hipStream_t stream);
 void launch_seq_stats(const Seq* seqs, const u8* lits, const ChunkMeta* meta, u32 nChunks, const u8* src, u32 chunkBytes, u32* stats, hipStream_t stream);
-void launch_sample_scatter(const u8* src, const u64* from, const u32* len, u8* stage, u32 nChunks, u32 chunkBytes, hipStream_t stream);
 void launch_dict_parse(const u8* dict, u32 dictSize, DictInfo* out, hipStream_t stream);
 void launch_block_prepass(const u8* src, FrameDesc* frames, BlockDesc* blocks, u32 nFrames, u32 nBlocks, u32 haveDict, u32 earlyLiterals, u32* status, hipStream_t stream);
 void launch_seq_decode(const u8* src, const FrameDesc* frames, BlockDesc* blocks, u32 nBlocks, SeqRec* recs, u32* status,
@@ -172,6 +178,8 @@ struct ZSTD_CCtx_s {
     // dealt to them in contiguous shares (compress_multi).  Empty = the context's own device only.
     std::vector<ZSTD_CCtx_s*> workers;
     DevBuf gatherIn, gatherOut;     // a many-range plan: the ranges of a kind side by side, and their output (compress_plan)
+    DevBuf batchStage, batchTab;    // a batch of independent entries: their chunks at chunk boundaries, and the pass's tables (compress_entries)
+    int lastBatchAlone = 0;         // entries of the last ZSTDMI_compressBatch that went through the single-call path (debug hook)
 };
 // History per chunk lives in LDS beside the chunk: up to 32 KiB of dictionary in front of 32 KiB chunks, or up to 60 KiB when
 // the whole input fits behind it in one chunk (small records, the usual dictionary case).
@@ -196,6 +204,8 @@ struct ZSTD_DCtx_s {
     bool lastWalkSerial = false; // the last call's frames were listed by the serial walk (ZSTDMI_debugLastWalkSerial)
     int execWaves = 0;          // ZSTDMI_DCtx_setExecWaves: waves per frame in exec_matches, 0 = by the number of frames
     DevBuf frames, blocks, recs, status, scratch, walkWs, slowFlags, stageSrc, stageDst, origin, originList;
+    DevBuf batchIn, batchOut, blockKeys;    // ZSTDMI_decompressBatch: the entries' table, what the batch walk made of them, one error key per block
+    int lastBatchAlone = 0;     // entries of the last ZSTDMI_decompressBatch that were decoded by the single-call path (debug hook)
     int originMode = 0;         // ZSTDMI_DCtx_setLongFrames: 0 = by cost (see decompress_device), 1 = never, 2 = every frame of 1 MiB or more
     StageTimer timer;
     // streaming adapter (ZSTD_decompressStream): whole frames are collected on the host, decoded in batches
@@ -696,7 +706,7 @@ size_t ZSTD_freeCCtx(ZSTD_CCtx* c)
         (void)hipSetDevice(c->device);
         if (c->ownStream) (void)hipStreamSynchronize(c->ownStream);
         c->seqs.release(); c->lits.release(); c->meta.release(); c->tables.release(); c->slots.release(); c->cand.release(); c->probe.release();
-        c->gatherIn.release(); c->gatherOut.release(); c->ldmSmall.release(); c->ldmBig.release(); c->offsets.release(); c->total.release(); c->stageSrc.release(); c->stageDst.release(); c->dict.release(); c->dictFullDev.release(); c->dictInfoDev.release();
+        c->gatherIn.release(); c->gatherOut.release(); c->batchStage.release(); c->batchTab.release(); c->ldmSmall.release(); c->ldmBig.release(); c->offsets.release(); c->total.release(); c->stageSrc.release(); c->stageDst.release(); c->dict.release(); c->dictFullDev.release(); c->dictInfoDev.release();
         c->timer.destroy();
         if (c->ownStream) (void)hipStreamDestroy(c->ownStream);
     }
@@ -906,7 +916,7 @@ size_t ZSTD_freeDCtx(ZSTD_DCtx* d)
     if (d->deviceOk) {
         (void)hipSetDevice(d->device);
         if (d->ownStream) (void)hipStreamSynchronize(d->ownStream);
-        d->frames.release(); d->blocks.release(); d->recs.release(); d->status.release(); d->scratch.release(); d->walkWs.release(); d->slowFlags.release(); d->stageSrc.release(); d->stageDst.release(); d->dict.release(); d->dictInfoDev.release(); d->origin.release(); d->originList.release();
+        d->frames.release(); d->blocks.release(); d->recs.release(); d->status.release(); d->scratch.release(); d->walkWs.release(); d->slowFlags.release(); d->stageSrc.release(); d->stageDst.release(); d->dict.release(); d->dictInfoDev.release(); d->origin.release(); d->originList.release(); d->batchIn.release(); d->batchOut.release(); d->blockKeys.release();
         d->timer.destroy();
         if (d->aux) { (void)hipStreamSynchronize(d->aux); (void)hipStreamDestroy(d->aux); }
         if (d->auxDone) (void)hipEventDestroy(d->auxDone);
@@ -1079,55 +1089,35 @@ static size_t dctx_sync_dictionary(ZSTD_DCtx* d)
     return 0;
 }
 
-// The decompress pipeline over device-resident buffers.  Two host round trips size the work lists (frames + blocks after the
-// counting walk, sequence records after the block pre-pass); everything else is one launch sequence:
-//   walk (count) | walk (emit) -> block_parse -> block_link -> seq_scan | seq_decode -> block_offsets [-> frame_rescan]
-//   -> decode_literals -> place_literals -> exec_matches
-static size_t decompress_device(ZSTD_DCtx* d, u8* d_dst, size_t dstCapacity, const u8* d_src, size_t srcSize)
+// the loaded dictionary as the decode kernels take it
+struct DecodeDict { bool fmt; const u8* dictFull; const DictInfo* dinfo; const u8* dictContent; u32 dictContentSize, dictID; };
+static DecodeDict decode_dict(const ZSTD_DCtx* d)
+{
+    DecodeDict k;
+    k.fmt = d->dictFormatted && !d->dictHost.empty();
+    k.dictFull = k.fmt ? (const u8*)d->dict.p : nullptr;
+    k.dinfo = k.fmt ? (const DictInfo*)d->dictInfoDev.p : nullptr;
+    k.dictContent = d->dictHost.empty() ? nullptr : (const u8*)d->dict.p + (k.fmt ? d->info.contentOff : 0u);
+    k.dictContentSize = d->dictHost.empty() ? 0u : (k.fmt ? d->info.contentSize : (u32)d->dictHost.size());
+    k.dictID = k.fmt ? d->info.dictID : 0u;
+    return k;
+}
+
+// Everything behind the frame walk: the lists (d->frames, d->blocks; offsets relative to d_src and d_dst) through block_prepass,
+// seq_decode, block_offsets, the literal decoder, the origin path and exec_matches.  `tail` enqueues what the caller wants read back
+// with the last status read (-> false: failed); st = the status words after it.  -> 0 or the error of the whole run.
+static size_t decode_lists(ZSTD_DCtx* d, const DecodeDict& dd, u8* d_dst, const u8* d_src, u32 nFrames, u32 nBlocks, u32 nUnsized, size_t dstCapacity, u32* st, const std::function<bool()>& tail)
 {
     hipStream_t s = d->stream;
-    if (srcSize == 0) return 0;
-    // a frame is at least 9 bytes; our own streams hold one per 64 KiB, foreign ones usually far fewer
-    const u32 maxFrames = (u32)((srcSize / 9 + 1) < (1u << 26) ? (srcSize / 9 + 1) : (1u << 26));
-    if (!d->status.ensure(kStWords * sizeof(u32)) || !d->walkWs.ensure(decode_walk_workspace_bytes(srcSize))) return ZERR(kErrMemoryAllocation);
     u32* status = (u32*)d->status.p;
-    { const size_t e = dctx_sync_dictionary(d); if (isErr(e)) return e; }
-    const bool fmt = d->dictFormatted && !d->dictHost.empty();
-    const u8* const dictFull = fmt ? (const u8*)d->dict.p : nullptr;
-    const DictInfo* const dinfo = fmt ? (const DictInfo*)d->dictInfoDev.p : nullptr;
-    const u8* const dictContent = d->dictHost.empty() ? nullptr : (const u8*)d->dict.p + (fmt ? d->info.contentOff : 0u);
-    const u32 dictContentSize = d->dictHost.empty() ? 0u : (fmt ? d->info.contentSize : (u32)d->dictHost.size());
-    const u32 dictID = fmt ? d->info.dictID : 0u;
-    auto read_status = [&](u32* st) -> bool {
-        if (hipMemcpyAsync(st, status, kStWords * sizeof(u32), hipMemcpyDeviceToHost, s) != hipSuccess) return false;
+    FrameDesc* frames = (FrameDesc*)d->frames.p; BlockDesc* blocks = (BlockDesc*)d->blocks.p;
+    const bool fmt = dd.fmt; const u8* const dictFull = dd.dictFull; const DictInfo* const dinfo = dd.dinfo;
+    const u8* const dictContent = dd.dictContent; const u32 dictContentSize = dd.dictContentSize;
+    auto read_status = [&](u32* w) -> bool {
+        if (hipMemcpyAsync(w, status, kStWords * sizeof(u32), hipMemcpyDeviceToHost, s) != hipSuccess) return false;
         if (hipStreamSynchronize(s) != hipSuccess) { (void)hipGetLastError(); return false; }
         return true;
     };
-    d->timer.begin(s);
-    {   // error key = "none" (all ones); everything else zero
-        u32 init[kStWords] = {}; init[kStErrKeyLo] = 0xFFFFFFFFu; init[kStErrKeyHi] = 0xFFFFFFFFu;
-        if (hipMemcpyAsync(status, init, sizeof init, hipMemcpyHostToDevice, s) != hipSuccess) return ZERR(kErrGeneric);
-    }
-    u32 st[kStWords] = {};
-    launch_frame_walk_count(d_src, srcSize, maxFrames, status, (u8*)d->walkWs.p, s);
-    if (!read_status(st)) return ZERR(kErrGeneric);
-    const bool serialWalk = !st[kStUsable];
-    d->lastWalkSerial = serialWalk;
-    if (serialWalk) {   // the segment links did not close: take the exact serial walk (it also yields the reference's error code)
-        launch_frame_walk_serial(d_src, srcSize, nullptr, nullptr, maxFrames, status, dictID, 0, s);
-        if (!read_status(st)) return ZERR(kErrGeneric);
-    }
-    if (st[kStErr]) return ZERR(st[kStErr]);
-    const u32 nFrames = st[kStFrames], nBlocks = st[kStBlocks], nUnsized = st[kStUnsized];
-    const u64 total = (u64)st[kStTotalLo] | ((u64)st[kStTotalHi] << 32);       // content sizes (bounds for frames without one)
-    if (!nUnsized && total > dstCapacity) return ZERR(kErrDstSizeTooSmall);
-    if (nFrames == 0) { d->timer.finish(); return 0; }
-    if (!d->frames.ensure((size_t)nFrames * sizeof(FrameDesc)) || !d->blocks.ensure((size_t)nBlocks * sizeof(BlockDesc) + 64) ||
-        !d->scratch.ensure((size_t)total + (size_t)nFrames * kLitSkew + 256) || !d->slowFlags.ensure((size_t)nBlocks + 64)) return ZERR(kErrMemoryAllocation);
-    FrameDesc* frames = (FrameDesc*)d->frames.p; BlockDesc* blocks = (BlockDesc*)d->blocks.p;
-    if (serialWalk) launch_frame_walk_serial(d_src, srcSize, frames, blocks, maxFrames, status, dictID, 1, s);
-    else            launch_frame_walk_emit(d_src, srcSize, frames, blocks, (u8*)d->walkWs.p, s);
-    d->timer.mark("frame_walk", s);
     // The literal decoder and seq_decode need nothing of each other (a block's Huffman streams and its FSE chains).  With few
     // blocks neither fills the chip — both are serial chains per block — so below kOverlapBlocks the literal decoder may run beside
     // seq_decode on a stream of its own (`early`: block_link then lets it write only the outputs whose place is known by now).
@@ -1207,12 +1197,147 @@ static size_t decompress_device(ZSTD_DCtx* d, u8* d_dst, size_t dstCapacity, con
         launch_origin_gather(frames, list, originCap, longest, status, origin, d_dst, dictContent, s);    d->timer.mark("origin_gather", s);
     }
     launch_exec_matches(d_src, d_dst, frames, blocks, nFrames, recs, status, dictContent, dictContentSize, s, execWaves);  d->timer.mark("exec_matches", s);
+    if (!tail()) return ZERR(kErrGeneric);
     if (!read_status(st)) return ZERR(kErrGeneric);
+    return 0;
+}
+
+// The decompress pipeline over device-resident buffers.  Two host round trips size the work lists (frames + blocks after the
+// counting walk, sequence records after the block pre-pass); everything else is one launch sequence:
+//   walk (count) | walk (emit) -> block_parse -> block_link -> seq_scan | seq_decode -> block_offsets [-> frame_rescan]
+//   -> decode_literals -> place_literals -> exec_matches
+static size_t decompress_device(ZSTD_DCtx* d, u8* d_dst, size_t dstCapacity, const u8* d_src, size_t srcSize)
+{
+    hipStream_t s = d->stream;
+    if (srcSize == 0) return 0;
+    // a frame is at least 9 bytes; our own streams hold one per 64 KiB, foreign ones usually far fewer
+    const u32 maxFrames = (u32)((srcSize / 9 + 1) < (1u << 26) ? (srcSize / 9 + 1) : (1u << 26));
+    if (!d->status.ensure(kStWords * sizeof(u32)) || !d->walkWs.ensure(decode_walk_workspace_bytes(srcSize))) return ZERR(kErrMemoryAllocation);
+    u32* status = (u32*)d->status.p;
+    { const size_t e = dctx_sync_dictionary(d); if (isErr(e)) return e; }
+    const DecodeDict dd = decode_dict(d);
+    const u32 dictID = dd.dictID;
+    auto read_status = [&](u32* st) -> bool {
+        if (hipMemcpyAsync(st, status, kStWords * sizeof(u32), hipMemcpyDeviceToHost, s) != hipSuccess) return false;
+        if (hipStreamSynchronize(s) != hipSuccess) { (void)hipGetLastError(); return false; }
+        return true;
+    };
+    d->timer.begin(s);
+    {   // error key = "none" (all ones); everything else zero
+        u32 init[kStWords] = {}; init[kStErrKeyLo] = 0xFFFFFFFFu; init[kStErrKeyHi] = 0xFFFFFFFFu;
+        if (hipMemcpyAsync(status, init, sizeof init, hipMemcpyHostToDevice, s) != hipSuccess) return ZERR(kErrGeneric);
+    }
+    u32 st[kStWords] = {};
+    launch_frame_walk_count(d_src, srcSize, maxFrames, status, (u8*)d->walkWs.p, s);
+    if (!read_status(st)) return ZERR(kErrGeneric);
+    const bool serialWalk = !st[kStUsable];
+    d->lastWalkSerial = serialWalk;
+    if (serialWalk) {   // the segment links did not close: take the exact serial walk (it also yields the reference's error code)
+        launch_frame_walk_serial(d_src, srcSize, nullptr, nullptr, maxFrames, status, dictID, 0, s);
+        if (!read_status(st)) return ZERR(kErrGeneric);
+    }
+    if (st[kStErr]) return ZERR(st[kStErr]);
+    const u32 nFrames = st[kStFrames], nBlocks = st[kStBlocks], nUnsized = st[kStUnsized];
+    const u64 total = (u64)st[kStTotalLo] | ((u64)st[kStTotalHi] << 32);       // content sizes (bounds for frames without one)
+    if (!nUnsized && total > dstCapacity) return ZERR(kErrDstSizeTooSmall);
+    if (nFrames == 0) { d->timer.finish(); return 0; }
+    if (!d->frames.ensure((size_t)nFrames * sizeof(FrameDesc)) || !d->blocks.ensure((size_t)nBlocks * sizeof(BlockDesc) + 64) ||
+        !d->scratch.ensure((size_t)total + (size_t)nFrames * kLitSkew + 256) || !d->slowFlags.ensure((size_t)nBlocks + 64)) return ZERR(kErrMemoryAllocation);
+    FrameDesc* frames = (FrameDesc*)d->frames.p; BlockDesc* blocks = (BlockDesc*)d->blocks.p;
+    if (serialWalk) launch_frame_walk_serial(d_src, srcSize, frames, blocks, maxFrames, status, dictID, 1, s);
+    else            launch_frame_walk_emit(d_src, srcSize, frames, blocks, (u8*)d->walkWs.p, s);
+    d->timer.mark("frame_walk", s);
+    { const size_t e = decode_lists(d, dd, d_dst, d_src, nFrames, nBlocks, nUnsized, dstCapacity, st, [] { return true; }); if (isErr(e)) return e; }
     d->timer.finish();
     if (st[kStErrKeyLo] != 0xFFFFFFFFu || st[kStErrKeyHi] != 0xFFFFFFFFu) return ZERR(st[kStErrKeyLo] & 0xFFFFu);   // the first failing block's first error
     if (st[kStErr]) return ZERR(st[kStErr]);                  // regenerated sizes of unsized frames exceed the destination
     if (nUnsized) return (size_t)((u64)st[kStActualLo] | ((u64)st[kStActualHi] << 32));
     return (size_t)total;
+}
+
+// ---- a batch of independent entries, each decoded as the single call would decode it alone (ZSTDMI_decompressBatch) ----
+// The decoder's unit of parallelism is the block and its lists hold 64-bit offsets, so n entries are ONE run of the pipeline: the
+// batch walk (one lane per entry, the exact serial walk) lists every entry's frames and blocks side by side, with offsets relative to
+// the lowest source and the lowest destination pointer of the call, and block_prepass .. exec_matches run once over the merged lists.
+// Errors stay with their entry: header-stage errors and dstSize_tooSmall are found by the walk (such an entry emits no frames), later
+// ones are filed per block (report_error, kStBlockKeysLo) and folded per entry.  The host synchronises as often as for one single
+// call.  An entry that holds a frame without a content size (where its output goes is known only after decoding: frame_rescan is
+// global by construction) or more than kBatchAloneAbove compressed bytes (one lane walks an entry's block headers) is decoded alone
+// afterwards by decompress_device, and counted.
+constexpr u64 kBatchAloneAbove = (u64)4 << 20;
+static size_t decompress_batch_impl(ZSTD_DCtx* d, const void* const* srcs, const size_t* srcSizes, size_t n, void* const* dsts, const size_t* dstCapacities, size_t* dstSizes)
+{
+    if (!d) return ZERR(kErrGeneric);
+    if (n == 0) { d->lastBatchAlone = 0; return 0; }
+    if (!srcs || !srcSizes || !dsts || !dstCapacities || !dstSizes) return ZERR(kErrGeneric);
+    if (n > 0xFFFFFFF0ull) return ZERR(kErrMemoryAllocation);
+    size_t e = dctx_bind(d); if (isErr(e)) return e;
+    if (d->workers.size() > 1) return ZERR(kErrParameterUnsupported);
+    d->lastBatchAlone = 0;
+    e = dctx_sync_dictionary(d); if (isErr(e)) return e;
+    hipStream_t s = d->stream;
+    const DecodeDict dd = decode_dict(d);
+    // one base pointer each: the lowest source, the lowest destination
+    uintptr_t loS = ~(uintptr_t)0, loD = ~(uintptr_t)0, hiD = 0;
+    for (size_t i = 0; i < n; i++) {
+        if (srcSizes[i] && srcs[i] && (uintptr_t)srcs[i] < loS) loS = (uintptr_t)srcs[i];
+        if (dsts[i]) { const uintptr_t p = (uintptr_t)dsts[i]; if (p < loD) loD = p; if (p + dstCapacities[i] > hiD) hiD = p + dstCapacities[i]; }
+    }
+    if (loS == ~(uintptr_t)0) loS = 0;
+    if (loD == ~(uintptr_t)0) loD = 0;
+    std::vector<BatchEntryIn> hIn(n);
+    for (size_t i = 0; i < n; i++) {
+        const bool noSrc = srcSizes[i] && !srcs[i];           // (the single call: srcSize_wrong, below)
+        hIn[i].srcOff = (srcSizes[i] && !noSrc) ? (u64)((uintptr_t)srcs[i] - loS) : 0;
+        hIn[i].srcSize = noSrc ? 0 : (u64)srcSizes[i];
+        hIn[i].dstOff = dsts[i] ? (u64)((uintptr_t)dsts[i] - loD) : 0;
+        hIn[i].dstCap = dsts[i] ? (u64)dstCapacities[i] : 0;
+    }
+    if (!d->status.ensure(kStWords * sizeof(u32)) || !d->batchIn.ensure(n * sizeof(BatchEntryIn)) || !d->batchOut.ensure(n * sizeof(BatchEntryOut))) return ZERR(kErrMemoryAllocation);
+    u32* status = (u32*)d->status.p;
+    const u8* const srcBase = (const u8*)loS; u8* const dstBase = (u8*)loD;
+    const BatchEntryIn* dIn = (const BatchEntryIn*)d->batchIn.p; BatchEntryOut* dOut = (BatchEntryOut*)d->batchOut.p;
+    std::vector<BatchEntryOut> hOut(n);
+    u32 init[kStWords] = {}; init[kStErrKeyLo] = 0xFFFFFFFFu; init[kStErrKeyHi] = 0xFFFFFFFFu;
+    u32 st[kStWords] = {};
+    d->timer.begin(s);
+    if (hipMemcpyAsync(status, init, sizeof init, hipMemcpyHostToDevice, s) != hipSuccess ||
+        hipMemcpyAsync(d->batchIn.p, hIn.data(), n * sizeof(BatchEntryIn), hipMemcpyHostToDevice, s) != hipSuccess) return ZERR(kErrGeneric);
+    launch_batch_walk_count(srcBase, dIn, dOut, (u32)n, dd.dictID, kBatchAloneAbove, status, s);
+    if (hipMemcpyAsync(hOut.data(), dOut, n * sizeof(BatchEntryOut), hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipMemcpyAsync(st, status, sizeof st, hipMemcpyDeviceToHost, s) != hipSuccess) return ZERR(kErrGeneric);
+    if (hipStreamSynchronize(s) != hipSuccess) { (void)hipGetLastError(); return ZERR(kErrGeneric); }
+    if (st[kStErr]) return ZERR(st[kStErr]);
+    const u32 nFrames = st[kStFrames], nBlocks = st[kStBlocks];
+    const u64 total = (u64)st[kStTotalLo] | ((u64)st[kStTotalHi] << 32);
+    u32 keyWords[2] = {0, 0};
+    if (nFrames) {
+        if (!d->frames.ensure((size_t)nFrames * sizeof(FrameDesc)) || !d->blocks.ensure((size_t)nBlocks * sizeof(BlockDesc) + 64) ||
+            !d->scratch.ensure((size_t)total + (size_t)nFrames * kLitSkew + 256) || !d->slowFlags.ensure((size_t)nBlocks + 64) ||
+            !d->blockKeys.ensure((size_t)nBlocks * sizeof(u64) + 8)) return ZERR(kErrMemoryAllocation);
+        keyWords[0] = (u32)(uintptr_t)d->blockKeys.p; keyWords[1] = (u32)((u64)(uintptr_t)d->blockKeys.p >> 32);
+        if (hipMemsetAsync(d->blockKeys.p, 0xFF, (size_t)nBlocks * sizeof(u64), s) != hipSuccess ||
+            hipMemcpyAsync(status + kStBlockKeysLo, &keyWords[0], sizeof(u32), hipMemcpyHostToDevice, s) != hipSuccess ||
+            hipMemcpyAsync(status + kStBlockKeysHi, &keyWords[1], sizeof(u32), hipMemcpyHostToDevice, s) != hipSuccess) return ZERR(kErrGeneric);
+        launch_batch_walk_emit(srcBase, dIn, dOut, (u32)n, (FrameDesc*)d->frames.p, (BlockDesc*)d->blocks.p, s);
+        d->timer.mark("batch_walk", s);
+        e = decode_lists(d, dd, dstBase, srcBase, nFrames, nBlocks, 0, (size_t)(hiD - loD), st, [&]() -> bool {
+            launch_batch_fold(dOut, (u32)n, (const u64*)d->blockKeys.p, s);
+            return hipMemcpyAsync(hOut.data(), dOut, n * sizeof(BatchEntryOut), hipMemcpyDeviceToHost, s) == hipSuccess;
+        });
+        if (isErr(e)) return e;
+    }
+    d->timer.finish();
+    for (size_t i = 0; i < n; i++) {
+        if (srcSizes[i] && !srcs[i]) { dstSizes[i] = ZERR(kErrSrcSizeWrong); continue; }
+        if (hOut[i].state != kBatchAlone) dstSizes[i] = (size_t)hOut[i].result;
+    }
+    for (size_t i = 0; i < n; i++) {
+        if ((srcSizes[i] && !srcs[i]) || hOut[i].state != kBatchAlone) continue;
+        dstSizes[i] = decompress_device(d, (u8*)dsts[i], dstCapacities[i], (const u8*)srcs[i], srcSizes[i]);
+        d->lastBatchAlone++;
+    }
+    return 0;
 }
 
 static size_t decompress_multi(ZSTD_DCtx* d, void* dst, size_t dstCapacity, const void* src, size_t srcSize);
@@ -1708,6 +1833,11 @@ size_t ZSTD_CCtx_loadDictionary(ZSTD_CCtx* c, const void* dict, size_t dictSize)
 size_t ZSTD_DCtx_loadDictionary(ZSTD_DCtx* d, const void* dict, size_t dictSize) { return guarded([&] { return ZSTD_DCtx_loadDictionary_impl(d, dict, dictSize); }); }
 size_t ZSTD_findFrameCompressedSize(const void* src, size_t srcSize) { return guarded([&] { return ZSTD_findFrameCompressedSize_impl(src, srcSize); }); }
 size_t ZSTD_decompressDCtx(ZSTD_DCtx* d, void* dst, size_t dstCapacity, const void* src, size_t srcSize) { return guarded([&] { return ZSTD_decompressDCtx_impl(d, dst, dstCapacity, src, srcSize); }); }
+size_t ZSTDMI_decompressBatch(ZSTD_DCtx* d, const void* const* srcs, const size_t* srcSizes, size_t n, void* const* dsts, const size_t* dstCapacities, size_t* dstSizes)
+{
+    return guarded([&] { return decompress_batch_impl(d, srcs, srcSizes, n, dsts, dstCapacities, dstSizes); });
+}
+int ZSTDMI_debugLastBatchAloneD(const ZSTD_DCtx* d) { return d ? d->lastBatchAlone : -1; }
 size_t ZSTDMI_decompressDevice(ZSTD_DCtx* d, void* d_dst, size_t dstCapacity, const void* d_src, size_t srcSize) { return guarded([&] { return ZSTDMI_decompressDevice_impl(d, d_dst, dstCapacity, d_src, srcSize); }); }
 size_t ZSTD_compressStream2(ZSTD_CCtx* c, ZSTD_outBuffer* output, ZSTD_inBuffer* input, int endOp) { return guarded([&] { return ZSTD_compressStream2_impl(c, output, input, endOp); }); }
 size_t ZSTD_decompressStream(ZSTD_DCtx* d, ZSTD_outBuffer* output, ZSTD_inBuffer* input) { return guarded([&] { return ZSTD_decompressStream_impl(d, output, input); }); }
@@ -1722,13 +1852,141 @@ unsigned long long ZSTD_getFrameContentSize(const void* src, size_t srcSize)
 
 } // extern "C"
 
-// ---- a batch of independent samples, each compressed as ZSTD_compress2 would compress it alone against the loaded dictionary ----
-// (the dictionary trainer's inner loop, dict_train.hip).  Samples of one framing class (same dictionary prefix, chunk size and
-// resolved parameters) go through the pipeline together: each chunk of a sample is staged at its own chunk boundary and the finder
-// takes its length from a per-chunk table (launch_lz's chunkLens); the sizes come from the chunks' ChunkMeta, nothing is gathered.
-// A sample the class model does not cover (empty, no dictionary prefix, multi-block frames, LDM, checksums) is compressed alone.
-// outSizes[i] = the compressed size of sample i (or its error).  stats (optional, host, 377 u32): literal / LL / ML / offset code
-// counts of the compressed blocks are added to it (seq_stats_kernel).
+// ---- a batch of independent entries, each compressed as the single call would compress it alone (ZSTDMI_compressBatch; the
+// dictionary trainer's inner loop, dict_train.hip) ----
+// Entries of one framing class (same dictionary prefix, chunk size and resolved parameters) go through the pipeline together: each
+// chunk of an entry is staged at its own chunk boundary (batch_stage_kernel) and the finder and the checksum take its length from a
+// per-chunk table (chunkLens); every chunk is a frame of its own, so what is written for it depends on nothing beside it.  With
+// destinations, batch_place_kernel gives every chunk its place as an offset from the lowest destination pointer and huf_encode and
+// gather write there directly; without (the trainer), only the sizes come back.  A pass holds whole entries, at most
+// ZSTDMI_CCtx_setPassChunks chunks; per pass one table goes up and the entries' sizes come back in one copy.
+// An entry the class model does not cover — empty, multi-block frames (history, the small-call 16 KiB cut, windows below 64 KiB),
+// LDM, the sparse-input probe (4 MiB and more), more chunks than a pass, several device workers — is compressed alone afterwards, in
+// entry order, by the single-call path, and counted in `alone`.
+// srcs[i]: device pointers.  dsts / caps: device pointers and their capacities, or null (sizes only).  outSizes[i] = the compressed
+// size of entry i (or its error).  d_stats (optional, device, 377 u32): seq_stats_kernel's counts of the batched chunks are added.
+static size_t compress_entries(ZSTD_CCtx* c, const CallParams& cp, const u8* const* srcs, const size_t* sizes, size_t n,
+                               u8* const* dsts, const size_t* caps, size_t* outSizes, u32* d_stats, int& alone)
+{
+    hipStream_t s = c->stream;
+    alone = 0;
+    const u32 passLimit = c->passChunks < 16384 ? c->passChunks : 16384;
+    struct Group { Framing fr; std::vector<size_t> members; };
+    std::vector<Group> groups;
+    std::vector<size_t> aloneList;
+    for (size_t i = 0; i < n; i++) {
+        const size_t S = sizes[i];
+        if (dsts) {         // (the single call's argument checks)
+            if (S && !srcs[i]) { outSizes[i] = ZERR(kErrSrcSizeWrong); continue; }
+            if (!dsts[i]) { outSizes[i] = caps[i] ? ZERR(kErrDstBufferNull) : ZERR(kErrDstSizeTooSmall); continue; }
+        }
+        const Framing fr = S ? resolve_framing(c, cp, S) : Framing{};
+        bool batched = S && !fr.frameBlocks && !fr.indepWindowLog && !fr.ldm && c->workers.size() <= 1 && (S + fr.chunkBytes - 1) / fr.chunkBytes <= passLimit;
+        if (batched && S >= (4u << 20)) { size_t err = 0; if (probe_group_bytes(c, cp, S, err) || isErr(err)) batched = false; }
+        if (!batched) { aloneList.push_back(i); continue; }
+        outSizes[i] = 0;
+        Group* g = nullptr;
+        for (auto& x : groups)
+            if (x.fr.prefixLen == fr.prefixLen && x.fr.chunkBytes == fr.chunkBytes && !memcmp(&x.fr.rs, &fr.rs, sizeof(Resolved))) { g = &x; break; }
+        if (!g) { groups.push_back(Group{fr, {}}); g = &groups.back(); }
+        g->members.push_back(i);
+    }
+    const bool fmtDict = cp.useDict && c->dictFormatted;
+    const u32 dictID = fmtDict ? c->info.dictID : 0u;
+    const u32 dictIdBytes = (dictID && cp.dictIDFlag) ? (dictID < 256 ? 1u : dictID < 65536 ? 2u : 4u) : 0u;
+    const u32 plainReps[3] = { 1, 4, 8 };
+    const u32* const initReps = fmtDict ? c->info.rep : plainReps;
+    bool first = true;
+    std::vector<u8> tab; std::vector<u64> got;
+    for (const Group& g : groups) {
+        const u32 cb = g.fr.chunkBytes, prefixLen = g.fr.prefixLen;
+        const Resolved rs = g.fr.rs;
+        const u8* prefix = prefixLen ? (const u8*)c->dict.p + (c->dictHost.size() - prefixLen) : nullptr;
+        const bool regionParse = rs.minStrideLog == 0 && c->parser == 0;
+        const bool hcChains = regionParse && rs.finder >= 2;
+        u32 hcDepth = rs.cp.searchLog < 2 ? 4u : rs.cp.searchLog > 5 ? 32u : 1u << rs.cp.searchLog;
+        if (hcDepth > 8 && rs.cp.strategy <= 4 && cp.searchLog == 0) hcDepth = 8;
+        const u32 strategy = rs.cp.strategy < kStratGreedy ? rs.cp.strategy : (u32)kStratGreedy;
+        for (size_t m0 = 0; m0 < g.members.size(); ) {
+            // the pass: whole entries, up to passLimit chunks
+            size_t m1 = m0; u32 nCh = 0;
+            while (m1 < g.members.size()) {
+                const u32 k = (u32)((sizes[g.members[m1]] + cb - 1) / cb);
+                if (nCh && nCh + k > passLimit) break;
+                nCh += k; ++m1;
+            }
+            const u32 nEnt = (u32)(m1 - m0);
+            // the pass's table, one upload: from[nCh] | entDst[nEnt] | entCap[nEnt] (u64) | len[nCh] | entFirst[nEnt + 1] (u32); behind it the sizes that come back
+            const size_t atDst = (size_t)nCh * 8, atCap = atDst + (size_t)nEnt * 8, atLen = atCap + (size_t)nEnt * 8, atFirst = atLen + (size_t)nCh * 4;
+            const size_t tabBytes = (atFirst + ((size_t)nEnt + 1) * 4 + 7) & ~(size_t)7;
+            tab.assign(tabBytes, 0);
+            u64* const hFrom = (u64*)tab.data(); u64* const hDst = (u64*)(tab.data() + atDst); u64* const hCap = (u64*)(tab.data() + atCap);
+            u32* const hLen = (u32*)(tab.data() + atLen); u32* const hFirst = (u32*)(tab.data() + atFirst);
+            uintptr_t lo = ~(uintptr_t)0, hi = 0;
+            if (dsts) for (size_t m = m0; m < m1; ++m) {
+                const size_t i = g.members[m];
+                const uintptr_t d = (uintptr_t)dsts[i];
+                lo = d < lo ? d : lo; hi = d + caps[i] > hi ? d + caps[i] : hi;
+            }
+            u8* const base = dsts ? (u8*)lo : nullptr;
+            const u64 span = dsts ? (u64)(hi - lo) : 0;
+            u32 ck = 0;
+            for (size_t m = m0; m < m1; ++m) {
+                const size_t i = g.members[m];
+                hFirst[m - m0] = ck;
+                hDst[m - m0] = dsts ? (u64)((uintptr_t)dsts[i] - lo) : 0;
+                hCap[m - m0] = dsts ? (u64)caps[i] : ~(u64)0;
+                for (u64 o = 0; o < sizes[i]; o += cb, ++ck) { hFrom[ck] = (u64)(uintptr_t)(srcs[i] + o); hLen[ck] = (u32)(sizes[i] - o < cb ? sizes[i] - o : cb); }
+            }
+            hFirst[nEnt] = ck;
+            if (!cctx_workspace(c, nCh) || (regionParse && !cctx_cand_workspace(c, nCh, hcChains)) || !c->batchStage.ensure((u64)nCh * cb + 64) ||
+                !c->batchTab.ensure(tabBytes + (size_t)nEnt * 8)) return ZERR(kErrMemoryAllocation);
+            u8* const dTab = (u8*)c->batchTab.p;
+            const u32* const dLen = (const u32*)(dTab + atLen);
+            u64* const dGot = (u64*)(dTab + tabBytes);
+            if (hipMemcpyAsync(dTab, tab.data(), tabBytes, hipMemcpyHostToDevice, s) != hipSuccess) return ZERR(kErrGeneric);
+            const u8* stage = (const u8*)c->batchStage.p;
+            Seq* seqs = (Seq*)c->seqs.p; u8* lits = (u8*)c->lits.p; ChunkMeta* meta = (ChunkMeta*)c->meta.p;
+            HufTable* tables = (HufTable*)c->tables.p; u8* slots = (u8*)c->slots.p; u64* offsets = (u64*)c->offsets.p; u64* total = (u64*)c->total.p;
+            const u64 stagedBytes = (u64)nCh * cb;
+            c->timer.begin(s);
+            launch_batch_stage((const u64*)dTab, dLen, (u8*)c->batchStage.p, nCh, cb, s);      c->timer.mark("batch_stage", s);
+            launch_lz(rs.finder, stage, stagedBytes, nCh, seqs, lits, meta, prefix, prefixLen, cb, dictIdBytes | (cp.contentSizeFlag ? 0u : 0x100u), rs.minStrideLog, 0,
+                      regionParse ? (u16*)c->cand.p : nullptr, hcChains ? (u16*)((u8*)c->cand.p + cand_plane_bytes(nCh)) : nullptr,
+                      regionParse ? (u32*)((u8*)c->cand.p + cand_plane_bytes(nCh) * (hcChains ? 2 : 1)) : nullptr, hcDepth, s, c->timer.hook(), (u32*)(total + 4), dLen);
+            launch_huf_build(lits, meta, tables, slots, nCh, rs.rawLiterals, stage, cb, s, c->timer.hook());
+            if (cp.checksumFlag) { launch_xxh64(stage, stagedBytes, meta, nCh, cb, 0, s, dLen);        c->timer.mark("xxh64", s); }
+            launch_seq_encode(seqs, meta, slots, nCh, strategy, (cp.checksumFlag ? 1u : 0u) | (cp.contentSizeFlag ? 0u : 2u), 1, dictID, dictIdBytes, initReps, 0, cb, stagedBytes, s);
+            c->timer.mark("seq_encode", s);
+            if (d_stats) launch_seq_stats(seqs, lits, meta, nCh, stage, cb, d_stats, s);
+            launch_batch_place(meta, nEnt, (const u32*)(dTab + atFirst), (const u64*)(dTab + atDst), (const u64*)(dTab + atCap), span, offsets, dGot, s);
+            c->timer.mark("batch_place", s);
+            if (dsts) {
+                launch_huf_encode(lits, meta, tables, slots, base, offsets, span, nCh, stage, cb, s);     c->timer.mark("huf_encode", s);
+                launch_gather(stage, stagedBytes, slots, meta, offsets, base, span, nCh, cb, s);          c->timer.mark("gather", s);
+            }
+            got.resize(nEnt);
+            if (hipMemcpyAsync(got.data(), dGot, (size_t)nEnt * 8, hipMemcpyDeviceToHost, s) != hipSuccess) return ZERR(kErrGeneric);
+            if (hipStreamSynchronize(s) != hipSuccess) { (void)hipGetLastError(); return ZERR(kErrGeneric); }
+            c->timer.finish(); c->nStages = c->timer.n;
+            for (int i = 0; i < c->timer.n; i++) { c->stageMs[i] = (first ? 0.f : c->stageMs[i]) + c->timer.ms[i]; c->stageNames[i] = c->timer.names[i]; }
+            first = false;
+            for (u32 e = 0; e < nEnt; ++e) outSizes[g.members[m0 + e]] = (size_t)got[e];
+            m0 = m1;
+        }
+    }
+    std::vector<u8> tmp;
+    for (size_t i : aloneList) {
+        if (dsts) outSizes[i] = compress_device(c, cp, dsts[i], caps[i], srcs[i], sizes[i]);
+        else { tmp.resize(ZSTD_compressBound(sizes[i])); outSizes[i] = compress_any(c, cp, tmp.data(), tmp.size(), srcs[i], sizes[i]); }
+        ++alone;
+    }
+    c->lastChunks = 0;                                  // (ZSTDMI_debugGetChunk: no ordinary call to look at)
+    return 0;
+}
+
+// the trainer's samples (host memory, sample i at src + offs[i]): uploaded once, then compress_entries without destinations.
+// stats (optional, host, 377 u32): literal / LL / ML / offset code counts of the compressed blocks are added to it.
 namespace zmi {
 size_t compress_samples(ZSTD_CCtx* c, const u8* src, const u64* offs, const size_t* sizes, size_t n, size_t* outSizes, u32* stats)
 {
@@ -1736,84 +1994,46 @@ size_t compress_samples(ZSTD_CCtx* c, const u8* src, const u64* offs, const size
     const CallParams cp = sticky_params(c);
     e = cctx_sync_dictionary(c); if (isErr(e)) return e;
     hipStream_t s = c->stream;
-    struct Group { Framing fr; std::vector<size_t> members; };
-    std::vector<Group> groups;
-    std::vector<u8> tmp;
     u64 maxEnd = 0;
-    for (size_t i = 0; i < n; i++) {
-        const size_t S = sizes[i];
-        const Framing fr = S ? resolve_framing(c, cp, S) : Framing{};
-        if (!S || !fr.prefixLen || fr.frameBlocks || fr.indepWindowLog || fr.ldm || cp.checksumFlag || c->workers.size() > 1) {
-            tmp.resize(ZSTD_compressBound(S));
-            outSizes[i] = compress_any(c, cp, tmp.data(), tmp.size(), src + offs[i], S);
-            continue;
-        }
-        outSizes[i] = 0;
-        maxEnd = offs[i] + S > maxEnd ? offs[i] + S : maxEnd;
-        Group* g = nullptr;
-        for (auto& x : groups)
-            if (x.fr.prefixLen == fr.prefixLen && x.fr.chunkBytes == fr.chunkBytes && !memcmp(&x.fr.rs, &fr.rs, sizeof(Resolved))) { g = &x; break; }
-        if (!g) { groups.push_back(Group{fr, {}}); g = &groups.back(); }
-        g->members.push_back(i);
-    }
-    if (groups.empty()) return 0;
-    DevBuf dSrc, dStage, dFrom, dLen, dStats;
+    for (size_t i = 0; i < n; i++) if (sizes[i] && offs[i] + sizes[i] > maxEnd) maxEnd = offs[i] + sizes[i];
+    DevBuf dSrc, dStats;
+    struct Free { DevBuf &a, &b; ~Free() { a.release(); b.release(); } } freeThem{dSrc, dStats};
     if (!dSrc.ensure(maxEnd + 16) || !dStats.ensure(377 * 4)) return ZERR(kErrMemoryAllocation);
-    bool ok = hipMemcpyAsync(dSrc.p, src, maxEnd, hipMemcpyHostToDevice, s) == hipSuccess && hipMemsetAsync(dStats.p, 0, 377 * 4, s) == hipSuccess;
-    const bool fmtDict = c->dictFormatted;
-    const u32 dictID = fmtDict ? c->info.dictID : 0u;
-    const u32 dictIdBytes = (dictID && cp.dictIDFlag) ? (dictID < 256 ? 1u : dictID < 65536 ? 2u : 4u) : 0u;
-    const u32 plainReps[3] = { 1, 4, 8 };
-    const u32* const initReps = fmtDict ? c->info.rep : plainReps;
-    for (const Group& g : groups) {
-        if (!ok) break;
-        const u32 cb = g.fr.chunkBytes, prefixLen = g.fr.prefixLen;
-        const Resolved rs = g.fr.rs;
-        const u8* prefix = (const u8*)c->dict.p + (c->dictHost.size() - prefixLen);
-        std::vector<u64> from; std::vector<u32> len; std::vector<size_t> owner;
-        for (size_t i : g.members)
-            for (u64 o = 0; o < sizes[i]; o += cb) { from.push_back(offs[i] + o); len.push_back((u32)(sizes[i] - o < cb ? sizes[i] - o : cb)); owner.push_back(i); }
-        const u32 pass = c->passChunks < 16384 ? c->passChunks : 16384;
-        const bool regionParse = rs.minStrideLog == 0 && c->parser == 0;
-        const bool hcChains = regionParse && rs.finder >= 2;
-        u32 hcDepth = rs.cp.searchLog < 2 ? 4u : rs.cp.searchLog > 5 ? 32u : 1u << rs.cp.searchLog;
-        if (hcDepth > 8 && rs.cp.strategy <= 4 && cp.searchLog == 0) hcDepth = 8;
-        const u32 strategy = rs.cp.strategy < kStratGreedy ? rs.cp.strategy : (u32)kStratGreedy;
-        std::vector<ChunkMeta> hm;
-        for (size_t c0 = 0; c0 < from.size() && ok; c0 += pass) {
-            const u32 nCh = (u32)(from.size() - c0 < pass ? from.size() - c0 : pass);
-            if (!cctx_workspace(c, nCh) || (regionParse && !cctx_cand_workspace(c, nCh, hcChains)) || !dStage.ensure((u64)nCh * cb + 64) ||
-                !dFrom.ensure((u64)nCh * 8) || !dLen.ensure((u64)nCh * 4)) return ZERR(kErrMemoryAllocation);
-            ok = hipMemcpyAsync(dFrom.p, from.data() + c0, (u64)nCh * 8, hipMemcpyHostToDevice, s) == hipSuccess &&
-                 hipMemcpyAsync(dLen.p, len.data() + c0, (u64)nCh * 4, hipMemcpyHostToDevice, s) == hipSuccess;
-            if (!ok) break;
-            const u8* stage = (const u8*)dStage.p;
-            launch_sample_scatter((const u8*)dSrc.p, (const u64*)dFrom.p, (const u32*)dLen.p, (u8*)dStage.p, nCh, cb, s);
-            Seq* seqs = (Seq*)c->seqs.p; u8* lits = (u8*)c->lits.p; ChunkMeta* meta = (ChunkMeta*)c->meta.p;
-            HufTable* tables = (HufTable*)c->tables.p; u8* slots = (u8*)c->slots.p; u64* total = (u64*)c->total.p;
-            const u64 stagedBytes = (u64)nCh * cb;
-            launch_lz(rs.finder, stage, stagedBytes, nCh, seqs, lits, meta, prefix, prefixLen, cb, dictIdBytes | (cp.contentSizeFlag ? 0u : 0x100u), rs.minStrideLog, 0,
-                      regionParse ? (u16*)c->cand.p : nullptr, hcChains ? (u16*)((u8*)c->cand.p + cand_plane_bytes(nCh)) : nullptr,
-                      regionParse ? (u32*)((u8*)c->cand.p + cand_plane_bytes(nCh) * (hcChains ? 2 : 1)) : nullptr, hcDepth, s, StageHook{}, (u32*)(total + 4),
-                      (const u32*)dLen.p);
-            launch_huf_build(lits, meta, tables, slots, nCh, rs.rawLiterals, stage, cb, s, StageHook{});
-            launch_seq_encode(seqs, meta, slots, nCh, strategy, cp.contentSizeFlag ? 0u : 2u, 1, dictID, dictIdBytes, initReps, 0, cb, stagedBytes, s);
-            if (stats) launch_seq_stats(seqs, lits, meta, nCh, stage, cb, (u32*)dStats.p, s);
-            hm.resize(nCh);
-            ok = hipMemcpyAsync(hm.data(), meta, (u64)nCh * sizeof(ChunkMeta), hipMemcpyDeviceToHost, s) == hipSuccess &&
-                 hipStreamSynchronize(s) == hipSuccess;
-            if (!ok) break;
-            for (u32 k = 0; k < nCh; k++) outSizes[owner[c0 + k]] += hm[k].outSize;
-        }
+    if ((maxEnd && hipMemcpyAsync(dSrc.p, src, maxEnd, hipMemcpyHostToDevice, s) != hipSuccess) || hipMemsetAsync(dStats.p, 0, 377 * 4, s) != hipSuccess) return ZERR(kErrGeneric);
+    std::vector<const u8*> srcs(n);
+    for (size_t i = 0; i < n; i++) srcs[i] = (const u8*)dSrc.p + offs[i];
+    int alone = 0;
+    e = compress_entries(c, cp, srcs.data(), sizes, n, nullptr, nullptr, outSizes, stats ? (u32*)dStats.p : nullptr, alone);
+    if (isErr(e)) return e;
+    if (stats) {
+        std::vector<u32> h(377);
+        if (hipMemcpyAsync(h.data(), dStats.p, 377 * 4, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) { (void)hipGetLastError(); return ZERR(kErrGeneric); }
+        for (u32 i = 0; i < 377; i++) stats[i] += h[i];
     }
-    std::vector<u32> h(377);
-    if (ok) ok = hipMemcpyAsync(h.data(), dStats.p, 377 * 4, hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
-    if (!ok) { (void)hipGetLastError(); return ZERR(kErrGeneric); }
-    if (stats) for (u32 i = 0; i < 377; i++) stats[i] += h[i];
-    c->lastChunks = 0;                                  // (ZSTDMI_debugGetChunk: no ordinary call to look at)
     return 0;
 }
 } // namespace zmi
+
+// The public batch: n device-resident entries, each to its own destination with its own status (include/zstd_mi355x.h)
+static size_t compress_batch_impl(ZSTD_CCtx* c, const void* const* srcs, const size_t* srcSizes, size_t n, void* const* dsts, const size_t* dstCapacities, size_t* dstSizes)
+{
+    if (!c) return ZERR(kErrGeneric);
+    if (n == 0) { c->lastBatchAlone = 0; return 0; }
+    if (!srcs || !srcSizes || !dsts || !dstCapacities || !dstSizes) return ZERR(kErrGeneric);
+    size_t e = cctx_bind(c); if (isErr(e)) return e;
+    if (c->workers.size() > 1) return ZERR(kErrParameterUnsupported);
+    c->lastBatchAlone = 0;
+    const CallParams cp = sticky_params(c);
+    e = check_call_params(cp);
+    if (isErr(e)) { for (size_t i = 0; i < n; i++) dstSizes[i] = e; return 0; }     // (what every single call would answer)
+    e = cctx_sync_dictionary(c); if (isErr(e)) return e;
+    return compress_entries(c, cp, (const u8* const*)srcs, srcSizes, n, (u8* const*)dsts, dstCapacities, dstSizes, nullptr, c->lastBatchAlone);
+}
+extern "C" size_t ZSTDMI_compressBatch(ZSTD_CCtx* c, const void* const* srcs, const size_t* srcSizes, size_t n, void* const* dsts, const size_t* dstCapacities, size_t* dstSizes)
+{
+    return guarded([&] { return compress_batch_impl(c, srcs, srcSizes, n, dsts, dstCapacities, dstSizes); });
+}
+extern "C" int ZSTDMI_debugLastBatchAlone(const ZSTD_CCtx* c) { return c ? c->lastBatchAlone : -1; }
 
 extern "C" size_t ZSTDMI_debugCompressSamples(ZSTD_CCtx* c, const void* src, const size_t* sizes, size_t n, size_t* outSizes)
 {
