@@ -247,6 +247,35 @@ size_t ZSTDMI_decompressBatch(ZSTD_DCtx* dctx, const void* const* srcs, const si
 int ZSTDMI_debugLastBatchAlone(const ZSTD_CCtx* cctx);
 int ZSTDMI_debugLastBatchAloneD(const ZSTD_DCtx* dctx);
 
+/* Seekable streams (the zstd seekable format, v0.1.0): random access at the granularity of the frame.
+ * Every stream this library writes is a run of independent frames (64 KiB of content at levels 1-2, 240-256 KiB at levels >= 3, 32 KiB
+ * or less behind a dictionary, one window under long-distance matching; ZSTDMI_CCtx_setHistory and ZSTD_c_windowLog change it).
+ * ZSTDMI_CCtx_setSeekTable(1) makes ZSTD_compress2 and ZSTDMI_compressDevice append a seek table to exactly those bytes — a skippable
+ * frame, so every zstd decoder still reads the stream; all fields little-endian:
+ *     0x184D2A5E (4) | Frame_Size (4) | N entries | Number_Of_Frames (4) | descriptor (1) | 0x8F92EAB1 (4)
+ *     entry: Compressed_Size (4) | Decompressed_Size (4) | [Checksum (4), only if the descriptor's bit 7 is set]
+ * one entry per frame in order (a skippable frame: Decompressed_Size 0).  This library writes 8-byte entries, descriptor 0: table
+ * checksums are neither written nor verified (the frames' own checksums, ZSTD_c_checksumFlag, still are).  0 = off (default); any
+ * other mode: parameter_outOfBound.  The table needs ZSTDMI_seekTableBound(srcSize) bytes on top of ZSTD_compressBound(srcSize); if it
+ * does not fit behind the frames the call returns dstSize_tooSmall.  With the switch on, ZSTDMI_compressBatch, ZSTD_compressStream2 and
+ * a context with several device workers return parameter_unsupported; ZSTD_compressCCtx ignores it (level-only parameters).
+ * ZSTDMI_decompressRange writes content[offset, offset + length) of a stream that ends in such a table (this library's or anyone's,
+ * 8- or 12-byte entries) to dst and returns the bytes written, min(length, max(total - offset, 0)); more than dstCapacity:
+ * dstSize_tooSmall, nothing written.  src and dst are host or device pointers, each on its own.  Only the frames that meet the range
+ * are decoded — a 1-byte read decodes one whole frame — and from a host source only the table and those frames' compressed bytes are
+ * copied to the device.  The context's dictionary applies; several device workers: parameter_unsupported.  Table errors: a stream below
+ * 17 bytes, a wrong footer magic, a skippable header that is missing, not ...5E, or of another size: prefix_unknown; reserved descriptor
+ * bits, more than 2^27 entries, a table longer than the stream, compressed sizes that do not add up to the bytes in front of the table,
+ * a frame whose content is not the size its entry names: corruption_detected. */
+size_t ZSTDMI_CCtx_setSeekTable(ZSTD_CCtx* cctx, unsigned mode);
+size_t ZSTDMI_seekTableBound(size_t srcSize);
+size_t ZSTDMI_decompressRange(ZSTD_DCtx* dctx, void* dst, size_t dstCapacity, const void* src, size_t srcSize,
+                              unsigned long long offset, size_t length);
+/* diagnostics of the last ZSTDMI_decompressRange: table entries with content it decoded; bytes it copied host -> device (0 for a
+ * device source); -1 without a context */
+int ZSTDMI_debugLastRangeFrames(const ZSTD_DCtx* dctx);
+long long ZSTDMI_debugLastRangeStaged(const ZSTD_DCtx* dctx);
+
 /* per-stage HIP-event timing of the LAST call (enable first).  Fills up to `cap` entries, returns the count. */
 size_t ZSTDMI_CCtx_setProfiling(ZSTD_CCtx* cctx, int enable);
 size_t ZSTDMI_DCtx_setProfiling(ZSTD_DCtx* dctx, int enable);

@@ -95,6 +95,11 @@ SIGNATURES = {
                                           ctypes.POINTER(c_void_p), ctypes.POINTER(c_size_t), ctypes.POINTER(c_size_t)]),
     "ZSTDMI_debugLastBatchAlone": (c_int, [c_void_p]),
     "ZSTDMI_debugLastBatchAloneD": (c_int, [c_void_p]),
+    "ZSTDMI_CCtx_setSeekTable": (c_size_t, [c_void_p, c_uint]),
+    "ZSTDMI_seekTableBound": (c_size_t, [c_size_t]),
+    "ZSTDMI_decompressRange": (c_size_t, [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_ull, c_size_t]),
+    "ZSTDMI_debugLastRangeFrames": (c_int, [c_void_p]),
+    "ZSTDMI_debugLastRangeStaged": (ctypes.c_longlong, [c_void_p]),
     "ZSTDMI_CCtx_setProfiling": (c_size_t, [c_void_p, c_int]),
     "ZSTDMI_DCtx_setProfiling": (c_size_t, [c_void_p, c_int]),
     "ZSTDMI_CCtx_getStageTimes": (c_int, [c_void_p, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_char_p), c_int]),

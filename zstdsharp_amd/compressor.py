@@ -39,6 +39,7 @@ class Compressor:
         if device is not None:
             ensure_zstd_success(self._lib, self._lib.ZSTDMI_CCtx_setDevice(self.cctx, device))
         self._level = 0
+        self._seek_table = False
         self.Level = level if level else self.DefaultCompressionLevel
 
     # ---- static members (S/Compressor.cs:8-10) ----
@@ -82,13 +83,24 @@ class Compressor:
     def GetCompressBound(length: int) -> int:                  # S/Compressor.cs:72-76
         return _ffi.load().ZSTD_compressBound(length)
 
+    # ---- seek table (ZSTDMI_CCtx_setSeekTable): Wrap appends one, Decompressor.unwrap_range reads ranges through it ----
+    @property
+    def seek_table(self) -> bool:
+        return self._seek_table
+
+    @seek_table.setter
+    def seek_table(self, on):
+        self._ensure_not_disposed()
+        ensure_zstd_success(self._lib, self._lib.ZSTDMI_CCtx_setSeekTable(self.cctx, 1 if on else 0))
+        self._seek_table = bool(on)
+
     # ---- Wrap (S/Compressor.cs:78-96) ----
     def Wrap(self, src, dest=None, offset: int = 0):
         """Wrap(src) -> bytes;  Wrap(src, dest[, offset]) -> number of bytes written into dest."""
         self._ensure_not_disposed()
         saddr, sn, skeep = _as_buffer(src)
         if dest is None:
-            cap = self.GetCompressBound(sn)
+            cap = self.GetCompressBound(sn) + (self._lib.ZSTDMI_seekTableBound(sn) if self._seek_table else 0)
             out = ctypes.create_string_buffer(max(cap, 1))
             n = ensure_zstd_success(self._lib, self._lib.ZSTD_compress2(self.cctx, out, cap, saddr, sn))
             return out.raw[:n]

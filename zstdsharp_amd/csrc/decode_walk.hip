@@ -347,6 +347,152 @@ void launch_batch_fold(BatchEntryOut* out, u32 nEntries, const u64* keys, hipStr
     hipLaunchKernelGGL(batch_fold_kernel, dim3((nEntries + 63) / 64), dim3(64), 0, stream, out, nEntries, keys);
 }
 
+// ------------------------------------------------------------------------------------------------
+// a range of a seekable stream (ZSTDMI_decompressRange): seek table + (offset, length) -> the batch walk's entries
+// ------------------------------------------------------------------------------------------------
+// exclusive prefix of (a, b) over the 1024 lanes of a workgroup, and the workgroup's sums
+__device__ inline void block_scan2(u64 a, u64 b, u64* __restrict__ shA, u64* __restrict__ shB, u64& exA, u64& exB, u64& allA, u64& allB)
+{
+    const u32 lane = lane_id(), wave = wave_id();
+    u64 ai = a, bi = b;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const u64 ta = __shfl_up(ai, d), tb = __shfl_up(bi, d);
+        if ((int)lane >= d) { ai += ta; bi += tb; }
+    }
+    if (lane == 63) { shA[wave] = ai; shB[wave] = bi; }
+    __syncthreads();
+    exA = ai - a; exB = bi - b; allA = 0; allB = 0;
+    for (u32 w = 0; w < 16; ++w) { if (w < wave) { exA += shA[w]; exB += shB[w]; } allA += shA[w]; allB += shB[w]; }
+    __syncthreads();
+}
+
+// select (single workgroup): `tab` = the table's skippable frame (tableBytes of it: header, n entries of `stride` bytes — a checksum
+// behind the two sizes is skipped —, footer; the host has read the footer).  Checks the header and that the compressed sizes add up to
+// the bytes in front of the table — so every offset derived from them lies inside the stream —, sums both columns, and finds the
+// entries with content that meet [offset, offset + length): their first and last, and those two's places.  -> the summary words.
+__global__ __launch_bounds__(1024) void seek_select_kernel(const u8* __restrict__ tab, u64 tableBytes, u32 n, u32 stride, u64 srcSize,
+                                                           u64 offset, u64 length, u64* __restrict__ sum)
+{
+    __shared__ u64 shA[16], shB[16], rec[6];
+    __shared__ u32 tileFirst, tileLast, firstIdx, lastIdx, nMeet;
+    const u32 tid = threadIdx.x;
+    if (tid == 0) { firstIdx = 0xFFFFFFFFu; lastIdx = 0; nMeet = 0; for (u32 k = 0; k < 6; ++k) rec[k] = 0; }
+    u64 end = offset + length; if (end < offset) end = ~0ull;
+    u64 carryC = 0, carryD = 0;
+    for (u32 base = 0; base < n; base += 1024) {
+        if (tid == 0) { tileFirst = 0xFFFFFFFFu; tileLast = 0; }
+        const u32 i = base + tid;
+        u64 c = 0, d = 0;
+        if (i < n) { const u8* p = tab + 8 + (u64)i * stride; c = readLE32(p); d = readLE32(p + 4); }
+        u64 exC, exD, allC, allD;
+        block_scan2(c, d, shA, shB, exC, exD, allC, allD);
+        const u64 cOff = carryC + exC, dOff = carryD + exD;
+        const bool meet = d > 0 && length > 0 && dOff < end && dOff + d > offset;
+        if (meet) { atomicMin(&tileFirst, i); atomicMax(&tileLast, i + 1); atomicAdd(&nMeet, 1u); }
+        carryC += allC; carryD += allD;
+        __syncthreads();
+        if (meet && i == tileFirst && firstIdx == 0xFFFFFFFFu) { firstIdx = i; rec[0] = cOff; rec[1] = dOff; rec[2] = d; }
+        if (meet && i + 1 == tileLast) { lastIdx = i; rec[3] = cOff + c; rec[4] = dOff; rec[5] = d; }     // (a later tile's overwrites an earlier one's)
+        __syncthreads();
+    }
+    if (tid == 0) {
+        u32 err = 0;
+        if (readLE32(tab) != 0x184D2A5Eu || (u64)readLE32(tab + 4) != tableBytes - 8) err = kErrPrefixUnknown;
+        else if (carryC != srcSize - tableBytes) err = kErrCorruption;
+        sum[kSeekErr] = err; sum[kSeekTotal] = carryD; sum[kSeekMeet] = nMeet; sum[kSeekFirst] = firstIdx; sum[kSeekLast] = lastIdx;
+        sum[kSeekCLo] = rec[0]; sum[kSeekDFirst] = rec[1]; sum[kSeekSizeFirst] = rec[2];
+        sum[kSeekCHi] = rec[3]; sum[kSeekDLast] = rec[4]; sum[kSeekSizeLast] = rec[5];
+        sum[kSeekKey] = ~0ull; sum[kSeekAlone] = 0;
+    }
+}
+
+// emit (single workgroup, the selected entries only): one BatchEntryIn per table entry first .. first + nSel - 1.  Sources are offsets
+// from the first selected frame; a frame wholly inside the range decodes to its place in dst (dstBias + its content offset - offset),
+// the first and the last one — where the range cuts them — to their slots in the edge buffer (edgeBias, edgeBias + slot1).  An entry
+// without content (a skippable frame) becomes an empty entry.  Every entry's capacity is its table size: the walk refuses more.
+__global__ __launch_bounds__(1024) void seek_emit_kernel(const u8* __restrict__ tab, u32 stride, u32 first, u32 nSel, u64 dFirst, u64 offset,
+                                                         u64 dstBias, u64 edgeBias, u64 slot1, u32 cutFirst, u32 cutLast, BatchEntryIn* __restrict__ out)
+{
+    __shared__ u64 shA[16], shB[16];
+    const u32 tid = threadIdx.x;
+    u64 carryC = 0, carryD = dFirst;
+    for (u32 base = 0; base < nSel; base += 1024) {
+        const u32 i = base + tid;
+        u64 c = 0, d = 0;
+        if (i < nSel) { const u8* p = tab + 8 + (u64)(first + i) * stride; c = readLE32(p); d = readLE32(p + 4); }
+        u64 exC, exD, allC, allD;
+        block_scan2(c, d, shA, shB, exC, exD, allC, allD);
+        if (i < nSel) {
+            const u64 dOff = carryD + exD;
+            BatchEntryIn e; e.srcOff = carryC + exC; e.srcSize = d ? c : 0; e.dstCap = d;
+            if (i == 0 && cutFirst) e.dstOff = edgeBias;
+            else if (i == nSel - 1 && cutLast) e.dstOff = edgeBias + slot1;
+            else e.dstOff = dstBias + (d ? dOff - offset : 0);
+            out[i] = e;
+        }
+        carryC += allC; carryD += allD;
+    }
+}
+
+// check: an entry that failed, or whose content is not the size its table entry names, fails the call (the first such entry's error;
+// a frame larger than its table size was refused by the walk with dstSize_tooSmall: corruption of the table); the others are counted
+__global__ __launch_bounds__(256) void range_check_kernel(const BatchEntryIn* __restrict__ in, const BatchEntryOut* __restrict__ out, u32 nEntries, u64* __restrict__ sum)
+{
+    const u32 e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= nEntries) return;
+    const BatchEntryOut o = out[e];
+    if (o.state == kBatchAlone) { atomicAdd((unsigned long long*)&sum[kSeekAlone], 1ull); return; }
+    u32 err = 0;
+    if (o.result > (u64)0 - (u64)kErrMaxCode) { err = (u32)((u64)0 - o.result); if (err == kErrDstSizeTooSmall) err = kErrCorruption; }
+    else if (o.result != in[e].dstCap) err = kErrCorruption;
+    if (err) atomicMin((unsigned long long*)&sum[kSeekKey], ((unsigned long long)e << 16) | err);
+}
+
+// clip: the wanted part of each edge frame from the edge buffer to its place in dst (blockIdx.y = the job)
+__global__ __launch_bounds__(256) void range_clip_kernel(u8* __restrict__ dst, const u8* __restrict__ edge, ClipJob j0, ClipJob j1)
+{
+    const ClipJob j = blockIdx.y ? j1 : j0;
+    if (!j.len) return;
+    u8* const d = dst + j.to; const u8* const s = edge + j.from;
+    const u64 gtid = (u64)blockIdx.x * 256 + threadIdx.x, nThreads = (u64)gridDim.x * 256;
+    // head: bring d to 16-byte alignment, then 16 B stores fed by unaligned loads
+    u64 head = (16 - ((uintptr_t)d & 15)) & 15;
+    if (head > j.len) head = j.len;
+    if (gtid < head) d[gtid] = s[gtid];
+    const u64 body = (j.len - head) >> 4;
+    uint4* const d4 = reinterpret_cast<uint4*>(d + head);
+    const u8* const sb = s + head;
+    for (u64 i = gtid; i < body; i += nThreads) {
+        uint4 v;
+        v.x = readLE32(sb + 16 * i); v.y = readLE32(sb + 16 * i + 4); v.z = readLE32(sb + 16 * i + 8); v.w = readLE32(sb + 16 * i + 12);
+        d4[i] = v;
+    }
+    const u64 done = head + (body << 4);
+    if (gtid < j.len - done) d[done + gtid] = s[done + gtid];
+}
+
+void launch_seek_select(const u8* tab, u64 tableBytes, u32 n, u32 stride, u64 srcSize, u64 offset, u64 length, u64* sum, hipStream_t stream)
+{
+    hipLaunchKernelGGL(seek_select_kernel, dim3(1), dim3(1024), 0, stream, tab, tableBytes, n, stride, srcSize, offset, length, sum);
+}
+void launch_seek_emit(const u8* tab, u32 stride, u32 first, u32 nSel, u64 dFirst, u64 offset, u64 dstBias, u64 edgeBias, u64 slot1, u32 cutFirst, u32 cutLast,
+                      BatchEntryIn* out, hipStream_t stream)
+{
+    hipLaunchKernelGGL(seek_emit_kernel, dim3(1), dim3(1024), 0, stream, tab, stride, first, nSel, dFirst, offset, dstBias, edgeBias, slot1, cutFirst, cutLast, out);
+}
+void launch_range_check(const BatchEntryIn* in, const BatchEntryOut* out, u32 nEntries, u64* sum, hipStream_t stream)
+{
+    hipLaunchKernelGGL(range_check_kernel, dim3((nEntries + 255) / 256), dim3(256), 0, stream, in, out, nEntries, sum);
+}
+void launch_range_clip(u8* dst, const u8* edge, ClipJob j0, ClipJob j1, hipStream_t stream)
+{
+    const u64 most = j0.len > j1.len ? j0.len : j1.len;
+    if (!most) return;
+    const u64 want = (most / 16 + 255) / 256 + 1;
+    hipLaunchKernelGGL(range_clip_kernel, dim3((u32)(want < 2048 ? want : 2048), 2), dim3(256), 0, stream, dst, edge, j0, j1);
+}
+
 size_t decode_walk_workspace_bytes(u64 srcSize)
 {
     const u64 nSeg = (srcSize + (1ull << kSegLog) - 1) >> kSegLog;

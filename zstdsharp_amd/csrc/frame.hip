@@ -97,6 +97,39 @@ __global__ __launch_bounds__(256) void batch_place_kernel(const ChunkMeta* __res
     entSize[e] = fits ? sum : (u64)0 - (u64)kErrDstSizeTooSmall;
 }
 
+// ---- seek table (ZSTDMI_CCtx_setSeekTable; the zstd seekable format) ----
+// entries: one (compressed size, content size) pair per frame of the pass, from the scan's offsets.  A frame is frameBlocks chunks
+// (the pass's last one may be shorter); the sizes are below 2^32 by construction (a frame holds at most 512 MiB of content).
+__global__ __launch_bounds__(256) void seek_entries_kernel(const u64* __restrict__ offsets, const u64* __restrict__ total, u32 nChunks, u32 frameBlocks,
+                                                           u32 chunkBytes, u64 passBytes, u32* __restrict__ entries)
+{
+    const u32 f = blockIdx.x * 256 + threadIdx.x;
+    const u32 nFrames = (nChunks + frameBlocks - 1) / frameBlocks;
+    if (f >= nFrames) return;
+    const u64 first = (u64)f * frameBlocks, next = first + frameBlocks;
+    const u64 cEnd = next < nChunks ? offsets[next] : *total;
+    const u64 span = (u64)frameBlocks * chunkBytes, at = (u64)f * span;
+    entries[2 * (u64)f] = (u32)(cEnd - offsets[first]);
+    entries[2 * (u64)f + 1] = (u32)((passBytes - at) < span ? (passBytes - at) : span);
+}
+
+// table: skippable header | n entries of 8 bytes | footer, one byte per lane (dst has no alignment to speak of)
+__global__ __launch_bounds__(256) void seek_table_kernel(const u32* __restrict__ entries, u32 n, u8* __restrict__ dst)
+{
+    const u64 bytes = 17 + 8 * (u64)n;
+    const u64 i = (u64)blockIdx.x * 256 + threadIdx.x;
+    if (i >= bytes) return;
+    u32 word; u32 k;
+    if (i < 8) { word = i < 4 ? 0x184D2A5Eu : (u32)(bytes - 8); k = (u32)i & 3; }
+    else if (i < 8 + 8 * (u64)n) { word = entries[(i - 8) >> 2]; k = (u32)i & 3; }
+    else {
+        const u32 j = (u32)(i - 8 - 8 * (u64)n);        // footer: count (4) | descriptor 0 | magic (4)
+        if (j == 4) { dst[i] = 0; return; }
+        word = j < 4 ? n : 0x8F92EAB1u; k = j < 4 ? j : j - 5;
+    }
+    dst[i] = (u8)(word >> (8 * k));
+}
+
 // ---- XXH64 (seed 0): 4 lanes per chunk, one per accumulator ----
 constexpr u64 P1 = 0x9E3779B185EBCA87ULL, P2 = 0xC2B2AE3D27D4EB4FULL, P3 = 0x165667B19E3779F9ULL,
               P4 = 0x85EBCA77C2B2AE63ULL, P5 = 0x27D4EB2F165667C5ULL;
@@ -152,6 +185,17 @@ void launch_xxh64(const u8* src, u64 srcSize, ChunkMeta* meta, u32 nChunks, u32 
     if (frameBlocks != 1) chunkLens = nullptr;
     const u32 nFrames = (nChunks + frameBlocks - 1) / frameBlocks;
     hipLaunchKernelGGL(xxh64_kernel, dim3((nFrames * 4 + 255) / 256), dim3(256), 0, stream, src, srcSize, meta, nChunks, chunkBytes, frameBlocks, chunkLens);
+}
+void launch_seek_entries(const u64* offsets, const u64* total, u32 nChunks, u32 frameBlocks, u32 chunkBytes, u64 passBytes, u32* entries, hipStream_t stream)
+{
+    if (!frameBlocks) frameBlocks = 1;
+    const u32 nFrames = (nChunks + frameBlocks - 1) / frameBlocks;
+    hipLaunchKernelGGL(seek_entries_kernel, dim3((nFrames + 255) / 256), dim3(256), 0, stream, offsets, total, nChunks, frameBlocks, chunkBytes, passBytes, entries);
+}
+void launch_seek_table(const u32* entries, u32 n, u8* dst, hipStream_t stream)
+{
+    const u64 bytes = 17 + 8 * (u64)n;
+    hipLaunchKernelGGL(seek_table_kernel, dim3((u32)((bytes + 255) / 256)), dim3(256), 0, stream, entries, n, dst);
 }
 void launch_batch_stage(const u64* from, const u32* len, u8* stage, u32 nChunks, u32 chunkBytes, hipStream_t stream)
 {

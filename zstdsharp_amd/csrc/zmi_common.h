@@ -155,6 +155,20 @@ struct BatchEntryOut {
     u32 pad;            // kBatchAlone: the single-call path decodes it afterwards (a frame without a content size, a very large entry)
 };
 
+// A range of a seekable stream (ZSTDMI_decompressRange): what seek_select_kernel makes of the seek table and (offset, length), and
+// what range_check_kernel finds after the decode — u64 words, read back by the host in one copy each.  "Selected" = the table entries
+// from the first to the last one with content that meets the range; cLo / cHi = the compressed bytes they span.
+enum : u32 { kSeekErr = 0, kSeekTotal = 1,      // the table's error (0 = none); content bytes of the whole stream
+             kSeekMeet = 2,                     // entries with content that meet the range
+             kSeekFirst = 3, kSeekLast = 4,     // their first and last index in the table
+             kSeekCLo = 5, kSeekCHi = 6,
+             kSeekDFirst = 7, kSeekSizeFirst = 8, kSeekDLast = 9, kSeekSizeLast = 10,      // content offset and size of the first and the last
+             kSeekKey = 11,                     // range_check: entry index << 16 | error of the first failing entry (all ones = none)
+             kSeekAlone = 12,                   // range_check: entries left to the single-call path
+             kSeekWords = 16 };
+// one copy of range_clip_kernel: bytes [from, from + len) of the edge buffer to dst + to
+struct ClipJob { u64 from, to, len; };
+
 // status words shared by the decoder's kernels and the host
 enum : u32 { kStFrames = 0, kStErr = 1, kStTotalLo = 2, kStTotalHi = 3, kStUsable = 4, kStUnsized = 5, kStBlocks = 6, kStSeqLo = 8, kStSeqHi = 9,
              kStErrKeyLo = 10, kStErrKeyHi = 11, kStActualLo = 12, kStActualHi = 13,

@@ -36,6 +36,8 @@ void launch_xxh64(const u8* src, u64 srcSize, ChunkMeta* meta, u32 nChunks, u32 
 void launch_batch_stage(const u64* from, const u32* len, u8* stage, u32 nChunks, u32 chunkBytes, hipStream_t stream);
 void launch_batch_place(const ChunkMeta* meta, u32 nEntries, const u32* entFirst, const u64* entDst, const u64* entCap, u64 span, u64* offsets, u64* entSize,
                         hipStream_t stream);
+void launch_seek_entries(const u64* offsets, const u64* total, u32 nChunks, u32 frameBlocks, u32 chunkBytes, u64 passBytes, u32* entries, hipStream_t stream);
+void launch_seek_table(const u32* entries, u32 n, u8* dst, hipStream_t stream);
 // long-distance matching (ldm.hip)
 size_t ldm_small_bytes(u64 n);
 size_t ldm_big_bytes(u64 nSplits);
@@ -52,6 +54,11 @@ void launch_frame_walk_serial(const u8* src, u64 srcSize, FrameDesc* frames, Blo
 void launch_batch_walk_count(const u8* src, const BatchEntryIn* in, BatchEntryOut* out, u32 nEntries, u32 dictID, u64 aloneAbove, u32* status, hipStream_t stream);
 void launch_batch_walk_emit(const u8* src, const BatchEntryIn* in, const BatchEntryOut* out, u32 nEntries, FrameDesc* frames, BlockDesc* blocks, hipStream_t stream);
 void launch_batch_fold(BatchEntryOut* out, u32 nEntries, const u64* keys, hipStream_t stream);
+void launch_seek_select(const u8* tab, u64 tableBytes, u32 n, u32 stride, u64 srcSize, u64 offset, u64 length, u64* sum, hipStream_t stream);
+void launch_seek_emit(const u8* tab, u32 stride, u32 first, u32 nSel, u64 dFirst, u64 offset, u64 dstBias, u64 edgeBias, u64 slot1, u32 cutFirst, u32 cutLast,
+                      BatchEntryIn* out, hipStream_t stream);
+void launch_range_check(const BatchEntryIn* in, const BatchEntryOut* out, u32 nEntries, u64* sum, hipStream_t stream);
+void launch_range_clip(u8* dst, const u8* edge, ClipJob j0, ClipJob j1, hipStream_t stream);
 void launch_seq_stats(const Seq* seqs, const u8* lits, const ChunkMeta* meta, u32 nChunks, const u8* src, u32 chunkBytes, u32* stats, hipStream_t stream);
 void launch_dict_parse(const u8* dict, u32 dictSize, DictInfo* out, hipStream_t stream);
 void launch_block_prepass(const u8* src, FrameDesc* frames, BlockDesc* blocks, u32 nFrames, u32 nBlocks, u32 haveDict, u32 earlyLiterals, u32* status, hipStream_t stream);
@@ -180,6 +187,10 @@ struct ZSTD_CCtx_s {
     DevBuf gatherIn, gatherOut;     // a many-range plan: the ranges of a kind side by side, and their output (compress_plan)
     DevBuf batchStage, batchTab;    // a batch of independent entries: their chunks at chunk boundaries, and the pass's tables (compress_entries)
     int lastBatchAlone = 0;         // entries of the last ZSTDMI_compressBatch that went through the single-call path (debug hook)
+    // ZSTDMI_CCtx_setSeekTable: one (compressed size, content size) pair per frame, filed on the device by every pass of a call
+    // (seekOn: this call files them) at the running index seekCount; compress_device writes the table behind the frames from them
+    int seekTable = 0; bool seekOn = false; u32 seekCount = 0;
+    DevBuf seekEntries, seekSort;
 };
 // History per chunk lives in LDS beside the chunk: up to 32 KiB of dictionary in front of 32 KiB chunks, or up to 60 KiB when
 // the whole input fits behind it in one chunk (small records, the usual dictionary case).
@@ -206,6 +217,8 @@ struct ZSTD_DCtx_s {
     DevBuf frames, blocks, recs, status, scratch, walkWs, slowFlags, stageSrc, stageDst, origin, originList;
     DevBuf batchIn, batchOut, blockKeys;    // ZSTDMI_decompressBatch: the entries' table, what the batch walk made of them, one error key per block
     int lastBatchAlone = 0;     // entries of the last ZSTDMI_decompressBatch that were decoded by the single-call path (debug hook)
+    DevBuf seekTab, seekSum, edge;          // ZSTDMI_decompressRange: a host source's seek table, the summary words, the frames the range cuts
+    int lastRangeFrames = 0; long long lastRangeStaged = 0;     // table entries the last range call decoded, bytes it copied host -> device (debug hooks)
     int originMode = 0;         // ZSTDMI_DCtx_setLongFrames: 0 = by cost (see decompress_device), 1 = never, 2 = every frame of 1 MiB or more
     StageTimer timer;
     // streaming adapter (ZSTD_decompressStream): whole frames are collected on the host, decoded in batches
@@ -257,11 +270,13 @@ struct CallParams {
     int minMatch = 0, chainLog = 0;     // accepted by the setters only at the value the kernels implement for the level/strategy in force THEN: checked again per call
     int ldm = 0, ldmHashLog = 0, ldmMinMatch = 0, ldmBucketSizeLog = 0, ldmHashRateLog = 0;     // (ZSTD_compressCCtx: all 0, as the reference's level-only parameters)
     bool useDict = true;
+    bool seek = false;                  // append a seek table (ZSTDMI_CCtx_setSeekTable; ZSTD_compressCCtx: never, as it never runs LDM)
 };
 static CallParams sticky_params(const ZSTD_CCtx* c)
 {
     CallParams p; p.level = c->level; p.checksumFlag = c->checksumFlag; p.contentSizeFlag = c->contentSizeFlag; p.dictIDFlag = c->dictIDFlag;
     p.strategy = c->strategy; p.targetLength = c->targetLength; p.windowLog = c->windowLog; p.searchLog = c->searchLog; p.minMatch = c->minMatch; p.chainLog = c->chainLog; p.useDict = true;
+    p.seek = c->seekTable != 0;
     p.ldm = c->ldm; p.ldmHashLog = c->ldmHashLog; p.ldmMinMatch = c->ldmMinMatch; p.ldmBucketSizeLog = c->ldmBucketSizeLog; p.ldmHashRateLog = c->ldmHashRateLog;
     return p;
 }
@@ -505,6 +520,12 @@ static size_t compress_range(ZSTD_CCtx* c, const CallParams& cp, u8* d_dst, size
         if (cp.checksumFlag) { launch_xxh64(src, n, meta, nChunks, chunkBytes, frameBlocks, s);             c->timer.mark("xxh64", s); }
         launch_seq_encode(seqs, meta, slots, nChunks, strategy, (cp.checksumFlag ? 1u : 0u) | (cp.contentSizeFlag ? 0u : 2u) | (hdrWindow << 8), 1, dictID, dictIdBytes, initReps, frameBlocks, chunkBytes, n, s);   c->timer.mark("seq_encode", s);
         launch_scan_sizes(meta, nChunks, offsets, total, s);                       c->timer.mark("scan", s);
+        if (c->seekOn) {        // the pass's frames into the call's seek table
+            const u32 nFrames = (nChunks + (frameBlocks ? frameBlocks : 1u) - 1) / (frameBlocks ? frameBlocks : 1u);
+            if (((size_t)c->seekCount + nFrames) * 8 > c->seekEntries.cap) return ZERR(kErrGeneric);
+            launch_seek_entries(offsets, total, nChunks, frameBlocks, chunkBytes, n, (u32*)c->seekEntries.p + 2 * (size_t)c->seekCount, s);
+            c->seekCount += nFrames;
+        }
         const size_t room = dstCapacity > produced ? dstCapacity - produced : 0;
         // the literals section (most of the output) is encoded straight into its final place; gather moves the rest
         launch_huf_encode(lits, meta, tables, slots, d_dst + produced, offsets, room, nChunks, src, chunkBytes, s);   c->timer.mark("huf_encode", s);
@@ -651,7 +672,9 @@ static size_t compress_plan(ZSTD_CCtx* c, const CallParams& cp, const std::vecto
           fill[k] += r.len;
       } }
     size_t got[2] = {0, 0};
+    u32 seekAt[3] = { c->seekCount, c->seekCount, c->seekCount };      // where each kind's seek-table entries begin (and where they end)
     for (int k = 0; k < 2; ++k) {
+        seekAt[k] = c->seekCount;
         if (!len[k]) continue;
         marks[k].assign(markAt[k].size(), 0);
         const u8* in = (const u8*)c->gatherIn.p + inAt[k];
@@ -659,6 +682,26 @@ static size_t compress_plan(ZSTD_CCtx* c, const CallParams& cp, const std::vecto
         const size_t n = compress_range(c, k ? cpSparse : cp, (u8*)c->gatherOut.p + outAt[k], bound[k], in, len[k], paramSize, first, &markAt[k], &marks[k]);
         if (isErr(n)) return n;
         got[k] = n;
+    }
+    seekAt[2] = c->seekCount;
+    if (c->seekOn && seekAt[2] > seekAt[0]) {
+        // the seek-table entries were filed kind by kind: into the order of the input, range by range (a range starts at a frame of its
+        // kind's framing, so its first entry is its start in the kind's input over that framing's span)
+        const size_t bytes = (size_t)(seekAt[2] - seekAt[0]) * 8;
+        u8* const ent = (u8*)c->seekEntries.p + (size_t)seekAt[0] * 8;
+        if (!c->seekSort.ensure(bytes)) return ZERR(kErrMemoryAllocation);
+        if (hipMemcpyAsync(c->seekSort.p, ent, bytes, hipMemcpyDeviceToDevice, c->stream) != hipSuccess) return ZERR(kErrGeneric);
+        const size_t span[2] = { resolve_framing(c, cp, paramSize).span(), resolve_framing(c, cpSparse, paramSize).span() };
+        const size_t kindEnd[2] = { (size_t)(seekAt[1] - seekAt[0]), (size_t)(seekAt[2] - seekAt[0]) };
+        size_t at = 0, seenK[2] = {0, 0};
+        for (size_t r = 0; r < R; ++r) {
+            const int k = plan[r].sparse;
+            const size_t i = seenK[k]++;
+            const size_t base = k ? kindEnd[0] : 0;
+            const size_t lo = base + markAt[k][i] / span[k], hi = i + 1 < markAt[k].size() ? base + markAt[k][i + 1] / span[k] : kindEnd[k];
+            if (hi > lo && hipMemcpyAsync(ent + at * 8, (const u8*)c->seekSort.p + lo * 8, (hi - lo) * 8, hipMemcpyDeviceToDevice, c->stream) != hipSuccess) return ZERR(kErrGeneric);
+            at += hi - lo;
+        }
     }
     if (got[0] + got[1] > dstCapacity) return ZERR(kErrDstSizeTooSmall);
     size_t pos = 0, seen[2] = {0, 0};
@@ -674,7 +717,7 @@ static size_t compress_plan(ZSTD_CCtx* c, const CallParams& cp, const std::vecto
     return pos;
 }
 
-static size_t compress_device(ZSTD_CCtx* c, const CallParams& cp, u8* d_dst, size_t dstCapacity, const u8* d_src, size_t srcSize)
+static size_t compress_frames(ZSTD_CCtx* c, const CallParams& cp, u8* d_dst, size_t dstCapacity, const u8* d_src, size_t srcSize)
 {
     bool first = true;
     { const size_t e = check_call_params(cp); if (isErr(e)) return e; }
@@ -689,6 +732,37 @@ static size_t compress_device(ZSTD_CCtx* c, const CallParams& cp, u8* d_dst, siz
     plan_ranges(counts, group, srcSize, plan);
     if (plan.size() == 1) { CallParams one = cp; if (plan[0].sparse) one.level = 1; return compress_range(c, one, d_dst, dstCapacity, d_src, srcSize, srcSize, first); }
     return compress_plan(c, cp, plan, srcSize, d_dst, dstCapacity, d_src, first);
+}
+
+// Seek table (the zstd seekable format: a skippable frame behind the last frame).  Frames a call can write: the smallest framing is a
+// frame per 4 KiB of content (a 60 KiB dictionary in front of 4 KiB chunks); windows below 64 KiB share 64 KiB frames; every pass
+// and every range of a plan ends on a frame boundary except the call's tail.  So a call of srcSize bytes writes at most
+// srcSize / 4096 + 1 frames (the + 1: the tail's partial frame, or the one frame of an empty input), each an 8-byte entry, behind
+// an 8-byte skippable header and in front of the 9-byte footer.
+static size_t seek_max_frames(size_t srcSize) { return srcSize / 4096 + 1; }
+static size_t seek_table_bound(size_t srcSize) { return 17 + 8 * seek_max_frames(srcSize); }
+
+// one call over device-resident buffers: the frames and, when the call asks for it, the seek table behind them
+static size_t compress_device(ZSTD_CCtx* c, const CallParams& cp, u8* d_dst, size_t dstCapacity, const u8* d_src, size_t srcSize)
+{
+    if (!cp.seek) return compress_frames(c, cp, d_dst, dstCapacity, d_src, srcSize);
+    if (!c->seekEntries.ensure(seek_max_frames(srcSize) * 8)) return ZERR(kErrMemoryAllocation);
+    struct On { ZSTD_CCtx* c; ~On() { c->seekOn = false; } } on{c};
+    c->seekOn = true; c->seekCount = 0;
+    const size_t r = compress_frames(c, cp, d_dst, dstCapacity, d_src, srcSize);
+    if (isErr(r)) return r;
+    hipStream_t s = c->stream;
+    if (srcSize == 0) {         // the one empty frame: the host wrote it and knows its size
+        const u32 e[2] = { (u32)r, 0 };
+        if (hipMemcpyAsync(c->seekEntries.p, e, sizeof e, hipMemcpyHostToDevice, s) != hipSuccess) return ZERR(kErrGeneric);
+        if (hipStreamSynchronize(s) != hipSuccess) { (void)hipGetLastError(); return ZERR(kErrGeneric); }
+        c->seekCount = 1;
+    }
+    const size_t tableBytes = 17 + 8 * (size_t)c->seekCount;
+    if (tableBytes > dstCapacity - r) return ZERR(kErrDstSizeTooSmall);
+    launch_seek_table((const u32*)c->seekEntries.p, c->seekCount, d_dst + r, s);
+    if (hipStreamSynchronize(s) != hipSuccess) { (void)hipGetLastError(); return ZERR(kErrGeneric); }
+    return r + tableBytes;
 }
 
 
@@ -706,7 +780,7 @@ size_t ZSTD_freeCCtx(ZSTD_CCtx* c)
         (void)hipSetDevice(c->device);
         if (c->ownStream) (void)hipStreamSynchronize(c->ownStream);
         c->seqs.release(); c->lits.release(); c->meta.release(); c->tables.release(); c->slots.release(); c->cand.release(); c->probe.release();
-        c->gatherIn.release(); c->gatherOut.release(); c->batchStage.release(); c->batchTab.release(); c->ldmSmall.release(); c->ldmBig.release(); c->offsets.release(); c->total.release(); c->stageSrc.release(); c->stageDst.release(); c->dict.release(); c->dictFullDev.release(); c->dictInfoDev.release();
+        c->gatherIn.release(); c->gatherOut.release(); c->batchStage.release(); c->batchTab.release(); c->ldmSmall.release(); c->ldmBig.release(); c->offsets.release(); c->total.release(); c->seekEntries.release(); c->seekSort.release(); c->stageSrc.release(); c->stageDst.release(); c->dict.release(); c->dictFullDev.release(); c->dictInfoDev.release();
         c->timer.destroy();
         if (c->ownStream) (void)hipStreamDestroy(c->ownStream);
     }
@@ -848,6 +922,7 @@ static size_t ZSTDMI_compressDevice_impl(ZSTD_CCtx* c, void* d_dst, size_t dstCa
     if (srcSize && !d_src) return ZERR(kErrSrcSizeWrong);
     if (!d_dst && dstCapacity) return ZERR(kErrDstBufferNull);
     if (!d_dst) return ZERR(kErrDstSizeTooSmall);
+    if (c->workers.size() > 1 && c->seekTable) return ZERR(kErrParameterUnsupported);       // (the workers' shares have no common table)
     if (c->workers.size() > 1 && srcSize) return compress_multi(c, sticky_params(c), d_dst, dstCapacity, d_src, srcSize);
     return compress_device(c, sticky_params(c), (u8*)d_dst, dstCapacity, (const u8*)d_src, srcSize);
 }
@@ -857,6 +932,7 @@ static size_t compress_any(ZSTD_CCtx* c, const CallParams& cp, void* dst, size_t
     size_t e = cctx_bind(c); if (isErr(e)) return e;
     if (srcSize && !src) return ZERR(kErrSrcSizeWrong);
     if (!dst) return ZERR(kErrDstSizeTooSmall);
+    if (c->workers.size() > 1 && cp.seek) return ZERR(kErrParameterUnsupported);
     if (c->workers.size() > 1 && srcSize) return compress_multi(c, cp, dst, dstCapacity, src, srcSize);
     const bool srcDev = srcSize ? is_device_ptr(src) : true, dstDev = is_device_ptr(dst);
     const u8* d_src = (const u8*)src; u8* d_dst = (u8*)dst;
@@ -867,7 +943,7 @@ static size_t compress_any(ZSTD_CCtx* c, const CallParams& cp, void* dst, size_t
         d_src = (const u8*)c->stageSrc.p;
     }
     if (!dstDev) {
-        const size_t worst = ZSTD_compressBound(srcSize) + 32;
+        const size_t worst = ZSTD_compressBound(srcSize) + 32 + (cp.seek ? seek_table_bound(srcSize) : 0);
         devCap = dstCapacity < worst ? dstCapacity : worst;
         if (!c->stageDst.ensure(devCap + 64)) return ZERR(kErrMemoryAllocation);
         d_dst = (u8*)c->stageDst.p;
@@ -916,7 +992,7 @@ size_t ZSTD_freeDCtx(ZSTD_DCtx* d)
     if (d->deviceOk) {
         (void)hipSetDevice(d->device);
         if (d->ownStream) (void)hipStreamSynchronize(d->ownStream);
-        d->frames.release(); d->blocks.release(); d->recs.release(); d->status.release(); d->scratch.release(); d->walkWs.release(); d->slowFlags.release(); d->stageSrc.release(); d->stageDst.release(); d->dict.release(); d->dictInfoDev.release(); d->origin.release(); d->originList.release(); d->batchIn.release(); d->batchOut.release(); d->blockKeys.release();
+        d->frames.release(); d->blocks.release(); d->recs.release(); d->status.release(); d->scratch.release(); d->walkWs.release(); d->slowFlags.release(); d->stageSrc.release(); d->stageDst.release(); d->dict.release(); d->dictInfoDev.release(); d->origin.release(); d->originList.release(); d->batchIn.release(); d->batchOut.release(); d->blockKeys.release(); d->seekTab.release(); d->seekSum.release(); d->edge.release();
         d->timer.destroy();
         if (d->aux) { (void)hipStreamSynchronize(d->aux); (void)hipStreamDestroy(d->aux); }
         if (d->auxDone) (void)hipEventDestroy(d->auxDone);
@@ -1265,6 +1341,46 @@ static size_t decompress_device(ZSTD_DCtx* d, u8* d_dst, size_t dstCapacity, con
 // global by construction) or more than kBatchAloneAbove compressed bytes (one lane walks an entry's block headers) is decoded alone
 // afterwards by decompress_device, and counted.
 constexpr u64 kBatchAloneAbove = (u64)4 << 20;
+// the batch's core over a device-resident entry table (d->batchIn, n entries; d->batchOut gets what the walk and the decoder make of
+// them): batch_walk_count -> batch_scan -> batch_walk_emit -> decode_lists -> batch_fold.  `readBack` enqueues the caller's copy of
+// whatever it wants of d->batchOut: called in front of each of the two host synchronisations that see final entries (after the
+// count: entries without frames are final; after the fold: all are).  -> 0, or the error of the whole run.
+static size_t decode_entries(ZSTD_DCtx* d, const DecodeDict& dd, const u8* srcBase, u8* dstBase, size_t dstSpan, u32 n, const std::function<bool()>& readBack)
+{
+    hipStream_t s = d->stream;
+    if (!d->status.ensure(kStWords * sizeof(u32))) return ZERR(kErrMemoryAllocation);
+    u32* status = (u32*)d->status.p;
+    const BatchEntryIn* dIn = (const BatchEntryIn*)d->batchIn.p; BatchEntryOut* dOut = (BatchEntryOut*)d->batchOut.p;
+    u32 init[kStWords] = {}; init[kStErrKeyLo] = 0xFFFFFFFFu; init[kStErrKeyHi] = 0xFFFFFFFFu;
+    u32 st[kStWords] = {};
+    if (hipMemcpyAsync(status, init, sizeof init, hipMemcpyHostToDevice, s) != hipSuccess) return ZERR(kErrGeneric);
+    launch_batch_walk_count(srcBase, dIn, dOut, n, dd.dictID, kBatchAloneAbove, status, s);
+    if (!readBack() ||
+        hipMemcpyAsync(st, status, sizeof st, hipMemcpyDeviceToHost, s) != hipSuccess) return ZERR(kErrGeneric);
+    if (hipStreamSynchronize(s) != hipSuccess) { (void)hipGetLastError(); return ZERR(kErrGeneric); }
+    if (st[kStErr]) return ZERR(st[kStErr]);
+    const u32 nFrames = st[kStFrames], nBlocks = st[kStBlocks];
+    const u64 total = (u64)st[kStTotalLo] | ((u64)st[kStTotalHi] << 32);
+    u32 keyWords[2] = {0, 0};
+    if (nFrames) {
+        if (!d->frames.ensure((size_t)nFrames * sizeof(FrameDesc)) || !d->blocks.ensure((size_t)nBlocks * sizeof(BlockDesc) + 64) ||
+            !d->scratch.ensure((size_t)total + (size_t)nFrames * kLitSkew + 256) || !d->slowFlags.ensure((size_t)nBlocks + 64) ||
+            !d->blockKeys.ensure((size_t)nBlocks * sizeof(u64) + 8)) return ZERR(kErrMemoryAllocation);
+        keyWords[0] = (u32)(uintptr_t)d->blockKeys.p; keyWords[1] = (u32)((u64)(uintptr_t)d->blockKeys.p >> 32);
+        if (hipMemsetAsync(d->blockKeys.p, 0xFF, (size_t)nBlocks * sizeof(u64), s) != hipSuccess ||
+            hipMemcpyAsync(status + kStBlockKeysLo, &keyWords[0], sizeof(u32), hipMemcpyHostToDevice, s) != hipSuccess ||
+            hipMemcpyAsync(status + kStBlockKeysHi, &keyWords[1], sizeof(u32), hipMemcpyHostToDevice, s) != hipSuccess) return ZERR(kErrGeneric);
+        launch_batch_walk_emit(srcBase, dIn, dOut, n, (FrameDesc*)d->frames.p, (BlockDesc*)d->blocks.p, s);
+        d->timer.mark("batch_walk", s);
+        const size_t e = decode_lists(d, dd, dstBase, srcBase, nFrames, nBlocks, 0, dstSpan, st, [&]() -> bool {
+            launch_batch_fold(dOut, n, (const u64*)d->blockKeys.p, s);
+            return readBack();
+        });
+        if (isErr(e)) return e;
+    }
+    return 0;
+}
+
 static size_t decompress_batch_impl(ZSTD_DCtx* d, const void* const* srcs, const size_t* srcSizes, size_t n, void* const* dsts, const size_t* dstCapacities, size_t* dstSizes)
 {
     if (!d) return ZERR(kErrGeneric);
@@ -1293,40 +1409,15 @@ static size_t decompress_batch_impl(ZSTD_DCtx* d, const void* const* srcs, const
         hIn[i].dstOff = dsts[i] ? (u64)((uintptr_t)dsts[i] - loD) : 0;
         hIn[i].dstCap = dsts[i] ? (u64)dstCapacities[i] : 0;
     }
-    if (!d->status.ensure(kStWords * sizeof(u32)) || !d->batchIn.ensure(n * sizeof(BatchEntryIn)) || !d->batchOut.ensure(n * sizeof(BatchEntryOut))) return ZERR(kErrMemoryAllocation);
-    u32* status = (u32*)d->status.p;
-    const u8* const srcBase = (const u8*)loS; u8* const dstBase = (u8*)loD;
-    const BatchEntryIn* dIn = (const BatchEntryIn*)d->batchIn.p; BatchEntryOut* dOut = (BatchEntryOut*)d->batchOut.p;
+    if (!d->batchIn.ensure(n * sizeof(BatchEntryIn)) || !d->batchOut.ensure(n * sizeof(BatchEntryOut))) return ZERR(kErrMemoryAllocation);
+    BatchEntryOut* dOut = (BatchEntryOut*)d->batchOut.p;
     std::vector<BatchEntryOut> hOut(n);
-    u32 init[kStWords] = {}; init[kStErrKeyLo] = 0xFFFFFFFFu; init[kStErrKeyHi] = 0xFFFFFFFFu;
-    u32 st[kStWords] = {};
     d->timer.begin(s);
-    if (hipMemcpyAsync(status, init, sizeof init, hipMemcpyHostToDevice, s) != hipSuccess ||
-        hipMemcpyAsync(d->batchIn.p, hIn.data(), n * sizeof(BatchEntryIn), hipMemcpyHostToDevice, s) != hipSuccess) return ZERR(kErrGeneric);
-    launch_batch_walk_count(srcBase, dIn, dOut, (u32)n, dd.dictID, kBatchAloneAbove, status, s);
-    if (hipMemcpyAsync(hOut.data(), dOut, n * sizeof(BatchEntryOut), hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipMemcpyAsync(st, status, sizeof st, hipMemcpyDeviceToHost, s) != hipSuccess) return ZERR(kErrGeneric);
-    if (hipStreamSynchronize(s) != hipSuccess) { (void)hipGetLastError(); return ZERR(kErrGeneric); }
-    if (st[kStErr]) return ZERR(st[kStErr]);
-    const u32 nFrames = st[kStFrames], nBlocks = st[kStBlocks];
-    const u64 total = (u64)st[kStTotalLo] | ((u64)st[kStTotalHi] << 32);
-    u32 keyWords[2] = {0, 0};
-    if (nFrames) {
-        if (!d->frames.ensure((size_t)nFrames * sizeof(FrameDesc)) || !d->blocks.ensure((size_t)nBlocks * sizeof(BlockDesc) + 64) ||
-            !d->scratch.ensure((size_t)total + (size_t)nFrames * kLitSkew + 256) || !d->slowFlags.ensure((size_t)nBlocks + 64) ||
-            !d->blockKeys.ensure((size_t)nBlocks * sizeof(u64) + 8)) return ZERR(kErrMemoryAllocation);
-        keyWords[0] = (u32)(uintptr_t)d->blockKeys.p; keyWords[1] = (u32)((u64)(uintptr_t)d->blockKeys.p >> 32);
-        if (hipMemsetAsync(d->blockKeys.p, 0xFF, (size_t)nBlocks * sizeof(u64), s) != hipSuccess ||
-            hipMemcpyAsync(status + kStBlockKeysLo, &keyWords[0], sizeof(u32), hipMemcpyHostToDevice, s) != hipSuccess ||
-            hipMemcpyAsync(status + kStBlockKeysHi, &keyWords[1], sizeof(u32), hipMemcpyHostToDevice, s) != hipSuccess) return ZERR(kErrGeneric);
-        launch_batch_walk_emit(srcBase, dIn, dOut, (u32)n, (FrameDesc*)d->frames.p, (BlockDesc*)d->blocks.p, s);
-        d->timer.mark("batch_walk", s);
-        e = decode_lists(d, dd, dstBase, srcBase, nFrames, nBlocks, 0, (size_t)(hiD - loD), st, [&]() -> bool {
-            launch_batch_fold(dOut, (u32)n, (const u64*)d->blockKeys.p, s);
-            return hipMemcpyAsync(hOut.data(), dOut, n * sizeof(BatchEntryOut), hipMemcpyDeviceToHost, s) == hipSuccess;
-        });
-        if (isErr(e)) return e;
-    }
+    if (hipMemcpyAsync(d->batchIn.p, hIn.data(), n * sizeof(BatchEntryIn), hipMemcpyHostToDevice, s) != hipSuccess) return ZERR(kErrGeneric);
+    e = decode_entries(d, dd, (const u8*)loS, (u8*)loD, (size_t)(hiD - loD), (u32)n, [&]() -> bool {
+        return hipMemcpyAsync(hOut.data(), dOut, n * sizeof(BatchEntryOut), hipMemcpyDeviceToHost, s) == hipSuccess;
+    });
+    if (isErr(e)) return e;
     d->timer.finish();
     for (size_t i = 0; i < n; i++) {
         if (srcSizes[i] && !srcs[i]) { dstSizes[i] = ZERR(kErrSrcSizeWrong); continue; }
@@ -1338,6 +1429,114 @@ static size_t decompress_batch_impl(ZSTD_DCtx* d, const void* const* srcs, const
         d->lastBatchAlone++;
     }
     return 0;
+}
+
+// ---- a byte range of a seekable stream (ZSTDMI_decompressRange) ----
+// The stream ends in a seek table (include/zstd_mi355x.h): one (compressed size, content size) pair per frame.  The host reads the
+// 9-byte footer (how long the table is); seek_select_kernel checks the rest of it and finds the entries whose content meets
+// [offset, offset + length) — one read-back of its summary words —; seek_emit_kernel turns those entries into the batch walk's table on
+// the device, and the batch's core (decode_entries) decodes them in one run: frames wholly inside the range straight to their place in
+// dst, the at most two frames the range cuts into an edge buffer, from which range_clip_kernel copies the wanted part.  An entry the
+// walk leaves to the single-call path (a frame without a content size, more than kBatchAloneAbove compressed bytes) is decoded by
+// decompress_device into the same place.  range_check_kernel holds every entry to the content size its table entry names.  A host
+// source is staged in two pieces only: the table, and the compressed bytes of the selected entries.
+static size_t decompress_range_impl(ZSTD_DCtx* d, void* dst, size_t dstCapacity, const void* src, size_t srcSize, unsigned long long offset, size_t length)
+{
+    size_t e = dctx_bind(d); if (isErr(e)) return e;
+    if (d->workers.size() > 1) return ZERR(kErrParameterUnsupported);
+    d->lastRangeFrames = 0; d->lastRangeStaged = 0;
+    if (srcSize && !src) return ZERR(kErrSrcSizeWrong);
+    if (srcSize < 17) return ZERR(kErrPrefixUnknown);
+    hipStream_t s = d->stream;
+    const bool srcDev = is_device_ptr(src), dstDev = dst ? is_device_ptr(dst) : false;
+    auto rd32 = [](const u8* p) { return (u32)p[0] | ((u32)p[1] << 8) | ((u32)p[2] << 16) | ((u32)p[3] << 24); };
+    u8 foot[9];
+    if (srcDev) {
+        if (hipMemcpyAsync(foot, (const u8*)src + srcSize - 9, 9, hipMemcpyDeviceToHost, s) != hipSuccess) return ZERR(kErrGeneric);
+        if (hipStreamSynchronize(s) != hipSuccess) { (void)hipGetLastError(); return ZERR(kErrGeneric); }
+    } else memcpy(foot, (const u8*)src + srcSize - 9, 9);
+    if (rd32(foot + 5) != 0x8F92EAB1u) return ZERR(kErrPrefixUnknown);
+    if (foot[4] & 0x7C) return ZERR(kErrCorruption);                    // reserved descriptor bits
+    const u32 N = rd32(foot);
+    if (N > (1u << 27)) return ZERR(kErrCorruption);
+    const u32 stride = (foot[4] & 0x80) ? 12u : 8u;                     // (checksums, where the table has them, are skipped)
+    const u64 tableBytes = 17 + (u64)N * stride;
+    if (tableBytes > srcSize) return ZERR(kErrCorruption);
+    e = dctx_sync_dictionary(d); if (isErr(e)) return e;
+    const DecodeDict dd = decode_dict(d);
+    if (!d->seekSum.ensure(kSeekWords * sizeof(u64))) return ZERR(kErrMemoryAllocation);
+    u64* const sum = (u64*)d->seekSum.p;
+    const u8* tab = (const u8*)src + (srcSize - tableBytes);
+    if (!srcDev) {
+        if (!d->seekTab.ensure((size_t)tableBytes + 64)) return ZERR(kErrMemoryAllocation);
+        if (hipMemcpyAsync(d->seekTab.p, tab, (size_t)tableBytes, hipMemcpyHostToDevice, s) != hipSuccess) return ZERR(kErrGeneric);
+        tab = (const u8*)d->seekTab.p; d->lastRangeStaged += (long long)tableBytes;
+    }
+    d->timer.begin(s);
+    launch_seek_select(tab, tableBytes, N, stride, srcSize, offset, length, sum, s);
+    u64 sm[kSeekWords] = {};
+    if (hipMemcpyAsync(sm, sum, sizeof sm, hipMemcpyDeviceToHost, s) != hipSuccess) return ZERR(kErrGeneric);
+    if (hipStreamSynchronize(s) != hipSuccess) { (void)hipGetLastError(); return ZERR(kErrGeneric); }
+    d->timer.mark("seek_select", s);
+    if (sm[kSeekErr]) return ZERR((u32)sm[kSeekErr]);
+    const u64 total = sm[kSeekTotal];
+    const u64 returned = offset < total ? ((u64)length < total - offset ? (u64)length : total - offset) : 0;
+    if (returned > dstCapacity) return ZERR(kErrDstSizeTooSmall);
+    if (!returned) { d->timer.finish(); return 0; }
+    if (!dst) return ZERR(kErrDstBufferNull);
+    const u64 nMeet = sm[kSeekMeet];
+    if (!nMeet || sm[kSeekLast] < sm[kSeekFirst]) return ZERR(kErrCorruption);
+    const u32 first = (u32)sm[kSeekFirst], last = (u32)sm[kSeekLast], nSel = last - first + 1;
+    const u64 cLo = sm[kSeekCLo], cHi = sm[kSeekCHi], end = offset + returned;
+    const u64 dFirst = sm[kSeekDFirst], sizeFirst = sm[kSeekSizeFirst], dLast = sm[kSeekDLast], sizeLast = sm[kSeekSizeLast];
+    const bool cutFirst = dFirst < offset || dFirst + sizeFirst > end, cutLast = last != first && dLast + sizeLast > end;
+    const u64 slot1 = cutFirst ? ((sizeFirst + 255) & ~(u64)255) : 0, edgeBytes = slot1 + (cutLast ? sizeLast : 0);
+    if (edgeBytes && !d->edge.ensure((size_t)edgeBytes + 64)) return ZERR(kErrMemoryAllocation);
+    const u8* srcBase = (const u8*)src + cLo;
+    if (!srcDev) {              // only the selected frames travel
+        if (!d->stageSrc.ensure((size_t)(cHi - cLo) + 64)) return ZERR(kErrMemoryAllocation);
+        if (hipMemcpyAsync(d->stageSrc.p, (const u8*)src + cLo, (size_t)(cHi - cLo), hipMemcpyHostToDevice, s) != hipSuccess) return ZERR(kErrGeneric);
+        srcBase = (const u8*)d->stageSrc.p; d->lastRangeStaged += (long long)(cHi - cLo);
+    }
+    u8* d_dst = (u8*)dst;
+    if (!dstDev) { if (!d->stageDst.ensure((size_t)returned + 64)) return ZERR(kErrMemoryAllocation); d_dst = (u8*)d->stageDst.p; }
+    // one base pointer for the destinations, the lowest: dst or the edge buffer
+    const uintptr_t pD = (uintptr_t)d_dst, pE = edgeBytes ? (uintptr_t)d->edge.p : pD;
+    const uintptr_t lo = pD < pE ? pD : pE, hi = (pD + returned > pE + edgeBytes) ? pD + (uintptr_t)returned : pE + (uintptr_t)edgeBytes;
+    if (!d->batchIn.ensure((size_t)nSel * sizeof(BatchEntryIn)) || !d->batchOut.ensure((size_t)nSel * sizeof(BatchEntryOut))) return ZERR(kErrMemoryAllocation);
+    launch_seek_emit(tab, stride, first, nSel, dFirst, offset, (u64)(pD - lo), (u64)(pE - lo), slot1, cutFirst ? 1u : 0u, cutLast ? 1u : 0u, (BatchEntryIn*)d->batchIn.p, s);
+    d->timer.mark("seek_emit", s);
+    e = decode_entries(d, dd, srcBase, (u8*)lo, (size_t)(hi - lo), nSel, [] { return true; });
+    if (isErr(e)) return e;
+    launch_range_check((const BatchEntryIn*)d->batchIn.p, (const BatchEntryOut*)d->batchOut.p, nSel, sum, s);
+    if (hipMemcpyAsync(sm, sum, sizeof sm, hipMemcpyDeviceToHost, s) != hipSuccess) return ZERR(kErrGeneric);
+    if (hipStreamSynchronize(s) != hipSuccess) { (void)hipGetLastError(); return ZERR(kErrGeneric); }
+    if (sm[kSeekKey] != ~0ull) return ZERR((u32)(sm[kSeekKey] & 0xFFFFu));
+    if (sm[kSeekAlone]) {       // (rare: the entries come to the host only then)
+        std::vector<BatchEntryIn> hIn(nSel); std::vector<BatchEntryOut> hOut(nSel);
+        if (hipMemcpyAsync(hIn.data(), d->batchIn.p, (size_t)nSel * sizeof(BatchEntryIn), hipMemcpyDeviceToHost, s) != hipSuccess ||
+            hipMemcpyAsync(hOut.data(), d->batchOut.p, (size_t)nSel * sizeof(BatchEntryOut), hipMemcpyDeviceToHost, s) != hipSuccess) return ZERR(kErrGeneric);
+        if (hipStreamSynchronize(s) != hipSuccess) { (void)hipGetLastError(); return ZERR(kErrGeneric); }
+        for (u32 i = 0; i < nSel; ++i) {
+            if (hOut[i].state != kBatchAlone) continue;
+            const size_t r = decompress_device(d, (u8*)lo + hIn[i].dstOff, (size_t)hIn[i].dstCap, srcBase + hIn[i].srcOff, (size_t)hIn[i].srcSize);
+            if (isErr(r)) return r == ZERR(kErrDstSizeTooSmall) ? ZERR(kErrCorruption) : r;
+            if (r != hIn[i].dstCap) return ZERR(kErrCorruption);
+        }
+    }
+    if (edgeBytes) {
+        ClipJob j0 = {0, 0, 0}, j1 = {0, 0, 0};
+        if (cutFirst) { const u64 from = offset > dFirst ? offset - dFirst : 0, stop = dFirst + sizeFirst < end ? dFirst + sizeFirst : end;
+                        j0.from = from; j0.to = dFirst + from - offset; j0.len = stop - (dFirst + from); }
+        if (cutLast) { j1.from = slot1; j1.to = dLast - offset; j1.len = end - dLast; }
+        launch_range_clip(d_dst, (const u8*)d->edge.p, j0, j1, s);
+        d->timer.mark("range_clip", s);
+    }
+    if (!dstDev && hipMemcpyAsync(dst, d_dst, (size_t)returned, hipMemcpyDeviceToHost, s) != hipSuccess) return ZERR(kErrGeneric);
+    if (hipStreamSynchronize(s) != hipSuccess) { (void)hipGetLastError(); return ZERR(kErrGeneric); }
+    d->timer.finish();
+    d->lastRangeFrames = (int)nMeet;
+    return (size_t)returned;
 }
 
 static size_t decompress_multi(ZSTD_DCtx* d, void* dst, size_t dstCapacity, const void* src, size_t srcSize);
@@ -1621,6 +1820,7 @@ static size_t ZSTD_compressStream2_impl(ZSTD_CCtx* c, ZSTD_outBuffer* output, ZS
     if (output->pos > output->size) return ZERR(104);          // dstBuffer_wrong
     if (input->pos > input->size) return ZERR(105);            // srcBuffer_wrong
     if ((unsigned)endOp > 2) return ZERR(kErrParameterOutOfBound);
+    if (c->seekTable) return ZERR(kErrParameterUnsupported);   // (a table per batch of the session would not be one table of the stream)
     if (input->size > input->pos && !input->src) return ZERR(kErrSrcSizeWrong);
     if (output->size > output->pos && !output->dst) return ZERR(kErrDstBufferNull);
     if (cstream_drain(c, output)) return c->sOut.size() - c->sOutPos;       // output full: nothing consumed this time
@@ -1751,6 +1951,8 @@ size_t ZSTDMI_CCtx_setHistory(ZSTD_CCtx* c, int bytes, unsigned frameBytes)
     if (!c || bytes > (48 << 10) || (frameBytes && (frameBytes < kChunkSize || frameBytes > (16u << 20)))) return ZERR(kErrParameterOutOfBound);
     c->historyBytes = bytes; if (frameBytes) c->frameBytes = frameBytes; return 0;
 }
+size_t ZSTDMI_CCtx_setSeekTable(ZSTD_CCtx* c, unsigned mode) { if (!c) return ZERR(kErrGeneric); if (mode > 1) return ZERR(kErrParameterOutOfBound); c->seekTable = (int)mode; return 0; }
+size_t ZSTDMI_seekTableBound(size_t srcSize) { return seek_table_bound(srcSize); }
 size_t ZSTDMI_CCtx_setParser(ZSTD_CCtx* c, unsigned mode) { if (!c || mode > 1) return ZERR(kErrParameterOutOfBound); c->parser = mode; return 0; }
 size_t ZSTDMI_CCtx_setProfiling(ZSTD_CCtx* c, int en) { if (!c) return ZERR(kErrGeneric); c->timer.enabled = en != 0; return 0; }
 size_t ZSTDMI_DCtx_setProfiling(ZSTD_DCtx* d, int en) { if (!d) return ZERR(kErrGeneric); d->timer.enabled = en != 0; return 0; }
@@ -1838,6 +2040,13 @@ size_t ZSTDMI_decompressBatch(ZSTD_DCtx* d, const void* const* srcs, const size_
     return guarded([&] { return decompress_batch_impl(d, srcs, srcSizes, n, dsts, dstCapacities, dstSizes); });
 }
 int ZSTDMI_debugLastBatchAloneD(const ZSTD_DCtx* d) { return d ? d->lastBatchAlone : -1; }
+size_t ZSTDMI_decompressRange(ZSTD_DCtx* d, void* dst, size_t dstCapacity, const void* src, size_t srcSize, unsigned long long offset, size_t length)
+{
+    if (!d) return ZERR(kErrGeneric);
+    return guarded([&] { return decompress_range_impl(d, dst, dstCapacity, src, srcSize, offset, length); });
+}
+int ZSTDMI_debugLastRangeFrames(const ZSTD_DCtx* d) { return d ? d->lastRangeFrames : -1; }
+long long ZSTDMI_debugLastRangeStaged(const ZSTD_DCtx* d) { return d ? d->lastRangeStaged : -1; }
 size_t ZSTDMI_decompressDevice(ZSTD_DCtx* d, void* d_dst, size_t dstCapacity, const void* d_src, size_t srcSize) { return guarded([&] { return ZSTDMI_decompressDevice_impl(d, d_dst, dstCapacity, d_src, srcSize); }); }
 size_t ZSTD_compressStream2(ZSTD_CCtx* c, ZSTD_outBuffer* output, ZSTD_inBuffer* input, int endOp) { return guarded([&] { return ZSTD_compressStream2_impl(c, output, input, endOp); }); }
 size_t ZSTD_decompressStream(ZSTD_DCtx* d, ZSTD_outBuffer* output, ZSTD_inBuffer* input) { return guarded([&] { return ZSTD_decompressStream_impl(d, output, input); }); }
@@ -1991,7 +2200,7 @@ namespace zmi {
 size_t compress_samples(ZSTD_CCtx* c, const u8* src, const u64* offs, const size_t* sizes, size_t n, size_t* outSizes, u32* stats)
 {
     size_t e = cctx_bind(c); if (isErr(e)) return e;
-    const CallParams cp = sticky_params(c);
+    CallParams cp = sticky_params(c); cp.seek = false;
     e = cctx_sync_dictionary(c); if (isErr(e)) return e;
     hipStream_t s = c->stream;
     u64 maxEnd = 0;
@@ -2021,7 +2230,7 @@ static size_t compress_batch_impl(ZSTD_CCtx* c, const void* const* srcs, const s
     if (n == 0) { c->lastBatchAlone = 0; return 0; }
     if (!srcs || !srcSizes || !dsts || !dstCapacities || !dstSizes) return ZERR(kErrGeneric);
     size_t e = cctx_bind(c); if (isErr(e)) return e;
-    if (c->workers.size() > 1) return ZERR(kErrParameterUnsupported);
+    if (c->workers.size() > 1 || c->seekTable) return ZERR(kErrParameterUnsupported);
     c->lastBatchAlone = 0;
     const CallParams cp = sticky_params(c);
     e = check_call_params(cp);

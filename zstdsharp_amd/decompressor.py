@@ -61,6 +61,28 @@ class Decompressor:
             return False, 0
         return True, ensure_zstd_success(self._lib, r)
 
+    def unwrap_range(self, src, offset: int, length: int):
+        """content[offset : offset + length] of a seekable stream (one that ends in a seek table: Compressor.seek_table) — only the
+        frames that meet the range are decoded.  src: bytes-like -> bytes; a contiguous CUDA uint8 tensor -> a CUDA uint8 tensor.
+        A range that runs past the end is clipped; one that starts there is empty."""
+        self._ensure_not_disposed()
+        if offset < 0 or length < 0:
+            raise ValueError("offset and length must not be negative")
+        lib = self._lib
+        if hasattr(src, "data_ptr"):
+            import torch
+            if not (src.is_cuda and src.dtype == torch.uint8 and src.is_contiguous()):
+                raise TypeError("expected a contiguous CUDA uint8 tensor")
+            out = torch.empty(max(length, 1), dtype=torch.uint8, device=src.device)
+            torch.cuda.synchronize(src.device)          # the library runs on a stream of its own
+            n = ensure_zstd_success(lib, lib.ZSTDMI_decompressRange(self.dctx, out.data_ptr(), length, src.data_ptr() if src.numel() else None,
+                                                                    src.numel(), offset, length))
+            return out[:n]
+        saddr, sn, skeep = _as_buffer(src)
+        out = ctypes.create_string_buffer(max(length, 1))
+        n = ensure_zstd_success(lib, lib.ZSTDMI_decompressRange(self.dctx, out, length, saddr, sn, offset, length))
+        return out.raw[:n]
+
     unwrap, try_unwrap, set_parameter, get_parameter, load_dictionary, get_decompressed_size = \
         Unwrap, TryUnwrap, SetParameter, GetParameter, LoadDictionary, GetDecompressedSize
 
