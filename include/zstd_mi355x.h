@@ -56,8 +56,8 @@ size_t     ZSTD_freeCCtx(ZSTD_CCtx* cctx);                                   /* 
  * most one split per 16 bytes), and a derived one below 5 is raised to 5.  ZSTD_ps_auto (the default) and ZSTD_ps_disable write
  * exactly what a context that never set the switch writes: the reference's auto rule (on for btopt and above at windowLog >= 27,
  * U/ZstdCompress.cs:276-284) is deliberately not adopted, so that no level's output changes.  ZSTD_compressCCtx ignores the switch
- * (level-only parameters, as the reference).  With a dictionary loaded, an LDM call of more than one block returns
- * parameter_unsupported from ZSTD_compress2; ZSTD_compressStream2 finds LDM matches inside each 16 MiB batch, not across batches. */
+ * (level-only parameters, as the reference).  With a dictionary loaded (ZSTD_CCtx_loadDictionary), an LDM call of more than one block
+ * returns parameter_unsupported from ZSTD_compress2 (ZSTD_CCtx_refPrefix is the way to match into a second buffer); ZSTD_compressStream2 finds LDM matches inside each 16 MiB batch, not across batches. */
 size_t     ZSTD_CCtx_setParameter(ZSTD_CCtx* cctx, int param, int value);
 size_t     ZSTD_CCtx_getParameter(const ZSTD_CCtx* cctx, int param, int* value);
 /* S/Compressor.cs:43-56 (dictionary load) -> U/ZstdCompress.cs:1286-1330, 5465-5503.  RAW-CONTENT dictionaries (any bytes
@@ -68,6 +68,26 @@ size_t     ZSTD_CCtx_getParameter(const ZSTD_CCtx* cctx, int param, int* value);
  * dictionary_corrupted (at this call when a device is bound, else at first use).  NULL/0 = no dictionary; under 8 bytes =
  * ignored, as in the reference.  The pointer may be host or device memory; the bytes are copied. */
 size_t     ZSTD_CCtx_loadDictionary(ZSTD_CCtx* cctx, const void* dict, size_t dictSize);
+/* U/ZstdCompress.cs:1723-1765: compress the next frame as a delta of `prefix` (the older version of the buffer; what zstd --patch-from
+ * is built on).  The prefix is RAW CONTENT whatever it starts with, host or device memory, REFERENCED, not copied: it must stay valid
+ * and unchanged until the consuming call returns (a device prefix is read in place, a host prefix is staged to HBM inside that call).
+ * Any call, NULL/0 included, cancels a loaded dictionary and an earlier prefix; ZSTD_CCtx_loadDictionary cancels a pending prefix.  The
+ * call touches no device.  NULL context: GENERIC; above 1 GiB: parameter_unsupported.
+ * SINGLE USE: the next ZSTD_compress2 or ZSTDMI_compressDevice consumes it, whatever that call returns; the call after that writes what
+ * a context without a prefix writes.  ZSTD_compressCCtx ignores it and leaves it pending.  While it is pending, ZSTD_compressStream2,
+ * ZSTDMI_compressBatch, a context with the seek-table switch on and a context with several device workers: parameter_unsupported.
+ * The consuming call writes ONE frame (ZSTD_DCtx_refPrefix serves one):
+ *   under 8 bytes      ignored, as in the reference;
+ *   short form         round_up(prefixSize, 4 KiB) + srcSize <= 64 KiB: exactly the bytes of ZSTD_CCtx_loadDictionary(the same raw
+ *                      bytes) followed by the same call;
+ *   long form          everything else: one single-segment frame with the content size, in the blocks of the long-distance framing for
+ *                      the level.  The block finders see no prefix; the long-distance stage indexes prefix and source as one window and
+ *                      runs unless ZSTD_c_enableLongDistanceMatching is ZSTD_ps_disable (ZSTD_ps_auto means ON here); its parameters
+ *                      left at 0 derive from windowLog = ceil_log2(prefixSize + srcSize), at least 17.
+ * The long form refuses with parameter_unsupported, before any byte is read: ZSTD_ps_disable, prefixSize + srcSize > 512 MiB (the
+ * decoder's offset record), a source of more than one pass (ZSTDMI_CCtx_setPassChunks), ZSTD_c_contentSizeFlag = 0, and a set
+ * ZSTD_c_windowLog below ceil_log2(prefixSize + srcSize).  The bytes written depend on the prefix's and the source's bytes alone. */
+size_t     ZSTD_CCtx_refPrefix(ZSTD_CCtx* cctx, const void* prefix, size_t prefixSize);
 /* S/Compressor.cs:73-76 -> U/ZstdCompress.cs:19-22 */
 size_t     ZSTD_compressBound(size_t srcSize);
 /* S/Compressor.cs:94 -> U/ZstdCompress.cs:7138-7177 */
@@ -89,6 +109,13 @@ size_t     ZSTD_DCtx_getParameter(ZSTD_DCtx* dctx, int param, int* value);
  * frame) and formatted ones (frames start from the dictionary's Huffman/FSE tables and repcodes and must name its dictID or
  * none; a malformed header -> dictionary_corrupted) */
 size_t     ZSTD_DCtx_loadDictionary(ZSTD_DCtx* dctx, const void* dict, size_t dictSize);
+/* U/ZstdDecompress.cs:2164-2202: decode the next call's frames behind `prefix` as raw-content history (any size, any first bytes).
+ * Referenced like ZSTD_CCtx_refPrefix's — a device prefix is read where it lies, no host copy is made — and cancels / is cancelled by
+ * ZSTD_DCtx_loadDictionary in the same way.  SINGLE USE: the next ZSTD_decompressDCtx or ZSTDMI_decompressDevice consumes it.  It
+ * applies to EVERY frame of that call, as ZSTD_decompress_usingDict does; the reference applies it to the first frame only (a prefix
+ * compressor writes one frame, so the two agree on what ZSTD_CCtx_refPrefix produced).  While it is pending, ZSTD_decompressStream,
+ * ZSTDMI_decompressBatch, ZSTDMI_decompressRange and a context with several device workers: parameter_unsupported. */
+size_t     ZSTD_DCtx_refPrefix(ZSTD_DCtx* dctx, const void* prefix, size_t prefixSize);
 /* S/Decompressor.cs:53 -> U/ZstdDecompress.cs:971-993 ; error = (unsigned long long)-2 (S/ThrowHelper.cs:7-8) */
 unsigned long long ZSTD_decompressBound(const void* src, size_t srcSize);
 unsigned long long ZSTD_getFrameContentSize(const void* src, size_t srcSize);

@@ -38,6 +38,7 @@ SIGNATURES = {
     "ZSTD_CCtx_setParameter": (c_size_t, [c_void_p, c_int, c_int]),
     "ZSTD_CCtx_getParameter": (c_size_t, [c_void_p, c_int, ctypes.POINTER(c_int)]),
     "ZSTD_CCtx_loadDictionary": (c_size_t, [c_void_p, c_void_p, c_size_t]),
+    "ZSTD_CCtx_refPrefix": (c_size_t, [c_void_p, c_void_p, c_size_t]),
     "ZSTD_compressBound": (c_size_t, [c_size_t]),
     "ZSTD_compress2": (c_size_t, [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t]),
     "ZSTD_compressCCtx": (c_size_t, [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_int]),
@@ -49,6 +50,7 @@ SIGNATURES = {
     "ZSTD_DCtx_setParameter": (c_size_t, [c_void_p, c_int, c_int]),
     "ZSTD_DCtx_getParameter": (c_size_t, [c_void_p, c_int, ctypes.POINTER(c_int)]),
     "ZSTD_DCtx_loadDictionary": (c_size_t, [c_void_p, c_void_p, c_size_t]),
+    "ZSTD_DCtx_refPrefix": (c_size_t, [c_void_p, c_void_p, c_size_t]),
     "ZSTD_decompressBound": (c_ull, [c_void_p, c_size_t]),
     "ZSTD_getFrameContentSize": (c_ull, [c_void_p, c_size_t]),
     "ZSTD_findFrameCompressedSize": (c_size_t, [c_void_p, c_size_t]),

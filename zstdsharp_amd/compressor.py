@@ -28,7 +28,37 @@ def _as_buffer(data):
     return ctypes.addressof(arr), len(mv), (arr, mv)
 
 
-class Compressor:
+def _as_prefix(prefix):
+    """bytes-like or a contiguous CUDA uint8 tensor -> (address, length, keepalive, device to synchronise or None)"""
+    if hasattr(prefix, "data_ptr"):
+        import torch
+        if not (prefix.is_cuda and prefix.dtype == torch.uint8 and prefix.is_contiguous()):
+            raise TypeError("expected a contiguous CUDA uint8 tensor")
+        return (prefix.data_ptr() if prefix.numel() else None), prefix.numel(), prefix, prefix.device
+    addr, n, keep = _as_buffer(prefix if prefix is not None else b"")
+    return addr, n, keep, None
+
+
+class _PrefixHolder:
+    """The referenced prefix of a context: kept alive until the consuming call has returned."""
+
+    _prefix_keep = None
+    _prefix_device = None
+
+    def _hold_prefix(self, keep, device):
+        self._prefix_keep, self._prefix_device = keep, device
+
+    def _prefix_ready(self):
+        # the library runs on a stream of its own: what torch has queued for a device prefix must have finished
+        if self._prefix_device is not None:
+            import torch
+            torch.cuda.synchronize(self._prefix_device)
+
+    def _release_prefix(self):
+        self._prefix_keep, self._prefix_device = None, None
+
+
+class Compressor(_PrefixHolder):
     """S/Compressor.cs:7-163.  One instance is used by one thread at a time."""
 
     def __init__(self, level: int = 0, device: int = None):
@@ -77,7 +107,19 @@ class Compressor:
     def LoadDictionary(self, dict_bytes):                     # S/Compressor.cs:36-43
         self._ensure_not_disposed()
         addr, n, keep = _as_buffer(dict_bytes if dict_bytes is not None else b"")
+        self._release_prefix()          # (ZSTD_CCtx_loadDictionary cancels a pending prefix)
         ensure_zstd_success(self._lib, self._lib.ZSTD_CCtx_loadDictionary(self.cctx, addr, n))
+
+    def RefPrefix(self, prefix):
+        """ZSTD_CCtx_refPrefix: the next Wrap / TryWrap compresses its source as a delta of `prefix` (bytes-like or a contiguous CUDA
+        uint8 tensor; raw content whatever it starts with) and writes ONE frame, which decodes behind Decompressor.RefPrefix(prefix).
+        Single use; cancels a loaded dictionary.  The object is referenced, not copied: it is kept alive here until the consuming
+        call has returned and must not change before."""
+        self._ensure_not_disposed()
+        addr, n, keep, device = _as_prefix(prefix)
+        self._release_prefix()
+        ensure_zstd_success(self._lib, self._lib.ZSTD_CCtx_refPrefix(self.cctx, addr, n))
+        self._hold_prefix(keep, device)
 
     @staticmethod
     def GetCompressBound(length: int) -> int:                  # S/Compressor.cs:72-76
@@ -98,6 +140,13 @@ class Compressor:
     def Wrap(self, src, dest=None, offset: int = 0):
         """Wrap(src) -> bytes;  Wrap(src, dest[, offset]) -> number of bytes written into dest."""
         self._ensure_not_disposed()
+        try:
+            self._prefix_ready()
+            return self._wrap(src, dest, offset)
+        finally:
+            self._release_prefix()      # (ZSTD_compress2 consumed it, whatever it returned)
+
+    def _wrap(self, src, dest, offset):
         saddr, sn, skeep = _as_buffer(src)
         if dest is None:
             cap = self.GetCompressBound(sn) + (self._lib.ZSTDMI_seekTableBound(sn) if self._seek_table else 0)
@@ -114,12 +163,16 @@ class Compressor:
         self._ensure_not_disposed()
         saddr, sn, skeep = _as_buffer(src)
         daddr, dn, dkeep = _as_buffer(dest)
-        r = self._lib.ZSTD_compress2(self.cctx, (daddr + offset) if daddr else None, dn - offset, saddr, sn)
+        try:
+            self._prefix_ready()
+            r = self._lib.ZSTD_compress2(self.cctx, (daddr + offset) if daddr else None, dn - offset, saddr, sn)
+        finally:
+            self._release_prefix()
         if r == DST_SIZE_TOO_SMALL:
             return False, 0
         return True, ensure_zstd_success(self._lib, r)
 
-    wrap, try_wrap, set_parameter, get_parameter, load_dictionary = Wrap, TryWrap, SetParameter, GetParameter, LoadDictionary
+    wrap, try_wrap, set_parameter, get_parameter, load_dictionary, ref_prefix = Wrap, TryWrap, SetParameter, GetParameter, LoadDictionary, RefPrefix
 
     # ---- lifetime (S/Compressor.cs:59-70, 124-147) ----
     def Dispose(self):

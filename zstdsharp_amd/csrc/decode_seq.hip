@@ -564,11 +564,18 @@ __global__ __launch_bounds__(64) void exec_matches_kernel(const u8* __restrict__
             if (dictSize) {                                 // uniform
                 // a match that starts in the dictionary (ZSTD_execSequence's extDict branch, :2223-2250): its first bytes come from
                 // the dictionary's tail (read-only, no dependency), the rest is an ordinary match whose source is the frame's start
+                // A dictionary part above 64 bytes is copied by the whole wave (a delta frame, ZSTD_DCtx_refPrefix, takes almost every
+                // byte from there, in matches of up to a block), a short one by its lane.
+                u32 back = 0;
                 if (have && (u64)off > bRel + dMatch) {
-                    const u32 back = (u32)((u64)off - (bRel + dMatch));
+                    back = (u32)((u64)off - (bRel + dMatch));
                     dictN = back < ml ? back : ml;
-                    const u8* ds = dict + (dictSize - back);
-                    for (u32 i = 0; i < dictN; i++) o[dMatch + i] = ds[i];
+                    if (dictN <= 64) { const u8* ds = dict + (dictSize - back); for (u32 i = 0; i < dictN; i++) o[dMatch + i] = ds[i]; }
+                }
+                u64 dm = ballot(dictN > 64);
+                while (dm) {
+                    const u32 i = ctz64(dm); dm &= dm - 1;
+                    wave_copy(o + read_lane(dMatch, i), dict + (dictSize - read_lane(back, i)), read_lane(dictN, i), lane);
                 }
             }
             const u32 dMatchR = dMatch + dictN, mlR = ml - dictN;      // what remains for the rounds
@@ -710,11 +717,17 @@ __global__ __launch_bounds__(64 * W) void exec_matches_wide_kernel(const u8* __r
             if (have && ((u64)off > bRel + dMatch + dictSize || off == 0)) errFlag = 1;       // (:2218-2223)
             u32 dictN = 0;
             if (dictSize) {                                      // uniform: a match that starts in the dictionary (:2223-2250)
+                // (parts above 64 bytes by the whole wave, as in the one-wave kernel)
+                u32 back = 0;
                 if (have && (u64)off > bRel + dMatch && (u64)off <= bRel + dMatch + dictSize) {
-                    const u32 back = (u32)((u64)off - (bRel + dMatch));
+                    back = (u32)((u64)off - (bRel + dMatch));
                     dictN = back < ml ? back : ml;
-                    const u8* ds = dict + (dictSize - back);
-                    for (u32 i = 0; i < dictN; i++) o[dMatch + i] = ds[i];
+                    if (dictN <= 64) { const u8* ds = dict + (dictSize - back); for (u32 i = 0; i < dictN; i++) o[dMatch + i] = ds[i]; }
+                }
+                u64 dm = ballot(dictN > 64);
+                while (dm) {
+                    const u32 i = ctz64(dm); dm &= dm - 1;
+                    wave_copy(o + read_lane(dMatch, i), dict + (dictSize - read_lane(back, i)), read_lane(dictN, i), lane);
                 }
             }
             const u32 dMatchR = dMatch + dictN, mlR = ml - dictN;

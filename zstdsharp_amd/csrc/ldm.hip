@@ -12,6 +12,13 @@
 //   ldm_merge           one wave per block that has LDM matches: the finder's sequences are trimmed around them and the block's
 //                       sequence store (seqs / lits / ChunkMeta) is rewritten in place
 // Every step is a function of the pass's bytes alone (no insert-order-dependent table): the output does not depend on scheduling.
+//
+// A referenced prefix (ZSTD_CCtx_refPrefix; the PFX instances of ldm_split and ldm_match): prefix and source lie in different buffers
+// and are ONE window.  Positions are virtual: the source's byte i is at base + i with base = the prefix length rounded up to a split
+// tile, the prefix's byte i at vlo + i with vlo = base - prefixLen, and nothing lies below vlo.  The prefix so ends exactly where
+// block 0 of the source begins: position - candidate is the zstd offset, the source's tiles and blocks keep their alignment, and no
+// tile straddles the seam.  Splits are taken over [vlo, end) — the rolling hash and a split's window run across the seam —, the
+// prefix's sort in front of the source's, and only the source's blocks are matched: the prefix's splits are candidates only.
 #include <hip/hip_runtime.h>
 #include "zmi_common.h"
 #include "zmi_device.h"
@@ -21,6 +28,7 @@ namespace zmi {
 constexpr u32 kLdmTile = 16384;         // bytes per workgroup of the split kernels (256 lanes x 64 positions); frames are multiples of it
 constexpr u32 kLdmSegCap = 4;           // splits kept per 64 positions (the first four): the workspace holds at most one per 16 bytes
 constexpr u32 kSortTile = 4096;         // elements per workgroup of the radix sort (16 rounds of 256)
+static_assert(kLdmPrefixAlign == kLdmTile, "a referenced prefix ends on a tile boundary of the virtual coordinate");
 
 // The gear table: splitmix64 of 0 .. 255 (the reference's table is another set of random constants; any fixed one serves)
 __device__ __forceinline__ u64 splitmix64(u64 i)
@@ -60,8 +68,9 @@ __device__ __forceinline__ u32 block_excl_scan256(u32 v, u32* part, u32* tot)
 // Split points (ZSTD_ldm_gear_feed): after byte p, h = (h << 1) + gear[byte]; a split ends at p + 1 when (h & stopMask) == 0.  Bit k
 // of h depends on the last k + 1 bytes only and stopMask lies below bit 64, so every lane starts 64 bytes ahead of its 64 positions
 // (never before its frame's start).  A split's window [p + 1 - minMatch, p + 1) must lie in the frame.
-template <bool EMIT>
-__global__ __launch_bounds__(256) void ldm_split_kernel(const u8* __restrict__ src, u64 n, u64 frameSpan, u32 minMatch, u64 stopMask, u32 hb,
+// PFX: n, the tiles and every position are virtual (see the head of the file); the one frame starts at pfx.vlo.
+template <bool EMIT, bool PFX>
+__global__ __launch_bounds__(256) void ldm_split_kernel(const u8* __restrict__ src, u64 n, u64 frameSpan, u32 minMatch, u64 stopMask, u32 hb, const LdmPrefix pfx,
                                                         u32* __restrict__ tileCount, const u32* __restrict__ tileBase,
                                                         u32* __restrict__ splitPos, u32* __restrict__ splitCheck, u64* __restrict__ key, u32* __restrict__ val)
 {
@@ -71,11 +80,12 @@ __global__ __launch_bounds__(256) void ldm_split_kernel(const u8* __restrict__ s
     const u32 tid = threadIdx.x;
     const u64 t0 = (u64)blockIdx.x * kLdmTile;
     const u64 tEnd = (t0 + kLdmTile) < n ? t0 + kLdmTile : n;
-    const u64 fStart = t0 / frameSpan * frameSpan;
+    auto byteAt = [&](u64 v) -> u32 { if (PFX) return v < pfx.base ? pfx.pre[v - pfx.vlo] : src[v - pfx.base]; return src[v]; };
+    const u64 fStart = PFX ? (u64)pfx.vlo : t0 / frameSpan * frameSpan;
     const u64 lo = t0 >= fStart + 64 ? t0 - 64 : fStart;
     gear[tid] = splitmix64(tid);
-    const u32 pre = (u32)(t0 - lo), len = pre + (u32)(tEnd - t0);
-    for (u32 i = tid; i < len; i += 256) buf[ldm_pad(64 - pre + i)] = src[lo + i];
+    const u32 pre = (u32)(t0 - lo), len = pre + (u32)(tEnd - t0);      // (PFX, the first tile: lo = vlo lies behind t0, pre wraps, the sums hold)
+    for (u32 i = tid; i < len; i += 256) buf[ldm_pad(64 - pre + i)] = (u8)byteAt(lo + i);
     __syncthreads();
     const u64 p0 = t0 + (u64)tid * 64;
     const u32 mm = minMatch < 64 ? minMatch : 64;
@@ -91,16 +101,17 @@ __global__ __launch_bounds__(256) void ldm_split_kernel(const u8* __restrict__ s
             const u64 wlo = p0 >= fStart + 64 ? p0 - 64 : fStart;
             for (u64 q = wlo; q < p0; ++q) h = (h << 1) + gear[buf[ldm_pad((u32)(64 + (s64)(q - t0)))]];
             const u32 cnt = (tEnd - p0) < 64 ? (u32)(tEnd - p0) : 64u;
-            for (u32 k = 0; k < cnt && found < kLdmSegCap; ++k) {
+            const u32 k0 = (PFX && p0 < fStart) ? ((fStart - p0) < 64 ? (u32)(fStart - p0) : 64u) : 0u;      // (nothing lies in front of the prefix)
+            for (u32 k = k0; k < cnt && found < kLdmSegCap; ++k) {
                 h = (h << 1) + gear[buf[ldm_pad(64 + tid * 64 + k)]];
                 const u64 p = p0 + k;
                 if ((h & stopMask) == 0 && p + 1 >= fStart + minMatch) {
                     if (pass == 1) {
                         const u32 w = (u32)(p + 1 - minMatch), i = base + found;
                         const u64 x = w >= lo ? window_hash([&](u32 j) { return (u32)buf[ldm_pad((u32)(64 + (s64)(w + j - t0)))]; }, mm)
-                                              : window_hash([&](u32 j) { return (u32)src[w + j]; }, mm);
+                                              : window_hash([&](u32 j) { return byteAt((u64)w + j); }, mm);
                         splitPos[i] = w; splitCheck[i] = (u32)(x >> 32);
-                        key[i] = ((u64)(w / frameSpan) << hb) | (x & ((1ull << hb) - 1)); val[i] = i;
+                        key[i] = ((u64)(PFX ? 0u : w / frameSpan) << hb) | (x & ((1ull << hb) - 1)); val[i] = i;
                     }
                     found++;
                 }
@@ -215,7 +226,12 @@ __device__ __forceinline__ u32 wave_match_back(const u8* a, const u8* b, u32 lim
 // wave, left to right, as ZSTD_ldm_generateSequences_internal does: a split in front of the anchor is skipped, every candidate is
 // extended forward (to the block's end) and backward (to the anchor, and not before its frame), the longest total whose forward part
 // reaches minMatch wins, and the anchor moves behind it.  Result per split: mLen (0 = none), mStart (pass offset), mOff.
-__global__ __launch_bounds__(256) void ldm_match_kernel(const u8* __restrict__ src, u64 n, u32 nChunks, u32 chunkBytes, u64 frameSpan, u32 minMatch, u32 bucketLog,
+// PFX: positions are virtual and the blocks are the source's (block c starts at pfx.base + c * chunkBytes).  The split's own side of
+// a compare always lies in the source; the candidate's side is read in two segments: a forward compare that starts in the prefix
+// runs on into the source, a backward one that starts in the source runs back into the prefix and stops at the prefix's first byte.
+// Either is cut at the seam into two wave compares of 256 bytes a step, the second only when the first matched to its end.
+template <bool PFX>
+__global__ __launch_bounds__(256) void ldm_match_kernel(const u8* __restrict__ src, u64 n, u32 nChunks, u32 chunkBytes, u64 frameSpan, u32 minMatch, u32 bucketLog, const LdmPrefix pfx,
                                                         const u32* __restrict__ splitPos, const u32* __restrict__ splitCheck, const u64* __restrict__ sortedKey,
                                                         const u32* __restrict__ sortedVal, const u32* __restrict__ inv, u32 nSplits,
                                                         u32* __restrict__ mStart, u32* __restrict__ mLen, u32* __restrict__ mOff)
@@ -223,10 +239,11 @@ __global__ __launch_bounds__(256) void ldm_match_kernel(const u8* __restrict__ s
     const u32 lane = lane_id();
     const u32 c = blockIdx.x * 4 + wave_id();
     if (c >= nChunks) return;
-    const u64 bStart = (u64)c * chunkBytes, bEnd = (bStart + chunkBytes) < n ? bStart + chunkBytes : n;
-    const u64 fStart = bStart / frameSpan * frameSpan;
+    const u64 bStart = (PFX ? (u64)pfx.base : 0u) + (u64)c * chunkBytes, bEnd = (bStart + chunkBytes) < n ? bStart + chunkBytes : n;
+    const u64 fStart = PFX ? (u64)pfx.vlo : bStart / frameSpan * frameSpan;
     const u32 s0 = lower_bound_u32(splitPos, nSplits, (u32)bStart), s1 = lower_bound_u32(splitPos, nSplits, (u32)bEnd);
     const u32 ents = 1u << bucketLog;
+    const u8* const vsrc = PFX ? src - pfx.base : src;      // virtual position -> source byte (positions >= base only)
     u32 anchor = (u32)bStart;
     for (u32 sb = s0; sb < s1; sb += 64) {
         const u32 s = sb + lane;
@@ -254,10 +271,22 @@ __global__ __launch_bounds__(256) void ldm_match_kernel(const u8* __restrict__ s
                 const u32 t = sortedVal[j - i];
                 if (splitCheck[t] != cs) continue;
                 const u32 cw = splitPos[t];
-                const u32 fwd = wave_match_fwd(src + w, src + cw, (u32)(bEnd - w));
+                const u32 fwdLim = (u32)(bEnd - w);
+                u32 fwd;
+                if (PFX && cw < pfx.base) {
+                    const u32 seg = pfx.base - cw;      // the candidate's bytes in front of the seam
+                    fwd = wave_match_fwd(vsrc + w, pfx.pre + (cw - pfx.vlo), fwdLim < seg ? fwdLim : seg);
+                    if (fwd == seg && fwdLim > seg) fwd += wave_match_fwd(vsrc + w + seg, src, fwdLim - seg);
+                } else fwd = wave_match_fwd(vsrc + w, vsrc + cw, fwdLim);
                 if (fwd < minMatch) continue;
                 const u32 backLim = (w - anchor) < (u32)(cw - fStart) ? (w - anchor) : (u32)(cw - fStart);
-                const u32 back = wave_match_back(src + w, src + cw, backLim);
+                u32 back;
+                if (PFX && cw < pfx.base) back = wave_match_back(vsrc + w, pfx.pre + (cw - pfx.vlo), backLim);
+                else if (PFX && backLim > cw - pfx.base) {
+                    const u32 seg = cw - pfx.base;      // the candidate's bytes behind the seam
+                    back = wave_match_back(vsrc + w, vsrc + cw, seg);
+                    if (back == seg) back += wave_match_back(vsrc + w - seg, pfx.pre + (pfx.base - pfx.vlo), backLim - seg);
+                } else back = wave_match_back(vsrc + w, vsrc + cw, backLim);
                 if (fwd + back > bestLen) { bestLen = fwd + back; bestBack = back; bestFwd = fwd; bestOff = w - cw; }
             }
             if (bestLen) {
@@ -276,7 +305,7 @@ __global__ __launch_bounds__(256) void ldm_match_kernel(const u8* __restrict__ s
 // holds).  The sequences go 64 at a time through LDS to the wave's scratch, each lane copying its sequence's literals from src;
 // then the scratch replaces the block's sequences.  Offsets stay raw (distance + 3): seq_encode resolves repcodes.
 struct StagedSeq { u32 litSrc, litDst; Seq q; };
-__global__ __launch_bounds__(256) void ldm_merge_kernel(const u8* __restrict__ src, u64 n, u32 nChunks, u32 chunkBytes, const u32* __restrict__ splitPos, u32 nSplits,
+__global__ __launch_bounds__(256) void ldm_merge_kernel(const u8* __restrict__ src, u64 n, u32 nChunks, u32 chunkBytes, u32 base, const u32* __restrict__ splitPos, u32 nSplits,
                                                         const u32* __restrict__ mStart, const u32* __restrict__ mLen, const u32* __restrict__ mOff,
                                                         Seq* __restrict__ seqs, u8* __restrict__ lits, ChunkMeta* __restrict__ meta, Seq* __restrict__ scratch, u32 nWaves)
 {
@@ -288,7 +317,8 @@ __global__ __launch_bounds__(256) void ldm_merge_kernel(const u8* __restrict__ s
     for (u32 c = g; c < nChunks; c += nWaves) {
         const u64 bStart = (u64)c * chunkBytes, bEnd = (bStart + chunkBytes) < n ? bStart + chunkBytes : n;
         const u32 blockLen = (u32)(bEnd - bStart);
-        const u32 s0 = lower_bound_u32(splitPos, nSplits, (u32)bStart), s1 = lower_bound_u32(splitPos, nSplits, (u32)bEnd);
+        const u32 vStart = base + (u32)bStart;      // splits and matches are filed by virtual position (base = 0 without a prefix)
+        const u32 s0 = lower_bound_u32(splitPos, nSplits, vStart), s1 = lower_bound_u32(splitPos, nSplits, vStart + blockLen);
         bool any = false;
         for (u32 s = s0 + lane; s < s1; s += 64) any |= mLen[s] != 0;
         if (!__ballot(any)) continue;
@@ -312,7 +342,7 @@ __global__ __launch_bounds__(256) void ldm_merge_kernel(const u8* __restrict__ s
         auto loadL = [&](u32 b) {
             const u32 s = b + lane;
             const u32 len = s < s1 ? mLen[s] : 0u;
-            lS = len ? mStart[s] - (u32)bStart : 0u; lE = lS + len; lO = len ? mOff[s] : 0u;
+            lS = len ? mStart[s] - vStart : 0u; lE = lS + len; lO = len ? mOff[s] : 0u;
             lMask = __ballot(len != 0); lBase = b;
         };
         if (nF) loadF(0);
@@ -383,21 +413,24 @@ size_t ldm_big_bytes(u64 nSplits)
 }
 
 // Count the splits of [src, src + n): -> the device word *total (the host reads it back and sizes the big workspace)
-void launch_ldm_count(const u8* src, u64 n, u64 frameSpan, const LdmLaunch& p, u8* small, hipStream_t stream)
+// With a prefix (pfx.pre != nullptr) n is the virtual end, pfx.base + the source's length, and frameSpan is not used.
+void launch_ldm_count(const u8* src, u64 n, u64 frameSpan, const LdmLaunch& p, u8* small, hipStream_t stream, const LdmPrefix& pfx)
 {
     const u32 nTiles = (u32)((n + kLdmTile - 1) / kLdmTile);
     u32* tileCount = (u32*)small; u32* tileBase = tileCount + nTiles + 16; u32* total = tileBase + nTiles + 16;
     const u32 m = p.minMatch < 64 ? p.minMatch : 64;
     const u64 stopMask = (p.hashRateLog > 0 && p.hashRateLog <= m) ? (((1ull << p.hashRateLog) - 1) << (m - p.hashRateLog)) : ((1ull << p.hashRateLog) - 1);
-    hipLaunchKernelGGL(ldm_split_kernel<false>, dim3(nTiles), dim3(256), 0, stream, src, n, frameSpan, p.minMatch, stopMask, 0u, tileCount, nullptr,
-                       nullptr, nullptr, nullptr, nullptr);
+    if (pfx.pre) hipLaunchKernelGGL((ldm_split_kernel<false, true>), dim3(nTiles), dim3(256), 0, stream, src, n, frameSpan, p.minMatch, stopMask, 0u, pfx, tileCount, nullptr,
+                                    nullptr, nullptr, nullptr, nullptr);
+    else hipLaunchKernelGGL((ldm_split_kernel<false, false>), dim3(nTiles), dim3(256), 0, stream, src, n, frameSpan, p.minMatch, stopMask, 0u, pfx, tileCount, nullptr,
+                            nullptr, nullptr, nullptr, nullptr);
     hipLaunchKernelGGL(ldm_scan_kernel, dim3(1), dim3(1024), 0, stream, tileCount, tileBase, nTiles, total);
 }
 u32* ldm_total_word(u8* small, u64 n) { const u32 nTiles = (u32)((n + kLdmTile - 1) / kLdmTile); return (u32*)small + 2 * (nTiles + 16); }
 
-// everything after the count: emit, sort, match, merge (nSplits > 0)
+// everything after the count: emit, sort, match, merge (nSplits > 0).  nChunks: the source's blocks.
 void launch_ldm_rest(const u8* src, u64 n, u32 nChunks, u32 chunkBytes, u64 frameSpan, const LdmLaunch& p, u32 nSplits, u8* small, u8* big,
-                     Seq* seqs, u8* lits, ChunkMeta* meta, hipStream_t stream, StageHook hook)
+                     Seq* seqs, u8* lits, ChunkMeta* meta, hipStream_t stream, StageHook hook, const LdmPrefix& pfx)
 {
     const u32 nTiles = (u32)((n + kLdmTile - 1) / kLdmTile);
     const u32* tileBase = (const u32*)small + nTiles + 16;
@@ -414,11 +447,13 @@ void launch_ldm_rest(const u8* src, u64 n, u32 nChunks, u32 chunkBytes, u64 fram
     const u32 m = p.minMatch < 64 ? p.minMatch : 64;
     const u64 stopMask = (p.hashRateLog > 0 && p.hashRateLog <= m) ? (((1ull << p.hashRateLog) - 1) << (m - p.hashRateLog)) : ((1ull << p.hashRateLog) - 1);
     const u32 hb = p.hashLog - p.bucketLog;
-    hipLaunchKernelGGL(ldm_split_kernel<true>, dim3(nTiles), dim3(256), 0, stream, src, n, frameSpan, p.minMatch, stopMask, hb, nullptr, tileBase,
-                       splitPos, splitCheck, keyA, valA);
+    if (pfx.pre) hipLaunchKernelGGL((ldm_split_kernel<true, true>), dim3(nTiles), dim3(256), 0, stream, src, n, frameSpan, p.minMatch, stopMask, hb, pfx, nullptr, tileBase,
+                                    splitPos, splitCheck, keyA, valA);
+    else hipLaunchKernelGGL((ldm_split_kernel<true, false>), dim3(nTiles), dim3(256), 0, stream, src, n, frameSpan, p.minMatch, stopMask, hb, pfx, nullptr, tileBase,
+                            splitPos, splitCheck, keyA, valA);
     hook("ldm_split");
     // key bits: the frame's index in the pass above the bucket's hb bits
-    const u64 nFrames = (n + frameSpan - 1) / frameSpan;
+    const u64 nFrames = pfx.pre ? 1u : (n + frameSpan - 1) / frameSpan;
     u32 fBits = 0; while (((u64)1 << fBits) < nFrames) ++fBits;
     const u32 keyBits = fBits + hb;
     for (u32 shift = 0; shift < keyBits; shift += 8) {
@@ -429,11 +464,13 @@ void launch_ldm_rest(const u8* src, u64 n, u32 nChunks, u32 chunkBytes, u64 fram
     }
     hipLaunchKernelGGL(ldm_inv_kernel, dim3((nSplits + 255) / 256), dim3(256), 0, stream, valA, inv, nSplits);
     hook("ldm_sort");
-    hipLaunchKernelGGL(ldm_match_kernel, dim3((nChunks + 3) / 4), dim3(256), 0, stream, src, n, nChunks, chunkBytes, frameSpan, p.minMatch, p.bucketLog,
-                       splitPos, splitCheck, keyA, valA, inv, nSplits, mStart, mLen, mOff);
+    if (pfx.pre) hipLaunchKernelGGL(ldm_match_kernel<true>, dim3((nChunks + 3) / 4), dim3(256), 0, stream, src, n, nChunks, chunkBytes, frameSpan, p.minMatch, p.bucketLog, pfx,
+                                    splitPos, splitCheck, keyA, valA, inv, nSplits, mStart, mLen, mOff);
+    else hipLaunchKernelGGL(ldm_match_kernel<false>, dim3((nChunks + 3) / 4), dim3(256), 0, stream, src, n, nChunks, chunkBytes, frameSpan, p.minMatch, p.bucketLog, pfx,
+                            splitPos, splitCheck, keyA, valA, inv, nSplits, mStart, mLen, mOff);
     hook("ldm_match");
     const u32 waves = nChunks < kMergeWaves ? ((nChunks + 3) & ~3u) : kMergeWaves;
-    hipLaunchKernelGGL(ldm_merge_kernel, dim3(waves / 4), dim3(256), 0, stream, src, n, nChunks, chunkBytes, splitPos, nSplits, mStart, mLen, mOff,
+    hipLaunchKernelGGL(ldm_merge_kernel, dim3(waves / 4), dim3(256), 0, stream, src, pfx.pre ? n - pfx.base : n, nChunks, chunkBytes, pfx.pre ? pfx.base : 0u, splitPos, nSplits, mStart, mLen, mOff,
                        seqs, lits, meta, scratch, waves);
     hook("ldm_merge");
 }

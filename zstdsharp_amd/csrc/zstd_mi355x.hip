@@ -41,10 +41,10 @@ void launch_seek_table(const u32* entries, u32 n, u8* dst, hipStream_t stream);
 // long-distance matching (ldm.hip)
 size_t ldm_small_bytes(u64 n);
 size_t ldm_big_bytes(u64 nSplits);
-void launch_ldm_count(const u8* src, u64 n, u64 frameSpan, const LdmLaunch& p, u8* small, hipStream_t stream);
+void launch_ldm_count(const u8* src, u64 n, u64 frameSpan, const LdmLaunch& p, u8* small, hipStream_t stream, const LdmPrefix& pfx);
 u32* ldm_total_word(u8* small, u64 n);
 void launch_ldm_rest(const u8* src, u64 n, u32 nChunks, u32 chunkBytes, u64 frameSpan, const LdmLaunch& p, u32 nSplits, u8* small, u8* big,
-                     Seq* seqs, u8* lits, ChunkMeta* meta, hipStream_t stream, StageHook hook);
+                     Seq* seqs, u8* lits, ChunkMeta* meta, hipStream_t stream, StageHook hook, const LdmPrefix& pfx);
 // decoder (decode_walk.hip, decode_lit.hip, decode_seq.hip)
 size_t decode_walk_workspace_bytes(u64 srcSize);
 void launch_frame_walk_count(const u8* src, u64 srcSize, u32 maxFrames, u32* status, u8* walkWs, hipStream_t stream);
@@ -191,6 +191,9 @@ struct ZSTD_CCtx_s {
     // (seekOn: this call files them) at the running index seekCount; compress_device writes the table behind the frames from them
     int seekTable = 0; bool seekOn = false; u32 seekCount = 0;
     DevBuf seekEntries, seekSort;
+    // ZSTD_CCtx_refPrefix: the caller's bytes (host or device), referenced until the next ZSTD_compress2 / ZSTDMI_compressDevice has
+    // consumed them; a host prefix of the long form is staged into pfxStage inside that call
+    const void* pfx = nullptr; size_t pfxSize = 0; DevBuf pfxStage;
 };
 // History per chunk lives in LDS beside the chunk: up to 32 KiB of dictionary in front of 32 KiB chunks, or up to 60 KiB when
 // the whole input fits behind it in one chunk (small records, the usual dictionary case).
@@ -230,6 +233,9 @@ struct ZSTD_DCtx_s {
     DictInfo info = {};
     u64 dictGen = 0;
     std::vector<ZSTD_DCtx_s*> workers;      // ZSTDMI_DCtx_setDevices (decompress_multi)
+    // ZSTD_DCtx_refPrefix: the caller's bytes (host or device), referenced until the next ZSTD_decompressDCtx / ZSTDMI_decompressDevice
+    // has consumed them.  pfxDev: the prefix as that call's kernels read it (the caller's device pointer, or pfxStage for a host prefix)
+    const void* pfx = nullptr; size_t pfxSize = 0; DevBuf pfxStage; const u8* pfxDev = nullptr;
 };
 
 
@@ -271,6 +277,7 @@ struct CallParams {
     int ldm = 0, ldmHashLog = 0, ldmMinMatch = 0, ldmBucketSizeLog = 0, ldmHashRateLog = 0;     // (ZSTD_compressCCtx: all 0, as the reference's level-only parameters)
     bool useDict = true;
     bool seek = false;                  // append a seek table (ZSTDMI_CCtx_setSeekTable; ZSTD_compressCCtx: never, as it never runs LDM)
+    const u8* pfx = nullptr; size_t pfxSize = 0;    // the long form of a referenced prefix (compress_prefixed): device bytes in front of the ONE frame
 };
 static CallParams sticky_params(const ZSTD_CCtx* c)
 {
@@ -360,6 +367,12 @@ constexpr int kLdmDefaultWindowLog = 27;
 constexpr u64 kLdmMaxFrame = (u64)512 << 20;        // every offset stays below the decoder's 2^29 record limit (kRecOffMax)
 static int ldm_window_log(const CallParams& cp) { return cp.windowLog ? cp.windowLog : kLdmDefaultWindowLog; }
 static bool ldm_active(const CallParams& cp, size_t paramSize) { return cp.ldm == 1 && paramSize > kChunkSize && ldm_window_log(cp) >= 17; }
+// the window of a referenced prefix in front of srcSize bytes: ceil_log2(prefixSize + srcSize), at least 17
+static u32 prefix_window_log(size_t prefixSize, size_t srcSize)
+{
+    u32 wl = 17; while (wl < 31 && ((u64)1 << wl) < (u64)prefixSize + srcSize) ++wl;
+    return wl;
+}
 static LdmLaunch ldm_resolve(const CallParams& cp, size_t paramSize)
 {
     u32 wl = (u32)ldm_window_log(cp);
@@ -377,12 +390,19 @@ static LdmLaunch ldm_resolve(const CallParams& cp, size_t paramSize)
 
 static Framing resolve_framing(const ZSTD_CCtx* c, const CallParams& cp, size_t paramSize)
 {
-    if (ldm_active(cp, paramSize)) {
+    if (cp.pfxSize || ldm_active(cp, paramSize)) {
         // Under LDM a frame is a window: min(2^windowLog, 512 MiB, the pass) of content (ldm.hip matches never leave their frame, so
         // no offset exceeds what the frame declares).  Blocks and history are those the level's windowLog > 16 path picks: full
         // 64 KiB blocks with far candidates at the fast strategy, 64 KiB - 16/32 KiB blocks behind LDS history above it.
-        Framing f; f.prefixLen = 0; f.indepWindowLog = 0; f.ldm = true; f.ldmP = ldm_resolve(cp, paramSize);
-        const u32 wl = (u32)ldm_window_log(cp);
+        // Behind a referenced prefix (the long form, compress_prefixed) the window is prefix + source, at least 2^17, and the whole
+        // source is ONE frame of those blocks.
+        Framing f; f.prefixLen = 0; f.indepWindowLog = 0; f.ldm = true;
+        u32 wl = (u32)ldm_window_log(cp);
+        if (cp.pfxSize) {
+            wl = prefix_window_log(cp.pfxSize, paramSize);
+            CallParams q = cp; q.windowLog = (int)wl;
+            f.ldmP = ldm_resolve(q, cp.pfxSize + paramSize);
+        } else f.ldmP = ldm_resolve(cp, paramSize);
         const u64 win = ((u64)1 << wl) < kLdmMaxFrame ? ((u64)1 << wl) : kLdmMaxFrame;
         const Resolved rf = resolve_call(cp, paramSize < win ? paramSize : (size_t)win, (u32)(win < ((u64)1 << 31) ? win : ((u64)1 << 31)));
         u32 chunkBytes = kChunkSize;
@@ -390,7 +410,7 @@ static Framing resolve_framing(const ZSTD_CCtx* c, const CallParams& cp, size_t 
             const int hb = c->historyBytes > 0 ? c->historyBytes : (rf.cp.strategy == kStratDfast ? (16 << 10) : (32 << 10));
             chunkBytes = kChunkSize - (round_tile((size_t)hb) > (48u << 10) ? (48u << 10) : round_tile((size_t)hb));
         }
-        u32 frameBlocks = (u32)(win / chunkBytes);
+        u32 frameBlocks = cp.pfxSize ? (u32)((paramSize + chunkBytes - 1) / chunkBytes) : (u32)(win / chunkBytes);
         if (frameBlocks > c->passChunks) frameBlocks = c->passChunks;
         if (frameBlocks < 2) frameBlocks = 2;
         f.chunkBytes = chunkBytes; f.frameBlocks = frameBlocks; f.rs = rf;
@@ -505,15 +525,19 @@ static size_t compress_range(ZSTD_CCtx* c, const CallParams& cp, u8* d_dst, size
                   regionParse ? (u32*)((u8*)c->cand.p + cand_plane_bytes(passChunks) * (hcChains ? 2 : 1)) : nullptr, hcDepth, s, c->timer.hook(), (u32*)(total + 4));      // (the claim counter: a word of `total`'s 64 bytes)
         if (fr.ldm) {       // long-distance matches into the finder's sequence store (ldm.hip); the splits are counted first to size the workspace
             const u64 span = (u64)frameBlocks * chunkBytes;
-            if (!c->ldmSmall.ensure(ldm_small_bytes(n))) return ZERR(kErrMemoryAllocation);
-            launch_ldm_count(src, n, span, fr.ldmP, (u8*)c->ldmSmall.p, s);
+            // a referenced prefix: splits over prefix and source as one window in the virtual coordinate (ldm.hip), nL = its end
+            LdmPrefix lp;
+            if (cp.pfxSize) { lp.pre = cp.pfx; lp.base = (u32)((cp.pfxSize + kLdmPrefixAlign - 1) / kLdmPrefixAlign * kLdmPrefixAlign); lp.vlo = lp.base - (u32)cp.pfxSize; }
+            const u64 nL = lp.base + n;
+            if (!c->ldmSmall.ensure(ldm_small_bytes(nL))) return ZERR(kErrMemoryAllocation);
+            launch_ldm_count(src, nL, span, fr.ldmP, (u8*)c->ldmSmall.p, s, lp);
             u32 nSplits = 0;
-            if (hipMemcpyAsync(&nSplits, ldm_total_word((u8*)c->ldmSmall.p, n), sizeof(u32), hipMemcpyDeviceToHost, s) != hipSuccess) return ZERR(kErrGeneric);
+            if (hipMemcpyAsync(&nSplits, ldm_total_word((u8*)c->ldmSmall.p, nL), sizeof(u32), hipMemcpyDeviceToHost, s) != hipSuccess) return ZERR(kErrGeneric);
             if (hipStreamSynchronize(s) != hipSuccess) { (void)hipGetLastError(); return ZERR(kErrGeneric); }
             c->timer.mark("ldm_count", s);
             if (nSplits) {
                 if (!c->ldmBig.ensure(ldm_big_bytes(nSplits))) return ZERR(kErrMemoryAllocation);
-                launch_ldm_rest(src, n, nChunks, chunkBytes, span, fr.ldmP, nSplits, (u8*)c->ldmSmall.p, (u8*)c->ldmBig.p, seqs, lits, meta, s, c->timer.hook());
+                launch_ldm_rest(src, nL, nChunks, chunkBytes, span, fr.ldmP, nSplits, (u8*)c->ldmSmall.p, (u8*)c->ldmBig.p, seqs, lits, meta, s, c->timer.hook(), lp);
             }
         }
         launch_huf_build(lits, meta, tables, slots, nChunks, rs.rawLiterals, src, chunkBytes, s, c->timer.hook());
@@ -568,7 +592,7 @@ static size_t probe_group_bytes(ZSTD_CCtx* c, const CallParams& cp, size_t srcSi
     err = 0;
     // (a caller-set targetLength keeps the level's own path: at the fast strategy it means raw literals, which the sparse ranges must not inherit)
     if (!(srcSize >= (4u << 20) && c->historyBytes < 0 && cp.strategy == 0 && cp.windowLog == 0 && cp.searchLog == 0 && cp.targetLength == 0)) return 0;
-    if (ldm_active(cp, srcSize)) return 0;          // (one range: LDM frames are windows)
+    if (cp.pfxSize || ldm_active(cp, srcSize)) return 0;          // (one range: LDM frames are windows)
     if (cp.useDict) { err = cctx_sync_dictionary(c); if (isErr(err)) return 0; err = 0; }
     if (cp.useDict && dict_prefix_len(c, srcSize)) return 0;
     if (resolve_call(cp, srcSize, kChunkSize).cp.strategy <= kStratFast) return 0;
@@ -780,7 +804,7 @@ size_t ZSTD_freeCCtx(ZSTD_CCtx* c)
         (void)hipSetDevice(c->device);
         if (c->ownStream) (void)hipStreamSynchronize(c->ownStream);
         c->seqs.release(); c->lits.release(); c->meta.release(); c->tables.release(); c->slots.release(); c->cand.release(); c->probe.release();
-        c->gatherIn.release(); c->gatherOut.release(); c->batchStage.release(); c->batchTab.release(); c->ldmSmall.release(); c->ldmBig.release(); c->offsets.release(); c->total.release(); c->seekEntries.release(); c->seekSort.release(); c->stageSrc.release(); c->stageDst.release(); c->dict.release(); c->dictFullDev.release(); c->dictInfoDev.release();
+        c->gatherIn.release(); c->gatherOut.release(); c->batchStage.release(); c->batchTab.release(); c->ldmSmall.release(); c->ldmBig.release(); c->offsets.release(); c->total.release(); c->seekEntries.release(); c->seekSort.release(); c->stageSrc.release(); c->stageDst.release(); c->pfxStage.release(); c->dict.release(); c->dictFullDev.release(); c->dictInfoDev.release();
         c->timer.destroy();
         if (c->ownStream) (void)hipStreamDestroy(c->ownStream);
     }
@@ -888,6 +912,7 @@ static size_t ZSTD_CCtx_loadDictionary_impl(ZSTD_CCtx* c, const void* dict, size
     if (!c) return ZERR(kErrGeneric);
     if (!c->sIn.empty() || c->sEnding) return ZERR(kErrStageWrong);        /* not in the middle of a streaming frame session, U/ZstdCompress.cs:1273 */
     c->dictGen++;
+    c->pfx = nullptr; c->pfxSize = 0;       // (a pending prefix is cancelled: ZSTD_clearAllDicts)
     c->dictFormatted = false; c->dictFull.clear();
     if (dict == nullptr || dictSize == 0) { c->dictHost.clear(); c->dictDirty = true; return 0; }          /* "no dictionary" */
     if (dictSize > (size_t)1 << 30) return ZERR(kErrParameterUnsupported);
@@ -957,12 +982,71 @@ static size_t compress_any(ZSTD_CCtx* c, const CallParams& cp, void* dst, size_t
     return r;
 }
 
-size_t ZSTDMI_compressDevice(ZSTD_CCtx* c, void* d_dst, size_t dstCapacity, const void* d_src, size_t srcSize) { return guarded([&] { return ZSTDMI_compressDevice_impl(c, d_dst, dstCapacity, d_src, srcSize); }); }
+// ZSTD_CCtx_refPrefix (U/ZstdCompress.cs:1723-1765): raw content in front of ONE frame, referenced and used once.
+// The call with a pending prefix.  Under 8 bytes: ignored (U/ZstdCompress.cs:5465-5503).  Short form — the prefix rounded up to 4 KiB
+// and the source fit one 64 KiB block —: the path of ZSTD_CCtx_loadDictionary(the same raw bytes), which writes one frame with the
+// prefix's last 60 KiB as LDS history.  Long form: one frame of the LDM framing's blocks whose long-distance stage indexes prefix and
+// source as one window (ldm.hip); the block finders see no prefix.  What the long form cannot do is refused before a byte is read.
+static size_t compress_prefixed(ZSTD_CCtx* c, void* dst, size_t dstCapacity, const void* src, size_t srcSize, bool deviceCall)
+{
+    const void* const pfx = c->pfx; const size_t pfxSize = c->pfxSize;
+    c->pfx = nullptr; c->pfxSize = 0;       // consumed, whatever this call returns (the reference consumes it at frame start)
+    size_t e = cctx_bind(c); if (isErr(e)) return e;
+    CallParams cp = sticky_params(c);
+    auto plain = [&]() { return deviceCall ? ZSTDMI_compressDevice_impl(c, dst, dstCapacity, src, srcSize) : compress_any(c, cp, dst, dstCapacity, src, srcSize); };
+    if (pfxSize < 8) return plain();
+    if (cp.seek || c->workers.size() > 1) return ZERR(kErrParameterUnsupported);
+    if (srcSize && !src) return ZERR(kErrSrcSizeWrong);
+    if (!dst) return dstCapacity && deviceCall ? ZERR(kErrDstBufferNull) : ZERR(kErrDstSizeTooSmall);
+    if (srcSize == 0) return plain();       // (the empty frame holds no match)
+    if (pfxSize <= kChunkSize && (size_t)round_tile(pfxSize) + srcSize <= kChunkSize) {
+        const size_t keep = pfxSize < kDictKeep ? pfxSize : kDictKeep;
+        std::vector<u8> h(keep);
+        if (hipMemcpy(h.data(), (const u8*)pfx + (pfxSize - keep), keep, hipMemcpyDefault) != hipSuccess) { (void)hipGetLastError(); return ZERR(kErrGeneric); }
+        c->dictHost.swap(h); c->dictFormatted = false; c->dictDirty = true; c->dictGen++;
+        const size_t r = plain();
+        c->dictHost.clear(); c->dictDirty = true; c->dictGen++;
+        return r;
+    }
+    { const size_t e2 = check_call_params(cp); if (isErr(e2)) return e2; }
+    if (cp.ldm == ZSTD_ps_disable || !cp.contentSizeFlag) return ZERR(kErrParameterUnsupported);
+    if ((u64)pfxSize + srcSize > kLdmMaxFrame) return ZERR(kErrParameterUnsupported);       // (the decoder's 29-bit offset record)
+    if (cp.windowLog && cp.windowLog < 31 && ((u64)1 << cp.windowLog) < (u64)pfxSize + srcSize) return ZERR(kErrParameterUnsupported);
+    cp.pfxSize = pfxSize;
+    { const Framing fr = resolve_framing(c, cp, srcSize); if ((srcSize + fr.chunkBytes - 1) / fr.chunkBytes > c->passChunks) return ZERR(kErrParameterUnsupported); }
+    if (is_device_ptr(pfx)) cp.pfx = (const u8*)pfx;
+    else {
+        if (!c->pfxStage.ensure(pfxSize + 64)) return ZERR(kErrMemoryAllocation);
+        if (hipMemcpyAsync(c->pfxStage.p, pfx, pfxSize, hipMemcpyHostToDevice, c->stream) != hipSuccess) return ZERR(kErrGeneric);
+        cp.pfx = (const u8*)c->pfxStage.p;
+    }
+    if (deviceCall) return compress_device(c, cp, (u8*)dst, dstCapacity, (const u8*)src, srcSize);
+    return compress_any(c, cp, dst, dstCapacity, src, srcSize);
+}
+static size_t ZSTD_CCtx_refPrefix_impl(ZSTD_CCtx* c, const void* prefix, size_t prefixSize)
+{
+    if (!c) return ZERR(kErrGeneric);
+    if (!c->sIn.empty() || c->sEnding) return ZERR(kErrStageWrong);
+    if (prefix && prefixSize > (size_t)1 << 30) return ZERR(kErrParameterUnsupported);
+    // ZSTD_clearAllDicts: a loaded dictionary and an earlier prefix are gone
+    c->dictGen++; c->dictFormatted = false; c->dictFull.clear(); c->dictHost.clear(); c->dictDirty = true;
+    c->pfx = nullptr; c->pfxSize = 0;
+    if (prefix && prefixSize) { c->pfx = prefix; c->pfxSize = prefixSize; }
+    return 0;
+}
+
+size_t ZSTDMI_compressDevice(ZSTD_CCtx* c, void* d_dst, size_t dstCapacity, const void* d_src, size_t srcSize)
+{
+    if (c && c->pfx) return guarded([&] { return compress_prefixed(c, d_dst, dstCapacity, d_src, srcSize, true); });
+    return guarded([&] { return ZSTDMI_compressDevice_impl(c, d_dst, dstCapacity, d_src, srcSize); });
+}
 size_t ZSTD_compress2(ZSTD_CCtx* c, void* dst, size_t dstCapacity, const void* src, size_t srcSize)
 {
     if (!c) return ZERR(kErrGeneric);
+    if (c->pfx) return guarded([&] { return compress_prefixed(c, dst, dstCapacity, src, srcSize, false); });
     return guarded([&] { return compress_any(c, sticky_params(c), dst, dstCapacity, src, srcSize); });
 }
+size_t ZSTD_CCtx_refPrefix(ZSTD_CCtx* c, const void* prefix, size_t prefixSize) { return guarded([&] { return ZSTD_CCtx_refPrefix_impl(c, prefix, prefixSize); }); }
 
 size_t ZSTD_compressCCtx(ZSTD_CCtx* c, void* dst, size_t dstCapacity, const void* src, size_t srcSize, int level)
 {
@@ -992,7 +1076,7 @@ size_t ZSTD_freeDCtx(ZSTD_DCtx* d)
     if (d->deviceOk) {
         (void)hipSetDevice(d->device);
         if (d->ownStream) (void)hipStreamSynchronize(d->ownStream);
-        d->frames.release(); d->blocks.release(); d->recs.release(); d->status.release(); d->scratch.release(); d->walkWs.release(); d->slowFlags.release(); d->stageSrc.release(); d->stageDst.release(); d->dict.release(); d->dictInfoDev.release(); d->origin.release(); d->originList.release(); d->batchIn.release(); d->batchOut.release(); d->blockKeys.release(); d->seekTab.release(); d->seekSum.release(); d->edge.release();
+        d->frames.release(); d->blocks.release(); d->recs.release(); d->status.release(); d->scratch.release(); d->walkWs.release(); d->slowFlags.release(); d->stageSrc.release(); d->stageDst.release(); d->dict.release(); d->dictInfoDev.release(); d->origin.release(); d->originList.release(); d->batchIn.release(); d->batchOut.release(); d->blockKeys.release(); d->seekTab.release(); d->seekSum.release(); d->edge.release(); d->pfxStage.release();
         d->timer.destroy();
         if (d->aux) { (void)hipStreamSynchronize(d->aux); (void)hipStreamDestroy(d->aux); }
         if (d->auxDone) (void)hipEventDestroy(d->auxDone);
@@ -1020,6 +1104,7 @@ static size_t ZSTD_DCtx_loadDictionary_impl(ZSTD_DCtx* d, const void* dict, size
 {
     if (!d) return ZERR(kErrGeneric);
     d->dictGen++;
+    d->pfx = nullptr; d->pfxSize = 0;       // (a pending prefix is cancelled: ZSTD_clearAllDicts)
     if (dict == nullptr || dictSize == 0) { d->dictHost.clear(); d->dictDirty = true; return 0; }
     if (dictSize > (size_t)1 << 30) return ZERR(kErrParameterUnsupported);
     std::vector<u8> h(dictSize);
@@ -1291,7 +1376,8 @@ static size_t decompress_device(ZSTD_DCtx* d, u8* d_dst, size_t dstCapacity, con
     if (!d->status.ensure(kStWords * sizeof(u32)) || !d->walkWs.ensure(decode_walk_workspace_bytes(srcSize))) return ZERR(kErrMemoryAllocation);
     u32* status = (u32*)d->status.p;
     { const size_t e = dctx_sync_dictionary(d); if (isErr(e)) return e; }
-    const DecodeDict dd = decode_dict(d);
+    DecodeDict dd = decode_dict(d);
+    if (d->pfxDev) { dd.dictContent = d->pfxDev; dd.dictContentSize = (u32)d->pfxSize; }      // ZSTD_DCtx_refPrefix: raw content, read where it lies
     const u32 dictID = dd.dictID;
     auto read_status = [&](u32* st) -> bool {
         if (hipMemcpyAsync(st, status, kStWords * sizeof(u32), hipMemcpyDeviceToHost, s) != hipSuccess) return false;
@@ -1388,7 +1474,7 @@ static size_t decompress_batch_impl(ZSTD_DCtx* d, const void* const* srcs, const
     if (!srcs || !srcSizes || !dsts || !dstCapacities || !dstSizes) return ZERR(kErrGeneric);
     if (n > 0xFFFFFFF0ull) return ZERR(kErrMemoryAllocation);
     size_t e = dctx_bind(d); if (isErr(e)) return e;
-    if (d->workers.size() > 1) return ZERR(kErrParameterUnsupported);
+    if (d->workers.size() > 1 || d->pfx) return ZERR(kErrParameterUnsupported);      // (a pending ZSTD_DCtx_refPrefix serves one single call)
     d->lastBatchAlone = 0;
     e = dctx_sync_dictionary(d); if (isErr(e)) return e;
     hipStream_t s = d->stream;
@@ -1443,7 +1529,7 @@ static size_t decompress_batch_impl(ZSTD_DCtx* d, const void* const* srcs, const
 static size_t decompress_range_impl(ZSTD_DCtx* d, void* dst, size_t dstCapacity, const void* src, size_t srcSize, unsigned long long offset, size_t length)
 {
     size_t e = dctx_bind(d); if (isErr(e)) return e;
-    if (d->workers.size() > 1) return ZERR(kErrParameterUnsupported);
+    if (d->workers.size() > 1 || d->pfx) return ZERR(kErrParameterUnsupported);
     d->lastRangeFrames = 0; d->lastRangeStaged = 0;
     if (srcSize && !src) return ZERR(kErrSrcSizeWrong);
     if (srcSize < 17) return ZERR(kErrPrefixUnknown);
@@ -1540,9 +1626,29 @@ static size_t decompress_range_impl(ZSTD_DCtx* d, void* dst, size_t dstCapacity,
 }
 
 static size_t decompress_multi(ZSTD_DCtx* d, void* dst, size_t dstCapacity, const void* src, size_t srcSize);
+// ZSTD_DCtx_refPrefix (U/ZstdDecompress.cs:2164-2202): the pending prefix becomes this call's raw-content dictionary — a device prefix
+// where it lies, a host prefix staged to HBM — and is consumed, whatever the call returns (PrefixUse's destructor)
+struct PrefixUse {
+    ZSTD_DCtx* d;
+    explicit PrefixUse(ZSTD_DCtx* dd) : d(dd) {}
+    size_t begin()
+    {
+        if (!d->pfx) return 0;
+        if (d->workers.size() > 1) return ZERR(kErrParameterUnsupported);
+        if (is_device_ptr(d->pfx)) { d->pfxDev = (const u8*)d->pfx; return 0; }
+        if (!d->pfxStage.ensure(d->pfxSize + 64)) return ZERR(kErrMemoryAllocation);
+        if (hipMemcpyAsync(d->pfxStage.p, d->pfx, d->pfxSize, hipMemcpyHostToDevice, d->stream) != hipSuccess) return ZERR(kErrGeneric);
+        d->pfxDev = (const u8*)d->pfxStage.p;
+        return 0;
+    }
+    ~PrefixUse() { d->pfx = nullptr; d->pfxSize = 0; d->pfxDev = nullptr; }
+};
 static size_t ZSTDMI_decompressDevice_impl(ZSTD_DCtx* d, void* d_dst, size_t dstCapacity, const void* d_src, size_t srcSize)
 {
+    if (!d) return ZERR(kErrGeneric);
+    PrefixUse use(d);
     size_t e = dctx_bind(d); if (isErr(e)) return e;
+    e = use.begin(); if (isErr(e)) return e;
     if (srcSize && !d_src) return ZERR(kErrSrcSizeWrong);
     if (d->workers.size() > 1 && srcSize) return decompress_multi(d, d_dst, dstCapacity, d_src, srcSize);
     return decompress_device(d, (u8*)d_dst, dstCapacity, (const u8*)d_src, srcSize);
@@ -1550,7 +1656,10 @@ static size_t ZSTDMI_decompressDevice_impl(ZSTD_DCtx* d, void* d_dst, size_t dst
 
 static size_t ZSTD_decompressDCtx_impl(ZSTD_DCtx* d, void* dst, size_t dstCapacity, const void* src, size_t srcSize)
 {
+    if (!d) return ZERR(kErrGeneric);
+    PrefixUse use(d);
     size_t e = dctx_bind(d); if (isErr(e)) return e;
+    e = use.begin(); if (isErr(e)) return e;
     if (srcSize && !src) return ZERR(kErrSrcSizeWrong);
     if (srcSize == 0) return 0;
     if (d->workers.size() > 1) return decompress_multi(d, dst, dstCapacity, src, srcSize);
@@ -1821,6 +1930,7 @@ static size_t ZSTD_compressStream2_impl(ZSTD_CCtx* c, ZSTD_outBuffer* output, ZS
     if (input->pos > input->size) return ZERR(105);            // srcBuffer_wrong
     if ((unsigned)endOp > 2) return ZERR(kErrParameterOutOfBound);
     if (c->seekTable) return ZERR(kErrParameterUnsupported);   // (a table per batch of the session would not be one table of the stream)
+    if (c->pfx) return ZERR(kErrParameterUnsupported);         // (a referenced prefix stands in front of ONE frame; a session writes one per batch)
     if (input->size > input->pos && !input->src) return ZERR(kErrSrcSizeWrong);
     if (output->size > output->pos && !output->dst) return ZERR(kErrDstBufferNull);
     if (cstream_drain(c, output)) return c->sOut.size() - c->sOutPos;       // output full: nothing consumed this time
@@ -1867,6 +1977,7 @@ static size_t ZSTD_decompressStream_impl(ZSTD_DCtx* d, ZSTD_outBuffer* output, Z
     if (input->pos > input->size) return ZERR(105);
     if (input->size > input->pos && !input->src) return ZERR(kErrSrcSizeWrong);
     if (output->size > output->pos && !output->dst) return ZERR(kErrDstBufferNull);
+    if (d->pfx) return ZERR(kErrParameterUnsupported);         // (a referenced prefix serves one single call)
     if (d->hostage && input->pos < input->size) { input->pos++; d->hostage = false; }       // that byte was consumed earlier
     size_t pending = dstream_drain(d, output);
     if (!pending) {
@@ -2033,6 +2144,16 @@ size_t ZSTDMI_debugPoisonedChunk(ZSTD_CCtx* c, unsigned nbSeq, unsigned litSize,
 // ---------------- entry points whose host-side containers may throw: guarded (see guarded()) ----------------
 size_t ZSTD_CCtx_loadDictionary(ZSTD_CCtx* c, const void* dict, size_t dictSize) { return guarded([&] { return ZSTD_CCtx_loadDictionary_impl(c, dict, dictSize); }); }
 size_t ZSTD_DCtx_loadDictionary(ZSTD_DCtx* d, const void* dict, size_t dictSize) { return guarded([&] { return ZSTD_DCtx_loadDictionary_impl(d, dict, dictSize); }); }
+size_t ZSTD_DCtx_refPrefix(ZSTD_DCtx* d, const void* prefix, size_t prefixSize)
+{
+    if (!d) return ZERR(kErrGeneric);
+    if (prefix && prefixSize > (size_t)1 << 30) return ZERR(kErrParameterUnsupported);
+    // ZSTD_clearAllDicts: a loaded dictionary and an earlier prefix are gone
+    d->dictGen++; d->dictHost.clear(); d->dictFormatted = false; d->dictDirty = true;
+    d->pfx = nullptr; d->pfxSize = 0;
+    if (prefix && prefixSize) { d->pfx = prefix; d->pfxSize = prefixSize; }
+    return 0;
+}
 size_t ZSTD_findFrameCompressedSize(const void* src, size_t srcSize) { return guarded([&] { return ZSTD_findFrameCompressedSize_impl(src, srcSize); }); }
 size_t ZSTD_decompressDCtx(ZSTD_DCtx* d, void* dst, size_t dstCapacity, const void* src, size_t srcSize) { return guarded([&] { return ZSTD_decompressDCtx_impl(d, dst, dstCapacity, src, srcSize); }); }
 size_t ZSTDMI_decompressBatch(ZSTD_DCtx* d, const void* const* srcs, const size_t* srcSizes, size_t n, void* const* dsts, const size_t* dstCapacities, size_t* dstSizes)
@@ -2230,7 +2351,7 @@ static size_t compress_batch_impl(ZSTD_CCtx* c, const void* const* srcs, const s
     if (n == 0) { c->lastBatchAlone = 0; return 0; }
     if (!srcs || !srcSizes || !dsts || !dstCapacities || !dstSizes) return ZERR(kErrGeneric);
     size_t e = cctx_bind(c); if (isErr(e)) return e;
-    if (c->workers.size() > 1 || c->seekTable) return ZERR(kErrParameterUnsupported);
+    if (c->workers.size() > 1 || c->seekTable || c->pfx) return ZERR(kErrParameterUnsupported);
     c->lastBatchAlone = 0;
     const CallParams cp = sticky_params(c);
     e = check_call_params(cp);

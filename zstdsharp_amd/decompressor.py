@@ -2,11 +2,11 @@
 import ctypes
 
 from . import _ffi
-from .compressor import _as_buffer
+from .compressor import _PrefixHolder, _as_buffer, _as_prefix
 from .errors import DST_SIZE_TOO_SMALL, ZstdException, ZSTD_ErrorCode, ensure_content_size_ok, ensure_zstd_success
 
 
-class Decompressor:
+class Decompressor(_PrefixHolder):
     """S/Decompressor.cs:7-148."""
 
     def __init__(self, device: int = None):
@@ -30,7 +30,18 @@ class Decompressor:
     def LoadDictionary(self, dict_bytes):                     # S/Decompressor.cs:29-36
         self._ensure_not_disposed()
         addr, n, keep = _as_buffer(dict_bytes if dict_bytes is not None else b"")
+        self._release_prefix()          # (ZSTD_DCtx_loadDictionary cancels a pending prefix)
         ensure_zstd_success(self._lib, self._lib.ZSTD_DCtx_loadDictionary(self.dctx, addr, n))
+
+    def RefPrefix(self, prefix):
+        """ZSTD_DCtx_refPrefix: the next Unwrap / TryUnwrap decodes its frames behind `prefix` (bytes-like or a contiguous CUDA uint8
+        tensor, read where it lies) — the prefix Compressor.RefPrefix was given.  Single use; cancels a loaded dictionary.  The object is
+        kept alive here until the consuming call has returned and must not change before."""
+        self._ensure_not_disposed()
+        addr, n, keep, device = _as_prefix(prefix)
+        self._release_prefix()
+        ensure_zstd_success(self._lib, self._lib.ZSTD_DCtx_refPrefix(self.dctx, addr, n))
+        self._hold_prefix(keep, device)
 
     @staticmethod
     def GetDecompressedSize(src) -> int:                      # S/Decompressor.cs:50-54
@@ -40,6 +51,13 @@ class Decompressor:
     def Unwrap(self, src, dest=None, offset: int = 0, maxDecompressedSize: int = (1 << 31) - 1):
         """Unwrap(src[, maxDecompressedSize=..]) -> bytes;  Unwrap(src, dest[, offset]) -> bytes written (S/Decompressor.cs:56-88)."""
         self._ensure_not_disposed()
+        try:
+            self._prefix_ready()
+            return self._unwrap(src, dest, offset, maxDecompressedSize)
+        finally:
+            self._release_prefix()      # (ZSTD_decompressDCtx consumed it, whatever it returned)
+
+    def _unwrap(self, src, dest, offset, maxDecompressedSize):
         saddr, sn, skeep = _as_buffer(src)
         if dest is None:
             expected = self.GetDecompressedSize(src)
@@ -56,7 +74,11 @@ class Decompressor:
         self._ensure_not_disposed()
         saddr, sn, skeep = _as_buffer(src)
         daddr, dn, dkeep = _as_buffer(dest)
-        r = self._lib.ZSTD_decompressDCtx(self.dctx, (daddr + offset) if daddr else None, dn - offset, saddr, sn)
+        try:
+            self._prefix_ready()
+            r = self._lib.ZSTD_decompressDCtx(self.dctx, (daddr + offset) if daddr else None, dn - offset, saddr, sn)
+        finally:
+            self._release_prefix()
         if r == DST_SIZE_TOO_SMALL:
             return False, 0
         return True, ensure_zstd_success(self._lib, r)
@@ -83,8 +105,8 @@ class Decompressor:
         n = ensure_zstd_success(lib, lib.ZSTDMI_decompressRange(self.dctx, out, length, saddr, sn, offset, length))
         return out.raw[:n]
 
-    unwrap, try_unwrap, set_parameter, get_parameter, load_dictionary, get_decompressed_size = \
-        Unwrap, TryUnwrap, SetParameter, GetParameter, LoadDictionary, GetDecompressedSize
+    unwrap, try_unwrap, set_parameter, get_parameter, load_dictionary, get_decompressed_size, ref_prefix = \
+        Unwrap, TryUnwrap, SetParameter, GetParameter, LoadDictionary, GetDecompressedSize, RefPrefix
 
     def Dispose(self):                                        # S/Decompressor.cs:113-147
         if getattr(self, "dctx", None):
