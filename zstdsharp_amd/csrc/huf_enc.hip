@@ -18,7 +18,7 @@
 //                       a byte is encoded.
 //   huf_encode_kernel : one 256-thread workgroup per chunk, wave w encodes stream w
 //                       (HUF_compress4X_usingCTable_internal, U/HufCompress.cs:1221-1321): symbols are taken last
-//                       to first, 8 per lane, their codes concatenated in registers, bit offsets come from a wave
+//                       to first, 16 per lane, their codes concatenated in registers, bit offsets come from a wave
 //                       prefix scan, and the lanes OR their bits into an LDS tile that is flushed with coalesced
 //                       dword stores.
 // Given the same literals and sequence count, the bytes produced equal the oracle's
@@ -701,14 +701,108 @@ extern "C" void ZSTDMI_debugReadHufStamps(unsigned long long* out16, int reset)
 #endif
 
 // ------------------------------------------------------------------------------------------------
-constexpr u32 kSymPerLane = 8;
-constexpr u32 kTileSyms   = 64 * kSymPerLane;             // 512 symbols per wave step, <= 5632 bits
-constexpr u32 kTileWords  = (kTileSyms * 11 + 31) / 32 + 2;
+constexpr u32 kSymPerLane = 16;
+constexpr u32 kTileSyms   = 64 * kSymPerLane;             // 1024 symbols per wave step, <= 11264 bits
+// 11264 bits behind at most 31 carried ones end in dword 352; a lane ORs four dwords per half whatever they hold, the last of
+// them at most three dwords further: 356, a whole number of 16-byte pieces (the tile is zeroed in those)
+constexpr u32 kTileWords  = 356;
+static_assert((31 + kTileSyms * 11) / 32 + 3 < kTileWords && kTileWords % 4 == 0 && kTileWords <= 128 * 4, "tile holds every OR; zeroed in two 16-byte stores per lane");
+static_assert((31 + kTileSyms * 11) / 32 <= 6 * 64, "a tile is flushed in at most six stores per lane");
 
-struct HufEncLds {
-    u32 ct[256];                       // code | nbBits << 16
+struct alignas(16) HufEncLds {
+    u32 ct[256];                       // nbBits | code << 8: a sum of entries keeps the sum of the lengths in its low byte (16 x 11 = 176),
+                                       // and a shift takes its count from the low bits of an entry or of such a sum as it is
     u32 tile[4][kTileWords];
 };
+typedef u32 u32x4u __attribute__((ext_vector_type(4), aligned(1)));     // one unaligned global_load_dwordx4
+
+// inclusive prefix sum across the wave without LDS: four steps inside the rows of 16 lanes (row_shr 1, 2, 4, 8: a lane without a
+// source keeps the 0), then the total of row 0 / 2 into row 1 / 3 (row_bcast:15) and that of rows 0-1 into rows 2-3 (row_bcast:31)
+__device__ __forceinline__ u32 wave_scan_incl_dpp(u32 v)
+{
+    v += (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xF, 0xF, false);
+    v += (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xF, 0xF, false);
+    v += (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xF, 0xF, false);
+    v += (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xF, 0xF, false);
+    v += (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xA, 0xF, false);
+    v += (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xC, 0xF, false);
+    return v;
+}
+
+// One tile of a stream: the lane's 16 symbols are the reversed indices kb .. kb + 15, i.e. the source bytes len - 1 - kb downwards,
+// which `pack` holds in descending order (byte 15 first) when all 16 are in range.  FULL: every lane's are (k0 + kTileSyms <= len):
+// no test per symbol.  Otherwise a lane whose 16 straddle the stream's start reads them byte by byte, and lanes behind it add nothing.
+template <bool FULL>
+__device__ __forceinline__ void huf_encode_tile(const u32* __restrict__ ct, u32* __restrict__ tile, const u8* __restrict__ sym, const u32 len,
+                                                const u32 kb, const uint4 pack, uint4& packNext, const u32 lane, u8* __restrict__ out,
+                                                u32& carry, u32& carryBits, u32& outWords)
+{
+    {
+        uint4* z4 = reinterpret_cast<uint4*>(tile);
+        z4[lane] = make_uint4(0u, 0u, 0u, 0u);
+        if (lane < kTileWords / 4 - 64) z4[64 + lane] = make_uint4(0u, 0u, 0u, 0u);
+    }
+    const u32 d[4] = { pack.x, pack.y, pack.z, pack.w };
+    const bool full16 = FULL || kb + kSymPerLane <= len;
+    u32 e[kSymPerLane];
+#pragma unroll
+    for (u32 j = 0; j < kSymPerLane; j++) {
+        u32 s8 = (d[3 - (j >> 2)] >> (8 * (3 - (j & 3)))) & 0xFFu;
+        if (FULL) e[j] = ct[s8];
+        else {
+            const u32 k = kb + j;
+            if (!full16) s8 = k < len ? (u32)sym[len - 1 - k] : 0u;
+            e[j] = k < len ? ct[s8] : 0u;
+        }
+    }
+    // codes are at most 11 bits: two fit 32 bits (one shift-or), four fit 64, eight need 88.  The two halves of the lane go to the
+    // tile separately: joining them would cost more shifts than the OR it saves.
+    u32 p[8], ps[8];
+#pragma unroll
+    for (u32 i = 0; i < 8; i++) { const u32 a = e[2 * i], b = e[2 * i + 1]; p[i] = ((b >> 8) << (a & 31u)) | (a >> 8); ps[i] = a + b; }
+    u64 q[4]; u32 qs[4];
+#pragma unroll
+    for (u32 i = 0; i < 4; i++) { q[i] = (u64)p[2 * i] | ((u64)p[2 * i + 1] << (ps[2 * i] & 63u)); qs[i] = ps[2 * i] + ps[2 * i + 1]; }
+    u64 lo[2]; u32 hi[2], hs[2];
+#pragma unroll
+    for (u32 h = 0; h < 2; h++) {
+        const u32 t = qs[2 * h];                                       // <= 44 in its low byte
+        lo[h] = q[2 * h] | (q[2 * h + 1] << (t & 63u));
+        hi[h] = (u32)((q[2 * h + 1] >> 1) >> (~t & 63u));              // >> (64 - t), also right for t = 0
+        hs[h] = qs[2 * h] + qs[2 * h + 1];
+    }
+    const u32 nb0 = hs[0] & 0xFFu, nb = (hs[0] + hs[1]) & 0xFFu;
+    const u32 incl = wave_scan_incl_dpp(nb);
+    const u32 tileBits = read_lane(incl, 63);
+    const u32 bitOff = carryBits + incl - nb;
+#pragma unroll
+    for (u32 h = 0; h < 2; h++) {
+        // up to 88 bits shifted by < 32: four dwords; a zero ORs nothing, so none of them is tested
+        const u32 at = h ? bitOff + nb0 : bitOff;
+        const u32 w0 = at >> 5, sh = at & 31u;
+        const u64 a0 = lo[h] << sh;
+        const u64 a1 = (((u64)hi[h] << 32) | (lo[h] >> 32)) << sh;
+        const u64 a2 = (u64)hi[h] << sh;
+        atomicOr(&tile[w0], (u32)a0);
+        atomicOr(&tile[w0 + 1], (u32)(a0 >> 32));
+        atomicOr(&tile[w0 + 2], (u32)(a1 >> 32));
+        atomicOr(&tile[w0 + 3], (u32)(a2 >> 32));
+    }
+    if (lane == 0 && carryBits) atomicOr(&tile[0], carry);
+    const u32 total = carryBits + tileBits;
+    const u32 fullWords = total >> 5;
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    // The next tile's symbols, on their way since the top of this tile, are waited for HERE: loads and stores share one in-order
+    // counter, so waiting for them at the top of the next tile would also wait until the stores below have reached L2.
+    if (FULL) asm volatile("" : "+v"(packNext.x), "+v"(packNext.y), "+v"(packNext.z), "+v"(packNext.w));
+#pragma unroll
+    for (u32 r = 0; r < 6; ++r) { const u32 i = lane + 64 * r; if (i < fullWords) *(u32u*)(out + 4 * (outWords + i)) = tile[i]; }
+    carry = tile[fullWords]; carryBits = total & 31;       // every lane reads the same LDS word
+    outWords += fullWords;
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
 
 // `dst` != nullptr: the literals section goes straight to its final place in the output (offsets[] from the scan; the
 // sequences section and the headers follow through gather_kernel); nullptr: into the chunk's slot (test hook).
@@ -718,7 +812,10 @@ __global__ __launch_bounds__(256) void huf_encode_kernel(const u8* __restrict__ 
                                                          const u8* __restrict__ src, const u32 chunkBytes)
 {
     __shared__ HufEncLds L;
-    const u32 c = blockIdx.x, tid = threadIdx.x, lane = lane_id(), wave = wave_id();
+    const u32 c = blockIdx.x, tid = threadIdx.x, lane = lane_id(), wave = uniform(wave_id());
+    // (the table entry is fetched beside the chunk's record, not behind it: the chunk's table exists whatever the literals' mode)
+    const HufTable* __restrict__ T = tables + c;
+    const u32 ctEntry = (u32)T->nbBits[tid] | ((u32)T->code[tid] << 8);
     const ChunkMeta m = meta_checked(meta[c]);
     const u32 litSize = m.litSize;
     const u8* __restrict__ lit = m.litFromSrc ? src + (u64)c * chunkBytes : lits + (u64)c * kLitStride;
@@ -744,8 +841,20 @@ __global__ __launch_bounds__(256) void huf_encode_kernel(const u8* __restrict__ 
         if (type == 0) for (u32 i = tid; i < litSize; i += 256) body[m.lhSize + i] = lit[i];
         return;
     }
-    const HufTable* __restrict__ T = tables + c;
-    L.ct[tid] = (u32)T->code[tid] | ((u32)T->nbBits[tid] << 16);
+    L.ct[tid] = ctEntry;
+    // the stream of this wave; its first symbols are on their way while the headers are written
+    const u32 nStreams = m.litSingle ? 1 : 4;
+    const u32 seg = m.litSingle ? litSize : (litSize + 3) / 4;
+    const u32 s0 = wave * seg;
+    const u32 len = uniform(wave >= nStreams ? 0u : (wave == nStreams - 1) ? litSize - s0 : seg);
+    const u8* __restrict__ sym = lit + s0;
+    auto load_pack = [&](u32 k0) -> uint4 {
+        const u32 kb = k0 + lane * kSymPerLane;
+        if (kb + kSymPerLane > len) return make_uint4(0u, 0u, 0u, 0u);
+        const u32x4u v = *reinterpret_cast<const u32x4u*>(sym + (len - kSymPerLane - kb));
+        return make_uint4(v.x, v.y, v.z, v.w);
+    };
+    uint4 packNext = load_pack(0);
     if (tid == 0) {
         const u32 cLitSize = m.litSectionSize - m.lhSize;
         switch (m.lhSize) {       // ZSTD_compressLiterals header (U/ZstdCompressLiterals.cs:150-182)
@@ -759,74 +868,30 @@ __global__ __launch_bounds__(256) void huf_encode_kernel(const u8* __restrict__ 
     if (!m.litSingle && tid < 3) writeLE16(payload + 2 * tid, meta[c].streamSize[tid]);       // jump table
     __syncthreads();
 
-    const u32 nStreams = m.litSingle ? 1 : 4;
     if (wave >= nStreams) return;
-    const u32 seg = m.litSingle ? litSize : (litSize + 3) / 4;
-    const u32 s0 = wave * seg;
-    const u32 len = (wave == nStreams - 1) ? litSize - s0 : seg;
     u8* out = payload + (m.litSingle ? 0 : 6);
     for (u32 w = 0; w < wave; w++) out += meta[c].streamSize[w];
-    const u8* __restrict__ sym = lit + s0;
     u32* tile = L.tile[wave];
 
     u32 carry = 0, carryBits = 0;        // bits of a partially filled dword carried into the next tile
     u32 outWords = 0;                    // dwords already flushed to `out`
-    // The lane's 8 symbols of a tile sit in 8 consecutive bytes (descending): one unaligned 8-byte load when all are in range —
+    // The lane's 16 symbols of a tile sit in 16 consecutive bytes (descending): one unaligned 16-byte load when all are in range —
     // issued a tile AHEAD (its way from HBM was the longest part of a tile's time); the tile belongs to this wave alone, so its LDS
     // traffic needs program order only (a wavefront fence: the workgroup fences that stood here waited for every store to reach
-    // L2, twice per tile).  0.74 -> 0.59 ms per GiB of Zipf bytes; writing the tile out a step later changed nothing more.
-    auto load_pack = [&](u32 k0) -> u64 {
-        const u32 kb = k0 + lane * kSymPerLane;
-        return (k0 < len && kb + kSymPerLane <= len) ? *reinterpret_cast<const u64u*>(sym + (len - kSymPerLane - kb)) : 0ull;
-    };
-    static_assert(kTileWords <= 3 * 64, "a tile is flushed in at most three stores per lane");
-    u64 packNext = load_pack(0);
-    for (u32 k0 = 0; k0 < len; k0 += kTileSyms) {
-        for (u32 i = lane; i < kTileWords; i += 64) tile[i] = 0;
-        // lane handles reversed indices k0 + lane*8 .. +7  ->  source bytes len-1-k, descending
-        const u32 kb = k0 + lane * kSymPerLane;
-        const bool full8 = kb + kSymPerLane <= len;
-        const u64 pack = packNext;
-        packNext = load_pack(k0 + kTileSyms);
-        // codes are at most 11 bits: symbols 0..4 fit one 64-bit accumulator (<= 55 bits), symbols 5..7 another (<= 33),
-        // so the per-symbol step is a plain shift-or; the two halves are joined once
-        u64 accA = 0, accB = 0; u32 nA = 0, nB = 0;
-#pragma unroll
-        for (u32 j = 0; j < kSymPerLane; j++) {
-            const u32 k = kb + j;
-            const u32 s8 = full8 ? (u32)(pack >> (8 * (kSymPerLane - 1 - j))) & 0xFFu : (k < len ? (u32)sym[len - 1 - k] : 0u);
-            const u32 e = k < len ? L.ct[s8] : 0u;
-            const u64 code = e & 0xFFFF; const u32 b = e >> 16;
-            if (j < 5) { accA |= code << nA; nA += b; } else { accB |= code << nB; nB += b; }
+    // L2, twice per tile).  Whole tiles run the body without a test per symbol; what is left of the stream — or all of a stream
+    // shorter than a tile — runs the general body once.
+    asm volatile("" : "+v"(packNext.x), "+v"(packNext.y), "+v"(packNext.z), "+v"(packNext.w));     // (so that the loop never waits at its top: see the flush)
+    u32 k0 = 0;
+    for (; k0 + kTileSyms <= len; k0 += kTileSyms) {
+        const uint4 pack = packNext;
+        {   // (no branch around the load: a lane whose next 16 are not all there reads the stream's first 16 and never uses them)
+            const u32 kn = k0 + kTileSyms + lane * kSymPerLane;
+            const u32x4u v = *reinterpret_cast<const u32x4u*>(sym + (kn + kSymPerLane <= len ? len - kSymPerLane - kn : 0u));
+            packNext = make_uint4(v.x, v.y, v.z, v.w);
         }
-        const u32 nb = nA + nB;
-        const u64 lo = accA | (nA < 64 ? accB << nA : 0ull);
-        const u64 hi = nA ? accB >> (64 - nA) : 0ull;
-        const u32 incl = wave_scan_incl(nb);
-        const u32 tileBits = read_lane(incl, 63);
-        const u32 bitOff = carryBits + incl - nb;
-        if (nb) {
-            const u32 w0 = bitOff >> 5, sh = bitOff & 31;
-            // up to 88 bits shifted by <32 -> spans at most 4 dwords
-            const u64 a0 = lo << sh;
-            const u64 a1 = sh ? ((lo >> (64 - sh)) | (hi << sh)) : hi;
-            atomicOr(&tile[w0], (u32)a0);
-            if ((u32)(a0 >> 32)) atomicOr(&tile[w0 + 1], (u32)(a0 >> 32));
-            if ((u32)a1) atomicOr(&tile[w0 + 2], (u32)a1);
-            if ((u32)(a1 >> 32)) atomicOr(&tile[w0 + 3], (u32)(a1 >> 32));
-        }
-        if (lane == 0 && carryBits) atomicOr(&tile[0], carry);
-        const u32 total = carryBits + tileBits;
-        const u32 fullWords = total >> 5;
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-#pragma unroll
-        for (u32 r = 0; r < 3; ++r) { const u32 i = lane + 64 * r; if (i < fullWords) *(u32u*)(out + 4 * (outWords + i)) = tile[i]; }
-        carry = tile[fullWords]; carryBits = total & 31;       // every lane reads the same LDS word
-        outWords += fullWords;
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
+        huf_encode_tile<true>(L.ct, tile, sym, len, k0 + lane * kSymPerLane, pack, packNext, lane, out, carry, carryBits, outWords);
     }
+    if (k0 < len) huf_encode_tile<false>(L.ct, tile, sym, len, k0 + lane * kSymPerLane, packNext, packNext, lane, out, carry, carryBits, outWords);
     if (lane == 0) {       // end mark + tail bytes (HUF_closeCStream, U/HufCompress.cs:964-979)
         u32 v = carry | (1u << carryBits);
         const u32 nbytes = (carryBits + 1 + 7) >> 3;
