@@ -116,6 +116,43 @@ __global__ void frame_walk_serial_kernel(const u8* __restrict__ src, u64 srcSize
 constexpr u32 kSegLog = 17;
 struct SegInfo { u64 entry, exit, dstBytes; u32 count, valid, blocks, pad; };
 
+// The scan for a segment's first frame start is a chain of dependent memory latencies (a window is tested before the next one is
+// fetched), so a window is wide: kWalkU groups of 1 KiB, a group being one 16-byte load per lane, all issued before the first is tested.
+#ifndef ZMI_WALK_U
+#define ZMI_WALK_U 4
+#endif
+constexpr u32 kWalkU = ZMI_WALK_U;
+constexpr u64 kWalkWindow = 1024ull * kWalkU;
+typedef u32 u32x4 __attribute__((ext_vector_type(4)));
+typedef u32x4 __attribute__((aligned(1))) u32x4u;
+
+__device__ __forceinline__ bool is_frame_magic(u32 v) { return v == 0xFD2FB528u || (v >> 4) == 0x184D2A5u; }
+// the n <= 16 bytes at src + off that lie inside the input, the others zero (no magic has a zero byte on top, so zeros never match)
+__device__ inline u32x4 load_piece_bytes(const u8* __restrict__ src, u64 srcSize, u64 off)
+{
+    u64 lo = 0, hi = 0;
+#pragma unroll
+    for (u32 k = 0; k < 8; ++k) {
+        if (off + k < srcSize) lo |= (u64)src[off + k] << (8 * k);
+        if (off + 8 + k < srcSize) hi |= (u64)src[off + 8 + k] << (8 * k);
+    }
+    u32x4 v; v.x = (u32)lo; v.y = (u32)(lo >> 32); v.z = (u32)hi; v.w = (u32)(hi >> 32);
+    return v;
+}
+// bit k: the dword at byte k of (v, next) is a frame or skippable-frame magic
+__device__ __forceinline__ u32 magic_mask16(u32x4 v, u32 next)
+{
+    const u32 d[5] = { v.x, v.y, v.z, v.w, next };
+    u32 mask = 0;
+#pragma unroll
+    for (u32 k = 0; k < 16; ++k) {
+        const u32 sh = 8 * (k & 3);
+        const u32 w = sh ? (d[k >> 2] >> sh) | (d[(k >> 2) + 1] << (32 - sh)) : d[k >> 2];
+        if (is_frame_magic(w)) mask |= 1u << k;
+    }
+    return mask;
+}
+
 __global__ __launch_bounds__(64) void walk_segments_kernel(const u8* __restrict__ src, u64 srcSize, SegInfo* __restrict__ segs, u32 nSeg)
 {
     const u32 s = blockIdx.x, lane = threadIdx.x;
@@ -123,93 +160,156 @@ __global__ __launch_bounds__(64) void walk_segments_kernel(const u8* __restrict_
     const u64 segStart = (u64)s << kSegLog;
     const u64 segEnd = (segStart + (1ull << kSegLog)) < srcSize ? segStart + (1ull << kSegLog) : srcSize;
     SegInfo r; r.entry = 0; r.exit = 0; r.dstBytes = 0; r.count = 0; r.valid = 0; r.blocks = 0; r.pad = 0;
-    u64 scan = segStart;
-    while (scan < segEnd) {
-        // 64 lanes x 4 byte positions: a position p is a candidate if the dword at p is a frame or skippable-frame magic
-        const u64 base = scan + 4 * lane;
-        u64 w = 0;
-        if (base + 8 <= srcSize) w = readLE64(src + base);
-        else for (u32 k = 0; k < 8; k++) if (base + k < srcSize) w |= (u64)src[base + k] << (8 * k);
-        u32 hit = 4;
+    // a position p is a candidate if the dword at p is a frame or skippable-frame magic; the position segEnd - 1 reads up to segEnd + 2
+    const u64 readEnd = segEnd + 3;
+    for (u64 win = segStart; win < segEnd && !r.valid; win += kWalkWindow) {
+        // lane l of group g holds the 16 positions from win + 1024 g + 16 l.  A window that lies inside the input with the dword behind
+        // it (every window but the last few of the input) is loaded without a condition in sight, so that nothing waits between the
+        // loads; in the others a piece that would reach past the input is read bytewise, and one wholly past readEnd not at all.
+        u32x4 v[kWalkU];
+        u32 tail;                                               // the dword behind the window: what the last lane's positions run into
+        if (win + kWalkWindow + 4 <= srcSize) {
+            const u8* const p = src + win + 16 * lane;
 #pragma unroll
-        for (int k = 3; k >= 0; k--) {
-            const u32 v = (u32)(w >> (8 * k));
-            if ((v == 0xFD2FB528u || (v & 0xFFFFFFF0u) == 0x184D2A50u) && base + k < segEnd) hit = k;
+            for (u32 g = 0; g < kWalkU; ++g) v[g] = *(const u32x4u*)(p + 1024 * g);
+            tail = readLE32(src + win + kWalkWindow);
+        } else {
+#pragma unroll
+            for (u32 g = 0; g < kWalkU; ++g) {
+                const u64 off = win + 1024 * g + 16 * lane;
+                v[g] = (u32x4)(0u);
+                if (off < readEnd) { if (off + 16 <= srcSize) v[g] = *(const u32x4u*)(src + off); else v[g] = load_piece_bytes(src, srcSize, off); }
+            }
+            tail = load_piece_bytes(src, srcSize, win + kWalkWindow).x;
         }
-        const u64 m = ballot(hit < 4);
-        if (!m) { scan += 256; continue; }
-        const u32 fl = ctz64(m);
-        const u64 cand = scan + 4 * fl + read_lane(hit, fl);
-        // validate by chaining until the chain leaves the segment (every lane walks the same chain: uniform)
-        u64 pos = cand, dstBytes = 0, nBlocks = 0; u32 count = 0; bool ok = true;
-        while (pos < segEnd) {
-            ChainOut o;
-            const u32 st = chain_step(src, srcSize, pos, o);
-            // frames naming a dictionary and frames without a content size take the serial walk (it knows the loaded dictionary,
-            // and the regenerated sizes of unsized frames decide where everything behind them goes)
-            if (st >= 2 || (st == 0 && (o.dictID || o.unsized))) { ok = false; break; }
-            if (st == 0) { count++; dstBytes += o.content; nBlocks += o.nbBlocks; }
-            pos = o.next;
+        u32 hm[kWalkU];                                         // per lane and group: hit mask of its 16 positions
+#pragma unroll
+        for (u32 g = 0; g < kWalkU; ++g) {
+            const u64 off = win + 1024 * g + 16 * lane;
+            u32 next = __shfl_down(v[g].x, 1);
+            const u32 carry = g + 1 < kWalkU ? read_lane(v[g + 1 < kWalkU ? g + 1 : g].x, 0) : tail;
+            if (lane == 63) next = carry;
+            u32 m = magic_mask16(v[g], next);
+            if (off >= segEnd) m = 0; else if (segEnd - off < 16) m &= (1u << (u32)(segEnd - off)) - 1u;
+            hm[g] = m;
         }
-        // A magic that turns up by chance inside a frame's payload (the sixteen skippable-frame magics: once per 270 MB of
-        // incompressible payload) can chain out of the segment too — a skippable frame of any size that stays inside the input is
-        // "valid" — and, where it lies in front of the segment's first real frame, the link check then sends the whole call to the
-        // serial walk (40 ms for 16 384 frames).  A real chain leaves the segment AT a frame (or at the end of the input): a
-        // candidate whose chain lands anywhere else is not one.
-        if (ok && pos != srcSize) {
-            u32 v = 0;
-            if (srcSize - pos >= 4) v = readLE32(src + pos);
-            if (!(v == 0xFD2FB528u || (v & 0xFFFFFFF0u) == 0x184D2A50u)) ok = false;
+        for (;;) {
+            // the lowest hit still in the masks: groups in order, then the first lane, then the lowest bit
+            u64 cand = ~0ull;
+#pragma unroll
+            for (u32 g = 0; g < kWalkU; ++g) {
+                if (cand != ~0ull) continue;
+                const u64 m = ballot(hm[g] != 0);
+                if (!m) continue;
+                const u32 fl = ctz64(m), bits = read_lane(hm[g], fl);
+                cand = win + 1024 * g + 16 * fl + (u32)__builtin_ctz(bits);
+                if (lane == fl) hm[g] = bits & (bits - 1);
+            }
+            if (cand == ~0ull) break;
+            // validate by chaining until the chain leaves the segment (every lane walks the same chain: uniform)
+            u64 pos = cand, dstBytes = 0, nBlocks = 0; u32 count = 0; bool ok = true;
+            while (pos < segEnd) {
+                ChainOut o;
+                const u32 st = chain_step(src, srcSize, pos, o);
+                // frames naming a dictionary and frames without a content size take the serial walk (it knows the loaded dictionary,
+                // and the regenerated sizes of unsized frames decide where everything behind them goes)
+                if (st >= 2 || (st == 0 && (o.dictID || o.unsized))) { ok = false; break; }
+                if (st == 0) { count++; dstBytes += o.content; nBlocks += o.nbBlocks; }
+                pos = o.next;
+            }
+            // A magic that turns up by chance inside a frame's payload (the sixteen skippable-frame magics: once per 270 MB of
+            // incompressible payload) can chain out of the segment too — a skippable frame of any size that stays inside the input is
+            // "valid" — and, where it lies in front of the segment's first real frame, the link check then sends the whole call to the
+            // serial walk (40 ms for 16 384 frames).  A real chain leaves the segment AT a frame (or at the end of the input): a
+            // candidate whose chain lands anywhere else is not one.
+            if (ok && pos != srcSize) {
+                u32 w = 0;
+                if (srcSize - pos >= 4) w = readLE32(src + pos);
+                if (!is_frame_magic(w)) ok = false;
+            }
+            if (ok && nBlocks < 0xFFFFFFF0ull) { r.entry = cand; r.exit = pos; r.dstBytes = dstBytes; r.count = count; r.blocks = (u32)nBlocks; r.valid = 1; break; }
+            // false positive (or a corrupt stream: the link check then sends us to the serial walk): on to the next hit
         }
-        if (ok && nBlocks < 0xFFFFFFF0ull) { r.entry = cand; r.exit = pos; r.dstBytes = dstBytes; r.count = count; r.blocks = (u32)nBlocks; r.valid = 1; break; }
-        scan = cand + 1;           // false positive (or a corrupt stream: the link check then sends us to the serial walk)
     }
     if (lane == 0) segs[s] = r;
 }
 
+// The single-workgroup scans (walk_link, seq_scan, frame_rescan) take kScanItems consecutive items per thread and round, and a
+// round's loads are issued before the round in front of it reaches its barrier: the barrier orders LDS only (lds_barrier; the
+// per-wave totals are double-buffered, so one barrier a round is enough), so no load waits for a barrier and a round costs its
+// arithmetic, not a memory latency.
+constexpr u32 kScanItems = 4;
+constexpr u32 kScanRound = 1024 * kScanItems;
+
+// (walk_link carries a whole SegInfo per item: two per thread keep it in registers)
+constexpr u32 kLinkItems = 2;
+constexpr u32 kLinkRound = 1024 * kLinkItems;
 // single workgroup: link check + prefix sums.  status: frames, total, blocks; [kStUsable] = 1 when the parallel walk is usable
 __global__ __launch_bounds__(1024) void walk_link_kernel(const SegInfo* __restrict__ segs, u32 nSeg, u64 srcSize, u32 maxFrames,
                                                          u32* __restrict__ frameBase, u32* __restrict__ blockBase, u64* __restrict__ dstBase,
                                                          u32* __restrict__ status)
 {
-    __shared__ u64 sh64[16], shBlk[16]; __shared__ u32 sh32[16]; __shared__ s32 shLast[16]; __shared__ u32 bad;
+    __shared__ u64 sh64[2][16], shBlk[2][16], shExit[2][16]; __shared__ u32 sh32[2][16]; __shared__ s32 shLast[2][16]; __shared__ u32 bad;
     const u32 tid = threadIdx.x, lane = lane_id(), wave = wave_id();
     if (tid == 0) bad = 0;
     __syncthreads();
-    u64 carryDst = 0, carryBlk = 0; u32 carryCnt = 0; s32 carryLast = -1;
-    for (u32 base = 0; base < nSeg; base += 1024) {
-        const u32 i = base + tid;
-        SegInfo g; g.valid = 0; g.count = 0; g.dstBytes = 0; g.entry = 0; g.exit = 0; g.blocks = 0;
-        if (i < nSeg) g = segs[i];
-        // inclusive scans inside the wave: counts, bytes, blocks, index of the last valid segment
-        u32 c = g.valid ? g.count : 0; u64 b = g.valid ? g.dstBytes : 0, k = g.valid ? g.blocks : 0; s32 lastv = g.valid ? (s32)i : -1;
-        u32 ci = c; u64 bi = b, ki = k; s32 li = lastv;
+    u64 carryDst = 0, carryBlk = 0, carryExit = 0; u32 carryCnt = 0; s32 carryLast = -1;
+    SegInfo g[kLinkItems], nx[kLinkItems];
+    auto load = [&](u32 base, SegInfo (&o)[kLinkItems]) {
+#pragma unroll
+        for (u32 j = 0; j < kLinkItems; ++j) {
+            const u32 i = base + tid * kLinkItems + j;
+            o[j].valid = 0; o[j].count = 0; o[j].dstBytes = 0; o[j].entry = 0; o[j].exit = 0; o[j].blocks = 0; o[j].pad = 0;
+            if (i < nSeg) o[j] = segs[i];
+        }
+    };
+    load(0, g);
+    u32 par = 0;
+    for (u32 base = 0; base < nSeg; base += kLinkRound, par ^= 1) {
+        if (base + kLinkRound < nSeg) load(base + kLinkRound, nx);
+        // my valid segments: counts, bytes, blocks, and the last one's index and exit
+        u32 c = 0; u64 b = 0, k = 0, ex = 0; s32 lastv = -1;
+#pragma unroll
+        for (u32 j = 0; j < kLinkItems; ++j)
+            if (g[j].valid) { c += g[j].count; b += g[j].dstBytes; k += g[j].blocks; lastv = (s32)(base + tid * kLinkItems + j); ex = g[j].exit; }
+        // inclusive scans inside the wave (the last valid segment so far travels with its exit: what the next valid one must enter at)
+        u32 ci = c; u64 bi = b, ki = k, ei = ex; s32 li = lastv;
 #pragma unroll
         for (int d = 1; d < 64; d <<= 1) {
-            const u32 tc = __shfl_up(ci, d); const u64 tb = __shfl_up(bi, d), tk = __shfl_up(ki, d); const s32 tl = __shfl_up(li, d);
-            if ((int)lane >= d) { ci += tc; bi += tb; ki += tk; li = tl > li ? tl : li; }
+            const u32 tc = __shfl_up(ci, d); const u64 tb = __shfl_up(bi, d), tk = __shfl_up(ki, d), te = __shfl_up(ei, d); const s32 tl = __shfl_up(li, d);
+            if ((int)lane >= d) { ci += tc; bi += tb; ki += tk; if (tl > li) { li = tl; ei = te; } }
         }
-        if (lane == 63) { sh32[wave] = ci; sh64[wave] = bi; shBlk[wave] = ki; shLast[wave] = li; }
-        __syncthreads();
-        u32 cb = carryCnt; u64 bb = carryDst, kb = carryBlk; s32 lb = carryLast; u32 call = 0; u64 ball = 0, kall = 0; s32 lall = -1;
+        if (lane == 63) { sh32[par][wave] = ci; sh64[par][wave] = bi; shBlk[par][wave] = ki; shLast[par][wave] = li; shExit[par][wave] = ei; }
+        lds_barrier();
+        u32 cb = carryCnt; u64 bb = carryDst, kb = carryBlk, eb = carryExit; s32 lb = carryLast; u32 call = 0; u64 ball = 0, kall = 0, eall = 0; s32 lall = -1;
+#pragma unroll 2
         for (u32 w = 0; w < 16; w++) {
-            if (w < wave) { cb += sh32[w]; bb += sh64[w]; kb += shBlk[w]; lb = shLast[w] > lb ? shLast[w] : lb; }
-            call += sh32[w]; ball += sh64[w]; kall += shBlk[w]; lall = shLast[w] > lall ? shLast[w] : lall;
+            const s32 lw = shLast[par][w]; const u64 ew = shExit[par][w];
+            if (w < wave) { cb += sh32[par][w]; bb += sh64[par][w]; kb += shBlk[par][w]; if (lw > lb) { lb = lw; eb = ew; } }
+            call += sh32[par][w]; ball += sh64[par][w]; kall += shBlk[par][w]; if (lw > lall) { lall = lw; eall = ew; }
         }
         // previous valid segment (exclusive): from the lanes before me in my wave, else from earlier waves / rounds
-        s32 prevInWave = __shfl_up(li, 1); if (lane == 0) prevInWave = -1;
-        const s32 prevValid = prevInWave > lb ? prevInWave : lb;
-        if (i < nSeg && g.valid) {
-            const u64 expect = prevValid >= 0 ? segs[prevValid].exit : 0;
-            if (g.entry != expect) atomicOr(&bad, 1u);
-            frameBase[i] = cb + ci - c; dstBase[i] = bb + bi - b; blockBase[i] = (u32)(kb + ki - k);
+        s32 prev = __shfl_up(li, 1); u64 prevExit = __shfl_up(ei, 1);
+        if (lane == 0 || prev <= lb) { prev = lb; prevExit = eb; }
+        u32 fb = cb + ci - c; u64 db = bb + bi - b, kk = kb + ki - k;
+#pragma unroll
+        for (u32 j = 0; j < kLinkItems; ++j) {
+            const u32 i = base + tid * kLinkItems + j;
+            if (i < nSeg && g[j].valid) {
+                const u64 expect = prev >= 0 ? prevExit : 0;
+                if (g[j].entry != expect) atomicOr(&bad, 1u);
+                frameBase[i] = fb; dstBase[i] = db; blockBase[i] = (u32)kk;
+                fb += g[j].count; db += g[j].dstBytes; kk += g[j].blocks; prev = (s32)i; prevExit = g[j].exit;
+            }
         }
-        carryCnt += call; carryDst += ball; carryBlk += kall; carryLast = lall > carryLast ? lall : carryLast;
-        __syncthreads();
+        carryCnt += call; carryDst += ball; carryBlk += kall; if (lall > carryLast) { carryLast = lall; carryExit = eall; }
+#pragma unroll
+        for (u32 j = 0; j < kLinkItems; ++j) g[j] = nx[j];
     }
+    __syncthreads();
     if (tid == 0) {
         u32 usable = !bad;
-        if (carryLast < 0) usable = 0; else if (segs[carryLast].exit != srcSize) usable = 0;
+        if (carryLast < 0 || carryExit != srcSize) usable = 0;
         if (carryCnt > maxFrames || carryBlk > 0xFFFFFFF0ull) usable = 0;
         status[kStFrames] = carryCnt; status[kStErr] = 0; status[kStTotalLo] = (u32)carryDst; status[kStTotalHi] = (u32)(carryDst >> 32);
         status[kStUsable] = usable; status[kStUnsized] = 0; status[kStBlocks] = (u32)carryBlk;
@@ -706,27 +806,48 @@ __global__ __launch_bounds__(64) void block_link_kernel(FrameDesc* __restrict__ 
 // ------------------------------------------------------------------------------------------------
 // seq_scan: where every block's sequence records go (exclusive scan of nbSeq), single workgroup
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(1024) void seq_scan_kernel(BlockDesc* __restrict__ blocks, u32 nBlocks, u32* __restrict__ status)
+// exclusive scan over n items of a single workgroup: load(i) -> the item's value, store(i, sum of the items before it); -> the total
+template <class Load, class Store>
+__device__ __forceinline__ u64 workgroup_scan(u32 n, u64 (*shW)[16], Load load, Store store)
 {
-    __shared__ u64 shW[16];
     const u32 tid = threadIdx.x, lane = lane_id(), wave = wave_id();
     u64 carry = 0;
-    for (u32 base = 0; base < nBlocks; base += 1024) {
-        const u32 i = base + tid;
-        u64 v = 0;
-        if (i < nBlocks) { const BlockDesc& B = blocks[i]; v = (B.type == 2 && !B.err) ? B.nbSeq : 0u; }
-        u64 incl = v;
+    u64 v[kScanItems], nx[kScanItems];
+    auto fetch = [&](u32 base, u64 (&o)[kScanItems]) {
+#pragma unroll
+        for (u32 j = 0; j < kScanItems; ++j) { const u32 i = base + tid * kScanItems + j; o[j] = i < n ? load(i) : 0; }
+    };
+    fetch(0, v);
+    u32 par = 0;
+    for (u32 base = 0; base < n; base += kScanRound, par ^= 1) {
+        if (base + kScanRound < n) fetch(base + kScanRound, nx);
+        u64 mine = 0;
+#pragma unroll
+        for (u32 j = 0; j < kScanItems; ++j) mine += v[j];
+        u64 incl = mine;
 #pragma unroll
         for (int d = 1; d < 64; d <<= 1) { const u64 t = __shfl_up(incl, d); if ((int)lane >= d) incl += t; }
-        if (lane == 63) shW[wave] = incl;
-        __syncthreads();
+        if (lane == 63) shW[par][wave] = incl;
+        lds_barrier();
         u64 before = carry, all = 0;
-        for (u32 w = 0; w < 16; ++w) { if (w < wave) before += shW[w]; all += shW[w]; }
-        if (i < nBlocks) blocks[i].seqBase = before + incl - v;
+        for (u32 w = 0; w < 16; ++w) { if (w < wave) before += shW[par][w]; all += shW[par][w]; }
+        u64 run = before + incl - mine;
+#pragma unroll
+        for (u32 j = 0; j < kScanItems; ++j) { const u32 i = base + tid * kScanItems + j; if (i < n) store(i, run); run += v[j]; }
         carry += all;
-        __syncthreads();
+#pragma unroll
+        for (u32 j = 0; j < kScanItems; ++j) v[j] = nx[j];
     }
-    if (tid == 0) { status[kStSeqLo] = (u32)carry; status[kStSeqHi] = (u32)(carry >> 32); }
+    return carry;
+}
+
+__global__ __launch_bounds__(1024) void seq_scan_kernel(BlockDesc* __restrict__ blocks, u32 nBlocks, u32* __restrict__ status)
+{
+    __shared__ u64 shW[2][16];
+    const u64 total = workgroup_scan(nBlocks, shW,
+        [&](u32 i) -> u64 { const BlockDesc& B = blocks[i]; return (B.type == 2 && !B.err) ? B.nbSeq : 0u; },
+        [&](u32 i, u64 before) { blocks[i].seqBase = before; });
+    if (threadIdx.x == 0) { status[kStSeqLo] = (u32)total; status[kStSeqHi] = (u32)(total >> 32); }
 }
 
 void launch_block_prepass(const u8* src, FrameDesc* frames, BlockDesc* blocks, u32 nFrames, u32 nBlocks, u32 haveDict, u32 earlyLiterals, u32* status, hipStream_t stream)
@@ -801,26 +922,13 @@ __global__ __launch_bounds__(64) void block_offsets_kernel(FrameDesc* __restrict
 // status, and a total beyond the destination's capacity stops everything behind this kernel
 __global__ __launch_bounds__(1024) void frame_rescan_kernel(FrameDesc* __restrict__ frames, u32 nFrames, u64 dstCapacity, u32* __restrict__ status)
 {
-    __shared__ u64 shW[16];
-    const u32 tid = threadIdx.x, lane = lane_id(), wave = wave_id();
-    u64 carry = 0;
-    for (u32 base = 0; base < nFrames; base += 1024) {
-        const u32 i = base + tid;
-        const u64 v = i < nFrames ? frames[i].dstSize : 0;
-        u64 incl = v;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) { const u64 t = __shfl_up(incl, d); if ((int)lane >= d) incl += t; }
-        if (lane == 63) shW[wave] = incl;
-        __syncthreads();
-        u64 before = carry, all = 0;
-        for (u32 w = 0; w < 16; ++w) { if (w < wave) before += shW[w]; all += shW[w]; }
-        if (i < nFrames) frames[i].dstOff = before + incl - v;
-        carry += all;
-        __syncthreads();
-    }
-    if (tid == 0) {
-        status[kStActualLo] = (u32)carry; status[kStActualHi] = (u32)(carry >> 32);
-        if (carry > dstCapacity) status[kStErr] = kErrDstSizeTooSmall;
+    __shared__ u64 shW[2][16];
+    const u64 total = workgroup_scan(nFrames, shW,
+        [&](u32 i) -> u64 { return frames[i].dstSize; },
+        [&](u32 i, u64 before) { frames[i].dstOff = before; });
+    if (threadIdx.x == 0) {
+        status[kStActualLo] = (u32)total; status[kStActualHi] = (u32)(total >> 32);
+        if (total > dstCapacity) status[kStErr] = kErrDstSizeTooSmall;
     }
 }
 
