@@ -303,6 +303,32 @@ size_t ZSTDMI_decompressRange(ZSTD_DCtx* dctx, void* dst, size_t dstCapacity, co
 int ZSTDMI_debugLastRangeFrames(const ZSTD_DCtx* dctx);
 long long ZSTDMI_debugLastRangeStaged(const ZSTD_DCtx* dctx);
 
+/* Gather reads: n ranges of ONE seekable stream in one call.  src (host or device memory, as for ZSTDMI_decompressRange) ends in a
+ * seek table; the five arrays are host memory; dsts[i] are device pointers anywhere, at any alignment and in any order, that overlap
+ * neither each other nor the source (the batch's convention).  Returns 0 when the call ran (n == 0: 0, without touching the device);
+ * GENERIC for a NULL context or a NULL array with n > 0, parameter_unsupported on a context with several device workers or a pending
+ * ZSTD_DCtx_refPrefix, memory_allocation for n above 0xFFFFFFF0 or when the arena cannot be had, and a table error (the prefix_unknown
+ * and corruption_detected cases of ZSTDMI_decompressRange, same codes) before anything is decoded.  The context's dictionary applies.
+ * dstSizes[i] is exactly what ZSTDMI_decompressRange(dctx, dsts[i], dstCapacities[i], src, srcSize, offsets[i], lengths[i]) returns
+ * on the same context, and the bytes at dsts[i] are the same: min(length, max(total - offset, 0)) bytes; 0 for a range past the end
+ * or of length 0 (dsts[i] may then be NULL); dstSize_tooSmall, nothing written, for more than dstCapacities[i].  Ranges may overlap,
+ * repeat and come in any order: every table entry with content that some served range meets is decoded ONCE, into an arena the context
+ * owns, and a gather kernel hands each range its bytes.  A frame that fails — a decode error, or a content size other than its
+ * entry's: corruption_detected — fails every range that meets it, with the code the single call gives; a failed range writes nothing
+ * and changes nothing of the ranges that do not meet the frame.  Nothing is ever written outside [dsts[i], dsts[i] + dstSizes[i]).
+ * From a host source only the table and the touched frames' compressed bytes are copied to the device, packed into one buffer.  The
+ * number of host synchronisations does not depend on n.  A range of more than 4 MiB is not gathered: it is handed to the single-range
+ * path after the gathered pass, in range order (its frames are decoded straight to their place).  A frame of more than 4 MiB
+ * compressed, or without a content size, is decoded by the single-call path into the arena and does not make its ranges go alone. */
+size_t ZSTDMI_decompressRanges(ZSTD_DCtx* dctx, const void* src, size_t srcSize,
+                               const unsigned long long* offsets, const size_t* lengths, size_t n,
+                               void* const* dsts, const size_t* dstCapacities, size_t* dstSizes);
+/* diagnostics of the last ZSTDMI_decompressRanges: DISTINCT table entries with content the gathered pass decoded; ranges handed to the
+ * single-range path; bytes copied host -> device (0 for a device source); -1 without a context */
+int ZSTDMI_debugLastRangesFrames(const ZSTD_DCtx* dctx);
+int ZSTDMI_debugLastRangesAlone(const ZSTD_DCtx* dctx);
+long long ZSTDMI_debugLastRangesStaged(const ZSTD_DCtx* dctx);
+
 /* per-stage HIP-event timing of the LAST call (enable first).  Fills up to `cap` entries, returns the count. */
 size_t ZSTDMI_CCtx_setProfiling(ZSTD_CCtx* cctx, int enable);
 size_t ZSTDMI_DCtx_setProfiling(ZSTD_DCtx* dctx, int enable);

@@ -102,6 +102,11 @@ SIGNATURES = {
     "ZSTDMI_decompressRange": (c_size_t, [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_ull, c_size_t]),
     "ZSTDMI_debugLastRangeFrames": (c_int, [c_void_p]),
     "ZSTDMI_debugLastRangeStaged": (ctypes.c_longlong, [c_void_p]),
+    "ZSTDMI_decompressRanges": (c_size_t, [c_void_p, c_void_p, c_size_t, ctypes.POINTER(c_ull), ctypes.POINTER(c_size_t), c_size_t,
+                                           ctypes.POINTER(c_void_p), ctypes.POINTER(c_size_t), ctypes.POINTER(c_size_t)]),
+    "ZSTDMI_debugLastRangesFrames": (c_int, [c_void_p]),
+    "ZSTDMI_debugLastRangesAlone": (c_int, [c_void_p]),
+    "ZSTDMI_debugLastRangesStaged": (ctypes.c_longlong, [c_void_p]),
     "ZSTDMI_CCtx_setProfiling": (c_size_t, [c_void_p, c_int]),
     "ZSTDMI_DCtx_setProfiling": (c_size_t, [c_void_p, c_int]),
     "ZSTDMI_CCtx_getStageTimes": (c_int, [c_void_p, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_char_p), c_int]),

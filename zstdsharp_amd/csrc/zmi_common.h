@@ -169,6 +169,35 @@ enum : u32 { kSeekErr = 0, kSeekTotal = 1,      // the table's error (0 = none);
 // one copy of range_clip_kernel: bytes [from, from + len) of the edge buffer to dst + to
 struct ClipJob { u64 from, to, len; };
 
+// Many ranges of a seekable stream in one call (ZSTDMI_decompressRanges, decode_ranges.hip).  The host says RangeIn of range i;
+// ranges_select_kernel files RangeRec: what the range returns (or its error, in the size_t convention) and, for a served range, the
+// first and the last table entry with content that it meets.  Every touched entry is decoded once into its slot of an arena.
+struct RangeIn { u64 offset, length, dstCap, dst; };            // dst: the device address (0 = NULL)
+enum : u32 { kRangeDone = 0,        // `result` is final: an empty range, dstSize_tooSmall, dstBuffer_null
+             kRangeServed = 1,      // the gathered pass decodes its entries; ranges_gather_kernel copies its bytes
+             kRangeAlone = 2 };     // more than kRangesAloneAbove bytes: the single-range path takes it afterwards
+struct RangeRec { u64 result; u32 first, last, state, pad; };
+constexpr u64 kRangesAloneAbove = (u64)4 << 20;
+constexpr u32 kRangesTile = 1024;           // table entries per workgroup of the grid-wide scans
+constexpr u32 kGatherSlice = 64u << 10;     // output bytes per workgroup of ranges_gather_kernel
+constexpr u32 kNoEntry = 0xFFFFFFFFu;       // decode index of a table entry that is not touched
+enum : u32 { kRgErr = 0, kRgTotal = 1,      // the table's error (0 = none); content bytes of the whole stream
+             kRgTouched = 2,                // distinct entries with content that the served ranges meet
+             kRgArena = 3, kRgCompact = 4,  // their content bytes (the arena), their compressed bytes (a host source's staging buffer)
+             kRgRuns = 5,                   // maximal runs of consecutive touched entries
+             kRgAloneEntries = 6,           // touched entries the batch walk left to the single-call path (ranges_alone_kernel)
+             kRgWords = 8 };
+// the pass's device workspace for a table of N entries, T = N / kRangesTile + 1 tiles (ranges_ws_bytes / ranges_ws)
+struct RangesWs {
+    u64* cOff; u64* dOff;       // N + 1 each: exclusive prefix of the compressed sizes, of the content sizes
+    u64* slot;                  // N: the entry's offset in the arena
+    u64* runs;                  // N + 2 words: the runs of touched entries as compressed [lo, hi) pairs (at most (N + 1) / 2 runs)
+    u64* tileIdx; u64* tileCover; u64* tilePlan;        // (T + 1) x 2, 1, 4: tile sums, then tile carries; the totals in row T
+    u64* sum;                   // kRgWords
+    u32* diff;                  // N + 1: +1 at a served range's first entry, -1 behind its last (mod 2^32); its prefix sum = ranges over an entry
+    u32* decIdx;                // N: the entry's index in the decode table, kNoEntry = not touched
+};
+
 // status words shared by the decoder's kernels and the host
 enum : u32 { kStFrames = 0, kStErr = 1, kStTotalLo = 2, kStTotalHi = 3, kStUsable = 4, kStUnsized = 5, kStBlocks = 6, kStSeqLo = 8, kStSeqHi = 9,
              kStErrKeyLo = 10, kStErrKeyHi = 11, kStActualLo = 12, kStActualHi = 13,

@@ -15,6 +15,7 @@
 #include <functional>
 #include "zmi_common.h"
 #include "zmi_cparams.h"
+#include "zmi_pack_runs.h"
 #include "../../include/zstd_mi355x.h"
 
 namespace zmi {
@@ -59,6 +60,15 @@ void launch_seek_emit(const u8* tab, u32 stride, u32 first, u32 nSel, u64 dFirst
                       BatchEntryIn* out, hipStream_t stream);
 void launch_range_check(const BatchEntryIn* in, const BatchEntryOut* out, u32 nEntries, u64* sum, hipStream_t stream);
 void launch_range_clip(u8* dst, const u8* edge, ClipJob j0, ClipJob j1, hipStream_t stream);
+// many ranges of a seekable stream (decode_ranges.hip)
+size_t ranges_ws_bytes(u32 n);
+RangesWs ranges_ws(u8* p, u32 n);
+void launch_seek_index(const u8* tab, u64 tableBytes, u32 n, u32 stride, u64 srcSize, const RangesWs& ws, hipStream_t stream);
+void launch_ranges_select(const RangeIn* in, RangeRec* recs, u32 nRanges, u32 n, const RangesWs& ws, hipStream_t stream);
+void launch_ranges_plan(const u8* tab, u32 n, u32 stride, u32 srcDev, const RangesWs& ws, BatchEntryIn* out, hipStream_t stream);
+void launch_ranges_alone(const BatchEntryOut* out, u32 nEntries, const RangesWs& ws, hipStream_t stream);
+void launch_ranges_gather(const RangeIn* in, const RangeRec* recs, u64* res, u32 nRanges, u32 nSlices, const RangesWs& ws, const BatchEntryOut* out,
+                          const u8* arena, hipStream_t stream);
 void launch_seq_stats(const Seq* seqs, const u8* lits, const ChunkMeta* meta, u32 nChunks, const u8* src, u32 chunkBytes, u32* stats, hipStream_t stream);
 void launch_dict_parse(const u8* dict, u32 dictSize, DictInfo* out, hipStream_t stream);
 void launch_block_prepass(const u8* src, FrameDesc* frames, BlockDesc* blocks, u32 nFrames, u32 nBlocks, u32 haveDict, u32 earlyLiterals, u32* status, hipStream_t stream);
@@ -222,6 +232,10 @@ struct ZSTD_DCtx_s {
     int lastBatchAlone = 0;     // entries of the last ZSTDMI_decompressBatch that were decoded by the single-call path (debug hook)
     DevBuf seekTab, seekSum, edge;          // ZSTDMI_decompressRange: a host source's seek table, the summary words, the frames the range cuts
     int lastRangeFrames = 0; long long lastRangeStaged = 0;     // table entries the last range call decoded, bytes it copied host -> device (debug hooks)
+    // ZSTDMI_decompressRanges: the pass's workspace (RangesWs), the ranges as the host states them / as ranges_select files them /
+    // their results, and the arena that holds every touched frame's content once
+    DevBuf rangesWs, rangesIn, rangesRec, rangesRes, arena;
+    int lastRangesFrames = 0, lastRangesAlone = 0; long long lastRangesStaged = 0;      // (debug hooks)
     int originMode = 0;         // ZSTDMI_DCtx_setLongFrames: 0 = by cost (see decompress_device), 1 = never, 2 = every frame of 1 MiB or more
     StageTimer timer;
     // streaming adapter (ZSTD_decompressStream): whole frames are collected on the host, decoded in batches
@@ -1076,7 +1090,7 @@ size_t ZSTD_freeDCtx(ZSTD_DCtx* d)
     if (d->deviceOk) {
         (void)hipSetDevice(d->device);
         if (d->ownStream) (void)hipStreamSynchronize(d->ownStream);
-        d->frames.release(); d->blocks.release(); d->recs.release(); d->status.release(); d->scratch.release(); d->walkWs.release(); d->slowFlags.release(); d->stageSrc.release(); d->stageDst.release(); d->dict.release(); d->dictInfoDev.release(); d->origin.release(); d->originList.release(); d->batchIn.release(); d->batchOut.release(); d->blockKeys.release(); d->seekTab.release(); d->seekSum.release(); d->edge.release(); d->pfxStage.release();
+        d->frames.release(); d->blocks.release(); d->recs.release(); d->status.release(); d->scratch.release(); d->walkWs.release(); d->slowFlags.release(); d->stageSrc.release(); d->stageDst.release(); d->dict.release(); d->dictInfoDev.release(); d->origin.release(); d->originList.release(); d->batchIn.release(); d->batchOut.release(); d->blockKeys.release(); d->seekTab.release(); d->seekSum.release(); d->edge.release(); d->pfxStage.release(); d->rangesWs.release(); d->rangesIn.release(); d->rangesRec.release(); d->rangesRes.release(); d->arena.release();
         d->timer.destroy();
         if (d->aux) { (void)hipStreamSynchronize(d->aux); (void)hipStreamDestroy(d->aux); }
         if (d->auxDone) (void)hipEventDestroy(d->auxDone);
@@ -1526,15 +1540,13 @@ static size_t decompress_batch_impl(ZSTD_DCtx* d, const void* const* srcs, const
 // walk leaves to the single-call path (a frame without a content size, more than kBatchAloneAbove compressed bytes) is decoded by
 // decompress_device into the same place.  range_check_kernel holds every entry to the content size its table entry names.  A host
 // source is staged in two pieces only: the table, and the compressed bytes of the selected entries.
-static size_t decompress_range_impl(ZSTD_DCtx* d, void* dst, size_t dstCapacity, const void* src, size_t srcSize, unsigned long long offset, size_t length)
+// the 9-byte footer of the stream's seek table, read on the host (a device source: one small copy back) -> the entry count, the
+// entries' stride and the table's length, or the table's error
+static size_t read_seek_footer(ZSTD_DCtx* d, const void* src, size_t srcSize, bool srcDev, u32& N, u32& stride, u64& tableBytes)
 {
-    size_t e = dctx_bind(d); if (isErr(e)) return e;
-    if (d->workers.size() > 1 || d->pfx) return ZERR(kErrParameterUnsupported);
-    d->lastRangeFrames = 0; d->lastRangeStaged = 0;
     if (srcSize && !src) return ZERR(kErrSrcSizeWrong);
     if (srcSize < 17) return ZERR(kErrPrefixUnknown);
     hipStream_t s = d->stream;
-    const bool srcDev = is_device_ptr(src), dstDev = dst ? is_device_ptr(dst) : false;
     auto rd32 = [](const u8* p) { return (u32)p[0] | ((u32)p[1] << 8) | ((u32)p[2] << 16) | ((u32)p[3] << 24); };
     u8 foot[9];
     if (srcDev) {
@@ -1543,11 +1555,23 @@ static size_t decompress_range_impl(ZSTD_DCtx* d, void* dst, size_t dstCapacity,
     } else memcpy(foot, (const u8*)src + srcSize - 9, 9);
     if (rd32(foot + 5) != 0x8F92EAB1u) return ZERR(kErrPrefixUnknown);
     if (foot[4] & 0x7C) return ZERR(kErrCorruption);                    // reserved descriptor bits
-    const u32 N = rd32(foot);
+    N = rd32(foot);
     if (N > (1u << 27)) return ZERR(kErrCorruption);
-    const u32 stride = (foot[4] & 0x80) ? 12u : 8u;                     // (checksums, where the table has them, are skipped)
-    const u64 tableBytes = 17 + (u64)N * stride;
+    stride = (foot[4] & 0x80) ? 12u : 8u;                               // (checksums, where the table has them, are skipped)
+    tableBytes = 17 + (u64)N * stride;
     if (tableBytes > srcSize) return ZERR(kErrCorruption);
+    return 0;
+}
+
+static size_t decompress_range_impl(ZSTD_DCtx* d, void* dst, size_t dstCapacity, const void* src, size_t srcSize, unsigned long long offset, size_t length)
+{
+    size_t e = dctx_bind(d); if (isErr(e)) return e;
+    if (d->workers.size() > 1 || d->pfx) return ZERR(kErrParameterUnsupported);
+    d->lastRangeFrames = 0; d->lastRangeStaged = 0;
+    hipStream_t s = d->stream;
+    const bool srcDev = is_device_ptr(src), dstDev = dst ? is_device_ptr(dst) : false;
+    u32 N, stride; u64 tableBytes;
+    e = read_seek_footer(d, src, srcSize, srcDev, N, stride, tableBytes); if (isErr(e)) return e;
     e = dctx_sync_dictionary(d); if (isErr(e)) return e;
     const DecodeDict dd = decode_dict(d);
     if (!d->seekSum.ensure(kSeekWords * sizeof(u64))) return ZERR(kErrMemoryAllocation);
@@ -1623,6 +1647,123 @@ static size_t decompress_range_impl(ZSTD_DCtx* d, void* dst, size_t dstCapacity,
     d->timer.finish();
     d->lastRangeFrames = (int)nMeet;
     return (size_t)returned;
+}
+
+
+// ---- many ranges of a seekable stream in one call (ZSTDMI_decompressRanges) ----
+// While one of these lives, the context's stage timer is off and keeps what it has recorded: the single-call paths that the pass hands
+// a frame or a range to begin the timer anew, and ZSTDMI_DCtx_getStageTimes is to show the pass.
+struct TimerPause {
+    StageTimer& t; const bool was; const int n;
+    explicit TimerPause(StageTimer& timer) : t(timer), was(timer.enabled), n(timer.n) { t.enabled = false; }
+    ~TimerPause() { t.enabled = was; t.n = n; }
+};
+// seek_index turns the table into prefix arrays once; ranges_select answers every range that needs no decoding and marks the entries
+// the others meet; ranges_plan makes ONE decode table of the touched entries — each decoded once, into its slot of the context's
+// arena, whatever number of ranges meets it — and decode_entries runs over it as over any batch.  An entry the walk leaves to the
+// single-call path is decoded by decompress_device into its slot; ranges_gather then checks each range's entries and copies its
+// bytes.  From a host source the table and the touched entries' compressed bytes travel, packed into one staging buffer.  A range of
+// more than kRangesAloneAbove bytes is handed to decompress_range_impl afterwards: it wants its frames decoded in place.
+static size_t decompress_ranges_impl(ZSTD_DCtx* d, const void* src, size_t srcSize, const unsigned long long* offsets, const size_t* lengths, size_t n,
+                                     void* const* dsts, const size_t* dstCapacities, size_t* dstSizes)
+{
+    if (!d) return ZERR(kErrGeneric);
+    if (n == 0) { d->lastRangesFrames = 0; d->lastRangesAlone = 0; d->lastRangesStaged = 0; return 0; }
+    if (!offsets || !lengths || !dsts || !dstCapacities || !dstSizes) return ZERR(kErrGeneric);
+    if (n > 0xFFFFFFF0ull) return ZERR(kErrMemoryAllocation);
+    size_t e = dctx_bind(d); if (isErr(e)) return e;
+    if (d->workers.size() > 1 || d->pfx) return ZERR(kErrParameterUnsupported);      // (a pending ZSTD_DCtx_refPrefix serves one single call)
+    d->lastRangesFrames = 0; d->lastRangesAlone = 0; d->lastRangesStaged = 0;
+    hipStream_t s = d->stream;
+    const bool srcDev = is_device_ptr(src);
+    u32 N, stride; u64 tableBytes;
+    e = read_seek_footer(d, src, srcSize, srcDev, N, stride, tableBytes); if (isErr(e)) return e;
+    e = dctx_sync_dictionary(d); if (isErr(e)) return e;
+    const DecodeDict dd = decode_dict(d);
+    const u32 nR = (u32)n;
+    if (!d->rangesWs.ensure(ranges_ws_bytes(N)) || !d->batchIn.ensure((size_t)N * sizeof(BatchEntryIn) + 64) ||
+        !d->rangesIn.ensure(n * sizeof(RangeIn)) || !d->rangesRec.ensure(n * sizeof(RangeRec)) || !d->rangesRes.ensure(n * sizeof(u64))) return ZERR(kErrMemoryAllocation);
+    const RangesWs ws = ranges_ws((u8*)d->rangesWs.p, N);
+    std::vector<RangeIn> hIn(n);
+    for (size_t i = 0; i < n; i++) { hIn[i].offset = offsets[i]; hIn[i].length = lengths[i]; hIn[i].dstCap = dstCapacities[i]; hIn[i].dst = (u64)(uintptr_t)dsts[i]; }
+    const u8* tab = (const u8*)src + (srcSize - tableBytes);
+    if (!srcDev) {
+        if (!d->seekTab.ensure((size_t)tableBytes + 64)) return ZERR(kErrMemoryAllocation);
+        if (hipMemcpyAsync(d->seekTab.p, tab, (size_t)tableBytes, hipMemcpyHostToDevice, s) != hipSuccess) return ZERR(kErrGeneric);
+        tab = (const u8*)d->seekTab.p; d->lastRangesStaged += (long long)tableBytes;
+    }
+    if (hipMemcpyAsync(d->rangesIn.p, hIn.data(), n * sizeof(RangeIn), hipMemcpyHostToDevice, s) != hipSuccess) return ZERR(kErrGeneric);
+    const RangeIn* dRanges = (const RangeIn*)d->rangesIn.p; RangeRec* dRecs = (RangeRec*)d->rangesRec.p;
+    d->timer.begin(s);
+    launch_seek_index(tab, tableBytes, N, stride, srcSize, ws, s);                                     d->timer.mark("seek_index", s);
+    launch_ranges_select(dRanges, dRecs, nR, N, ws, s);                                                d->timer.mark("ranges_select", s);
+    launch_ranges_plan(tab, N, stride, srcDev ? 1u : 0u, ws, (BatchEntryIn*)d->batchIn.p, s);          d->timer.mark("ranges_plan", s);
+    u64 sm[kRgWords] = {};
+    if (hipMemcpyAsync(sm, ws.sum, sizeof sm, hipMemcpyDeviceToHost, s) != hipSuccess) return ZERR(kErrGeneric);
+    if (hipStreamSynchronize(s) != hipSuccess) { (void)hipGetLastError(); return ZERR(kErrGeneric); }
+    if (sm[kRgErr]) { d->timer.finish(); return ZERR((u32)sm[kRgErr]); }
+    const u64 total = sm[kRgTotal], arenaBytes = sm[kRgArena], packedBytes = sm[kRgCompact], nRuns = sm[kRgRuns];
+    const u32 nTouched = (u32)sm[kRgTouched];
+    std::vector<u8> packed;     // (these four are sources of asynchronous copies: they live until the last synchronisation below)
+    std::vector<u64> runs;
+    std::vector<BatchEntryIn> eIn; std::vector<BatchEntryOut> eOut;
+    if (nTouched) {
+        if (!d->arena.ensure((size_t)arenaBytes + 64) || !d->batchOut.ensure((size_t)nTouched * sizeof(BatchEntryOut))) return ZERR(kErrMemoryAllocation);
+        const u8* srcBase = (const u8*)src;
+        if (!srcDev) {          // only the touched frames travel, in one copy
+            runs.resize(2 * (size_t)nRuns); packed.resize((size_t)packedBytes);
+            if (hipMemcpyAsync(runs.data(), ws.runs, runs.size() * sizeof(u64), hipMemcpyDeviceToHost, s) != hipSuccess) return ZERR(kErrGeneric);
+            if (hipStreamSynchronize(s) != hipSuccess) { (void)hipGetLastError(); return ZERR(kErrGeneric); }
+            if (pack_runs(runs.data(), (size_t)nRuns, (const u8*)src, srcSize, packed.data(), packed.size()) != packed.size()) return ZERR(kErrGeneric);
+            if (!d->stageSrc.ensure(packed.size() + 64)) return ZERR(kErrMemoryAllocation);
+            if (hipMemcpyAsync(d->stageSrc.p, packed.data(), packed.size(), hipMemcpyHostToDevice, s) != hipSuccess) return ZERR(kErrGeneric);
+            srcBase = (const u8*)d->stageSrc.p; d->lastRangesStaged += (long long)packed.size();
+        }
+        u64 someAlone = 0;
+        e = decode_entries(d, dd, srcBase, (u8*)d->arena.p, (size_t)arenaBytes, nTouched, [&]() -> bool {
+            launch_ranges_alone((const BatchEntryOut*)d->batchOut.p, nTouched, ws, s);
+            return hipMemcpyAsync(&someAlone, ws.sum + kRgAloneEntries, sizeof(u64), hipMemcpyDeviceToHost, s) == hipSuccess;
+        });
+        if (isErr(e)) return e;
+        if (someAlone) {        // (rare: the entries come to the host only then)
+            eIn.resize(nTouched); eOut.resize(nTouched);
+            if (hipMemcpyAsync(eIn.data(), d->batchIn.p, (size_t)nTouched * sizeof(BatchEntryIn), hipMemcpyDeviceToHost, s) != hipSuccess ||
+                hipMemcpyAsync(eOut.data(), d->batchOut.p, (size_t)nTouched * sizeof(BatchEntryOut), hipMemcpyDeviceToHost, s) != hipSuccess) return ZERR(kErrGeneric);
+            if (hipStreamSynchronize(s) != hipSuccess) { (void)hipGetLastError(); return ZERR(kErrGeneric); }
+            const TimerPause pause(d->timer);       // (decompress_device times itself: the pass keeps its own stages)
+            for (u32 i = 0; i < nTouched; ++i) {
+                if (eOut[i].state != kBatchAlone) continue;
+                eOut[i].result = (u64)decompress_device(d, (u8*)d->arena.p + eIn[i].dstOff, (size_t)eIn[i].dstCap, srcBase + eIn[i].srcOff, (size_t)eIn[i].srcSize);
+                if (hipMemcpyAsync((BatchEntryOut*)d->batchOut.p + i, &eOut[i], sizeof(BatchEntryOut), hipMemcpyHostToDevice, s) != hipSuccess) return ZERR(kErrGeneric);
+            }
+        }
+    }
+    std::vector<u64> hRes(n);
+    // what range i returns when nothing fails (ranges_select's rule, on the host: it has the total now)
+    auto returned = [&](size_t i) -> u64 { return offsets[i] < total ? ((u64)lengths[i] < total - offsets[i] ? (u64)lengths[i] : total - offsets[i]) : 0; };
+    u64 longest = 0;            // of the ranges the gather serves: the number of its slices
+    for (size_t i = 0; i < n; i++) {
+        const u64 ret = returned(i);
+        if (ret <= dstCapacities[i] && ret <= kRangesAloneAbove && dsts[i] && ret > longest) longest = ret;
+    }
+    launch_ranges_gather(dRanges, dRecs, (u64*)d->rangesRes.p, nR, (u32)((longest + kGatherSlice - 1) / kGatherSlice), ws, (const BatchEntryOut*)d->batchOut.p,
+                         (const u8*)d->arena.p, s);
+    d->timer.mark("ranges_gather", s);
+    if (hipMemcpyAsync(hRes.data(), d->rangesRes.p, n * sizeof(u64), hipMemcpyDeviceToHost, s) != hipSuccess) return ZERR(kErrGeneric);
+    if (hipStreamSynchronize(s) != hipSuccess) { (void)hipGetLastError(); return ZERR(kErrGeneric); }
+    d->timer.finish();
+    d->lastRangesFrames = (int)nTouched;
+    // the ranges that go alone, in range order
+    const long long staged = d->lastRangesStaged; long long stagedAlone = 0; int alone = 0;
+    const TimerPause pause(d->timer);               // (the stage times stay the gathered pass's)
+    for (size_t i = 0; i < n; i++) {
+        const u64 ret = returned(i);
+        if (ret > dstCapacities[i] || !dsts[i] || ret <= kRangesAloneAbove) { dstSizes[i] = (size_t)hRes[i]; continue; }
+        dstSizes[i] = decompress_range_impl(d, dsts[i], dstCapacities[i], src, srcSize, offsets[i], lengths[i]);
+        stagedAlone += d->lastRangeStaged; alone++;
+    }
+    d->lastRangesAlone = alone; d->lastRangesStaged = staged + stagedAlone;
+    return 0;
 }
 
 static size_t decompress_multi(ZSTD_DCtx* d, void* dst, size_t dstCapacity, const void* src, size_t srcSize);
@@ -2168,6 +2309,14 @@ size_t ZSTDMI_decompressRange(ZSTD_DCtx* d, void* dst, size_t dstCapacity, const
 }
 int ZSTDMI_debugLastRangeFrames(const ZSTD_DCtx* d) { return d ? d->lastRangeFrames : -1; }
 long long ZSTDMI_debugLastRangeStaged(const ZSTD_DCtx* d) { return d ? d->lastRangeStaged : -1; }
+size_t ZSTDMI_decompressRanges(ZSTD_DCtx* d, const void* src, size_t srcSize, const unsigned long long* offsets, const size_t* lengths, size_t n,
+                               void* const* dsts, const size_t* dstCapacities, size_t* dstSizes)
+{
+    return guarded([&] { return decompress_ranges_impl(d, src, srcSize, offsets, lengths, n, dsts, dstCapacities, dstSizes); });
+}
+int ZSTDMI_debugLastRangesFrames(const ZSTD_DCtx* d) { return d ? d->lastRangesFrames : -1; }
+int ZSTDMI_debugLastRangesAlone(const ZSTD_DCtx* d) { return d ? d->lastRangesAlone : -1; }
+long long ZSTDMI_debugLastRangesStaged(const ZSTD_DCtx* d) { return d ? d->lastRangesStaged : -1; }
 size_t ZSTDMI_decompressDevice(ZSTD_DCtx* d, void* d_dst, size_t dstCapacity, const void* d_src, size_t srcSize) { return guarded([&] { return ZSTDMI_decompressDevice_impl(d, d_dst, dstCapacity, d_src, srcSize); }); }
 size_t ZSTD_compressStream2(ZSTD_CCtx* c, ZSTD_outBuffer* output, ZSTD_inBuffer* input, int endOp) { return guarded([&] { return ZSTD_compressStream2_impl(c, output, input, endOp); }); }
 size_t ZSTD_decompressStream(ZSTD_DCtx* d, ZSTD_outBuffer* output, ZSTD_inBuffer* input) { return guarded([&] { return ZSTD_decompressStream_impl(d, output, input); }); }

@@ -3,7 +3,7 @@ import ctypes
 
 from . import _ffi
 from .compressor import _PrefixHolder, _as_buffer, _as_prefix
-from .errors import DST_SIZE_TOO_SMALL, ZstdException, ZSTD_ErrorCode, ensure_content_size_ok, ensure_zstd_success
+from .errors import DST_SIZE_TOO_SMALL, ZstdException, ZSTD_ErrorCode, ensure_content_size_ok, ensure_zstd_success, get_error_code, is_error
 
 
 class Decompressor(_PrefixHolder):
@@ -104,6 +104,61 @@ class Decompressor(_PrefixHolder):
         out = ctypes.create_string_buffer(max(length, 1))
         n = ensure_zstd_success(lib, lib.ZSTDMI_decompressRange(self.dctx, out, length, saddr, sn, offset, length))
         return out.raw[:n]
+
+    def unwrap_ranges(self, src, ranges):
+        """[content[o : o + l] for (o, l) in ranges] of a seekable stream in ONE call (ZSTDMI_decompressRanges): every frame that some
+        range meets is decoded once, however many ranges meet it.  src: bytes-like -> a list of bytes; a contiguous CUDA uint8 tensor
+        -> a list of CUDA uint8 tensors (slices of one buffer).  Ranges may overlap, repeat and come in any order; one that runs past
+        the end is clipped.  A range that fails raises ZstdException naming its index."""
+        self._ensure_not_disposed()
+        import torch
+        from .seekable import read_seek_table
+        ranges = [(int(o), int(l)) for o, l in ranges]
+        if any(o < 0 or l < 0 for o, l in ranges):
+            raise ValueError("offset and length must not be negative")
+        lib, n = self._lib, len(ranges)
+        on_device = hasattr(src, "data_ptr")
+        if on_device:
+            if not (src.is_cuda and src.dtype == torch.uint8 and src.is_contiguous()):
+                raise TypeError("expected a contiguous CUDA uint8 tensor")
+            size, device = src.numel(), src.device
+            # only the stream's tail comes back: the 9-byte footer says how long the table is
+            foot = bytes(src[max(size - 9, 0):].cpu().numpy())
+            tail = foot
+            if size >= 17 and foot[5:] == bytes([0xB1, 0xEA, 0x92, 0x8F]):
+                count, stride = int.from_bytes(foot[:4], "little"), 12 if foot[4] & 0x80 else 8
+                if count <= (1 << 27) and 17 + count * stride <= size:
+                    tail = bytes(src[size - (17 + count * stride):].cpu().numpy())
+            entries, _ = read_seek_table(tail, front=size - len(tail))
+            saddr, sn, skeep = (src.data_ptr() if size else None), size, src
+        else:
+            saddr, sn, skeep = _as_buffer(src)
+            entries, _ = read_seek_table(src)
+            device = torch.device("cuda", torch.cuda.current_device())
+        if n == 0:
+            return []
+        total = sum(d for _, d in entries)
+        want = [min(l, max(total - o, 0)) for o, l in ranges]
+        starts, at = [], 0
+        for w in want:
+            starts.append(at)
+            at += w
+        out = torch.empty(max(at, 1), dtype=torch.uint8, device=device)
+        base = out.data_ptr()
+        offsets = (ctypes.c_ulonglong * n)(*[o for o, _ in ranges])
+        lengths = (ctypes.c_size_t * n)(*[l for _, l in ranges])
+        dsts = (ctypes.c_void_p * n)(*[(base + s) if w else None for s, w in zip(starts, want)])
+        caps = (ctypes.c_size_t * n)(*want)
+        got = (ctypes.c_size_t * n)()
+        torch.cuda.synchronize(device)          # the library runs on a stream of its own
+        ensure_zstd_success(lib, lib.ZSTDMI_decompressRanges(self.dctx, saddr, sn, offsets, lengths, n, dsts, caps, got))
+        for i in range(n):
+            if is_error(got[i]):
+                raise ZstdException(get_error_code(got[i]), f"range {i}: {lib.ZSTD_getErrorName(got[i]).decode()}")
+        if on_device:
+            return [out[s:s + g] for s, g in zip(starts, got)]
+        host = out.cpu().numpy().tobytes()      # one download for all ranges
+        return [host[s:s + g] for s, g in zip(starts, got)]
 
     unwrap, try_unwrap, set_parameter, get_parameter, load_dictionary, get_decompressed_size, ref_prefix = \
         Unwrap, TryUnwrap, SetParameter, GetParameter, LoadDictionary, GetDecompressedSize, RefPrefix

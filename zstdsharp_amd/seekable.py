@@ -16,16 +16,17 @@ def _fail(code, what):
     raise ZstdException(code, f"seek table: {what}")
 
 
-def read_seek_table(blob):
+def read_seek_table(blob, front=0):
     """-> ([(compressed size, content size), ...], the table's byte length): one pair per frame of the stream, in order; the table
     is the last `byte length` bytes of blob.  Checksums, where the table has them, are skipped.  Raises ZstdException with the code
-    ZSTDMI_decompressRange gives for the same table."""
+    ZSTDMI_decompressRange gives for the same table.  front: bytes of the stream in front of blob that the caller did not bring
+    (blob is then the stream's tail and must hold the whole table)."""
     mv = memoryview(blob).cast("B")
-    size = len(mv)
+    size = front + len(mv)
     bad_prefix, corrupt = ZSTD_ErrorCode.ZSTD_error_prefix_unknown, ZSTD_ErrorCode.ZSTD_error_corruption_detected
     if size < 17:
         _fail(bad_prefix, "the stream is shorter than an empty table")
-    count, descriptor, magic = struct.unpack("<IBI", mv[size - 9:])
+    count, descriptor, magic = struct.unpack("<IBI", mv[len(mv) - 9:])
     if magic != SEEKABLE_MAGIC:
         _fail(bad_prefix, "no seekable magic at the end of the stream")
     if descriptor & 0x7C:
@@ -37,10 +38,12 @@ def read_seek_table(blob):
     if table_bytes > size:
         _fail(corrupt, "the table is longer than the stream")
     at = size - table_bytes
-    head_magic, frame_size = struct.unpack("<II", mv[at:at + 8])
+    if at < front:
+        raise ValueError("the tail does not hold the whole table")
+    head_magic, frame_size = struct.unpack("<II", mv[at - front:at - front + 8])
     if head_magic != SKIPPABLE_MAGIC or frame_size != table_bytes - 8:
         _fail(bad_prefix, "no skippable header of the table's size in front of it")
-    entries = [struct.unpack_from("<II", mv, at + 8 + i * stride) for i in range(count)]
+    entries = [struct.unpack_from("<II", mv, at - front + 8 + i * stride) for i in range(count)]
     if sum(c for c, _ in entries) != at:
         _fail(corrupt, "the compressed sizes do not add up to the bytes in front of the table")
     return entries, table_bytes
