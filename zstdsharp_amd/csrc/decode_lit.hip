@@ -11,6 +11,7 @@
 //   selfsync : a workgroup per block, 64 lanes per stream;
 //   slow     : one wave per block, everything the others pass on (12-bit tables).
 #include "zmi_decode.h"
+#include "zmi_host.h"
 
 namespace zmi {
 

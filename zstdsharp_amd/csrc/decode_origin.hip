@@ -21,6 +21,7 @@
 // frames is shorter than the walk of that frame alone (decompress_device); everything else keeps the one-wave walk, which wins
 // whenever a call has thousands of frames.
 #include "zmi_decode.h"
+#include "zmi_host.h"
 
 namespace zmi {
 

@@ -11,6 +11,7 @@
 //   ranges_gather  : per served range: every met entry decoded to the size its table entry names, or nothing is copied; then its
 //                    bytes from the arena slots to its destination, one workgroup per 64 KiB slice of its output.
 #include "zmi_device.h"
+#include "zmi_host.h"
 
 namespace zmi {
 

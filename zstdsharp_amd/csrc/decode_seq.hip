@@ -13,6 +13,7 @@
 //   exec_matches    : one wave per frame, blocks in order (the only ordered stage): the matches (ZSTD_execSequence, :2187-2262),
 //                     64 at a time in dependency rounds; then the frame's checksum (U/ZstdDecompress.cs:1186-1208).
 #include "zmi_decode.h"
+#include "zmi_host.h"
 
 namespace zmi {
 

@@ -19,6 +19,7 @@
 //                     (U/ZstdDecompress.cs:1177-1184).
 //   frame_rescan    : only when some frame carries no content size: output offsets of the frames from their regenerated sizes.
 #include "zmi_decode.h"
+#include "zmi_host.h"
 
 namespace zmi {
 

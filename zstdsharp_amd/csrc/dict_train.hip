@@ -24,6 +24,7 @@
 #include "zmi_common.h"
 #include "zmi_device.h"
 #include "../../include/zstd_mi355x.h"
+#include "zmi_host.h"
 
 namespace zmi {
 
@@ -203,14 +204,9 @@ __global__ __launch_bounds__(kSelThreads) void dt_select_kernel(const u8* __rest
     if (tid == 0) C->tail = tail;
 }
 
-size_t compress_samples(ZSTD_CCtx* c, const u8* src, const u64* offs, const size_t* sizes, size_t n, size_t* outSizes, u32* stats);
-
 } // namespace zmi
 
 using namespace zmi;
-
-#define ZERR(code) ((size_t)0 - (size_t)(code))
-static inline bool isErr(size_t c) { return c > ZERR(kErrMaxCode); }
 
 namespace {
 
@@ -330,8 +326,7 @@ size_t finalize(Device& dev, void* dictBuffer, size_t capacity, const void* cont
     u32* const dSize = (u32*)dCount.p + 377;
     launch_dict_entropy((const u32*)dCount.p, offcodeMax, (u8*)dOut.p, 256 - 8, dSize, dev.s);
     u32 eSize = 0;
-    if (hipMemcpyAsync(&eSize, dSize, 4, hipMemcpyDeviceToHost, dev.s) != hipSuccess) return ZERR(kErrGeneric);
-    if (hipStreamSynchronize(dev.s) != hipSuccess) { (void)hipGetLastError(); return ZERR(kErrGeneric); }
+    if (isErr(dev_read(&eSize, dSize, 4, dev.s))) return ZERR(kErrGeneric);
     if (eSize == 0) return ZERR(kErrGeneric);
     if (eSize == 0xFFFFFFFFu) return ZERR(kErrDstSizeTooSmall);
     if (hipMemcpy(header + hSize, dOut.p, eSize, hipMemcpyDeviceToHost) != hipSuccess) return ZERR(kErrGeneric);
@@ -422,7 +417,7 @@ size_t train_d(Device& dev, u8* dictOut, size_t capacity, const u8* samples, con
     if (hipMemcpyAsync(cands.data(), dCands.p, sizeof(SelCand) * nK, hipMemcpyDeviceToHost, s) != hipSuccess ||
         hipMemcpyAsync(dicts.data(), dDict.p, dicts.size(), hipMemcpyDeviceToHost, s) != hipSuccess)
         return ZERR(kErrGeneric);
-    if (hipStreamSynchronize(s) != hipSuccess) { (void)hipGetLastError(); return ZERR(kErrGeneric); }
+    if (isErr(stream_wait(s))) return ZERR(kErrGeneric);
     const unsigned nbFinalize = (unsigned)((u64)nbTrain * kAccelFinalize[accel] / 100);
     for (u32 i = 0; i < nK; i++) {
         const u8* const cand = dicts.data() + (u64)capacity * i;

@@ -2,6 +2,7 @@
 // stream (the "variable-length output" step of SURVEY.md §7), plus the optional XXH64 content checksum
 // (U/Xxhash.cs:378-600, written by ZSTD_writeEpilogue U/ZstdCompress.cs:5641-5652).
 #include "zmi_device.h"
+#include "zmi_host.h"
 
 namespace zmi {
 

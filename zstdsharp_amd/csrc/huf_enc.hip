@@ -25,6 +25,7 @@
 // (tests/test_gpu_parity.py::test_entropy_stage_is_byte_identical_to_oracle).
 #include "zmi_device.h"
 #include "zmi_fse.h"
+#include "zmi_host.h"
 
 namespace zmi {
 

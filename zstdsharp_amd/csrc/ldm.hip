@@ -22,6 +22,7 @@
 #include <hip/hip_runtime.h>
 #include "zmi_common.h"
 #include "zmi_device.h"
+#include "zmi_host.h"
 
 namespace zmi {
 

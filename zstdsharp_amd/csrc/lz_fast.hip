@@ -30,6 +30,7 @@
 // HBM traffic per chunk: read n, write literals (<= n) + 8 B per sequence.
 #include <type_traits>
 #include "zmi_device.h"
+#include "zmi_host.h"
 
 namespace zmi {
 

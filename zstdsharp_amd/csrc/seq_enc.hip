@@ -13,6 +13,7 @@
 // 16 384 independent chunks per GiB, which is why this kernel keeps LDS small.
 #include "zmi_device.h"
 #include "zmi_fse.h"
+#include "zmi_host.h"
 
 namespace zmi {
 

@@ -1,0 +1,228 @@
+// zmi_host.h — what the host files of libzstd_mi355x.so share (zstd_mi355x.hip, zstd_mi355x_dec.hip, dict_train.hip): the prototypes
+// of every launch function the kernel files define (each of those files includes this header, so a signature or a default argument is
+// stated once and a definition that drifts from it does not compile or link), error codes as return values, device buffers, the
+// stage timer and the small helpers around pointers, devices and worker threads.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <string.h>
+#include <vector>
+#include <thread>
+#include <new>
+#include "zmi_common.h"
+#include "../../include/zstd_mi355x.h"
+
+namespace zmi {
+// kernels (lz_fast.hip, huf_enc.hip, seq_enc.hip, frame.hip, decode.hip)
+void launch_lz(u32 finder, const u8* src, u64 srcSize, u32 nChunks, Seq* seqs, u8* lits, ChunkMeta* meta, const u8* prefix, u32 prefixLen,
+               u32 chunkBytes, u32 fhExtra, u32 minStrideLog, u32 frameBlocks, u16* cand, u16* chain, u32* regionList, u32 hcDepth, hipStream_t stream, StageHook hook, u32* claimCtr,
+               const u32* chunkLens = nullptr);
+void launch_lz_probe(const u8* src, u64 srcSize, u64 front, u64 groupBytes, u32 nGroups, u32 tilesPerGroup, u32* out, hipStream_t stream);
+void launch_huf_build(const u8* lits, ChunkMeta* meta, HufTable* tables, u8* slots, u32 nChunks, u32 rawLiterals, const u8* src, u32 chunkBytes,
+                      hipStream_t stream, StageHook hook);
+void launch_huf_encode(const u8* lits, const ChunkMeta* meta, const HufTable* tables, u8* slots, u8* dst, const u64* offsets, u64 dstCapacity,
+                       u32 nChunks, const u8* src, u32 chunkBytes, hipStream_t stream);
+void launch_seq_encode(Seq* seqs, ChunkMeta* meta, u8* slots, u32 nChunks, u32 strategy, u32 checksumFlag, u32 resolveReps,
+                       u32 dictID, u32 dictIdBytes, const u32* initReps, u32 frameBlocks, u32 chunkBytes, u64 srcSize, hipStream_t stream);
+void launch_scan_sizes(const ChunkMeta* meta, u32 nChunks, u64* offsets, u64* total, hipStream_t stream);
+void launch_gather(const u8* src, u64 srcSize, const u8* slots, const ChunkMeta* meta, const u64* offsets, u8* dst, u64 dstCapacity,
+                   u32 nChunks, u32 chunkBytes, hipStream_t stream);
+void launch_xxh64(const u8* src, u64 srcSize, ChunkMeta* meta, u32 nChunks, u32 chunkBytes, u32 frameBlocks, hipStream_t stream, const u32* chunkLens = nullptr);
+void launch_batch_stage(const u64* from, const u32* len, u8* stage, u32 nChunks, u32 chunkBytes, hipStream_t stream);
+void launch_batch_place(const ChunkMeta* meta, u32 nEntries, const u32* entFirst, const u64* entDst, const u64* entCap, u64 span, u64* offsets, u64* entSize,
+                        hipStream_t stream);
+void launch_seek_entries(const u64* offsets, const u64* total, u32 nChunks, u32 frameBlocks, u32 chunkBytes, u64 passBytes, u32* entries, hipStream_t stream);
+void launch_seek_table(const u32* entries, u32 n, u8* dst, hipStream_t stream);
+// long-distance matching (ldm.hip)
+size_t ldm_small_bytes(u64 n);
+size_t ldm_big_bytes(u64 nSplits);
+void launch_ldm_count(const u8* src, u64 n, u64 frameSpan, const LdmLaunch& p, u8* small, hipStream_t stream, const LdmPrefix& pfx);
+u32* ldm_total_word(u8* small, u64 n);
+void launch_ldm_rest(const u8* src, u64 n, u32 nChunks, u32 chunkBytes, u64 frameSpan, const LdmLaunch& p, u32 nSplits, u8* small, u8* big,
+                     Seq* seqs, u8* lits, ChunkMeta* meta, hipStream_t stream, StageHook hook, const LdmPrefix& pfx);
+// decoder (decode_walk.hip, decode_lit.hip, decode_seq.hip)
+size_t decode_walk_workspace_bytes(u64 srcSize);
+void launch_frame_walk_count(const u8* src, u64 srcSize, u32 maxFrames, u32* status, u8* walkWs, hipStream_t stream);
+void launch_frame_walk_emit(const u8* src, u64 srcSize, FrameDesc* frames, BlockDesc* blocks, u8* walkWs, hipStream_t stream);
+void launch_frame_walk_serial(const u8* src, u64 srcSize, FrameDesc* frames, BlockDesc* blocks, u32 maxFrames, u32* status, u32 dictID, u32 emit,
+                              hipStream_t stream);
+void launch_batch_walk_count(const u8* src, const BatchEntryIn* in, BatchEntryOut* out, u32 nEntries, u32 dictID, u64 aloneAbove, u32* status, hipStream_t stream);
+void launch_batch_walk_emit(const u8* src, const BatchEntryIn* in, const BatchEntryOut* out, u32 nEntries, FrameDesc* frames, BlockDesc* blocks, hipStream_t stream);
+void launch_batch_fold(BatchEntryOut* out, u32 nEntries, const u64* keys, hipStream_t stream);
+void launch_seek_select(const u8* tab, u64 tableBytes, u32 n, u32 stride, u64 srcSize, u64 offset, u64 length, u64* sum, hipStream_t stream);
+void launch_seek_emit(const u8* tab, u32 stride, u32 first, u32 nSel, u64 dFirst, u64 offset, u64 dstBias, u64 edgeBias, u64 slot1, u32 cutFirst, u32 cutLast,
+                      BatchEntryIn* out, hipStream_t stream);
+void launch_range_check(const BatchEntryIn* in, const BatchEntryOut* out, u32 nEntries, u64* sum, hipStream_t stream);
+void launch_range_clip(u8* dst, const u8* edge, ClipJob j0, ClipJob j1, hipStream_t stream);
+// many ranges of a seekable stream (decode_ranges.hip)
+size_t ranges_ws_bytes(u32 n);
+RangesWs ranges_ws(u8* p, u32 n);
+void launch_seek_index(const u8* tab, u64 tableBytes, u32 n, u32 stride, u64 srcSize, const RangesWs& ws, hipStream_t stream);
+void launch_ranges_select(const RangeIn* in, RangeRec* recs, u32 nRanges, u32 n, const RangesWs& ws, hipStream_t stream);
+void launch_ranges_plan(const u8* tab, u32 n, u32 stride, u32 srcDev, const RangesWs& ws, BatchEntryIn* out, hipStream_t stream);
+void launch_ranges_alone(const BatchEntryOut* out, u32 nEntries, const RangesWs& ws, hipStream_t stream);
+void launch_ranges_gather(const RangeIn* in, const RangeRec* recs, u64* res, u32 nRanges, u32 nSlices, const RangesWs& ws, const BatchEntryOut* out,
+                          const u8* arena, hipStream_t stream);
+void launch_seq_stats(const Seq* seqs, const u8* lits, const ChunkMeta* meta, u32 nChunks, const u8* src, u32 chunkBytes, u32* stats, hipStream_t stream);
+void launch_dict_parse(const u8* dict, u32 dictSize, DictInfo* out, hipStream_t stream);
+void launch_block_prepass(const u8* src, FrameDesc* frames, BlockDesc* blocks, u32 nFrames, u32 nBlocks, u32 haveDict, u32 earlyLiterals, u32* status, hipStream_t stream);
+void launch_seq_decode(const u8* src, const FrameDesc* frames, BlockDesc* blocks, u32 nBlocks, SeqRec* recs, u32* status,
+                       const u8* dictFull, const DictInfo* di, hipStream_t stream);
+void launch_block_offsets(FrameDesc* frames, BlockDesc* blocks, u32 nFrames, const DictInfo* di, u32 rescan, u64 dstCapacity, u32* status, hipStream_t stream);
+void launch_decode_literals(const u8* src, u8* out, u8* scratch, const FrameDesc* frames, const BlockDesc* blocks, u32 nBlocks, u32* status,
+                            u8* slowFlags, u32 mode, const u8* dictFull, const DictInfo* di, hipStream_t stream, StageHook hook);
+void launch_place_literals(const u8* src, u8* out, const u8* scratch, const FrameDesc* frames, const BlockDesc* blocks, u32 nBlocks,
+                           const SeqRec* recs, const u32* status, hipStream_t stream);
+void launch_exec_matches(const u8* src, u8* out, const FrameDesc* frames, const BlockDesc* blocks, u32 nFrames, const SeqRec* recs, u32* status,
+                         const u8* dict, u32 dictSize, hipStream_t stream, int wide);
+void launch_origin_select(FrameDesc* frames, u32 nFrames, u64 minBytes, u32* list, u32 listCap, u64 originCap, u32* status, hipStream_t stream);
+void launch_origin_init(const FrameDesc* frames, const BlockDesc* blocks, const u32* list, u32 listCap, u64 maxFrameBytes, const SeqRec* recs, u32* status,
+                        u32* origin, u32 dictSize, hipStream_t stream);
+void launch_origin_jump(const FrameDesc* frames, const u32* list, u32 listCap, u64 maxFrameBytes, u32* status, u32* origin, u32* done, u32 r0, u32 r1, hipStream_t stream);
+void launch_origin_gather(const FrameDesc* frames, const u32* list, u32 listCap, u64 maxFrameBytes, const u32* status, const u32* origin, u8* out, const u8* dict, hipStream_t stream);
+// a batch of samples through the compressor, sizes (and sequence statistics) only (zstd_mi355x.hip; the dictionary trainer's inner loop)
+size_t compress_samples(ZSTD_CCtx* c, const u8* src, const u64* offs, const size_t* sizes, size_t n, size_t* outSizes, u32* stats);
+}
+
+using namespace zmi;
+
+#define ZERR(code) ((size_t)0 - (size_t)(code))
+static inline bool isErr(size_t c) { return c > ZERR(kErrMaxCode); }
+// No C++ exception may cross the C ABI (the caller is P/Invoke): host-side container growth is the only thing that throws here.
+template <class F> static size_t guarded(F f)
+{
+    try { return f(); }
+    catch (const std::bad_alloc&) { return ZERR(kErrMemoryAllocation); }
+    catch (...) { return ZERR(kErrGeneric); }
+}
+
+namespace {
+
+constexpr int kMaxStages = 24;
+
+struct DevBuf {
+    void* p = nullptr; size_t cap = 0;
+    bool ensure(size_t n)
+    {
+        if (n <= cap) return true;
+        if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
+        size_t want = n + (n >> 3) + 4096;
+        if (hipMalloc(&p, want) != hipSuccess) { p = nullptr; if (hipMalloc(&p, n) != hipSuccess) { p = nullptr; return false; } want = n; }
+        cap = want; return true;
+    }
+    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+};
+
+struct StageTimer {
+    bool enabled = false;
+    hipEvent_t ev[kMaxStages + 1] = {};
+    const char* names[kMaxStages] = {};
+    float ms[kMaxStages] = {};
+    int n = 0; bool created = false; hipStream_t stream = nullptr;
+    static void hook_fn(void* self, const char* name) { StageTimer* t = (StageTimer*)self; t->mark(name, t->stream); }
+    StageHook hook() { StageHook h; if (enabled) { h.fn = hook_fn; h.self = this; } return h; }
+    void begin(hipStream_t s) { n = 0; stream = s; if (!enabled) return; if (!created) { for (auto& e : ev) (void)hipEventCreate(&e); created = true; } (void)hipEventRecord(ev[0], s); }
+    void mark(const char* name, hipStream_t s) { if (!enabled || n >= kMaxStages) return; names[n] = name; (void)hipEventRecord(ev[n + 1], s); n++; }
+    void finish() { if (!enabled) return; for (int i = 0; i < n; i++) { float t = 0; (void)hipEventElapsedTime(&t, ev[i], ev[i + 1]); ms[i] = t; } }
+    void destroy() { if (created) for (auto& e : ev) (void)hipEventDestroy(e); created = false; }
+};
+
+bool is_device_ptr(const void* p)
+{
+    if (!p) return false;
+    hipPointerAttribute_t a;
+    if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }
+    return a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged;
+}
+
+// a zstd-format dictionary starts with the magic 0xEC30A437 (ZSTD_MAGIC_DICTIONARY); anything else is raw content
+bool is_formatted_dictionary(const u8* p, size_t n)
+{
+    return n >= 8 && ((u32)p[0] | ((u32)p[1] << 8) | ((u32)p[2] << 16) | ((u32)p[3] << 24)) == 0xEC30A437u;
+}
+
+// devices the kernels can run on: the leading run of gfx950 agents (device ordinals stay HIP's, so a context's device index means
+// the same thing to the caller's runtime; the code objects in this library are gfx950 only)
+int device_count()
+{
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess) { (void)hipGetLastError(); return 0; }
+    int ok = 0;
+    for (; ok < n; ++ok) {
+        hipDeviceProp_t p;
+        if (hipGetDeviceProperties(&p, ok) != hipSuccess) { (void)hipGetLastError(); break; }
+        if (strncmp(p.gcnArchName, "gfx950", 6) != 0) break;
+    }
+    return ok;
+}
+
+} // namespace
+
+// run f(0 .. n - 1), one host thread each (f(0) on the caller's): a device worker's calls block on its own stream
+// (nothing may leave a thread as an exception: -> false, and the caller reports memory_allocation)
+template <class F> static bool run_on_workers(size_t n, F f)
+{
+    std::vector<std::thread> th;
+    std::vector<u8> bad(n, 0);
+    th.reserve(n);
+    auto one = [&f, &bad](size_t i) { try { f(i); } catch (...) { bad[i] = 1; } };
+    bool ok = true;
+    for (size_t i = 1; i < n; ++i) { try { th.emplace_back(one, i); } catch (...) { ok = false; break; } }
+    if (ok) one(0);
+    for (auto& t : th) t.join();
+    for (size_t i = 0; i < n; ++i) ok = ok && !bad[i];
+    return ok;
+}
+
+// a copy between any two places (host or device, this device or a peer), enqueued on s
+static size_t copy_any(void* dst, const void* src, size_t n, hipStream_t s)
+{
+    if (!n) return 0;
+    if (hipMemcpyAsync(dst, src, n, hipMemcpyDefault, s) != hipSuccess) { (void)hipGetLastError(); return ZERR(kErrGeneric); }
+    return 0;
+}
+
+// wait for everything enqueued on s -> 0 or generic (the failed wait's error is taken off the runtime's record)
+static size_t stream_wait(hipStream_t s)
+{
+    if (hipStreamSynchronize(s) != hipSuccess) { (void)hipGetLastError(); return ZERR(kErrGeneric); }
+    return 0;
+}
+// device memory read back to the host: the copy, enqueued on s, and the wait for it
+static size_t dev_read(void* host, const void* dev, size_t bytes, hipStream_t s)
+{
+    if (hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, s) != hipSuccess) return ZERR(kErrGeneric);
+    return stream_wait(s);
+}
+
+// ---- what ZSTD_CCtx_s and ZSTD_DCtx_s do alike (device, deviceOk, ownStream, stream, workers, dictGen) ----
+// make the context's device the current one; the first time, check that it is there and create the context's stream
+template <class Ctx> static size_t ctx_bind(Ctx* c)
+{
+    if (!c) return ZERR(kErrGeneric);
+    if (!c->deviceOk) {
+        if (device_count() <= c->device) return ZERR(kErrInitMissing);       // no gfx950 device: fail loudly, never fall back
+        if (hipSetDevice(c->device) != hipSuccess) return ZERR(kErrInitMissing);
+        if (!c->ownStream && hipStreamCreateWithFlags(&c->ownStream, hipStreamNonBlocking) != hipSuccess) return ZERR(kErrMemoryAllocation);
+        if (!c->stream) c->stream = c->ownStream;
+        c->deviceOk = true;
+    } else if (hipSetDevice(c->device) != hipSuccess) return ZERR(kErrInitMissing);
+    return 0;
+}
+template <class Ctx> static size_t ctx_set_device(Ctx* c, int device) { if (!c) return ZERR(kErrGeneric); if (c->deviceOk && device != c->device) return ZERR(kErrStageWrong); c->device = device; return 0; }
+template <class Ctx> static size_t ctx_set_stream(Ctx* c, void* st, size_t (*bind)(Ctx*)) { size_t e = bind(c); if (isErr(e)) return e; c->stream = st ? (hipStream_t)st : c->ownStream; return 0; }
+// devices: one worker per entry (an ordinal may repeat: several workers share that device); n <= 1 = back to the context's own device
+template <class Ctx> static size_t ctx_set_devices(Ctx* c, const int* devices, int n, Ctx* (*create)(void), size_t (*release)(Ctx*))
+{
+    if (!c || n < 0 || n > 64 || (n && !devices)) return ZERR(kErrParameterOutOfBound);
+    for (int i = 0; i < n; ++i) if (devices[i] < 0 || devices[i] >= device_count()) return ZERR(kErrInitMissing);
+    for (Ctx* w : c->workers) (void)release(w);
+    c->workers.clear();
+    if (n <= 1) { if (n == 1) return ctx_set_device(c, devices[0]); return 0; }
+    for (int i = 0; i < n; ++i) {
+        Ctx* w = create();
+        if (!w) return ZERR(kErrMemoryAllocation);
+        w->device = devices[i]; w->dictGen = ~(u64)0;
+        c->workers.push_back(w);
+    }
+    return 0;
+}

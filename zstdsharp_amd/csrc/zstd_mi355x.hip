@@ -1,166 +1,11 @@
-// zstd_mi355x.hip — host side of libzstd_mi355x.so: contexts, parameters, error names, HBM workspaces and the
-// launch sequences of the compress / decompress pipelines.  The C ABI is declared in include/zstd_mi355x.h.
+// zstd_mi355x.hip — the compressor's host side of libzstd_mi355x.so: the compression context, parameters, HBM workspaces, the launch
+// sequences of the compress pipeline, the ZSTD_compressStream2 adapter, device workers, and the library's error names and version.
+// The decoder's host side is zstd_mi355x_dec.hip; what both share is zmi_host.h.  The C ABI is declared in include/zstd_mi355x.h.
 //
 // There is no CPU codec in this library: without a usable gfx950 device every compress/decompress call returns
 // ZSTD_error_init_missing, loudly.
-#include <hip/hip_runtime.h>
-#include <stdlib.h>
-#include <string.h>
-#include <stdio.h>
-#include <vector>
-#include <cstring>
-#include <mutex>
-#include <thread>
-#include <new>
-#include <functional>
-#include "zmi_common.h"
 #include "zmi_cparams.h"
-#include "zmi_pack_runs.h"
-#include "../../include/zstd_mi355x.h"
-
-namespace zmi {
-// kernels (lz_fast.hip, huf_enc.hip, seq_enc.hip, frame.hip, decode.hip)
-void launch_lz(u32 finder, const u8* src, u64 srcSize, u32 nChunks, Seq* seqs, u8* lits, ChunkMeta* meta, const u8* prefix, u32 prefixLen,
-               u32 chunkBytes, u32 fhExtra, u32 minStrideLog, u32 frameBlocks, u16* cand, u16* chain, u32* regionList, u32 hcDepth, hipStream_t stream, StageHook hook, u32* claimCtr,
-               const u32* chunkLens = nullptr);
-void launch_lz_probe(const u8* src, u64 srcSize, u64 front, u64 groupBytes, u32 nGroups, u32 tilesPerGroup, u32* out, hipStream_t stream);
-void launch_huf_build(const u8* lits, ChunkMeta* meta, HufTable* tables, u8* slots, u32 nChunks, u32 rawLiterals, const u8* src, u32 chunkBytes,
-                      hipStream_t stream, StageHook hook);
-void launch_huf_encode(const u8* lits, const ChunkMeta* meta, const HufTable* tables, u8* slots, u8* dst, const u64* offsets, u64 dstCapacity,
-                       u32 nChunks, const u8* src, u32 chunkBytes, hipStream_t stream);
-void launch_seq_encode(Seq* seqs, ChunkMeta* meta, u8* slots, u32 nChunks, u32 strategy, u32 checksumFlag, u32 resolveReps,
-                       u32 dictID, u32 dictIdBytes, const u32* initReps, u32 frameBlocks, u32 chunkBytes, u64 srcSize, hipStream_t stream);
-void launch_scan_sizes(const ChunkMeta* meta, u32 nChunks, u64* offsets, u64* total, hipStream_t stream);
-void launch_gather(const u8* src, u64 srcSize, const u8* slots, const ChunkMeta* meta, const u64* offsets, u8* dst, u64 dstCapacity,
-                   u32 nChunks, u32 chunkBytes, hipStream_t stream);
-void launch_xxh64(const u8* src, u64 srcSize, ChunkMeta* meta, u32 nChunks, u32 chunkBytes, u32 frameBlocks, hipStream_t stream, const u32* chunkLens = nullptr);
-void launch_batch_stage(const u64* from, const u32* len, u8* stage, u32 nChunks, u32 chunkBytes, hipStream_t stream);
-void launch_batch_place(const ChunkMeta* meta, u32 nEntries, const u32* entFirst, const u64* entDst, const u64* entCap, u64 span, u64* offsets, u64* entSize,
-                        hipStream_t stream);
-void launch_seek_entries(const u64* offsets, const u64* total, u32 nChunks, u32 frameBlocks, u32 chunkBytes, u64 passBytes, u32* entries, hipStream_t stream);
-void launch_seek_table(const u32* entries, u32 n, u8* dst, hipStream_t stream);
-// long-distance matching (ldm.hip)
-size_t ldm_small_bytes(u64 n);
-size_t ldm_big_bytes(u64 nSplits);
-void launch_ldm_count(const u8* src, u64 n, u64 frameSpan, const LdmLaunch& p, u8* small, hipStream_t stream, const LdmPrefix& pfx);
-u32* ldm_total_word(u8* small, u64 n);
-void launch_ldm_rest(const u8* src, u64 n, u32 nChunks, u32 chunkBytes, u64 frameSpan, const LdmLaunch& p, u32 nSplits, u8* small, u8* big,
-                     Seq* seqs, u8* lits, ChunkMeta* meta, hipStream_t stream, StageHook hook, const LdmPrefix& pfx);
-// decoder (decode_walk.hip, decode_lit.hip, decode_seq.hip)
-size_t decode_walk_workspace_bytes(u64 srcSize);
-void launch_frame_walk_count(const u8* src, u64 srcSize, u32 maxFrames, u32* status, u8* walkWs, hipStream_t stream);
-void launch_frame_walk_emit(const u8* src, u64 srcSize, FrameDesc* frames, BlockDesc* blocks, u8* walkWs, hipStream_t stream);
-void launch_frame_walk_serial(const u8* src, u64 srcSize, FrameDesc* frames, BlockDesc* blocks, u32 maxFrames, u32* status, u32 dictID, u32 emit,
-                              hipStream_t stream);
-void launch_batch_walk_count(const u8* src, const BatchEntryIn* in, BatchEntryOut* out, u32 nEntries, u32 dictID, u64 aloneAbove, u32* status, hipStream_t stream);
-void launch_batch_walk_emit(const u8* src, const BatchEntryIn* in, const BatchEntryOut* out, u32 nEntries, FrameDesc* frames, BlockDesc* blocks, hipStream_t stream);
-void launch_batch_fold(BatchEntryOut* out, u32 nEntries, const u64* keys, hipStream_t stream);
-void launch_seek_select(const u8* tab, u64 tableBytes, u32 n, u32 stride, u64 srcSize, u64 offset, u64 length, u64* sum, hipStream_t stream);
-void launch_seek_emit(const u8* tab, u32 stride, u32 first, u32 nSel, u64 dFirst, u64 offset, u64 dstBias, u64 edgeBias, u64 slot1, u32 cutFirst, u32 cutLast,
-                      BatchEntryIn* out, hipStream_t stream);
-void launch_range_check(const BatchEntryIn* in, const BatchEntryOut* out, u32 nEntries, u64* sum, hipStream_t stream);
-void launch_range_clip(u8* dst, const u8* edge, ClipJob j0, ClipJob j1, hipStream_t stream);
-// many ranges of a seekable stream (decode_ranges.hip)
-size_t ranges_ws_bytes(u32 n);
-RangesWs ranges_ws(u8* p, u32 n);
-void launch_seek_index(const u8* tab, u64 tableBytes, u32 n, u32 stride, u64 srcSize, const RangesWs& ws, hipStream_t stream);
-void launch_ranges_select(const RangeIn* in, RangeRec* recs, u32 nRanges, u32 n, const RangesWs& ws, hipStream_t stream);
-void launch_ranges_plan(const u8* tab, u32 n, u32 stride, u32 srcDev, const RangesWs& ws, BatchEntryIn* out, hipStream_t stream);
-void launch_ranges_alone(const BatchEntryOut* out, u32 nEntries, const RangesWs& ws, hipStream_t stream);
-void launch_ranges_gather(const RangeIn* in, const RangeRec* recs, u64* res, u32 nRanges, u32 nSlices, const RangesWs& ws, const BatchEntryOut* out,
-                          const u8* arena, hipStream_t stream);
-void launch_seq_stats(const Seq* seqs, const u8* lits, const ChunkMeta* meta, u32 nChunks, const u8* src, u32 chunkBytes, u32* stats, hipStream_t stream);
-void launch_dict_parse(const u8* dict, u32 dictSize, DictInfo* out, hipStream_t stream);
-void launch_block_prepass(const u8* src, FrameDesc* frames, BlockDesc* blocks, u32 nFrames, u32 nBlocks, u32 haveDict, u32 earlyLiterals, u32* status, hipStream_t stream);
-void launch_seq_decode(const u8* src, const FrameDesc* frames, BlockDesc* blocks, u32 nBlocks, SeqRec* recs, u32* status,
-                       const u8* dictFull, const DictInfo* di, hipStream_t stream);
-void launch_block_offsets(FrameDesc* frames, BlockDesc* blocks, u32 nFrames, const DictInfo* di, u32 rescan, u64 dstCapacity, u32* status, hipStream_t stream);
-void launch_decode_literals(const u8* src, u8* out, u8* scratch, const FrameDesc* frames, const BlockDesc* blocks, u32 nBlocks, u32* status,
-                            u8* slowFlags, u32 mode, const u8* dictFull, const DictInfo* di, hipStream_t stream, StageHook hook);
-void launch_place_literals(const u8* src, u8* out, const u8* scratch, const FrameDesc* frames, const BlockDesc* blocks, u32 nBlocks,
-                           const SeqRec* recs, const u32* status, hipStream_t stream);
-void launch_exec_matches(const u8* src, u8* out, const FrameDesc* frames, const BlockDesc* blocks, u32 nFrames, const SeqRec* recs, u32* status,
-                         const u8* dict, u32 dictSize, hipStream_t stream, int wide);
-void launch_origin_select(FrameDesc* frames, u32 nFrames, u64 minBytes, u32* list, u32 listCap, u64 originCap, u32* status, hipStream_t stream);
-void launch_origin_init(const FrameDesc* frames, const BlockDesc* blocks, const u32* list, u32 listCap, u64 maxFrameBytes, const SeqRec* recs, u32* status,
-                        u32* origin, u32 dictSize, hipStream_t stream);
-void launch_origin_jump(const FrameDesc* frames, const u32* list, u32 listCap, u64 maxFrameBytes, u32* status, u32* origin, u32* done, u32 r0, u32 r1, hipStream_t stream);
-void launch_origin_gather(const FrameDesc* frames, const u32* list, u32 listCap, u64 maxFrameBytes, const u32* status, const u32* origin, u8* out, const u8* dict, hipStream_t stream);
-}
-
-using namespace zmi;
-
-#define ZERR(code) ((size_t)0 - (size_t)(code))
-static inline bool isErr(size_t c) { return c > ZERR(kErrMaxCode); }
-// No C++ exception may cross the C ABI (the caller is P/Invoke): host-side container growth is the only thing that throws here.
-template <class F> static size_t guarded(F f)
-{
-    try { return f(); }
-    catch (const std::bad_alloc&) { return ZERR(kErrMemoryAllocation); }
-    catch (...) { return ZERR(kErrGeneric); }
-}
-
-namespace {
-
-constexpr int kMaxStages = 24;
-
-struct DevBuf {
-    void* p = nullptr; size_t cap = 0;
-    bool ensure(size_t n)
-    {
-        if (n <= cap) return true;
-        if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
-        size_t want = n + (n >> 3) + 4096;
-        if (hipMalloc(&p, want) != hipSuccess) { p = nullptr; if (hipMalloc(&p, n) != hipSuccess) { p = nullptr; return false; } want = n; }
-        cap = want; return true;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-};
-
-struct StageTimer {
-    bool enabled = false;
-    hipEvent_t ev[kMaxStages + 1] = {};
-    const char* names[kMaxStages] = {};
-    float ms[kMaxStages] = {};
-    int n = 0; bool created = false; hipStream_t stream = nullptr;
-    static void hook_fn(void* self, const char* name) { StageTimer* t = (StageTimer*)self; t->mark(name, t->stream); }
-    StageHook hook() { StageHook h; if (enabled) { h.fn = hook_fn; h.self = this; } return h; }
-    void begin(hipStream_t s) { n = 0; stream = s; if (!enabled) return; if (!created) { for (auto& e : ev) (void)hipEventCreate(&e); created = true; } (void)hipEventRecord(ev[0], s); }
-    void mark(const char* name, hipStream_t s) { if (!enabled || n >= kMaxStages) return; names[n] = name; (void)hipEventRecord(ev[n + 1], s); n++; }
-    void finish() { if (!enabled) return; for (int i = 0; i < n; i++) { float t = 0; (void)hipEventElapsedTime(&t, ev[i], ev[i + 1]); ms[i] = t; } }
-    void destroy() { if (created) for (auto& e : ev) (void)hipEventDestroy(e); created = false; }
-};
-
-bool is_device_ptr(const void* p)
-{
-    if (!p) return false;
-    hipPointerAttribute_t a;
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }
-    return a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged;
-}
-
-// a zstd-format dictionary starts with the magic 0xEC30A437 (ZSTD_MAGIC_DICTIONARY); anything else is raw content
-bool is_formatted_dictionary(const u8* p, size_t n)
-{
-    return n >= 8 && ((u32)p[0] | ((u32)p[1] << 8) | ((u32)p[2] << 16) | ((u32)p[3] << 24)) == 0xEC30A437u;
-}
-
-// devices the kernels can run on: the leading run of gfx950 agents (device ordinals stay HIP's, so a context's device index means
-// the same thing to the caller's runtime; the code objects in this library are gfx950 only)
-int device_count()
-{
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess) { (void)hipGetLastError(); return 0; }
-    int ok = 0;
-    for (; ok < n; ++ok) {
-        hipDeviceProp_t p;
-        if (hipGetDeviceProperties(&p, ok) != hipSuccess) { (void)hipGetLastError(); break; }
-        if (strncmp(p.gcnArchName, "gfx950", 6) != 0) break;
-    }
-    return ok;
-}
-
-} // namespace
+#include "zmi_host.h"
 
 // ======================================================================================================
 struct ZSTD_CCtx_s {
@@ -219,68 +64,10 @@ static u32 dict_prefix_len(const ZSTD_CCtx* c, size_t srcSize)
     return (u32)(have < (32u << 10) ? have : (32u << 10));
 }
 
-struct ZSTD_DCtx_s {
-    int windowLogMax = 27;
-    int device = 0; bool deviceOk = false;
-    hipStream_t ownStream = nullptr, stream = nullptr;
-    hipStream_t aux = nullptr; hipEvent_t auxDone = nullptr;     // the literal decoder beside seq_decode (decompress_device)
-    int overlapMode = 0;        // ZSTDMI_DCtx_setOverlap: 0 = by block count, 1 = never, 2 = always
-    bool lastWalkSerial = false; // the last call's frames were listed by the serial walk (ZSTDMI_debugLastWalkSerial)
-    int execWaves = 0;          // ZSTDMI_DCtx_setExecWaves: waves per frame in exec_matches, 0 = by the number of frames
-    DevBuf frames, blocks, recs, status, scratch, walkWs, slowFlags, stageSrc, stageDst, origin, originList;
-    DevBuf batchIn, batchOut, blockKeys;    // ZSTDMI_decompressBatch: the entries' table, what the batch walk made of them, one error key per block
-    int lastBatchAlone = 0;     // entries of the last ZSTDMI_decompressBatch that were decoded by the single-call path (debug hook)
-    DevBuf seekTab, seekSum, edge;          // ZSTDMI_decompressRange: a host source's seek table, the summary words, the frames the range cuts
-    int lastRangeFrames = 0; long long lastRangeStaged = 0;     // table entries the last range call decoded, bytes it copied host -> device (debug hooks)
-    // ZSTDMI_decompressRanges: the pass's workspace (RangesWs), the ranges as the host states them / as ranges_select files them /
-    // their results, and the arena that holds every touched frame's content once
-    DevBuf rangesWs, rangesIn, rangesRec, rangesRes, arena;
-    int lastRangesFrames = 0, lastRangesAlone = 0; long long lastRangesStaged = 0;      // (debug hooks)
-    int originMode = 0;         // ZSTDMI_DCtx_setLongFrames: 0 = by cost (see decompress_device), 1 = never, 2 = every frame of 1 MiB or more
-    StageTimer timer;
-    // streaming adapter (ZSTD_decompressStream): whole frames are collected on the host, decoded in batches
-    std::vector<u8> dIn, dOut; size_t dOutPos = 0; bool hostage = false;
-    u32 litDecoder = 0;         // 0 auto, 1 serial (4 lanes per frame), 2 self-synchronising (256 lanes per frame), 3 serial with compact tables
-    // dictionary (ZSTD_DCtx_loadDictionary): host copy, uploaded at the next decompression.  Raw content: the bytes are the
-    // history.  Formatted (magic 0xEC30A437): dict_parse_kernel validates the header and fills `info`; the history is the content.
-    std::vector<u8> dictHost; DevBuf dict, dictInfoDev; bool dictDirty = false, dictFormatted = false;
-    DictInfo info = {};
-    u64 dictGen = 0;
-    std::vector<ZSTD_DCtx_s*> workers;      // ZSTDMI_DCtx_setDevices (decompress_multi)
-    // ZSTD_DCtx_refPrefix: the caller's bytes (host or device), referenced until the next ZSTD_decompressDCtx / ZSTDMI_decompressDevice
-    // has consumed them.  pfxDev: the prefix as that call's kernels read it (the caller's device pointer, or pfxStage for a host prefix)
-    const void* pfx = nullptr; size_t pfxSize = 0; DevBuf pfxStage; const u8* pfxDev = nullptr;
-};
 
 
 static size_t cctx_sync_dictionary(ZSTD_CCtx* c);
-static size_t cctx_bind(ZSTD_CCtx* c)
-{
-    if (!c) return ZERR(kErrGeneric);
-    if (!c->deviceOk) {
-        if (device_count() <= c->device) return ZERR(kErrInitMissing);       // no gfx950 device: fail loudly, never fall back
-        if (hipSetDevice(c->device) != hipSuccess) return ZERR(kErrInitMissing);
-        if (!c->ownStream && hipStreamCreateWithFlags(&c->ownStream, hipStreamNonBlocking) != hipSuccess) return ZERR(kErrMemoryAllocation);
-        if (!c->stream) c->stream = c->ownStream;
-        c->deviceOk = true;
-    } else if (hipSetDevice(c->device) != hipSuccess) return ZERR(kErrInitMissing);
-    return 0;
-}
-static size_t dctx_sync_dictionary(ZSTD_DCtx* d);
-static size_t dctx_bind(ZSTD_DCtx* d)
-{
-    if (!d) return ZERR(kErrGeneric);
-    if (!d->deviceOk) {
-        if (device_count() <= d->device) return ZERR(kErrInitMissing);
-        if (hipSetDevice(d->device) != hipSuccess) return ZERR(kErrInitMissing);
-        if (!d->ownStream && hipStreamCreateWithFlags(&d->ownStream, hipStreamNonBlocking) != hipSuccess) return ZERR(kErrMemoryAllocation);
-        if (!d->aux && hipStreamCreateWithFlags(&d->aux, hipStreamNonBlocking) != hipSuccess) return ZERR(kErrMemoryAllocation);
-        if (!d->auxDone && hipEventCreateWithFlags(&d->auxDone, hipEventDisableTiming) != hipSuccess) return ZERR(kErrMemoryAllocation);
-        if (!d->stream) d->stream = d->ownStream;
-        d->deviceOk = true;
-    } else if (hipSetDevice(d->device) != hipSuccess) return ZERR(kErrInitMissing);
-    return 0;
-}
+static size_t cctx_bind(ZSTD_CCtx* c) { return ctx_bind(c); }
 
 // The parameters one compression call runs with: the context's sticky ones (ZSTD_compress2, ZSTD_compressStream2) or, for
 // ZSTD_compressCCtx, the level alone with default frame parameters and no dictionary (U/ZstdCompress.cs:5751-5776:
@@ -351,8 +138,7 @@ static size_t cctx_sync_dictionary(ZSTD_CCtx* c)
         if (!c->dictFullDev.ensure(n + 64) || !c->dictInfoDev.ensure(sizeof(DictInfo))) return ZERR(kErrMemoryAllocation);
         if (hipMemcpyAsync(c->dictFullDev.p, c->dictFull.data(), n, hipMemcpyHostToDevice, s) != hipSuccess) return ZERR(kErrGeneric);
         launch_dict_parse((const u8*)c->dictFullDev.p, (u32)n, (DictInfo*)c->dictInfoDev.p, s);
-        if (hipMemcpyAsync(&c->info, c->dictInfoDev.p, sizeof(DictInfo), hipMemcpyDeviceToHost, s) != hipSuccess) return ZERR(kErrGeneric);
-        if (hipStreamSynchronize(s) != hipSuccess) { (void)hipGetLastError(); return ZERR(kErrGeneric); }
+        if (isErr(dev_read(&c->info, c->dictInfoDev.p, sizeof(DictInfo), s))) return ZERR(kErrGeneric);
         if (c->info.err) { c->dictFull.clear(); c->dictHost.clear(); c->dictFormatted = false; c->dictDirty = false; return ZERR(kErrDictionaryCorrupted); }
         const size_t keep = c->info.contentSize < kDictKeep ? c->info.contentSize : kDictKeep;
         c->dictHost.assign(c->dictFull.end() - (ptrdiff_t)keep, c->dictFull.end());
@@ -360,7 +146,7 @@ static size_t cctx_sync_dictionary(ZSTD_CCtx* c)
     if (!c->dictHost.empty()) {
         if (!c->dict.ensure(c->dictHost.size() + 64)) return ZERR(kErrMemoryAllocation);
         if (hipMemcpyAsync(c->dict.p, c->dictHost.data(), c->dictHost.size(), hipMemcpyHostToDevice, s) != hipSuccess) return ZERR(kErrGeneric);
-        if (hipStreamSynchronize(s) != hipSuccess) { (void)hipGetLastError(); return ZERR(kErrGeneric); }
+        if (isErr(stream_wait(s))) return ZERR(kErrGeneric);
     }
     c->dictDirty = false;
     return 0;
@@ -497,7 +283,7 @@ static size_t compress_range(ZSTD_CCtx* c, const CallParams& cp, u8* d_dst, size
         if (cp.checksumFlag) { f[n++] = 0x99; f[n++] = 0xE9; f[n++] = 0xD8; f[n++] = 0x51; }   // XXH64("") low 32 bits = 0x51D8E999
         if (dstCapacity < n) return ZERR(kErrDstSizeTooSmall);
         if (hipMemcpyAsync(d_dst, f, n, hipMemcpyHostToDevice, s) != hipSuccess) return ZERR(kErrGeneric);
-        (void)hipStreamSynchronize(s);
+        (void)hipStreamSynchronize(s);       // (deliberately not stream_wait: a failed wait is ignored here)
         return n;
     }
     if (cp.useDict) { const size_t e = cctx_sync_dictionary(c); if (isErr(e)) return e; }
@@ -546,8 +332,7 @@ static size_t compress_range(ZSTD_CCtx* c, const CallParams& cp, u8* d_dst, size
             if (!c->ldmSmall.ensure(ldm_small_bytes(nL))) return ZERR(kErrMemoryAllocation);
             launch_ldm_count(src, nL, span, fr.ldmP, (u8*)c->ldmSmall.p, s, lp);
             u32 nSplits = 0;
-            if (hipMemcpyAsync(&nSplits, ldm_total_word((u8*)c->ldmSmall.p, nL), sizeof(u32), hipMemcpyDeviceToHost, s) != hipSuccess) return ZERR(kErrGeneric);
-            if (hipStreamSynchronize(s) != hipSuccess) { (void)hipGetLastError(); return ZERR(kErrGeneric); }
+            if (isErr(dev_read(&nSplits, ldm_total_word((u8*)c->ldmSmall.p, nL), sizeof(u32), s))) return ZERR(kErrGeneric);
             c->timer.mark("ldm_count", s);
             if (nSplits) {
                 if (!c->ldmBig.ensure(ldm_big_bytes(nSplits))) return ZERR(kErrMemoryAllocation);
@@ -574,7 +359,7 @@ static size_t compress_range(ZSTD_CCtx* c, const CallParams& cp, u8* d_dst, size
             const u64 ck = (*markAt)[i] / chunkBytes;
             if (ck >= c0 && ck < c0 + nChunks && hipMemcpyAsync(&(*marks)[i], offsets + (ck - c0), sizeof(u64), hipMemcpyDeviceToHost, s) != hipSuccess) return ZERR(kErrGeneric);
         }
-        if (hipStreamSynchronize(s) != hipSuccess) { (void)hipGetLastError(); return ZERR(kErrGeneric); }
+        if (isErr(stream_wait(s))) return ZERR(kErrGeneric);
         if (markAt) for (size_t i = 0; i < markAt->size(); ++i) { const u64 ck = (*markAt)[i] / chunkBytes; if (ck >= c0 && ck < c0 + nChunks) (*marks)[i] += produced; }
         // stage times of the call = sums over its passes (inputs above 1 GiB take several)
         c->timer.finish(); c->nStages = c->timer.n;
@@ -619,8 +404,7 @@ static size_t probe_run(ZSTD_CCtx* c, const u8* d_src, size_t len, size_t front,
     const u32 nGroups = (u32)((len + group - 1) / group);
     if (!c->probe.ensure((size_t)nGroups * sizeof(u32))) return ZERR(kErrMemoryAllocation);
     launch_lz_probe(d_src, len, front, group, nGroups, kProbeTiles, (u32*)c->probe.p, c->stream);
-    if (hipMemcpyAsync(counts, c->probe.p, (size_t)nGroups * sizeof(u32), hipMemcpyDeviceToHost, c->stream) != hipSuccess) return ZERR(kErrGeneric);
-    if (hipStreamSynchronize(c->stream) != hipSuccess) { (void)hipGetLastError(); return ZERR(kErrGeneric); }
+    if (isErr(dev_read(counts, c->probe.p, (size_t)nGroups * sizeof(u32), c->stream))) return ZERR(kErrGeneric);
     return 0;
 }
 static void plan_ranges(const std::vector<u32>& counts, size_t group, size_t srcSize, std::vector<PlanRange>& out)
@@ -663,21 +447,6 @@ static size_t check_call_params(const CallParams& cp)
     return 0;
 }
 
-// run f(0 .. n - 1), one host thread each (f(0) on the caller's): a device worker's calls block on its own stream
-// (nothing may leave a thread as an exception: -> false, and the caller reports memory_allocation)
-template <class F> static bool run_on_workers(size_t n, F f)
-{
-    std::vector<std::thread> th;
-    std::vector<u8> bad(n, 0);
-    th.reserve(n);
-    auto one = [&f, &bad](size_t i) { try { f(i); } catch (...) { bad[i] = 1; } };
-    bool ok = true;
-    for (size_t i = 1; i < n; ++i) { try { th.emplace_back(one, i); } catch (...) { ok = false; break; } }
-    if (ok) one(0);
-    for (auto& t : th) t.join();
-    for (size_t i = 0; i < n; ++i) ok = ok && !bad[i];
-    return ok;
-}
 static size_t compress_multi(ZSTD_CCtx* c, const CallParams& cp, void* dst, size_t dstCapacity, const void* src, size_t srcSize);
 
 // A plan of several ranges (a mixed input: stretches the level's finder is for, stretches without matches) as it stands is a run of
@@ -750,7 +519,7 @@ static size_t compress_plan(ZSTD_CCtx* c, const CallParams& cp, const std::vecto
         if (hipMemcpyAsync(d_dst + pos, (const u8*)c->gatherOut.p + outAt[k] + lo, (size_t)(hi - lo), hipMemcpyDeviceToDevice, c->stream) != hipSuccess) return ZERR(kErrGeneric);
         pos += (size_t)(hi - lo);
     }
-    if (hipStreamSynchronize(c->stream) != hipSuccess) { (void)hipGetLastError(); return ZERR(kErrGeneric); }
+    if (isErr(stream_wait(c->stream))) return ZERR(kErrGeneric);
     c->lastChunks = 0;
     return pos;
 }
@@ -793,13 +562,13 @@ static size_t compress_device(ZSTD_CCtx* c, const CallParams& cp, u8* d_dst, siz
     if (srcSize == 0) {         // the one empty frame: the host wrote it and knows its size
         const u32 e[2] = { (u32)r, 0 };
         if (hipMemcpyAsync(c->seekEntries.p, e, sizeof e, hipMemcpyHostToDevice, s) != hipSuccess) return ZERR(kErrGeneric);
-        if (hipStreamSynchronize(s) != hipSuccess) { (void)hipGetLastError(); return ZERR(kErrGeneric); }
+        if (isErr(stream_wait(s))) return ZERR(kErrGeneric);
         c->seekCount = 1;
     }
     const size_t tableBytes = 17 + 8 * (size_t)c->seekCount;
     if (tableBytes > dstCapacity - r) return ZERR(kErrDstSizeTooSmall);
     launch_seek_table((const u32*)c->seekEntries.p, c->seekCount, d_dst + r, s);
-    if (hipStreamSynchronize(s) != hipSuccess) { (void)hipGetLastError(); return ZERR(kErrGeneric); }
+    if (isErr(stream_wait(s))) return ZERR(kErrGeneric);
     return r + tableBytes;
 }
 
@@ -991,7 +760,7 @@ static size_t compress_any(ZSTD_CCtx* c, const CallParams& cp, void* dst, size_t
     if (isErr(r)) return r;
     if (!dstDev) {
         if (hipMemcpyAsync(dst, d_dst, r, hipMemcpyDeviceToHost, c->stream) != hipSuccess) return ZERR(kErrGeneric);
-        if (hipStreamSynchronize(c->stream) != hipSuccess) return ZERR(kErrGeneric);
+        if (hipStreamSynchronize(c->stream) != hipSuccess) return ZERR(kErrGeneric);      // (deliberately not stream_wait: no hipGetLastError behind this wait)
     }
     return r;
 }
@@ -1080,750 +849,6 @@ size_t ZSTD_CStreamOutSize(void) { return ZSTD_compressBound((size_t)1 << 17) + 
 size_t ZSTD_DStreamInSize(void)  { return ((size_t)1 << 17) + 3; }
 size_t ZSTD_DStreamOutSize(void) { return (size_t)1 << 17; }
 
-// ---------------- decompression ----------------
-ZSTD_DCtx* ZSTD_createDCtx(void) { return new (std::nothrow) ZSTD_DCtx_s(); }
-size_t ZSTD_freeDCtx(ZSTD_DCtx* d)
-{
-    if (!d) return 0;
-    for (ZSTD_DCtx* w : d->workers) (void)ZSTD_freeDCtx(w);
-    d->workers.clear();
-    if (d->deviceOk) {
-        (void)hipSetDevice(d->device);
-        if (d->ownStream) (void)hipStreamSynchronize(d->ownStream);
-        d->frames.release(); d->blocks.release(); d->recs.release(); d->status.release(); d->scratch.release(); d->walkWs.release(); d->slowFlags.release(); d->stageSrc.release(); d->stageDst.release(); d->dict.release(); d->dictInfoDev.release(); d->origin.release(); d->originList.release(); d->batchIn.release(); d->batchOut.release(); d->blockKeys.release(); d->seekTab.release(); d->seekSum.release(); d->edge.release(); d->pfxStage.release(); d->rangesWs.release(); d->rangesIn.release(); d->rangesRec.release(); d->rangesRes.release(); d->arena.release();
-        d->timer.destroy();
-        if (d->aux) { (void)hipStreamSynchronize(d->aux); (void)hipStreamDestroy(d->aux); }
-        if (d->auxDone) (void)hipEventDestroy(d->auxDone);
-        if (d->ownStream) (void)hipStreamDestroy(d->ownStream);
-    }
-    delete d;
-    return 0;
-}
-size_t ZSTD_DCtx_setParameter(ZSTD_DCtx* d, int param, int value)
-{
-    if (!d) return ZERR(kErrGeneric);
-    if (param == ZSTD_d_windowLogMax) { if (value != 0 && (value < 10 || value > 31)) return ZERR(kErrParameterOutOfBound); d->windowLogMax = value ? value : 27; return 0; }
-    return ZERR(kErrParameterUnsupported);
-}
-size_t ZSTD_DCtx_getParameter(ZSTD_DCtx* d, int param, int* value)
-{
-    if (!d || !value) return ZERR(kErrGeneric);
-    if (param == ZSTD_d_windowLogMax) { *value = d->windowLogMax; return 0; }
-    return ZERR(kErrParameterUnsupported);
-}
-// ZSTD_decompress_insertDictionary, U/ZstdDecompress.cs:1909-1931: without the magic the bytes are raw content, history in
-// front of every frame (ZSTD_refDictContent, :1758-1771); with it (0xEC30A437) the header's Huffman and FSE tables and
-// repcodes are what every frame starts from and frames must name its dictID or none (ZSTD_loadDEntropy, :1773-1875).
-static size_t ZSTD_DCtx_loadDictionary_impl(ZSTD_DCtx* d, const void* dict, size_t dictSize)
-{
-    if (!d) return ZERR(kErrGeneric);
-    d->dictGen++;
-    d->pfx = nullptr; d->pfxSize = 0;       // (a pending prefix is cancelled: ZSTD_clearAllDicts)
-    if (dict == nullptr || dictSize == 0) { d->dictHost.clear(); d->dictDirty = true; return 0; }
-    if (dictSize > (size_t)1 << 30) return ZERR(kErrParameterUnsupported);
-    std::vector<u8> h(dictSize);
-    if (is_device_ptr(dict)) {
-        if (hipMemcpy(h.data(), dict, dictSize, hipMemcpyDeviceToHost) != hipSuccess) return ZERR(kErrGeneric);
-    } else memcpy(h.data(), dict, dictSize);
-    d->dictFormatted = is_formatted_dictionary(h.data(), dictSize);
-    d->dictHost.swap(h);
-    d->dictDirty = true;
-    if (d->dictFormatted && !isErr(dctx_bind(d))) return dctx_sync_dictionary(d);      // validated now when a device is there, else at first use
-    d->dictDirty = true;
-    return 0;
-}
-
-// Host-side header walk for host buffers (ZSTD_findFrameSizeInfo, U/ZstdDecompress.cs:877-951): headers only, no payload.
-static size_t host_frame_size_info(const u8* src, size_t srcSize, unsigned long long* bound)
-{
-    auto rd32 = [](const u8* p) { return (u32)p[0] | ((u32)p[1] << 8) | ((u32)p[2] << 16) | ((u32)p[3] << 24); };
-    if (srcSize >= 8 && (rd32(src) & 0xFFFFFFF0u) == 0x184D2A50u) {
-        const u64 sz = (u64)rd32(src + 4) + 8;
-        if (sz > srcSize) return ZERR(kErrSrcSizeWrong);
-        *bound = 0; return (size_t)sz;
-    }
-    if (srcSize < 5) return ZERR(kErrSrcSizeWrong);
-    if (rd32(src) != 0xFD2FB528u) return ZERR(kErrPrefixUnknown);
-    const u8 fhd = src[4];
-    static const size_t did[4] = { 0, 1, 2, 4 }, fcsB[4] = { 0, 2, 4, 8 };
-    const u32 single = (fhd >> 5) & 1, fcsId = fhd >> 6;
-    const size_t fhs = 5 + !single + did[fhd & 3] + fcsB[fcsId] + (single && !fcsId);
-    if (srcSize < fhs) return ZERR(kErrSrcSizeWrong);
-    if (fhd & 0x08) return ZERR(kErrFrameParameterUnsupported);
-    size_t pos = 5; u64 windowSize = 0, fcs = ~0ull;
-    if (!single) { const u8 wl = src[pos++]; const u32 wlog = (wl >> 3) + 10; if (wlog > 31) return ZERR(kErrWindowTooLarge); windowSize = 1ull << wlog; windowSize += (windowSize >> 3) * (wl & 7); }
-    pos += did[fhd & 3];
-    switch (fcsId) {
-    case 0: if (single) fcs = src[pos]; break;
-    case 1: fcs = (u64)((u32)src[pos] | ((u32)src[pos + 1] << 8)) + 256; break;
-    case 2: fcs = rd32(src + pos); break;
-    default: fcs = (u64)rd32(src + pos) | ((u64)rd32(src + pos + 4) << 32); break;
-    }
-    if (single) windowSize = fcs;
-    const u64 blockSizeMax = windowSize < (1u << 17) ? windowSize : (1u << 17);
-    const u8* ip = src + fhs; size_t remaining = srcSize - fhs; u64 nbBlocks = 0;
-    for (;;) {
-        if (remaining < 3) return ZERR(kErrSrcSizeWrong);
-        const u32 bh = (u32)ip[0] | ((u32)ip[1] << 8) | ((u32)ip[2] << 16);
-        const u32 last = bh & 1, type = (bh >> 1) & 3; u32 cSize = bh >> 3;
-        if (type == 3) return ZERR(kErrCorruption);
-        if (type == 1) cSize = 1;
-        if (3 + (size_t)cSize > remaining) return ZERR(kErrSrcSizeWrong);
-        ip += 3 + cSize; remaining -= 3 + cSize; nbBlocks++;
-        if (last) break;
-    }
-    if ((fhd >> 2) & 1) { if (remaining < 4) return ZERR(kErrSrcSizeWrong); ip += 4; }
-    *bound = fcs != ~0ull ? fcs : nbBlocks * blockSizeMax;
-    return (size_t)(ip - src);
-}
-
-// Window size a frame header declares (ZSTD_getFrameHeader_advanced, U/ZstdDecompress.cs:462-634): the window descriptor, or the
-// content size of a single-segment frame.  0 = not a zstd frame header, or not all of it is there yet.
-static u64 host_frame_window(const u8* src, size_t srcSize)
-{
-    auto rd32 = [](const u8* p) { return (u32)p[0] | ((u32)p[1] << 8) | ((u32)p[2] << 16) | ((u32)p[3] << 24); };
-    if (srcSize < 5 || rd32(src) != 0xFD2FB528u) return 0;
-    const u8 fhd = src[4];
-    static const size_t did[4] = { 0, 1, 2, 4 }, fcsB[4] = { 0, 2, 4, 8 };
-    const u32 single = (fhd >> 5) & 1, fcsId = fhd >> 6;
-    const size_t fhs = 5 + !single + did[fhd & 3] + fcsB[fcsId] + (single && !fcsId);
-    if (srcSize < fhs) return 0;
-    if (!single) { const u8 wl = src[5]; const u32 wlog = (wl >> 3) + 10; if (wlog > 31) return ~0ull; const u64 w = 1ull << wlog; return w + (w >> 3) * (wl & 7); }
-    const size_t pos = 5 + did[fhd & 3];
-    switch (fcsId) {
-    case 0: return src[pos];
-    case 1: return (u64)((u32)src[pos] | ((u32)src[pos + 1] << 8)) + 256;
-    case 2: return rd32(src + pos);
-    default: return (u64)rd32(src + pos) | ((u64)rd32(src + pos + 4) << 32);
-    }
-}
-
-static const u8* host_view(const void* src, size_t srcSize, std::vector<u8>& tmp)
-{
-    if (!is_device_ptr(src)) return (const u8*)src;
-    tmp.resize(srcSize);
-    if (hipMemcpy(tmp.data(), src, srcSize, hipMemcpyDeviceToHost) != hipSuccess) return nullptr;
-    return tmp.data();
-}
-
-static unsigned long long ZSTD_decompressBound_impl(const void* src, size_t srcSize)
-{
-    std::vector<u8> tmp; const u8* ip = srcSize ? host_view(src, srcSize, tmp) : (const u8*)src;
-    if (srcSize && !ip) return (unsigned long long)0 - 2;
-    unsigned long long bound = 0;
-    while (srcSize > 0) {
-        unsigned long long b = 0; const size_t cs = host_frame_size_info(ip, srcSize, &b);
-        if (isErr(cs)) return (unsigned long long)0 - 2;
-        ip += cs; srcSize -= cs; bound += b;
-    }
-    return bound;
-}
-static size_t ZSTD_findFrameCompressedSize_impl(const void* src, size_t srcSize)
-{
-    std::vector<u8> tmp; const u8* ip = host_view(src, srcSize, tmp);
-    if (!ip) return ZERR(kErrSrcSizeWrong);
-    unsigned long long b; return host_frame_size_info(ip, srcSize, &b);
-}
-static unsigned long long ZSTD_getFrameContentSize_impl(const void* src, size_t srcSize)
-{
-    std::vector<u8> tmp; const size_t look = srcSize < 18 ? srcSize : 18;
-    const u8* ip = look ? host_view(src, look, tmp) : nullptr;
-    if (!ip || look < 5) return (unsigned long long)0 - 2;
-    auto rd32 = [](const u8* p) { return (u32)p[0] | ((u32)p[1] << 8) | ((u32)p[2] << 16) | ((u32)p[3] << 24); };
-    if ((rd32(ip) & 0xFFFFFFF0u) == 0x184D2A50u) return 0;
-    if (rd32(ip) != 0xFD2FB528u) return (unsigned long long)0 - 2;
-    const u8 fhd = ip[4]; static const size_t did[4] = { 0, 1, 2, 4 }, fcsB[4] = { 0, 2, 4, 8 };
-    const u32 single = (fhd >> 5) & 1, fcsId = fhd >> 6;
-    const size_t fhs = 5 + !single + did[fhd & 3] + fcsB[fcsId] + (single && !fcsId);
-    if (look < fhs) return (unsigned long long)0 - 2;
-    size_t pos = 5 + !single + did[fhd & 3];
-    switch (fcsId) {
-    case 0: return single ? ip[pos] : (unsigned long long)0 - 1;
-    case 1: return (u64)((u32)ip[pos] | ((u32)ip[pos + 1] << 8)) + 256;
-    case 2: return rd32(ip + pos);
-    default: return (u64)rd32(ip + pos) | ((u64)rd32(ip + pos + 4) << 32);
-    }
-}
-
-// upload a newly loaded dictionary; a formatted one is validated on the device (ZSTD_loadDEntropy's checks) -> dictionary_corrupted
-static size_t dctx_sync_dictionary(ZSTD_DCtx* d)
-{
-    if (!d->dictDirty) return 0;
-    hipStream_t s = d->stream;
-    if (!d->dictHost.empty()) {
-        if (!d->dict.ensure(d->dictHost.size() + 64) || !d->dictInfoDev.ensure(sizeof(DictInfo))) return ZERR(kErrMemoryAllocation);
-        if (hipMemcpyAsync(d->dict.p, d->dictHost.data(), d->dictHost.size(), hipMemcpyHostToDevice, s) != hipSuccess) return ZERR(kErrGeneric);
-        if (d->dictFormatted) {
-            launch_dict_parse((const u8*)d->dict.p, (u32)d->dictHost.size(), (DictInfo*)d->dictInfoDev.p, s);
-            if (hipMemcpyAsync(&d->info, d->dictInfoDev.p, sizeof(DictInfo), hipMemcpyDeviceToHost, s) != hipSuccess) return ZERR(kErrGeneric);
-        }
-        if (hipStreamSynchronize(s) != hipSuccess) { (void)hipGetLastError(); return ZERR(kErrGeneric); }
-        if (d->dictFormatted && d->info.err) { d->dictHost.clear(); d->dictFormatted = false; d->dictDirty = false; return ZERR(kErrDictionaryCorrupted); }
-    }
-    d->dictDirty = false;
-    return 0;
-}
-
-// the loaded dictionary as the decode kernels take it
-struct DecodeDict { bool fmt; const u8* dictFull; const DictInfo* dinfo; const u8* dictContent; u32 dictContentSize, dictID; };
-static DecodeDict decode_dict(const ZSTD_DCtx* d)
-{
-    DecodeDict k;
-    k.fmt = d->dictFormatted && !d->dictHost.empty();
-    k.dictFull = k.fmt ? (const u8*)d->dict.p : nullptr;
-    k.dinfo = k.fmt ? (const DictInfo*)d->dictInfoDev.p : nullptr;
-    k.dictContent = d->dictHost.empty() ? nullptr : (const u8*)d->dict.p + (k.fmt ? d->info.contentOff : 0u);
-    k.dictContentSize = d->dictHost.empty() ? 0u : (k.fmt ? d->info.contentSize : (u32)d->dictHost.size());
-    k.dictID = k.fmt ? d->info.dictID : 0u;
-    return k;
-}
-
-// Everything behind the frame walk: the lists (d->frames, d->blocks; offsets relative to d_src and d_dst) through block_prepass,
-// seq_decode, block_offsets, the literal decoder, the origin path and exec_matches.  `tail` enqueues what the caller wants read back
-// with the last status read (-> false: failed); st = the status words after it.  -> 0 or the error of the whole run.
-static size_t decode_lists(ZSTD_DCtx* d, const DecodeDict& dd, u8* d_dst, const u8* d_src, u32 nFrames, u32 nBlocks, u32 nUnsized, size_t dstCapacity, u32* st, const std::function<bool()>& tail)
-{
-    hipStream_t s = d->stream;
-    u32* status = (u32*)d->status.p;
-    FrameDesc* frames = (FrameDesc*)d->frames.p; BlockDesc* blocks = (BlockDesc*)d->blocks.p;
-    const bool fmt = dd.fmt; const u8* const dictFull = dd.dictFull; const DictInfo* const dinfo = dd.dinfo;
-    const u8* const dictContent = dd.dictContent; const u32 dictContentSize = dd.dictContentSize;
-    auto read_status = [&](u32* w) -> bool {
-        if (hipMemcpyAsync(w, status, kStWords * sizeof(u32), hipMemcpyDeviceToHost, s) != hipSuccess) return false;
-        if (hipStreamSynchronize(s) != hipSuccess) { (void)hipGetLastError(); return false; }
-        return true;
-    };
-    // The literal decoder and seq_decode need nothing of each other (a block's Huffman streams and its FSE chains).  With few
-    // blocks neither fills the chip — both are serial chains per block — so below kOverlapBlocks the literal decoder may run beside
-    // seq_decode on a stream of its own (`early`: block_link then lets it write only the outputs whose place is known by now).
-    // Whether it does is decided once the pre-pass has counted both kinds of work (below).
-    constexpr u32 kOverlapBlocks = 12288;
-    const bool early = d->overlapMode == 2 || (d->overlapMode == 0 && nBlocks <= kOverlapBlocks);
-    launch_block_prepass(d_src, frames, blocks, nFrames, nBlocks, fmt ? 1u : 0u, early ? 1u : 0u, status, s);
-    if (!read_status(st)) return ZERR(kErrGeneric);
-    d->timer.mark("block_prepass", s);
-    const u64 nSeq = (u64)st[kStSeqLo] | ((u64)st[kStSeqHi] << 32);
-    if (!d->recs.ensure((size_t)(nSeq + 64) * sizeof(SeqRec))) return ZERR(kErrMemoryAllocation);
-    // Long frames (decode_origin.hip).  The ordered walk of exec_matches moves a frame at about kWalkRate, all frames at
-    // once; the origin path sweeps the frames it is given at about kSweepRate together.  A frame belongs on the origin path when its
-    // own walk would outlast the sweep of every frame at least as long: the smallest size class 2^(20+k) with
-    // 2^(20+k) / kWalkRate >= bytes(frames >= 2^(20+k)) / kSweepRate, from the per-class sums block_link filed.
-    u64 originMin = 0, originBytes = 0, originLongest = 0; u32 originCap = 0;
-    // (the walk has 64 x W sequences in flight per frame, W waves by the number of frames: measured on 1 - 4 MiB level-5 frames)
-    const int execWaves = d->execWaves ? d->execWaves : nFrames <= 256 ? 16 : nFrames <= 512 ? 8 : nFrames <= 1024 ? 4 : nFrames <= 2048 ? 2 : 1;
-    if (d->originMode != 1) {
-        const double kWalkRate = execWaves >= 16 ? 0.42e9 : execWaves == 8 ? 0.33e9 : execWaves == 4 ? 0.24e9 : execWaves == 2 ? 0.19e9 : 0.15e9;
-        constexpr double kSweepRate = 20e9;
-        u64 above = 0;
-        u64 sums[12];
-        for (int k = 0; k < 12; ++k) sums[k] = (u64)st[kStBigBins + 2 * k] | ((u64)st[kStBigBins + 2 * k + 1] << 32);
-        for (int k = 11; k >= 0; --k) {
-            above += sums[k];
-            if (!above) continue;
-            const double size = (double)((u64)1 << (20 + k));
-            if (d->originMode == 2 || size / kWalkRate >= (double)above / kSweepRate) { originMin = (u64)1 << (20 + k); originBytes = above; }
-        }
-        if (originMin) {
-            // how many frames that can be (a frame of class k holds at least 2^(20+k) bytes) and how long the longest (below 2^(21+k))
-            u64 cap = 0;
-            for (int k = 0; k < 12; ++k) if (((u64)1 << (20 + k)) >= originMin && sums[k]) { cap += sums[k] >> (20 + k); originLongest = (u64)1 << (21 + k); }
-            if (originLongest > originBytes) originLongest = originBytes;
-            originCap = (u32)(cap < 65535 ? cap : 65535);       // (a grid dimension; more long frames than that keep the walk)
-            // (+ one word per 1024 origins: origin_jump_kernel's finished regions)
-            if (!d->origin.ensure((size_t)(originBytes + 1024 * (u64)originCap) * sizeof(u32) + (size_t)((originBytes + 1024 * (u64)originCap) / 1024 + 64) * sizeof(u32)) ||
-                !d->originList.ensure((size_t)originCap * sizeof(u32))) { originMin = 0; (void)hipGetLastError(); }
-        }
-    }
-    SeqRec* recs = (SeqRec*)d->recs.p;
-    struct AuxGuard { hipStream_t a; bool on; ~AuxGuard() { if (on) (void)hipStreamSynchronize(a); } } auxGuard{ d->aux, false };   // nothing of this call outlives it
-    // Beside each other only when both are substantial (from five coded literal bytes per sequence): a Huffman symbol costs its chain
-    // about 26 ns per literal byte (four streams), a sequence about 270 ns — text (three or four literal bytes per sequence) has nothing to hide behind seq_decode and only loses LDS
-    // bandwidth to the company (measured: 1 GiB of 1 MiB level-5 frames, mixed corpus 14.7 -> 13.4 ms, text 15.5 -> 15.7 ms), and
-    // input without sequences (Zipf bytes) has no seq_decode to hide behind.
-    const u64 litBytes = (u64)st[kStLitLo] | ((u64)st[kStLitHi] << 32);
-    const bool beside = early && nSeq && (d->overlapMode == 2 || (litBytes >= 5 * nSeq && nSeq >= 64 * (u64)nBlocks));
-    if (getenv("ZMI_DEBUG")) fprintf(stderr, "zmi: blocks %u seqs %llu coded literal bytes %llu early %d beside %d\n", nBlocks, (unsigned long long)nSeq, (unsigned long long)litBytes, (int)early, (int)beside);
-    if (beside) {               // (the host has just waited for the pre-pass: everything the literal decoder reads is there)
-        launch_decode_literals(d_src, d_dst, (u8*)d->scratch.p, frames, blocks, nBlocks, status, (u8*)d->slowFlags.p, d->litDecoder, dictFull, dinfo, d->aux, StageHook());
-        if (hipEventRecord(d->auxDone, d->aux) != hipSuccess) return ZERR(kErrGeneric);
-        auxGuard.on = true;
-    }
-    launch_seq_decode(d_src, frames, blocks, nBlocks, recs, status, dictFull, dinfo, s);            d->timer.mark("seq_decode", s);
-    launch_block_offsets(frames, blocks, nFrames, dinfo, nUnsized ? 1u : 0u, dstCapacity, status, s);  d->timer.mark("block_offsets", s);
-    if (auxGuard.on) { if (hipStreamWaitEvent(s, d->auxDone, 0) != hipSuccess) return ZERR(kErrGeneric); d->timer.mark("decode_literals", s); }     // (what of it seq_decode did not cover)
-    else launch_decode_literals(d_src, d_dst, (u8*)d->scratch.p, frames, blocks, nBlocks, status, (u8*)d->slowFlags.p, d->litDecoder, dictFull, dinfo, s, d->timer.hook());
-    launch_place_literals(d_src, d_dst, (const u8*)d->scratch.p, frames, blocks, nBlocks, recs, status, s);    d->timer.mark("place_literals", s);
-    if (originMin) {
-        const u64 entries = originBytes + 1024 * (u64)originCap, longest = originLongest;
-        u32* const origin = (u32*)d->origin.p; const u32* const list = (const u32*)d->originList.p;
-        launch_origin_select(frames, nFrames, originMin, (u32*)d->originList.p, originCap, entries, status, s);
-        launch_origin_init(frames, blocks, list, originCap, longest, recs, status, origin, dictContent ? dictContentSize : 0u, s);    d->timer.mark("origin_init", s);
-        // The rounds in groups of six, the host looking at the last one's verdict in between: ordinary data settles in about ten
-        // rounds, and a round that only finds out that nothing is left still costs its launch (the kernels check the flag too).
-        for (u32 r = 0; r < kOriginRounds; r += 6) {
-            launch_origin_jump(frames, list, originCap, longest, status, origin, origin + entries, r, r + 6, s);
-            u32 open = 0;
-            const u32 lastRound = (r + 6 < kOriginRounds ? r + 6 : kOriginRounds) - 1;
-            if (hipMemcpyAsync(&open, status + kStOriginChanged + lastRound, sizeof(u32), hipMemcpyDeviceToHost, s) != hipSuccess) return ZERR(kErrGeneric);
-            if (hipStreamSynchronize(s) != hipSuccess) { (void)hipGetLastError(); return ZERR(kErrGeneric); }
-            if (!open) break;
-        }
-        d->timer.mark("origin_jump", s);
-        launch_origin_gather(frames, list, originCap, longest, status, origin, d_dst, dictContent, s);    d->timer.mark("origin_gather", s);
-    }
-    launch_exec_matches(d_src, d_dst, frames, blocks, nFrames, recs, status, dictContent, dictContentSize, s, execWaves);  d->timer.mark("exec_matches", s);
-    if (!tail()) return ZERR(kErrGeneric);
-    if (!read_status(st)) return ZERR(kErrGeneric);
-    return 0;
-}
-
-// The decompress pipeline over device-resident buffers.  Two host round trips size the work lists (frames + blocks after the
-// counting walk, sequence records after the block pre-pass); everything else is one launch sequence:
-//   walk (count) | walk (emit) -> block_parse -> block_link -> seq_scan | seq_decode -> block_offsets [-> frame_rescan]
-//   -> decode_literals -> place_literals -> exec_matches
-static size_t decompress_device(ZSTD_DCtx* d, u8* d_dst, size_t dstCapacity, const u8* d_src, size_t srcSize)
-{
-    hipStream_t s = d->stream;
-    if (srcSize == 0) return 0;
-    // a frame is at least 9 bytes; our own streams hold one per 64 KiB, foreign ones usually far fewer
-    const u32 maxFrames = (u32)((srcSize / 9 + 1) < (1u << 26) ? (srcSize / 9 + 1) : (1u << 26));
-    if (!d->status.ensure(kStWords * sizeof(u32)) || !d->walkWs.ensure(decode_walk_workspace_bytes(srcSize))) return ZERR(kErrMemoryAllocation);
-    u32* status = (u32*)d->status.p;
-    { const size_t e = dctx_sync_dictionary(d); if (isErr(e)) return e; }
-    DecodeDict dd = decode_dict(d);
-    if (d->pfxDev) { dd.dictContent = d->pfxDev; dd.dictContentSize = (u32)d->pfxSize; }      // ZSTD_DCtx_refPrefix: raw content, read where it lies
-    const u32 dictID = dd.dictID;
-    auto read_status = [&](u32* st) -> bool {
-        if (hipMemcpyAsync(st, status, kStWords * sizeof(u32), hipMemcpyDeviceToHost, s) != hipSuccess) return false;
-        if (hipStreamSynchronize(s) != hipSuccess) { (void)hipGetLastError(); return false; }
-        return true;
-    };
-    d->timer.begin(s);
-    {   // error key = "none" (all ones); everything else zero
-        u32 init[kStWords] = {}; init[kStErrKeyLo] = 0xFFFFFFFFu; init[kStErrKeyHi] = 0xFFFFFFFFu;
-        if (hipMemcpyAsync(status, init, sizeof init, hipMemcpyHostToDevice, s) != hipSuccess) return ZERR(kErrGeneric);
-    }
-    u32 st[kStWords] = {};
-    launch_frame_walk_count(d_src, srcSize, maxFrames, status, (u8*)d->walkWs.p, s);
-    if (!read_status(st)) return ZERR(kErrGeneric);
-    const bool serialWalk = !st[kStUsable];
-    d->lastWalkSerial = serialWalk;
-    if (serialWalk) {   // the segment links did not close: take the exact serial walk (it also yields the reference's error code)
-        launch_frame_walk_serial(d_src, srcSize, nullptr, nullptr, maxFrames, status, dictID, 0, s);
-        if (!read_status(st)) return ZERR(kErrGeneric);
-    }
-    if (st[kStErr]) return ZERR(st[kStErr]);
-    const u32 nFrames = st[kStFrames], nBlocks = st[kStBlocks], nUnsized = st[kStUnsized];
-    const u64 total = (u64)st[kStTotalLo] | ((u64)st[kStTotalHi] << 32);       // content sizes (bounds for frames without one)
-    if (!nUnsized && total > dstCapacity) return ZERR(kErrDstSizeTooSmall);
-    if (nFrames == 0) { d->timer.finish(); return 0; }
-    if (!d->frames.ensure((size_t)nFrames * sizeof(FrameDesc)) || !d->blocks.ensure((size_t)nBlocks * sizeof(BlockDesc) + 64) ||
-        !d->scratch.ensure((size_t)total + (size_t)nFrames * kLitSkew + 256) || !d->slowFlags.ensure((size_t)nBlocks + 64)) return ZERR(kErrMemoryAllocation);
-    FrameDesc* frames = (FrameDesc*)d->frames.p; BlockDesc* blocks = (BlockDesc*)d->blocks.p;
-    if (serialWalk) launch_frame_walk_serial(d_src, srcSize, frames, blocks, maxFrames, status, dictID, 1, s);
-    else            launch_frame_walk_emit(d_src, srcSize, frames, blocks, (u8*)d->walkWs.p, s);
-    d->timer.mark("frame_walk", s);
-    { const size_t e = decode_lists(d, dd, d_dst, d_src, nFrames, nBlocks, nUnsized, dstCapacity, st, [] { return true; }); if (isErr(e)) return e; }
-    d->timer.finish();
-    if (st[kStErrKeyLo] != 0xFFFFFFFFu || st[kStErrKeyHi] != 0xFFFFFFFFu) return ZERR(st[kStErrKeyLo] & 0xFFFFu);   // the first failing block's first error
-    if (st[kStErr]) return ZERR(st[kStErr]);                  // regenerated sizes of unsized frames exceed the destination
-    if (nUnsized) return (size_t)((u64)st[kStActualLo] | ((u64)st[kStActualHi] << 32));
-    return (size_t)total;
-}
-
-// ---- a batch of independent entries, each decoded as the single call would decode it alone (ZSTDMI_decompressBatch) ----
-// The decoder's unit of parallelism is the block and its lists hold 64-bit offsets, so n entries are ONE run of the pipeline: the
-// batch walk (one lane per entry, the exact serial walk) lists every entry's frames and blocks side by side, with offsets relative to
-// the lowest source and the lowest destination pointer of the call, and block_prepass .. exec_matches run once over the merged lists.
-// Errors stay with their entry: header-stage errors and dstSize_tooSmall are found by the walk (such an entry emits no frames), later
-// ones are filed per block (report_error, kStBlockKeysLo) and folded per entry.  The host synchronises as often as for one single
-// call.  An entry that holds a frame without a content size (where its output goes is known only after decoding: frame_rescan is
-// global by construction) or more than kBatchAloneAbove compressed bytes (one lane walks an entry's block headers) is decoded alone
-// afterwards by decompress_device, and counted.
-constexpr u64 kBatchAloneAbove = (u64)4 << 20;
-// the batch's core over a device-resident entry table (d->batchIn, n entries; d->batchOut gets what the walk and the decoder make of
-// them): batch_walk_count -> batch_scan -> batch_walk_emit -> decode_lists -> batch_fold.  `readBack` enqueues the caller's copy of
-// whatever it wants of d->batchOut: called in front of each of the two host synchronisations that see final entries (after the
-// count: entries without frames are final; after the fold: all are).  -> 0, or the error of the whole run.
-static size_t decode_entries(ZSTD_DCtx* d, const DecodeDict& dd, const u8* srcBase, u8* dstBase, size_t dstSpan, u32 n, const std::function<bool()>& readBack)
-{
-    hipStream_t s = d->stream;
-    if (!d->status.ensure(kStWords * sizeof(u32))) return ZERR(kErrMemoryAllocation);
-    u32* status = (u32*)d->status.p;
-    const BatchEntryIn* dIn = (const BatchEntryIn*)d->batchIn.p; BatchEntryOut* dOut = (BatchEntryOut*)d->batchOut.p;
-    u32 init[kStWords] = {}; init[kStErrKeyLo] = 0xFFFFFFFFu; init[kStErrKeyHi] = 0xFFFFFFFFu;
-    u32 st[kStWords] = {};
-    if (hipMemcpyAsync(status, init, sizeof init, hipMemcpyHostToDevice, s) != hipSuccess) return ZERR(kErrGeneric);
-    launch_batch_walk_count(srcBase, dIn, dOut, n, dd.dictID, kBatchAloneAbove, status, s);
-    if (!readBack() ||
-        hipMemcpyAsync(st, status, sizeof st, hipMemcpyDeviceToHost, s) != hipSuccess) return ZERR(kErrGeneric);
-    if (hipStreamSynchronize(s) != hipSuccess) { (void)hipGetLastError(); return ZERR(kErrGeneric); }
-    if (st[kStErr]) return ZERR(st[kStErr]);
-    const u32 nFrames = st[kStFrames], nBlocks = st[kStBlocks];
-    const u64 total = (u64)st[kStTotalLo] | ((u64)st[kStTotalHi] << 32);
-    u32 keyWords[2] = {0, 0};
-    if (nFrames) {
-        if (!d->frames.ensure((size_t)nFrames * sizeof(FrameDesc)) || !d->blocks.ensure((size_t)nBlocks * sizeof(BlockDesc) + 64) ||
-            !d->scratch.ensure((size_t)total + (size_t)nFrames * kLitSkew + 256) || !d->slowFlags.ensure((size_t)nBlocks + 64) ||
-            !d->blockKeys.ensure((size_t)nBlocks * sizeof(u64) + 8)) return ZERR(kErrMemoryAllocation);
-        keyWords[0] = (u32)(uintptr_t)d->blockKeys.p; keyWords[1] = (u32)((u64)(uintptr_t)d->blockKeys.p >> 32);
-        if (hipMemsetAsync(d->blockKeys.p, 0xFF, (size_t)nBlocks * sizeof(u64), s) != hipSuccess ||
-            hipMemcpyAsync(status + kStBlockKeysLo, &keyWords[0], sizeof(u32), hipMemcpyHostToDevice, s) != hipSuccess ||
-            hipMemcpyAsync(status + kStBlockKeysHi, &keyWords[1], sizeof(u32), hipMemcpyHostToDevice, s) != hipSuccess) return ZERR(kErrGeneric);
-        launch_batch_walk_emit(srcBase, dIn, dOut, n, (FrameDesc*)d->frames.p, (BlockDesc*)d->blocks.p, s);
-        d->timer.mark("batch_walk", s);
-        const size_t e = decode_lists(d, dd, dstBase, srcBase, nFrames, nBlocks, 0, dstSpan, st, [&]() -> bool {
-            launch_batch_fold(dOut, n, (const u64*)d->blockKeys.p, s);
-            return readBack();
-        });
-        if (isErr(e)) return e;
-    }
-    return 0;
-}
-
-static size_t decompress_batch_impl(ZSTD_DCtx* d, const void* const* srcs, const size_t* srcSizes, size_t n, void* const* dsts, const size_t* dstCapacities, size_t* dstSizes)
-{
-    if (!d) return ZERR(kErrGeneric);
-    if (n == 0) { d->lastBatchAlone = 0; return 0; }
-    if (!srcs || !srcSizes || !dsts || !dstCapacities || !dstSizes) return ZERR(kErrGeneric);
-    if (n > 0xFFFFFFF0ull) return ZERR(kErrMemoryAllocation);
-    size_t e = dctx_bind(d); if (isErr(e)) return e;
-    if (d->workers.size() > 1 || d->pfx) return ZERR(kErrParameterUnsupported);      // (a pending ZSTD_DCtx_refPrefix serves one single call)
-    d->lastBatchAlone = 0;
-    e = dctx_sync_dictionary(d); if (isErr(e)) return e;
-    hipStream_t s = d->stream;
-    const DecodeDict dd = decode_dict(d);
-    // one base pointer each: the lowest source, the lowest destination
-    uintptr_t loS = ~(uintptr_t)0, loD = ~(uintptr_t)0, hiD = 0;
-    for (size_t i = 0; i < n; i++) {
-        if (srcSizes[i] && srcs[i] && (uintptr_t)srcs[i] < loS) loS = (uintptr_t)srcs[i];
-        if (dsts[i]) { const uintptr_t p = (uintptr_t)dsts[i]; if (p < loD) loD = p; if (p + dstCapacities[i] > hiD) hiD = p + dstCapacities[i]; }
-    }
-    if (loS == ~(uintptr_t)0) loS = 0;
-    if (loD == ~(uintptr_t)0) loD = 0;
-    std::vector<BatchEntryIn> hIn(n);
-    for (size_t i = 0; i < n; i++) {
-        const bool noSrc = srcSizes[i] && !srcs[i];           // (the single call: srcSize_wrong, below)
-        hIn[i].srcOff = (srcSizes[i] && !noSrc) ? (u64)((uintptr_t)srcs[i] - loS) : 0;
-        hIn[i].srcSize = noSrc ? 0 : (u64)srcSizes[i];
-        hIn[i].dstOff = dsts[i] ? (u64)((uintptr_t)dsts[i] - loD) : 0;
-        hIn[i].dstCap = dsts[i] ? (u64)dstCapacities[i] : 0;
-    }
-    if (!d->batchIn.ensure(n * sizeof(BatchEntryIn)) || !d->batchOut.ensure(n * sizeof(BatchEntryOut))) return ZERR(kErrMemoryAllocation);
-    BatchEntryOut* dOut = (BatchEntryOut*)d->batchOut.p;
-    std::vector<BatchEntryOut> hOut(n);
-    d->timer.begin(s);
-    if (hipMemcpyAsync(d->batchIn.p, hIn.data(), n * sizeof(BatchEntryIn), hipMemcpyHostToDevice, s) != hipSuccess) return ZERR(kErrGeneric);
-    e = decode_entries(d, dd, (const u8*)loS, (u8*)loD, (size_t)(hiD - loD), (u32)n, [&]() -> bool {
-        return hipMemcpyAsync(hOut.data(), dOut, n * sizeof(BatchEntryOut), hipMemcpyDeviceToHost, s) == hipSuccess;
-    });
-    if (isErr(e)) return e;
-    d->timer.finish();
-    for (size_t i = 0; i < n; i++) {
-        if (srcSizes[i] && !srcs[i]) { dstSizes[i] = ZERR(kErrSrcSizeWrong); continue; }
-        if (hOut[i].state != kBatchAlone) dstSizes[i] = (size_t)hOut[i].result;
-    }
-    for (size_t i = 0; i < n; i++) {
-        if ((srcSizes[i] && !srcs[i]) || hOut[i].state != kBatchAlone) continue;
-        dstSizes[i] = decompress_device(d, (u8*)dsts[i], dstCapacities[i], (const u8*)srcs[i], srcSizes[i]);
-        d->lastBatchAlone++;
-    }
-    return 0;
-}
-
-// ---- a byte range of a seekable stream (ZSTDMI_decompressRange) ----
-// The stream ends in a seek table (include/zstd_mi355x.h): one (compressed size, content size) pair per frame.  The host reads the
-// 9-byte footer (how long the table is); seek_select_kernel checks the rest of it and finds the entries whose content meets
-// [offset, offset + length) — one read-back of its summary words —; seek_emit_kernel turns those entries into the batch walk's table on
-// the device, and the batch's core (decode_entries) decodes them in one run: frames wholly inside the range straight to their place in
-// dst, the at most two frames the range cuts into an edge buffer, from which range_clip_kernel copies the wanted part.  An entry the
-// walk leaves to the single-call path (a frame without a content size, more than kBatchAloneAbove compressed bytes) is decoded by
-// decompress_device into the same place.  range_check_kernel holds every entry to the content size its table entry names.  A host
-// source is staged in two pieces only: the table, and the compressed bytes of the selected entries.
-// the 9-byte footer of the stream's seek table, read on the host (a device source: one small copy back) -> the entry count, the
-// entries' stride and the table's length, or the table's error
-static size_t read_seek_footer(ZSTD_DCtx* d, const void* src, size_t srcSize, bool srcDev, u32& N, u32& stride, u64& tableBytes)
-{
-    if (srcSize && !src) return ZERR(kErrSrcSizeWrong);
-    if (srcSize < 17) return ZERR(kErrPrefixUnknown);
-    hipStream_t s = d->stream;
-    auto rd32 = [](const u8* p) { return (u32)p[0] | ((u32)p[1] << 8) | ((u32)p[2] << 16) | ((u32)p[3] << 24); };
-    u8 foot[9];
-    if (srcDev) {
-        if (hipMemcpyAsync(foot, (const u8*)src + srcSize - 9, 9, hipMemcpyDeviceToHost, s) != hipSuccess) return ZERR(kErrGeneric);
-        if (hipStreamSynchronize(s) != hipSuccess) { (void)hipGetLastError(); return ZERR(kErrGeneric); }
-    } else memcpy(foot, (const u8*)src + srcSize - 9, 9);
-    if (rd32(foot + 5) != 0x8F92EAB1u) return ZERR(kErrPrefixUnknown);
-    if (foot[4] & 0x7C) return ZERR(kErrCorruption);                    // reserved descriptor bits
-    N = rd32(foot);
-    if (N > (1u << 27)) return ZERR(kErrCorruption);
-    stride = (foot[4] & 0x80) ? 12u : 8u;                               // (checksums, where the table has them, are skipped)
-    tableBytes = 17 + (u64)N * stride;
-    if (tableBytes > srcSize) return ZERR(kErrCorruption);
-    return 0;
-}
-
-static size_t decompress_range_impl(ZSTD_DCtx* d, void* dst, size_t dstCapacity, const void* src, size_t srcSize, unsigned long long offset, size_t length)
-{
-    size_t e = dctx_bind(d); if (isErr(e)) return e;
-    if (d->workers.size() > 1 || d->pfx) return ZERR(kErrParameterUnsupported);
-    d->lastRangeFrames = 0; d->lastRangeStaged = 0;
-    hipStream_t s = d->stream;
-    const bool srcDev = is_device_ptr(src), dstDev = dst ? is_device_ptr(dst) : false;
-    u32 N, stride; u64 tableBytes;
-    e = read_seek_footer(d, src, srcSize, srcDev, N, stride, tableBytes); if (isErr(e)) return e;
-    e = dctx_sync_dictionary(d); if (isErr(e)) return e;
-    const DecodeDict dd = decode_dict(d);
-    if (!d->seekSum.ensure(kSeekWords * sizeof(u64))) return ZERR(kErrMemoryAllocation);
-    u64* const sum = (u64*)d->seekSum.p;
-    const u8* tab = (const u8*)src + (srcSize - tableBytes);
-    if (!srcDev) {
-        if (!d->seekTab.ensure((size_t)tableBytes + 64)) return ZERR(kErrMemoryAllocation);
-        if (hipMemcpyAsync(d->seekTab.p, tab, (size_t)tableBytes, hipMemcpyHostToDevice, s) != hipSuccess) return ZERR(kErrGeneric);
-        tab = (const u8*)d->seekTab.p; d->lastRangeStaged += (long long)tableBytes;
-    }
-    d->timer.begin(s);
-    launch_seek_select(tab, tableBytes, N, stride, srcSize, offset, length, sum, s);
-    u64 sm[kSeekWords] = {};
-    if (hipMemcpyAsync(sm, sum, sizeof sm, hipMemcpyDeviceToHost, s) != hipSuccess) return ZERR(kErrGeneric);
-    if (hipStreamSynchronize(s) != hipSuccess) { (void)hipGetLastError(); return ZERR(kErrGeneric); }
-    d->timer.mark("seek_select", s);
-    if (sm[kSeekErr]) return ZERR((u32)sm[kSeekErr]);
-    const u64 total = sm[kSeekTotal];
-    const u64 returned = offset < total ? ((u64)length < total - offset ? (u64)length : total - offset) : 0;
-    if (returned > dstCapacity) return ZERR(kErrDstSizeTooSmall);
-    if (!returned) { d->timer.finish(); return 0; }
-    if (!dst) return ZERR(kErrDstBufferNull);
-    const u64 nMeet = sm[kSeekMeet];
-    if (!nMeet || sm[kSeekLast] < sm[kSeekFirst]) return ZERR(kErrCorruption);
-    const u32 first = (u32)sm[kSeekFirst], last = (u32)sm[kSeekLast], nSel = last - first + 1;
-    const u64 cLo = sm[kSeekCLo], cHi = sm[kSeekCHi], end = offset + returned;
-    const u64 dFirst = sm[kSeekDFirst], sizeFirst = sm[kSeekSizeFirst], dLast = sm[kSeekDLast], sizeLast = sm[kSeekSizeLast];
-    const bool cutFirst = dFirst < offset || dFirst + sizeFirst > end, cutLast = last != first && dLast + sizeLast > end;
-    const u64 slot1 = cutFirst ? ((sizeFirst + 255) & ~(u64)255) : 0, edgeBytes = slot1 + (cutLast ? sizeLast : 0);
-    if (edgeBytes && !d->edge.ensure((size_t)edgeBytes + 64)) return ZERR(kErrMemoryAllocation);
-    const u8* srcBase = (const u8*)src + cLo;
-    if (!srcDev) {              // only the selected frames travel
-        if (!d->stageSrc.ensure((size_t)(cHi - cLo) + 64)) return ZERR(kErrMemoryAllocation);
-        if (hipMemcpyAsync(d->stageSrc.p, (const u8*)src + cLo, (size_t)(cHi - cLo), hipMemcpyHostToDevice, s) != hipSuccess) return ZERR(kErrGeneric);
-        srcBase = (const u8*)d->stageSrc.p; d->lastRangeStaged += (long long)(cHi - cLo);
-    }
-    u8* d_dst = (u8*)dst;
-    if (!dstDev) { if (!d->stageDst.ensure((size_t)returned + 64)) return ZERR(kErrMemoryAllocation); d_dst = (u8*)d->stageDst.p; }
-    // one base pointer for the destinations, the lowest: dst or the edge buffer
-    const uintptr_t pD = (uintptr_t)d_dst, pE = edgeBytes ? (uintptr_t)d->edge.p : pD;
-    const uintptr_t lo = pD < pE ? pD : pE, hi = (pD + returned > pE + edgeBytes) ? pD + (uintptr_t)returned : pE + (uintptr_t)edgeBytes;
-    if (!d->batchIn.ensure((size_t)nSel * sizeof(BatchEntryIn)) || !d->batchOut.ensure((size_t)nSel * sizeof(BatchEntryOut))) return ZERR(kErrMemoryAllocation);
-    launch_seek_emit(tab, stride, first, nSel, dFirst, offset, (u64)(pD - lo), (u64)(pE - lo), slot1, cutFirst ? 1u : 0u, cutLast ? 1u : 0u, (BatchEntryIn*)d->batchIn.p, s);
-    d->timer.mark("seek_emit", s);
-    e = decode_entries(d, dd, srcBase, (u8*)lo, (size_t)(hi - lo), nSel, [] { return true; });
-    if (isErr(e)) return e;
-    launch_range_check((const BatchEntryIn*)d->batchIn.p, (const BatchEntryOut*)d->batchOut.p, nSel, sum, s);
-    if (hipMemcpyAsync(sm, sum, sizeof sm, hipMemcpyDeviceToHost, s) != hipSuccess) return ZERR(kErrGeneric);
-    if (hipStreamSynchronize(s) != hipSuccess) { (void)hipGetLastError(); return ZERR(kErrGeneric); }
-    if (sm[kSeekKey] != ~0ull) return ZERR((u32)(sm[kSeekKey] & 0xFFFFu));
-    if (sm[kSeekAlone]) {       // (rare: the entries come to the host only then)
-        std::vector<BatchEntryIn> hIn(nSel); std::vector<BatchEntryOut> hOut(nSel);
-        if (hipMemcpyAsync(hIn.data(), d->batchIn.p, (size_t)nSel * sizeof(BatchEntryIn), hipMemcpyDeviceToHost, s) != hipSuccess ||
-            hipMemcpyAsync(hOut.data(), d->batchOut.p, (size_t)nSel * sizeof(BatchEntryOut), hipMemcpyDeviceToHost, s) != hipSuccess) return ZERR(kErrGeneric);
-        if (hipStreamSynchronize(s) != hipSuccess) { (void)hipGetLastError(); return ZERR(kErrGeneric); }
-        for (u32 i = 0; i < nSel; ++i) {
-            if (hOut[i].state != kBatchAlone) continue;
-            const size_t r = decompress_device(d, (u8*)lo + hIn[i].dstOff, (size_t)hIn[i].dstCap, srcBase + hIn[i].srcOff, (size_t)hIn[i].srcSize);
-            if (isErr(r)) return r == ZERR(kErrDstSizeTooSmall) ? ZERR(kErrCorruption) : r;
-            if (r != hIn[i].dstCap) return ZERR(kErrCorruption);
-        }
-    }
-    if (edgeBytes) {
-        ClipJob j0 = {0, 0, 0}, j1 = {0, 0, 0};
-        if (cutFirst) { const u64 from = offset > dFirst ? offset - dFirst : 0, stop = dFirst + sizeFirst < end ? dFirst + sizeFirst : end;
-                        j0.from = from; j0.to = dFirst + from - offset; j0.len = stop - (dFirst + from); }
-        if (cutLast) { j1.from = slot1; j1.to = dLast - offset; j1.len = end - dLast; }
-        launch_range_clip(d_dst, (const u8*)d->edge.p, j0, j1, s);
-        d->timer.mark("range_clip", s);
-    }
-    if (!dstDev && hipMemcpyAsync(dst, d_dst, (size_t)returned, hipMemcpyDeviceToHost, s) != hipSuccess) return ZERR(kErrGeneric);
-    if (hipStreamSynchronize(s) != hipSuccess) { (void)hipGetLastError(); return ZERR(kErrGeneric); }
-    d->timer.finish();
-    d->lastRangeFrames = (int)nMeet;
-    return (size_t)returned;
-}
-
-
-// ---- many ranges of a seekable stream in one call (ZSTDMI_decompressRanges) ----
-// While one of these lives, the context's stage timer is off and keeps what it has recorded: the single-call paths that the pass hands
-// a frame or a range to begin the timer anew, and ZSTDMI_DCtx_getStageTimes is to show the pass.
-struct TimerPause {
-    StageTimer& t; const bool was; const int n;
-    explicit TimerPause(StageTimer& timer) : t(timer), was(timer.enabled), n(timer.n) { t.enabled = false; }
-    ~TimerPause() { t.enabled = was; t.n = n; }
-};
-// seek_index turns the table into prefix arrays once; ranges_select answers every range that needs no decoding and marks the entries
-// the others meet; ranges_plan makes ONE decode table of the touched entries — each decoded once, into its slot of the context's
-// arena, whatever number of ranges meets it — and decode_entries runs over it as over any batch.  An entry the walk leaves to the
-// single-call path is decoded by decompress_device into its slot; ranges_gather then checks each range's entries and copies its
-// bytes.  From a host source the table and the touched entries' compressed bytes travel, packed into one staging buffer.  A range of
-// more than kRangesAloneAbove bytes is handed to decompress_range_impl afterwards: it wants its frames decoded in place.
-static size_t decompress_ranges_impl(ZSTD_DCtx* d, const void* src, size_t srcSize, const unsigned long long* offsets, const size_t* lengths, size_t n,
-                                     void* const* dsts, const size_t* dstCapacities, size_t* dstSizes)
-{
-    if (!d) return ZERR(kErrGeneric);
-    if (n == 0) { d->lastRangesFrames = 0; d->lastRangesAlone = 0; d->lastRangesStaged = 0; return 0; }
-    if (!offsets || !lengths || !dsts || !dstCapacities || !dstSizes) return ZERR(kErrGeneric);
-    if (n > 0xFFFFFFF0ull) return ZERR(kErrMemoryAllocation);
-    size_t e = dctx_bind(d); if (isErr(e)) return e;
-    if (d->workers.size() > 1 || d->pfx) return ZERR(kErrParameterUnsupported);      // (a pending ZSTD_DCtx_refPrefix serves one single call)
-    d->lastRangesFrames = 0; d->lastRangesAlone = 0; d->lastRangesStaged = 0;
-    hipStream_t s = d->stream;
-    const bool srcDev = is_device_ptr(src);
-    u32 N, stride; u64 tableBytes;
-    e = read_seek_footer(d, src, srcSize, srcDev, N, stride, tableBytes); if (isErr(e)) return e;
-    e = dctx_sync_dictionary(d); if (isErr(e)) return e;
-    const DecodeDict dd = decode_dict(d);
-    const u32 nR = (u32)n;
-    if (!d->rangesWs.ensure(ranges_ws_bytes(N)) || !d->batchIn.ensure((size_t)N * sizeof(BatchEntryIn) + 64) ||
-        !d->rangesIn.ensure(n * sizeof(RangeIn)) || !d->rangesRec.ensure(n * sizeof(RangeRec)) || !d->rangesRes.ensure(n * sizeof(u64))) return ZERR(kErrMemoryAllocation);
-    const RangesWs ws = ranges_ws((u8*)d->rangesWs.p, N);
-    std::vector<RangeIn> hIn(n);
-    for (size_t i = 0; i < n; i++) { hIn[i].offset = offsets[i]; hIn[i].length = lengths[i]; hIn[i].dstCap = dstCapacities[i]; hIn[i].dst = (u64)(uintptr_t)dsts[i]; }
-    const u8* tab = (const u8*)src + (srcSize - tableBytes);
-    if (!srcDev) {
-        if (!d->seekTab.ensure((size_t)tableBytes + 64)) return ZERR(kErrMemoryAllocation);
-        if (hipMemcpyAsync(d->seekTab.p, tab, (size_t)tableBytes, hipMemcpyHostToDevice, s) != hipSuccess) return ZERR(kErrGeneric);
-        tab = (const u8*)d->seekTab.p; d->lastRangesStaged += (long long)tableBytes;
-    }
-    if (hipMemcpyAsync(d->rangesIn.p, hIn.data(), n * sizeof(RangeIn), hipMemcpyHostToDevice, s) != hipSuccess) return ZERR(kErrGeneric);
-    const RangeIn* dRanges = (const RangeIn*)d->rangesIn.p; RangeRec* dRecs = (RangeRec*)d->rangesRec.p;
-    d->timer.begin(s);
-    launch_seek_index(tab, tableBytes, N, stride, srcSize, ws, s);                                     d->timer.mark("seek_index", s);
-    launch_ranges_select(dRanges, dRecs, nR, N, ws, s);                                                d->timer.mark("ranges_select", s);
-    launch_ranges_plan(tab, N, stride, srcDev ? 1u : 0u, ws, (BatchEntryIn*)d->batchIn.p, s);          d->timer.mark("ranges_plan", s);
-    u64 sm[kRgWords] = {};
-    if (hipMemcpyAsync(sm, ws.sum, sizeof sm, hipMemcpyDeviceToHost, s) != hipSuccess) return ZERR(kErrGeneric);
-    if (hipStreamSynchronize(s) != hipSuccess) { (void)hipGetLastError(); return ZERR(kErrGeneric); }
-    if (sm[kRgErr]) { d->timer.finish(); return ZERR((u32)sm[kRgErr]); }
-    const u64 total = sm[kRgTotal], arenaBytes = sm[kRgArena], packedBytes = sm[kRgCompact], nRuns = sm[kRgRuns];
-    const u32 nTouched = (u32)sm[kRgTouched];
-    std::vector<u8> packed;     // (these four are sources of asynchronous copies: they live until the last synchronisation below)
-    std::vector<u64> runs;
-    std::vector<BatchEntryIn> eIn; std::vector<BatchEntryOut> eOut;
-    if (nTouched) {
-        if (!d->arena.ensure((size_t)arenaBytes + 64) || !d->batchOut.ensure((size_t)nTouched * sizeof(BatchEntryOut))) return ZERR(kErrMemoryAllocation);
-        const u8* srcBase = (const u8*)src;
-        if (!srcDev) {          // only the touched frames travel, in one copy
-            runs.resize(2 * (size_t)nRuns); packed.resize((size_t)packedBytes);
-            if (hipMemcpyAsync(runs.data(), ws.runs, runs.size() * sizeof(u64), hipMemcpyDeviceToHost, s) != hipSuccess) return ZERR(kErrGeneric);
-            if (hipStreamSynchronize(s) != hipSuccess) { (void)hipGetLastError(); return ZERR(kErrGeneric); }
-            if (pack_runs(runs.data(), (size_t)nRuns, (const u8*)src, srcSize, packed.data(), packed.size()) != packed.size()) return ZERR(kErrGeneric);
-            if (!d->stageSrc.ensure(packed.size() + 64)) return ZERR(kErrMemoryAllocation);
-            if (hipMemcpyAsync(d->stageSrc.p, packed.data(), packed.size(), hipMemcpyHostToDevice, s) != hipSuccess) return ZERR(kErrGeneric);
-            srcBase = (const u8*)d->stageSrc.p; d->lastRangesStaged += (long long)packed.size();
-        }
-        u64 someAlone = 0;
-        e = decode_entries(d, dd, srcBase, (u8*)d->arena.p, (size_t)arenaBytes, nTouched, [&]() -> bool {
-            launch_ranges_alone((const BatchEntryOut*)d->batchOut.p, nTouched, ws, s);
-            return hipMemcpyAsync(&someAlone, ws.sum + kRgAloneEntries, sizeof(u64), hipMemcpyDeviceToHost, s) == hipSuccess;
-        });
-        if (isErr(e)) return e;
-        if (someAlone) {        // (rare: the entries come to the host only then)
-            eIn.resize(nTouched); eOut.resize(nTouched);
-            if (hipMemcpyAsync(eIn.data(), d->batchIn.p, (size_t)nTouched * sizeof(BatchEntryIn), hipMemcpyDeviceToHost, s) != hipSuccess ||
-                hipMemcpyAsync(eOut.data(), d->batchOut.p, (size_t)nTouched * sizeof(BatchEntryOut), hipMemcpyDeviceToHost, s) != hipSuccess) return ZERR(kErrGeneric);
-            if (hipStreamSynchronize(s) != hipSuccess) { (void)hipGetLastError(); return ZERR(kErrGeneric); }
-            const TimerPause pause(d->timer);       // (decompress_device times itself: the pass keeps its own stages)
-            for (u32 i = 0; i < nTouched; ++i) {
-                if (eOut[i].state != kBatchAlone) continue;
-                eOut[i].result = (u64)decompress_device(d, (u8*)d->arena.p + eIn[i].dstOff, (size_t)eIn[i].dstCap, srcBase + eIn[i].srcOff, (size_t)eIn[i].srcSize);
-                if (hipMemcpyAsync((BatchEntryOut*)d->batchOut.p + i, &eOut[i], sizeof(BatchEntryOut), hipMemcpyHostToDevice, s) != hipSuccess) return ZERR(kErrGeneric);
-            }
-        }
-    }
-    std::vector<u64> hRes(n);
-    // what range i returns when nothing fails (ranges_select's rule, on the host: it has the total now)
-    auto returned = [&](size_t i) -> u64 { return offsets[i] < total ? ((u64)lengths[i] < total - offsets[i] ? (u64)lengths[i] : total - offsets[i]) : 0; };
-    u64 longest = 0;            // of the ranges the gather serves: the number of its slices
-    for (size_t i = 0; i < n; i++) {
-        const u64 ret = returned(i);
-        if (ret <= dstCapacities[i] && ret <= kRangesAloneAbove && dsts[i] && ret > longest) longest = ret;
-    }
-    launch_ranges_gather(dRanges, dRecs, (u64*)d->rangesRes.p, nR, (u32)((longest + kGatherSlice - 1) / kGatherSlice), ws, (const BatchEntryOut*)d->batchOut.p,
-                         (const u8*)d->arena.p, s);
-    d->timer.mark("ranges_gather", s);
-    if (hipMemcpyAsync(hRes.data(), d->rangesRes.p, n * sizeof(u64), hipMemcpyDeviceToHost, s) != hipSuccess) return ZERR(kErrGeneric);
-    if (hipStreamSynchronize(s) != hipSuccess) { (void)hipGetLastError(); return ZERR(kErrGeneric); }
-    d->timer.finish();
-    d->lastRangesFrames = (int)nTouched;
-    // the ranges that go alone, in range order
-    const long long staged = d->lastRangesStaged; long long stagedAlone = 0; int alone = 0;
-    const TimerPause pause(d->timer);               // (the stage times stay the gathered pass's)
-    for (size_t i = 0; i < n; i++) {
-        const u64 ret = returned(i);
-        if (ret > dstCapacities[i] || !dsts[i] || ret <= kRangesAloneAbove) { dstSizes[i] = (size_t)hRes[i]; continue; }
-        dstSizes[i] = decompress_range_impl(d, dsts[i], dstCapacities[i], src, srcSize, offsets[i], lengths[i]);
-        stagedAlone += d->lastRangeStaged; alone++;
-    }
-    d->lastRangesAlone = alone; d->lastRangesStaged = staged + stagedAlone;
-    return 0;
-}
-
-static size_t decompress_multi(ZSTD_DCtx* d, void* dst, size_t dstCapacity, const void* src, size_t srcSize);
-// ZSTD_DCtx_refPrefix (U/ZstdDecompress.cs:2164-2202): the pending prefix becomes this call's raw-content dictionary — a device prefix
-// where it lies, a host prefix staged to HBM — and is consumed, whatever the call returns (PrefixUse's destructor)
-struct PrefixUse {
-    ZSTD_DCtx* d;
-    explicit PrefixUse(ZSTD_DCtx* dd) : d(dd) {}
-    size_t begin()
-    {
-        if (!d->pfx) return 0;
-        if (d->workers.size() > 1) return ZERR(kErrParameterUnsupported);
-        if (is_device_ptr(d->pfx)) { d->pfxDev = (const u8*)d->pfx; return 0; }
-        if (!d->pfxStage.ensure(d->pfxSize + 64)) return ZERR(kErrMemoryAllocation);
-        if (hipMemcpyAsync(d->pfxStage.p, d->pfx, d->pfxSize, hipMemcpyHostToDevice, d->stream) != hipSuccess) return ZERR(kErrGeneric);
-        d->pfxDev = (const u8*)d->pfxStage.p;
-        return 0;
-    }
-    ~PrefixUse() { d->pfx = nullptr; d->pfxSize = 0; d->pfxDev = nullptr; }
-};
-static size_t ZSTDMI_decompressDevice_impl(ZSTD_DCtx* d, void* d_dst, size_t dstCapacity, const void* d_src, size_t srcSize)
-{
-    if (!d) return ZERR(kErrGeneric);
-    PrefixUse use(d);
-    size_t e = dctx_bind(d); if (isErr(e)) return e;
-    e = use.begin(); if (isErr(e)) return e;
-    if (srcSize && !d_src) return ZERR(kErrSrcSizeWrong);
-    if (d->workers.size() > 1 && srcSize) return decompress_multi(d, d_dst, dstCapacity, d_src, srcSize);
-    return decompress_device(d, (u8*)d_dst, dstCapacity, (const u8*)d_src, srcSize);
-}
-
-static size_t ZSTD_decompressDCtx_impl(ZSTD_DCtx* d, void* dst, size_t dstCapacity, const void* src, size_t srcSize)
-{
-    if (!d) return ZERR(kErrGeneric);
-    PrefixUse use(d);
-    size_t e = dctx_bind(d); if (isErr(e)) return e;
-    e = use.begin(); if (isErr(e)) return e;
-    if (srcSize && !src) return ZERR(kErrSrcSizeWrong);
-    if (srcSize == 0) return 0;
-    if (d->workers.size() > 1) return decompress_multi(d, dst, dstCapacity, src, srcSize);
-    const bool srcDev = is_device_ptr(src), dstDev = dst ? is_device_ptr(dst) : false;
-    const u8* d_src = (const u8*)src; u8* d_dst = (u8*)dst;
-    if (!srcDev) {
-        if (!d->stageSrc.ensure(srcSize + 64)) return ZERR(kErrMemoryAllocation);
-        if (hipMemcpyAsync(d->stageSrc.p, src, srcSize, hipMemcpyHostToDevice, d->stream) != hipSuccess) return ZERR(kErrGeneric);
-        d_src = (const u8*)d->stageSrc.p;
-    }
-    if (!dstDev) {
-        if (!d->stageDst.ensure(dstCapacity + 64)) return ZERR(kErrMemoryAllocation);
-        d_dst = (u8*)d->stageDst.p;
-    }
-    const size_t r = decompress_device(d, d_dst, dstCapacity, d_src, srcSize);
-    if (isErr(r)) return r;
-    if (!dstDev && r) {
-        if (hipMemcpyAsync(dst, d_dst, r, hipMemcpyDeviceToHost, d->stream) != hipSuccess) return ZERR(kErrGeneric);
-        if (hipStreamSynchronize(d->stream) != hipSuccess) return ZERR(kErrGeneric);
-    }
-    return r;
-}
-
 // ---------------- several devices behind one context (SURVEY.md section 8 e; ZSTDMI_*_setDevices) ----------------
 // north_star: "chunks partition naturally across the 8 GPUs of one node".  Frames are the independent unit (a match never leaves its
 // frame), so a call's frames are dealt to the device workers in contiguous shares: every worker stages its share on its own device,
@@ -1831,13 +856,6 @@ static size_t ZSTD_decompressDCtx_impl(ZSTD_DCtx* d, void* dst, size_t dstCapaci
 // caller's buffer one behind the other.  What is written does not depend on the number of workers: shares are cut on frame
 // boundaries (on probe-group boundaries when the sparse-input probe runs), parameters are resolved for the whole range, and the probe's
 // plan is made once over all shares' counts.  No collective: the only exchange is the final copy (device to host, or peer to peer).
-static size_t copy_any(void* dst, const void* src, size_t n, hipStream_t s)
-{
-    if (!n) return 0;
-    if (hipMemcpyAsync(dst, src, n, hipMemcpyDefault, s) != hipSuccess) { (void)hipGetLastError(); return ZERR(kErrGeneric); }
-    return 0;
-}
-
 static size_t compress_multi(ZSTD_CCtx* c, const CallParams& cp, void* dst, size_t dstCapacity, const void* src, size_t srcSize)
 {
     { const size_t e = check_call_params(cp); if (isErr(e)) return e; }
@@ -1914,7 +932,7 @@ static size_t compress_multi(ZSTD_CCtx* c, const CallParams& cp, void* dst, size
         ZSTD_CCtx* w = c->workers[i];
         if (isErr(cctx_bind(w))) return;
         size_t e = copy_any((u8*)dst + at[i], w->stageDst.p, produced[i], w->stream);
-        if (!isErr(e) && hipStreamSynchronize(w->stream) != hipSuccess) { (void)hipGetLastError(); e = ZERR(kErrGeneric); }
+        if (!isErr(e)) e = stream_wait(w->stream);
         if (isErr(e)) res[i] = e;
     });
     if (!ok) return ZERR(kErrMemoryAllocation);
@@ -1924,78 +942,6 @@ static size_t compress_multi(ZSTD_CCtx* c, const CallParams& cp, void* dst, size
     for (int i = 0; i < w0->nStages; i++) { c->stageMs[i] = w0->stageMs[i]; c->stageNames[i] = w0->stageNames[i]; }
     c->lastChunks = 0;
     (void)cctx_bind(c);
-    return total;
-}
-
-// decompress: the frames of the input (a host-side header walk) in contiguous shares by compressed size
-static size_t decompress_multi(ZSTD_DCtx* d, void* dst, size_t dstCapacity, const void* src, size_t srcSize)
-{
-    const size_t W = d->workers.size();
-    bool ok = true;
-    std::vector<u8> tmp;
-    const u8* const ip = host_view(src, srcSize, tmp);
-    if (!ip) return ZERR(kErrGeneric);
-    struct Piece { size_t off, len; unsigned long long bound; bool sized; };
-    std::vector<Piece> frames;
-    { size_t pos = 0;
-      while (pos < srcSize) {
-          unsigned long long b = 0; const size_t fs = host_frame_size_info(ip + pos, srcSize - pos, &b);
-          if (isErr(fs)) { if (frames.empty() || fs != ZERR(kErrPrefixUnknown)) return fs; return ZERR(kErrSrcSizeWrong); }     // as ZSTD_decompressMultiFrame: garbage behind a frame
-          Piece p; p.off = pos; p.len = fs; p.bound = b;
-          p.sized = ZSTD_getFrameContentSize_impl(ip + pos, fs) < (unsigned long long)0 - 2;
-          frames.push_back(p); pos += fs;
-      } }
-    // shares of about equal compressed size
-    std::vector<size_t> lo(W + 1, frames.size());
-    { size_t acc = 0, k = 0; lo[0] = 0;
-      for (size_t f = 0; f < frames.size(); ++f) { while (k + 1 < W && acc >= srcSize * (k + 1) / W) lo[++k] = f; acc += frames[f].len; }
-      while (k + 1 < W) lo[++k] = frames.size(); lo[W] = frames.size(); }
-    std::vector<size_t> res(W, 0), got(W, 0);
-    std::vector<unsigned long long> bound(W, 0);
-    bool allSized = true;
-    for (size_t i = 0; i < W; ++i) for (size_t f = lo[i]; f < lo[i + 1]; ++f) { bound[i] += frames[f].bound; allSized = allSized && frames[f].sized; }
-    if (allSized) { unsigned long long t = 0; for (size_t i = 0; i < W; ++i) t += bound[i]; if (t > dstCapacity) return ZERR(kErrDstSizeTooSmall); }
-    { const size_t e = dctx_sync_dictionary(d); if (isErr(e)) return e; }
-    for (ZSTD_DCtx* w : d->workers) {
-        w->litDecoder = d->litDecoder; w->originMode = d->originMode; w->overlapMode = d->overlapMode; w->timer.enabled = d->timer.enabled;
-        if (w->dictGen != d->dictGen) { w->dictHost = d->dictHost; w->dictFormatted = d->dictFormatted; w->dictDirty = true; w->dictGen = d->dictGen; }
-    }
-    std::vector<size_t> at(W, 0);
-    for (size_t i = 1; i < W; ++i) at[i] = at[i - 1] + (size_t)bound[i - 1];       // exact when every frame has a content size
-    ok = run_on_workers(W, [&](size_t i) {
-        ZSTD_DCtx* w = d->workers[i];
-        size_t e = dctx_bind(w); if (isErr(e)) { res[i] = e; return; }
-        if (lo[i] == lo[i + 1]) return;
-        const size_t a = frames[lo[i]].off, n = frames[lo[i + 1] - 1].off + frames[lo[i + 1] - 1].len - a;
-        if (!w->stageSrc.ensure(n + 64) || !w->stageDst.ensure((size_t)bound[i] + 64)) { res[i] = ZERR(kErrMemoryAllocation); return; }
-        e = copy_any(w->stageSrc.p, ip + a, n, w->stream); if (isErr(e)) { res[i] = e; return; }
-        const size_t r = decompress_device(w, (u8*)w->stageDst.p, (size_t)bound[i], (const u8*)w->stageSrc.p, n);
-        if (isErr(r)) { res[i] = r; return; }
-        got[i] = r;
-        if (allSized) {         // its place in the caller's buffer is known
-            e = copy_any((u8*)dst + at[i], w->stageDst.p, r, w->stream);
-            if (!isErr(e) && hipStreamSynchronize(w->stream) != hipSuccess) { (void)hipGetLastError(); e = ZERR(kErrGeneric); }
-            if (isErr(e)) res[i] = e;
-        }
-    });
-    if (!ok) return ZERR(kErrMemoryAllocation);
-    for (size_t i = 0; i < W; ++i) if (isErr(res[i])) return res[i];          // the first share's error is the first frame's
-    size_t total = 0;
-    for (size_t i = 0; i < W; ++i) total += got[i];
-    if (!allSized) {            // frames without a content size: the shares' places follow from what they regenerated
-        if (total > dstCapacity) return ZERR(kErrDstSizeTooSmall);
-        size_t pos = 0;
-        for (size_t i = 0; i < W; ++i) {
-            ZSTD_DCtx* w = d->workers[i];
-            if (isErr(dctx_bind(w))) return ZERR(kErrGeneric);
-            const size_t e = copy_any((u8*)dst + pos, w->stageDst.p, got[i], w->stream); if (isErr(e)) return e;
-            if (hipStreamSynchronize(w->stream) != hipSuccess) { (void)hipGetLastError(); return ZERR(kErrGeneric); }
-            pos += got[i];
-        }
-    }
-    d->timer.n = d->workers[0]->timer.n;
-    for (int i = 0; i < d->timer.n; i++) { d->timer.ms[i] = d->workers[0]->timer.ms[i]; d->timer.names[i] = d->workers[0]->timer.names[i]; }
-    (void)dctx_bind(d);
     return total;
 }
 
@@ -2097,104 +1043,11 @@ static size_t ZSTD_compressStream2_impl(ZSTD_CCtx* c, ZSTD_outBuffer* output, ZS
     return left;
 }
 
-// ZSTD_decompressStream (S/Decompressor.cs:97-106 <- S/DecompressionStream.cs:88-162; U/ZstdDecompress.cs:2816-3205).
-// Compressed bytes are collected until at least one whole frame is present (frame sizes come from the block headers,
-// ZSTD_findFrameSizeInfo); all whole frames collected so far are decoded in one GPU batch into a pending buffer that is
-// handed out as the caller's output space allows.  Returns 0 when a frame boundary is reached and everything is flushed,
-// an error, or a non-zero hint.  As in the reference (U/ZstdDecompress.cs:3170-3194) the last input byte is held hostage
-// while decoded data is still pending, so that a caller who stops feeding at end of input still gets called back.
-static size_t dstream_drain(ZSTD_DCtx* d, ZSTD_outBuffer* o)
-{
-    const size_t avail = d->dOut.size() - d->dOutPos, room = o->size - o->pos;
-    const size_t n = avail < room ? avail : room;
-    if (n) { memcpy((u8*)o->dst + o->pos, d->dOut.data() + d->dOutPos, n); o->pos += n; d->dOutPos += n; }
-    if (d->dOutPos == d->dOut.size()) { d->dOut.clear(); d->dOutPos = 0; }
-    return d->dOut.size() - d->dOutPos;
-}
-static size_t ZSTD_decompressStream_impl(ZSTD_DCtx* d, ZSTD_outBuffer* output, ZSTD_inBuffer* input)
-{
-    if (!d || !output || !input) return ZERR(kErrGeneric);
-    if (output->pos > output->size) return ZERR(104);
-    if (input->pos > input->size) return ZERR(105);
-    if (input->size > input->pos && !input->src) return ZERR(kErrSrcSizeWrong);
-    if (output->size > output->pos && !output->dst) return ZERR(kErrDstBufferNull);
-    if (d->pfx) return ZERR(kErrParameterUnsupported);         // (a referenced prefix serves one single call)
-    if (d->hostage && input->pos < input->size) { input->pos++; d->hostage = false; }       // that byte was consumed earlier
-    size_t pending = dstream_drain(d, output);
-    if (!pending) {
-        const size_t n = input->size - input->pos;
-        if (n) { d->dIn.insert(d->dIn.end(), (const u8*)input->src + input->pos, (const u8*)input->src + input->size); input->pos = input->size; }
-        size_t whole = 0; unsigned long long bound = 0;
-        while (whole < d->dIn.size()) {
-            unsigned long long b = 0;
-            // ZSTD_d_windowLogMax bounds what a streamed frame may ask for (U/ZstdDecompress.cs:2966-2969, with the 1 KiB floor of
-            // :2965): checked as soon as the header is there, before the frame is collected or anything is sized from it
-            { u64 w = host_frame_window(d->dIn.data() + whole, d->dIn.size() - whole);
-              if (w && w < 1024) w = 1024;
-              if (w > (1ull << d->windowLogMax)) { d->dIn.clear(); return ZERR(kErrWindowTooLarge); } }
-            const size_t fs = host_frame_size_info(d->dIn.data() + whole, d->dIn.size() - whole, &b);
-            if (isErr(fs)) { if (fs == ZERR(kErrSrcSizeWrong)) break; return fs; }          // incomplete frame: wait for more input
-            whole += fs; bound += b;
-        }
-        if (whole) {
-            d->dOut.resize((size_t)bound); d->dOutPos = 0;
-            const size_t r = ZSTD_decompressDCtx_impl(d, d->dOut.data(), d->dOut.size(), d->dIn.data(), whole);
-            if (isErr(r)) { d->dOut.clear(); return r; }
-            d->dOut.resize(r);
-            d->dIn.erase(d->dIn.begin(), d->dIn.begin() + (ptrdiff_t)whole);
-            pending = dstream_drain(d, output);
-        }
-    }
-    if (pending) {
-        if (!d->hostage && input->pos == input->size && input->pos > 0) { input->pos--; d->hostage = true; }
-        return 1;
-    }
-    if (d->hostage) return 1;                                  // flushed, but the hostage byte has not been handed back yet
-    return d->dIn.empty() ? 0 : 1;                             // 0 only on a frame boundary
-}
-
 // ---------------- extensions ----------------
 int ZSTDMI_deviceCount(void) { return device_count(); }
-size_t ZSTDMI_CCtx_setDevice(ZSTD_CCtx* c, int device) { if (!c) return ZERR(kErrGeneric); if (c->deviceOk && device != c->device) return ZERR(kErrStageWrong); c->device = device; return 0; }
-size_t ZSTDMI_DCtx_setDevice(ZSTD_DCtx* d, int device) { if (!d) return ZERR(kErrGeneric); if (d->deviceOk && device != d->device) return ZERR(kErrStageWrong); d->device = device; return 0; }
-// devices: one worker per entry (an ordinal may repeat: several workers share that device); n <= 1 = back to the context's own device
-size_t ZSTDMI_CCtx_setDevices(ZSTD_CCtx* c, const int* devices, int n)
-{
-    if (!c || n < 0 || n > 64 || (n && !devices)) return ZERR(kErrParameterOutOfBound);
-    for (int i = 0; i < n; ++i) if (devices[i] < 0 || devices[i] >= device_count()) return ZERR(kErrInitMissing);
-    for (ZSTD_CCtx* w : c->workers) (void)ZSTD_freeCCtx(w);
-    c->workers.clear();
-    if (n <= 1) { if (n == 1) return ZSTDMI_CCtx_setDevice(c, devices[0]); return 0; }
-    for (int i = 0; i < n; ++i) {
-        ZSTD_CCtx* w = ZSTD_createCCtx();
-        if (!w) return ZERR(kErrMemoryAllocation);
-        w->device = devices[i]; w->dictGen = ~(u64)0;
-        c->workers.push_back(w);
-    }
-    return 0;
-}
-size_t ZSTDMI_DCtx_setDevices(ZSTD_DCtx* d, const int* devices, int n)
-{
-    if (!d || n < 0 || n > 64 || (n && !devices)) return ZERR(kErrParameterOutOfBound);
-    for (int i = 0; i < n; ++i) if (devices[i] < 0 || devices[i] >= device_count()) return ZERR(kErrInitMissing);
-    for (ZSTD_DCtx* w : d->workers) (void)ZSTD_freeDCtx(w);
-    d->workers.clear();
-    if (n <= 1) { if (n == 1) return ZSTDMI_DCtx_setDevice(d, devices[0]); return 0; }
-    for (int i = 0; i < n; ++i) {
-        ZSTD_DCtx* w = ZSTD_createDCtx();
-        if (!w) return ZERR(kErrMemoryAllocation);
-        w->device = devices[i]; w->dictGen = ~(u64)0;
-        d->workers.push_back(w);
-    }
-    return 0;
-}
-size_t ZSTDMI_CCtx_setStream(ZSTD_CCtx* c, void* st) { size_t e = cctx_bind(c); if (isErr(e)) return e; c->stream = st ? (hipStream_t)st : c->ownStream; return 0; }
-size_t ZSTDMI_DCtx_setStream(ZSTD_DCtx* d, void* st) { size_t e = dctx_bind(d); if (isErr(e)) return e; d->stream = st ? (hipStream_t)st : d->ownStream; return 0; }
-int ZSTDMI_debugLastWalkSerial(const ZSTD_DCtx* d) { return d ? (int)d->lastWalkSerial : -1; }
-size_t ZSTDMI_DCtx_setExecWaves(ZSTD_DCtx* d, unsigned waves) { if (!d || (waves != 0 && waves != 1 && waves != 2 && waves != 4 && waves != 8 && waves != 16)) return ZERR(kErrParameterOutOfBound); d->execWaves = (int)waves; return 0; }
-size_t ZSTDMI_DCtx_setOverlap(ZSTD_DCtx* d, unsigned mode) { if (!d || mode > 2) return ZERR(kErrParameterOutOfBound); d->overlapMode = (int)mode; return 0; }
-size_t ZSTDMI_DCtx_setLongFrames(ZSTD_DCtx* d, unsigned mode) { if (!d || mode > 2) return ZERR(kErrParameterOutOfBound); d->originMode = (int)mode; return 0; }
-size_t ZSTDMI_DCtx_setLiteralDecoder(ZSTD_DCtx* d, unsigned mode) { if (!d || mode > 3) return ZERR(kErrParameterOutOfBound); d->litDecoder = mode; return 0; }
+size_t ZSTDMI_CCtx_setDevice(ZSTD_CCtx* c, int device) { return ctx_set_device(c, device); }
+size_t ZSTDMI_CCtx_setDevices(ZSTD_CCtx* c, const int* devices, int n) { return ctx_set_devices(c, devices, n, ZSTD_createCCtx, ZSTD_freeCCtx); }
+size_t ZSTDMI_CCtx_setStream(ZSTD_CCtx* c, void* st) { return ctx_set_stream(c, st, cctx_bind); }
 size_t ZSTDMI_CCtx_setPassChunks(ZSTD_CCtx* c, unsigned chunks) { if (!c || chunks == 0 || chunks > (1u << 20)) return ZERR(kErrParameterOutOfBound); c->passChunks = chunks; return 0; }
 // bytes: 0 = independent 64 KiB frames; > 0 = cross-chunk history of that many bytes per block (rounded to 4 KiB, at most 48 KiB);
 // < 0 = by level.  frameBytes: content of one multi-block frame (64 KiB .. 16 MiB), 0 = keep.
@@ -2207,19 +1060,11 @@ size_t ZSTDMI_CCtx_setSeekTable(ZSTD_CCtx* c, unsigned mode) { if (!c) return ZE
 size_t ZSTDMI_seekTableBound(size_t srcSize) { return seek_table_bound(srcSize); }
 size_t ZSTDMI_CCtx_setParser(ZSTD_CCtx* c, unsigned mode) { if (!c || mode > 1) return ZERR(kErrParameterOutOfBound); c->parser = mode; return 0; }
 size_t ZSTDMI_CCtx_setProfiling(ZSTD_CCtx* c, int en) { if (!c) return ZERR(kErrGeneric); c->timer.enabled = en != 0; return 0; }
-size_t ZSTDMI_DCtx_setProfiling(ZSTD_DCtx* d, int en) { if (!d) return ZERR(kErrGeneric); d->timer.enabled = en != 0; return 0; }
 int ZSTDMI_CCtx_getStageTimes(const ZSTD_CCtx* c, float* ms, const char** names, int cap)
 {
     if (!c) return 0;
     int n = c->nStages < cap ? c->nStages : cap;
     for (int i = 0; i < n; i++) { if (ms) ms[i] = c->stageMs[i]; if (names) names[i] = c->stageNames[i]; }
-    return n;
-}
-int ZSTDMI_DCtx_getStageTimes(const ZSTD_DCtx* d, float* ms, const char** names, int cap)
-{
-    if (!d) return 0;
-    int n = d->timer.n < cap ? d->timer.n : cap;
-    for (int i = 0; i < n; i++) { if (ms) ms[i] = d->timer.ms[i]; if (names) names[i] = d->timer.names[i]; }
     return n;
 }
 
@@ -2254,8 +1099,7 @@ size_t ZSTDMI_debugEntropyBlock(ZSTD_CCtx* c, void* dst, size_t dstCapacity, con
     { const u32 plainReps[3] = { 1, 4, 8 };
       const Resolved rs = resolve_call(sticky_params(c), srcSize, kChunkSize);
       launch_seq_encode((Seq*)c->seqs.p, (ChunkMeta*)c->meta.p, (u8*)c->slots.p, 1, rs.cp.strategy < kStratGreedy ? rs.cp.strategy : (u32)kStratGreedy, 0, 0, 0, 0, plainReps, 0, kChunkSize, 0, s); }
-    if (hipMemcpyAsync(&m, c->meta.p, sizeof m, hipMemcpyDeviceToHost, s) != hipSuccess) return ZERR(kErrGeneric);
-    if (hipStreamSynchronize(s) != hipSuccess) { (void)hipGetLastError(); return ZERR(kErrGeneric); }
+    if (isErr(dev_read(&m, c->meta.p, sizeof m, s))) return ZERR(kErrGeneric);
     if (m.blockType != 2) return 0;
     if (m.bodySize > dstCapacity) return ZERR(kErrDstSizeTooSmall);
     if (hipMemcpy(dst, (u8*)c->slots.p + m.fhSize + 3, m.bodySize, hipMemcpyDeviceToHost) != hipSuccess) return ZERR(kErrGeneric);
@@ -2276,58 +1120,14 @@ size_t ZSTDMI_debugPoisonedChunk(ZSTD_CCtx* c, unsigned nbSeq, unsigned litSize,
     launch_huf_encode((u8*)c->lits.p, (ChunkMeta*)c->meta.p, (HufTable*)c->tables.p, (u8*)c->slots.p, nullptr, nullptr, 0, 1, (const u8*)c->lits.p, kChunkSize, s);
     { const u32 plainReps[3] = { 1, 4, 8 };
       launch_seq_encode((Seq*)c->seqs.p, (ChunkMeta*)c->meta.p, (u8*)c->slots.p, 1, 1, 0, 1, 0, 0, plainReps, 0, kChunkSize, srcSize < kChunkSize ? srcSize : kChunkSize, s); }
-    if (hipMemcpyAsync(&m, c->meta.p, sizeof m, hipMemcpyDeviceToHost, s) != hipSuccess) return ZERR(kErrGeneric);
-    if (hipStreamSynchronize(s) != hipSuccess) { (void)hipGetLastError(); return ZERR(kErrGeneric); }
+    if (isErr(dev_read(&m, c->meta.p, sizeof m, s))) return ZERR(kErrGeneric);
     c->lastChunks = 0;
     return m.outSize;
 }
 
 // ---------------- entry points whose host-side containers may throw: guarded (see guarded()) ----------------
 size_t ZSTD_CCtx_loadDictionary(ZSTD_CCtx* c, const void* dict, size_t dictSize) { return guarded([&] { return ZSTD_CCtx_loadDictionary_impl(c, dict, dictSize); }); }
-size_t ZSTD_DCtx_loadDictionary(ZSTD_DCtx* d, const void* dict, size_t dictSize) { return guarded([&] { return ZSTD_DCtx_loadDictionary_impl(d, dict, dictSize); }); }
-size_t ZSTD_DCtx_refPrefix(ZSTD_DCtx* d, const void* prefix, size_t prefixSize)
-{
-    if (!d) return ZERR(kErrGeneric);
-    if (prefix && prefixSize > (size_t)1 << 30) return ZERR(kErrParameterUnsupported);
-    // ZSTD_clearAllDicts: a loaded dictionary and an earlier prefix are gone
-    d->dictGen++; d->dictHost.clear(); d->dictFormatted = false; d->dictDirty = true;
-    d->pfx = nullptr; d->pfxSize = 0;
-    if (prefix && prefixSize) { d->pfx = prefix; d->pfxSize = prefixSize; }
-    return 0;
-}
-size_t ZSTD_findFrameCompressedSize(const void* src, size_t srcSize) { return guarded([&] { return ZSTD_findFrameCompressedSize_impl(src, srcSize); }); }
-size_t ZSTD_decompressDCtx(ZSTD_DCtx* d, void* dst, size_t dstCapacity, const void* src, size_t srcSize) { return guarded([&] { return ZSTD_decompressDCtx_impl(d, dst, dstCapacity, src, srcSize); }); }
-size_t ZSTDMI_decompressBatch(ZSTD_DCtx* d, const void* const* srcs, const size_t* srcSizes, size_t n, void* const* dsts, const size_t* dstCapacities, size_t* dstSizes)
-{
-    return guarded([&] { return decompress_batch_impl(d, srcs, srcSizes, n, dsts, dstCapacities, dstSizes); });
-}
-int ZSTDMI_debugLastBatchAloneD(const ZSTD_DCtx* d) { return d ? d->lastBatchAlone : -1; }
-size_t ZSTDMI_decompressRange(ZSTD_DCtx* d, void* dst, size_t dstCapacity, const void* src, size_t srcSize, unsigned long long offset, size_t length)
-{
-    if (!d) return ZERR(kErrGeneric);
-    return guarded([&] { return decompress_range_impl(d, dst, dstCapacity, src, srcSize, offset, length); });
-}
-int ZSTDMI_debugLastRangeFrames(const ZSTD_DCtx* d) { return d ? d->lastRangeFrames : -1; }
-long long ZSTDMI_debugLastRangeStaged(const ZSTD_DCtx* d) { return d ? d->lastRangeStaged : -1; }
-size_t ZSTDMI_decompressRanges(ZSTD_DCtx* d, const void* src, size_t srcSize, const unsigned long long* offsets, const size_t* lengths, size_t n,
-                               void* const* dsts, const size_t* dstCapacities, size_t* dstSizes)
-{
-    return guarded([&] { return decompress_ranges_impl(d, src, srcSize, offsets, lengths, n, dsts, dstCapacities, dstSizes); });
-}
-int ZSTDMI_debugLastRangesFrames(const ZSTD_DCtx* d) { return d ? d->lastRangesFrames : -1; }
-int ZSTDMI_debugLastRangesAlone(const ZSTD_DCtx* d) { return d ? d->lastRangesAlone : -1; }
-long long ZSTDMI_debugLastRangesStaged(const ZSTD_DCtx* d) { return d ? d->lastRangesStaged : -1; }
-size_t ZSTDMI_decompressDevice(ZSTD_DCtx* d, void* d_dst, size_t dstCapacity, const void* d_src, size_t srcSize) { return guarded([&] { return ZSTDMI_decompressDevice_impl(d, d_dst, dstCapacity, d_src, srcSize); }); }
 size_t ZSTD_compressStream2(ZSTD_CCtx* c, ZSTD_outBuffer* output, ZSTD_inBuffer* input, int endOp) { return guarded([&] { return ZSTD_compressStream2_impl(c, output, input, endOp); }); }
-size_t ZSTD_decompressStream(ZSTD_DCtx* d, ZSTD_outBuffer* output, ZSTD_inBuffer* input) { return guarded([&] { return ZSTD_decompressStream_impl(d, output, input); }); }
-unsigned long long ZSTD_decompressBound(const void* src, size_t srcSize)
-{
-    try { return ZSTD_decompressBound_impl(src, srcSize); } catch (...) { return (unsigned long long)0 - 2; }      /* ZSTD_CONTENTSIZE_ERROR */
-}
-unsigned long long ZSTD_getFrameContentSize(const void* src, size_t srcSize)
-{
-    try { return ZSTD_getFrameContentSize_impl(src, srcSize); } catch (...) { return (unsigned long long)0 - 2; }      /* ZSTD_CONTENTSIZE_ERROR */
-}
 
 } // extern "C"
 
@@ -2445,8 +1245,7 @@ static size_t compress_entries(ZSTD_CCtx* c, const CallParams& cp, const u8* con
                 launch_gather(stage, stagedBytes, slots, meta, offsets, base, span, nCh, cb, s);          c->timer.mark("gather", s);
             }
             got.resize(nEnt);
-            if (hipMemcpyAsync(got.data(), dGot, (size_t)nEnt * 8, hipMemcpyDeviceToHost, s) != hipSuccess) return ZERR(kErrGeneric);
-            if (hipStreamSynchronize(s) != hipSuccess) { (void)hipGetLastError(); return ZERR(kErrGeneric); }
+            if (isErr(dev_read(got.data(), dGot, (size_t)nEnt * 8, s))) return ZERR(kErrGeneric);
             c->timer.finish(); c->nStages = c->timer.n;
             for (int i = 0; i < c->timer.n; i++) { c->stageMs[i] = (first ? 0.f : c->stageMs[i]) + c->timer.ms[i]; c->stageNames[i] = c->timer.names[i]; }
             first = false;
@@ -2487,6 +1286,7 @@ size_t compress_samples(ZSTD_CCtx* c, const u8* src, const u64* offs, const size
     if (stats) {
         std::vector<u32> h(377);
         if (hipMemcpyAsync(h.data(), dStats.p, 377 * 4, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) { (void)hipGetLastError(); return ZERR(kErrGeneric); }
+        // (deliberately not dev_read: a failed copy, too, is followed by hipGetLastError here)
         for (u32 i = 0; i < 377; i++) stats[i] += h[i];
     }
     return 0;

@@ -1,0 +1,991 @@
+// zstd_mi355x_dec.hip — the decoder's host side: the decompression context, its parameters and dictionary, the host-side frame-header
+// functions, the launch sequences of the decompress pipeline (one buffer, a batch, a range and many ranges of a seekable stream,
+// several devices), the ZSTD_decompressStream adapter and every decoder entry point of the C ABI (include/zstd_mi355x.h).
+#include <stdlib.h>
+#include <stdio.h>
+#include <functional>
+#include "zmi_pack_runs.h"
+#include "zmi_host.h"
+
+struct ZSTD_DCtx_s {
+    int windowLogMax = 27;
+    int device = 0; bool deviceOk = false;
+    hipStream_t ownStream = nullptr, stream = nullptr;
+    hipStream_t aux = nullptr; hipEvent_t auxDone = nullptr;     // the literal decoder beside seq_decode (decompress_device)
+    int overlapMode = 0;        // ZSTDMI_DCtx_setOverlap: 0 = by block count, 1 = never, 2 = always
+    bool lastWalkSerial = false; // the last call's frames were listed by the serial walk (ZSTDMI_debugLastWalkSerial)
+    int execWaves = 0;          // ZSTDMI_DCtx_setExecWaves: waves per frame in exec_matches, 0 = by the number of frames
+    DevBuf frames, blocks, recs, status, scratch, walkWs, slowFlags, stageSrc, stageDst, origin, originList;
+    DevBuf batchIn, batchOut, blockKeys;    // ZSTDMI_decompressBatch: the entries' table, what the batch walk made of them, one error key per block
+    int lastBatchAlone = 0;     // entries of the last ZSTDMI_decompressBatch that were decoded by the single-call path (debug hook)
+    DevBuf seekTab, seekSum, edge;          // ZSTDMI_decompressRange: a host source's seek table, the summary words, the frames the range cuts
+    int lastRangeFrames = 0; long long lastRangeStaged = 0;     // table entries the last range call decoded, bytes it copied host -> device (debug hooks)
+    // ZSTDMI_decompressRanges: the pass's workspace (RangesWs), the ranges as the host states them / as ranges_select files them /
+    // their results, and the arena that holds every touched frame's content once
+    DevBuf rangesWs, rangesIn, rangesRec, rangesRes, arena;
+    int lastRangesFrames = 0, lastRangesAlone = 0; long long lastRangesStaged = 0;      // (debug hooks)
+    int originMode = 0;         // ZSTDMI_DCtx_setLongFrames: 0 = by cost (see decompress_device), 1 = never, 2 = every frame of 1 MiB or more
+    StageTimer timer;
+    // streaming adapter (ZSTD_decompressStream): whole frames are collected on the host, decoded in batches
+    std::vector<u8> dIn, dOut; size_t dOutPos = 0; bool hostage = false;
+    u32 litDecoder = 0;         // 0 auto, 1 serial (4 lanes per frame), 2 self-synchronising (256 lanes per frame), 3 serial with compact tables
+    // dictionary (ZSTD_DCtx_loadDictionary): host copy, uploaded at the next decompression.  Raw content: the bytes are the
+    // history.  Formatted (magic 0xEC30A437): dict_parse_kernel validates the header and fills `info`; the history is the content.
+    std::vector<u8> dictHost; DevBuf dict, dictInfoDev; bool dictDirty = false, dictFormatted = false;
+    DictInfo info = {};
+    u64 dictGen = 0;
+    std::vector<ZSTD_DCtx_s*> workers;      // ZSTDMI_DCtx_setDevices (decompress_multi)
+    // ZSTD_DCtx_refPrefix: the caller's bytes (host or device), referenced until the next ZSTD_decompressDCtx / ZSTDMI_decompressDevice
+    // has consumed them.  pfxDev: the prefix as that call's kernels read it (the caller's device pointer, or pfxStage for a host prefix)
+    const void* pfx = nullptr; size_t pfxSize = 0; DevBuf pfxStage; const u8* pfxDev = nullptr;
+};
+
+static size_t dctx_sync_dictionary(ZSTD_DCtx* d);
+static size_t dctx_bind(ZSTD_DCtx* d)
+{
+    const size_t e = ctx_bind(d); if (isErr(e)) return e;
+    if (!d->aux && hipStreamCreateWithFlags(&d->aux, hipStreamNonBlocking) != hipSuccess) return ZERR(kErrMemoryAllocation);
+    if (!d->auxDone && hipEventCreateWithFlags(&d->auxDone, hipEventDisableTiming) != hipSuccess) return ZERR(kErrMemoryAllocation);
+    return 0;
+}
+
+extern "C" {
+
+// ---------------- decompression ----------------
+ZSTD_DCtx* ZSTD_createDCtx(void) { return new (std::nothrow) ZSTD_DCtx_s(); }
+size_t ZSTD_freeDCtx(ZSTD_DCtx* d)
+{
+    if (!d) return 0;
+    for (ZSTD_DCtx* w : d->workers) (void)ZSTD_freeDCtx(w);
+    d->workers.clear();
+    if (d->deviceOk) {
+        (void)hipSetDevice(d->device);
+        if (d->ownStream) (void)hipStreamSynchronize(d->ownStream);
+        d->frames.release(); d->blocks.release(); d->recs.release(); d->status.release(); d->scratch.release(); d->walkWs.release(); d->slowFlags.release(); d->stageSrc.release(); d->stageDst.release(); d->dict.release(); d->dictInfoDev.release(); d->origin.release(); d->originList.release(); d->batchIn.release(); d->batchOut.release(); d->blockKeys.release(); d->seekTab.release(); d->seekSum.release(); d->edge.release(); d->pfxStage.release(); d->rangesWs.release(); d->rangesIn.release(); d->rangesRec.release(); d->rangesRes.release(); d->arena.release();
+        d->timer.destroy();
+        if (d->aux) { (void)hipStreamSynchronize(d->aux); (void)hipStreamDestroy(d->aux); }
+        if (d->auxDone) (void)hipEventDestroy(d->auxDone);
+        if (d->ownStream) (void)hipStreamDestroy(d->ownStream);
+    }
+    delete d;
+    return 0;
+}
+size_t ZSTD_DCtx_setParameter(ZSTD_DCtx* d, int param, int value)
+{
+    if (!d) return ZERR(kErrGeneric);
+    if (param == ZSTD_d_windowLogMax) { if (value != 0 && (value < 10 || value > 31)) return ZERR(kErrParameterOutOfBound); d->windowLogMax = value ? value : 27; return 0; }
+    return ZERR(kErrParameterUnsupported);
+}
+size_t ZSTD_DCtx_getParameter(ZSTD_DCtx* d, int param, int* value)
+{
+    if (!d || !value) return ZERR(kErrGeneric);
+    if (param == ZSTD_d_windowLogMax) { *value = d->windowLogMax; return 0; }
+    return ZERR(kErrParameterUnsupported);
+}
+// ZSTD_decompress_insertDictionary, U/ZstdDecompress.cs:1909-1931: without the magic the bytes are raw content, history in
+// front of every frame (ZSTD_refDictContent, :1758-1771); with it (0xEC30A437) the header's Huffman and FSE tables and
+// repcodes are what every frame starts from and frames must name its dictID or none (ZSTD_loadDEntropy, :1773-1875).
+static size_t ZSTD_DCtx_loadDictionary_impl(ZSTD_DCtx* d, const void* dict, size_t dictSize)
+{
+    if (!d) return ZERR(kErrGeneric);
+    d->dictGen++;
+    d->pfx = nullptr; d->pfxSize = 0;       // (a pending prefix is cancelled: ZSTD_clearAllDicts)
+    if (dict == nullptr || dictSize == 0) { d->dictHost.clear(); d->dictDirty = true; return 0; }
+    if (dictSize > (size_t)1 << 30) return ZERR(kErrParameterUnsupported);
+    std::vector<u8> h(dictSize);
+    if (is_device_ptr(dict)) {
+        if (hipMemcpy(h.data(), dict, dictSize, hipMemcpyDeviceToHost) != hipSuccess) return ZERR(kErrGeneric);
+    } else memcpy(h.data(), dict, dictSize);
+    d->dictFormatted = is_formatted_dictionary(h.data(), dictSize);
+    d->dictHost.swap(h);
+    d->dictDirty = true;
+    if (d->dictFormatted && !isErr(dctx_bind(d))) return dctx_sync_dictionary(d);      // validated now when a device is there, else at first use
+    d->dictDirty = true;
+    return 0;
+}
+
+// Host-side header walk for host buffers (ZSTD_findFrameSizeInfo, U/ZstdDecompress.cs:877-951): headers only, no payload.
+static size_t host_frame_size_info(const u8* src, size_t srcSize, unsigned long long* bound)
+{
+    auto rd32 = [](const u8* p) { return (u32)p[0] | ((u32)p[1] << 8) | ((u32)p[2] << 16) | ((u32)p[3] << 24); };
+    if (srcSize >= 8 && (rd32(src) & 0xFFFFFFF0u) == 0x184D2A50u) {
+        const u64 sz = (u64)rd32(src + 4) + 8;
+        if (sz > srcSize) return ZERR(kErrSrcSizeWrong);
+        *bound = 0; return (size_t)sz;
+    }
+    if (srcSize < 5) return ZERR(kErrSrcSizeWrong);
+    if (rd32(src) != 0xFD2FB528u) return ZERR(kErrPrefixUnknown);
+    const u8 fhd = src[4];
+    static const size_t did[4] = { 0, 1, 2, 4 }, fcsB[4] = { 0, 2, 4, 8 };
+    const u32 single = (fhd >> 5) & 1, fcsId = fhd >> 6;
+    const size_t fhs = 5 + !single + did[fhd & 3] + fcsB[fcsId] + (single && !fcsId);
+    if (srcSize < fhs) return ZERR(kErrSrcSizeWrong);
+    if (fhd & 0x08) return ZERR(kErrFrameParameterUnsupported);
+    size_t pos = 5; u64 windowSize = 0, fcs = ~0ull;
+    if (!single) { const u8 wl = src[pos++]; const u32 wlog = (wl >> 3) + 10; if (wlog > 31) return ZERR(kErrWindowTooLarge); windowSize = 1ull << wlog; windowSize += (windowSize >> 3) * (wl & 7); }
+    pos += did[fhd & 3];
+    switch (fcsId) {
+    case 0: if (single) fcs = src[pos]; break;
+    case 1: fcs = (u64)((u32)src[pos] | ((u32)src[pos + 1] << 8)) + 256; break;
+    case 2: fcs = rd32(src + pos); break;
+    default: fcs = (u64)rd32(src + pos) | ((u64)rd32(src + pos + 4) << 32); break;
+    }
+    if (single) windowSize = fcs;
+    const u64 blockSizeMax = windowSize < (1u << 17) ? windowSize : (1u << 17);
+    const u8* ip = src + fhs; size_t remaining = srcSize - fhs; u64 nbBlocks = 0;
+    for (;;) {
+        if (remaining < 3) return ZERR(kErrSrcSizeWrong);
+        const u32 bh = (u32)ip[0] | ((u32)ip[1] << 8) | ((u32)ip[2] << 16);
+        const u32 last = bh & 1, type = (bh >> 1) & 3; u32 cSize = bh >> 3;
+        if (type == 3) return ZERR(kErrCorruption);
+        if (type == 1) cSize = 1;
+        if (3 + (size_t)cSize > remaining) return ZERR(kErrSrcSizeWrong);
+        ip += 3 + cSize; remaining -= 3 + cSize; nbBlocks++;
+        if (last) break;
+    }
+    if ((fhd >> 2) & 1) { if (remaining < 4) return ZERR(kErrSrcSizeWrong); ip += 4; }
+    *bound = fcs != ~0ull ? fcs : nbBlocks * blockSizeMax;
+    return (size_t)(ip - src);
+}
+
+// Window size a frame header declares (ZSTD_getFrameHeader_advanced, U/ZstdDecompress.cs:462-634): the window descriptor, or the
+// content size of a single-segment frame.  0 = not a zstd frame header, or not all of it is there yet.
+static u64 host_frame_window(const u8* src, size_t srcSize)
+{
+    auto rd32 = [](const u8* p) { return (u32)p[0] | ((u32)p[1] << 8) | ((u32)p[2] << 16) | ((u32)p[3] << 24); };
+    if (srcSize < 5 || rd32(src) != 0xFD2FB528u) return 0;
+    const u8 fhd = src[4];
+    static const size_t did[4] = { 0, 1, 2, 4 }, fcsB[4] = { 0, 2, 4, 8 };
+    const u32 single = (fhd >> 5) & 1, fcsId = fhd >> 6;
+    const size_t fhs = 5 + !single + did[fhd & 3] + fcsB[fcsId] + (single && !fcsId);
+    if (srcSize < fhs) return 0;
+    if (!single) { const u8 wl = src[5]; const u32 wlog = (wl >> 3) + 10; if (wlog > 31) return ~0ull; const u64 w = 1ull << wlog; return w + (w >> 3) * (wl & 7); }
+    const size_t pos = 5 + did[fhd & 3];
+    switch (fcsId) {
+    case 0: return src[pos];
+    case 1: return (u64)((u32)src[pos] | ((u32)src[pos + 1] << 8)) + 256;
+    case 2: return rd32(src + pos);
+    default: return (u64)rd32(src + pos) | ((u64)rd32(src + pos + 4) << 32);
+    }
+}
+
+static const u8* host_view(const void* src, size_t srcSize, std::vector<u8>& tmp)
+{
+    if (!is_device_ptr(src)) return (const u8*)src;
+    tmp.resize(srcSize);
+    if (hipMemcpy(tmp.data(), src, srcSize, hipMemcpyDeviceToHost) != hipSuccess) return nullptr;
+    return tmp.data();
+}
+
+static unsigned long long ZSTD_decompressBound_impl(const void* src, size_t srcSize)
+{
+    std::vector<u8> tmp; const u8* ip = srcSize ? host_view(src, srcSize, tmp) : (const u8*)src;
+    if (srcSize && !ip) return (unsigned long long)0 - 2;
+    unsigned long long bound = 0;
+    while (srcSize > 0) {
+        unsigned long long b = 0; const size_t cs = host_frame_size_info(ip, srcSize, &b);
+        if (isErr(cs)) return (unsigned long long)0 - 2;
+        ip += cs; srcSize -= cs; bound += b;
+    }
+    return bound;
+}
+static size_t ZSTD_findFrameCompressedSize_impl(const void* src, size_t srcSize)
+{
+    std::vector<u8> tmp; const u8* ip = host_view(src, srcSize, tmp);
+    if (!ip) return ZERR(kErrSrcSizeWrong);
+    unsigned long long b; return host_frame_size_info(ip, srcSize, &b);
+}
+static unsigned long long ZSTD_getFrameContentSize_impl(const void* src, size_t srcSize)
+{
+    std::vector<u8> tmp; const size_t look = srcSize < 18 ? srcSize : 18;
+    const u8* ip = look ? host_view(src, look, tmp) : nullptr;
+    if (!ip || look < 5) return (unsigned long long)0 - 2;
+    auto rd32 = [](const u8* p) { return (u32)p[0] | ((u32)p[1] << 8) | ((u32)p[2] << 16) | ((u32)p[3] << 24); };
+    if ((rd32(ip) & 0xFFFFFFF0u) == 0x184D2A50u) return 0;
+    if (rd32(ip) != 0xFD2FB528u) return (unsigned long long)0 - 2;
+    const u8 fhd = ip[4]; static const size_t did[4] = { 0, 1, 2, 4 }, fcsB[4] = { 0, 2, 4, 8 };
+    const u32 single = (fhd >> 5) & 1, fcsId = fhd >> 6;
+    const size_t fhs = 5 + !single + did[fhd & 3] + fcsB[fcsId] + (single && !fcsId);
+    if (look < fhs) return (unsigned long long)0 - 2;
+    size_t pos = 5 + !single + did[fhd & 3];
+    switch (fcsId) {
+    case 0: return single ? ip[pos] : (unsigned long long)0 - 1;
+    case 1: return (u64)((u32)ip[pos] | ((u32)ip[pos + 1] << 8)) + 256;
+    case 2: return rd32(ip + pos);
+    default: return (u64)rd32(ip + pos) | ((u64)rd32(ip + pos + 4) << 32);
+    }
+}
+
+// upload a newly loaded dictionary; a formatted one is validated on the device (ZSTD_loadDEntropy's checks) -> dictionary_corrupted
+static size_t dctx_sync_dictionary(ZSTD_DCtx* d)
+{
+    if (!d->dictDirty) return 0;
+    hipStream_t s = d->stream;
+    if (!d->dictHost.empty()) {
+        if (!d->dict.ensure(d->dictHost.size() + 64) || !d->dictInfoDev.ensure(sizeof(DictInfo))) return ZERR(kErrMemoryAllocation);
+        if (hipMemcpyAsync(d->dict.p, d->dictHost.data(), d->dictHost.size(), hipMemcpyHostToDevice, s) != hipSuccess) return ZERR(kErrGeneric);
+        if (d->dictFormatted) {
+            launch_dict_parse((const u8*)d->dict.p, (u32)d->dictHost.size(), (DictInfo*)d->dictInfoDev.p, s);
+            if (hipMemcpyAsync(&d->info, d->dictInfoDev.p, sizeof(DictInfo), hipMemcpyDeviceToHost, s) != hipSuccess) return ZERR(kErrGeneric);
+        }
+        { const size_t e = stream_wait(s); if (isErr(e)) return e; }
+        if (d->dictFormatted && d->info.err) { d->dictHost.clear(); d->dictFormatted = false; d->dictDirty = false; return ZERR(kErrDictionaryCorrupted); }
+    }
+    d->dictDirty = false;
+    return 0;
+}
+
+// the loaded dictionary as the decode kernels take it
+struct DecodeDict { bool fmt; const u8* dictFull; const DictInfo* dinfo; const u8* dictContent; u32 dictContentSize, dictID; };
+static DecodeDict decode_dict(const ZSTD_DCtx* d)
+{
+    DecodeDict k;
+    k.fmt = d->dictFormatted && !d->dictHost.empty();
+    k.dictFull = k.fmt ? (const u8*)d->dict.p : nullptr;
+    k.dinfo = k.fmt ? (const DictInfo*)d->dictInfoDev.p : nullptr;
+    k.dictContent = d->dictHost.empty() ? nullptr : (const u8*)d->dict.p + (k.fmt ? d->info.contentOff : 0u);
+    k.dictContentSize = d->dictHost.empty() ? 0u : (k.fmt ? d->info.contentSize : (u32)d->dictHost.size());
+    k.dictID = k.fmt ? d->info.dictID : 0u;
+    return k;
+}
+
+// the status words (d->status, kSt*): error key = "none" (all ones), everything else zero
+static size_t status_reset(ZSTD_DCtx* d)
+{
+    // (static: the source of an asynchronous copy outlives this function)
+    static const struct Init { u32 w[kStWords] = {}; Init() { w[kStErrKeyLo] = w[kStErrKeyHi] = 0xFFFFFFFFu; } } init;
+    if (hipMemcpyAsync(d->status.p, init.w, sizeof init.w, hipMemcpyHostToDevice, d->stream) != hipSuccess) return ZERR(kErrGeneric);
+    return 0;
+}
+static size_t status_read(ZSTD_DCtx* d, u32* st) { return dev_read(st, d->status.p, kStWords * sizeof(u32), d->stream); }
+static u64 st_u64(const u32* st, u32 lo, u32 hi) { return (u64)st[lo] | ((u64)st[hi] << 32); }
+
+// the work lists of a run over nFrames frames and nBlocks blocks with `total` bytes of content
+static bool ensure_lists(ZSTD_DCtx* d, u32 nFrames, u32 nBlocks, u64 total)
+{
+    return d->frames.ensure((size_t)nFrames * sizeof(FrameDesc)) && d->blocks.ensure((size_t)nBlocks * sizeof(BlockDesc) + 64) &&
+           d->scratch.ensure((size_t)total + (size_t)nFrames * kLitSkew + 256) && d->slowFlags.ensure((size_t)nBlocks + 64);
+}
+
+// Everything behind the frame walk: the lists (d->frames, d->blocks; offsets relative to d_src and d_dst) through block_prepass,
+// seq_decode, block_offsets, the literal decoder, the origin path and exec_matches.  `tail` enqueues what the caller wants read back
+// with the last status read (-> false: failed); st = the status words after it.  -> 0 or the error of the whole run.
+static size_t decode_lists(ZSTD_DCtx* d, const DecodeDict& dd, u8* d_dst, const u8* d_src, u32 nFrames, u32 nBlocks, u32 nUnsized, size_t dstCapacity, u32* st, const std::function<bool()>& tail)
+{
+    hipStream_t s = d->stream;
+    u32* status = (u32*)d->status.p;
+    FrameDesc* frames = (FrameDesc*)d->frames.p; BlockDesc* blocks = (BlockDesc*)d->blocks.p;
+    const bool fmt = dd.fmt; const u8* const dictFull = dd.dictFull; const DictInfo* const dinfo = dd.dinfo;
+    const u8* const dictContent = dd.dictContent; const u32 dictContentSize = dd.dictContentSize;
+    // The literal decoder and seq_decode need nothing of each other (a block's Huffman streams and its FSE chains).  With few
+    // blocks neither fills the chip — both are serial chains per block — so below kOverlapBlocks the literal decoder may run beside
+    // seq_decode on a stream of its own (`early`: block_link then lets it write only the outputs whose place is known by now).
+    // Whether it does is decided once the pre-pass has counted both kinds of work (below).
+    constexpr u32 kOverlapBlocks = 12288;
+    const bool early = d->overlapMode == 2 || (d->overlapMode == 0 && nBlocks <= kOverlapBlocks);
+    launch_block_prepass(d_src, frames, blocks, nFrames, nBlocks, fmt ? 1u : 0u, early ? 1u : 0u, status, s);
+    { const size_t e = status_read(d, st); if (isErr(e)) return e; }
+    d->timer.mark("block_prepass", s);
+    const u64 nSeq = st_u64(st, kStSeqLo, kStSeqHi);
+    if (!d->recs.ensure((size_t)(nSeq + 64) * sizeof(SeqRec))) return ZERR(kErrMemoryAllocation);
+    // Long frames (decode_origin.hip).  The ordered walk of exec_matches moves a frame at about kWalkRate, all frames at
+    // once; the origin path sweeps the frames it is given at about kSweepRate together.  A frame belongs on the origin path when its
+    // own walk would outlast the sweep of every frame at least as long: the smallest size class 2^(20+k) with
+    // 2^(20+k) / kWalkRate >= bytes(frames >= 2^(20+k)) / kSweepRate, from the per-class sums block_link filed.
+    u64 originMin = 0, originBytes = 0, originLongest = 0; u32 originCap = 0;
+    // (the walk has 64 x W sequences in flight per frame, W waves by the number of frames: measured on 1 - 4 MiB level-5 frames)
+    const int execWaves = d->execWaves ? d->execWaves : nFrames <= 256 ? 16 : nFrames <= 512 ? 8 : nFrames <= 1024 ? 4 : nFrames <= 2048 ? 2 : 1;
+    if (d->originMode != 1) {
+        const double kWalkRate = execWaves >= 16 ? 0.42e9 : execWaves == 8 ? 0.33e9 : execWaves == 4 ? 0.24e9 : execWaves == 2 ? 0.19e9 : 0.15e9;
+        constexpr double kSweepRate = 20e9;
+        u64 above = 0;
+        u64 sums[12];
+        for (int k = 0; k < 12; ++k) sums[k] = st_u64(st, kStBigBins + 2 * k, kStBigBins + 2 * k + 1);
+        for (int k = 11; k >= 0; --k) {
+            above += sums[k];
+            if (!above) continue;
+            const double size = (double)((u64)1 << (20 + k));
+            if (d->originMode == 2 || size / kWalkRate >= (double)above / kSweepRate) { originMin = (u64)1 << (20 + k); originBytes = above; }
+        }
+        if (originMin) {
+            // how many frames that can be (a frame of class k holds at least 2^(20+k) bytes) and how long the longest (below 2^(21+k))
+            u64 cap = 0;
+            for (int k = 0; k < 12; ++k) if (((u64)1 << (20 + k)) >= originMin && sums[k]) { cap += sums[k] >> (20 + k); originLongest = (u64)1 << (21 + k); }
+            if (originLongest > originBytes) originLongest = originBytes;
+            originCap = (u32)(cap < 65535 ? cap : 65535);       // (a grid dimension; more long frames than that keep the walk)
+            // (+ one word per 1024 origins: origin_jump_kernel's finished regions)
+            if (!d->origin.ensure((size_t)(originBytes + 1024 * (u64)originCap) * sizeof(u32) + (size_t)((originBytes + 1024 * (u64)originCap) / 1024 + 64) * sizeof(u32)) ||
+                !d->originList.ensure((size_t)originCap * sizeof(u32))) { originMin = 0; (void)hipGetLastError(); }
+        }
+    }
+    SeqRec* recs = (SeqRec*)d->recs.p;
+    struct AuxGuard { hipStream_t a; bool on; ~AuxGuard() { if (on) (void)hipStreamSynchronize(a); } } auxGuard{ d->aux, false };   // nothing of this call outlives it
+    // Beside each other only when both are substantial (from five coded literal bytes per sequence): a Huffman symbol costs its chain
+    // about 26 ns per literal byte (four streams), a sequence about 270 ns — text (three or four literal bytes per sequence) has nothing to hide behind seq_decode and only loses LDS
+    // bandwidth to the company (measured: 1 GiB of 1 MiB level-5 frames, mixed corpus 14.7 -> 13.4 ms, text 15.5 -> 15.7 ms), and
+    // input without sequences (Zipf bytes) has no seq_decode to hide behind.
+    const u64 litBytes = st_u64(st, kStLitLo, kStLitHi);
+    const bool beside = early && nSeq && (d->overlapMode == 2 || (litBytes >= 5 * nSeq && nSeq >= 64 * (u64)nBlocks));
+    if (getenv("ZMI_DEBUG")) fprintf(stderr, "zmi: blocks %u seqs %llu coded literal bytes %llu early %d beside %d\n", nBlocks, (unsigned long long)nSeq, (unsigned long long)litBytes, (int)early, (int)beside);
+    if (beside) {               // (the host has just waited for the pre-pass: everything the literal decoder reads is there)
+        launch_decode_literals(d_src, d_dst, (u8*)d->scratch.p, frames, blocks, nBlocks, status, (u8*)d->slowFlags.p, d->litDecoder, dictFull, dinfo, d->aux, StageHook());
+        if (hipEventRecord(d->auxDone, d->aux) != hipSuccess) return ZERR(kErrGeneric);
+        auxGuard.on = true;
+    }
+    launch_seq_decode(d_src, frames, blocks, nBlocks, recs, status, dictFull, dinfo, s);            d->timer.mark("seq_decode", s);
+    launch_block_offsets(frames, blocks, nFrames, dinfo, nUnsized ? 1u : 0u, dstCapacity, status, s);  d->timer.mark("block_offsets", s);
+    if (auxGuard.on) { if (hipStreamWaitEvent(s, d->auxDone, 0) != hipSuccess) return ZERR(kErrGeneric); d->timer.mark("decode_literals", s); }     // (what of it seq_decode did not cover)
+    else launch_decode_literals(d_src, d_dst, (u8*)d->scratch.p, frames, blocks, nBlocks, status, (u8*)d->slowFlags.p, d->litDecoder, dictFull, dinfo, s, d->timer.hook());
+    launch_place_literals(d_src, d_dst, (const u8*)d->scratch.p, frames, blocks, nBlocks, recs, status, s);    d->timer.mark("place_literals", s);
+    if (originMin) {
+        const u64 entries = originBytes + 1024 * (u64)originCap, longest = originLongest;
+        u32* const origin = (u32*)d->origin.p; const u32* const list = (const u32*)d->originList.p;
+        launch_origin_select(frames, nFrames, originMin, (u32*)d->originList.p, originCap, entries, status, s);
+        launch_origin_init(frames, blocks, list, originCap, longest, recs, status, origin, dictContent ? dictContentSize : 0u, s);    d->timer.mark("origin_init", s);
+        // The rounds in groups of six, the host looking at the last one's verdict in between: ordinary data settles in about ten
+        // rounds, and a round that only finds out that nothing is left still costs its launch (the kernels check the flag too).
+        for (u32 r = 0; r < kOriginRounds; r += 6) {
+            launch_origin_jump(frames, list, originCap, longest, status, origin, origin + entries, r, r + 6, s);
+            u32 open = 0;
+            const u32 lastRound = (r + 6 < kOriginRounds ? r + 6 : kOriginRounds) - 1;
+            { const size_t e = dev_read(&open, status + kStOriginChanged + lastRound, sizeof(u32), s); if (isErr(e)) return e; }
+            if (!open) break;
+        }
+        d->timer.mark("origin_jump", s);
+        launch_origin_gather(frames, list, originCap, longest, status, origin, d_dst, dictContent, s);    d->timer.mark("origin_gather", s);
+    }
+    launch_exec_matches(d_src, d_dst, frames, blocks, nFrames, recs, status, dictContent, dictContentSize, s, execWaves);  d->timer.mark("exec_matches", s);
+    if (!tail()) return ZERR(kErrGeneric);
+    return status_read(d, st);
+}
+
+// The decompress pipeline over device-resident buffers.  Two host round trips size the work lists (frames + blocks after the
+// counting walk, sequence records after the block pre-pass); everything else is one launch sequence:
+//   walk (count) | walk (emit) -> block_parse -> block_link -> seq_scan | seq_decode -> block_offsets [-> frame_rescan]
+//   -> decode_literals -> place_literals -> exec_matches
+static size_t decompress_device(ZSTD_DCtx* d, u8* d_dst, size_t dstCapacity, const u8* d_src, size_t srcSize)
+{
+    hipStream_t s = d->stream;
+    if (srcSize == 0) return 0;
+    // a frame is at least 9 bytes; our own streams hold one per 64 KiB, foreign ones usually far fewer
+    const u32 maxFrames = (u32)((srcSize / 9 + 1) < (1u << 26) ? (srcSize / 9 + 1) : (1u << 26));
+    if (!d->status.ensure(kStWords * sizeof(u32)) || !d->walkWs.ensure(decode_walk_workspace_bytes(srcSize))) return ZERR(kErrMemoryAllocation);
+    u32* status = (u32*)d->status.p;
+    { const size_t e = dctx_sync_dictionary(d); if (isErr(e)) return e; }
+    DecodeDict dd = decode_dict(d);
+    if (d->pfxDev) { dd.dictContent = d->pfxDev; dd.dictContentSize = (u32)d->pfxSize; }      // ZSTD_DCtx_refPrefix: raw content, read where it lies
+    const u32 dictID = dd.dictID;
+    d->timer.begin(s);
+    { const size_t e = status_reset(d); if (isErr(e)) return e; }
+    u32 st[kStWords] = {};
+    launch_frame_walk_count(d_src, srcSize, maxFrames, status, (u8*)d->walkWs.p, s);
+    { const size_t e = status_read(d, st); if (isErr(e)) return e; }
+    const bool serialWalk = !st[kStUsable];
+    d->lastWalkSerial = serialWalk;
+    if (serialWalk) {   // the segment links did not close: take the exact serial walk (it also yields the reference's error code)
+        launch_frame_walk_serial(d_src, srcSize, nullptr, nullptr, maxFrames, status, dictID, 0, s);
+        const size_t e = status_read(d, st); if (isErr(e)) return e;
+    }
+    if (st[kStErr]) return ZERR(st[kStErr]);
+    const u32 nFrames = st[kStFrames], nBlocks = st[kStBlocks], nUnsized = st[kStUnsized];
+    const u64 total = st_u64(st, kStTotalLo, kStTotalHi);       // content sizes (bounds for frames without one)
+    if (!nUnsized && total > dstCapacity) return ZERR(kErrDstSizeTooSmall);
+    if (nFrames == 0) { d->timer.finish(); return 0; }
+    if (!ensure_lists(d, nFrames, nBlocks, total)) return ZERR(kErrMemoryAllocation);
+    FrameDesc* frames = (FrameDesc*)d->frames.p; BlockDesc* blocks = (BlockDesc*)d->blocks.p;
+    if (serialWalk) launch_frame_walk_serial(d_src, srcSize, frames, blocks, maxFrames, status, dictID, 1, s);
+    else            launch_frame_walk_emit(d_src, srcSize, frames, blocks, (u8*)d->walkWs.p, s);
+    d->timer.mark("frame_walk", s);
+    { const size_t e = decode_lists(d, dd, d_dst, d_src, nFrames, nBlocks, nUnsized, dstCapacity, st, [] { return true; }); if (isErr(e)) return e; }
+    d->timer.finish();
+    if (st[kStErrKeyLo] != 0xFFFFFFFFu || st[kStErrKeyHi] != 0xFFFFFFFFu) return ZERR(st[kStErrKeyLo] & 0xFFFFu);   // the first failing block's first error
+    if (st[kStErr]) return ZERR(st[kStErr]);                  // regenerated sizes of unsized frames exceed the destination
+    if (nUnsized) return (size_t)st_u64(st, kStActualLo, kStActualHi);
+    return (size_t)total;
+}
+
+// ---- a batch of independent entries, each decoded as the single call would decode it alone (ZSTDMI_decompressBatch) ----
+// The decoder's unit of parallelism is the block and its lists hold 64-bit offsets, so n entries are ONE run of the pipeline: the
+// batch walk (one lane per entry, the exact serial walk) lists every entry's frames and blocks side by side, with offsets relative to
+// the lowest source and the lowest destination pointer of the call, and block_prepass .. exec_matches run once over the merged lists.
+// Errors stay with their entry: header-stage errors and dstSize_tooSmall are found by the walk (such an entry emits no frames), later
+// ones are filed per block (report_error, kStBlockKeysLo) and folded per entry.  The host synchronises as often as for one single
+// call.  An entry that holds a frame without a content size (where its output goes is known only after decoding: frame_rescan is
+// global by construction) or more than kBatchAloneAbove compressed bytes (one lane walks an entry's block headers) is decoded alone
+// afterwards by decompress_device, and counted.
+constexpr u64 kBatchAloneAbove = (u64)4 << 20;
+// the batch's core over a device-resident entry table (d->batchIn, n entries; d->batchOut gets what the walk and the decoder make of
+// them): batch_walk_count -> batch_scan -> batch_walk_emit -> decode_lists -> batch_fold.  `readBack` enqueues the caller's copy of
+// whatever it wants of d->batchOut: called in front of each of the two host synchronisations that see final entries (after the
+// count: entries without frames are final; after the fold: all are).  -> 0, or the error of the whole run.
+static size_t decode_entries(ZSTD_DCtx* d, const DecodeDict& dd, const u8* srcBase, u8* dstBase, size_t dstSpan, u32 n, const std::function<bool()>& readBack)
+{
+    hipStream_t s = d->stream;
+    if (!d->status.ensure(kStWords * sizeof(u32))) return ZERR(kErrMemoryAllocation);
+    u32* status = (u32*)d->status.p;
+    const BatchEntryIn* dIn = (const BatchEntryIn*)d->batchIn.p; BatchEntryOut* dOut = (BatchEntryOut*)d->batchOut.p;
+    u32 st[kStWords] = {};
+    { const size_t e = status_reset(d); if (isErr(e)) return e; }
+    launch_batch_walk_count(srcBase, dIn, dOut, n, dd.dictID, kBatchAloneAbove, status, s);
+    if (!readBack() ||
+        hipMemcpyAsync(st, status, sizeof st, hipMemcpyDeviceToHost, s) != hipSuccess) return ZERR(kErrGeneric);
+    { const size_t e = stream_wait(s); if (isErr(e)) return e; }
+    if (st[kStErr]) return ZERR(st[kStErr]);
+    const u32 nFrames = st[kStFrames], nBlocks = st[kStBlocks];
+    const u64 total = st_u64(st, kStTotalLo, kStTotalHi);
+    u32 keyWords[2] = {0, 0};
+    if (nFrames) {
+        if (!ensure_lists(d, nFrames, nBlocks, total) || !d->blockKeys.ensure((size_t)nBlocks * sizeof(u64) + 8)) return ZERR(kErrMemoryAllocation);
+        keyWords[0] = (u32)(uintptr_t)d->blockKeys.p; keyWords[1] = (u32)((u64)(uintptr_t)d->blockKeys.p >> 32);
+        if (hipMemsetAsync(d->blockKeys.p, 0xFF, (size_t)nBlocks * sizeof(u64), s) != hipSuccess ||
+            hipMemcpyAsync(status + kStBlockKeysLo, &keyWords[0], sizeof(u32), hipMemcpyHostToDevice, s) != hipSuccess ||
+            hipMemcpyAsync(status + kStBlockKeysHi, &keyWords[1], sizeof(u32), hipMemcpyHostToDevice, s) != hipSuccess) return ZERR(kErrGeneric);
+        launch_batch_walk_emit(srcBase, dIn, dOut, n, (FrameDesc*)d->frames.p, (BlockDesc*)d->blocks.p, s);
+        d->timer.mark("batch_walk", s);
+        const size_t e = decode_lists(d, dd, dstBase, srcBase, nFrames, nBlocks, 0, dstSpan, st, [&]() -> bool {
+            launch_batch_fold(dOut, n, (const u64*)d->blockKeys.p, s);
+            return readBack();
+        });
+        if (isErr(e)) return e;
+    }
+    return 0;
+}
+
+static size_t decompress_batch_impl(ZSTD_DCtx* d, const void* const* srcs, const size_t* srcSizes, size_t n, void* const* dsts, const size_t* dstCapacities, size_t* dstSizes)
+{
+    if (!d) return ZERR(kErrGeneric);
+    if (n == 0) { d->lastBatchAlone = 0; return 0; }
+    if (!srcs || !srcSizes || !dsts || !dstCapacities || !dstSizes) return ZERR(kErrGeneric);
+    if (n > 0xFFFFFFF0ull) return ZERR(kErrMemoryAllocation);
+    size_t e = dctx_bind(d); if (isErr(e)) return e;
+    if (d->workers.size() > 1 || d->pfx) return ZERR(kErrParameterUnsupported);      // (a pending ZSTD_DCtx_refPrefix serves one single call)
+    d->lastBatchAlone = 0;
+    e = dctx_sync_dictionary(d); if (isErr(e)) return e;
+    hipStream_t s = d->stream;
+    const DecodeDict dd = decode_dict(d);
+    // one base pointer each: the lowest source, the lowest destination
+    uintptr_t loS = ~(uintptr_t)0, loD = ~(uintptr_t)0, hiD = 0;
+    for (size_t i = 0; i < n; i++) {
+        if (srcSizes[i] && srcs[i] && (uintptr_t)srcs[i] < loS) loS = (uintptr_t)srcs[i];
+        if (dsts[i]) { const uintptr_t p = (uintptr_t)dsts[i]; if (p < loD) loD = p; if (p + dstCapacities[i] > hiD) hiD = p + dstCapacities[i]; }
+    }
+    if (loS == ~(uintptr_t)0) loS = 0;
+    if (loD == ~(uintptr_t)0) loD = 0;
+    std::vector<BatchEntryIn> hIn(n);
+    for (size_t i = 0; i < n; i++) {
+        const bool noSrc = srcSizes[i] && !srcs[i];           // (the single call: srcSize_wrong, below)
+        hIn[i].srcOff = (srcSizes[i] && !noSrc) ? (u64)((uintptr_t)srcs[i] - loS) : 0;
+        hIn[i].srcSize = noSrc ? 0 : (u64)srcSizes[i];
+        hIn[i].dstOff = dsts[i] ? (u64)((uintptr_t)dsts[i] - loD) : 0;
+        hIn[i].dstCap = dsts[i] ? (u64)dstCapacities[i] : 0;
+    }
+    if (!d->batchIn.ensure(n * sizeof(BatchEntryIn)) || !d->batchOut.ensure(n * sizeof(BatchEntryOut))) return ZERR(kErrMemoryAllocation);
+    BatchEntryOut* dOut = (BatchEntryOut*)d->batchOut.p;
+    std::vector<BatchEntryOut> hOut(n);
+    d->timer.begin(s);
+    if (hipMemcpyAsync(d->batchIn.p, hIn.data(), n * sizeof(BatchEntryIn), hipMemcpyHostToDevice, s) != hipSuccess) return ZERR(kErrGeneric);
+    e = decode_entries(d, dd, (const u8*)loS, (u8*)loD, (size_t)(hiD - loD), (u32)n, [&]() -> bool {
+        return hipMemcpyAsync(hOut.data(), dOut, n * sizeof(BatchEntryOut), hipMemcpyDeviceToHost, s) == hipSuccess;
+    });
+    if (isErr(e)) return e;
+    d->timer.finish();
+    for (size_t i = 0; i < n; i++) {
+        if (srcSizes[i] && !srcs[i]) { dstSizes[i] = ZERR(kErrSrcSizeWrong); continue; }
+        if (hOut[i].state != kBatchAlone) dstSizes[i] = (size_t)hOut[i].result;
+    }
+    for (size_t i = 0; i < n; i++) {
+        if ((srcSizes[i] && !srcs[i]) || hOut[i].state != kBatchAlone) continue;
+        dstSizes[i] = decompress_device(d, (u8*)dsts[i], dstCapacities[i], (const u8*)srcs[i], srcSizes[i]);
+        d->lastBatchAlone++;
+    }
+    return 0;
+}
+
+// ---- a byte range of a seekable stream (ZSTDMI_decompressRange) ----
+// The stream ends in a seek table (include/zstd_mi355x.h): one (compressed size, content size) pair per frame.  The host reads the
+// 9-byte footer (how long the table is); seek_select_kernel checks the rest of it and finds the entries whose content meets
+// [offset, offset + length) — one read-back of its summary words —; seek_emit_kernel turns those entries into the batch walk's table on
+// the device, and the batch's core (decode_entries) decodes them in one run: frames wholly inside the range straight to their place in
+// dst, the at most two frames the range cuts into an edge buffer, from which range_clip_kernel copies the wanted part.  An entry the
+// walk leaves to the single-call path (a frame without a content size, more than kBatchAloneAbove compressed bytes) is decoded by
+// decompress_device into the same place.  range_check_kernel holds every entry to the content size its table entry names.  A host
+// source is staged in two pieces only: the table, and the compressed bytes of the selected entries.
+// a stream's seek table as the kernels read it: n entries of `stride` bytes in tableBytes bytes at tab (device memory: in a device
+// source where it lies, a host source's copy in d->seekTab)
+struct SeekTable { const u8* tab; u32 n, stride; u64 tableBytes; bool srcDev; };
+// the 9-byte footer of the stream's seek table, read on the host (a device source: one small copy back) -> the entry count, the
+// entries' stride and the table's length, or the table's error
+static size_t read_seek_footer(ZSTD_DCtx* d, const void* src, size_t srcSize, bool srcDev, u32& N, u32& stride, u64& tableBytes)
+{
+    if (srcSize && !src) return ZERR(kErrSrcSizeWrong);
+    if (srcSize < 17) return ZERR(kErrPrefixUnknown);
+    hipStream_t s = d->stream;
+    auto rd32 = [](const u8* p) { return (u32)p[0] | ((u32)p[1] << 8) | ((u32)p[2] << 16) | ((u32)p[3] << 24); };
+    u8 foot[9];
+    if (srcDev) {
+        const size_t e = dev_read(foot, (const u8*)src + srcSize - 9, 9, s); if (isErr(e)) return e;
+    } else memcpy(foot, (const u8*)src + srcSize - 9, 9);
+    if (rd32(foot + 5) != 0x8F92EAB1u) return ZERR(kErrPrefixUnknown);
+    if (foot[4] & 0x7C) return ZERR(kErrCorruption);                    // reserved descriptor bits
+    N = rd32(foot);
+    if (N > (1u << 27)) return ZERR(kErrCorruption);
+    stride = (foot[4] & 0x80) ? 12u : 8u;                               // (checksums, where the table has them, are skipped)
+    tableBytes = 17 + (u64)N * stride;
+    if (tableBytes > srcSize) return ZERR(kErrCorruption);
+    return 0;
+}
+// what a call on a seekable stream begins with: the footer, the dictionary, a host source's table staged (its bytes counted in *staged)
+static size_t open_seek_table(ZSTD_DCtx* d, const void* src, size_t srcSize, SeekTable* t, long long* staged)
+{
+    t->srcDev = is_device_ptr(src);
+    size_t e = read_seek_footer(d, src, srcSize, t->srcDev, t->n, t->stride, t->tableBytes); if (isErr(e)) return e;
+    e = dctx_sync_dictionary(d); if (isErr(e)) return e;
+    t->tab = (const u8*)src + (srcSize - t->tableBytes);
+    if (!t->srcDev) {
+        if (!d->seekTab.ensure((size_t)t->tableBytes + 64)) return ZERR(kErrMemoryAllocation);
+        if (hipMemcpyAsync(d->seekTab.p, t->tab, (size_t)t->tableBytes, hipMemcpyHostToDevice, d->stream) != hipSuccess) return ZERR(kErrGeneric);
+        t->tab = (const u8*)d->seekTab.p; *staged += (long long)t->tableBytes;
+    }
+    return 0;
+}
+// what a range returns of a stream of `total` bytes of content when nothing fails
+static u64 range_returned(u64 offset, u64 length, u64 total) { return offset < total ? (length < total - offset ? length : total - offset) : 0; }
+// the entry tables of the last decode_entries run, brought to the host (rare: only when an entry was left to the single-call path)
+static size_t fetch_entries(ZSTD_DCtx* d, u32 n, std::vector<BatchEntryIn>& hIn, std::vector<BatchEntryOut>& hOut)
+{
+    hIn.resize(n); hOut.resize(n);
+    if (hipMemcpyAsync(hIn.data(), d->batchIn.p, (size_t)n * sizeof(BatchEntryIn), hipMemcpyDeviceToHost, d->stream) != hipSuccess ||
+        hipMemcpyAsync(hOut.data(), d->batchOut.p, (size_t)n * sizeof(BatchEntryOut), hipMemcpyDeviceToHost, d->stream) != hipSuccess) return ZERR(kErrGeneric);
+    return stream_wait(d->stream);
+}
+
+static size_t decompress_range_impl(ZSTD_DCtx* d, void* dst, size_t dstCapacity, const void* src, size_t srcSize, unsigned long long offset, size_t length)
+{
+    size_t e = dctx_bind(d); if (isErr(e)) return e;
+    if (d->workers.size() > 1 || d->pfx) return ZERR(kErrParameterUnsupported);
+    d->lastRangeFrames = 0; d->lastRangeStaged = 0;
+    hipStream_t s = d->stream;
+    const bool dstDev = dst ? is_device_ptr(dst) : false;
+    SeekTable t;
+    e = open_seek_table(d, src, srcSize, &t, &d->lastRangeStaged); if (isErr(e)) return e;
+    const bool srcDev = t.srcDev;
+    const DecodeDict dd = decode_dict(d);
+    if (!d->seekSum.ensure(kSeekWords * sizeof(u64))) return ZERR(kErrMemoryAllocation);
+    u64* const sum = (u64*)d->seekSum.p;
+    d->timer.begin(s);
+    launch_seek_select(t.tab, t.tableBytes, t.n, t.stride, srcSize, offset, length, sum, s);
+    u64 sm[kSeekWords] = {};
+    e = dev_read(sm, sum, sizeof sm, s); if (isErr(e)) return e;
+    d->timer.mark("seek_select", s);
+    if (sm[kSeekErr]) return ZERR((u32)sm[kSeekErr]);
+    const u64 returned = range_returned(offset, length, sm[kSeekTotal]);
+    if (returned > dstCapacity) return ZERR(kErrDstSizeTooSmall);
+    if (!returned) { d->timer.finish(); return 0; }
+    if (!dst) return ZERR(kErrDstBufferNull);
+    const u64 nMeet = sm[kSeekMeet];
+    if (!nMeet || sm[kSeekLast] < sm[kSeekFirst]) return ZERR(kErrCorruption);
+    const u32 first = (u32)sm[kSeekFirst], last = (u32)sm[kSeekLast], nSel = last - first + 1;
+    const u64 cLo = sm[kSeekCLo], cHi = sm[kSeekCHi], end = offset + returned;
+    const u64 dFirst = sm[kSeekDFirst], sizeFirst = sm[kSeekSizeFirst], dLast = sm[kSeekDLast], sizeLast = sm[kSeekSizeLast];
+    const bool cutFirst = dFirst < offset || dFirst + sizeFirst > end, cutLast = last != first && dLast + sizeLast > end;
+    const u64 slot1 = cutFirst ? ((sizeFirst + 255) & ~(u64)255) : 0, edgeBytes = slot1 + (cutLast ? sizeLast : 0);
+    if (edgeBytes && !d->edge.ensure((size_t)edgeBytes + 64)) return ZERR(kErrMemoryAllocation);
+    const u8* srcBase = (const u8*)src + cLo;
+    if (!srcDev) {              // only the selected frames travel
+        if (!d->stageSrc.ensure((size_t)(cHi - cLo) + 64)) return ZERR(kErrMemoryAllocation);
+        if (hipMemcpyAsync(d->stageSrc.p, (const u8*)src + cLo, (size_t)(cHi - cLo), hipMemcpyHostToDevice, s) != hipSuccess) return ZERR(kErrGeneric);
+        srcBase = (const u8*)d->stageSrc.p; d->lastRangeStaged += (long long)(cHi - cLo);
+    }
+    u8* d_dst = (u8*)dst;
+    if (!dstDev) { if (!d->stageDst.ensure((size_t)returned + 64)) return ZERR(kErrMemoryAllocation); d_dst = (u8*)d->stageDst.p; }
+    // one base pointer for the destinations, the lowest: dst or the edge buffer
+    const uintptr_t pD = (uintptr_t)d_dst, pE = edgeBytes ? (uintptr_t)d->edge.p : pD;
+    const uintptr_t lo = pD < pE ? pD : pE, hi = (pD + returned > pE + edgeBytes) ? pD + (uintptr_t)returned : pE + (uintptr_t)edgeBytes;
+    if (!d->batchIn.ensure((size_t)nSel * sizeof(BatchEntryIn)) || !d->batchOut.ensure((size_t)nSel * sizeof(BatchEntryOut))) return ZERR(kErrMemoryAllocation);
+    launch_seek_emit(t.tab, t.stride, first, nSel, dFirst, offset, (u64)(pD - lo), (u64)(pE - lo), slot1, cutFirst ? 1u : 0u, cutLast ? 1u : 0u, (BatchEntryIn*)d->batchIn.p, s);
+    d->timer.mark("seek_emit", s);
+    e = decode_entries(d, dd, srcBase, (u8*)lo, (size_t)(hi - lo), nSel, [] { return true; });
+    if (isErr(e)) return e;
+    launch_range_check((const BatchEntryIn*)d->batchIn.p, (const BatchEntryOut*)d->batchOut.p, nSel, sum, s);
+    e = dev_read(sm, sum, sizeof sm, s); if (isErr(e)) return e;
+    if (sm[kSeekKey] != ~0ull) return ZERR((u32)(sm[kSeekKey] & 0xFFFFu));
+    if (sm[kSeekAlone]) {       // (rare: the entries come to the host only then)
+        std::vector<BatchEntryIn> hIn; std::vector<BatchEntryOut> hOut;
+        e = fetch_entries(d, nSel, hIn, hOut); if (isErr(e)) return e;
+        for (u32 i = 0; i < nSel; ++i) {
+            if (hOut[i].state != kBatchAlone) continue;
+            const size_t r = decompress_device(d, (u8*)lo + hIn[i].dstOff, (size_t)hIn[i].dstCap, srcBase + hIn[i].srcOff, (size_t)hIn[i].srcSize);
+            if (isErr(r)) return r == ZERR(kErrDstSizeTooSmall) ? ZERR(kErrCorruption) : r;
+            if (r != hIn[i].dstCap) return ZERR(kErrCorruption);
+        }
+    }
+    if (edgeBytes) {
+        ClipJob j0 = {0, 0, 0}, j1 = {0, 0, 0};
+        if (cutFirst) { const u64 from = offset > dFirst ? offset - dFirst : 0, stop = dFirst + sizeFirst < end ? dFirst + sizeFirst : end;
+                        j0.from = from; j0.to = dFirst + from - offset; j0.len = stop - (dFirst + from); }
+        if (cutLast) { j1.from = slot1; j1.to = dLast - offset; j1.len = end - dLast; }
+        launch_range_clip(d_dst, (const u8*)d->edge.p, j0, j1, s);
+        d->timer.mark("range_clip", s);
+    }
+    if (!dstDev && hipMemcpyAsync(dst, d_dst, (size_t)returned, hipMemcpyDeviceToHost, s) != hipSuccess) return ZERR(kErrGeneric);
+    e = stream_wait(s); if (isErr(e)) return e;
+    d->timer.finish();
+    d->lastRangeFrames = (int)nMeet;
+    return (size_t)returned;
+}
+
+
+// ---- many ranges of a seekable stream in one call (ZSTDMI_decompressRanges) ----
+// While one of these lives, the context's stage timer is off and keeps what it has recorded: the single-call paths that the pass hands
+// a frame or a range to begin the timer anew, and ZSTDMI_DCtx_getStageTimes is to show the pass.
+struct TimerPause {
+    StageTimer& t; const bool was; const int n;
+    explicit TimerPause(StageTimer& timer) : t(timer), was(timer.enabled), n(timer.n) { t.enabled = false; }
+    ~TimerPause() { t.enabled = was; t.n = n; }
+};
+// seek_index turns the table into prefix arrays once; ranges_select answers every range that needs no decoding and marks the entries
+// the others meet; ranges_plan makes ONE decode table of the touched entries — each decoded once, into its slot of the context's
+// arena, whatever number of ranges meets it — and decode_entries runs over it as over any batch.  An entry the walk leaves to the
+// single-call path is decoded by decompress_device into its slot; ranges_gather then checks each range's entries and copies its
+// bytes.  From a host source the table and the touched entries' compressed bytes travel, packed into one staging buffer.  A range of
+// more than kRangesAloneAbove bytes is handed to decompress_range_impl afterwards: it wants its frames decoded in place.
+static size_t decompress_ranges_impl(ZSTD_DCtx* d, const void* src, size_t srcSize, const unsigned long long* offsets, const size_t* lengths, size_t n,
+                                     void* const* dsts, const size_t* dstCapacities, size_t* dstSizes)
+{
+    if (!d) return ZERR(kErrGeneric);
+    if (n == 0) { d->lastRangesFrames = 0; d->lastRangesAlone = 0; d->lastRangesStaged = 0; return 0; }
+    if (!offsets || !lengths || !dsts || !dstCapacities || !dstSizes) return ZERR(kErrGeneric);
+    if (n > 0xFFFFFFF0ull) return ZERR(kErrMemoryAllocation);
+    size_t e = dctx_bind(d); if (isErr(e)) return e;
+    if (d->workers.size() > 1 || d->pfx) return ZERR(kErrParameterUnsupported);      // (a pending ZSTD_DCtx_refPrefix serves one single call)
+    d->lastRangesFrames = 0; d->lastRangesAlone = 0; d->lastRangesStaged = 0;
+    hipStream_t s = d->stream;
+    SeekTable t;
+    e = open_seek_table(d, src, srcSize, &t, &d->lastRangesStaged); if (isErr(e)) return e;
+    const bool srcDev = t.srcDev; const u32 N = t.n;
+    const DecodeDict dd = decode_dict(d);
+    const u32 nR = (u32)n;
+    if (!d->rangesWs.ensure(ranges_ws_bytes(N)) || !d->batchIn.ensure((size_t)N * sizeof(BatchEntryIn) + 64) ||
+        !d->rangesIn.ensure(n * sizeof(RangeIn)) || !d->rangesRec.ensure(n * sizeof(RangeRec)) || !d->rangesRes.ensure(n * sizeof(u64))) return ZERR(kErrMemoryAllocation);
+    const RangesWs ws = ranges_ws((u8*)d->rangesWs.p, N);
+    std::vector<RangeIn> hIn(n);
+    for (size_t i = 0; i < n; i++) { hIn[i].offset = offsets[i]; hIn[i].length = lengths[i]; hIn[i].dstCap = dstCapacities[i]; hIn[i].dst = (u64)(uintptr_t)dsts[i]; }
+    if (hipMemcpyAsync(d->rangesIn.p, hIn.data(), n * sizeof(RangeIn), hipMemcpyHostToDevice, s) != hipSuccess) return ZERR(kErrGeneric);
+    const RangeIn* dRanges = (const RangeIn*)d->rangesIn.p; RangeRec* dRecs = (RangeRec*)d->rangesRec.p;
+    d->timer.begin(s);
+    launch_seek_index(t.tab, t.tableBytes, N, t.stride, srcSize, ws, s);                               d->timer.mark("seek_index", s);
+    launch_ranges_select(dRanges, dRecs, nR, N, ws, s);                                                d->timer.mark("ranges_select", s);
+    launch_ranges_plan(t.tab, N, t.stride, srcDev ? 1u : 0u, ws, (BatchEntryIn*)d->batchIn.p, s);          d->timer.mark("ranges_plan", s);
+    u64 sm[kRgWords] = {};
+    e = dev_read(sm, ws.sum, sizeof sm, s); if (isErr(e)) return e;
+    if (sm[kRgErr]) { d->timer.finish(); return ZERR((u32)sm[kRgErr]); }
+    const u64 total = sm[kRgTotal], arenaBytes = sm[kRgArena], packedBytes = sm[kRgCompact], nRuns = sm[kRgRuns];
+    const u32 nTouched = (u32)sm[kRgTouched];
+    std::vector<u8> packed;     // (these four are sources of asynchronous copies: they live until the last synchronisation below)
+    std::vector<u64> runs;
+    std::vector<BatchEntryIn> eIn; std::vector<BatchEntryOut> eOut;
+    if (nTouched) {
+        if (!d->arena.ensure((size_t)arenaBytes + 64) || !d->batchOut.ensure((size_t)nTouched * sizeof(BatchEntryOut))) return ZERR(kErrMemoryAllocation);
+        const u8* srcBase = (const u8*)src;
+        if (!srcDev) {          // only the touched frames travel, in one copy
+            runs.resize(2 * (size_t)nRuns); packed.resize((size_t)packedBytes);
+            e = dev_read(runs.data(), ws.runs, runs.size() * sizeof(u64), s); if (isErr(e)) return e;
+            if (pack_runs(runs.data(), (size_t)nRuns, (const u8*)src, srcSize, packed.data(), packed.size()) != packed.size()) return ZERR(kErrGeneric);
+            if (!d->stageSrc.ensure(packed.size() + 64)) return ZERR(kErrMemoryAllocation);
+            if (hipMemcpyAsync(d->stageSrc.p, packed.data(), packed.size(), hipMemcpyHostToDevice, s) != hipSuccess) return ZERR(kErrGeneric);
+            srcBase = (const u8*)d->stageSrc.p; d->lastRangesStaged += (long long)packed.size();
+        }
+        u64 someAlone = 0;
+        e = decode_entries(d, dd, srcBase, (u8*)d->arena.p, (size_t)arenaBytes, nTouched, [&]() -> bool {
+            launch_ranges_alone((const BatchEntryOut*)d->batchOut.p, nTouched, ws, s);
+            return hipMemcpyAsync(&someAlone, ws.sum + kRgAloneEntries, sizeof(u64), hipMemcpyDeviceToHost, s) == hipSuccess;
+        });
+        if (isErr(e)) return e;
+        if (someAlone) {        // (rare: the entries come to the host only then)
+            e = fetch_entries(d, nTouched, eIn, eOut); if (isErr(e)) return e;
+            const TimerPause pause(d->timer);       // (decompress_device times itself: the pass keeps its own stages)
+            for (u32 i = 0; i < nTouched; ++i) {
+                if (eOut[i].state != kBatchAlone) continue;
+                eOut[i].result = (u64)decompress_device(d, (u8*)d->arena.p + eIn[i].dstOff, (size_t)eIn[i].dstCap, srcBase + eIn[i].srcOff, (size_t)eIn[i].srcSize);
+                if (hipMemcpyAsync((BatchEntryOut*)d->batchOut.p + i, &eOut[i], sizeof(BatchEntryOut), hipMemcpyHostToDevice, s) != hipSuccess) return ZERR(kErrGeneric);
+            }
+        }
+    }
+    std::vector<u64> hRes(n);
+    // (what a range returns: ranges_select's rule, on the host: it has the total now)
+    u64 longest = 0;            // of the ranges the gather serves: the number of its slices
+    for (size_t i = 0; i < n; i++) {
+        const u64 ret = range_returned(offsets[i], lengths[i], total);
+        if (ret <= dstCapacities[i] && ret <= kRangesAloneAbove && dsts[i] && ret > longest) longest = ret;
+    }
+    launch_ranges_gather(dRanges, dRecs, (u64*)d->rangesRes.p, nR, (u32)((longest + kGatherSlice - 1) / kGatherSlice), ws, (const BatchEntryOut*)d->batchOut.p,
+                         (const u8*)d->arena.p, s);
+    d->timer.mark("ranges_gather", s);
+    e = dev_read(hRes.data(), d->rangesRes.p, n * sizeof(u64), s); if (isErr(e)) return e;
+    d->timer.finish();
+    d->lastRangesFrames = (int)nTouched;
+    // the ranges that go alone, in range order
+    const long long staged = d->lastRangesStaged; long long stagedAlone = 0; int alone = 0;
+    const TimerPause pause(d->timer);               // (the stage times stay the gathered pass's)
+    for (size_t i = 0; i < n; i++) {
+        const u64 ret = range_returned(offsets[i], lengths[i], total);
+        if (ret > dstCapacities[i] || !dsts[i] || ret <= kRangesAloneAbove) { dstSizes[i] = (size_t)hRes[i]; continue; }
+        dstSizes[i] = decompress_range_impl(d, dsts[i], dstCapacities[i], src, srcSize, offsets[i], lengths[i]);
+        stagedAlone += d->lastRangeStaged; alone++;
+    }
+    d->lastRangesAlone = alone; d->lastRangesStaged = staged + stagedAlone;
+    return 0;
+}
+
+static size_t decompress_multi(ZSTD_DCtx* d, void* dst, size_t dstCapacity, const void* src, size_t srcSize);
+// ZSTD_DCtx_refPrefix (U/ZstdDecompress.cs:2164-2202): the pending prefix becomes this call's raw-content dictionary — a device prefix
+// where it lies, a host prefix staged to HBM — and is consumed, whatever the call returns (PrefixUse's destructor)
+struct PrefixUse {
+    ZSTD_DCtx* d;
+    explicit PrefixUse(ZSTD_DCtx* dd) : d(dd) {}
+    size_t begin()
+    {
+        if (!d->pfx) return 0;
+        if (d->workers.size() > 1) return ZERR(kErrParameterUnsupported);
+        if (is_device_ptr(d->pfx)) { d->pfxDev = (const u8*)d->pfx; return 0; }
+        if (!d->pfxStage.ensure(d->pfxSize + 64)) return ZERR(kErrMemoryAllocation);
+        if (hipMemcpyAsync(d->pfxStage.p, d->pfx, d->pfxSize, hipMemcpyHostToDevice, d->stream) != hipSuccess) return ZERR(kErrGeneric);
+        d->pfxDev = (const u8*)d->pfxStage.p;
+        return 0;
+    }
+    ~PrefixUse() { d->pfx = nullptr; d->pfxSize = 0; d->pfxDev = nullptr; }
+};
+static size_t ZSTDMI_decompressDevice_impl(ZSTD_DCtx* d, void* d_dst, size_t dstCapacity, const void* d_src, size_t srcSize)
+{
+    if (!d) return ZERR(kErrGeneric);
+    PrefixUse use(d);
+    size_t e = dctx_bind(d); if (isErr(e)) return e;
+    e = use.begin(); if (isErr(e)) return e;
+    if (srcSize && !d_src) return ZERR(kErrSrcSizeWrong);
+    if (d->workers.size() > 1 && srcSize) return decompress_multi(d, d_dst, dstCapacity, d_src, srcSize);
+    return decompress_device(d, (u8*)d_dst, dstCapacity, (const u8*)d_src, srcSize);
+}
+
+static size_t ZSTD_decompressDCtx_impl(ZSTD_DCtx* d, void* dst, size_t dstCapacity, const void* src, size_t srcSize)
+{
+    if (!d) return ZERR(kErrGeneric);
+    PrefixUse use(d);
+    size_t e = dctx_bind(d); if (isErr(e)) return e;
+    e = use.begin(); if (isErr(e)) return e;
+    if (srcSize && !src) return ZERR(kErrSrcSizeWrong);
+    if (srcSize == 0) return 0;
+    if (d->workers.size() > 1) return decompress_multi(d, dst, dstCapacity, src, srcSize);
+    const bool srcDev = is_device_ptr(src), dstDev = dst ? is_device_ptr(dst) : false;
+    const u8* d_src = (const u8*)src; u8* d_dst = (u8*)dst;
+    if (!srcDev) {
+        if (!d->stageSrc.ensure(srcSize + 64)) return ZERR(kErrMemoryAllocation);
+        if (hipMemcpyAsync(d->stageSrc.p, src, srcSize, hipMemcpyHostToDevice, d->stream) != hipSuccess) return ZERR(kErrGeneric);
+        d_src = (const u8*)d->stageSrc.p;
+    }
+    if (!dstDev) {
+        if (!d->stageDst.ensure(dstCapacity + 64)) return ZERR(kErrMemoryAllocation);
+        d_dst = (u8*)d->stageDst.p;
+    }
+    const size_t r = decompress_device(d, d_dst, dstCapacity, d_src, srcSize);
+    if (isErr(r)) return r;
+    if (!dstDev && r) {
+        if (hipMemcpyAsync(dst, d_dst, r, hipMemcpyDeviceToHost, d->stream) != hipSuccess) return ZERR(kErrGeneric);
+        if (hipStreamSynchronize(d->stream) != hipSuccess) return ZERR(kErrGeneric);      // (deliberately not stream_wait: no hipGetLastError behind this wait)
+    }
+    return r;
+}
+
+// ---------------- several devices behind one context (ZSTDMI_DCtx_setDevices; the compressor's side: compress_multi, zstd_mi355x.hip) ----------------
+// decompress: the frames of the input (a host-side header walk) in contiguous shares by compressed size
+static size_t decompress_multi(ZSTD_DCtx* d, void* dst, size_t dstCapacity, const void* src, size_t srcSize)
+{
+    const size_t W = d->workers.size();
+    bool ok = true;
+    std::vector<u8> tmp;
+    const u8* const ip = host_view(src, srcSize, tmp);
+    if (!ip) return ZERR(kErrGeneric);
+    struct Piece { size_t off, len; unsigned long long bound; bool sized; };
+    std::vector<Piece> frames;
+    { size_t pos = 0;
+      while (pos < srcSize) {
+          unsigned long long b = 0; const size_t fs = host_frame_size_info(ip + pos, srcSize - pos, &b);
+          if (isErr(fs)) { if (frames.empty() || fs != ZERR(kErrPrefixUnknown)) return fs; return ZERR(kErrSrcSizeWrong); }     // as ZSTD_decompressMultiFrame: garbage behind a frame
+          Piece p; p.off = pos; p.len = fs; p.bound = b;
+          p.sized = ZSTD_getFrameContentSize_impl(ip + pos, fs) < (unsigned long long)0 - 2;
+          frames.push_back(p); pos += fs;
+      } }
+    // shares of about equal compressed size
+    std::vector<size_t> lo(W + 1, frames.size());
+    { size_t acc = 0, k = 0; lo[0] = 0;
+      for (size_t f = 0; f < frames.size(); ++f) { while (k + 1 < W && acc >= srcSize * (k + 1) / W) lo[++k] = f; acc += frames[f].len; }
+      while (k + 1 < W) lo[++k] = frames.size(); lo[W] = frames.size(); }
+    std::vector<size_t> res(W, 0), got(W, 0);
+    std::vector<unsigned long long> bound(W, 0);
+    bool allSized = true;
+    for (size_t i = 0; i < W; ++i) for (size_t f = lo[i]; f < lo[i + 1]; ++f) { bound[i] += frames[f].bound; allSized = allSized && frames[f].sized; }
+    if (allSized) { unsigned long long t = 0; for (size_t i = 0; i < W; ++i) t += bound[i]; if (t > dstCapacity) return ZERR(kErrDstSizeTooSmall); }
+    { const size_t e = dctx_sync_dictionary(d); if (isErr(e)) return e; }
+    for (ZSTD_DCtx* w : d->workers) {
+        w->litDecoder = d->litDecoder; w->originMode = d->originMode; w->overlapMode = d->overlapMode; w->timer.enabled = d->timer.enabled;
+        if (w->dictGen != d->dictGen) { w->dictHost = d->dictHost; w->dictFormatted = d->dictFormatted; w->dictDirty = true; w->dictGen = d->dictGen; }
+    }
+    std::vector<size_t> at(W, 0);
+    for (size_t i = 1; i < W; ++i) at[i] = at[i - 1] + (size_t)bound[i - 1];       // exact when every frame has a content size
+    ok = run_on_workers(W, [&](size_t i) {
+        ZSTD_DCtx* w = d->workers[i];
+        size_t e = dctx_bind(w); if (isErr(e)) { res[i] = e; return; }
+        if (lo[i] == lo[i + 1]) return;
+        const size_t a = frames[lo[i]].off, n = frames[lo[i + 1] - 1].off + frames[lo[i + 1] - 1].len - a;
+        if (!w->stageSrc.ensure(n + 64) || !w->stageDst.ensure((size_t)bound[i] + 64)) { res[i] = ZERR(kErrMemoryAllocation); return; }
+        e = copy_any(w->stageSrc.p, ip + a, n, w->stream); if (isErr(e)) { res[i] = e; return; }
+        const size_t r = decompress_device(w, (u8*)w->stageDst.p, (size_t)bound[i], (const u8*)w->stageSrc.p, n);
+        if (isErr(r)) { res[i] = r; return; }
+        got[i] = r;
+        if (allSized) {         // its place in the caller's buffer is known
+            e = copy_any((u8*)dst + at[i], w->stageDst.p, r, w->stream);
+            if (!isErr(e)) e = stream_wait(w->stream);
+            if (isErr(e)) res[i] = e;
+        }
+    });
+    if (!ok) return ZERR(kErrMemoryAllocation);
+    for (size_t i = 0; i < W; ++i) if (isErr(res[i])) return res[i];          // the first share's error is the first frame's
+    size_t total = 0;
+    for (size_t i = 0; i < W; ++i) total += got[i];
+    if (!allSized) {            // frames without a content size: the shares' places follow from what they regenerated
+        if (total > dstCapacity) return ZERR(kErrDstSizeTooSmall);
+        size_t pos = 0;
+        for (size_t i = 0; i < W; ++i) {
+            ZSTD_DCtx* w = d->workers[i];
+            if (isErr(dctx_bind(w))) return ZERR(kErrGeneric);
+            size_t e = copy_any((u8*)dst + pos, w->stageDst.p, got[i], w->stream); if (isErr(e)) return e;
+            e = stream_wait(w->stream); if (isErr(e)) return e;
+            pos += got[i];
+        }
+    }
+    d->timer.n = d->workers[0]->timer.n;
+    for (int i = 0; i < d->timer.n; i++) { d->timer.ms[i] = d->workers[0]->timer.ms[i]; d->timer.names[i] = d->workers[0]->timer.names[i]; }
+    (void)dctx_bind(d);
+    return total;
+}
+
+// ---------------- streaming adapter on the batched engine ----------------
+// ZSTD_decompressStream (S/Decompressor.cs:97-106 <- S/DecompressionStream.cs:88-162; U/ZstdDecompress.cs:2816-3205).
+// Compressed bytes are collected until at least one whole frame is present (frame sizes come from the block headers,
+// ZSTD_findFrameSizeInfo); all whole frames collected so far are decoded in one GPU batch into a pending buffer that is
+// handed out as the caller's output space allows.  Returns 0 when a frame boundary is reached and everything is flushed,
+// an error, or a non-zero hint.  As in the reference (U/ZstdDecompress.cs:3170-3194) the last input byte is held hostage
+// while decoded data is still pending, so that a caller who stops feeding at end of input still gets called back.
+static size_t dstream_drain(ZSTD_DCtx* d, ZSTD_outBuffer* o)
+{
+    const size_t avail = d->dOut.size() - d->dOutPos, room = o->size - o->pos;
+    const size_t n = avail < room ? avail : room;
+    if (n) { memcpy((u8*)o->dst + o->pos, d->dOut.data() + d->dOutPos, n); o->pos += n; d->dOutPos += n; }
+    if (d->dOutPos == d->dOut.size()) { d->dOut.clear(); d->dOutPos = 0; }
+    return d->dOut.size() - d->dOutPos;
+}
+static size_t ZSTD_decompressStream_impl(ZSTD_DCtx* d, ZSTD_outBuffer* output, ZSTD_inBuffer* input)
+{
+    if (!d || !output || !input) return ZERR(kErrGeneric);
+    if (output->pos > output->size) return ZERR(104);
+    if (input->pos > input->size) return ZERR(105);
+    if (input->size > input->pos && !input->src) return ZERR(kErrSrcSizeWrong);
+    if (output->size > output->pos && !output->dst) return ZERR(kErrDstBufferNull);
+    if (d->pfx) return ZERR(kErrParameterUnsupported);         // (a referenced prefix serves one single call)
+    if (d->hostage && input->pos < input->size) { input->pos++; d->hostage = false; }       // that byte was consumed earlier
+    size_t pending = dstream_drain(d, output);
+    if (!pending) {
+        const size_t n = input->size - input->pos;
+        if (n) { d->dIn.insert(d->dIn.end(), (const u8*)input->src + input->pos, (const u8*)input->src + input->size); input->pos = input->size; }
+        size_t whole = 0; unsigned long long bound = 0;
+        while (whole < d->dIn.size()) {
+            unsigned long long b = 0;
+            // ZSTD_d_windowLogMax bounds what a streamed frame may ask for (U/ZstdDecompress.cs:2966-2969, with the 1 KiB floor of
+            // :2965): checked as soon as the header is there, before the frame is collected or anything is sized from it
+            { u64 w = host_frame_window(d->dIn.data() + whole, d->dIn.size() - whole);
+              if (w && w < 1024) w = 1024;
+              if (w > (1ull << d->windowLogMax)) { d->dIn.clear(); return ZERR(kErrWindowTooLarge); } }
+            const size_t fs = host_frame_size_info(d->dIn.data() + whole, d->dIn.size() - whole, &b);
+            if (isErr(fs)) { if (fs == ZERR(kErrSrcSizeWrong)) break; return fs; }          // incomplete frame: wait for more input
+            whole += fs; bound += b;
+        }
+        if (whole) {
+            d->dOut.resize((size_t)bound); d->dOutPos = 0;
+            const size_t r = ZSTD_decompressDCtx_impl(d, d->dOut.data(), d->dOut.size(), d->dIn.data(), whole);
+            if (isErr(r)) { d->dOut.clear(); return r; }
+            d->dOut.resize(r);
+            d->dIn.erase(d->dIn.begin(), d->dIn.begin() + (ptrdiff_t)whole);
+            pending = dstream_drain(d, output);
+        }
+    }
+    if (pending) {
+        if (!d->hostage && input->pos == input->size && input->pos > 0) { input->pos--; d->hostage = true; }
+        return 1;
+    }
+    if (d->hostage) return 1;                                  // flushed, but the hostage byte has not been handed back yet
+    return d->dIn.empty() ? 0 : 1;                             // 0 only on a frame boundary
+}
+
+// ---------------- extensions ----------------
+size_t ZSTDMI_DCtx_setDevice(ZSTD_DCtx* d, int device) { return ctx_set_device(d, device); }
+size_t ZSTDMI_DCtx_setDevices(ZSTD_DCtx* d, const int* devices, int n) { return ctx_set_devices(d, devices, n, ZSTD_createDCtx, ZSTD_freeDCtx); }
+size_t ZSTDMI_DCtx_setStream(ZSTD_DCtx* d, void* st) { return ctx_set_stream(d, st, dctx_bind); }
+int ZSTDMI_debugLastWalkSerial(const ZSTD_DCtx* d) { return d ? (int)d->lastWalkSerial : -1; }
+size_t ZSTDMI_DCtx_setExecWaves(ZSTD_DCtx* d, unsigned waves) { if (!d || (waves != 0 && waves != 1 && waves != 2 && waves != 4 && waves != 8 && waves != 16)) return ZERR(kErrParameterOutOfBound); d->execWaves = (int)waves; return 0; }
+size_t ZSTDMI_DCtx_setOverlap(ZSTD_DCtx* d, unsigned mode) { if (!d || mode > 2) return ZERR(kErrParameterOutOfBound); d->overlapMode = (int)mode; return 0; }
+size_t ZSTDMI_DCtx_setLongFrames(ZSTD_DCtx* d, unsigned mode) { if (!d || mode > 2) return ZERR(kErrParameterOutOfBound); d->originMode = (int)mode; return 0; }
+size_t ZSTDMI_DCtx_setLiteralDecoder(ZSTD_DCtx* d, unsigned mode) { if (!d || mode > 3) return ZERR(kErrParameterOutOfBound); d->litDecoder = mode; return 0; }
+size_t ZSTDMI_DCtx_setProfiling(ZSTD_DCtx* d, int en) { if (!d) return ZERR(kErrGeneric); d->timer.enabled = en != 0; return 0; }
+int ZSTDMI_DCtx_getStageTimes(const ZSTD_DCtx* d, float* ms, const char** names, int cap)
+{
+    if (!d) return 0;
+    int n = d->timer.n < cap ? d->timer.n : cap;
+    for (int i = 0; i < n; i++) { if (ms) ms[i] = d->timer.ms[i]; if (names) names[i] = d->timer.names[i]; }
+    return n;
+}
+
+// ---------------- entry points whose host-side containers may throw: guarded (see guarded()) ----------------
+size_t ZSTD_DCtx_loadDictionary(ZSTD_DCtx* d, const void* dict, size_t dictSize) { return guarded([&] { return ZSTD_DCtx_loadDictionary_impl(d, dict, dictSize); }); }
+size_t ZSTD_DCtx_refPrefix(ZSTD_DCtx* d, const void* prefix, size_t prefixSize)
+{
+    if (!d) return ZERR(kErrGeneric);
+    if (prefix && prefixSize > (size_t)1 << 30) return ZERR(kErrParameterUnsupported);
+    // ZSTD_clearAllDicts: a loaded dictionary and an earlier prefix are gone
+    d->dictGen++; d->dictHost.clear(); d->dictFormatted = false; d->dictDirty = true;
+    d->pfx = nullptr; d->pfxSize = 0;
+    if (prefix && prefixSize) { d->pfx = prefix; d->pfxSize = prefixSize; }
+    return 0;
+}
+size_t ZSTD_findFrameCompressedSize(const void* src, size_t srcSize) { return guarded([&] { return ZSTD_findFrameCompressedSize_impl(src, srcSize); }); }
+size_t ZSTD_decompressDCtx(ZSTD_DCtx* d, void* dst, size_t dstCapacity, const void* src, size_t srcSize) { return guarded([&] { return ZSTD_decompressDCtx_impl(d, dst, dstCapacity, src, srcSize); }); }
+size_t ZSTDMI_decompressBatch(ZSTD_DCtx* d, const void* const* srcs, const size_t* srcSizes, size_t n, void* const* dsts, const size_t* dstCapacities, size_t* dstSizes)
+{
+    return guarded([&] { return decompress_batch_impl(d, srcs, srcSizes, n, dsts, dstCapacities, dstSizes); });
+}
+int ZSTDMI_debugLastBatchAloneD(const ZSTD_DCtx* d) { return d ? d->lastBatchAlone : -1; }
+size_t ZSTDMI_decompressRange(ZSTD_DCtx* d, void* dst, size_t dstCapacity, const void* src, size_t srcSize, unsigned long long offset, size_t length)
+{
+    if (!d) return ZERR(kErrGeneric);
+    return guarded([&] { return decompress_range_impl(d, dst, dstCapacity, src, srcSize, offset, length); });
+}
+int ZSTDMI_debugLastRangeFrames(const ZSTD_DCtx* d) { return d ? d->lastRangeFrames : -1; }
+long long ZSTDMI_debugLastRangeStaged(const ZSTD_DCtx* d) { return d ? d->lastRangeStaged : -1; }
+size_t ZSTDMI_decompressRanges(ZSTD_DCtx* d, const void* src, size_t srcSize, const unsigned long long* offsets, const size_t* lengths, size_t n,
+                               void* const* dsts, const size_t* dstCapacities, size_t* dstSizes)
+{
+    return guarded([&] { return decompress_ranges_impl(d, src, srcSize, offsets, lengths, n, dsts, dstCapacities, dstSizes); });
+}
+int ZSTDMI_debugLastRangesFrames(const ZSTD_DCtx* d) { return d ? d->lastRangesFrames : -1; }
+int ZSTDMI_debugLastRangesAlone(const ZSTD_DCtx* d) { return d ? d->lastRangesAlone : -1; }
+long long ZSTDMI_debugLastRangesStaged(const ZSTD_DCtx* d) { return d ? d->lastRangesStaged : -1; }
+size_t ZSTDMI_decompressDevice(ZSTD_DCtx* d, void* d_dst, size_t dstCapacity, const void* d_src, size_t srcSize) { return guarded([&] { return ZSTDMI_decompressDevice_impl(d, d_dst, dstCapacity, d_src, srcSize); }); }
+size_t ZSTD_decompressStream(ZSTD_DCtx* d, ZSTD_outBuffer* output, ZSTD_inBuffer* input) { return guarded([&] { return ZSTD_decompressStream_impl(d, output, input); }); }
+unsigned long long ZSTD_decompressBound(const void* src, size_t srcSize)
+{
+    try { return ZSTD_decompressBound_impl(src, srcSize); } catch (...) { return (unsigned long long)0 - 2; }      /* ZSTD_CONTENTSIZE_ERROR */
+}
+unsigned long long ZSTD_getFrameContentSize(const void* src, size_t srcSize)
+{
+    try { return ZSTD_getFrameContentSize_impl(src, srcSize); } catch (...) { return (unsigned long long)0 - 2; }      /* ZSTD_CONTENTSIZE_ERROR */
+}
+
+} // extern "C"
