@@ -64,7 +64,8 @@ size_t     ZSTD_CCtx_getParameter(const ZSTD_CCtx* cctx, int param, int* value);
  * that do not start with the magic 0xEC30A437): history in front of every frame, no dictID.  FORMATTED dictionaries (the
  * magic, a dictID, entropy tables, repcodes, content — what the trainer returns): the content is the history, the frames
  * carry the dictID (unless ZSTD_c_dictIDFlag = 0) and start from the dictionary's repcodes; its entropy tables are not
- * used (every block carries its own — valid for any decoder holding the dictionary).  A malformed header ->
+ * used by default (every block carries its own — valid for any decoder holding the dictionary); ZSTDMI_CCtx_setDictEntropy(1)
+ * turns them on.  A malformed header ->
  * dictionary_corrupted (at this call when a device is bound, else at first use).  NULL/0 = no dictionary; under 8 bytes =
  * ignored, as in the reference.  The pointer may be host or device memory; the bytes are copied. */
 size_t     ZSTD_CCtx_loadDictionary(ZSTD_CCtx* cctx, const void* dict, size_t dictSize);
@@ -295,6 +296,19 @@ int ZSTDMI_debugLastBatchAloneD(const ZSTD_DCtx* dctx);
  * bits, more than 2^27 entries, a table longer than the stream, compressed sizes that do not add up to the bytes in front of the table,
  * a frame whose content is not the size its entry names: corruption_detected. */
 size_t ZSTDMI_CCtx_setSeekTable(ZSTD_CCtx* cctx, unsigned mode);
+/* Code with a formatted dictionary's entropy tables (ZSTD_loadCEntropy, U/ZstdCompress.cs:5259-5400).  0 = off (the default: no
+ * existing output changes; making it the default is a separate, later decision), 1 = on, any other mode: parameter_outOfBound; NULL
+ * context: GENERIC.  Sticky; the call touches no device.  On, and with a FORMATTED dictionary in use, the first block of every frame
+ * (behind a dictionary a frame has one block) has the dictionary's Huffman table and its three FSE tables as its previous entropy
+ * state, decided as the reference decides below the lazy strategy: a treeless literals section (type 3) where the table covers the
+ * literals and a tree of the block's own would not pay for its description — always up to 1024 literals; raw only up to 6 literals
+ * and one stream up to 1023 when the table has no zero weight — and set_repeat (mode 3, no table description) for LL / OF / ML where
+ * the dictionary's table is valid for the alphabet, defaults are allowed and the block has fewer than 1000 sequences.  Later blocks
+ * of a frame describe their own tables as ever.  A Huffman table of fewer than 256 symbols or with codes above 11 bits is not used.
+ * Honoured by ZSTD_compress2, ZSTDMI_compressDevice, ZSTDMI_compressBatch (bytes equal to the single call), ZSTD_compressStream2,
+ * ZSTDMI_debugCompressSamples and contexts with several device workers.  Without a dictionary, with a raw-content dictionary, behind
+ * ZSTD_CCtx_refPrefix and in ZSTD_compressCCtx the switch changes nothing.  Every zstd decoder holding the dictionary reads the frames. */
+size_t ZSTDMI_CCtx_setDictEntropy(ZSTD_CCtx* cctx, unsigned mode);
 size_t ZSTDMI_seekTableBound(size_t srcSize);
 size_t ZSTDMI_decompressRange(ZSTD_DCtx* dctx, void* dst, size_t dstCapacity, const void* src, size_t srcSize,
                               unsigned long long offset, size_t length);

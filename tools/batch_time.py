@@ -7,7 +7,9 @@ tests/golden/trained_16k.dict.  Per point, compress and decompress:
   (d) the batch call's stage times (ZSTDMI_*_getStageTimes)
 Best of 3 after a warm-up call of the same shape; the host clock stops after the call's final synchronise (every call ends with one).
 The input is 16 MiB of generated data repeated (entries are independent, so the repeats are nobody's match).
-python tools/batch_time.py [MiB]"""
+python tools/batch_time.py [MiB] [--dict-entropy] [--dict-row]
+  --dict-entropy : the dictionary row with ZSTDMI_CCtx_setDictEntropy on (the dictionary's entropy tables in the compressor)
+  --dict-row     : only the dictionary row"""
 import ctypes, sys, os, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -16,7 +18,11 @@ torch.zeros(1, device="cuda")
 import zstdsharp_amd as z, datagen
 lib = z._ffi.load()
 MiB = 1 << 20
-total = (int(sys.argv[1]) if len(sys.argv) > 1 else 256) * MiB
+FLAGS = [a for a in sys.argv[1:] if a.startswith("--")]
+ARGS = [a for a in sys.argv[1:] if not a.startswith("--")]
+assert all(f in ("--dict-entropy", "--dict-row") for f in FLAGS), FLAGS
+DICT_ENTROPY, DICT_ROW = "--dict-entropy" in FLAGS, "--dict-row" in FLAGS
+total = (int(ARGS[0]) if ARGS else 256) * MiB
 SAMPLE = 4096
 DICT = open(os.path.join(ROOT, "tests", "golden", "trained_16k.dict"), "rb").read()
 
@@ -52,6 +58,8 @@ def ok(r):
 
 data = {k: torch.from_numpy(np.frombuffer(datagen.gen(k, 16 * MiB, 5), dtype=np.uint8).copy()).cuda().repeat(total // (16 * MiB)) for k in ("text", "zipf")}
 points = [(kind, size, level, None) for size in (4096, 16384, 65536) for kind in ("text", "zipf") for level in (1, 3)] + [("text", 4096, 3, DICT)]
+if DICT_ROW:
+    points = points[-1:]
 print(f"{total // MiB} MiB per point; ms per call of all entries (GB/s of content)", flush=True)
 for kind, size, level, dic in points:
     src = data[kind]
@@ -63,6 +71,8 @@ for kind, size, level, dic in points:
     lib.ZSTD_CCtx_setParameter(c, 100, level)
     if dic:
         ok(lib.ZSTD_CCtx_loadDictionary(c, dic, len(dic))); ok(lib.ZSTD_DCtx_loadDictionary(d, dic, len(dic)))
+        if DICT_ENTROPY:
+            ok(lib.ZSTDMI_CCtx_setDictEntropy(c, 1))
     s_ptr, d_ptr, o_ptr = ptrs(src.data_ptr(), [i * size for i in range(n)]), ptrs(dst.data_ptr(), [i * cap for i in range(n)]), ptrs(out.data_ptr(), [i * size for i in range(n)])
     s_sz, d_cap, got, back = sizes([size] * n), sizes([cap] * n), (ctypes.c_size_t * n)(), (ctypes.c_size_t * n)()
     # (b) batch
@@ -97,7 +107,7 @@ for kind, size, level, dic in points:
     cc = best_of(concat_c)
     dc = best_of(lambda: ok(lib.ZSTDMI_decompressDevice(d, out.data_ptr(), total, dst.data_ptr(), whole[0])))
     gbs = lambda t: total / t / 1e9
-    name = f"{kind} {size // 1024:2d} KiB L{level}{' dict' if dic else ''}"
+    name = f"{kind} {size // 1024:2d} KiB L{level}{' dict' if dic else ''}{'+entropy' if dic and DICT_ENTROPY else ''}"
     print(f"| {name:22s} | {n:6d} | {comp_bytes / total:.3f} | {ca * 1e3:8.1f} ({gbs(ca):6.2f}) | {cb * 1e3:7.2f} ({gbs(cb):6.1f}) | {cc * 1e3:7.2f} ({gbs(cc):6.1f}) "
           f"| {da * 1e3:8.1f} ({gbs(da):6.2f}) | {db * 1e3:7.2f} ({gbs(db):6.1f}) | {dc * 1e3:7.2f} ({gbs(dc):6.1f}) |", flush=True)
     print(f"    compress stages ms: {cst}\n    decompress stages ms: {dst_t}", flush=True)

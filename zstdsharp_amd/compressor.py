@@ -70,6 +70,7 @@ class Compressor(_PrefixHolder):
             ensure_zstd_success(self._lib, self._lib.ZSTDMI_CCtx_setDevice(self.cctx, device))
         self._level = 0
         self._seek_table = False
+        self._dict_entropy = False
         self.Level = level if level else self.DefaultCompressionLevel
 
     # ---- static members (S/Compressor.cs:8-10) ----
@@ -135,6 +136,17 @@ class Compressor(_PrefixHolder):
         self._ensure_not_disposed()
         ensure_zstd_success(self._lib, self._lib.ZSTDMI_CCtx_setSeekTable(self.cctx, 1 if on else 0))
         self._seek_table = bool(on)
+
+    # ---- dictionary entropy tables (ZSTDMI_CCtx_setDictEntropy): code first blocks with a formatted dictionary's tables; off by default ----
+    @property
+    def dict_entropy(self) -> bool:
+        return self._dict_entropy
+
+    @dict_entropy.setter
+    def dict_entropy(self, on):
+        self._ensure_not_disposed()
+        ensure_zstd_success(self._lib, self._lib.ZSTDMI_CCtx_setDictEntropy(self.cctx, 1 if on else 0))
+        self._dict_entropy = bool(on)
 
     # ---- Wrap (S/Compressor.cs:78-96) ----
     def Wrap(self, src, dest=None, offset: int = 0):

@@ -19,6 +19,7 @@
 //                     (U/ZstdDecompress.cs:1177-1184).
 //   frame_rescan    : only when some frame carries no content size: output offsets of the frames from their regenerated sizes.
 #include "zmi_decode.h"
+#include "zmi_fse.h"
 #include "zmi_host.h"
 
 namespace zmi {
@@ -979,6 +980,96 @@ __global__ __launch_bounds__(64) void dict_parse_kernel(const u8* __restrict__ d
 void launch_dict_parse(const u8* dict, u32 dictSize, DictInfo* out, hipStream_t stream)
 {
     hipLaunchKernelGGL(dict_parse_kernel, dim3(1), dim3(64), 0, stream, dict, dictSize, out);
+}
+
+// The same header as the COMPRESSOR uses it (ZSTD_loadCEntropy, U/ZstdCompress.cs:5259-5400), one wave, once per dictionary load:
+// the Huffman description becomes a code table (HUF_readCTable, U/HufCompress.cs:237-290: weights -> lengths -> canonical codes in
+// symbol order), the three NCounts become compression tables (FSE_buildCTable_wksp by the wave, straight into the record), and the
+// four repeat states say what a block may rely on: the Huffman table is `valid` without a zero weight and otherwise needs a look at
+// the block's literals; an FSE table is `valid` when every symbol up to the alphabet's maximum has a probability
+// (ZSTD_dictNCountRepeat, :5239-5257; for offsets the maximum follows from the content size).  The weights and NCount readers are
+// the decoder's.  `info` is what dict_parse_kernel left: the offsets are inside the dictionary.
+struct DictCtabScratch { DictScratch hs; s16 norm[3][64]; u32 dictMax[3], log[3], nbSymbols, hufLog, ok, valPerRank[14]; u16 cum[64]; u8 tableSymbol[512]; };
+__global__ __launch_bounds__(64) void dict_ctables_kernel(const u8* __restrict__ dict, u32 dictSize, const DictInfo* __restrict__ info,
+                                                          DictCTables* __restrict__ out)
+{
+    __shared__ DictCtabScratch S;
+    const u32 lane = threadIdx.x;
+    const DictInfo d = *info;
+    const bool sane = !d.err && d.hufOff < d.ofOff && d.ofOff < d.mlOff && d.mlOff < d.llOff && d.llOff < d.repOff && d.repOff <= dictSize;
+    for (u32 t = 0; t < 3; ++t) S.norm[t][lane] = 0;
+    if (lane == 0) { S.ok = 0; S.nbSymbols = 0; S.hufLog = 0; for (u32 t = 0; t < 3; ++t) { S.dictMax[t] = 0; S.log[t] = 5; } }
+    wave_lds_sync();
+    if (lane == 0 && sane) {
+        u32 nbSymbols = 0, hufLog = 0;
+        const u32 hs = huf_read_stats(S.hs, dict + d.hufOff, d.ofOff - d.hufOff, &nbSymbols, &hufLog);
+        // order of the record: LL, OF, ML
+        u32 mOF = 31, mML = 52, mLL = 35, lOF = 0, lML = 0, lLL = 0;
+        const u32 hOF = read_ncount(S.norm[1], &mOF, &lOF, dict + d.ofOff, d.mlOff - d.ofOff);
+        const u32 hML = read_ncount(S.norm[2], &mML, &lML, dict + d.mlOff, d.llOff - d.mlOff);
+        const u32 hLL = read_ncount(S.norm[0], &mLL, &lLL, dict + d.llOff, d.repOff - d.llOff);
+        if (hs && hufLog <= 12 && nbSymbols <= 256 && hOF && hML && hLL && mOF <= 31 && mML <= 52 && mLL <= 35 && lOF <= 8 && lML <= 9 && lLL <= 9) {
+            S.ok = 1; S.nbSymbols = nbSymbols; S.hufLog = hufLog;
+            S.dictMax[0] = mLL; S.dictMax[1] = mOF; S.dictMax[2] = mML; S.log[0] = lLL; S.log[1] = lOF; S.log[2] = lML;
+        }
+    }
+    wave_lds_sync();
+    const u32 ok = S.ok, nbSym = S.nbSymbols, hl = S.hufLog;
+    if (!ok) for (u32 t = 0; t < 3; ++t) S.norm[t][lane] = lane == 0 ? (s16)32 : (s16)0;      // (a table of one symbol: never used, never out of range)
+    wave_lds_sync();
+    {   // HUF_readCTable
+        u32 nb[4], pre[4]; bool zero = false;
+#pragma unroll
+        for (u32 k = 0; k < 4; ++k) {
+            const u32 sIdx = k * 64 + lane;
+            const u32 w = (ok && sIdx < nbSym) ? S.hs.weights[sIdx] : 0u;
+            nb[k] = w ? hl + 1 - w : 0u; pre[k] = 0;
+            zero |= ballot(sIdx < nbSym && w == 0) != 0;
+        }
+        u32 mn = 0;
+        for (u32 r = 12; r >= 1; r--) {
+            const u32 n = popc64(ballot(nb[0] == r)) + popc64(ballot(nb[1] == r)) + popc64(ballot(nb[2] == r)) + popc64(ballot(nb[3] == r));
+            if (lane == 0) S.valPerRank[r] = mn;
+            mn = (mn + n) >> 1;
+            u32 acc = 0;
+#pragma unroll
+            for (u32 k = 0; k < 4; ++k) {
+                const u64 b = ballot(nb[k] == r);
+                if (nb[k] == r) pre[k] = acc + popc64(b & lanemask_lt());
+                acc += popc64(b);
+            }
+        }
+        if (lane == 0) S.valPerRank[0] = 0;
+        wave_lds_sync();
+#pragma unroll
+        for (u32 k = 0; k < 4; ++k) {
+            const u32 sIdx = k * 64 + lane;
+            out->hufNbBits[sIdx] = (u8)nb[k];
+            out->hufCode[sIdx] = (u16)(nb[k] ? S.valPerRank[nb[k]] + pre[k] : 0u);
+        }
+        // (the encoder's tiles are sized for codes of at most 11 bits, the longest its own trees have: a longer table is not used)
+        if (lane == 0) out->hufMode = (ok && nbSym == 256 && hl <= 11) ? (zero ? kDictHufCheck : kDictHufValid) : kDictHufNone;
+    }
+    const u32 content = d.contentSize < (1u << 30) ? d.contentSize : (1u << 30);
+    u32 ofMax = highbit32(content + (128u << 10)); if (ofMax > 31) ofMax = 31;
+    for (u32 t = 0; t < 3; ++t) {
+        const u32 full = t == 0 ? 35u : t == 1 ? 31u : 52u, need = t == 1 ? ofMax : full;
+        u16* const st = t == 0 ? out->llState : t == 1 ? out->ofState : out->mlState;
+        SymTT* const tt = t == 0 ? out->llTT : t == 1 ? out->ofTT : out->mlTT;
+        const u32 log = ok ? S.log[t] : 5u;
+        const u64 present = ballot(lane <= S.dictMax[t] && S.norm[t][lane] != 0);
+        const u64 needMask = (2ull << need) - 1ull;
+        fse_build_ctable_wave(st, tt, S.norm[t], full, log, S.cum, S.tableSymbol, lane);
+        if (lane == 0) {
+            out->seqValid[t] = (ok && S.dictMax[t] >= need && (present & needMask) == needMask) ? 1u : 0u;
+            out->seqLog[t] = log; out->seqPresent[t] = ok ? present : 0ull;
+            if (t == 0) out->pad = 0;
+        }
+    }
+}
+void launch_dict_ctables(const u8* dict, u32 dictSize, const DictInfo* info, DictCTables* out, hipStream_t stream)
+{
+    hipLaunchKernelGGL(dict_ctables_kernel, dim3(1), dim3(64), 0, stream, dict, dictSize, info, out);
 }
 
 } // namespace zmi

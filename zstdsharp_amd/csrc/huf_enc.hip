@@ -401,6 +401,9 @@ __device__ __forceinline__ void hist_count_range(HufHistLds& L, const u8* __rest
 
 // Front half: the four per-stream histograms (they also size the four streams) and the sample maxima.  One wave per workgroup;
 // a wave takes (chunk, stream) items blockIdx.x, blockIdx.x + gridDim.x, ...
+// MINLIT: literals up to this many are stored raw whatever they hold — 63, or 6 where a dictionary's Huffman table may be reused
+// (huf_tree_kernel<true> decides per chunk; a histogram it does not need costs a few bytes of reading).
+template <u32 MINLIT>
 __global__ __launch_bounds__(64) void huf_hist_kernel(const u8* __restrict__ lits, const ChunkMeta* __restrict__ meta,
                                                       u8* __restrict__ slots, const u32 rawLiterals, const u8* __restrict__ src, const u32 chunkBytes,
                                                       const u32 nItems)
@@ -422,7 +425,7 @@ __global__ __launch_bounds__(64) void huf_hist_kernel(const u8* __restrict__ lit
         const u32 litSize = m0.litSize, nbSeqIn = m0.nbSeq;
         // ZSTD_compressLiterals: <= 63 literals are stored raw (no previous table in a one-block frame)
         // (rawLiterals: literal compression is off — the fast strategy with a step, i.e. negative levels; U/ZstdCompressInternal.cs:146-173)
-        if (litSize <= 63 || rawLiterals) continue;   // huf_tree_kernel stores them raw
+        if (litSize <= MINLIT || rawLiterals) continue;   // huf_tree_kernel stores them raw
         HufWork* __restrict__ W = reinterpret_cast<HufWork*>(slots + (u64)c * kSlotStride);
         // (a chunk without sequences never copied its literals: they are its source bytes, lz_fast.hip)
         const u8* __restrict__ lit = m0.litFromSrc ? src + (u64)c * chunkBytes : lits + (u64)c * kLitStride;
@@ -460,8 +463,16 @@ __global__ __launch_bounds__(64) void huf_hist_kernel(const u8* __restrict__ lit
 // Back half: the verdict and HUF_sort (parallel over the 256 symbols, four per lane), then the serial constructions
 // (HUF_buildTree, HUF_setMaxHeight, HUF_compressWeights) and the decisions.  One wave per chunk and 5.4 KiB of LDS, so
 // that ~29 chunks per CU hide each other's LDS latency.
+// DICT (ZSTDMI_CCtx_setDictEntropy with a formatted dictionary): the first block of a frame has the dictionary's Huffman table as its
+// previous table, and ZSTD_compressLiterals / HUF_compress_internal decide with it (U/ZstdCompressLiterals.cs:86-185,
+// U/HufCompress.cs:1360-1543): raw up to 6 literals instead of 63 and a single stream up to 1023 when the table is `valid`; the
+// table as it is for <= 1024 literals (preferRepeat: every strategy here is below lazy) once it is known to cover them; else the
+// block's own tree unless the old table costs no more than the new one with its description.  What the old table costs follows
+// from the histograms in registers.  A block coded with it gets kLitTreeless and a copy of the dictionary's codes as its table.
+// The instance without DICT is the code from before the switch existed.
+template <bool DICT>
 __global__ __launch_bounds__(64) void huf_tree_kernel(ChunkMeta* __restrict__ meta, HufTable* __restrict__ tables, const u8* __restrict__ slots,
-                                                      const u32 rawLiterals)
+                                                      const u32 rawLiterals, const DictCTables* __restrict__ dct, const u32 frameBlocks)
 {
     __shared__ HufTreeLds L;
     const u32 c = blockIdx.x, lane = threadIdx.x, tid = lane;
@@ -478,13 +489,16 @@ __global__ __launch_bounds__(64) void huf_tree_kernel(ChunkMeta* __restrict__ me
 #ifdef ZMI_LZ_STAMPS
     unsigned long long stampAcc[10] = {0,0,0,0,0,0,0,0,0,0}; unsigned long long stampLast = __builtin_amdgcn_s_memtime();
 #endif
+    // the dictionary's table stands behind a frame's first block only (a later block never writes a treeless section)
+    u32 dMode = kDictHufNone;
+    if (DICT) { if ((frameBlocks ? c % frameBlocks : 0u) == 0) dMode = dct->hufMode; }
     // ZSTD_compressLiterals: <= 63 literals are stored raw (no previous table in a one-block frame)
-    if (litSize <= 63 || rawLiterals) {        // (or ZSTD_noCompressLiterals because literal compression is disabled, U/ZstdCompressLiterals.cs:99-101)
+    if (litSize <= ((DICT && dMode == kDictHufValid) ? 6u : 63u) || rawLiterals) {        // (or ZSTD_noCompressLiterals because literal compression is disabled, U/ZstdCompressLiterals.cs:99-101)
         if (tid == 0) store_section(kLitRaw, lhSizeRaw, lhSizeRaw + litSize);
         return;
     }
     const u32 lhSize = 3 + (litSize >= 1024) + (litSize >= 16384);
-    const u32 single = litSize < 256;
+    const u32 single = litSize < 256 || (DICT && dMode == kDictHufValid && lhSize == 3);
     HufTable* T = tables + c;
     u32 hst[4][4], cnt[4];          // [stream][k]: symbol k * 64 + lane
 #pragma unroll
@@ -493,8 +507,26 @@ __global__ __launch_bounds__(64) void huf_tree_kernel(ChunkMeta* __restrict__ me
 #pragma unroll
         for (u32 w = 0; w < 4; ++w) { hst[w][k] = W->hist[w][k * 64 + lane]; cnt[k] += hst[w][k]; }
     }
+    // what the dictionary's table makes of the four streams, and whether it has a code for every literal that occurs
+    u32 dictBits[4] = { 0, 0, 0, 0 };
+    bool useOld = false, oldUsable = false;
+    if (DICT && dMode != kDictHufNone) {
+        u32 dnb[4]; bool covered = true;
+#pragma unroll
+        for (u32 k = 0; k < 4; ++k) { dnb[k] = dct->hufNbBits[k * 64 + lane]; covered &= ballot(cnt[k] != 0 && dnb[k] == 0) == 0; }
+#pragma unroll
+        for (u32 w = 0; w < 4; ++w) {
+            u32 bits = 0;
+#pragma unroll
+            for (u32 k = 0; k < 4; ++k) bits += hst[w][k] * dnb[k];
+            dictBits[w] = wave_sum(bits);
+        }
+        oldUsable = covered;                                        // (a `valid` table covers every byte: HUF_validateCTable for `check`)
+        useOld = dMode == kDictHufValid && covered && litSize <= 1024;      // preferRepeat with a valid table: no look at the literals
+    }
     u32 shCompressed = 1, maxSV = 0, shRle = 0, shRleByte = 0;
-    {   // compressible at all?  (HUF_compress_internal, U/HufCompress.cs:1412-1462) — uniform
+    if (DICT && useOld) shCompressed = 0;
+    else {   // compressible at all?  (HUF_compress_internal, U/HufCompress.cs:1412-1462) — uniform
         u32 largest = cnt[0];
 #pragma unroll
         for (u32 k = 0; k < 4; ++k) {
@@ -512,6 +544,7 @@ __global__ __launch_bounds__(64) void huf_tree_kernel(ChunkMeta* __restrict__ me
             for (u32 k = 0; k < 4; ++k) { const u64 b = ballot(cnt[k] == litSize); if (b) shRleByte = k * 64 + ctz64(b); }
         }
         else if (largest <= (litSize >> 7) + 4) shCompressed = 0;
+        if (DICT && shCompressed && oldUsable && litSize <= 1024) { useOld = true; shCompressed = 0; }      // preferRepeat after the check
     }
     u32 huffLog = 0;
     u32 streamBits[4] = { 0, 0, 0, 0 };
@@ -640,7 +673,8 @@ __global__ __launch_bounds__(64) void huf_tree_kernel(ChunkMeta* __restrict__ me
     }
     u32 wsWave = 0;
     if (shCompressed) wsWave = huf_compress_weights_wave(L, T->hdr + 1, maxSV, lane);      // (uniform branch, uniform result)
-    if (tid != 0) return;
+    if (!DICT && tid != 0) return;      // (DICT: every lane takes the same decisions, lane 0 stores them, the wave copies the table)
+    const bool lead = !DICT || tid == 0;
 
     // ---------------- remaining serial section: tree description + decisions ----------------
     bool compressed = shCompressed != 0;
@@ -648,17 +682,29 @@ __global__ __launch_bounds__(64) void huf_tree_kernel(ChunkMeta* __restrict__ me
     u32 hSize = 0, cLitSize = 0;
     u32 streamSize[4] = { 0, 0, 0, 0 };
     if (compressed) {
-        T->maxSV = maxSV; T->tableLog = huffLog;
+        if (lead) { T->maxSV = maxSV; T->tableLog = huffLog; }
         const u32 ws = wsWave;
-        if (ws > 1 && ws < maxSV / 2) { T->hdr[0] = (u8)ws; hSize = ws + 1; }
+        if (ws > 1 && ws < maxSV / 2) { if (lead) T->hdr[0] = (u8)ws; hSize = ws + 1; }
         else if (maxSV > 128) { compressed = false; }     // HUF_writeCTable_wksp fails -> ZSTD_compressLiterals stores raw
         else {
-            T->hdr[0] = (u8)(128 + (maxSV - 1));
-            L.weights[maxSV] = 0;
-            for (u32 n = 0; n < maxSV; n += 2) T->hdr[(n / 2) + 1] = (u8)((L.weights[n] << 4) + L.weights[n + 1]);
+            if (lead) {
+                T->hdr[0] = (u8)(128 + (maxSV - 1));
+                L.weights[maxSV] = 0;
+                for (u32 n = 0; n < maxSV; n += 2) T->hdr[(n / 2) + 1] = (u8)((L.weights[n] << 4) + L.weights[n + 1]);
+            }
             hSize = ((maxSV + 1) / 2) + 1;
         }
-        if (compressed && hSize + 12 >= litSize) compressed = false;
+        if (DICT && compressed && oldUsable) {      // the old table unless the new one pays for its description (HUF_estimateCompressedSize: bits >> 3)
+            const u32 oldSize = (dictBits[0] + dictBits[1] + dictBits[2] + dictBits[3]) >> 3;
+            const u32 newSize = (streamBits[0] + streamBits[1] + streamBits[2] + streamBits[3]) >> 3;
+            if (oldSize <= hSize + newSize || hSize + 12 >= litSize) useOld = true;
+        }
+        if (compressed && !(DICT && useOld) && hSize + 12 >= litSize) compressed = false;
+    }
+    if (DICT && useOld) {
+        compressed = true; hSize = 0;
+#pragma unroll
+        for (u32 w = 0; w < 4; w++) streamBits[w] = dictBits[w];
     }
     if (compressed) {
         if (single) {
@@ -678,18 +724,24 @@ __global__ __launch_bounds__(64) void huf_tree_kernel(ChunkMeta* __restrict__ me
         if (compressed && cLitSize >= litSize - 1) compressed = false;                     // HUF_compressCTable_internal
         if (compressed && cLitSize >= litSize - min_gain(litSize)) compressed = false;     // ZSTD_compressLiterals
     }
-    if (compressed) {
-        store_section(kLitCompressed, lhSize, lhSize + cLitSize);
-        mOut->litSingle = single; mOut->hufHdrSize = hSize;
-        mOut->streamSize[0] = streamSize[0]; mOut->streamSize[1] = streamSize[1]; mOut->streamSize[2] = streamSize[2]; mOut->streamSize[3] = streamSize[3];
-    } else if (rle) {
-        store_section(kLitRle, lhSizeRaw, lhSizeRaw + 1); mOut->rleByte = shRleByte;
-    } else {
-        store_section(kLitRaw, lhSizeRaw, lhSizeRaw + litSize);
+    if (lead) {
+        if (compressed) {
+            store_section((DICT && useOld) ? kLitTreeless : kLitCompressed, lhSize, lhSize + cLitSize);
+            mOut->litSingle = single; mOut->hufHdrSize = hSize;
+            mOut->streamSize[0] = streamSize[0]; mOut->streamSize[1] = streamSize[1]; mOut->streamSize[2] = streamSize[2]; mOut->streamSize[3] = streamSize[3];
+        } else if (rle) {
+            store_section(kLitRle, lhSizeRaw, lhSizeRaw + 1); mOut->rleByte = shRleByte;
+        } else {
+            store_section(kLitRaw, lhSizeRaw, lhSizeRaw + litSize);
+        }
+    }
+    if (DICT && useOld && compressed) {     // huf_encode_kernel reads the chunk's table as ever
+#pragma unroll
+        for (u32 k = 0; k < 4; ++k) { const u32 sIdx = k * 64 + lane; T->nbBits[sIdx] = dct->hufNbBits[sIdx]; T->code[sIdx] = dct->hufCode[sIdx]; }
     }
     ZMI_HSTAMP(7);
 #ifdef ZMI_LZ_STAMPS
-    for (int i = 1; i < 10; i++) atomicAdd(&g_hufStamps[i], stampAcc[i]);
+    if (tid == 0) for (int i = 1; i < 10; i++) atomicAdd(&g_hufStamps[i], stampAcc[i]);
 #endif
 }
 
@@ -807,6 +859,10 @@ __device__ __forceinline__ void huf_encode_tile(const u32* __restrict__ ct, u32*
 
 // `dst` != nullptr: the literals section goes straight to its final place in the output (offsets[] from the scan; the
 // sequences section and the headers follow through gather_kernel); nullptr: into the chunk's slot (test hook).
+// DICT: a kLitTreeless chunk is coded like a compressed one — its table is the dictionary's, copied by huf_tree_kernel<true> — under
+// literals type 3 and without a tree description; its single stream may hold up to 1023 symbols (less than one tile).  Without
+// DICT such a record is not expected and stored raw, as any unknown mode.
+template <bool DICT>
 __global__ __launch_bounds__(256) void huf_encode_kernel(const u8* __restrict__ lits, const ChunkMeta* __restrict__ meta,
                                                          const HufTable* __restrict__ tables, u8* __restrict__ slots,
                                                          u8* __restrict__ dst, const u64* __restrict__ offsets, u64 dstCapacity,
@@ -828,7 +884,8 @@ __global__ __launch_bounds__(256) void huf_encode_kernel(const u8* __restrict__ 
         body = dst + off + m.fhSize + 3;
     }
 
-    if (m.litMode != kLitCompressed) {
+    const bool treeless = DICT && m.litMode == kLitTreeless;
+    if (m.litMode != kLitCompressed && !treeless) {
         // ZSTD_noCompressLiterals / ZSTD_compressRleLiteralsBlock (U/ZstdCompressLiterals.cs:8-83)
         const u32 type = m.litMode == kLitRle ? 1u : 0u;
         if (tid == 0) {
@@ -858,14 +915,16 @@ __global__ __launch_bounds__(256) void huf_encode_kernel(const u8* __restrict__ 
     uint4 packNext = load_pack(0);
     if (tid == 0) {
         const u32 cLitSize = m.litSectionSize - m.lhSize;
+        const u32 hType = treeless ? 3u : 2u;
         switch (m.lhSize) {       // ZSTD_compressLiterals header (U/ZstdCompressLiterals.cs:150-182)
-        case 3: writeLE24(body, 2u + ((m.litSingle ? 0u : 1u) << 2) + (litSize << 4) + (cLitSize << 14)); break;
-        case 4: writeLE32(body, 2u + (2u << 2) + (litSize << 4) + (cLitSize << 18)); break;
-        default: writeLE32(body, 2u + (3u << 2) + (litSize << 4) + (cLitSize << 22)); body[4] = (u8)(cLitSize >> 10); break;
+        case 3: writeLE24(body, hType + ((m.litSingle ? 0u : 1u) << 2) + (litSize << 4) + (cLitSize << 14)); break;
+        case 4: writeLE32(body, hType + (2u << 2) + (litSize << 4) + (cLitSize << 18)); break;
+        default: writeLE32(body, hType + (3u << 2) + (litSize << 4) + (cLitSize << 22)); body[4] = (u8)(cLitSize >> 10); break;
         }
     }
-    for (u32 i = tid; i < m.hufHdrSize; i += 256) body[m.lhSize + i] = T->hdr[i];
-    u8* payload = body + m.lhSize + m.hufHdrSize;
+    const u32 hufHdrSize = treeless ? 0u : m.hufHdrSize;
+    for (u32 i = tid; i < hufHdrSize; i += 256) body[m.lhSize + i] = T->hdr[i];
+    u8* payload = body + m.lhSize + hufHdrSize;
     if (!m.litSingle && tid < 3) writeLE16(payload + 2 * tid, meta[c].streamSize[tid]);       // jump table
     __syncthreads();
 
@@ -901,21 +960,25 @@ __global__ __launch_bounds__(256) void huf_encode_kernel(const u8* __restrict__ 
     }
 }
 
+// dct != nullptr: the first block of every frame (frameBlocks as in seq_encode: 0 = every chunk a frame) may reuse the dictionary's table
 void launch_huf_build(const u8* lits, ChunkMeta* meta, HufTable* tables, u8* slots, u32 nChunks, u32 rawLiterals, const u8* src, u32 chunkBytes,
-                      hipStream_t stream, StageHook hook)
+                      hipStream_t stream, StageHook hook, const DictCTables* dct, u32 frameBlocks)
 {
     // a throughput kernel: a wave per (chunk, stream) item while that keeps every CU's share short, several items per wave beyond
     const u32 nItems = 4 * nChunks, perWave = (nItems + kHistItemsPerWave - 1) / kHistItemsPerWave;
     const u32 grid = nItems <= kHistMinGrid ? nItems : (perWave > kHistMinGrid ? perWave : kHistMinGrid);
-    hipLaunchKernelGGL(huf_hist_kernel, dim3(grid), dim3(64), 0, stream, lits, meta, slots, rawLiterals, src, chunkBytes, nItems);
+    if (dct) hipLaunchKernelGGL(huf_hist_kernel<6>, dim3(grid), dim3(64), 0, stream, lits, meta, slots, rawLiterals, src, chunkBytes, nItems);
+    else hipLaunchKernelGGL(huf_hist_kernel<63>, dim3(grid), dim3(64), 0, stream, lits, meta, slots, rawLiterals, src, chunkBytes, nItems);
     hook("huf_hist");
-    hipLaunchKernelGGL(huf_tree_kernel, dim3(nChunks), dim3(64), 0, stream, meta, tables, slots, rawLiterals);
+    if (dct) hipLaunchKernelGGL(huf_tree_kernel<true>, dim3(nChunks), dim3(64), 0, stream, meta, tables, slots, rawLiterals, dct, frameBlocks);
+    else hipLaunchKernelGGL(huf_tree_kernel<false>, dim3(nChunks), dim3(64), 0, stream, meta, tables, slots, rawLiterals, dct, frameBlocks);
     hook("huf_tree");
 }
 void launch_huf_encode(const u8* lits, const ChunkMeta* meta, const HufTable* tables, u8* slots, u8* dst, const u64* offsets, u64 dstCapacity,
-                       u32 nChunks, const u8* src, u32 chunkBytes, hipStream_t stream)
+                       u32 nChunks, const u8* src, u32 chunkBytes, hipStream_t stream, bool dictEntropy)
 {
-    hipLaunchKernelGGL(huf_encode_kernel, dim3(nChunks), dim3(256), 0, stream, lits, meta, tables, slots, dst, offsets, dstCapacity, src, chunkBytes);
+    if (dictEntropy) hipLaunchKernelGGL(huf_encode_kernel<true>, dim3(nChunks), dim3(256), 0, stream, lits, meta, tables, slots, dst, offsets, dstCapacity, src, chunkBytes);
+    else hipLaunchKernelGGL(huf_encode_kernel<false>, dim3(nChunks), dim3(256), 0, stream, lits, meta, tables, slots, dst, offsets, dstCapacity, src, chunkBytes);
 }
 
 // ---- the entropy tables of a trained dictionary (ZDICT_analyzeEntropy, U/Zdict.cs:174-408), one wave ----

@@ -57,22 +57,31 @@ struct SeqTable { const u16* state; const SymTT* tt; u32 tableLog; };
 
 // ZSTD_selectEncodingType + ZSTD_buildCTable for one of LL/OF/ML, whole wave: the decisions, FSE_normalizeCount and
 // FSE_writeNCount run on lane 0 (short), the table itself is built by all lanes.  Returns bytes written to `op` (uniform).
+// DICT with dState != nullptr (the dictionary's table for this alphabet is `valid`, and this is a frame's first block): set_repeat
+// comes before set_basic where defaults are allowed and the block has fewer than 1000 sequences (ZSTD_selectEncodingType's branch
+// below lazy, U/ZstdCompressSequences.cs:400-469); the table and the transforms are then copied from the record into the wave's
+// LDS arrays, nothing is described, and lastCountSize stays what the last COMPRESSED description left.  dPresent (bit s: the
+// dictionary's table gives symbol s a probability) is checked against the block's codes all the same: a `valid` table has them all.
+template <bool DICT>
 __device__ __forceinline__ u32 build_seq_table(SeqWaveLds& W, u8* op, u32* count, u32 maxPossible, u32 FSELog, u32 nbSeq, u32 lastCode,
                                                const s16* defaultNorm, u32 defaultNormLog, u32 defaultMax, bool defaultAllowedByMax,
-                                               u32 strategy, u16* stateTable, SymTT* tt, u32* typeOut, u32* tableLogOut, u32* lastCountSize, u32 lane)
+                                               u32 strategy, u16* stateTable, SymTT* tt, u32* typeOut, u32* tableLogOut, u32* lastCountSize, u32 lane,
+                                               const u16* __restrict__ dState, const SymTT* __restrict__ dTT, u32 dLog, u64 dPresent)
 {
     u32 type = 0, max = 0, tableLog = 0, n = 0;
     if (lane == 0) {
         u32 mostFrequent = 0; max = maxPossible;
         while (!count[max]) max--;
-        for (u32 s = 0; s <= max; s++) if (count[s] > mostFrequent) mostFrequent = count[s];
+        u64 used = 0;
+        for (u32 s = 0; s <= max; s++) { if (count[s] > mostFrequent) mostFrequent = count[s]; if (DICT && count[s]) used |= 1ull << s; }
         const bool isDefaultAllowed = defaultAllowedByMax ? (max <= defaultMax) : true;
         if (mostFrequent == nbSeq) type = (isDefaultAllowed && nbSeq <= 2) ? 0 : 1;
         else {
             type = 2;
             if (isDefaultAllowed) {
                 const u32 mult = 10 - strategy, dynamicFse_nbSeq_min = ((1u << defaultNormLog) * mult) >> 3;
-                if (nbSeq < dynamicFse_nbSeq_min || mostFrequent < (nbSeq >> (defaultNormLog - 1))) type = 0;
+                if (DICT && dState && nbSeq < 1000 && (used & ~dPresent) == 0) type = 3;
+                else if (nbSeq < dynamicFse_nbSeq_min || mostFrequent < (nbSeq >> (defaultNormLog - 1))) type = 0;
             }
         }
         if (type == 1) {        // set_rle: FSE_buildCTable_rle
@@ -83,6 +92,8 @@ __device__ __forceinline__ u32 build_seq_table(SeqWaveLds& W, u8* op, u32* count
         } else if (type == 0) { // set_basic
             for (u32 s = 0; s <= defaultMax; s++) W.norm[s] = defaultNorm[s];
             max = defaultMax; tableLog = defaultNormLog;
+        } else if (DICT && type == 3) {     // set_repeat
+            tableLog = dLog;
         } else {                // set_compressed
             u32 nbSeq_1 = nbSeq;
             tableLog = fse_optimal_table_log(FSELog, nbSeq, max, 2);
@@ -93,16 +104,25 @@ __device__ __forceinline__ u32 build_seq_table(SeqWaveLds& W, u8* op, u32* count
     }
     type = uniform(type); max = uniform(max); tableLog = uniform(tableLog); n = uniform(n);
     wave_lds_sync();
-    if (type != 1) fse_build_ctable_wave(stateTable, tt, W.norm, max, tableLog, W.cumul, W.tableSymbol, lane);
+    if (DICT && type == 3) {
+        for (u32 i = lane; i < (1u << tableLog); i += 64) stateTable[i] = dState[i];
+        if (lane <= maxPossible) tt[lane] = dTT[lane];
+        wave_lds_sync();
+    }
+    else if (type != 1) fse_build_ctable_wave(stateTable, tt, W.norm, max, tableLog, W.cumul, W.tableSymbol, lane);
     *typeOut = type; *tableLogOut = tableLog;
     if (type == 2) *lastCountSize = n;
     return n;
 }
 
+// DICT (ZSTDMI_CCtx_setDictEntropy with a formatted dictionary): a frame's first block may take the dictionary's LL / OF / ML tables
+// as they are (mode 3, build_seq_table); the instance without DICT is the code from before the switch existed.
+template <bool DICT>
 __global__ __launch_bounds__(256) void seq_encode_kernel(Seq* __restrict__ seqs, ChunkMeta* __restrict__ meta,
                                                          u8* __restrict__ slots, u32 nChunks, u32 strategy, u32 checksumFlag, u32 resolveReps,
                                                          u32 dictID, u32 dictIdBytes, u32 initRep0, u32 initRep1, u32 initRep2,
-                                                         const u32 frameBlocks, const u32 chunkBytes, const u64 srcSize)
+                                                         const u32 frameBlocks, const u32 chunkBytes, const u64 srcSize,
+                                                         const DictCTables* __restrict__ dct)
 {
     __shared__ SeqWaveLds Ws[4];
     __shared__ u32 sBatchSeq[4];          // sequences each of the four chunks sends through the state chains (0: none)
@@ -112,7 +132,7 @@ __global__ __launch_bounds__(256) void seq_encode_kernel(Seq* __restrict__ seqs,
     const bool live = c < nChunks;        // (a wave without a chunk still meets the workgroup's barriers below)
     SeqWaveLds& W = Ws[wave];
     ChunkMeta m = {};
-    if (live) m = meta_checked(meta[c]);
+    if (live) m = meta_checked<false>(meta[c]);
     const u32 nbSeq = m.nbSeq, n = m.srcSize;
     // Multi-block frames (row f-1): chunk c is block bf of frame c / frameBlocks.  A later block never relies on the repcodes the
     // blocks before it leave behind — whether one of them ends up stored raw (and so leaves the decoder's history untouched,
@@ -209,9 +229,25 @@ __global__ __launch_bounds__(256) void seq_encode_kernel(Seq* __restrict__ seqs,
         const Seq last = sq[nbSeq - 1];
         const u32 lastLL = ll_code(last.litLength), lastOF = highbit32(last.offBase), lastML = ml_code(last.mlBase);
         u32 LLtype, OFtype, MLtype, llLog, ofLog, mlLog, lastCountSize = 0;
-        op += build_seq_table(W, op, W.count[0], 35, 9, nbSeq, lastLL, cLL_defaultNorm, 6, 35, false, strategy, W.llState, W.llTT, &LLtype, &llLog, &lastCountSize, lane);
-        op += build_seq_table(W, op, W.count[1], 31, 8, nbSeq, lastOF, cOF_defaultNorm, 5, 28, true,  strategy, W.ofState, W.ofTT, &OFtype, &ofLog, &lastCountSize, lane);
-        op += build_seq_table(W, op, W.count[2], 52, 9, nbSeq, lastML, cML_defaultNorm, 6, 52, false, strategy, W.mlState, W.mlTT, &MLtype, &mlLog, &lastCountSize, lane);
+        // the dictionary's tables stand behind a frame's first block only, each where ZSTD_loadCEntropy found it `valid`
+        const u16 *dLL = nullptr, *dOF = nullptr, *dML = nullptr;
+        u32 dLogLL = 0, dLogOF = 0, dLogML = 0; u64 dHasLL = 0, dHasOF = 0, dHasML = 0;
+        if (DICT && bf == 0) {
+            if (dct->seqValid[0]) dLL = dct->llState;
+            if (dct->seqValid[1]) dOF = dct->ofState;
+            if (dct->seqValid[2]) dML = dct->mlState;
+            dLogLL = dct->seqLog[0]; dLogOF = dct->seqLog[1]; dLogML = dct->seqLog[2];
+            dHasLL = dct->seqPresent[0]; dHasOF = dct->seqPresent[1]; dHasML = dct->seqPresent[2];
+            if (dLogLL > 9) dLogLL = 9;         // (what the LDS arrays hold; dict_ctables_kernel never writes more)
+            if (dLogOF > 8) dLogOF = 8;
+            if (dLogML > 9) dLogML = 9;
+        }
+        op += build_seq_table<DICT>(W, op, W.count[0], 35, 9, nbSeq, lastLL, cLL_defaultNorm, 6, 35, false, strategy, W.llState, W.llTT, &LLtype, &llLog, &lastCountSize, lane,
+                                    dLL, DICT ? dct->llTT : nullptr, dLogLL, dHasLL);
+        op += build_seq_table<DICT>(W, op, W.count[1], 31, 8, nbSeq, lastOF, cOF_defaultNorm, 5, 28, true,  strategy, W.ofState, W.ofTT, &OFtype, &ofLog, &lastCountSize, lane,
+                                    dOF, DICT ? dct->ofTT : nullptr, dLogOF, dHasOF);
+        op += build_seq_table<DICT>(W, op, W.count[2], 52, 9, nbSeq, lastML, cML_defaultNorm, 6, 52, false, strategy, W.mlState, W.mlTT, &MLtype, &mlLog, &lastCountSize, lane,
+                                    dML, DICT ? dct->mlTT : nullptr, dLogML, dHasML);
         // lastCountSize must be the size of the LAST compressed table description (U/ZstdCompress.cs:3196-3224)
         if (lane == 0) *seqHead = (u8)((LLtype << 6) + (OFtype << 4) + (MLtype << 2));
 
@@ -412,10 +448,13 @@ __global__ __launch_bounds__(256) void seq_encode_kernel(Seq* __restrict__ seqs,
 }
 
 void launch_seq_encode(Seq* seqs, ChunkMeta* meta, u8* slots, u32 nChunks, u32 strategy, u32 checksumFlag, u32 resolveReps,
-                       u32 dictID, u32 dictIdBytes, const u32* initReps, u32 frameBlocks, u32 chunkBytes, u64 srcSize, hipStream_t stream)
+                       u32 dictID, u32 dictIdBytes, const u32* initReps, u32 frameBlocks, u32 chunkBytes, u64 srcSize, hipStream_t stream,
+                       const DictCTables* dct)
 {
-    hipLaunchKernelGGL(seq_encode_kernel, dim3((nChunks + 3) / 4), dim3(256), 0, stream, seqs, meta, slots, nChunks, strategy, checksumFlag, resolveReps,
-                       dictID, dictIdBytes, initReps[0], initReps[1], initReps[2], frameBlocks, chunkBytes, srcSize);
+    if (dct) hipLaunchKernelGGL(seq_encode_kernel<true>, dim3((nChunks + 3) / 4), dim3(256), 0, stream, seqs, meta, slots, nChunks, strategy, checksumFlag, resolveReps,
+                                dictID, dictIdBytes, initReps[0], initReps[1], initReps[2], frameBlocks, chunkBytes, srcSize, dct);
+    else hipLaunchKernelGGL(seq_encode_kernel<false>, dim3((nChunks + 3) / 4), dim3(256), 0, stream, seqs, meta, slots, nChunks, strategy, checksumFlag, resolveReps,
+                            dictID, dictIdBytes, initReps[0], initReps[1], initReps[2], frameBlocks, chunkBytes, srcSize, dct);
 }
 
 #ifdef ZMI_LZ_STAMPS

@@ -28,7 +28,8 @@ constexpr u32 kMaxSeq     = kChunkSize / 4;        // a sequence consumes >= 4 i
 // one stored sequence: same meaning as the reference's seqDef_s (U/seqDef_s.cs)
 struct Seq { u32 offBase; u16 litLength; u16 mlBase; };   // offBase 1..3 repcode, >=4 distance+3 ; mlBase = matchLength-3
 
-enum LitMode : u32 { kLitRaw = 0, kLitRle = 1, kLitCompressed = 2 };
+// kLitTreeless: Huffman-coded with the formatted dictionary's table (literals type 3, no tree description; ZSTDMI_CCtx_setDictEntropy)
+enum LitMode : u32 { kLitRaw = 0, kLitRle = 1, kLitCompressed = 2, kLitTreeless = 3 };
 
 // per-chunk record that travels between the pipeline's kernels (HBM resident)
 struct ChunkMeta {
@@ -60,6 +61,27 @@ struct HufTable {
     u8  nbBits[256];
     u8  hdr[132];       // tree description as written by HUF_writeCTable (<= 129 bytes)
     u32 maxSV, tableLog;
+};
+
+// one symbol's transform of an FSE compression table (FSE_symbolCompressionTransform, U/FseCompress.cs:13-191)
+struct SymTT { s32 deltaFindState; u32 deltaNbBits; };
+
+// A formatted dictionary's entropy tables as the compressor uses them (ZSTD_loadCEntropy, U/ZstdCompress.cs:5259-5400), built once
+// per dictionary load by dict_ctables_kernel and read by every chunk of a call with ZSTDMI_CCtx_setDictEntropy on (it stays in L2).
+// The Huffman table is in HufTable's layout (canonical codes as HUF_readCTable assigns them), the three FSE tables in the layout
+// seq_encode_kernel keeps in LDS.  The four repeat states: hufMode, and seqValid[] in the order LL, OF, ML.
+enum : u32 { kDictHufNone = 0, kDictHufCheck = 1, kDictHufValid = 2 };
+struct DictCTables {
+    u16 hufCode[256];
+    u8  hufNbBits[256];
+    u32 hufMode;            // kDictHufValid: no zero weight; kDictHufCheck: every literal of a block must have a code; kDictHufNone: the
+                            // table cannot be used (fewer than 256 symbols, or codes longer than the encoder's 11 bits)
+    u32 seqValid[3];        // 1 = FSE_repeat_valid: set_repeat may be chosen without looking at the block's codes
+    u32 seqLog[3];          // tableLog
+    u32 pad;
+    u64 seqPresent[3];      // bit s: symbol s has a probability in the table
+    u16 llState[512], mlState[512], ofState[256];
+    SymTT llTT[36], mlTT[53], ofTT[32];
 };
 
 // ---- decoder side ----

@@ -58,12 +58,17 @@ __device__ __forceinline__ void writeLE32(u8* p, u32 v) { p[0] = (u8)v; p[1] = (
 
 // What the entropy stage may rely on in a ChunkMeta whatever the match finder left there (a finder bug, or an experiment build
 // without its emit phase, must not turn into out-of-bounds addresses downstream): sizes inside the chunk's buffers; a record that
-// breaks them is taken as "no sequences".  Every consumer applies the same function, so all of them see the same chunk.
+// breaks them is taken as "no sequences"; a literals mode that is none of LitMode's is taken as raw.  Every consumer applies the same
+// function, so all of them see the same chunk.  LITMODE = false is for seq_encode_kernel alone, which never reads the mode and writes
+// the record back whole: touching the field there made the compiler split the record differently (16 bytes of scratch less, 12 bytes
+// of LDS per thread more — a workgroup less per CU); the kernels behind it bound the mode themselves when they read the record.
+template <bool LITMODE = true>
 __device__ __forceinline__ ChunkMeta meta_checked(ChunkMeta m)
 {
     if (m.srcSize > kChunkSize) m.srcSize = kChunkSize;
     if (m.nbSeq > kMaxSeq || m.litSize > m.srcSize) { m.nbSeq = 0; if (m.litSize > m.srcSize) m.litSize = m.srcSize; }
     if (m.fhSize > 18) m.fhSize = 18;
+    if (LITMODE && m.litMode > kLitTreeless) m.litMode = kLitRaw;
     return m;
 }
 

@@ -13,8 +13,6 @@
 
 namespace zmi {
 
-struct SymTT { s32 deltaFindState; u32 deltaNbBits; };
-
 __device__ __forceinline__ u32 fse_min_table_log(u32 srcSize, u32 maxSV)
 {
     const u32 a = highbit32(srcSize) + 1, b = highbit32(maxSV) + 2;

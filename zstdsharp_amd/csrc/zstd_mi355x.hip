@@ -32,8 +32,11 @@ struct ZSTD_CCtx_s {
     // dictionary (ZSTD_CCtx_loadDictionary).  dictHost = the history bytes: the last kDictKeep bytes of a raw-content dictionary
     // or of a formatted dictionary's content; host copy + device copy made at the next compression.  A formatted dictionary
     // (dictFull, validated on the device into `info`) also gives the frames their dictID and the first repcodes; its entropy
-    // tables are not used (every block carries its own), which any decoder holding the dictionary accepts.
-    std::vector<u8> dictHost, dictFull; DevBuf dict, dictFullDev, dictInfoDev; bool dictDirty = false, dictFormatted = false;
+    // tables are not used (every block carries its own), which any decoder holding the dictionary accepts — unless
+    // ZSTDMI_CCtx_setDictEntropy turned them on: then dictCTabDev holds them as compression tables (dict_ctables_kernel, built with
+    // the dictionary's upload) and the first block of every frame is coded with them as its previous entropy state.
+    std::vector<u8> dictHost, dictFull; DevBuf dict, dictFullDev, dictInfoDev, dictCTabDev; bool dictDirty = false, dictFormatted = false;
+    int dictEntropy = 0;        // ZSTDMI_CCtx_setDictEntropy (sticky)
     DictInfo info = {};
     u64 dictGen = 0;            // bumped by every ZSTD_CCtx_loadDictionary: device workers copy the dictionary when theirs is older
     // ZSTDMI_CCtx_setDevices: one worker context per listed device (its own stream and workspaces there); a call's frames are
@@ -78,6 +81,7 @@ struct CallParams {
     int ldm = 0, ldmHashLog = 0, ldmMinMatch = 0, ldmBucketSizeLog = 0, ldmHashRateLog = 0;     // (ZSTD_compressCCtx: all 0, as the reference's level-only parameters)
     bool useDict = true;
     bool seek = false;                  // append a seek table (ZSTDMI_CCtx_setSeekTable; ZSTD_compressCCtx: never, as it never runs LDM)
+    bool dictEntropy = false;           // code with a formatted dictionary's entropy tables (ZSTDMI_CCtx_setDictEntropy; ZSTD_compressCCtx uses no dictionary)
     const u8* pfx = nullptr; size_t pfxSize = 0;    // the long form of a referenced prefix (compress_prefixed): device bytes in front of the ONE frame
 };
 static CallParams sticky_params(const ZSTD_CCtx* c)
@@ -85,6 +89,7 @@ static CallParams sticky_params(const ZSTD_CCtx* c)
     CallParams p; p.level = c->level; p.checksumFlag = c->checksumFlag; p.contentSizeFlag = c->contentSizeFlag; p.dictIDFlag = c->dictIDFlag;
     p.strategy = c->strategy; p.targetLength = c->targetLength; p.windowLog = c->windowLog; p.searchLog = c->searchLog; p.minMatch = c->minMatch; p.chainLog = c->chainLog; p.useDict = true;
     p.seek = c->seekTable != 0;
+    p.dictEntropy = c->dictEntropy != 0;
     p.ldm = c->ldm; p.ldmHashLog = c->ldmHashLog; p.ldmMinMatch = c->ldmMinMatch; p.ldmBucketSizeLog = c->ldmBucketSizeLog; p.ldmHashRateLog = c->ldmHashRateLog;
     return p;
 }
@@ -142,6 +147,11 @@ static size_t cctx_sync_dictionary(ZSTD_CCtx* c)
         if (c->info.err) { c->dictFull.clear(); c->dictHost.clear(); c->dictFormatted = false; c->dictDirty = false; return ZERR(kErrDictionaryCorrupted); }
         const size_t keep = c->info.contentSize < kDictKeep ? c->info.contentSize : kDictKeep;
         c->dictHost.assign(c->dictFull.end() - (ptrdiff_t)keep, c->dictFull.end());
+        if (c->dictEntropy) {       // (the setter marks the dictionary dirty, so a switch turned on later builds them too)
+            if (!c->dictCTabDev.ensure(sizeof(DictCTables))) return ZERR(kErrMemoryAllocation);
+            launch_dict_ctables((const u8*)c->dictFullDev.p, (u32)n, (const DictInfo*)c->dictInfoDev.p, (DictCTables*)c->dictCTabDev.p, s);
+            if (isErr(stream_wait(s))) return ZERR(kErrGeneric);
+        }
     }
     if (!c->dictHost.empty()) {
         if (!c->dict.ensure(c->dictHost.size() + 64)) return ZERR(kErrMemoryAllocation);
@@ -150,6 +160,12 @@ static size_t cctx_sync_dictionary(ZSTD_CCtx* c)
     }
     c->dictDirty = false;
     return 0;
+}
+
+// the dictionary's compression tables for a call, or nullptr: the switch is on and a formatted dictionary is in use (synced before)
+static const DictCTables* call_dict_ctables(const ZSTD_CCtx* c, const CallParams& cp)
+{
+    return (cp.dictEntropy && cp.useDict && c->dictFormatted && c->dictCTabDev.p) ? (const DictCTables*)c->dictCTabDev.p : nullptr;
 }
 
 // How a range of paramSize bytes is cut into blocks and frames (a function of the parameters, the loaded dictionary and that size):
@@ -298,6 +314,7 @@ static size_t compress_range(ZSTD_CCtx* c, const CallParams& cp, u8* d_dst, size
     const u32 dictIdBytes = (dictID && cp.dictIDFlag) ? (dictID < 256 ? 1u : dictID < 65536 ? 2u : 4u) : 0u;
     const u32 plainReps[3] = { 1, 4, 8 };
     const u32* const initReps = fmtDict ? c->info.rep : plainReps;
+    const DictCTables* const dct = call_dict_ctables(c, cp);
     const u8* prefix = prefixLen ? (const u8*)c->dict.p + (c->dictHost.size() - prefixLen) : nullptr;
     const u64 totalChunks = (srcSize + chunkBytes - 1) / chunkBytes;
     u32 passChunks = (u32)(totalChunks < c->passChunks ? totalChunks : c->passChunks);
@@ -339,9 +356,9 @@ static size_t compress_range(ZSTD_CCtx* c, const CallParams& cp, u8* d_dst, size
                 launch_ldm_rest(src, nL, nChunks, chunkBytes, span, fr.ldmP, nSplits, (u8*)c->ldmSmall.p, (u8*)c->ldmBig.p, seqs, lits, meta, s, c->timer.hook(), lp);
             }
         }
-        launch_huf_build(lits, meta, tables, slots, nChunks, rs.rawLiterals, src, chunkBytes, s, c->timer.hook());
+        launch_huf_build(lits, meta, tables, slots, nChunks, rs.rawLiterals, src, chunkBytes, s, c->timer.hook(), dct, frameBlocks);
         if (cp.checksumFlag) { launch_xxh64(src, n, meta, nChunks, chunkBytes, frameBlocks, s);             c->timer.mark("xxh64", s); }
-        launch_seq_encode(seqs, meta, slots, nChunks, strategy, (cp.checksumFlag ? 1u : 0u) | (cp.contentSizeFlag ? 0u : 2u) | (hdrWindow << 8), 1, dictID, dictIdBytes, initReps, frameBlocks, chunkBytes, n, s);   c->timer.mark("seq_encode", s);
+        launch_seq_encode(seqs, meta, slots, nChunks, strategy, (cp.checksumFlag ? 1u : 0u) | (cp.contentSizeFlag ? 0u : 2u) | (hdrWindow << 8), 1, dictID, dictIdBytes, initReps, frameBlocks, chunkBytes, n, s, dct);   c->timer.mark("seq_encode", s);
         launch_scan_sizes(meta, nChunks, offsets, total, s);                       c->timer.mark("scan", s);
         if (c->seekOn) {        // the pass's frames into the call's seek table
             const u32 nFrames = (nChunks + (frameBlocks ? frameBlocks : 1u) - 1) / (frameBlocks ? frameBlocks : 1u);
@@ -351,7 +368,7 @@ static size_t compress_range(ZSTD_CCtx* c, const CallParams& cp, u8* d_dst, size
         }
         const size_t room = dstCapacity > produced ? dstCapacity - produced : 0;
         // the literals section (most of the output) is encoded straight into its final place; gather moves the rest
-        launch_huf_encode(lits, meta, tables, slots, d_dst + produced, offsets, room, nChunks, src, chunkBytes, s);   c->timer.mark("huf_encode", s);
+        launch_huf_encode(lits, meta, tables, slots, d_dst + produced, offsets, room, nChunks, src, chunkBytes, s, dct != nullptr);   c->timer.mark("huf_encode", s);
         launch_gather(src, n, slots, meta, offsets, d_dst + produced, room, nChunks, chunkBytes, s);      c->timer.mark("gather", s);
         u64 passTotal = 0;
         if (hipMemcpyAsync(&passTotal, total, sizeof(u64), hipMemcpyDeviceToHost, s) != hipSuccess) return ZERR(kErrGeneric);
@@ -587,7 +604,7 @@ size_t ZSTD_freeCCtx(ZSTD_CCtx* c)
         (void)hipSetDevice(c->device);
         if (c->ownStream) (void)hipStreamSynchronize(c->ownStream);
         c->seqs.release(); c->lits.release(); c->meta.release(); c->tables.release(); c->slots.release(); c->cand.release(); c->probe.release();
-        c->gatherIn.release(); c->gatherOut.release(); c->batchStage.release(); c->batchTab.release(); c->ldmSmall.release(); c->ldmBig.release(); c->offsets.release(); c->total.release(); c->seekEntries.release(); c->seekSort.release(); c->stageSrc.release(); c->stageDst.release(); c->pfxStage.release(); c->dict.release(); c->dictFullDev.release(); c->dictInfoDev.release();
+        c->gatherIn.release(); c->gatherOut.release(); c->batchStage.release(); c->batchTab.release(); c->ldmSmall.release(); c->ldmBig.release(); c->offsets.release(); c->total.release(); c->seekEntries.release(); c->seekSort.release(); c->stageSrc.release(); c->stageDst.release(); c->pfxStage.release(); c->dict.release(); c->dictFullDev.release(); c->dictInfoDev.release(); c->dictCTabDev.release();
         c->timer.destroy();
         if (c->ownStream) (void)hipStreamDestroy(c->ownStream);
     }
@@ -866,6 +883,7 @@ static size_t compress_multi(ZSTD_CCtx* c, const CallParams& cp, void* dst, size
     if (cp.useDict) { const size_t e = cctx_sync_dictionary(c); if (isErr(e)) return e; }
     for (ZSTD_CCtx* w : c->workers) {
         w->historyBytes = c->historyBytes; w->frameBytes = c->frameBytes; w->parser = c->parser; w->passChunks = c->passChunks; w->timer.enabled = c->timer.enabled;
+        w->dictEntropy = c->dictEntropy;        // (before the dictionary: a worker builds the tables when it uploads its copy)
         if (w->dictGen != c->dictGen) {
             w->dictHost = c->dictHost; w->dictFull = c->dictFull; w->dictFormatted = c->dictFormatted; w->info = c->info; w->dictDirty = true; w->dictGen = c->dictGen;
         }
@@ -1058,6 +1076,15 @@ size_t ZSTDMI_CCtx_setHistory(ZSTD_CCtx* c, int bytes, unsigned frameBytes)
 }
 size_t ZSTDMI_CCtx_setSeekTable(ZSTD_CCtx* c, unsigned mode) { if (!c) return ZERR(kErrGeneric); if (mode > 1) return ZERR(kErrParameterOutOfBound); c->seekTable = (int)mode; return 0; }
 size_t ZSTDMI_seekTableBound(size_t srcSize) { return seek_table_bound(srcSize); }
+// (no device is touched: a loaded formatted dictionary is marked for another upload, which builds — or no longer builds — its tables)
+size_t ZSTDMI_CCtx_setDictEntropy(ZSTD_CCtx* c, unsigned mode)
+{
+    if (!c) return ZERR(kErrGeneric);
+    if (mode > 1) return ZERR(kErrParameterOutOfBound);
+    if (c->dictEntropy != (int)mode && c->dictFormatted) { c->dictDirty = true; c->dictGen++; }
+    c->dictEntropy = (int)mode;
+    return 0;
+}
 size_t ZSTDMI_CCtx_setParser(ZSTD_CCtx* c, unsigned mode) { if (!c || mode > 1) return ZERR(kErrParameterOutOfBound); c->parser = mode; return 0; }
 size_t ZSTDMI_CCtx_setProfiling(ZSTD_CCtx* c, int en) { if (!c) return ZERR(kErrGeneric); c->timer.enabled = en != 0; return 0; }
 int ZSTDMI_CCtx_getStageTimes(const ZSTD_CCtx* c, float* ms, const char** names, int cap)
@@ -1112,14 +1139,17 @@ size_t ZSTDMI_debugPoisonedChunk(ZSTD_CCtx* c, unsigned nbSeq, unsigned litSize,
     size_t e = cctx_bind(c); if (isErr(e)) return e;
     if (!cctx_workspace(c, 1)) return ZERR(kErrMemoryAllocation);
     hipStream_t s = c->stream;
+    // (with ZSTDMI_CCtx_setDictEntropy on and a formatted dictionary loaded, the instances that read its tables run)
+    e = cctx_sync_dictionary(c); if (isErr(e)) return e;
+    const DictCTables* const dct = call_dict_ctables(c, sticky_params(c));
     ChunkMeta m = {}; m.srcSize = srcSize; m.nbSeq = nbSeq; m.litSize = litSize; m.fhSize = 7;
     (void)hipMemsetAsync(c->seqs.p, (int)(fill & 0xFF), (size_t)kMaxSeq * sizeof(Seq), s);
     (void)hipMemsetAsync(c->lits.p, (int)(fill & 0xFF), kLitStride, s);
     (void)hipMemcpyAsync(c->meta.p, &m, sizeof m, hipMemcpyHostToDevice, s);
-    launch_huf_build((u8*)c->lits.p, (ChunkMeta*)c->meta.p, (HufTable*)c->tables.p, (u8*)c->slots.p, 1, 0, (const u8*)c->lits.p, kChunkSize, s, StageHook());
-    launch_huf_encode((u8*)c->lits.p, (ChunkMeta*)c->meta.p, (HufTable*)c->tables.p, (u8*)c->slots.p, nullptr, nullptr, 0, 1, (const u8*)c->lits.p, kChunkSize, s);
+    launch_huf_build((u8*)c->lits.p, (ChunkMeta*)c->meta.p, (HufTable*)c->tables.p, (u8*)c->slots.p, 1, 0, (const u8*)c->lits.p, kChunkSize, s, StageHook(), dct, 0);
+    launch_huf_encode((u8*)c->lits.p, (ChunkMeta*)c->meta.p, (HufTable*)c->tables.p, (u8*)c->slots.p, nullptr, nullptr, 0, 1, (const u8*)c->lits.p, kChunkSize, s, dct != nullptr);
     { const u32 plainReps[3] = { 1, 4, 8 };
-      launch_seq_encode((Seq*)c->seqs.p, (ChunkMeta*)c->meta.p, (u8*)c->slots.p, 1, 1, 0, 1, 0, 0, plainReps, 0, kChunkSize, srcSize < kChunkSize ? srcSize : kChunkSize, s); }
+      launch_seq_encode((Seq*)c->seqs.p, (ChunkMeta*)c->meta.p, (u8*)c->slots.p, 1, 1, 0, 1, 0, 0, plainReps, 0, kChunkSize, srcSize < kChunkSize ? srcSize : kChunkSize, s, dct); }
     if (isErr(dev_read(&m, c->meta.p, sizeof m, s))) return ZERR(kErrGeneric);
     c->lastChunks = 0;
     return m.outSize;
@@ -1175,6 +1205,7 @@ static size_t compress_entries(ZSTD_CCtx* c, const CallParams& cp, const u8* con
     const u32 dictIdBytes = (dictID && cp.dictIDFlag) ? (dictID < 256 ? 1u : dictID < 65536 ? 2u : 4u) : 0u;
     const u32 plainReps[3] = { 1, 4, 8 };
     const u32* const initReps = fmtDict ? c->info.rep : plainReps;
+    const DictCTables* const dct = call_dict_ctables(c, cp);
     bool first = true;
     std::vector<u8> tab; std::vector<u64> got;
     for (const Group& g : groups) {
@@ -1233,15 +1264,15 @@ static size_t compress_entries(ZSTD_CCtx* c, const CallParams& cp, const u8* con
             launch_lz(rs.finder, stage, stagedBytes, nCh, seqs, lits, meta, prefix, prefixLen, cb, dictIdBytes | (cp.contentSizeFlag ? 0u : 0x100u), rs.minStrideLog, 0,
                       regionParse ? (u16*)c->cand.p : nullptr, hcChains ? (u16*)((u8*)c->cand.p + cand_plane_bytes(nCh)) : nullptr,
                       regionParse ? (u32*)((u8*)c->cand.p + cand_plane_bytes(nCh) * (hcChains ? 2 : 1)) : nullptr, hcDepth, s, c->timer.hook(), (u32*)(total + 4), dLen);
-            launch_huf_build(lits, meta, tables, slots, nCh, rs.rawLiterals, stage, cb, s, c->timer.hook());
+            launch_huf_build(lits, meta, tables, slots, nCh, rs.rawLiterals, stage, cb, s, c->timer.hook(), dct, 0);
             if (cp.checksumFlag) { launch_xxh64(stage, stagedBytes, meta, nCh, cb, 0, s, dLen);        c->timer.mark("xxh64", s); }
-            launch_seq_encode(seqs, meta, slots, nCh, strategy, (cp.checksumFlag ? 1u : 0u) | (cp.contentSizeFlag ? 0u : 2u), 1, dictID, dictIdBytes, initReps, 0, cb, stagedBytes, s);
+            launch_seq_encode(seqs, meta, slots, nCh, strategy, (cp.checksumFlag ? 1u : 0u) | (cp.contentSizeFlag ? 0u : 2u), 1, dictID, dictIdBytes, initReps, 0, cb, stagedBytes, s, dct);
             c->timer.mark("seq_encode", s);
             if (d_stats) launch_seq_stats(seqs, lits, meta, nCh, stage, cb, d_stats, s);
             launch_batch_place(meta, nEnt, (const u32*)(dTab + atFirst), (const u64*)(dTab + atDst), (const u64*)(dTab + atCap), span, offsets, dGot, s);
             c->timer.mark("batch_place", s);
             if (dsts) {
-                launch_huf_encode(lits, meta, tables, slots, base, offsets, span, nCh, stage, cb, s);     c->timer.mark("huf_encode", s);
+                launch_huf_encode(lits, meta, tables, slots, base, offsets, span, nCh, stage, cb, s, dct != nullptr);     c->timer.mark("huf_encode", s);
                 launch_gather(stage, stagedBytes, slots, meta, offsets, base, span, nCh, cb, s);          c->timer.mark("gather", s);
             }
             got.resize(nEnt);
