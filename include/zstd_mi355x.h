@@ -259,9 +259,14 @@ size_t ZSTDMI_decompressDevice(ZSTD_DCtx* dctx, void* d_dst, size_t dstCapacity,
  * pipeline per class of resolved parameters (the cParams tiers at 16 KiB, 128 KiB and 256 KiB), ZSTDMI_CCtx_setPassChunks blocks at
  * most: a gather kernel stages them from the pointer array, the kernels of the single call run once over all of them, and a placement
  * kernel sends each result straight to its destination; the sizes come back in one copy per pass.  So do entries of several blocks
- * that are independent 64 KiB frames (behind a dictionary, or with ZSTDMI_CCtx_setHistory(0)) below 4 MiB.  Everything else — empty
- * entries, multi-block frames, LDM above one block, ZSTD_c_windowLog 10 .. 15 above one window, 4 MiB and more — is handed to the
- * single-call path one entry at a time, after the batched passes, in entry order.
+ * below 4 MiB, at every level: independent 64 KiB frames (behind a dictionary, or with ZSTDMI_CCtx_setHistory(0)), and multi-block
+ * frames whose blocks match into history held on chip — the 64 KiB frames of four 16 KiB blocks that levels 1-2 write for calls up to
+ * 32 MiB, and the 48 KiB or 32 KiB blocks in 240-256 KiB frames of the levels >= 3 (or of ZSTDMI_CCtx_setHistory(h > 0) at a level
+ * whose finder is the dual-hash or the chain finder), also under ZSTD_c_windowLog >= 16; the kernels then take each block's place in
+ * its frame from a per-chunk table.  Everything else — empty entries, LDM above one block, ZSTD_c_windowLog 10 .. 15 above one
+ * window, entries of 4 MiB and more (the sparse-input probe decides per call there), entries of more blocks than a pass, and the
+ * fast strategy's full 64 KiB blocks with far candidates (levels 1-2 with ZSTDMI_CCtx_setHistory(h > 0) or a window above 2^16) — is
+ * handed to the single-call path one entry at a time, after the batched passes, in entry order.
  * Decompress.  One lane per entry walks that entry's frames exactly as the single call's serial walk does (every frame, skippable
  * frames, trailing bytes, a dictID that is not the loaded one); the frames and blocks of all entries then go through the decoder ONCE,
  * with as many host synchronisations as a single call makes.  An entry's error is its first failing block's first error.  Entries

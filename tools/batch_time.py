@@ -1,15 +1,19 @@
 """Batched calls against a loop of single calls (run on the GPU box): 256 MiB of device-resident entries of 4 KiB, 16 KiB and 64 KiB
-(65 536, 16 384 and 4096 entries), text and Zipf bytes at levels 1 and 3, and 4 KiB text records at level 3 with
-tests/golden/trained_16k.dict.  Per point, compress and decompress:
+(65 536, 16 384 and 4096 entries), text and Zipf bytes at levels 1 and 3, 4 KiB text records at level 3 with
+tests/golden/trained_16k.dict, and entries of several blocks — 256 KiB (1024 entries) and 1 MiB (256 entries), the multi-block frames
+with history of the default settings — at the same kinds and levels.  Per point, compress and decompress:
   (a) loop   : one ZSTDMI_compressDevice / ZSTDMI_decompressDevice call per entry (timed on the first 4096 entries, scaled to all)
   (b) batch  : one ZSTDMI_compressBatch / ZSTDMI_decompressBatch call
   (c) concat : one single call on the concatenation — a different product (the entries are not decodable on their own), the ceiling
   (d) the batch call's stage times (ZSTDMI_*_getStageTimes)
 Best of 3 after a warm-up call of the same shape; the host clock stops after the call's final synchronise (every call ends with one).
 The input is 16 MiB of generated data repeated (entries are independent, so the repeats are nobody's match).
-python tools/batch_time.py [MiB] [--dict-entropy] [--dict-row]
+python tools/batch_time.py [MiB] [--dict-entropy] [--dict-row] [--frames-rows] [--measure-only]
   --dict-entropy : the dictionary row with ZSTDMI_CCtx_setDictEntropy on (the dictionary's entropy tables in the compressor)
-  --dict-row     : only the dictionary row"""
+  --dict-row     : only the dictionary row
+  --frames-rows  : only the 256 KiB and 1 MiB rows
+  --measure-only : no assertion that every entry took the batched pass and that the batch beats the loop; the number of entries that
+                   went alone is printed instead (for a library from before the multi-block rows were batched: the "before" column)"""
 import ctypes, sys, os, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -20,8 +24,8 @@ lib = z._ffi.load()
 MiB = 1 << 20
 FLAGS = [a for a in sys.argv[1:] if a.startswith("--")]
 ARGS = [a for a in sys.argv[1:] if not a.startswith("--")]
-assert all(f in ("--dict-entropy", "--dict-row") for f in FLAGS), FLAGS
-DICT_ENTROPY, DICT_ROW = "--dict-entropy" in FLAGS, "--dict-row" in FLAGS
+assert all(f in ("--dict-entropy", "--dict-row", "--frames-rows", "--measure-only") for f in FLAGS), FLAGS
+DICT_ENTROPY, DICT_ROW, FRAMES_ROWS, MEASURE_ONLY = "--dict-entropy" in FLAGS, "--dict-row" in FLAGS, "--frames-rows" in FLAGS, "--measure-only" in FLAGS
 total = (int(ARGS[0]) if ARGS else 256) * MiB
 SAMPLE = 4096
 DICT = open(os.path.join(ROOT, "tests", "golden", "trained_16k.dict"), "rb").read()
@@ -58,8 +62,8 @@ def ok(r):
 
 data = {k: torch.from_numpy(np.frombuffer(datagen.gen(k, 16 * MiB, 5), dtype=np.uint8).copy()).cuda().repeat(total // (16 * MiB)) for k in ("text", "zipf")}
 points = [(kind, size, level, None) for size in (4096, 16384, 65536) for kind in ("text", "zipf") for level in (1, 3)] + [("text", 4096, 3, DICT)]
-if DICT_ROW:
-    points = points[-1:]
+frames_points = [(kind, size, level, None) for size in (256 << 10, 1 << 20) for kind in ("text", "zipf") for level in (1, 3)]
+points = points[-1:] if DICT_ROW else frames_points if FRAMES_ROWS else points + frames_points
 print(f"{total // MiB} MiB per point; ms per call of all entries (GB/s of content)", flush=True)
 for kind, size, level, dic in points:
     src = data[kind]
@@ -78,7 +82,8 @@ for kind, size, level, dic in points:
     # (b) batch
     lib.ZSTDMI_CCtx_setProfiling(c, 1); lib.ZSTDMI_DCtx_setProfiling(d, 1)
     cb = best_of(lambda: ok(lib.ZSTDMI_compressBatch(c, s_ptr, s_sz, n, d_ptr, d_cap, got)))
-    assert not any(lib.ZSTD_isError(g) for g in got) and lib.ZSTDMI_debugLastBatchAlone(c) == 0
+    alone = lib.ZSTDMI_debugLastBatchAlone(c)
+    assert not any(lib.ZSTD_isError(g) for g in got) and (alone == 0 or MEASURE_ONLY)
     cst = stage_times(lib.ZSTDMI_CCtx_getStageTimes, c)
     db = best_of(lambda: ok(lib.ZSTDMI_decompressBatch(d, d_ptr, got, n, o_ptr, s_sz, back)))
     assert all(b == size for b in back) and lib.ZSTDMI_debugLastBatchAloneD(d) == 0 and bool(torch.equal(out, src))
@@ -111,7 +116,9 @@ for kind, size, level, dic in points:
     print(f"| {name:22s} | {n:6d} | {comp_bytes / total:.3f} | {ca * 1e3:8.1f} ({gbs(ca):6.2f}) | {cb * 1e3:7.2f} ({gbs(cb):6.1f}) | {cc * 1e3:7.2f} ({gbs(cc):6.1f}) "
           f"| {da * 1e3:8.1f} ({gbs(da):6.2f}) | {db * 1e3:7.2f} ({gbs(db):6.1f}) | {dc * 1e3:7.2f} ({gbs(dc):6.1f}) |", flush=True)
     print(f"    compress stages ms: {cst}\n    decompress stages ms: {dst_t}", flush=True)
-    assert cb < ca and db < da, "the batch call must beat the loop of single calls"
+    if MEASURE_ONLY:
+        print(f"    entries compressed alone: {alone} of {n}", flush=True)
+    assert MEASURE_ONLY or (cb < ca and db < da), "the batch call must beat the loop of single calls"
     lib.ZSTD_freeCCtx(c); lib.ZSTD_freeDCtx(d)
     del dst, out
     torch.cuda.empty_cache()

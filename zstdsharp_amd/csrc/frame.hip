@@ -140,16 +140,21 @@ __device__ __forceinline__ u64 xxh_merge(u64 acc, u64 v) { acc ^= xxh_round(0, v
 
 // (one frame = frameBlocks chunks of chunkBytes; the checksum is filed with the frame's last block, which carries it)
 // chunkLens (optional; single-block frames only): chunk c holds chunkLens[c] bytes at c * chunkBytes (a batch of independent inputs)
+// chunkFrames (optional; a batch's multi-block frames, see lz_kernel): one group of 4 lanes per CHUNK; the group of a frame's first
+// block (bits 24-31 zero) hashes the frame's bits 0-23 bytes, which lie in one piece from that chunk on, the others leave
 __global__ __launch_bounds__(256) void xxh64_kernel(const u8* __restrict__ src, u64 srcSize, ChunkMeta* __restrict__ meta, u32 nChunks, u32 chunkBytes,
-                                                    u32 frameBlocks, const u32* __restrict__ chunkLens)
+                                                    u32 frameBlocks, const u32* __restrict__ chunkLens, const u32* __restrict__ chunkFrames)
 {
     const u32 t = blockIdx.x * 256 + threadIdx.x;
     const u32 f = t >> 2, j = t & 3;
+    if (chunkFrames) frameBlocks = 1;                      // (f counts chunks)
     if ((u64)f * frameBlocks >= nChunks) return;           // whole groups of 4 lanes leave together
+    const u32 place = chunkFrames ? chunkFrames[f] : 0u;
+    if (place >> 24) return;
     const u64 frameBytes = (u64)frameBlocks * chunkBytes;
     const u64 base = (u64)f * frameBytes;
-    const u32 n = chunkLens ? chunkLens[f] : (u32)((srcSize - base) < frameBytes ? (srcSize - base) : frameBytes);
-    const u32 c = (f + 1) * frameBlocks <= nChunks ? (f + 1) * frameBlocks - 1 : nChunks - 1;
+    const u32 n = chunkFrames ? (place & 0xFFFFFFu) : chunkLens ? chunkLens[f] : (u32)((srcSize - base) < frameBytes ? (srcSize - base) : frameBytes);
+    const u32 c = chunkFrames ? f + (n - 1) / chunkBytes : (f + 1) * frameBlocks <= nChunks ? (f + 1) * frameBlocks - 1 : nChunks - 1;
     const u8* p = src + base;
     u64 h;
     const u32 stripes = n >> 5;
@@ -180,12 +185,13 @@ void launch_gather(const u8* src, u64 srcSize, const u8* slots, const ChunkMeta*
 {
     hipLaunchKernelGGL(gather_kernel, dim3(nChunks), dim3(256), 0, stream, src, srcSize, slots, meta, offsets, dst, dstCapacity, chunkBytes);
 }
-void launch_xxh64(const u8* src, u64 srcSize, ChunkMeta* meta, u32 nChunks, u32 chunkBytes, u32 frameBlocks, hipStream_t stream, const u32* chunkLens)
+void launch_xxh64(const u8* src, u64 srcSize, ChunkMeta* meta, u32 nChunks, u32 chunkBytes, u32 frameBlocks, hipStream_t stream, const u32* chunkLens,
+                  const u32* chunkFrames)
 {
     if (!frameBlocks) frameBlocks = 1;
-    if (frameBlocks != 1) chunkLens = nullptr;
-    const u32 nFrames = (nChunks + frameBlocks - 1) / frameBlocks;
-    hipLaunchKernelGGL(xxh64_kernel, dim3((nFrames * 4 + 255) / 256), dim3(256), 0, stream, src, srcSize, meta, nChunks, chunkBytes, frameBlocks, chunkLens);
+    if (frameBlocks != 1) chunkLens = nullptr; else chunkFrames = nullptr;
+    const u32 nFrames = chunkFrames ? nChunks : (nChunks + frameBlocks - 1) / frameBlocks;
+    hipLaunchKernelGGL(xxh64_kernel, dim3((nFrames * 4 + 255) / 256), dim3(256), 0, stream, src, srcSize, meta, nChunks, chunkBytes, frameBlocks, chunkLens, chunkFrames);
 }
 void launch_seek_entries(const u64* offsets, const u64* total, u32 nChunks, u32 frameBlocks, u32 chunkBytes, u64 passBytes, u32* entries, hipStream_t stream)
 {

@@ -796,13 +796,16 @@ __device__ __forceinline__ void dense_rest(LzLds& L, const u32 n, const u32 inse
 // candidates + one-step lazy deferral; levels >= 5: the place of U/ZstdLazy.cs:1743-2032).  The host maps strategy -> MODE.
 // DICT: a dictionary prefix is present (its bounds checks fold away otherwise)
 // FAR: matches may start in the input in front of the block (same frame): those candidates are verified against global memory
-template <int MODE, int SHORT, bool DICT, bool FAR>
+// TAB: a block's place in its frame comes from a table (chunkFrames: a batch of entries of different lengths).  A template parameter
+// because these kernels sit at the register cap: as a run-time branch the pointer and the select added scratch to the instances
+// every single call of the levels >= 3 runs; without TAB the code is that of a kernel without the table.
+template <int MODE, int SHORT, bool DICT, bool FAR, bool TAB>
 __global__ __launch_bounds__(1024) void lz_kernel(const u8* __restrict__ src, u64 srcSize,
                                                   Seq* __restrict__ seqs, u8* __restrict__ lits,
                                                   ChunkMeta* __restrict__ meta,
                                                   const u8* __restrict__ prefixArg, const u32 prefixLenArg, const u32 chunkBytes,
                                                   const u32 fhExtra, const u32 minStrideLog, const u32 frameBlocksArg, u16* __restrict__ candAll, u16* __restrict__ chainAll, u32* __restrict__ regionList, const u32 nChunks,
-                                                  u32* __restrict__ claimCtr, const u32* __restrict__ chunkLens)
+                                                  u32* __restrict__ claimCtr, const u32* __restrict__ chunkLens, const u32* __restrict__ chunkFrames)
 {
     extern __shared__ __attribute__((aligned(16))) u8 ldsRaw[];
     LzLds& L = *reinterpret_cast<LzLds*>(ldsRaw);
@@ -836,7 +839,9 @@ __global__ __launch_bounds__(1024) void lz_kernel(const u8* __restrict__ src, u6
     //  no history; a dictionary is history of the frame's first block only, whose image is the layout the decoder sees)
     const u32 frameBlocks = frameBlocksArg & 0x7FFFFFFFu;
     const bool indep = (frameBlocksArg >> 31) != 0;
-    const u32 bf = ((DICT || FAR) && frameBlocks) ? c % frameBlocks : 0u;               // block index inside its frame
+    // chunkFrames (optional, beside chunkLens; blocks behind LDS history only): a batch's entries differ in length, so a chunk's place
+    // comes from a table instead of the call's size: bits 24-31 the block index inside its frame, bits 0-23 the frame's content size
+    const u32 bf = ((DICT || FAR) && frameBlocks) ? (TAB ? chunkFrames[c] >> 24 : c % frameBlocks) : 0u;               // block index inside its frame
     const u32 farAvail = FAR ? ((u64)bf * cb < kFarMax ? bf * cb : kFarMax) : 0u;      // bytes of far history in front of the block
     u32 prefixLen = prefixLenArg; const u8* __restrict__ prefix = prefixArg;
     if (DICT && frameBlocks && !indep) { const u64 back = (u64)bf * cb; prefixLen = back < hist ? (u32)back : hist; prefix = in - prefixLen; }
@@ -1507,7 +1512,7 @@ __global__ __launch_bounds__(1024) void lz_kernel(const u8* __restrict__ src, u6
         m.srcSize = nData; m.nbSeq = nbSeq; m.litSize = litBase;
         if ((DICT || FAR) && frameBlocks) {   // only a frame's first block carries the frame header, sized for the whole frame's content
             const u64 fStart = base - (u64)bf * cb, fMax = (u64)frameBlocks * cb;
-            const u64 fLen = (srcSize - fStart) < fMax ? (srcSize - fStart) : fMax;
+            const u64 fLen = TAB ? (u64)(chunkFrames[c] & 0xFFFFFFu) : (srcSize - fStart) < fMax ? (srcSize - fStart) : fMax;
             const u32 fcsField = fLen < 256 ? 0u : fLen < 65536 + 256 ? 2u : fLen <= 0xFFFFFFFFull ? 4u : 8u;       // (behind a window descriptor)
             m.fhSize = bf == 0 ? ((fhExtra >> 12) ? 6u + ((fhExtra & 0x100u) ? 0u : fcsField) : (fhExtra & 0x100u) ? 6u : frame_header_size64(fLen)) + (fhExtra & 7u) : 0u;
         } else m.fhSize = ((fhExtra & 0x100u) ? 6u : frame_header_size(nData)) + (fhExtra & 7u);      // fhExtra: bits 0-2 bytes of the dictID field (formatted dictionary); bit 8: window descriptor instead of a content size (magic, descriptor, window byte); bits 12-16: an explicit windowLog (multi-block frames only: descriptor AND content size)
@@ -1526,11 +1531,11 @@ __global__ __launch_bounds__(1024) void lz_kernel(const u8* __restrict__ src, u6
 // tail in front of it, is staged again; the fast finder's table gets the first tile's positions (the latest occurrence per
 // bucket, as the tile loop left it; the first-occurrence table starts empty: it only ever serves the tile that filled it); and
 // the region parse takes the tiles after the first from the state lz_kernel recorded.
-template <int MODE, bool DICT>
+template <int MODE, bool DICT, bool TAB>
 __global__ __launch_bounds__(1024) void lz_region_kernel(const u8* __restrict__ src, u64 srcSize, Seq* __restrict__ seqs, u8* __restrict__ lits,
                                                          ChunkMeta* __restrict__ meta, u16* __restrict__ candAll, u16* __restrict__ chainAll, const u32* __restrict__ regionList,
                                                          const u8* __restrict__ prefixArg, const u32 prefixLenArg, const u32 chunkBytes, const u32 frameBlocksArg, const u32 hcDepth,
-                                                         const u32* __restrict__ chunkLens)
+                                                         const u32* __restrict__ chunkLens, const u32* __restrict__ chunkFrames)
 {
     const u32 frameBlocks = frameBlocksArg & 0x7FFFFFFFu;
     const bool indep = (frameBlocksArg >> 31) != 0;
@@ -1547,7 +1552,7 @@ __global__ __launch_bounds__(1024) void lz_region_kernel(const u8* __restrict__ 
     const u32 hist = DICT ? kChunkSize - ((chunkBytes + kTilePos - 1) & ~(kTilePos - 1)) : 0u;
     const u64 base = (u64)c * cb;
     const u8* __restrict__ in = src + base;
-    const u32 bf = (DICT && frameBlocks) ? c % frameBlocks : 0u;
+    const u32 bf = (DICT && frameBlocks) ? (TAB ? chunkFrames[c] >> 24 : c % frameBlocks) : 0u;
     u32 prefixLen = prefixLenArg; const u8* __restrict__ prefix = prefixArg;
     if (DICT && frameBlocks && !indep) { const u64 back = (u64)bf * cb; prefixLen = back < hist ? (u32)back : hist; prefix = in - prefixLen; }
     if (DICT && indep && bf) prefixLen = 0;
@@ -1679,10 +1684,10 @@ extern "C" void ZSTDMI_debugReadLzStamps(unsigned long long* out16, int reset)
 }
 #endif
 
-template <int MODE, int SHORT, bool DICT, bool FAR = false>
+template <int MODE, int SHORT, bool DICT, bool FAR = false, bool TAB = false>
 static void launch_one(const u8* src, u64 srcSize, u32 nChunks, Seq* seqs, u8* lits, ChunkMeta* meta, const u8* prefix, u32 prefixLen,
                        u32 chunkBytes, u32 fhExtra, u32 minStrideLog, u32 frameBlocks, u16* cand, u16* chain, u32* regionList, u32 hcDepth, hipStream_t stream, StageHook hook, u32* claimCtr,
-                       const u32* chunkLens)
+                       const u32* chunkLens, const u32* chunkFrames)
 {
     // the region parse of dense chunks: a second kernel behind a work list (see lz_region_kernel), inlined for the others
     constexpr bool kSplit = (MODE == 0 && !DICT && !FAR) || MODE == 2;
@@ -1690,8 +1695,8 @@ static void launch_one(const u8* src, u64 srcSize, u32 nChunks, Seq* seqs, u8* l
     static bool attrSet[64] = {};
     int dev = 0; (void)hipGetDevice(&dev);
     if (!attrSet[dev & 63]) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(lz_kernel<MODE, SHORT, DICT, FAR>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(LzLds));
-        if constexpr (kSplit) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(lz_region_kernel<MODE, DICT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(LzLds));
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(lz_kernel<MODE, SHORT, DICT, FAR, TAB>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(LzLds));
+        if constexpr (kSplit) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(lz_region_kernel<MODE, DICT, TAB>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(LzLds));
         attrSet[dev & 63] = true;
     }
     if (FAR) cand = nullptr;
@@ -1702,12 +1707,12 @@ static void launch_one(const u8* src, u64 srcSize, u32 nChunks, Seq* seqs, u8* l
     const bool claim = MODE == 0 && !DICT && !FAR && claimCtr && nChunks > cuCount[dev & 63];
     if (claim) (void)hipMemsetAsync(claimCtr, 0, sizeof(u32), stream);
     const u32 grid = claim ? cuCount[dev & 63] : nChunks;
-    hipLaunchKernelGGL((lz_kernel<MODE, SHORT, DICT, FAR>), dim3(grid), dim3(kTile), sizeof(LzLds), stream, src, srcSize, seqs, lits, meta, prefix, prefixLen, chunkBytes, fhExtra, minStrideLog, frameBlocks, cand, cand ? chain : nullptr, cand ? regionList : nullptr, nChunks,
-                       claim ? claimCtr : nullptr, chunkLens);
+    hipLaunchKernelGGL((lz_kernel<MODE, SHORT, DICT, FAR, TAB>), dim3(grid), dim3(kTile), sizeof(LzLds), stream, src, srcSize, seqs, lits, meta, prefix, prefixLen, chunkBytes, fhExtra, minStrideLog, frameBlocks, cand, cand ? chain : nullptr, cand ? regionList : nullptr, nChunks,
+                       claim ? claimCtr : nullptr, chunkLens, chunkFrames);
     hook("lz_fast");
     if constexpr (kSplit) if (cand) {                      // the dense chunks' rest: 256 workgroups (one per CU) walk the list
-        hipLaunchKernelGGL((lz_region_kernel<MODE, DICT>), dim3(nChunks < 256 ? nChunks : 256), dim3(kTile), sizeof(LzLds), stream, src, srcSize, seqs, lits, meta, cand, chain, regionList,
-                           prefix, prefixLen, chunkBytes, frameBlocks, hcDepth, chunkLens);
+        hipLaunchKernelGGL((lz_region_kernel<MODE, DICT, TAB>), dim3(nChunks < 256 ? nChunks : 256), dim3(kTile), sizeof(LzLds), stream, src, srcSize, seqs, lits, meta, cand, chain, regionList,
+                           prefix, prefixLen, chunkBytes, frameBlocks, hcDepth, chunkLens, chunkFrames);
         hook("lz_region");
     }
 }
@@ -1721,24 +1726,33 @@ static void launch_one(const u8* src, u64 srcSize, u32 nChunks, Seq* seqs, u8* l
 // cand / regionList (null: off): workspace of the region parse, 65536 u16 per chunk and 1 + nChunks u32.
 void launch_lz(u32 finder, const u8* src, u64 srcSize, u32 nChunks, Seq* seqs, u8* lits, ChunkMeta* meta, const u8* prefix, u32 prefixLen,
                u32 chunkBytes, u32 fhExtra, u32 minStrideLog, u32 frameBlocks, u16* cand, u16* chain, u32* regionList, u32 hcDepth, hipStream_t stream, StageHook hook, u32* claimCtr,
-               const u32* chunkLens)
+               const u32* chunkLens, const u32* chunkFrames)
 {
+    // (the table form exists for blocks behind LDS history only: the full-64-KiB-block instances below take no chunkFrames, while
+    //  seq_encode and xxh64 would still follow it)
+    assert(!chunkFrames || (chunkBytes < kChunkSize && frameBlocks && chunkLens));
     if (chunkBytes >= kChunkSize && frameBlocks && finder == 0) {       // fast strategy with cross-chunk history: full 64 KiB blocks, far candidates
-        launch_one<0, 5, false, true>(src, srcSize, nChunks, seqs, lits, meta, nullptr, 0, kChunkSize, fhExtra, minStrideLog, frameBlocks, nullptr, nullptr, nullptr, 0, stream, hook, claimCtr, nullptr);
+        launch_one<0, 5, false, true>(src, srcSize, nChunks, seqs, lits, meta, nullptr, 0, kChunkSize, fhExtra, minStrideLog, frameBlocks, nullptr, nullptr, nullptr, 0, stream, hook, claimCtr, nullptr, nullptr);
         return;
     }
     if (chunkBytes >= kChunkSize) {
         switch (finder) {
-        case 0:  launch_one<0, 5, false>(src, srcSize, nChunks, seqs, lits, meta, nullptr, 0, kChunkSize, fhExtra, minStrideLog, 0, cand, chain, regionList, hcDepth, stream, hook, claimCtr, chunkLens); break;
-        case 1:  launch_one<1, 5, false>(src, srcSize, nChunks, seqs, lits, meta, nullptr, 0, kChunkSize, fhExtra, minStrideLog, 0, cand, chain, regionList, hcDepth, stream, hook, claimCtr, chunkLens); break;
-        default: launch_one<2, 5, false>(src, srcSize, nChunks, seqs, lits, meta, nullptr, 0, kChunkSize, fhExtra, minStrideLog, 0, cand, chain, regionList, hcDepth, stream, hook, claimCtr, chunkLens); break;
+        case 0:  launch_one<0, 5, false>(src, srcSize, nChunks, seqs, lits, meta, nullptr, 0, kChunkSize, fhExtra, minStrideLog, 0, cand, chain, regionList, hcDepth, stream, hook, claimCtr, chunkLens, nullptr); break;
+        case 1:  launch_one<1, 5, false>(src, srcSize, nChunks, seqs, lits, meta, nullptr, 0, kChunkSize, fhExtra, minStrideLog, 0, cand, chain, regionList, hcDepth, stream, hook, claimCtr, chunkLens, nullptr); break;
+        default: launch_one<2, 5, false>(src, srcSize, nChunks, seqs, lits, meta, nullptr, 0, kChunkSize, fhExtra, minStrideLog, 0, cand, chain, regionList, hcDepth, stream, hook, claimCtr, chunkLens, nullptr); break;
         }
         return;
     }
     switch (finder) {
-    case 0:  launch_one<0, 5, true>(src, srcSize, nChunks, seqs, lits, meta, prefix, prefixLen, chunkBytes, fhExtra, minStrideLog, frameBlocks, cand, chain, regionList, hcDepth, stream, hook, claimCtr, chunkLens); break;
-    case 1:  launch_one<1, 5, true>(src, srcSize, nChunks, seqs, lits, meta, prefix, prefixLen, chunkBytes, fhExtra, minStrideLog, frameBlocks, cand, chain, regionList, hcDepth, stream, hook, claimCtr, chunkLens); break;
-    default: launch_one<2, 5, true>(src, srcSize, nChunks, seqs, lits, meta, prefix, prefixLen, chunkBytes, fhExtra, minStrideLog, frameBlocks, cand, chain, regionList, hcDepth, stream, hook, claimCtr, chunkLens); break;
+    case 0:  if (chunkFrames) launch_one<0, 5, true, false, true>(src, srcSize, nChunks, seqs, lits, meta, prefix, prefixLen, chunkBytes, fhExtra, minStrideLog, frameBlocks, cand, chain, regionList, hcDepth, stream, hook, claimCtr, chunkLens, chunkFrames);
+             else launch_one<0, 5, true>(src, srcSize, nChunks, seqs, lits, meta, prefix, prefixLen, chunkBytes, fhExtra, minStrideLog, frameBlocks, cand, chain, regionList, hcDepth, stream, hook, claimCtr, chunkLens, nullptr);
+             break;
+    case 1:  if (chunkFrames) launch_one<1, 5, true, false, true>(src, srcSize, nChunks, seqs, lits, meta, prefix, prefixLen, chunkBytes, fhExtra, minStrideLog, frameBlocks, cand, chain, regionList, hcDepth, stream, hook, claimCtr, chunkLens, chunkFrames);
+             else launch_one<1, 5, true>(src, srcSize, nChunks, seqs, lits, meta, prefix, prefixLen, chunkBytes, fhExtra, minStrideLog, frameBlocks, cand, chain, regionList, hcDepth, stream, hook, claimCtr, chunkLens, nullptr);
+             break;
+    default: if (chunkFrames) launch_one<2, 5, true, false, true>(src, srcSize, nChunks, seqs, lits, meta, prefix, prefixLen, chunkBytes, fhExtra, minStrideLog, frameBlocks, cand, chain, regionList, hcDepth, stream, hook, claimCtr, chunkLens, chunkFrames);
+             else launch_one<2, 5, true>(src, srcSize, nChunks, seqs, lits, meta, prefix, prefixLen, chunkBytes, fhExtra, minStrideLog, frameBlocks, cand, chain, regionList, hcDepth, stream, hook, claimCtr, chunkLens, nullptr);
+             break;
     }
 }
 

@@ -122,7 +122,7 @@ __global__ __launch_bounds__(256) void seq_encode_kernel(Seq* __restrict__ seqs,
                                                          u8* __restrict__ slots, u32 nChunks, u32 strategy, u32 checksumFlag, u32 resolveReps,
                                                          u32 dictID, u32 dictIdBytes, u32 initRep0, u32 initRep1, u32 initRep2,
                                                          const u32 frameBlocks, const u32 chunkBytes, const u64 srcSize,
-                                                         const DictCTables* __restrict__ dct)
+                                                         const DictCTables* __restrict__ dct, const u32* __restrict__ chunkFrames)
 {
     __shared__ SeqWaveLds Ws[4];
     __shared__ u32 sBatchSeq[4];          // sequences each of the four chunks sends through the state chains (0: none)
@@ -139,11 +139,14 @@ __global__ __launch_bounds__(256) void seq_encode_kernel(Seq* __restrict__ seqs,
     // U/ZstdCompress.cs:3620-3640) is only known once it has been encoded — so its history starts as "unknown" (0 matches no
     // offset): offsets are written in full until the block itself has defined the repcode they would use.  That is always a
     // valid encoding (the decoder pushes a full offset whatever it equals) and costs a few bits per block.
-    const u32 bf = frameBlocks ? c % frameBlocks : 0u;
+    // chunkFrames (optional): a batch of entries of different lengths: the block index (bits 24-31) and the frame's content size
+    // (bits 0-23) per chunk from a table, as in lz_kernel
+    const u32 place = (frameBlocks && chunkFrames && live) ? chunkFrames[c] : 0u;
+    const u32 bf = frameBlocks ? (chunkFrames ? place >> 24 : c % frameBlocks) : 0u;
     u64 frameLen = n; bool lastBlock = true;
     if (frameBlocks) {
         const u64 fStart = (u64)(c - bf) * chunkBytes, fMax = (u64)frameBlocks * chunkBytes;
-        frameLen = (srcSize - fStart) < fMax ? (srcSize - fStart) : fMax;
+        frameLen = chunkFrames ? (u64)(place & 0xFFFFFFu) : (srcSize - fStart) < fMax ? (srcSize - fStart) : fMax;
         lastBlock = (u64)(bf + 1) * chunkBytes >= frameLen;
         if (bf) { initRep0 = 0; initRep1 = 0; initRep2 = 0; }
     }
@@ -449,12 +452,12 @@ __global__ __launch_bounds__(256) void seq_encode_kernel(Seq* __restrict__ seqs,
 
 void launch_seq_encode(Seq* seqs, ChunkMeta* meta, u8* slots, u32 nChunks, u32 strategy, u32 checksumFlag, u32 resolveReps,
                        u32 dictID, u32 dictIdBytes, const u32* initReps, u32 frameBlocks, u32 chunkBytes, u64 srcSize, hipStream_t stream,
-                       const DictCTables* dct)
+                       const DictCTables* dct, const u32* chunkFrames)
 {
     if (dct) hipLaunchKernelGGL(seq_encode_kernel<true>, dim3((nChunks + 3) / 4), dim3(256), 0, stream, seqs, meta, slots, nChunks, strategy, checksumFlag, resolveReps,
-                                dictID, dictIdBytes, initReps[0], initReps[1], initReps[2], frameBlocks, chunkBytes, srcSize, dct);
+                                dictID, dictIdBytes, initReps[0], initReps[1], initReps[2], frameBlocks, chunkBytes, srcSize, dct, chunkFrames);
     else hipLaunchKernelGGL(seq_encode_kernel<false>, dim3((nChunks + 3) / 4), dim3(256), 0, stream, seqs, meta, slots, nChunks, strategy, checksumFlag, resolveReps,
-                            dictID, dictIdBytes, initReps[0], initReps[1], initReps[2], frameBlocks, chunkBytes, srcSize, dct);
+                            dictID, dictIdBytes, initReps[0], initReps[1], initReps[2], frameBlocks, chunkBytes, srcSize, dct, chunkFrames);
 }
 
 #ifdef ZMI_LZ_STAMPS

@@ -5,6 +5,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <string.h>
+#include <assert.h>
 #include <vector>
 #include <thread>
 #include <new>
@@ -13,9 +14,12 @@
 
 namespace zmi {
 // kernels (lz_fast.hip, huf_enc.hip, seq_enc.hip, frame.hip, decode.hip)
+// chunkLens / chunkFrames (a batch of entries, each staged at a chunk boundary): per chunk its length, and — multi-block frames behind
+// LDS history only — its place: chunk_frame_word(block index inside its frame, the frame's content size)
+inline u32 chunk_frame_word(u32 blockInFrame, u32 frameLen) { assert(blockInFrame < 256 && frameLen < (1u << 24)); return (blockInFrame << 24) | frameLen; }
 void launch_lz(u32 finder, const u8* src, u64 srcSize, u32 nChunks, Seq* seqs, u8* lits, ChunkMeta* meta, const u8* prefix, u32 prefixLen,
                u32 chunkBytes, u32 fhExtra, u32 minStrideLog, u32 frameBlocks, u16* cand, u16* chain, u32* regionList, u32 hcDepth, hipStream_t stream, StageHook hook, u32* claimCtr,
-               const u32* chunkLens = nullptr);
+               const u32* chunkLens = nullptr, const u32* chunkFrames = nullptr);
 void launch_lz_probe(const u8* src, u64 srcSize, u64 front, u64 groupBytes, u32 nGroups, u32 tilesPerGroup, u32* out, hipStream_t stream);
 void launch_huf_build(const u8* lits, ChunkMeta* meta, HufTable* tables, u8* slots, u32 nChunks, u32 rawLiterals, const u8* src, u32 chunkBytes,
                       hipStream_t stream, StageHook hook, const DictCTables* dct = nullptr, u32 frameBlocks = 0);
@@ -23,11 +27,12 @@ void launch_huf_encode(const u8* lits, const ChunkMeta* meta, const HufTable* ta
                        u32 nChunks, const u8* src, u32 chunkBytes, hipStream_t stream, bool dictEntropy = false);
 void launch_seq_encode(Seq* seqs, ChunkMeta* meta, u8* slots, u32 nChunks, u32 strategy, u32 checksumFlag, u32 resolveReps,
                        u32 dictID, u32 dictIdBytes, const u32* initReps, u32 frameBlocks, u32 chunkBytes, u64 srcSize, hipStream_t stream,
-                       const DictCTables* dct = nullptr);
+                       const DictCTables* dct = nullptr, const u32* chunkFrames = nullptr);
 void launch_scan_sizes(const ChunkMeta* meta, u32 nChunks, u64* offsets, u64* total, hipStream_t stream);
 void launch_gather(const u8* src, u64 srcSize, const u8* slots, const ChunkMeta* meta, const u64* offsets, u8* dst, u64 dstCapacity,
                    u32 nChunks, u32 chunkBytes, hipStream_t stream);
-void launch_xxh64(const u8* src, u64 srcSize, ChunkMeta* meta, u32 nChunks, u32 chunkBytes, u32 frameBlocks, hipStream_t stream, const u32* chunkLens = nullptr);
+void launch_xxh64(const u8* src, u64 srcSize, ChunkMeta* meta, u32 nChunks, u32 chunkBytes, u32 frameBlocks, hipStream_t stream, const u32* chunkLens = nullptr,
+                  const u32* chunkFrames = nullptr);
 void launch_batch_stage(const u64* from, const u32* len, u8* stage, u32 nChunks, u32 chunkBytes, hipStream_t stream);
 void launch_batch_place(const ChunkMeta* meta, u32 nEntries, const u32* entFirst, const u64* entDst, const u64* entCap, u64 span, u64* offsets, u64* entSize,
                         hipStream_t stream);

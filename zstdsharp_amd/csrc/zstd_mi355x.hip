@@ -282,6 +282,25 @@ static Framing resolve_framing(const ZSTD_CCtx* c, const CallParams& cp, size_t 
     return f;
 }
 
+// What the finder and the sequence encoder are launched with for a framing: derived in one place for the single call
+// (compress_range) and the batch (compress_entries), whose bytes must be the same.
+struct LaunchState { bool regionParse, hcChains; u32 hcDepth, strategy, lzFrameBlocks; };
+static LaunchState launch_state(const ZSTD_CCtx* c, const CallParams& cp, const Framing& fr)
+{
+    const Resolved& rs = fr.rs;
+    LaunchState L;
+    L.lzFrameBlocks = fr.frameBlocks | (fr.indepWindowLog ? 0x80000000u : 0u);       // (independent blocks: no history between them)
+    L.regionParse = rs.minStrideLog == 0 && !(rs.finder == 0 && fr.frameBlocks && fr.chunkBytes >= kChunkSize) && c->parser == 0;   // (not the far-candidate finder)
+    L.hcChains = L.regionParse && rs.finder >= 2;
+    // attempts per position of the level >= 5 search: the reference's 1 << searchLog (U/ZstdLazy.cs:641-642), between 4 and 32; the
+    // greedy and lazy strategies (levels 5-7) stop at 8 unless ZSTD_c_searchLog asks for more: measured on text, 32 attempts
+    // instead of 8 cost twice the time for 1 % of size
+    L.hcDepth = rs.cp.searchLog < 2 ? 4u : rs.cp.searchLog > 5 ? 32u : 1u << rs.cp.searchLog;
+    if (L.hcDepth > 8 && rs.cp.strategy <= 4 && cp.searchLog == 0) L.hcDepth = 8;
+    L.strategy = rs.cp.strategy < kStratGreedy ? rs.cp.strategy : (u32)kStratGreedy;      // ZSTD_selectEncodingType's < lazy heuristic is the one seq_encode holds (U/ZstdCompressSequences.cs:400-469): levels whose strategy is lazy or above get greedy's constants
+    return L;
+}
+
 // the compress pipeline over device-resident buffers: one range of the input with one set of parameters (see compress_device)
 // paramSize: the size the parameters are resolved for — the whole range's, of which [d_src, d_src + srcSize) may be a frame-aligned
 // part (a device worker's share of the range, compress_multi): what is written for a stretch of frames depends on nothing else
@@ -305,7 +324,9 @@ static size_t compress_range(ZSTD_CCtx* c, const CallParams& cp, u8* d_dst, size
     if (cp.useDict) { const size_t e = cctx_sync_dictionary(c); if (isErr(e)) return e; }
     const Framing fr = resolve_framing(c, cp, paramSize);
     const u32 prefixLen = fr.prefixLen, chunkBytes = fr.chunkBytes, frameBlocks = fr.frameBlocks;
-    const u32 lzFrameBlocks = frameBlocks | (fr.indepWindowLog ? 0x80000000u : 0u);       // (independent blocks: no history between them)
+    const LaunchState ls = launch_state(c, cp, fr);
+    const u32 lzFrameBlocks = ls.lzFrameBlocks, hcDepth = ls.hcDepth, strategy = ls.strategy;
+    const bool regionParse = ls.regionParse, hcChains = ls.hcChains;
     const u32 hdrWindow = fr.indepWindowLog;
     const Resolved rs = fr.rs;
     // a formatted dictionary: its dictID in every frame header (unless ZSTD_c_dictIDFlag = 0), its repcodes in front of every frame
@@ -321,15 +342,7 @@ static size_t compress_range(ZSTD_CCtx* c, const CallParams& cp, u8* d_dst, size
     if (fr.ldm) { const u32 most = (u32)(((u64)1 << 31) / chunkBytes) / frameBlocks * frameBlocks; if (passChunks > most) passChunks = most; }    // (ldm.hip: u32 offsets in a pass)
     if (frameBlocks && passChunks < totalChunks) { passChunks -= passChunks % frameBlocks; if (!passChunks) passChunks = frameBlocks; }     // frames never straddle passes
     if (!cctx_workspace(c, passChunks)) return ZERR(kErrMemoryAllocation);
-    const bool regionParse = rs.minStrideLog == 0 && !(rs.finder == 0 && frameBlocks && chunkBytes >= kChunkSize) && c->parser == 0;   // (not the far-candidate finder)
-    const bool hcChains = regionParse && rs.finder >= 2;
-    // attempts per position of the level >= 5 search: the reference's 1 << searchLog (U/ZstdLazy.cs:641-642), between 4 and 32; the
-    // greedy and lazy strategies (levels 5-7) stop at 8 unless ZSTD_c_searchLog asks for more: measured on text, 32 attempts
-    // instead of 8 cost twice the time for 1 % of size
-    u32 hcDepth = rs.cp.searchLog < 2 ? 4u : rs.cp.searchLog > 5 ? 32u : 1u << rs.cp.searchLog;
-    if (hcDepth > 8 && rs.cp.strategy <= 4 && cp.searchLog == 0) hcDepth = 8;
     if (regionParse && !cctx_cand_workspace(c, passChunks, hcChains)) return ZERR(kErrMemoryAllocation);
-    const u32 strategy = rs.cp.strategy < kStratGreedy ? rs.cp.strategy : (u32)kStratGreedy;      // ZSTD_selectEncodingType's < lazy heuristic is the one seq_encode holds (U/ZstdCompressSequences.cs:400-469): levels whose strategy is lazy or above get greedy's constants
     size_t produced = 0;
     for (u64 c0 = 0; c0 < totalChunks; c0 += passChunks) {
         const u32 nChunks = (u32)((totalChunks - c0) < passChunks ? (totalChunks - c0) : passChunks);
@@ -1163,15 +1176,20 @@ size_t ZSTD_compressStream2(ZSTD_CCtx* c, ZSTD_outBuffer* output, ZSTD_inBuffer*
 
 // ---- a batch of independent entries, each compressed as the single call would compress it alone (ZSTDMI_compressBatch; the
 // dictionary trainer's inner loop, dict_train.hip) ----
-// Entries of one framing class (same dictionary prefix, chunk size and resolved parameters) go through the pipeline together: each
-// chunk of an entry is staged at its own chunk boundary (batch_stage_kernel) and the finder and the checksum take its length from a
-// per-chunk table (chunkLens); every chunk is a frame of its own, so what is written for it depends on nothing beside it.  With
+// Entries of one framing class (same dictionary prefix, chunk size, blocks per frame and resolved parameters) go through the pipeline
+// together: each chunk of an entry is staged at its own chunk boundary (batch_stage_kernel) and the finder and the checksum take its
+// length from a per-chunk table (chunkLens).  Where every chunk is a frame of its own, what is written for it depends on nothing
+// beside it.  Multi-block frames behind LDS history (the small-call 16 KiB cut of levels 1-2, the 48 / 32 KiB blocks of the dual-hash
+// and chain finders) take a second column (chunkFrames): the block's index inside its frame and the frame's content size, which the
+// single call derives from its total size; all chunks of an entry but the last are full, so a block's history lies in front of it in
+// the staging buffer as it does in the entry.  With
 // destinations, batch_place_kernel gives every chunk its place as an offset from the lowest destination pointer and huf_encode and
 // gather write there directly; without (the trainer), only the sizes come back.  A pass holds whole entries, at most
 // ZSTDMI_CCtx_setPassChunks chunks; per pass one table goes up and the entries' sizes come back in one copy.
-// An entry the class model does not cover — empty, multi-block frames (history, the small-call 16 KiB cut, windows below 64 KiB),
-// LDM, the sparse-input probe (4 MiB and more), more chunks than a pass, several device workers — is compressed alone afterwards, in
-// entry order, by the single-call path, and counted in `alone`.
+// An entry the class model does not cover — empty, windows below 64 KiB above one window, LDM above one block, the fast strategy's
+// full 64 KiB blocks with far candidates (no per-chunk tables in that kernel), the sparse-input probe and multi-block frames of
+// 4 MiB and more, more chunks than a pass, several device workers — is compressed alone afterwards, in entry order, by the
+// single-call path, and counted in `alone`.
 // srcs[i]: device pointers.  dsts / caps: device pointers and their capacities, or null (sizes only).  outSizes[i] = the compressed
 // size of entry i (or its error).  d_stats (optional, device, 377 u32): seq_stats_kernel's counts of the batched chunks are added.
 static size_t compress_entries(ZSTD_CCtx* c, const CallParams& cp, const u8* const* srcs, const size_t* sizes, size_t n,
@@ -1179,6 +1197,7 @@ static size_t compress_entries(ZSTD_CCtx* c, const CallParams& cp, const u8* con
 {
     hipStream_t s = c->stream;
     alone = 0;
+    const DictCTables* const dct = call_dict_ctables(c, cp);
     const u32 passLimit = c->passChunks < 16384 ? c->passChunks : 16384;
     struct Group { Framing fr; std::vector<size_t> members; };
     std::vector<Group> groups;
@@ -1190,13 +1209,19 @@ static size_t compress_entries(ZSTD_CCtx* c, const CallParams& cp, const u8* con
             if (!dsts[i]) { outSizes[i] = caps[i] ? ZERR(kErrDstBufferNull) : ZERR(kErrDstSizeTooSmall); continue; }
         }
         const Framing fr = S ? resolve_framing(c, cp, S) : Framing{};
-        bool batched = S && !fr.frameBlocks && !fr.indepWindowLog && !fr.ldm && c->workers.size() <= 1 && (S + fr.chunkBytes - 1) / fr.chunkBytes <= passLimit;
+        bool batched = S && !fr.indepWindowLog && !fr.ldm && c->workers.size() <= 1 && (S + fr.chunkBytes - 1) / fr.chunkBytes <= passLimit;
+        // multi-block frames: the blocks behind LDS history (chunks below 64 KiB; the full 64 KiB blocks with far candidates have no
+        // table form, launch_lz), below 4 MiB and of at most 256 chunks (a block index and a frame size that fit chunk_frame_word);
+        // with a dictionary's entropy tables (huf_tree_kernel<true> finds a frame's first block by c % frameBlocks), or with sizes
+        // only and statistics (the trainer's finalize step), as before: alone
+        if (batched && fr.frameBlocks)
+            batched = S < (4u << 20) && (S + fr.chunkBytes - 1) / fr.chunkBytes <= 256 && fr.chunkBytes < kChunkSize && !dct && !d_stats;
         if (batched && S >= (4u << 20)) { size_t err = 0; if (probe_group_bytes(c, cp, S, err) || isErr(err)) batched = false; }
         if (!batched) { aloneList.push_back(i); continue; }
         outSizes[i] = 0;
         Group* g = nullptr;
         for (auto& x : groups)
-            if (x.fr.prefixLen == fr.prefixLen && x.fr.chunkBytes == fr.chunkBytes && !memcmp(&x.fr.rs, &fr.rs, sizeof(Resolved))) { g = &x; break; }
+            if (x.fr.prefixLen == fr.prefixLen && x.fr.chunkBytes == fr.chunkBytes && x.fr.frameBlocks == fr.frameBlocks && !memcmp(&x.fr.rs, &fr.rs, sizeof(Resolved))) { g = &x; break; }
         if (!g) { groups.push_back(Group{fr, {}}); g = &groups.back(); }
         g->members.push_back(i);
     }
@@ -1205,18 +1230,15 @@ static size_t compress_entries(ZSTD_CCtx* c, const CallParams& cp, const u8* con
     const u32 dictIdBytes = (dictID && cp.dictIDFlag) ? (dictID < 256 ? 1u : dictID < 65536 ? 2u : 4u) : 0u;
     const u32 plainReps[3] = { 1, 4, 8 };
     const u32* const initReps = fmtDict ? c->info.rep : plainReps;
-    const DictCTables* const dct = call_dict_ctables(c, cp);
     bool first = true;
     std::vector<u8> tab; std::vector<u64> got;
     for (const Group& g : groups) {
-        const u32 cb = g.fr.chunkBytes, prefixLen = g.fr.prefixLen;
+        const u32 cb = g.fr.chunkBytes, prefixLen = g.fr.prefixLen, frameBlocks = g.fr.frameBlocks;
         const Resolved rs = g.fr.rs;
         const u8* prefix = prefixLen ? (const u8*)c->dict.p + (c->dictHost.size() - prefixLen) : nullptr;
-        const bool regionParse = rs.minStrideLog == 0 && c->parser == 0;
-        const bool hcChains = regionParse && rs.finder >= 2;
-        u32 hcDepth = rs.cp.searchLog < 2 ? 4u : rs.cp.searchLog > 5 ? 32u : 1u << rs.cp.searchLog;
-        if (hcDepth > 8 && rs.cp.strategy <= 4 && cp.searchLog == 0) hcDepth = 8;
-        const u32 strategy = rs.cp.strategy < kStratGreedy ? rs.cp.strategy : (u32)kStratGreedy;
+        const LaunchState ls = launch_state(c, cp, g.fr);
+        const bool regionParse = ls.regionParse, hcChains = ls.hcChains;
+        const u32 hcDepth = ls.hcDepth, strategy = ls.strategy;
         for (size_t m0 = 0; m0 < g.members.size(); ) {
             // the pass: whole entries, up to passLimit chunks
             size_t m1 = m0; u32 nCh = 0;
@@ -1226,12 +1248,14 @@ static size_t compress_entries(ZSTD_CCtx* c, const CallParams& cp, const u8* con
                 nCh += k; ++m1;
             }
             const u32 nEnt = (u32)(m1 - m0);
-            // the pass's table, one upload: from[nCh] | entDst[nEnt] | entCap[nEnt] (u64) | len[nCh] | entFirst[nEnt + 1] (u32); behind it the sizes that come back
+            // the pass's table, one upload: from[nCh] | entDst[nEnt] | entCap[nEnt] (u64) | len[nCh] | entFirst[nEnt + 1] | with multi-block frames frame[nCh] (u32);
+            // behind it the sizes that come back
             const size_t atDst = (size_t)nCh * 8, atCap = atDst + (size_t)nEnt * 8, atLen = atCap + (size_t)nEnt * 8, atFirst = atLen + (size_t)nCh * 4;
-            const size_t tabBytes = (atFirst + ((size_t)nEnt + 1) * 4 + 7) & ~(size_t)7;
+            const size_t atFrame = atFirst + ((size_t)nEnt + 1) * 4;
+            const size_t tabBytes = (atFrame + (frameBlocks ? (size_t)nCh * 4 : 0) + 7) & ~(size_t)7;
             tab.assign(tabBytes, 0);
             u64* const hFrom = (u64*)tab.data(); u64* const hDst = (u64*)(tab.data() + atDst); u64* const hCap = (u64*)(tab.data() + atCap);
-            u32* const hLen = (u32*)(tab.data() + atLen); u32* const hFirst = (u32*)(tab.data() + atFirst);
+            u32* const hLen = (u32*)(tab.data() + atLen); u32* const hFirst = (u32*)(tab.data() + atFirst); u32* const hFrame = (u32*)(tab.data() + atFrame);
             uintptr_t lo = ~(uintptr_t)0, hi = 0;
             if (dsts) for (size_t m = m0; m < m1; ++m) {
                 const size_t i = g.members[m];
@@ -1246,13 +1270,21 @@ static size_t compress_entries(ZSTD_CCtx* c, const CallParams& cp, const u8* con
                 hFirst[m - m0] = ck;
                 hDst[m - m0] = dsts ? (u64)((uintptr_t)dsts[i] - lo) : 0;
                 hCap[m - m0] = dsts ? (u64)caps[i] : ~(u64)0;
-                for (u64 o = 0; o < sizes[i]; o += cb, ++ck) { hFrom[ck] = (u64)(uintptr_t)(srcs[i] + o); hLen[ck] = (u32)(sizes[i] - o < cb ? sizes[i] - o : cb); }
+                const u64 frameSpan = (u64)frameBlocks * cb;
+                for (u64 o = 0, k = 0; o < sizes[i]; o += cb, ++ck, ++k) {
+                    hFrom[ck] = (u64)(uintptr_t)(srcs[i] + o); hLen[ck] = (u32)(sizes[i] - o < cb ? sizes[i] - o : cb);
+                    if (frameBlocks) {          // block k % frameBlocks of the frame that starts at fStart, as the single call counts them
+                        const u64 fStart = (k - k % frameBlocks) * cb;
+                        hFrame[ck] = chunk_frame_word((u32)(k % frameBlocks), (u32)(sizes[i] - fStart < frameSpan ? sizes[i] - fStart : frameSpan));
+                    }
+                }
             }
             hFirst[nEnt] = ck;
             if (!cctx_workspace(c, nCh) || (regionParse && !cctx_cand_workspace(c, nCh, hcChains)) || !c->batchStage.ensure((u64)nCh * cb + 64) ||
                 !c->batchTab.ensure(tabBytes + (size_t)nEnt * 8)) return ZERR(kErrMemoryAllocation);
             u8* const dTab = (u8*)c->batchTab.p;
             const u32* const dLen = (const u32*)(dTab + atLen);
+            const u32* const dFrame = frameBlocks ? (const u32*)(dTab + atFrame) : nullptr;
             u64* const dGot = (u64*)(dTab + tabBytes);
             if (hipMemcpyAsync(dTab, tab.data(), tabBytes, hipMemcpyHostToDevice, s) != hipSuccess) return ZERR(kErrGeneric);
             const u8* stage = (const u8*)c->batchStage.p;
@@ -1261,12 +1293,12 @@ static size_t compress_entries(ZSTD_CCtx* c, const CallParams& cp, const u8* con
             const u64 stagedBytes = (u64)nCh * cb;
             c->timer.begin(s);
             launch_batch_stage((const u64*)dTab, dLen, (u8*)c->batchStage.p, nCh, cb, s);      c->timer.mark("batch_stage", s);
-            launch_lz(rs.finder, stage, stagedBytes, nCh, seqs, lits, meta, prefix, prefixLen, cb, dictIdBytes | (cp.contentSizeFlag ? 0u : 0x100u), rs.minStrideLog, 0,
+            launch_lz(rs.finder, stage, stagedBytes, nCh, seqs, lits, meta, prefix, prefixLen, cb, dictIdBytes | (cp.contentSizeFlag ? 0u : 0x100u), rs.minStrideLog, ls.lzFrameBlocks,
                       regionParse ? (u16*)c->cand.p : nullptr, hcChains ? (u16*)((u8*)c->cand.p + cand_plane_bytes(nCh)) : nullptr,
-                      regionParse ? (u32*)((u8*)c->cand.p + cand_plane_bytes(nCh) * (hcChains ? 2 : 1)) : nullptr, hcDepth, s, c->timer.hook(), (u32*)(total + 4), dLen);
-            launch_huf_build(lits, meta, tables, slots, nCh, rs.rawLiterals, stage, cb, s, c->timer.hook(), dct, 0);
-            if (cp.checksumFlag) { launch_xxh64(stage, stagedBytes, meta, nCh, cb, 0, s, dLen);        c->timer.mark("xxh64", s); }
-            launch_seq_encode(seqs, meta, slots, nCh, strategy, (cp.checksumFlag ? 1u : 0u) | (cp.contentSizeFlag ? 0u : 2u), 1, dictID, dictIdBytes, initReps, 0, cb, stagedBytes, s, dct);
+                      regionParse ? (u32*)((u8*)c->cand.p + cand_plane_bytes(nCh) * (hcChains ? 2 : 1)) : nullptr, hcDepth, s, c->timer.hook(), (u32*)(total + 4), dLen, dFrame);
+            launch_huf_build(lits, meta, tables, slots, nCh, rs.rawLiterals, stage, cb, s, c->timer.hook(), dct, 0);      // (dct: single-block frames only, see above)
+            if (cp.checksumFlag) { launch_xxh64(stage, stagedBytes, meta, nCh, cb, frameBlocks, s, dLen, dFrame);        c->timer.mark("xxh64", s); }
+            launch_seq_encode(seqs, meta, slots, nCh, strategy, (cp.checksumFlag ? 1u : 0u) | (cp.contentSizeFlag ? 0u : 2u), 1, dictID, dictIdBytes, initReps, frameBlocks, cb, stagedBytes, s, dct, dFrame);
             c->timer.mark("seq_encode", s);
             if (d_stats) launch_seq_stats(seqs, lits, meta, nCh, stage, cb, d_stats, s);
             launch_batch_place(meta, nEnt, (const u32*)(dTab + atFirst), (const u64*)(dTab + atDst), (const u64*)(dTab + atCap), span, offsets, dGot, s);
