@@ -348,6 +348,27 @@ int ZSTDMI_debugLastRangesFrames(const ZSTD_DCtx* dctx);
 int ZSTDMI_debugLastRangesAlone(const ZSTD_DCtx* dctx);
 long long ZSTDMI_debugLastRangesStaged(const ZSTD_DCtx* dctx);
 
+/* Segmented stream decoding: ZSTD_decompressStream decodes a frame that is still arriving in SEGMENTS — runs of whole blocks —
+ * instead of collecting the whole frame first.  bytes == 0 (the default): off, ZSTD_decompressStream behaves exactly as without this
+ * call.  Otherwise `bytes` is the compressed size at which a segment is cut: whenever the frame in progress has at least that many
+ * bytes of whole blocks buffered, those blocks are decoded and handed out (1 = a segment per block, as blocks arrive; a segment never
+ * holds more than 2048 blocks).  A frame that is whole when the call first looks at it and holds fewer than `bytes` of blocks is
+ * decoded as before.  Sticky; touches no device; zeroes the two counters below; GENERIC for a NULL context.  Between segments the
+ * context keeps the last window of output on the device (and the dictionary's content until the frame has produced a window), the blocks that define the Huffman and FSE tables in force (at most four, on
+ * the host), the three repcodes and the running checksum; the host holds at most bytes + one block + the caller's input + those four
+ * blocks of a frame in progress.  The bytes handed out are those of the one-shot call, the return values follow the same protocol
+ * (0 only on a frame boundary with everything flushed); a frame checksum is verified when the last block has been decoded
+ * (checksum_wrong).  On damaged input the call returns an error no later than the end of the frame; bytes handed out before the failing
+ * segment stay handed out.  A match that reaches further back than the frame's declared window is corruption_detected here, as in the
+ * reference's streaming decoder (the one-shot call still has those bytes and decodes it).  With several device workers on the context
+ * (ZSTDMI_DCtx_setDevices) ZSTD_decompressStream returns parameter_unsupported while the switch is on. */
+size_t ZSTDMI_DCtx_setStreamSegment(ZSTD_DCtx* dctx, size_t bytes);
+/* diagnostics of the stream session (since the last ZSTDMI_DCtx_setStreamSegment, or the context's creation), counted while the
+ * switch is on: the largest number of compressed bytes held on the host at once (the input buffer plus the carried blocks); segments
+ * decoded; -1 without a context */
+long long ZSTDMI_debugStreamPeakInput(const ZSTD_DCtx* dctx);
+int ZSTDMI_debugStreamSegments(const ZSTD_DCtx* dctx);
+
 /* per-stage HIP-event timing of the LAST call (enable first).  Fills up to `cap` entries, returns the count. */
 size_t ZSTDMI_CCtx_setProfiling(ZSTD_CCtx* cctx, int enable);
 size_t ZSTDMI_DCtx_setProfiling(ZSTD_DCtx* dctx, int enable);

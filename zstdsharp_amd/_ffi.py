@@ -108,6 +108,9 @@ SIGNATURES = {
     "ZSTDMI_debugLastRangesFrames": (c_int, [c_void_p]),
     "ZSTDMI_debugLastRangesAlone": (c_int, [c_void_p]),
     "ZSTDMI_debugLastRangesStaged": (ctypes.c_longlong, [c_void_p]),
+    "ZSTDMI_DCtx_setStreamSegment": (c_size_t, [c_void_p, c_size_t]),
+    "ZSTDMI_debugStreamPeakInput": (ctypes.c_longlong, [c_void_p]),
+    "ZSTDMI_debugStreamSegments": (c_int, [c_void_p]),
     "ZSTDMI_CCtx_setProfiling": (c_size_t, [c_void_p, c_int]),
     "ZSTDMI_DCtx_setProfiling": (c_size_t, [c_void_p, c_int]),
     "ZSTDMI_CCtx_getStageTimes": (c_int, [c_void_p, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_char_p), c_int]),

@@ -731,14 +731,20 @@ __device__ __forceinline__ u32 latest_before(u64 mask, u32 firstOfBatch, u32 car
     const u64 prior = mask & lanemask_lt();
     return prior ? firstOfBatch + (63u - (u32)__builtin_clzll(prior)) : carried;
 }
-__global__ __launch_bounds__(64) void block_link_kernel(FrameDesc* __restrict__ frames, BlockDesc* __restrict__ blocks, u32 nFrames, u32 haveDict,
-                                                        u32 earlyLiterals, u32* __restrict__ status)
+// PH (a fragment of a segmented stream, ZSTDMI_DCtx_setStreamSegment): the frame's first `phantoms` blocks are earlier
+// blocks of the stream, put in front again only because they DEFINE a table some later block may still use.  They are linked like
+// any block — later blocks' hufSrc / tblSrc may name them — and then made to regenerate nothing: an RLE block of no bytes, which
+// every later stage passes over; what they themselves lack (a table defined before the oldest carried block) is no error.  A fragment
+// is one frame, linked by this kernel whatever its number of blocks.
+template <bool PH>
+__device__ __forceinline__ void block_link_body(FrameDesc* __restrict__ frames, BlockDesc* __restrict__ blocks, u32 nFrames, u32 haveDict,
+                                                u32 earlyLiterals, u32* __restrict__ status, u32 phantoms)
 {
     const u32 f = blockIdx.x, lane = threadIdx.x;
     if (f >= nFrames) return;
     FrameDesc& F = frames[f];
     const u32 first = uniform(F.firstBlock), nb = uniform(F.nbBlocks);
-    if (nb <= kLinkSmall) return;                              // (a lane of block_link_small_kernel takes it)
+    if (!PH && nb <= kLinkSmall) return;                       // (a lane of block_link_small_kernel takes it)
     const u64 dstSize = F.dstSize;
     // a formatted dictionary: every frame starts from its Huffman table and its three FSE tables (ZSTD_decompressBegin_usingDict,
     // U/ZstdDecompress.cs:1956-1990); without one nothing is defined before the frame's first block defines it
@@ -754,16 +760,17 @@ __global__ __launch_bounds__(64) void block_link_kernel(FrameDesc* __restrict__ 
             live = B.type == 2 && !B.err;
             if (live) { litType = B.litType; litSize = B.litSize; nbSeq = B.nbSeq; modes = B.modes; }
         }
+        const bool ph = PH && k0 + lane < phantoms;
         u32 err = 0;
         // the Huffman table of a treeless literals section is the latest one defined in front of it (U/ZstdDecompressBlock.cs:197-207)
         const u64 defHuf = ballot(live && litType == 2);
         u32 hufSrc = kNoBlock;
         if (live && litType == 2) hufSrc = bi;
-        else if (live && litType == 3) { hufSrc = latest_before(defHuf, first + k0, lastHuf, lane); if (hufSrc == kNoBlock) err = kErrDictionaryCorrupted; }
+        else if (live && litType == 3) { hufSrc = latest_before(defHuf, first + k0, lastHuf, lane); if (hufSrc == kNoBlock && !ph) err = kErrDictionaryCorrupted; }
         if (defHuf) lastHuf = first + k0 + (63u - (u32)__builtin_clzll(defHuf));
         // regenerated literals of Huffman-coded sections, one after the other in the frame's scratch (dstSize long: a block that does
         // not fit takes none of it and is an error, so the bound holds for every block whatever later kernels do with the frame)
-        const bool coded = live && litType >= 2;
+        const bool coded = live && litType >= 2 && !ph;
         const u64 mine = coded ? litSize : 0u;
         u64 incl = mine;
 #pragma unroll
@@ -773,7 +780,7 @@ __global__ __launch_bounds__(64) void block_link_kernel(FrameDesc* __restrict__ 
         litAcc += __shfl(incl, 63);
         // repeat-mode FSE tables: the latest table of that kind defined in front of the block (:1780-1786)
         const bool seqs = live && nbSeq != 0;
-        if (ballot(seqs)) hasSeq = 1;
+        if (ballot(seqs && !ph)) hasSeq = 1;
         u32 src3[3];
 #pragma unroll
         for (u32 t = 0; t < 3; ++t) {
@@ -781,10 +788,11 @@ __global__ __launch_bounds__(64) void block_link_kernel(FrameDesc* __restrict__ 
             const u64 def = ballot(seqs && mode != 3);
             u32& last = t == 0 ? lastTbl0 : t == 1 ? lastTbl1 : lastTbl2;
             src3[t] = bi;
-            if (seqs && mode == 3) { src3[t] = latest_before(def, first + k0, last, lane); if (src3[t] == kNoBlock) err = err ? err : (u32)kErrCorruption; }
+            if (seqs && mode == 3) { src3[t] = latest_before(def, first + k0, last, lane); if (src3[t] == kNoBlock && !ph) err = err ? err : (u32)kErrCorruption; }
             if (def) last = first + k0 + (63u - (u32)__builtin_clzll(def));
         }
-        if (live) {
+        if (ph && have) { BlockDesc& B = blocks[bi]; B.type = 1; B.outSize = 0; B.nbSeq = 0; }
+        else if (live) {
             BlockDesc& B = blocks[bi];
             if (litType >= 2) {
                 B.hufSrc = hufSrc; B.litRel = litRel;
@@ -803,6 +811,16 @@ __global__ __launch_bounds__(64) void block_link_kernel(FrameDesc* __restrict__ 
         if (hasSeq && dstSize >= (1u << 20) && dstSize < (1ull << 30))
             atomicAdd(reinterpret_cast<unsigned long long*>(status + kStBigBins) + highbit32((u32)(dstSize >> 20)), (unsigned long long)dstSize);
     }
+}
+__global__ __launch_bounds__(64) void block_link_kernel(FrameDesc* __restrict__ frames, BlockDesc* __restrict__ blocks, u32 nFrames, u32 haveDict,
+                                                        u32 earlyLiterals, u32* __restrict__ status)
+{
+    block_link_body<false>(frames, blocks, nFrames, haveDict, earlyLiterals, status, 0);
+}
+__global__ __launch_bounds__(64) void block_link_stream_kernel(FrameDesc* __restrict__ frames, BlockDesc* __restrict__ blocks, u32 nFrames, u32 haveDict,
+                                                               u32 earlyLiterals, u32* __restrict__ status, u32 phantoms)
+{
+    block_link_body<true>(frames, blocks, nFrames, haveDict, earlyLiterals, status, phantoms);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -852,9 +870,15 @@ __global__ __launch_bounds__(1024) void seq_scan_kernel(BlockDesc* __restrict__ 
     if (threadIdx.x == 0) { status[kStSeqLo] = (u32)total; status[kStSeqHi] = (u32)(total >> 32); }
 }
 
-void launch_block_prepass(const u8* src, FrameDesc* frames, BlockDesc* blocks, u32 nFrames, u32 nBlocks, u32 haveDict, u32 earlyLiterals, u32* status, hipStream_t stream)
+void launch_block_prepass(const u8* src, FrameDesc* frames, BlockDesc* blocks, u32 nFrames, u32 nBlocks, u32 haveDict, u32 earlyLiterals, u32* status, hipStream_t stream,
+                          u32 phantoms)
 {
     hipLaunchKernelGGL(block_parse_kernel, dim3((nBlocks + 255) / 256), dim3(256), 0, stream, src, blocks, nBlocks, status);
+    if (phantoms) {             // a fragment of a segmented stream: one frame whose first blocks are carried definers
+        hipLaunchKernelGGL(block_link_stream_kernel, dim3(nFrames), dim3(64), 0, stream, frames, blocks, nFrames, haveDict, earlyLiterals, status, phantoms);
+        hipLaunchKernelGGL(seq_scan_kernel, dim3(1), dim3(1024), 0, stream, blocks, nBlocks, status);
+        return;
+    }
     hipLaunchKernelGGL(block_link_small_kernel, dim3((nFrames + 63) / 64), dim3(64), 0, stream, frames, blocks, nFrames, haveDict, earlyLiterals, status);
     if (nBlocks > nFrames) hipLaunchKernelGGL(block_link_kernel, dim3(nFrames), dim3(64), 0, stream, frames, blocks, nFrames, haveDict, earlyLiterals, status);      // (some frame has several blocks)
     hipLaunchKernelGGL(seq_scan_kernel, dim3(1), dim3(1024), 0, stream, blocks, nBlocks, status);

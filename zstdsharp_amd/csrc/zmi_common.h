@@ -124,6 +124,10 @@ struct FrameDesc {      // one per frame found by the frame walk (U/ZstdDecompre
     u64 originOff;      // then: index of its first entry in the origin array
 };
 
+// XXH64 of a frame that is decoded in segments (decode_stream.hip): the state between two segments.  reset: acc = the four seeds
+// (P1 + P2, P2, 0, -P1), everything else zero (xxh_carry_reset, zstd_mi355x_dec.hip)
+struct XxhCarry { u64 acc[4]; u64 total; u32 tailLen; u32 hash; u8 tail[32]; };
+
 constexpr u32 kNoBlock   = 0xFFFFFFFFu;     // table source: nothing defined it (corruption, or the default where that is legal)
 constexpr u32 kDictBlock = 0xFFFFFFFEu;     // table source: the formatted dictionary
 

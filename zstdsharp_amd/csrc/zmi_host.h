@@ -71,7 +71,8 @@ void launch_ranges_gather(const RangeIn* in, const RangeRec* recs, u64* res, u32
 void launch_seq_stats(const Seq* seqs, const u8* lits, const ChunkMeta* meta, u32 nChunks, const u8* src, u32 chunkBytes, u32* stats, hipStream_t stream);
 void launch_dict_parse(const u8* dict, u32 dictSize, DictInfo* out, hipStream_t stream);
 void launch_dict_ctables(const u8* dict, u32 dictSize, const DictInfo* info, DictCTables* out, hipStream_t stream);
-void launch_block_prepass(const u8* src, FrameDesc* frames, BlockDesc* blocks, u32 nFrames, u32 nBlocks, u32 haveDict, u32 earlyLiterals, u32* status, hipStream_t stream);
+void launch_block_prepass(const u8* src, FrameDesc* frames, BlockDesc* blocks, u32 nFrames, u32 nBlocks, u32 haveDict, u32 earlyLiterals, u32* status, hipStream_t stream,
+                          u32 phantoms = 0);     // phantoms: decode_walk.hip block_link_body
 void launch_seq_decode(const u8* src, const FrameDesc* frames, BlockDesc* blocks, u32 nBlocks, SeqRec* recs, u32* status,
                        const u8* dictFull, const DictInfo* di, hipStream_t stream);
 void launch_block_offsets(FrameDesc* frames, BlockDesc* blocks, u32 nFrames, const DictInfo* di, u32 rescan, u64 dstCapacity, u32* status, hipStream_t stream);
@@ -79,6 +80,9 @@ void launch_decode_literals(const u8* src, u8* out, u8* scratch, const FrameDesc
                             u8* slowFlags, u32 mode, const u8* dictFull, const DictInfo* di, hipStream_t stream, StageHook hook);
 void launch_place_literals(const u8* src, u8* out, const u8* scratch, const FrameDesc* frames, const BlockDesc* blocks, u32 nBlocks,
                            const SeqRec* recs, const u32* status, hipStream_t stream);
+// a segmented stream's carried state (decode_stream.hip)
+void launch_stream_carry(const BlockDesc* blocks, u32 nBlocks, DictInfo* reps, hipStream_t stream);
+void launch_stream_xxh(XxhCarry* st, const u8* data, u64 n, u32 final, hipStream_t stream);
 void launch_exec_matches(const u8* src, u8* out, const FrameDesc* frames, const BlockDesc* blocks, u32 nFrames, const SeqRec* recs, u32* status,
                          const u8* dict, u32 dictSize, hipStream_t stream, int wide);
 void launch_origin_select(FrameDesc* frames, u32 nFrames, u64 minBytes, u32* list, u32 listCap, u64 originCap, u32* status, hipStream_t stream);

@@ -5,6 +5,7 @@
 #include <stdio.h>
 #include <functional>
 #include "zmi_pack_runs.h"
+#include "zmi_stream_scan.h"
 #include "zmi_host.h"
 
 struct ZSTD_DCtx_s {
@@ -28,6 +29,31 @@ struct ZSTD_DCtx_s {
     StageTimer timer;
     // streaming adapter (ZSTD_decompressStream): whole frames are collected on the host, decoded in batches
     std::vector<u8> dIn, dOut; size_t dOutPos = 0; bool hostage = false;
+    // ZSTDMI_DCtx_setStreamSegment: a frame that is still arriving is decoded in segments, runs of whole blocks; `seg`
+    // is what one segment leaves for the next.  dIn then starts at the first block that has not been decoded yet.
+    size_t segBytes = 0;        // 0 = off: whole frames only
+    struct CarriedBlock { std::vector<u8> bytes; u32 defines; };        // a block (header and body) that defines a live table
+    struct SegBlock { size_t off, size; u32 defines; };                 // a whole block of dIn, scanned and not yet decoded
+    struct StreamSeg {
+        bool active = false;    // inside a frame
+        bool first = true;      // no segment of it decoded yet: repcodes from the dictionary or the format's
+        bool lastSeen = false;  // `blocks` ends with the frame's last block (and the checksum behind it is there)
+        u8 hdr[12] = {}; u32 hdrLen = 0;        // the header every fragment begins with
+        u8 lastByte = 0;        // (source of a one-byte copy)
+        u64 histKeep = 0;       // bytes of history a later block may reach once the frame has produced a window: the window, at most
+                                // what a sequence record can name.  Until then everything is kept: the format lets a block reach the
+                                // WHOLE dictionary while the frame's output has not exceeded the window (ZSTD_checkDictValidity)
+        u64 window = 0;         // the window the header declares (a single-segment frame: its content size)
+        XxhCarry xxhHost = {};  // (source and target of the checksum state's asynchronous copies)
+        u64 blockMax = 0;       // the bound of a block's content as the fragment's header states it: min(window, 128 KiB)
+        u64 fcs = ~0ull, produced = 0; bool checksum = false;
+        std::vector<CarriedBlock> carried;      // at most four, in stream order
+        std::vector<SegBlock> blocks; size_t scanned = 0;
+        u64 histLen = 0; int histCur = 0;
+        u64 skip = 0;           // bytes of a skippable frame still to drop
+    } seg;
+    DevBuf hist[2], segReps, segXxh;            // the history (rolled from one buffer into the other), the repcode triple (a DictInfo), the XXH64 state
+    int streamSegments = 0; long long streamPeakInput = 0;      // (debug hooks; the setter zeroes them)
     u32 litDecoder = 0;         // 0 auto, 1 serial (4 lanes per frame), 2 self-synchronising (256 lanes per frame), 3 serial with compact tables
     // dictionary (ZSTD_DCtx_loadDictionary): host copy, uploaded at the next decompression.  Raw content: the bytes are the
     // history.  Formatted (magic 0xEC30A437): dict_parse_kernel validates the header and fills `info`; the history is the content.
@@ -62,6 +88,7 @@ size_t ZSTD_freeDCtx(ZSTD_DCtx* d)
         (void)hipSetDevice(d->device);
         if (d->ownStream) (void)hipStreamSynchronize(d->ownStream);
         d->frames.release(); d->blocks.release(); d->recs.release(); d->status.release(); d->scratch.release(); d->walkWs.release(); d->slowFlags.release(); d->stageSrc.release(); d->stageDst.release(); d->dict.release(); d->dictInfoDev.release(); d->origin.release(); d->originList.release(); d->batchIn.release(); d->batchOut.release(); d->blockKeys.release(); d->seekTab.release(); d->seekSum.release(); d->edge.release(); d->pfxStage.release(); d->rangesWs.release(); d->rangesIn.release(); d->rangesRec.release(); d->rangesRes.release(); d->arena.release();
+        d->hist[0].release(); d->hist[1].release(); d->segReps.release(); d->segXxh.release();
         d->timer.destroy();
         if (d->aux) { (void)hipStreamSynchronize(d->aux); (void)hipStreamDestroy(d->aux); }
         if (d->auxDone) (void)hipEventDestroy(d->auxDone);
@@ -270,7 +297,11 @@ static bool ensure_lists(ZSTD_DCtx* d, u32 nFrames, u32 nBlocks, u64 total)
 // Everything behind the frame walk: the lists (d->frames, d->blocks; offsets relative to d_src and d_dst) through block_prepass,
 // seq_decode, block_offsets, the literal decoder, the origin path and exec_matches.  `tail` enqueues what the caller wants read back
 // with the last status read (-> false: failed); st = the status words after it.  -> 0 or the error of the whole run.
-static size_t decode_lists(ZSTD_DCtx* d, const DecodeDict& dd, u8* d_dst, const u8* d_src, u32 nFrames, u32 nBlocks, u32 nUnsized, size_t dstCapacity, u32* st, const std::function<bool()>& tail)
+// `link` (a fragment of a segmented stream, decode_fragment): the first link->phantoms blocks only define tables, and the frame's
+// repcodes start from link->reps where that is not NULL.
+struct StreamLink { u32 phantoms; const DictInfo* reps; };
+static size_t decode_lists(ZSTD_DCtx* d, const DecodeDict& dd, u8* d_dst, const u8* d_src, u32 nFrames, u32 nBlocks, u32 nUnsized, size_t dstCapacity, u32* st, const std::function<bool()>& tail,
+                           const StreamLink* link = nullptr)
 {
     hipStream_t s = d->stream;
     u32* status = (u32*)d->status.p;
@@ -283,7 +314,7 @@ static size_t decode_lists(ZSTD_DCtx* d, const DecodeDict& dd, u8* d_dst, const 
     // Whether it does is decided once the pre-pass has counted both kinds of work (below).
     constexpr u32 kOverlapBlocks = 12288;
     const bool early = d->overlapMode == 2 || (d->overlapMode == 0 && nBlocks <= kOverlapBlocks);
-    launch_block_prepass(d_src, frames, blocks, nFrames, nBlocks, fmt ? 1u : 0u, early ? 1u : 0u, status, s);
+    launch_block_prepass(d_src, frames, blocks, nFrames, nBlocks, fmt ? 1u : 0u, early ? 1u : 0u, status, s, link ? link->phantoms : 0u);
     { const size_t e = status_read(d, st); if (isErr(e)) return e; }
     d->timer.mark("block_prepass", s);
     const u64 nSeq = st_u64(st, kStSeqLo, kStSeqHi);
@@ -333,7 +364,7 @@ static size_t decode_lists(ZSTD_DCtx* d, const DecodeDict& dd, u8* d_dst, const 
         auxGuard.on = true;
     }
     launch_seq_decode(d_src, frames, blocks, nBlocks, recs, status, dictFull, dinfo, s);            d->timer.mark("seq_decode", s);
-    launch_block_offsets(frames, blocks, nFrames, dinfo, nUnsized ? 1u : 0u, dstCapacity, status, s);  d->timer.mark("block_offsets", s);
+    launch_block_offsets(frames, blocks, nFrames, link && link->reps ? link->reps : dinfo, nUnsized ? 1u : 0u, dstCapacity, status, s);  d->timer.mark("block_offsets", s);
     if (auxGuard.on) { if (hipStreamWaitEvent(s, d->auxDone, 0) != hipSuccess) return ZERR(kErrGeneric); d->timer.mark("decode_literals", s); }     // (what of it seq_decode did not cover)
     else launch_decode_literals(d_src, d_dst, (u8*)d->scratch.p, frames, blocks, nBlocks, status, (u8*)d->slowFlags.p, d->litDecoder, dictFull, dinfo, s, d->timer.hook());
     launch_place_literals(d_src, d_dst, (const u8*)d->scratch.p, frames, blocks, nBlocks, recs, status, s);    d->timer.mark("place_literals", s);
@@ -883,6 +914,304 @@ static size_t dstream_drain(ZSTD_DCtx* d, ZSTD_outBuffer* o)
     if (d->dOutPos == d->dOut.size()) { d->dOut.clear(); d->dOutPos = 0; }
     return d->dOut.size() - d->dOutPos;
 }
+// ---------------- a long frame in segments (ZSTDMI_DCtx_setStreamSegment) ----------------
+// With the switch on, a frame that is not whole when the adapter first looks at it — or holds at least `segBytes` of blocks — is decoded
+// as it arrives: whenever that many bytes of whole blocks are buffered they become one FRAGMENT, an ordinary frame as far as the
+// pipeline can tell: a header without content size and checksum, the carried blocks (earlier blocks that define a Huffman or FSE table
+// still in force; the link kernels parse them and make them regenerate nothing), and the segment's blocks, the last one marked last.
+// History is the context's device buffer, passed the way a referenced prefix is; the repcodes come from and go to a device triple;
+// the frame's checksum runs over the segments' outputs with carried state (decode_stream.hip).
+// a segment holds at most this many blocks, so that its output's bound (blocks x 128 KiB) stays 256 MiB whatever the blocks hold
+constexpr size_t kSegMaxBlocks = 2048;
+constexpr u64 kHistMax = kRecOffMax;            // (a match further back is refused by seq_decode: windowTooLarge)
+
+// a zstd frame header as the segmented adapter needs it -> false: not all of it is there (or no zstd frame)
+struct HostHeader { size_t fhs; u64 window, fcs; u32 didBytes; bool single, checksum; u8 wd; };
+static bool host_header(const u8* src, size_t n, HostHeader* h)
+{
+    auto rd32 = [](const u8* p) { return (u32)p[0] | ((u32)p[1] << 8) | ((u32)p[2] << 16) | ((u32)p[3] << 24); };
+    if (n < 5 || rd32(src) != 0xFD2FB528u) return false;
+    const u8 fhd = src[4];
+    static const u32 did[4] = { 0, 1, 2, 4 }, fcsB[4] = { 0, 2, 4, 8 };
+    const u32 single = (fhd >> 5) & 1, fcsId = fhd >> 6;
+    h->fhs = 5 + !single + did[fhd & 3] + fcsB[fcsId] + (single && !fcsId);
+    if (n < h->fhs) return false;
+    h->single = single != 0; h->checksum = ((fhd >> 2) & 1) != 0; h->didBytes = did[fhd & 3]; h->wd = single ? 0 : src[5];
+    size_t pos = 5 + !single + h->didBytes;
+    h->fcs = ~0ull;
+    switch (fcsId) {
+    case 0: if (single) h->fcs = src[pos]; break;
+    case 1: h->fcs = (u64)((u32)src[pos] | ((u32)src[pos + 1] << 8)) + 256; break;
+    case 2: h->fcs = rd32(src + pos); break;
+    default: h->fcs = (u64)rd32(src + pos) | ((u64)rd32(src + pos + 4) << 32); break;
+    }
+    if (single) h->window = h->fcs;
+    else { const u32 wlog = (h->wd >> 3) + 10; const u64 w = 1ull << wlog; h->window = w + (w >> 3) * (h->wd & 7); }
+    return true;
+}
+static u64 window_of_descriptor(u8 wd) { const u64 w = 1ull << ((wd >> 3) + 10); return w + (w >> 3) * (wd & 7); }
+// the smallest window descriptor that covers `size` bytes (a single-segment frame has none of its own)
+static u8 descriptor_covering(u64 size)
+{
+    for (u32 e = 0; e < 22; ++e) for (u32 m = 0; m < 8; ++m) { const u8 wd = (u8)((e << 3) | m); if (window_of_descriptor(wd) >= size) return wd; }
+    return (u8)((21u << 3) | 7u);
+}
+
+static void stream_end_frame(ZSTD_DCtx* d)
+{
+    ZSTD_DCtx_s::StreamSeg& g = d->seg;
+    g.active = false; g.first = true; g.lastSeen = false; g.carried.clear(); g.blocks.clear(); g.scanned = 0; g.histLen = 0; g.skip = 0;
+}
+static void stream_note_input(ZSTD_DCtx* d)
+{
+    size_t held = d->dIn.size();
+    for (const auto& c : d->seg.carried) held += c.bytes.size();
+    if ((long long)held > d->streamPeakInput) d->streamPeakInput = (long long)held;
+}
+static void xxh_carry_reset(XxhCarry* x)
+{
+    const u64 P1 = 0x9E3779B185EBCA87ULL, P2 = 0xC2B2AE3D27D4EB4FULL;
+    memset(x, 0, sizeof *x);
+    x->acc[0] = P1 + P2; x->acc[1] = P2; x->acc[2] = 0; x->acc[3] = 0 - P1;
+}
+
+// the frame whose header (all of it) is at the front of dIn begins: the fragment header, the first history, the checksum state
+static size_t stream_begin_frame(ZSTD_DCtx* d, const HostHeader& h)
+{
+    ZSTD_DCtx_s::StreamSeg& g = d->seg;
+    size_t e = dctx_bind(d); if (isErr(e)) return e;
+    e = dctx_sync_dictionary(d); if (isErr(e)) return e;
+    stream_end_frame(d);
+    const u8* src = d->dIn.data();
+    const u8 wd = h.single ? descriptor_covering(h.fcs) : h.wd;
+    u32 n = 0;
+    g.hdr[n++] = 0x28; g.hdr[n++] = 0xB5; g.hdr[n++] = 0x2F; g.hdr[n++] = 0xFD;
+    g.hdr[n++] = (u8)(src[4] & 3);              // the dictID's size; no content size, no checksum, a window descriptor
+    g.hdr[n++] = wd;
+    for (u32 i = 0; i < h.didBytes; ++i) g.hdr[n++] = src[5 + !h.single + i];
+    g.hdrLen = n;
+    const u64 fragWindow = window_of_descriptor(wd);
+    g.blockMax = fragWindow < (1u << 17) ? fragWindow : (1u << 17);
+    g.histKeep = h.window < kHistMax ? h.window : kHistMax; g.window = h.window;
+    g.fcs = h.fcs; g.checksum = h.checksum; g.produced = 0;
+    if (!d->segReps.ensure(sizeof(DictInfo)) || !d->segXxh.ensure(sizeof(XxhCarry)) || !d->status.ensure(kStWords * sizeof(u32))) return ZERR(kErrMemoryAllocation);
+    hipStream_t s = d->stream;
+    const DecodeDict dd = decode_dict(d);
+    if (dd.dictContent && dd.dictContentSize) {         // the dictionary's content, all of it, is the first history
+        const u64 keep = dd.dictContentSize < kHistMax ? dd.dictContentSize : kHistMax;
+        if (!d->hist[0].ensure((size_t)keep + 64)) return ZERR(kErrMemoryAllocation);
+        if (hipMemcpyAsync(d->hist[0].p, dd.dictContent + (dd.dictContentSize - keep), (size_t)keep, hipMemcpyDeviceToDevice, s) != hipSuccess) return ZERR(kErrGeneric);
+        g.histLen = keep; g.histCur = 0;
+    }
+    if (g.checksum) {
+        xxh_carry_reset(&g.xxhHost);
+        if (hipMemcpyAsync(d->segXxh.p, &g.xxhHost, sizeof g.xxhHost, hipMemcpyHostToDevice, s) != hipSuccess) return ZERR(kErrGeneric);
+    }
+    e = stream_wait(s); if (isErr(e)) return e;
+    d->dIn.erase(d->dIn.begin(), d->dIn.begin() + (ptrdiff_t)h.fhs);
+    g.active = true;
+    return 0;
+}
+
+// one fragment (srcSize bytes at d_src: header, `phantoms` carried blocks, the segment's blocks) through the pipeline -> its content
+// in d_dst, the repcodes behind it in d->segReps.  -> the content's size, or the error
+static size_t decode_fragment(ZSTD_DCtx* d, u8* d_dst, size_t dstCapacity, const u8* d_src, size_t srcSize, u32 phantoms)
+{
+    ZSTD_DCtx_s::StreamSeg& g = d->seg;
+    hipStream_t s = d->stream;
+    u32* status = (u32*)d->status.p;
+    DecodeDict dd = decode_dict(d);
+    dd.dictContent = g.histLen ? (const u8*)d->hist[g.histCur].p : nullptr; dd.dictContentSize = (u32)g.histLen;
+    d->timer.begin(s);
+    { const size_t e = status_reset(d); if (isErr(e)) return e; }
+    u32 st[kStWords] = {};
+    // (the exact serial walk: one frame, and it checks the dictID the fragment's header repeats)
+    launch_frame_walk_serial(d_src, srcSize, nullptr, nullptr, 1, status, dd.dictID, 0, s);
+    { const size_t e = status_read(d, st); if (isErr(e)) return e; }
+    if (st[kStErr]) return ZERR(st[kStErr]);
+    const u32 nFrames = st[kStFrames], nBlocks = st[kStBlocks];
+    const u64 total = st_u64(st, kStTotalLo, kStTotalHi);
+    if (nFrames != 1 || nBlocks <= phantoms || total > dstCapacity) return ZERR(kErrGeneric);       // (the host built it otherwise)
+    if (!ensure_lists(d, nFrames, nBlocks, total)) return ZERR(kErrMemoryAllocation);
+    FrameDesc* frames = (FrameDesc*)d->frames.p; BlockDesc* blocks = (BlockDesc*)d->blocks.p;
+    launch_frame_walk_serial(d_src, srcSize, frames, blocks, 1, status, dd.dictID, 1, s);
+    d->timer.mark("frame_walk", s);
+    const StreamLink link = { phantoms, g.first ? nullptr : (const DictInfo*)d->segReps.p };
+    { const size_t e = decode_lists(d, dd, d_dst, d_src, nFrames, nBlocks, 1, dstCapacity, st, [&]() -> bool {
+          launch_stream_carry(blocks, nBlocks, (DictInfo*)d->segReps.p, s);
+          return true;
+      }, &link);
+      if (isErr(e)) return e; }
+    d->timer.finish();
+    if (st[kStErrKeyLo] != 0xFFFFFFFFu || st[kStErrKeyHi] != 0xFFFFFFFFu) return ZERR(st[kStErrKeyLo] & 0xFFFFu);
+    if (st[kStErr]) return ZERR(st[kStErr]);
+    return (size_t)st_u64(st, kStActualLo, kStActualHi);
+}
+
+// the whole blocks at the front of dIn (g.blocks) as one segment: decoded into dOut, the carried state brought forward
+static size_t stream_decode_segment(ZSTD_DCtx* d)
+{
+    ZSTD_DCtx_s::StreamSeg& g = d->seg;
+    hipStream_t s = d->stream;
+    size_t e = dctx_bind(d); if (isErr(e)) return e;
+    const u32 P = (u32)g.carried.size();
+    size_t fragSize = g.hdrLen + g.scanned;
+    for (const auto& c : g.carried) fragSize += c.bytes.size();
+    const size_t cap = (size_t)((P + g.blocks.size()) * g.blockMax);
+    if (!d->stageSrc.ensure(fragSize + 64) || !d->stageDst.ensure(cap + 64)) return ZERR(kErrMemoryAllocation);
+    u8* const frag = (u8*)d->stageSrc.p; u8* const out = (u8*)d->stageDst.p;
+    size_t at = 0;
+    auto put = [&](const u8* p, size_t n) -> bool { const bool ok = hipMemcpyAsync(frag + at, p, n, hipMemcpyHostToDevice, s) == hipSuccess; at += n; return ok; };
+    if (!put(g.hdr, g.hdrLen)) return ZERR(kErrGeneric);
+    for (const auto& c : g.carried) if (!put(c.bytes.data(), c.bytes.size())) return ZERR(kErrGeneric);
+    const size_t lastAt = at + g.blocks.back().off;
+    if (!put(d->dIn.data(), g.scanned)) return ZERR(kErrGeneric);
+    g.lastByte = (u8)(d->dIn[g.blocks.back().off] | 1);         // the fragment ends with its last block
+    if (hipMemcpyAsync(frag + lastAt, &g.lastByte, 1, hipMemcpyHostToDevice, s) != hipSuccess) return ZERR(kErrGeneric);
+    const size_t n = decode_fragment(d, out, cap, frag, fragSize, P);
+    if (isErr(n)) return n;
+    g.produced += n;
+    if (g.fcs != ~0ull && (g.produced > g.fcs || (g.lastSeen && g.produced != g.fcs))) return ZERR(kErrCorruption);      // U/ZstdDecompress.cs:1177-1184
+    XxhCarry& x = g.xxhHost;
+    if (g.checksum) {           // (on this stream: beside the copies below, on the context's second stream, the stream was measured slower)
+        launch_stream_xxh((XxhCarry*)d->segXxh.p, out, n, g.lastSeen ? 1u : 0u, s);
+        if (g.lastSeen && hipMemcpyAsync(&x, d->segXxh.p, sizeof x, hipMemcpyDeviceToHost, s) != hipSuccess) return ZERR(kErrGeneric);
+    }
+    d->dOut.resize(n); d->dOutPos = 0;
+    if (n && hipMemcpyAsync(d->dOut.data(), out, n, hipMemcpyDeviceToHost, s) != hipSuccess) return ZERR(kErrGeneric);
+    if (!g.lastSeen) {          // what later blocks may reach of (history, this output), into the other buffer: everything while the
+                                // frame has produced less than its window, the last histKeep bytes from then on
+        const u64 limit = g.produced >= g.window ? g.histKeep : kHistMax;
+        const u64 keep = g.histLen + n < limit ? g.histLen + n : limit;
+        const u64 fromOut = n < keep ? n : keep, fromOld = keep - fromOut;
+        DevBuf& to = d->hist[g.histCur ^ 1];
+        // (a window of up to 64 MiB is allocated at once, a larger one doubles: every growth is a hipFree and a hipMalloc)
+        u64 room = keep;
+        if (to.cap < keep + 64) { const u64 top = g.histKeep > keep ? g.histKeep : keep; room = (g.histKeep <= (64u << 20) || 2 * keep > top) ? top : 2 * keep; }
+        if (!to.ensure((size_t)room + 64)) return ZERR(kErrMemoryAllocation);
+        if (fromOld && hipMemcpyAsync(to.p, (const u8*)d->hist[g.histCur].p + (g.histLen - fromOld), (size_t)fromOld, hipMemcpyDeviceToDevice, s) != hipSuccess) return ZERR(kErrGeneric);
+        if (fromOut && hipMemcpyAsync((u8*)to.p + fromOld, out + (n - fromOut), (size_t)fromOut, hipMemcpyDeviceToDevice, s) != hipSuccess) return ZERR(kErrGeneric);
+        g.histCur ^= 1; g.histLen = keep;
+    }
+    e = stream_wait(s); if (isErr(e)) return e;
+    d->streamSegments++;
+    g.first = false;
+    size_t consumed = g.scanned;
+    if (g.lastSeen) {
+        if (g.checksum) {
+            const u8* c = d->dIn.data() + g.scanned;
+            const u32 want = (u32)c[0] | ((u32)c[1] << 8) | ((u32)c[2] << 16) | ((u32)c[3] << 24);
+            if (x.hash != want) return ZERR(kErrChecksumWrong);
+            consumed += 4;
+        }
+        d->dIn.erase(d->dIn.begin(), d->dIn.begin() + (ptrdiff_t)consumed);
+        stream_end_frame(d);
+        return 0;
+    }
+    // which blocks define the tables in force now: per table the latest definer, among the carried blocks and this segment's
+    int owner[4] = { -1, -1, -1, -1 };
+    for (u32 i = 0; i < P; ++i) for (u32 t = 0; t < 4; ++t) if (g.carried[i].defines & (1u << t)) owner[t] = (int)i;
+    for (size_t j = 0; j < g.blocks.size(); ++j) for (u32 t = 0; t < 4; ++t) if (g.blocks[j].defines & (1u << t)) owner[t] = (int)(P + j);
+    std::vector<ZSTD_DCtx_s::CarriedBlock> next;
+    for (int k = 0; k < (int)(P + g.blocks.size()); ++k) {      // (stream order; at most four are kept)
+        if (k != owner[0] && k != owner[1] && k != owner[2] && k != owner[3]) continue;
+        ZSTD_DCtx_s::CarriedBlock c;
+        if (k < (int)P) c = std::move(g.carried[k]);
+        else { const ZSTD_DCtx_s::SegBlock& b = g.blocks[k - P]; c.bytes.assign(d->dIn.begin() + (ptrdiff_t)b.off, d->dIn.begin() + (ptrdiff_t)(b.off + b.size)); c.defines = b.defines; c.bytes[0] &= 0xFE; }
+        next.push_back(std::move(c));
+    }
+    g.carried.swap(next);
+    d->dIn.erase(d->dIn.begin(), d->dIn.begin() + (ptrdiff_t)consumed);
+    g.blocks.clear(); g.scanned = 0;
+    return 0;
+}
+
+// one step of the segmented adapter with nothing pending in dOut -> 1: something moved (output in dOut, or state), 0: more input is
+// needed, or an error
+static size_t stream_step(ZSTD_DCtx* d)
+{
+    ZSTD_DCtx_s::StreamSeg& g = d->seg;
+    if (g.skip) {               // inside a skippable frame
+        const size_t n = g.skip < d->dIn.size() ? (size_t)g.skip : d->dIn.size();
+        d->dIn.erase(d->dIn.begin(), d->dIn.begin() + (ptrdiff_t)n); g.skip -= n;
+        return n ? 1 : 0;
+    }
+    if (g.active) {
+        const size_t segBytes = d->segBytes ? d->segBytes : 1;
+        while (!g.lastSeen && g.blocks.size() < kSegMaxBlocks) {
+            ScanBlock b;
+            const size_t sz = scan_block(d->dIn.data() + g.scanned, d->dIn.size() - g.scanned, &b);
+            if (!sz) break;
+            if (b.type == 3) return ZERR(kErrCorruption);
+            if (b.last && g.checksum && d->dIn.size() - (g.scanned + sz) < 4) break;        // whole only with its checksum
+            g.blocks.push_back({ g.scanned, sz, b.defines }); g.scanned += sz;
+            if (b.last) g.lastSeen = true;
+        }
+        if (g.blocks.empty() || !(g.lastSeen || g.scanned >= segBytes || g.blocks.size() >= kSegMaxBlocks)) return 0;
+        const size_t e = stream_decode_segment(d);
+        return isErr(e) ? e : 1;
+    }
+    // on a frame boundary: whole frames below the segment size go the way they always went, all that are there in one run
+    size_t whole = 0; unsigned long long bound = 0;
+    while (whole < d->dIn.size()) {
+        const u8* p = d->dIn.data() + whole; const size_t n = d->dIn.size() - whole;
+        { u64 w = host_frame_window(p, n);
+          if (w && w < 1024) w = 1024;
+          if (w > (1ull << d->windowLogMax)) { if (whole) break; return ZERR(kErrWindowTooLarge); } }
+        unsigned long long b = 0;
+        const size_t fs = host_frame_size_info(p, n, &b);
+        HostHeader h;
+        if (isErr(fs)) {
+            if (whole) break;                                   // (first what is whole)
+            if (fs != ZERR(kErrSrcSizeWrong)) return fs;
+            if (n >= 8 && (((u32)p[0] | ((u32)p[1] << 8) | ((u32)p[2] << 16) | ((u32)p[3] << 24)) & 0xFFFFFFF0u) == 0x184D2A50u) {
+                g.skip = (u64)((u32)p[4] | ((u32)p[5] << 8) | ((u32)p[6] << 16) | ((u32)p[7] << 24)) + 8;
+                return 1;
+            }
+            if (!host_header(p, n, &h)) return 0;               // the header itself is still arriving
+            const size_t e = stream_begin_frame(d, h);
+            return isErr(e) ? e : 1;
+        }
+        if (d->segBytes && host_header(p, n, &h) && fs - h.fhs - (h.checksum ? 4 : 0) >= d->segBytes) {
+            if (whole) break;
+            const size_t e = stream_begin_frame(d, h);
+            return isErr(e) ? e : 1;
+        }
+        whole += fs; bound += b;
+    }
+    if (!whole) return 0;
+    d->dOut.resize((size_t)bound); d->dOutPos = 0;
+    const size_t r = ZSTD_decompressDCtx_impl(d, d->dOut.data(), d->dOut.size(), d->dIn.data(), whole);
+    if (isErr(r)) { d->dOut.clear(); return r; }
+    d->dOut.resize(r);
+    d->dIn.erase(d->dIn.begin(), d->dIn.begin() + (ptrdiff_t)whole);
+    return 1;
+}
+
+static size_t stream_segmented(ZSTD_DCtx* d, ZSTD_outBuffer* output, ZSTD_inBuffer* input)
+{
+    if (d->workers.size() > 1) return ZERR(kErrParameterUnsupported);      // (segments are one device's)
+    if (d->hostage && input->pos < input->size) { input->pos++; d->hostage = false; }
+    size_t pending = dstream_drain(d, output);
+    if (!pending) {
+        if (input->size > input->pos) { d->dIn.insert(d->dIn.end(), (const u8*)input->src + input->pos, (const u8*)input->src + input->size); input->pos = input->size; }
+        stream_note_input(d);
+        for (;;) {
+            const size_t r = stream_step(d);
+            if (isErr(r)) { d->dIn.clear(); d->dOut.clear(); d->dOutPos = 0; d->hostage = false; stream_end_frame(d); return r; }     // what was handed out stays handed out
+            if (!r) break;
+            pending = dstream_drain(d, output);
+            if (pending) break;
+        }
+    }
+    if (pending) {
+        if (!d->hostage && input->pos == input->size && input->pos > 0) { input->pos--; d->hostage = true; }
+        return 1;
+    }
+    if (d->hostage) return 1;
+    return (!d->seg.active && !d->seg.skip && d->dIn.empty()) ? 0 : 1;     // 0 only on a frame boundary
+}
+
 static size_t ZSTD_decompressStream_impl(ZSTD_DCtx* d, ZSTD_outBuffer* output, ZSTD_inBuffer* input)
 {
     if (!d || !output || !input) return ZERR(kErrGeneric);
@@ -891,6 +1220,7 @@ static size_t ZSTD_decompressStream_impl(ZSTD_DCtx* d, ZSTD_outBuffer* output, Z
     if (input->size > input->pos && !input->src) return ZERR(kErrSrcSizeWrong);
     if (output->size > output->pos && !output->dst) return ZERR(kErrDstBufferNull);
     if (d->pfx) return ZERR(kErrParameterUnsupported);         // (a referenced prefix serves one single call)
+    if (d->segBytes || d->seg.active || d->seg.skip) return stream_segmented(d, output, input);     // (a frame begun in segments ends in segments)
     if (d->hostage && input->pos < input->size) { input->pos++; d->hostage = false; }       // that byte was consumed earlier
     size_t pending = dstream_drain(d, output);
     if (!pending) {
@@ -929,6 +1259,14 @@ static size_t ZSTD_decompressStream_impl(ZSTD_DCtx* d, ZSTD_outBuffer* output, Z
 size_t ZSTDMI_DCtx_setDevice(ZSTD_DCtx* d, int device) { return ctx_set_device(d, device); }
 size_t ZSTDMI_DCtx_setDevices(ZSTD_DCtx* d, const int* devices, int n) { return ctx_set_devices(d, devices, n, ZSTD_createDCtx, ZSTD_freeDCtx); }
 size_t ZSTDMI_DCtx_setStream(ZSTD_DCtx* d, void* st) { return ctx_set_stream(d, st, dctx_bind); }
+size_t ZSTDMI_DCtx_setStreamSegment(ZSTD_DCtx* d, size_t bytes)
+{
+    if (!d) return ZERR(kErrGeneric);
+    d->segBytes = bytes; d->streamSegments = 0; d->streamPeakInput = 0;
+    return 0;
+}
+long long ZSTDMI_debugStreamPeakInput(const ZSTD_DCtx* d) { return d ? d->streamPeakInput : -1; }
+int ZSTDMI_debugStreamSegments(const ZSTD_DCtx* d) { return d ? d->streamSegments : -1; }
 int ZSTDMI_debugLastWalkSerial(const ZSTD_DCtx* d) { return d ? (int)d->lastWalkSerial : -1; }
 size_t ZSTDMI_DCtx_setExecWaves(ZSTD_DCtx* d, unsigned waves) { if (!d || (waves != 0 && waves != 1 && waves != 2 && waves != 4 && waves != 8 && waves != 16)) return ZERR(kErrParameterOutOfBound); d->execWaves = (int)waves; return 0; }
 size_t ZSTDMI_DCtx_setOverlap(ZSTD_DCtx* d, unsigned mode) { if (!d || mode > 2) return ZERR(kErrParameterOutOfBound); d->overlapMode = (int)mode; return 0; }

@@ -14,6 +14,7 @@ class Decompressor(_PrefixHolder):
         self.dctx = self._lib.ZSTD_createDCtx()          # S/Decompressor.cs:12
         if not self.dctx:
             raise MemoryError("ZSTD_createDCtx")
+        self._stream_segment = 0
         if device is not None:
             ensure_zstd_success(self._lib, self._lib.ZSTDMI_DCtx_setDevice(self.dctx, device))
 
@@ -26,6 +27,20 @@ class Decompressor(_PrefixHolder):
         v = ctypes.c_int(0)
         ensure_zstd_success(self._lib, self._lib.ZSTD_DCtx_getParameter(self.dctx, int(parameter), ctypes.byref(v)))
         return v.value
+
+    @property
+    def stream_segment(self) -> int:
+        """ZSTDMI_DCtx_setStreamSegment: the compressed size at which DecompressionStream / ZSTD_decompressStream cut a frame that is
+        still arriving into segments and hand their content out; 0 (the default) = whole frames only."""
+        return self._stream_segment
+
+    @stream_segment.setter
+    def stream_segment(self, nbytes: int):
+        self._ensure_not_disposed()
+        if nbytes < 0:
+            raise ValueError("stream_segment must not be negative")
+        ensure_zstd_success(self._lib, self._lib.ZSTDMI_DCtx_setStreamSegment(self.dctx, int(nbytes)))
+        self._stream_segment = int(nbytes)
 
     def LoadDictionary(self, dict_bytes):                     # S/Decompressor.cs:29-36
         self._ensure_not_disposed()

@@ -90,11 +90,14 @@ class DecompressionStream:
     """S/DecompressionStream.cs:79-112: Read() loops ZSTD_decompressStream, refilling its input buffer from the inner
     stream; end of input with an unfinished frame raises EndOfStreamException("Premature end of stream")."""
 
-    def __init__(self, stream, bufferSize: int = 0, decompressor: Decompressor = None, leaveOpen: bool = True):
+    def __init__(self, stream, bufferSize: int = 0, decompressor: Decompressor = None, leaveOpen: bool = True, segment: int = None):
+        """segment: Decompressor.stream_segment for this stream's decompressor (None = leave it as it is; 0 = whole frames only)."""
         self._lib = _ffi.load()
         self.innerStream = stream
         self._own = decompressor is None
         self.decompressor = decompressor if decompressor is not None else Decompressor()
+        if segment is not None:
+            self.decompressor.stream_segment = segment
         self._inSize = bufferSize if bufferSize > 0 else ensure_zstd_success(self._lib, self._lib.ZSTD_CStreamInSize())          # S/DecompressionStream.cs:41 (the reference asks the C-stream size here)
         self._inBuf = ctypes.create_string_buffer(self._inSize)
         self._input = ZSTD_inBuffer(ctypes.addressof(self._inBuf), 0, 0)
