@@ -314,6 +314,30 @@ size_t ZSTDMI_CCtx_setSeekTable(ZSTD_CCtx* cctx, unsigned mode);
  * ZSTDMI_debugCompressSamples and contexts with several device workers.  Without a dictionary, with a raw-content dictionary, behind
  * ZSTD_CCtx_refPrefix and in ZSTD_compressCCtx the switch changes nothing.  Every zstd decoder holding the dictionary reads the frames. */
 size_t ZSTDMI_CCtx_setDictEntropy(ZSTD_CCtx* cctx, unsigned mode);
+/* One frame per call and per stream session, as the reference writes it (S/Compressor.cs Wrap, S/CompressionStream.cs).  0 = off (the
+ * default: a run of independent frames, every existing output unchanged), 1 = on, any other mode: parameter_outOfBound; NULL context:
+ * GENERIC.  Sticky; the call touches no device.
+ * On, ZSTD_compress2 and ZSTDMI_compressDevice write a source of more than 64 KiB as exactly ONE frame: the blocks of the long-distance
+ * framing for the level (full 64 KiB blocks with far candidates at the fast strategy, 48 / 32 KiB blocks behind LDS history above it)
+ * without its stage, every block but the first behind the input in front of it, also across the passes of ZSTDMI_CCtx_setPassChunks —
+ * the bytes depend on the input and the parameters alone.  Header: with wl = ZSTD_c_windowLog or else the level's windowLog for the
+ * source size, a single segment with the content size when srcSize <= 2^wl, otherwise a window descriptor for 2^wl AND the content
+ * size; ZSTD_c_contentSizeFlag = 0: a window descriptor alone.  Last_Block on the last block only; with ZSTD_c_checksumFlag the XXH64
+ * of the whole content behind it (a serial chain over the input: see README "One frame per call").  Sources of at most 64 KiB, the
+ * empty one included: the bytes of the switch off.  The sparse-input probe is honoured when it finds one kind of data in the whole
+ * call; a mixed input is not cut into ranges and takes the level's own path as a whole.
+ * ZSTD_compressStream2 writes one frame per session: a window descriptor for the level's default windowLog (or ZSTD_c_windowLog), no
+ * content size; ZSTD_e_flush ends a block, ZSTD_e_end sets Last_Block (on an empty block when nothing is buffered) and appends the
+ * checksum.  ZSTDMI_compressBatch: bytes equal to the single call; entries above 64 KiB go through the single-call path.
+ * ZSTD_compressCCtx ignores the switch; behind ZSTD_CCtx_refPrefix, and under long-distance matching when the source fits one of
+ * its frames, the output is one frame already and does not change.
+ * parameter_unsupported at the consuming call, with the context left usable: a source above 2 GiB; ZSTD_c_windowLog 10 .. 17; a seek
+ * table; several device workers; a loaded dictionary (sources above 64 KiB, and every stream session); long-distance matching with a
+ * source of more than one of its frames (and in every stream session).
+ * The trade: one long frame decodes at the long-frame rate (ZSTDMI_DCtx_setLongFrames; this library's decoder walks a frame of 1 GiB
+ * or more in order), not at that of independent frames, cannot be sharded by frame, and its checksum is one serial chain (seconds per
+ * GiB on both sides).  Figures: README "One frame per call". */
+size_t ZSTDMI_CCtx_setSingleFrame(ZSTD_CCtx* cctx, unsigned mode);
 size_t ZSTDMI_seekTableBound(size_t srcSize);
 size_t ZSTDMI_decompressRange(ZSTD_DCtx* dctx, void* dst, size_t dstCapacity, const void* src, size_t srcSize,
                               unsigned long long offset, size_t length);

@@ -71,6 +71,7 @@ class Compressor(_PrefixHolder):
         self._level = 0
         self._seek_table = False
         self._dict_entropy = False
+        self._single_frame = False
         self.Level = level if level else self.DefaultCompressionLevel
 
     # ---- static members (S/Compressor.cs:8-10) ----
@@ -147,6 +148,17 @@ class Compressor(_PrefixHolder):
         self._ensure_not_disposed()
         ensure_zstd_success(self._lib, self._lib.ZSTDMI_CCtx_setDictEntropy(self.cctx, 1 if on else 0))
         self._dict_entropy = bool(on)
+
+    # ---- one frame per Wrap and per stream session (ZSTDMI_CCtx_setSingleFrame), as the reference writes; off by default ----
+    @property
+    def single_frame(self) -> bool:
+        return self._single_frame
+
+    @single_frame.setter
+    def single_frame(self, on):
+        self._ensure_not_disposed()
+        ensure_zstd_success(self._lib, self._lib.ZSTDMI_CCtx_setSingleFrame(self.cctx, 1 if on else 0))
+        self._single_frame = bool(on)
 
     # ---- Wrap (S/Compressor.cs:78-96) ----
     def Wrap(self, src, dest=None, offset: int = 0):

@@ -799,13 +799,16 @@ __device__ __forceinline__ void dense_rest(LzLds& L, const u32 n, const u32 inse
 // TAB: a block's place in its frame comes from a table (chunkFrames: a batch of entries of different lengths).  A template parameter
 // because these kernels sit at the register cap: as a run-time branch the pointer and the select added scratch to the instances
 // every single call of the levels >= 3 runs; without TAB the code is that of a kernel without the table.
-template <int MODE, int SHORT, bool DICT, bool FAR, bool TAB>
+// TAB == 2: the call's input is ONE frame that passes (and a stream's batches) cut anywhere (ZSTDMI_CCtx_setSingleFrame):
+// frameAt = bytes of the frame in front of src, all of them readable there as history; frameTotal = the frame's content size.
+template <int MODE, int SHORT, bool DICT, bool FAR, int TAB>
 __global__ __launch_bounds__(1024) void lz_kernel(const u8* __restrict__ src, u64 srcSize,
                                                   Seq* __restrict__ seqs, u8* __restrict__ lits,
                                                   ChunkMeta* __restrict__ meta,
                                                   const u8* __restrict__ prefixArg, const u32 prefixLenArg, const u32 chunkBytes,
                                                   const u32 fhExtra, const u32 minStrideLog, const u32 frameBlocksArg, u16* __restrict__ candAll, u16* __restrict__ chainAll, u32* __restrict__ regionList, const u32 nChunks,
-                                                  u32* __restrict__ claimCtr, const u32* __restrict__ chunkLens, const u32* __restrict__ chunkFrames)
+                                                  u32* __restrict__ claimCtr, const u32* __restrict__ chunkLens, const u32* __restrict__ chunkFrames,
+                                                  const u64 frameAt, const u64 frameTotal)
 {
     extern __shared__ __attribute__((aligned(16))) u8 ldsRaw[];
     LzLds& L = *reinterpret_cast<LzLds*>(ldsRaw);
@@ -841,10 +844,11 @@ __global__ __launch_bounds__(1024) void lz_kernel(const u8* __restrict__ src, u6
     const bool indep = (frameBlocksArg >> 31) != 0;
     // chunkFrames (optional, beside chunkLens; blocks behind LDS history only): a batch's entries differ in length, so a chunk's place
     // comes from a table instead of the call's size: bits 24-31 the block index inside its frame, bits 0-23 the frame's content size
-    const u32 bf = ((DICT || FAR) && frameBlocks) ? (TAB ? chunkFrames[c] >> 24 : c % frameBlocks) : 0u;               // block index inside its frame
-    const u32 farAvail = FAR ? ((u64)bf * cb < kFarMax ? bf * cb : kFarMax) : 0u;      // bytes of far history in front of the block
+    // (TAB == 2: only whether the block is its frame's first; what lies in front of it is counted in bytes)
+    const u32 bf = ((DICT || FAR) && frameBlocks) ? (TAB == 1 ? chunkFrames[c] >> 24 : TAB == 2 ? (frameAt + base != 0 ? 1u : 0u) : c % frameBlocks) : 0u;               // block index inside its frame
+    const u32 farAvail = FAR ? (TAB == 2 ? (frameAt + base < kFarMax ? (u32)(frameAt + base) : kFarMax) : (u64)bf * cb < kFarMax ? bf * cb : kFarMax) : 0u;      // bytes of far history in front of the block
     u32 prefixLen = prefixLenArg; const u8* __restrict__ prefix = prefixArg;
-    if (DICT && frameBlocks && !indep) { const u64 back = (u64)bf * cb; prefixLen = back < hist ? (u32)back : hist; prefix = in - prefixLen; }
+    if (DICT && frameBlocks && !indep) { const u64 back = TAB == 2 ? frameAt + base : (u64)bf * cb; prefixLen = back < hist ? (u32)back : hist; prefix = in - prefixLen; }
     if (DICT && indep && bf) prefixLen = 0;
     const u32 lowLimit = DICT ? hist - prefixLen : 0u;
     // chunkLens (optional): chunk c holds chunkLens[c] <= cb bytes at c * cb (a batch of independent inputs, each staged at a
@@ -1512,7 +1516,7 @@ __global__ __launch_bounds__(1024) void lz_kernel(const u8* __restrict__ src, u6
         m.srcSize = nData; m.nbSeq = nbSeq; m.litSize = litBase;
         if ((DICT || FAR) && frameBlocks) {   // only a frame's first block carries the frame header, sized for the whole frame's content
             const u64 fStart = base - (u64)bf * cb, fMax = (u64)frameBlocks * cb;
-            const u64 fLen = TAB ? (u64)(chunkFrames[c] & 0xFFFFFFu) : (srcSize - fStart) < fMax ? (srcSize - fStart) : fMax;
+            const u64 fLen = TAB == 1 ? (u64)(chunkFrames[c] & 0xFFFFFFu) : TAB == 2 ? frameTotal : (srcSize - fStart) < fMax ? (srcSize - fStart) : fMax;
             const u32 fcsField = fLen < 256 ? 0u : fLen < 65536 + 256 ? 2u : fLen <= 0xFFFFFFFFull ? 4u : 8u;       // (behind a window descriptor)
             m.fhSize = bf == 0 ? ((fhExtra >> 12) ? 6u + ((fhExtra & 0x100u) ? 0u : fcsField) : (fhExtra & 0x100u) ? 6u : frame_header_size64(fLen)) + (fhExtra & 7u) : 0u;
         } else m.fhSize = ((fhExtra & 0x100u) ? 6u : frame_header_size(nData)) + (fhExtra & 7u);      // fhExtra: bits 0-2 bytes of the dictID field (formatted dictionary); bit 8: window descriptor instead of a content size (magic, descriptor, window byte); bits 12-16: an explicit windowLog (multi-block frames only: descriptor AND content size)
@@ -1531,11 +1535,11 @@ __global__ __launch_bounds__(1024) void lz_kernel(const u8* __restrict__ src, u6
 // tail in front of it, is staged again; the fast finder's table gets the first tile's positions (the latest occurrence per
 // bucket, as the tile loop left it; the first-occurrence table starts empty: it only ever serves the tile that filled it); and
 // the region parse takes the tiles after the first from the state lz_kernel recorded.
-template <int MODE, bool DICT, bool TAB>
+template <int MODE, bool DICT, int TAB>
 __global__ __launch_bounds__(1024) void lz_region_kernel(const u8* __restrict__ src, u64 srcSize, Seq* __restrict__ seqs, u8* __restrict__ lits,
                                                          ChunkMeta* __restrict__ meta, u16* __restrict__ candAll, u16* __restrict__ chainAll, const u32* __restrict__ regionList,
                                                          const u8* __restrict__ prefixArg, const u32 prefixLenArg, const u32 chunkBytes, const u32 frameBlocksArg, const u32 hcDepth,
-                                                         const u32* __restrict__ chunkLens, const u32* __restrict__ chunkFrames)
+                                                         const u32* __restrict__ chunkLens, const u32* __restrict__ chunkFrames, const u64 frameAt)
 {
     const u32 frameBlocks = frameBlocksArg & 0x7FFFFFFFu;
     const bool indep = (frameBlocksArg >> 31) != 0;
@@ -1552,9 +1556,9 @@ __global__ __launch_bounds__(1024) void lz_region_kernel(const u8* __restrict__ 
     const u32 hist = DICT ? kChunkSize - ((chunkBytes + kTilePos - 1) & ~(kTilePos - 1)) : 0u;
     const u64 base = (u64)c * cb;
     const u8* __restrict__ in = src + base;
-    const u32 bf = (DICT && frameBlocks) ? (TAB ? chunkFrames[c] >> 24 : c % frameBlocks) : 0u;
+    const u32 bf = (DICT && frameBlocks) ? (TAB == 1 ? chunkFrames[c] >> 24 : TAB == 2 ? 0u : c % frameBlocks) : 0u;
     u32 prefixLen = prefixLenArg; const u8* __restrict__ prefix = prefixArg;
-    if (DICT && frameBlocks && !indep) { const u64 back = (u64)bf * cb; prefixLen = back < hist ? (u32)back : hist; prefix = in - prefixLen; }
+    if (DICT && frameBlocks && !indep) { const u64 back = TAB == 2 ? frameAt + base : (u64)bf * cb; prefixLen = back < hist ? (u32)back : hist; prefix = in - prefixLen; }
     if (DICT && indep && bf) prefixLen = 0;
     const u32 lowLimit = DICT ? hist - prefixLen : 0u;
     const u32 nData = chunkLens ? chunkLens[c] : (u32)((srcSize - base) < cb ? (srcSize - base) : cb);
@@ -1684,10 +1688,10 @@ extern "C" void ZSTDMI_debugReadLzStamps(unsigned long long* out16, int reset)
 }
 #endif
 
-template <int MODE, int SHORT, bool DICT, bool FAR = false, bool TAB = false>
+template <int MODE, int SHORT, bool DICT, bool FAR = false, int TAB = 0>
 static void launch_one(const u8* src, u64 srcSize, u32 nChunks, Seq* seqs, u8* lits, ChunkMeta* meta, const u8* prefix, u32 prefixLen,
                        u32 chunkBytes, u32 fhExtra, u32 minStrideLog, u32 frameBlocks, u16* cand, u16* chain, u32* regionList, u32 hcDepth, hipStream_t stream, StageHook hook, u32* claimCtr,
-                       const u32* chunkLens, const u32* chunkFrames)
+                       const u32* chunkLens, const u32* chunkFrames, u64 frameAt = 0, u64 frameTotal = 0)
 {
     // the region parse of dense chunks: a second kernel behind a work list (see lz_region_kernel), inlined for the others
     constexpr bool kSplit = (MODE == 0 && !DICT && !FAR) || MODE == 2;
@@ -1708,11 +1712,11 @@ static void launch_one(const u8* src, u64 srcSize, u32 nChunks, Seq* seqs, u8* l
     if (claim) (void)hipMemsetAsync(claimCtr, 0, sizeof(u32), stream);
     const u32 grid = claim ? cuCount[dev & 63] : nChunks;
     hipLaunchKernelGGL((lz_kernel<MODE, SHORT, DICT, FAR, TAB>), dim3(grid), dim3(kTile), sizeof(LzLds), stream, src, srcSize, seqs, lits, meta, prefix, prefixLen, chunkBytes, fhExtra, minStrideLog, frameBlocks, cand, cand ? chain : nullptr, cand ? regionList : nullptr, nChunks,
-                       claim ? claimCtr : nullptr, chunkLens, chunkFrames);
+                       claim ? claimCtr : nullptr, chunkLens, chunkFrames, frameAt, frameTotal);
     hook("lz_fast");
     if constexpr (kSplit) if (cand) {                      // the dense chunks' rest: 256 workgroups (one per CU) walk the list
         hipLaunchKernelGGL((lz_region_kernel<MODE, DICT, TAB>), dim3(nChunks < 256 ? nChunks : 256), dim3(kTile), sizeof(LzLds), stream, src, srcSize, seqs, lits, meta, cand, chain, regionList,
-                           prefix, prefixLen, chunkBytes, frameBlocks, hcDepth, chunkLens, chunkFrames);
+                           prefix, prefixLen, chunkBytes, frameBlocks, hcDepth, chunkLens, chunkFrames, frameAt);
         hook("lz_region");
     }
 }
@@ -1726,8 +1730,19 @@ static void launch_one(const u8* src, u64 srcSize, u32 nChunks, Seq* seqs, u8* l
 // cand / regionList (null: off): workspace of the region parse, 65536 u16 per chunk and 1 + nChunks u32.
 void launch_lz(u32 finder, const u8* src, u64 srcSize, u32 nChunks, Seq* seqs, u8* lits, ChunkMeta* meta, const u8* prefix, u32 prefixLen,
                u32 chunkBytes, u32 fhExtra, u32 minStrideLog, u32 frameBlocks, u16* cand, u16* chain, u32* regionList, u32 hcDepth, hipStream_t stream, StageHook hook, u32* claimCtr,
-               const u32* chunkLens, const u32* chunkFrames)
+               const u32* chunkLens, const u32* chunkFrames, const FramePlace* place)
 {
+    if (place) {
+        // one frame across passes: the long-distance framing's blocks (resolve_framing), each with its place in bytes.  Instances of
+        // their own (TAB == 2), so the kernels of a context without the switch are the ones from before it existed.
+        assert(frameBlocks && !chunkLens && !chunkFrames && !prefixLen && (chunkBytes >= kChunkSize) == (finder == 0));
+        switch (finder) {
+        case 0:  launch_one<0, 5, false, true, 2>(src, srcSize, nChunks, seqs, lits, meta, nullptr, 0, kChunkSize, fhExtra, minStrideLog, frameBlocks, nullptr, nullptr, nullptr, 0, stream, hook, claimCtr, nullptr, nullptr, place->at, place->total); break;
+        case 1:  launch_one<1, 5, true, false, 2>(src, srcSize, nChunks, seqs, lits, meta, nullptr, 0, chunkBytes, fhExtra, minStrideLog, frameBlocks, cand, chain, regionList, hcDepth, stream, hook, claimCtr, nullptr, nullptr, place->at, place->total); break;
+        default: launch_one<2, 5, true, false, 2>(src, srcSize, nChunks, seqs, lits, meta, nullptr, 0, chunkBytes, fhExtra, minStrideLog, frameBlocks, cand, chain, regionList, hcDepth, stream, hook, claimCtr, nullptr, nullptr, place->at, place->total); break;
+        }
+        return;
+    }
     // (the table form exists for blocks behind LDS history only: the full-64-KiB-block instances below take no chunkFrames, while
     //  seq_encode and xxh64 would still follow it)
     assert(!chunkFrames || (chunkBytes < kChunkSize && frameBlocks && chunkLens));
@@ -1744,13 +1759,13 @@ void launch_lz(u32 finder, const u8* src, u64 srcSize, u32 nChunks, Seq* seqs, u
         return;
     }
     switch (finder) {
-    case 0:  if (chunkFrames) launch_one<0, 5, true, false, true>(src, srcSize, nChunks, seqs, lits, meta, prefix, prefixLen, chunkBytes, fhExtra, minStrideLog, frameBlocks, cand, chain, regionList, hcDepth, stream, hook, claimCtr, chunkLens, chunkFrames);
+    case 0:  if (chunkFrames) launch_one<0, 5, true, false, 1>(src, srcSize, nChunks, seqs, lits, meta, prefix, prefixLen, chunkBytes, fhExtra, minStrideLog, frameBlocks, cand, chain, regionList, hcDepth, stream, hook, claimCtr, chunkLens, chunkFrames);
              else launch_one<0, 5, true>(src, srcSize, nChunks, seqs, lits, meta, prefix, prefixLen, chunkBytes, fhExtra, minStrideLog, frameBlocks, cand, chain, regionList, hcDepth, stream, hook, claimCtr, chunkLens, nullptr);
              break;
-    case 1:  if (chunkFrames) launch_one<1, 5, true, false, true>(src, srcSize, nChunks, seqs, lits, meta, prefix, prefixLen, chunkBytes, fhExtra, minStrideLog, frameBlocks, cand, chain, regionList, hcDepth, stream, hook, claimCtr, chunkLens, chunkFrames);
+    case 1:  if (chunkFrames) launch_one<1, 5, true, false, 1>(src, srcSize, nChunks, seqs, lits, meta, prefix, prefixLen, chunkBytes, fhExtra, minStrideLog, frameBlocks, cand, chain, regionList, hcDepth, stream, hook, claimCtr, chunkLens, chunkFrames);
              else launch_one<1, 5, true>(src, srcSize, nChunks, seqs, lits, meta, prefix, prefixLen, chunkBytes, fhExtra, minStrideLog, frameBlocks, cand, chain, regionList, hcDepth, stream, hook, claimCtr, chunkLens, nullptr);
              break;
-    default: if (chunkFrames) launch_one<2, 5, true, false, true>(src, srcSize, nChunks, seqs, lits, meta, prefix, prefixLen, chunkBytes, fhExtra, minStrideLog, frameBlocks, cand, chain, regionList, hcDepth, stream, hook, claimCtr, chunkLens, chunkFrames);
+    default: if (chunkFrames) launch_one<2, 5, true, false, 1>(src, srcSize, nChunks, seqs, lits, meta, prefix, prefixLen, chunkBytes, fhExtra, minStrideLog, frameBlocks, cand, chain, regionList, hcDepth, stream, hook, claimCtr, chunkLens, chunkFrames);
              else launch_one<2, 5, true>(src, srcSize, nChunks, seqs, lits, meta, prefix, prefixLen, chunkBytes, fhExtra, minStrideLog, frameBlocks, cand, chain, regionList, hcDepth, stream, hook, claimCtr, chunkLens, nullptr);
              break;
     }

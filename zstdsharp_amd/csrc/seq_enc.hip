@@ -117,12 +117,15 @@ __device__ __forceinline__ u32 build_seq_table(SeqWaveLds& W, u8* op, u32* count
 
 // DICT (ZSTDMI_CCtx_setDictEntropy with a formatted dictionary): a frame's first block may take the dictionary's LL / OF / ML tables
 // as they are (mode 3, build_seq_table); the instance without DICT is the code from before the switch existed.
-template <bool DICT>
+// SF (ZSTDMI_CCtx_setSingleFrame): the call's input is ONE frame cut anywhere by passes and stream batches; frameAt = bytes of the
+// frame in front of chunk 0, frameTotal = the frame's content size (~0: not known yet, the frame goes on behind this pass).
+template <bool DICT, bool SF>
 __global__ __launch_bounds__(256) void seq_encode_kernel(Seq* __restrict__ seqs, ChunkMeta* __restrict__ meta,
                                                          u8* __restrict__ slots, u32 nChunks, u32 strategy, u32 checksumFlag, u32 resolveReps,
                                                          u32 dictID, u32 dictIdBytes, u32 initRep0, u32 initRep1, u32 initRep2,
                                                          const u32 frameBlocks, const u32 chunkBytes, const u64 srcSize,
-                                                         const DictCTables* __restrict__ dct, const u32* __restrict__ chunkFrames)
+                                                         const DictCTables* __restrict__ dct, const u32* __restrict__ chunkFrames,
+                                                         const u64 frameAt, const u64 frameTotal)
 {
     __shared__ SeqWaveLds Ws[4];
     __shared__ u32 sBatchSeq[4];          // sequences each of the four chunks sends through the state chains (0: none)
@@ -142,9 +145,13 @@ __global__ __launch_bounds__(256) void seq_encode_kernel(Seq* __restrict__ seqs,
     // chunkFrames (optional): a batch of entries of different lengths: the block index (bits 24-31) and the frame's content size
     // (bits 0-23) per chunk from a table, as in lz_kernel
     const u32 place = (frameBlocks && chunkFrames && live) ? chunkFrames[c] : 0u;
-    const u32 bf = frameBlocks ? (chunkFrames ? place >> 24 : c % frameBlocks) : 0u;
+    const u32 bf = SF ? (frameAt + (u64)c * chunkBytes != 0 ? 1u : 0u) : frameBlocks ? (chunkFrames ? place >> 24 : c % frameBlocks) : 0u;   // (SF: first block or not)
     u64 frameLen = n; bool lastBlock = true;
-    if (frameBlocks) {
+    if (SF) {
+        frameLen = frameTotal;
+        lastBlock = frameAt + (u64)(c + 1) * chunkBytes >= frameTotal;
+        if (bf) { initRep0 = 0; initRep1 = 0; initRep2 = 0; }
+    } else if (frameBlocks) {
         const u64 fStart = (u64)(c - bf) * chunkBytes, fMax = (u64)frameBlocks * chunkBytes;
         frameLen = chunkFrames ? (u64)(place & 0xFFFFFFu) : (srcSize - fStart) < fMax ? (srcSize - fStart) : fMax;
         lastBlock = (u64)(bf + 1) * chunkBytes >= frameLen;
@@ -452,12 +459,18 @@ __global__ __launch_bounds__(256) void seq_encode_kernel(Seq* __restrict__ seqs,
 
 void launch_seq_encode(Seq* seqs, ChunkMeta* meta, u8* slots, u32 nChunks, u32 strategy, u32 checksumFlag, u32 resolveReps,
                        u32 dictID, u32 dictIdBytes, const u32* initReps, u32 frameBlocks, u32 chunkBytes, u64 srcSize, hipStream_t stream,
-                       const DictCTables* dct, const u32* chunkFrames)
+                       const DictCTables* dct, const u32* chunkFrames, const FramePlace* place)
 {
-    if (dct) hipLaunchKernelGGL(seq_encode_kernel<true>, dim3((nChunks + 3) / 4), dim3(256), 0, stream, seqs, meta, slots, nChunks, strategy, checksumFlag, resolveReps,
-                                dictID, dictIdBytes, initReps[0], initReps[1], initReps[2], frameBlocks, chunkBytes, srcSize, dct, chunkFrames);
-    else hipLaunchKernelGGL(seq_encode_kernel<false>, dim3((nChunks + 3) / 4), dim3(256), 0, stream, seqs, meta, slots, nChunks, strategy, checksumFlag, resolveReps,
-                            dictID, dictIdBytes, initReps[0], initReps[1], initReps[2], frameBlocks, chunkBytes, srcSize, dct, chunkFrames);
+    if (place) {
+        assert(!dct && !chunkFrames);
+        hipLaunchKernelGGL((seq_encode_kernel<false, true>), dim3((nChunks + 3) / 4), dim3(256), 0, stream, seqs, meta, slots, nChunks, strategy, checksumFlag, resolveReps,
+                           dictID, dictIdBytes, initReps[0], initReps[1], initReps[2], frameBlocks, chunkBytes, srcSize, dct, chunkFrames, place->at, place->total);
+        return;
+    }
+    if (dct) hipLaunchKernelGGL((seq_encode_kernel<true, false>), dim3((nChunks + 3) / 4), dim3(256), 0, stream, seqs, meta, slots, nChunks, strategy, checksumFlag, resolveReps,
+                                dictID, dictIdBytes, initReps[0], initReps[1], initReps[2], frameBlocks, chunkBytes, srcSize, dct, chunkFrames, (u64)0, (u64)0);
+    else hipLaunchKernelGGL((seq_encode_kernel<false, false>), dim3((nChunks + 3) / 4), dim3(256), 0, stream, seqs, meta, slots, nChunks, strategy, checksumFlag, resolveReps,
+                            dictID, dictIdBytes, initReps[0], initReps[1], initReps[2], frameBlocks, chunkBytes, srcSize, dct, chunkFrames, (u64)0, (u64)0);
 }
 
 #ifdef ZMI_LZ_STAMPS

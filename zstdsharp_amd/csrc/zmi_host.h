@@ -16,10 +16,13 @@ namespace zmi {
 // kernels (lz_fast.hip, huf_enc.hip, seq_enc.hip, frame.hip, decode.hip)
 // chunkLens / chunkFrames (a batch of entries, each staged at a chunk boundary): per chunk its length, and — multi-block frames behind
 // LDS history only — its place: chunk_frame_word(block index inside its frame, the frame's content size)
+// place (ZSTDMI_CCtx_setSingleFrame): the call's input is ONE frame that passes and stream batches cut anywhere: `at` = bytes of the frame in
+// front of src (readable there, as far as the finders reach back), `total` = the frame's content size (~0: the frame goes on behind this pass)
+struct FramePlace { u64 at, total; };
 inline u32 chunk_frame_word(u32 blockInFrame, u32 frameLen) { assert(blockInFrame < 256 && frameLen < (1u << 24)); return (blockInFrame << 24) | frameLen; }
 void launch_lz(u32 finder, const u8* src, u64 srcSize, u32 nChunks, Seq* seqs, u8* lits, ChunkMeta* meta, const u8* prefix, u32 prefixLen,
                u32 chunkBytes, u32 fhExtra, u32 minStrideLog, u32 frameBlocks, u16* cand, u16* chain, u32* regionList, u32 hcDepth, hipStream_t stream, StageHook hook, u32* claimCtr,
-               const u32* chunkLens = nullptr, const u32* chunkFrames = nullptr);
+               const u32* chunkLens = nullptr, const u32* chunkFrames = nullptr, const FramePlace* place = nullptr);
 void launch_lz_probe(const u8* src, u64 srcSize, u64 front, u64 groupBytes, u32 nGroups, u32 tilesPerGroup, u32* out, hipStream_t stream);
 void launch_huf_build(const u8* lits, ChunkMeta* meta, HufTable* tables, u8* slots, u32 nChunks, u32 rawLiterals, const u8* src, u32 chunkBytes,
                       hipStream_t stream, StageHook hook, const DictCTables* dct = nullptr, u32 frameBlocks = 0);
@@ -27,7 +30,7 @@ void launch_huf_encode(const u8* lits, const ChunkMeta* meta, const HufTable* ta
                        u32 nChunks, const u8* src, u32 chunkBytes, hipStream_t stream, bool dictEntropy = false);
 void launch_seq_encode(Seq* seqs, ChunkMeta* meta, u8* slots, u32 nChunks, u32 strategy, u32 checksumFlag, u32 resolveReps,
                        u32 dictID, u32 dictIdBytes, const u32* initReps, u32 frameBlocks, u32 chunkBytes, u64 srcSize, hipStream_t stream,
-                       const DictCTables* dct = nullptr, const u32* chunkFrames = nullptr);
+                       const DictCTables* dct = nullptr, const u32* chunkFrames = nullptr, const FramePlace* place = nullptr);
 void launch_scan_sizes(const ChunkMeta* meta, u32 nChunks, u64* offsets, u64* total, hipStream_t stream);
 void launch_gather(const u8* src, u64 srcSize, const u8* slots, const ChunkMeta* meta, const u64* offsets, u8* dst, u64 dstCapacity,
                    u32 nChunks, u32 chunkBytes, hipStream_t stream);
@@ -82,7 +85,16 @@ void launch_place_literals(const u8* src, u8* out, const u8* scratch, const Fram
                            const SeqRec* recs, const u32* status, hipStream_t stream);
 // a segmented stream's carried state (decode_stream.hip)
 void launch_stream_carry(const BlockDesc* blocks, u32 nBlocks, DictInfo* reps, hipStream_t stream);
+// XXH64 with carried state (frame.hip): the decoder's segmented streams and the compressor's single frame across passes and batches.
+// xxh_carry_reset: the state of an empty input (host).  launch_xxh_carry_file: the finished hash into the chunk that carries the checksum.
 void launch_stream_xxh(XxhCarry* st, const u8* data, u64 n, u32 final, hipStream_t stream);
+void launch_xxh_carry_file(const XxhCarry* st, ChunkMeta* chunk, hipStream_t stream);
+inline void xxh_carry_reset(XxhCarry* x)
+{
+    const u64 P1 = 0x9E3779B185EBCA87ULL, P2 = 0xC2B2AE3D27D4EB4FULL;
+    memset(x, 0, sizeof *x);
+    x->acc[0] = P1 + P2; x->acc[1] = P2; x->acc[2] = 0; x->acc[3] = 0 - P1;
+}
 void launch_exec_matches(const u8* src, u8* out, const FrameDesc* frames, const BlockDesc* blocks, u32 nFrames, const SeqRec* recs, u32* status,
                          const u8* dict, u32 dictSize, hipStream_t stream, int wide);
 void launch_origin_select(FrameDesc* frames, u32 nFrames, u64 minBytes, u32* list, u32 listCap, u64 originCap, u32* status, hipStream_t stream);

@@ -52,6 +52,11 @@ struct ZSTD_CCtx_s {
     // ZSTD_CCtx_refPrefix: the caller's bytes (host or device), referenced until the next ZSTD_compress2 / ZSTDMI_compressDevice has
     // consumed them; a host prefix of the long form is staged into pfxStage inside that call
     const void* pfx = nullptr; size_t pfxSize = 0; DevBuf pfxStage;
+    // ZSTDMI_CCtx_setSingleFrame (sticky): a call of more than 64 KiB, and a stream session, is ONE frame.  sfXxh: the content checksum's
+    // state, carried from pass to pass and from batch to batch (frame.hip); a session keeps what the switch was when it began
+    // (sSingle; and the checksum flag, which its header states), the bytes it has put into its frame (sTotal) and the last kStreamTail of them as the next batch's history (sTail)
+    int singleFrame = 0; DevBuf sfXxh; XxhCarry sfXxhHost = {};
+    bool sSingle = false; int sChecksum = 0; u64 sTotal = 0; std::vector<u8> sTail;     // (sChecksum: the flag the session's header states)
 };
 // History per chunk lives in LDS beside the chunk: up to 32 KiB of dictionary in front of 32 KiB chunks, or up to 60 KiB when
 // the whole input fits behind it in one chunk (small records, the usual dictionary case).
@@ -83,6 +88,10 @@ struct CallParams {
     bool seek = false;                  // append a seek table (ZSTDMI_CCtx_setSeekTable; ZSTD_compressCCtx: never, as it never runs LDM)
     bool dictEntropy = false;           // code with a formatted dictionary's entropy tables (ZSTDMI_CCtx_setDictEntropy; ZSTD_compressCCtx uses no dictionary)
     const u8* pfx = nullptr; size_t pfxSize = 0;    // the long form of a referenced prefix (compress_prefixed): device bytes in front of the ONE frame
+    bool single = false;                // one frame per call (ZSTDMI_CCtx_setSingleFrame; ZSTD_compressCCtx: never, level-only parameters)
+    // a batch of a single-frame stream session (cstream_compress_single): streamAt bytes of the frame lie in front of it (the last
+    // kStreamTail of them readable in front of the source), and the batch ends the frame or not
+    bool stream = false, streamEnd = false; u64 streamAt = 0;
 };
 static CallParams sticky_params(const ZSTD_CCtx* c)
 {
@@ -90,6 +99,7 @@ static CallParams sticky_params(const ZSTD_CCtx* c)
     p.strategy = c->strategy; p.targetLength = c->targetLength; p.windowLog = c->windowLog; p.searchLog = c->searchLog; p.minMatch = c->minMatch; p.chainLog = c->chainLog; p.useDict = true;
     p.seek = c->seekTable != 0;
     p.dictEntropy = c->dictEntropy != 0;
+    p.single = c->singleFrame != 0;
     p.ldm = c->ldm; p.ldmHashLog = c->ldmHashLog; p.ldmMinMatch = c->ldmMinMatch; p.ldmBucketSizeLog = c->ldmBucketSizeLog; p.ldmHashRateLog = c->ldmHashRateLog;
     return p;
 }
@@ -172,6 +182,8 @@ static const DictCTables* call_dict_ctables(const ZSTD_CCtx* c, const CallParams
 // bytes of dictionary in front of every chunk, bytes per block, blocks per frame (0 = every block a frame of its own), and what
 // the level resolves to for it.
 struct Framing { u32 prefixLen, chunkBytes, frameBlocks; Resolved rs; u32 indepWindowLog = 0; bool ldm = false; LdmLaunch ldmP = {};
+                 bool single = false; u32 singleWindowLog = 0;      // ONE frame across passes; the window its header declares beside (or instead of) the content size, 0 = a single segment
+
                  size_t span() const { return (size_t)chunkBytes * (frameBlocks ? frameBlocks : 1u); } };
 
 // Long-distance matching (ZSTD_c_enableLongDistanceMatching = ZSTD_ps_enable): on for a call of more than one block whose window is
@@ -204,8 +216,33 @@ static LdmLaunch ldm_resolve(const CallParams& cp, size_t paramSize)
     return p;
 }
 
+// ZSTDMI_CCtx_setSingleFrame: a call of more than one 64 KiB block, and every batch of a stream session, is (part of) ONE frame.
+// A stream does not know its size: its parameters are those of the levels' default tier.
+constexpr size_t kStreamParamSize = (size_t)1 << 30;
+constexpr size_t kStreamTail = (size_t)256 << 10;       // history in front of a batch: more than any finder reaches back (lz_fast.hip: 64 KiB + kFarMax)
+constexpr u64 kSingleMax = (u64)2 << 30;
+static bool single_active(const CallParams& cp, size_t paramSize) { return cp.single && !cp.pfxSize && (cp.stream || (paramSize > kChunkSize && !ldm_active(cp, paramSize))); }
+
 static Framing resolve_framing(const ZSTD_CCtx* c, const CallParams& cp, size_t paramSize)
 {
+    if (single_active(cp, paramSize)) {
+        // The blocks are the long-distance framing's (below) without its stage: full 64 KiB blocks with far candidates at the fast
+        // strategy, 64 KiB - 16/32 KiB blocks behind LDS history above it; every block but the first sees the input in front of it,
+        // wherever a pass or a batch begins (FramePlace).  The header is the reference's: with wl = ZSTD_c_windowLog, or the level's
+        // windowLog for this size, a single segment when the content fits 2^wl, else a window descriptor for 2^wl beside the content
+        // size (no finder reaches 2^18 back, and a wl below 18 was refused: check_single_frame).
+        Framing f; f.prefixLen = 0; f.single = true;
+        const Resolved rf = resolve_call(cp, paramSize, (u32)1 << 31);
+        u32 chunkBytes = kChunkSize;
+        if (rf.finder != 0) {
+            const int hb = c->historyBytes > 0 ? c->historyBytes : (rf.cp.strategy == kStratDfast ? (16 << 10) : (32 << 10));
+            chunkBytes = kChunkSize - (round_tile((size_t)hb) > (48u << 10) ? (48u << 10) : round_tile((size_t)hb));
+        }
+        const u32 wl = cp.windowLog ? (u32)cp.windowLog : rf.cp.windowLog;
+        f.singleWindowLog = (cp.stream || (u64)paramSize > ((u64)1 << wl)) ? wl : 0u;
+        f.chunkBytes = chunkBytes; f.frameBlocks = 0x7FFFFFFFu; f.rs = rf;      // (frameBlocks: "blocks share a frame"; a block's place comes from FramePlace)
+        return f;
+    }
     if (cp.pfxSize || ldm_active(cp, paramSize)) {
         // Under LDM a frame is a window: min(2^windowLog, 512 MiB, the pass) of content (ldm.hip matches never leave their frame, so
         // no offset exceeds what the frame declares).  Blocks and history are those the level's windowLog > 16 path picks: full
@@ -327,8 +364,19 @@ static size_t compress_range(ZSTD_CCtx* c, const CallParams& cp, u8* d_dst, size
     const LaunchState ls = launch_state(c, cp, fr);
     const u32 lzFrameBlocks = ls.lzFrameBlocks, hcDepth = ls.hcDepth, strategy = ls.strategy;
     const bool regionParse = ls.regionParse, hcChains = ls.hcChains;
-    const u32 hdrWindow = fr.indepWindowLog;
+    const u32 hdrWindow = fr.single ? fr.singleWindowLog : fr.indepWindowLog;
     const Resolved rs = fr.rs;
+    // one frame: where this range lies in it (a one-shot call IS the frame; a stream's batch continues it) and how long it is;
+    // a stream's header never carries a content size
+    const u64 sfAt = cp.stream ? cp.streamAt : 0u, sfTotal = cp.stream ? (cp.streamEnd ? cp.streamAt + srcSize : ~(u64)0) : (u64)srcSize;
+    const bool withSize = cp.contentSizeFlag && !cp.stream;
+    if (fr.single && cp.checksumFlag) {
+        if (!c->sfXxh.ensure(sizeof(XxhCarry))) return ZERR(kErrMemoryAllocation);
+        if (sfAt == 0) {
+            xxh_carry_reset(&c->sfXxhHost);
+            if (hipMemcpyAsync(c->sfXxh.p, &c->sfXxhHost, sizeof(XxhCarry), hipMemcpyHostToDevice, s) != hipSuccess) return ZERR(kErrGeneric);
+        }
+    }
     // a formatted dictionary: its dictID in every frame header (unless ZSTD_c_dictIDFlag = 0), its repcodes in front of every frame
     const bool fmtDict = cp.useDict && c->dictFormatted;
     const u32 dictID = fmtDict ? c->info.dictID : 0u;
@@ -340,7 +388,7 @@ static size_t compress_range(ZSTD_CCtx* c, const CallParams& cp, u8* d_dst, size
     const u64 totalChunks = (srcSize + chunkBytes - 1) / chunkBytes;
     u32 passChunks = (u32)(totalChunks < c->passChunks ? totalChunks : c->passChunks);
     if (fr.ldm) { const u32 most = (u32)(((u64)1 << 31) / chunkBytes) / frameBlocks * frameBlocks; if (passChunks > most) passChunks = most; }    // (ldm.hip: u32 offsets in a pass)
-    if (frameBlocks && passChunks < totalChunks) { passChunks -= passChunks % frameBlocks; if (!passChunks) passChunks = frameBlocks; }     // frames never straddle passes
+    if (frameBlocks && !fr.single && passChunks < totalChunks) { passChunks -= passChunks % frameBlocks; if (!passChunks) passChunks = frameBlocks; }     // frames never straddle passes
     if (!cctx_workspace(c, passChunks)) return ZERR(kErrMemoryAllocation);
     if (regionParse && !cctx_cand_workspace(c, passChunks, hcChains)) return ZERR(kErrMemoryAllocation);
     size_t produced = 0;
@@ -350,9 +398,12 @@ static size_t compress_range(ZSTD_CCtx* c, const CallParams& cp, u8* d_dst, size
         const u64 n = (srcSize - c0 * chunkBytes) < (u64)nChunks * chunkBytes ? (srcSize - c0 * chunkBytes) : (u64)nChunks * chunkBytes;
         Seq* seqs = (Seq*)c->seqs.p; u8* lits = (u8*)c->lits.p; ChunkMeta* meta = (ChunkMeta*)c->meta.p;
         HufTable* tables = (HufTable*)c->tables.p; u8* slots = (u8*)c->slots.p; u64* offsets = (u64*)c->offsets.p; u64* total = (u64*)c->total.p;
+        // (one frame: the pass's first block lies place.at bytes into it; everything the kernels knew from a chunk's index in the pass comes from there)
+        const FramePlace place = { sfAt + c0 * chunkBytes, sfTotal };
+        const FramePlace* const pl = fr.single ? &place : nullptr;
         c->timer.begin(s);
-        launch_lz(rs.finder, src, n, nChunks, seqs, lits, meta, prefix, prefixLen, chunkBytes, dictIdBytes | (cp.contentSizeFlag ? 0u : 0x100u) | (hdrWindow << 12), rs.minStrideLog, lzFrameBlocks, regionParse ? (u16*)c->cand.p : nullptr, hcChains ? (u16*)((u8*)c->cand.p + cand_plane_bytes(passChunks)) : nullptr,
-                  regionParse ? (u32*)((u8*)c->cand.p + cand_plane_bytes(passChunks) * (hcChains ? 2 : 1)) : nullptr, hcDepth, s, c->timer.hook(), (u32*)(total + 4));      // (the claim counter: a word of `total`'s 64 bytes)
+        launch_lz(rs.finder, src, n, nChunks, seqs, lits, meta, prefix, prefixLen, chunkBytes, dictIdBytes | (withSize ? 0u : 0x100u) | (hdrWindow << 12), rs.minStrideLog, lzFrameBlocks, regionParse ? (u16*)c->cand.p : nullptr, hcChains ? (u16*)((u8*)c->cand.p + cand_plane_bytes(passChunks)) : nullptr,
+                  regionParse ? (u32*)((u8*)c->cand.p + cand_plane_bytes(passChunks) * (hcChains ? 2 : 1)) : nullptr, hcDepth, s, c->timer.hook(), (u32*)(total + 4), nullptr, nullptr, pl);      // (the claim counter: a word of `total`'s 64 bytes)
         if (fr.ldm) {       // long-distance matches into the finder's sequence store (ldm.hip); the splits are counted first to size the workspace
             const u64 span = (u64)frameBlocks * chunkBytes;
             // a referenced prefix: splits over prefix and source as one window in the virtual coordinate (ldm.hip), nL = its end
@@ -370,8 +421,15 @@ static size_t compress_range(ZSTD_CCtx* c, const CallParams& cp, u8* d_dst, size
             }
         }
         launch_huf_build(lits, meta, tables, slots, nChunks, rs.rawLiterals, src, chunkBytes, s, c->timer.hook(), dct, frameBlocks);
-        if (cp.checksumFlag) { launch_xxh64(src, n, meta, nChunks, chunkBytes, frameBlocks, s);             c->timer.mark("xxh64", s); }
-        launch_seq_encode(seqs, meta, slots, nChunks, strategy, (cp.checksumFlag ? 1u : 0u) | (cp.contentSizeFlag ? 0u : 2u) | (hdrWindow << 8), 1, dictID, dictIdBytes, initReps, frameBlocks, chunkBytes, n, s, dct);   c->timer.mark("seq_encode", s);
+        if (cp.checksumFlag && fr.single) {
+            // XXH64 does not merge: the whole content is one serial chain, carried from pass to pass (and from batch to batch); the
+            // pass that ends the frame files the hash with its last block
+            const bool ends = place.at + n == sfTotal;
+            launch_stream_xxh((XxhCarry*)c->sfXxh.p, src, n, ends ? 1u : 0u, s);
+            if (ends) launch_xxh_carry_file((const XxhCarry*)c->sfXxh.p, meta + (nChunks - 1), s);
+            c->timer.mark("xxh64", s);
+        } else if (cp.checksumFlag) { launch_xxh64(src, n, meta, nChunks, chunkBytes, frameBlocks, s);             c->timer.mark("xxh64", s); }
+        launch_seq_encode(seqs, meta, slots, nChunks, strategy, (cp.checksumFlag ? 1u : 0u) | (withSize ? 0u : 2u) | (hdrWindow << 8), 1, dictID, dictIdBytes, initReps, frameBlocks, chunkBytes, n, s, dct, nullptr, pl);   c->timer.mark("seq_encode", s);
         launch_scan_sizes(meta, nChunks, offsets, total, s);                       c->timer.mark("scan", s);
         if (c->seekOn) {        // the pass's frames into the call's seek table
             const u32 nFrames = (nChunks + (frameBlocks ? frameBlocks : 1u) - 1) / (frameBlocks ? frameBlocks : 1u);
@@ -425,7 +483,8 @@ static size_t probe_group_bytes(ZSTD_CCtx* c, const CallParams& cp, size_t srcSi
     if (cp.useDict) { err = cctx_sync_dictionary(c); if (isErr(err)) return 0; err = 0; }
     if (cp.useDict && dict_prefix_len(c, srcSize)) return 0;
     if (resolve_call(cp, srcSize, kChunkSize).cp.strategy <= kStratFast) return 0;
-    const Framing fr = resolve_framing(c, cp, srcSize);
+    CallParams framed = cp; framed.single = false;      // (one frame or not, the probe looks at the groups it looks at today)
+    const Framing fr = resolve_framing(c, framed, srcSize);
     return (size_t)16 * (fr.frameBlocks ? fr.span() : (size_t)kChunkSize * 4);      // a multiple of 64 KiB
 }
 // counts of the groups of [d_src, d_src + len); `front` = bytes of the input readable in front of d_src (a worker's share of a call)
@@ -465,6 +524,20 @@ static void plan_ranges(const std::vector<u32>& counts, size_t group, size_t src
 static size_t check_ldm_dict(const ZSTD_CCtx* c, const CallParams& cp, size_t srcSize)
 {
     if (ldm_active(cp, srcSize) && cp.useDict && (c->dictFormatted || c->dictHost.size() >= 8)) return ZERR(kErrParameterUnsupported);
+    return 0;
+}
+// ZSTDMI_CCtx_setSingleFrame with what one frame across passes cannot be: refused at the call, before a byte is read.  (Calls of at
+// most 64 KiB are one frame with or without the switch, and a referenced prefix writes one frame anyway: nothing to refuse.)
+static size_t check_single_frame(const ZSTD_CCtx* c, const CallParams& cp, size_t srcSize)
+{
+    if (!cp.single || cp.pfxSize || (!cp.stream && srcSize <= kChunkSize)) return 0;
+    if ((u64)srcSize > kSingleMax) return ZERR(kErrParameterUnsupported);
+    if (cp.seek || c->workers.size() > 1) return ZERR(kErrParameterUnsupported);       // (frames are the seek table's and the workers' unit)
+    if (cp.windowLog >= 10 && cp.windowLog < 18) return ZERR(kErrParameterUnsupported); // (the finders reach up to 2^18 back)
+    if (cp.useDict && (c->dictFormatted || c->dictHost.size() >= 8)) return ZERR(kErrParameterUnsupported);   // (a dictionary's framing: a prefix in front of independent blocks)
+    if (cp.stream ? cp.ldm == 1 : ldm_active(cp, srcSize)) {       // one LDM frame is one frame already (bytes unchanged); more than one is not
+        if (cp.stream || srcSize > resolve_framing(c, cp, srcSize).span()) return ZERR(kErrParameterUnsupported);
+    }
     return 0;
 }
 static size_t check_call_params(const CallParams& cp)
@@ -559,6 +632,7 @@ static size_t compress_frames(ZSTD_CCtx* c, const CallParams& cp, u8* d_dst, siz
     bool first = true;
     { const size_t e = check_call_params(cp); if (isErr(e)) return e; }
     { const size_t e = check_ldm_dict(c, cp, srcSize); if (isErr(e)) return e; }
+    { const size_t e = check_single_frame(c, cp, srcSize); if (isErr(e)) return e; }
     size_t err = 0;
     const size_t group = probe_group_bytes(c, cp, srcSize, err);
     if (isErr(err)) return err;
@@ -568,6 +642,9 @@ static size_t compress_frames(ZSTD_CCtx* c, const CallParams& cp, u8* d_dst, siz
     std::vector<PlanRange> plan;
     plan_ranges(counts, group, srcSize, plan);
     if (plan.size() == 1) { CallParams one = cp; if (plan[0].sparse) one.level = 1; return compress_range(c, one, d_dst, dstCapacity, d_src, srcSize, srcSize, first); }
+    // one frame is not cut into ranges: a mixed input takes the level's own path as a whole (its stretches without matches cost the
+    // level's finder instead of level 1's)
+    if (single_active(cp, srcSize)) return compress_range(c, cp, d_dst, dstCapacity, d_src, srcSize, srcSize, first);
     return compress_plan(c, cp, plan, srcSize, d_dst, dstCapacity, d_src, first);
 }
 
@@ -617,7 +694,7 @@ size_t ZSTD_freeCCtx(ZSTD_CCtx* c)
         (void)hipSetDevice(c->device);
         if (c->ownStream) (void)hipStreamSynchronize(c->ownStream);
         c->seqs.release(); c->lits.release(); c->meta.release(); c->tables.release(); c->slots.release(); c->cand.release(); c->probe.release();
-        c->gatherIn.release(); c->gatherOut.release(); c->batchStage.release(); c->batchTab.release(); c->ldmSmall.release(); c->ldmBig.release(); c->offsets.release(); c->total.release(); c->seekEntries.release(); c->seekSort.release(); c->stageSrc.release(); c->stageDst.release(); c->pfxStage.release(); c->dict.release(); c->dictFullDev.release(); c->dictInfoDev.release(); c->dictCTabDev.release();
+        c->gatherIn.release(); c->gatherOut.release(); c->batchStage.release(); c->batchTab.release(); c->ldmSmall.release(); c->ldmBig.release(); c->offsets.release(); c->total.release(); c->seekEntries.release(); c->seekSort.release(); c->stageSrc.release(); c->stageDst.release(); c->pfxStage.release(); c->sfXxh.release(); c->dict.release(); c->dictFullDev.release(); c->dictInfoDev.release(); c->dictCTabDev.release();
         c->timer.destroy();
         if (c->ownStream) (void)hipStreamDestroy(c->ownStream);
     }
@@ -761,6 +838,7 @@ static size_t ZSTDMI_compressDevice_impl(ZSTD_CCtx* c, void* d_dst, size_t dstCa
     if (!d_dst && dstCapacity) return ZERR(kErrDstBufferNull);
     if (!d_dst) return ZERR(kErrDstSizeTooSmall);
     if (c->workers.size() > 1 && c->seekTable) return ZERR(kErrParameterUnsupported);       // (the workers' shares have no common table)
+    { const size_t e2 = check_single_frame(c, sticky_params(c), srcSize); if (isErr(e2)) return e2; }
     if (c->workers.size() > 1 && srcSize) return compress_multi(c, sticky_params(c), d_dst, dstCapacity, d_src, srcSize);
     return compress_device(c, sticky_params(c), (u8*)d_dst, dstCapacity, (const u8*)d_src, srcSize);
 }
@@ -771,6 +849,7 @@ static size_t compress_any(ZSTD_CCtx* c, const CallParams& cp, void* dst, size_t
     if (srcSize && !src) return ZERR(kErrSrcSizeWrong);
     if (!dst) return ZERR(kErrDstSizeTooSmall);
     if (c->workers.size() > 1 && cp.seek) return ZERR(kErrParameterUnsupported);
+    { const size_t e2 = check_single_frame(c, cp, srcSize); if (isErr(e2)) return e2; }
     if (c->workers.size() > 1 && srcSize) return compress_multi(c, cp, dst, dstCapacity, src, srcSize);
     const bool srcDev = srcSize ? is_device_ptr(src) : true, dstDev = is_device_ptr(dst);
     const u8* d_src = (const u8*)src; u8* d_dst = (u8*)dst;
@@ -1041,6 +1120,50 @@ static size_t cstream_compress(ZSTD_CCtx* c, size_t n)      // first n buffered 
     c->sIn.erase(c->sIn.begin(), c->sIn.begin() + (ptrdiff_t)n);
     return 0;
 }
+// A batch of a single-frame session (ZSTDMI_CCtx_setSingleFrame): the first n buffered bytes continue the session's ONE frame.  The last
+// kStreamTail bytes the frame already holds go up in front of the batch, so its first block has its history where every other
+// block finds it: in front of itself.  The first batch writes the header (a window descriptor, no content size), the batch of
+// ZSTD_e_end sets Last_Block and appends the checksum.
+static size_t cstream_compress_single(ZSTD_CCtx* c, size_t n, bool ending)
+{
+    CallParams cp = sticky_params(c);
+    cp.single = true; cp.stream = true; cp.streamAt = c->sTotal; cp.streamEnd = ending; cp.seek = false; cp.checksumFlag = c->sChecksum;
+    size_t e = cctx_bind(c); if (isErr(e)) return e;
+    e = check_call_params(cp); if (isErr(e)) return e;
+    e = check_single_frame(c, cp, n); if (isErr(e)) return e;
+    if (c->sTotal + n > kSingleMax) return ZERR(kErrParameterUnsupported);
+    const size_t tail = c->sTail.size(), pad = (256 - tail % 256) % 256;       // (the batch itself begins 256-byte aligned)
+    const size_t cap = ZSTD_compressBound(n) + 32;
+    if (!c->stageSrc.ensure(pad + tail + n + 64) || !c->stageDst.ensure(cap + 64)) return ZERR(kErrMemoryAllocation);
+    u8* const d_src = (u8*)c->stageSrc.p + pad + tail;
+    if (tail && hipMemcpyAsync(d_src - tail, c->sTail.data(), tail, hipMemcpyHostToDevice, c->stream) != hipSuccess) return ZERR(kErrGeneric);
+    if (hipMemcpyAsync(d_src, c->sIn.data(), n, hipMemcpyHostToDevice, c->stream) != hipSuccess) return ZERR(kErrGeneric);
+    bool first = true;
+    const size_t r = compress_range(c, cp, (u8*)c->stageDst.p, cap, d_src, n, kStreamParamSize, first);
+    if (isErr(r)) return r;
+    const size_t at = c->sOut.size();
+    c->sOut.resize(at + r);
+    if (isErr(dev_read(c->sOut.data() + at, c->stageDst.p, r, c->stream))) { c->sOut.resize(at); return ZERR(kErrGeneric); }
+    c->sTail.insert(c->sTail.end(), c->sIn.begin(), c->sIn.begin() + (ptrdiff_t)n);
+    if (c->sTail.size() > kStreamTail) c->sTail.erase(c->sTail.begin(), c->sTail.end() - (ptrdiff_t)kStreamTail);
+    c->sTotal += n;
+    c->sIn.erase(c->sIn.begin(), c->sIn.begin() + (ptrdiff_t)n);
+    return 0;
+}
+// ZSTD_e_end with nothing buffered behind earlier batches: an empty raw last block, and the checksum of what the frame holds
+static size_t cstream_end_single(ZSTD_CCtx* c)
+{
+    u8 f[7] = { 1, 0, 0 }; size_t n = 3;
+    if (c->sChecksum) {
+        size_t e = cctx_bind(c); if (isErr(e)) return e;
+        u32 h = 0;
+        launch_stream_xxh((XxhCarry*)c->sfXxh.p, (const u8*)c->sfXxh.p, 0, 1, c->stream);
+        if (isErr(dev_read(&h, (const u8*)c->sfXxh.p + offsetof(XxhCarry, hash), sizeof h, c->stream))) return ZERR(kErrGeneric);
+        for (u32 i = 0; i < 4; ++i) f[n++] = (u8)(h >> (8 * i));
+    }
+    c->sOut.insert(c->sOut.end(), f, f + n);
+    return 0;
+}
 static size_t ZSTD_compressStream2_impl(ZSTD_CCtx* c, ZSTD_outBuffer* output, ZSTD_inBuffer* input, int endOp)
 {
     if (!c || !output || !input) return ZERR(kErrGeneric);
@@ -1052,14 +1175,20 @@ static size_t ZSTD_compressStream2_impl(ZSTD_CCtx* c, ZSTD_outBuffer* output, ZS
     if (input->size > input->pos && !input->src) return ZERR(kErrSrcSizeWrong);
     if (output->size > output->pos && !output->dst) return ZERR(kErrDstBufferNull);
     if (cstream_drain(c, output)) return c->sOut.size() - c->sOutPos;       // output full: nothing consumed this time
+    if (!c->sWrote && !c->sEnding && c->sIn.empty()) { c->sSingle = c->singleFrame != 0; c->sChecksum = c->checksumFlag; c->sTotal = 0; c->sTail.clear(); }      // a session begins
+    if (c->sSingle && !c->sEnding) {    // what one frame per session cannot be: refused before anything is taken
+        CallParams cp = sticky_params(c); cp.single = true; cp.stream = true; cp.seek = false;
+        const size_t e = check_single_frame(c, cp, 0); if (isErr(e)) return e;
+    }
     if (!c->sEnding) {
         const size_t n = input->size - input->pos;
         if (n) { c->sIn.insert(c->sIn.end(), (const u8*)input->src + input->pos, (const u8*)input->src + input->size); input->pos = input->size; c->sWrote = true; }
         size_t e = 0;
         if (endOp == 0) {                                      // ZSTD_e_continue: whole chunks only, so that frames stay 64 KiB
-            if (c->sIn.size() >= c->sBatch) e = cstream_compress(c, c->sIn.size() / kChunkSize * kChunkSize);
+            if (c->sIn.size() >= c->sBatch) { const size_t whole = c->sIn.size() / kChunkSize * kChunkSize; e = c->sSingle ? cstream_compress_single(c, whole, false) : cstream_compress(c, whole); }
         } else {
-            if (!c->sIn.empty()) e = cstream_compress(c, c->sIn.size());
+            if (!c->sIn.empty()) e = c->sSingle ? cstream_compress_single(c, c->sIn.size(), endOp == 2) : cstream_compress(c, c->sIn.size());     // (ZSTD_e_flush ends a block, not the frame)
+            else if (endOp == 2 && c->sSingle && c->sTotal) e = cstream_end_single(c);
             else if (endOp == 2 && !c->sWrote) {               // ZSTD_e_end on an empty stream: the empty frame (U/ZstdCompress.cs:5598-5656)
                 u8 tmp[16]; const size_t r = ZSTD_compress2(c, tmp, sizeof tmp, tmp, 0);
                 if (isErr(r)) e = r; else c->sOut.insert(c->sOut.end(), tmp, tmp + r);
@@ -1069,7 +1198,7 @@ static size_t ZSTD_compressStream2_impl(ZSTD_CCtx* c, ZSTD_outBuffer* output, ZS
         if (isErr(e)) return e;
     }
     const size_t left = cstream_drain(c, output);
-    if (c->sEnding && left == 0) { c->sEnding = false; c->sWrote = false; }    // frame session closed; the context may start another
+    if (c->sEnding && left == 0) { c->sEnding = false; c->sWrote = false; c->sTotal = 0; c->sTail.clear(); }    // frame session closed; the context may start another
     if (endOp == 0) return left ? left : (c->sBatch > c->sIn.size() ? c->sBatch - c->sIn.size() : 1);
     return left;
 }
@@ -1088,6 +1217,8 @@ size_t ZSTDMI_CCtx_setHistory(ZSTD_CCtx* c, int bytes, unsigned frameBytes)
     c->historyBytes = bytes; if (frameBytes) c->frameBytes = frameBytes; return 0;
 }
 size_t ZSTDMI_CCtx_setSeekTable(ZSTD_CCtx* c, unsigned mode) { if (!c) return ZERR(kErrGeneric); if (mode > 1) return ZERR(kErrParameterOutOfBound); c->seekTable = (int)mode; return 0; }
+// (no device is touched; what the switch cannot be combined with is refused by the call that would have to do it: check_single_frame)
+size_t ZSTDMI_CCtx_setSingleFrame(ZSTD_CCtx* c, unsigned mode) { if (!c) return ZERR(kErrGeneric); if (mode > 1) return ZERR(kErrParameterOutOfBound); c->singleFrame = (int)mode; return 0; }
 size_t ZSTDMI_seekTableBound(size_t srcSize) { return seek_table_bound(srcSize); }
 // (no device is touched: a loaded formatted dictionary is marked for another upload, which builds — or no longer builds — its tables)
 size_t ZSTDMI_CCtx_setDictEntropy(ZSTD_CCtx* c, unsigned mode)
@@ -1186,7 +1317,8 @@ size_t ZSTD_compressStream2(ZSTD_CCtx* c, ZSTD_outBuffer* output, ZSTD_inBuffer*
 // destinations, batch_place_kernel gives every chunk its place as an offset from the lowest destination pointer and huf_encode and
 // gather write there directly; without (the trainer), only the sizes come back.  A pass holds whole entries, at most
 // ZSTDMI_CCtx_setPassChunks chunks; per pass one table goes up and the entries' sizes come back in one copy.
-// An entry the class model does not cover — empty, windows below 64 KiB above one window, LDM above one block, the fast strategy's
+// An entry the class model does not cover — empty, windows below 64 KiB above one window, LDM above one block, more than one block under
+// ZSTDMI_CCtx_setSingleFrame (one frame per entry: a framing of its own), the fast strategy's
 // full 64 KiB blocks with far candidates (no per-chunk tables in that kernel), the sparse-input probe and multi-block frames of
 // 4 MiB and more, more chunks than a pass, several device workers — is compressed alone afterwards, in entry order, by the
 // single-call path, and counted in `alone`.
@@ -1209,7 +1341,7 @@ static size_t compress_entries(ZSTD_CCtx* c, const CallParams& cp, const u8* con
             if (!dsts[i]) { outSizes[i] = caps[i] ? ZERR(kErrDstBufferNull) : ZERR(kErrDstSizeTooSmall); continue; }
         }
         const Framing fr = S ? resolve_framing(c, cp, S) : Framing{};
-        bool batched = S && !fr.indepWindowLog && !fr.ldm && c->workers.size() <= 1 && (S + fr.chunkBytes - 1) / fr.chunkBytes <= passLimit;
+        bool batched = S && !fr.indepWindowLog && !fr.ldm && !fr.single && c->workers.size() <= 1 && (S + fr.chunkBytes - 1) / fr.chunkBytes <= passLimit;
         // multi-block frames: the blocks behind LDS history (chunks below 64 KiB; the full 64 KiB blocks with far candidates have no
         // table form, launch_lz), below 4 MiB and of at most 256 chunks (a block index and a frame size that fit chunk_frame_word);
         // with a dictionary's entropy tables (huf_tree_kernel<true> finds a frame's first block by c % frameBlocks), or with sizes

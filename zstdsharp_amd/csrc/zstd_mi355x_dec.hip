@@ -968,12 +968,6 @@ static void stream_note_input(ZSTD_DCtx* d)
     for (const auto& c : d->seg.carried) held += c.bytes.size();
     if ((long long)held > d->streamPeakInput) d->streamPeakInput = (long long)held;
 }
-static void xxh_carry_reset(XxhCarry* x)
-{
-    const u64 P1 = 0x9E3779B185EBCA87ULL, P2 = 0xC2B2AE3D27D4EB4FULL;
-    memset(x, 0, sizeof *x);
-    x->acc[0] = P1 + P2; x->acc[1] = P2; x->acc[2] = 0; x->acc[3] = 0 - P1;
-}
 
 // the frame whose header (all of it) is at the front of dIn begins: the fragment header, the first history, the checksum state
 static size_t stream_begin_frame(ZSTD_DCtx* d, const HostHeader& h)
