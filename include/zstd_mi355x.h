@@ -314,6 +314,26 @@ size_t ZSTDMI_CCtx_setSeekTable(ZSTD_CCtx* cctx, unsigned mode);
  * ZSTDMI_debugCompressSamples and contexts with several device workers.  Without a dictionary, with a raw-content dictionary, behind
  * ZSTD_CCtx_refPrefix and in ZSTD_compressCCtx the switch changes nothing.  Every zstd decoder holding the dictionary reads the frames. */
 size_t ZSTDMI_CCtx_setDictEntropy(ZSTD_CCtx* cctx, unsigned mode);
+/* Index a dictionary once, when it is uploaded, and match against ALL of it (the reference digests a dictionary once, ZSTD_createCDict /
+ * ZSTD_loadDictionaryContent, and probes its table beside the block's own, ZSTD_compressBlock_fast_dictMatchState).  0 = off (the
+ * default: no existing output changes), 1 = on, any other mode: parameter_outOfBound; NULL context: GENERIC.  Sticky; the call touches
+ * no device; before or after ZSTD_CCtx_loadDictionary, a loaded dictionary is uploaded again by the next call that uses it.
+ * On, with a dictionary of at least 8 bytes in use and the fast strategy resolved (levels <= 2, negative levels, ZSTD_c_strategy = 1):
+ * the last min(content size, 188 KiB) bytes of the dictionary's content stay on the device behind a hash index built once per upload
+ * and per device worker; no dictionary byte is staged or hashed per chunk; every position the finder probes also looks one candidate
+ * up in that index.  A source of up to 64 KiB is one block in one single-segment frame (without the switch: 64 KiB minus the staged
+ * dictionary tail, 4 KiB behind 60 KiB of it); larger sources are independent 64 KiB frames, each behind the dictionary.  A match
+ * into the dictionary ends with the dictionary.  DictID, content size, checksum, ZSTD_c_dictIDFlag and the dictionary's repcodes are
+ * as without the switch, and ZSTDMI_CCtx_setDictEntropy composes with it.  Honoured by ZSTD_compress2, ZSTDMI_compressDevice,
+ * ZSTDMI_compressBatch (bytes equal to the single call; entries up to 64 KiB are one block), ZSTD_compressStream2,
+ * ZSTDMI_debugCompressSamples and contexts with several device workers.  The switch changes nothing without a dictionary, at levels
+ * whose finder is not the fast one (>= 3), under ZSTD_c_windowLog 10 .. 15, behind ZSTD_CCtx_refPrefix and in ZSTD_compressCCtx; what
+ * a dictionary is refused with (long-distance matching above one block, ZSTDMI_CCtx_setSingleFrame) stays refused.  Dictionary
+ * content in front of its last 188 KiB is not matched against.  Every zstd decoder holding the dictionary reads the frames. */
+size_t ZSTDMI_CCtx_setDictIndex(ZSTD_CCtx* cctx, unsigned mode);
+/* (debug) dictionary content bytes the index covers: 0 with the switch off, without a dictionary, or for a formatted dictionary no
+ * call has validated on a device yet; -1 without a context */
+long long ZSTDMI_debugDictIndexed(const ZSTD_CCtx* cctx);
 /* One frame per call and per stream session, as the reference writes it (S/Compressor.cs Wrap, S/CompressionStream.cs).  0 = off (the
  * default: a run of independent frames, every existing output unchanged), 1 = on, any other mode: parameter_outOfBound; NULL context:
  * GENERIC.  Sticky; the call touches no device.

@@ -8,7 +8,11 @@ with history of the default settings — at the same kinds and levels.  Per poin
   (d) the batch call's stage times (ZSTDMI_*_getStageTimes)
 Best of 3 after a warm-up call of the same shape; the host clock stops after the call's final synchronise (every call ends with one).
 The input is 16 MiB of generated data repeated (entries are independent, so the repeats are nobody's match).
-python tools/batch_time.py [MiB] [--dict-entropy] [--dict-row] [--frames-rows] [--measure-only]
+python tools/batch_time.py [MiB] [--dict-entropy] [--dict-row] [--frames-rows] [--measure-only] [--dict-index-rows] [--dict-index]
+  --dict-index-rows : only the rows of ZSTDMI_CCtx_setDictIndex, batch calls alone: 4 KiB text entries at level 1 with
+                   tests/golden/train_default_text.dict, and the 1000 held-out JSON records of tests/golden/make_golden_train.py
+                   tiled to the total with train_default_json.dict; the ratio, the batch call's ms and its stage times
+  --dict-index   : those rows with the switch on (without it they also run on a library from before the switch existed)
   --dict-entropy : the dictionary row with ZSTDMI_CCtx_setDictEntropy on (the dictionary's entropy tables in the compressor)
   --dict-row     : only the dictionary row
   --frames-rows  : only the 256 KiB and 1 MiB rows
@@ -24,7 +28,8 @@ lib = z._ffi.load()
 MiB = 1 << 20
 FLAGS = [a for a in sys.argv[1:] if a.startswith("--")]
 ARGS = [a for a in sys.argv[1:] if not a.startswith("--")]
-assert all(f in ("--dict-entropy", "--dict-row", "--frames-rows", "--measure-only") for f in FLAGS), FLAGS
+assert all(f in ("--dict-entropy", "--dict-row", "--frames-rows", "--measure-only", "--dict-index-rows", "--dict-index") for f in FLAGS), FLAGS
+DICT_INDEX_ROWS, DICT_INDEX = "--dict-index-rows" in FLAGS, "--dict-index" in FLAGS
 DICT_ENTROPY, DICT_ROW, FRAMES_ROWS, MEASURE_ONLY = "--dict-entropy" in FLAGS, "--dict-row" in FLAGS, "--frames-rows" in FLAGS, "--measure-only" in FLAGS
 total = (int(ARGS[0]) if ARGS else 256) * MiB
 SAMPLE = 4096
@@ -60,6 +65,55 @@ def ok(r):
     return r
 
 
+def dict_index_rows():
+    golden = os.path.join(ROOT, "tests", "golden")
+    sys.path.insert(0, golden)
+    import make_golden_train as mgt
+    text = datagen.gen("text", 16 * MiB, 5) * (total // (16 * MiB))
+    recs = mgt.json_records(2000, 77)[1000:]
+    json_blob = b"".join(recs); json_sizes = [len(r) for r in recs]
+    reps = total // len(json_blob)
+    rows = [("text 4 KiB L1 train_default_text", "train_default_text.dict", text, [4096] * (total // 4096)),
+            ("json records L1 train_default_json", "train_default_json.dict", json_blob * reps, json_sizes * reps)]
+    print(f"dictionary index {'on' if DICT_INDEX else 'off'}; entropy tables {'on' if DICT_ENTROPY else 'off'}", flush=True)
+    for name, dname, blob, szs in rows:
+        dic = open(os.path.join(golden, dname), "rb").read()
+        src = torch.from_numpy(np.frombuffer(blob, dtype=np.uint8).copy()).cuda()
+        n = len(szs)
+        offs = np.concatenate(([0], np.cumsum(szs)[:-1])).tolist()
+        caps = [lib.ZSTD_compressBound(x) for x in szs]
+        coffs = np.concatenate(([0], np.cumsum(caps)[:-1])).tolist()
+        dst = torch.empty(sum(caps) + 64, dtype=torch.uint8, device="cuda")
+        out = torch.empty(len(blob), dtype=torch.uint8, device="cuda")
+        c, d = lib.ZSTD_createCCtx(), lib.ZSTD_createDCtx()
+        lib.ZSTD_CCtx_setParameter(c, 100, 1)
+        if DICT_INDEX:
+            ok(lib.ZSTDMI_CCtx_setDictIndex(c, 1))
+        if DICT_ENTROPY:
+            ok(lib.ZSTDMI_CCtx_setDictEntropy(c, 1))
+        torch.cuda.synchronize(); t0 = time.perf_counter()
+        ok(lib.ZSTD_CCtx_loadDictionary(c, dic, len(dic)))
+        tiny = (ctypes.c_size_t * 1)()
+        ok(lib.ZSTDMI_compressBatch(c, ptrs(src.data_ptr(), [0]), sizes([8]), 1, ptrs(dst.data_ptr(), [0]), sizes([caps[0]]), tiny))
+        load_ms = (time.perf_counter() - t0) * 1e3       # the load, the dictionary's upload (and index) and one 8-byte entry
+        ok(lib.ZSTD_DCtx_loadDictionary(d, dic, len(dic)))
+        s_ptr, d_ptr, o_ptr = ptrs(src.data_ptr(), offs), ptrs(dst.data_ptr(), coffs), ptrs(out.data_ptr(), offs)
+        s_sz, d_cap, got, back = sizes(szs), sizes(caps), (ctypes.c_size_t * n)(), (ctypes.c_size_t * n)()
+        lib.ZSTDMI_CCtx_setProfiling(c, 1)
+        cb = best_of(lambda: ok(lib.ZSTDMI_compressBatch(c, s_ptr, s_sz, n, d_ptr, d_cap, got)))
+        assert not any(lib.ZSTD_isError(g) for g in got) and lib.ZSTDMI_debugLastBatchAlone(c) == 0
+        cst = stage_times(lib.ZSTDMI_CCtx_getStageTimes, c)
+        ok(lib.ZSTDMI_decompressBatch(d, d_ptr, got, n, o_ptr, s_sz, back))
+        assert list(back) == szs and bool(torch.equal(out, src))
+        print(f"| {name:36s} | {n:7d} | ratio {sum(got) / len(blob):.4f} | batch {cb * 1e3:7.2f} ms | load + first call {load_ms:6.2f} ms |\n    compress stages ms: {cst}", flush=True)
+        lib.ZSTD_freeCCtx(c); lib.ZSTD_freeDCtx(d)
+        del src, dst, out
+        torch.cuda.empty_cache()
+
+
+if DICT_INDEX_ROWS:
+    dict_index_rows()
+    sys.exit(0)
 data = {k: torch.from_numpy(np.frombuffer(datagen.gen(k, 16 * MiB, 5), dtype=np.uint8).copy()).cuda().repeat(total // (16 * MiB)) for k in ("text", "zipf")}
 points = [(kind, size, level, None) for size in (4096, 16384, 65536) for kind in ("text", "zipf") for level in (1, 3)] + [("text", 4096, 3, DICT)]
 frames_points = [(kind, size, level, None) for size in (256 << 10, 1 << 20) for kind in ("text", "zipf") for level in (1, 3)]

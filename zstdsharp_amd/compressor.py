@@ -71,6 +71,7 @@ class Compressor(_PrefixHolder):
         self._level = 0
         self._seek_table = False
         self._dict_entropy = False
+        self._dict_index = False
         self._single_frame = False
         self.Level = level if level else self.DefaultCompressionLevel
 
@@ -148,6 +149,17 @@ class Compressor(_PrefixHolder):
         self._ensure_not_disposed()
         ensure_zstd_success(self._lib, self._lib.ZSTDMI_CCtx_setDictEntropy(self.cctx, 1 if on else 0))
         self._dict_entropy = bool(on)
+
+    # ---- dictionary index (ZSTDMI_CCtx_setDictIndex): the whole dictionary indexed once at upload, nothing staged per chunk; off by default ----
+    @property
+    def dict_index(self) -> bool:
+        return self._dict_index
+
+    @dict_index.setter
+    def dict_index(self, on):
+        self._ensure_not_disposed()
+        ensure_zstd_success(self._lib, self._lib.ZSTDMI_CCtx_setDictIndex(self.cctx, 1 if on else 0))
+        self._dict_index = bool(on)
 
     # ---- one frame per Wrap and per stream session (ZSTDMI_CCtx_setSingleFrame), as the reference writes; off by default ----
     @property

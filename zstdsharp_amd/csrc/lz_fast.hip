@@ -181,6 +181,56 @@ __device__ __forceinline__ u32 match_len_far(const LzLds& L, u32 p, const u8* __
     return l >= 4 ? l : 0;
 }
 
+// Dictionary index (ZSTDMI_CCtx_setDictIndex): one u32 per bucket in global memory, built once per loaded dictionary
+// over its last `len` <= kFarMax content bytes: (position + 1) << 14 | tag14, 0 = empty; of the positions of a bucket the one nearest
+// the dictionary's end stays (atomicMax).  The bucket is the top `log` <= 18 bits of the finder's hash product, the tag the 14 bits
+// below them (disjoint from the bucket whatever the log), so a miss is dropped without a read of dictionary bytes.
+constexpr u32 kDictIdxMaxLog = 18, kDictIdxMinLog = 10;
+static_assert(kFarMax + 1 < (1u << kDictIdxMaxLog), "a dictionary position + 1 fits the entry's 18 bits");
+__device__ __forceinline__ u32 didx_tag(u32 prod, u32 log) { return (prod >> (kDictIdxMaxLog - log)) & 0x3FFFu; }
+
+// match_len_far against a candidate in the dictionary, `back` bytes in front of its end (g = the candidate's address): the match ends
+// with the dictionary at the latest; reads reach at most kLenCap bytes past g, inside the padding behind the content
+__device__ __forceinline__ u32 match_len_dict(const LzLds& L, u32 p, const u8* __restrict__ g, u32 back, u64 w, u32 n)
+{
+    const u64 cw = readLE64(g);
+    if ((u32)cw != (u32)w) return 0;
+    u64 x = w ^ cw;
+    u32 l = x ? (ctz64(x) >> 3) : 8;
+    if (!x) {
+        while (l < kLenCap && l < back && p + l + 8 <= n) {
+            x = lds_load8(L.in, p + l) ^ readLE64(g + l);
+            if (x) { l += ctz64(x) >> 3; break; }
+            l += 8;
+        }
+    }
+    if (l > back) l = back;
+    if (l > n - p) l = n - p;
+    if (l > kLenCap) l = kLenCap;
+    return l >= 4 ? l : 0;
+}
+
+__global__ __launch_bounds__(256) void dict_index_kernel(const u8* __restrict__ content, const u32 len, u32* __restrict__ table, const u32 log)
+{
+    for (u32 i = blockIdx.x * 256 + threadIdx.x; i + 8 <= len; i += gridDim.x * 256) {
+        const u32 hp = hash6p(readLE64(content + i));
+        atomicMax(&table[hp >> (32 - log)], ((i + 1) << 14) | didx_tag(hp, log));
+    }
+}
+// table: 1 << log entries, zeroed here; content: the indexed bytes (their last 8 start no entry: a hash reads 8 bytes)
+void launch_dict_index(const u8* content, u32 len, u32* table, u32 log, hipStream_t stream)
+{
+    (void)hipMemsetAsync(table, 0, sizeof(u32) << log, stream);
+    hipLaunchKernelGGL(dict_index_kernel, dim3((len + 255) / 256 < 256 ? (len + 255) / 256 : 256), dim3(256), 0, stream, content, len, table, log);
+}
+u32 dict_index_log(u32 len)
+{
+    u32 log = kDictIdxMinLog;
+    while (log < kDictIdxMaxLog && (1u << log) < len) ++log;
+    return log;
+}
+u32 dict_index_max() { return kFarMax; }
+
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Region parse (fast strategy, dense data).  The tile loop above computes a verified match at EVERY position and then selects
@@ -801,6 +851,11 @@ __device__ __forceinline__ void dense_rest(LzLds& L, const u32 n, const u32 inse
 // every single call of the levels >= 3 runs; without TAB the code is that of a kernel without the table.
 // TAB == 2: the call's input is ONE frame that passes (and a stream's batches) cut anywhere (ZSTDMI_CCtx_setSingleFrame):
 // frameAt = bytes of the frame in front of src, all of them readable there as history; frameTotal = the frame's content size.
+// TAB == 3 (on the FAR instance of the fast finder): every chunk is a frame of its own behind an INDEXED dictionary
+// (ZSTDMI_CCtx_setDictIndex).  The chunk alone sits in LDS; what lies "in front of the block" is the dictionary's
+// content, whose candidates come from one gather per probed position out of the index in global memory.  The arguments an instance
+// without a dictionary prefix, a region parse and a frame place leaves idle carry it: prefixArg = the END of the dictionary's
+// content, prefixLenArg = the indexed bytes in front of it, chainAll = the index (u32 per bucket), frameAt = log2 of its buckets.
 template <int MODE, int SHORT, bool DICT, bool FAR, int TAB>
 __global__ __launch_bounds__(1024) void lz_kernel(const u8* __restrict__ src, u64 srcSize,
                                                   Seq* __restrict__ seqs, u8* __restrict__ lits,
@@ -838,6 +893,10 @@ __global__ __launch_bounds__(1024) void lz_kernel(const u8* __restrict__ src, u6
     const u32 hist = DICT ? kChunkSize - ((chunkBytes + kTilePos - 1) & ~(kTilePos - 1)) : 0u;      // (chunks below a tile: ZSTD_c_windowLog 10, 11)
     const u64 base = (u64)c * cb;
     const u8* __restrict__ in = src + base;
+    // the byte behind the far history's last: the block itself, or the end of an indexed dictionary
+    const u8* __restrict__ const farEnd = TAB == 3 ? prefixArg : in;
+    const u32* __restrict__ const dictIdx = TAB == 3 ? reinterpret_cast<const u32*>(chainAll) : nullptr;
+    const u32 dictLog = TAB == 3 ? (u32)frameAt : 0u;
     // (frameBlocksArg bit 31: the frame's blocks are independent of each other — windows below 64 KiB, where a block IS the window:
     //  no history; a dictionary is history of the frame's first block only, whose image is the layout the decoder sees)
     const u32 frameBlocks = frameBlocksArg & 0x7FFFFFFFu;
@@ -846,7 +905,7 @@ __global__ __launch_bounds__(1024) void lz_kernel(const u8* __restrict__ src, u6
     // comes from a table instead of the call's size: bits 24-31 the block index inside its frame, bits 0-23 the frame's content size
     // (TAB == 2: only whether the block is its frame's first; what lies in front of it is counted in bytes)
     const u32 bf = ((DICT || FAR) && frameBlocks) ? (TAB == 1 ? chunkFrames[c] >> 24 : TAB == 2 ? (frameAt + base != 0 ? 1u : 0u) : c % frameBlocks) : 0u;               // block index inside its frame
-    const u32 farAvail = FAR ? (TAB == 2 ? (frameAt + base < kFarMax ? (u32)(frameAt + base) : kFarMax) : (u64)bf * cb < kFarMax ? bf * cb : kFarMax) : 0u;      // bytes of far history in front of the block
+    const u32 farAvail = FAR ? TAB == 3 ? prefixLenArg : (TAB == 2 ? (frameAt + base < kFarMax ? (u32)(frameAt + base) : kFarMax) : (u64)bf * cb < kFarMax ? bf * cb : kFarMax) : 0u;      // bytes of far history in front of the block
     u32 prefixLen = prefixLenArg; const u8* __restrict__ prefix = prefixArg;
     if (DICT && frameBlocks && !indep) { const u64 back = TAB == 2 ? frameAt + base : (u64)bf * cb; prefixLen = back < hist ? (u32)back : hist; prefix = in - prefixLen; }
     if (DICT && indep && bf) prefixLen = 0;
@@ -928,7 +987,7 @@ __global__ __launch_bounds__(1024) void lz_kernel(const u8* __restrict__ src, u6
             pfValid = true;
         }
     }
-    if (FAR && farAvail) {
+    if (FAR && TAB != 3 && farAvail) {
         // the table starts out holding the input in front of the block (what the reference's table still holds from the blocks
         // before, U/ZstdFast.cs:9-46): latest occurrence per bucket, straight from global memory
         for (u32 i = tid * kFarStep; i < farAvail; i += kTile * kFarStep) {
@@ -964,7 +1023,7 @@ __global__ __launch_bounds__(1024) void lz_kernel(const u8* __restrict__ src, u6
         // backward: give bytes of the pending literal run to the match while they agree (ZstdFast.cs:242-247)
         // (four bytes per step: the dwords in front of the match and of its source, compared from the top)
         if (FAR && off > p) {                                          // the source lies in front of the block: byte steps against global memory
-            while (p > floorPos && off - p < farAvail && L.in[p - 1] == in[(s64)p - 1 - (s64)off]) --p;
+            while (p > floorPos && off - p < farAvail && L.in[p - 1] == (TAB == 3 ? farEnd : in)[(s64)p - 1 - (s64)off]) --p;
         } else for (;;) {
             u32 room = p - floorPos;                                   // bytes the pending literal run can give
             const u32 srcRoom = p - off - lowLimit;                    // bytes in front of the source
@@ -996,6 +1055,18 @@ __global__ __launch_bounds__(1024) void lz_kernel(const u8* __restrict__ src, u6
         for (;;) {
             const u32 pos = e + 8 * lane;              // reads past n land in the table region: harmless, clamped below
             const s32 sp = (s32)pos - (s32)off;                        // FAR: a negative source position is in front of the block
+            if constexpr (TAB == 3) {
+                // an indexed dictionary: a match into it ends with it (the 8 bytes read at its last ones end inside the padding)
+                const bool dictTail = off > p && sp > -8;
+                const u64 x = lds_load8(L.in, pos) ^ (sp < 0 ? readLE64(farEnd + sp) : lds_load8(L.in, dictTail ? 0u : (u32)sp));
+                const u64 bad = ballot(x != 0 || pos + 8 > n || dictTail);
+                if (bad == 0) { e += 512; continue; }
+                const u32 fl = ctz64(bad);
+                u32 cnt = x ? (ctz64(x) >> 3) : 8;
+                if (dictTail) { const u32 left = sp < 0 ? (u32)-sp : 0u; cnt = cnt < left ? cnt : left; }
+                e += 8 * fl + read_lane(cnt, fl);
+                break;
+            }
             const u64 x = lds_load8(L.in, pos) ^ ((FAR && sp < 0) ? readLE64(in + sp) : lds_load8(L.in, (u32)sp));
             const u64 bad = ballot(x != 0 || pos + 8 > n);
             if (bad == 0) { e += 512; continue; }
@@ -1070,16 +1141,19 @@ __global__ __launch_bounds__(1024) void lz_kernel(const u8* __restrict__ src, u6
         // ---------------- probe ----------------
         // fast: h = hash product, cand = table entry.  dual: h = long product, h2 = short product, cand = tableL | tableS << 16
         u64 w[kPPT], w2[kPPT]; u32 h[kPPT], h2[kPPT], cand[kPPT]; bool valid[kPPT];
+        u32 dcand[TAB == 3 ? kPPT : 1];          // TAB == 3: the dictionary index's entries, gathered here and first looked at behind the barrier
 #pragma unroll
         for (u32 j = 0; j < kPPT; ++j) {
             const u32 q = probed(j), p = tileStart + q;
             valid[j] = j < nPass && j * kTile + tid < slots && p + 8 <= n && p >= lowLimit; w[j] = 0; w2[j] = 0; h[j] = 0; h2[j] = 0; cand[j] = 0;
+            if constexpr (TAB == 3) dcand[j] = 0;
             if (j >= nPass) continue;            // uniform
             if (valid[j]) {
                 lds_load16(L.in, p, w[j], w2[j]);
                 if (MODE == 0) {
                     h[j] = hash6p(w[j]);
                     cand[j] = table[hidx(h[j])];
+                    if constexpr (TAB == 3) dcand[j] = dictIdx[h[j] >> (32 - dictLog)];
                     if (!fused) atomicMin(&first[hidx(h[j])], ((stamp + q) << 16) | htag(h[j]));
                 } else {
                     h[j] = hash8p(w[j]); h2[j] = hash_shortp<SHORT>(w[j]);
@@ -1143,6 +1217,12 @@ __global__ __launch_bounds__(1024) void lz_kernel(const u8* __restrict__ src, u6
                                 const u32 l2 = crel >= kFarMax ? match_len(L, p, crel - kFarMax, w[j], w2[j], n)
                                                                : match_len_far(L, p, in - (kFarMax - crel), w[j], n);
                                 if (l2 > len) { len = l2; off = kFarMax + p - crel; }
+                            }
+                            // the dictionary's candidate: further away than anything in the block, so it has to be longer
+                            if constexpr (TAB == 3) if (dcand[j] && (dcand[j] & 0x3FFFu) == didx_tag(h[j], dictLog) && len < kLenCap) {
+                                const u32 back = farAvail - ((dcand[j] >> 14) - 1);
+                                const u32 l2 = match_len_dict(L, p, farEnd - back, back, w[j], n);
+                                if (l2 > len) { len = l2; off = p + back; }
                             }
                         } else if (cand[j] && (cand[j] & 0xFFFFu) == tag && len < kLenCap) {
                             const u32 cpos = (cand[j] >> 16) - 1;
@@ -1711,7 +1791,7 @@ static void launch_one(const u8* src, u64 srcSize, u32 nChunks, Seq* seqs, u8* l
     const bool claim = MODE == 0 && !DICT && !FAR && claimCtr && nChunks > cuCount[dev & 63];
     if (claim) (void)hipMemsetAsync(claimCtr, 0, sizeof(u32), stream);
     const u32 grid = claim ? cuCount[dev & 63] : nChunks;
-    hipLaunchKernelGGL((lz_kernel<MODE, SHORT, DICT, FAR, TAB>), dim3(grid), dim3(kTile), sizeof(LzLds), stream, src, srcSize, seqs, lits, meta, prefix, prefixLen, chunkBytes, fhExtra, minStrideLog, frameBlocks, cand, cand ? chain : nullptr, cand ? regionList : nullptr, nChunks,
+    hipLaunchKernelGGL((lz_kernel<MODE, SHORT, DICT, FAR, TAB>), dim3(grid), dim3(kTile), sizeof(LzLds), stream, src, srcSize, seqs, lits, meta, prefix, prefixLen, chunkBytes, fhExtra, minStrideLog, frameBlocks, cand, (cand || TAB == 3) ? chain : nullptr, cand ? regionList : nullptr, nChunks,
                        claim ? claimCtr : nullptr, chunkLens, chunkFrames, frameAt, frameTotal);
     hook("lz_fast");
     if constexpr (kSplit) if (cand) {                      // the dense chunks' rest: 256 workgroups (one per CU) walk the list
@@ -1728,10 +1808,20 @@ static void launch_one(const u8* src, u64 srcSize, u32 nChunks, Seq* seqs, u8* l
 // form one frame and each sees up to 64 KiB - chunkBytes of the input in front of it.  chunkBytes < 64 KiB with neither: independent
 // frames of chunkBytes each (ZSTD_c_windowLog 10 .. 15: a frame is its own window), on the same instantiation with an empty history.
 // cand / regionList (null: off): workspace of the region parse, 65536 u16 per chunk and 1 + nChunks u32.
+// dix (null: off): an indexed dictionary behind full 64 KiB chunks, each a frame of its own (fast finder only; chunkLens allowed).
 void launch_lz(u32 finder, const u8* src, u64 srcSize, u32 nChunks, Seq* seqs, u8* lits, ChunkMeta* meta, const u8* prefix, u32 prefixLen,
                u32 chunkBytes, u32 fhExtra, u32 minStrideLog, u32 frameBlocks, u16* cand, u16* chain, u32* regionList, u32 hcDepth, hipStream_t stream, StageHook hook, u32* claimCtr,
-               const u32* chunkLens, const u32* chunkFrames, const FramePlace* place)
+               const u32* chunkLens, const u32* chunkFrames, const FramePlace* place, const DictIndexRef* dix)
 {
+    if (dix) {
+        // every chunk a frame of its own behind an indexed dictionary: the FAR instance with the dictionary as what lies in front of
+        // the block (TAB == 3, see lz_kernel for the arguments that carry the index).  An instance of its own, so the kernels of a
+        // context without the switch are the ones from before it existed.
+        assert(finder == 0 && !place && !chunkFrames && !frameBlocks && chunkBytes == kChunkSize && dix->len >= 8 && dix->len <= kFarMax);
+        launch_one<0, 5, false, true, 3>(src, srcSize, nChunks, seqs, lits, meta, dix->end, dix->len, kChunkSize, fhExtra, minStrideLog, 0, nullptr, (u16*)dix->table, nullptr, 0, stream, hook, claimCtr,
+                                         chunkLens, nullptr, dix->log, 0);
+        return;
+    }
     if (place) {
         // one frame across passes: the long-distance framing's blocks (resolve_framing), each with its place in bytes.  Instances of
         // their own (TAB == 2), so the kernels of a context without the switch are the ones from before it existed.

@@ -19,10 +19,16 @@ namespace zmi {
 // place (ZSTDMI_CCtx_setSingleFrame): the call's input is ONE frame that passes and stream batches cut anywhere: `at` = bytes of the frame in
 // front of src (readable there, as far as the finders reach back), `total` = the frame's content size (~0: the frame goes on behind this pass)
 struct FramePlace { u64 at, total; };
+// an indexed dictionary (ZSTDMI_CCtx_setDictIndex; lz_fast.hip): `end` = the byte behind its content on the device (readable for 64
+// bytes more), `len` = the indexed bytes in front of `end`, `table` = 1 << log buckets
+struct DictIndexRef { const u8* end; u32 len; const u32* table; u32 log; };
+void launch_dict_index(const u8* content, u32 len, u32* table, u32 log, hipStream_t stream);
+u32 dict_index_log(u32 len);        // log2 of the buckets for `len` indexed bytes
+u32 dict_index_max();               // the most bytes an index covers (the far candidates' reach)
 inline u32 chunk_frame_word(u32 blockInFrame, u32 frameLen) { assert(blockInFrame < 256 && frameLen < (1u << 24)); return (blockInFrame << 24) | frameLen; }
 void launch_lz(u32 finder, const u8* src, u64 srcSize, u32 nChunks, Seq* seqs, u8* lits, ChunkMeta* meta, const u8* prefix, u32 prefixLen,
                u32 chunkBytes, u32 fhExtra, u32 minStrideLog, u32 frameBlocks, u16* cand, u16* chain, u32* regionList, u32 hcDepth, hipStream_t stream, StageHook hook, u32* claimCtr,
-               const u32* chunkLens = nullptr, const u32* chunkFrames = nullptr, const FramePlace* place = nullptr);
+               const u32* chunkLens = nullptr, const u32* chunkFrames = nullptr, const FramePlace* place = nullptr, const DictIndexRef* dix = nullptr);
 void launch_lz_probe(const u8* src, u64 srcSize, u64 front, u64 groupBytes, u32 nGroups, u32 tilesPerGroup, u32* out, hipStream_t stream);
 void launch_huf_build(const u8* lits, ChunkMeta* meta, HufTable* tables, u8* slots, u32 nChunks, u32 rawLiterals, const u8* src, u32 chunkBytes,
                       hipStream_t stream, StageHook hook, const DictCTables* dct = nullptr, u32 frameBlocks = 0);

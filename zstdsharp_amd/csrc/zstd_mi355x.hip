@@ -37,6 +37,12 @@ struct ZSTD_CCtx_s {
     // the dictionary's upload) and the first block of every frame is coded with them as its previous entropy state.
     std::vector<u8> dictHost, dictFull; DevBuf dict, dictFullDev, dictInfoDev, dictCTabDev; bool dictDirty = false, dictFormatted = false;
     int dictEntropy = 0;        // ZSTDMI_CCtx_setDictEntropy (sticky)
+    // ZSTDMI_CCtx_setDictIndex (sticky): the dictionary's content — its last dict_index_max() bytes — stays whole on the device with a
+    // hash index over it, built once per upload (lz_fast.hip), and the fast strategy's chunks look candidates up there instead of
+    // staging a tail of it.  dictWide = those bytes of a raw-content dictionary (kept at every load, so the switch may come later; a
+    // formatted one has them in dictFull); dictIdxEnd / Len / Log = what the last upload indexed (Len 0: nothing).
+    int dictIndex = 0;
+    std::vector<u8> dictWide; DevBuf dictWideDev, dictIdxDev; const u8* dictIdxEnd = nullptr; u32 dictIdxLen = 0, dictIdxLog = 0;
     DictInfo info = {};
     u64 dictGen = 0;            // bumped by every ZSTD_CCtx_loadDictionary: device workers copy the dictionary when theirs is older
     // ZSTDMI_CCtx_setDevices: one worker context per listed device (its own stream and workspaces there); a call's frames are
@@ -74,6 +80,16 @@ static u32 dict_prefix_len(const ZSTD_CCtx* c, size_t srcSize)
 
 
 
+// -> content bytes of the loaded dictionary that the index covers (0 = no index: switch off, no dictionary, or one below 8 bytes,
+// which is no dictionary at all); a formatted dictionary's content size is known once it has been validated (cctx_sync_dictionary)
+static u32 dict_index_len(const ZSTD_CCtx* c)
+{
+    if (!c->dictIndex) return 0;
+    const size_t have = c->dictFormatted ? (c->dictFull.empty() ? 0 : c->info.contentSize) : c->dictWide.size();
+    if (have < 8) return 0;
+    return (u32)(have < dict_index_max() ? have : dict_index_max());
+}
+
 static size_t cctx_sync_dictionary(ZSTD_CCtx* c);
 static size_t cctx_bind(ZSTD_CCtx* c) { return ctx_bind(c); }
 
@@ -86,6 +102,7 @@ struct CallParams {
     int ldm = 0, ldmHashLog = 0, ldmMinMatch = 0, ldmBucketSizeLog = 0, ldmHashRateLog = 0;     // (ZSTD_compressCCtx: all 0, as the reference's level-only parameters)
     bool useDict = true;
     bool seek = false;                  // append a seek table (ZSTDMI_CCtx_setSeekTable; ZSTD_compressCCtx: never, as it never runs LDM)
+    bool dictIndex = false;             // look candidates up in the dictionary's index (ZSTDMI_CCtx_setDictIndex; ZSTD_compressCCtx uses no dictionary)
     bool dictEntropy = false;           // code with a formatted dictionary's entropy tables (ZSTDMI_CCtx_setDictEntropy; ZSTD_compressCCtx uses no dictionary)
     const u8* pfx = nullptr; size_t pfxSize = 0;    // the long form of a referenced prefix (compress_prefixed): device bytes in front of the ONE frame
     bool single = false;                // one frame per call (ZSTDMI_CCtx_setSingleFrame; ZSTD_compressCCtx: never, level-only parameters)
@@ -99,6 +116,7 @@ static CallParams sticky_params(const ZSTD_CCtx* c)
     p.strategy = c->strategy; p.targetLength = c->targetLength; p.windowLog = c->windowLog; p.searchLog = c->searchLog; p.minMatch = c->minMatch; p.chainLog = c->chainLog; p.useDict = true;
     p.seek = c->seekTable != 0;
     p.dictEntropy = c->dictEntropy != 0;
+    p.dictIndex = c->dictIndex != 0;
     p.single = c->singleFrame != 0;
     p.ldm = c->ldm; p.ldmHashLog = c->ldmHashLog; p.ldmMinMatch = c->ldmMinMatch; p.ldmBucketSizeLog = c->ldmBucketSizeLog; p.ldmHashRateLog = c->ldmHashRateLog;
     return p;
@@ -168,6 +186,22 @@ static size_t cctx_sync_dictionary(ZSTD_CCtx* c)
         if (hipMemcpyAsync(c->dict.p, c->dictHost.data(), c->dictHost.size(), hipMemcpyHostToDevice, s) != hipSuccess) return ZERR(kErrGeneric);
         if (isErr(stream_wait(s))) return ZERR(kErrGeneric);
     }
+    c->dictIdxLen = 0;
+    if (const u32 ixLen = dict_index_len(c)) {      // (the setter marks the dictionary dirty, as ZSTDMI_CCtx_setDictEntropy does)
+        // the content's end on the device, with 64 readable bytes behind it: a formatted dictionary's ends dictFullDev; a raw one goes up whole
+        const u8* end = nullptr;
+        if (c->dictFormatted) end = (const u8*)c->dictFullDev.p + c->dictFull.size();
+        else {
+            if (!c->dictWideDev.ensure((size_t)ixLen + 64)) return ZERR(kErrMemoryAllocation);
+            if (hipMemcpyAsync(c->dictWideDev.p, c->dictWide.data() + (c->dictWide.size() - ixLen), ixLen, hipMemcpyHostToDevice, s) != hipSuccess) return ZERR(kErrGeneric);
+            end = (const u8*)c->dictWideDev.p + ixLen;
+        }
+        const u32 log = dict_index_log(ixLen);
+        if (!c->dictIdxDev.ensure(sizeof(u32) << log)) return ZERR(kErrMemoryAllocation);
+        launch_dict_index(end - ixLen, ixLen, (u32*)c->dictIdxDev.p, log, s);
+        if (isErr(stream_wait(s))) return ZERR(kErrGeneric);
+        c->dictIdxEnd = end; c->dictIdxLen = ixLen; c->dictIdxLog = log;
+    }
     c->dictDirty = false;
     return 0;
 }
@@ -182,6 +216,7 @@ static const DictCTables* call_dict_ctables(const ZSTD_CCtx* c, const CallParams
 // bytes of dictionary in front of every chunk, bytes per block, blocks per frame (0 = every block a frame of its own), and what
 // the level resolves to for it.
 struct Framing { u32 prefixLen, chunkBytes, frameBlocks; Resolved rs; u32 indepWindowLog = 0; bool ldm = false; LdmLaunch ldmP = {};
+                 bool dictIndex = false;    // full 64 KiB chunks, each a frame, behind the indexed dictionary (ZSTDMI_CCtx_setDictIndex)
                  bool single = false; u32 singleWindowLog = 0;      // ONE frame across passes; the window its header declares beside (or instead of) the content size, 0 = a single segment
 
                  size_t span() const { return (size_t)chunkBytes * (frameBlocks ? frameBlocks : 1u); } };
@@ -269,6 +304,12 @@ static Framing resolve_framing(const ZSTD_CCtx* c, const CallParams& cp, size_t 
         f.chunkBytes = chunkBytes; f.frameBlocks = frameBlocks; f.rs = rf;
         return f;
     }
+    // An indexed dictionary at the fast strategy: nothing of it is staged, so a chunk is a whole 64 KiB block and every chunk a
+    // single-segment frame behind the dictionary (ZSTD_c_windowLog 10 .. 15 keeps its own framing: a window below the block)
+    if (cp.useDict && cp.dictIndex && dict_index_len(c) && !(cp.windowLog >= 10 && cp.windowLog < (int)kChunkLog)) {
+        const Resolved rx = resolve_call(cp, paramSize, kChunkSize);
+        if (rx.finder == 0) { Framing f; f.prefixLen = 0; f.chunkBytes = kChunkSize; f.frameBlocks = 0; f.rs = rx; f.dictIndex = true; return f; }
+    }
     const u32 prefixLen = cp.useDict ? dict_prefix_len(c, paramSize) : 0u;
     u32 chunkBytes = kChunkSize - round_tile(prefixLen);
     // ZSTD_c_windowLog 10 .. 15: independent frames of 1 << windowLog bytes (the reference cuts blocks at the window size and lets
@@ -327,7 +368,7 @@ static LaunchState launch_state(const ZSTD_CCtx* c, const CallParams& cp, const 
     const Resolved& rs = fr.rs;
     LaunchState L;
     L.lzFrameBlocks = fr.frameBlocks | (fr.indepWindowLog ? 0x80000000u : 0u);       // (independent blocks: no history between them)
-    L.regionParse = rs.minStrideLog == 0 && !(rs.finder == 0 && fr.frameBlocks && fr.chunkBytes >= kChunkSize) && c->parser == 0;   // (not the far-candidate finder)
+    L.regionParse = rs.minStrideLog == 0 && !(rs.finder == 0 && fr.frameBlocks && fr.chunkBytes >= kChunkSize) && !fr.dictIndex && c->parser == 0;   // (not the far-candidate finder)
     L.hcChains = L.regionParse && rs.finder >= 2;
     // attempts per position of the level >= 5 search: the reference's 1 << searchLog (U/ZstdLazy.cs:641-642), between 4 and 32; the
     // greedy and lazy strategies (levels 5-7) stop at 8 unless ZSTD_c_searchLog asks for more: measured on text, 32 attempts
@@ -385,6 +426,8 @@ static size_t compress_range(ZSTD_CCtx* c, const CallParams& cp, u8* d_dst, size
     const u32* const initReps = fmtDict ? c->info.rep : plainReps;
     const DictCTables* const dct = call_dict_ctables(c, cp);
     const u8* prefix = prefixLen ? (const u8*)c->dict.p + (c->dictHost.size() - prefixLen) : nullptr;
+    const DictIndexRef dixRef = { c->dictIdxEnd, c->dictIdxLen, (const u32*)c->dictIdxDev.p, c->dictIdxLog };
+    const DictIndexRef* const dix = fr.dictIndex ? &dixRef : nullptr;
     const u64 totalChunks = (srcSize + chunkBytes - 1) / chunkBytes;
     u32 passChunks = (u32)(totalChunks < c->passChunks ? totalChunks : c->passChunks);
     if (fr.ldm) { const u32 most = (u32)(((u64)1 << 31) / chunkBytes) / frameBlocks * frameBlocks; if (passChunks > most) passChunks = most; }    // (ldm.hip: u32 offsets in a pass)
@@ -403,7 +446,7 @@ static size_t compress_range(ZSTD_CCtx* c, const CallParams& cp, u8* d_dst, size
         const FramePlace* const pl = fr.single ? &place : nullptr;
         c->timer.begin(s);
         launch_lz(rs.finder, src, n, nChunks, seqs, lits, meta, prefix, prefixLen, chunkBytes, dictIdBytes | (withSize ? 0u : 0x100u) | (hdrWindow << 12), rs.minStrideLog, lzFrameBlocks, regionParse ? (u16*)c->cand.p : nullptr, hcChains ? (u16*)((u8*)c->cand.p + cand_plane_bytes(passChunks)) : nullptr,
-                  regionParse ? (u32*)((u8*)c->cand.p + cand_plane_bytes(passChunks) * (hcChains ? 2 : 1)) : nullptr, hcDepth, s, c->timer.hook(), (u32*)(total + 4), nullptr, nullptr, pl);      // (the claim counter: a word of `total`'s 64 bytes)
+                  regionParse ? (u32*)((u8*)c->cand.p + cand_plane_bytes(passChunks) * (hcChains ? 2 : 1)) : nullptr, hcDepth, s, c->timer.hook(), (u32*)(total + 4), nullptr, nullptr, pl, dix);      // (the claim counter: a word of `total`'s 64 bytes)
         if (fr.ldm) {       // long-distance matches into the finder's sequence store (ldm.hip); the splits are counted first to size the workspace
             const u64 span = (u64)frameBlocks * chunkBytes;
             // a referenced prefix: splits over prefix and source as one window in the virtual coordinate (ldm.hip), nL = its end
@@ -694,7 +737,7 @@ size_t ZSTD_freeCCtx(ZSTD_CCtx* c)
         (void)hipSetDevice(c->device);
         if (c->ownStream) (void)hipStreamSynchronize(c->ownStream);
         c->seqs.release(); c->lits.release(); c->meta.release(); c->tables.release(); c->slots.release(); c->cand.release(); c->probe.release();
-        c->gatherIn.release(); c->gatherOut.release(); c->batchStage.release(); c->batchTab.release(); c->ldmSmall.release(); c->ldmBig.release(); c->offsets.release(); c->total.release(); c->seekEntries.release(); c->seekSort.release(); c->stageSrc.release(); c->stageDst.release(); c->pfxStage.release(); c->sfXxh.release(); c->dict.release(); c->dictFullDev.release(); c->dictInfoDev.release(); c->dictCTabDev.release();
+        c->gatherIn.release(); c->gatherOut.release(); c->batchStage.release(); c->batchTab.release(); c->ldmSmall.release(); c->ldmBig.release(); c->offsets.release(); c->total.release(); c->seekEntries.release(); c->seekSort.release(); c->stageSrc.release(); c->stageDst.release(); c->pfxStage.release(); c->sfXxh.release(); c->dict.release(); c->dictWideDev.release(); c->dictIdxDev.release(); c->dictFullDev.release(); c->dictInfoDev.release(); c->dictCTabDev.release();
         c->timer.destroy();
         if (c->ownStream) (void)hipStreamDestroy(c->ownStream);
     }
@@ -803,7 +846,7 @@ static size_t ZSTD_CCtx_loadDictionary_impl(ZSTD_CCtx* c, const void* dict, size
     if (!c->sIn.empty() || c->sEnding) return ZERR(kErrStageWrong);        /* not in the middle of a streaming frame session, U/ZstdCompress.cs:1273 */
     c->dictGen++;
     c->pfx = nullptr; c->pfxSize = 0;       // (a pending prefix is cancelled: ZSTD_clearAllDicts)
-    c->dictFormatted = false; c->dictFull.clear();
+    c->dictFormatted = false; c->dictFull.clear(); c->dictWide.clear();
     if (dict == nullptr || dictSize == 0) { c->dictHost.clear(); c->dictDirty = true; return 0; }          /* "no dictionary" */
     if (dictSize > (size_t)1 << 30) return ZERR(kErrParameterUnsupported);
     u8 head[8] = {};
@@ -825,6 +868,13 @@ static size_t ZSTD_CCtx_loadDictionary_impl(ZSTD_CCtx* c, const void* dict, size
     if (dev) { if (hipMemcpy(h.data(), tail, h.size(), hipMemcpyDeviceToHost) != hipSuccess) return ZERR(kErrGeneric); }
     else memcpy(h.data(), tail, h.size());
     c->dictHost.swap(h);
+    if (dictSize >= 8) {        // what an index would cover (ZSTDMI_CCtx_setDictIndex, before or after this load)
+        std::vector<u8> wide(dictSize < dict_index_max() ? dictSize : dict_index_max());
+        const u8* from = (const u8*)dict + (dictSize - wide.size());
+        if (dev) { if (hipMemcpy(wide.data(), from, wide.size(), hipMemcpyDeviceToHost) != hipSuccess) return ZERR(kErrGeneric); }
+        else memcpy(wide.data(), from, wide.size());
+        c->dictWide.swap(wide);
+    }
     c->dictDirty = true;
     return 0;
 }
@@ -921,7 +971,7 @@ static size_t ZSTD_CCtx_refPrefix_impl(ZSTD_CCtx* c, const void* prefix, size_t 
     if (!c->sIn.empty() || c->sEnding) return ZERR(kErrStageWrong);
     if (prefix && prefixSize > (size_t)1 << 30) return ZERR(kErrParameterUnsupported);
     // ZSTD_clearAllDicts: a loaded dictionary and an earlier prefix are gone
-    c->dictGen++; c->dictFormatted = false; c->dictFull.clear(); c->dictHost.clear(); c->dictDirty = true;
+    c->dictGen++; c->dictFormatted = false; c->dictFull.clear(); c->dictHost.clear(); c->dictWide.clear(); c->dictDirty = true;
     c->pfx = nullptr; c->pfxSize = 0;
     if (prefix && prefixSize) { c->pfx = prefix; c->pfxSize = prefixSize; }
     return 0;
@@ -976,8 +1026,9 @@ static size_t compress_multi(ZSTD_CCtx* c, const CallParams& cp, void* dst, size
     for (ZSTD_CCtx* w : c->workers) {
         w->historyBytes = c->historyBytes; w->frameBytes = c->frameBytes; w->parser = c->parser; w->passChunks = c->passChunks; w->timer.enabled = c->timer.enabled;
         w->dictEntropy = c->dictEntropy;        // (before the dictionary: a worker builds the tables when it uploads its copy)
+        w->dictIndex = c->dictIndex;            // (and the index)
         if (w->dictGen != c->dictGen) {
-            w->dictHost = c->dictHost; w->dictFull = c->dictFull; w->dictFormatted = c->dictFormatted; w->info = c->info; w->dictDirty = true; w->dictGen = c->dictGen;
+            w->dictHost = c->dictHost; w->dictFull = c->dictFull; w->dictWide = c->dictWide; w->dictFormatted = c->dictFormatted; w->info = c->info; w->dictDirty = true; w->dictGen = c->dictGen;
         }
     }
     size_t err = 0;
@@ -1229,6 +1280,16 @@ size_t ZSTDMI_CCtx_setDictEntropy(ZSTD_CCtx* c, unsigned mode)
     c->dictEntropy = (int)mode;
     return 0;
 }
+// (no device is touched: a loaded dictionary is marked for another upload, which builds — or no longer builds — its index)
+size_t ZSTDMI_CCtx_setDictIndex(ZSTD_CCtx* c, unsigned mode)
+{
+    if (!c) return ZERR(kErrGeneric);
+    if (mode > 1) return ZERR(kErrParameterOutOfBound);
+    if (c->dictIndex != (int)mode && (c->dictFormatted || !c->dictWide.empty())) { c->dictDirty = true; c->dictGen++; }
+    c->dictIndex = (int)mode;
+    return 0;
+}
+long long ZSTDMI_debugDictIndexed(const ZSTD_CCtx* c) { return c ? (long long)dict_index_len(c) : -1; }
 size_t ZSTDMI_CCtx_setParser(ZSTD_CCtx* c, unsigned mode) { if (!c || mode > 1) return ZERR(kErrParameterOutOfBound); c->parser = mode; return 0; }
 size_t ZSTDMI_CCtx_setProfiling(ZSTD_CCtx* c, int en) { if (!c) return ZERR(kErrGeneric); c->timer.enabled = en != 0; return 0; }
 int ZSTDMI_CCtx_getStageTimes(const ZSTD_CCtx* c, float* ms, const char** names, int cap)
@@ -1353,7 +1414,7 @@ static size_t compress_entries(ZSTD_CCtx* c, const CallParams& cp, const u8* con
         outSizes[i] = 0;
         Group* g = nullptr;
         for (auto& x : groups)
-            if (x.fr.prefixLen == fr.prefixLen && x.fr.chunkBytes == fr.chunkBytes && x.fr.frameBlocks == fr.frameBlocks && !memcmp(&x.fr.rs, &fr.rs, sizeof(Resolved))) { g = &x; break; }
+            if (x.fr.prefixLen == fr.prefixLen && x.fr.chunkBytes == fr.chunkBytes && x.fr.frameBlocks == fr.frameBlocks && x.fr.dictIndex == fr.dictIndex && !memcmp(&x.fr.rs, &fr.rs, sizeof(Resolved))) { g = &x; break; }
         if (!g) { groups.push_back(Group{fr, {}}); g = &groups.back(); }
         g->members.push_back(i);
     }
@@ -1368,6 +1429,7 @@ static size_t compress_entries(ZSTD_CCtx* c, const CallParams& cp, const u8* con
         const u32 cb = g.fr.chunkBytes, prefixLen = g.fr.prefixLen, frameBlocks = g.fr.frameBlocks;
         const Resolved rs = g.fr.rs;
         const u8* prefix = prefixLen ? (const u8*)c->dict.p + (c->dictHost.size() - prefixLen) : nullptr;
+        const DictIndexRef dixRef = { c->dictIdxEnd, c->dictIdxLen, (const u32*)c->dictIdxDev.p, c->dictIdxLog };
         const LaunchState ls = launch_state(c, cp, g.fr);
         const bool regionParse = ls.regionParse, hcChains = ls.hcChains;
         const u32 hcDepth = ls.hcDepth, strategy = ls.strategy;
@@ -1427,7 +1489,7 @@ static size_t compress_entries(ZSTD_CCtx* c, const CallParams& cp, const u8* con
             launch_batch_stage((const u64*)dTab, dLen, (u8*)c->batchStage.p, nCh, cb, s);      c->timer.mark("batch_stage", s);
             launch_lz(rs.finder, stage, stagedBytes, nCh, seqs, lits, meta, prefix, prefixLen, cb, dictIdBytes | (cp.contentSizeFlag ? 0u : 0x100u), rs.minStrideLog, ls.lzFrameBlocks,
                       regionParse ? (u16*)c->cand.p : nullptr, hcChains ? (u16*)((u8*)c->cand.p + cand_plane_bytes(nCh)) : nullptr,
-                      regionParse ? (u32*)((u8*)c->cand.p + cand_plane_bytes(nCh) * (hcChains ? 2 : 1)) : nullptr, hcDepth, s, c->timer.hook(), (u32*)(total + 4), dLen, dFrame);
+                      regionParse ? (u32*)((u8*)c->cand.p + cand_plane_bytes(nCh) * (hcChains ? 2 : 1)) : nullptr, hcDepth, s, c->timer.hook(), (u32*)(total + 4), dLen, dFrame, nullptr, g.fr.dictIndex ? &dixRef : nullptr);
             launch_huf_build(lits, meta, tables, slots, nCh, rs.rawLiterals, stage, cb, s, c->timer.hook(), dct, 0);      // (dct: single-block frames only, see above)
             if (cp.checksumFlag) { launch_xxh64(stage, stagedBytes, meta, nCh, cb, frameBlocks, s, dLen, dFrame);        c->timer.mark("xxh64", s); }
             launch_seq_encode(seqs, meta, slots, nCh, strategy, (cp.checksumFlag ? 1u : 0u) | (cp.contentSizeFlag ? 0u : 2u), 1, dictID, dictIdBytes, initReps, frameBlocks, cb, stagedBytes, s, dct, dFrame);
