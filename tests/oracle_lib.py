@@ -44,6 +44,9 @@ def lib():
         o.zso_entropy_block.argtypes = [vp, sz, ctypes.POINTER(ZsoSeq), sz, vp, sz, ctypes.c_uint32, sz]
         o.zso_huf_buildLengths.restype = sz
         o.zso_huf_buildLengths.argtypes = [vp, ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint32, ctypes.c_uint32]
+        o.zso_huf_readStats.restype = sz
+        o.zso_huf_readStats.argtypes = [vp, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32), vp, sz]
+        o.zso_decompressBound.restype = ctypes.c_uint64
         _lib = o
     return _lib
 

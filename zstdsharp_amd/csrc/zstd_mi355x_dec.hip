@@ -135,7 +135,8 @@ static size_t ZSTD_DCtx_loadDictionary_impl(ZSTD_DCtx* d, const void* dict, size
 static size_t host_frame_size_info(const u8* src, size_t srcSize, unsigned long long* bound)
 {
     auto rd32 = [](const u8* p) { return (u32)p[0] | ((u32)p[1] << 8) | ((u32)p[2] << 16) | ((u32)p[3] << 24); };
-    if (srcSize >= 8 && (rd32(src) & 0xFFFFFFF0u) == 0x184D2A50u) {
+    if (srcSize >= 4 && (rd32(src) & 0xFFFFFFF0u) == 0x184D2A50u) {
+        if (srcSize < 8) return ZERR(kErrSrcSizeWrong);         // a skippable frame's header that is still arriving: wait, as for a zstd frame's
         const u64 sz = (u64)rd32(src + 4) + 8;
         if (sz > srcSize) return ZERR(kErrSrcSizeWrong);
         *bound = 0; return (size_t)sz;
