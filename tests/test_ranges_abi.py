@@ -4,13 +4,13 @@ built with a stand-alone main under AddressSanitizer and UBSan and run over an e
 and 1000 seeded runs.  No kernel is launched here."""
 import ctypes
 import os
-import shutil
 import subprocess
 
 import pytest
 
 import zstdsharp_amd as z
 from zstdsharp_amd import _ffi
+from host_cc import host_compiler
 from zstdsharp_amd.errors import ZSTD_ErrorCode, get_error_code, is_error
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -73,17 +73,6 @@ def test_null_context_and_null_arrays():
         r = lib.ZSTDMI_decompressRanges(d.dctx, blob, len(blob), a[0], a[1], 1, a[2], a[3], a[4])
         assert is_error(r) and get_error_code(r) == GENERIC, hole
     d.Dispose()
-
-
-def host_compiler():
-    """a host C++ compiler: g++ where there is one, else the clang++ behind the hipcc that builds the library (HIPCC as build() reads it).
-    The library cannot be built without the latter, so none at all is an error of the machine, not a reason to skip."""
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    rocm_clang = os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(hipcc))), "llvm", "bin", "clang++")
-    for cxx in (shutil.which("g++"), shutil.which("clang++"), rocm_clang if os.path.exists(rocm_clang) else None, "/opt/rocm/llvm/bin/clang++"):
-        if cxx and os.path.exists(cxx):
-            return cxx
-    pytest.fail("no host C++ compiler: neither g++ nor the clang++ that hipcc drives")
 
 
 def test_run_packing_under_sanitizers(tmp_path):

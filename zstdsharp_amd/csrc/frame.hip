@@ -101,17 +101,16 @@ __global__ __launch_bounds__(256) void batch_place_kernel(const ChunkMeta* __res
 // ---- seek table (ZSTDMI_CCtx_setSeekTable; the zstd seekable format) ----
 // entries: one (compressed size, content size) pair per frame of the pass, from the scan's offsets.  A frame is frameBlocks chunks
 // (the pass's last one may be shorter); the sizes are below 2^32 by construction (a frame holds at most 512 MiB of content).
-__global__ __launch_bounds__(256) void seek_entries_kernel(const u64* __restrict__ offsets, const u64* __restrict__ total, u32 nChunks, u32 frameBlocks,
-                                                           u32 chunkBytes, u64 passBytes, u32* __restrict__ entries)
+__global__ __launch_bounds__(256) void seek_entries_kernel(const u64* __restrict__ offsets, const u64* __restrict__ total, u32 nChunks, const FrameLayout frames,
+                                                           u32* __restrict__ entries)
 {
     const u32 f = blockIdx.x * 256 + threadIdx.x;
-    const u32 nFrames = (nChunks + frameBlocks - 1) / frameBlocks;
+    const u32 nFrames = (nChunks + frames.frameBlocks - 1) / frames.frameBlocks;
     if (f >= nFrames) return;
-    const u64 first = (u64)f * frameBlocks, next = first + frameBlocks;
+    const u64 first = (u64)f * frames.frameBlocks, next = first + frames.frameBlocks;
     const u64 cEnd = next < nChunks ? offsets[next] : *total;
-    const u64 span = (u64)frameBlocks * chunkBytes, at = (u64)f * span;
     entries[2 * (u64)f] = (u32)(cEnd - offsets[first]);
-    entries[2 * (u64)f + 1] = (u32)((passBytes - at) < span ? (passBytes - at) : span);
+    entries[2 * (u64)f + 1] = (u32)block_place<kArith>(frames, (u32)first).frameLen;
 }
 
 // table: skippable header | n entries of 8 bytes | footer, one byte per lane (dst has no alignment to speak of)
@@ -138,24 +137,23 @@ __device__ __forceinline__ u64 rotl64(u64 x, int r) { return (x << r) | (x >> (6
 __device__ __forceinline__ u64 xxh_round(u64 acc, u64 in) { acc += in * P2; acc = rotl64(acc, 31); return acc * P1; }
 __device__ __forceinline__ u64 xxh_merge(u64 acc, u64 v) { acc ^= xxh_round(0, v); return acc * P1 + P4; }
 
-// (one frame = frameBlocks chunks of chunkBytes; the checksum is filed with the frame's last block, which carries it)
+// (frames, zmi_frame.h: the frame's bytes lie in one piece from its first chunk on; the checksum is filed with the frame's last block,
+// which carries it.  frames.frameBlocks >= 1.)
 // chunkLens (optional; single-block frames only): chunk c holds chunkLens[c] bytes at c * chunkBytes (a batch of independent inputs)
-// chunkFrames (optional; a batch's multi-block frames, see lz_kernel): one group of 4 lanes per CHUNK; the group of a frame's first
-// block (bits 24-31 zero) hashes the frame's bits 0-23 bytes, which lie in one piece from that chunk on, the others leave
-__global__ __launch_bounds__(256) void xxh64_kernel(const u8* __restrict__ src, u64 srcSize, ChunkMeta* __restrict__ meta, u32 nChunks, u32 chunkBytes,
-                                                    u32 frameBlocks, const u32* __restrict__ chunkLens, const u32* __restrict__ chunkFrames)
+// The table form (a batch's multi-block frames, see lz_kernel): one group of 4 lanes per CHUNK, of which the groups of the frames'
+// first blocks hash and the others leave; else one group per frame.
+__global__ __launch_bounds__(256) void xxh64_kernel(const u8* __restrict__ src, ChunkMeta* __restrict__ meta, u32 nChunks, const FrameLayout frames,
+                                                    const u32* __restrict__ chunkLens)
 {
     const u32 t = blockIdx.x * 256 + threadIdx.x;
     const u32 f = t >> 2, j = t & 3;
-    if (chunkFrames) frameBlocks = 1;                      // (f counts chunks)
-    if ((u64)f * frameBlocks >= nChunks) return;           // whole groups of 4 lanes leave together
-    const u32 place = chunkFrames ? chunkFrames[f] : 0u;
-    if (place >> 24) return;
-    const u64 frameBytes = (u64)frameBlocks * chunkBytes;
-    const u64 base = (u64)f * frameBytes;
-    const u32 n = chunkFrames ? (place & 0xFFFFFFu) : chunkLens ? chunkLens[f] : (u32)((srcSize - base) < frameBytes ? (srcSize - base) : frameBytes);
-    const u32 c = chunkFrames ? f + (n - 1) / chunkBytes : (f + 1) * frameBlocks <= nChunks ? (f + 1) * frameBlocks - 1 : nChunks - 1;
-    const u8* p = src + base;
+    const u64 first = frames.form == kTable ? (u64)f : (u64)f * frames.frameBlocks;     // the chunk this group looks at
+    if (first >= nChunks) return;                          // whole groups of 4 lanes leave together
+    const BlockPlace at = frames.form == kTable ? block_place<kTable>(frames, (u32)first) : block_place<kArith>(frames, (u32)first);
+    if (at.block) return;
+    const u32 n = chunkLens ? chunkLens[f] : (u32)at.frameLen;
+    const u32 c = (u32)first + (n ? (n - 1) / frames.chunkBytes : 0u);        // the frame's last block
+    const u8* p = src + first * frames.chunkBytes;
     u64 h;
     const u32 stripes = n >> 5;
     u64 v = j == 0 ? P1 + P2 : j == 1 ? P2 : j == 2 ? 0 : 0 - P1;
@@ -255,13 +253,15 @@ void launch_gather(const u8* src, u64 srcSize, const u8* slots, const ChunkMeta*
 {
     hipLaunchKernelGGL(gather_kernel, dim3(nChunks), dim3(256), 0, stream, src, srcSize, slots, meta, offsets, dst, dstCapacity, chunkBytes);
 }
-void launch_xxh64(const u8* src, u64 srcSize, ChunkMeta* meta, u32 nChunks, u32 chunkBytes, u32 frameBlocks, hipStream_t stream, const u32* chunkLens,
-                  const u32* chunkFrames)
+void launch_xxh64(const u8* src, ChunkMeta* meta, u32 nChunks, const FrameLayout& frames, hipStream_t stream, const u32* chunkLens)
 {
-    if (!frameBlocks) frameBlocks = 1;
-    if (frameBlocks != 1) chunkLens = nullptr; else chunkFrames = nullptr;
-    const u32 nFrames = chunkFrames ? nChunks : (nChunks + frameBlocks - 1) / frameBlocks;
-    hipLaunchKernelGGL(xxh64_kernel, dim3((nFrames * 4 + 255) / 256), dim3(256), 0, stream, src, srcSize, meta, nChunks, chunkBytes, frameBlocks, chunkLens, chunkFrames);
+    assert(frames.form != kSingle);                         // (one frame across passes: launch_stream_xxh)
+    FrameLayout g = frames;
+    if (!g.frameBlocks) g.frameBlocks = 1;
+    assert(g.form == kArith || g.frameBlocks > 1);          // (the table states multi-block frames only)
+    if (g.frameBlocks != 1) chunkLens = nullptr;
+    const u32 nFrames = g.form == kTable ? nChunks : (nChunks + g.frameBlocks - 1) / g.frameBlocks;
+    hipLaunchKernelGGL(xxh64_kernel, dim3((nFrames * 4 + 255) / 256), dim3(256), 0, stream, src, meta, nChunks, g, chunkLens);
 }
 void launch_stream_xxh(XxhCarry* st, const u8* data, u64 n, u32 final, hipStream_t stream)
 {
@@ -271,11 +271,13 @@ void launch_xxh_carry_file(const XxhCarry* st, ChunkMeta* chunk, hipStream_t str
 {
     hipLaunchKernelGGL(xxh_carry_file_kernel, dim3(1), dim3(64), 0, stream, st, chunk);
 }
-void launch_seek_entries(const u64* offsets, const u64* total, u32 nChunks, u32 frameBlocks, u32 chunkBytes, u64 passBytes, u32* entries, hipStream_t stream)
+void launch_seek_entries(const u64* offsets, const u64* total, u32 nChunks, const FrameLayout& frames, u32* entries, hipStream_t stream)
 {
-    if (!frameBlocks) frameBlocks = 1;
-    const u32 nFrames = (nChunks + frameBlocks - 1) / frameBlocks;
-    hipLaunchKernelGGL(seek_entries_kernel, dim3((nFrames + 255) / 256), dim3(256), 0, stream, offsets, total, nChunks, frameBlocks, chunkBytes, passBytes, entries);
+    assert(frames.form == kArith);
+    FrameLayout g = frames;
+    if (!g.frameBlocks) g.frameBlocks = 1;
+    const u32 nFrames = (nChunks + g.frameBlocks - 1) / g.frameBlocks;
+    hipLaunchKernelGGL(seek_entries_kernel, dim3((nFrames + 255) / 256), dim3(256), 0, stream, offsets, total, nChunks, g, entries);
 }
 void launch_seek_table(const u32* entries, u32 n, u8* dst, hipStream_t stream)
 {

@@ -491,7 +491,7 @@ __global__ __launch_bounds__(64) void huf_tree_kernel(ChunkMeta* __restrict__ me
 #endif
     // the dictionary's table stands behind a frame's first block only (a later block never writes a treeless section)
     u32 dMode = kDictHufNone;
-    if (DICT) { if ((frameBlocks ? c % frameBlocks : 0u) == 0) dMode = dct->hufMode; }
+    if (DICT) { if (!frameBlocks || block_index(c, frameBlocks) == 0) dMode = dct->hufMode; }
     // ZSTD_compressLiterals: <= 63 literals are stored raw (no previous table in a one-block frame)
     if (litSize <= ((DICT && dMode == kDictHufValid) ? 6u : 63u) || rawLiterals) {        // (or ZSTD_noCompressLiterals because literal compression is disabled, U/ZstdCompressLiterals.cs:99-101)
         if (tid == 0) store_section(kLitRaw, lhSizeRaw, lhSizeRaw + litSize);
@@ -960,10 +960,13 @@ __global__ __launch_bounds__(256) void huf_encode_kernel(const u8* __restrict__ 
     }
 }
 
-// dct != nullptr: the first block of every frame (frameBlocks as in seq_encode: 0 = every chunk a frame) may reuse the dictionary's table
-void launch_huf_build(const u8* lits, ChunkMeta* meta, HufTable* tables, u8* slots, u32 nChunks, u32 rawLiterals, const u8* src, u32 chunkBytes,
-                      hipStream_t stream, StageHook hook, const DictCTables* dct, u32 frameBlocks)
+// dct != nullptr: the first block of every frame (frames as in seq_encode) may reuse the dictionary's table; a dictionary's framing
+// counts the blocks of a frame by the chunk's index
+void launch_huf_build(const u8* lits, ChunkMeta* meta, HufTable* tables, u8* slots, u32 nChunks, u32 rawLiterals, const u8* src, const FrameLayout& frames,
+                      hipStream_t stream, StageHook hook, const DictCTables* dct)
 {
+    assert(!dct || frames.form == kArith);
+    const u32 chunkBytes = frames.chunkBytes, frameBlocks = frames.frameBlocks;
     // a throughput kernel: a wave per (chunk, stream) item while that keeps every CU's share short, several items per wave beyond
     const u32 nItems = 4 * nChunks, perWave = (nItems + kHistItemsPerWave - 1) / kHistItemsPerWave;
     const u32 grid = nItems <= kHistMinGrid ? nItems : (perWave > kHistMinGrid ? perWave : kHistMinGrid);

@@ -846,11 +846,13 @@ __device__ __forceinline__ void dense_rest(LzLds& L, const u32 n, const u32 inse
 // candidates + one-step lazy deferral; levels >= 5: the place of U/ZstdLazy.cs:1743-2032).  The host maps strategy -> MODE.
 // DICT: a dictionary prefix is present (its bounds checks fold away otherwise)
 // FAR: matches may start in the input in front of the block (same frame): those candidates are verified against global memory
-// TAB: a block's place in its frame comes from a table (chunkFrames: a batch of entries of different lengths).  A template parameter
-// because these kernels sit at the register cap: as a run-time branch the pointer and the select added scratch to the instances
-// every single call of the levels >= 3 runs; without TAB the code is that of a kernel without the table.
-// TAB == 2: the call's input is ONE frame that passes (and a stream's batches) cut anywhere (ZSTDMI_CCtx_setSingleFrame):
-// frameAt = bytes of the frame in front of src, all of them readable there as history; frameTotal = the frame's content size.
+// TAB: the form in which a block's place in its frame is stated (zmi_frame.h, block_place): 0 = from the chunk's index and the call's
+// size, 1 = from a table (chunkFrames: a batch of entries of different lengths), 2 = in bytes (frameAt / frameTotal: the call's input
+// is ONE frame that passes and a stream's batches cut anywhere, ZSTDMI_CCtx_setSingleFrame; the frameAt bytes in front
+// of src are readable there as history).  A template parameter because these kernels sit at the register cap: as a run-time branch
+// the pointer and the select added scratch to the instances every single call of the levels >= 3 runs; an instance
+// holds the code of its own form alone.
+// fh: the frame header (zmi_frame.h), of which the finder needs the size: it leaves in ChunkMeta::fhSize what seq_encode_kernel will write.
 // TAB == 3 (on the FAR instance of the fast finder): every chunk is a frame of its own behind an INDEXED dictionary
 // (ZSTDMI_CCtx_setDictIndex).  The chunk alone sits in LDS; what lies "in front of the block" is the dictionary's
 // content, whose candidates come from one gather per probed position out of the index in global memory.  The arguments an instance
@@ -861,7 +863,7 @@ __global__ __launch_bounds__(1024) void lz_kernel(const u8* __restrict__ src, u6
                                                   Seq* __restrict__ seqs, u8* __restrict__ lits,
                                                   ChunkMeta* __restrict__ meta,
                                                   const u8* __restrict__ prefixArg, const u32 prefixLenArg, const u32 chunkBytes,
-                                                  const u32 fhExtra, const u32 minStrideLog, const u32 frameBlocksArg, u16* __restrict__ candAll, u16* __restrict__ chainAll, u32* __restrict__ regionList, const u32 nChunks,
+                                                  const FrameHeaderSpec fh, const u32 minStrideLog, const u32 frameBlocksArg, u16* __restrict__ candAll, u16* __restrict__ chainAll, u32* __restrict__ regionList, const u32 nChunks,
                                                   u32* __restrict__ claimCtr, const u32* __restrict__ chunkLens, const u32* __restrict__ chunkFrames,
                                                   const u64 frameAt, const u64 frameTotal)
 {
@@ -875,6 +877,7 @@ __global__ __launch_bounds__(1024) void lz_kernel(const u8* __restrict__ src, u6
     // workgroup's first arrives prefetched (a stamped build had 42 % of an unprefetched Zipf chunk's time in this load).  The claim
     // is made one chunk ahead of the prefetch (thread 0 holds the answer in a register through a chunk), so nobody waits for it.
     constexpr bool kPrefetch = MODE == 0 && !DICT && !FAR;      // (the dual-hash finders have no 16 registers to spare)
+    constexpr int kPlaceForm = TAB == 1 ? kTable : TAB == 2 ? kSingle : kArith;
     uint4 pf0 = {0, 0, 0, 0}, pf1 = pf0, pf2 = pf0, pf3 = pf0; bool pfValid = false;
     const bool claiming = kPrefetch && claimCtr != nullptr;     // uniform
     u32 claimed = 0;                                            // thread 0: the chunk after the next
@@ -897,17 +900,19 @@ __global__ __launch_bounds__(1024) void lz_kernel(const u8* __restrict__ src, u6
     const u8* __restrict__ const farEnd = TAB == 3 ? prefixArg : in;
     const u32* __restrict__ const dictIdx = TAB == 3 ? reinterpret_cast<const u32*>(chainAll) : nullptr;
     const u32 dictLog = TAB == 3 ? (u32)frameAt : 0u;
-    // (frameBlocksArg bit 31: the frame's blocks are independent of each other — windows below 64 KiB, where a block IS the window:
-    //  no history; a dictionary is history of the frame's first block only, whose image is the layout the decoder sees)
-    const u32 frameBlocks = frameBlocksArg & 0x7FFFFFFFu;
-    const bool indep = (frameBlocksArg >> 31) != 0;
-    // chunkFrames (optional, beside chunkLens; blocks behind LDS history only): a batch's entries differ in length, so a chunk's place
-    // comes from a table instead of the call's size: bits 24-31 the block index inside its frame, bits 0-23 the frame's content size
-    // (TAB == 2: only whether the block is its frame's first; what lies in front of it is counted in bytes)
-    const u32 bf = ((DICT || FAR) && frameBlocks) ? (TAB == 1 ? chunkFrames[c] >> 24 : TAB == 2 ? (frameAt + base != 0 ? 1u : 0u) : c % frameBlocks) : 0u;               // block index inside its frame
-    const u32 farAvail = FAR ? TAB == 3 ? prefixLenArg : (TAB == 2 ? (frameAt + base < kFarMax ? (u32)(frameAt + base) : kFarMax) : (u64)bf * cb < kFarMax ? bf * cb : kFarMax) : 0u;      // bytes of far history in front of the block
+    // (independent blocks — windows below 64 KiB, where a block IS the window: no history; a dictionary is history of the frame's
+    //  first block only, whose image is the layout the decoder sees)
+    const u32 frameBlocks = frame_blocks_decode(frameBlocksArg).frameBlocks;
+    const bool indep = frame_blocks_decode(frameBlocksArg).independent;
+    // the block's place in its frame (zmi_frame.h: from the call's size, from a batch's table beside chunkLens, or — one frame across
+    // passes — counted in bytes); a chunk that is a frame of its own, and every chunk behind an indexed dictionary, has none
+    const bool framed = (DICT || FAR) && frameBlocks;
+    const FrameLayout frames = { kPlaceForm, cb, frameBlocks, srcSize, chunkFrames, frameAt, frameTotal };
+    const BlockPlace place = framed ? block_place<kPlaceForm>(frames, c) : block_alone(0);
+    const u32 bf = place.block;
+    const u32 farAvail = FAR ? TAB == 3 ? prefixLenArg : place.front < kFarMax ? (u32)place.front : kFarMax : 0u;      // bytes of far history in front of the block
     u32 prefixLen = prefixLenArg; const u8* __restrict__ prefix = prefixArg;
-    if (DICT && frameBlocks && !indep) { const u64 back = TAB == 2 ? frameAt + base : (u64)bf * cb; prefixLen = back < hist ? (u32)back : hist; prefix = in - prefixLen; }
+    if (DICT && frameBlocks && !indep) { prefixLen = place.front < hist ? (u32)place.front : hist; prefix = in - prefixLen; }
     if (DICT && indep && bf) prefixLen = 0;
     const u32 lowLimit = DICT ? hist - prefixLen : 0u;
     // chunkLens (optional): chunk c holds chunkLens[c] <= cb bytes at c * cb (a batch of independent inputs, each staged at a
@@ -1594,12 +1599,10 @@ __global__ __launch_bounds__(1024) void lz_kernel(const u8* __restrict__ src, u6
     if (tid == 0) {
         ChunkMeta m = {};
         m.srcSize = nData; m.nbSeq = nbSeq; m.litSize = litBase;
-        if ((DICT || FAR) && frameBlocks) {   // only a frame's first block carries the frame header, sized for the whole frame's content
-            const u64 fStart = base - (u64)bf * cb, fMax = (u64)frameBlocks * cb;
-            const u64 fLen = TAB == 1 ? (u64)(chunkFrames[c] & 0xFFFFFFu) : TAB == 2 ? frameTotal : (srcSize - fStart) < fMax ? (srcSize - fStart) : fMax;
-            const u32 fcsField = fLen < 256 ? 0u : fLen < 65536 + 256 ? 2u : fLen <= 0xFFFFFFFFull ? 4u : 8u;       // (behind a window descriptor)
-            m.fhSize = bf == 0 ? ((fhExtra >> 12) ? 6u + ((fhExtra & 0x100u) ? 0u : fcsField) : (fhExtra & 0x100u) ? 6u : frame_header_size64(fLen)) + (fhExtra & 7u) : 0u;
-        } else m.fhSize = ((fhExtra & 0x100u) ? 6u : frame_header_size(nData)) + (fhExtra & 7u);      // fhExtra: bits 0-2 bytes of the dictID field (formatted dictionary); bit 8: window descriptor instead of a content size (magic, descriptor, window byte); bits 12-16: an explicit windowLog (multi-block frames only: descriptor AND content size)
+        // only a frame's first block carries the frame header, sized for the whole frame's content (worked out here, behind the
+        // parse, so that the frame's length does not live through it)
+        if (framed) m.fhSize = bf == 0 ? frame_header_bytes(fh, block_place<kPlaceForm>(frames, c).frameLen) : 0u;
+        else m.fhSize = frame_header_bytes(fh, nData);
         m.litFromSrc = deferred ? 1u : 0u;       // (then nbSeq = 0 and litBase = nData: the literals are the chunk itself)
         m.regionCursor = regionCursor;
         meta[c] = m;
@@ -1621,8 +1624,8 @@ __global__ __launch_bounds__(1024) void lz_region_kernel(const u8* __restrict__ 
                                                          const u8* __restrict__ prefixArg, const u32 prefixLenArg, const u32 chunkBytes, const u32 frameBlocksArg, const u32 hcDepth,
                                                          const u32* __restrict__ chunkLens, const u32* __restrict__ chunkFrames, const u64 frameAt)
 {
-    const u32 frameBlocks = frameBlocksArg & 0x7FFFFFFFu;
-    const bool indep = (frameBlocksArg >> 31) != 0;
+    const u32 frameBlocks = frame_blocks_decode(frameBlocksArg).frameBlocks;
+    const bool indep = frame_blocks_decode(frameBlocksArg).independent;
     extern __shared__ __attribute__((aligned(16))) u8 ldsRaw[];
     LzLds& L = *reinterpret_cast<LzLds*>(ldsRaw);
     const u32 tid = threadIdx.x, lane = lane_id(), wave = uniform(wave_id());
@@ -1636,10 +1639,13 @@ __global__ __launch_bounds__(1024) void lz_region_kernel(const u8* __restrict__ 
     const u32 hist = DICT ? kChunkSize - ((chunkBytes + kTilePos - 1) & ~(kTilePos - 1)) : 0u;
     const u64 base = (u64)c * cb;
     const u8* __restrict__ in = src + base;
-    const u32 bf = (DICT && frameBlocks) ? (TAB == 1 ? chunkFrames[c] >> 24 : TAB == 2 ? 0u : c % frameBlocks) : 0u;
+    // (srcSize, frameTotal: the frame's length is not asked for here.  The block index is read for independent blocks only, which
+    //  the single-frame form never has: that it is "first or not" there, where this kernel once took 0, changes nothing)
+    const FrameLayout frames = { TAB, cb, frameBlocks, srcSize, chunkFrames, frameAt, 0 };
+    const BlockPlace place = (DICT && frameBlocks) ? block_place<TAB>(frames, c) : block_alone(0);
     u32 prefixLen = prefixLenArg; const u8* __restrict__ prefix = prefixArg;
-    if (DICT && frameBlocks && !indep) { const u64 back = TAB == 2 ? frameAt + base : (u64)bf * cb; prefixLen = back < hist ? (u32)back : hist; prefix = in - prefixLen; }
-    if (DICT && indep && bf) prefixLen = 0;
+    if (DICT && frameBlocks && !indep) { prefixLen = place.front < hist ? (u32)place.front : hist; prefix = in - prefixLen; }
+    if (DICT && indep && place.block) prefixLen = 0;
     const u32 lowLimit = DICT ? hist - prefixLen : 0u;
     const u32 nData = chunkLens ? chunkLens[c] : (u32)((srcSize - base) < cb ? (srcSize - base) : cb);
     const u32 n = hist + nData;
@@ -1769,9 +1775,7 @@ extern "C" void ZSTDMI_debugReadLzStamps(unsigned long long* out16, int reset)
 #endif
 
 template <int MODE, int SHORT, bool DICT, bool FAR = false, int TAB = 0>
-static void launch_one(const u8* src, u64 srcSize, u32 nChunks, Seq* seqs, u8* lits, ChunkMeta* meta, const u8* prefix, u32 prefixLen,
-                       u32 chunkBytes, u32 fhExtra, u32 minStrideLog, u32 frameBlocks, u16* cand, u16* chain, u32* regionList, u32 hcDepth, hipStream_t stream, StageHook hook, u32* claimCtr,
-                       const u32* chunkLens, const u32* chunkFrames, u64 frameAt = 0, u64 frameTotal = 0)
+static void launch_one(const LzLaunch& a)
 {
     // the region parse of dense chunks: a second kernel behind a work list (see lz_region_kernel), inlined for the others
     constexpr bool kSplit = (MODE == 0 && !DICT && !FAR) || MODE == 2;
@@ -1783,82 +1787,69 @@ static void launch_one(const u8* src, u64 srcSize, u32 nChunks, Seq* seqs, u8* l
         if constexpr (kSplit) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(lz_region_kernel<MODE, DICT, TAB>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(LzLds));
         attrSet[dev & 63] = true;
     }
-    if (FAR) cand = nullptr;
-    if (cand && kSplit) (void)hipMemsetAsync(regionList, 0, sizeof(u32), stream);
+    // (the full 64 KiB blocks with far candidates have no region parse, no per-chunk tables and nothing staged in front of them)
+    assert(!FAR || TAB == 3 || (!a.chunkLens && !a.prefixLen));
+    u16* const cand = FAR ? nullptr : a.cand;
+    const u32 chunkBytes = DICT ? a.frames.chunkBytes : kChunkSize;
+    const u32 frameBlocks = frame_blocks_encode((DICT || FAR) ? a.frames.frameBlocks : 0u, a.independent);
+    if (cand && kSplit) (void)hipMemsetAsync(a.regionList, 0, sizeof(u32), a.stream);
     // the fast finder on plain chunks, more chunks than CUs: one workgroup per CU, chunks claimed from a counter (see lz_kernel)
     static u32 cuCount[64] = {};
     if (!cuCount[dev & 63]) { int n = 0; (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev); cuCount[dev & 63] = n > 0 ? (u32)n : 256u; }
-    const bool claim = MODE == 0 && !DICT && !FAR && claimCtr && nChunks > cuCount[dev & 63];
-    if (claim) (void)hipMemsetAsync(claimCtr, 0, sizeof(u32), stream);
-    const u32 grid = claim ? cuCount[dev & 63] : nChunks;
-    hipLaunchKernelGGL((lz_kernel<MODE, SHORT, DICT, FAR, TAB>), dim3(grid), dim3(kTile), sizeof(LzLds), stream, src, srcSize, seqs, lits, meta, prefix, prefixLen, chunkBytes, fhExtra, minStrideLog, frameBlocks, cand, (cand || TAB == 3) ? chain : nullptr, cand ? regionList : nullptr, nChunks,
-                       claim ? claimCtr : nullptr, chunkLens, chunkFrames, frameAt, frameTotal);
-    hook("lz_fast");
+    const bool claim = MODE == 0 && !DICT && !FAR && a.claimCtr && a.nChunks > cuCount[dev & 63];
+    if (claim) (void)hipMemsetAsync(a.claimCtr, 0, sizeof(u32), a.stream);
+    const u32 grid = claim ? cuCount[dev & 63] : a.nChunks;
+    hipLaunchKernelGGL((lz_kernel<MODE, SHORT, DICT, FAR, TAB>), dim3(grid), dim3(kTile), sizeof(LzLds), a.stream, a.src, a.srcSize, a.seqs, a.lits, a.meta, a.prefix, a.prefixLen, chunkBytes, a.header,
+                       a.minStrideLog, frameBlocks, cand, (cand || TAB == 3) ? a.chain : nullptr, cand ? a.regionList : nullptr, a.nChunks,
+                       claim ? a.claimCtr : nullptr, a.chunkLens, a.frames.table, a.frames.at, a.frames.total);
+    a.hook("lz_fast");
     if constexpr (kSplit) if (cand) {                      // the dense chunks' rest: 256 workgroups (one per CU) walk the list
-        hipLaunchKernelGGL((lz_region_kernel<MODE, DICT, TAB>), dim3(nChunks < 256 ? nChunks : 256), dim3(kTile), sizeof(LzLds), stream, src, srcSize, seqs, lits, meta, cand, chain, regionList,
-                           prefix, prefixLen, chunkBytes, frameBlocks, hcDepth, chunkLens, chunkFrames, frameAt);
-        hook("lz_region");
+        hipLaunchKernelGGL((lz_region_kernel<MODE, DICT, TAB>), dim3(a.nChunks < 256 ? a.nChunks : 256), dim3(kTile), sizeof(LzLds), a.stream, a.src, a.srcSize, a.seqs, a.lits, a.meta, cand, a.chain, a.regionList,
+                           a.prefix, a.prefixLen, chunkBytes, frameBlocks, a.hcDepth, a.chunkLens, a.frames.table, a.frames.at);
+        a.hook("lz_region");
     }
 }
 
-// finder: 0 = fast, 1 = dual (8-byte + 5-byte hashes), 2 = dual + lazy deferral.  (A 4-byte short hash, the reference's
-// minMatch at levels 4+, was measured and lost ratio on every corpus tried: far 4-byte matches cost more than literals.)
-// prefix/prefixLen: the dictionary bytes every chunk sees as history (null/0 without one); chunkBytes = 64 KiB minus prefixLen
-// rounded up to whole 4 KiB tiles.  frameBlocks > 0: cross-chunk history instead (no dictionary): `frameBlocks` chunks of chunkBytes
-// form one frame and each sees up to 64 KiB - chunkBytes of the input in front of it.  chunkBytes < 64 KiB with neither: independent
-// frames of chunkBytes each (ZSTD_c_windowLog 10 .. 15: a frame is its own window), on the same instantiation with an empty history.
-// cand / regionList (null: off): workspace of the region parse, 65536 u16 per chunk and 1 + nChunks u32.
-// dix (null: off): an indexed dictionary behind full 64 KiB chunks, each a frame of its own (fast finder only; chunkLens allowed).
-void launch_lz(u32 finder, const u8* src, u64 srcSize, u32 nChunks, Seq* seqs, u8* lits, ChunkMeta* meta, const u8* prefix, u32 prefixLen,
-               u32 chunkBytes, u32 fhExtra, u32 minStrideLog, u32 frameBlocks, u16* cand, u16* chain, u32* regionList, u32 hcDepth, hipStream_t stream, StageHook hook, u32* claimCtr,
-               const u32* chunkLens, const u32* chunkFrames, const FramePlace* place, const DictIndexRef* dix)
+// The indexed-dictionary instance (TAB == 3, see lz_kernel) reads the index from arguments that an instance without a dictionary
+// prefix, a region parse and a frame place leaves idle.  This is the one place that says which: prefix = the END of the dictionary's
+// content, prefixLen = the indexed bytes in front of it, chain = the index (u32 per bucket), frames.at = log2 of its buckets.
+static LzLaunch dict_index_args(const LzLaunch& a)
 {
-    if (dix) {
+    LzLaunch x = a;
+    x.prefix = a.dix->end; x.prefixLen = a.dix->len; x.chain = (u16*)a.dix->table; x.frames.at = a.dix->log;
+    x.cand = nullptr; x.regionList = nullptr;
+    return x;
+}
+
+// Selects the finder's instance for a.finder: 0 = fast, 1 = dual (8-byte + 5-byte hashes), 2 = dual + lazy deferral.  (A 4-byte short
+// hash, the reference's minMatch at levels 4+, was measured and lost ratio on every corpus tried: far 4-byte matches cost more than
+// literals.)  See LzLaunch (zmi_host.h) for the arguments.
+void launch_lz(const LzLaunch& a)
+{
+    const bool full = a.frames.chunkBytes >= kChunkSize;
+    const u32 f = a.finder;
+    if (a.dix) {
         // every chunk a frame of its own behind an indexed dictionary: the FAR instance with the dictionary as what lies in front of
-        // the block (TAB == 3, see lz_kernel for the arguments that carry the index).  An instance of its own, so the kernels of a
-        // context without the switch are the ones from before it existed.
-        assert(finder == 0 && !place && !chunkFrames && !frameBlocks && chunkBytes == kChunkSize && dix->len >= 8 && dix->len <= kFarMax);
-        launch_one<0, 5, false, true, 3>(src, srcSize, nChunks, seqs, lits, meta, dix->end, dix->len, kChunkSize, fhExtra, minStrideLog, 0, nullptr, (u16*)dix->table, nullptr, 0, stream, hook, claimCtr,
-                                         chunkLens, nullptr, dix->log, 0);
-        return;
+        // the block.  An instance of its own, so the kernels of a context without the switch are the ones from before it existed.
+        assert(f == 0 && a.frames.form == kArith && !a.frames.frameBlocks && full && a.dix->len >= 8 && a.dix->len <= kFarMax);
+        return launch_one<0, 5, false, true, 3>(dict_index_args(a));
     }
-    if (place) {
+    if (a.frames.form == kSingle) {
         // one frame across passes: the long-distance framing's blocks (resolve_framing), each with its place in bytes.  Instances of
-        // their own (TAB == 2), so the kernels of a context without the switch are the ones from before it existed.
-        assert(frameBlocks && !chunkLens && !chunkFrames && !prefixLen && (chunkBytes >= kChunkSize) == (finder == 0));
-        switch (finder) {
-        case 0:  launch_one<0, 5, false, true, 2>(src, srcSize, nChunks, seqs, lits, meta, nullptr, 0, kChunkSize, fhExtra, minStrideLog, frameBlocks, nullptr, nullptr, nullptr, 0, stream, hook, claimCtr, nullptr, nullptr, place->at, place->total); break;
-        case 1:  launch_one<1, 5, true, false, 2>(src, srcSize, nChunks, seqs, lits, meta, nullptr, 0, chunkBytes, fhExtra, minStrideLog, frameBlocks, cand, chain, regionList, hcDepth, stream, hook, claimCtr, nullptr, nullptr, place->at, place->total); break;
-        default: launch_one<2, 5, true, false, 2>(src, srcSize, nChunks, seqs, lits, meta, nullptr, 0, chunkBytes, fhExtra, minStrideLog, frameBlocks, cand, chain, regionList, hcDepth, stream, hook, claimCtr, nullptr, nullptr, place->at, place->total); break;
-        }
-        return;
+        // their own, so the kernels of a context without the switch are the ones from before it existed.
+        assert(a.frames.frameBlocks && !a.chunkLens && !a.prefixLen && full == (f == 0));
+        return f == 0 ? launch_one<0, 5, false, true, 2>(a) : f == 1 ? launch_one<1, 5, true, false, 2>(a) : launch_one<2, 5, true, false, 2>(a);
     }
-    // (the table form exists for blocks behind LDS history only: the full-64-KiB-block instances below take no chunkFrames, while
-    //  seq_encode and xxh64 would still follow it)
-    assert(!chunkFrames || (chunkBytes < kChunkSize && frameBlocks && chunkLens));
-    if (chunkBytes >= kChunkSize && frameBlocks && finder == 0) {       // fast strategy with cross-chunk history: full 64 KiB blocks, far candidates
-        launch_one<0, 5, false, true>(src, srcSize, nChunks, seqs, lits, meta, nullptr, 0, kChunkSize, fhExtra, minStrideLog, frameBlocks, nullptr, nullptr, nullptr, 0, stream, hook, claimCtr, nullptr, nullptr);
-        return;
+    if (a.frames.form == kTable) {
+        // (the table form exists for blocks behind LDS history only: the full-64-KiB-block instances take no table, while seq_encode
+        //  and xxh64 would still follow it)
+        assert(!full && a.frames.frameBlocks && a.chunkLens);
+        return f == 0 ? launch_one<0, 5, true, false, 1>(a) : f == 1 ? launch_one<1, 5, true, false, 1>(a) : launch_one<2, 5, true, false, 1>(a);
     }
-    if (chunkBytes >= kChunkSize) {
-        switch (finder) {
-        case 0:  launch_one<0, 5, false>(src, srcSize, nChunks, seqs, lits, meta, nullptr, 0, kChunkSize, fhExtra, minStrideLog, 0, cand, chain, regionList, hcDepth, stream, hook, claimCtr, chunkLens, nullptr); break;
-        case 1:  launch_one<1, 5, false>(src, srcSize, nChunks, seqs, lits, meta, nullptr, 0, kChunkSize, fhExtra, minStrideLog, 0, cand, chain, regionList, hcDepth, stream, hook, claimCtr, chunkLens, nullptr); break;
-        default: launch_one<2, 5, false>(src, srcSize, nChunks, seqs, lits, meta, nullptr, 0, kChunkSize, fhExtra, minStrideLog, 0, cand, chain, regionList, hcDepth, stream, hook, claimCtr, chunkLens, nullptr); break;
-        }
-        return;
-    }
-    switch (finder) {
-    case 0:  if (chunkFrames) launch_one<0, 5, true, false, 1>(src, srcSize, nChunks, seqs, lits, meta, prefix, prefixLen, chunkBytes, fhExtra, minStrideLog, frameBlocks, cand, chain, regionList, hcDepth, stream, hook, claimCtr, chunkLens, chunkFrames);
-             else launch_one<0, 5, true>(src, srcSize, nChunks, seqs, lits, meta, prefix, prefixLen, chunkBytes, fhExtra, minStrideLog, frameBlocks, cand, chain, regionList, hcDepth, stream, hook, claimCtr, chunkLens, nullptr);
-             break;
-    case 1:  if (chunkFrames) launch_one<1, 5, true, false, 1>(src, srcSize, nChunks, seqs, lits, meta, prefix, prefixLen, chunkBytes, fhExtra, minStrideLog, frameBlocks, cand, chain, regionList, hcDepth, stream, hook, claimCtr, chunkLens, chunkFrames);
-             else launch_one<1, 5, true>(src, srcSize, nChunks, seqs, lits, meta, prefix, prefixLen, chunkBytes, fhExtra, minStrideLog, frameBlocks, cand, chain, regionList, hcDepth, stream, hook, claimCtr, chunkLens, nullptr);
-             break;
-    default: if (chunkFrames) launch_one<2, 5, true, false, 1>(src, srcSize, nChunks, seqs, lits, meta, prefix, prefixLen, chunkBytes, fhExtra, minStrideLog, frameBlocks, cand, chain, regionList, hcDepth, stream, hook, claimCtr, chunkLens, chunkFrames);
-             else launch_one<2, 5, true>(src, srcSize, nChunks, seqs, lits, meta, prefix, prefixLen, chunkBytes, fhExtra, minStrideLog, frameBlocks, cand, chain, regionList, hcDepth, stream, hook, claimCtr, chunkLens, nullptr);
-             break;
-    }
+    if (full && a.frames.frameBlocks && f == 0) return launch_one<0, 5, false, true>(a);      // fast strategy with cross-chunk history: full 64 KiB blocks, far candidates
+    if (full) return f == 0 ? launch_one<0, 5, false>(a) : f == 1 ? launch_one<1, 5, false>(a) : launch_one<2, 5, false>(a);       // plain chunks, each a frame
+    // a dictionary's tail, or the frame's earlier blocks, in LDS in front of a block below 64 KiB
+    return f == 0 ? launch_one<0, 5, true>(a) : f == 1 ? launch_one<1, 5, true>(a) : launch_one<2, 5, true>(a);
 }
 
 } // namespace zmi

@@ -117,15 +117,14 @@ __device__ __forceinline__ u32 build_seq_table(SeqWaveLds& W, u8* op, u32* count
 
 // DICT (ZSTDMI_CCtx_setDictEntropy with a formatted dictionary): a frame's first block may take the dictionary's LL / OF / ML tables
 // as they are (mode 3, build_seq_table); the instance without DICT is the code from before the switch existed.
-// SF (ZSTDMI_CCtx_setSingleFrame): the call's input is ONE frame cut anywhere by passes and stream batches; frameAt = bytes of the
-// frame in front of chunk 0, frameTotal = the frame's content size (~0: not known yet, the frame goes on behind this pass).
+// SF (ZSTDMI_CCtx_setSingleFrame): the call's input is ONE frame cut anywhere by passes and stream batches (frames.form == kSingle;
+// frames.total ~0: not known yet, the frame goes on behind this pass).
+// fh / frames (zmi_frame.h): the header a frame's first block is given, and how the chunks map to frames.
 template <bool DICT, bool SF>
 __global__ __launch_bounds__(256) void seq_encode_kernel(Seq* __restrict__ seqs, ChunkMeta* __restrict__ meta,
-                                                         u8* __restrict__ slots, u32 nChunks, u32 strategy, u32 checksumFlag, u32 resolveReps,
-                                                         u32 dictID, u32 dictIdBytes, u32 initRep0, u32 initRep1, u32 initRep2,
-                                                         const u32 frameBlocks, const u32 chunkBytes, const u64 srcSize,
-                                                         const DictCTables* __restrict__ dct, const u32* __restrict__ chunkFrames,
-                                                         const u64 frameAt, const u64 frameTotal)
+                                                         u8* __restrict__ slots, u32 nChunks, u32 strategy, const FrameHeaderSpec fh, u32 resolveReps,
+                                                         u32 initRep0, u32 initRep1, u32 initRep2, const FrameLayout frames,
+                                                         const DictCTables* __restrict__ dct)
 {
     __shared__ SeqWaveLds Ws[4];
     __shared__ u32 sBatchSeq[4];          // sequences each of the four chunks sends through the state chains (0: none)
@@ -142,21 +141,13 @@ __global__ __launch_bounds__(256) void seq_encode_kernel(Seq* __restrict__ seqs,
     // U/ZstdCompress.cs:3620-3640) is only known once it has been encoded — so its history starts as "unknown" (0 matches no
     // offset): offsets are written in full until the block itself has defined the repcode they would use.  That is always a
     // valid encoding (the decoder pushes a full offset whatever it equals) and costs a few bits per block.
-    // chunkFrames (optional): a batch of entries of different lengths: the block index (bits 24-31) and the frame's content size
-    // (bits 0-23) per chunk from a table, as in lz_kernel
-    const u32 place = (frameBlocks && chunkFrames && live) ? chunkFrames[c] : 0u;
-    const u32 bf = SF ? (frameAt + (u64)c * chunkBytes != 0 ? 1u : 0u) : frameBlocks ? (chunkFrames ? place >> 24 : c % frameBlocks) : 0u;   // (SF: first block or not)
-    u64 frameLen = n; bool lastBlock = true;
-    if (SF) {
-        frameLen = frameTotal;
-        lastBlock = frameAt + (u64)(c + 1) * chunkBytes >= frameTotal;
-        if (bf) { initRep0 = 0; initRep1 = 0; initRep2 = 0; }
-    } else if (frameBlocks) {
-        const u64 fStart = (u64)(c - bf) * chunkBytes, fMax = (u64)frameBlocks * chunkBytes;
-        frameLen = chunkFrames ? (u64)(place & 0xFFFFFFu) : (srcSize - fStart) < fMax ? (srcSize - fStart) : fMax;
-        lastBlock = (u64)(bf + 1) * chunkBytes >= frameLen;
-        if (bf) { initRep0 = 0; initRep1 = 0; initRep2 = 0; }
-    }
+    // (a batch of entries of different lengths states the place per chunk in a table, as in lz_kernel; a wave without a chunk reads none)
+    BlockPlace at = block_alone(n);
+    if (SF) at = block_place<kSingle>(frames, c);
+    else if (frames.frameBlocks && live) at = frames.form == kTable ? block_place<kTable>(frames, c) : block_place<kArith>(frames, c);
+    const u32 bf = at.block;                                  // (SF: first block or not)
+    const u64 frameLen = at.frameLen; const bool lastBlock = at.last;
+    if (bf) { initRep0 = 0; initRep1 = 0; initRep2 = 0; }
     Seq* __restrict__ sq = seqs + (u64)c * kMaxSeq;
     u8* const slot = slots + (u64)c * kSlotStride;
     u8* const body = slot + m.fhSize + 3;
@@ -415,35 +406,8 @@ __global__ __launch_bounds__(256) void seq_encode_kernel(Seq* __restrict__ seqs,
     u32 cSize = (u32)(op - body);
     if (!giveUp && cSize >= n - ((n >> 6) + 2)) giveUp = true;                      // ZSTD_minGain
 
-    // ---- frame header in front of the frame's first block (ZSTD_writeFrameHeader, U/ZstdCompress.cs:4817-4929): single segment with
-    // the content size, or — ZSTD_c_contentSizeFlag = 0 (checksumFlag bit 1) — a window descriptor and no content size: the smallest
-    // power of two that holds the frame (>= 1 KiB), so that no offset and no block exceeds the declared window ----
-    if (bf == 0) {
-        writeLE32(slot, 0xFD2FB528u);
-        const u32 didCode = dictIdBytes == 4 ? 3u : dictIdBytes;          // dictID field of 0, 1, 2 or 4 bytes (U/ZstdCompress.cs:4843-4849, 4896-4918)
-        const u32 wlSet = (checksumFlag >> 8) & 31u;          // an explicit window (frames of independent blocks, each a window long)
-        if ((checksumFlag & 2u) || wlSet) {
-            u32 wl = wlSet;
-            if (!wl) { wl = 10; while (((u64)1 << wl) < frameLen) ++wl; }
-            const u32 fcsCode = (checksumFlag & 2u) ? 0u : (frameLen >= 256) + (frameLen >= 65536 + 256) + (frameLen > 0xFFFFFFFFull);
-            slot[4] = (u8)(didCode + ((checksumFlag & 1u) << 2) + (fcsCode << 6));
-            slot[5] = (u8)((wl - 10) << 3);
-            for (u32 i = 0; i < dictIdBytes; i++) slot[6 + i] = (u8)(dictID >> (8 * i));
-            u8* const fcs = slot + 6 + dictIdBytes;               // (not a single segment: a content size below 256 has no field)
-            if (fcsCode == 1) writeLE16(fcs, (u32)frameLen - 256);
-            else if (fcsCode == 2) writeLE32(fcs, (u32)frameLen);
-            else if (fcsCode == 3) { writeLE32(fcs, (u32)frameLen); writeLE32(fcs + 4, (u32)(frameLen >> 32)); }
-        } else {
-            const u32 fcsCode = (frameLen >= 256) + (frameLen >= 65536 + 256) + (frameLen > 0xFFFFFFFFull);
-            slot[4] = (u8)(didCode + ((checksumFlag & 1u) << 2) + (1u << 5) + (fcsCode << 6));
-            for (u32 i = 0; i < dictIdBytes; i++) slot[5 + i] = (u8)(dictID >> (8 * i));
-            u8* const fcs = slot + 5 + dictIdBytes;
-            if (fcsCode == 0) fcs[0] = (u8)frameLen;
-            else if (fcsCode == 1) writeLE16(fcs, (u32)frameLen - 256);
-            else if (fcsCode == 2) writeLE32(fcs, (u32)frameLen);
-            else { writeLE32(fcs, (u32)frameLen); writeLE32(fcs + 4, (u32)(frameLen >> 32)); }
-        }
-    }
+    // ---- frame header in front of the frame's first block: the bytes whose count the finder left in fhSize (zmi_frame.h) ----
+    if (bf == 0) frame_header_write(fh, frameLen, slot);
     u8* const bh = slot + m.fhSize;
     const u32 lastBit = lastBlock ? 1u : 0u;                  // Last_Block (U/ZstdCompress.cs:4757-4760)
     if (giveUp) {            // ZSTD_noCompressBlock: the gather kernel copies the n source bytes behind this header
@@ -453,24 +417,17 @@ __global__ __launch_bounds__(256) void seq_encode_kernel(Seq* __restrict__ seqs,
         writeLE24(bh, lastBit + (2u << 1) + (cSize << 3));
         m.blockType = 2; m.bodySize = cSize;
     }
-    m.outSize = m.fhSize + 3 + cSize + (((checksumFlag & 1u) && lastBlock) ? 4 : 0);
+    m.outSize = m.fhSize + 3 + cSize + ((fh.checksum && lastBlock) ? 4 : 0);
     meta[c] = m;
 }
 
-void launch_seq_encode(Seq* seqs, ChunkMeta* meta, u8* slots, u32 nChunks, u32 strategy, u32 checksumFlag, u32 resolveReps,
-                       u32 dictID, u32 dictIdBytes, const u32* initReps, u32 frameBlocks, u32 chunkBytes, u64 srcSize, hipStream_t stream,
-                       const DictCTables* dct, const u32* chunkFrames, const FramePlace* place)
+void launch_seq_encode(Seq* seqs, ChunkMeta* meta, u8* slots, u32 nChunks, u32 strategy, const FrameHeaderSpec& header, u32 resolveReps,
+                       const u32* initReps, const FrameLayout& frames, hipStream_t stream, const DictCTables* dct)
 {
-    if (place) {
-        assert(!dct && !chunkFrames);
-        hipLaunchKernelGGL((seq_encode_kernel<false, true>), dim3((nChunks + 3) / 4), dim3(256), 0, stream, seqs, meta, slots, nChunks, strategy, checksumFlag, resolveReps,
-                           dictID, dictIdBytes, initReps[0], initReps[1], initReps[2], frameBlocks, chunkBytes, srcSize, dct, chunkFrames, place->at, place->total);
-        return;
-    }
-    if (dct) hipLaunchKernelGGL((seq_encode_kernel<true, false>), dim3((nChunks + 3) / 4), dim3(256), 0, stream, seqs, meta, slots, nChunks, strategy, checksumFlag, resolveReps,
-                                dictID, dictIdBytes, initReps[0], initReps[1], initReps[2], frameBlocks, chunkBytes, srcSize, dct, chunkFrames, (u64)0, (u64)0);
-    else hipLaunchKernelGGL((seq_encode_kernel<false, false>), dim3((nChunks + 3) / 4), dim3(256), 0, stream, seqs, meta, slots, nChunks, strategy, checksumFlag, resolveReps,
-                            dictID, dictIdBytes, initReps[0], initReps[1], initReps[2], frameBlocks, chunkBytes, srcSize, dct, chunkFrames, (u64)0, (u64)0);
+    assert(!dct || frames.form != kSingle);
+    const auto kernel = frames.form == kSingle ? seq_encode_kernel<false, true> : dct ? seq_encode_kernel<true, false> : seq_encode_kernel<false, false>;
+    hipLaunchKernelGGL(kernel, dim3((nChunks + 3) / 4), dim3(256), 0, stream, seqs, meta, slots, nChunks, strategy, header, resolveReps,
+                       initReps[0], initReps[1], initReps[2], frames, dct);
 }
 
 #ifdef ZMI_LZ_STAMPS

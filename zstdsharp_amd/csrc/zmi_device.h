@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "zmi_common.h"
+#include "zmi_frame.h"
 
 namespace zmi {
 
@@ -71,9 +72,5 @@ __device__ __forceinline__ ChunkMeta meta_checked(ChunkMeta m)
     if (LITMODE && m.litMode > kLitTreeless) m.litMode = kLitRaw;
     return m;
 }
-
-// frame header size for a chunk of n bytes: magic + FHD + FCS, single-segment (U/ZstdCompress.cs:4817-4929)
-__host__ __device__ __forceinline__ u32 frame_header_size(u32 n) { return 4 + 1 + (n < 256 ? 1 : (n < 65536 + 256 ? 2 : 4)); }
-__host__ __device__ __forceinline__ u32 frame_header_size64(u64 n) { return 4 + 1 + (n < 256 ? 1 : (n < 65536 + 256 ? 2 : (n <= 0xFFFFFFFFull ? 4 : 8))); }
 
 } // namespace zmi

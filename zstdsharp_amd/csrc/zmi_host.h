@@ -10,42 +10,57 @@
 #include <thread>
 #include <new>
 #include "zmi_common.h"
+#include "zmi_frame.h"
 #include "../../include/zstd_mi355x.h"
 
 namespace zmi {
 // kernels (lz_fast.hip, huf_enc.hip, seq_enc.hip, frame.hip, decode.hip)
-// chunkLens / chunkFrames (a batch of entries, each staged at a chunk boundary): per chunk its length, and — multi-block frames behind
-// LDS history only — its place: chunk_frame_word(block index inside its frame, the frame's content size)
-// place (ZSTDMI_CCtx_setSingleFrame): the call's input is ONE frame that passes and stream batches cut anywhere: `at` = bytes of the frame in
-// front of src (readable there, as far as the finders reach back), `total` = the frame's content size (~0: the frame goes on behind this pass)
-struct FramePlace { u64 at, total; };
 // an indexed dictionary (ZSTDMI_CCtx_setDictIndex; lz_fast.hip): `end` = the byte behind its content on the device (readable for 64
 // bytes more), `len` = the indexed bytes in front of `end`, `table` = 1 << log buckets
 struct DictIndexRef { const u8* end; u32 len; const u32* table; u32 log; };
 void launch_dict_index(const u8* content, u32 len, u32* table, u32 log, hipStream_t stream);
 u32 dict_index_log(u32 len);        // log2 of the buckets for `len` indexed bytes
 u32 dict_index_max();               // the most bytes an index covers (the far candidates' reach)
-inline u32 chunk_frame_word(u32 blockInFrame, u32 frameLen) { assert(blockInFrame < 256 && frameLen < (1u << 24)); return (blockInFrame << 24) | frameLen; }
-void launch_lz(u32 finder, const u8* src, u64 srcSize, u32 nChunks, Seq* seqs, u8* lits, ChunkMeta* meta, const u8* prefix, u32 prefixLen,
-               u32 chunkBytes, u32 fhExtra, u32 minStrideLog, u32 frameBlocks, u16* cand, u16* chain, u32* regionList, u32 hcDepth, hipStream_t stream, StageHook hook, u32* claimCtr,
-               const u32* chunkLens = nullptr, const u32* chunkFrames = nullptr, const FramePlace* place = nullptr, const DictIndexRef* dix = nullptr);
+// What the match finder is launched with.  frames (zmi_frame.h): chunkBytes = 64 KiB minus what lies in LDS in front of a block, rounded
+// up to whole 4 KiB tiles — the dictionary's tail (prefix / prefixLen: the bytes every chunk sees as history), or, with frameBlocks > 0
+// and no dictionary, up to 64 KiB - chunkBytes of the input in front of the block, as far back as its frame reaches; chunkBytes
+// < 64 KiB with neither: independent frames of chunkBytes each (ZSTD_c_windowLog 10 .. 15: a frame is its own window), on the same
+// instance with an empty history.  independent: the blocks of a frame share no history (frame_blocks_encode).
+// chunkLens (optional): a batch of entries, each staged at a chunk boundary: per chunk its length.
+// cand / chain / regionList (null: off): workspace of the region parse, 65536 u16 per chunk (twice with the hash chains of the
+// level >= 5 search, hcDepth attempts per position) and 1 + nChunks u32.  claimCtr: a zeroable word for the chunk claims (lz_kernel).
+// dix (null: off): an indexed dictionary behind full 64 KiB chunks, each a frame of its own (fast finder only; chunkLens allowed).
+struct LzLaunch {
+    u32 finder;
+    const u8* src; u64 srcSize; u32 nChunks;
+    Seq* seqs; u8* lits; ChunkMeta* meta;
+    const u8* prefix; u32 prefixLen;
+    FrameLayout frames; bool independent;
+    FrameHeaderSpec header;
+    u32 minStrideLog;
+    u16* cand; u16* chain; u32* regionList; u32 hcDepth;
+    u32* claimCtr;
+    const u32* chunkLens;
+    const DictIndexRef* dix;
+    hipStream_t stream; StageHook hook;
+};
+void launch_lz(const LzLaunch& a);
 void launch_lz_probe(const u8* src, u64 srcSize, u64 front, u64 groupBytes, u32 nGroups, u32 tilesPerGroup, u32* out, hipStream_t stream);
-void launch_huf_build(const u8* lits, ChunkMeta* meta, HufTable* tables, u8* slots, u32 nChunks, u32 rawLiterals, const u8* src, u32 chunkBytes,
-                      hipStream_t stream, StageHook hook, const DictCTables* dct = nullptr, u32 frameBlocks = 0);
+// frames: a dictionary's entropy tables (dct) serve the first block of every frame
+void launch_huf_build(const u8* lits, ChunkMeta* meta, HufTable* tables, u8* slots, u32 nChunks, u32 rawLiterals, const u8* src, const FrameLayout& frames,
+                      hipStream_t stream, StageHook hook, const DictCTables* dct = nullptr);
 void launch_huf_encode(const u8* lits, const ChunkMeta* meta, const HufTable* tables, u8* slots, u8* dst, const u64* offsets, u64 dstCapacity,
                        u32 nChunks, const u8* src, u32 chunkBytes, hipStream_t stream, bool dictEntropy = false);
-void launch_seq_encode(Seq* seqs, ChunkMeta* meta, u8* slots, u32 nChunks, u32 strategy, u32 checksumFlag, u32 resolveReps,
-                       u32 dictID, u32 dictIdBytes, const u32* initReps, u32 frameBlocks, u32 chunkBytes, u64 srcSize, hipStream_t stream,
-                       const DictCTables* dct = nullptr, const u32* chunkFrames = nullptr, const FramePlace* place = nullptr);
+void launch_seq_encode(Seq* seqs, ChunkMeta* meta, u8* slots, u32 nChunks, u32 strategy, const FrameHeaderSpec& header, u32 resolveReps,
+                       const u32* initReps, const FrameLayout& frames, hipStream_t stream, const DictCTables* dct = nullptr);
 void launch_scan_sizes(const ChunkMeta* meta, u32 nChunks, u64* offsets, u64* total, hipStream_t stream);
 void launch_gather(const u8* src, u64 srcSize, const u8* slots, const ChunkMeta* meta, const u64* offsets, u8* dst, u64 dstCapacity,
                    u32 nChunks, u32 chunkBytes, hipStream_t stream);
-void launch_xxh64(const u8* src, u64 srcSize, ChunkMeta* meta, u32 nChunks, u32 chunkBytes, u32 frameBlocks, hipStream_t stream, const u32* chunkLens = nullptr,
-                  const u32* chunkFrames = nullptr);
+void launch_xxh64(const u8* src, ChunkMeta* meta, u32 nChunks, const FrameLayout& frames, hipStream_t stream, const u32* chunkLens = nullptr);
 void launch_batch_stage(const u64* from, const u32* len, u8* stage, u32 nChunks, u32 chunkBytes, hipStream_t stream);
 void launch_batch_place(const ChunkMeta* meta, u32 nEntries, const u32* entFirst, const u64* entDst, const u64* entCap, u64 span, u64* offsets, u64* entSize,
                         hipStream_t stream);
-void launch_seek_entries(const u64* offsets, const u64* total, u32 nChunks, u32 frameBlocks, u32 chunkBytes, u64 passBytes, u32* entries, hipStream_t stream);
+void launch_seek_entries(const u64* offsets, const u64* total, u32 nChunks, const FrameLayout& frames, u32* entries, hipStream_t stream);
 void launch_seek_table(const u32* entries, u32 n, u8* dst, hipStream_t stream);
 // long-distance matching (ldm.hip)
 size_t ldm_small_bytes(u64 n);

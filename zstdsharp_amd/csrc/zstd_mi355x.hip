@@ -258,24 +258,31 @@ constexpr size_t kStreamTail = (size_t)256 << 10;       // history in front of a
 constexpr u64 kSingleMax = (u64)2 << 30;
 static bool single_active(const CallParams& cp, size_t paramSize) { return cp.single && !cp.pfxSize && (cp.stream || (paramSize > kChunkSize && !ldm_active(cp, paramSize))); }
 
+// bytes per block of a multi-block frame: the fast strategy keeps full 64 KiB blocks (far candidates); the dual-hash finders' blocks
+// shrink to 64 KiB minus the hb bytes of history (whole 4 KiB tiles, at most 48 KiB) they carry in front of them in LDS
+static u32 history_block_bytes(const Resolved& rf, int hb)
+{
+    if (rf.finder == 0) return kChunkSize;
+    const u32 histB = round_tile((size_t)hb);
+    return kChunkSize - (histB > (48u << 10) ? (48u << 10) : histB);
+}
+// the history of the framings that always have one (LDM windows, one frame per call): the context's, or by strategy
+static int history_bytes_or_default(const ZSTD_CCtx* c, const Resolved& rf) { return c->historyBytes > 0 ? c->historyBytes : (rf.cp.strategy == kStratDfast ? (16 << 10) : (32 << 10)); }
+
 static Framing resolve_framing(const ZSTD_CCtx* c, const CallParams& cp, size_t paramSize)
 {
     if (single_active(cp, paramSize)) {
         // The blocks are the long-distance framing's (below) without its stage: full 64 KiB blocks with far candidates at the fast
         // strategy, 64 KiB - 16/32 KiB blocks behind LDS history above it; every block but the first sees the input in front of it,
-        // wherever a pass or a batch begins (FramePlace).  The header is the reference's: with wl = ZSTD_c_windowLog, or the level's
+        // wherever a pass or a batch begins (zmi_frame.h, kSingle).  The header is the reference's: with wl = ZSTD_c_windowLog, or the level's
         // windowLog for this size, a single segment when the content fits 2^wl, else a window descriptor for 2^wl beside the content
         // size (no finder reaches 2^18 back, and a wl below 18 was refused: check_single_frame).
         Framing f; f.prefixLen = 0; f.single = true;
         const Resolved rf = resolve_call(cp, paramSize, (u32)1 << 31);
-        u32 chunkBytes = kChunkSize;
-        if (rf.finder != 0) {
-            const int hb = c->historyBytes > 0 ? c->historyBytes : (rf.cp.strategy == kStratDfast ? (16 << 10) : (32 << 10));
-            chunkBytes = kChunkSize - (round_tile((size_t)hb) > (48u << 10) ? (48u << 10) : round_tile((size_t)hb));
-        }
+        const u32 chunkBytes = history_block_bytes(rf, history_bytes_or_default(c, rf));
         const u32 wl = cp.windowLog ? (u32)cp.windowLog : rf.cp.windowLog;
         f.singleWindowLog = (cp.stream || (u64)paramSize > ((u64)1 << wl)) ? wl : 0u;
-        f.chunkBytes = chunkBytes; f.frameBlocks = 0x7FFFFFFFu; f.rs = rf;      // (frameBlocks: "blocks share a frame"; a block's place comes from FramePlace)
+        f.chunkBytes = chunkBytes; f.frameBlocks = 0x7FFFFFFFu; f.rs = rf;      // (frameBlocks: "blocks share a frame"; a block's place is counted in bytes: zmi_frame.h, kSingle)
         return f;
     }
     if (cp.pfxSize || ldm_active(cp, paramSize)) {
@@ -293,11 +300,7 @@ static Framing resolve_framing(const ZSTD_CCtx* c, const CallParams& cp, size_t 
         } else f.ldmP = ldm_resolve(cp, paramSize);
         const u64 win = ((u64)1 << wl) < kLdmMaxFrame ? ((u64)1 << wl) : kLdmMaxFrame;
         const Resolved rf = resolve_call(cp, paramSize < win ? paramSize : (size_t)win, (u32)(win < ((u64)1 << 31) ? win : ((u64)1 << 31)));
-        u32 chunkBytes = kChunkSize;
-        if (rf.finder != 0) {
-            const int hb = c->historyBytes > 0 ? c->historyBytes : (rf.cp.strategy == kStratDfast ? (16 << 10) : (32 << 10));
-            chunkBytes = kChunkSize - (round_tile((size_t)hb) > (48u << 10) ? (48u << 10) : round_tile((size_t)hb));
-        }
+        const u32 chunkBytes = history_block_bytes(rf, history_bytes_or_default(c, rf));
         u32 frameBlocks = cp.pfxSize ? (u32)((paramSize + chunkBytes - 1) / chunkBytes) : (u32)(win / chunkBytes);
         if (frameBlocks > c->passChunks) frameBlocks = c->passChunks;
         if (frameBlocks < 2) frameBlocks = 2;
@@ -335,8 +338,7 @@ static Framing resolve_framing(const ZSTD_CCtx* c, const CallParams& cp, size_t 
             // 188 KiB back); the dual-hash finders' 16-bit tables cannot hold far positions, so their blocks shrink to
             // 64 KiB - hist and carry the hist bytes in front of them in LDS
             const Resolved rf = resolve_call(cp, paramSize < frameBytes ? paramSize : frameBytes, frameBytes);
-            if (rf.finder == 0) chunkBytes = kChunkSize;
-            else { const u32 histB = round_tile((size_t)hb) > (48u << 10) ? (48u << 10) : round_tile((size_t)hb); chunkBytes = kChunkSize - histB; }
+            chunkBytes = history_block_bytes(rf, hb);
             frameBlocks = frameBytes / chunkBytes; if (frameBlocks < 2) frameBlocks = 2;
             rs = rf;
         }
@@ -360,14 +362,21 @@ static Framing resolve_framing(const ZSTD_CCtx* c, const CallParams& cp, size_t 
     return f;
 }
 
-// What the finder and the sequence encoder are launched with for a framing: derived in one place for the single call
-// (compress_range) and the batch (compress_entries), whose bytes must be the same.
-struct LaunchState { bool regionParse, hcChains; u32 hcDepth, strategy, lzFrameBlocks; };
+// What the kernels of a pass are launched with for a framing: derived in one place for the single call (compress_range) and the
+// batch (compress_entries), whose bytes must be the same.
+struct LaunchState {
+    bool regionParse, hcChains, independent; u32 hcDepth, strategy;
+    FrameHeaderSpec header;             // of every frame the call writes
+    u32 initReps[3];                // the repcodes in front of every frame: a formatted dictionary's, or the format's
+    const DictCTables* dct;         // a formatted dictionary's entropy tables (ZSTDMI_CCtx_setDictEntropy), or null
+    const u8* prefix;               // the dictionary's tail in front of every chunk (fr.prefixLen bytes), or null
+    DictIndexRef dix;               // the indexed dictionary (fr.dictIndex)
+};
 static LaunchState launch_state(const ZSTD_CCtx* c, const CallParams& cp, const Framing& fr)
 {
     const Resolved& rs = fr.rs;
     LaunchState L;
-    L.lzFrameBlocks = fr.frameBlocks | (fr.indepWindowLog ? 0x80000000u : 0u);       // (independent blocks: no history between them)
+    L.independent = fr.indepWindowLog != 0;       // (no history between the blocks of a frame)
     L.regionParse = rs.minStrideLog == 0 && !(rs.finder == 0 && fr.frameBlocks && fr.chunkBytes >= kChunkSize) && !fr.dictIndex && c->parser == 0;   // (not the far-candidate finder)
     L.hcChains = L.regionParse && rs.finder >= 2;
     // attempts per position of the level >= 5 search: the reference's 1 << searchLog (U/ZstdLazy.cs:641-642), between 4 and 32; the
@@ -376,7 +385,47 @@ static LaunchState launch_state(const ZSTD_CCtx* c, const CallParams& cp, const 
     L.hcDepth = rs.cp.searchLog < 2 ? 4u : rs.cp.searchLog > 5 ? 32u : 1u << rs.cp.searchLog;
     if (L.hcDepth > 8 && rs.cp.strategy <= 4 && cp.searchLog == 0) L.hcDepth = 8;
     L.strategy = rs.cp.strategy < kStratGreedy ? rs.cp.strategy : (u32)kStratGreedy;      // ZSTD_selectEncodingType's < lazy heuristic is the one seq_encode holds (U/ZstdCompressSequences.cs:400-469): levels whose strategy is lazy or above get greedy's constants
+    // a formatted dictionary: its dictID in every frame header (unless ZSTD_c_dictIDFlag = 0), its repcodes in front of every frame.
+    // The window: one frame per call states its own beside (or instead of) the content size, frames of independent blocks the
+    // block's; a stream's header never carries a content size
+    const bool fmtDict = cp.useDict && c->dictFormatted;
+    L.header.dictID = fmtDict ? c->info.dictID : 0u;
+    L.header.dictIdBytes = (u8)(cp.dictIDFlag ? dict_id_bytes(L.header.dictID) : 0u);
+    L.header.checksum = cp.checksumFlag ? 1 : 0;
+    L.header.noContentSize = (cp.contentSizeFlag && !cp.stream) ? 0 : 1;
+    L.header.windowLog = (u8)(fr.single ? fr.singleWindowLog : fr.indepWindowLog);
+    const u32 plainReps[3] = { 1, 4, 8 };
+    for (int i = 0; i < 3; ++i) L.initReps[i] = fmtDict ? c->info.rep[i] : plainReps[i];
+    L.dct = call_dict_ctables(c, cp);
+    L.prefix = fr.prefixLen ? (const u8*)c->dict.p + (c->dictHost.size() - fr.prefixLen) : nullptr;
+    L.dix = DictIndexRef{ c->dictIdxEnd, c->dictIdxLen, (const u32*)c->dictIdxDev.p, c->dictIdxLog };
     return L;
+}
+// the finder's launch for a pass of nChunks chunks (the candidate planes lie where a workspace for planeChunks chunks puts them:
+// candidates | hash chains | work list, cctx_cand_workspace)
+static LzLaunch pass_lz(ZSTD_CCtx* c, const LaunchState& L, const Framing& fr, const u8* src, u64 srcSize, u32 nChunks, u32 planeChunks, const FrameLayout& frames, const u32* chunkLens)
+{
+    LzLaunch a = {};
+    a.finder = fr.rs.finder; a.src = src; a.srcSize = srcSize; a.nChunks = nChunks;
+    a.seqs = (Seq*)c->seqs.p; a.lits = (u8*)c->lits.p; a.meta = (ChunkMeta*)c->meta.p;
+    a.prefix = L.prefix; a.prefixLen = fr.prefixLen;
+    a.frames = frames; a.independent = L.independent; a.header = L.header; a.minStrideLog = fr.rs.minStrideLog;
+    u8* const planes = (u8*)c->cand.p;
+    a.cand = L.regionParse ? (u16*)planes : nullptr;
+    a.chain = L.hcChains ? (u16*)(planes + cand_plane_bytes(planeChunks)) : nullptr;
+    a.regionList = L.regionParse ? (u32*)(planes + cand_plane_bytes(planeChunks) * (L.hcChains ? 2 : 1)) : nullptr;
+    a.hcDepth = L.hcDepth;
+    a.claimCtr = (u32*)((u64*)c->total.p + 4);      // (the claim counter: a word of `total`'s 64 bytes)
+    a.chunkLens = chunkLens; a.dix = fr.dictIndex ? &L.dix : nullptr;
+    a.stream = c->stream; a.hook = c->timer.hook();
+    return a;
+}
+// a pass is over: its stage times into the call's, which are sums over its passes (inputs above 1 GiB take several)
+static void add_stage_times(ZSTD_CCtx* c, bool& first)
+{
+    c->timer.finish(); c->nStages = c->timer.n;
+    for (int i = 0; i < c->timer.n; i++) { c->stageMs[i] = (first ? 0.f : c->stageMs[i]) + c->timer.ms[i]; c->stageNames[i] = c->timer.names[i]; }
+    first = false;
 }
 
 // the compress pipeline over device-resident buffers: one range of the input with one set of parameters (see compress_device)
@@ -388,10 +437,9 @@ static size_t compress_range(ZSTD_CCtx* c, const CallParams& cp, u8* d_dst, size
 {
     hipStream_t s = c->stream;
     if (srcSize == 0) {     // ZSTD_writeEpilogue on an empty frame: header (FCS=0, single segment) + empty raw last block
-        u8 f[13]; size_t n = 0;
-        f[n++] = 0x28; f[n++] = 0xB5; f[n++] = 0x2F; f[n++] = 0xFD;
-        if (cp.contentSizeFlag) { f[n++] = (u8)((cp.checksumFlag ? 4 : 0) | 0x20); f[n++] = 0; }
-        else { f[n++] = (u8)(cp.checksumFlag ? 4 : 0); f[n++] = (u8)(((cp.windowLog >= 10 ? cp.windowLog : 10) - 10) << 3); }   // window descriptor, no content size
+        FrameHeaderSpec h = {}; h.checksum = cp.checksumFlag ? 1 : 0; h.noContentSize = cp.contentSizeFlag ? 0 : 1;
+        if (h.noContentSize && cp.windowLog >= 10) h.windowLog = (u8)cp.windowLog;     // (the window descriptor states the caller's window)
+        u8 f[18 + 3 + 4]; size_t n = frame_header_write(h, 0, f);
         f[n++] = 1; f[n++] = 0; f[n++] = 0;
         if (cp.checksumFlag) { f[n++] = 0x99; f[n++] = 0xE9; f[n++] = 0xD8; f[n++] = 0x51; }   // XXH64("") low 32 bits = 0x51D8E999
         if (dstCapacity < n) return ZERR(kErrDstSizeTooSmall);
@@ -401,16 +449,11 @@ static size_t compress_range(ZSTD_CCtx* c, const CallParams& cp, u8* d_dst, size
     }
     if (cp.useDict) { const size_t e = cctx_sync_dictionary(c); if (isErr(e)) return e; }
     const Framing fr = resolve_framing(c, cp, paramSize);
-    const u32 prefixLen = fr.prefixLen, chunkBytes = fr.chunkBytes, frameBlocks = fr.frameBlocks;
+    const u32 chunkBytes = fr.chunkBytes, frameBlocks = fr.frameBlocks;
     const LaunchState ls = launch_state(c, cp, fr);
-    const u32 lzFrameBlocks = ls.lzFrameBlocks, hcDepth = ls.hcDepth, strategy = ls.strategy;
-    const bool regionParse = ls.regionParse, hcChains = ls.hcChains;
-    const u32 hdrWindow = fr.single ? fr.singleWindowLog : fr.indepWindowLog;
     const Resolved rs = fr.rs;
-    // one frame: where this range lies in it (a one-shot call IS the frame; a stream's batch continues it) and how long it is;
-    // a stream's header never carries a content size
+    // one frame: where this range lies in it (a one-shot call IS the frame; a stream's batch continues it) and how long it is
     const u64 sfAt = cp.stream ? cp.streamAt : 0u, sfTotal = cp.stream ? (cp.streamEnd ? cp.streamAt + srcSize : ~(u64)0) : (u64)srcSize;
-    const bool withSize = cp.contentSizeFlag && !cp.stream;
     if (fr.single && cp.checksumFlag) {
         if (!c->sfXxh.ensure(sizeof(XxhCarry))) return ZERR(kErrMemoryAllocation);
         if (sfAt == 0) {
@@ -418,22 +461,13 @@ static size_t compress_range(ZSTD_CCtx* c, const CallParams& cp, u8* d_dst, size
             if (hipMemcpyAsync(c->sfXxh.p, &c->sfXxhHost, sizeof(XxhCarry), hipMemcpyHostToDevice, s) != hipSuccess) return ZERR(kErrGeneric);
         }
     }
-    // a formatted dictionary: its dictID in every frame header (unless ZSTD_c_dictIDFlag = 0), its repcodes in front of every frame
-    const bool fmtDict = cp.useDict && c->dictFormatted;
-    const u32 dictID = fmtDict ? c->info.dictID : 0u;
-    const u32 dictIdBytes = (dictID && cp.dictIDFlag) ? (dictID < 256 ? 1u : dictID < 65536 ? 2u : 4u) : 0u;
-    const u32 plainReps[3] = { 1, 4, 8 };
-    const u32* const initReps = fmtDict ? c->info.rep : plainReps;
-    const DictCTables* const dct = call_dict_ctables(c, cp);
-    const u8* prefix = prefixLen ? (const u8*)c->dict.p + (c->dictHost.size() - prefixLen) : nullptr;
-    const DictIndexRef dixRef = { c->dictIdxEnd, c->dictIdxLen, (const u32*)c->dictIdxDev.p, c->dictIdxLog };
-    const DictIndexRef* const dix = fr.dictIndex ? &dixRef : nullptr;
+    const DictCTables* const dct = ls.dct;
     const u64 totalChunks = (srcSize + chunkBytes - 1) / chunkBytes;
     u32 passChunks = (u32)(totalChunks < c->passChunks ? totalChunks : c->passChunks);
-    if (fr.ldm) { const u32 most = (u32)(((u64)1 << 31) / chunkBytes) / frameBlocks * frameBlocks; if (passChunks > most) passChunks = most; }    // (ldm.hip: u32 offsets in a pass)
-    if (frameBlocks && !fr.single && passChunks < totalChunks) { passChunks -= passChunks % frameBlocks; if (!passChunks) passChunks = frameBlocks; }     // frames never straddle passes
+    if (fr.ldm) { const u32 most = whole_frame_chunks((u32)(((u64)1 << 31) / chunkBytes), frameBlocks); if (passChunks > most) passChunks = most; }    // (ldm.hip: u32 offsets in a pass)
+    if (frameBlocks && !fr.single && passChunks < totalChunks) { passChunks = whole_frame_chunks(passChunks, frameBlocks); if (!passChunks) passChunks = frameBlocks; }     // frames never straddle passes
     if (!cctx_workspace(c, passChunks)) return ZERR(kErrMemoryAllocation);
-    if (regionParse && !cctx_cand_workspace(c, passChunks, hcChains)) return ZERR(kErrMemoryAllocation);
+    if (ls.regionParse && !cctx_cand_workspace(c, passChunks, ls.hcChains)) return ZERR(kErrMemoryAllocation);
     size_t produced = 0;
     for (u64 c0 = 0; c0 < totalChunks; c0 += passChunks) {
         const u32 nChunks = (u32)((totalChunks - c0) < passChunks ? (totalChunks - c0) : passChunks);
@@ -441,12 +475,10 @@ static size_t compress_range(ZSTD_CCtx* c, const CallParams& cp, u8* d_dst, size
         const u64 n = (srcSize - c0 * chunkBytes) < (u64)nChunks * chunkBytes ? (srcSize - c0 * chunkBytes) : (u64)nChunks * chunkBytes;
         Seq* seqs = (Seq*)c->seqs.p; u8* lits = (u8*)c->lits.p; ChunkMeta* meta = (ChunkMeta*)c->meta.p;
         HufTable* tables = (HufTable*)c->tables.p; u8* slots = (u8*)c->slots.p; u64* offsets = (u64*)c->offsets.p; u64* total = (u64*)c->total.p;
-        // (one frame: the pass's first block lies place.at bytes into it; everything the kernels knew from a chunk's index in the pass comes from there)
-        const FramePlace place = { sfAt + c0 * chunkBytes, sfTotal };
-        const FramePlace* const pl = fr.single ? &place : nullptr;
+        // (one frame: the pass's first block lies frames.at bytes into it; everything the kernels knew from a chunk's index in the pass comes from there)
+        const FrameLayout frames = fr.single ? layout_single(chunkBytes, frameBlocks, sfAt + c0 * chunkBytes, sfTotal) : layout_arith(chunkBytes, frameBlocks, n);
         c->timer.begin(s);
-        launch_lz(rs.finder, src, n, nChunks, seqs, lits, meta, prefix, prefixLen, chunkBytes, dictIdBytes | (withSize ? 0u : 0x100u) | (hdrWindow << 12), rs.minStrideLog, lzFrameBlocks, regionParse ? (u16*)c->cand.p : nullptr, hcChains ? (u16*)((u8*)c->cand.p + cand_plane_bytes(passChunks)) : nullptr,
-                  regionParse ? (u32*)((u8*)c->cand.p + cand_plane_bytes(passChunks) * (hcChains ? 2 : 1)) : nullptr, hcDepth, s, c->timer.hook(), (u32*)(total + 4), nullptr, nullptr, pl, dix);      // (the claim counter: a word of `total`'s 64 bytes)
+        launch_lz(pass_lz(c, ls, fr, src, n, nChunks, passChunks, frames, nullptr));
         if (fr.ldm) {       // long-distance matches into the finder's sequence store (ldm.hip); the splits are counted first to size the workspace
             const u64 span = (u64)frameBlocks * chunkBytes;
             // a referenced prefix: splits over prefix and source as one window in the virtual coordinate (ldm.hip), nL = its end
@@ -463,21 +495,21 @@ static size_t compress_range(ZSTD_CCtx* c, const CallParams& cp, u8* d_dst, size
                 launch_ldm_rest(src, nL, nChunks, chunkBytes, span, fr.ldmP, nSplits, (u8*)c->ldmSmall.p, (u8*)c->ldmBig.p, seqs, lits, meta, s, c->timer.hook(), lp);
             }
         }
-        launch_huf_build(lits, meta, tables, slots, nChunks, rs.rawLiterals, src, chunkBytes, s, c->timer.hook(), dct, frameBlocks);
+        launch_huf_build(lits, meta, tables, slots, nChunks, rs.rawLiterals, src, frames, s, c->timer.hook(), dct);
         if (cp.checksumFlag && fr.single) {
             // XXH64 does not merge: the whole content is one serial chain, carried from pass to pass (and from batch to batch); the
             // pass that ends the frame files the hash with its last block
-            const bool ends = place.at + n == sfTotal;
+            const bool ends = frames.at + n == sfTotal;
             launch_stream_xxh((XxhCarry*)c->sfXxh.p, src, n, ends ? 1u : 0u, s);
             if (ends) launch_xxh_carry_file((const XxhCarry*)c->sfXxh.p, meta + (nChunks - 1), s);
             c->timer.mark("xxh64", s);
-        } else if (cp.checksumFlag) { launch_xxh64(src, n, meta, nChunks, chunkBytes, frameBlocks, s);             c->timer.mark("xxh64", s); }
-        launch_seq_encode(seqs, meta, slots, nChunks, strategy, (cp.checksumFlag ? 1u : 0u) | (withSize ? 0u : 2u) | (hdrWindow << 8), 1, dictID, dictIdBytes, initReps, frameBlocks, chunkBytes, n, s, dct, nullptr, pl);   c->timer.mark("seq_encode", s);
+        } else if (cp.checksumFlag) { launch_xxh64(src, meta, nChunks, frames, s);             c->timer.mark("xxh64", s); }
+        launch_seq_encode(seqs, meta, slots, nChunks, ls.strategy, ls.header, 1, ls.initReps, frames, s, dct);   c->timer.mark("seq_encode", s);
         launch_scan_sizes(meta, nChunks, offsets, total, s);                       c->timer.mark("scan", s);
         if (c->seekOn) {        // the pass's frames into the call's seek table
             const u32 nFrames = (nChunks + (frameBlocks ? frameBlocks : 1u) - 1) / (frameBlocks ? frameBlocks : 1u);
             if (((size_t)c->seekCount + nFrames) * 8 > c->seekEntries.cap) return ZERR(kErrGeneric);
-            launch_seek_entries(offsets, total, nChunks, frameBlocks, chunkBytes, n, (u32*)c->seekEntries.p + 2 * (size_t)c->seekCount, s);
+            launch_seek_entries(offsets, total, nChunks, frames, (u32*)c->seekEntries.p + 2 * (size_t)c->seekCount, s);
             c->seekCount += nFrames;
         }
         const size_t room = dstCapacity > produced ? dstCapacity - produced : 0;
@@ -492,10 +524,7 @@ static size_t compress_range(ZSTD_CCtx* c, const CallParams& cp, u8* d_dst, size
         }
         if (isErr(stream_wait(s))) return ZERR(kErrGeneric);
         if (markAt) for (size_t i = 0; i < markAt->size(); ++i) { const u64 ck = (*markAt)[i] / chunkBytes; if (ck >= c0 && ck < c0 + nChunks) (*marks)[i] += produced; }
-        // stage times of the call = sums over its passes (inputs above 1 GiB take several)
-        c->timer.finish(); c->nStages = c->timer.n;
-        for (int i = 0; i < c->timer.n; i++) { c->stageMs[i] = (first ? 0.f : c->stageMs[i]) + c->timer.ms[i]; c->stageNames[i] = c->timer.names[i]; }
-        first = false;
+        add_stage_times(c, first);
         if (passTotal > room) return ZERR(kErrDstSizeTooSmall);
         produced += (size_t)passTotal;
         c->lastChunks = nChunks; c->lastSrc = src; c->lastChunkBytes = chunkBytes;
@@ -1322,15 +1351,15 @@ size_t ZSTDMI_debugEntropyBlock(ZSTD_CCtx* c, void* dst, size_t dstCapacity, con
     if (!cctx_workspace(c, 1)) return ZERR(kErrMemoryAllocation);
     hipStream_t s = c->stream;
     ChunkMeta m = {}; m.srcSize = (u32)srcSize; m.nbSeq = (u32)nbSeq; m.litSize = (u32)litSize;
-    m.fhSize = 4 + 1 + (srcSize < 256 ? 1 : 2);
+    m.fhSize = frame_header_bytes(FrameHeaderSpec{}, srcSize);
     if (nbSeq) (void)hipMemcpyAsync(c->seqs.p, seqs, nbSeq * sizeof(Seq), hipMemcpyHostToDevice, s);
     if (litSize) (void)hipMemcpyAsync(c->lits.p, lits, litSize, hipMemcpyHostToDevice, s);
     (void)hipMemcpyAsync(c->meta.p, &m, sizeof m, hipMemcpyHostToDevice, s);
-    launch_huf_build((u8*)c->lits.p, (ChunkMeta*)c->meta.p, (HufTable*)c->tables.p, (u8*)c->slots.p, 1, 0, nullptr, 0, s, StageHook());
+    launch_huf_build((u8*)c->lits.p, (ChunkMeta*)c->meta.p, (HufTable*)c->tables.p, (u8*)c->slots.p, 1, 0, nullptr, layout_arith(0, 0, 0), s, StageHook());
     launch_huf_encode((u8*)c->lits.p, (ChunkMeta*)c->meta.p, (HufTable*)c->tables.p, (u8*)c->slots.p, nullptr, nullptr, 0, 1, nullptr, 0, s);
     { const u32 plainReps[3] = { 1, 4, 8 };
       const Resolved rs = resolve_call(sticky_params(c), srcSize, kChunkSize);
-      launch_seq_encode((Seq*)c->seqs.p, (ChunkMeta*)c->meta.p, (u8*)c->slots.p, 1, rs.cp.strategy < kStratGreedy ? rs.cp.strategy : (u32)kStratGreedy, 0, 0, 0, 0, plainReps, 0, kChunkSize, 0, s); }
+      launch_seq_encode((Seq*)c->seqs.p, (ChunkMeta*)c->meta.p, (u8*)c->slots.p, 1, rs.cp.strategy < kStratGreedy ? rs.cp.strategy : (u32)kStratGreedy, FrameHeaderSpec{}, 0, plainReps, layout_arith(kChunkSize, 0, 0), s); }
     if (isErr(dev_read(&m, c->meta.p, sizeof m, s))) return ZERR(kErrGeneric);
     if (m.blockType != 2) return 0;
     if (m.bodySize > dstCapacity) return ZERR(kErrDstSizeTooSmall);
@@ -1347,14 +1376,14 @@ size_t ZSTDMI_debugPoisonedChunk(ZSTD_CCtx* c, unsigned nbSeq, unsigned litSize,
     // (with ZSTDMI_CCtx_setDictEntropy on and a formatted dictionary loaded, the instances that read its tables run)
     e = cctx_sync_dictionary(c); if (isErr(e)) return e;
     const DictCTables* const dct = call_dict_ctables(c, sticky_params(c));
-    ChunkMeta m = {}; m.srcSize = srcSize; m.nbSeq = nbSeq; m.litSize = litSize; m.fhSize = 7;
+    ChunkMeta m = {}; m.srcSize = srcSize; m.nbSeq = nbSeq; m.litSize = litSize; m.fhSize = frame_header_bytes(FrameHeaderSpec{}, srcSize < kChunkSize ? srcSize : kChunkSize);
     (void)hipMemsetAsync(c->seqs.p, (int)(fill & 0xFF), (size_t)kMaxSeq * sizeof(Seq), s);
     (void)hipMemsetAsync(c->lits.p, (int)(fill & 0xFF), kLitStride, s);
     (void)hipMemcpyAsync(c->meta.p, &m, sizeof m, hipMemcpyHostToDevice, s);
-    launch_huf_build((u8*)c->lits.p, (ChunkMeta*)c->meta.p, (HufTable*)c->tables.p, (u8*)c->slots.p, 1, 0, (const u8*)c->lits.p, kChunkSize, s, StageHook(), dct, 0);
+    launch_huf_build((u8*)c->lits.p, (ChunkMeta*)c->meta.p, (HufTable*)c->tables.p, (u8*)c->slots.p, 1, 0, (const u8*)c->lits.p, layout_arith(kChunkSize, 0, 0), s, StageHook(), dct);
     launch_huf_encode((u8*)c->lits.p, (ChunkMeta*)c->meta.p, (HufTable*)c->tables.p, (u8*)c->slots.p, nullptr, nullptr, 0, 1, (const u8*)c->lits.p, kChunkSize, s, dct != nullptr);
     { const u32 plainReps[3] = { 1, 4, 8 };
-      launch_seq_encode((Seq*)c->seqs.p, (ChunkMeta*)c->meta.p, (u8*)c->slots.p, 1, 1, 0, 1, 0, 0, plainReps, 0, kChunkSize, srcSize < kChunkSize ? srcSize : kChunkSize, s, dct); }
+      launch_seq_encode((Seq*)c->seqs.p, (ChunkMeta*)c->meta.p, (u8*)c->slots.p, 1, 1, FrameHeaderSpec{}, 1, plainReps, layout_arith(kChunkSize, 0, srcSize < kChunkSize ? srcSize : kChunkSize), s, dct); }
     if (isErr(dev_read(&m, c->meta.p, sizeof m, s))) return ZERR(kErrGeneric);
     c->lastChunks = 0;
     return m.outSize;
@@ -1405,7 +1434,7 @@ static size_t compress_entries(ZSTD_CCtx* c, const CallParams& cp, const u8* con
         bool batched = S && !fr.indepWindowLog && !fr.ldm && !fr.single && c->workers.size() <= 1 && (S + fr.chunkBytes - 1) / fr.chunkBytes <= passLimit;
         // multi-block frames: the blocks behind LDS history (chunks below 64 KiB; the full 64 KiB blocks with far candidates have no
         // table form, launch_lz), below 4 MiB and of at most 256 chunks (a block index and a frame size that fit chunk_frame_word);
-        // with a dictionary's entropy tables (huf_tree_kernel<true> finds a frame's first block by c % frameBlocks), or with sizes
+        // with a dictionary's entropy tables (huf_tree_kernel<true> finds a frame's first block in the arithmetic form alone), or with sizes
         // only and statistics (the trainer's finalize step), as before: alone
         if (batched && fr.frameBlocks)
             batched = S < (4u << 20) && (S + fr.chunkBytes - 1) / fr.chunkBytes <= 256 && fr.chunkBytes < kChunkSize && !dct && !d_stats;
@@ -1418,21 +1447,13 @@ static size_t compress_entries(ZSTD_CCtx* c, const CallParams& cp, const u8* con
         if (!g) { groups.push_back(Group{fr, {}}); g = &groups.back(); }
         g->members.push_back(i);
     }
-    const bool fmtDict = cp.useDict && c->dictFormatted;
-    const u32 dictID = fmtDict ? c->info.dictID : 0u;
-    const u32 dictIdBytes = (dictID && cp.dictIDFlag) ? (dictID < 256 ? 1u : dictID < 65536 ? 2u : 4u) : 0u;
-    const u32 plainReps[3] = { 1, 4, 8 };
-    const u32* const initReps = fmtDict ? c->info.rep : plainReps;
     bool first = true;
     std::vector<u8> tab; std::vector<u64> got;
     for (const Group& g : groups) {
-        const u32 cb = g.fr.chunkBytes, prefixLen = g.fr.prefixLen, frameBlocks = g.fr.frameBlocks;
+        const u32 cb = g.fr.chunkBytes, frameBlocks = g.fr.frameBlocks;
         const Resolved rs = g.fr.rs;
-        const u8* prefix = prefixLen ? (const u8*)c->dict.p + (c->dictHost.size() - prefixLen) : nullptr;
-        const DictIndexRef dixRef = { c->dictIdxEnd, c->dictIdxLen, (const u32*)c->dictIdxDev.p, c->dictIdxLog };
         const LaunchState ls = launch_state(c, cp, g.fr);
         const bool regionParse = ls.regionParse, hcChains = ls.hcChains;
-        const u32 hcDepth = ls.hcDepth, strategy = ls.strategy;
         for (size_t m0 = 0; m0 < g.members.size(); ) {
             // the pass: whole entries, up to passLimit chunks
             size_t m1 = m0; u32 nCh = 0;
@@ -1464,12 +1485,13 @@ static size_t compress_entries(ZSTD_CCtx* c, const CallParams& cp, const u8* con
                 hFirst[m - m0] = ck;
                 hDst[m - m0] = dsts ? (u64)((uintptr_t)dsts[i] - lo) : 0;
                 hCap[m - m0] = dsts ? (u64)caps[i] : ~(u64)0;
-                const u64 frameSpan = (u64)frameBlocks * cb;
+                const FrameLayout entry = layout_arith(cb, frameBlocks, sizes[i]);      // the entry as the single call frames it
                 for (u64 o = 0, k = 0; o < sizes[i]; o += cb, ++ck, ++k) {
                     hFrom[ck] = (u64)(uintptr_t)(srcs[i] + o); hLen[ck] = (u32)(sizes[i] - o < cb ? sizes[i] - o : cb);
-                    if (frameBlocks) {          // block k % frameBlocks of the frame that starts at fStart, as the single call counts them
-                        const u64 fStart = (k - k % frameBlocks) * cb;
-                        hFrame[ck] = chunk_frame_word((u32)(k % frameBlocks), (u32)(sizes[i] - fStart < frameSpan ? sizes[i] - fStart : frameSpan));
+                    if (frameBlocks) {
+                        const BlockPlace at = block_place<kArith>(entry, (u32)k);
+                        assert(at.block < kFrameWordBlocks && at.frameLen < kFrameWordLen);
+                        hFrame[ck] = chunk_frame_word(at.block, (u32)at.frameLen);
                     }
                 }
             }
@@ -1483,16 +1505,16 @@ static size_t compress_entries(ZSTD_CCtx* c, const CallParams& cp, const u8* con
             if (hipMemcpyAsync(dTab, tab.data(), tabBytes, hipMemcpyHostToDevice, s) != hipSuccess) return ZERR(kErrGeneric);
             const u8* stage = (const u8*)c->batchStage.p;
             Seq* seqs = (Seq*)c->seqs.p; u8* lits = (u8*)c->lits.p; ChunkMeta* meta = (ChunkMeta*)c->meta.p;
-            HufTable* tables = (HufTable*)c->tables.p; u8* slots = (u8*)c->slots.p; u64* offsets = (u64*)c->offsets.p; u64* total = (u64*)c->total.p;
+            HufTable* tables = (HufTable*)c->tables.p; u8* slots = (u8*)c->slots.p; u64* offsets = (u64*)c->offsets.p;
             const u64 stagedBytes = (u64)nCh * cb;
             c->timer.begin(s);
             launch_batch_stage((const u64*)dTab, dLen, (u8*)c->batchStage.p, nCh, cb, s);      c->timer.mark("batch_stage", s);
-            launch_lz(rs.finder, stage, stagedBytes, nCh, seqs, lits, meta, prefix, prefixLen, cb, dictIdBytes | (cp.contentSizeFlag ? 0u : 0x100u), rs.minStrideLog, ls.lzFrameBlocks,
-                      regionParse ? (u16*)c->cand.p : nullptr, hcChains ? (u16*)((u8*)c->cand.p + cand_plane_bytes(nCh)) : nullptr,
-                      regionParse ? (u32*)((u8*)c->cand.p + cand_plane_bytes(nCh) * (hcChains ? 2 : 1)) : nullptr, hcDepth, s, c->timer.hook(), (u32*)(total + 4), dLen, dFrame, nullptr, g.fr.dictIndex ? &dixRef : nullptr);
-            launch_huf_build(lits, meta, tables, slots, nCh, rs.rawLiterals, stage, cb, s, c->timer.hook(), dct, 0);      // (dct: single-block frames only, see above)
-            if (cp.checksumFlag) { launch_xxh64(stage, stagedBytes, meta, nCh, cb, frameBlocks, s, dLen, dFrame);        c->timer.mark("xxh64", s); }
-            launch_seq_encode(seqs, meta, slots, nCh, strategy, (cp.checksumFlag ? 1u : 0u) | (cp.contentSizeFlag ? 0u : 2u), 1, dictID, dictIdBytes, initReps, frameBlocks, cb, stagedBytes, s, dct, dFrame);
+            // (multi-block frames: each chunk's place from the table; else every chunk a frame.  dct: single-block frames only, see above)
+            const FrameLayout frames = dFrame ? layout_table(cb, frameBlocks, dFrame) : layout_arith(cb, 0, stagedBytes);
+            launch_lz(pass_lz(c, ls, g.fr, stage, stagedBytes, nCh, nCh, frames, dLen));
+            launch_huf_build(lits, meta, tables, slots, nCh, rs.rawLiterals, stage, frames, s, c->timer.hook(), dct);
+            if (cp.checksumFlag) { launch_xxh64(stage, meta, nCh, frames, s, dLen);        c->timer.mark("xxh64", s); }
+            launch_seq_encode(seqs, meta, slots, nCh, ls.strategy, ls.header, 1, ls.initReps, frames, s, dct);
             c->timer.mark("seq_encode", s);
             if (d_stats) launch_seq_stats(seqs, lits, meta, nCh, stage, cb, d_stats, s);
             launch_batch_place(meta, nEnt, (const u32*)(dTab + atFirst), (const u64*)(dTab + atDst), (const u64*)(dTab + atCap), span, offsets, dGot, s);
@@ -1503,9 +1525,7 @@ static size_t compress_entries(ZSTD_CCtx* c, const CallParams& cp, const u8* con
             }
             got.resize(nEnt);
             if (isErr(dev_read(got.data(), dGot, (size_t)nEnt * 8, s))) return ZERR(kErrGeneric);
-            c->timer.finish(); c->nStages = c->timer.n;
-            for (int i = 0; i < c->timer.n; i++) { c->stageMs[i] = (first ? 0.f : c->stageMs[i]) + c->timer.ms[i]; c->stageNames[i] = c->timer.names[i]; }
-            first = false;
+            add_stage_times(c, first);
             for (u32 e = 0; e < nEnt; ++e) outSizes[g.members[m0 + e]] = (size_t)got[e];
             m0 = m1;
         }
