@@ -327,10 +327,21 @@ size_t ZSTDMI_CCtx_setDictEntropy(ZSTD_CCtx* cctx, unsigned mode);
  * as without the switch, and ZSTDMI_CCtx_setDictEntropy composes with it.  Honoured by ZSTD_compress2, ZSTDMI_compressDevice,
  * ZSTDMI_compressBatch (bytes equal to the single call; entries up to 64 KiB are one block), ZSTD_compressStream2,
  * ZSTDMI_debugCompressSamples and contexts with several device workers.  The switch changes nothing without a dictionary, at levels
- * whose finder is not the fast one (>= 3), under ZSTD_c_windowLog 10 .. 15, behind ZSTD_CCtx_refPrefix and in ZSTD_compressCCtx; what
+ * whose finder is not the fast one (>= 3; ZSTDMI_CCtx_setDictIndexStrategy below extends it to levels 3-4), under ZSTD_c_windowLog 10 .. 15, behind ZSTD_CCtx_refPrefix and in ZSTD_compressCCtx; what
  * a dictionary is refused with (long-distance matching above one block, ZSTDMI_CCtx_setSingleFrame) stays refused.  Dictionary
  * content in front of its last 188 KiB is not matched against.  Every zstd decoder holding the dictionary reads the frames. */
 size_t ZSTDMI_CCtx_setDictIndex(ZSTD_CCtx* cctx, unsigned mode);
+/* The highest strategy at which an index that is switched on (ZSTDMI_CCtx_setDictIndex(1)) is used.
+ * 1 = fast only (the default: exactly what ZSTDMI_CCtx_setDictIndex describes above); 2 = also doubleFast (level 3, the default
+ * level, and level 4: wherever the call resolves to the dual-hash finder).  Sticky; touches no device.  NULL: GENERIC.  0 or above 2:
+ * parameter_outOfBound (3+ is kept for the chain finder of the levels >= 5, which the index does not serve).
+ * With the index off the setting changes nothing.  With it on, a change of the setting has a loaded dictionary uploaded again by
+ * the next call that uses it; ZSTD_CCtx_loadDictionary, ZSTDMI_CCtx_setDictIndex and this call may come in any order, and the level
+ * or ZSTD_c_strategy may change between calls without another load.  At 2 an upload builds three tables over the same bytes (the
+ * fast finder's, and one per hash of the dual finder: at most 1 MiB each); a position the dual finder probes looks up one candidate
+ * in each of its two, behind its four candidates in the block, and a dictionary candidate has to be longer to win.  Framing, entry
+ * points, what stays unchanged (now: levels >= 5) and the refusals are those of ZSTDMI_CCtx_setDictIndex. */
+size_t ZSTDMI_CCtx_setDictIndexStrategy(ZSTD_CCtx* cctx, unsigned maxStrategy);
 /* (debug) dictionary content bytes the index covers: 0 with the switch off, without a dictionary, or for a formatted dictionary no
  * call has validated on a device yet; -1 without a context */
 long long ZSTDMI_debugDictIndexed(const ZSTD_CCtx* cctx);

@@ -9,10 +9,14 @@ with history of the default settings — at the same kinds and levels.  Per poin
 Best of 3 after a warm-up call of the same shape; the host clock stops after the call's final synchronise (every call ends with one).
 The input is 16 MiB of generated data repeated (entries are independent, so the repeats are nobody's match).
 python tools/batch_time.py [MiB] [--dict-entropy] [--dict-row] [--frames-rows] [--measure-only] [--dict-index-rows] [--dict-index]
+                           [--level=N] [--dict-index-strategy=N]
   --dict-index-rows : only the rows of ZSTDMI_CCtx_setDictIndex, batch calls alone: 4 KiB text entries at level 1 with
                    tests/golden/train_default_text.dict, and the 1000 held-out JSON records of tests/golden/make_golden_train.py
                    tiled to the total with train_default_json.dict; the ratio, the batch call's ms and its stage times
   --dict-index   : those rows with the switch on (without it they also run on a library from before the switch existed)
+  --level=N      : those rows at level N instead of 1 (3: the dual-hash finder)
+  --dict-index-strategy=N : those rows with ZSTDMI_CCtx_setDictIndexStrategy(N) (2: the index also serves level 3; without the flag the
+                   call is not made, so the rows also run on a library from before it existed)
   --dict-entropy : the dictionary row with ZSTDMI_CCtx_setDictEntropy on (the dictionary's entropy tables in the compressor)
   --dict-row     : only the dictionary row
   --frames-rows  : only the 256 KiB and 1 MiB rows
@@ -28,8 +32,12 @@ lib = z._ffi.load()
 MiB = 1 << 20
 FLAGS = [a for a in sys.argv[1:] if a.startswith("--")]
 ARGS = [a for a in sys.argv[1:] if not a.startswith("--")]
+VALUED = {f.split("=", 1)[0]: int(f.split("=", 1)[1]) for f in FLAGS if "=" in f}
+FLAGS = [f for f in FLAGS if "=" not in f]
 assert all(f in ("--dict-entropy", "--dict-row", "--frames-rows", "--measure-only", "--dict-index-rows", "--dict-index") for f in FLAGS), FLAGS
+assert all(f in ("--level", "--dict-index-strategy") for f in VALUED), VALUED
 DICT_INDEX_ROWS, DICT_INDEX = "--dict-index-rows" in FLAGS, "--dict-index" in FLAGS
+INDEX_LEVEL, INDEX_STRATEGY = VALUED.get("--level", 1), VALUED.get("--dict-index-strategy")
 DICT_ENTROPY, DICT_ROW, FRAMES_ROWS, MEASURE_ONLY = "--dict-entropy" in FLAGS, "--dict-row" in FLAGS, "--frames-rows" in FLAGS, "--measure-only" in FLAGS
 total = (int(ARGS[0]) if ARGS else 256) * MiB
 SAMPLE = 4096
@@ -73,9 +81,10 @@ def dict_index_rows():
     recs = mgt.json_records(2000, 77)[1000:]
     json_blob = b"".join(recs); json_sizes = [len(r) for r in recs]
     reps = total // len(json_blob)
-    rows = [("text 4 KiB L1 train_default_text", "train_default_text.dict", text, [4096] * (total // 4096)),
-            ("json records L1 train_default_json", "train_default_json.dict", json_blob * reps, json_sizes * reps)]
-    print(f"dictionary index {'on' if DICT_INDEX else 'off'}; entropy tables {'on' if DICT_ENTROPY else 'off'}", flush=True)
+    rows = [(f"text 4 KiB L{INDEX_LEVEL} train_default_text", "train_default_text.dict", text, [4096] * (total // 4096)),
+            (f"json records L{INDEX_LEVEL} train_default_json", "train_default_json.dict", json_blob * reps, json_sizes * reps)]
+    print(f"level {INDEX_LEVEL}; dictionary index {'on' if DICT_INDEX else 'off'}, up to strategy {INDEX_STRATEGY if INDEX_STRATEGY else '1 (not set)'}; "
+          f"entropy tables {'on' if DICT_ENTROPY else 'off'}", flush=True)
     for name, dname, blob, szs in rows:
         dic = open(os.path.join(golden, dname), "rb").read()
         src = torch.from_numpy(np.frombuffer(blob, dtype=np.uint8).copy()).cuda()
@@ -86,9 +95,11 @@ def dict_index_rows():
         dst = torch.empty(sum(caps) + 64, dtype=torch.uint8, device="cuda")
         out = torch.empty(len(blob), dtype=torch.uint8, device="cuda")
         c, d = lib.ZSTD_createCCtx(), lib.ZSTD_createDCtx()
-        lib.ZSTD_CCtx_setParameter(c, 100, 1)
+        lib.ZSTD_CCtx_setParameter(c, 100, INDEX_LEVEL)
         if DICT_INDEX:
             ok(lib.ZSTDMI_CCtx_setDictIndex(c, 1))
+        if INDEX_STRATEGY:
+            ok(lib.ZSTDMI_CCtx_setDictIndexStrategy(c, INDEX_STRATEGY))
         if DICT_ENTROPY:
             ok(lib.ZSTDMI_CCtx_setDictEntropy(c, 1))
         torch.cuda.synchronize(); t0 = time.perf_counter()

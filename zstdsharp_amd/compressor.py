@@ -72,6 +72,7 @@ class Compressor(_PrefixHolder):
         self._seek_table = False
         self._dict_entropy = False
         self._dict_index = False
+        self._dict_index_strategy = 1
         self._single_frame = False
         self.Level = level if level else self.DefaultCompressionLevel
 
@@ -160,6 +161,17 @@ class Compressor(_PrefixHolder):
         self._ensure_not_disposed()
         ensure_zstd_success(self._lib, self._lib.ZSTDMI_CCtx_setDictIndex(self.cctx, 1 if on else 0))
         self._dict_index = bool(on)
+
+    # ---- how far up the strategies dict_index reaches (ZSTDMI_CCtx_setDictIndexStrategy): 1 = fast only (default), 2 = also doubleFast (level 3) ----
+    @property
+    def dict_index_strategy(self) -> int:
+        return self._dict_index_strategy
+
+    @dict_index_strategy.setter
+    def dict_index_strategy(self, max_strategy):
+        self._ensure_not_disposed()
+        ensure_zstd_success(self._lib, self._lib.ZSTDMI_CCtx_setDictIndexStrategy(self.cctx, int(max_strategy)))
+        self._dict_index_strategy = int(max_strategy)
 
     # ---- one frame per Wrap and per stream session (ZSTDMI_CCtx_setSingleFrame), as the reference writes; off by default ----
     @property

@@ -210,10 +210,13 @@ __device__ __forceinline__ u32 match_len_dict(const LzLds& L, u32 p, const u8* _
     return l >= 4 ? l : 0;
 }
 
+// HASH: the finder's hash that the table serves: 0 = hash6p (fast), 1 = hash8p (the dual finder's long one), 2 = hash_shortp<5> (its short one)
+template <int HASH> __device__ __forceinline__ u32 didx_hash(u64 w) { return HASH == 0 ? hash6p(w) : HASH == 1 ? hash8p(w) : hash_shortp<5>(w); }
+template <int HASH>
 __global__ __launch_bounds__(256) void dict_index_kernel(const u8* __restrict__ content, const u32 len, u32* __restrict__ table, const u32 log)
 {
     for (u32 i = blockIdx.x * 256 + threadIdx.x; i + 8 <= len; i += gridDim.x * 256) {
-        const u32 hp = hash6p(readLE64(content + i));
+        const u32 hp = didx_hash<HASH>(readLE64(content + i));
         atomicMax(&table[hp >> (32 - log)], ((i + 1) << 14) | didx_tag(hp, log));
     }
 }
@@ -221,7 +224,16 @@ __global__ __launch_bounds__(256) void dict_index_kernel(const u8* __restrict__ 
 void launch_dict_index(const u8* content, u32 len, u32* table, u32 log, hipStream_t stream)
 {
     (void)hipMemsetAsync(table, 0, sizeof(u32) << log, stream);
-    hipLaunchKernelGGL(dict_index_kernel, dim3((len + 255) / 256 < 256 ? (len + 255) / 256 : 256), dim3(256), 0, stream, content, len, table, log);
+    hipLaunchKernelGGL(dict_index_kernel<0>, dim3((len + 255) / 256 < 256 ? (len + 255) / 256 : 256), dim3(256), 0, stream, content, len, table, log);
+}
+// the dual finder's two tables (ZSTDMI_CCtx_setDictIndexStrategy(2)) over the same bytes, by the same rules: one per hash of a probed position
+void launch_dict_index_dual(const u8* content, u32 len, u32* tableLong, u32* tableShort, u32 log, hipStream_t stream)
+{
+    const dim3 grid((len + 255) / 256 < 256 ? (len + 255) / 256 : 256);
+    (void)hipMemsetAsync(tableLong, 0, sizeof(u32) << log, stream);
+    (void)hipMemsetAsync(tableShort, 0, sizeof(u32) << log, stream);
+    hipLaunchKernelGGL(dict_index_kernel<1>, grid, dim3(256), 0, stream, content, len, tableLong, log);
+    hipLaunchKernelGGL(dict_index_kernel<2>, grid, dim3(256), 0, stream, content, len, tableShort, log);
 }
 u32 dict_index_log(u32 len)
 {
@@ -858,6 +870,10 @@ __device__ __forceinline__ void dense_rest(LzLds& L, const u32 n, const u32 inse
 // content, whose candidates come from one gather per probed position out of the index in global memory.  The arguments an instance
 // without a dictionary prefix, a region parse and a frame place leaves idle carry it: prefixArg = the END of the dictionary's
 // content, prefixLenArg = the indexed bytes in front of it, chainAll = the index (u32 per bucket), frameAt = log2 of its buckets.
+// On the dual finder (MODE == 1; ZSTDMI_CCtx_setDictIndexStrategy(2)) the LDS tables stay what they are, 16-bit positions of the block,
+// and a probed position gathers two entries, one per hash: chainAll = the index under hash8p, chunkFrames = the one under
+// hash_shortp<5>, both of 1 << frameAt buckets.  They are loaded BEHIND the probe barrier, at the head of the position's verification
+// (DESIGN.md 3a says why), and looked at after its four in-block candidates.
 template <int MODE, int SHORT, bool DICT, bool FAR, int TAB>
 __global__ __launch_bounds__(1024) void lz_kernel(const u8* __restrict__ src, u64 srcSize,
                                                   Seq* __restrict__ seqs, u8* __restrict__ lits,
@@ -900,6 +916,7 @@ __global__ __launch_bounds__(1024) void lz_kernel(const u8* __restrict__ src, u6
     const u8* __restrict__ const farEnd = TAB == 3 ? prefixArg : in;
     const u32* __restrict__ const dictIdx = TAB == 3 ? reinterpret_cast<const u32*>(chainAll) : nullptr;
     const u32 dictLog = TAB == 3 ? (u32)frameAt : 0u;
+    const u32* __restrict__ const dictIdxS = (TAB == 3 && MODE != 0) ? chunkFrames : nullptr;
     // (independent blocks — windows below 64 KiB, where a block IS the window: no history; a dictionary is history of the frame's
     //  first block only, whose image is the layout the decoder sees)
     const u32 frameBlocks = frame_blocks_decode(frameBlocksArg).frameBlocks;
@@ -1237,6 +1254,9 @@ __global__ __launch_bounds__(1024) void lz_kernel(const u8* __restrict__ src, u6
                     }
                 } else {
                     const u32 hL = hidx(h[j]), hS = hidx(h2[j]);
+                    // TAB == 3: the dictionary's two entries, in flight while the block's own candidates are compared
+                    u32 dL = 0, dS = 0;
+                    if constexpr (TAB == 3) { dL = dictIdx[h[j] >> (32 - dictLog)]; dS = dictIdxS[h2[j] >> (32 - dictLog)]; }
                     const u32 eL = firstL[hL >> 1], eS = firstS[hS >> 1];
                     const u32 fL = eL >> 16, fS = eS >> 16;
                     // the first position of a bucket in this tile becomes the bucket's entry for later tiles: one writer per
@@ -1268,6 +1288,22 @@ __global__ __launch_bounds__(1024) void lz_kernel(const u8* __restrict__ src, u6
                         if (cp != c1p) {
                             const u32 l2 = match_len(L, p, cp, w[j], w2[j], n);
                             if (l2 > len) { len = l2; off = p - cp; }
+                        }
+                    }
+                    // the dictionary's candidates, long then short: further away than anything in the block, so they have to be longer
+                    if constexpr (TAB == 3) {
+                        u32 backL = 0;
+                        if (len < kLenCap && dL && (dL & 0x3FFFu) == didx_tag(h[j], dictLog)) {
+                            backL = farAvail - ((dL >> 14) - 1);
+                            const u32 l2 = match_len_dict(L, p, farEnd - backL, backL, w[j], n);
+                            if (l2 > len) { len = l2; off = p + backL; }
+                        }
+                        if (len < kLenCap && dS && (dS & 0x3FFFu) == didx_tag(h2[j], dictLog)) {
+                            const u32 back = farAvail - ((dS >> 14) - 1);
+                            if (back != backL) {
+                                const u32 l2 = match_len_dict(L, p, farEnd - back, back, w[j], n);
+                                if (l2 > len) { len = l2; off = p + back; }
+                            }
                         }
                     }
                 }
@@ -1812,11 +1848,13 @@ static void launch_one(const LzLaunch& a)
 
 // The indexed-dictionary instance (TAB == 3, see lz_kernel) reads the index from arguments that an instance without a dictionary
 // prefix, a region parse and a frame place leaves idle.  This is the one place that says which: prefix = the END of the dictionary's
-// content, prefixLen = the indexed bytes in front of it, chain = the index (u32 per bucket), frames.at = log2 of its buckets.
+// content, prefixLen = the indexed bytes in front of it, chain = the index (u32 per bucket), frames.at = log2 of its buckets.  The dual
+// finder has two: chain = the index under its long hash, frames.table = the one under its short hash.
 static LzLaunch dict_index_args(const LzLaunch& a)
 {
     LzLaunch x = a;
-    x.prefix = a.dix->end; x.prefixLen = a.dix->len; x.chain = (u16*)a.dix->table; x.frames.at = a.dix->log;
+    x.prefix = a.dix->end; x.prefixLen = a.dix->len; x.chain = (u16*)(a.finder == 0 ? a.dix->table : a.dix->tableLong); x.frames.at = a.dix->log;
+    if (a.finder != 0) x.frames.table = a.dix->tableShort;
     x.cand = nullptr; x.regionList = nullptr;
     return x;
 }
@@ -1831,8 +1869,9 @@ void launch_lz(const LzLaunch& a)
     if (a.dix) {
         // every chunk a frame of its own behind an indexed dictionary: the FAR instance with the dictionary as what lies in front of
         // the block.  An instance of its own, so the kernels of a context without the switch are the ones from before it existed.
-        assert(f == 0 && a.frames.form == kArith && !a.frames.frameBlocks && full && a.dix->len >= 8 && a.dix->len <= kFarMax);
-        return launch_one<0, 5, false, true, 3>(dict_index_args(a));
+        assert(f <= 1 && a.frames.form == kArith && !a.frames.frameBlocks && full && a.dix->len >= 8 && a.dix->len <= kFarMax);
+        assert(f == 0 || (a.dix->tableLong && a.dix->tableShort && !a.frames.table));
+        return f == 0 ? launch_one<0, 5, false, true, 3>(dict_index_args(a)) : launch_one<1, 5, false, true, 3>(dict_index_args(a));
     }
     if (a.frames.form == kSingle) {
         // one frame across passes: the long-distance framing's blocks (resolve_framing), each with its place in bytes.  Instances of

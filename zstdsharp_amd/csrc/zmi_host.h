@@ -16,9 +16,11 @@
 namespace zmi {
 // kernels (lz_fast.hip, huf_enc.hip, seq_enc.hip, frame.hip, decode.hip)
 // an indexed dictionary (ZSTDMI_CCtx_setDictIndex; lz_fast.hip): `end` = the byte behind its content on the device (readable for 64
-// bytes more), `len` = the indexed bytes in front of `end`, `table` = 1 << log buckets
-struct DictIndexRef { const u8* end; u32 len; const u32* table; u32 log; };
+// bytes more), `len` = the indexed bytes in front of `end`, `table` = 1 << log buckets under the fast finder's hash; tableLong /
+// tableShort (ZSTDMI_CCtx_setDictIndexStrategy(2); else null) = as many under each of the dual finder's two
+struct DictIndexRef { const u8* end; u32 len; const u32* table; u32 log; const u32* tableLong; const u32* tableShort; };
 void launch_dict_index(const u8* content, u32 len, u32* table, u32 log, hipStream_t stream);
+void launch_dict_index_dual(const u8* content, u32 len, u32* tableLong, u32* tableShort, u32 log, hipStream_t stream);
 u32 dict_index_log(u32 len);        // log2 of the buckets for `len` indexed bytes
 u32 dict_index_max();               // the most bytes an index covers (the far candidates' reach)
 // What the match finder is launched with.  frames (zmi_frame.h): chunkBytes = 64 KiB minus what lies in LDS in front of a block, rounded
@@ -29,7 +31,7 @@ u32 dict_index_max();               // the most bytes an index covers (the far c
 // chunkLens (optional): a batch of entries, each staged at a chunk boundary: per chunk its length.
 // cand / chain / regionList (null: off): workspace of the region parse, 65536 u16 per chunk (twice with the hash chains of the
 // level >= 5 search, hcDepth attempts per position) and 1 + nChunks u32.  claimCtr: a zeroable word for the chunk claims (lz_kernel).
-// dix (null: off): an indexed dictionary behind full 64 KiB chunks, each a frame of its own (fast finder only; chunkLens allowed).
+// dix (null: off): an indexed dictionary behind full 64 KiB chunks, each a frame of its own (fast finder, or the dual one where dix has its two tables; chunkLens allowed).
 struct LzLaunch {
     u32 finder;
     const u8* src; u64 srcSize; u32 nChunks;

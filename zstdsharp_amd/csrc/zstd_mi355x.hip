@@ -41,8 +41,10 @@ struct ZSTD_CCtx_s {
     // hash index over it, built once per upload (lz_fast.hip), and the fast strategy's chunks look candidates up there instead of
     // staging a tail of it.  dictWide = those bytes of a raw-content dictionary (kept at every load, so the switch may come later; a
     // formatted one has them in dictFull); dictIdxEnd / Len / Log = what the last upload indexed (Len 0: nothing).
-    int dictIndex = 0;
-    std::vector<u8> dictWide; DevBuf dictWideDev, dictIdxDev; const u8* dictIdxEnd = nullptr; u32 dictIdxLen = 0, dictIdxLog = 0;
+    // ZSTDMI_CCtx_setDictIndexStrategy (sticky): the highest strategy at which the index is used.  At 2 an upload builds, behind the
+    // fast finder's table in dictIdxDev, one table per hash of the dual finder (all three, so the level may change between calls).
+    int dictIndex = 0, dictIndexStrategy = 1;
+    std::vector<u8> dictWide; DevBuf dictWideDev, dictIdxDev; const u8* dictIdxEnd = nullptr; u32 dictIdxLen = 0, dictIdxLog = 0; bool dictIdxDual = false;
     DictInfo info = {};
     u64 dictGen = 0;            // bumped by every ZSTD_CCtx_loadDictionary: device workers copy the dictionary when theirs is older
     // ZSTDMI_CCtx_setDevices: one worker context per listed device (its own stream and workspaces there); a call's frames are
@@ -103,6 +105,7 @@ struct CallParams {
     bool useDict = true;
     bool seek = false;                  // append a seek table (ZSTDMI_CCtx_setSeekTable; ZSTD_compressCCtx: never, as it never runs LDM)
     bool dictIndex = false;             // look candidates up in the dictionary's index (ZSTDMI_CCtx_setDictIndex; ZSTD_compressCCtx uses no dictionary)
+    int dictIndexStrategy = 1;          // ... at strategies up to this one (ZSTDMI_CCtx_setDictIndexStrategy)
     bool dictEntropy = false;           // code with a formatted dictionary's entropy tables (ZSTDMI_CCtx_setDictEntropy; ZSTD_compressCCtx uses no dictionary)
     const u8* pfx = nullptr; size_t pfxSize = 0;    // the long form of a referenced prefix (compress_prefixed): device bytes in front of the ONE frame
     bool single = false;                // one frame per call (ZSTDMI_CCtx_setSingleFrame; ZSTD_compressCCtx: never, level-only parameters)
@@ -116,7 +119,7 @@ static CallParams sticky_params(const ZSTD_CCtx* c)
     p.strategy = c->strategy; p.targetLength = c->targetLength; p.windowLog = c->windowLog; p.searchLog = c->searchLog; p.minMatch = c->minMatch; p.chainLog = c->chainLog; p.useDict = true;
     p.seek = c->seekTable != 0;
     p.dictEntropy = c->dictEntropy != 0;
-    p.dictIndex = c->dictIndex != 0;
+    p.dictIndex = c->dictIndex != 0; p.dictIndexStrategy = c->dictIndexStrategy;
     p.single = c->singleFrame != 0;
     p.ldm = c->ldm; p.ldmHashLog = c->ldmHashLog; p.ldmMinMatch = c->ldmMinMatch; p.ldmBucketSizeLog = c->ldmBucketSizeLog; p.ldmHashRateLog = c->ldmHashRateLog;
     return p;
@@ -197,8 +200,12 @@ static size_t cctx_sync_dictionary(ZSTD_CCtx* c)
             end = (const u8*)c->dictWideDev.p + ixLen;
         }
         const u32 log = dict_index_log(ixLen);
-        if (!c->dictIdxDev.ensure(sizeof(u32) << log)) return ZERR(kErrMemoryAllocation);
-        launch_dict_index(end - ixLen, ixLen, (u32*)c->dictIdxDev.p, log, s);
+        const bool dual = c->dictIndexStrategy >= 2;        // (the setter marks the dictionary dirty too)
+        if (!c->dictIdxDev.ensure((sizeof(u32) << log) * (dual ? 3 : 1))) return ZERR(kErrMemoryAllocation);
+        u32* const tables = (u32*)c->dictIdxDev.p;          // fast [| long | short], 1 << log entries each
+        launch_dict_index(end - ixLen, ixLen, tables, log, s);
+        if (dual) launch_dict_index_dual(end - ixLen, ixLen, tables + ((size_t)1 << log), tables + ((size_t)2 << log), log, s);
+        c->dictIdxDual = dual;
         if (isErr(stream_wait(s))) return ZERR(kErrGeneric);
         c->dictIdxEnd = end; c->dictIdxLen = ixLen; c->dictIdxLog = log;
     }
@@ -307,11 +314,12 @@ static Framing resolve_framing(const ZSTD_CCtx* c, const CallParams& cp, size_t 
         f.chunkBytes = chunkBytes; f.frameBlocks = frameBlocks; f.rs = rf;
         return f;
     }
-    // An indexed dictionary at the fast strategy: nothing of it is staged, so a chunk is a whole 64 KiB block and every chunk a
-    // single-segment frame behind the dictionary (ZSTD_c_windowLog 10 .. 15 keeps its own framing: a window below the block)
+    // An indexed dictionary at the fast strategy — and, with ZSTDMI_CCtx_setDictIndexStrategy(2), at doubleFast: nothing of it is
+    // staged, so a chunk is a whole 64 KiB block and every chunk a single-segment frame behind the dictionary (ZSTD_c_windowLog
+    // 10 .. 15 keeps its own framing: a window below the block)
     if (cp.useDict && cp.dictIndex && dict_index_len(c) && !(cp.windowLog >= 10 && cp.windowLog < (int)kChunkLog)) {
         const Resolved rx = resolve_call(cp, paramSize, kChunkSize);
-        if (rx.finder == 0) { Framing f; f.prefixLen = 0; f.chunkBytes = kChunkSize; f.frameBlocks = 0; f.rs = rx; f.dictIndex = true; return f; }
+        if (rx.finder == 0 || (rx.finder == 1 && cp.dictIndexStrategy >= 2)) { Framing f; f.prefixLen = 0; f.chunkBytes = kChunkSize; f.frameBlocks = 0; f.rs = rx; f.dictIndex = true; return f; }
     }
     const u32 prefixLen = cp.useDict ? dict_prefix_len(c, paramSize) : 0u;
     u32 chunkBytes = kChunkSize - round_tile(prefixLen);
@@ -398,7 +406,11 @@ static LaunchState launch_state(const ZSTD_CCtx* c, const CallParams& cp, const 
     for (int i = 0; i < 3; ++i) L.initReps[i] = fmtDict ? c->info.rep[i] : plainReps[i];
     L.dct = call_dict_ctables(c, cp);
     L.prefix = fr.prefixLen ? (const u8*)c->dict.p + (c->dictHost.size() - fr.prefixLen) : nullptr;
-    L.dix = DictIndexRef{ c->dictIdxEnd, c->dictIdxLen, (const u32*)c->dictIdxDev.p, c->dictIdxLog };
+    {
+        const u32* const tables = (const u32*)c->dictIdxDev.p;
+        const bool dual = c->dictIdxDual && tables;
+        L.dix = DictIndexRef{ c->dictIdxEnd, c->dictIdxLen, tables, c->dictIdxLog, dual ? tables + ((size_t)1 << c->dictIdxLog) : nullptr, dual ? tables + ((size_t)2 << c->dictIdxLog) : nullptr };
+    }
     return L;
 }
 // the finder's launch for a pass of nChunks chunks (the candidate planes lie where a workspace for planeChunks chunks puts them:
@@ -1055,7 +1067,7 @@ static size_t compress_multi(ZSTD_CCtx* c, const CallParams& cp, void* dst, size
     for (ZSTD_CCtx* w : c->workers) {
         w->historyBytes = c->historyBytes; w->frameBytes = c->frameBytes; w->parser = c->parser; w->passChunks = c->passChunks; w->timer.enabled = c->timer.enabled;
         w->dictEntropy = c->dictEntropy;        // (before the dictionary: a worker builds the tables when it uploads its copy)
-        w->dictIndex = c->dictIndex;            // (and the index)
+        w->dictIndex = c->dictIndex; w->dictIndexStrategy = c->dictIndexStrategy;       // (and the index, as far up the strategies as the parent's)
         if (w->dictGen != c->dictGen) {
             w->dictHost = c->dictHost; w->dictFull = c->dictFull; w->dictWide = c->dictWide; w->dictFormatted = c->dictFormatted; w->info = c->info; w->dictDirty = true; w->dictGen = c->dictGen;
         }
@@ -1316,6 +1328,16 @@ size_t ZSTDMI_CCtx_setDictIndex(ZSTD_CCtx* c, unsigned mode)
     if (mode > 1) return ZERR(kErrParameterOutOfBound);
     if (c->dictIndex != (int)mode && (c->dictFormatted || !c->dictWide.empty())) { c->dictDirty = true; c->dictGen++; }
     c->dictIndex = (int)mode;
+    return 0;
+}
+// (no device is touched: with the index on, a loaded dictionary is marked for another upload, which builds — or no longer builds —
+//  the dual finder's two tables; with it off nothing changes until it is turned on, and that setter marks the dictionary itself)
+size_t ZSTDMI_CCtx_setDictIndexStrategy(ZSTD_CCtx* c, unsigned maxStrategy)
+{
+    if (!c) return ZERR(kErrGeneric);
+    if (maxStrategy < 1 || maxStrategy > 2) return ZERR(kErrParameterOutOfBound);
+    if (c->dictIndexStrategy != (int)maxStrategy && c->dictIndex && (c->dictFormatted || !c->dictWide.empty())) { c->dictDirty = true; c->dictGen++; }
+    c->dictIndexStrategy = (int)maxStrategy;
     return 0;
 }
 long long ZSTDMI_debugDictIndexed(const ZSTD_CCtx* c) { return c ? (long long)dict_index_len(c) : -1; }
