@@ -82,7 +82,7 @@ struct LzLds {
     u16 jumpB[kTilePos];                 // second buffer of the doubling rounds; once they end it is reused as
                                          // endOf[r+1] = absolute end of the r-th selected match of the tile (u32[kTilePos/4+2]), endOf[0] = anchor
     // per-tile counters, slot = tile mod 3: between two consecutive verify barriers one slot is read (tile t), one is
-    // accumulated (tile t+1, whose fused probe/verify may already run) and the third is reset for tile t+2
+    // accumulated (tile t+1, whose probe may already run) and the third is reset for tile t+2
     u64 nzWords[3];                      // bit g = matchMask[g] != 0 (accumulated with atomicOr during verify)
     u32 matchCount[3];                   // matches in the current tile (decides sparse / dense selection)
     u16 sparseList[64];                  // sparse path: the tile's matches in position order
@@ -853,36 +853,49 @@ __device__ __forceinline__ void dense_rest(LzLds& L, const u32 n, const u32 inse
 #endif
 }
 
-// MODE 0 = fast strategy (one 6-byte hash; levels 1-2 and the negative levels); 1 = doubleFast strategy (8-byte + SHORT-byte
+// MODE 0 = fast strategy (one 6-byte hash; levels 1-2 and the negative levels); 1 = doubleFast strategy (8-byte + 5-byte
 // hashes, four candidates per position; levels 3-4: the place of U/ZstdDoubleFast.cs:51-247); 2 = greedy and above (the dual
 // candidates + one-step lazy deferral; levels >= 5: the place of U/ZstdLazy.cs:1743-2032).  The host maps strategy -> MODE.
 // DICT: a dictionary prefix is present (its bounds checks fold away otherwise)
 // FAR: matches may start in the input in front of the block (same frame): those candidates are verified against global memory
-// TAB: the form in which a block's place in its frame is stated (zmi_frame.h, block_place): 0 = from the chunk's index and the call's
-// size, 1 = from a table (chunkFrames: a batch of entries of different lengths), 2 = in bytes (frameAt / frameTotal: the call's input
-// is ONE frame that passes and a stream's batches cut anywhere, ZSTDMI_CCtx_setSingleFrame; the frameAt bytes in front
-// of src are readable there as history).  A template parameter because these kernels sit at the register cap: as a run-time branch
-// the pointer and the select added scratch to the instances every single call of the levels >= 3 runs; an instance
-// holds the code of its own form alone.
+// TAB: the form in which a block's place in its frame is stated (zmi_frame.h, block_place): kArith = from the chunk's index and the
+// call's size, kTable = from a table (chunkFrames: a batch of entries of different lengths), kSingle = in bytes (frameAt / frameTotal:
+// the call's input is ONE frame that passes and a stream's batches cut anywhere, ZSTDMI_CCtx_setSingleFrame; the frameAt
+// bytes in front of src are readable there as history) — or kPlaceIndexed, below.  A template parameter because these kernels sit at
+// the register cap: as a run-time branch the pointer and the select added scratch to the instances every single call of the levels
+// >= 3 runs; an instance holds the code of its own form alone.
+// kPlaceIndexed (on the FAR instances of the fast and the dual finder): every chunk is a frame of its own — no place to compute —
+// behind an INDEXED dictionary, LzArgs::dix (ZSTDMI_CCtx_setDictIndex).  The chunk alone sits in LDS; what lies "in front
+// of the block" is the dictionary's content, whose candidates come from one gather per probed position out of dix.table in global
+// memory.  On the dual finder (MODE == 1; ZSTDMI_CCtx_setDictIndexStrategy(2)) the LDS tables stay what they are, 16-bit positions of
+// the block, and a probed position gathers two entries, one per hash: dix.tableLong under hash8p, dix.tableShort under hash_shortp<5>.
+// They are loaded BEHIND the probe barrier, at the head of the position's verification (DESIGN.md 3a says why), and looked at after
+// its four in-block candidates.
+constexpr int kPlaceIndexed = 3;         // beside FrameForm's three values: lz_kernel's TAB alone takes it
+// What lz_kernel is launched with: launch_one fills it from LzLaunch (zmi_host.h, which says what the fields hold).
 // fh: the frame header (zmi_frame.h), of which the finder needs the size: it leaves in ChunkMeta::fhSize what seq_encode_kernel will write.
-// TAB == 3 (on the FAR instance of the fast finder): every chunk is a frame of its own behind an INDEXED dictionary
-// (ZSTDMI_CCtx_setDictIndex).  The chunk alone sits in LDS; what lies "in front of the block" is the dictionary's
-// content, whose candidates come from one gather per probed position out of the index in global memory.  The arguments an instance
-// without a dictionary prefix, a region parse and a frame place leaves idle carry it: prefixArg = the END of the dictionary's
-// content, prefixLenArg = the indexed bytes in front of it, chainAll = the index (u32 per bucket), frameAt = log2 of its buckets.
-// On the dual finder (MODE == 1; ZSTDMI_CCtx_setDictIndexStrategy(2)) the LDS tables stay what they are, 16-bit positions of the block,
-// and a probed position gathers two entries, one per hash: chainAll = the index under hash8p, chunkFrames = the one under
-// hash_shortp<5>, both of 1 << frameAt buckets.  They are loaded BEHIND the probe barrier, at the head of the position's verification
-// (DESIGN.md 3a says why), and looked at after its four in-block candidates.
-template <int MODE, int SHORT, bool DICT, bool FAR, int TAB>
-__global__ __launch_bounds__(1024) void lz_kernel(const u8* __restrict__ src, u64 srcSize,
-                                                  Seq* __restrict__ seqs, u8* __restrict__ lits,
-                                                  ChunkMeta* __restrict__ meta,
-                                                  const u8* __restrict__ prefixArg, const u32 prefixLenArg, const u32 chunkBytes,
-                                                  const FrameHeaderSpec fh, const u32 minStrideLog, const u32 frameBlocksArg, u16* __restrict__ candAll, u16* __restrict__ chainAll, u32* __restrict__ regionList, const u32 nChunks,
-                                                  u32* __restrict__ claimCtr, const u32* __restrict__ chunkLens, const u32* __restrict__ chunkFrames,
-                                                  const u64 frameAt, const u64 frameTotal)
+// frameBlocksArg: frame_blocks_encode.  cand, regionList: null = no region parse.  claimCtr: null = chunk c + gridDim.x is next.
+struct LzArgs {
+    const u8* src; u64 srcSize;
+    Seq* seqs; u8* lits; ChunkMeta* meta;
+    const u8* prefix; u32 prefixLen, chunkBytes;
+    FrameHeaderSpec fh;
+    u32 minStrideLog, frameBlocksArg, nChunks;
+    u16* cand; u32* regionList; u32* claimCtr;
+    const u32* chunkLens; const u32* chunkFrames;
+    u64 frameAt, frameTotal;
+    DictIndexRef dix;
+};
+template <int MODE, bool DICT, bool FAR, int TAB>
+__global__ __launch_bounds__(1024) void lz_kernel(const LzArgs a)
 {
+    const u8* __restrict__ const src = a.src; const u64 srcSize = a.srcSize;
+    Seq* __restrict__ const seqs = a.seqs; u8* __restrict__ const lits = a.lits; ChunkMeta* __restrict__ const meta = a.meta;
+    const u32 chunkBytes = a.chunkBytes, minStrideLog = a.minStrideLog, nChunks = a.nChunks;
+    const FrameHeaderSpec fh = a.fh;
+    u16* __restrict__ const candAll = a.cand; u32* __restrict__ const regionList = a.regionList; u32* __restrict__ const claimCtr = a.claimCtr;
+    const u32* __restrict__ const chunkLens = a.chunkLens; const u32* __restrict__ const chunkFrames = a.chunkFrames;
+    const u64 frameAt = a.frameAt, frameTotal = a.frameTotal;
     extern __shared__ __attribute__((aligned(16))) u8 ldsRaw[];
     LzLds& L = *reinterpret_cast<LzLds*>(ldsRaw);
     const u32 tid = threadIdx.x, lane = lane_id(), wave = uniform(wave_id());
@@ -893,7 +906,8 @@ __global__ __launch_bounds__(1024) void lz_kernel(const u8* __restrict__ src, u6
     // workgroup's first arrives prefetched (a stamped build had 42 % of an unprefetched Zipf chunk's time in this load).  The claim
     // is made one chunk ahead of the prefetch (thread 0 holds the answer in a register through a chunk), so nobody waits for it.
     constexpr bool kPrefetch = MODE == 0 && !DICT && !FAR;      // (the dual-hash finders have no 16 registers to spare)
-    constexpr int kPlaceForm = TAB == 1 ? kTable : TAB == 2 ? kSingle : kArith;
+    constexpr bool kIndexed = TAB == kPlaceIndexed;
+    constexpr int kPlaceForm = kIndexed ? kArith : TAB;
     uint4 pf0 = {0, 0, 0, 0}, pf1 = pf0, pf2 = pf0, pf3 = pf0; bool pfValid = false;
     const bool claiming = kPrefetch && claimCtr != nullptr;     // uniform
     u32 claimed = 0;                                            // thread 0: the chunk after the next
@@ -913,22 +927,22 @@ __global__ __launch_bounds__(1024) void lz_kernel(const u8* __restrict__ src, u6
     const u64 base = (u64)c * cb;
     const u8* __restrict__ in = src + base;
     // the byte behind the far history's last: the block itself, or the end of an indexed dictionary
-    const u8* __restrict__ const farEnd = TAB == 3 ? prefixArg : in;
-    const u32* __restrict__ const dictIdx = TAB == 3 ? reinterpret_cast<const u32*>(chainAll) : nullptr;
-    const u32 dictLog = TAB == 3 ? (u32)frameAt : 0u;
-    const u32* __restrict__ const dictIdxS = (TAB == 3 && MODE != 0) ? chunkFrames : nullptr;
+    const u8* __restrict__ const farEnd = kIndexed ? a.dix.end : in;
+    const u32* __restrict__ const dictIdx = !kIndexed ? nullptr : MODE == 0 ? a.dix.table : a.dix.tableLong;
+    const u32 dictLog = kIndexed ? a.dix.log : 0u;
+    const u32* __restrict__ const dictIdxS = (kIndexed && MODE != 0) ? a.dix.tableShort : nullptr;
     // (independent blocks — windows below 64 KiB, where a block IS the window: no history; a dictionary is history of the frame's
     //  first block only, whose image is the layout the decoder sees)
-    const u32 frameBlocks = frame_blocks_decode(frameBlocksArg).frameBlocks;
-    const bool indep = frame_blocks_decode(frameBlocksArg).independent;
+    const u32 frameBlocks = frame_blocks_decode(a.frameBlocksArg).frameBlocks;
+    const bool indep = frame_blocks_decode(a.frameBlocksArg).independent;
     // the block's place in its frame (zmi_frame.h: from the call's size, from a batch's table beside chunkLens, or — one frame across
     // passes — counted in bytes); a chunk that is a frame of its own, and every chunk behind an indexed dictionary, has none
     const bool framed = (DICT || FAR) && frameBlocks;
     const FrameLayout frames = { kPlaceForm, cb, frameBlocks, srcSize, chunkFrames, frameAt, frameTotal };
     const BlockPlace place = framed ? block_place<kPlaceForm>(frames, c) : block_alone(0);
     const u32 bf = place.block;
-    const u32 farAvail = FAR ? TAB == 3 ? prefixLenArg : place.front < kFarMax ? (u32)place.front : kFarMax : 0u;      // bytes of far history in front of the block
-    u32 prefixLen = prefixLenArg; const u8* __restrict__ prefix = prefixArg;
+    const u32 farAvail = FAR ? kIndexed ? a.dix.len : place.front < kFarMax ? (u32)place.front : kFarMax : 0u;      // bytes of far history in front of the block
+    u32 prefixLen = a.prefixLen; const u8* __restrict__ prefix = a.prefix;
     if (DICT && frameBlocks && !indep) { prefixLen = place.front < hist ? (u32)place.front : hist; prefix = in - prefixLen; }
     if (DICT && indep && bf) prefixLen = 0;
     const u32 lowLimit = DICT ? hist - prefixLen : 0u;
@@ -1009,7 +1023,7 @@ __global__ __launch_bounds__(1024) void lz_kernel(const u8* __restrict__ src, u6
             pfValid = true;
         }
     }
-    if (FAR && TAB != 3 && farAvail) {
+    if (FAR && !kIndexed && farAvail) {
         // the table starts out holding the input in front of the block (what the reference's table still holds from the blocks
         // before, U/ZstdFast.cs:9-46): latest occurrence per bucket, straight from global memory
         for (u32 i = tid * kFarStep; i < farAvail; i += kTile * kFarStep) {
@@ -1045,7 +1059,7 @@ __global__ __launch_bounds__(1024) void lz_kernel(const u8* __restrict__ src, u6
         // backward: give bytes of the pending literal run to the match while they agree (ZstdFast.cs:242-247)
         // (four bytes per step: the dwords in front of the match and of its source, compared from the top)
         if (FAR && off > p) {                                          // the source lies in front of the block: byte steps against global memory
-            while (p > floorPos && off - p < farAvail && L.in[p - 1] == (TAB == 3 ? farEnd : in)[(s64)p - 1 - (s64)off]) --p;
+            while (p > floorPos && off - p < farAvail && L.in[p - 1] == farEnd[(s64)p - 1 - (s64)off]) --p;
         } else for (;;) {
             u32 room = p - floorPos;                                   // bytes the pending literal run can give
             const u32 srcRoom = p - off - lowLimit;                    // bytes in front of the source
@@ -1077,7 +1091,7 @@ __global__ __launch_bounds__(1024) void lz_kernel(const u8* __restrict__ src, u6
         for (;;) {
             const u32 pos = e + 8 * lane;              // reads past n land in the table region: harmless, clamped below
             const s32 sp = (s32)pos - (s32)off;                        // FAR: a negative source position is in front of the block
-            if constexpr (TAB == 3) {
+            if constexpr (kIndexed) {
                 // an indexed dictionary: a match into it ends with it (the 8 bytes read at its last ones end inside the padding)
                 const bool dictTail = off > p && sp > -8;
                 const u64 x = lds_load8(L.in, pos) ^ (sp < 0 ? readLE64(farEnd + sp) : lds_load8(L.in, dictTail ? 0u : (u32)sp));
@@ -1148,8 +1162,7 @@ __global__ __launch_bounds__(1024) void lz_kernel(const u8* __restrict__ src, u6
         cov = super ? superCov : L.covMask[covPar];
         // (A sparse tile could fuse probe and verify and defer its table inserts behind the verify barrier — one barrier
         // less, measured 7 % faster — but the next tile's probes would then race with those inserts and the output would
-        // depend on wave timing.  Determinism is part of the contract, so the two-barrier form stays.)
-        constexpr bool fused = false;
+        // depend on wave timing.  Determinism is part of the contract, so the two-barrier form is the only one.)
         // probed position of lattice cell c = j * kTile + tid: c * stride + a pseudo-random residue, so that a repeat of
         // earlier data lines up with inserted positions one time in `stride` whatever its distance (a fixed lattice would
         // never see a repeat whose distance is not a multiple of the stride)
@@ -1163,22 +1176,22 @@ __global__ __launch_bounds__(1024) void lz_kernel(const u8* __restrict__ src, u6
         // ---------------- probe ----------------
         // fast: h = hash product, cand = table entry.  dual: h = long product, h2 = short product, cand = tableL | tableS << 16
         u64 w[kPPT], w2[kPPT]; u32 h[kPPT], h2[kPPT], cand[kPPT]; bool valid[kPPT];
-        u32 dcand[TAB == 3 ? kPPT : 1];          // TAB == 3: the dictionary index's entries, gathered here and first looked at behind the barrier
+        u32 dcand[kIndexed ? kPPT : 1];          // an indexed dictionary's entries, gathered here and first looked at behind the barrier
 #pragma unroll
         for (u32 j = 0; j < kPPT; ++j) {
             const u32 q = probed(j), p = tileStart + q;
             valid[j] = j < nPass && j * kTile + tid < slots && p + 8 <= n && p >= lowLimit; w[j] = 0; w2[j] = 0; h[j] = 0; h2[j] = 0; cand[j] = 0;
-            if constexpr (TAB == 3) dcand[j] = 0;
+            if constexpr (kIndexed) dcand[j] = 0;
             if (j >= nPass) continue;            // uniform
             if (valid[j]) {
                 lds_load16(L.in, p, w[j], w2[j]);
                 if (MODE == 0) {
                     h[j] = hash6p(w[j]);
                     cand[j] = table[hidx(h[j])];
-                    if constexpr (TAB == 3) dcand[j] = dictIdx[h[j] >> (32 - dictLog)];
-                    if (!fused) atomicMin(&first[hidx(h[j])], ((stamp + q) << 16) | htag(h[j]));
+                    if constexpr (kIndexed) dcand[j] = dictIdx[h[j] >> (32 - dictLog)];
+                    atomicMin(&first[hidx(h[j])], ((stamp + q) << 16) | htag(h[j]));
                 } else {
-                    h[j] = hash8p(w[j]); h2[j] = hash_shortp<SHORT>(w[j]);
+                    h[j] = hash8p(w[j]); h2[j] = hash_shortp<5>(w[j]);
                     const u32 hL = hidx(h[j]), hS = hidx(h2[j]);
                     cand[j] = (u32)tableL[hL] | ((u32)tableS[hS] << 16);
                     atomicMin(&firstL[hL >> 1], ((stamp + q) << 16) | htag(h[j])); atomicMin(&firstS[hS >> 1], ((stamp + q) << 16) | htag(h2[j]));
@@ -1188,7 +1201,7 @@ __global__ __launch_bounds__(1024) void lz_kernel(const u8* __restrict__ src, u6
         ZMI_STAMP(1);
         // (LDS-only barriers in this loop: __syncthreads() also waits for the wave's outstanding global loads — the NEXT chunk's
         //  bytes, fetched on purpose behind this chunk's work — and for every sequence and literal store to be acknowledged)
-        if (!fused) lds_barrier();             // every probe of this tile precedes every insert of this tile
+        lds_barrier();                         // every probe of this tile precedes every insert of this tile
         ZMI_STAMP(2);
         u64 mmJ[kPPT], cmJ[kPPT];
         const bool slotMasks = strideLog == 0 || super;      // (uniform) array index = j * kTile + tid: a wave's ballots ARE its mask words
@@ -1204,7 +1217,7 @@ __global__ __launch_bounds__(1024) void lz_kernel(const u8* __restrict__ src, u6
             const u32 q = probed(j), p = tileStart + q;
             u32 len = 0, off = 0;
             if (valid[j]) {
-                if (MODE == 0 && !fused) atomicMax(&table[hidx(h[j])], FAR ? ((kFarMax + p + 1) << 14) | (htag(h[j]) >> 2) : ((p + 1) << 16) | htag(h[j]));
+                if (MODE == 0) atomicMax(&table[hidx(h[j])], FAR ? ((kFarMax + p + 1) << 14) | (htag(h[j]) >> 2) : ((p + 1) << 16) | htag(h[j]));
                 // (1) periods 1..4: bytes p..p+7 repeat with period d and the d bytes before p agree — runs and tiny
                 //     patterns, which neither table can see inside one tile
                 u32 per = 0;
@@ -1227,9 +1240,9 @@ __global__ __launch_bounds__(1024) void lz_kernel(const u8* __restrict__ src, u6
                     else {
                         // (2) same-tile first occurrence, (3) latest occurrence in earlier tiles: keep the longer, nearer on ties
                         const u32 tag = htag(h[j]);
-                        const u32 f = fused ? 0xFFFFFFFFu : first[hidx(h[j])];
+                        const u32 f = first[hidx(h[j])];
                         const u32 fq = (f >> 16) - stamp;                 // (an entry seen here was written by this tile: see `stamp`)
-                        if (!fused && fq < q && (f & 0xFFFFu) == tag) {
+                        if (fq < q && (f & 0xFFFFu) == tag) {
                             const u32 cpos = tileStart + fq;
                             len = match_len(L, p, cpos, w[j], w2[j], n); off = p - cpos;
                         }
@@ -1241,7 +1254,7 @@ __global__ __launch_bounds__(1024) void lz_kernel(const u8* __restrict__ src, u6
                                 if (l2 > len) { len = l2; off = kFarMax + p - crel; }
                             }
                             // the dictionary's candidate: further away than anything in the block, so it has to be longer
-                            if constexpr (TAB == 3) if (dcand[j] && (dcand[j] & 0x3FFFu) == didx_tag(h[j], dictLog) && len < kLenCap) {
+                            if constexpr (kIndexed) if (dcand[j] && (dcand[j] & 0x3FFFu) == didx_tag(h[j], dictLog) && len < kLenCap) {
                                 const u32 back = farAvail - ((dcand[j] >> 14) - 1);
                                 const u32 l2 = match_len_dict(L, p, farEnd - back, back, w[j], n);
                                 if (l2 > len) { len = l2; off = p + back; }
@@ -1254,9 +1267,9 @@ __global__ __launch_bounds__(1024) void lz_kernel(const u8* __restrict__ src, u6
                     }
                 } else {
                     const u32 hL = hidx(h[j]), hS = hidx(h2[j]);
-                    // TAB == 3: the dictionary's two entries, in flight while the block's own candidates are compared
+                    // an indexed dictionary's two entries, in flight while the block's own candidates are compared
                     u32 dL = 0, dS = 0;
-                    if constexpr (TAB == 3) { dL = dictIdx[h[j] >> (32 - dictLog)]; dS = dictIdxS[h2[j] >> (32 - dictLog)]; }
+                    if constexpr (kIndexed) { dL = dictIdx[h[j] >> (32 - dictLog)]; dS = dictIdxS[h2[j] >> (32 - dictLog)]; }
                     const u32 eL = firstL[hL >> 1], eS = firstS[hS >> 1];
                     const u32 fL = eL >> 16, fS = eS >> 16;
                     // the first position of a bucket in this tile becomes the bucket's entry for later tiles: one writer per
@@ -1291,7 +1304,7 @@ __global__ __launch_bounds__(1024) void lz_kernel(const u8* __restrict__ src, u6
                         }
                     }
                     // the dictionary's candidates, long then short: further away than anything in the block, so they have to be longer
-                    if constexpr (TAB == 3) {
+                    if constexpr (kIndexed) {
                         u32 backL = 0;
                         if (len < kLenCap && dL && (dL & 0x3FFFu) == didx_tag(h[j], dictLog)) {
                             backL = farAvail - ((dL >> 14) - 1);
@@ -1307,10 +1320,6 @@ __global__ __launch_bounds__(1024) void lz_kernel(const u8* __restrict__ src, u6
                         }
                     }
                 }
-            }
-            if (MODE != 0 && SHORT == 4) {
-                // a 4-byte match far away costs more than its literals (offset bits + three codes against ~5 bits a byte)
-                if (len == 4 && off >= 256) len = 0;
             }
             if (MODE == 2 && strideLog == 0) {
                 // lazy deferral (U/ZstdLazy.cs:1836-1870): a match yields to the one starting one byte later when that one
@@ -1352,10 +1361,6 @@ __global__ __launch_bounds__(1024) void lz_kernel(const u8* __restrict__ src, u6
         const u32 c0 = cursor > tileStart ? cursor - tileStart : 0;       // entry cursor, tile-relative
         const u32 matchCount = L.matchCount[par];
         if (tid == 0) { const u32 nx = (it + 2) % 3; L.nzWords[nx] = 0; L.matchCount[nx] = 0; }    // slot of the iteration after next: idle until the next barrier
-        if (fused) {                           // the deferred inserts of a sparse tile (every probe of the tile came before the barrier)
-#pragma unroll
-            for (u32 j = 0; j < kPPT; ++j) if (valid[j]) atomicMax(&table[hidx(h[j])], ((tileStart + probed(j) + 1) << 16) | htag(h[j]));
-        }
         // matches per 4096 positions had every position been probed
         prevDensity = (matchCount << strideLog) / nSubT;
         prevStride = strideLog;
@@ -1810,21 +1815,23 @@ extern "C" void ZSTDMI_debugReadLzStamps(unsigned long long* out16, int reset)
 }
 #endif
 
-template <int MODE, int SHORT, bool DICT, bool FAR = false, int TAB = 0>
+template <int MODE, bool DICT, bool FAR = false, int TAB = kArith>
 static void launch_one(const LzLaunch& a)
 {
     // the region parse of dense chunks: a second kernel behind a work list (see lz_region_kernel), inlined for the others
     constexpr bool kSplit = (MODE == 0 && !DICT && !FAR) || MODE == 2;
+    constexpr bool kIndexed = TAB == kPlaceIndexed;
     // (the attribute is per device: a process may hold contexts on several GPUs)
     static bool attrSet[64] = {};
     int dev = 0; (void)hipGetDevice(&dev);
     if (!attrSet[dev & 63]) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(lz_kernel<MODE, SHORT, DICT, FAR, TAB>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(LzLds));
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(lz_kernel<MODE, DICT, FAR, TAB>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(LzLds));
         if constexpr (kSplit) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(lz_region_kernel<MODE, DICT, TAB>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(LzLds));
         attrSet[dev & 63] = true;
     }
-    // (the full 64 KiB blocks with far candidates have no region parse, no per-chunk tables and nothing staged in front of them)
-    assert(!FAR || TAB == 3 || (!a.chunkLens && !a.prefixLen));
+    // (the full 64 KiB blocks with far candidates have no region parse, no per-chunk tables and nothing staged in front of them; behind
+    //  an indexed dictionary a batch's chunks do have their lengths)
+    assert(!FAR || (!a.prefixLen && (kIndexed || !a.chunkLens)));
     u16* const cand = FAR ? nullptr : a.cand;
     const u32 chunkBytes = DICT ? a.frames.chunkBytes : kChunkSize;
     const u32 frameBlocks = frame_blocks_encode((DICT || FAR) ? a.frames.frameBlocks : 0u, a.independent);
@@ -1835,28 +1842,16 @@ static void launch_one(const LzLaunch& a)
     const bool claim = MODE == 0 && !DICT && !FAR && a.claimCtr && a.nChunks > cuCount[dev & 63];
     if (claim) (void)hipMemsetAsync(a.claimCtr, 0, sizeof(u32), a.stream);
     const u32 grid = claim ? cuCount[dev & 63] : a.nChunks;
-    hipLaunchKernelGGL((lz_kernel<MODE, SHORT, DICT, FAR, TAB>), dim3(grid), dim3(kTile), sizeof(LzLds), a.stream, a.src, a.srcSize, a.seqs, a.lits, a.meta, a.prefix, a.prefixLen, chunkBytes, a.header,
-                       a.minStrideLog, frameBlocks, cand, (cand || TAB == 3) ? a.chain : nullptr, cand ? a.regionList : nullptr, a.nChunks,
-                       claim ? a.claimCtr : nullptr, a.chunkLens, a.frames.table, a.frames.at, a.frames.total);
+    const LzArgs k = { a.src, a.srcSize, a.seqs, a.lits, a.meta, a.prefix, a.prefixLen, chunkBytes, a.header, a.minStrideLog, frameBlocks, a.nChunks,
+                       cand, cand ? a.regionList : nullptr, claim ? a.claimCtr : nullptr, a.chunkLens, a.frames.table, a.frames.at, a.frames.total,
+                       kIndexed ? *a.dix : DictIndexRef{} };
+    hipLaunchKernelGGL((lz_kernel<MODE, DICT, FAR, TAB>), dim3(grid), dim3(kTile), sizeof(LzLds), a.stream, k);
     a.hook("lz_fast");
     if constexpr (kSplit) if (cand) {                      // the dense chunks' rest: 256 workgroups (one per CU) walk the list
         hipLaunchKernelGGL((lz_region_kernel<MODE, DICT, TAB>), dim3(a.nChunks < 256 ? a.nChunks : 256), dim3(kTile), sizeof(LzLds), a.stream, a.src, a.srcSize, a.seqs, a.lits, a.meta, cand, a.chain, a.regionList,
                            a.prefix, a.prefixLen, chunkBytes, frameBlocks, a.hcDepth, a.chunkLens, a.frames.table, a.frames.at);
         a.hook("lz_region");
     }
-}
-
-// The indexed-dictionary instance (TAB == 3, see lz_kernel) reads the index from arguments that an instance without a dictionary
-// prefix, a region parse and a frame place leaves idle.  This is the one place that says which: prefix = the END of the dictionary's
-// content, prefixLen = the indexed bytes in front of it, chain = the index (u32 per bucket), frames.at = log2 of its buckets.  The dual
-// finder has two: chain = the index under its long hash, frames.table = the one under its short hash.
-static LzLaunch dict_index_args(const LzLaunch& a)
-{
-    LzLaunch x = a;
-    x.prefix = a.dix->end; x.prefixLen = a.dix->len; x.chain = (u16*)(a.finder == 0 ? a.dix->table : a.dix->tableLong); x.frames.at = a.dix->log;
-    if (a.finder != 0) x.frames.table = a.dix->tableShort;
-    x.cand = nullptr; x.regionList = nullptr;
-    return x;
 }
 
 // Selects the finder's instance for a.finder: 0 = fast, 1 = dual (8-byte + 5-byte hashes), 2 = dual + lazy deferral.  (A 4-byte short
@@ -1870,25 +1865,27 @@ void launch_lz(const LzLaunch& a)
         // every chunk a frame of its own behind an indexed dictionary: the FAR instance with the dictionary as what lies in front of
         // the block.  An instance of its own, so the kernels of a context without the switch are the ones from before it existed.
         assert(f <= 1 && a.frames.form == kArith && !a.frames.frameBlocks && full && a.dix->len >= 8 && a.dix->len <= kFarMax);
-        assert(f == 0 || (a.dix->tableLong && a.dix->tableShort && !a.frames.table));
-        return f == 0 ? launch_one<0, 5, false, true, 3>(dict_index_args(a)) : launch_one<1, 5, false, true, 3>(dict_index_args(a));
+        assert(f == 0 ? a.dix->table != nullptr : (a.dix->tableLong && a.dix->tableShort));
+        // nothing is staged in front of a chunk, no chunk has a place in a frame, and there is no region parse
+        assert(!a.prefix && !a.prefixLen && !a.frames.table && !a.cand && !a.chain && !a.regionList);
+        return f == 0 ? launch_one<0, false, true, kPlaceIndexed>(a) : launch_one<1, false, true, kPlaceIndexed>(a);
     }
     if (a.frames.form == kSingle) {
         // one frame across passes: the long-distance framing's blocks (resolve_framing), each with its place in bytes.  Instances of
         // their own, so the kernels of a context without the switch are the ones from before it existed.
         assert(a.frames.frameBlocks && !a.chunkLens && !a.prefixLen && full == (f == 0));
-        return f == 0 ? launch_one<0, 5, false, true, 2>(a) : f == 1 ? launch_one<1, 5, true, false, 2>(a) : launch_one<2, 5, true, false, 2>(a);
+        return f == 0 ? launch_one<0, false, true, kSingle>(a) : f == 1 ? launch_one<1, true, false, kSingle>(a) : launch_one<2, true, false, kSingle>(a);
     }
     if (a.frames.form == kTable) {
         // (the table form exists for blocks behind LDS history only: the full-64-KiB-block instances take no table, while seq_encode
         //  and xxh64 would still follow it)
         assert(!full && a.frames.frameBlocks && a.chunkLens);
-        return f == 0 ? launch_one<0, 5, true, false, 1>(a) : f == 1 ? launch_one<1, 5, true, false, 1>(a) : launch_one<2, 5, true, false, 1>(a);
+        return f == 0 ? launch_one<0, true, false, kTable>(a) : f == 1 ? launch_one<1, true, false, kTable>(a) : launch_one<2, true, false, kTable>(a);
     }
-    if (full && a.frames.frameBlocks && f == 0) return launch_one<0, 5, false, true>(a);      // fast strategy with cross-chunk history: full 64 KiB blocks, far candidates
-    if (full) return f == 0 ? launch_one<0, 5, false>(a) : f == 1 ? launch_one<1, 5, false>(a) : launch_one<2, 5, false>(a);       // plain chunks, each a frame
+    if (full && a.frames.frameBlocks && f == 0) return launch_one<0, false, true>(a);      // fast strategy with cross-chunk history: full 64 KiB blocks, far candidates
+    if (full) return f == 0 ? launch_one<0, false>(a) : f == 1 ? launch_one<1, false>(a) : launch_one<2, false>(a);       // plain chunks, each a frame
     // a dictionary's tail, or the frame's earlier blocks, in LDS in front of a block below 64 KiB
-    return f == 0 ? launch_one<0, 5, true>(a) : f == 1 ? launch_one<1, 5, true>(a) : launch_one<2, 5, true>(a);
+    return f == 0 ? launch_one<0, true>(a) : f == 1 ? launch_one<1, true>(a) : launch_one<2, true>(a);
 }
 
 } // namespace zmi

@@ -31,7 +31,8 @@ u32 dict_index_max();               // the most bytes an index covers (the far c
 // chunkLens (optional): a batch of entries, each staged at a chunk boundary: per chunk its length.
 // cand / chain / regionList (null: off): workspace of the region parse, 65536 u16 per chunk (twice with the hash chains of the
 // level >= 5 search, hcDepth attempts per position) and 1 + nChunks u32.  claimCtr: a zeroable word for the chunk claims (lz_kernel).
-// dix (null: off): an indexed dictionary behind full 64 KiB chunks, each a frame of its own (fast finder, or the dual one where dix has its two tables; chunkLens allowed).
+// dix (null: off): an indexed dictionary behind full 64 KiB chunks, each a frame of its own (fast finder, or the dual one where dix has
+// its two tables; chunkLens allowed; prefix, cand, chain, regionList and frames.table are null).  The kernel gets a copy (LzArgs::dix).
 struct LzLaunch {
     u32 finder;
     const u8* src; u64 srcSize; u32 nChunks;
