@@ -280,6 +280,40 @@ size_t ZSTDMI_decompressBatch(ZSTD_DCtx* dctx, const void* const* srcs, const si
 int ZSTDMI_debugLastBatchAlone(const ZSTD_CCtx* cctx);
 int ZSTDMI_debugLastBatchAloneD(const ZSTD_DCtx* dctx);
 
+/* Packs: n device buffers into ONE contiguous, standard seekable stream whose frames end exactly at the entries' boundaries — the write
+ * side of ZSTDMI_decompressRanges.  srcs and srcSizes are host arrays; srcs[i] and d_dst are device pointers as for ZSTDMI_compressBatch,
+ * anywhere in HBM, at any alignment; d_dst overlaps no source.
+ * The bytes.  For i = 0 .. n - 1 in order, exactly the frames ZSTDMI_compressDevice writes for entry i alone — on the same context with
+ * its level, sticky parameters, dictionary, ZSTDMI_CCtx_setDictEntropy / setDictIndex / setSingleFrame and long-distance settings, and
+ * with the seek-table switch off; an empty entry is the one empty frame —, one entry's behind the other's without a gap, and behind the
+ * last frame ONE seek table in the format described under "Seekable streams" below (8-byte entries, descriptor 0): one entry per frame in
+ * stream order, the (Compressed_Size, Decompressed_Size) pairs ZSTDMI_CCtx_setSeekTable(1) lists for each entry alone, one entry's pairs
+ * behind the other's.  Frames written with ZSTD_c_contentSizeFlag = 0 have their true content size in the table; an entry above 64 KiB
+ * under ZSTDMI_CCtx_setSingleFrame is one frame and one pair.  n == 0 writes the 17-byte empty table.  So `zstd -d` restores the
+ * concatenation of the entries, any reader of the seekable format finds the frames, and ZSTDMI_decompressRanges with offsets[i] =
+ * srcSizes[0] + .. + srcSizes[i - 1] and lengths[i] = srcSizes[i] returns entry i and decodes that entry's frames alone.
+ * The context's own seek-table switch is not consulted, and the call leaves it and every other state of the context as it found it.
+ * How.  Entries ZSTDMI_compressBatch would batch (see above) go through its passes in rounds of at most ZSTDMI_CCtx_setPassChunks blocks,
+ * into an arena the context owns; the host then knows the round's size, compares it with the capacity that is left, and a gather kernel
+ * moves the frames to their place; their table entries are made on the device.  An entry the batch would hand to the single-call path
+ * (counted by ZSTDMI_debugLastPackAlone) is written straight to its place in the stream.  Host synchronisations depend on the number of
+ * rounds, passes and alone entries, not on n; the device memory held beyond the batch's own is bounded by the round.
+ * Returns the bytes written, frames plus table, or ONE error for the whole call: GENERIC for a NULL context or a NULL array with n > 0;
+ * init_missing without a device; memory_allocation; parameter_unsupported on a context with several device workers, with a pending
+ * ZSTD_CCtx_refPrefix (which stays pending), or when the stream would hold more than 2^27 frames; otherwise the error
+ * ZSTDMI_compressDevice gives for the lowest-index entry that fails (srcSize_wrong for a NULL source with a size, a refused parameter,
+ * dstBuffer_null ...); dstSize_tooSmall when frames plus table do not fit.  Nothing is ever written at or beyond d_dst + dstCapacity;
+ * what lies inside the capacity after an error is unspecified.
+ * ZSTDMI_packBound touches no device: the sum of ZSTD_compressBound(srcSizes[i]), + 17, + 8 * the sum of (srcSizes[i] / 4096 + 1) —
+ * ZSTDMI_seekTableBound per entry, with one header and footer.  A call with that much room never returns dstSize_tooSmall.  GENERIC
+ * for NULL with n > 0; srcSize_wrong when a term or the sum does not fit a size_t. */
+size_t ZSTDMI_packBound(const size_t* srcSizes, size_t n);
+size_t ZSTDMI_compressPack(ZSTD_CCtx* cctx, void* d_dst, size_t dstCapacity,
+                           const void* const* srcs, const size_t* srcSizes, size_t n);
+/* diagnostics of the last ZSTDMI_compressPack: entries the single-call path took; entries of the table written; -1 without a context */
+int       ZSTDMI_debugLastPackAlone(const ZSTD_CCtx* cctx);
+long long ZSTDMI_debugLastPackFrames(const ZSTD_CCtx* cctx);
+
 /* Seekable streams (the zstd seekable format, v0.1.0): random access at the granularity of the frame.
  * Every stream this library writes is a run of independent frames (64 KiB of content at levels 1-2, 240-256 KiB at levels >= 3, 32 KiB
  * or less behind a dictionary, one window under long-distance matching; ZSTDMI_CCtx_setHistory and ZSTD_c_windowLog change it).
@@ -291,7 +325,8 @@ int ZSTDMI_debugLastBatchAloneD(const ZSTD_DCtx* dctx);
  * checksums are neither written nor verified (the frames' own checksums, ZSTD_c_checksumFlag, still are).  0 = off (default); any
  * other mode: parameter_outOfBound.  The table needs ZSTDMI_seekTableBound(srcSize) bytes on top of ZSTD_compressBound(srcSize); if it
  * does not fit behind the frames the call returns dstSize_tooSmall.  With the switch on, ZSTDMI_compressBatch, ZSTD_compressStream2 and
- * a context with several device workers return parameter_unsupported; ZSTD_compressCCtx ignores it (level-only parameters).
+ * a context with several device workers return parameter_unsupported (many buffers into one seekable stream: ZSTDMI_compressPack
+ * above); ZSTD_compressCCtx ignores it (level-only parameters).
  * ZSTDMI_decompressRange writes content[offset, offset + length) of a stream that ends in such a table (this library's or anyone's,
  * 8- or 12-byte entries) to dst and returns the bytes written, min(length, max(total - offset, 0)); more than dstCapacity:
  * dstSize_tooSmall, nothing written.  src and dst are host or device pointers, each on its own.  Only the frames that meet the range

@@ -9,8 +9,8 @@ from .compressor import Compressor
 from .decompressor import Decompressor
 from .dictbuilder import DictBuilder
 from . import _ffi
-from .batch import compress_batch, decompress_batch
+from .batch import compress_batch, compress_pack, decompress_batch, pack_ranges
 from .seekable import read_seek_table
 from .streams import CompressionStream, DecompressionStream, EndOfStreamException
 
-__all__ = ["Compressor", "Decompressor", "DictBuilder", "CompressionStream", "DecompressionStream", "EndOfStreamException", "ZstdException", "ZSTD_ErrorCode", "compress_batch", "decompress_batch", "read_seek_table", "_ffi"]
+__all__ = ["Compressor", "Decompressor", "DictBuilder", "CompressionStream", "DecompressionStream", "EndOfStreamException", "ZstdException", "ZSTD_ErrorCode", "compress_batch", "compress_pack", "decompress_batch", "pack_ranges", "read_seek_table", "_ffi"]

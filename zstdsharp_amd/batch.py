@@ -1,6 +1,7 @@
 """Many small buffers in one call (ZSTDMI_compressBatch / ZSTDMI_decompressBatch, include/zstd_mi355x.h): every item is compressed as
 Compressor.Wrap would compress it alone — a complete stream that decodes on its own — and decoded as Decompressor.Unwrap would decode
-it, but the items share one pass through the GPU pipeline.
+it, but the items share one pass through the GPU pipeline.  compress_pack (ZSTDMI_compressPack) writes the items as ONE seekable
+stream instead: the same frames side by side, one seek table behind them; pack_ranges names record i for Decompressor.unwrap_ranges.
 
 torch is imported inside the functions: the package imports without it.
 """
@@ -93,3 +94,38 @@ def compress_batch(compressor, items):
     out = _run(torch, lib, lib.ZSTDMI_compressBatch, compressor.cctx, device, srcs, sizes, [lib.ZSTD_compressBound(x) for x in sizes], tensors)
     del keep
     return out
+
+
+def compress_pack(compressor, items):
+    """items as for compress_batch -> ONE seekable stream (ZSTDMI_compressPack): item i's frames as Compressor.Wrap writes them for it
+    alone, one item's behind the other's, and one seek table behind the last (read_seek_table reads it).  Bytes-like items -> bytes;
+    CUDA uint8 tensors -> one CUDA uint8 tensor of exactly the stream's length.  An empty list is the 17-byte empty table.  Uses the
+    compressor's level, parameters and dictionary; its seek_table switch is not consulted."""
+    import torch
+    compressor._ensure_not_disposed()
+    lib = compressor._lib
+    items = list(items)
+    n = len(items)
+    if n:
+        tensors, device, sizes, srcs, keep = _gather(torch, items)
+    else:
+        tensors, device, sizes, srcs, keep = False, torch.device("cuda", torch.cuda.current_device()), [], [], None
+    cap = lib.ZSTDMI_packBound(_size_array(sizes), n)
+    if is_error(cap):
+        raise ZstdException(get_error_code(cap), lib.ZSTD_getErrorName(cap).decode())
+    out = torch.empty(cap, dtype=torch.uint8, device=device)
+    torch.cuda.synchronize(device)          # the library runs on a stream of its own
+    r = lib.ZSTDMI_compressPack(compressor.cctx, out.data_ptr(), cap, _pointer_array(srcs), _size_array(sizes), n)
+    del keep
+    if is_error(r):
+        raise ZstdException(get_error_code(r), lib.ZSTD_getErrorName(r).decode())
+    return out[:r] if tensors else out[:r].cpu().numpy().tobytes()
+
+
+def pack_ranges(sizes):
+    """-> [(offset, length), ...] for Decompressor.unwrap_ranges: record i of a pack whose items had these sizes."""
+    ranges, at = [], 0
+    for s in sizes:
+        ranges.append((at, int(s)))
+        at += int(s)
+    return ranges

@@ -130,6 +130,97 @@ __global__ __launch_bounds__(256) void seek_table_kernel(const u32* __restrict__
     dst[i] = (u8)(word >> (8 * k));
 }
 
+// ---- a pack (ZSTDMI_compressPack): n entries' frames side by side in ONE stream, one seek table behind them ----
+// entries of a batched pass: entry e owns the chunks [entFirst[e], entFirst[e + 1]) and its frames the table rows from entSeek[e] on.
+// A frame is frameBlocks consecutive chunks of the entry (its last one may be shorter), one chunk where frameBlocks is 0: compressed
+// size = the chunks' frame bytes, content size = their lengths — seek_entries_kernel's pairs, from the per-chunk tables instead of the
+// arithmetic form.  One lane per entry; a row at or beyond `cap` is not written (the host sized the rows from the same framing).
+__global__ __launch_bounds__(256) void pack_entries_kernel(const ChunkMeta* __restrict__ meta, u32 nEntries, const u32* __restrict__ entFirst,
+                                                           const u32* __restrict__ chunkLens, u32 frameBlocks, const u32* __restrict__ entSeek,
+                                                           u32* __restrict__ entries, u32 cap)
+{
+    const u32 e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= nEntries) return;
+    const u32 c0 = entFirst[e], c1 = entFirst[e + 1], fb = frameBlocks ? frameBlocks : 1u;
+    u32 row = entSeek[e];
+    for (u32 c = c0; c < c1; ++row) {
+        u32 cSize = 0, dSize = 0;
+        for (u32 k = 0; k < fb && c < c1; ++k, ++c) { cSize += meta[c].outSize; dSize += chunkLens[c]; }
+        if (row < cap) { entries[2 * (u64)row] = cSize; entries[2 * (u64)row + 1] = dSize; }
+    }
+}
+
+// placement: at[e] = the exclusive sum of size[0 .. e), entry e's offset from the round's first byte in the stream.  One workgroup
+// striding with a carry, as scan_sizes_kernel (a round holds at most a few hundred thousand entries); 64-bit sums throughout: 1024
+// stored entries of 4 MiB do not fit 32 bits.
+__device__ __forceinline__ u64 wave_scan_incl64(u64 v)
+{
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) { const u64 t = __shfl_up(v, d); if ((int)lane_id() >= d) v += t; }
+    return v;
+}
+__global__ __launch_bounds__(1024) void pack_place_kernel(const u64* __restrict__ size, u32 nEntries, u64* __restrict__ at)
+{
+    __shared__ u64 waveSum[16];
+    const u32 tid = threadIdx.x, lane = lane_id(), wave = wave_id();
+    u64 carry = 0;
+    for (u32 base = 0; base < nEntries; base += 1024) {
+        const u32 i = base + tid;
+        const u64 v = i < nEntries ? size[i] : 0;
+        const u64 incl = wave_scan_incl64(v);
+        if (lane == 63) waveSum[wave] = incl;
+        __syncthreads();
+        u64 before = 0, all = 0;
+#pragma unroll
+        for (u32 k = 0; k < 16; k++) { const u64 s = waveSum[k]; all += s; if (k < wave) before += s; }
+        if (i < nEntries) at[i] = carry + before + incl - v;
+        carry += all;
+        __syncthreads();
+    }
+}
+
+// gather: entry e's size[e] bytes from its arena slot (slot[e], 16-byte aligned; slot[e + 1] - slot[e] bytes long) to dst + at[e], any
+// alignment, the entries densely side by side.  The unit of work is a wave and a slice: blockIdx.x = a group of kPackGroup entries,
+// dealt to the workgroup's four waves in turn; blockIdx.y = the kPackSlice bytes of an entry this workgroup copies, so that a long
+// entry (a stored one: megabytes) is spread over the chip and a group of short ones (20 bytes each) costs one workgroup, not sixteen.
+// A slice goes as ranges_gather's pieces do, in 16-byte stores at the DESTINATION's alignment fed by unaligned 16-byte loads, the ragged
+// head and tail byte by byte: every store lies in [dst + at[e] + lo, dst + at[e] + hi) with hi <= size[e], every load below size[e] in
+// the slot.  An entry that does not fit its slot or `room` is not copied (the host compared the sum with the capacity before the launch).
+constexpr u32 kPackGroup = 16, kPackSlice = 16u << 10;
+__device__ __forceinline__ void wave_copy(u8* __restrict__ d, const u8* __restrict__ s, u32 n, u32 lane)
+{
+    u32 head = (u32)((16 - ((uintptr_t)d & 15)) & 15);
+    if (head > n) head = n;
+    if (lane < head) d[lane] = s[lane];
+    const u32 body = (n - head) >> 4;
+    uint4* d4 = reinterpret_cast<uint4*>(d + head);
+    const u8* sb = s + head;
+#pragma unroll 4
+    for (u32 i = lane; i < body; i += kWave) {
+        uint4 v;
+        v.x = readLE32(sb + 16 * i); v.y = readLE32(sb + 16 * i + 4); v.z = readLE32(sb + 16 * i + 8); v.w = readLE32(sb + 16 * i + 12);
+        d4[i] = v;
+    }
+    const u32 done = head + (body << 4);
+    if (lane < n - done) d[done + lane] = s[done + lane];
+}
+__global__ __launch_bounds__(256) void pack_gather_kernel(const u8* __restrict__ arena, const u64* __restrict__ slot, const u64* __restrict__ size,
+                                                          const u64* __restrict__ at, u32 nEntries, u8* __restrict__ dst, u64 room)
+{
+    const u32 lane = lane_id();
+    const u64 lo = (u64)blockIdx.y * kPackSlice;
+    for (u32 k = wave_id(); k < kPackGroup; k += 4) {
+        const u32 e = blockIdx.x * kPackGroup + k;
+        if (e >= nEntries) return;
+        const u64 n = size[e];
+        if (lo >= n) continue;
+        const u64 s0 = slot[e], a = at[e];
+        if (n > slot[e + 1] - s0 || a > room || n > room - a) continue;
+        const u64 hi = n < lo + kPackSlice ? n : lo + kPackSlice;
+        wave_copy(dst + a + lo, arena + s0 + lo, (u32)(hi - lo), lane);
+    }
+}
+
 // ---- XXH64 (seed 0): 4 lanes per chunk, one per accumulator ----
 constexpr u64 P1 = 0x9E3779B185EBCA87ULL, P2 = 0xC2B2AE3D27D4EB4FULL, P3 = 0x165667B19E3779F9ULL,
               P4 = 0x85EBCA77C2B2AE63ULL, P5 = 0x27D4EB2F165667C5ULL;
@@ -283,6 +374,21 @@ void launch_seek_table(const u32* entries, u32 n, u8* dst, hipStream_t stream)
 {
     const u64 bytes = 17 + 8 * (u64)n;
     hipLaunchKernelGGL(seek_table_kernel, dim3((u32)((bytes + 255) / 256)), dim3(256), 0, stream, entries, n, dst);
+}
+void launch_pack_entries(const ChunkMeta* meta, u32 nEntries, const u32* entFirst, const u32* chunkLens, u32 frameBlocks, const u32* entSeek, u32* entries,
+                         u32 cap, hipStream_t stream)
+{
+    hipLaunchKernelGGL(pack_entries_kernel, dim3((nEntries + 255) / 256), dim3(256), 0, stream, meta, nEntries, entFirst, chunkLens, frameBlocks, entSeek, entries, cap);
+}
+void launch_pack_place(const u64* size, u32 nEntries, u64* at, hipStream_t stream)
+{
+    hipLaunchKernelGGL(pack_place_kernel, dim3(1), dim3(1024), 0, stream, size, nEntries, at);
+}
+void launch_pack_gather(const u8* arena, const u64* slot, const u64* size, const u64* at, u32 nEntries, u64 longest, u8* dst, u64 room, hipStream_t stream)
+{
+    const u32 nSlices = (u32)((longest + kPackSlice - 1) / kPackSlice);
+    hipLaunchKernelGGL(pack_gather_kernel, dim3((nEntries + kPackGroup - 1) / kPackGroup, nSlices ? nSlices : 1), dim3(256), 0, stream, arena, slot, size, at,
+                       nEntries, dst, room);
 }
 void launch_batch_stage(const u64* from, const u32* len, u8* stage, u32 nChunks, u32 chunkBytes, hipStream_t stream)
 {

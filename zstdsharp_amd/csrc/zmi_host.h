@@ -65,6 +65,13 @@ void launch_batch_place(const ChunkMeta* meta, u32 nEntries, const u32* entFirst
                         hipStream_t stream);
 void launch_seek_entries(const u64* offsets, const u64* total, u32 nChunks, const FrameLayout& frames, u32* entries, hipStream_t stream);
 void launch_seek_table(const u32* entries, u32 n, u8* dst, hipStream_t stream);
+// a pack (ZSTDMI_compressPack, frame.hip): a batched pass's seek-table rows per entry (entSeek[e] = the row of entry e's first frame, rows
+// at or beyond cap are dropped); the entries' places in the stream (at = exclusive sums of size); their bytes from the arena's slots
+// (slot[nEntries + 1]) to dst + at, `longest` = the largest size, nothing at or beyond dst + room
+void launch_pack_entries(const ChunkMeta* meta, u32 nEntries, const u32* entFirst, const u32* chunkLens, u32 frameBlocks, const u32* entSeek, u32* entries,
+                         u32 cap, hipStream_t stream);
+void launch_pack_place(const u64* size, u32 nEntries, u64* at, hipStream_t stream);
+void launch_pack_gather(const u8* arena, const u64* slot, const u64* size, const u64* at, u32 nEntries, u64 longest, u8* dst, u64 room, hipStream_t stream);
 // long-distance matching (ldm.hip)
 size_t ldm_small_bytes(u64 n);
 size_t ldm_big_bytes(u64 nSplits);

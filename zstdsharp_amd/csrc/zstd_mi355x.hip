@@ -6,6 +6,7 @@
 // ZSTD_error_init_missing, loudly.
 #include "zmi_cparams.h"
 #include "zmi_host.h"
+#include <unordered_map>
 
 // ======================================================================================================
 struct ZSTD_CCtx_s {
@@ -53,6 +54,9 @@ struct ZSTD_CCtx_s {
     DevBuf gatherIn, gatherOut;     // a many-range plan: the ranges of a kind side by side, and their output (compress_plan)
     DevBuf batchStage, batchTab;    // a batch of independent entries: their chunks at chunk boundaries, and the pass's tables (compress_entries)
     int lastBatchAlone = 0;         // entries of the last ZSTDMI_compressBatch that went through the single-call path (debug hook)
+    // ZSTDMI_compressPack: a round's frames in bound-sized slots before they are placed, and its placement table (compress_pack_impl);
+    // entries the last pack handed to the single-call path and rows of the table it wrote (debug hooks)
+    DevBuf packArena, packTab; int lastPackAlone = 0; long long lastPackFrames = 0;
     // ZSTDMI_CCtx_setSeekTable: one (compressed size, content size) pair per frame, filed on the device by every pass of a call
     // (seekOn: this call files them) at the running index seekCount; compress_device writes the table behind the frames from them
     int seekTable = 0; bool seekOn = false; u32 seekCount = 0;
@@ -778,7 +782,7 @@ size_t ZSTD_freeCCtx(ZSTD_CCtx* c)
         (void)hipSetDevice(c->device);
         if (c->ownStream) (void)hipStreamSynchronize(c->ownStream);
         c->seqs.release(); c->lits.release(); c->meta.release(); c->tables.release(); c->slots.release(); c->cand.release(); c->probe.release();
-        c->gatherIn.release(); c->gatherOut.release(); c->batchStage.release(); c->batchTab.release(); c->ldmSmall.release(); c->ldmBig.release(); c->offsets.release(); c->total.release(); c->seekEntries.release(); c->seekSort.release(); c->stageSrc.release(); c->stageDst.release(); c->pfxStage.release(); c->sfXxh.release(); c->dict.release(); c->dictWideDev.release(); c->dictIdxDev.release(); c->dictFullDev.release(); c->dictInfoDev.release(); c->dictCTabDev.release();
+        c->gatherIn.release(); c->gatherOut.release(); c->batchStage.release(); c->batchTab.release(); c->packArena.release(); c->packTab.release(); c->ldmSmall.release(); c->ldmBig.release(); c->offsets.release(); c->total.release(); c->seekEntries.release(); c->seekSort.release(); c->stageSrc.release(); c->stageDst.release(); c->pfxStage.release(); c->sfXxh.release(); c->dict.release(); c->dictWideDev.release(); c->dictIdxDev.release(); c->dictFullDev.release(); c->dictInfoDev.release(); c->dictCTabDev.release();
         c->timer.destroy();
         if (c->ownStream) (void)hipStreamDestroy(c->ownStream);
     }
@@ -1436,13 +1440,32 @@ size_t ZSTD_compressStream2(ZSTD_CCtx* c, ZSTD_outBuffer* output, ZSTD_inBuffer*
 // single-call path, and counted in `alone`.
 // srcs[i]: device pointers.  dsts / caps: device pointers and their capacities, or null (sizes only).  outSizes[i] = the compressed
 // size of entry i (or its error).  d_stats (optional, device, 377 u32): seq_stats_kernel's counts of the batched chunks are added.
+// seekIdx (optional; ZSTDMI_compressPack): the row of c->seekEntries (seekCap rows) at which entry i's frames are filed, one
+// (compressed size, content size) pair per frame, by every pass from its ChunkMeta (pack_entries_kernel).
+//
+// entry_batched -> does an entry of S bytes (S > 0, framed as fr) share a batched pass?  One rule for compress_entries, which sorts
+// its entries by it, and for ZSTDMI_compressPack, which cuts its rounds by it.
+static bool entry_batched(ZSTD_CCtx* c, const CallParams& cp, size_t S, const Framing& fr, u32 passLimit, bool dct, bool stats)
+{
+    bool batched = S && !fr.indepWindowLog && !fr.ldm && !fr.single && c->workers.size() <= 1 && (S + fr.chunkBytes - 1) / fr.chunkBytes <= passLimit;
+    // multi-block frames: the blocks behind LDS history (chunks below 64 KiB; the full 64 KiB blocks with far candidates have no
+    // table form, launch_lz), below 4 MiB and of at most 256 chunks (a block index and a frame size that fit chunk_frame_word);
+    // with a dictionary's entropy tables (huf_tree_kernel<true> finds a frame's first block in the arithmetic form alone), or with sizes
+    // only and statistics (the trainer's finalize step), as before: alone
+    if (batched && fr.frameBlocks)
+        batched = S < (4u << 20) && (S + fr.chunkBytes - 1) / fr.chunkBytes <= 256 && fr.chunkBytes < kChunkSize && !dct && !stats;
+    if (batched && S >= (4u << 20)) { size_t err = 0; if (probe_group_bytes(c, cp, S, err) || isErr(err)) batched = false; }
+    return batched;
+}
+static u32 batch_pass_limit(const ZSTD_CCtx* c) { return c->passChunks < 16384 ? c->passChunks : 16384; }
 static size_t compress_entries(ZSTD_CCtx* c, const CallParams& cp, const u8* const* srcs, const size_t* sizes, size_t n,
-                               u8* const* dsts, const size_t* caps, size_t* outSizes, u32* d_stats, int& alone)
+                               u8* const* dsts, const size_t* caps, size_t* outSizes, u32* d_stats, int& alone,
+                               const u32* seekIdx = nullptr, u32 seekCap = 0)
 {
     hipStream_t s = c->stream;
     alone = 0;
     const DictCTables* const dct = call_dict_ctables(c, cp);
-    const u32 passLimit = c->passChunks < 16384 ? c->passChunks : 16384;
+    const u32 passLimit = batch_pass_limit(c);
     struct Group { Framing fr; std::vector<size_t> members; };
     std::vector<Group> groups;
     std::vector<size_t> aloneList;
@@ -1453,15 +1476,7 @@ static size_t compress_entries(ZSTD_CCtx* c, const CallParams& cp, const u8* con
             if (!dsts[i]) { outSizes[i] = caps[i] ? ZERR(kErrDstBufferNull) : ZERR(kErrDstSizeTooSmall); continue; }
         }
         const Framing fr = S ? resolve_framing(c, cp, S) : Framing{};
-        bool batched = S && !fr.indepWindowLog && !fr.ldm && !fr.single && c->workers.size() <= 1 && (S + fr.chunkBytes - 1) / fr.chunkBytes <= passLimit;
-        // multi-block frames: the blocks behind LDS history (chunks below 64 KiB; the full 64 KiB blocks with far candidates have no
-        // table form, launch_lz), below 4 MiB and of at most 256 chunks (a block index and a frame size that fit chunk_frame_word);
-        // with a dictionary's entropy tables (huf_tree_kernel<true> finds a frame's first block in the arithmetic form alone), or with sizes
-        // only and statistics (the trainer's finalize step), as before: alone
-        if (batched && fr.frameBlocks)
-            batched = S < (4u << 20) && (S + fr.chunkBytes - 1) / fr.chunkBytes <= 256 && fr.chunkBytes < kChunkSize && !dct && !d_stats;
-        if (batched && S >= (4u << 20)) { size_t err = 0; if (probe_group_bytes(c, cp, S, err) || isErr(err)) batched = false; }
-        if (!batched) { aloneList.push_back(i); continue; }
+        if (!S || !entry_batched(c, cp, S, fr, passLimit, dct != nullptr, d_stats != nullptr)) { aloneList.push_back(i); continue; }
         outSizes[i] = 0;
         Group* g = nullptr;
         for (auto& x : groups)
@@ -1489,7 +1504,8 @@ static size_t compress_entries(ZSTD_CCtx* c, const CallParams& cp, const u8* con
             // behind it the sizes that come back
             const size_t atDst = (size_t)nCh * 8, atCap = atDst + (size_t)nEnt * 8, atLen = atCap + (size_t)nEnt * 8, atFirst = atLen + (size_t)nCh * 4;
             const size_t atFrame = atFirst + ((size_t)nEnt + 1) * 4;
-            const size_t tabBytes = (atFrame + (frameBlocks ? (size_t)nCh * 4 : 0) + 7) & ~(size_t)7;
+            const size_t atSeek = atFrame + (frameBlocks ? (size_t)nCh * 4 : 0);        // (a pack: | entSeek[nEnt])
+            const size_t tabBytes = (atSeek + (seekIdx ? (size_t)nEnt * 4 : 0) + 7) & ~(size_t)7;
             tab.assign(tabBytes, 0);
             u64* const hFrom = (u64*)tab.data(); u64* const hDst = (u64*)(tab.data() + atDst); u64* const hCap = (u64*)(tab.data() + atCap);
             u32* const hLen = (u32*)(tab.data() + atLen); u32* const hFirst = (u32*)(tab.data() + atFirst); u32* const hFrame = (u32*)(tab.data() + atFrame);
@@ -1505,6 +1521,7 @@ static size_t compress_entries(ZSTD_CCtx* c, const CallParams& cp, const u8* con
             for (size_t m = m0; m < m1; ++m) {
                 const size_t i = g.members[m];
                 hFirst[m - m0] = ck;
+                if (seekIdx) ((u32*)(tab.data() + atSeek))[m - m0] = seekIdx[i];
                 hDst[m - m0] = dsts ? (u64)((uintptr_t)dsts[i] - lo) : 0;
                 hCap[m - m0] = dsts ? (u64)caps[i] : ~(u64)0;
                 const FrameLayout entry = layout_arith(cb, frameBlocks, sizes[i]);      // the entry as the single call frames it
@@ -1541,6 +1558,10 @@ static size_t compress_entries(ZSTD_CCtx* c, const CallParams& cp, const u8* con
             if (d_stats) launch_seq_stats(seqs, lits, meta, nCh, stage, cb, d_stats, s);
             launch_batch_place(meta, nEnt, (const u32*)(dTab + atFirst), (const u64*)(dTab + atDst), (const u64*)(dTab + atCap), span, offsets, dGot, s);
             c->timer.mark("batch_place", s);
+            if (seekIdx) {
+                launch_pack_entries(meta, nEnt, (const u32*)(dTab + atFirst), dLen, frameBlocks, (const u32*)(dTab + atSeek), (u32*)c->seekEntries.p, seekCap, s);
+                c->timer.mark("pack_entries", s);
+            }
             if (dsts) {
                 launch_huf_encode(lits, meta, tables, slots, base, offsets, span, nCh, stage, cb, s, dct != nullptr);     c->timer.mark("huf_encode", s);
                 launch_gather(stage, stagedBytes, slots, meta, offsets, base, span, nCh, cb, s);          c->timer.mark("gather", s);
@@ -1612,6 +1633,176 @@ extern "C" size_t ZSTDMI_compressBatch(ZSTD_CCtx* c, const void* const* srcs, co
     return guarded([&] { return compress_batch_impl(c, srcs, srcSizes, n, dsts, dstCapacities, dstSizes); });
 }
 extern "C" int ZSTDMI_debugLastBatchAlone(const ZSTD_CCtx* c) { return c ? c->lastBatchAlone : -1; }
+
+// ---- a pack: n device-resident entries into ONE seekable stream (ZSTDMI_compressPack, include/zstd_mi355x.h) ----
+// The entries are walked in order and cut into ROUNDS: maximal runs of entries compress_entries batches (entry_batched), at most
+// ZSTDMI_CCtx_setPassChunks chunks each.  A round goes through compress_entries into the context's arena, entry i at the prefix sum of
+// the ZSTD_compressBound of those in front of it (rounded up to 16 bytes); its sizes come back as a batch's do, the host compares their
+// sum with what is left of the capacity, and only then are pack_place (the exclusive scan of the sizes) and pack_gather launched, which
+// move each entry's bytes to d_dst + at + its place.  An entry the batch would hand to the single-call path is not staged: the host
+// knows the running offset, compress_frames writes it straight to d_dst + at with the capacity that is left.  The table's rows are
+// filed on the device — a round's by pack_entries_kernel at rows the host counts from each entry's Framing, an alone entry's by the
+// seek table's own mechanism (seekOn) — and read back round by round (8 bytes a frame), so that what the call holds on the device is
+// bounded by the round; the table goes up behind the last frame in one copy.  Host synchronisations: per pass and per alone entry
+// what the batch and the single call make, plus two per round.
+constexpr u64 kPackMaxFrames = (u64)1 << 27;        // (the decoder's limit on a table's entries)
+static size_t pack_bound(const size_t* sizes, size_t n)
+{
+    if (n && !sizes) return ZERR(kErrGeneric);
+    size_t sum = 17;
+    for (size_t i = 0; i < n; i++) {
+        const size_t b = ZSTD_compressBound(sizes[i]), t = 8 * seek_max_frames(sizes[i]);
+        if (isErr(b) || b < sizes[i]) return ZERR(kErrSrcSizeWrong);
+        if (__builtin_add_overflow(sum, b, &sum) || __builtin_add_overflow(sum, t, &sum) || isErr(sum)) return ZERR(kErrSrcSizeWrong);
+    }
+    return sum;
+}
+namespace {
+// the stage times of a pack: sums by stage name over its rounds and alone entries, in the order the stages first ran
+struct PackStages {
+    const char* names[kMaxStages]; float ms[kMaxStages]; int n = 0;
+    void add(const char* name, float t)
+    {
+        for (int i = 0; i < n; i++) if (names[i] == name || !strcmp(names[i], name)) { ms[i] += t; return; }
+        if (n < kMaxStages) { names[n] = name; ms[n] = t; n++; }
+    }
+    void add_call(const ZSTD_CCtx* c) { for (int i = 0; i < c->nStages; i++) add(c->stageNames[i], c->stageMs[i]); }
+    void add_timer(ZSTD_CCtx* c) { c->timer.finish(); for (int i = 0; i < c->timer.n; i++) add(c->timer.names[i], c->timer.ms[i]); }
+    void file(ZSTD_CCtx* c) const { c->nStages = n; for (int i = 0; i < n; i++) { c->stageNames[i] = names[i]; c->stageMs[i] = ms[i]; } }
+};
+}
+static size_t compress_pack_impl(ZSTD_CCtx* c, u8* d_dst, size_t dstCapacity, const u8* const* srcs, const size_t* sizes, size_t n)
+{
+    if (!c || (n && (!srcs || !sizes))) return ZERR(kErrGeneric);
+    size_t e = cctx_bind(c); if (isErr(e)) return e;
+    if (c->workers.size() > 1 || c->pfx) return ZERR(kErrParameterUnsupported);
+    c->lastPackAlone = 0; c->lastPackFrames = 0;
+    CallParams cp = sticky_params(c); cp.seek = false;      // (the context's own switch is not consulted)
+    hipStream_t s = c->stream;
+    // what the single call would refuse, for the lowest entry it refuses, before a byte is read
+    for (size_t i = 0; i < n; i++) if (sizes[i] && !srcs[i]) return ZERR(kErrSrcSizeWrong);
+    if (!d_dst) return dstCapacity ? ZERR(kErrDstBufferNull) : ZERR(kErrDstSizeTooSmall);
+    if (n) { e = check_call_params(cp); if (isErr(e)) return e; }
+    e = cctx_sync_dictionary(c); if (isErr(e)) return e;
+    const DictCTables* const dct = call_dict_ctables(c, cp);
+    const u32 passLimit = batch_pass_limit(c);
+    // per entry: batched or alone, its chunks and its frames (a batched entry's follow from its Framing).  All of it is a function of
+    // the size within one call, and a record store's sizes repeat: resolved once per distinct size
+    struct Kind { bool batched; u32 chunks, frames; };
+    std::unordered_map<size_t, Kind> kinds;
+    std::vector<u8> batched(n); std::vector<u32> chunks(n), frames(n);
+    for (size_t i = 0; i < n; i++) {
+        const size_t S = sizes[i];
+        auto it = kinds.find(S);
+        if (it == kinds.end()) {
+            if (isErr(ZSTD_compressBound(S)) || ZSTD_compressBound(S) < S) return ZERR(kErrSrcSizeWrong);
+            const Framing fr = S ? resolve_framing(c, cp, S) : Framing{};
+            Kind k = { S && entry_batched(c, cp, S, fr, passLimit, dct != nullptr, false), 0, 0 };
+            if (k.batched) {
+                k.chunks = (u32)((S + fr.chunkBytes - 1) / fr.chunkBytes);
+                k.frames = fr.frameBlocks ? (k.chunks + fr.frameBlocks - 1) / fr.frameBlocks : k.chunks;
+            } else {
+                e = check_ldm_dict(c, cp, S); if (isErr(e)) return e;
+                e = check_single_frame(c, cp, S); if (isErr(e)) return e;
+            }
+            it = kinds.emplace(S, k).first;
+        }
+        batched[i] = it->second.batched; chunks[i] = it->second.chunks; frames[i] = it->second.frames;
+    }
+    struct Off { ZSTD_CCtx* c; ~Off() { c->seekOn = false; c->seekCount = 0; } } off{c};
+    std::vector<u32> table;             // the rows, two words each, in stream order
+    std::vector<u8*> slotPtr; std::vector<size_t> slotCap, got; std::vector<u32> seekIdx; std::vector<u64> tab;
+    PackStages st;
+    size_t at = 0;
+    int alone = 0;
+    for (size_t i = 0; i < n; ) {
+        if (table.size() / 2 > kPackMaxFrames) return ZERR(kErrParameterUnsupported);
+        const size_t room = dstCapacity - at;
+        if (!batched[i]) {
+            // alone: straight to its place.  Its rows: one frame per call knows its own (the empty frame; one frame across passes,
+            // which the seek table's switch refuses), the others file theirs pass by pass as under ZSTDMI_CCtx_setSeekTable
+            const size_t S = sizes[i];
+            const bool oneFrame = S == 0 || single_active(cp, S);
+            if (!oneFrame) {
+                if (!c->seekEntries.ensure(seek_max_frames(S) * 8)) return ZERR(kErrMemoryAllocation);
+                c->seekOn = true; c->seekCount = 0;
+            }
+            const size_t r = compress_frames(c, cp, d_dst + at, room, srcs[i], S);
+            c->seekOn = false;
+            if (isErr(r)) return r;
+            if (S) st.add_call(c);
+            if (oneFrame) { if (r > 0xFFFFFFFFu || S > 0xFFFFFFFFu) return ZERR(kErrGeneric); table.push_back((u32)r); table.push_back((u32)S); }
+            else {
+                const size_t rows = table.size();
+                table.resize(rows + 2 * (size_t)c->seekCount);
+                if (c->seekCount && isErr(dev_read(table.data() + rows, c->seekEntries.p, (size_t)c->seekCount * 8, s))) return ZERR(kErrGeneric);
+            }
+            at += r; ++alone; ++i;
+            continue;
+        }
+        // a round: the batched entries [i, j), at most passLimit chunks
+        size_t j = i; u32 nCh = 0, nRows = 0; size_t arenaBytes = 0;
+        slotPtr.clear(); slotCap.clear(); seekIdx.clear(); tab.clear();
+        while (j < n && batched[j] && !(nCh && nCh + chunks[j] > passLimit)) {
+            tab.push_back(arenaBytes); seekIdx.push_back(nRows);
+            slotCap.push_back(ZSTD_compressBound(sizes[j]));
+            arenaBytes += (slotCap.back() + 15) & ~(size_t)15;
+            nCh += chunks[j]; nRows += frames[j]; ++j;
+        }
+        const u32 nEnt = (u32)(j - i);
+        tab.push_back(arenaBytes);                                  // slot[nEnt + 1] | size[nEnt] | at[nEnt] (device only)
+        if (!c->packArena.ensure(arenaBytes + 64) || !c->seekEntries.ensure((size_t)nRows * 8) || !c->packTab.ensure(((size_t)3 * nEnt + 1) * 8)) return ZERR(kErrMemoryAllocation);
+        for (u32 k = 0; k < nEnt; k++) slotPtr.push_back((u8*)c->packArena.p + tab[k]);
+        got.assign(nEnt, 0);
+        int roundAlone = 0;
+        e = compress_entries(c, cp, srcs + i, sizes + i, nEnt, slotPtr.data(), slotCap.data(), got.data(), nullptr, roundAlone, seekIdx.data(), nRows);
+        if (isErr(e)) return e;
+        if (roundAlone) return ZERR(kErrGeneric);                   // (never: the rounds are cut by compress_entries' own rule)
+        st.add_call(c);
+        u64 total = 0, longest = 0;
+        for (u32 k = 0; k < nEnt; k++) {
+            if (isErr(got[k])) return got[k];
+            tab.push_back(got[k]); total += got[k]; if (got[k] > longest) longest = got[k];
+        }
+        if (total > room) return ZERR(kErrDstSizeTooSmall);         // (before anything that writes d_dst is launched)
+        u64* const dTab = (u64*)c->packTab.p;
+        if (hipMemcpyAsync(dTab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, s) != hipSuccess) return ZERR(kErrGeneric);
+        c->timer.begin(s);
+        launch_pack_place(dTab + nEnt + 1, nEnt, dTab + 2 * (size_t)nEnt + 1, s);                    c->timer.mark("pack_place", s);
+        launch_pack_gather((const u8*)c->packArena.p, dTab, dTab + nEnt + 1, dTab + 2 * (size_t)nEnt + 1, nEnt, longest, d_dst + at, room, s);
+        c->timer.mark("pack_gather", s);
+        const size_t rows = table.size();
+        table.resize(rows + 2 * (size_t)nRows);
+        if (isErr(dev_read(table.data() + rows, c->seekEntries.p, (size_t)nRows * 8, s))) return ZERR(kErrGeneric);
+        st.add_timer(c);
+        at += (size_t)total; i = j;
+    }
+    const size_t nFrames = table.size() / 2;
+    if (nFrames > kPackMaxFrames) return ZERR(kErrParameterUnsupported);
+    const size_t tableBytes = 17 + 8 * nFrames;
+    if (tableBytes > dstCapacity - at) return ZERR(kErrDstSizeTooSmall);
+    // the table behind the last frame: skippable header | rows | footer (include/zstd_mi355x.h "Seekable streams"), in one copy
+    std::vector<u8> image(tableBytes);
+    frame_put_le(image.data(), 0x184D2A5Eu, 4); frame_put_le(image.data() + 4, tableBytes - 8, 4);
+    for (size_t k = 0; k < table.size(); k++) frame_put_le(image.data() + 8 + 4 * k, table[k], 4);
+    frame_put_le(image.data() + tableBytes - 9, nFrames, 4); image[tableBytes - 5] = 0; frame_put_le(image.data() + tableBytes - 4, 0x8F92EAB1u, 4);
+    c->timer.begin(s);
+    if (hipMemcpyAsync(d_dst + at, image.data(), tableBytes, hipMemcpyHostToDevice, s) != hipSuccess) return ZERR(kErrGeneric);
+    c->timer.mark("pack_table", s);
+    if (isErr(stream_wait(s))) return ZERR(kErrGeneric);
+    st.add_timer(c);
+    st.file(c);
+    c->lastPackAlone = alone; c->lastPackFrames = (long long)nFrames;
+    c->lastChunks = 0;
+    return at + tableBytes;
+}
+extern "C" size_t ZSTDMI_packBound(const size_t* srcSizes, size_t n) { return pack_bound(srcSizes, n); }
+extern "C" size_t ZSTDMI_compressPack(ZSTD_CCtx* c, void* d_dst, size_t dstCapacity, const void* const* srcs, const size_t* srcSizes, size_t n)
+{
+    return guarded([&] { return compress_pack_impl(c, (u8*)d_dst, dstCapacity, (const u8* const*)srcs, srcSizes, n); });
+}
+extern "C" int ZSTDMI_debugLastPackAlone(const ZSTD_CCtx* c) { return c ? c->lastPackAlone : -1; }
+extern "C" long long ZSTDMI_debugLastPackFrames(const ZSTD_CCtx* c) { return c ? c->lastPackFrames : -1; }
 
 extern "C" size_t ZSTDMI_debugCompressSamples(ZSTD_CCtx* c, const void* src, const size_t* sizes, size_t n, size_t* outSizes)
 {
