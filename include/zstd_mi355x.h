@@ -57,7 +57,8 @@ size_t     ZSTD_freeCCtx(ZSTD_CCtx* cctx);                                   /* 
  * exactly what a context that never set the switch writes: the reference's auto rule (on for btopt and above at windowLog >= 27,
  * U/ZstdCompress.cs:276-284) is deliberately not adopted, so that no level's output changes.  ZSTD_compressCCtx ignores the switch
  * (level-only parameters, as the reference).  With a dictionary loaded (ZSTD_CCtx_loadDictionary), an LDM call of more than one block
- * returns parameter_unsupported from ZSTD_compress2 (ZSTD_CCtx_refPrefix is the way to match into a second buffer); ZSTD_compressStream2 finds LDM matches inside each 16 MiB batch, not across batches. */
+ * returns parameter_unsupported from ZSTD_compress2 (ZSTD_CCtx_refPrefix is the way to match into a second buffer); ZSTD_compressStream2 finds LDM matches inside each 16 MiB batch, not across batches
+ * unless the session writes one frame with a sliding window (ZSTDMI_CCtx_setSingleFrame with ZSTDMI_CCtx_setSlidingLdm, below). */
 size_t     ZSTD_CCtx_setParameter(ZSTD_CCtx* cctx, int param, int value);
 size_t     ZSTD_CCtx_getParameter(const ZSTD_CCtx* cctx, int param, int* value);
 /* S/Compressor.cs:43-56 (dictionary load) -> U/ZstdCompress.cs:1286-1330, 5465-5503.  RAW-CONTENT dictionaries (any bytes
@@ -404,6 +405,26 @@ long long ZSTDMI_debugDictIndexed(const ZSTD_CCtx* cctx);
  * or more in order), not at that of independent frames, cannot be sharded by frame, and its checksum is one serial chain (seconds per
  * GiB on both sides).  Figures: README "One frame per call". */
 size_t ZSTDMI_CCtx_setSingleFrame(ZSTD_CCtx* cctx, unsigned mode);
+/* Long-distance matching whose window slides with the one frame (the reference's ZSTD_ldm_* under `zstd --long`).  0 = off (the
+ * default), 1 = on, any other mode: parameter_outOfBound; NULL context: GENERIC.  Sticky; the call touches no device.
+ * It takes effect only with ZSTDMI_CCtx_setSingleFrame on AND ZSTD_c_enableLongDistanceMatching = ZSTD_ps_enable, in exactly the
+ * calls that combination is refused in without it: every ZSTD_compressStream2 session, and a ZSTD_compress2 / ZSTDMI_compressDevice
+ * whose source exceeds one long-distance frame (min(2^windowLog, 512 MiB, one pass)).  Everywhere else — a source that fits one
+ * long-distance frame, ZSTD_ps_auto / ZSTD_ps_disable, single-frame off, ZSTD_compressCCtx, a pending ZSTD_CCtx_refPrefix — the
+ * bytes are those of the switch off.
+ * In effect: ONE frame of the single-frame blocks for the level (64 / 48 / 32 KiB), found by the same block finders, and the
+ * long-distance stage adds matches at any distance up to 2^wl in front of a position, wherever a pass or a stream batch begins; wl =
+ * ZSTD_c_windowLog, or 27; the stage's other parameters follow from wl as they do for aligned windows.  No offset exceeds 2^wl.
+ * Header: the single-frame rules with that wl (a call: a single segment when srcSize <= 2^wl, else a window descriptor for 2^wl and
+ * the content size; a stream: the descriptor alone).  The stage runs once per pass (per batch of a stream: 16 MiB, or what a flush or
+ * the end finds buffered) over the up to 2^wl bytes of the frame in front of the pass — indexed, not matched again — and the pass.
+ * A call reads them in place in its own source; a session keeps them on the device: it holds 2^wl bytes + one batch + 4 MiB there from
+ * its first batch to its end.  The same input, parameters, pass size and flush positions give the same bytes; other than plain
+ * single-frame output, the bytes MAY change with ZSTDMI_CCtx_setPassChunks and with where batches end (a step's index is its window's).
+ * parameter_unsupported at the consuming call: ZSTD_c_windowLog 29 .. 31 (the decoder's offset record holds 29 bits), and what
+ * ZSTDMI_CCtx_setSingleFrame refuses otherwise.  ZSTDMI_compressBatch / ZSTDMI_compressPack: such an entry goes through the single-call
+ * path.  Cost: every step indexes its window again ((2^wl + n) of stage work for n bytes).  Figures: README "Sliding long-distance window". */
+size_t ZSTDMI_CCtx_setSlidingLdm(ZSTD_CCtx* cctx, unsigned mode);
 size_t ZSTDMI_seekTableBound(size_t srcSize);
 size_t ZSTDMI_decompressRange(ZSTD_DCtx* dctx, void* dst, size_t dstCapacity, const void* src, size_t srcSize,
                               unsigned long long offset, size_t length);

@@ -107,6 +107,7 @@ SIGNATURES = {
     "ZSTDMI_CCtx_setDictIndexStrategy": (c_size_t, [c_void_p, c_uint]),
     "ZSTDMI_debugDictIndexed": (ctypes.c_longlong, [c_void_p]),
     "ZSTDMI_CCtx_setSingleFrame": (c_size_t, [c_void_p, c_uint]),
+    "ZSTDMI_CCtx_setSlidingLdm": (c_size_t, [c_void_p, c_uint]),
     "ZSTDMI_seekTableBound": (c_size_t, [c_size_t]),
     "ZSTDMI_decompressRange": (c_size_t, [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_ull, c_size_t]),
     "ZSTDMI_debugLastRangeFrames": (c_int, [c_void_p]),

@@ -74,6 +74,7 @@ class Compressor(_PrefixHolder):
         self._dict_index = False
         self._dict_index_strategy = 1
         self._single_frame = False
+        self._sliding_ldm = False
         self.Level = level if level else self.DefaultCompressionLevel
 
     # ---- static members (S/Compressor.cs:8-10) ----
@@ -183,6 +184,17 @@ class Compressor(_PrefixHolder):
         self._ensure_not_disposed()
         ensure_zstd_success(self._lib, self._lib.ZSTDMI_CCtx_setSingleFrame(self.cctx, 1 if on else 0))
         self._single_frame = bool(on)
+
+    # ---- under single_frame, a long-distance window that slides with the frame (ZSTDMI_CCtx_setSlidingLdm); off by default ----
+    @property
+    def sliding_ldm(self) -> bool:
+        return self._sliding_ldm
+
+    @sliding_ldm.setter
+    def sliding_ldm(self, on):
+        self._ensure_not_disposed()
+        ensure_zstd_success(self._lib, self._lib.ZSTDMI_CCtx_setSlidingLdm(self.cctx, 1 if on else 0))
+        self._sliding_ldm = bool(on)
 
     # ---- Wrap (S/Compressor.cs:78-96) ----
     def Wrap(self, src, dest=None, offset: int = 0):

@@ -19,6 +19,9 @@
 // block 0 of the source begins: position - candidate is the zstd offset, the source's tiles and blocks keep their alignment, and no
 // tile straddles the seam.  Splits are taken over [vlo, end) — the rolling hash and a split's window run across the seam —, the
 // prefix's sort in front of the source's, and only the source's blocks are matched: the prefix's splits are candidates only.
+// A window that slides with ONE frame (ZSTDMI_CCtx_setSlidingLdm; the WIN instance of ldm_match): the same coordinate, with the frame's
+// own content in front of the pass — up to 2^windowLog bytes of it, in the same buffer — in the prefix's place, and a distance bound,
+// because such a pass may be longer than its window.
 #include <hip/hip_runtime.h>
 #include "zmi_common.h"
 #include "zmi_device.h"
@@ -231,7 +234,11 @@ __device__ __forceinline__ u32 wave_match_back(const u8* a, const u8* b, u32 lim
 // a compare always lies in the source; the candidate's side is read in two segments: a forward compare that starts in the prefix
 // runs on into the source, a backward one that starts in the source runs back into the prefix and stops at the prefix's first byte.
 // Either is cut at the seam into two wave compares of 256 bytes a step, the second only when the first matched to its end.
-template <bool PFX>
+// WIN (a window that slides with its frame, ZSTDMI_CCtx_setSlidingLdm; with PFX): what lies in front of the source is the frame's own
+// content, up to pfx.maxDist = 2^windowLog bytes of it, and the source may be longer than that, so the index holds splits further back
+// than a position may reach: a candidate more than pfx.maxDist behind its split is passed over (a match keeps its candidate's
+// distance when it is extended, so no offset exceeds the window).
+template <bool PFX, bool WIN = false>
 __global__ __launch_bounds__(256) void ldm_match_kernel(const u8* __restrict__ src, u64 n, u32 nChunks, u32 chunkBytes, u64 frameSpan, u32 minMatch, u32 bucketLog, const LdmPrefix pfx,
                                                         const u32* __restrict__ splitPos, const u32* __restrict__ splitCheck, const u64* __restrict__ sortedKey,
                                                         const u32* __restrict__ sortedVal, const u32* __restrict__ inv, u32 nSplits,
@@ -256,6 +263,7 @@ __global__ __launch_bounds__(256) void ldm_match_kernel(const u8* __restrict__ s
                 const u32 j = inv[s]; const u64 k = sortedKey[j]; const u32 cs = splitCheck[s];
                 for (u32 i = 1; i <= ents && i <= j; ++i) {
                     if (sortedKey[j - i] != k) break;
+                    if (WIN && w - splitPos[sortedVal[j - i]] > pfx.maxDist) break;      // (a bucket's splits lie in position order: the rest is further back)
                     if (splitCheck[sortedVal[j - i]] == cs) { has = true; break; }
                 }
             }
@@ -272,6 +280,7 @@ __global__ __launch_bounds__(256) void ldm_match_kernel(const u8* __restrict__ s
                 const u32 t = sortedVal[j - i];
                 if (splitCheck[t] != cs) continue;
                 const u32 cw = splitPos[t];
+                if (WIN && w - cw > pfx.maxDist) break;
                 const u32 fwdLim = (u32)(bEnd - w);
                 u32 fwd;
                 if (PFX && cw < pfx.base) {
@@ -465,7 +474,9 @@ void launch_ldm_rest(const u8* src, u64 n, u32 nChunks, u32 chunkBytes, u64 fram
     }
     hipLaunchKernelGGL(ldm_inv_kernel, dim3((nSplits + 255) / 256), dim3(256), 0, stream, valA, inv, nSplits);
     hook("ldm_sort");
-    if (pfx.pre) hipLaunchKernelGGL(ldm_match_kernel<true>, dim3((nChunks + 3) / 4), dim3(256), 0, stream, src, n, nChunks, chunkBytes, frameSpan, p.minMatch, p.bucketLog, pfx,
+    if (pfx.pre && pfx.maxDist) hipLaunchKernelGGL((ldm_match_kernel<true, true>), dim3((nChunks + 3) / 4), dim3(256), 0, stream, src, n, nChunks, chunkBytes, frameSpan, p.minMatch, p.bucketLog, pfx,
+                                                   splitPos, splitCheck, keyA, valA, inv, nSplits, mStart, mLen, mOff);
+    else if (pfx.pre) hipLaunchKernelGGL(ldm_match_kernel<true>, dim3((nChunks + 3) / 4), dim3(256), 0, stream, src, n, nChunks, chunkBytes, frameSpan, p.minMatch, p.bucketLog, pfx,
                                     splitPos, splitCheck, keyA, valA, inv, nSplits, mStart, mLen, mOff);
     else hipLaunchKernelGGL(ldm_match_kernel<false>, dim3((nChunks + 3) / 4), dim3(256), 0, stream, src, n, nChunks, chunkBytes, frameSpan, p.minMatch, p.bucketLog, pfx,
                             splitPos, splitCheck, keyA, valA, inv, nSplits, mStart, mLen, mOff);

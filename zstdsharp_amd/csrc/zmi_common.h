@@ -247,7 +247,9 @@ struct StageHook {
 struct LdmLaunch { u32 minMatch, hashLog, bucketLog, hashRateLog; };
 // A referenced prefix in front of the pass (ZSTD_CCtx_refPrefix, ldm.hip): device pointer (nullptr = none), the source's first byte
 // in the virtual coordinate (the prefix length rounded up to kLdmPrefixAlign) and the prefix's first byte there (base - prefix length)
-struct LdmPrefix { const u8* pre = nullptr; u32 base = 0, vlo = 0; };
+// maxDist (0 = none): a window that slides with its frame (ZSTDMI_CCtx_setSlidingLdm): the "prefix" is the frame's content in front of
+// the pass, and no match may lie further back than this many bytes
+struct LdmPrefix { const u8* pre = nullptr; u32 base = 0, vlo = 0, maxDist = 0; };
 constexpr u32 kLdmPrefixAlign = 16384;
 constexpr u32 kLdmMinHashRateLog = 5;      // the split workspace keeps at most one split per 16 bytes: denser split rates are refused
 

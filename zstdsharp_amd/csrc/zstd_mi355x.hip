@@ -69,6 +69,12 @@ struct ZSTD_CCtx_s {
     // (sSingle; and the checksum flag, which its header states), the bytes it has put into its frame (sTotal) and the last kStreamTail of them as the next batch's history (sTail)
     int singleFrame = 0; DevBuf sfXxh; XxhCarry sfXxhHost = {};
     bool sSingle = false; int sChecksum = 0; u64 sTotal = 0; std::vector<u8> sTail;     // (sChecksum: the flag the session's header states)
+    // ZSTDMI_CCtx_setSlidingLdm (sticky): under the single frame, long-distance matching's window slides with the frame (sliding_active).
+    // A session notes at its beginning whether it runs so and with which windowLog (sSliding, sSlideLog); it then keeps the frame's
+    // latest content on the device instead of sTail: sWin holds sWinFill bytes, the last min(sTotal, 2^sSlideLog) of the frame among
+    // them, and every batch is appended there (cstream_compress_sliding)
+    int slidingLdm = 0;
+    bool sSliding = false; int sSlideLog = 0; DevBuf sWin; size_t sWinFill = 0;
 };
 // History per chunk lives in LDS beside the chunk: up to 32 KiB of dictionary in front of 32 KiB chunks, or up to 60 KiB when
 // the whole input fits behind it in one chunk (small records, the usual dictionary case).
@@ -113,6 +119,7 @@ struct CallParams {
     bool dictEntropy = false;           // code with a formatted dictionary's entropy tables (ZSTDMI_CCtx_setDictEntropy; ZSTD_compressCCtx uses no dictionary)
     const u8* pfx = nullptr; size_t pfxSize = 0;    // the long form of a referenced prefix (compress_prefixed): device bytes in front of the ONE frame
     bool single = false;                // one frame per call (ZSTDMI_CCtx_setSingleFrame; ZSTD_compressCCtx: never, level-only parameters)
+    bool sliding = false;               // ... whose long-distance window slides with it (ZSTDMI_CCtx_setSlidingLdm; takes effect where sliding_active says)
     // a batch of a single-frame stream session (cstream_compress_single): streamAt bytes of the frame lie in front of it (the last
     // kStreamTail of them readable in front of the source), and the batch ends the frame or not
     bool stream = false, streamEnd = false; u64 streamAt = 0;
@@ -124,7 +131,7 @@ static CallParams sticky_params(const ZSTD_CCtx* c)
     p.seek = c->seekTable != 0;
     p.dictEntropy = c->dictEntropy != 0;
     p.dictIndex = c->dictIndex != 0; p.dictIndexStrategy = c->dictIndexStrategy;
-    p.single = c->singleFrame != 0;
+    p.single = c->singleFrame != 0; p.sliding = c->slidingLdm != 0;
     p.ldm = c->ldm; p.ldmHashLog = c->ldmHashLog; p.ldmMinMatch = c->ldmMinMatch; p.ldmBucketSizeLog = c->ldmBucketSizeLog; p.ldmHashRateLog = c->ldmHashRateLog;
     return p;
 }
@@ -229,6 +236,7 @@ static const DictCTables* call_dict_ctables(const ZSTD_CCtx* c, const CallParams
 struct Framing { u32 prefixLen, chunkBytes, frameBlocks; Resolved rs; u32 indepWindowLog = 0; bool ldm = false; LdmLaunch ldmP = {};
                  bool dictIndex = false;    // full 64 KiB chunks, each a frame, behind the indexed dictionary (ZSTDMI_CCtx_setDictIndex)
                  bool single = false; u32 singleWindowLog = 0;      // ONE frame across passes; the window its header declares beside (or instead of) the content size, 0 = a single segment
+                 u32 slideLog = 0;          // single and ldm: the stage's window is the 2^slideLog bytes in front of a position, wherever a pass or a batch begins (0: off)
 
                  size_t span() const { return (size_t)chunkBytes * (frameBlocks ? frameBlocks : 1u); } };
 
@@ -280,9 +288,26 @@ static u32 history_block_bytes(const Resolved& rf, int hb)
 // the history of the framings that always have one (LDM windows, one frame per call): the context's, or by strategy
 static int history_bytes_or_default(const ZSTD_CCtx* c, const Resolved& rf) { return c->historyBytes > 0 ? c->historyBytes : (rf.cp.strategy == kStratDfast ? (16 << 10) : (32 << 10)); }
 
+static Framing resolve_framing(const ZSTD_CCtx* c, const CallParams& cp, size_t paramSize);
+// the content of one frame of the long-distance framing (an aligned window: min(2^windowLog, 512 MiB, a pass))
+static size_t ldm_frame_span(const ZSTD_CCtx* c, const CallParams& cp, size_t paramSize)
+{
+    CallParams plain = cp; plain.single = false; plain.sliding = false;
+    return resolve_framing(c, plain, paramSize).span();
+}
+// ZSTDMI_CCtx_setSlidingLdm takes effect exactly where check_single_frame refuses without it: one frame, ZSTD_ps_enable, and a stream
+// session or a call of more than one long-distance frame.  (Everywhere else the switch changes nothing.)
+static bool sliding_active(const ZSTD_CCtx* c, const CallParams& cp, size_t paramSize)
+{
+    if (!cp.sliding || !cp.single || cp.pfxSize || cp.ldm != 1) return false;
+    if (cp.stream) return true;
+    return ldm_active(cp, paramSize) && paramSize > ldm_frame_span(c, cp, paramSize);
+}
+
 static Framing resolve_framing(const ZSTD_CCtx* c, const CallParams& cp, size_t paramSize)
 {
-    if (single_active(cp, paramSize)) {
+    const bool sliding = sliding_active(c, cp, paramSize);
+    if (sliding || single_active(cp, paramSize)) {
         // The blocks are the long-distance framing's (below) without its stage: full 64 KiB blocks with far candidates at the fast
         // strategy, 64 KiB - 16/32 KiB blocks behind LDS history above it; every block but the first sees the input in front of it,
         // wherever a pass or a batch begins (zmi_frame.h, kSingle).  The header is the reference's: with wl = ZSTD_c_windowLog, or the level's
@@ -291,9 +316,13 @@ static Framing resolve_framing(const ZSTD_CCtx* c, const CallParams& cp, size_t 
         Framing f; f.prefixLen = 0; f.single = true;
         const Resolved rf = resolve_call(cp, paramSize, (u32)1 << 31);
         const u32 chunkBytes = history_block_bytes(rf, history_bytes_or_default(c, rf));
-        const u32 wl = cp.windowLog ? (u32)cp.windowLog : rf.cp.windowLog;
+        // With a sliding long-distance window (sliding_active) the blocks, the finders and the header's rules are the same; wl is the
+        // stage's window (ZSTD_c_windowLog, or 27), its parameters follow from it as they do for the aligned windows, and the stage
+        // lets no offset exceed it (ldm.hip, WIN).
+        const u32 wl = sliding ? (u32)ldm_window_log(cp) : cp.windowLog ? (u32)cp.windowLog : rf.cp.windowLog;
         f.singleWindowLog = (cp.stream || (u64)paramSize > ((u64)1 << wl)) ? wl : 0u;
         f.chunkBytes = chunkBytes; f.frameBlocks = 0x7FFFFFFFu; f.rs = rf;      // (frameBlocks: "blocks share a frame"; a block's place is counted in bytes: zmi_frame.h, kSingle)
+        if (sliding) { f.ldm = true; f.slideLog = wl; f.ldmP = ldm_resolve(cp, paramSize); }
         return f;
     }
     if (cp.pfxSize || ldm_active(cp, paramSize)) {
@@ -480,7 +509,7 @@ static size_t compress_range(ZSTD_CCtx* c, const CallParams& cp, u8* d_dst, size
     const DictCTables* const dct = ls.dct;
     const u64 totalChunks = (srcSize + chunkBytes - 1) / chunkBytes;
     u32 passChunks = (u32)(totalChunks < c->passChunks ? totalChunks : c->passChunks);
-    if (fr.ldm) { const u32 most = whole_frame_chunks((u32)(((u64)1 << 31) / chunkBytes), frameBlocks); if (passChunks > most) passChunks = most; }    // (ldm.hip: u32 offsets in a pass)
+    if (fr.ldm) { const u32 fit = (u32)(((u64)1 << 31) / chunkBytes), most = fr.slideLog ? fit : whole_frame_chunks(fit, frameBlocks); if (passChunks > most) passChunks = most; }    // (ldm.hip: u32 offsets in a pass; a sliding window adds at most 2^28 in front)
     if (frameBlocks && !fr.single && passChunks < totalChunks) { passChunks = whole_frame_chunks(passChunks, frameBlocks); if (!passChunks) passChunks = frameBlocks; }     // frames never straddle passes
     if (!cctx_workspace(c, passChunks)) return ZERR(kErrMemoryAllocation);
     if (ls.regionParse && !cctx_cand_workspace(c, passChunks, ls.hcChains)) return ZERR(kErrMemoryAllocation);
@@ -499,7 +528,14 @@ static size_t compress_range(ZSTD_CCtx* c, const CallParams& cp, u8* d_dst, size
             const u64 span = (u64)frameBlocks * chunkBytes;
             // a referenced prefix: splits over prefix and source as one window in the virtual coordinate (ldm.hip), nL = its end
             LdmPrefix lp;
-            if (cp.pfxSize) { lp.pre = cp.pfx; lp.base = (u32)((cp.pfxSize + kLdmPrefixAlign - 1) / kLdmPrefixAlign * kLdmPrefixAlign); lp.vlo = lp.base - (u32)cp.pfxSize; }
+            if (fr.slideLog) {
+                // a sliding window: what the frame holds in front of this pass, up to 2^slideLog bytes of it, takes the prefix's place.
+                // It lies in front of src (the caller's own input; a session's device window) and is read there.  The first pass has
+                // nothing in front of it and runs the same instances, for the distance bound: it may be longer than the window.
+                const u64 keep = frames.at < ((u64)1 << fr.slideLog) ? frames.at : ((u64)1 << fr.slideLog);
+                lp.pre = src - keep; lp.base = (u32)((keep + kLdmPrefixAlign - 1) / kLdmPrefixAlign * kLdmPrefixAlign); lp.vlo = lp.base - (u32)keep;
+                lp.maxDist = 1u << fr.slideLog;
+            } else if (cp.pfxSize) { lp.pre = cp.pfx; lp.base = (u32)((cp.pfxSize + kLdmPrefixAlign - 1) / kLdmPrefixAlign * kLdmPrefixAlign); lp.vlo = lp.base - (u32)cp.pfxSize; }
             const u64 nL = lp.base + n;
             if (!c->ldmSmall.ensure(ldm_small_bytes(nL))) return ZERR(kErrMemoryAllocation);
             launch_ldm_count(src, nL, span, fr.ldmP, (u8*)c->ldmSmall.p, s, lp);
@@ -623,8 +659,10 @@ static size_t check_single_frame(const ZSTD_CCtx* c, const CallParams& cp, size_
     if (cp.seek || c->workers.size() > 1) return ZERR(kErrParameterUnsupported);       // (frames are the seek table's and the workers' unit)
     if (cp.windowLog >= 10 && cp.windowLog < 18) return ZERR(kErrParameterUnsupported); // (the finders reach up to 2^18 back)
     if (cp.useDict && (c->dictFormatted || c->dictHost.size() >= 8)) return ZERR(kErrParameterUnsupported);   // (a dictionary's framing: a prefix in front of independent blocks)
-    if (cp.stream ? cp.ldm == 1 : ldm_active(cp, srcSize)) {       // one LDM frame is one frame already (bytes unchanged); more than one is not
-        if (cp.stream || srcSize > resolve_framing(c, cp, srcSize).span()) return ZERR(kErrParameterUnsupported);
+    if (cp.stream ? cp.ldm == 1 : ldm_active(cp, srcSize)) {       // one LDM frame is one frame already (bytes unchanged); more than one is not,
+        if (cp.stream || srcSize > ldm_frame_span(c, cp, srcSize)) {  // unless the window slides (ZSTDMI_CCtx_setSlidingLdm): up to 2^28, the decoder's 29-bit offset record
+            if (!cp.sliding || ldm_window_log(cp) > 28) return ZERR(kErrParameterUnsupported);
+        }
     }
     return 0;
 }
@@ -782,7 +820,7 @@ size_t ZSTD_freeCCtx(ZSTD_CCtx* c)
         (void)hipSetDevice(c->device);
         if (c->ownStream) (void)hipStreamSynchronize(c->ownStream);
         c->seqs.release(); c->lits.release(); c->meta.release(); c->tables.release(); c->slots.release(); c->cand.release(); c->probe.release();
-        c->gatherIn.release(); c->gatherOut.release(); c->batchStage.release(); c->batchTab.release(); c->packArena.release(); c->packTab.release(); c->ldmSmall.release(); c->ldmBig.release(); c->offsets.release(); c->total.release(); c->seekEntries.release(); c->seekSort.release(); c->stageSrc.release(); c->stageDst.release(); c->pfxStage.release(); c->sfXxh.release(); c->dict.release(); c->dictWideDev.release(); c->dictIdxDev.release(); c->dictFullDev.release(); c->dictInfoDev.release(); c->dictCTabDev.release();
+        c->gatherIn.release(); c->gatherOut.release(); c->batchStage.release(); c->batchTab.release(); c->packArena.release(); c->packTab.release(); c->ldmSmall.release(); c->ldmBig.release(); c->offsets.release(); c->total.release(); c->seekEntries.release(); c->seekSort.release(); c->stageSrc.release(); c->stageDst.release(); c->pfxStage.release(); c->sfXxh.release(); c->sWin.release(); c->dict.release(); c->dictWideDev.release(); c->dictIdxDev.release(); c->dictFullDev.release(); c->dictInfoDev.release(); c->dictCTabDev.release();
         c->timer.destroy();
         if (c->ownStream) (void)hipStreamDestroy(c->ownStream);
     }
@@ -1224,6 +1262,7 @@ static size_t cstream_compress_single(ZSTD_CCtx* c, size_t n, bool ending)
 {
     CallParams cp = sticky_params(c);
     cp.single = true; cp.stream = true; cp.streamAt = c->sTotal; cp.streamEnd = ending; cp.seek = false; cp.checksumFlag = c->sChecksum;
+    cp.sliding = false;     // (a session that did not begin with a sliding window has none: the refusal stands)
     size_t e = cctx_bind(c); if (isErr(e)) return e;
     e = check_call_params(cp); if (isErr(e)) return e;
     e = check_single_frame(c, cp, n); if (isErr(e)) return e;
@@ -1244,6 +1283,59 @@ static size_t cstream_compress_single(ZSTD_CCtx* c, size_t n, bool ending)
     if (c->sTail.size() > kStreamTail) c->sTail.erase(c->sTail.begin(), c->sTail.end() - (ptrdiff_t)kStreamTail);
     c->sTotal += n;
     c->sIn.erase(c->sIn.begin(), c->sIn.begin() + (ptrdiff_t)n);
+    return 0;
+}
+// The same for a session whose long-distance window slides (ZSTDMI_CCtx_setSlidingLdm; sSliding): the frame's latest content stays on
+// the device, in sWin, and a batch is appended to it, so that the 2^sSlideLog bytes in front of the batch (the stage's window, and the
+// finders' history with them) lie in front of it where compress_range reads them.  sWin holds the window, one batch and kSlideSlack
+// bytes more.  When the next batch does not fit, the window's bytes are moved to the front: a left shift by more than kSlideSlack, done
+// as device-to-device copies of at most the shift's length each, front to back on the one stream, so that no copy overlaps itself
+// (at most 2^sSlideLog / kSlideSlack + 1 of them, and only once per kSlideSlack bytes of input).  A batch is at most sBatch bytes:
+// more is cut, which a session without the switch does not do.
+constexpr size_t kSlideSlack = (size_t)4 << 20;
+static CallParams sliding_session_params(const ZSTD_CCtx* c)
+{
+    CallParams cp = sticky_params(c);
+    cp.single = true; cp.stream = true; cp.seek = false; cp.checksumFlag = c->sChecksum;
+    cp.sliding = true; cp.ldm = 1; cp.windowLog = c->sSlideLog;         // (what the session noted when it began)
+    return cp;
+}
+static size_t cstream_compress_sliding(ZSTD_CCtx* c, size_t n, bool ending)
+{
+    size_t e = cctx_bind(c); if (isErr(e)) return e;
+    const size_t win = (size_t)1 << c->sSlideLog, room = win + c->sBatch + kSlideSlack;
+    while (n) {
+        const size_t m = n < c->sBatch ? n : c->sBatch;
+        CallParams cp = sliding_session_params(c);
+        cp.streamAt = c->sTotal; cp.streamEnd = ending && m == n;
+        e = check_call_params(cp); if (isErr(e)) return e;
+        e = check_single_frame(c, cp, m); if (isErr(e)) return e;
+        if (c->sTotal + m > kSingleMax) return ZERR(kErrParameterUnsupported);
+        const size_t cap = ZSTD_compressBound(m) + 32;
+        if (c->sTotal == 0) { c->sWinFill = 0; if (!c->sWin.ensure(room + 64)) return ZERR(kErrMemoryAllocation); }      // (allocated by the session's first batch)
+        if (!c->sWin.p || c->sWin.cap < room + 64) return ZERR(kErrGeneric);
+        if (!c->stageDst.ensure(cap + 64)) return ZERR(kErrMemoryAllocation);
+        u8* const w = (u8*)c->sWin.p;
+        if (c->sWinFill + m > room) {       // roll: the last `win` bytes to the front (sWinFill > win + kSlideSlack here)
+            const size_t shift = c->sWinFill - win;
+            for (size_t at = 0; at < win; at += shift) {
+                const size_t len = win - at < shift ? win - at : shift;
+                if (hipMemcpyAsync(w + at, w + at + shift, len, hipMemcpyDeviceToDevice, c->stream) != hipSuccess) return ZERR(kErrGeneric);
+            }
+            c->sWinFill = win;
+        }
+        u8* const d_src = w + c->sWinFill;
+        if (hipMemcpyAsync(d_src, c->sIn.data(), m, hipMemcpyHostToDevice, c->stream) != hipSuccess) return ZERR(kErrGeneric);
+        bool first = true;
+        const size_t r = compress_range(c, cp, (u8*)c->stageDst.p, cap, d_src, m, kStreamParamSize, first);
+        if (isErr(r)) return r;
+        const size_t at = c->sOut.size();
+        c->sOut.resize(at + r);
+        if (isErr(dev_read(c->sOut.data() + at, c->stageDst.p, r, c->stream))) { c->sOut.resize(at); return ZERR(kErrGeneric); }
+        c->sWinFill += m; c->sTotal += m;
+        c->sIn.erase(c->sIn.begin(), c->sIn.begin() + (ptrdiff_t)m);
+        n -= m;
+    }
     return 0;
 }
 // ZSTD_e_end with nothing buffered behind earlier batches: an empty raw last block, and the checksum of what the frame holds
@@ -1271,9 +1363,11 @@ static size_t ZSTD_compressStream2_impl(ZSTD_CCtx* c, ZSTD_outBuffer* output, ZS
     if (input->size > input->pos && !input->src) return ZERR(kErrSrcSizeWrong);
     if (output->size > output->pos && !output->dst) return ZERR(kErrDstBufferNull);
     if (cstream_drain(c, output)) return c->sOut.size() - c->sOutPos;       // output full: nothing consumed this time
-    if (!c->sWrote && !c->sEnding && c->sIn.empty()) { c->sSingle = c->singleFrame != 0; c->sChecksum = c->checksumFlag; c->sTotal = 0; c->sTail.clear(); }      // a session begins
+    if (!c->sWrote && !c->sEnding && c->sIn.empty()) { c->sSingle = c->singleFrame != 0; c->sChecksum = c->checksumFlag; c->sTotal = 0; c->sTail.clear();      // a session begins
+        c->sSliding = c->sSingle && c->slidingLdm && c->ldm == 1; c->sSlideLog = c->windowLog ? c->windowLog : kLdmDefaultWindowLog; c->sWinFill = 0; }
     if (c->sSingle && !c->sEnding) {    // what one frame per session cannot be: refused before anything is taken
-        CallParams cp = sticky_params(c); cp.single = true; cp.stream = true; cp.seek = false;
+        CallParams cp = sticky_params(c); cp.single = true; cp.stream = true; cp.seek = false; cp.sliding = false;
+        if (c->sSliding) cp = sliding_session_params(c);
         const size_t e = check_single_frame(c, cp, 0); if (isErr(e)) return e;
     }
     if (!c->sEnding) {
@@ -1281,9 +1375,9 @@ static size_t ZSTD_compressStream2_impl(ZSTD_CCtx* c, ZSTD_outBuffer* output, ZS
         if (n) { c->sIn.insert(c->sIn.end(), (const u8*)input->src + input->pos, (const u8*)input->src + input->size); input->pos = input->size; c->sWrote = true; }
         size_t e = 0;
         if (endOp == 0) {                                      // ZSTD_e_continue: whole chunks only, so that frames stay 64 KiB
-            if (c->sIn.size() >= c->sBatch) { const size_t whole = c->sIn.size() / kChunkSize * kChunkSize; e = c->sSingle ? cstream_compress_single(c, whole, false) : cstream_compress(c, whole); }
+            if (c->sIn.size() >= c->sBatch) { const size_t whole = c->sIn.size() / kChunkSize * kChunkSize; e = c->sSliding ? cstream_compress_sliding(c, whole, false) : c->sSingle ? cstream_compress_single(c, whole, false) : cstream_compress(c, whole); }
         } else {
-            if (!c->sIn.empty()) e = c->sSingle ? cstream_compress_single(c, c->sIn.size(), endOp == 2) : cstream_compress(c, c->sIn.size());     // (ZSTD_e_flush ends a block, not the frame)
+            if (!c->sIn.empty()) e = c->sSliding ? cstream_compress_sliding(c, c->sIn.size(), endOp == 2) : c->sSingle ? cstream_compress_single(c, c->sIn.size(), endOp == 2) : cstream_compress(c, c->sIn.size());     // (ZSTD_e_flush ends a block, not the frame)
             else if (endOp == 2 && c->sSingle && c->sTotal) e = cstream_end_single(c);
             else if (endOp == 2 && !c->sWrote) {               // ZSTD_e_end on an empty stream: the empty frame (U/ZstdCompress.cs:5598-5656)
                 u8 tmp[16]; const size_t r = ZSTD_compress2(c, tmp, sizeof tmp, tmp, 0);
@@ -1294,7 +1388,8 @@ static size_t ZSTD_compressStream2_impl(ZSTD_CCtx* c, ZSTD_outBuffer* output, ZS
         if (isErr(e)) return e;
     }
     const size_t left = cstream_drain(c, output);
-    if (c->sEnding && left == 0) { c->sEnding = false; c->sWrote = false; c->sTotal = 0; c->sTail.clear(); }    // frame session closed; the context may start another
+    if (c->sEnding && left == 0) { c->sEnding = false; c->sWrote = false; c->sTotal = 0; c->sTail.clear();      // frame session closed; the context may start another
+        if (c->sSliding) { c->sSliding = false; c->sWinFill = 0; if (c->deviceOk && !isErr(cctx_bind(c))) c->sWin.release(); } }       // (and its device window goes with it)
     if (endOp == 0) return left ? left : (c->sBatch > c->sIn.size() ? c->sBatch - c->sIn.size() : 1);
     return left;
 }
@@ -1315,6 +1410,8 @@ size_t ZSTDMI_CCtx_setHistory(ZSTD_CCtx* c, int bytes, unsigned frameBytes)
 size_t ZSTDMI_CCtx_setSeekTable(ZSTD_CCtx* c, unsigned mode) { if (!c) return ZERR(kErrGeneric); if (mode > 1) return ZERR(kErrParameterOutOfBound); c->seekTable = (int)mode; return 0; }
 // (no device is touched; what the switch cannot be combined with is refused by the call that would have to do it: check_single_frame)
 size_t ZSTDMI_CCtx_setSingleFrame(ZSTD_CCtx* c, unsigned mode) { if (!c) return ZERR(kErrGeneric); if (mode > 1) return ZERR(kErrParameterOutOfBound); c->singleFrame = (int)mode; return 0; }
+// (no device is touched; where the switch takes effect: sliding_active, and what it cannot be combined with: check_single_frame)
+size_t ZSTDMI_CCtx_setSlidingLdm(ZSTD_CCtx* c, unsigned mode) { if (!c) return ZERR(kErrGeneric); if (mode > 1) return ZERR(kErrParameterOutOfBound); c->slidingLdm = (int)mode; return 0; }
 size_t ZSTDMI_seekTableBound(size_t srcSize) { return seek_table_bound(srcSize); }
 // (no device is touched: a loaded formatted dictionary is marked for another upload, which builds — or no longer builds — its tables)
 size_t ZSTDMI_CCtx_setDictEntropy(ZSTD_CCtx* c, unsigned mode)
@@ -1722,7 +1819,7 @@ static size_t compress_pack_impl(ZSTD_CCtx* c, u8* d_dst, size_t dstCapacity, co
             // alone: straight to its place.  Its rows: one frame per call knows its own (the empty frame; one frame across passes,
             // which the seek table's switch refuses), the others file theirs pass by pass as under ZSTDMI_CCtx_setSeekTable
             const size_t S = sizes[i];
-            const bool oneFrame = S == 0 || single_active(cp, S);
+            const bool oneFrame = S == 0 || single_active(cp, S) || sliding_active(c, cp, S);
             if (!oneFrame) {
                 if (!c->seekEntries.ensure(seek_max_frames(S) * 8)) return ZERR(kErrMemoryAllocation);
                 c->seekOn = true; c->seekCount = 0;

@@ -29,13 +29,15 @@ class CompressionStream:
     ZSTD_e_end until nothing remains (S/CompressionStream.cs:113-147)."""
 
     def __init__(self, stream, level: int = 0, bufferSize: int = 0, compressor: Compressor = None, leaveOpen: bool = True,
-                 single_frame: bool = None):
+                 single_frame: bool = None, sliding_ldm: bool = None):
         self._lib = _ffi.load()
         self.innerStream = stream
         self._own = compressor is None
         self.compressor = compressor if compressor is not None else Compressor(level)
         if single_frame is not None:                          # one frame per stream session (Compressor.single_frame); None: as the compressor has it
             self.compressor.single_frame = single_frame
+        if sliding_ldm is not None:                           # ... whose long-distance window slides across batches (Compressor.sliding_ldm)
+            self.compressor.sliding_ldm = sliding_ldm
         self._outSize = bufferSize if bufferSize > 0 else ensure_zstd_success(self._lib, self._lib.ZSTD_CStreamOutSize())      # S/CompressionStream.cs:40-41
         self._out = ctypes.create_string_buffer(self._outSize)
         self._leaveOpen = leaveOpen
