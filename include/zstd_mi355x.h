@@ -370,7 +370,8 @@ size_t ZSTDMI_CCtx_setDictIndex(ZSTD_CCtx* cctx, unsigned mode);
 /* The highest strategy at which an index that is switched on (ZSTDMI_CCtx_setDictIndex(1)) is used.
  * 1 = fast only (the default: exactly what ZSTDMI_CCtx_setDictIndex describes above); 2 = also doubleFast (level 3, the default
  * level, and level 4: wherever the call resolves to the dual-hash finder).  Sticky; touches no device.  NULL: GENERIC.  0 or above 2:
- * parameter_outOfBound (3+ is kept for the chain finder of the levels >= 5, which the index does not serve).
+ * parameter_outOfBound (the chain finder of the levels >= 5 has a switch of its own, ZSTDMI_CCtx_setDictIndexChain below; this
+ * setting keeps refusing 3 and above).
  * With the index off the setting changes nothing.  With it on, a change of the setting has a loaded dictionary uploaded again by
  * the next call that uses it; ZSTD_CCtx_loadDictionary, ZSTDMI_CCtx_setDictIndex and this call may come in any order, and the level
  * or ZSTD_c_strategy may change between calls without another load.  At 2 an upload builds three tables over the same bytes (the
@@ -378,6 +379,23 @@ size_t ZSTDMI_CCtx_setDictIndex(ZSTD_CCtx* cctx, unsigned mode);
  * in each of its two, behind its four candidates in the block, and a dictionary candidate has to be longer to win.  Framing, entry
  * points, what stays unchanged (now: levels >= 5) and the refusals are those of ZSTDMI_CCtx_setDictIndex. */
 size_t ZSTDMI_CCtx_setDictIndexStrategy(ZSTD_CCtx* cctx, unsigned maxStrategy);
+/* The index for the chain finder: levels >= 5 and ZSTD_c_strategy >= 3.  0 = off (the default), 1 = on, any other mode:
+ * parameter_outOfBound; NULL context: GENERIC.  Sticky; touches no device; any order relative to ZSTD_CCtx_loadDictionary,
+ * ZSTDMI_CCtx_setDictIndex and ZSTDMI_CCtx_setDictIndexStrategy, of whose value it is independent (that setting reaches strategy 2,
+ * this switch covers what lies above).  While the index is on, a change has a loaded dictionary uploaded again by the next call that
+ * uses it; an upload then builds the same three tables as ZSTDMI_CCtx_setDictIndexStrategy(2), so the level may change between calls
+ * without another load.  It takes effect where ZSTDMI_CCtx_setDictIndex(1) is set, a dictionary of at least 8 bytes is in use and the
+ * call resolves to the chain finder: nothing of the dictionary is staged or linked into hash chains per chunk, a source of up to
+ * 64 KiB is one block in one single-segment frame (without it: 64 KiB minus the staged tail), larger sources are independent 64 KiB
+ * frames, and every position looks up, behind its walk down the block's chains, one candidate per hash (5 and 8 bytes) anywhere in the
+ * dictionary's last 188 KiB; a dictionary candidate has to be longer than the block's best to win, and a match into the dictionary ends
+ * with it.  There are no chains inside the dictionary: one candidate per hash, where the staged tail offered a chain's depth of them.
+ * Header fields, dictID, repcodes, checksum, ZSTDMI_CCtx_setDictEntropy, the entry points, ZSTD_c_windowLog 10 .. 15 and the refusals
+ * are those of ZSTDMI_CCtx_setDictIndex. */
+size_t ZSTDMI_CCtx_setDictIndexChain(ZSTD_CCtx* cctx, unsigned mode);
+/* (debug) chunks that the last pass launched by the last compress call handed to the region parse's kernel of its own (the fast
+ * finder's on plain chunks, the chain finder's): 0 when it did not run, -1 without a context */
+long long ZSTDMI_debugLastRegionChunks(const ZSTD_CCtx* cctx);
 /* (debug) dictionary content bytes the index covers: 0 with the switch off, without a dictionary, or for a formatted dictionary no
  * call has validated on a device yet; -1 without a context */
 long long ZSTDMI_debugDictIndexed(const ZSTD_CCtx* cctx);

@@ -9,7 +9,7 @@ with history of the default settings — at the same kinds and levels.  Per poin
 Best of 3 after a warm-up call of the same shape; the host clock stops after the call's final synchronise (every call ends with one).
 The input is 16 MiB of generated data repeated (entries are independent, so the repeats are nobody's match).
 python tools/batch_time.py [MiB] [--dict-entropy] [--dict-row] [--frames-rows] [--measure-only] [--dict-index-rows] [--dict-index]
-                           [--level=N] [--dict-index-strategy=N]
+                           [--level=N] [--dict-index-strategy=N] [--dict-index-chain]
   --dict-index-rows : only the rows of ZSTDMI_CCtx_setDictIndex, batch calls alone: 4 KiB text entries at level 1 with
                    tests/golden/train_default_text.dict, and the 1000 held-out JSON records of tests/golden/make_golden_train.py
                    tiled to the total with train_default_json.dict; the ratio, the batch call's ms and its stage times
@@ -17,6 +17,8 @@ python tools/batch_time.py [MiB] [--dict-entropy] [--dict-row] [--frames-rows] [
   --level=N      : those rows at level N instead of 1 (3: the dual-hash finder)
   --dict-index-strategy=N : those rows with ZSTDMI_CCtx_setDictIndexStrategy(N) (2: the index also serves level 3; without the flag the
                    call is not made, so the rows also run on a library from before it existed)
+  --dict-index-chain : those rows with ZSTDMI_CCtx_setDictIndexChain(1) (the index also serves the levels >= 5; without the flag the call
+                   is not made, so the rows also run on a library from before it existed)
   --dict-entropy : the dictionary row with ZSTDMI_CCtx_setDictEntropy on (the dictionary's entropy tables in the compressor)
   --dict-row     : only the dictionary row
   --frames-rows  : only the 256 KiB and 1 MiB rows
@@ -34,10 +36,10 @@ FLAGS = [a for a in sys.argv[1:] if a.startswith("--")]
 ARGS = [a for a in sys.argv[1:] if not a.startswith("--")]
 VALUED = {f.split("=", 1)[0]: int(f.split("=", 1)[1]) for f in FLAGS if "=" in f}
 FLAGS = [f for f in FLAGS if "=" not in f]
-assert all(f in ("--dict-entropy", "--dict-row", "--frames-rows", "--measure-only", "--dict-index-rows", "--dict-index") for f in FLAGS), FLAGS
+assert all(f in ("--dict-entropy", "--dict-row", "--frames-rows", "--measure-only", "--dict-index-rows", "--dict-index", "--dict-index-chain") for f in FLAGS), FLAGS
 assert all(f in ("--level", "--dict-index-strategy") for f in VALUED), VALUED
 DICT_INDEX_ROWS, DICT_INDEX = "--dict-index-rows" in FLAGS, "--dict-index" in FLAGS
-INDEX_LEVEL, INDEX_STRATEGY = VALUED.get("--level", 1), VALUED.get("--dict-index-strategy")
+INDEX_LEVEL, INDEX_STRATEGY, INDEX_CHAIN = VALUED.get("--level", 1), VALUED.get("--dict-index-strategy"), "--dict-index-chain" in FLAGS
 DICT_ENTROPY, DICT_ROW, FRAMES_ROWS, MEASURE_ONLY = "--dict-entropy" in FLAGS, "--dict-row" in FLAGS, "--frames-rows" in FLAGS, "--measure-only" in FLAGS
 total = (int(ARGS[0]) if ARGS else 256) * MiB
 SAMPLE = 4096
@@ -83,7 +85,7 @@ def dict_index_rows():
     reps = total // len(json_blob)
     rows = [(f"text 4 KiB L{INDEX_LEVEL} train_default_text", "train_default_text.dict", text, [4096] * (total // 4096)),
             (f"json records L{INDEX_LEVEL} train_default_json", "train_default_json.dict", json_blob * reps, json_sizes * reps)]
-    print(f"level {INDEX_LEVEL}; dictionary index {'on' if DICT_INDEX else 'off'}, up to strategy {INDEX_STRATEGY if INDEX_STRATEGY else '1 (not set)'}; "
+    print(f"level {INDEX_LEVEL}; dictionary index {'on' if DICT_INDEX else 'off'}, up to strategy {INDEX_STRATEGY if INDEX_STRATEGY else '1 (not set)'}, chain finder {'on' if INDEX_CHAIN else 'off'}; "
           f"entropy tables {'on' if DICT_ENTROPY else 'off'}", flush=True)
     for name, dname, blob, szs in rows:
         dic = open(os.path.join(golden, dname), "rb").read()
@@ -100,6 +102,8 @@ def dict_index_rows():
             ok(lib.ZSTDMI_CCtx_setDictIndex(c, 1))
         if INDEX_STRATEGY:
             ok(lib.ZSTDMI_CCtx_setDictIndexStrategy(c, INDEX_STRATEGY))
+        if INDEX_CHAIN:
+            ok(lib.ZSTDMI_CCtx_setDictIndexChain(c, 1))
         if DICT_ENTROPY:
             ok(lib.ZSTDMI_CCtx_setDictEntropy(c, 1))
         torch.cuda.synchronize(); t0 = time.perf_counter()

@@ -105,6 +105,8 @@ SIGNATURES = {
     "ZSTDMI_CCtx_setDictEntropy": (c_size_t, [c_void_p, c_uint]),
     "ZSTDMI_CCtx_setDictIndex": (c_size_t, [c_void_p, c_uint]),
     "ZSTDMI_CCtx_setDictIndexStrategy": (c_size_t, [c_void_p, c_uint]),
+    "ZSTDMI_CCtx_setDictIndexChain": (c_size_t, [c_void_p, c_uint]),
+    "ZSTDMI_debugLastRegionChunks": (ctypes.c_longlong, [c_void_p]),
     "ZSTDMI_debugDictIndexed": (ctypes.c_longlong, [c_void_p]),
     "ZSTDMI_CCtx_setSingleFrame": (c_size_t, [c_void_p, c_uint]),
     "ZSTDMI_CCtx_setSlidingLdm": (c_size_t, [c_void_p, c_uint]),

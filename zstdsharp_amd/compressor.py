@@ -73,6 +73,7 @@ class Compressor(_PrefixHolder):
         self._dict_entropy = False
         self._dict_index = False
         self._dict_index_strategy = 1
+        self._dict_index_chain = False
         self._single_frame = False
         self._sliding_ldm = False
         self.Level = level if level else self.DefaultCompressionLevel
@@ -173,6 +174,17 @@ class Compressor(_PrefixHolder):
         self._ensure_not_disposed()
         ensure_zstd_success(self._lib, self._lib.ZSTDMI_CCtx_setDictIndexStrategy(self.cctx, int(max_strategy)))
         self._dict_index_strategy = int(max_strategy)
+
+    # ---- dict_index for the chain finder, levels 5 and up (ZSTDMI_CCtx_setDictIndexChain); off by default ----
+    @property
+    def dict_index_chain(self) -> bool:
+        return self._dict_index_chain
+
+    @dict_index_chain.setter
+    def dict_index_chain(self, on):
+        self._ensure_not_disposed()
+        ensure_zstd_success(self._lib, self._lib.ZSTDMI_CCtx_setDictIndexChain(self.cctx, 1 if on else 0))
+        self._dict_index_chain = bool(on)
 
     # ---- one frame per Wrap and per stream session (ZSTDMI_CCtx_setSingleFrame), as the reference writes; off by default ----
     @property

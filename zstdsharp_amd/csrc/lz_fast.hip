@@ -210,6 +210,31 @@ __device__ __forceinline__ u32 match_len_dict(const LzLds& L, u32 p, const u8* _
     return l >= 4 ? l : 0;
 }
 
+// the same for the chain finder (ZSTDMI_CCtx_setDictIndexChain), whose matches are measured up to kHcLenCap = 64 bytes, the data's last
+// ones included: p + 8 <= n, so the last LDS read (three dwords from p + 56 rounded down) ends below n + kInPad; a read of the
+// dictionary starts in front of its end and reaches at most 7 bytes behind it
+constexpr u32 kHcLenCap = 64;
+static_assert(kHcLenCap - 8 + 12 <= kInPad + 8, "match_len_dict_hc reads LDS up to p + kHcLenCap + 4 with p <= n - 8");
+__device__ __forceinline__ u32 match_len_dict_hc(const LzLds& L, u32 p, const u8* __restrict__ g, u32 back, u64 w, u32 n)
+{
+    constexpr u32 cap = kHcLenCap;
+    const u64 cw = readLE64(g);
+    if ((u32)cw != (u32)w) return 0;
+    u64 x = w ^ cw;
+    u32 l = x ? (ctz64(x) >> 3) : 8;
+    if (!x) {
+        while (l < cap && l < back) {
+            x = lds_load8(L.in, p + l) ^ readLE64(g + l);
+            if (x) { l += ctz64(x) >> 3; break; }
+            l += 8;
+        }
+    }
+    if (l > back) l = back;
+    if (l > n - p) l = n - p;
+    if (l > cap) l = cap;
+    return l >= 4 ? l : 0;
+}
+
 // HASH: the finder's hash that the table serves: 0 = hash6p (fast), 1 = hash8p (the dual finder's long one), 2 = hash_shortp<5> (its short one)
 template <int HASH> __device__ __forceinline__ u32 didx_hash(u64 w) { return HASH == 0 ? hash6p(w) : HASH == 1 ? hash8p(w) : hash_shortp<5>(w); }
 template <int HASH>
@@ -405,8 +430,15 @@ struct HcLds {                           // laid over the 64 KiB of the hash tab
 };
 static_assert(sizeof(HcLds) == sizeof(u32) * (2u << kHashLog), "HcLds fills the tables' place");
 
+// IDX (ZSTDMI_CCtx_setDictIndexChain): the chunk stands behind an indexed dictionary.  Behind the chain walk a position
+// probes one entry of dix.tableLong and one of dix.tableShort; a dictionary match that is strictly longer than the block's best (it is
+// further away than anything in the block) leaves kDictCand in candG and its distance back from the dictionary's end in distG, the
+// workgroup's second plane: written only there, read by the walker only on kDictCand.
+constexpr u32 kDictCand = 0xFFFFu;       // (a block candidate has 8 readable bytes: position + 1 <= 65528)
+template <bool IDX = false>
 __device__ __forceinline__ void hc_tiles(LzLds& L, const u32 n, const u32 tFrom, const u32 tTo, const u32 candFrom, const u32 lowLimit, const u32 depth,
-                                         u16* __restrict__ candG, u16* __restrict__ chainG, const u32 tid, const u32 lane, const u32 wave
+                                         u16* __restrict__ candG, u16* __restrict__ chainG, const DictIndexRef& dix, u32* __restrict__ distG,
+                                         const u32 tid, const u32 lane, const u32 wave
 #ifdef ZMI_LZ_STAMPS
                                          , unsigned long long* dAcc, unsigned long long& dLast
 #endif
@@ -552,6 +584,38 @@ __device__ __forceinline__ void hc_tiles(LzLds& L, const u32 n, const u32 tFrom,
             pair_walk(I0{}, I2{});
             take_over(I1{}); take_over(I3{});
             pair_walk(I1{}, I3{});
+            if constexpr (IDX) {
+                // a short pass of its own over the four positions (inside the walk it would cost the walk registers): the eight
+                // entries in flight together, a miss on the 14-bit tag dropped before any dictionary byte is read
+                const u32 dLog = dix.log;
+                u32 eL[4], eS[4];
+#pragma unroll
+                for (u32 j = 0; j < 4; ++j) {
+                    eL[j] = 0; eS[j] = 0;
+                    if (valid[j] && bestLen[j] < 64) {
+                        const u32 hL = hash8p(a1[j]), hS = hash_shortp<5>(a1[j]);
+                        const u32 vL = dix.tableLong[hL >> (32 - dLog)], vS = dix.tableShort[hS >> (32 - dLog)];
+                        eL[j] = (vL & 0x3FFFu) == didx_tag(hL, dLog) ? vL >> 14 : 0u;        // position + 1, 0 = none
+                        eS[j] = (vS & 0x3FFFu) == didx_tag(hS, dLog) ? vS >> 14 : 0u;
+                    }
+                }
+#pragma unroll
+                for (u32 j = 0; j < 4; ++j) {
+                    if (eS[j] == eL[j]) eS[j] = 0;
+                    u32 dist = 0;
+                    if (eL[j]) {
+                        const u32 back = dix.len - (eL[j] - 1);
+                        const u32 l = match_len_dict_hc(L, p0 + j, dix.end - back, back, a1[j], n);
+                        if (l > bestLen[j]) { bestLen[j] = l; dist = back; }
+                    }
+                    if (eS[j]) {
+                        const u32 back = dix.len - (eS[j] - 1);
+                        const u32 l = match_len_dict_hc(L, p0 + j, dix.end - back, back, a1[j], n);
+                        if (l > bestLen[j]) { bestLen[j] = l; dist = back; }
+                    }
+                    if (dist) { best[j] = kDictCand; distG[p0 + j] = dist; }
+                }
+            }
             u64 out4 = 0;
 #pragma unroll
             for (u32 j = 0; j < 4; ++j) out4 |= (u64)(best[j] & 0xFFFFu) << (16 * j);
@@ -568,12 +632,18 @@ __device__ __forceinline__ void hc_tiles(LzLds& L, const u32 n, const u32 tFrom,
 // MODE as in lz_kernel (0 fast, 1 dual-hash, 2 dual-hash + lazy deferral).  hist / lowLimit: the history in front of the block in
 // LDS (positions below lowLimit are padding); insertFrom: first tile whose positions still have to go into the tables (lz_region_kernel
 // starts from empty tables: the history tiles and the block's first tile; inlined in lz_kernel: fromTile).
-template <int MODE>
+// IDX (MODE 2 only; see hc_tiles): a candidate may lie in the indexed dictionary.  The walker then speaks of a match's source by its
+// OFFSET (above the position: position + distance back from the dictionary's end), which reaches 64 KiB + 188 KiB: 18 bits, of which
+// the upper two go where the 16-bit places have room — a taken match is at least 4 long, so the third entry of the positions it covers
+// is free (C[p + 2]); a region's last end is below 2^17, so D.lastEnd carries them from bit 20 up.
+template <int MODE, bool IDX = false>
 __device__ __forceinline__ void dense_rest(LzLds& L, const u32 n, const u32 insertFrom, const u32 fromTile, const u32 nTiles, const u32 hist, const u32 lowLimit,
                                            u16* __restrict__ candG, u16* __restrict__ chainG, const u32 hcDepth,
                                            Seq* __restrict__ seqOut, u8* __restrict__ litOut,
-                                           u32& cursor, u32& nbSeq, u32& litBase, bool& deferred, const u32 tid, const u32 lane, const u32 wave)
+                                           u32& cursor, u32& nbSeq, u32& litBase, bool& deferred, const u32 tid, const u32 lane, const u32 wave,
+                                           const DictIndexRef& dix = DictIndexRef{}, u32* __restrict__ distG = nullptr)
 {
+    static_assert(!IDX || MODE == 2, "the indexed region parse is the chain finder's");
     static_assert(sizeof(DenseLds) <= sizeof(L.tileLen) + sizeof(L.tileOff) + sizeof(L.jump), "DenseLds must fit over tileLen .. jump");
     DenseLds& D = *reinterpret_cast<DenseLds*>(&L.tileLen[0]);
     // positions of a pass's matches by rank: behind DenseLds, over what is left of the tile loop's arrays (all idle by now)
@@ -588,9 +658,9 @@ __device__ __forceinline__ void dense_rest(LzLds& L, const u32 n, const u32 inse
 #endif
     // ---------------- I: candidates of every position, tile by tile ----------------
 #if defined(ZMI_EXP_STOP) && ZMI_EXP_STOP == 3
-    if constexpr (MODE == 2) { hc_tiles(L, n, lowLimit >> kTileLog, hist >> kTileLog, fromTile, lowLimit, hcDepth, candG, chainG, tid, lane, wave); __syncthreads(); return; }
+    if constexpr (MODE == 2) { hc_tiles<IDX>(L, n, lowLimit >> kTileLog, hist >> kTileLog, fromTile, lowLimit, hcDepth, candG, chainG, dix, distG, tid, lane, wave); __syncthreads(); return; }
 #endif
-    if constexpr (MODE == 2) hc_tiles(L, n, lowLimit >> kTileLog, nTiles, fromTile, lowLimit, hcDepth, candG, chainG, tid, lane, wave
+    if constexpr (MODE == 2) hc_tiles<IDX>(L, n, lowLimit >> kTileLog, nTiles, fromTile, lowLimit, hcDepth, candG, chainG, dix, distG, tid, lane, wave
 #ifdef ZMI_LZ_STAMPS
                                       , dAcc, dLast
 #endif
@@ -659,6 +729,28 @@ __device__ __forceinline__ void dense_rest(LzLds& L, const u32 n, const u32 inse
                 ++p; l = l2; cpos = c2 - 1;
             }
         };
+        // IDX: the same three by offset.  A dictionary match is verified up to 64 bytes like one in the block and goes on through the
+        // same-offset rule below (it does not run on in place: a lane's stretch is below 128 bytes); it ends with the dictionary
+        auto cand_off = [&](u32 p, u32 cv) -> u32 { return cv == kDictCand ? p + distG[p] : p - (cv - 1); };
+        auto verify_off = [&](u32 p, u32 off) -> u32 {
+            if (off <= p) return verify(p, p - off);
+            const u32 back = off - p;
+            return match_len_dict_hc(L, p, dix.end - back, back, lds_load8(L.in, p), n);
+        };
+        auto lazy_off = [&](u32& p, u32& l, u32& off, const u32 bound) {
+            for (;;) {
+                if (p + 1 >= bound || p + 9 > n) break;
+                const u32 c2 = C[p + 1 - lo];
+                if (!c2) break;
+                const u32 off2 = cand_off(p + 1, c2);
+                const u32 l2 = verify_off(p + 1, off2);
+                if (!l2) break;
+                const int g1 = (int)(l * 4) - (int)highbit32(off + 1) + 4;
+                const int g2 = (int)(l2 * 4) - (int)highbit32(off2 + 1);
+                if (g2 <= g1) break;
+                ++p; l = l2; off = off2;
+            }
+        };
         // ---- step 1, speculative: where does the parse LEAVE this region?  The lane starts kWarm positions in front of its region
         // (the first region of a pass at the cursor it was handed): a greedy parse forgets where it started within a few matches,
         // so it usually leaves the region exactly where the parse that comes through the regions before it will.  Nothing is written ----
@@ -679,8 +771,13 @@ __device__ __forceinline__ void dense_rest(LzLds& L, const u32 n, const u32 inse
                 p += skip;
                 if (p >= re) break;
                 const u32 cp = (u32)(c4 >> (16 * skip)) & 0xFFFFu;
-                u32 l = (p + 8 <= n) ? verify(p, cp - 1) : 0u;
-                if (MODE == 2 && l) { u32 cq = cp - 1; lazy(p, l, cq, re); }
+                u32 l = 0;
+                if constexpr (IDX) {
+                    if (p + 8 <= n) { u32 off = cand_off(p, cp); l = verify_off(p, off); if (l) lazy_off(p, l, off, re); }
+                } else {
+                    l = (p + 8 <= n) ? verify(p, cp - 1) : 0u;
+                    if (MODE == 2 && l) { u32 cq = cp - 1; lazy(p, l, cq, re); }
+                }
                 p += l ? l : 1u;
             }
             if (p < re) p = re;
@@ -710,12 +807,18 @@ __device__ __forceinline__ void dense_rest(LzLds& L, const u32 n, const u32 inse
                 if (p >= bound) break;
                 const u32 cp = (u32)(c4 >> (16 * skip)) & 0xFFFFu;
                 if (p + 8 > n) { ++p; continue; }
-                u32 cpos = cp - 1;
-                u32 l = verify(p, cpos);
-                if (MODE == 2 && l) lazy(p, l, cpos, bound);
+                u32 cpos = cp - 1, l, offX = 0;
+                if constexpr (IDX) { offX = cand_off(p, cp); l = verify_off(p, offX); if (l) lazy_off(p, l, offX, bound); cpos = p - offX; }
+                else {
+                    l = verify(p, cpos);
+                    if (MODE == 2 && l) lazy(p, l, cpos, bound);
+                }
                 if (!lastReg && p + l > eSpec) l = eSpec - p;
                 if (l < 4) { ++p; continue; }
-                const u32 off = p - cpos;
+                const u32 off = IDX ? offX : p - cpos;
+                if (IDX && off > p) {       // the source lies in the dictionary: byte steps against global memory, as far as it is indexed
+                    while (p > anchor && off - p < dix.len && L.in[p - 1] == dix.end[-(s64)(off - p) - 1]) { --p; ++l; }
+                } else
                 while (p > anchor && cpos > lowLimit && L.in[p - 1] == L.in[cpos - 1]) { --p; --cpos; ++l; }     // ZstdFast.cs:242-247
                 const u32 q = p - rs;                                    // 0 .. 126
                 {   // bytes [q, q + l) of the lane's stretch (a backward extension can make a match longer than the 64 verified bytes)
@@ -728,13 +831,14 @@ __device__ __forceinline__ void dense_rest(LzLds& L, const u32 n, const u32 inse
                     if (lastStart == firstStart) firstLen += l;
                 } else {
                     C[p - lo] = (u16)off; C[p - lo + 1] = (u16)l;
+                    if constexpr (IDX) C[p - lo + 2] = (u16)(off >> 16);
                     if (!(selLo | selHi)) { firstOff = off; firstLen = l; firstStart = p; }
                     if (q < 64) selLo |= 1ull << q; else selHi |= 1ull << (q - 64);
                     lastStart = p;
                 }
                 p += l; anchor = p; lastOff = off; lastEnd = p;
             }
-            D.lastEnd[tid] = lastEnd; D.lastOff[tid] = (u16)lastOff; D.covHi[tid] = covHi;
+            D.lastEnd[tid] = IDX ? lastEnd | ((lastOff >> 16) << 20) : lastEnd; D.lastOff[tid] = (u16)lastOff; D.covHi[tid] = covHi;
         }
         ZMI_DSTAMP(13);
         // ---- where the pass's last match ends (the next pass's cursor) ----
@@ -753,7 +857,7 @@ __device__ __forceinline__ void dense_rest(LzLds& L, const u32 n, const u32 inse
         if (mine) {
             if (tid > 0) covLo |= D.covHi[tid - 1];                            // what the lane before this one did beyond its region
             if (cursor > rs) covLo |= cursor - rs >= 64 ? ~0ull : ((1ull << (cursor - rs)) - 1);     // a match from before the pass
-            if ((selLo | selHi) && tid > 0 && firstStart == D.lastEnd[tid - 1] && firstOff == (u32)D.lastOff[tid - 1]) {
+            if ((selLo | selHi) && tid > 0 && (IDX ? firstStart | ((firstOff >> 16) << 20) : firstStart) == D.lastEnd[tid - 1] && (IDX ? firstOff & 0xFFFFu : firstOff) == (u32)D.lastOff[tid - 1]) {
                 absorbed = firstLen;
                 if (selLo) selLo &= selLo - 1; else selHi &= selHi - 1;
             }
@@ -795,7 +899,7 @@ __device__ __forceinline__ void dense_rest(LzLds& L, const u32 n, const u32 inse
         lds_barrier();
         for (u32 k = tid; k < totM; k += kTile) {
             const u32 pos = rankPos[k], prev = k ? rankPos[k - 1] : 0u;
-            const u32 off = C[pos], len = C[pos + 1], plen = C[prev + 1];
+            const u32 off = IDX ? (u32)C[pos] | ((u32)C[pos + 2] << 16) : (u32)C[pos], len = C[pos + 1], plen = C[prev + 1];
             const u32 pe = k ? lo + prev + plen : cursor;
             Seq sq; sq.offBase = off + 3; sq.litLength = (u16)(lo + pos - pe); sq.mlBase = (u16)(len - 3);
             // (streaming stores, here and for the literals: what this kernel should keep in L2 is its candidate plane)
@@ -1625,7 +1729,8 @@ __global__ __launch_bounds__(1024) void lz_kernel(const LzArgs a)
         // a chunk whose first tile is dense in matches (text, source code, structured data) is finished by lz_region_kernel: this
         // loop verifies every position to keep one in eight.  (A kernel of its own: with the region parse inlined here the tile
         // loop itself ran 8 % slower on sparse data — code size.)
-        if (!FAR && regionList && tileStart == hist && !super && strideLog == 0 && matchCount >= kDenseMin && nTiles > (hist >> kTileLog) + 2) {      // uniform
+        // (of the far instances the chain finder behind an indexed dictionary alone has a region parse)
+        if ((!FAR || (kIndexed && MODE == 2)) && regionList && tileStart == hist && !super && strideLog == 0 && matchCount >= kDenseMin && nTiles > (hist >> kTileLog) + 2) {      // uniform
             if constexpr ((MODE == 0 && !DICT) || MODE == 2) { regionCursor = cursor + 1; break; }     // (kSplit of launch_one)
             else {
                 __syncthreads();
@@ -1659,12 +1764,23 @@ __global__ __launch_bounds__(1024) void lz_kernel(const LzArgs a)
 // tail in front of it, is staged again; the fast finder's table gets the first tile's positions (the latest occurrence per
 // bucket, as the tile loop left it; the first-occurrence table starts empty: it only ever serves the tile that filled it); and
 // the region parse takes the tiles after the first from the state lz_kernel recorded.
-template <int MODE, bool DICT, int TAB>
+// TAB == kPlaceIndexed (MODE 2, no DICT; ZSTDMI_CCtx_setDictIndexChain): the chunk alone is staged, behind an indexed dictionary, and
+// the kernel takes one argument more, a RegionDix — a pack of none or one, so that the other instances keep the arguments they had.
+// (The plain alternative, one device function behind two kernels, was compiled: lz_region_kernel<2, true, 1> then came out with 52
+//  bytes of scratch for its 56 and the indexed kernel with 36 for its 28.  Existing instances are to keep their code objects, so the
+//  pack stays.)
+struct RegionDix { DictIndexRef dix; u32* dist; };      // dist: 65536 u32 per workgroup (dense_rest's distG)
+__device__ __forceinline__ RegionDix region_dix() { return RegionDix{}; }
+__device__ __forceinline__ const RegionDix& region_dix(const RegionDix& r) { return r; }
+template <int MODE, bool DICT, int TAB, class... DX>
 __global__ __launch_bounds__(1024) void lz_region_kernel(const u8* __restrict__ src, u64 srcSize, Seq* __restrict__ seqs, u8* __restrict__ lits,
                                                          ChunkMeta* __restrict__ meta, u16* __restrict__ candAll, u16* __restrict__ chainAll, const u32* __restrict__ regionList,
                                                          const u8* __restrict__ prefixArg, const u32 prefixLenArg, const u32 chunkBytes, const u32 frameBlocksArg, const u32 hcDepth,
-                                                         const u32* __restrict__ chunkLens, const u32* __restrict__ chunkFrames, const u64 frameAt)
+                                                         const u32* __restrict__ chunkLens, const u32* __restrict__ chunkFrames, const u64 frameAt, const DX... dx)
 {
+    constexpr bool kIndexed = TAB == kPlaceIndexed;
+    static_assert(kIndexed == (sizeof...(DX) == 1) && (!kIndexed || (MODE == 2 && !DICT)), "the indexed instance, and it alone, takes a RegionDix");
+    constexpr int kPlaceForm = kIndexed ? kArith : TAB;
     const u32 frameBlocks = frame_blocks_decode(frameBlocksArg).frameBlocks;
     const bool indep = frame_blocks_decode(frameBlocksArg).independent;
     extern __shared__ __attribute__((aligned(16))) u8 ldsRaw[];
@@ -1682,8 +1798,8 @@ __global__ __launch_bounds__(1024) void lz_region_kernel(const u8* __restrict__ 
     const u8* __restrict__ in = src + base;
     // (srcSize, frameTotal: the frame's length is not asked for here.  The block index is read for independent blocks only, which
     //  the single-frame form never has: that it is "first or not" there, where this kernel once took 0, changes nothing)
-    const FrameLayout frames = { TAB, cb, frameBlocks, srcSize, chunkFrames, frameAt, 0 };
-    const BlockPlace place = (DICT && frameBlocks) ? block_place<TAB>(frames, c) : block_alone(0);
+    const FrameLayout frames = { kPlaceForm, cb, frameBlocks, srcSize, chunkFrames, frameAt, 0 };
+    const BlockPlace place = (DICT && frameBlocks) ? block_place<kPlaceForm>(frames, c) : block_alone(0);
     u32 prefixLen = prefixLenArg; const u8* __restrict__ prefix = prefixArg;
     if (DICT && frameBlocks && !indep) { prefixLen = place.front < hist ? (u32)place.front : hist; prefix = in - prefixLen; }
     if (DICT && indep && place.block) prefixLen = 0;
@@ -1741,6 +1857,11 @@ __global__ __launch_bounds__(1024) void lz_region_kernel(const u8* __restrict__ 
     const u32 nTiles = (n + kTilePos - 1) / kTilePos;
     // (candidate and link planes belong to the WORKGROUP, not to the chunk: written and read back within a chunk's time, the same
     //  128 KiB per CU again and again stay in L2 / the memory-side cache instead of travelling to HBM and back)
+    if constexpr (kIndexed) {
+        const RegionDix& rd = region_dix(dx...);
+        dense_rest<MODE, true>(L, n, insertFrom, 1, nTiles, hist, lowLimit, candAll + (u64)blockIdx.x * kChunkSize, chainAll + (u64)blockIdx.x * kChunkSize, hcDepth,
+                               seqs + (u64)c * kMaxSeq, lits + (u64)c * kLitStride, cursor, nbSeq, litBase, deferred, tid, lane, wave, rd.dix, rd.dist + (u64)blockIdx.x * kChunkSize);
+    } else
     dense_rest<MODE>(L, n, insertFrom, (hist >> kTileLog) + 1, nTiles, hist, lowLimit, candAll + (u64)blockIdx.x * kChunkSize, chainAll ? chainAll + (u64)blockIdx.x * kChunkSize : nullptr, hcDepth,
                      seqs + (u64)c * kMaxSeq, lits + (u64)c * kLitStride, cursor, nbSeq, litBase, deferred, tid, lane, wave);
     if (tid == 0) { meta[c].nbSeq = nbSeq; meta[c].litSize = litBase; meta[c].litFromSrc = deferred ? 1u : 0u; }
@@ -1826,13 +1947,14 @@ static void launch_one(const LzLaunch& a)
     int dev = 0; (void)hipGetDevice(&dev);
     if (!attrSet[dev & 63]) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(lz_kernel<MODE, DICT, FAR, TAB>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(LzLds));
-        if constexpr (kSplit) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(lz_region_kernel<MODE, DICT, TAB>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(LzLds));
+        if constexpr (kSplit && kIndexed) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(lz_region_kernel<MODE, DICT, TAB, RegionDix>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(LzLds));
+        else if constexpr (kSplit) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(lz_region_kernel<MODE, DICT, TAB>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(LzLds));
         attrSet[dev & 63] = true;
     }
-    // (the full 64 KiB blocks with far candidates have no region parse, no per-chunk tables and nothing staged in front of them; behind
-    //  an indexed dictionary a batch's chunks do have their lengths)
+    // (the full 64 KiB blocks with far candidates have no region parse — but the chain finder's behind an indexed dictionary —, no
+    //  per-chunk tables and nothing staged in front of them; behind an indexed dictionary a batch's chunks do have their lengths)
     assert(!FAR || (!a.prefixLen && (kIndexed || !a.chunkLens)));
-    u16* const cand = FAR ? nullptr : a.cand;
+    u16* const cand = (FAR && !(kIndexed && MODE == 2)) ? nullptr : a.cand;
     const u32 chunkBytes = DICT ? a.frames.chunkBytes : kChunkSize;
     const u32 frameBlocks = frame_blocks_encode((DICT || FAR) ? a.frames.frameBlocks : 0u, a.independent);
     if (cand && kSplit) (void)hipMemsetAsync(a.regionList, 0, sizeof(u32), a.stream);
@@ -1847,7 +1969,12 @@ static void launch_one(const LzLaunch& a)
                        kIndexed ? *a.dix : DictIndexRef{} };
     hipLaunchKernelGGL((lz_kernel<MODE, DICT, FAR, TAB>), dim3(grid), dim3(kTile), sizeof(LzLds), a.stream, k);
     a.hook("lz_fast");
-    if constexpr (kSplit) if (cand) {                      // the dense chunks' rest: 256 workgroups (one per CU) walk the list
+    if constexpr (kSplit && kIndexed) { if (cand) {
+        hipLaunchKernelGGL((lz_region_kernel<MODE, DICT, TAB, RegionDix>), dim3(a.nChunks < 256 ? a.nChunks : 256), dim3(kTile), sizeof(LzLds), a.stream, a.src, a.srcSize, a.seqs, a.lits, a.meta, cand, a.chain, a.regionList,
+                           a.prefix, a.prefixLen, chunkBytes, frameBlocks, a.hcDepth, a.chunkLens, a.frames.table, a.frames.at, RegionDix{ *a.dix, a.dist });
+        a.hook("lz_region");
+    } }
+    else if constexpr (kSplit) if (cand) {                 // the dense chunks' rest: 256 workgroups (one per CU) walk the list
         hipLaunchKernelGGL((lz_region_kernel<MODE, DICT, TAB>), dim3(a.nChunks < 256 ? a.nChunks : 256), dim3(kTile), sizeof(LzLds), a.stream, a.src, a.srcSize, a.seqs, a.lits, a.meta, cand, a.chain, a.regionList,
                            a.prefix, a.prefixLen, chunkBytes, frameBlocks, a.hcDepth, a.chunkLens, a.frames.table, a.frames.at);
         a.hook("lz_region");
@@ -1864,11 +1991,13 @@ void launch_lz(const LzLaunch& a)
     if (a.dix) {
         // every chunk a frame of its own behind an indexed dictionary: the FAR instance with the dictionary as what lies in front of
         // the block.  An instance of its own, so the kernels of a context without the switch are the ones from before it existed.
-        assert(f <= 1 && a.frames.form == kArith && !a.frames.frameBlocks && full && a.dix->len >= 8 && a.dix->len <= kFarMax);
+        assert(f <= 2 && a.frames.form == kArith && !a.frames.frameBlocks && full && a.dix->len >= 8 && a.dix->len <= kFarMax);
         assert(f == 0 ? a.dix->table != nullptr : (a.dix->tableLong && a.dix->tableShort));
-        // nothing is staged in front of a chunk, no chunk has a place in a frame, and there is no region parse
-        assert(!a.prefix && !a.prefixLen && !a.frames.table && !a.cand && !a.chain && !a.regionList);
-        return f == 0 ? launch_one<0, false, true, kPlaceIndexed>(a) : launch_one<1, false, true, kPlaceIndexed>(a);
+        // nothing is staged in front of a chunk, no chunk has a place in a frame, and there is no region parse — but the chain finder's
+        // (ZSTDMI_CCtx_setDictIndexChain), which comes with all three planes or, under ZSTDMI_CCtx_setParser(1), with none
+        assert(!a.prefix && !a.prefixLen && !a.frames.table);
+        assert(f == 2 ? (!a.cand == !a.chain && !a.cand == !a.regionList && !a.cand == !a.dist) : (!a.cand && !a.chain && !a.regionList && !a.dist));
+        return f == 0 ? launch_one<0, false, true, kPlaceIndexed>(a) : f == 1 ? launch_one<1, false, true, kPlaceIndexed>(a) : launch_one<2, false, true, kPlaceIndexed>(a);
     }
     if (a.frames.form == kSingle) {
         // one frame across passes: the long-distance framing's blocks (resolve_framing), each with its place in bytes.  Instances of

@@ -32,7 +32,9 @@ u32 dict_index_max();               // the most bytes an index covers (the far c
 // cand / chain / regionList (null: off): workspace of the region parse, 65536 u16 per chunk (twice with the hash chains of the
 // level >= 5 search, hcDepth attempts per position) and 1 + nChunks u32.  claimCtr: a zeroable word for the chunk claims (lz_kernel).
 // dix (null: off): an indexed dictionary behind full 64 KiB chunks, each a frame of its own (fast finder, or the dual one where dix has
-// its two tables; chunkLens allowed; prefix, cand, chain, regionList and frames.table are null).  The kernel gets a copy (LzArgs::dix).
+// its two tables; chunkLens allowed; prefix and frames.table are null, and so are cand, chain and regionList below the chain finder).
+// The kernel gets a copy (LzArgs::dix).  dist (the chain finder behind dix; else null): the region parse's second plane, 65536 u32 for each
+// of lz_region_kernel's at most 256 workgroups: where a position's candidate lies in the dictionary (ZSTDMI_CCtx_setDictIndexChain).
 struct LzLaunch {
     u32 finder;
     const u8* src; u64 srcSize; u32 nChunks;
@@ -42,6 +44,7 @@ struct LzLaunch {
     FrameHeaderSpec header;
     u32 minStrideLog;
     u16* cand; u16* chain; u32* regionList; u32 hcDepth;
+    u32* dist;
     u32* claimCtr;
     const u32* chunkLens;
     const DictIndexRef* dix;

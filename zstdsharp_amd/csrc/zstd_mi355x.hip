@@ -44,7 +44,11 @@ struct ZSTD_CCtx_s {
     // formatted one has them in dictFull); dictIdxEnd / Len / Log = what the last upload indexed (Len 0: nothing).
     // ZSTDMI_CCtx_setDictIndexStrategy (sticky): the highest strategy at which the index is used.  At 2 an upload builds, behind the
     // fast finder's table in dictIdxDev, one table per hash of the dual finder (all three, so the level may change between calls).
-    int dictIndex = 0, dictIndexStrategy = 1;
+    // ZSTDMI_CCtx_setDictIndexChain (sticky): the index also serves what resolves to the chain finder (levels 5 and up); an upload then
+    // builds the dual finder's two tables as at strategy 2.  dixDist: the second plane of the chain search's dense chunks (lz_fast.hip),
+    // of a context that uses it alone.  lastRegionList: the work list of the last pass's lz_region_kernel, null = none ran (debug hook)
+    int dictIndex = 0, dictIndexStrategy = 1, dictIndexChain = 0;
+    DevBuf dixDist; const u32* lastRegionList = nullptr;
     std::vector<u8> dictWide; DevBuf dictWideDev, dictIdxDev; const u8* dictIdxEnd = nullptr; u32 dictIdxLen = 0, dictIdxLog = 0; bool dictIdxDual = false;
     DictInfo info = {};
     u64 dictGen = 0;            // bumped by every ZSTD_CCtx_loadDictionary: device workers copy the dictionary when theirs is older
@@ -116,6 +120,7 @@ struct CallParams {
     bool seek = false;                  // append a seek table (ZSTDMI_CCtx_setSeekTable; ZSTD_compressCCtx: never, as it never runs LDM)
     bool dictIndex = false;             // look candidates up in the dictionary's index (ZSTDMI_CCtx_setDictIndex; ZSTD_compressCCtx uses no dictionary)
     int dictIndexStrategy = 1;          // ... at strategies up to this one (ZSTDMI_CCtx_setDictIndexStrategy)
+    bool dictIndexChain = false;        // ... and where the call resolves to the chain finder (ZSTDMI_CCtx_setDictIndexChain)
     bool dictEntropy = false;           // code with a formatted dictionary's entropy tables (ZSTDMI_CCtx_setDictEntropy; ZSTD_compressCCtx uses no dictionary)
     const u8* pfx = nullptr; size_t pfxSize = 0;    // the long form of a referenced prefix (compress_prefixed): device bytes in front of the ONE frame
     bool single = false;                // one frame per call (ZSTDMI_CCtx_setSingleFrame; ZSTD_compressCCtx: never, level-only parameters)
@@ -130,7 +135,7 @@ static CallParams sticky_params(const ZSTD_CCtx* c)
     p.strategy = c->strategy; p.targetLength = c->targetLength; p.windowLog = c->windowLog; p.searchLog = c->searchLog; p.minMatch = c->minMatch; p.chainLog = c->chainLog; p.useDict = true;
     p.seek = c->seekTable != 0;
     p.dictEntropy = c->dictEntropy != 0;
-    p.dictIndex = c->dictIndex != 0; p.dictIndexStrategy = c->dictIndexStrategy;
+    p.dictIndex = c->dictIndex != 0; p.dictIndexStrategy = c->dictIndexStrategy; p.dictIndexChain = c->dictIndexChain != 0;
     p.single = c->singleFrame != 0; p.sliding = c->slidingLdm != 0;
     p.ldm = c->ldm; p.ldmHashLog = c->ldmHashLog; p.ldmMinMatch = c->ldmMinMatch; p.ldmBucketSizeLog = c->ldmBucketSizeLog; p.ldmHashRateLog = c->ldmHashRateLog;
     return p;
@@ -172,6 +177,8 @@ static bool cctx_workspace(ZSTD_CCtx* c, u32 nChunks)
 // the region parse of the fast strategy keeps one candidate position (u16) per input byte between its two steps (lz_fast.hip)
 // region parse: candidates (u16 per position of a chunk's 64 KiB image) [+ the hash chains of the level >= 5 finder, same size] + the work list
 static size_t cand_plane_bytes(u32 nChunks) { return (size_t)nChunks * kChunkSize * sizeof(u16) + 256; }
+// the chain search behind an indexed dictionary: one u32 per position for each of lz_region_kernel's workgroups (at most 256)
+static bool cctx_dist_workspace(ZSTD_CCtx* c, u32 nChunks) { return c->dixDist.ensure((size_t)(nChunks < 256 ? nChunks : 256) * kChunkSize * sizeof(u32)); }
 static bool cctx_cand_workspace(ZSTD_CCtx* c, u32 nChunks, bool chains) { return c->cand.ensure(cand_plane_bytes(nChunks) * (chains ? 2 : 1) + ((size_t)nChunks + 1) * sizeof(u32)); }
 
 // upload a newly loaded dictionary; a formatted one is first validated on the device (ZSTD_loadCEntropy's checks are those of
@@ -211,7 +218,7 @@ static size_t cctx_sync_dictionary(ZSTD_CCtx* c)
             end = (const u8*)c->dictWideDev.p + ixLen;
         }
         const u32 log = dict_index_log(ixLen);
-        const bool dual = c->dictIndexStrategy >= 2;        // (the setter marks the dictionary dirty too)
+        const bool dual = c->dictIndexStrategy >= 2 || c->dictIndexChain;       // (the setters mark the dictionary dirty too)
         if (!c->dictIdxDev.ensure((sizeof(u32) << log) * (dual ? 3 : 1))) return ZERR(kErrMemoryAllocation);
         u32* const tables = (u32*)c->dictIdxDev.p;          // fast [| long | short], 1 << log entries each
         launch_dict_index(end - ixLen, ixLen, tables, log, s);
@@ -347,12 +354,13 @@ static Framing resolve_framing(const ZSTD_CCtx* c, const CallParams& cp, size_t 
         f.chunkBytes = chunkBytes; f.frameBlocks = frameBlocks; f.rs = rf;
         return f;
     }
-    // An indexed dictionary at the fast strategy — and, with ZSTDMI_CCtx_setDictIndexStrategy(2), at doubleFast: nothing of it is
+    // An indexed dictionary at the fast strategy — with ZSTDMI_CCtx_setDictIndexStrategy(2) at doubleFast, with
+    // ZSTDMI_CCtx_setDictIndexChain(1) at everything above, the chain finder (whatever the other setting says): nothing of it is
     // staged, so a chunk is a whole 64 KiB block and every chunk a single-segment frame behind the dictionary (ZSTD_c_windowLog
     // 10 .. 15 keeps its own framing: a window below the block)
     if (cp.useDict && cp.dictIndex && dict_index_len(c) && !(cp.windowLog >= 10 && cp.windowLog < (int)kChunkLog)) {
         const Resolved rx = resolve_call(cp, paramSize, kChunkSize);
-        if (rx.finder == 0 || (rx.finder == 1 && cp.dictIndexStrategy >= 2)) { Framing f; f.prefixLen = 0; f.chunkBytes = kChunkSize; f.frameBlocks = 0; f.rs = rx; f.dictIndex = true; return f; }
+        if (rx.finder == 0 || (rx.finder == 1 && cp.dictIndexStrategy >= 2) || (rx.finder == 2 && cp.dictIndexChain)) { Framing f; f.prefixLen = 0; f.chunkBytes = kChunkSize; f.frameBlocks = 0; f.rs = rx; f.dictIndex = true; return f; }
     }
     const u32 prefixLen = cp.useDict ? dict_prefix_len(c, paramSize) : 0u;
     u32 chunkBytes = kChunkSize - round_tile(prefixLen);
@@ -418,7 +426,9 @@ static LaunchState launch_state(const ZSTD_CCtx* c, const CallParams& cp, const 
     const Resolved& rs = fr.rs;
     LaunchState L;
     L.independent = fr.indepWindowLog != 0;       // (no history between the blocks of a frame)
-    L.regionParse = rs.minStrideLog == 0 && !(rs.finder == 0 && fr.frameBlocks && fr.chunkBytes >= kChunkSize) && !fr.dictIndex && c->parser == 0;   // (not the far-candidate finder)
+    // (not the far-candidate finder; behind an indexed dictionary the chain finder alone has one)
+    assert(!fr.dictIndex || (!fr.prefixLen && !fr.frameBlocks && fr.chunkBytes == kChunkSize && (rs.finder < 2 || cp.dictIndexChain)));
+    L.regionParse = rs.minStrideLog == 0 && !(rs.finder == 0 && fr.frameBlocks && fr.chunkBytes >= kChunkSize) && (!fr.dictIndex || rs.finder == 2) && c->parser == 0;
     L.hcChains = L.regionParse && rs.finder >= 2;
     // attempts per position of the level >= 5 search: the reference's 1 << searchLog (U/ZstdLazy.cs:641-642), between 4 and 32; the
     // greedy and lazy strategies (levels 5-7) stop at 8 unless ZSTD_c_searchLog asks for more: measured on text, 32 attempts
@@ -460,6 +470,8 @@ static LzLaunch pass_lz(ZSTD_CCtx* c, const LaunchState& L, const Framing& fr, c
     a.chain = L.hcChains ? (u16*)(planes + cand_plane_bytes(planeChunks)) : nullptr;
     a.regionList = L.regionParse ? (u32*)(planes + cand_plane_bytes(planeChunks) * (L.hcChains ? 2 : 1)) : nullptr;
     a.hcDepth = L.hcDepth;
+    a.dist = (L.regionParse && fr.dictIndex) ? (u32*)c->dixDist.p : nullptr;
+    c->lastRegionList = (L.regionParse && (fr.rs.finder == 2 || (fr.rs.finder == 0 && !fr.prefixLen && fr.chunkBytes >= kChunkSize))) ? a.regionList : nullptr;
     a.claimCtr = (u32*)((u64*)c->total.p + 4);      // (the claim counter: a word of `total`'s 64 bytes)
     a.chunkLens = chunkLens; a.dix = fr.dictIndex ? &L.dix : nullptr;
     a.stream = c->stream; a.hook = c->timer.hook();
@@ -481,6 +493,7 @@ static size_t compress_range(ZSTD_CCtx* c, const CallParams& cp, u8* d_dst, size
                              const std::vector<size_t>* markAt = nullptr, std::vector<u64>* marks = nullptr)
 {
     hipStream_t s = c->stream;
+    c->lastRegionList = nullptr;
     if (srcSize == 0) {     // ZSTD_writeEpilogue on an empty frame: header (FCS=0, single segment) + empty raw last block
         FrameHeaderSpec h = {}; h.checksum = cp.checksumFlag ? 1 : 0; h.noContentSize = cp.contentSizeFlag ? 0 : 1;
         if (h.noContentSize && cp.windowLog >= 10) h.windowLog = (u8)cp.windowLog;     // (the window descriptor states the caller's window)
@@ -513,6 +526,7 @@ static size_t compress_range(ZSTD_CCtx* c, const CallParams& cp, u8* d_dst, size
     if (frameBlocks && !fr.single && passChunks < totalChunks) { passChunks = whole_frame_chunks(passChunks, frameBlocks); if (!passChunks) passChunks = frameBlocks; }     // frames never straddle passes
     if (!cctx_workspace(c, passChunks)) return ZERR(kErrMemoryAllocation);
     if (ls.regionParse && !cctx_cand_workspace(c, passChunks, ls.hcChains)) return ZERR(kErrMemoryAllocation);
+    if (ls.regionParse && fr.dictIndex && !cctx_dist_workspace(c, passChunks)) return ZERR(kErrMemoryAllocation);
     size_t produced = 0;
     for (u64 c0 = 0; c0 < totalChunks; c0 += passChunks) {
         const u32 nChunks = (u32)((totalChunks - c0) < passChunks ? (totalChunks - c0) : passChunks);
@@ -819,7 +833,7 @@ size_t ZSTD_freeCCtx(ZSTD_CCtx* c)
     if (c->deviceOk) {
         (void)hipSetDevice(c->device);
         if (c->ownStream) (void)hipStreamSynchronize(c->ownStream);
-        c->seqs.release(); c->lits.release(); c->meta.release(); c->tables.release(); c->slots.release(); c->cand.release(); c->probe.release();
+        c->seqs.release(); c->lits.release(); c->meta.release(); c->tables.release(); c->slots.release(); c->cand.release(); c->lastRegionList = nullptr; c->dixDist.release(); c->probe.release();
         c->gatherIn.release(); c->gatherOut.release(); c->batchStage.release(); c->batchTab.release(); c->packArena.release(); c->packTab.release(); c->ldmSmall.release(); c->ldmBig.release(); c->offsets.release(); c->total.release(); c->seekEntries.release(); c->seekSort.release(); c->stageSrc.release(); c->stageDst.release(); c->pfxStage.release(); c->sfXxh.release(); c->sWin.release(); c->dict.release(); c->dictWideDev.release(); c->dictIdxDev.release(); c->dictFullDev.release(); c->dictInfoDev.release(); c->dictCTabDev.release();
         c->timer.destroy();
         if (c->ownStream) (void)hipStreamDestroy(c->ownStream);
@@ -967,6 +981,7 @@ size_t ZSTD_compressBound(size_t n) { return n + (n >> 8) + (n < (128u << 10) ? 
 static size_t ZSTDMI_compressDevice_impl(ZSTD_CCtx* c, void* d_dst, size_t dstCapacity, const void* d_src, size_t srcSize)
 {
     size_t e = cctx_bind(c); if (isErr(e)) return e;
+    c->lastRegionList = nullptr;
     if (srcSize && !d_src) return ZERR(kErrSrcSizeWrong);
     if (!d_dst && dstCapacity) return ZERR(kErrDstBufferNull);
     if (!d_dst) return ZERR(kErrDstSizeTooSmall);
@@ -979,6 +994,7 @@ static size_t ZSTDMI_compressDevice_impl(ZSTD_CCtx* c, void* d_dst, size_t dstCa
 static size_t compress_any(ZSTD_CCtx* c, const CallParams& cp, void* dst, size_t dstCapacity, const void* src, size_t srcSize)
 {
     size_t e = cctx_bind(c); if (isErr(e)) return e;
+    c->lastRegionList = nullptr;        // (ZSTDMI_debugLastRegionChunks speaks of this call from here on)
     if (srcSize && !src) return ZERR(kErrSrcSizeWrong);
     if (!dst) return ZERR(kErrDstSizeTooSmall);
     if (c->workers.size() > 1 && cp.seek) return ZERR(kErrParameterUnsupported);
@@ -1017,6 +1033,7 @@ static size_t compress_prefixed(ZSTD_CCtx* c, void* dst, size_t dstCapacity, con
     const void* const pfx = c->pfx; const size_t pfxSize = c->pfxSize;
     c->pfx = nullptr; c->pfxSize = 0;       // consumed, whatever this call returns (the reference consumes it at frame start)
     size_t e = cctx_bind(c); if (isErr(e)) return e;
+    c->lastRegionList = nullptr;
     CallParams cp = sticky_params(c);
     auto plain = [&]() { return deviceCall ? ZSTDMI_compressDevice_impl(c, dst, dstCapacity, src, srcSize) : compress_any(c, cp, dst, dstCapacity, src, srcSize); };
     if (pfxSize < 8) return plain();
@@ -1103,13 +1120,14 @@ static size_t compress_multi(ZSTD_CCtx* c, const CallParams& cp, void* dst, size
     { const size_t e = check_call_params(cp); if (isErr(e)) return e; }
     { const size_t e = check_ldm_dict(c, cp, srcSize); if (isErr(e)) return e; }
     const size_t W = c->workers.size();
+    for (ZSTD_CCtx* w : c->workers) w->lastRegionList = nullptr;
     bool ok = true;
     // the workers run with the parent's settings and dictionary
     if (cp.useDict) { const size_t e = cctx_sync_dictionary(c); if (isErr(e)) return e; }
     for (ZSTD_CCtx* w : c->workers) {
         w->historyBytes = c->historyBytes; w->frameBytes = c->frameBytes; w->parser = c->parser; w->passChunks = c->passChunks; w->timer.enabled = c->timer.enabled;
         w->dictEntropy = c->dictEntropy;        // (before the dictionary: a worker builds the tables when it uploads its copy)
-        w->dictIndex = c->dictIndex; w->dictIndexStrategy = c->dictIndexStrategy;       // (and the index, as far up the strategies as the parent's)
+        w->dictIndex = c->dictIndex; w->dictIndexStrategy = c->dictIndexStrategy; w->dictIndexChain = c->dictIndexChain;       // (and the index, as far up the strategies as the parent's)
         if (w->dictGen != c->dictGen) {
             w->dictHost = c->dictHost; w->dictFull = c->dictFull; w->dictWide = c->dictWide; w->dictFormatted = c->dictFormatted; w->info = c->info; w->dictDirty = true; w->dictGen = c->dictGen;
         }
@@ -1441,6 +1459,29 @@ size_t ZSTDMI_CCtx_setDictIndexStrategy(ZSTD_CCtx* c, unsigned maxStrategy)
     c->dictIndexStrategy = (int)maxStrategy;
     return 0;
 }
+// (no device is touched: with the index on, a loaded dictionary is marked for another upload, which builds — or, where
+//  ZSTDMI_CCtx_setDictIndexStrategy does not ask for them either, no longer builds — the two tables the chain finder's search probes)
+size_t ZSTDMI_CCtx_setDictIndexChain(ZSTD_CCtx* c, unsigned mode)
+{
+    if (!c) return ZERR(kErrGeneric);
+    if (mode > 1) return ZERR(kErrParameterOutOfBound);
+    if (c->dictIndexChain != (int)mode && c->dictIndex && (c->dictFormatted || !c->dictWide.empty())) { c->dictDirty = true; c->dictGen++; }
+    c->dictIndexChain = (int)mode;
+    return 0;
+}
+// chunks the last pass of the last compress call handed to lz_region_kernel: its work list's count, read back here
+long long ZSTDMI_debugLastRegionChunks(const ZSTD_CCtx* c)
+{
+    if (!c) return -1;
+    const ZSTD_CCtx* const w = c->workers.size() > 1 ? c->workers.back() : c;
+    if (!w->lastRegionList || !w->deviceOk) return 0;
+    int before = 0;
+    if (hipGetDevice(&before) != hipSuccess || hipSetDevice(w->device) != hipSuccess) { (void)hipGetLastError(); return 0; }
+    u32 count = 0;
+    if (hipStreamSynchronize(w->stream) != hipSuccess || hipMemcpy(&count, w->lastRegionList, sizeof count, hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); count = 0; }
+    (void)hipSetDevice(before);         // (a hook leaves the caller's current device where it was)
+    return (long long)count;
+}
 long long ZSTDMI_debugDictIndexed(const ZSTD_CCtx* c) { return c ? (long long)dict_index_len(c) : -1; }
 size_t ZSTDMI_CCtx_setParser(ZSTD_CCtx* c, unsigned mode) { if (!c || mode > 1) return ZERR(kErrParameterOutOfBound); c->parser = mode; return 0; }
 size_t ZSTDMI_CCtx_setProfiling(ZSTD_CCtx* c, int en) { if (!c) return ZERR(kErrGeneric); c->timer.enabled = en != 0; return 0; }
@@ -1561,6 +1602,7 @@ static size_t compress_entries(ZSTD_CCtx* c, const CallParams& cp, const u8* con
 {
     hipStream_t s = c->stream;
     alone = 0;
+    c->lastRegionList = nullptr;        // (entries that go alone pass through compress_range, which notes its own)
     const DictCTables* const dct = call_dict_ctables(c, cp);
     const u32 passLimit = batch_pass_limit(c);
     struct Group { Framing fr; std::vector<size_t> members; };
@@ -1632,7 +1674,7 @@ static size_t compress_entries(ZSTD_CCtx* c, const CallParams& cp, const u8* con
                 }
             }
             hFirst[nEnt] = ck;
-            if (!cctx_workspace(c, nCh) || (regionParse && !cctx_cand_workspace(c, nCh, hcChains)) || !c->batchStage.ensure((u64)nCh * cb + 64) ||
+            if (!cctx_workspace(c, nCh) || (regionParse && !cctx_cand_workspace(c, nCh, hcChains)) || (regionParse && g.fr.dictIndex && !cctx_dist_workspace(c, nCh)) || !c->batchStage.ensure((u64)nCh * cb + 64) ||
                 !c->batchTab.ensure(tabBytes + (size_t)nEnt * 8)) return ZERR(kErrMemoryAllocation);
             u8* const dTab = (u8*)c->batchTab.p;
             const u32* const dLen = (const u32*)(dTab + atLen);
@@ -1686,6 +1728,7 @@ namespace zmi {
 size_t compress_samples(ZSTD_CCtx* c, const u8* src, const u64* offs, const size_t* sizes, size_t n, size_t* outSizes, u32* stats)
 {
     size_t e = cctx_bind(c); if (isErr(e)) return e;
+    c->lastRegionList = nullptr;
     CallParams cp = sticky_params(c); cp.seek = false;
     e = cctx_sync_dictionary(c); if (isErr(e)) return e;
     hipStream_t s = c->stream;
@@ -1714,6 +1757,7 @@ size_t compress_samples(ZSTD_CCtx* c, const u8* src, const u64* offs, const size
 static size_t compress_batch_impl(ZSTD_CCtx* c, const void* const* srcs, const size_t* srcSizes, size_t n, void* const* dsts, const size_t* dstCapacities, size_t* dstSizes)
 {
     if (!c) return ZERR(kErrGeneric);
+    c->lastRegionList = nullptr;
     if (n == 0) { c->lastBatchAlone = 0; return 0; }
     if (!srcs || !srcSizes || !dsts || !dstCapacities || !dstSizes) return ZERR(kErrGeneric);
     size_t e = cctx_bind(c); if (isErr(e)) return e;
@@ -1772,6 +1816,7 @@ static size_t compress_pack_impl(ZSTD_CCtx* c, u8* d_dst, size_t dstCapacity, co
 {
     if (!c || (n && (!srcs || !sizes))) return ZERR(kErrGeneric);
     size_t e = cctx_bind(c); if (isErr(e)) return e;
+    c->lastRegionList = nullptr;
     if (c->workers.size() > 1 || c->pfx) return ZERR(kErrParameterUnsupported);
     c->lastPackAlone = 0; c->lastPackFrames = 0;
     CallParams cp = sticky_params(c); cp.seek = false;      // (the context's own switch is not consulted)
