@@ -27,6 +27,8 @@ extern "C" {
 
 typedef struct ZSTD_CCtx_s ZSTD_CCtx;
 typedef struct ZSTD_DCtx_s ZSTD_DCtx;
+typedef struct ZSTD_CDict_s ZSTD_CDict;
+typedef struct ZSTD_DDict_s ZSTD_DDict;
 
 /* U/ZSTD_cParameter.cs / U/ZSTD_dParameter.cs values that the safe API uses */
 enum {
@@ -124,6 +126,78 @@ unsigned long long ZSTD_getFrameContentSize(const void* src, size_t srcSize);
 size_t     ZSTD_findFrameCompressedSize(const void* src, size_t srcSize);
 /* S/Decompressor.cs:86 -> U/ZstdDecompress.cs:1365-1368 */
 size_t     ZSTD_decompressDCtx(ZSTD_DCtx* dctx, void* dst, size_t dstCapacity, const void* src, size_t srcSize);
+
+/* ---- digested dictionaries: U/ZstdCompress.cs:1700, 5984-6205; U/ZstdDdict.cs:178-279; U/ZstdDecompress.cs:2014-2067, 2300 ----
+ * A dictionary digested ONCE and shared: what ZSTD_CCtx_loadDictionary / ZSTD_DCtx_loadDictionary make per context and per load — the
+ * upload, the validation of a formatted dictionary, its tables — a ZSTD_CDict / ZSTD_DDict makes at its creation, on a stream of its
+ * own, and never writes again.  Any number of contexts and threads may then reference one object at the same time without a lock;
+ * referencing it and switching between several touches no device and uploads nothing.  Lifetime is the caller's, as in libzstd: an
+ * object must outlive every context that references it, and ZSTD_freeCCtx / ZSTD_freeDCtx never touch it.
+ * Not provided: ZSTD_createCDict_byReference / ZSTD_createDDict_byReference (the bytes are always copied), the *_advanced
+ * constructors, ZSTD_d_refMultipleDDicts and ZSTD_estimateCDictSize.
+ *
+ * ZSTD_createCDict: `dict` is host or device memory; the bytes are copied.  compressionLevel 0 means 3 (U/ZstdCompress.cs:5991).  It is
+ * created on the device a fresh context binds (ordinal 0; ZSTDMI_createCDictOnDevice for another) and holds there the staged tail, the
+ * content with 64 readable bytes behind it, the fast finder's index and the dual finder's two tables over it (what every combination of
+ * ZSTDMI_CCtx_setDictIndex / setDictIndexStrategy / setDictIndexChain asks for) and, for a formatted dictionary, DictInfo and the
+ * compression tables of ZSTDMI_CCtx_setDictEntropy; it keeps its host bytes.  NULL: without a device, on allocation failure, and for a
+ * formatted dictionary whose header is refused (what ZSTD_CCtx_loadDictionary answers with dictionary_corrupted).  Under 8 bytes
+ * (NULL/0 included): a CDict that is no dictionary, as in ZSTD_CCtx_loadDictionary. */
+ZSTD_CDict* ZSTD_createCDict(const void* dict, size_t dictSize, int compressionLevel);
+ZSTD_CDict* ZSTDMI_createCDictOnDevice(const void* dict, size_t dictSize, int compressionLevel, int device);
+size_t      ZSTD_freeCDict(ZSTD_CDict* cdict);                               /* NULL is accepted; returns 0 */
+size_t      ZSTD_sizeof_CDict(const ZSTD_CDict* cdict);                      /* host + device bytes held; NULL: 0 */
+unsigned    ZSTD_getDictID_fromCDict(const ZSTD_CDict* cdict);               /* 0 for raw content and for NULL */
+/* Sticky; the CDict is referenced, not copied; the call touches no device.  It cancels a loaded dictionary and a pending
+ * ZSTD_CCtx_refPrefix, and is cancelled by ZSTD_CCtx_loadDictionary (NULL included) and by ZSTD_CCtx_refPrefix; cdict = NULL returns
+ * to no dictionary; a NULL context: GENERIC; in the middle of a stream session: stage_wrong, as ZSTD_CCtx_loadDictionary.
+ * While it is in force the CDict's level stands in for ZSTD_c_compressionLevel in every call that uses the dictionary
+ * (U/ZstdCompress.cs:6968; ZSTD_CCtx_getParameter still reports what was set, and it counts again once the reference is gone); every
+ * other sticky parameter and every ZSTDMI_CCtx_set* switch applies as with a loaded dictionary, and ZSTD_compressCCtx ignores the
+ * reference as it ignores a loaded dictionary.  THE BYTES: every entry point writes exactly what the same context writes after
+ * ZSTD_c_compressionLevel = the CDict's level and ZSTD_CCtx_loadDictionary(the same bytes); what is refused with a loaded dictionary
+ * (long-distance matching above one block, ZSTDMI_CCtx_setSingleFrame above 64 KiB) stays refused.
+ * Where the device copies cannot be shared — a context bound to another device than the CDict's, a context with several device
+ * workers — the context makes a private upload from the CDict's host bytes, exactly as after ZSTD_CCtx_loadDictionary: same output,
+ * never an error. */
+size_t      ZSTD_CCtx_refCDict(ZSTD_CCtx* cctx, const ZSTD_CDict* cdict);
+/* U/ZstdCompress.cs:6205: ONE call with the CDict's level and default frame parameters (content size on, checksum off, dictID on); the
+ * context's four dictionary switches (ZSTDMI_CCtx_setDictEntropy / setDictIndex / setDictIndexStrategy / setDictIndexChain) apply.  The
+ * context's sticky parameters, its dictionary or reference and a pending prefix are left as found.  Host or device buffers, as for
+ * ZSTD_compress2.  NULL context or NULL cdict: GENERIC. */
+size_t      ZSTD_compress_usingCDict(ZSTD_CCtx* cctx, void* dst, size_t dstCapacity, const void* src, size_t srcSize, const ZSTD_CDict* cdict);
+/* ZSTD_createDDict: as ZSTD_createCDict (host or device bytes, copied; device 0 or ZSTDMI_createDDictOnDevice; NULL without a device, on
+ * allocation failure and for a formatted dictionary that ZSTD_DCtx_loadDictionary refuses with dictionary_corrupted).  It holds the
+ * bytes on the device, DictInfo and, for a formatted dictionary, its literal-length, offset and match-length DECODING tables ready-made
+ * in the format the sequence decoder holds per block on chip: a context that references the DDict copies them for every block that
+ * repeats the dictionary's tables instead of building them again from their descriptions. */
+ZSTD_DDict* ZSTD_createDDict(const void* dict, size_t dictSize);
+ZSTD_DDict* ZSTDMI_createDDictOnDevice(const void* dict, size_t dictSize, int device);
+size_t      ZSTD_freeDDict(ZSTD_DDict* ddict);                               /* NULL is accepted; returns 0 */
+size_t      ZSTD_sizeof_DDict(const ZSTD_DDict* ddict);                      /* host + device bytes held; NULL: 0 */
+unsigned    ZSTD_getDictID_fromDDict(const ZSTD_DDict* ddict);               /* 0 for raw content and for NULL */
+/* These relate to ZSTD_DCtx_loadDictionary and ZSTD_DCtx_refPrefix as ZSTD_CCtx_refCDict / ZSTD_compress_usingCDict relate to their
+ * counterparts: sticky, referenced, no device touched; cancels and is cancelled by the other two; ddict = NULL: no dictionary; NULL
+ * context: GENERIC.  Every decode entry point applies a referenced DDict exactly where it applies a loaded dictionary
+ * (ZSTD_decompressDCtx, ZSTDMI_decompressDevice, ZSTDMI_decompressBatch, ZSTDMI_decompressRange(s), ZSTD_decompressStream with and
+ * without ZSTDMI_DCtx_setStreamSegment): the same bytes and the same error codes, dictionary_wrong for a foreign dictID included.  A
+ * context on another device or with several device workers makes a private upload of the DDict's bytes (and builds tables per block).
+ * ZSTD_decompress_usingDDict (U/ZstdDecompress.cs:2300) is ONE ZSTD_decompressDCtx with that dictionary; the context's own dictionary
+ * or reference and a pending prefix are left as found. */
+size_t      ZSTD_DCtx_refDDict(ZSTD_DCtx* dctx, const ZSTD_DDict* ddict);
+size_t      ZSTD_decompress_usingDDict(ZSTD_DCtx* dctx, void* dst, size_t dstCapacity, const void* src, size_t srcSize, const ZSTD_DDict* ddict);
+/* U/ZstdDecompress.cs:2014-2060.  Host memory in, no device touched.  The dictID a formatted dictionary states (its bytes 4..7), 0 for raw
+ * content, NULL and fewer than 8 bytes; the dictID a zstd frame's header names, 0 for a frame without one, a skippable frame, a wrong
+ * magic and a header that is not all there. */
+unsigned    ZSTD_getDictID_fromDict(const void* dict, size_t dictSize);
+unsigned    ZSTD_getDictID_fromFrame(const void* src, size_t srcSize);
+/* diagnostics: dictionary uploads this context itself has made since its creation (its device workers' and the private uploads of a
+ * CDict / DDict it could not share included: 0 on a context that only ever referenced shareable ones); -1 without a context */
+long long   ZSTDMI_debugDictUploads(const ZSTD_CCtx* cctx);
+long long   ZSTDMI_debugDictUploadsD(const ZSTD_DCtx* dctx);
+/* diagnostic: compressed blocks of the last decode call that took at least one sequence table from a DDict's ready-made set (0 through
+ * ZSTD_DCtx_loadDictionary, with a raw-content DDict and where the DDict is not shared); -1 without a context */
+long long   ZSTDMI_debugLastDictTableBlocks(const ZSTD_DCtx* dctx);
 
 /* ---- errors: S/ThrowHelper.cs:12-13 -> U/ErrorPrivate.cs:10-24, 35-120 ---- */
 unsigned    ZSTD_isError(size_t code);

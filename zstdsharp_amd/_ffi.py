@@ -74,6 +74,25 @@ SIGNATURES = {
                                                            ctypes.POINTER(ZDICT_fastCover_params_t)]),
     "ZDICT_finalizeDictionary": (c_size_t, [c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, ctypes.POINTER(c_size_t), c_uint,
                                             ZDICT_params_t]),
+    "ZSTD_createCDict": (c_void_p, [c_void_p, c_size_t, c_int]),
+    "ZSTDMI_createCDictOnDevice": (c_void_p, [c_void_p, c_size_t, c_int, c_int]),
+    "ZSTD_freeCDict": (c_size_t, [c_void_p]),
+    "ZSTD_sizeof_CDict": (c_size_t, [c_void_p]),
+    "ZSTD_getDictID_fromCDict": (c_uint, [c_void_p]),
+    "ZSTD_CCtx_refCDict": (c_size_t, [c_void_p, c_void_p]),
+    "ZSTD_compress_usingCDict": (c_size_t, [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]),
+    "ZSTD_createDDict": (c_void_p, [c_void_p, c_size_t]),
+    "ZSTDMI_createDDictOnDevice": (c_void_p, [c_void_p, c_size_t, c_int]),
+    "ZSTD_freeDDict": (c_size_t, [c_void_p]),
+    "ZSTD_sizeof_DDict": (c_size_t, [c_void_p]),
+    "ZSTD_getDictID_fromDDict": (c_uint, [c_void_p]),
+    "ZSTD_DCtx_refDDict": (c_size_t, [c_void_p, c_void_p]),
+    "ZSTD_decompress_usingDDict": (c_size_t, [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]),
+    "ZSTD_getDictID_fromDict": (c_uint, [c_void_p, c_size_t]),
+    "ZSTD_getDictID_fromFrame": (c_uint, [c_void_p, c_size_t]),
+    "ZSTDMI_debugDictUploads": (ctypes.c_longlong, [c_void_p]),
+    "ZSTDMI_debugDictUploadsD": (ctypes.c_longlong, [c_void_p]),
+    "ZSTDMI_debugLastDictTableBlocks": (ctypes.c_longlong, [c_void_p]),
     "ZSTDMI_deviceCount": (c_int, []),
     "ZSTDMI_CCtx_setDevice": (c_size_t, [c_void_p, c_int]),
     "ZSTDMI_DCtx_setDevice": (c_size_t, [c_void_p, c_int]),

@@ -76,6 +76,7 @@ class Compressor(_PrefixHolder):
         self._dict_index_chain = False
         self._single_frame = False
         self._sliding_ldm = False
+        self._cdict = None              # the CDict RefCDict holds
         self.Level = level if level else self.DefaultCompressionLevel
 
     # ---- static members (S/Compressor.cs:8-10) ----
@@ -114,7 +115,30 @@ class Compressor(_PrefixHolder):
         self._ensure_not_disposed()
         addr, n, keep = _as_buffer(dict_bytes if dict_bytes is not None else b"")
         self._release_prefix()          # (ZSTD_CCtx_loadDictionary cancels a pending prefix)
+        self._cdict = None              # (and a referenced CDict)
         ensure_zstd_success(self._lib, self._lib.ZSTD_CCtx_loadDictionary(self.cctx, addr, n))
+
+    def RefCDict(self, cdict):
+        """ZSTD_CCtx_refCDict: compress against a digested dictionary (dictionaries.CDict) from now on, at ITS level; None = no
+        dictionary.  Nothing is uploaded: the CDict is shared.  Cancels a loaded dictionary and a pending prefix.  The object is kept
+        referenced here so that it cannot be collected while the context uses it."""
+        self._ensure_not_disposed()
+        if cdict is not None:
+            cdict._ensure_not_disposed()
+        self._release_prefix()
+        ensure_zstd_success(self._lib, self._lib.ZSTD_CCtx_refCDict(self.cctx, cdict.handle if cdict is not None else None))
+        self._cdict = cdict
+
+    def WrapUsingCDict(self, src, cdict):
+        """ZSTD_compress_usingCDict: src -> bytes, ONE call with the CDict's level and default frame parameters; this object's
+        parameters, dictionary and reference are left as they are."""
+        self._ensure_not_disposed()
+        cdict._ensure_not_disposed()
+        saddr, sn, skeep = _as_buffer(src)
+        cap = self.GetCompressBound(sn)
+        out = ctypes.create_string_buffer(max(cap, 1))
+        n = ensure_zstd_success(self._lib, self._lib.ZSTD_compress_usingCDict(self.cctx, out, cap, saddr, sn, cdict.handle))
+        return out.raw[:n]
 
     def RefPrefix(self, prefix):
         """ZSTD_CCtx_refPrefix: the next Wrap / TryWrap compresses its source as a delta of `prefix` (bytes-like or a contiguous CUDA
@@ -124,6 +148,7 @@ class Compressor(_PrefixHolder):
         self._ensure_not_disposed()
         addr, n, keep, device = _as_prefix(prefix)
         self._release_prefix()
+        self._cdict = None              # (ZSTD_CCtx_refPrefix cancels a referenced CDict)
         ensure_zstd_success(self._lib, self._lib.ZSTD_CCtx_refPrefix(self.cctx, addr, n))
         self._hold_prefix(keep, device)
 
@@ -245,6 +270,7 @@ class Compressor(_PrefixHolder):
         return True, ensure_zstd_success(self._lib, r)
 
     wrap, try_wrap, set_parameter, get_parameter, load_dictionary, ref_prefix = Wrap, TryWrap, SetParameter, GetParameter, LoadDictionary, RefPrefix
+    ref_cdict, wrap_using_cdict = RefCDict, WrapUsingCDict
 
     # ---- lifetime (S/Compressor.cs:59-70, 124-147) ----
     def Dispose(self):

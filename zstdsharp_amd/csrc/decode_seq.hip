@@ -233,9 +233,14 @@ __device__ __forceinline__ void seq_fields_batch(const SeqLds& L, u32 buf, u32 s
     S.s0 = s0; S.s1 = s1; S.s2 = s2; S.outBase += totalOut; S.litUsed += totalLit;
 }
 
-__global__ __launch_bounds__(256) void seq_decode_kernel(const u8* __restrict__ src, const FrameDesc* __restrict__ frames, BlockDesc* __restrict__ blocks,
-                                                         u32 nBlocks, SeqRec* __restrict__ recs, u32* __restrict__ status,
-                                                         const u8* __restrict__ dictFull, const DictInfo* __restrict__ di)
+// The kernel's body, in two instances.  kReady = false is the kernel as it always was.  kReady = true (launched only for a context that
+// references a DDict over a formatted dictionary) takes a table a block repeats from the dictionary out of the DDict's ready-made image
+// (dictTabs, launch_dict_seq_tables) — a coalesced copy of 1 << log words that every workgroup reads from L2 — instead of parsing the
+// description and building the table again; a description that does not parse never becomes a DDict, so the copy has no error branch.
+template <bool kReady>
+__device__ __forceinline__ void seq_decode_body(const u8* __restrict__ src, const FrameDesc* __restrict__ frames, BlockDesc* __restrict__ blocks,
+                                                u32 nBlocks, SeqRec* __restrict__ recs, u32* __restrict__ status,
+                                                const u8* __restrict__ dictFull, const DictInfo* __restrict__ di, const u32* __restrict__ dictTabs)
 {
     __shared__ SeqLds L;
     const u32 lane = lane_id(), wave = uniform(wave_id()), b0 = blockIdx.x * kPack;
@@ -251,21 +256,31 @@ __global__ __launch_bounds__(256) void seq_decode_kernel(const u8* __restrict__ 
             const BlockDesc& B = blocks[bi];
             if (uniform((u32)B.type) == 2 && uniform(B.nbSeq) != 0 && !uniform(B.err)) {
                 const u32 s = uniform(B.tblSrc[t]);
-                const u8* d; u32 avail, mode;
-                if (s == kDictBlock) {                              // dctx->fseEntropy from the dictionary (U/ZstdDecompress.cs:1956-1990)
-                    const u32 o0 = uniform(t == 0 ? di->llOff : t == 1 ? di->ofOff : di->mlOff), o1 = uniform(t == 0 ? di->repOff : t == 1 ? di->mlOff : di->llOff);
-                    d = dictFull + o0; avail = o1 - o0; mode = 2;
+                bool ready = false;
+                if constexpr (kReady) ready = s == kDictBlock;
+                if (ready) {                                        // the table is there: 1 << log packed entries (log >= 5), 16 bytes a lane and round
+                    const u32 at = t == 0 ? kTabLL : t == 1 ? kTabOF : kTabML;
+                    res = uniform(dictTabs[kDictTabLogs + t]);
+                    const uint4* __restrict__ const from = reinterpret_cast<const uint4*>(dictTabs + at);
+                    u32* const to = L.tab[sl] + at;
+                    for (u32 i = lane; i < (1u << res) / 4; i += 64) { const uint4 v = from[i]; to[4 * i] = v.x; to[4 * i + 1] = v.y; to[4 * i + 2] = v.z; to[4 * i + 3] = v.w; }
                 } else {
-                    const BlockDesc& S = blocks[s];
-                    mode = (uniform(S.modes) >> (6 - 2 * t)) & 3;
-                    const u32 o = uniform(S.tblOff[t]);
-                    d = src + S.srcOff + o; avail = uniform(S.bsz) - o;
+                    const u8* d; u32 avail, mode;
+                    if (s == kDictBlock) {                              // dctx->fseEntropy from the dictionary (U/ZstdDecompress.cs:1956-1990)
+                        const u32 o0 = uniform(t == 0 ? di->llOff : t == 1 ? di->ofOff : di->mlOff), o1 = uniform(t == 0 ? di->repOff : t == 1 ? di->mlOff : di->llOff);
+                        d = dictFull + o0; avail = o1 - o0; mode = 2;
+                    } else {
+                        const BlockDesc& S = blocks[s];
+                        mode = (uniform(S.modes) >> (6 - 2 * t)) & 3;
+                        const u32 o = uniform(S.tblOff[t]);
+                        d = src + S.srcOff + o; avail = uniform(S.bsz) - o;
+                    }
+                    u32 lg;
+                    if (t == 0)      lg = set_seq_table(L.build.norm[wave], L.build.symbolNext[wave], L.tab[sl] + kTabLL, mode, 35, 9, d, avail, 0, dLL_defaultNorm, 6, 35, lane);
+                    else if (t == 1) lg = set_seq_table(L.build.norm[wave], L.build.symbolNext[wave], L.tab[sl] + kTabOF, mode, 31, 8, d, avail, 1, dOF_defaultNorm, 5, 28, lane);
+                    else             lg = set_seq_table(L.build.norm[wave], L.build.symbolNext[wave], L.tab[sl] + kTabML, mode, 52, 9, d, avail, 2, dML_defaultNorm, 6, 52, lane);
+                    res = lg == 0xFFFFFFFFu ? ((s == kDictBlock ? (u32)kErrDictionaryCorrupted : (u32)kErrCorruption) << 8) | 0xFFu : lg;
                 }
-                u32 lg;
-                if (t == 0)      lg = set_seq_table(L.build.norm[wave], L.build.symbolNext[wave], L.tab[sl] + kTabLL, mode, 35, 9, d, avail, 0, dLL_defaultNorm, 6, 35, lane);
-                else if (t == 1) lg = set_seq_table(L.build.norm[wave], L.build.symbolNext[wave], L.tab[sl] + kTabOF, mode, 31, 8, d, avail, 1, dOF_defaultNorm, 5, 28, lane);
-                else             lg = set_seq_table(L.build.norm[wave], L.build.symbolNext[wave], L.tab[sl] + kTabML, mode, 52, 9, d, avail, 2, dML_defaultNorm, 6, 52, lane);
-                res = lg == 0xFFFFFFFFu ? ((s == kDictBlock ? (u32)kErrDictionaryCorrupted : (u32)kErrCorruption) << 8) | 0xFFu : lg;
             }
         }
         if (lane == 0) L.tblErr[sl][t] = res;
@@ -281,6 +296,14 @@ __global__ __launch_bounds__(256) void seq_decode_kernel(const u8* __restrict__ 
         // the reference stops at the first corrupt table in LL, OF, ML order
         if ((r0 & 0xFF) == 0xFF) mErr = r0 >> 8; else if ((r1 & 0xFF) == 0xFF) mErr = r1 >> 8; else if ((r2 & 0xFF) == 0xFF) mErr = r2 >> 8;
         else { mNbSeq = MB.nbSeq; myLogs = r0 | (r1 << 8) | (r2 << 16); }
+    }
+    if constexpr (kReady) {     // (diagnostic: blocks that took at least one table from the ready-made set)
+        if (wave == 0) {
+            const bool took = lane < kPack && b0 + lane < nBlocks && MB.type == 2 && MB.nbSeq != 0 && !MB.err &&
+                              (MB.tblSrc[0] == kDictBlock || MB.tblSrc[1] == kDictBlock || MB.tblSrc[2] == kDictBlock);
+            const u64 m = ballot(took);
+            if (m && lane == 0) atomicAdd(status + kStDictTabBlocks, popc64(m));
+        }
     }
     const u32 mBsz = MB.bsz, mBitsOff = MB.bitsOff, mLitSize = MB.litSize;
     const u8* const mSp = src + MB.srcOff + mBitsOff;
@@ -412,10 +435,52 @@ __global__ __launch_bounds__(256) void seq_decode_kernel(const u8* __restrict__ 
 #endif
 }
 
-void launch_seq_decode(const u8* src, const FrameDesc* frames, BlockDesc* blocks, u32 nBlocks, SeqRec* recs, u32* status,
-                       const u8* dictFull, const DictInfo* di, hipStream_t stream)
+__global__ __launch_bounds__(256) void seq_decode_kernel(const u8* __restrict__ src, const FrameDesc* __restrict__ frames, BlockDesc* __restrict__ blocks,
+                                                         u32 nBlocks, SeqRec* __restrict__ recs, u32* __restrict__ status,
+                                                         const u8* __restrict__ dictFull, const DictInfo* __restrict__ di)
 {
-    hipLaunchKernelGGL(seq_decode_kernel, dim3((nBlocks + kPack - 1) / kPack), dim3(256), 0, stream, src, frames, blocks, nBlocks, recs, status, dictFull, di);
+    seq_decode_body<false>(src, frames, blocks, nBlocks, recs, status, dictFull, di, nullptr);
+}
+__global__ __launch_bounds__(256) void seq_decode_ready_kernel(const u8* __restrict__ src, const FrameDesc* __restrict__ frames, BlockDesc* __restrict__ blocks,
+                                                               u32 nBlocks, SeqRec* __restrict__ recs, u32* __restrict__ status,
+                                                               const u8* __restrict__ dictFull, const DictInfo* __restrict__ di, const u32* __restrict__ dictTabs)
+{
+    seq_decode_body<true>(src, frames, blocks, nBlocks, recs, status, dictFull, di, dictTabs);
+}
+
+void launch_seq_decode(const u8* src, const FrameDesc* frames, BlockDesc* blocks, u32 nBlocks, SeqRec* recs, u32* status,
+                       const u8* dictFull, const DictInfo* di, const u32* dictTabs, hipStream_t stream)
+{
+    const dim3 grid((nBlocks + kPack - 1) / kPack);
+    if (dictTabs) hipLaunchKernelGGL(seq_decode_ready_kernel, grid, dim3(256), 0, stream, src, frames, blocks, nBlocks, recs, status, dictFull, di, dictTabs);
+    else          hipLaunchKernelGGL(seq_decode_kernel, grid, dim3(256), 0, stream, src, frames, blocks, nBlocks, recs, status, dictFull, di);
+}
+
+// The dictionary's LL, OF and ML decoding tables, once (ZSTD_createDDict): wave t runs set_seq_table over the dictionary's description of
+// table t exactly as seq_decode_kernel's phase A does per block, into the same packed entries at the same places, and the image goes out
+// to `tabs` with the three logs behind it (all ones for a description that does not parse: the host then refuses the dictionary).
+__global__ __launch_bounds__(192) void dict_seq_tables_kernel(const u8* __restrict__ dictFull, const DictInfo* __restrict__ di, u32* __restrict__ tabs)
+{
+    __shared__ u32 tab[kTabWords];
+    __shared__ s16 norm[3][64];
+    __shared__ u16 symbolNext[3][64];
+    const u32 lane = lane_id(), t = uniform(wave_id());         // t: 0 LL, 1 OF, 2 ML
+    for (u32 i = threadIdx.x; i < kTabWords; i += 192) tab[i] = 0;
+    __syncthreads();
+    const u32 o0 = uniform(t == 0 ? di->llOff : t == 1 ? di->ofOff : di->mlOff), o1 = uniform(t == 0 ? di->repOff : t == 1 ? di->mlOff : di->llOff);
+    const u8* const d = dictFull + o0; const u32 avail = o1 - o0;
+    u32 lg;
+    if (t == 0)      lg = set_seq_table(norm[t], symbolNext[t], tab + kTabLL, 2, 35, 9, d, avail, 0, dLL_defaultNorm, 6, 35, lane);
+    else if (t == 1) lg = set_seq_table(norm[t], symbolNext[t], tab + kTabOF, 2, 31, 8, d, avail, 1, dOF_defaultNorm, 5, 28, lane);
+    else             lg = set_seq_table(norm[t], symbolNext[t], tab + kTabML, 2, 52, 9, d, avail, 2, dML_defaultNorm, 6, 52, lane);
+    if (lane == 0) tabs[kDictTabLogs + t] = lg;
+    if (t == 0 && lane == 0) tabs[kDictTabLogs + 3] = 0;
+    __syncthreads();
+    for (u32 i = threadIdx.x; i < kTabWords; i += 192) tabs[i] = tab[i];
+}
+void launch_dict_seq_tables(const u8* dictFull, const DictInfo* di, u32* tabs, hipStream_t stream)
+{
+    hipLaunchKernelGGL(dict_seq_tables_kernel, dim3(1), dim3(192), 0, stream, dictFull, di, tabs);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -233,7 +233,8 @@ enum : u32 { kStFrames = 0, kStErr = 1, kStTotalLo = 2, kStTotalHi = 3, kStUsabl
              kStOriginChanged = 18,     // .. 18 + kOriginRounds: round r of the pointer jumping changed something
              kStLitLo = 54, kStLitHi = 55,              // regenerated bytes of all Huffman-coded literals sections (u64; block_link)
              kStBigBins = 56,           // 12 x u64: content bytes of the frames with sequences by size class, bin k = [2^(20+k), 2^(21+k)), below 2^30
-             kStWords = 80 };
+             kStDictTabBlocks = 80,     // blocks that copied a sequence table from a DDict's ready-made set (seq_decode_kernel's instance for it)
+             kStWords = 82 };
 constexpr u32 kOriginRounds = 36;
 
 // Stage timing (ZSTDMI_*_setProfiling): a launcher that issues several kernels marks the end of each on the context's timer, so

@@ -110,8 +110,13 @@ void launch_dict_parse(const u8* dict, u32 dictSize, DictInfo* out, hipStream_t 
 void launch_dict_ctables(const u8* dict, u32 dictSize, const DictInfo* info, DictCTables* out, hipStream_t stream);
 void launch_block_prepass(const u8* src, FrameDesc* frames, BlockDesc* blocks, u32 nFrames, u32 nBlocks, u32 haveDict, u32 earlyLiterals, u32* status, hipStream_t stream,
                           u32 phantoms = 0);     // phantoms: decode_walk.hip block_link_body
+// dictTabs (null: none): a DDict's ready-made tables, which the kernel's instance for them copies where a block repeats the dictionary's
 void launch_seq_decode(const u8* src, const FrameDesc* frames, BlockDesc* blocks, u32 nBlocks, SeqRec* recs, u32* status,
-                       const u8* dictFull, const DictInfo* di, hipStream_t stream);
+                       const u8* dictFull, const DictInfo* di, const u32* dictTabs, hipStream_t stream);
+// A formatted dictionary's three sequence decoding tables, built once (ZSTD_createDDict): words [0, 1280) are the image seq_decode_kernel
+// holds per block in LDS (LL at 0, ML at 512, OF at 1024), words kDictTabLogs + 0 / 1 / 2 the LL / OF / ML table logs (all ones: corrupt)
+constexpr u32 kDictTabLogs = 1280, kDictTabWords = 1284;
+void launch_dict_seq_tables(const u8* dictFull, const DictInfo* di, u32* tabs, hipStream_t stream);
 void launch_block_offsets(FrameDesc* frames, BlockDesc* blocks, u32 nFrames, const DictInfo* di, u32 rescan, u64 dstCapacity, u32* status, hipStream_t stream);
 void launch_decode_literals(const u8* src, u8* out, u8* scratch, const FrameDesc* frames, const BlockDesc* blocks, u32 nBlocks, u32* status,
                             u8* slowFlags, u32 mode, const u8* dictFull, const DictInfo* di, hipStream_t stream, StageHook hook);

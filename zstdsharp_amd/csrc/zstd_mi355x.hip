@@ -9,6 +9,23 @@
 #include <unordered_map>
 
 // ======================================================================================================
+// A dictionary as the compressor holds it, on the host and on one device: the fields a context fills from ZSTD_CCtx_loadDictionary and
+// cctx_sync_dictionary (described at ZSTD_CCtx_s::own below), or a ZSTD_CDict fills once, whole, at its creation.
+struct DictDigest {
+    std::vector<u8> dictHost, dictFull, dictWide;
+    DevBuf dict, dictFullDev, dictInfoDev, dictCTabDev, dictWideDev, dictIdxDev;
+    const u8* dictIdxEnd = nullptr; u32 dictIdxLen = 0, dictIdxLog = 0; bool dictIdxDual = false;
+    DictInfo info = {};
+    bool dictFormatted = false;
+    void release() { dict.release(); dictFullDev.release(); dictInfoDev.release(); dictCTabDev.release(); dictWideDev.release(); dictIdxDev.release(); }
+    size_t bytes() const { return dictHost.capacity() + dictFull.capacity() + dictWide.capacity() + dict.cap + dictFullDev.cap + dictInfoDev.cap + dictCTabDev.cap + dictWideDev.cap + dictIdxDev.cap; }
+};
+// ZSTD_createCDict: a digest built whole on `device` at creation — the staged tail, the content with its index (all three tables), and
+// for a formatted dictionary DictInfo and the DictCTables — and never written again: any number of contexts and threads read it without
+// a lock.  Its host fields are what it keeps of the caller's bytes: a context that cannot share the device copies makes a private
+// upload from them (cctx_adopt_cdict).
+struct ZSTD_CDict_s { DictDigest dg; int level = 3; int device = 0; };
+
 struct ZSTD_CCtx_s {
     int level = 3;              // ZSTD_CLEVEL_DEFAULT
     int checksumFlag = 0, contentSizeFlag = 1, dictIDFlag = 1;
@@ -36,7 +53,10 @@ struct ZSTD_CCtx_s {
     // tables are not used (every block carries its own), which any decoder holding the dictionary accepts — unless
     // ZSTDMI_CCtx_setDictEntropy turned them on: then dictCTabDev holds them as compression tables (dict_ctables_kernel, built with
     // the dictionary's upload) and the first block of every frame is coded with them as its previous entropy state.
-    std::vector<u8> dictHost, dictFull; DevBuf dict, dictFullDev, dictInfoDev, dictCTabDev; bool dictDirty = false, dictFormatted = false;
+    // These fields are one DictDigest (above): `own` is what this context loaded and uploaded itself; while a ZSTD_CDict is referenced
+    // (cdict, ZSTD_CCtx_refCDict) every reader takes the digest in force from dict_in_force() instead — the CDict's where it can be
+    // shared, else `own` filled from the CDict's host bytes (cctx_adopt_cdict).  dictUploads: uploads of `own` (ZSTDMI_debugDictUploads)
+    DictDigest own; const ZSTD_CDict_s* cdict = nullptr; bool dictDirty = false; long long dictUploads = 0;
     int dictEntropy = 0;        // ZSTDMI_CCtx_setDictEntropy (sticky)
     // ZSTDMI_CCtx_setDictIndex (sticky): the dictionary's content — its last dict_index_max() bytes — stays whole on the device with a
     // hash index over it, built once per upload (lz_fast.hip), and the fast strategy's chunks look candidates up there instead of
@@ -49,8 +69,6 @@ struct ZSTD_CCtx_s {
     // of a context that uses it alone.  lastRegionList: the work list of the last pass's lz_region_kernel, null = none ran (debug hook)
     int dictIndex = 0, dictIndexStrategy = 1, dictIndexChain = 0;
     DevBuf dixDist; const u32* lastRegionList = nullptr;
-    std::vector<u8> dictWide; DevBuf dictWideDev, dictIdxDev; const u8* dictIdxEnd = nullptr; u32 dictIdxLen = 0, dictIdxLog = 0; bool dictIdxDual = false;
-    DictInfo info = {};
     u64 dictGen = 0;            // bumped by every ZSTD_CCtx_loadDictionary: device workers copy the dictionary when theirs is older
     // ZSTDMI_CCtx_setDevices: one worker context per listed device (its own stream and workspaces there); a call's frames are
     // dealt to them in contiguous shares (compress_multi).  Empty = the context's own device only.
@@ -84,10 +102,15 @@ struct ZSTD_CCtx_s {
 // the whole input fits behind it in one chunk (small records, the usual dictionary case).
 constexpr size_t kDictKeep = 60u << 10;
 static u32 round_tile(size_t n) { return (u32)((n + 4095) & ~(size_t)4095); }
+// A referenced CDict's device copies serve a context on the CDict's device that has no device workers (a worker uploads its own copy,
+// as of a loaded dictionary); everywhere else the context holds a private upload of the same bytes in `own`.
+static bool cdict_shared(const ZSTD_CCtx* c) { return c->cdict && c->cdict->device == c->device && c->workers.size() <= 1; }
+// the digest every reader of dictionary state asks: the CDict's while one is shared, else the context's own
+static const DictDigest& dict_in_force(const ZSTD_CCtx* c) { return cdict_shared(c) ? c->cdict->dg : c->own; }
 // -> bytes of dictionary used as history for an input of srcSize bytes (0 = none)
 static u32 dict_prefix_len(const ZSTD_CCtx* c, size_t srcSize)
 {
-    const size_t have = c->dictHost.size();
+    const size_t have = dict_in_force(c).dictHost.size();
     if (have < 8) return 0;                                  // ZSTD_compress_insertDictionary ignores dictionaries < 8 bytes, U/ZstdCompress.cs:5469-5477
     const size_t wide = have < kDictKeep ? have : kDictKeep;
     if (srcSize <= kChunkSize - round_tile(wide)) return (u32)wide;
@@ -96,15 +119,16 @@ static u32 dict_prefix_len(const ZSTD_CCtx* c, size_t srcSize)
 
 
 
-// -> content bytes of the loaded dictionary that the index covers (0 = no index: switch off, no dictionary, or one below 8 bytes,
-// which is no dictionary at all); a formatted dictionary's content size is known once it has been validated (cctx_sync_dictionary)
-static u32 dict_index_len(const ZSTD_CCtx* c)
+// -> content bytes of a dictionary that an index covers (0: one below 8 bytes, which is no dictionary at all); a formatted
+// dictionary's content size is known once it has been validated (digest_upload)
+static u32 digest_index_len(const DictDigest& g)
 {
-    if (!c->dictIndex) return 0;
-    const size_t have = c->dictFormatted ? (c->dictFull.empty() ? 0 : c->info.contentSize) : c->dictWide.size();
+    const size_t have = g.dictFormatted ? (g.dictFull.empty() ? 0 : g.info.contentSize) : g.dictWide.size();
     if (have < 8) return 0;
     return (u32)(have < dict_index_max() ? have : dict_index_max());
 }
+// -> content bytes of the dictionary in force that the index covers (0 = no index: switch off, or no dictionary)
+static u32 dict_index_len(const ZSTD_CCtx* c) { return c->dictIndex ? digest_index_len(dict_in_force(c)) : 0u; }
 
 static size_t cctx_sync_dictionary(ZSTD_CCtx* c);
 static size_t cctx_bind(ZSTD_CCtx* c) { return ctx_bind(c); }
@@ -131,7 +155,7 @@ struct CallParams {
 };
 static CallParams sticky_params(const ZSTD_CCtx* c)
 {
-    CallParams p; p.level = c->level; p.checksumFlag = c->checksumFlag; p.contentSizeFlag = c->contentSizeFlag; p.dictIDFlag = c->dictIDFlag;
+    CallParams p; p.level = c->cdict ? c->cdict->level : c->level; p.checksumFlag = c->checksumFlag; p.contentSizeFlag = c->contentSizeFlag; p.dictIDFlag = c->dictIDFlag;
     p.strategy = c->strategy; p.targetLength = c->targetLength; p.windowLog = c->windowLog; p.searchLog = c->searchLog; p.minMatch = c->minMatch; p.chainLog = c->chainLog; p.useDict = true;
     p.seek = c->seekTable != 0;
     p.dictEntropy = c->dictEntropy != 0;
@@ -181,60 +205,70 @@ static size_t cand_plane_bytes(u32 nChunks) { return (size_t)nChunks * kChunkSiz
 static bool cctx_dist_workspace(ZSTD_CCtx* c, u32 nChunks) { return c->dixDist.ensure((size_t)(nChunks < 256 ? nChunks : 256) * kChunkSize * sizeof(u32)); }
 static bool cctx_cand_workspace(ZSTD_CCtx* c, u32 nChunks, bool chains) { return c->cand.ensure(cand_plane_bytes(nChunks) * (chains ? 2 : 1) + ((size_t)nChunks + 1) * sizeof(u32)); }
 
-// upload a newly loaded dictionary; a formatted one is first validated on the device (ZSTD_loadCEntropy's checks are those of
-// ZSTD_loadDEntropy plus the symbol-coverage rules that only matter to an encoder reusing the tables) -> dictionary_corrupted
-static size_t cctx_sync_dictionary(ZSTD_CCtx* c)
+// A digest's host bytes onto the current device, on stream s, waited for: a formatted dictionary is first validated there
+// (ZSTD_loadCEntropy's checks are those of ZSTD_loadDEntropy plus the symbol-coverage rules that only matter to an encoder reusing the
+// tables) -> dictionary_corrupted, with the digest emptied.  entropy: build its DictCTables; index: the fast finder's table over the
+// content's last dict_index_max() bytes; dual: behind it the dual finder's two.  (A context passes its switches, a CDict all three.)
+static size_t digest_upload(DictDigest& g, hipStream_t s, bool entropy, bool index, bool dual)
 {
-    if (!c->dictDirty) return 0;
-    hipStream_t s = c->stream;
-    if (c->dictFormatted) {
-        const size_t n = c->dictFull.size();
-        if (!c->dictFullDev.ensure(n + 64) || !c->dictInfoDev.ensure(sizeof(DictInfo))) return ZERR(kErrMemoryAllocation);
-        if (hipMemcpyAsync(c->dictFullDev.p, c->dictFull.data(), n, hipMemcpyHostToDevice, s) != hipSuccess) return ZERR(kErrGeneric);
-        launch_dict_parse((const u8*)c->dictFullDev.p, (u32)n, (DictInfo*)c->dictInfoDev.p, s);
-        if (isErr(dev_read(&c->info, c->dictInfoDev.p, sizeof(DictInfo), s))) return ZERR(kErrGeneric);
-        if (c->info.err) { c->dictFull.clear(); c->dictHost.clear(); c->dictFormatted = false; c->dictDirty = false; return ZERR(kErrDictionaryCorrupted); }
-        const size_t keep = c->info.contentSize < kDictKeep ? c->info.contentSize : kDictKeep;
-        c->dictHost.assign(c->dictFull.end() - (ptrdiff_t)keep, c->dictFull.end());
-        if (c->dictEntropy) {       // (the setter marks the dictionary dirty, so a switch turned on later builds them too)
-            if (!c->dictCTabDev.ensure(sizeof(DictCTables))) return ZERR(kErrMemoryAllocation);
-            launch_dict_ctables((const u8*)c->dictFullDev.p, (u32)n, (const DictInfo*)c->dictInfoDev.p, (DictCTables*)c->dictCTabDev.p, s);
+    if (g.dictFormatted) {
+        const size_t n = g.dictFull.size();
+        if (!g.dictFullDev.ensure(n + 64) || !g.dictInfoDev.ensure(sizeof(DictInfo))) return ZERR(kErrMemoryAllocation);
+        if (hipMemcpyAsync(g.dictFullDev.p, g.dictFull.data(), n, hipMemcpyHostToDevice, s) != hipSuccess) return ZERR(kErrGeneric);
+        launch_dict_parse((const u8*)g.dictFullDev.p, (u32)n, (DictInfo*)g.dictInfoDev.p, s);
+        if (isErr(dev_read(&g.info, g.dictInfoDev.p, sizeof(DictInfo), s))) return ZERR(kErrGeneric);
+        if (g.info.err) { g.dictFull.clear(); g.dictHost.clear(); g.dictFormatted = false; return ZERR(kErrDictionaryCorrupted); }
+        const size_t keep = g.info.contentSize < kDictKeep ? g.info.contentSize : kDictKeep;
+        g.dictHost.assign(g.dictFull.end() - (ptrdiff_t)keep, g.dictFull.end());
+        if (entropy) {
+            if (!g.dictCTabDev.ensure(sizeof(DictCTables))) return ZERR(kErrMemoryAllocation);
+            launch_dict_ctables((const u8*)g.dictFullDev.p, (u32)n, (const DictInfo*)g.dictInfoDev.p, (DictCTables*)g.dictCTabDev.p, s);
             if (isErr(stream_wait(s))) return ZERR(kErrGeneric);
         }
     }
-    if (!c->dictHost.empty()) {
-        if (!c->dict.ensure(c->dictHost.size() + 64)) return ZERR(kErrMemoryAllocation);
-        if (hipMemcpyAsync(c->dict.p, c->dictHost.data(), c->dictHost.size(), hipMemcpyHostToDevice, s) != hipSuccess) return ZERR(kErrGeneric);
+    if (!g.dictHost.empty()) {
+        if (!g.dict.ensure(g.dictHost.size() + 64)) return ZERR(kErrMemoryAllocation);
+        if (hipMemcpyAsync(g.dict.p, g.dictHost.data(), g.dictHost.size(), hipMemcpyHostToDevice, s) != hipSuccess) return ZERR(kErrGeneric);
         if (isErr(stream_wait(s))) return ZERR(kErrGeneric);
     }
-    c->dictIdxLen = 0;
-    if (const u32 ixLen = dict_index_len(c)) {      // (the setter marks the dictionary dirty, as ZSTDMI_CCtx_setDictEntropy does)
+    g.dictIdxLen = 0;
+    if (const u32 ixLen = index ? digest_index_len(g) : 0u) {
         // the content's end on the device, with 64 readable bytes behind it: a formatted dictionary's ends dictFullDev; a raw one goes up whole
         const u8* end = nullptr;
-        if (c->dictFormatted) end = (const u8*)c->dictFullDev.p + c->dictFull.size();
+        if (g.dictFormatted) end = (const u8*)g.dictFullDev.p + g.dictFull.size();
         else {
-            if (!c->dictWideDev.ensure((size_t)ixLen + 64)) return ZERR(kErrMemoryAllocation);
-            if (hipMemcpyAsync(c->dictWideDev.p, c->dictWide.data() + (c->dictWide.size() - ixLen), ixLen, hipMemcpyHostToDevice, s) != hipSuccess) return ZERR(kErrGeneric);
-            end = (const u8*)c->dictWideDev.p + ixLen;
+            if (!g.dictWideDev.ensure((size_t)ixLen + 64)) return ZERR(kErrMemoryAllocation);
+            if (hipMemcpyAsync(g.dictWideDev.p, g.dictWide.data() + (g.dictWide.size() - ixLen), ixLen, hipMemcpyHostToDevice, s) != hipSuccess) return ZERR(kErrGeneric);
+            end = (const u8*)g.dictWideDev.p + ixLen;
         }
         const u32 log = dict_index_log(ixLen);
-        const bool dual = c->dictIndexStrategy >= 2 || c->dictIndexChain;       // (the setters mark the dictionary dirty too)
-        if (!c->dictIdxDev.ensure((sizeof(u32) << log) * (dual ? 3 : 1))) return ZERR(kErrMemoryAllocation);
-        u32* const tables = (u32*)c->dictIdxDev.p;          // fast [| long | short], 1 << log entries each
+        if (!g.dictIdxDev.ensure((sizeof(u32) << log) * (dual ? 3 : 1))) return ZERR(kErrMemoryAllocation);
+        u32* const tables = (u32*)g.dictIdxDev.p;          // fast [| long | short], 1 << log entries each
         launch_dict_index(end - ixLen, ixLen, tables, log, s);
         if (dual) launch_dict_index_dual(end - ixLen, ixLen, tables + ((size_t)1 << log), tables + ((size_t)2 << log), log, s);
-        c->dictIdxDual = dual;
+        g.dictIdxDual = dual;
         if (isErr(stream_wait(s))) return ZERR(kErrGeneric);
-        c->dictIdxEnd = end; c->dictIdxLen = ixLen; c->dictIdxLog = log;
+        g.dictIdxEnd = end; g.dictIdxLen = ixLen; g.dictIdxLog = log;
     }
-    c->dictDirty = false;
     return 0;
+}
+// upload a newly loaded dictionary with what the context's switches ask of it (their setters mark it dirty, so a switch turned on
+// later builds its tables too).  A shared CDict is complete and on the device already: nothing to do, and nothing is counted.
+static size_t cctx_sync_dictionary(ZSTD_CCtx* c)
+{
+    if (cdict_shared(c) || !c->dictDirty) return 0;
+    if (c->own.dictFormatted || !c->own.dictHost.empty()) c->dictUploads++;
+    const size_t e = digest_upload(c->own, c->stream, c->dictEntropy != 0, c->dictIndex != 0, c->dictIndexStrategy >= 2 || c->dictIndexChain);
+    if (isErr(e) && e != ZERR(kErrDictionaryCorrupted)) return e;
+    c->dictDirty = false;
+    return e;
 }
 
 // the dictionary's compression tables for a call, or nullptr: the switch is on and a formatted dictionary is in use (synced before)
 static const DictCTables* call_dict_ctables(const ZSTD_CCtx* c, const CallParams& cp)
 {
-    return (cp.dictEntropy && cp.useDict && c->dictFormatted && c->dictCTabDev.p) ? (const DictCTables*)c->dictCTabDev.p : nullptr;
+    const DictDigest& g = dict_in_force(c);
+    return (cp.dictEntropy && cp.useDict && g.dictFormatted && g.dictCTabDev.p) ? (const DictCTables*)g.dictCTabDev.p : nullptr;
 }
 
 // How a range of paramSize bytes is cut into blocks and frames (a function of the parameters, the loaded dictionary and that size):
@@ -439,20 +473,21 @@ static LaunchState launch_state(const ZSTD_CCtx* c, const CallParams& cp, const 
     // a formatted dictionary: its dictID in every frame header (unless ZSTD_c_dictIDFlag = 0), its repcodes in front of every frame.
     // The window: one frame per call states its own beside (or instead of) the content size, frames of independent blocks the
     // block's; a stream's header never carries a content size
-    const bool fmtDict = cp.useDict && c->dictFormatted;
-    L.header.dictID = fmtDict ? c->info.dictID : 0u;
+    const DictDigest& g = dict_in_force(c);
+    const bool fmtDict = cp.useDict && g.dictFormatted;
+    L.header.dictID = fmtDict ? g.info.dictID : 0u;
     L.header.dictIdBytes = (u8)(cp.dictIDFlag ? dict_id_bytes(L.header.dictID) : 0u);
     L.header.checksum = cp.checksumFlag ? 1 : 0;
     L.header.noContentSize = (cp.contentSizeFlag && !cp.stream) ? 0 : 1;
     L.header.windowLog = (u8)(fr.single ? fr.singleWindowLog : fr.indepWindowLog);
     const u32 plainReps[3] = { 1, 4, 8 };
-    for (int i = 0; i < 3; ++i) L.initReps[i] = fmtDict ? c->info.rep[i] : plainReps[i];
+    for (int i = 0; i < 3; ++i) L.initReps[i] = fmtDict ? g.info.rep[i] : plainReps[i];
     L.dct = call_dict_ctables(c, cp);
-    L.prefix = fr.prefixLen ? (const u8*)c->dict.p + (c->dictHost.size() - fr.prefixLen) : nullptr;
+    L.prefix = fr.prefixLen ? (const u8*)g.dict.p + (g.dictHost.size() - fr.prefixLen) : nullptr;
     {
-        const u32* const tables = (const u32*)c->dictIdxDev.p;
-        const bool dual = c->dictIdxDual && tables;
-        L.dix = DictIndexRef{ c->dictIdxEnd, c->dictIdxLen, tables, c->dictIdxLog, dual ? tables + ((size_t)1 << c->dictIdxLog) : nullptr, dual ? tables + ((size_t)2 << c->dictIdxLog) : nullptr };
+        const u32* const tables = (const u32*)g.dictIdxDev.p;
+        const bool dual = g.dictIdxDual && tables;
+        L.dix = DictIndexRef{ g.dictIdxEnd, g.dictIdxLen, tables, g.dictIdxLog, dual ? tables + ((size_t)1 << g.dictIdxLog) : nullptr, dual ? tables + ((size_t)2 << g.dictIdxLog) : nullptr };
     }
     return L;
 }
@@ -661,7 +696,7 @@ static void plan_ranges(const std::vector<u32>& counts, size_t group, size_t src
 // LDM together with a dictionary: the dictionary's framing (a prefix in front of independent 64 KiB frames) cannot hold a window-sized frame
 static size_t check_ldm_dict(const ZSTD_CCtx* c, const CallParams& cp, size_t srcSize)
 {
-    if (ldm_active(cp, srcSize) && cp.useDict && (c->dictFormatted || c->dictHost.size() >= 8)) return ZERR(kErrParameterUnsupported);
+    if (ldm_active(cp, srcSize) && cp.useDict && (dict_in_force(c).dictFormatted || dict_in_force(c).dictHost.size() >= 8)) return ZERR(kErrParameterUnsupported);
     return 0;
 }
 // ZSTDMI_CCtx_setSingleFrame with what one frame across passes cannot be: refused at the call, before a byte is read.  (Calls of at
@@ -672,7 +707,7 @@ static size_t check_single_frame(const ZSTD_CCtx* c, const CallParams& cp, size_
     if ((u64)srcSize > kSingleMax) return ZERR(kErrParameterUnsupported);
     if (cp.seek || c->workers.size() > 1) return ZERR(kErrParameterUnsupported);       // (frames are the seek table's and the workers' unit)
     if (cp.windowLog >= 10 && cp.windowLog < 18) return ZERR(kErrParameterUnsupported); // (the finders reach up to 2^18 back)
-    if (cp.useDict && (c->dictFormatted || c->dictHost.size() >= 8)) return ZERR(kErrParameterUnsupported);   // (a dictionary's framing: a prefix in front of independent blocks)
+    if (cp.useDict && (dict_in_force(c).dictFormatted || dict_in_force(c).dictHost.size() >= 8)) return ZERR(kErrParameterUnsupported);   // (a dictionary's framing: a prefix in front of independent blocks)
     if (cp.stream ? cp.ldm == 1 : ldm_active(cp, srcSize)) {       // one LDM frame is one frame already (bytes unchanged); more than one is not,
         if (cp.stream || srcSize > ldm_frame_span(c, cp, srcSize)) {  // unless the window slides (ZSTDMI_CCtx_setSlidingLdm): up to 2^28, the decoder's 29-bit offset record
             if (!cp.sliding || ldm_window_log(cp) > 28) return ZERR(kErrParameterUnsupported);
@@ -834,7 +869,7 @@ size_t ZSTD_freeCCtx(ZSTD_CCtx* c)
         (void)hipSetDevice(c->device);
         if (c->ownStream) (void)hipStreamSynchronize(c->ownStream);
         c->seqs.release(); c->lits.release(); c->meta.release(); c->tables.release(); c->slots.release(); c->cand.release(); c->lastRegionList = nullptr; c->dixDist.release(); c->probe.release();
-        c->gatherIn.release(); c->gatherOut.release(); c->batchStage.release(); c->batchTab.release(); c->packArena.release(); c->packTab.release(); c->ldmSmall.release(); c->ldmBig.release(); c->offsets.release(); c->total.release(); c->seekEntries.release(); c->seekSort.release(); c->stageSrc.release(); c->stageDst.release(); c->pfxStage.release(); c->sfXxh.release(); c->sWin.release(); c->dict.release(); c->dictWideDev.release(); c->dictIdxDev.release(); c->dictFullDev.release(); c->dictInfoDev.release(); c->dictCTabDev.release();
+        c->gatherIn.release(); c->gatherOut.release(); c->batchStage.release(); c->batchTab.release(); c->packArena.release(); c->packTab.release(); c->ldmSmall.release(); c->ldmBig.release(); c->offsets.release(); c->total.release(); c->seekEntries.release(); c->seekSort.release(); c->stageSrc.release(); c->stageDst.release(); c->pfxStage.release(); c->sfXxh.release(); c->sWin.release(); c->own.release();
         c->timer.destroy();
         if (c->ownStream) (void)hipStreamDestroy(c->ownStream);
     }
@@ -943,8 +978,9 @@ static size_t ZSTD_CCtx_loadDictionary_impl(ZSTD_CCtx* c, const void* dict, size
     if (!c->sIn.empty() || c->sEnding) return ZERR(kErrStageWrong);        /* not in the middle of a streaming frame session, U/ZstdCompress.cs:1273 */
     c->dictGen++;
     c->pfx = nullptr; c->pfxSize = 0;       // (a pending prefix is cancelled: ZSTD_clearAllDicts)
-    c->dictFormatted = false; c->dictFull.clear(); c->dictWide.clear();
-    if (dict == nullptr || dictSize == 0) { c->dictHost.clear(); c->dictDirty = true; return 0; }          /* "no dictionary" */
+    c->cdict = nullptr;                     // (and a referenced CDict)
+    c->own.dictFormatted = false; c->own.dictFull.clear(); c->own.dictWide.clear();
+    if (dict == nullptr || dictSize == 0) { c->own.dictHost.clear(); c->dictDirty = true; return 0; }          /* "no dictionary" */
     if (dictSize > (size_t)1 << 30) return ZERR(kErrParameterUnsupported);
     u8 head[8] = {};
     const bool dev = is_device_ptr(dict);
@@ -955,7 +991,7 @@ static size_t ZSTD_CCtx_loadDictionary_impl(ZSTD_CCtx* c, const void* dict, size
         std::vector<u8> full(dictSize);
         if (dev) { if (hipMemcpy(full.data(), dict, dictSize, hipMemcpyDeviceToHost) != hipSuccess) return ZERR(kErrGeneric); }
         else memcpy(full.data(), dict, dictSize);
-        c->dictFull.swap(full); c->dictHost.clear(); c->dictFormatted = true; c->dictDirty = true;
+        c->own.dictFull.swap(full); c->own.dictHost.clear(); c->own.dictFormatted = true; c->dictDirty = true;
         if (!isErr(cctx_bind(c))) return cctx_sync_dictionary(c);          // validated now when a device is there, else at first use
         return 0;
     }
@@ -964,13 +1000,13 @@ static size_t ZSTD_CCtx_loadDictionary_impl(ZSTD_CCtx* c, const void* dict, size
     const u8* tail = (const u8*)dict + (dictSize - h.size());
     if (dev) { if (hipMemcpy(h.data(), tail, h.size(), hipMemcpyDeviceToHost) != hipSuccess) return ZERR(kErrGeneric); }
     else memcpy(h.data(), tail, h.size());
-    c->dictHost.swap(h);
+    c->own.dictHost.swap(h);
     if (dictSize >= 8) {        // what an index would cover (ZSTDMI_CCtx_setDictIndex, before or after this load)
         std::vector<u8> wide(dictSize < dict_index_max() ? dictSize : dict_index_max());
         const u8* from = (const u8*)dict + (dictSize - wide.size());
         if (dev) { if (hipMemcpy(wide.data(), from, wide.size(), hipMemcpyDeviceToHost) != hipSuccess) return ZERR(kErrGeneric); }
         else memcpy(wide.data(), from, wide.size());
-        c->dictWide.swap(wide);
+        c->own.dictWide.swap(wide);
     }
     c->dictDirty = true;
     return 0;
@@ -1045,9 +1081,9 @@ static size_t compress_prefixed(ZSTD_CCtx* c, void* dst, size_t dstCapacity, con
         const size_t keep = pfxSize < kDictKeep ? pfxSize : kDictKeep;
         std::vector<u8> h(keep);
         if (hipMemcpy(h.data(), (const u8*)pfx + (pfxSize - keep), keep, hipMemcpyDefault) != hipSuccess) { (void)hipGetLastError(); return ZERR(kErrGeneric); }
-        c->dictHost.swap(h); c->dictFormatted = false; c->dictDirty = true; c->dictGen++;
+        c->own.dictHost.swap(h); c->own.dictFormatted = false; c->dictDirty = true; c->dictGen++;
         const size_t r = plain();
-        c->dictHost.clear(); c->dictDirty = true; c->dictGen++;
+        c->own.dictHost.clear(); c->dictDirty = true; c->dictGen++;
         return r;
     }
     { const size_t e2 = check_call_params(cp); if (isErr(e2)) return e2; }
@@ -1070,11 +1106,115 @@ static size_t ZSTD_CCtx_refPrefix_impl(ZSTD_CCtx* c, const void* prefix, size_t 
     if (!c) return ZERR(kErrGeneric);
     if (!c->sIn.empty() || c->sEnding) return ZERR(kErrStageWrong);
     if (prefix && prefixSize > (size_t)1 << 30) return ZERR(kErrParameterUnsupported);
-    // ZSTD_clearAllDicts: a loaded dictionary and an earlier prefix are gone
-    c->dictGen++; c->dictFormatted = false; c->dictFull.clear(); c->dictHost.clear(); c->dictWide.clear(); c->dictDirty = true;
+    // ZSTD_clearAllDicts: a loaded dictionary, a referenced CDict and an earlier prefix are gone
+    c->cdict = nullptr;
+    c->dictGen++; c->own.dictFormatted = false; c->own.dictFull.clear(); c->own.dictHost.clear(); c->own.dictWide.clear(); c->dictDirty = true;
     c->pfx = nullptr; c->pfxSize = 0;
     if (prefix && prefixSize) { c->pfx = prefix; c->pfxSize = prefixSize; }
     return 0;
+}
+
+// ---------------- digested dictionaries (ZSTD_createCDict, U/ZstdCompress.cs:5984-6110; ZSTD_CCtx_refCDict, :1700) ----------------
+// a dictionary's bytes (host memory) into a digest's host fields, as ZSTD_CCtx_loadDictionary files them
+static void digest_set_bytes(DictDigest& g, const u8* b, size_t n)
+{
+    g.dictFormatted = false; g.dictFull.clear(); g.dictWide.clear(); g.dictHost.clear(); g.info = DictInfo{};
+    if (!n) return;
+    if (is_formatted_dictionary(b, n)) { g.dictFull.assign(b, b + n); g.dictFormatted = true; return; }
+    const size_t keep = n < 8 ? n : (n < kDictKeep ? n : kDictKeep);
+    g.dictHost.assign(b + (n - keep), b + n);
+    if (n >= 8) { const size_t wide = n < dict_index_max() ? n : dict_index_max(); g.dictWide.assign(b + (n - wide), b + n); }
+}
+static ZSTD_CDict* create_cdict(const void* dict, size_t dictSize, int level, int device)
+{
+    if ((dictSize && !dict) || dictSize > (size_t)1 << 30) return nullptr;
+    if (device < 0 || device_count() <= device) return nullptr;       // no gfx950 device: no digest
+    if (hipSetDevice(device) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+    ZSTD_CDict_s* cd = new (std::nothrow) ZSTD_CDict_s();
+    if (!cd) return nullptr;
+    if (level < ZSTD_minCLevel()) level = ZSTD_minCLevel();
+    if (level > ZSTD_maxCLevel()) level = ZSTD_maxCLevel();
+    cd->level = level == 0 ? 3 : level; cd->device = device;            // (0 means the default level, U/ZstdCompress.cs:5991)
+    bool ok = true;
+    hipStream_t s = nullptr;
+    try {       // (host containers may throw: nothing of a half-made CDict is left behind)
+        std::vector<u8> bytes(dictSize);
+        if (dictSize && hipMemcpy(bytes.data(), dict, dictSize, hipMemcpyDefault) != hipSuccess) { (void)hipGetLastError(); ok = false; }
+        if (ok) digest_set_bytes(cd->dg, bytes.data(), dictSize);
+        // whole, on a stream of its own, waited for: every table any switch of a context can ask for
+        if (ok && hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); s = nullptr; ok = false; }
+        if (ok) ok = !isErr(digest_upload(cd->dg, s, true, true, true)) && !isErr(stream_wait(s));
+    } catch (...) { ok = false; }
+    if (s) (void)hipStreamDestroy(s);
+    if (!ok) { cd->dg.release(); delete cd; return nullptr; }
+    return cd;
+}
+ZSTD_CDict* ZSTDMI_createCDictOnDevice(const void* dict, size_t dictSize, int compressionLevel, int device) { return create_cdict(dict, dictSize, compressionLevel, device); }
+ZSTD_CDict* ZSTD_createCDict(const void* dict, size_t dictSize, int compressionLevel) { return ZSTDMI_createCDictOnDevice(dict, dictSize, compressionLevel, 0); }
+size_t ZSTD_freeCDict(ZSTD_CDict* cd)
+{
+    if (!cd) return 0;
+    if (hipSetDevice(cd->device) == hipSuccess) cd->dg.release(); else (void)hipGetLastError();
+    delete cd;
+    return 0;
+}
+size_t ZSTD_sizeof_CDict(const ZSTD_CDict* cd) { return cd ? sizeof(*cd) + cd->dg.bytes() : 0; }
+unsigned ZSTD_getDictID_fromCDict(const ZSTD_CDict* cd) { return (cd && cd->dg.dictFormatted) ? cd->dg.info.dictID : 0u; }
+
+// The context's own digest follows its reference: empty while the CDict's device copies are shared, a private copy of the CDict's host
+// bytes (uploaded by the next call, exactly as after ZSTD_CCtx_loadDictionary) while they cannot be.  Touches no device.
+static void cctx_adopt_cdict(ZSTD_CCtx* c)
+{
+    c->dictGen++; c->dictDirty = true;
+    DictDigest& g = c->own;
+    g.dictFormatted = false; g.dictFull.clear(); g.dictHost.clear(); g.dictWide.clear();
+    if (!c->cdict || cdict_shared(c)) return;
+    const DictDigest& from = c->cdict->dg;
+    g.dictFormatted = from.dictFormatted; g.dictFull = from.dictFull; g.dictHost = from.dictHost; g.dictWide = from.dictWide; g.info = from.info;
+}
+size_t ZSTD_CCtx_refCDict(ZSTD_CCtx* c, const ZSTD_CDict* cdict)
+{
+    if (!c) return ZERR(kErrGeneric);
+    if (!c->sIn.empty() || c->sEnding) return ZERR(kErrStageWrong);
+    return guarded([&]() -> size_t {
+        c->pfx = nullptr; c->pfxSize = 0;       // ZSTD_clearAllDicts: a loaded dictionary and a pending prefix are gone
+        c->cdict = cdict;
+        cctx_adopt_cdict(c);
+        return 0;
+    });
+}
+size_t ZSTD_compress_usingCDict(ZSTD_CCtx* c, void* dst, size_t dstCapacity, const void* src, size_t srcSize, const ZSTD_CDict* cdict)
+{
+    if (!c || !cdict) return ZERR(kErrGeneric);
+    // the CDict's level, default frame parameters, the context's four dictionary switches; the context's own dictionary or reference
+    // steps aside for the call (where the CDict cannot be shared, its host fields do, and are uploaded again by their next use)
+    CallParams p; p.level = cdict->level; p.useDict = true;
+    p.dictEntropy = c->dictEntropy != 0; p.dictIndex = c->dictIndex != 0; p.dictIndexStrategy = c->dictIndexStrategy; p.dictIndexChain = c->dictIndexChain != 0;
+    return guarded([&]() -> size_t {
+        const ZSTD_CDict_s* const was = c->cdict;
+        c->cdict = cdict;
+        if (cdict_shared(c)) {
+            const size_t r = compress_any(c, p, dst, dstCapacity, src, srcSize);
+            c->cdict = was;
+            return r;
+        }
+        DictDigest& g = c->own;
+        std::vector<u8> h, f, w; const bool fmt = g.dictFormatted; const DictInfo info = g.info;
+        h.swap(g.dictHost); f.swap(g.dictFull); w.swap(g.dictWide);
+        size_t r;
+        try { cctx_adopt_cdict(c); r = compress_any(c, p, dst, dstCapacity, src, srcSize); }
+        catch (...) { r = ZERR(kErrMemoryAllocation); }
+        g.dictHost.swap(h); g.dictFull.swap(f); g.dictWide.swap(w); g.dictFormatted = fmt; g.info = info;
+        c->cdict = was; c->dictDirty = true; c->dictGen++;
+        return r;
+    });
+}
+long long ZSTDMI_debugDictUploads(const ZSTD_CCtx* c)
+{
+    if (!c) return -1;
+    long long n = c->dictUploads;
+    for (const ZSTD_CCtx* w : c->workers) n += w->dictUploads;
+    return n;
 }
 
 size_t ZSTDMI_compressDevice(ZSTD_CCtx* c, void* d_dst, size_t dstCapacity, const void* d_src, size_t srcSize)
@@ -1129,7 +1269,7 @@ static size_t compress_multi(ZSTD_CCtx* c, const CallParams& cp, void* dst, size
         w->dictEntropy = c->dictEntropy;        // (before the dictionary: a worker builds the tables when it uploads its copy)
         w->dictIndex = c->dictIndex; w->dictIndexStrategy = c->dictIndexStrategy; w->dictIndexChain = c->dictIndexChain;       // (and the index, as far up the strategies as the parent's)
         if (w->dictGen != c->dictGen) {
-            w->dictHost = c->dictHost; w->dictFull = c->dictFull; w->dictWide = c->dictWide; w->dictFormatted = c->dictFormatted; w->info = c->info; w->dictDirty = true; w->dictGen = c->dictGen;
+            w->own.dictHost = c->own.dictHost; w->own.dictFull = c->own.dictFull; w->own.dictWide = c->own.dictWide; w->own.dictFormatted = c->own.dictFormatted; w->own.info = c->own.info; w->dictDirty = true; w->dictGen = c->dictGen;
         }
     }
     size_t err = 0;
@@ -1414,8 +1554,14 @@ static size_t ZSTD_compressStream2_impl(ZSTD_CCtx* c, ZSTD_outBuffer* output, ZS
 
 // ---------------- extensions ----------------
 int ZSTDMI_deviceCount(void) { return device_count(); }
-size_t ZSTDMI_CCtx_setDevice(ZSTD_CCtx* c, int device) { return ctx_set_device(c, device); }
-size_t ZSTDMI_CCtx_setDevices(ZSTD_CCtx* c, const int* devices, int n) { return ctx_set_devices(c, devices, n, ZSTD_createCCtx, ZSTD_freeCCtx); }
+// (a referenced CDict is shared or copied by where the context runs: cctx_adopt_cdict)
+size_t ZSTDMI_CCtx_setDevice(ZSTD_CCtx* c, int device) { const size_t e = ctx_set_device(c, device); if (c && c->cdict) (void)guarded([&]() -> size_t { cctx_adopt_cdict(c); return 0; }); return e; }
+size_t ZSTDMI_CCtx_setDevices(ZSTD_CCtx* c, const int* devices, int n)
+{
+    const size_t e = ctx_set_devices(c, devices, n, ZSTD_createCCtx, ZSTD_freeCCtx);
+    if (c && c->cdict) (void)guarded([&]() -> size_t { cctx_adopt_cdict(c); return 0; });
+    return e;
+}
 size_t ZSTDMI_CCtx_setStream(ZSTD_CCtx* c, void* st) { return ctx_set_stream(c, st, cctx_bind); }
 size_t ZSTDMI_CCtx_setPassChunks(ZSTD_CCtx* c, unsigned chunks) { if (!c || chunks == 0 || chunks > (1u << 20)) return ZERR(kErrParameterOutOfBound); c->passChunks = chunks; return 0; }
 // bytes: 0 = independent 64 KiB frames; > 0 = cross-chunk history of that many bytes per block (rounded to 4 KiB, at most 48 KiB);
@@ -1436,7 +1582,7 @@ size_t ZSTDMI_CCtx_setDictEntropy(ZSTD_CCtx* c, unsigned mode)
 {
     if (!c) return ZERR(kErrGeneric);
     if (mode > 1) return ZERR(kErrParameterOutOfBound);
-    if (c->dictEntropy != (int)mode && c->dictFormatted) { c->dictDirty = true; c->dictGen++; }
+    if (c->dictEntropy != (int)mode && c->own.dictFormatted) { c->dictDirty = true; c->dictGen++; }
     c->dictEntropy = (int)mode;
     return 0;
 }
@@ -1445,7 +1591,7 @@ size_t ZSTDMI_CCtx_setDictIndex(ZSTD_CCtx* c, unsigned mode)
 {
     if (!c) return ZERR(kErrGeneric);
     if (mode > 1) return ZERR(kErrParameterOutOfBound);
-    if (c->dictIndex != (int)mode && (c->dictFormatted || !c->dictWide.empty())) { c->dictDirty = true; c->dictGen++; }
+    if (c->dictIndex != (int)mode && (c->own.dictFormatted || !c->own.dictWide.empty())) { c->dictDirty = true; c->dictGen++; }
     c->dictIndex = (int)mode;
     return 0;
 }
@@ -1455,7 +1601,7 @@ size_t ZSTDMI_CCtx_setDictIndexStrategy(ZSTD_CCtx* c, unsigned maxStrategy)
 {
     if (!c) return ZERR(kErrGeneric);
     if (maxStrategy < 1 || maxStrategy > 2) return ZERR(kErrParameterOutOfBound);
-    if (c->dictIndexStrategy != (int)maxStrategy && c->dictIndex && (c->dictFormatted || !c->dictWide.empty())) { c->dictDirty = true; c->dictGen++; }
+    if (c->dictIndexStrategy != (int)maxStrategy && c->dictIndex && (c->own.dictFormatted || !c->own.dictWide.empty())) { c->dictDirty = true; c->dictGen++; }
     c->dictIndexStrategy = (int)maxStrategy;
     return 0;
 }
@@ -1465,7 +1611,7 @@ size_t ZSTDMI_CCtx_setDictIndexChain(ZSTD_CCtx* c, unsigned mode)
 {
     if (!c) return ZERR(kErrGeneric);
     if (mode > 1) return ZERR(kErrParameterOutOfBound);
-    if (c->dictIndexChain != (int)mode && c->dictIndex && (c->dictFormatted || !c->dictWide.empty())) { c->dictDirty = true; c->dictGen++; }
+    if (c->dictIndexChain != (int)mode && c->dictIndex && (c->own.dictFormatted || !c->own.dictWide.empty())) { c->dictDirty = true; c->dictGen++; }
     c->dictIndexChain = (int)mode;
     return 0;
 }

@@ -7,6 +7,7 @@
 #include "zmi_pack_runs.h"
 #include "zmi_stream_scan.h"
 #include "zmi_host.h"
+#include "zmi_dictid.h"
 
 struct ZSTD_DCtx_s {
     int windowLogMax = 27;
@@ -60,11 +61,22 @@ struct ZSTD_DCtx_s {
     std::vector<u8> dictHost; DevBuf dict, dictInfoDev; bool dictDirty = false, dictFormatted = false;
     DictInfo info = {};
     u64 dictGen = 0;
+    // ZSTD_DCtx_refDDict: a digested dictionary, referenced.  decode_dict() hands the kernels its device copies and ready-made
+    // sequence tables where they can be shared (ddict_shared); elsewhere the fields above hold a private copy of its bytes (dctx_adopt_ddict)
+    const ZSTD_DDict_s* ddict = nullptr;
+    long long dictUploads = 0;          // uploads this context made itself (ZSTDMI_debugDictUploadsD)
+    long long lastDictTabBlocks = 0;    // blocks of the last call that copied a ready-made table (ZSTDMI_debugLastDictTableBlocks)
     std::vector<ZSTD_DCtx_s*> workers;      // ZSTDMI_DCtx_setDevices (decompress_multi)
     // ZSTD_DCtx_refPrefix: the caller's bytes (host or device), referenced until the next ZSTD_decompressDCtx / ZSTDMI_decompressDevice
     // has consumed them.  pfxDev: the prefix as that call's kernels read it (the caller's device pointer, or pfxStage for a host prefix)
     const void* pfx = nullptr; size_t pfxSize = 0; DevBuf pfxStage; const u8* pfxDev = nullptr;
 };
+
+// ZSTD_createDDict: a dictionary uploaded, validated and digested once on `device`, immutable afterwards (any number of contexts and
+// threads read it without a lock): the bytes with 64 readable ones behind them, DictInfo, and for a formatted dictionary its three
+// sequence decoding tables ready-made in seq_decode_kernel's LDS format (seqTabs: kDictTabWords words, decode_seq.hip).
+struct ZSTD_DDict_s { std::vector<u8> host; DevBuf dict, dictInfoDev, seqTabs; DictInfo info = {}; bool formatted = false; int device = 0; };
+static bool ddict_shared(const ZSTD_DCtx* d) { return d->ddict && d->ddict->device == d->device && d->workers.size() <= 1; }
 
 static size_t dctx_sync_dictionary(ZSTD_DCtx* d);
 static size_t dctx_bind(ZSTD_DCtx* d)
@@ -117,6 +129,7 @@ static size_t ZSTD_DCtx_loadDictionary_impl(ZSTD_DCtx* d, const void* dict, size
     if (!d) return ZERR(kErrGeneric);
     d->dictGen++;
     d->pfx = nullptr; d->pfxSize = 0;       // (a pending prefix is cancelled: ZSTD_clearAllDicts)
+    d->ddict = nullptr;                     // (and a referenced DDict)
     if (dict == nullptr || dictSize == 0) { d->dictHost.clear(); d->dictDirty = true; return 0; }
     if (dictSize > (size_t)1 << 30) return ZERR(kErrParameterUnsupported);
     std::vector<u8> h(dictSize);
@@ -247,9 +260,10 @@ static unsigned long long ZSTD_getFrameContentSize_impl(const void* src, size_t 
 // upload a newly loaded dictionary; a formatted one is validated on the device (ZSTD_loadDEntropy's checks) -> dictionary_corrupted
 static size_t dctx_sync_dictionary(ZSTD_DCtx* d)
 {
-    if (!d->dictDirty) return 0;
+    if (ddict_shared(d) || !d->dictDirty) return 0;     // (a shared DDict is on the device already)
     hipStream_t s = d->stream;
     if (!d->dictHost.empty()) {
+        d->dictUploads++;
         if (!d->dict.ensure(d->dictHost.size() + 64) || !d->dictInfoDev.ensure(sizeof(DictInfo))) return ZERR(kErrMemoryAllocation);
         if (hipMemcpyAsync(d->dict.p, d->dictHost.data(), d->dictHost.size(), hipMemcpyHostToDevice, s) != hipSuccess) return ZERR(kErrGeneric);
         if (d->dictFormatted) {
@@ -264,10 +278,23 @@ static size_t dctx_sync_dictionary(ZSTD_DCtx* d)
 }
 
 // the loaded dictionary as the decode kernels take it
-struct DecodeDict { bool fmt; const u8* dictFull; const DictInfo* dinfo; const u8* dictContent; u32 dictContentSize, dictID; };
+// seqTabs: a DDict's ready-made sequence tables (null for a loaded dictionary and for raw content)
+struct DecodeDict { bool fmt; const u8* dictFull; const DictInfo* dinfo; const u8* dictContent; u32 dictContentSize, dictID; const u32* seqTabs; };
 static DecodeDict decode_dict(const ZSTD_DCtx* d)
 {
     DecodeDict k;
+    if (ddict_shared(d)) {
+        const ZSTD_DDict_s& g = *d->ddict;
+        k.fmt = g.formatted && !g.host.empty();
+        k.dictFull = k.fmt ? (const u8*)g.dict.p : nullptr;
+        k.dinfo = k.fmt ? (const DictInfo*)g.dictInfoDev.p : nullptr;
+        k.dictContent = g.host.empty() ? nullptr : (const u8*)g.dict.p + (k.fmt ? g.info.contentOff : 0u);
+        k.dictContentSize = g.host.empty() ? 0u : (k.fmt ? g.info.contentSize : (u32)g.host.size());
+        k.dictID = k.fmt ? g.info.dictID : 0u;
+        k.seqTabs = k.fmt ? (const u32*)g.seqTabs.p : nullptr;
+        return k;
+    }
+    k.seqTabs = nullptr;
     k.fmt = d->dictFormatted && !d->dictHost.empty();
     k.dictFull = k.fmt ? (const u8*)d->dict.p : nullptr;
     k.dinfo = k.fmt ? (const DictInfo*)d->dictInfoDev.p : nullptr;
@@ -364,7 +391,7 @@ static size_t decode_lists(ZSTD_DCtx* d, const DecodeDict& dd, u8* d_dst, const 
         if (hipEventRecord(d->auxDone, d->aux) != hipSuccess) return ZERR(kErrGeneric);
         auxGuard.on = true;
     }
-    launch_seq_decode(d_src, frames, blocks, nBlocks, recs, status, dictFull, dinfo, s);            d->timer.mark("seq_decode", s);
+    launch_seq_decode(d_src, frames, blocks, nBlocks, recs, status, dictFull, dinfo, dd.seqTabs, s);            d->timer.mark("seq_decode", s);
     launch_block_offsets(frames, blocks, nFrames, link && link->reps ? link->reps : dinfo, nUnsized ? 1u : 0u, dstCapacity, status, s);  d->timer.mark("block_offsets", s);
     if (auxGuard.on) { if (hipStreamWaitEvent(s, d->auxDone, 0) != hipSuccess) return ZERR(kErrGeneric); d->timer.mark("decode_literals", s); }     // (what of it seq_decode did not cover)
     else launch_decode_literals(d_src, d_dst, (u8*)d->scratch.p, frames, blocks, nBlocks, status, (u8*)d->slowFlags.p, d->litDecoder, dictFull, dinfo, s, d->timer.hook());
@@ -388,7 +415,9 @@ static size_t decode_lists(ZSTD_DCtx* d, const DecodeDict& dd, u8* d_dst, const 
     }
     launch_exec_matches(d_src, d_dst, frames, blocks, nFrames, recs, status, dictContent, dictContentSize, s, execWaves);  d->timer.mark("exec_matches", s);
     if (!tail()) return ZERR(kErrGeneric);
-    return status_read(d, st);
+    { const size_t e = status_read(d, st); if (isErr(e)) return e; }
+    d->lastDictTabBlocks += st[kStDictTabBlocks];
+    return 0;
 }
 
 // The decompress pipeline over device-resident buffers.  Two host round trips size the work lists (frames + blocks after the
@@ -1250,9 +1279,117 @@ static size_t ZSTD_decompressStream_impl(ZSTD_DCtx* d, ZSTD_outBuffer* output, Z
     return d->dIn.empty() ? 0 : 1;                             // 0 only on a frame boundary
 }
 
+// ---------------- digested dictionaries (ZSTD_createDDict, U/ZstdDdict.cs:178-279; ZSTD_DCtx_refDDict, U/ZstdDecompress.cs:2300) ----------------
+static ZSTD_DDict* create_ddict(const void* dict, size_t dictSize, int device)
+{
+    if ((dictSize && !dict) || dictSize > (size_t)1 << 30) return nullptr;
+    if (device < 0 || device_count() <= device) return nullptr;       // no gfx950 device: no digest
+    if (hipSetDevice(device) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+    ZSTD_DDict_s* g = new (std::nothrow) ZSTD_DDict_s();
+    if (!g) return nullptr;
+    g->device = device;
+    bool ok = true;
+    try { g->host.resize(dictSize); } catch (...) { ok = false; }      // (nothing of a half-made DDict is left behind)
+    ok = ok && (!dictSize || hipMemcpy(g->host.data(), dict, dictSize, hipMemcpyDefault) == hipSuccess);
+    g->formatted = ok && is_formatted_dictionary(g->host.data(), dictSize);
+    hipStream_t s = nullptr;
+    if (ok && hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) { s = nullptr; ok = false; }
+    if (ok && dictSize) {
+        ok = g->dict.ensure(dictSize + 64) && g->dictInfoDev.ensure(sizeof(DictInfo)) &&
+             hipMemcpyAsync(g->dict.p, g->host.data(), dictSize, hipMemcpyHostToDevice, s) == hipSuccess;
+        if (ok && g->formatted) {
+            launch_dict_parse((const u8*)g->dict.p, (u32)dictSize, (DictInfo*)g->dictInfoDev.p, s);
+            ok = !isErr(dev_read(&g->info, g->dictInfoDev.p, sizeof(DictInfo), s)) && !g->info.err;      // (what dict_parse refuses never becomes a DDict)
+            if (ok) {
+                u32 logs[3] = { 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu };
+                ok = g->seqTabs.ensure(kDictTabWords * sizeof(u32));
+                if (ok) {
+                    launch_dict_seq_tables((const u8*)g->dict.p, (const DictInfo*)g->dictInfoDev.p, (u32*)g->seqTabs.p, s);
+                    ok = !isErr(dev_read(logs, (const u32*)g->seqTabs.p + kDictTabLogs, sizeof logs, s)) &&
+                         logs[0] != 0xFFFFFFFFu && logs[1] != 0xFFFFFFFFu && logs[2] != 0xFFFFFFFFu;
+                }
+            }
+        }
+        if (ok) ok = !isErr(stream_wait(s));
+    }
+    if (s) (void)hipStreamDestroy(s);
+    if (!ok) { (void)hipGetLastError(); g->dict.release(); g->dictInfoDev.release(); g->seqTabs.release(); delete g; return nullptr; }
+    return g;
+}
+ZSTD_DDict* ZSTDMI_createDDictOnDevice(const void* dict, size_t dictSize, int device) { return create_ddict(dict, dictSize, device); }
+ZSTD_DDict* ZSTD_createDDict(const void* dict, size_t dictSize) { return ZSTDMI_createDDictOnDevice(dict, dictSize, 0); }
+size_t ZSTD_freeDDict(ZSTD_DDict* g)
+{
+    if (!g) return 0;
+    if (hipSetDevice(g->device) == hipSuccess) { g->dict.release(); g->dictInfoDev.release(); g->seqTabs.release(); } else (void)hipGetLastError();
+    delete g;
+    return 0;
+}
+size_t ZSTD_sizeof_DDict(const ZSTD_DDict* g) { return g ? sizeof(*g) + g->host.capacity() + g->dict.cap + g->dictInfoDev.cap + g->seqTabs.cap : 0; }
+unsigned ZSTD_getDictID_fromDDict(const ZSTD_DDict* g) { return (g && g->formatted) ? g->info.dictID : 0u; }
+// The context's own dictionary fields follow its reference: empty while the DDict is shared, a private copy of its bytes (uploaded by
+// the next call, exactly as after ZSTD_DCtx_loadDictionary) while it cannot be.  Touches no device.
+static void dctx_adopt_ddict(ZSTD_DCtx* d)
+{
+    d->dictGen++; d->dictDirty = true; d->dictHost.clear(); d->dictFormatted = false;
+    if (!d->ddict || ddict_shared(d)) return;
+    d->dictHost = d->ddict->host; d->dictFormatted = d->ddict->formatted;
+}
+size_t ZSTD_DCtx_refDDict(ZSTD_DCtx* d, const ZSTD_DDict* ddict)
+{
+    if (!d) return ZERR(kErrGeneric);
+    return guarded([&]() -> size_t {
+        d->pfx = nullptr; d->pfxSize = 0;       // ZSTD_clearAllDicts: a loaded dictionary and a pending prefix are gone
+        d->ddict = ddict;
+        dctx_adopt_ddict(d);
+        return 0;
+    });
+}
+size_t ZSTD_decompress_usingDDict(ZSTD_DCtx* d, void* dst, size_t dstCapacity, const void* src, size_t srcSize, const ZSTD_DDict* ddict)
+{
+    if (!d || !ddict) return ZERR(kErrGeneric);
+    // the context's own dictionary or reference and a pending prefix step aside for the call and are left as found (where the DDict
+    // cannot be shared, the context's bytes are uploaded again by their next use)
+    return guarded([&]() -> size_t {
+        d->lastDictTabBlocks = 0;
+        const ZSTD_DDict_s* const was = d->ddict;
+        const void* const pfx = d->pfx; const size_t pfxSize = d->pfxSize;
+        d->pfx = nullptr; d->pfxSize = 0;
+        d->ddict = ddict;
+        size_t r;
+        if (ddict_shared(d)) r = ZSTD_decompressDCtx_impl(d, dst, dstCapacity, src, srcSize);
+        else {
+            std::vector<u8> h; const bool fmt = d->dictFormatted;
+            h.swap(d->dictHost);
+            try { dctx_adopt_ddict(d); r = ZSTD_decompressDCtx_impl(d, dst, dstCapacity, src, srcSize); }
+            catch (...) { r = ZERR(kErrMemoryAllocation); }
+            d->dictHost.swap(h); d->dictFormatted = fmt; d->dictDirty = true; d->dictGen++;
+        }
+        d->ddict = was; d->pfx = pfx; d->pfxSize = pfxSize;
+        return r;
+    });
+}
+long long ZSTDMI_debugDictUploadsD(const ZSTD_DCtx* d)
+{
+    if (!d) return -1;
+    long long n = d->dictUploads;
+    for (const ZSTD_DCtx* w : d->workers) n += w->dictUploads;
+    return n;
+}
+long long ZSTDMI_debugLastDictTableBlocks(const ZSTD_DCtx* d) { return d ? d->lastDictTabBlocks : -1; }
+// host memory in, no device touched (zmi_dictid.h)
+unsigned ZSTD_getDictID_fromDict(const void* dict, size_t dictSize) { return dictid_from_dict((const u8*)dict, dictSize); }
+unsigned ZSTD_getDictID_fromFrame(const void* src, size_t srcSize) { return dictid_from_frame((const u8*)src, srcSize); }
+
 // ---------------- extensions ----------------
-size_t ZSTDMI_DCtx_setDevice(ZSTD_DCtx* d, int device) { return ctx_set_device(d, device); }
-size_t ZSTDMI_DCtx_setDevices(ZSTD_DCtx* d, const int* devices, int n) { return ctx_set_devices(d, devices, n, ZSTD_createDCtx, ZSTD_freeDCtx); }
+// (a referenced DDict is shared or copied by where the context runs: dctx_adopt_ddict)
+size_t ZSTDMI_DCtx_setDevice(ZSTD_DCtx* d, int device) { const size_t e = ctx_set_device(d, device); if (d && d->ddict) (void)guarded([&]() -> size_t { dctx_adopt_ddict(d); return 0; }); return e; }
+size_t ZSTDMI_DCtx_setDevices(ZSTD_DCtx* d, const int* devices, int n)
+{
+    const size_t e = ctx_set_devices(d, devices, n, ZSTD_createDCtx, ZSTD_freeDCtx);
+    if (d && d->ddict) (void)guarded([&]() -> size_t { dctx_adopt_ddict(d); return 0; });
+    return e;
+}
 size_t ZSTDMI_DCtx_setStream(ZSTD_DCtx* d, void* st) { return ctx_set_stream(d, st, dctx_bind); }
 size_t ZSTDMI_DCtx_setStreamSegment(ZSTD_DCtx* d, size_t bytes)
 {
@@ -1282,36 +1419,37 @@ size_t ZSTD_DCtx_refPrefix(ZSTD_DCtx* d, const void* prefix, size_t prefixSize)
 {
     if (!d) return ZERR(kErrGeneric);
     if (prefix && prefixSize > (size_t)1 << 30) return ZERR(kErrParameterUnsupported);
-    // ZSTD_clearAllDicts: a loaded dictionary and an earlier prefix are gone
+    // ZSTD_clearAllDicts: a loaded dictionary, a referenced DDict and an earlier prefix are gone
+    d->ddict = nullptr;
     d->dictGen++; d->dictHost.clear(); d->dictFormatted = false; d->dictDirty = true;
     d->pfx = nullptr; d->pfxSize = 0;
     if (prefix && prefixSize) { d->pfx = prefix; d->pfxSize = prefixSize; }
     return 0;
 }
 size_t ZSTD_findFrameCompressedSize(const void* src, size_t srcSize) { return guarded([&] { return ZSTD_findFrameCompressedSize_impl(src, srcSize); }); }
-size_t ZSTD_decompressDCtx(ZSTD_DCtx* d, void* dst, size_t dstCapacity, const void* src, size_t srcSize) { return guarded([&] { return ZSTD_decompressDCtx_impl(d, dst, dstCapacity, src, srcSize); }); }
+size_t ZSTD_decompressDCtx(ZSTD_DCtx* d, void* dst, size_t dstCapacity, const void* src, size_t srcSize) { return guarded([&] { if (d) d->lastDictTabBlocks = 0; return ZSTD_decompressDCtx_impl(d, dst, dstCapacity, src, srcSize); }); }
 size_t ZSTDMI_decompressBatch(ZSTD_DCtx* d, const void* const* srcs, const size_t* srcSizes, size_t n, void* const* dsts, const size_t* dstCapacities, size_t* dstSizes)
 {
-    return guarded([&] { return decompress_batch_impl(d, srcs, srcSizes, n, dsts, dstCapacities, dstSizes); });
+    return guarded([&] { if (d) d->lastDictTabBlocks = 0; return decompress_batch_impl(d, srcs, srcSizes, n, dsts, dstCapacities, dstSizes); });
 }
 int ZSTDMI_debugLastBatchAloneD(const ZSTD_DCtx* d) { return d ? d->lastBatchAlone : -1; }
 size_t ZSTDMI_decompressRange(ZSTD_DCtx* d, void* dst, size_t dstCapacity, const void* src, size_t srcSize, unsigned long long offset, size_t length)
 {
     if (!d) return ZERR(kErrGeneric);
-    return guarded([&] { return decompress_range_impl(d, dst, dstCapacity, src, srcSize, offset, length); });
+    return guarded([&] { d->lastDictTabBlocks = 0; return decompress_range_impl(d, dst, dstCapacity, src, srcSize, offset, length); });
 }
 int ZSTDMI_debugLastRangeFrames(const ZSTD_DCtx* d) { return d ? d->lastRangeFrames : -1; }
 long long ZSTDMI_debugLastRangeStaged(const ZSTD_DCtx* d) { return d ? d->lastRangeStaged : -1; }
 size_t ZSTDMI_decompressRanges(ZSTD_DCtx* d, const void* src, size_t srcSize, const unsigned long long* offsets, const size_t* lengths, size_t n,
                                void* const* dsts, const size_t* dstCapacities, size_t* dstSizes)
 {
-    return guarded([&] { return decompress_ranges_impl(d, src, srcSize, offsets, lengths, n, dsts, dstCapacities, dstSizes); });
+    return guarded([&] { if (d) d->lastDictTabBlocks = 0; return decompress_ranges_impl(d, src, srcSize, offsets, lengths, n, dsts, dstCapacities, dstSizes); });
 }
 int ZSTDMI_debugLastRangesFrames(const ZSTD_DCtx* d) { return d ? d->lastRangesFrames : -1; }
 int ZSTDMI_debugLastRangesAlone(const ZSTD_DCtx* d) { return d ? d->lastRangesAlone : -1; }
 long long ZSTDMI_debugLastRangesStaged(const ZSTD_DCtx* d) { return d ? d->lastRangesStaged : -1; }
-size_t ZSTDMI_decompressDevice(ZSTD_DCtx* d, void* d_dst, size_t dstCapacity, const void* d_src, size_t srcSize) { return guarded([&] { return ZSTDMI_decompressDevice_impl(d, d_dst, dstCapacity, d_src, srcSize); }); }
-size_t ZSTD_decompressStream(ZSTD_DCtx* d, ZSTD_outBuffer* output, ZSTD_inBuffer* input) { return guarded([&] { return ZSTD_decompressStream_impl(d, output, input); }); }
+size_t ZSTDMI_decompressDevice(ZSTD_DCtx* d, void* d_dst, size_t dstCapacity, const void* d_src, size_t srcSize) { return guarded([&] { if (d) d->lastDictTabBlocks = 0; return ZSTDMI_decompressDevice_impl(d, d_dst, dstCapacity, d_src, srcSize); }); }
+size_t ZSTD_decompressStream(ZSTD_DCtx* d, ZSTD_outBuffer* output, ZSTD_inBuffer* input) { return guarded([&] { if (d) d->lastDictTabBlocks = 0; return ZSTD_decompressStream_impl(d, output, input); }); }
 unsigned long long ZSTD_decompressBound(const void* src, size_t srcSize)
 {
     try { return ZSTD_decompressBound_impl(src, srcSize); } catch (...) { return (unsigned long long)0 - 2; }      /* ZSTD_CONTENTSIZE_ERROR */

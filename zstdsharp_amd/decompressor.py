@@ -15,6 +15,7 @@ class Decompressor(_PrefixHolder):
         if not self.dctx:
             raise MemoryError("ZSTD_createDCtx")
         self._stream_segment = 0
+        self._ddict = None              # the DDict RefDDict holds
         if device is not None:
             ensure_zstd_success(self._lib, self._lib.ZSTDMI_DCtx_setDevice(self.dctx, device))
 
@@ -46,7 +47,31 @@ class Decompressor(_PrefixHolder):
         self._ensure_not_disposed()
         addr, n, keep = _as_buffer(dict_bytes if dict_bytes is not None else b"")
         self._release_prefix()          # (ZSTD_DCtx_loadDictionary cancels a pending prefix)
+        self._ddict = None              # (and a referenced DDict)
         ensure_zstd_success(self._lib, self._lib.ZSTD_DCtx_loadDictionary(self.dctx, addr, n))
+
+    def RefDDict(self, ddict):
+        """ZSTD_DCtx_refDDict: decode behind a digested dictionary (dictionaries.DDict) from now on; None = no dictionary.  Nothing is
+        uploaded: the DDict is shared.  Cancels a loaded dictionary and a pending prefix.  The object is kept referenced here so that
+        it cannot be collected while the context uses it."""
+        self._ensure_not_disposed()
+        if ddict is not None:
+            ddict._ensure_not_disposed()
+        self._release_prefix()
+        ensure_zstd_success(self._lib, self._lib.ZSTD_DCtx_refDDict(self.dctx, ddict.handle if ddict is not None else None))
+        self._ddict = ddict
+
+    def UnwrapUsingDDict(self, src, ddict, maxDecompressedSize: int = (1 << 31) - 1):
+        """ZSTD_decompress_usingDDict: src -> bytes, ONE call behind the DDict; this object's dictionary or reference is left as it is."""
+        self._ensure_not_disposed()
+        ddict._ensure_not_disposed()
+        saddr, sn, skeep = _as_buffer(src)
+        expected = self.GetDecompressedSize(src)
+        if expected > maxDecompressedSize:
+            raise ZstdException(ZSTD_ErrorCode.ZSTD_error_dstSize_tooSmall, f"Decompressed content size {expected} is greater than {maxDecompressedSize}")
+        out = ctypes.create_string_buffer(max(expected, 1))
+        n = ensure_zstd_success(self._lib, self._lib.ZSTD_decompress_usingDDict(self.dctx, out, expected, saddr, sn, ddict.handle))
+        return out.raw[:n]
 
     def RefPrefix(self, prefix):
         """ZSTD_DCtx_refPrefix: the next Unwrap / TryUnwrap decodes its frames behind `prefix` (bytes-like or a contiguous CUDA uint8
@@ -55,6 +80,7 @@ class Decompressor(_PrefixHolder):
         self._ensure_not_disposed()
         addr, n, keep, device = _as_prefix(prefix)
         self._release_prefix()
+        self._ddict = None              # (ZSTD_DCtx_refPrefix cancels a referenced DDict)
         ensure_zstd_success(self._lib, self._lib.ZSTD_DCtx_refPrefix(self.dctx, addr, n))
         self._hold_prefix(keep, device)
 
@@ -177,6 +203,7 @@ class Decompressor(_PrefixHolder):
 
     unwrap, try_unwrap, set_parameter, get_parameter, load_dictionary, get_decompressed_size, ref_prefix = \
         Unwrap, TryUnwrap, SetParameter, GetParameter, LoadDictionary, GetDecompressedSize, RefPrefix
+    ref_ddict, unwrap_using_ddict = RefDDict, UnwrapUsingDDict
 
     def Dispose(self):                                        # S/Decompressor.cs:113-147
         if getattr(self, "dctx", None):
