@@ -37,8 +37,11 @@ enum {
     ZSTD_c_enableLongDistanceMatching = 160, ZSTD_c_ldmHashLog = 161, ZSTD_c_ldmMinMatch = 162, ZSTD_c_ldmBucketSizeLog = 163,
     ZSTD_c_ldmHashRateLog = 164,
     ZSTD_c_contentSizeFlag = 200, ZSTD_c_checksumFlag = 201, ZSTD_c_dictIDFlag = 202, ZSTD_c_nbWorkers = 400,
-    ZSTD_d_windowLogMax = 100
+    ZSTD_d_windowLogMax = 100,
+    ZSTD_d_refMultipleDDicts = 1003         /* ZSTD_d_experimentalParam4, as in the reference */
 };
+/* U/ZSTD_refMultipleDDicts_e.cs: the values of ZSTD_d_refMultipleDDicts */
+enum { ZSTD_rmd_refSingleDDict = 0, ZSTD_rmd_refMultipleDDicts = 1 };
 /* U/ZSTD_paramSwitch_e.cs: the values of ZSTD_c_enableLongDistanceMatching */
 enum { ZSTD_ps_auto = 0, ZSTD_ps_enable = 1, ZSTD_ps_disable = 2 };
 
@@ -134,7 +137,8 @@ size_t     ZSTD_decompressDCtx(ZSTD_DCtx* dctx, void* dst, size_t dstCapacity, c
  * referencing it and switching between several touches no device and uploads nothing.  Lifetime is the caller's, as in libzstd: an
  * object must outlive every context that references it, and ZSTD_freeCCtx / ZSTD_freeDCtx never touch it.
  * Not provided: ZSTD_createCDict_byReference / ZSTD_createDDict_byReference (the bytes are always copied), the *_advanced
- * constructors, ZSTD_d_refMultipleDDicts and ZSTD_estimateCDictSize.
+ * constructors and ZSTD_estimateCDictSize; per-entry dictionaries in ZSTDMI_compressBatch (the compressor's side of
+ * ZSTD_d_refMultipleDDicts, below), a DDict set for segmented streams and a DDict set with several device workers.
  *
  * ZSTD_createCDict: `dict` is host or device memory; the bytes are copied.  compressionLevel 0 means 3 (U/ZstdCompress.cs:5991).  It is
  * created on the device a fresh context binds (ordinal 0; ZSTDMI_createCDictOnDevice for another) and holds there the staged tail, the
@@ -198,6 +202,36 @@ long long   ZSTDMI_debugDictUploadsD(const ZSTD_DCtx* dctx);
 /* diagnostic: compressed blocks of the last decode call that took at least one sequence table from a DDict's ready-made set (0 through
  * ZSTD_DCtx_loadDictionary, with a raw-content DDict and where the DDict is not shared); -1 without a context */
 long long   ZSTDMI_debugLastDictTableBlocks(const ZSTD_DCtx* dctx);
+/* ---- many dictionaries, one context: ZSTD_d_refMultipleDDicts (U/ZstdDecompress.cs:8-115, 343-366, 2300-2339) ----
+ * ZSTD_DCtx_setParameter(dctx, ZSTD_d_refMultipleDDicts, v): v = ZSTD_rmd_refSingleDDict (0, the default) or ZSTD_rmd_refMultipleDDicts
+ * (1); anything else: parameter_outOfBound.  Sticky; ZSTD_DCtx_getParameter reads it back; neither call touches a device.
+ * While it is 1, ZSTD_DCtx_refDDict(dctx, ddict) with a non-NULL DDict makes it the CURRENT DDict, as always, and also files it in
+ * the context's SET; a DDict whose dictID the set holds already replaces that entry.  The set is referenced, not copied (lifetime of
+ * the DDicts is the caller's, as for one reference), the call touches no device, and the set lives until ZSTD_freeDCtx.  It holds up to
+ * 65 536 DDicts; beyond that, and when memory runs out, the call answers memory_allocation and leaves the context as it was.
+ * ZSTD_DCtx_refDDict(NULL), ZSTD_DCtx_loadDictionary and ZSTD_DCtx_refPrefix clear the current DDict and leave the set alone.  The set is
+ * consulted only while a DDict is current and the parameter is 1; with the parameter back at 0 the context is a single-DDict context
+ * with its current DDict.  Raw-content DDicts (dictID 0) are kept in the set (the newest replaces), are never selected by a frame, and
+ * serve only as the current DDict.
+ * THE RULE, per frame and independent of the frame's neighbours: a frame whose header names a dictID != 0 that is in the set is decoded
+ * behind that DDict (content as history, Huffman table, the three sequence tables, ready-made, and repcodes).  Every other frame is
+ * treated exactly as the single-DDict decoder treats it with the current DDict: a frame without a dictID uses the current DDict, and a
+ * dictID that is not in the set answers dictionary_wrong unless it is the current one's.
+ * ONE DIFFERENCE FROM THE REFERENCE: there a selected DDict stays current for the following frames of the call, so a frame without a
+ * dictID that follows a frame naming A is decoded behind A.  Here it is decoded behind the DDict of the last ZSTD_DCtx_refDDict: the
+ * batch contract (entry i equals the single call on entry i) and the parallel walk both need a rule without order.
+ * It applies wherever a referenced DDict applies: ZSTD_decompressDCtx and ZSTDMI_decompressDevice (a concatenation of frames naming
+ * different dictionaries), ZSTDMI_decompressBatch (entries it decodes alone afterwards included), ZSTDMI_decompressRange(s), and
+ * ZSTD_decompressStream without a stream segment; with every ZSTDMI_DCtx_setLongFrames / setExecWaves / setLiteralDecoder / setOverlap
+ * value.  ZSTD_decompress_usingDDict stays ONE call behind that DDict alone: the set is not consulted and is left as found.
+ * parameter_unsupported, before a byte is read, while the parameter is 1, a DDict is current, the set holds two or more DDicts, and:
+ * the context has several device workers (ZSTDMI_DCtx_setDevices); or a DDict of the set (or the current one) lives on another device
+ * than the context; or ZSTDMI_DCtx_setStreamSegment is non-zero in ZSTD_decompressStream.  A set of exactly one DDict takes the
+ * single-DDict path in all of these, private upload included.
+ * ZSTDMI_debugLastSetFrames: frames of the last decode call whose dictionary was found in the set by dictID (entries and frames the call
+ * handed to its own single-call path included; frames of entries that end with a header-stage error are not counted), counted on the
+ * device by the frame walk; 0 whenever the single-dictionary kernels ran; -1 without a context. */
+long long   ZSTDMI_debugLastSetFrames(const ZSTD_DCtx* dctx);
 
 /* ---- errors: S/ThrowHelper.cs:12-13 -> U/ErrorPrivate.cs:10-24, 35-120 ---- */
 unsigned    ZSTD_isError(size_t code);

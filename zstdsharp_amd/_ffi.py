@@ -93,6 +93,7 @@ SIGNATURES = {
     "ZSTDMI_debugDictUploads": (ctypes.c_longlong, [c_void_p]),
     "ZSTDMI_debugDictUploadsD": (ctypes.c_longlong, [c_void_p]),
     "ZSTDMI_debugLastDictTableBlocks": (ctypes.c_longlong, [c_void_p]),
+    "ZSTDMI_debugLastSetFrames": (ctypes.c_longlong, [c_void_p]),
     "ZSTDMI_deviceCount": (c_int, []),
     "ZSTDMI_CCtx_setDevice": (c_size_t, [c_void_p, c_int]),
     "ZSTDMI_DCtx_setDevice": (c_size_t, [c_void_p, c_int]),

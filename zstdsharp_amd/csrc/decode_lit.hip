@@ -23,9 +23,13 @@ struct LitJob {
     const u8* hsrc; u32 hlen;       // this block's compressed literals (behind the section header; description included when own)
     u8* dst; u32 litSize; u32 single;
 };
+// kSet (ZSTD_d_refMultipleDDicts with two or more DDicts in the set): the dictionary's Huffman description is that of the block's own
+// frame, slots[F.dictSlot].  Every lane computes its job itself from plain per-lane loads — the serial decoders carry several blocks,
+// possibly behind several dictionaries, in one wave — so nothing here relies on the dictionary being the same across a wave.
+template <bool kSet>
 __device__ __forceinline__ bool lit_job(LitJob& J, u32 bi, const BlockDesc* __restrict__ blocks, const FrameDesc* __restrict__ frames,
                                         const u8* __restrict__ src, u8* __restrict__ out, u8* __restrict__ scratch,
-                                        const u8* __restrict__ dictFull, const DictInfo* __restrict__ di)
+                                        const u8* __restrict__ dictFull, const DictInfo* __restrict__ di, const DictSlot* __restrict__ slots)
 {
     const BlockDesc& B = blocks[bi];
     if (B.type != 2 || B.litType < 2 || B.err) return false;
@@ -34,7 +38,11 @@ __device__ __forceinline__ bool lit_job(LitJob& J, u32 bi, const BlockDesc* __re
     J.hsrc = src + B.srcOff + B.lhSize; J.hlen = B.litCSize; J.litSize = B.litSize; J.single = B.litSingle;
     J.own = B.hufSrc == bi; J.tErr = kErrCorruption;
     if (J.own) { J.tsrc = J.hsrc; J.tlen = J.hlen; }
-    else if (B.hufSrc == kDictBlock) { J.tsrc = dictFull + di->hufOff; J.tlen = di->hufSize; J.tErr = kErrDictionaryCorrupted; }
+    else if (B.hufSrc == kDictBlock) {
+        if constexpr (kSet) { const DictSlot& D = slots[F.dictSlot]; J.tsrc = D.dictFull + D.hufOff; J.tlen = D.hufSize; }
+        else { J.tsrc = dictFull + di->hufOff; J.tlen = di->hufSize; }
+        J.tErr = kErrDictionaryCorrupted;
+    }
     else { const BlockDesc& S = blocks[B.hufSrc]; J.tsrc = src + S.srcOff + S.lhSize; J.tlen = S.litCSize; }
     // a block without sequences regenerates exactly its literals: they are decoded in place
     J.dst = B.litInPlace ? out + F.dstOff + B.dstRel : scratch + F.scratchOff + B.litRel + (u64)B.frame * kLitSkew;
@@ -181,16 +189,17 @@ __device__ __forceinline__ bool streams4(Streams4& S, const u8* hsrc, u32 hlen, 
 
 // slow path: one block per wave, handles everything (incl. 12-bit Huffman tables); only runs for blocks the quad kernels flagged
 // (slowFlags null: every block)
-__global__ __launch_bounds__(64) void decode_literals_slow_kernel(const u8* __restrict__ src, u8* __restrict__ out, u8* __restrict__ scratch,
-                                                                  const FrameDesc* __restrict__ frames, const BlockDesc* __restrict__ blocks, u32 nBlocks,
-                                                                  u32* __restrict__ status, const u8* __restrict__ slowFlags,
-                                                                  const u8* __restrict__ dictFull, const DictInfo* __restrict__ di)
+template <bool kSet>
+__device__ __forceinline__ void decode_literals_slow_body(const u8* __restrict__ src, u8* __restrict__ out, u8* __restrict__ scratch,
+                                                          const FrameDesc* __restrict__ frames, const BlockDesc* __restrict__ blocks, u32 nBlocks,
+                                                          u32* __restrict__ status, const u8* __restrict__ slowFlags, const u8* __restrict__ dictFull,
+                                                          const DictInfo* __restrict__ di, const DictSlot* __restrict__ slots)
 {
     __shared__ LitLds L;
     const u32 bi = blockIdx.x, lane = threadIdx.x;
     if (bi >= nBlocks || (slowFlags && !slowFlags[bi]) || status[kStErr]) return;
     LitJob J;
-    if (!lit_job(J, bi, blocks, frames, src, out, scratch, dictFull, di)) return;
+    if (!lit_job<kSet>(J, bi, blocks, frames, src, out, scratch, dictFull, di, slots)) return;
     u32 err = 0;
     do {
         u32 nbSymbols = 0, tableLog = 0, hs = 0;
@@ -213,6 +222,19 @@ __global__ __launch_bounds__(64) void decode_literals_slow_kernel(const u8* __re
         if (ballot(!ok)) err = kErrCorruption;
     } while (false);
     if (err && lane == 0) report_error(status, bi, kStageLiterals, err);
+}
+__global__ __launch_bounds__(64) void decode_literals_slow_kernel(const u8* __restrict__ src, u8* __restrict__ out, u8* __restrict__ scratch,
+                                                                  const FrameDesc* __restrict__ frames, const BlockDesc* __restrict__ blocks, u32 nBlocks,
+                                                                  u32* __restrict__ status, const u8* __restrict__ slowFlags, const u8* __restrict__ dictFull,
+                                                                  const DictInfo* __restrict__ di)
+{
+    decode_literals_slow_body<false>(src, out, scratch, frames, blocks, nBlocks, status, slowFlags, dictFull, di, nullptr);
+}
+__global__ __launch_bounds__(64) void decode_literals_slow_set_kernel(const u8* __restrict__ src, u8* __restrict__ out, u8* __restrict__ scratch,
+                                                                      const FrameDesc* __restrict__ frames, const BlockDesc* __restrict__ blocks, u32 nBlocks,
+                                                                      u32* __restrict__ status, const u8* __restrict__ slowFlags, const DictSlot* __restrict__ slots)
+{
+    decode_literals_slow_body<true>(src, out, scratch, frames, blocks, nBlocks, status, slowFlags, nullptr, nullptr, slots);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -550,10 +572,11 @@ __device__ u32 quad_decode_literals_c(u16* __restrict__ huf, CompactLds& Q, cons
     return Q.meta[3] ? (u32)kErrCorruption : 0u;
 }
 
-__global__ __launch_bounds__(64) void decode_literals_compact_kernel(const u8* __restrict__ src, u8* __restrict__ out, u8* __restrict__ scratch,
-                                                                     const FrameDesc* __restrict__ frames, const BlockDesc* __restrict__ blocks, u32 nBlocks,
-                                                                     u32* __restrict__ status, u8* __restrict__ slowFlags,
-                                                                     const u8* __restrict__ dictFull, const DictInfo* __restrict__ di)
+template <bool kSet>
+__device__ __forceinline__ void decode_literals_compact_body(const u8* __restrict__ src, u8* __restrict__ out, u8* __restrict__ scratch,
+                                                             const FrameDesc* __restrict__ frames, const BlockDesc* __restrict__ blocks, u32 nBlocks,
+                                                             u32* __restrict__ status, u8* __restrict__ slowFlags, const u8* __restrict__ dictFull,
+                                                             const DictInfo* __restrict__ di, const DictSlot* __restrict__ slots)
 {
     __shared__ __attribute__((aligned(2048))) u16 tables[kQuadsC][1024];
     __shared__ CompactLds Qs[kQuadsC];
@@ -563,18 +586,32 @@ __global__ __launch_bounds__(64) void decode_literals_compact_kernel(const u8* _
     if (ql == 0) slowFlags[bi] = 0;
     if (status[kStErr]) return;
     LitJob J;
-    if (!lit_job(J, bi, blocks, frames, src, out, scratch, dictFull, di)) return;
+    if (!lit_job<kSet>(J, bi, blocks, frames, src, out, scratch, dictFull, di, slots)) return;
     const u32 err = quad_decode_literals_c(tables[q], Qs[q], J, ql);
     if (ql == 0) {
         if (err == 0xFFFFu) slowFlags[bi] = 1;
         else if (err) report_error(status, bi, kStageLiterals, err);
     }
 }
+__global__ __launch_bounds__(64) void decode_literals_compact_kernel(const u8* __restrict__ src, u8* __restrict__ out, u8* __restrict__ scratch,
+                                                                     const FrameDesc* __restrict__ frames, const BlockDesc* __restrict__ blocks, u32 nBlocks,
+                                                                     u32* __restrict__ status, u8* __restrict__ slowFlags, const u8* __restrict__ dictFull,
+                                                                     const DictInfo* __restrict__ di)
+{
+    decode_literals_compact_body<false>(src, out, scratch, frames, blocks, nBlocks, status, slowFlags, dictFull, di, nullptr);
+}
+__global__ __launch_bounds__(64) void decode_literals_compact_set_kernel(const u8* __restrict__ src, u8* __restrict__ out, u8* __restrict__ scratch,
+                                                                         const FrameDesc* __restrict__ frames, const BlockDesc* __restrict__ blocks, u32 nBlocks,
+                                                                         u32* __restrict__ status, u8* __restrict__ slowFlags, const DictSlot* __restrict__ slots)
+{
+    decode_literals_compact_body<true>(src, out, scratch, frames, blocks, nBlocks, status, slowFlags, nullptr, nullptr, slots);
+}
 
-__global__ __launch_bounds__(64) void decode_literals_kernel(const u8* __restrict__ src, u8* __restrict__ out, u8* __restrict__ scratch,
-                                                             const FrameDesc* __restrict__ frames, const BlockDesc* __restrict__ blocks, u32 nBlocks,
-                                                             u32* __restrict__ status, u8* __restrict__ slowFlags,
-                                                             const u8* __restrict__ dictFull, const DictInfo* __restrict__ di)
+template <bool kSet>
+__device__ __forceinline__ void decode_literals_body(const u8* __restrict__ src, u8* __restrict__ out, u8* __restrict__ scratch,
+                                                     const FrameDesc* __restrict__ frames, const BlockDesc* __restrict__ blocks, u32 nBlocks,
+                                                     u32* __restrict__ status, u8* __restrict__ slowFlags, const u8* __restrict__ dictFull,
+                                                     const DictInfo* __restrict__ di, const DictSlot* __restrict__ slots)
 {
     __shared__ __attribute__((aligned(4096))) u16 tables[kQuads][2048];
     __shared__ QuadLds Qs[kQuads];
@@ -584,12 +621,25 @@ __global__ __launch_bounds__(64) void decode_literals_kernel(const u8* __restric
     if (ql == 0) slowFlags[bi] = 0;
     if (status[kStErr]) return;
     LitJob J;
-    if (!lit_job(J, bi, blocks, frames, src, out, scratch, dictFull, di)) return;
+    if (!lit_job<kSet>(J, bi, blocks, frames, src, out, scratch, dictFull, di, slots)) return;
     const u32 err = quad_decode_literals(tables[q], Qs[q], J, ql);
     if (ql == 0) {
         if (err == 0xFFFFu) slowFlags[bi] = 1;
         else if (err) report_error(status, bi, kStageLiterals, err);
     }
+}
+__global__ __launch_bounds__(64) void decode_literals_kernel(const u8* __restrict__ src, u8* __restrict__ out, u8* __restrict__ scratch,
+                                                             const FrameDesc* __restrict__ frames, const BlockDesc* __restrict__ blocks, u32 nBlocks,
+                                                             u32* __restrict__ status, u8* __restrict__ slowFlags, const u8* __restrict__ dictFull,
+                                                             const DictInfo* __restrict__ di)
+{
+    decode_literals_body<false>(src, out, scratch, frames, blocks, nBlocks, status, slowFlags, dictFull, di, nullptr);
+}
+__global__ __launch_bounds__(64) void decode_literals_set_kernel(const u8* __restrict__ src, u8* __restrict__ out, u8* __restrict__ scratch,
+                                                                 const FrameDesc* __restrict__ frames, const BlockDesc* __restrict__ blocks, u32 nBlocks,
+                                                                 u32* __restrict__ status, u8* __restrict__ slowFlags, const DictSlot* __restrict__ slots)
+{
+    decode_literals_body<true>(src, out, scratch, frames, blocks, nBlocks, status, slowFlags, nullptr, nullptr, slots);
 }
 
 // =====================================================================================================================
@@ -870,18 +920,32 @@ __device__ __forceinline__ u32 sync_decode_literals(SyncLds& L, const LitJob& J,
     return L.err ? (u32)kErrCorruption : 0u;
 }
 
-__global__ __launch_bounds__(256) void decode_literals_sync_kernel(const u8* __restrict__ src, u8* __restrict__ out, u8* __restrict__ scratch,
-                                                                   const FrameDesc* __restrict__ frames, const BlockDesc* __restrict__ blocks, u32 nBlocks,
-                                                                   u32* __restrict__ status, const u8* __restrict__ dictFull, const DictInfo* __restrict__ di)
+template <bool kSet>
+__device__ __forceinline__ void decode_literals_sync_body(const u8* __restrict__ src, u8* __restrict__ out, u8* __restrict__ scratch,
+                                                          const FrameDesc* __restrict__ frames, const BlockDesc* __restrict__ blocks, u32 nBlocks,
+                                                          u32* __restrict__ status, const u8* __restrict__ dictFull, const DictInfo* __restrict__ di,
+                                                          const DictSlot* __restrict__ slots)
 {
     extern __shared__ __attribute__((aligned(16))) u8 syncLdsRaw[];
     SyncLds& L = *reinterpret_cast<SyncLds*>(syncLdsRaw);
     const u32 bi = blockIdx.x, tid = threadIdx.x;
     if (bi >= nBlocks || status[kStErr]) return;
     LitJob J;
-    if (!lit_job(J, bi, blocks, frames, src, out, scratch, dictFull, di)) return;
+    if (!lit_job<kSet>(J, bi, blocks, frames, src, out, scratch, dictFull, di, slots)) return;
     const u32 err = sync_decode_literals(L, J, tid);
     if (err && tid == 0) report_error(status, bi, kStageLiterals, err);
+}
+__global__ __launch_bounds__(256) void decode_literals_sync_kernel(const u8* __restrict__ src, u8* __restrict__ out, u8* __restrict__ scratch,
+                                                                   const FrameDesc* __restrict__ frames, const BlockDesc* __restrict__ blocks, u32 nBlocks,
+                                                                   u32* __restrict__ status, const u8* __restrict__ dictFull, const DictInfo* __restrict__ di)
+{
+    decode_literals_sync_body<false>(src, out, scratch, frames, blocks, nBlocks, status, dictFull, di, nullptr);
+}
+__global__ __launch_bounds__(256) void decode_literals_sync_set_kernel(const u8* __restrict__ src, u8* __restrict__ out, u8* __restrict__ scratch,
+                                                                       const FrameDesc* __restrict__ frames, const BlockDesc* __restrict__ blocks, u32 nBlocks,
+                                                                       u32* __restrict__ status, const DictSlot* __restrict__ slots)
+{
+    decode_literals_sync_body<true>(src, out, scratch, frames, blocks, nBlocks, status, nullptr, nullptr, slots);
 }
 
 // Three literal decoders (tools/lit_decoder_crossover.py, MI355X, 64 KiB Zipf frames):
@@ -890,7 +954,8 @@ __global__ __launch_bounds__(256) void decode_literals_sync_kernel(const u8* __r
 //   selfsync (256 lanes per block): 0.15 ms up to 256 blocks, 0.25 ms per 1000 blocks beyond.
 // mode: 0 = choose by block count, 1 = serial, 2 = self-synchronising, 3 = compact.
 void launch_decode_literals(const u8* src, u8* out, u8* scratch, const FrameDesc* frames, const BlockDesc* blocks, u32 nBlocks, u32* status,
-                            u8* slowFlags, u32 mode, const u8* dictFull, const DictInfo* di, hipStream_t stream, StageHook hook)
+                            u8* slowFlags, u32 mode, const u8* dictFull, const DictInfo* di, hipStream_t stream, StageHook hook,
+                            const DictSlot* slots)
 {
     if (mode == 0) {
         static int cus[64] = {};                     // per device
@@ -907,8 +972,21 @@ void launch_decode_literals(const u8* src, u8* out, u8* scratch, const FrameDesc
         static bool attrSet[64] = {};               // per device
         int dev = 0; (void)hipGetDevice(&dev);
         if (!attrSet[dev & 63]) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(decode_literals_sync_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(SyncLds)); attrSet[dev & 63] = true; }
+        if (slots) {
+            static bool attrSetS[64] = {};
+            if (!attrSetS[dev & 63]) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(decode_literals_sync_set_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(SyncLds)); attrSetS[dev & 63] = true; }
+            hipLaunchKernelGGL(decode_literals_sync_set_kernel, dim3(nBlocks), dim3(256), sizeof(SyncLds), stream, src, out, scratch, frames, blocks, nBlocks, status, slots);
+        } else
         hipLaunchKernelGGL(decode_literals_sync_kernel, dim3(nBlocks), dim3(256), sizeof(SyncLds), stream, src, out, scratch, frames, blocks, nBlocks, status, dictFull, di);
         hook("decode_literals");
+        return;
+    }
+    if (slots) {
+        if (mode == 3) hipLaunchKernelGGL(decode_literals_compact_set_kernel, dim3((nBlocks + kQuadsC - 1) / kQuadsC), dim3(64), 0, stream, src, out, scratch, frames, blocks, nBlocks, status, slowFlags, slots);
+        else           hipLaunchKernelGGL(decode_literals_set_kernel, dim3((nBlocks + kQuads - 1) / kQuads), dim3(64), 0, stream, src, out, scratch, frames, blocks, nBlocks, status, slowFlags, slots);
+        hook("decode_literals");
+        hipLaunchKernelGGL(decode_literals_slow_set_kernel, dim3(nBlocks), dim3(64), 0, stream, src, out, scratch, frames, blocks, nBlocks, status, (const u8*)slowFlags, slots);
+        hook("decode_literals_slow");
         return;
     }
     if (mode == 3) hipLaunchKernelGGL(decode_literals_compact_kernel, dim3((nBlocks + kQuadsC - 1) / kQuadsC), dim3(64), 0, stream, src, out, scratch, frames, blocks, nBlocks, status, slowFlags, dictFull, di);

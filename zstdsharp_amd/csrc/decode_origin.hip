@@ -59,11 +59,16 @@ __global__ __launch_bounds__(256) void origin_fill_kernel(const FrameDesc* __res
 }
 
 // the match bytes' first origins: one wave per block, 64 sequences at a time, the batch's match bytes dealt to the lanes in order
-__global__ __launch_bounds__(256) void origin_init_kernel(const FrameDesc* __restrict__ frames, const BlockDesc* __restrict__ blocks, const u32* __restrict__ list,
-                                                          const SeqRec* __restrict__ recs, u32* __restrict__ status, u32* __restrict__ origin, const u32 dictSize)
+// kSet (ZSTD_d_refMultipleDDicts with two or more DDicts in the set): the dictionary in front of the frame is its own,
+// slots[F.dictSlot]; a workgroup has one frame (blockIdx.y), so dictSize is uniform for it
+template <bool kSet>
+__device__ __forceinline__ void origin_init_body(const FrameDesc* __restrict__ frames, const BlockDesc* __restrict__ blocks, const u32* __restrict__ list,
+                                                 const SeqRec* __restrict__ recs, u32* __restrict__ status, u32* __restrict__ origin, u32 dictSize,
+                                                 const DictSlot* __restrict__ slots)
 {
     if (blockIdx.y >= status[kStOriginFrames]) return;
     const FrameDesc& F = frames[list[blockIdx.y]];
+    if constexpr (kSet) { const DictSlot& D = slots[uniform(F.dictSlot)]; dictSize = uniform64((u64)D.content) ? uniform(D.contentSize) : 0u; }
     u32* __restrict__ const P = origin + F.originOff;
     const u32 lane = lane_id(), first = uniform(F.firstBlock), nb = uniform(F.nbBlocks);
     for (u32 k = blockIdx.x * 4 + uniform(wave_id()); k < nb; k += gridDim.x * 4) {
@@ -103,6 +108,17 @@ __global__ __launch_bounds__(256) void origin_init_kernel(const FrameDesc* __res
             }
         }
     }
+}
+__global__ __launch_bounds__(256) void origin_init_kernel(const FrameDesc* __restrict__ frames, const BlockDesc* __restrict__ blocks, const u32* __restrict__ list,
+                                                          const SeqRec* __restrict__ recs, u32* __restrict__ status, u32* __restrict__ origin, const u32 dictSize)
+{
+    origin_init_body<false>(frames, blocks, list, recs, status, origin, dictSize, nullptr);
+}
+__global__ __launch_bounds__(256) void origin_init_set_kernel(const FrameDesc* __restrict__ frames, const BlockDesc* __restrict__ blocks, const u32* __restrict__ list,
+                                                              const SeqRec* __restrict__ recs, u32* __restrict__ status, u32* __restrict__ origin,
+                                                              const DictSlot* __restrict__ slots)
+{
+    origin_init_body<true>(frames, blocks, list, recs, status, origin, 0, slots);
 }
 
 // one round of origin[i] = origin[origin[i]]; four entries per thread, 1024 per workgroup and step = one REGION.
@@ -156,12 +172,15 @@ __global__ __launch_bounds__(256) void origin_jump_kernel(const FrameDesc* __res
 }
 
 // out[i] = out[origin[i]]; four bytes per thread
-__global__ __launch_bounds__(256) void origin_gather_kernel(const FrameDesc* __restrict__ frames, const u32* __restrict__ list, const u32* __restrict__ status,
-                                                            const u32* __restrict__ origin, u8* __restrict__ out, const u8* __restrict__ dict)
+template <bool kSet>
+__device__ __forceinline__ void origin_gather_body(const FrameDesc* __restrict__ frames, const u32* __restrict__ list, const u32* __restrict__ status,
+                                                   const u32* __restrict__ origin, u8* __restrict__ out, const u8* __restrict__ dict,
+                                                   const DictSlot* __restrict__ slots)
 {
     if (blockIdx.y >= status[kStOriginFrames] || status[kStErr]) return;
     const FrameDesc& F = frames[list[blockIdx.y]];
     if (F.bad) return;
+    if constexpr (kSet) dict = reinterpret_cast<const u8*>(uniform64((u64)slots[uniform(F.dictSlot)].content));     // (one frame per workgroup)
     const u32* __restrict__ const P = origin + F.originOff;
     u8* const fout = out + F.dstOff;
     const u32 n = (u32)F.dstSize, n4 = (n + 3) >> 2;
@@ -186,6 +205,16 @@ __global__ __launch_bounds__(256) void origin_gather_kernel(const FrameDesc* __r
         }
     }
 }
+__global__ __launch_bounds__(256) void origin_gather_kernel(const FrameDesc* __restrict__ frames, const u32* __restrict__ list, const u32* __restrict__ status,
+                                                            const u32* __restrict__ origin, u8* __restrict__ out, const u8* __restrict__ dict)
+{
+    origin_gather_body<false>(frames, list, status, origin, out, dict, nullptr);
+}
+__global__ __launch_bounds__(256) void origin_gather_set_kernel(const FrameDesc* __restrict__ frames, const u32* __restrict__ list, const u32* __restrict__ status,
+                                                                const u32* __restrict__ origin, u8* __restrict__ out, const DictSlot* __restrict__ slots)
+{
+    origin_gather_body<true>(frames, list, status, origin, out, nullptr, slots);
+}
 
 void launch_origin_select(FrameDesc* frames, u32 nFrames, u64 minBytes, u32* list, u32 listCap, u64 originCap, u32* status, hipStream_t stream)
 {
@@ -207,13 +236,14 @@ static dim3 origin_grid(u64 maxFrameBytes, u32 listCap)
 }
 // select + fill + init (queued behind block_offsets; the literals are not needed yet)
 void launch_origin_init(const FrameDesc* frames, const BlockDesc* blocks, const u32* list, u32 listCap, u64 maxFrameBytes, const SeqRec* recs, u32* status,
-                        u32* origin, u32 dictSize, hipStream_t stream)
+                        u32* origin, u32 dictSize, hipStream_t stream, const DictSlot* slots)
 {
     const dim3 grid = origin_grid(maxFrameBytes, listCap), tb(256);
     u64 bw = (maxFrameBytes / (128u << 10) + 4) / 4;             // one wave per block of 128 KiB
     if (bw > 4096) bw = 4096;
     hipLaunchKernelGGL(origin_fill_kernel, grid, tb, 0, stream, frames, list, (const u32*)status, origin);
-    hipLaunchKernelGGL(origin_init_kernel, dim3((u32)bw, listCap), tb, 0, stream, frames, blocks, list, recs, status, origin, dictSize);
+    if (slots) hipLaunchKernelGGL(origin_init_set_kernel, dim3((u32)bw, listCap), tb, 0, stream, frames, blocks, list, recs, status, origin, slots);
+    else hipLaunchKernelGGL(origin_init_kernel, dim3((u32)bw, listCap), tb, 0, stream, frames, blocks, list, recs, status, origin, dictSize);
 }
 // rounds [r0, r1) of the pointer jumping; done: one word per 1024 origins, any contents before round 0
 void launch_origin_jump(const FrameDesc* frames, const u32* list, u32 listCap, u64 maxFrameBytes, u32* status, u32* origin, u32* done, u32 r0, u32 r1, hipStream_t stream)
@@ -221,9 +251,11 @@ void launch_origin_jump(const FrameDesc* frames, const u32* list, u32 listCap, u
     const dim3 grid = origin_grid(maxFrameBytes, listCap), tb(256);
     for (u32 r = r0; r < r1 && r < kOriginRounds; ++r) hipLaunchKernelGGL(origin_jump_kernel, grid, tb, 0, stream, frames, list, status, origin, done, r);
 }
-void launch_origin_gather(const FrameDesc* frames, const u32* list, u32 listCap, u64 maxFrameBytes, const u32* status, const u32* origin, u8* out, const u8* dict, hipStream_t stream)
+void launch_origin_gather(const FrameDesc* frames, const u32* list, u32 listCap, u64 maxFrameBytes, const u32* status, const u32* origin, u8* out, const u8* dict, hipStream_t stream,
+                          const DictSlot* slots)
 {
-    hipLaunchKernelGGL(origin_gather_kernel, origin_grid(maxFrameBytes, listCap), dim3(256), 0, stream, frames, list, status, origin, out, dict);
+    if (slots) hipLaunchKernelGGL(origin_gather_set_kernel, origin_grid(maxFrameBytes, listCap), dim3(256), 0, stream, frames, list, status, origin, out, slots);
+    else hipLaunchKernelGGL(origin_gather_kernel, origin_grid(maxFrameBytes, listCap), dim3(256), 0, stream, frames, list, status, origin, out, dict);
 }
 
 } // namespace zmi

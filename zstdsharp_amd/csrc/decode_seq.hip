@@ -237,10 +237,14 @@ __device__ __forceinline__ void seq_fields_batch(const SeqLds& L, u32 buf, u32 s
 // references a DDict over a formatted dictionary) takes a table a block repeats from the dictionary out of the DDict's ready-made image
 // (dictTabs, launch_dict_seq_tables) — a coalesced copy of 1 << log words that every workgroup reads from L2 — instead of parsing the
 // description and building the table again; a description that does not parse never becomes a DDict, so the copy has no error branch.
-template <bool kReady>
+// kSet (with kReady; ZSTD_d_refMultipleDDicts with two or more DDicts in the set): the dictionary is the one of the block's own frame,
+// slots[frames[B.frame].dictSlot].  Phase A gives a wave ONE (block, table) task at a time, so what it reads of the record is
+// wave-uniform per task although the workgroup's kPack blocks may sit behind kPack dictionaries; phases B and C read no dictionary.
+template <bool kReady, bool kSet = false>
 __device__ __forceinline__ void seq_decode_body(const u8* __restrict__ src, const FrameDesc* __restrict__ frames, BlockDesc* __restrict__ blocks,
                                                 u32 nBlocks, SeqRec* __restrict__ recs, u32* __restrict__ status,
-                                                const u8* __restrict__ dictFull, const DictInfo* __restrict__ di, const u32* __restrict__ dictTabs)
+                                                const u8* __restrict__ dictFull, const DictInfo* __restrict__ di, const u32* __restrict__ dictTabs,
+                                                const DictSlot* __restrict__ slots = nullptr)
 {
     __shared__ SeqLds L;
     const u32 lane = lane_id(), wave = uniform(wave_id()), b0 = blockIdx.x * kPack;
@@ -258,6 +262,9 @@ __device__ __forceinline__ void seq_decode_body(const u8* __restrict__ src, cons
                 const u32 s = uniform(B.tblSrc[t]);
                 bool ready = false;
                 if constexpr (kReady) ready = s == kDictBlock;
+                if constexpr (kSet) {
+                    if (ready) dictTabs = reinterpret_cast<const u32*>(uniform64((u64)slots[uniform(frames[uniform(B.frame)].dictSlot)].seqTabs));
+                }
                 if (ready) {                                        // the table is there: 1 << log packed entries (log >= 5), 16 bytes a lane and round
                     const u32 at = t == 0 ? kTabLL : t == 1 ? kTabOF : kTabML;
                     res = uniform(dictTabs[kDictTabLogs + t]);
@@ -447,12 +454,18 @@ __global__ __launch_bounds__(256) void seq_decode_ready_kernel(const u8* __restr
 {
     seq_decode_body<true>(src, frames, blocks, nBlocks, recs, status, dictFull, di, dictTabs);
 }
+__global__ __launch_bounds__(256) void seq_decode_set_kernel(const u8* __restrict__ src, const FrameDesc* __restrict__ frames, BlockDesc* __restrict__ blocks,
+                                                             u32 nBlocks, SeqRec* __restrict__ recs, u32* __restrict__ status, const DictSlot* __restrict__ slots)
+{
+    seq_decode_body<true, true>(src, frames, blocks, nBlocks, recs, status, nullptr, nullptr, nullptr, slots);
+}
 
 void launch_seq_decode(const u8* src, const FrameDesc* frames, BlockDesc* blocks, u32 nBlocks, SeqRec* recs, u32* status,
-                       const u8* dictFull, const DictInfo* di, const u32* dictTabs, hipStream_t stream)
+                       const u8* dictFull, const DictInfo* di, const u32* dictTabs, hipStream_t stream, const DictSlot* slots)
 {
     const dim3 grid((nBlocks + kPack - 1) / kPack);
-    if (dictTabs) hipLaunchKernelGGL(seq_decode_ready_kernel, grid, dim3(256), 0, stream, src, frames, blocks, nBlocks, recs, status, dictFull, di, dictTabs);
+    if (slots) hipLaunchKernelGGL(seq_decode_set_kernel, grid, dim3(256), 0, stream, src, frames, blocks, nBlocks, recs, status, slots);
+    else if (dictTabs) hipLaunchKernelGGL(seq_decode_ready_kernel, grid, dim3(256), 0, stream, src, frames, blocks, nBlocks, recs, status, dictFull, di, dictTabs);
     else          hipLaunchKernelGGL(seq_decode_kernel, grid, dim3(256), 0, stream, src, frames, blocks, nBlocks, recs, status, dictFull, di);
 }
 
@@ -582,14 +595,25 @@ void launch_place_literals(const u8* src, u8* out, const u8* scratch, const Fram
 // ------------------------------------------------------------------------------------------------
 // exec_matches: the ordered stage, one wave per frame
 // ------------------------------------------------------------------------------------------------
+// kSet (ZSTD_d_refMultipleDDicts with two or more DDicts in the set): `dictArg` is the slot table, and the history in front of the frame
+// is its own dictionary's content, slots[F.dictSlot].  A workgroup has one frame, so dict and dictSize stay uniform for it — per frame,
+// no longer per launch.  kSet = false is the kernel as it always was.  (The kernels themselves are the templates, not wrappers around
+// an inlined body: inlining turns the arguments' __restrict__ into scoped metadata, and the register allocation of the parent's
+// instances moved with it.)
+template <bool kSet>
 __global__ __launch_bounds__(64) void exec_matches_kernel(const u8* __restrict__ src, u8* __restrict__ out, const FrameDesc* __restrict__ frames,
                                                           const BlockDesc* __restrict__ blocks, u32 nFrames, const SeqRec* __restrict__ recs,
-                                                          u32* __restrict__ status, const u8* __restrict__ dict, const u32 dictSize)
+                                                          u32* __restrict__ status, const u8* __restrict__ dictArg, const u32 dictSizeArg)
 {
     const u32 f = blockIdx.x, lane = threadIdx.x;
     if (f >= nFrames || status[kStErr]) return;
     const FrameDesc& F = frames[f];
     if (F.bad || !(F.hasSeq || F.checksum)) return;
+    const u8* __restrict__ dict = dictArg; u32 dictSize = dictSizeArg;
+    if constexpr (kSet) {
+        const DictSlot& D = reinterpret_cast<const DictSlot*>(dictArg)[uniform(F.dictSlot)];
+        dict = reinterpret_cast<const u8*>(uniform64((u64)D.content)); dictSize = dict ? uniform(D.contentSize) : 0u;
+    }
     const bool viaOrigin = uniform(F.viaOrigin) != 0;           // its matches are in place already (decode_origin.hip): the checksum is what is left
     if (viaOrigin && !F.checksum) return;
     u8* const fout = out + F.dstOff;
@@ -636,6 +660,10 @@ __global__ __launch_bounds__(64) void exec_matches_kernel(const u8* __restrict__
                 if (have && (u64)off > bRel + dMatch) {
                     back = (u32)((u64)off - (bRel + dMatch));
                     dictN = back < ml ? back : ml;
+                    // (kSet: `dict` is a loaded value, which the compiler cannot prove distinct from the output as it can the twin's
+                    // __restrict__ argument: the byte loop would wait for every load before its store.  lane_copy states the order itself.)
+                    if constexpr (kSet) { if (dictN <= 64) lane_copy(o + dMatch, dict + (dictSize - back), dictN); }
+                    else
                     if (dictN <= 64) { const u8* ds = dict + (dictSize - back); for (u32 i = 0; i < dictN; i++) o[dMatch + i] = ds[i]; }
                 }
                 u64 dm = ballot(dictN > 64);
@@ -730,10 +758,10 @@ __global__ __launch_bounds__(64) void exec_matches_kernel(const u8* __restrict__
 // touches (an index interval, found by binary search over the batch's bounds in LDS), a round runs every match whose interval is
 // complete.  The done bits are double-buffered by round parity, so one barrier per round is enough.
 // ------------------------------------------------------------------------------------------------
-template <int W>
+template <int W, bool kSet = false>
 __global__ __launch_bounds__(64 * W) void exec_matches_wide_kernel(const u8* __restrict__ src, u8* __restrict__ out, const FrameDesc* __restrict__ frames,
                                                                    const BlockDesc* __restrict__ blocks, u32 nFrames, const SeqRec* __restrict__ recs,
-                                                                   u32* __restrict__ status, const u8* __restrict__ dict, const u32 dictSize)
+                                                                   u32* __restrict__ status, const u8* __restrict__ dictArg, const u32 dictSizeArg)
 {
     constexpr u32 kB = 64u * W;                                  // sequences per batch
     __shared__ u32 endOfOut[kB], startOfOut[kB];                 // block-relative bounds of the batch's match outputs (monotone; 0xFFFFFFFF: no sequence)
@@ -744,6 +772,11 @@ __global__ __launch_bounds__(64 * W) void exec_matches_wide_kernel(const u8* __r
     if (f >= nFrames || status[kStErr]) return;
     const FrameDesc& F = frames[f];
     if (F.bad || !(F.hasSeq || F.checksum)) return;
+    const u8* __restrict__ dict = dictArg; u32 dictSize = dictSizeArg;
+    if constexpr (kSet) {       // (as in exec_matches_kernel: the slot table, one frame per workgroup)
+        const DictSlot& D = reinterpret_cast<const DictSlot*>(dictArg)[uniform(F.dictSlot)];
+        dict = reinterpret_cast<const u8*>(uniform64((u64)D.content)); dictSize = dict ? uniform(D.contentSize) : 0u;
+    }
     const bool viaOrigin = uniform(F.viaOrigin) != 0;
     if (viaOrigin && !F.checksum) return;
     u8* const fout = out + F.dstOff;
@@ -788,6 +821,10 @@ __global__ __launch_bounds__(64 * W) void exec_matches_wide_kernel(const u8* __r
                 if (have && (u64)off > bRel + dMatch && (u64)off <= bRel + dMatch + dictSize) {
                     back = (u32)((u64)off - (bRel + dMatch));
                     dictN = back < ml ? back : ml;
+                    // (kSet: `dict` is a loaded value, which the compiler cannot prove distinct from the output as it can the twin's
+                    // __restrict__ argument: the byte loop would wait for every load before its store.  lane_copy states the order itself.)
+                    if constexpr (kSet) { if (dictN <= 64) lane_copy(o + dMatch, dict + (dictSize - back), dictN); }
+                    else
                     if (dictN <= 64) { const u8* ds = dict + (dictSize - back); for (u32 i = 0; i < dictN; i++) o[dMatch + i] = ds[i]; }
                 }
                 u64 dm = ballot(dictN > 64);
@@ -889,8 +926,20 @@ __global__ __launch_bounds__(64 * W) void exec_matches_wide_kernel(const u8* __r
 // 16 waves 2.4; 1024 frames: 6.8 / 5.5 / 4.3 / 5.7 / 7.3 at 1 / 2 / 4 / 8 / 16; 2048 frames: 8.3 / 6.5 / 8.0 at 1 / 2 / 4; 4096
 // frames: 9.8 / 12.3 at 1 / 2 — i.e. as many waves as keep frames x waves at about 4096 (the caller's rule, decompress_device)
 void launch_exec_matches(const u8* src, u8* out, const FrameDesc* frames, const BlockDesc* blocks, u32 nFrames, const SeqRec* recs, u32* status,
-                         const u8* dict, u32 dictSize, hipStream_t stream, int wide)
+                         const u8* dict, u32 dictSize, hipStream_t stream, int wide, const DictSlot* slots)
 {
+    if (slots) {                // the set instances: the slot table rides in the dictionary pointer's place
+        const u8* const tab = reinterpret_cast<const u8*>(slots);
+        switch (wide) {
+        case 16: hipLaunchKernelGGL((exec_matches_wide_kernel<16, true>), dim3(nFrames), dim3(1024), 0, stream, src, out, frames, blocks, nFrames, recs, status, tab, 0u); return;
+        case 8:  hipLaunchKernelGGL((exec_matches_wide_kernel<8, true>),  dim3(nFrames), dim3(512),  0, stream, src, out, frames, blocks, nFrames, recs, status, tab, 0u); return;
+        case 4:  hipLaunchKernelGGL((exec_matches_wide_kernel<4, true>),  dim3(nFrames), dim3(256),  0, stream, src, out, frames, blocks, nFrames, recs, status, tab, 0u); return;
+        case 2:  hipLaunchKernelGGL((exec_matches_wide_kernel<2, true>),  dim3(nFrames), dim3(128),  0, stream, src, out, frames, blocks, nFrames, recs, status, tab, 0u); return;
+        default: break;
+        }
+        hipLaunchKernelGGL(exec_matches_kernel<true>, dim3(nFrames), dim3(64), 0, stream, src, out, frames, blocks, nFrames, recs, status, tab, 0u);
+        return;
+    }
     const u32 ds = dict ? dictSize : 0u;
     switch (wide) {
     case 16: hipLaunchKernelGGL(exec_matches_wide_kernel<16>, dim3(nFrames), dim3(1024), 0, stream, src, out, frames, blocks, nFrames, recs, status, dict, ds); return;
@@ -901,7 +950,7 @@ void launch_exec_matches(const u8* src, u8* out, const FrameDesc* frames, const 
     }
     // dict: a raw-content dictionary (or a formatted one's content) = history in front of EVERY frame (ZSTD_refDictContent,
     // U/ZstdDecompress.cs:1758-1771); may be null
-    hipLaunchKernelGGL(exec_matches_kernel, dim3(nFrames), dim3(64), 0, stream, src, out, frames, blocks, nFrames, recs, status, dict, dict ? dictSize : 0u);
+    hipLaunchKernelGGL(exec_matches_kernel<false>, dim3(nFrames), dim3(64), 0, stream, src, out, frames, blocks, nFrames, recs, status, dict, dict ? dictSize : 0u);
 }
 
 } // namespace zmi

@@ -83,26 +83,39 @@ __device__ inline u32 emit_frame(const u8* __restrict__ src, u64 srcSize, u64 po
     const u32 st = chain_step_t<true>(src, srcSize, pos, o, frameIdx, firstBlock, blocks);
     if (st) return st;
     FrameDesc f; f.srcOff = pos; f.dstOff = dstOff; f.scratchOff = dstOff; f.srcSize = o.next - pos; f.dstSize = o.content;
-    f.firstBlock = firstBlock; f.nbBlocks = o.nbBlocks; f.unsized = o.unsized; f.checksum = o.checksum; f.bad = 0; f.hasSeq = 0; f.viaOrigin = 0; f.pad = 0; f.originOff = 0;
+    f.firstBlock = firstBlock; f.nbBlocks = o.nbBlocks; f.unsized = o.unsized; f.checksum = o.checksum; f.bad = 0; f.hasSeq = 0; f.viaOrigin = 0; f.dictSlot = 0; f.originOff = 0;
     frames[frameIdx] = f;
     return 0;
 }
 
 // the exact serial walk (ZSTD_decompressMultiFrame's loop, U/ZstdDecompress.cs:1216-1315), one lane.  emit = 0: count frames and
 // blocks, sum the content sizes, find the first error; emit = 1 (same input, lists allocated): write the lists.
-__global__ void frame_walk_serial_kernel(const u8* __restrict__ src, u64 srcSize, FrameDesc* __restrict__ frames, BlockDesc* __restrict__ blocks,
-                                         u32 maxFrames, u32* __restrict__ status, u32 dictID, u32 emit)
+// kSet (ZSTD_d_refMultipleDDicts with two or more DDicts in the set): a frame's dictID is looked up in the slot table (dictset_select,
+// zmi_dictset.h: nSet sorted records, the current DDict's behind them), the record's index goes into the frame's descriptor, and the
+// frames found in the set are counted into the status words.  kSet = false is the kernel as it always was.
+template <bool kSet>
+__device__ __forceinline__ void frame_walk_serial_body(const u8* __restrict__ src, u64 srcSize, FrameDesc* __restrict__ frames, BlockDesc* __restrict__ blocks,
+                                                       u32 maxFrames, u32* __restrict__ status, u32 dictID, u32 emit, const DictSlot* __restrict__ slots, u32 nSet)
 {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    u64 pos = 0, dstOff = 0; u32 n = 0, err = 0, nUnsized = 0; u64 nBlocks = 0;
+    u64 pos = 0, dstOff = 0; u32 n = 0, err = 0, nUnsized = 0; u64 nBlocks = 0; u32 nInSet = 0;
     while (srcSize - pos >= 5) {            // ZSTD_decompressMultiFrame loop condition (U/ZstdDecompress.cs:1228)
         ChainOut o;
         // (emit: the same input has been through the counting pass, which stopped at the first error and sized the lists)
         const u32 st = emit ? emit_frame(src, srcSize, pos, o, n, (u32)nBlocks, dstOff, frames, blocks) : chain_step(src, srcSize, pos, o);
         if (st == 1) { pos = o.next; continue; }
         if (st) { err = (st == kErrPrefixUnknown && n > 0) ? (u32)kErrSrcSizeWrong : st; break; }
-        if (o.dictID && o.dictID != dictID) { err = kErrDictionaryWrong; break; }       // U/ZstdDecompress.cs:1404-1412 (dictID 0 = none loaded)
-        if (n >= maxFrames || nBlocks + o.nbBlocks > 0xFFFFFFF0ull) { err = kErrMemoryAllocation; break; }
+        if constexpr (kSet) {
+            u32 inSet, wrong;
+            const u32 slot = dictset_select(slots, nSet, o.dictID, &inSet, &wrong);
+            if (wrong) { err = kErrDictionaryWrong; break; }
+            if (n >= maxFrames || nBlocks + o.nbBlocks > 0xFFFFFFF0ull) { err = kErrMemoryAllocation; break; }
+            if (emit) frames[n].dictSlot = slot;            // (emit_frame has just written frames[n])
+            nInSet += inSet;
+        } else {
+            if (o.dictID && o.dictID != dictID) { err = kErrDictionaryWrong; break; }       // U/ZstdDecompress.cs:1404-1412 (dictID 0 = none loaded)
+            if (n >= maxFrames || nBlocks + o.nbBlocks > 0xFFFFFFF0ull) { err = kErrMemoryAllocation; break; }
+        }
         n++; nUnsized += o.unsized; nBlocks += o.nbBlocks;
         dstOff += o.content; pos = o.next;
     }
@@ -110,6 +123,17 @@ __global__ void frame_walk_serial_kernel(const u8* __restrict__ src, u64 srcSize
     if (emit) return;
     status[kStFrames] = n; status[kStErr] = err; status[kStTotalLo] = (u32)dstOff; status[kStTotalHi] = (u32)(dstOff >> 32);
     status[kStUnsized] = nUnsized; status[kStBlocks] = (u32)nBlocks;
+    if constexpr (kSet) status[kStSetFrames] = err ? 0u : nInSet;
+}
+__global__ void frame_walk_serial_kernel(const u8* __restrict__ src, u64 srcSize, FrameDesc* __restrict__ frames, BlockDesc* __restrict__ blocks,
+                                         u32 maxFrames, u32* __restrict__ status, u32 dictID, u32 emit)
+{
+    frame_walk_serial_body<false>(src, srcSize, frames, blocks, maxFrames, status, dictID, emit, nullptr, 0);
+}
+__global__ void frame_walk_serial_set_kernel(const u8* __restrict__ src, u64 srcSize, FrameDesc* __restrict__ frames, BlockDesc* __restrict__ blocks,
+                                             u32 maxFrames, u32* __restrict__ status, u32 emit, const DictSlot* __restrict__ slots, u32 nSet)
+{
+    frame_walk_serial_body<true>(src, srcSize, frames, blocks, maxFrames, status, 0, emit, slots, nSet);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -341,8 +365,10 @@ __global__ __launch_bounds__(256) void walk_emit_kernel(const u8* __restrict__ s
 // frames, trailing garbage, a dictID that is not the loaded one — in count-then-emit form like the walks above
 // ------------------------------------------------------------------------------------------------
 // count: what frame_walk_serial_kernel's counting pass and the host's checks behind it make of the entry
-__global__ __launch_bounds__(64) void batch_walk_count_kernel(const u8* __restrict__ src, const BatchEntryIn* __restrict__ in, BatchEntryOut* __restrict__ out, u32 nEntries,
-                                                              u32 dictID, u64 aloneAbove)
+// kSet: as in frame_walk_serial_body; the frames found in the set are counted for the entries that are decoded here
+template <bool kSet>
+__device__ __forceinline__ void batch_walk_count_body(const u8* __restrict__ src, const BatchEntryIn* __restrict__ in, BatchEntryOut* __restrict__ out, u32 nEntries,
+                                                      u32 dictID, u64 aloneAbove, const DictSlot* __restrict__ slots, u32 nSet, u32* __restrict__ status)
 {
     const u32 e = blockIdx.x * 64 + threadIdx.x;
     if (e >= nEntries) return;
@@ -351,13 +377,18 @@ __global__ __launch_bounds__(64) void batch_walk_count_kernel(const u8* __restri
     if (E.srcSize > aloneAbove) { r.state = kBatchAlone; out[e] = r; return; }
     const u64 end = E.srcOff + E.srcSize;
     const u32 maxFrames = (u32)((E.srcSize / 9 + 1) < (1u << 26) ? (E.srcSize / 9 + 1) : (1u << 26));
-    u64 pos = E.srcOff, content = 0, nBlocks = 0; u32 n = 0, err = 0, nUnsized = 0;
+    u64 pos = E.srcOff, content = 0, nBlocks = 0; u32 n = 0, err = 0, nUnsized = 0, nInSet = 0;
     while (end - pos >= 5) {
         ChainOut o;
         const u32 st = chain_step(src, end, pos, o);
         if (st == 1) { pos = o.next; continue; }
         if (st) { err = (st == kErrPrefixUnknown && n > 0) ? (u32)kErrSrcSizeWrong : st; break; }
-        if (o.dictID && o.dictID != dictID) { err = kErrDictionaryWrong; break; }
+        if constexpr (kSet) {
+            u32 inSet, wrong;
+            (void)dictset_select(slots, nSet, o.dictID, &inSet, &wrong);
+            if (wrong) { err = kErrDictionaryWrong; break; }
+            nInSet += inSet;
+        } else if (o.dictID && o.dictID != dictID) { err = kErrDictionaryWrong; break; }
         if (n >= maxFrames || nBlocks + o.nbBlocks > 0xFFFFFFF0ull) { err = kErrMemoryAllocation; break; }
         n++; nUnsized += o.unsized; nBlocks += o.nbBlocks;
         content += o.content; pos = o.next;
@@ -368,6 +399,17 @@ __global__ __launch_bounds__(64) void batch_walk_count_kernel(const u8* __restri
     else if (content > E.dstCap) { r.state = kBatchDone; r.result = (u64)0 - (u64)kErrDstSizeTooSmall; }
     else { r.state = kBatchDecode; r.result = content; r.nFrames = n; r.nBlocks = (u32)nBlocks; }
     out[e] = r;
+    if constexpr (kSet) { if (r.state == kBatchDecode && nInSet) atomicAdd(status + kStSetFrames, nInSet); }
+}
+__global__ __launch_bounds__(64) void batch_walk_count_kernel(const u8* __restrict__ src, const BatchEntryIn* __restrict__ in, BatchEntryOut* __restrict__ out, u32 nEntries,
+                                                              u32 dictID, u64 aloneAbove)
+{
+    batch_walk_count_body<false>(src, in, out, nEntries, dictID, aloneAbove, nullptr, 0, nullptr);
+}
+__global__ __launch_bounds__(64) void batch_walk_count_set_kernel(const u8* __restrict__ src, const BatchEntryIn* __restrict__ in, BatchEntryOut* __restrict__ out, u32 nEntries,
+                                                                  u64 aloneAbove, const DictSlot* __restrict__ slots, u32 nSet, u32* __restrict__ status)
+{
+    batch_walk_count_body<true>(src, in, out, nEntries, 0, aloneAbove, slots, nSet, status);
 }
 
 // scan (single workgroup): every decoded entry's first frame, first block and literal-scratch offset; the totals go to the status
@@ -404,8 +446,9 @@ __global__ __launch_bounds__(256) void batch_scan_kernel(BatchEntryOut* __restri
 
 // emit: the same walk again, into the lists.  A frame's content goes to the entry's destination plus the frame's place inside the
 // entry; its literal scratch is the scratch prefix sum (in a single call both are the same number; here they are not)
-__global__ __launch_bounds__(64) void batch_walk_emit_kernel(const u8* __restrict__ src, const BatchEntryIn* __restrict__ in, const BatchEntryOut* __restrict__ out, u32 nEntries,
-                                                             FrameDesc* __restrict__ frames, BlockDesc* __restrict__ blocks)
+template <bool kSet>
+__device__ __forceinline__ void batch_walk_emit_body(const u8* __restrict__ src, const BatchEntryIn* __restrict__ in, const BatchEntryOut* __restrict__ out, u32 nEntries,
+                                                     FrameDesc* __restrict__ frames, BlockDesc* __restrict__ blocks, const DictSlot* __restrict__ slots, u32 nSet)
 {
     const u32 e = blockIdx.x * 64 + threadIdx.x;
     if (e >= nEntries) return;
@@ -418,9 +461,23 @@ __global__ __launch_bounds__(64) void batch_walk_emit_kernel(const u8* __restric
         ChainOut o;
         const u32 st = emit_frame(src, end, pos, o, idx, blk, dstOff, frames, blocks);
         if (st >= 2) return;                                   // cannot happen: the counting pass walked the same bytes
-        if (st == 0) { frames[idx].scratchOff = scr; idx++; blk += o.nbBlocks; dstOff += o.content; scr += o.content; }
+        if (st == 0) {
+            frames[idx].scratchOff = scr;
+            if constexpr (kSet) { u32 inSet, wrong; frames[idx].dictSlot = dictset_select(slots, nSet, o.dictID, &inSet, &wrong); }     // (the count refused a wrong one)
+            idx++; blk += o.nbBlocks; dstOff += o.content; scr += o.content;
+        }
         pos = o.next;
     }
+}
+__global__ __launch_bounds__(64) void batch_walk_emit_kernel(const u8* __restrict__ src, const BatchEntryIn* __restrict__ in, const BatchEntryOut* __restrict__ out, u32 nEntries,
+                                                             FrameDesc* __restrict__ frames, BlockDesc* __restrict__ blocks)
+{
+    batch_walk_emit_body<false>(src, in, out, nEntries, frames, blocks, nullptr, 0);
+}
+__global__ __launch_bounds__(64) void batch_walk_emit_set_kernel(const u8* __restrict__ src, const BatchEntryIn* __restrict__ in, const BatchEntryOut* __restrict__ out, u32 nEntries,
+                                                                 FrameDesc* __restrict__ frames, BlockDesc* __restrict__ blocks, const DictSlot* __restrict__ slots, u32 nSet)
+{
+    batch_walk_emit_body<true>(src, in, out, nEntries, frames, blocks, slots, nSet);
 }
 
 // fold: an entry's error is the smallest key of its blocks — its first failing block's first error, what the single call reports
@@ -435,14 +492,18 @@ __global__ __launch_bounds__(64) void batch_fold_kernel(BatchEntryOut* __restric
     if (key != ~0ull) out[e].result = (u64)0 - (key & 0xFFFFull);
 }
 
-void launch_batch_walk_count(const u8* src, const BatchEntryIn* in, BatchEntryOut* out, u32 nEntries, u32 dictID, u64 aloneAbove, u32* status, hipStream_t stream)
+void launch_batch_walk_count(const u8* src, const BatchEntryIn* in, BatchEntryOut* out, u32 nEntries, u32 dictID, u64 aloneAbove, u32* status, hipStream_t stream,
+                             const DictSlot* slots, u32 nSet)
 {
-    hipLaunchKernelGGL(batch_walk_count_kernel, dim3((nEntries + 63) / 64), dim3(64), 0, stream, src, in, out, nEntries, dictID, aloneAbove);
+    if (slots) hipLaunchKernelGGL(batch_walk_count_set_kernel, dim3((nEntries + 63) / 64), dim3(64), 0, stream, src, in, out, nEntries, aloneAbove, slots, nSet, status);
+    else hipLaunchKernelGGL(batch_walk_count_kernel, dim3((nEntries + 63) / 64), dim3(64), 0, stream, src, in, out, nEntries, dictID, aloneAbove);
     hipLaunchKernelGGL(batch_scan_kernel, dim3(1), dim3(256), 0, stream, out, nEntries, status);
 }
-void launch_batch_walk_emit(const u8* src, const BatchEntryIn* in, const BatchEntryOut* out, u32 nEntries, FrameDesc* frames, BlockDesc* blocks, hipStream_t stream)
+void launch_batch_walk_emit(const u8* src, const BatchEntryIn* in, const BatchEntryOut* out, u32 nEntries, FrameDesc* frames, BlockDesc* blocks, hipStream_t stream,
+                            const DictSlot* slots, u32 nSet)
 {
-    hipLaunchKernelGGL(batch_walk_emit_kernel, dim3((nEntries + 63) / 64), dim3(64), 0, stream, src, in, out, nEntries, frames, blocks);
+    if (slots) hipLaunchKernelGGL(batch_walk_emit_set_kernel, dim3((nEntries + 63) / 64), dim3(64), 0, stream, src, in, out, nEntries, frames, blocks, slots, nSet);
+    else hipLaunchKernelGGL(batch_walk_emit_kernel, dim3((nEntries + 63) / 64), dim3(64), 0, stream, src, in, out, nEntries, frames, blocks);
 }
 void launch_batch_fold(BatchEntryOut* out, u32 nEntries, const u64* keys, hipStream_t stream)
 {
@@ -624,9 +685,10 @@ void launch_frame_walk_emit(const u8* src, u64 srcSize, FrameDesc* frames, Block
     hipLaunchKernelGGL(walk_emit_kernel, dim3((w.nSeg + 255) / 256), dim3(256), 0, stream, src, srcSize, w.segs, w.nSeg, w.frameBase, w.blockBase, w.dstBase, frames, blocks);
 }
 void launch_frame_walk_serial(const u8* src, u64 srcSize, FrameDesc* frames, BlockDesc* blocks, u32 maxFrames, u32* status, u32 dictID, u32 emit,
-                              hipStream_t stream)
+                              hipStream_t stream, const DictSlot* slots, u32 nSet)
 {
-    hipLaunchKernelGGL(frame_walk_serial_kernel, dim3(1), dim3(64), 0, stream, src, srcSize, frames, blocks, maxFrames, status, dictID, emit);
+    if (slots) hipLaunchKernelGGL(frame_walk_serial_set_kernel, dim3(1), dim3(64), 0, stream, src, srcSize, frames, blocks, maxFrames, status, emit, slots, nSet);
+    else hipLaunchKernelGGL(frame_walk_serial_kernel, dim3(1), dim3(64), 0, stream, src, srcSize, frames, blocks, maxFrames, status, dictID, emit);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -684,13 +746,17 @@ __global__ __launch_bounds__(256) void block_parse_kernel(const u8* __restrict__
 // frames of up to kLinkSmall blocks (a stream of single-block 64 KiB frames has 16 384 of them per GiB): one LANE per frame, the
 // blocks one after the other — a wave per frame costs three times as much there; longer frames: block_link_kernel below
 constexpr u32 kLinkSmall = 4;
+// kSet: "a formatted dictionary" is a property of the frame's own dictionary (slots[F.dictSlot]); a lane has a frame of its own here,
+// so haveDict is per lane.  (The kernel itself is the template: as a wrapper around an inlined body the parent's instance took one SGPR more.)
+template <bool kSet>
 __global__ __launch_bounds__(64) void block_link_small_kernel(FrameDesc* __restrict__ frames, BlockDesc* __restrict__ blocks, u32 nFrames, u32 haveDict,
-                                                              u32 earlyLiterals, u32* __restrict__ status)
+                                                              u32 earlyLiterals, u32* __restrict__ status, const DictSlot* __restrict__ slots)
 {
     const u32 f = blockIdx.x * 64 + threadIdx.x;
     if (f >= nFrames) return;
     FrameDesc& F = frames[f];
     if (F.nbBlocks > kLinkSmall) return;                       // (a wave of block_link_kernel takes it)
+    if constexpr (kSet) haveDict = slots[F.dictSlot].formatted;
     // a formatted dictionary: every frame starts from its Huffman table and its three FSE tables (ZSTD_decompressBegin_usingDict,
     // U/ZstdDecompress.cs:1956-1990); without one nothing is defined before the frame's first block defines it
     u32 lastHuf = haveDict ? kDictBlock : kNoBlock;
@@ -736,13 +802,15 @@ __device__ __forceinline__ u32 latest_before(u64 mask, u32 firstOfBatch, u32 car
 // any block — later blocks' hufSrc / tblSrc may name them — and then made to regenerate nothing: an RLE block of no bytes, which
 // every later stage passes over; what they themselves lack (a table defined before the oldest carried block) is no error.  A fragment
 // is one frame, linked by this kernel whatever its number of blocks.
-template <bool PH>
+// kSet: haveDict is the frame's own dictionary's (one frame per wave: uniform)
+template <bool PH, bool kSet = false>
 __device__ __forceinline__ void block_link_body(FrameDesc* __restrict__ frames, BlockDesc* __restrict__ blocks, u32 nFrames, u32 haveDict,
-                                                u32 earlyLiterals, u32* __restrict__ status, u32 phantoms)
+                                                u32 earlyLiterals, u32* __restrict__ status, u32 phantoms, const DictSlot* __restrict__ slots = nullptr)
 {
     const u32 f = blockIdx.x, lane = threadIdx.x;
     if (f >= nFrames) return;
     FrameDesc& F = frames[f];
+    if constexpr (kSet) haveDict = uniform(slots[uniform(F.dictSlot)].formatted);
     const u32 first = uniform(F.firstBlock), nb = uniform(F.nbBlocks);
     if (!PH && nb <= kLinkSmall) return;                       // (a lane of block_link_small_kernel takes it)
     const u64 dstSize = F.dstSize;
@@ -817,6 +885,11 @@ __global__ __launch_bounds__(64) void block_link_kernel(FrameDesc* __restrict__ 
 {
     block_link_body<false>(frames, blocks, nFrames, haveDict, earlyLiterals, status, 0);
 }
+__global__ __launch_bounds__(64) void block_link_set_kernel(FrameDesc* __restrict__ frames, BlockDesc* __restrict__ blocks, u32 nFrames,
+                                                            u32 earlyLiterals, u32* __restrict__ status, const DictSlot* __restrict__ slots)
+{
+    block_link_body<false, true>(frames, blocks, nFrames, 0, earlyLiterals, status, 0, slots);
+}
 __global__ __launch_bounds__(64) void block_link_stream_kernel(FrameDesc* __restrict__ frames, BlockDesc* __restrict__ blocks, u32 nFrames, u32 haveDict,
                                                                u32 earlyLiterals, u32* __restrict__ status, u32 phantoms)
 {
@@ -871,15 +944,21 @@ __global__ __launch_bounds__(1024) void seq_scan_kernel(BlockDesc* __restrict__ 
 }
 
 void launch_block_prepass(const u8* src, FrameDesc* frames, BlockDesc* blocks, u32 nFrames, u32 nBlocks, u32 haveDict, u32 earlyLiterals, u32* status, hipStream_t stream,
-                          u32 phantoms)
+                          u32 phantoms, const DictSlot* slots)
 {
     hipLaunchKernelGGL(block_parse_kernel, dim3((nBlocks + 255) / 256), dim3(256), 0, stream, src, blocks, nBlocks, status);
+    if (slots) {                // (never a fragment of a segmented stream: the host refuses that combination)
+        hipLaunchKernelGGL(block_link_small_kernel<true>, dim3((nFrames + 63) / 64), dim3(64), 0, stream, frames, blocks, nFrames, 0u, earlyLiterals, status, slots);
+        if (nBlocks > nFrames) hipLaunchKernelGGL(block_link_set_kernel, dim3(nFrames), dim3(64), 0, stream, frames, blocks, nFrames, earlyLiterals, status, slots);
+        hipLaunchKernelGGL(seq_scan_kernel, dim3(1), dim3(1024), 0, stream, blocks, nBlocks, status);
+        return;
+    }
     if (phantoms) {             // a fragment of a segmented stream: one frame whose first blocks are carried definers
         hipLaunchKernelGGL(block_link_stream_kernel, dim3(nFrames), dim3(64), 0, stream, frames, blocks, nFrames, haveDict, earlyLiterals, status, phantoms);
         hipLaunchKernelGGL(seq_scan_kernel, dim3(1), dim3(1024), 0, stream, blocks, nBlocks, status);
         return;
     }
-    hipLaunchKernelGGL(block_link_small_kernel, dim3((nFrames + 63) / 64), dim3(64), 0, stream, frames, blocks, nFrames, haveDict, earlyLiterals, status);
+    hipLaunchKernelGGL(block_link_small_kernel<false>, dim3((nFrames + 63) / 64), dim3(64), 0, stream, frames, blocks, nFrames, haveDict, earlyLiterals, status, (const DictSlot*)nullptr);
     if (nBlocks > nFrames) hipLaunchKernelGGL(block_link_kernel, dim3(nFrames), dim3(64), 0, stream, frames, blocks, nFrames, haveDict, earlyLiterals, status);      // (some frame has several blocks)
     hipLaunchKernelGGL(seq_scan_kernel, dim3(1), dim3(1024), 0, stream, blocks, nBlocks, status);
 }
@@ -887,13 +966,19 @@ void launch_block_prepass(const u8* src, FrameDesc* frames, BlockDesc* blocks, u
 // ------------------------------------------------------------------------------------------------
 // block_offsets: output offsets and starting repcodes of the blocks of a frame (one wave per frame, after seq_decode)
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(64) void block_offsets_kernel(FrameDesc* __restrict__ frames, BlockDesc* __restrict__ blocks, u32 nFrames,
-                                                           const DictInfo* __restrict__ di, u32* __restrict__ status)
+// kSet: the repcodes a frame starts from are its own dictionary's (one frame per wave: the record's fields are wave-uniform)
+template <bool kSet>
+__device__ __forceinline__ void block_offsets_body(FrameDesc* __restrict__ frames, BlockDesc* __restrict__ blocks, u32 nFrames,
+                                                   const DictInfo* __restrict__ di, u32* __restrict__ status, const DictSlot* __restrict__ slots)
 {
     const u32 f = blockIdx.x, lane = threadIdx.x;
     if (f >= nFrames) return;
     const u32 first = frames[f].firstBlock, nb = frames[f].nbBlocks;
     u32 r0 = 1, r1 = 4, r2 = 8;                                // ZSTD_decompressBegin, U/ZstdDecompress.cs:1933-1954
+    if constexpr (kSet) {
+        const DictSlot& D = slots[uniform(frames[f].dictSlot)];
+        if (uniform(D.formatted)) { r0 = uniform(D.rep[0]); r1 = uniform(D.rep[1]); r2 = uniform(D.rep[2]); }
+    } else
     if (di) { r0 = uniform(di->rep[0]); r1 = uniform(di->rep[1]); r2 = uniform(di->rep[2]); }
     u64 acc = 0; u32 bad = 0;
     for (u32 k0 = 0; k0 < nb; k0 += 64) {
@@ -943,6 +1028,16 @@ __global__ __launch_bounds__(64) void block_offsets_kernel(FrameDesc* __restrict
         }
     }
 }
+__global__ __launch_bounds__(64) void block_offsets_kernel(FrameDesc* __restrict__ frames, BlockDesc* __restrict__ blocks, u32 nFrames,
+                                                           const DictInfo* __restrict__ di, u32* __restrict__ status)
+{
+    block_offsets_body<false>(frames, blocks, nFrames, di, status, nullptr);
+}
+__global__ __launch_bounds__(64) void block_offsets_set_kernel(FrameDesc* __restrict__ frames, BlockDesc* __restrict__ blocks, u32 nFrames,
+                                                               u32* __restrict__ status, const DictSlot* __restrict__ slots)
+{
+    block_offsets_body<true>(frames, blocks, nFrames, nullptr, status, slots);
+}
 
 // frames without a content size: the frames' output offsets from their regenerated sizes (single workgroup); the total goes to
 // status, and a total beyond the destination's capacity stops everything behind this kernel
@@ -958,9 +1053,11 @@ __global__ __launch_bounds__(1024) void frame_rescan_kernel(FrameDesc* __restric
     }
 }
 
-void launch_block_offsets(FrameDesc* frames, BlockDesc* blocks, u32 nFrames, const DictInfo* di, u32 rescan, u64 dstCapacity, u32* status, hipStream_t stream)
+void launch_block_offsets(FrameDesc* frames, BlockDesc* blocks, u32 nFrames, const DictInfo* di, u32 rescan, u64 dstCapacity, u32* status, hipStream_t stream,
+                          const DictSlot* slots)
 {
-    hipLaunchKernelGGL(block_offsets_kernel, dim3(nFrames), dim3(64), 0, stream, frames, blocks, nFrames, di, status);
+    if (slots) hipLaunchKernelGGL(block_offsets_set_kernel, dim3(nFrames), dim3(64), 0, stream, frames, blocks, nFrames, status, slots);
+    else hipLaunchKernelGGL(block_offsets_kernel, dim3(nFrames), dim3(64), 0, stream, frames, blocks, nFrames, di, status);
     if (rescan) hipLaunchKernelGGL(frame_rescan_kernel, dim3(1), dim3(1024), 0, stream, frames, nFrames, dstCapacity, status);
 }
 

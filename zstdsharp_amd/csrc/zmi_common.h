@@ -120,7 +120,7 @@ struct FrameDesc {      // one per frame found by the frame walk (U/ZstdDecompre
     u32 bad;            // 1 = some stage failed in this frame (its error is in the status words): later stages leave it alone
     u32 hasSeq;         // 1 = at least one block holds sequences (the ordered executor has work in this frame)
     u32 viaOrigin;      // 1 = the frame's matches are resolved by the origin path (decode_origin.hip): exec_matches only checks its checksum
-    u32 pad;
+    u32 dictSlot;       // its dictionary's record in the slot table (zmi_dictset.h) when the set kernels run (ZSTD_d_refMultipleDDicts); else 0, unread
     u64 originOff;      // then: index of its first entry in the origin array
 };
 
@@ -234,7 +234,8 @@ enum : u32 { kStFrames = 0, kStErr = 1, kStTotalLo = 2, kStTotalHi = 3, kStUsabl
              kStLitLo = 54, kStLitHi = 55,              // regenerated bytes of all Huffman-coded literals sections (u64; block_link)
              kStBigBins = 56,           // 12 x u64: content bytes of the frames with sequences by size class, bin k = [2^(20+k), 2^(21+k)), below 2^30
              kStDictTabBlocks = 80,     // blocks that copied a sequence table from a DDict's ready-made set (seq_decode_kernel's instance for it)
-             kStWords = 82 };
+             kStSetFrames = 82,         // frames whose dictionary was found in the DDict set by dictID (the walks' set instances)
+             kStWords = 84 };
 constexpr u32 kOriginRounds = 36;
 
 // Stage timing (ZSTDMI_*_setProfiling): a launcher that issues several kernels marks the end of each on the context's timer, so

@@ -66,6 +66,16 @@ struct ZSTD_DCtx_s {
     const ZSTD_DDict_s* ddict = nullptr;
     long long dictUploads = 0;          // uploads this context made itself (ZSTDMI_debugDictUploadsD)
     long long lastDictTabBlocks = 0;    // blocks of the last call that copied a ready-made table (ZSTDMI_debugLastDictTableBlocks)
+    // ZSTD_d_refMultipleDDicts (U/ZstdDecompress.cs:8-115, 2300-2339): while the parameter is 1, ZSTD_DCtx_refDDict also files the DDict in
+    // ddictSet (references, sorted by dictID; lives until ZSTD_freeDCtx).  With a DDict current and two or more in the set, a decode call
+    // runs the kernels' set instances over slotTab: the set's sorted image (zmi_dictset.h) with the current DDict's record behind it,
+    // uploaded by the first call after setGen moved (dctx_sync_slots).
+    int refMultiple = 0;
+    DictSet<const ZSTD_DDict_s*> ddictSet;
+    std::vector<DictSlot> slotHost; DevBuf slotTab;
+    u64 setGen = 0, slotGen = ~(u64)0;  // setGen: bumped when the set, the current DDict or the context's device changes
+    u64 foreignGen = ~(u64)0; bool foreign = false;     // (at setGen == foreignGen) some DDict of the set lives on another device
+    long long lastSetFrames = 0;        // frames of the last call whose dictionary was found in the set (ZSTDMI_debugLastSetFrames)
     std::vector<ZSTD_DCtx_s*> workers;      // ZSTDMI_DCtx_setDevices (decompress_multi)
     // ZSTD_DCtx_refPrefix: the caller's bytes (host or device), referenced until the next ZSTD_decompressDCtx / ZSTDMI_decompressDevice
     // has consumed them.  pfxDev: the prefix as that call's kernels read it (the caller's device pointer, or pfxStage for a host prefix)
@@ -77,6 +87,20 @@ struct ZSTD_DCtx_s {
 // sequence decoding tables ready-made in seq_decode_kernel's LDS format (seqTabs: kDictTabWords words, decode_seq.hip).
 struct ZSTD_DDict_s { std::vector<u8> host; DevBuf dict, dictInfoDev, seqTabs; DictInfo info = {}; bool formatted = false; int device = 0; };
 static bool ddict_shared(const ZSTD_DCtx* d) { return d->ddict && d->ddict->device == d->device && d->workers.size() <= 1; }
+// the set is in force: frames select their DDict by dictID (a set of one is the single-DDict path, private upload included)
+static bool set_active(const ZSTD_DCtx* d) { return d->refMultiple && d->ddict && d->ddictSet.size() >= 2; }
+// what a decode call answers before it reads a byte: the set's kernels serve one device and whole frames only.  Touches no device.
+static size_t set_check(ZSTD_DCtx* d, bool segmented = false)
+{
+    if (!set_active(d)) return 0;
+    if (d->workers.size() > 1 || segmented || !ddict_shared(d)) return ZERR(kErrParameterUnsupported);
+    if (d->foreignGen != d->setGen) {
+        d->foreign = false;
+        for (const auto& e : d->ddictSet.entries) if (e.ref->device != d->device) { d->foreign = true; break; }
+        d->foreignGen = d->setGen;
+    }
+    return d->foreign ? ZERR(kErrParameterUnsupported) : 0;
+}
 
 static size_t dctx_sync_dictionary(ZSTD_DCtx* d);
 static size_t dctx_bind(ZSTD_DCtx* d)
@@ -99,7 +123,7 @@ size_t ZSTD_freeDCtx(ZSTD_DCtx* d)
     if (d->deviceOk) {
         (void)hipSetDevice(d->device);
         if (d->ownStream) (void)hipStreamSynchronize(d->ownStream);
-        d->frames.release(); d->blocks.release(); d->recs.release(); d->status.release(); d->scratch.release(); d->walkWs.release(); d->slowFlags.release(); d->stageSrc.release(); d->stageDst.release(); d->dict.release(); d->dictInfoDev.release(); d->origin.release(); d->originList.release(); d->batchIn.release(); d->batchOut.release(); d->blockKeys.release(); d->seekTab.release(); d->seekSum.release(); d->edge.release(); d->pfxStage.release(); d->rangesWs.release(); d->rangesIn.release(); d->rangesRec.release(); d->rangesRes.release(); d->arena.release();
+        d->frames.release(); d->blocks.release(); d->recs.release(); d->status.release(); d->scratch.release(); d->walkWs.release(); d->slowFlags.release(); d->stageSrc.release(); d->stageDst.release(); d->dict.release(); d->dictInfoDev.release(); d->origin.release(); d->originList.release(); d->batchIn.release(); d->batchOut.release(); d->blockKeys.release(); d->seekTab.release(); d->seekSum.release(); d->edge.release(); d->pfxStage.release(); d->rangesWs.release(); d->rangesIn.release(); d->rangesRec.release(); d->rangesRes.release(); d->arena.release(); d->slotTab.release();
         d->hist[0].release(); d->hist[1].release(); d->segReps.release(); d->segXxh.release();
         d->timer.destroy();
         if (d->aux) { (void)hipStreamSynchronize(d->aux); (void)hipStreamDestroy(d->aux); }
@@ -113,12 +137,18 @@ size_t ZSTD_DCtx_setParameter(ZSTD_DCtx* d, int param, int value)
 {
     if (!d) return ZERR(kErrGeneric);
     if (param == ZSTD_d_windowLogMax) { if (value != 0 && (value < 10 || value > 31)) return ZERR(kErrParameterOutOfBound); d->windowLogMax = value ? value : 27; return 0; }
+    if (param == ZSTD_d_refMultipleDDicts) {        // sticky; the set itself stays as it is (U/ZstdDecompress.cs:2441-2447)
+        if (value != ZSTD_rmd_refSingleDDict && value != ZSTD_rmd_refMultipleDDicts) return ZERR(kErrParameterOutOfBound);
+        d->refMultiple = value;
+        return 0;
+    }
     return ZERR(kErrParameterUnsupported);
 }
 size_t ZSTD_DCtx_getParameter(ZSTD_DCtx* d, int param, int* value)
 {
     if (!d || !value) return ZERR(kErrGeneric);
     if (param == ZSTD_d_windowLogMax) { *value = d->windowLogMax; return 0; }
+    if (param == ZSTD_d_refMultipleDDicts) { *value = d->refMultiple; return 0; }
     return ZERR(kErrParameterUnsupported);
 }
 // ZSTD_decompress_insertDictionary, U/ZstdDecompress.cs:1909-1931: without the magic the bytes are raw content, history in
@@ -279,10 +309,14 @@ static size_t dctx_sync_dictionary(ZSTD_DCtx* d)
 
 // the loaded dictionary as the decode kernels take it
 // seqTabs: a DDict's ready-made sequence tables (null for a loaded dictionary and for raw content)
-struct DecodeDict { bool fmt; const u8* dictFull; const DictInfo* dinfo; const u8* dictContent; u32 dictContentSize, dictID; const u32* seqTabs; };
+// slots (null: the single-dictionary kernels run): the context's DDict set as the kernels' set instances read it, nSet records sorted by
+// dictID and the current DDict's behind them (dctx_sync_slots); the other fields then describe the current DDict
+struct DecodeDict { bool fmt; const u8* dictFull; const DictInfo* dinfo; const u8* dictContent; u32 dictContentSize, dictID; const u32* seqTabs;
+                    const DictSlot* slots; u32 nSet; };
 static DecodeDict decode_dict(const ZSTD_DCtx* d)
 {
     DecodeDict k;
+    k.slots = nullptr; k.nSet = 0;
     if (ddict_shared(d)) {
         const ZSTD_DDict_s& g = *d->ddict;
         k.fmt = g.formatted && !g.host.empty();
@@ -302,6 +336,39 @@ static DecodeDict decode_dict(const ZSTD_DCtx* d)
     k.dictContentSize = d->dictHost.empty() ? 0u : (k.fmt ? d->info.contentSize : (u32)d->dictHost.size());
     k.dictID = k.fmt ? d->info.dictID : 0u;
     return k;
+}
+
+// a DDict as a record of the slot table (what decode_dict says of a shared one)
+static void fill_slot(const ZSTD_DDict_s* g, DictSlot& r)
+{
+    r = DictSlot{};
+    if (!g || g->host.empty()) return;
+    const bool fmt = g->formatted;
+    r.formatted = fmt ? 1u : 0u;
+    r.dictFull = fmt ? (const u8*)g->dict.p : nullptr;
+    r.content = (const u8*)g->dict.p + (fmt ? g->info.contentOff : 0u);
+    r.contentSize = fmt ? g->info.contentSize : (u32)g->host.size();
+    r.seqTabs = fmt ? (const u32*)g->seqTabs.p : nullptr;
+    if (!fmt) return;
+    r.dictID = g->info.dictID;
+    r.hufOff = g->info.hufOff; r.hufSize = g->info.hufSize; r.ofOff = g->info.ofOff; r.mlOff = g->info.mlOff; r.llOff = g->info.llOff; r.repOff = g->info.repOff;
+    for (int i = 0; i < 3; ++i) r.rep[i] = g->info.rep[i];
+}
+// The set for this call (after set_check): nothing while it is not in force; else the slot table, uploaded when the set, the current
+// DDict or the device changed since the last upload — one small copy on the context's stream, in front of the kernels that read it.
+static size_t dctx_sync_slots(ZSTD_DCtx* d, DecodeDict& dd)
+{
+    dd.slots = nullptr; dd.nSet = 0;
+    if (!set_active(d) || d->pfxDev) return 0;
+    if (d->slotGen != d->setGen) {
+        if (!d->ddictSet.image(d->slotHost, d->ddict, fill_slot)) return ZERR(kErrMemoryAllocation);
+        if (!d->slotTab.ensure(d->slotHost.size() * sizeof(DictSlot) + 64)) return ZERR(kErrMemoryAllocation);
+        if (hipMemcpyAsync(d->slotTab.p, d->slotHost.data(), d->slotHost.size() * sizeof(DictSlot), hipMemcpyHostToDevice, d->stream) != hipSuccess) return ZERR(kErrGeneric);
+        { const size_t e = stream_wait(d->stream); if (isErr(e)) return e; }       // (slotHost may change before the next call's kernels run)
+        d->slotGen = d->setGen;
+    }
+    dd.slots = (const DictSlot*)d->slotTab.p; dd.nSet = (u32)d->ddictSet.size();
+    return 0;
 }
 
 // the status words (d->status, kSt*): error key = "none" (all ones), everything else zero
@@ -336,13 +403,14 @@ static size_t decode_lists(ZSTD_DCtx* d, const DecodeDict& dd, u8* d_dst, const 
     FrameDesc* frames = (FrameDesc*)d->frames.p; BlockDesc* blocks = (BlockDesc*)d->blocks.p;
     const bool fmt = dd.fmt; const u8* const dictFull = dd.dictFull; const DictInfo* const dinfo = dd.dinfo;
     const u8* const dictContent = dd.dictContent; const u32 dictContentSize = dd.dictContentSize;
+    const DictSlot* const slots = dd.slots;         // not null: every stage below runs its set instance and reads the dictionary per frame
     // The literal decoder and seq_decode need nothing of each other (a block's Huffman streams and its FSE chains).  With few
     // blocks neither fills the chip — both are serial chains per block — so below kOverlapBlocks the literal decoder may run beside
     // seq_decode on a stream of its own (`early`: block_link then lets it write only the outputs whose place is known by now).
     // Whether it does is decided once the pre-pass has counted both kinds of work (below).
     constexpr u32 kOverlapBlocks = 12288;
     const bool early = d->overlapMode == 2 || (d->overlapMode == 0 && nBlocks <= kOverlapBlocks);
-    launch_block_prepass(d_src, frames, blocks, nFrames, nBlocks, fmt ? 1u : 0u, early ? 1u : 0u, status, s, link ? link->phantoms : 0u);
+    launch_block_prepass(d_src, frames, blocks, nFrames, nBlocks, fmt ? 1u : 0u, early ? 1u : 0u, status, s, link ? link->phantoms : 0u, slots);
     { const size_t e = status_read(d, st); if (isErr(e)) return e; }
     d->timer.mark("block_prepass", s);
     const u64 nSeq = st_u64(st, kStSeqLo, kStSeqHi);
@@ -387,20 +455,20 @@ static size_t decode_lists(ZSTD_DCtx* d, const DecodeDict& dd, u8* d_dst, const 
     const bool beside = early && nSeq && (d->overlapMode == 2 || (litBytes >= 5 * nSeq && nSeq >= 64 * (u64)nBlocks));
     if (getenv("ZMI_DEBUG")) fprintf(stderr, "zmi: blocks %u seqs %llu coded literal bytes %llu early %d beside %d\n", nBlocks, (unsigned long long)nSeq, (unsigned long long)litBytes, (int)early, (int)beside);
     if (beside) {               // (the host has just waited for the pre-pass: everything the literal decoder reads is there)
-        launch_decode_literals(d_src, d_dst, (u8*)d->scratch.p, frames, blocks, nBlocks, status, (u8*)d->slowFlags.p, d->litDecoder, dictFull, dinfo, d->aux, StageHook());
+        launch_decode_literals(d_src, d_dst, (u8*)d->scratch.p, frames, blocks, nBlocks, status, (u8*)d->slowFlags.p, d->litDecoder, dictFull, dinfo, d->aux, StageHook(), slots);
         if (hipEventRecord(d->auxDone, d->aux) != hipSuccess) return ZERR(kErrGeneric);
         auxGuard.on = true;
     }
-    launch_seq_decode(d_src, frames, blocks, nBlocks, recs, status, dictFull, dinfo, dd.seqTabs, s);            d->timer.mark("seq_decode", s);
-    launch_block_offsets(frames, blocks, nFrames, link && link->reps ? link->reps : dinfo, nUnsized ? 1u : 0u, dstCapacity, status, s);  d->timer.mark("block_offsets", s);
+    launch_seq_decode(d_src, frames, blocks, nBlocks, recs, status, dictFull, dinfo, dd.seqTabs, s, slots);     d->timer.mark("seq_decode", s);
+    launch_block_offsets(frames, blocks, nFrames, link && link->reps ? link->reps : dinfo, nUnsized ? 1u : 0u, dstCapacity, status, s, slots);  d->timer.mark("block_offsets", s);
     if (auxGuard.on) { if (hipStreamWaitEvent(s, d->auxDone, 0) != hipSuccess) return ZERR(kErrGeneric); d->timer.mark("decode_literals", s); }     // (what of it seq_decode did not cover)
-    else launch_decode_literals(d_src, d_dst, (u8*)d->scratch.p, frames, blocks, nBlocks, status, (u8*)d->slowFlags.p, d->litDecoder, dictFull, dinfo, s, d->timer.hook());
+    else launch_decode_literals(d_src, d_dst, (u8*)d->scratch.p, frames, blocks, nBlocks, status, (u8*)d->slowFlags.p, d->litDecoder, dictFull, dinfo, s, d->timer.hook(), slots);
     launch_place_literals(d_src, d_dst, (const u8*)d->scratch.p, frames, blocks, nBlocks, recs, status, s);    d->timer.mark("place_literals", s);
     if (originMin) {
         const u64 entries = originBytes + 1024 * (u64)originCap, longest = originLongest;
         u32* const origin = (u32*)d->origin.p; const u32* const list = (const u32*)d->originList.p;
         launch_origin_select(frames, nFrames, originMin, (u32*)d->originList.p, originCap, entries, status, s);
-        launch_origin_init(frames, blocks, list, originCap, longest, recs, status, origin, dictContent ? dictContentSize : 0u, s);    d->timer.mark("origin_init", s);
+        launch_origin_init(frames, blocks, list, originCap, longest, recs, status, origin, dictContent ? dictContentSize : 0u, s, slots);    d->timer.mark("origin_init", s);
         // The rounds in groups of six, the host looking at the last one's verdict in between: ordinary data settles in about ten
         // rounds, and a round that only finds out that nothing is left still costs its launch (the kernels check the flag too).
         for (u32 r = 0; r < kOriginRounds; r += 6) {
@@ -411,9 +479,9 @@ static size_t decode_lists(ZSTD_DCtx* d, const DecodeDict& dd, u8* d_dst, const 
             if (!open) break;
         }
         d->timer.mark("origin_jump", s);
-        launch_origin_gather(frames, list, originCap, longest, status, origin, d_dst, dictContent, s);    d->timer.mark("origin_gather", s);
+        launch_origin_gather(frames, list, originCap, longest, status, origin, d_dst, dictContent, s, slots);    d->timer.mark("origin_gather", s);
     }
-    launch_exec_matches(d_src, d_dst, frames, blocks, nFrames, recs, status, dictContent, dictContentSize, s, execWaves);  d->timer.mark("exec_matches", s);
+    launch_exec_matches(d_src, d_dst, frames, blocks, nFrames, recs, status, dictContent, dictContentSize, s, execWaves, slots);  d->timer.mark("exec_matches", s);
     if (!tail()) return ZERR(kErrGeneric);
     { const size_t e = status_read(d, st); if (isErr(e)) return e; }
     d->lastDictTabBlocks += st[kStDictTabBlocks];
@@ -435,6 +503,7 @@ static size_t decompress_device(ZSTD_DCtx* d, u8* d_dst, size_t dstCapacity, con
     { const size_t e = dctx_sync_dictionary(d); if (isErr(e)) return e; }
     DecodeDict dd = decode_dict(d);
     if (d->pfxDev) { dd.dictContent = d->pfxDev; dd.dictContentSize = (u32)d->pfxSize; }      // ZSTD_DCtx_refPrefix: raw content, read where it lies
+    { const size_t e = dctx_sync_slots(d, dd); if (isErr(e)) return e; }
     const u32 dictID = dd.dictID;
     d->timer.begin(s);
     { const size_t e = status_reset(d); if (isErr(e)) return e; }
@@ -443,9 +512,12 @@ static size_t decompress_device(ZSTD_DCtx* d, u8* d_dst, size_t dstCapacity, con
     { const size_t e = status_read(d, st); if (isErr(e)) return e; }
     const bool serialWalk = !st[kStUsable];
     d->lastWalkSerial = serialWalk;
+    // (the parallel walk lists only frames that name no dictionary: all of them are the current DDict's, the single-dictionary kernels' case)
+    if (!serialWalk) { dd.slots = nullptr; dd.nSet = 0; }
     if (serialWalk) {   // the segment links did not close: take the exact serial walk (it also yields the reference's error code)
-        launch_frame_walk_serial(d_src, srcSize, nullptr, nullptr, maxFrames, status, dictID, 0, s);
+        launch_frame_walk_serial(d_src, srcSize, nullptr, nullptr, maxFrames, status, dictID, 0, s, dd.slots, dd.nSet);
         const size_t e = status_read(d, st); if (isErr(e)) return e;
+        if (dd.slots) d->lastSetFrames += st[kStSetFrames];
     }
     if (st[kStErr]) return ZERR(st[kStErr]);
     const u32 nFrames = st[kStFrames], nBlocks = st[kStBlocks], nUnsized = st[kStUnsized];
@@ -454,7 +526,7 @@ static size_t decompress_device(ZSTD_DCtx* d, u8* d_dst, size_t dstCapacity, con
     if (nFrames == 0) { d->timer.finish(); return 0; }
     if (!ensure_lists(d, nFrames, nBlocks, total)) return ZERR(kErrMemoryAllocation);
     FrameDesc* frames = (FrameDesc*)d->frames.p; BlockDesc* blocks = (BlockDesc*)d->blocks.p;
-    if (serialWalk) launch_frame_walk_serial(d_src, srcSize, frames, blocks, maxFrames, status, dictID, 1, s);
+    if (serialWalk) launch_frame_walk_serial(d_src, srcSize, frames, blocks, maxFrames, status, dictID, 1, s, dd.slots, dd.nSet);
     else            launch_frame_walk_emit(d_src, srcSize, frames, blocks, (u8*)d->walkWs.p, s);
     d->timer.mark("frame_walk", s);
     { const size_t e = decode_lists(d, dd, d_dst, d_src, nFrames, nBlocks, nUnsized, dstCapacity, st, [] { return true; }); if (isErr(e)) return e; }
@@ -487,11 +559,12 @@ static size_t decode_entries(ZSTD_DCtx* d, const DecodeDict& dd, const u8* srcBa
     const BatchEntryIn* dIn = (const BatchEntryIn*)d->batchIn.p; BatchEntryOut* dOut = (BatchEntryOut*)d->batchOut.p;
     u32 st[kStWords] = {};
     { const size_t e = status_reset(d); if (isErr(e)) return e; }
-    launch_batch_walk_count(srcBase, dIn, dOut, n, dd.dictID, kBatchAloneAbove, status, s);
+    launch_batch_walk_count(srcBase, dIn, dOut, n, dd.dictID, kBatchAloneAbove, status, s, dd.slots, dd.nSet);
     if (!readBack() ||
         hipMemcpyAsync(st, status, sizeof st, hipMemcpyDeviceToHost, s) != hipSuccess) return ZERR(kErrGeneric);
     { const size_t e = stream_wait(s); if (isErr(e)) return e; }
     if (st[kStErr]) return ZERR(st[kStErr]);
+    if (dd.slots) d->lastSetFrames += st[kStSetFrames];
     const u32 nFrames = st[kStFrames], nBlocks = st[kStBlocks];
     const u64 total = st_u64(st, kStTotalLo, kStTotalHi);
     u32 keyWords[2] = {0, 0};
@@ -501,7 +574,7 @@ static size_t decode_entries(ZSTD_DCtx* d, const DecodeDict& dd, const u8* srcBa
         if (hipMemsetAsync(d->blockKeys.p, 0xFF, (size_t)nBlocks * sizeof(u64), s) != hipSuccess ||
             hipMemcpyAsync(status + kStBlockKeysLo, &keyWords[0], sizeof(u32), hipMemcpyHostToDevice, s) != hipSuccess ||
             hipMemcpyAsync(status + kStBlockKeysHi, &keyWords[1], sizeof(u32), hipMemcpyHostToDevice, s) != hipSuccess) return ZERR(kErrGeneric);
-        launch_batch_walk_emit(srcBase, dIn, dOut, n, (FrameDesc*)d->frames.p, (BlockDesc*)d->blocks.p, s);
+        launch_batch_walk_emit(srcBase, dIn, dOut, n, (FrameDesc*)d->frames.p, (BlockDesc*)d->blocks.p, s, dd.slots, dd.nSet);
         d->timer.mark("batch_walk", s);
         const size_t e = decode_lists(d, dd, dstBase, srcBase, nFrames, nBlocks, 0, dstSpan, st, [&]() -> bool {
             launch_batch_fold(dOut, n, (const u64*)d->blockKeys.p, s);
@@ -520,10 +593,12 @@ static size_t decompress_batch_impl(ZSTD_DCtx* d, const void* const* srcs, const
     if (n > 0xFFFFFFF0ull) return ZERR(kErrMemoryAllocation);
     size_t e = dctx_bind(d); if (isErr(e)) return e;
     if (d->workers.size() > 1 || d->pfx) return ZERR(kErrParameterUnsupported);      // (a pending ZSTD_DCtx_refPrefix serves one single call)
+    e = set_check(d); if (isErr(e)) return e;
     d->lastBatchAlone = 0;
     e = dctx_sync_dictionary(d); if (isErr(e)) return e;
     hipStream_t s = d->stream;
-    const DecodeDict dd = decode_dict(d);
+    DecodeDict dd = decode_dict(d);
+    e = dctx_sync_slots(d, dd); if (isErr(e)) return e;
     // one base pointer each: the lowest source, the lowest destination
     uintptr_t loS = ~(uintptr_t)0, loD = ~(uintptr_t)0, hiD = 0;
     for (size_t i = 0; i < n; i++) {
@@ -624,13 +699,15 @@ static size_t decompress_range_impl(ZSTD_DCtx* d, void* dst, size_t dstCapacity,
 {
     size_t e = dctx_bind(d); if (isErr(e)) return e;
     if (d->workers.size() > 1 || d->pfx) return ZERR(kErrParameterUnsupported);
+    e = set_check(d); if (isErr(e)) return e;
     d->lastRangeFrames = 0; d->lastRangeStaged = 0;
     hipStream_t s = d->stream;
     const bool dstDev = dst ? is_device_ptr(dst) : false;
     SeekTable t;
     e = open_seek_table(d, src, srcSize, &t, &d->lastRangeStaged); if (isErr(e)) return e;
     const bool srcDev = t.srcDev;
-    const DecodeDict dd = decode_dict(d);
+    DecodeDict dd = decode_dict(d);
+    e = dctx_sync_slots(d, dd); if (isErr(e)) return e;
     if (!d->seekSum.ensure(kSeekWords * sizeof(u64))) return ZERR(kErrMemoryAllocation);
     u64* const sum = (u64*)d->seekSum.p;
     d->timer.begin(s);
@@ -719,12 +796,14 @@ static size_t decompress_ranges_impl(ZSTD_DCtx* d, const void* src, size_t srcSi
     if (n > 0xFFFFFFF0ull) return ZERR(kErrMemoryAllocation);
     size_t e = dctx_bind(d); if (isErr(e)) return e;
     if (d->workers.size() > 1 || d->pfx) return ZERR(kErrParameterUnsupported);      // (a pending ZSTD_DCtx_refPrefix serves one single call)
+    e = set_check(d); if (isErr(e)) return e;
     d->lastRangesFrames = 0; d->lastRangesAlone = 0; d->lastRangesStaged = 0;
     hipStream_t s = d->stream;
     SeekTable t;
     e = open_seek_table(d, src, srcSize, &t, &d->lastRangesStaged); if (isErr(e)) return e;
     const bool srcDev = t.srcDev; const u32 N = t.n;
-    const DecodeDict dd = decode_dict(d);
+    DecodeDict dd = decode_dict(d);
+    e = dctx_sync_slots(d, dd); if (isErr(e)) return e;
     const u32 nR = (u32)n;
     if (!d->rangesWs.ensure(ranges_ws_bytes(N)) || !d->batchIn.ensure((size_t)N * sizeof(BatchEntryIn) + 64) ||
         !d->rangesIn.ensure(n * sizeof(RangeIn)) || !d->rangesRec.ensure(n * sizeof(RangeRec)) || !d->rangesRes.ensure(n * sizeof(u64))) return ZERR(kErrMemoryAllocation);
@@ -820,7 +899,8 @@ static size_t ZSTDMI_decompressDevice_impl(ZSTD_DCtx* d, void* d_dst, size_t dst
 {
     if (!d) return ZERR(kErrGeneric);
     PrefixUse use(d);
-    size_t e = dctx_bind(d); if (isErr(e)) return e;
+    size_t e = set_check(d); if (isErr(e)) return e;
+    e = dctx_bind(d); if (isErr(e)) return e;
     e = use.begin(); if (isErr(e)) return e;
     if (srcSize && !d_src) return ZERR(kErrSrcSizeWrong);
     if (d->workers.size() > 1 && srcSize) return decompress_multi(d, d_dst, dstCapacity, d_src, srcSize);
@@ -831,7 +911,8 @@ static size_t ZSTD_decompressDCtx_impl(ZSTD_DCtx* d, void* dst, size_t dstCapaci
 {
     if (!d) return ZERR(kErrGeneric);
     PrefixUse use(d);
-    size_t e = dctx_bind(d); if (isErr(e)) return e;
+    size_t e = set_check(d); if (isErr(e)) return e;
+    e = dctx_bind(d); if (isErr(e)) return e;
     e = use.begin(); if (isErr(e)) return e;
     if (srcSize && !src) return ZERR(kErrSrcSizeWrong);
     if (srcSize == 0) return 0;
@@ -1244,6 +1325,7 @@ static size_t ZSTD_decompressStream_impl(ZSTD_DCtx* d, ZSTD_outBuffer* output, Z
     if (input->size > input->pos && !input->src) return ZERR(kErrSrcSizeWrong);
     if (output->size > output->pos && !output->dst) return ZERR(kErrDstBufferNull);
     if (d->pfx) return ZERR(kErrParameterUnsupported);         // (a referenced prefix serves one single call)
+    { const size_t e = set_check(d, d->segBytes != 0); if (isErr(e)) return e; }       // (a DDict set serves whole frames only)
     if (d->segBytes || d->seg.active || d->seg.skip) return stream_segmented(d, output, input);     // (a frame begun in segments ends in segments)
     if (d->hostage && input->pos < input->size) { input->pos++; d->hostage = false; }       // that byte was consumed earlier
     size_t pending = dstream_drain(d, output);
@@ -1339,8 +1421,12 @@ size_t ZSTD_DCtx_refDDict(ZSTD_DCtx* d, const ZSTD_DDict* ddict)
 {
     if (!d) return ZERR(kErrGeneric);
     return guarded([&]() -> size_t {
+        // ZSTD_d_refMultipleDDicts: the DDict also joins the set, replacing an entry of equal dictID (U/ZstdDecompress.cs:2319-2333); a set
+        // that cannot take it leaves the context as it was.  NULL clears the current DDict only (ZSTD_clearDict).  No device is touched.
+        if (ddict && d->refMultiple && !d->ddictSet.insert(ZSTD_getDictID_fromDDict(ddict), ddict)) return ZERR(kErrMemoryAllocation);
         d->pfx = nullptr; d->pfxSize = 0;       // ZSTD_clearAllDicts: a loaded dictionary and a pending prefix are gone
         d->ddict = ddict;
+        d->setGen++;
         dctx_adopt_ddict(d);
         return 0;
     });
@@ -1351,11 +1437,12 @@ size_t ZSTD_decompress_usingDDict(ZSTD_DCtx* d, void* dst, size_t dstCapacity, c
     // the context's own dictionary or reference and a pending prefix step aside for the call and are left as found (where the DDict
     // cannot be shared, the context's bytes are uploaded again by their next use)
     return guarded([&]() -> size_t {
-        d->lastDictTabBlocks = 0;
+        d->lastDictTabBlocks = d->lastSetFrames = 0;
         const ZSTD_DDict_s* const was = d->ddict;
         const void* const pfx = d->pfx; const size_t pfxSize = d->pfxSize;
         d->pfx = nullptr; d->pfxSize = 0;
         d->ddict = ddict;
+        const int multi = d->refMultiple; d->refMultiple = 0;       // ONE call behind this DDict alone: the set steps aside too (and its image stays good)
         size_t r;
         if (ddict_shared(d)) r = ZSTD_decompressDCtx_impl(d, dst, dstCapacity, src, srcSize);
         else {
@@ -1365,7 +1452,7 @@ size_t ZSTD_decompress_usingDDict(ZSTD_DCtx* d, void* dst, size_t dstCapacity, c
             catch (...) { r = ZERR(kErrMemoryAllocation); }
             d->dictHost.swap(h); d->dictFormatted = fmt; d->dictDirty = true; d->dictGen++;
         }
-        d->ddict = was; d->pfx = pfx; d->pfxSize = pfxSize;
+        d->ddict = was; d->pfx = pfx; d->pfxSize = pfxSize; d->refMultiple = multi;
         return r;
     });
 }
@@ -1377,16 +1464,18 @@ long long ZSTDMI_debugDictUploadsD(const ZSTD_DCtx* d)
     return n;
 }
 long long ZSTDMI_debugLastDictTableBlocks(const ZSTD_DCtx* d) { return d ? d->lastDictTabBlocks : -1; }
+long long ZSTDMI_debugLastSetFrames(const ZSTD_DCtx* d) { return d ? d->lastSetFrames : -1; }
 // host memory in, no device touched (zmi_dictid.h)
 unsigned ZSTD_getDictID_fromDict(const void* dict, size_t dictSize) { return dictid_from_dict((const u8*)dict, dictSize); }
 unsigned ZSTD_getDictID_fromFrame(const void* src, size_t srcSize) { return dictid_from_frame((const u8*)src, srcSize); }
 
 // ---------------- extensions ----------------
 // (a referenced DDict is shared or copied by where the context runs: dctx_adopt_ddict)
-size_t ZSTDMI_DCtx_setDevice(ZSTD_DCtx* d, int device) { const size_t e = ctx_set_device(d, device); if (d && d->ddict) (void)guarded([&]() -> size_t { dctx_adopt_ddict(d); return 0; }); return e; }
+size_t ZSTDMI_DCtx_setDevice(ZSTD_DCtx* d, int device) { const size_t e = ctx_set_device(d, device); if (d) d->setGen++; if (d && d->ddict) (void)guarded([&]() -> size_t { dctx_adopt_ddict(d); return 0; }); return e; }
 size_t ZSTDMI_DCtx_setDevices(ZSTD_DCtx* d, const int* devices, int n)
 {
     const size_t e = ctx_set_devices(d, devices, n, ZSTD_createDCtx, ZSTD_freeDCtx);
+    if (d) d->setGen++;
     if (d && d->ddict) (void)guarded([&]() -> size_t { dctx_adopt_ddict(d); return 0; });
     return e;
 }
@@ -1427,29 +1516,29 @@ size_t ZSTD_DCtx_refPrefix(ZSTD_DCtx* d, const void* prefix, size_t prefixSize)
     return 0;
 }
 size_t ZSTD_findFrameCompressedSize(const void* src, size_t srcSize) { return guarded([&] { return ZSTD_findFrameCompressedSize_impl(src, srcSize); }); }
-size_t ZSTD_decompressDCtx(ZSTD_DCtx* d, void* dst, size_t dstCapacity, const void* src, size_t srcSize) { return guarded([&] { if (d) d->lastDictTabBlocks = 0; return ZSTD_decompressDCtx_impl(d, dst, dstCapacity, src, srcSize); }); }
+size_t ZSTD_decompressDCtx(ZSTD_DCtx* d, void* dst, size_t dstCapacity, const void* src, size_t srcSize) { return guarded([&] { if (d) d->lastDictTabBlocks = d->lastSetFrames = 0; return ZSTD_decompressDCtx_impl(d, dst, dstCapacity, src, srcSize); }); }
 size_t ZSTDMI_decompressBatch(ZSTD_DCtx* d, const void* const* srcs, const size_t* srcSizes, size_t n, void* const* dsts, const size_t* dstCapacities, size_t* dstSizes)
 {
-    return guarded([&] { if (d) d->lastDictTabBlocks = 0; return decompress_batch_impl(d, srcs, srcSizes, n, dsts, dstCapacities, dstSizes); });
+    return guarded([&] { if (d) d->lastDictTabBlocks = d->lastSetFrames = 0; return decompress_batch_impl(d, srcs, srcSizes, n, dsts, dstCapacities, dstSizes); });
 }
 int ZSTDMI_debugLastBatchAloneD(const ZSTD_DCtx* d) { return d ? d->lastBatchAlone : -1; }
 size_t ZSTDMI_decompressRange(ZSTD_DCtx* d, void* dst, size_t dstCapacity, const void* src, size_t srcSize, unsigned long long offset, size_t length)
 {
     if (!d) return ZERR(kErrGeneric);
-    return guarded([&] { d->lastDictTabBlocks = 0; return decompress_range_impl(d, dst, dstCapacity, src, srcSize, offset, length); });
+    return guarded([&] { d->lastDictTabBlocks = d->lastSetFrames = 0; return decompress_range_impl(d, dst, dstCapacity, src, srcSize, offset, length); });
 }
 int ZSTDMI_debugLastRangeFrames(const ZSTD_DCtx* d) { return d ? d->lastRangeFrames : -1; }
 long long ZSTDMI_debugLastRangeStaged(const ZSTD_DCtx* d) { return d ? d->lastRangeStaged : -1; }
 size_t ZSTDMI_decompressRanges(ZSTD_DCtx* d, const void* src, size_t srcSize, const unsigned long long* offsets, const size_t* lengths, size_t n,
                                void* const* dsts, const size_t* dstCapacities, size_t* dstSizes)
 {
-    return guarded([&] { if (d) d->lastDictTabBlocks = 0; return decompress_ranges_impl(d, src, srcSize, offsets, lengths, n, dsts, dstCapacities, dstSizes); });
+    return guarded([&] { if (d) d->lastDictTabBlocks = d->lastSetFrames = 0; return decompress_ranges_impl(d, src, srcSize, offsets, lengths, n, dsts, dstCapacities, dstSizes); });
 }
 int ZSTDMI_debugLastRangesFrames(const ZSTD_DCtx* d) { return d ? d->lastRangesFrames : -1; }
 int ZSTDMI_debugLastRangesAlone(const ZSTD_DCtx* d) { return d ? d->lastRangesAlone : -1; }
 long long ZSTDMI_debugLastRangesStaged(const ZSTD_DCtx* d) { return d ? d->lastRangesStaged : -1; }
-size_t ZSTDMI_decompressDevice(ZSTD_DCtx* d, void* d_dst, size_t dstCapacity, const void* d_src, size_t srcSize) { return guarded([&] { if (d) d->lastDictTabBlocks = 0; return ZSTDMI_decompressDevice_impl(d, d_dst, dstCapacity, d_src, srcSize); }); }
-size_t ZSTD_decompressStream(ZSTD_DCtx* d, ZSTD_outBuffer* output, ZSTD_inBuffer* input) { return guarded([&] { if (d) d->lastDictTabBlocks = 0; return ZSTD_decompressStream_impl(d, output, input); }); }
+size_t ZSTDMI_decompressDevice(ZSTD_DCtx* d, void* d_dst, size_t dstCapacity, const void* d_src, size_t srcSize) { return guarded([&] { if (d) d->lastDictTabBlocks = d->lastSetFrames = 0; return ZSTDMI_decompressDevice_impl(d, d_dst, dstCapacity, d_src, srcSize); }); }
+size_t ZSTD_decompressStream(ZSTD_DCtx* d, ZSTD_outBuffer* output, ZSTD_inBuffer* input) { return guarded([&] { if (d) d->lastDictTabBlocks = d->lastSetFrames = 0; return ZSTD_decompressStream_impl(d, output, input); }); }
 unsigned long long ZSTD_decompressBound(const void* src, size_t srcSize)
 {
     try { return ZSTD_decompressBound_impl(src, srcSize); } catch (...) { return (unsigned long long)0 - 2; }      /* ZSTD_CONTENTSIZE_ERROR */

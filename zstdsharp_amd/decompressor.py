@@ -6,6 +6,13 @@ from .compressor import _PrefixHolder, _as_buffer, _as_prefix
 from .errors import DST_SIZE_TOO_SMALL, ZstdException, ZSTD_ErrorCode, ensure_content_size_ok, ensure_zstd_success, get_error_code, is_error
 
 
+# ZSTD_DCtx_setParameter's parameters (include/zstd_mi355x.h) and the values of ZSTD_d_refMultipleDDicts
+ZSTD_d_windowLogMax = 100
+ZSTD_d_refMultipleDDicts = 1003
+ZSTD_rmd_refSingleDDict = 0
+ZSTD_rmd_refMultipleDDicts = 1
+
+
 class Decompressor(_PrefixHolder):
     """S/Decompressor.cs:7-148."""
 
@@ -16,6 +23,7 @@ class Decompressor(_PrefixHolder):
             raise MemoryError("ZSTD_createDCtx")
         self._stream_segment = 0
         self._ddict = None              # the DDict RefDDict holds
+        self._ddict_set = {}            # ZSTD_d_refMultipleDDicts: dictID -> every DDict the context's set references (until Dispose)
         if device is not None:
             ensure_zstd_success(self._lib, self._lib.ZSTDMI_DCtx_setDevice(self.dctx, device))
 
@@ -58,8 +66,11 @@ class Decompressor(_PrefixHolder):
         if ddict is not None:
             ddict._ensure_not_disposed()
         self._release_prefix()
+        multiple = ddict is not None and self.GetParameter(ZSTD_d_refMultipleDDicts) == ZSTD_rmd_refMultipleDDicts
         ensure_zstd_success(self._lib, self._lib.ZSTD_DCtx_refDDict(self.dctx, ddict.handle if ddict is not None else None))
         self._ddict = ddict
+        if multiple:                    # the context's set took it (an equal dictID replaced): none may be collected while it may be selected
+            self._ddict_set[ddict.dict_id] = ddict
 
     def UnwrapUsingDDict(self, src, ddict, maxDecompressedSize: int = (1 << 31) - 1):
         """ZSTD_decompress_usingDDict: src -> bytes, ONE call behind the DDict; this object's dictionary or reference is left as it is."""
@@ -209,6 +220,8 @@ class Decompressor(_PrefixHolder):
         if getattr(self, "dctx", None):
             self._lib.ZSTD_freeDCtx(self.dctx)
             self.dctx = None
+            self._ddict = None
+            self._ddict_set = {}        # (the set went with the context: its DDicts are the caller's again)
 
     dispose = close = Dispose
 
