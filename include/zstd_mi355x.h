@@ -137,8 +137,8 @@ size_t     ZSTD_decompressDCtx(ZSTD_DCtx* dctx, void* dst, size_t dstCapacity, c
  * referencing it and switching between several touches no device and uploads nothing.  Lifetime is the caller's, as in libzstd: an
  * object must outlive every context that references it, and ZSTD_freeCCtx / ZSTD_freeDCtx never touch it.
  * Not provided: ZSTD_createCDict_byReference / ZSTD_createDDict_byReference (the bytes are always copied), the *_advanced
- * constructors and ZSTD_estimateCDictSize; per-entry dictionaries in ZSTDMI_compressBatch (the compressor's side of
- * ZSTD_d_refMultipleDDicts, below), a DDict set for segmented streams and a DDict set with several device workers.
+ * constructors and ZSTD_estimateCDictSize; a DDict set for segmented streams and a DDict set with several device workers.  (The
+ * compressor's side of ZSTD_d_refMultipleDDicts, below, is ZSTDMI_compressBatchCDicts: a CDict per entry of a batch.)
  *
  * ZSTD_createCDict: `dict` is host or device memory; the bytes are copied.  compressionLevel 0 means 3 (U/ZstdCompress.cs:5991).  It is
  * created on the device a fresh context binds (ordinal 0; ZSTDMI_createCDictOnDevice for another) and holds there the staged tail, the
@@ -388,6 +388,32 @@ size_t ZSTDMI_decompressBatch(ZSTD_DCtx* dctx, const void* const* srcs, const si
 /* diagnostics: entries of the last batch call that did NOT take the batched pass (handed to the single-call path); -1 without a context */
 int ZSTDMI_debugLastBatchAlone(const ZSTD_CCtx* cctx);
 int ZSTDMI_debugLastBatchAloneD(const ZSTD_DCtx* dctx);
+/* ---- a CDict per entry: many dictionaries, one compress pass (the compressor's side of ZSTD_d_refMultipleDDicts) ----
+ * The arrays and pointers are those of ZSTDMI_compressBatch; cdicts is a host array of n entries, cdicts[i] == NULL: entry i has no
+ * dictionary.  Per entry, dstSizes[i] (a size or an error code) and the bytes at dsts[i] are exactly what ZSTD_CCtx_refCDict(cctx,
+ * cdicts[i]) followed by ZSTDMI_compressBatch on entry i alone gives: the context's sticky parameters and its four dictionary switches
+ * (ZSTDMI_CCtx_setDictEntropy / setDictIndex / setDictIndexStrategy / setDictIndexChain) apply, the CDict's level stands in for
+ * ZSTD_c_compressionLevel, a NULL entry runs at the context's own level without a dictionary.  The context's own loaded dictionary,
+ * CDict reference or set is never consulted, and it and every other state is left as found.  One entry's failure changes nothing of
+ * another's.
+ * How.  Entries share a pass by what has to be equal for their blocks to share a kernel launch — the block size (behind a staged
+ * dictionary tail: 64 KiB minus the tail rounded up to 4 KiB), blocks per frame, indexed or not, and the parameters the CDict's level
+ * resolves to — not by the dictionary: a pass behind two or more CDicts uploads one record per CDict and one index per block, and
+ * every stage that takes the dictionary as launch constants runs an instance that reads it per block from there.  (Entries of which
+ * nothing is staged or indexed — no dictionary, a CDict under 8 bytes — run the plain finder and share passes per CDict.)  A pass
+ * behind one CDict launches what ZSTDMI_compressBatch launches.
+ * Whole-call answers: n == 0: 0, no device is touched.  A NULL context, or any NULL array (cdicts included) with n > 0: GENERIC.  No
+ * device: init_missing.  memory_allocation.  parameter_unsupported, before a byte is read: several device workers, the seek-table
+ * switch, a pending ZSTD_CCtx_refPrefix (which stays pending), more than 65536 distinct CDicts (NULL entries are no CDict and do not
+ * count), or two or more distinct non-NULL CDicts of which one lives on another device than the context (a single such CDict beside
+ * NULL entries is served by the context's private upload of it, as after ZSTD_CCtx_refCDict).  A call whose entries all name one CDict (or all NULL) IS ZSTD_CCtx_refCDict +
+ * ZSTDMI_compressBatch — the same kernels, the private upload where the digest cannot be shared — after which the context's own
+ * reference is back. */
+size_t ZSTDMI_compressBatchCDicts(ZSTD_CCtx* cctx, const void* const* srcs, const size_t* srcSizes, size_t n,
+                                  void* const* dsts, const size_t* dstCapacities, size_t* dstSizes,
+                                  const ZSTD_CDict* const* cdicts);
+long long ZSTDMI_debugLastBatchPasses(const ZSTD_CCtx* cctx);     /* passes through the pipeline the last batch call made (either entry point; entries that went alone are ZSTDMI_debugLastBatchAlone's); -1 without a context */
+long long ZSTDMI_debugLastBatchSetChunks(const ZSTD_CCtx* cctx);  /* chunks of the last batch call that ran in set instances; 0 whenever the single-dictionary kernels ran; -1 without a context */
 
 /* Packs: n device buffers into ONE contiguous, standard seekable stream whose frames end exactly at the entries' boundaries — the write
  * side of ZSTDMI_decompressRanges.  srcs and srcSizes are host arrays; srcs[i] and d_dst are device pointers as for ZSTDMI_compressBatch,

@@ -115,7 +115,11 @@ SIGNATURES = {
                                         ctypes.POINTER(c_void_p), ctypes.POINTER(c_size_t), ctypes.POINTER(c_size_t)]),
     "ZSTDMI_decompressBatch": (c_size_t, [c_void_p, ctypes.POINTER(c_void_p), ctypes.POINTER(c_size_t), c_size_t,
                                           ctypes.POINTER(c_void_p), ctypes.POINTER(c_size_t), ctypes.POINTER(c_size_t)]),
+    "ZSTDMI_compressBatchCDicts": (c_size_t, [c_void_p, ctypes.POINTER(c_void_p), ctypes.POINTER(c_size_t), c_size_t,
+                                              ctypes.POINTER(c_void_p), ctypes.POINTER(c_size_t), ctypes.POINTER(c_size_t), ctypes.POINTER(c_void_p)]),
     "ZSTDMI_debugLastBatchAlone": (c_int, [c_void_p]),
+    "ZSTDMI_debugLastBatchPasses": (ctypes.c_longlong, [c_void_p]),
+    "ZSTDMI_debugLastBatchSetChunks": (ctypes.c_longlong, [c_void_p]),
     "ZSTDMI_debugLastBatchAloneD": (c_int, [c_void_p]),
     "ZSTDMI_packBound": (c_size_t, [ctypes.POINTER(c_size_t), c_size_t]),
     "ZSTDMI_compressPack": (c_size_t, [c_void_p, c_void_p, c_size_t, ctypes.POINTER(c_void_p), ctypes.POINTER(c_size_t), c_size_t]),

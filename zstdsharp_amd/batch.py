@@ -79,20 +79,36 @@ def decompress_batch(decompressor, items, sizes):
     return out
 
 
-def compress_batch(compressor, items):
+def compress_batch(compressor, items, cdicts=None):
     """items: a list of torch CUDA uint8 tensors (-> a list of CUDA uint8 tensors, views of one buffer) or of bytes-like objects
     (uploaded in one copy -> a list of bytes).  Uses the compressor's level, parameters and dictionary.  An item that fails raises
-    ZstdException naming its index."""
+    ZstdException naming its index.
+    cdicts (ZSTDMI_compressBatchCDicts): one dictionaries.CDict or None per item.  Item i is then written as after RefCDict(cdicts[i]) —
+    at that CDict's level, behind it alone, None = no dictionary — whatever dictionary the compressor itself holds, and items behind
+    different CDicts share passes.  The CDicts stay referenced until the call returns."""
     import torch
     compressor._ensure_not_disposed()
     lib = compressor._lib
     items = list(items)
     n = len(items)
+    if cdicts is not None:
+        cdicts = list(cdicts)
+        if len(cdicts) != n:
+            raise ValueError("one CDict (or None) per item")
+        for d in cdicts:
+            if d is not None:
+                d._ensure_not_disposed()
     if n == 0:
         return []
     tensors, device, sizes, srcs, keep = _gather(torch, items)
-    out = _run(torch, lib, lib.ZSTDMI_compressBatch, compressor.cctx, device, srcs, sizes, [lib.ZSTD_compressBound(x) for x in sizes], tensors)
-    del keep
+    call = lib.ZSTDMI_compressBatch
+    if cdicts is not None:
+        handles = _pointer_array([d.handle if d is not None else None for d in cdicts])
+
+        def call(ctx, srcs_, sizes_, n_, dsts_, caps_, got_):
+            return lib.ZSTDMI_compressBatchCDicts(ctx, srcs_, sizes_, n_, dsts_, caps_, got_, handles)
+    out = _run(torch, lib, call, compressor.cctx, device, srcs, sizes, [lib.ZSTD_compressBound(x) for x in sizes], tensors)
+    del keep, cdicts
     return out
 
 

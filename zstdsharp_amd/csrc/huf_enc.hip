@@ -470,12 +470,21 @@ __global__ __launch_bounds__(64) void huf_hist_kernel(const u8* __restrict__ lit
 // block's own tree unless the old table costs no more than the new one with its description.  What the old table costs follows
 // from the histograms in registers.  A block coded with it gets kLitTreeless and a copy of the dictionary's codes as its table.
 // The instance without DICT is the code from before the switch existed.
-template <bool DICT>
+// SET (ZSTDMI_compressBatchCDicts, zmi_cdictset.h; on the DICT instance): the chunk's tables come from dictSlots[chunkSlot[c]].dct, one
+// scalar load per workgroup; null there means "this chunk has no dictionary tables", and it comes out as the instance without DICT
+// writes it (dMode stays kDictHufNone, which switches every DICT step off).
+// (The kernel is a template on SET itself, which costs the other instances a `false` in their mangled names: as an inlined body behind
+// two kernels, huf_tree_kernel<true> / <false> came out with 52 / 45 SGPR spills for the 56 / 46 they have.  dictSlots and chunkSlot
+// are arguments of every instance; the instances without SET never load them.)
+template <bool DICT, bool SET = false>
 __global__ __launch_bounds__(64) void huf_tree_kernel(ChunkMeta* __restrict__ meta, HufTable* __restrict__ tables, const u8* __restrict__ slots,
-                                                      const u32 rawLiterals, const DictCTables* __restrict__ dct, const u32 frameBlocks)
+                                                      const u32 rawLiterals, const DictCTables* __restrict__ dctArg, const u32 frameBlocks,
+                                                      const CDictSlot* __restrict__ dictSlots, const u32* __restrict__ chunkSlot)
 {
+    static_assert(!SET || DICT, "the set form stands on the DICT instance");
     __shared__ HufTreeLds L;
     const u32 c = blockIdx.x, lane = threadIdx.x, tid = lane;
+    const DictCTables* __restrict__ const dct = SET ? dictSlots[chunkSlot[c]].dct : dctArg;
     // (the record is written back field by field: a whole-struct copy kept across the kernel went through scratch memory)
     const ChunkMeta m = meta_checked(meta[c]);
     ChunkMeta* const mOut = meta + c;
@@ -491,7 +500,7 @@ __global__ __launch_bounds__(64) void huf_tree_kernel(ChunkMeta* __restrict__ me
 #endif
     // the dictionary's table stands behind a frame's first block only (a later block never writes a treeless section)
     u32 dMode = kDictHufNone;
-    if (DICT) { if (!frameBlocks || block_index(c, frameBlocks) == 0) dMode = dct->hufMode; }
+    if (DICT && (!SET || dct)) { if (!frameBlocks || block_index(c, frameBlocks) == 0) dMode = dct->hufMode; }
     // ZSTD_compressLiterals: <= 63 literals are stored raw (no previous table in a one-block frame)
     if (litSize <= ((DICT && dMode == kDictHufValid) ? 6u : 63u) || rawLiterals) {        // (or ZSTD_noCompressLiterals because literal compression is disabled, U/ZstdCompressLiterals.cs:99-101)
         if (tid == 0) store_section(kLitRaw, lhSizeRaw, lhSizeRaw + litSize);
@@ -963,9 +972,11 @@ __global__ __launch_bounds__(256) void huf_encode_kernel(const u8* __restrict__ 
 // dct != nullptr: the first block of every frame (frames as in seq_encode) may reuse the dictionary's table; a dictionary's framing
 // counts the blocks of a frame by the chunk's index
 void launch_huf_build(const u8* lits, ChunkMeta* meta, HufTable* tables, u8* slots, u32 nChunks, u32 rawLiterals, const u8* src, const FrameLayout& frames,
-                      hipStream_t stream, StageHook hook, const DictCTables* dct)
+                      hipStream_t stream, StageHook hook, const DictCTables* dct, const CDictSlot* dictSlots, const u32* chunkSlot)
 {
-    assert(!dct || frames.form == kArith);
+    assert((!dct && !dictSlots) || frames.form == kArith);
+    assert(!dictSlots == !chunkSlot);
+    // (a set pass: dct != null says that one of its slots has tables — the short-literal histograms are wanted — and is not read)
     const u32 chunkBytes = frames.chunkBytes, frameBlocks = frames.frameBlocks;
     // a throughput kernel: a wave per (chunk, stream) item while that keeps every CU's share short, several items per wave beyond
     const u32 nItems = 4 * nChunks, perWave = (nItems + kHistItemsPerWave - 1) / kHistItemsPerWave;
@@ -973,8 +984,9 @@ void launch_huf_build(const u8* lits, ChunkMeta* meta, HufTable* tables, u8* slo
     if (dct) hipLaunchKernelGGL(huf_hist_kernel<6>, dim3(grid), dim3(64), 0, stream, lits, meta, slots, rawLiterals, src, chunkBytes, nItems);
     else hipLaunchKernelGGL(huf_hist_kernel<63>, dim3(grid), dim3(64), 0, stream, lits, meta, slots, rawLiterals, src, chunkBytes, nItems);
     hook("huf_hist");
-    if (dct) hipLaunchKernelGGL(huf_tree_kernel<true>, dim3(nChunks), dim3(64), 0, stream, meta, tables, slots, rawLiterals, dct, frameBlocks);
-    else hipLaunchKernelGGL(huf_tree_kernel<false>, dim3(nChunks), dim3(64), 0, stream, meta, tables, slots, rawLiterals, dct, frameBlocks);
+    if (dictSlots && dct) hipLaunchKernelGGL((huf_tree_kernel<true, true>), dim3(nChunks), dim3(64), 0, stream, meta, tables, slots, rawLiterals, dct, frameBlocks, dictSlots, chunkSlot);
+    else if (dct) hipLaunchKernelGGL((huf_tree_kernel<true>), dim3(nChunks), dim3(64), 0, stream, meta, tables, slots, rawLiterals, dct, frameBlocks, dictSlots, chunkSlot);
+    else hipLaunchKernelGGL((huf_tree_kernel<false>), dim3(nChunks), dim3(64), 0, stream, meta, tables, slots, rawLiterals, dct, frameBlocks, dictSlots, chunkSlot);
     hook("huf_tree");
 }
 void launch_huf_encode(const u8* lits, const ChunkMeta* meta, const HufTable* tables, u8* slots, u8* dst, const u64* offsets, u64 dstCapacity,

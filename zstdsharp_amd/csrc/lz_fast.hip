@@ -976,6 +976,19 @@ __device__ __forceinline__ void dense_rest(LzLds& L, const u32 n, const u32 inse
 // They are loaded BEHIND the probe barrier, at the head of the position's verification (DESIGN.md 3a says why), and looked at after
 // its four in-block candidates.
 constexpr int kPlaceIndexed = 3;         // beside FrameForm's three values: lz_kernel's TAB alone takes it
+// The SET forms (ZSTDMI_compressBatchCDicts, zmi_cdictset.h): a batch's pass behind two or more dictionaries.  kArithSet (on the DICT
+// instances; every chunk a frame of its own, as a dictionary's framing makes them): the staged tail and its length come per chunk from
+// LzArgs::slots[chunkSlot[c]] — hist and chunkBytes stay the launch's, a pass holds tails of one tile count.  kPlaceIndexedSet: the
+// indexed dictionary comes from there.  Both take the size of the header's dictID field from the slot.  The chunk index is the same in
+// every lane, so these are scalar loads at the head of a chunk: SGPRs, no VGPR.  Instances of their own (TAB values), so that the
+// kernels of every call behind one dictionary are the ones from before the forms existed.
+constexpr int kArithSet = 4, kPlaceIndexedSet = 5;
+constexpr bool lz_tab_set(int tab) { return tab == kArithSet || tab == kPlaceIndexedSet; }
+constexpr bool lz_tab_indexed(int tab) { return tab == kPlaceIndexed || tab == kPlaceIndexedSet; }
+constexpr int lz_tab_place(int tab) { return (lz_tab_set(tab) || lz_tab_indexed(tab)) ? (int)kArith : tab; }
+// A slot is read through the constant address space: nothing writes the table while a kernel runs, so its loads are invariant and the
+// compiler may repeat one where it would otherwise keep the value in a register through a chunk (these kernels have none to spare).
+typedef const __attribute__((address_space(4))) CDictSlot* SlotRef;
 // What lz_kernel is launched with: launch_one fills it from LzLaunch (zmi_host.h, which says what the fields hold).
 // fh: the frame header (zmi_frame.h), of which the finder needs the size: it leaves in ChunkMeta::fhSize what seq_encode_kernel will write.
 // frameBlocksArg: frame_blocks_encode.  cand, regionList: null = no region parse.  claimCtr: null = chunk c + gridDim.x is next.
@@ -989,6 +1002,7 @@ struct LzArgs {
     const u32* chunkLens; const u32* chunkFrames;
     u64 frameAt, frameTotal;
     DictIndexRef dix;
+    const CDictSlot* slots; const u32* chunkSlot;       // the SET forms
 };
 template <int MODE, bool DICT, bool FAR, int TAB>
 __global__ __launch_bounds__(1024) void lz_kernel(const LzArgs a)
@@ -1010,8 +1024,9 @@ __global__ __launch_bounds__(1024) void lz_kernel(const LzArgs a)
     // workgroup's first arrives prefetched (a stamped build had 42 % of an unprefetched Zipf chunk's time in this load).  The claim
     // is made one chunk ahead of the prefetch (thread 0 holds the answer in a register through a chunk), so nobody waits for it.
     constexpr bool kPrefetch = MODE == 0 && !DICT && !FAR;      // (the dual-hash finders have no 16 registers to spare)
-    constexpr bool kIndexed = TAB == kPlaceIndexed;
-    constexpr int kPlaceForm = kIndexed ? kArith : TAB;
+    constexpr bool kIndexed = lz_tab_indexed(TAB), kSet = lz_tab_set(TAB);
+    constexpr int kPlaceForm = lz_tab_place(TAB);
+    static_assert(!kSet || (kIndexed ? (FAR && !DICT) : (DICT && !FAR)), "a set form stands on its twin's instance");
     uint4 pf0 = {0, 0, 0, 0}, pf1 = pf0, pf2 = pf0, pf3 = pf0; bool pfValid = false;
     const bool claiming = kPrefetch && claimCtr != nullptr;     // uniform
     u32 claimed = 0;                                            // thread 0: the chunk after the next
@@ -1031,10 +1046,14 @@ __global__ __launch_bounds__(1024) void lz_kernel(const LzArgs a)
     const u64 base = (u64)c * cb;
     const u8* __restrict__ in = src + base;
     // the byte behind the far history's last: the block itself, or the end of an indexed dictionary
-    const u8* __restrict__ const farEnd = kIndexed ? a.dix.end : in;
-    const u32* __restrict__ const dictIdx = !kIndexed ? nullptr : MODE == 0 ? a.dix.table : a.dix.tableLong;
-    const u32 dictLog = kIndexed ? a.dix.log : 0u;
-    const u32* __restrict__ const dictIdxS = (kIndexed && MODE != 0) ? a.dix.tableShort : nullptr;
+    // (a set form: the chunk's dictionary, and the header's dictID bytes with it, from the pass's slot table)
+    const SlotRef slot = kSet ? (SlotRef)(a.slots + a.chunkSlot[c]) : nullptr;
+    FrameHeaderSpec fhc = fh;
+    if (kSet) fhc.dictIdBytes = (u8)slot->dictIdBytes;
+    const u8* __restrict__ const farEnd = !kIndexed ? in : kSet ? slot->dix.end : a.dix.end;
+    const u32* __restrict__ const dictIdx = !kIndexed ? nullptr : MODE == 0 ? (kSet ? slot->dix.table : a.dix.table) : (kSet ? slot->dix.tableLong : a.dix.tableLong);
+    const u32 dictLog = !kIndexed ? 0u : kSet ? slot->dix.log : a.dix.log;
+    const u32* __restrict__ const dictIdxS = !(kIndexed && MODE != 0) ? nullptr : kSet ? slot->dix.tableShort : a.dix.tableShort;
     // (independent blocks — windows below 64 KiB, where a block IS the window: no history; a dictionary is history of the frame's
     //  first block only, whose image is the layout the decoder sees)
     const u32 frameBlocks = frame_blocks_decode(a.frameBlocksArg).frameBlocks;
@@ -1045,8 +1064,8 @@ __global__ __launch_bounds__(1024) void lz_kernel(const LzArgs a)
     const FrameLayout frames = { kPlaceForm, cb, frameBlocks, srcSize, chunkFrames, frameAt, frameTotal };
     const BlockPlace place = framed ? block_place<kPlaceForm>(frames, c) : block_alone(0);
     const u32 bf = place.block;
-    const u32 farAvail = FAR ? kIndexed ? a.dix.len : place.front < kFarMax ? (u32)place.front : kFarMax : 0u;      // bytes of far history in front of the block
-    u32 prefixLen = a.prefixLen; const u8* __restrict__ prefix = a.prefix;
+    const u32 farAvail = FAR ? kIndexed ? (kSet ? slot->dix.len : a.dix.len) : place.front < kFarMax ? (u32)place.front : kFarMax : 0u;      // bytes of far history in front of the block
+    u32 prefixLen = (kSet && DICT) ? slot->tailLen : a.prefixLen; const u8* __restrict__ prefix = (kSet && DICT) ? slot->tail : a.prefix;
     if (DICT && frameBlocks && !indep) { prefixLen = place.front < hist ? (u32)place.front : hist; prefix = in - prefixLen; }
     if (DICT && indep && bf) prefixLen = 0;
     const u32 lowLimit = DICT ? hist - prefixLen : 0u;
@@ -1747,8 +1766,8 @@ __global__ __launch_bounds__(1024) void lz_kernel(const LzArgs a)
         m.srcSize = nData; m.nbSeq = nbSeq; m.litSize = litBase;
         // only a frame's first block carries the frame header, sized for the whole frame's content (worked out here, behind the
         // parse, so that the frame's length does not live through it)
-        if (framed) m.fhSize = bf == 0 ? frame_header_bytes(fh, block_place<kPlaceForm>(frames, c).frameLen) : 0u;
-        else m.fhSize = frame_header_bytes(fh, nData);
+        if (framed) m.fhSize = bf == 0 ? frame_header_bytes(fhc, block_place<kPlaceForm>(frames, c).frameLen) : 0u;
+        else m.fhSize = frame_header_bytes(fhc, nData);
         m.litFromSrc = deferred ? 1u : 0u;       // (then nbSeq = 0 and litBase = nData: the literals are the chunk itself)
         m.regionCursor = regionCursor;
         meta[c] = m;
@@ -1772,15 +1791,21 @@ __global__ __launch_bounds__(1024) void lz_kernel(const LzArgs a)
 struct RegionDix { DictIndexRef dix; u32* dist; };      // dist: 65536 u32 per workgroup (dense_rest's distG)
 __device__ __forceinline__ RegionDix region_dix() { return RegionDix{}; }
 __device__ __forceinline__ const RegionDix& region_dix(const RegionDix& r) { return r; }
+// The SET forms (see lz_kernel): kArithSet on the staged instance, kPlaceIndexedSet on the indexed one.  Their one extra argument is the
+// pass's slot table with the per-chunk index, and, for the indexed form, dist as in RegionDix.  The chunk comes from the work list: the
+// same in every lane, so the slot's fields are scalar loads here too.
+struct RegionSet { const CDictSlot* slots; const u32* chunkSlot; u32* dist; };
+__device__ __forceinline__ const RegionSet& region_dix(const RegionSet& r) { return r; }
 template <int MODE, bool DICT, int TAB, class... DX>
 __global__ __launch_bounds__(1024) void lz_region_kernel(const u8* __restrict__ src, u64 srcSize, Seq* __restrict__ seqs, u8* __restrict__ lits,
                                                          ChunkMeta* __restrict__ meta, u16* __restrict__ candAll, u16* __restrict__ chainAll, const u32* __restrict__ regionList,
                                                          const u8* __restrict__ prefixArg, const u32 prefixLenArg, const u32 chunkBytes, const u32 frameBlocksArg, const u32 hcDepth,
                                                          const u32* __restrict__ chunkLens, const u32* __restrict__ chunkFrames, const u64 frameAt, const DX... dx)
 {
-    constexpr bool kIndexed = TAB == kPlaceIndexed;
-    static_assert(kIndexed == (sizeof...(DX) == 1) && (!kIndexed || (MODE == 2 && !DICT)), "the indexed instance, and it alone, takes a RegionDix");
-    constexpr int kPlaceForm = kIndexed ? kArith : TAB;
+    constexpr bool kIndexed = lz_tab_indexed(TAB), kSet = lz_tab_set(TAB);
+    static_assert((kIndexed || kSet) == (sizeof...(DX) == 1) && (!kIndexed || (MODE == 2 && !DICT)) && (!kSet || kIndexed || DICT),
+                  "the indexed instance and the set forms, and they alone, take a RegionDix / RegionSet");
+    constexpr int kPlaceForm = lz_tab_place(TAB);
     const u32 frameBlocks = frame_blocks_decode(frameBlocksArg).frameBlocks;
     const bool indep = frame_blocks_decode(frameBlocksArg).independent;
     extern __shared__ __attribute__((aligned(16))) u8 ldsRaw[];
@@ -1801,6 +1826,7 @@ __global__ __launch_bounds__(1024) void lz_region_kernel(const u8* __restrict__ 
     const FrameLayout frames = { kPlaceForm, cb, frameBlocks, srcSize, chunkFrames, frameAt, 0 };
     const BlockPlace place = (DICT && frameBlocks) ? block_place<kPlaceForm>(frames, c) : block_alone(0);
     u32 prefixLen = prefixLenArg; const u8* __restrict__ prefix = prefixArg;
+    if constexpr (kSet && DICT) { const RegionSet& st = region_dix(dx...); const SlotRef slot = (SlotRef)(st.slots + st.chunkSlot[c]); prefixLen = slot->tailLen; prefix = slot->tail; }
     if (DICT && frameBlocks && !indep) { prefixLen = place.front < hist ? (u32)place.front : hist; prefix = in - prefixLen; }
     if (DICT && indep && place.block) prefixLen = 0;
     const u32 lowLimit = DICT ? hist - prefixLen : 0u;
@@ -1857,7 +1883,13 @@ __global__ __launch_bounds__(1024) void lz_region_kernel(const u8* __restrict__ 
     const u32 nTiles = (n + kTilePos - 1) / kTilePos;
     // (candidate and link planes belong to the WORKGROUP, not to the chunk: written and read back within a chunk's time, the same
     //  128 KiB per CU again and again stay in L2 / the memory-side cache instead of travelling to HBM and back)
-    if constexpr (kIndexed) {
+    if constexpr (kIndexed && kSet) {
+        const RegionSet& st = region_dix(dx...);
+        const SlotRef slot = (SlotRef)(st.slots + st.chunkSlot[c]);
+        const DictIndexRef dixc = { slot->dix.end, slot->dix.len, slot->dix.table, slot->dix.log, slot->dix.tableLong, slot->dix.tableShort };
+        dense_rest<MODE, true>(L, n, insertFrom, 1, nTiles, hist, lowLimit, candAll + (u64)blockIdx.x * kChunkSize, chainAll + (u64)blockIdx.x * kChunkSize, hcDepth,
+                               seqs + (u64)c * kMaxSeq, lits + (u64)c * kLitStride, cursor, nbSeq, litBase, deferred, tid, lane, wave, dixc, st.dist + (u64)blockIdx.x * kChunkSize);
+    } else if constexpr (kIndexed) {
         const RegionDix& rd = region_dix(dx...);
         dense_rest<MODE, true>(L, n, insertFrom, 1, nTiles, hist, lowLimit, candAll + (u64)blockIdx.x * kChunkSize, chainAll + (u64)blockIdx.x * kChunkSize, hcDepth,
                                seqs + (u64)c * kMaxSeq, lits + (u64)c * kLitStride, cursor, nbSeq, litBase, deferred, tid, lane, wave, rd.dix, rd.dist + (u64)blockIdx.x * kChunkSize);
@@ -1941,13 +1973,15 @@ static void launch_one(const LzLaunch& a)
 {
     // the region parse of dense chunks: a second kernel behind a work list (see lz_region_kernel), inlined for the others
     constexpr bool kSplit = (MODE == 0 && !DICT && !FAR) || MODE == 2;
-    constexpr bool kIndexed = TAB == kPlaceIndexed;
+    constexpr bool kIndexed = lz_tab_indexed(TAB), kSet = lz_tab_set(TAB);
+    assert(kSet == (a.slots != nullptr) && kSet == (a.chunkSlot != nullptr));
     // (the attribute is per device: a process may hold contexts on several GPUs)
     static bool attrSet[64] = {};
     int dev = 0; (void)hipGetDevice(&dev);
     if (!attrSet[dev & 63]) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(lz_kernel<MODE, DICT, FAR, TAB>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(LzLds));
-        if constexpr (kSplit && kIndexed) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(lz_region_kernel<MODE, DICT, TAB, RegionDix>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(LzLds));
+        if constexpr (kSplit && kSet) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(lz_region_kernel<MODE, DICT, TAB, RegionSet>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(LzLds));
+        else if constexpr (kSplit && kIndexed) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(lz_region_kernel<MODE, DICT, TAB, RegionDix>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(LzLds));
         else if constexpr (kSplit) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(lz_region_kernel<MODE, DICT, TAB>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(LzLds));
         attrSet[dev & 63] = true;
     }
@@ -1966,10 +2000,15 @@ static void launch_one(const LzLaunch& a)
     const u32 grid = claim ? cuCount[dev & 63] : a.nChunks;
     const LzArgs k = { a.src, a.srcSize, a.seqs, a.lits, a.meta, a.prefix, a.prefixLen, chunkBytes, a.header, a.minStrideLog, frameBlocks, a.nChunks,
                        cand, cand ? a.regionList : nullptr, claim ? a.claimCtr : nullptr, a.chunkLens, a.frames.table, a.frames.at, a.frames.total,
-                       kIndexed ? *a.dix : DictIndexRef{} };
+                       (kIndexed && !kSet) ? *a.dix : DictIndexRef{}, a.slots, a.chunkSlot };
     hipLaunchKernelGGL((lz_kernel<MODE, DICT, FAR, TAB>), dim3(grid), dim3(kTile), sizeof(LzLds), a.stream, k);
     a.hook("lz_fast");
-    if constexpr (kSplit && kIndexed) { if (cand) {
+    if constexpr (kSplit && kSet) { if (cand) {
+        hipLaunchKernelGGL((lz_region_kernel<MODE, DICT, TAB, RegionSet>), dim3(a.nChunks < 256 ? a.nChunks : 256), dim3(kTile), sizeof(LzLds), a.stream, a.src, a.srcSize, a.seqs, a.lits, a.meta, cand, a.chain, a.regionList,
+                           nullptr, 0u, chunkBytes, frameBlocks, a.hcDepth, a.chunkLens, a.frames.table, a.frames.at, RegionSet{ a.slots, a.chunkSlot, kIndexed ? a.dist : nullptr });
+        a.hook("lz_region");
+    } }
+    else if constexpr (kSplit && kIndexed) { if (cand) {
         hipLaunchKernelGGL((lz_region_kernel<MODE, DICT, TAB, RegionDix>), dim3(a.nChunks < 256 ? a.nChunks : 256), dim3(kTile), sizeof(LzLds), a.stream, a.src, a.srcSize, a.seqs, a.lits, a.meta, cand, a.chain, a.regionList,
                            a.prefix, a.prefixLen, chunkBytes, frameBlocks, a.hcDepth, a.chunkLens, a.frames.table, a.frames.at, RegionDix{ *a.dix, a.dist });
         a.hook("lz_region");
@@ -1991,13 +2030,20 @@ void launch_lz(const LzLaunch& a)
     if (a.dix) {
         // every chunk a frame of its own behind an indexed dictionary: the FAR instance with the dictionary as what lies in front of
         // the block.  An instance of its own, so the kernels of a context without the switch are the ones from before it existed.
-        assert(f <= 2 && a.frames.form == kArith && !a.frames.frameBlocks && full && a.dix->len >= 8 && a.dix->len <= kFarMax);
-        assert(f == 0 ? a.dix->table != nullptr : (a.dix->tableLong && a.dix->tableShort));
+        // (a set pass says only THAT its chunks lie behind indexed dictionaries: each chunk's is in its slot)
+        assert(f <= 2 && a.frames.form == kArith && !a.frames.frameBlocks && full && (a.slots || (a.dix->len >= 8 && a.dix->len <= kFarMax)));
+        assert(a.slots || (f == 0 ? a.dix->table != nullptr : (a.dix->tableLong && a.dix->tableShort)));
         // nothing is staged in front of a chunk, no chunk has a place in a frame, and there is no region parse — but the chain finder's
         // (ZSTDMI_CCtx_setDictIndexChain), which comes with all three planes or, under ZSTDMI_CCtx_setParser(1), with none
         assert(!a.prefix && !a.prefixLen && !a.frames.table);
         assert(f == 2 ? (!a.cand == !a.chain && !a.cand == !a.regionList && !a.cand == !a.dist) : (!a.cand && !a.chain && !a.regionList && !a.dist));
+        if (a.slots) return f == 0 ? launch_one<0, false, true, kPlaceIndexedSet>(a) : f == 1 ? launch_one<1, false, true, kPlaceIndexedSet>(a) : launch_one<2, false, true, kPlaceIndexedSet>(a);
         return f == 0 ? launch_one<0, false, true, kPlaceIndexed>(a) : f == 1 ? launch_one<1, false, true, kPlaceIndexed>(a) : launch_one<2, false, true, kPlaceIndexed>(a);
+    }
+    if (a.slots) {
+        // a set pass behind staged tails: every chunk a frame of its own below 64 KiB, as a dictionary's framing cuts them
+        assert(a.frames.form == kArith && !a.frames.frameBlocks && !full && a.prefixLen && a.chunkLens);
+        return f == 0 ? launch_one<0, true, false, kArithSet>(a) : f == 1 ? launch_one<1, true, false, kArithSet>(a) : launch_one<2, true, false, kArithSet>(a);
     }
     if (a.frames.form == kSingle) {
         // one frame across passes: the long-distance framing's blocks (resolve_framing), each with its place in bytes.  Instances of

@@ -120,12 +120,17 @@ __device__ __forceinline__ u32 build_seq_table(SeqWaveLds& W, u8* op, u32* count
 // SF (ZSTDMI_CCtx_setSingleFrame): the call's input is ONE frame cut anywhere by passes and stream batches (frames.form == kSingle;
 // frames.total ~0: not known yet, the frame goes on behind this pass).
 // fh / frames (zmi_frame.h): the header a frame's first block is given, and how the chunks map to frames.
-template <bool DICT, bool SF>
-__global__ __launch_bounds__(256) void seq_encode_kernel(Seq* __restrict__ seqs, ChunkMeta* __restrict__ meta,
-                                                         u8* __restrict__ slots, u32 nChunks, u32 strategy, const FrameHeaderSpec fh, u32 resolveReps,
-                                                         u32 initRep0, u32 initRep1, u32 initRep2, const FrameLayout frames,
-                                                         const DictCTables* __restrict__ dct)
+// SET (ZSTDMI_compressBatchCDicts, zmi_cdictset.h; on the DICT instance): a pass behind two or more dictionaries.  The header's dictID,
+// the repcodes in front of a frame and dct come per chunk from dictSlots[chunkSlot[c]] (a wave's chunk: scalar loads); a slot without
+// tables (raw content, no dictionary, the switch off) leaves its chunks what the instance without DICT makes of them.
+// The body stands behind two kernels, below: seq_encode_kernel<DICT, SF> with the arguments it always had, and seq_encode_set_kernel.
+template <bool DICT, bool SF, bool SET>
+__device__ __forceinline__ void seq_encode_body(Seq* __restrict__ seqs, ChunkMeta* __restrict__ meta,
+                                                u8* __restrict__ slots, u32 nChunks, u32 strategy, const FrameHeaderSpec& fhArg, u32 resolveReps,
+                                                u32 initRep0, u32 initRep1, u32 initRep2, const FrameLayout& frames,
+                                                const DictCTables* __restrict__ dctArg, const CDictSlot* __restrict__ dictSlots, const u32* __restrict__ chunkSlot)
 {
+    static_assert(!SET || (DICT && !SF), "the set form stands on the DICT instance");
     __shared__ SeqWaveLds Ws[4];
     __shared__ u32 sBatchSeq[4];          // sequences each of the four chunks sends through the state chains (0: none)
     __shared__ u32 sFinalState[4][3];
@@ -136,6 +141,12 @@ __global__ __launch_bounds__(256) void seq_encode_kernel(Seq* __restrict__ seqs,
     ChunkMeta m = {};
     if (live) m = meta_checked<false>(meta[c]);
     const u32 nbSeq = m.nbSeq, n = m.srcSize;
+    FrameHeaderSpec fh = fhArg; const DictCTables* __restrict__ dct = dctArg;
+    if (SET) {
+        const CDictSlot* __restrict__ const ds = dictSlots + (live ? chunkSlot[c] : 0u);
+        fh.dictID = ds->dictID; fh.dictIdBytes = (u8)ds->dictIdBytes; dct = ds->dct;
+        initRep0 = ds->rep[0]; initRep1 = ds->rep[1]; initRep2 = ds->rep[2];
+    }
     // Multi-block frames (row f-1): chunk c is block bf of frame c / frameBlocks.  A later block never relies on the repcodes the
     // blocks before it leave behind — whether one of them ends up stored raw (and so leaves the decoder's history untouched,
     // U/ZstdCompress.cs:3620-3640) is only known once it has been encoded — so its history starts as "unknown" (0 matches no
@@ -233,7 +244,7 @@ __global__ __launch_bounds__(256) void seq_encode_kernel(Seq* __restrict__ seqs,
         // the dictionary's tables stand behind a frame's first block only, each where ZSTD_loadCEntropy found it `valid`
         const u16 *dLL = nullptr, *dOF = nullptr, *dML = nullptr;
         u32 dLogLL = 0, dLogOF = 0, dLogML = 0; u64 dHasLL = 0, dHasOF = 0, dHasML = 0;
-        if (DICT && bf == 0) {
+        if (DICT && bf == 0 && (!SET || dct)) {
             if (dct->seqValid[0]) dLL = dct->llState;
             if (dct->seqValid[1]) dOF = dct->ofState;
             if (dct->seqValid[2]) dML = dct->mlState;
@@ -244,11 +255,11 @@ __global__ __launch_bounds__(256) void seq_encode_kernel(Seq* __restrict__ seqs,
             if (dLogML > 9) dLogML = 9;
         }
         op += build_seq_table<DICT>(W, op, W.count[0], 35, 9, nbSeq, lastLL, cLL_defaultNorm, 6, 35, false, strategy, W.llState, W.llTT, &LLtype, &llLog, &lastCountSize, lane,
-                                    dLL, DICT ? dct->llTT : nullptr, dLogLL, dHasLL);
+                                    dLL, (DICT && (!SET || dct)) ? dct->llTT : nullptr, dLogLL, dHasLL);
         op += build_seq_table<DICT>(W, op, W.count[1], 31, 8, nbSeq, lastOF, cOF_defaultNorm, 5, 28, true,  strategy, W.ofState, W.ofTT, &OFtype, &ofLog, &lastCountSize, lane,
-                                    dOF, DICT ? dct->ofTT : nullptr, dLogOF, dHasOF);
+                                    dOF, (DICT && (!SET || dct)) ? dct->ofTT : nullptr, dLogOF, dHasOF);
         op += build_seq_table<DICT>(W, op, W.count[2], 52, 9, nbSeq, lastML, cML_defaultNorm, 6, 52, false, strategy, W.mlState, W.mlTT, &MLtype, &mlLog, &lastCountSize, lane,
-                                    dML, DICT ? dct->mlTT : nullptr, dLogML, dHasML);
+                                    dML, (DICT && (!SET || dct)) ? dct->mlTT : nullptr, dLogML, dHasML);
         // lastCountSize must be the size of the LAST compressed table description (U/ZstdCompress.cs:3196-3224)
         if (lane == 0) *seqHead = (u8)((LLtype << 6) + (OFtype << 4) + (MLtype << 2));
 
@@ -420,11 +431,31 @@ __global__ __launch_bounds__(256) void seq_encode_kernel(Seq* __restrict__ seqs,
     m.outSize = m.fhSize + 3 + cSize + ((fh.checksum && lastBlock) ? 4 : 0);
     meta[c] = m;
 }
+template <bool DICT, bool SF>
+__global__ __launch_bounds__(256) void seq_encode_kernel(Seq* __restrict__ seqs, ChunkMeta* __restrict__ meta,
+                                                         u8* __restrict__ slots, u32 nChunks, u32 strategy, const FrameHeaderSpec fh, u32 resolveReps,
+                                                         u32 initRep0, u32 initRep1, u32 initRep2, const FrameLayout frames,
+                                                         const DictCTables* __restrict__ dct)
+{
+    seq_encode_body<DICT, SF, false>(seqs, meta, slots, nChunks, strategy, fh, resolveReps, initRep0, initRep1, initRep2, frames, dct, nullptr, nullptr);
+}
+__global__ __launch_bounds__(256) void seq_encode_set_kernel(Seq* __restrict__ seqs, ChunkMeta* __restrict__ meta,
+                                                             u8* __restrict__ slots, u32 nChunks, u32 strategy, const FrameHeaderSpec fh, u32 resolveReps,
+                                                             const FrameLayout frames, const CDictSlot* __restrict__ dictSlots, const u32* __restrict__ chunkSlot)
+{
+    seq_encode_body<true, false, true>(seqs, meta, slots, nChunks, strategy, fh, resolveReps, 0, 0, 0, frames, nullptr, dictSlots, chunkSlot);
+}
 
 void launch_seq_encode(Seq* seqs, ChunkMeta* meta, u8* slots, u32 nChunks, u32 strategy, const FrameHeaderSpec& header, u32 resolveReps,
-                       const u32* initReps, const FrameLayout& frames, hipStream_t stream, const DictCTables* dct)
+                       const u32* initReps, const FrameLayout& frames, hipStream_t stream, const DictCTables* dct,
+                       const CDictSlot* dictSlots, const u32* chunkSlot)
 {
-    assert(!dct || frames.form != kSingle);
+    assert((!dct && !dictSlots) || frames.form != kSingle);
+    assert(!dictSlots == !chunkSlot && (!dictSlots || !frames.frameBlocks));
+    if (dictSlots) {
+        hipLaunchKernelGGL(seq_encode_set_kernel, dim3((nChunks + 3) / 4), dim3(256), 0, stream, seqs, meta, slots, nChunks, strategy, header, resolveReps, frames, dictSlots, chunkSlot);
+        return;
+    }
     const auto kernel = frames.form == kSingle ? seq_encode_kernel<false, true> : dct ? seq_encode_kernel<true, false> : seq_encode_kernel<false, false>;
     hipLaunchKernelGGL(kernel, dim3((nChunks + 3) / 4), dim3(256), 0, stream, seqs, meta, slots, nChunks, strategy, header, resolveReps,
                        initReps[0], initReps[1], initReps[2], frames, dct);

@@ -12,14 +12,12 @@
 #include "zmi_common.h"
 #include "zmi_frame.h"
 #include "zmi_dictset.h"
+#include "zmi_cdictset.h"
 #include "../../include/zstd_mi355x.h"
 
 namespace zmi {
 // kernels (lz_fast.hip, huf_enc.hip, seq_enc.hip, frame.hip, decode.hip)
-// an indexed dictionary (ZSTDMI_CCtx_setDictIndex; lz_fast.hip): `end` = the byte behind its content on the device (readable for 64
-// bytes more), `len` = the indexed bytes in front of `end`, `table` = 1 << log buckets under the fast finder's hash; tableLong /
-// tableShort (ZSTDMI_CCtx_setDictIndexStrategy(2); else null) = as many under each of the dual finder's two
-struct DictIndexRef { const u8* end; u32 len; const u32* table; u32 log; const u32* tableLong; const u32* tableShort; };
+// (an indexed dictionary, DictIndexRef: zmi_cdictset.h)
 void launch_dict_index(const u8* content, u32 len, u32* table, u32 log, hipStream_t stream);
 void launch_dict_index_dual(const u8* content, u32 len, u32* tableLong, u32* tableShort, u32 log, hipStream_t stream);
 u32 dict_index_log(u32 len);        // log2 of the buckets for `len` indexed bytes
@@ -36,6 +34,9 @@ u32 dict_index_max();               // the most bytes an index covers (the far c
 // its two tables; chunkLens allowed; prefix and frames.table are null, and so are cand, chain and regionList below the chain finder).
 // The kernel gets a copy (LzArgs::dix).  dist (the chain finder behind dix; else null): the region parse's second plane, 65536 u32 for each
 // of lz_region_kernel's at most 256 workgroups: where a position's candidate lies in the dictionary (ZSTDMI_CCtx_setDictIndexChain).
+// slots / chunkSlot (null: off; ZSTDMI_compressBatchCDicts, zmi_cdictset.h): a pass behind two or more dictionaries.  The finder's
+// set instance then takes the tail (prefix, prefixLen) or the index (dix) per chunk from slots[chunkSlot[c]], and the frame header's
+// dictID bytes with them; of prefix / prefixLen / dix the host states only whether there is one (prefixLen != 0, dix != null).
 struct LzLaunch {
     u32 finder;
     const u8* src; u64 srcSize; u32 nChunks;
@@ -49,17 +50,21 @@ struct LzLaunch {
     u32* claimCtr;
     const u32* chunkLens;
     const DictIndexRef* dix;
+    const CDictSlot* slots; const u32* chunkSlot;
     hipStream_t stream; StageHook hook;
 };
 void launch_lz(const LzLaunch& a);
 void launch_lz_probe(const u8* src, u64 srcSize, u64 front, u64 groupBytes, u32 nGroups, u32 tilesPerGroup, u32* out, hipStream_t stream);
 // frames: a dictionary's entropy tables (dct) serve the first block of every frame
+// dictSlots / chunkSlot (null: off), here and in launch_seq_encode: the stage's set instance, which reads dct — and seq_encode the
+// header's dictID and the first repcodes — per chunk from dictSlots[chunkSlot[c]]; the arguments they replace are not read
 void launch_huf_build(const u8* lits, ChunkMeta* meta, HufTable* tables, u8* slots, u32 nChunks, u32 rawLiterals, const u8* src, const FrameLayout& frames,
-                      hipStream_t stream, StageHook hook, const DictCTables* dct = nullptr);
+                      hipStream_t stream, StageHook hook, const DictCTables* dct = nullptr, const CDictSlot* dictSlots = nullptr, const u32* chunkSlot = nullptr);
 void launch_huf_encode(const u8* lits, const ChunkMeta* meta, const HufTable* tables, u8* slots, u8* dst, const u64* offsets, u64 dstCapacity,
                        u32 nChunks, const u8* src, u32 chunkBytes, hipStream_t stream, bool dictEntropy = false);
 void launch_seq_encode(Seq* seqs, ChunkMeta* meta, u8* slots, u32 nChunks, u32 strategy, const FrameHeaderSpec& header, u32 resolveReps,
-                       const u32* initReps, const FrameLayout& frames, hipStream_t stream, const DictCTables* dct = nullptr);
+                       const u32* initReps, const FrameLayout& frames, hipStream_t stream, const DictCTables* dct = nullptr,
+                       const CDictSlot* dictSlots = nullptr, const u32* chunkSlot = nullptr);
 void launch_scan_sizes(const ChunkMeta* meta, u32 nChunks, u64* offsets, u64* total, hipStream_t stream);
 void launch_gather(const u8* src, u64 srcSize, const u8* slots, const ChunkMeta* meta, const u64* offsets, u8* dst, u64 dstCapacity,
                    u32 nChunks, u32 chunkBytes, hipStream_t stream);

@@ -76,6 +76,8 @@ struct ZSTD_CCtx_s {
     DevBuf gatherIn, gatherOut;     // a many-range plan: the ranges of a kind side by side, and their output (compress_plan)
     DevBuf batchStage, batchTab;    // a batch of independent entries: their chunks at chunk boundaries, and the pass's tables (compress_entries)
     int lastBatchAlone = 0;         // entries of the last ZSTDMI_compressBatch that went through the single-call path (debug hook)
+    // batched passes of the last compress_entries, and the chunks of those that ran the set instances (ZSTDMI_compressBatchCDicts; debug hooks)
+    long long lastBatchPasses = 0, lastBatchSetChunks = 0;
     // ZSTDMI_compressPack: a round's frames in bound-sized slots before they are placed, and its placement table (compress_pack_impl);
     // entries the last pack handed to the single-call path and rows of the table it wrote (debug hooks)
     DevBuf packArena, packTab; int lastPackAlone = 0; long long lastPackFrames = 0;
@@ -1183,6 +1185,28 @@ size_t ZSTD_CCtx_refCDict(ZSTD_CCtx* c, const ZSTD_CDict* cdict)
         return 0;
     });
 }
+// run() with `cdict` in force as after ZSTD_CCtx_refCDict (null: no dictionary at all); then the context's own dictionary or reference
+// is back.  Where the CDict cannot be shared, its host fields stand in for the context's and are uploaded again by their next use.
+extern "C++" { template <class F> static size_t under_cdict(ZSTD_CCtx* c, const ZSTD_CDict_s* cdict, F run)
+{
+    const ZSTD_CDict_s* const was = c->cdict;
+    c->cdict = cdict;
+    if (cdict_shared(c)) {
+        size_t r;
+        try { r = run(); } catch (...) { c->cdict = was; throw; }      // (the entry point's guarded() names the error)
+        c->cdict = was;
+        return r;
+    }
+    DictDigest& g = c->own;
+    std::vector<u8> h, f, w; const bool fmt = g.dictFormatted; const DictInfo info = g.info;
+    h.swap(g.dictHost); f.swap(g.dictFull); w.swap(g.dictWide);
+    size_t r;
+    try { cctx_adopt_cdict(c); r = run(); }
+    catch (...) { r = ZERR(kErrMemoryAllocation); }
+    g.dictHost.swap(h); g.dictFull.swap(f); g.dictWide.swap(w); g.dictFormatted = fmt; g.info = info;
+    c->cdict = was; c->dictDirty = true; c->dictGen++;
+    return r;
+} }
 size_t ZSTD_compress_usingCDict(ZSTD_CCtx* c, void* dst, size_t dstCapacity, const void* src, size_t srcSize, const ZSTD_CDict* cdict)
 {
     if (!c || !cdict) return ZERR(kErrGeneric);
@@ -1190,24 +1214,7 @@ size_t ZSTD_compress_usingCDict(ZSTD_CCtx* c, void* dst, size_t dstCapacity, con
     // steps aside for the call (where the CDict cannot be shared, its host fields do, and are uploaded again by their next use)
     CallParams p; p.level = cdict->level; p.useDict = true;
     p.dictEntropy = c->dictEntropy != 0; p.dictIndex = c->dictIndex != 0; p.dictIndexStrategy = c->dictIndexStrategy; p.dictIndexChain = c->dictIndexChain != 0;
-    return guarded([&]() -> size_t {
-        const ZSTD_CDict_s* const was = c->cdict;
-        c->cdict = cdict;
-        if (cdict_shared(c)) {
-            const size_t r = compress_any(c, p, dst, dstCapacity, src, srcSize);
-            c->cdict = was;
-            return r;
-        }
-        DictDigest& g = c->own;
-        std::vector<u8> h, f, w; const bool fmt = g.dictFormatted; const DictInfo info = g.info;
-        h.swap(g.dictHost); f.swap(g.dictFull); w.swap(g.dictWide);
-        size_t r;
-        try { cctx_adopt_cdict(c); r = compress_any(c, p, dst, dstCapacity, src, srcSize); }
-        catch (...) { r = ZERR(kErrMemoryAllocation); }
-        g.dictHost.swap(h); g.dictFull.swap(f); g.dictWide.swap(w); g.dictFormatted = fmt; g.info = info;
-        c->cdict = was; c->dictDirty = true; c->dictGen++;
-        return r;
-    });
+    return guarded([&]() -> size_t { return under_cdict(c, cdict, [&] { return compress_any(c, p, dst, dstCapacity, src, srcSize); }); });
 }
 long long ZSTDMI_debugDictUploads(const ZSTD_CCtx* c)
 {
@@ -1726,6 +1733,19 @@ size_t ZSTD_compressStream2(ZSTD_CCtx* c, ZSTD_outBuffer* output, ZSTD_inBuffer*
 // size of entry i (or its error).  d_stats (optional, device, 377 u32): seq_stats_kernel's counts of the batched chunks are added.
 // seekIdx (optional; ZSTDMI_compressPack): the row of c->seekEntries (seekCap rows) at which entry i's frames are filed, one
 // (compressed size, content size) pair per frame, by every pass from its ChunkMeta (pack_entries_kernel).
+// cdicts (optional; ZSTDMI_compressBatchCDicts): entry i is compressed behind cdicts[i] (null: without a dictionary) as after
+// ZSTD_CCtx_refCDict, all of them shareable by this context (on its device, no workers) — or a single one that is not, of which the
+// context holds its private upload (compress_batch_cdicts_impl).  `cp` then holds the context's parameters without
+// a reference; what the call runs with is resolved per distinct CDict, because its level is: CallParams here, LaunchState per pass.
+// For the length of a resolve or a launch the CDict is the context's reference (c->cdict), which is put back at the end.  Entries
+// share a group, and so a pass, by what has to be equal for their chunks to share a launch — chunk size (the staged tail in whole
+// 4 KiB tiles), blocks per frame, indexed or not, the resolved parameters the kernels act on (same_launch_params: a call without
+// `cdicts` keeps its classes by the whole of Resolved, and so its passes) — not by the dictionary nor by the tail's exact length.
+// (Only where nothing of the dictionary is staged or indexed — no dictionary, content below 8 bytes — the finder runs its plain
+// instance, which has no set form and takes the header's dictID bytes as launch constants: such entries group by CDict as well, and
+// never with staged or indexed ones, whatever else is equal: under ZSTD_c_windowLog 10 .. 15 both kinds have chunks of one window.)
+// A pass that holds two or more distinct CDicts uploads a slot table (zmi_cdictset.h) with each chunk's index into it and runs the
+// stages' set instances; a pass behind one is launched exactly as the call without `cdicts` launches it.
 //
 // entry_batched -> does an entry of S bytes (S > 0, framed as fr) share a batched pass?  One rule for compress_entries, which sorts
 // its entries by it, and for ZSTDMI_compressPack, which cuts its rounds by it.
@@ -1741,17 +1761,43 @@ static bool entry_batched(ZSTD_CCtx* c, const CallParams& cp, size_t S, const Fr
     if (batched && S >= (4u << 20)) { size_t err = 0; if (probe_group_bytes(c, cp, S, err) || isErr(err)) batched = false; }
     return batched;
 }
+// What of two entries' resolved parameters has to be equal for their chunks to share a launch: the parts the kernels act on (finder,
+// probing stride, raw literals, seq_encode's strategy constants, the chain search's depth).  The rest of a CParams — windowLog, hashLog
+// and chainLog, which ZSTD_adjustCParams shrinks with the entry's size — reaches no kernel.
+static bool same_launch_params(const Resolved& a, const Resolved& b)
+{
+    return a.finder == b.finder && a.minStrideLog == b.minStrideLog && a.rawLiterals == b.rawLiterals && a.cp.strategy == b.cp.strategy && a.cp.searchLog == b.cp.searchLog;
+}
 static u32 batch_pass_limit(const ZSTD_CCtx* c) { return c->passChunks < 16384 ? c->passChunks : 16384; }
 static size_t compress_entries(ZSTD_CCtx* c, const CallParams& cp, const u8* const* srcs, const size_t* sizes, size_t n,
                                u8* const* dsts, const size_t* caps, size_t* outSizes, u32* d_stats, int& alone,
-                               const u32* seekIdx = nullptr, u32 seekCap = 0)
+                               const u32* seekIdx = nullptr, u32 seekCap = 0, const ZSTD_CDict_s* const* cdicts = nullptr)
 {
     hipStream_t s = c->stream;
     alone = 0;
     c->lastRegionList = nullptr;        // (entries that go alone pass through compress_range, which notes its own)
-    const DictCTables* const dct = call_dict_ctables(c, cp);
+    c->lastBatchPasses = 0; c->lastBatchSetChunks = 0;
     const u32 passLimit = batch_pass_limit(c);
-    struct Group { Framing fr; std::vector<size_t> members; };
+    // per-entry CDicts: the distinct ones, each entry's index among them, and the parameters each of them makes of the context's
+    std::vector<const void*> dicts; std::vector<u32> slotOf; std::vector<CallParams> cps; std::vector<size_t> slotErr;
+    struct Restore { ZSTD_CCtx* c; const ZSTD_CDict_s* was; ~Restore() { c->cdict = was; } } restore{c, c->cdict};
+    if (cdicts) {
+        const int bad = cdict_slots_assign((const void* const*)cdicts, n, dicts, slotOf);
+        if (bad) return bad == 1 ? ZERR(kErrParameterUnsupported) : ZERR(kErrMemoryAllocation);
+        for (const void* d : dicts) {
+            CallParams q = cp;
+            if (d) q.level = ((const ZSTD_CDict_s*)d)->level; else q.useDict = false;
+            cps.push_back(q); slotErr.push_back(check_call_params(q));       // (what every single call behind this CDict would answer)
+        }
+    }
+    // the parameters entry i runs with; with per-entry CDicts its CDict becomes the reference in force
+    auto params_of = [&](size_t i) -> const CallParams& {
+        if (!cdicts) return cp;
+        c->cdict = (const ZSTD_CDict_s*)dicts[slotOf[i]];
+        return cps[slotOf[i]];
+    };
+    // (cdicts: plain = nothing of the members' dictionaries is staged or indexed, and they all lie behind `slot`; tail = each member's prefixLen)
+    struct Group { Framing fr; u32 slot; bool plain; std::vector<size_t> members; std::vector<u32> tail; };
     std::vector<Group> groups;
     std::vector<size_t> aloneList;
     for (size_t i = 0; i < n; i++) {
@@ -1760,21 +1806,28 @@ static size_t compress_entries(ZSTD_CCtx* c, const CallParams& cp, const u8* con
             if (S && !srcs[i]) { outSizes[i] = ZERR(kErrSrcSizeWrong); continue; }
             if (!dsts[i]) { outSizes[i] = caps[i] ? ZERR(kErrDstBufferNull) : ZERR(kErrDstSizeTooSmall); continue; }
         }
-        const Framing fr = S ? resolve_framing(c, cp, S) : Framing{};
-        if (!S || !entry_batched(c, cp, S, fr, passLimit, dct != nullptr, d_stats != nullptr)) { aloneList.push_back(i); continue; }
+        if (cdicts && isErr(slotErr[slotOf[i]])) { outSizes[i] = slotErr[slotOf[i]]; continue; }
+        const CallParams& cpi = params_of(i);
+        const Framing fr = S ? resolve_framing(c, cpi, S) : Framing{};
+        if (!S || !entry_batched(c, cpi, S, fr, passLimit, call_dict_ctables(c, cpi) != nullptr, d_stats != nullptr)) { aloneList.push_back(i); continue; }
         outSizes[i] = 0;
+        const u32 slot = cdicts ? slotOf[i] : 0u;
+        const bool plain = !fr.prefixLen && !fr.dictIndex;      // (the finder's plain instance: no set form)
         Group* g = nullptr;
         for (auto& x : groups)
-            if (x.fr.prefixLen == fr.prefixLen && x.fr.chunkBytes == fr.chunkBytes && x.fr.frameBlocks == fr.frameBlocks && x.fr.dictIndex == fr.dictIndex && !memcmp(&x.fr.rs, &fr.rs, sizeof(Resolved))) { g = &x; break; }
-        if (!g) { groups.push_back(Group{fr, {}}); g = &groups.back(); }
+            if ((cdicts ? (x.plain == plain && (!plain || x.slot == slot)) : x.fr.prefixLen == fr.prefixLen) && x.fr.chunkBytes == fr.chunkBytes && x.fr.frameBlocks == fr.frameBlocks && x.fr.dictIndex == fr.dictIndex &&
+                (cdicts ? same_launch_params(x.fr.rs, fr.rs) : !memcmp(&x.fr.rs, &fr.rs, sizeof(Resolved)))) { g = &x; break; }
+        if (!g) { groups.push_back(Group{fr, slot, plain, {}, {}}); g = &groups.back(); }
         g->members.push_back(i);
+        if (cdicts) g->tail.push_back(fr.prefixLen);
     }
     bool first = true;
     std::vector<u8> tab; std::vector<u64> got;
+    std::vector<u32> chunkSlot, used; std::vector<CDictSlot> slotTab; std::vector<u8> slotDone;
     for (const Group& g : groups) {
         const u32 cb = g.fr.chunkBytes, frameBlocks = g.fr.frameBlocks;
         const Resolved rs = g.fr.rs;
-        const LaunchState ls = launch_state(c, cp, g.fr);
+        LaunchState ls = launch_state(c, params_of(g.members[0]), g.fr);
         const bool regionParse = ls.regionParse, hcChains = ls.hcChains;
         for (size_t m0 = 0; m0 < g.members.size(); ) {
             // the pass: whole entries, up to passLimit chunks
@@ -1790,8 +1843,36 @@ static size_t compress_entries(ZSTD_CCtx* c, const CallParams& cp, const u8* con
             const size_t atDst = (size_t)nCh * 8, atCap = atDst + (size_t)nEnt * 8, atLen = atCap + (size_t)nEnt * 8, atFirst = atLen + (size_t)nCh * 4;
             const size_t atFrame = atFirst + ((size_t)nEnt + 1) * 4;
             const size_t atSeek = atFrame + (frameBlocks ? (size_t)nCh * 4 : 0);        // (a pack: | entSeek[nEnt])
-            const size_t tabBytes = (atSeek + (seekIdx ? (size_t)nEnt * 4 : 0) + 7) & ~(size_t)7;
+            // per-entry CDicts: the pass's launch state is that of its dictionary, or, behind two or more of them, the group's with a
+            // slot table: | chunkSlot[nCh] (u32) | slots[used.size()] (CDictSlot)
+            Framing fr = g.fr;
+            if (cdicts) {
+                chunkSlot.clear();
+                for (size_t m = m0; m < m1; ++m) chunkSlot.insert(chunkSlot.end(), (sizes[g.members[m]] + cb - 1) / cb, slotOf[g.members[m]]);
+                if (!cdict_pass_image(chunkSlot, used)) return ZERR(kErrMemoryAllocation);
+                slotTab.assign(used.size(), CDictSlot{});
+                slotDone.assign(used.size(), 0);
+                for (size_t m = m0; m < m1; ++m) {      // each slot from the first entry behind it; the pass's state is its first entry's
+                    const size_t i = g.members[m];
+                    const size_t k = std::lower_bound(used.begin(), used.end(), slotOf[i]) - used.begin();
+                    assert(!slotDone[k] || slotTab[k].tailLen == g.tail[m]);        // (one dictionary, one chunk size: one tail)
+                    if (slotDone[k]) continue;
+                    fr.prefixLen = g.tail[m];
+                    const LaunchState lu = launch_state(c, params_of(i), fr);
+                    slotTab[k] = CDictSlot{ lu.prefix, lu.dct, lu.dix, fr.prefixLen, lu.header.dictID, lu.header.dictIdBytes, { lu.initReps[0], lu.initReps[1], lu.initReps[2] } };
+                    slotDone[k] = 1;
+                    if (m == m0) ls = lu;
+                }
+                fr.prefixLen = g.tail[m0];
+            }
+            const bool set = cdicts && used.size() >= 2;
+            const DictCTables* dct = ls.dct;
+            if (set) for (const CDictSlot& r : slotTab) if (r.dct) dct = r.dct;     // (any: "some slot has tables")
+            const size_t atChunkSlot = atSeek + (seekIdx ? (size_t)nEnt * 4 : 0);
+            const size_t atSlots = (atChunkSlot + (set ? (size_t)nCh * 4 : 0) + 7) & ~(size_t)7;
+            const size_t tabBytes = (atSlots + (set ? slotTab.size() * sizeof(CDictSlot) : 0) + 7) & ~(size_t)7;
             tab.assign(tabBytes, 0);
+            if (set) { memcpy(tab.data() + atChunkSlot, chunkSlot.data(), (size_t)nCh * 4); memcpy(tab.data() + atSlots, slotTab.data(), slotTab.size() * sizeof(CDictSlot)); }
             u64* const hFrom = (u64*)tab.data(); u64* const hDst = (u64*)(tab.data() + atDst); u64* const hCap = (u64*)(tab.data() + atCap);
             u32* const hLen = (u32*)(tab.data() + atLen); u32* const hFirst = (u32*)(tab.data() + atFirst); u32* const hFrame = (u32*)(tab.data() + atFrame);
             uintptr_t lo = ~(uintptr_t)0, hi = 0;
@@ -1835,11 +1916,18 @@ static size_t compress_entries(ZSTD_CCtx* c, const CallParams& cp, const u8* con
             launch_batch_stage((const u64*)dTab, dLen, (u8*)c->batchStage.p, nCh, cb, s);      c->timer.mark("batch_stage", s);
             // (multi-block frames: each chunk's place from the table; else every chunk a frame.  dct: single-block frames only, see above)
             const FrameLayout frames = dFrame ? layout_table(cb, frameBlocks, dFrame) : layout_arith(cb, 0, stagedBytes);
-            launch_lz(pass_lz(c, ls, g.fr, stage, stagedBytes, nCh, nCh, frames, dLen));
-            launch_huf_build(lits, meta, tables, slots, nCh, rs.rawLiterals, stage, frames, s, c->timer.hook(), dct);
+            const CDictSlot* const dSlots = set ? (const CDictSlot*)(dTab + atSlots) : nullptr;
+            const u32* const dChunkSlot = set ? (const u32*)(dTab + atChunkSlot) : nullptr;
+            LzLaunch lz = pass_lz(c, ls, fr, stage, stagedBytes, nCh, nCh, frames, dLen);
+            // (a set pass: the finder's set instance — behind staged tails or behind indexes — takes each chunk's dictionary from its slot)
+            assert(!set || fr.prefixLen || fr.dictIndex);
+            if (set) { lz.slots = dSlots; lz.chunkSlot = dChunkSlot; lz.prefix = nullptr; }
+            launch_lz(lz);
+            launch_huf_build(lits, meta, tables, slots, nCh, rs.rawLiterals, stage, frames, s, c->timer.hook(), dct, dSlots, dChunkSlot);
             if (cp.checksumFlag) { launch_xxh64(stage, meta, nCh, frames, s, dLen);        c->timer.mark("xxh64", s); }
-            launch_seq_encode(seqs, meta, slots, nCh, ls.strategy, ls.header, 1, ls.initReps, frames, s, dct);
+            launch_seq_encode(seqs, meta, slots, nCh, ls.strategy, ls.header, 1, ls.initReps, frames, s, dct, dSlots, dChunkSlot);
             c->timer.mark("seq_encode", s);
+            c->lastBatchPasses++; if (set) c->lastBatchSetChunks += nCh;
             if (d_stats) launch_seq_stats(seqs, lits, meta, nCh, stage, cb, d_stats, s);
             launch_batch_place(meta, nEnt, (const u32*)(dTab + atFirst), (const u64*)(dTab + atDst), (const u64*)(dTab + atCap), span, offsets, dGot, s);
             c->timer.mark("batch_place", s);
@@ -1860,8 +1948,9 @@ static size_t compress_entries(ZSTD_CCtx* c, const CallParams& cp, const u8* con
     }
     std::vector<u8> tmp;
     for (size_t i : aloneList) {
-        if (dsts) outSizes[i] = compress_device(c, cp, dsts[i], caps[i], srcs[i], sizes[i]);
-        else { tmp.resize(ZSTD_compressBound(sizes[i])); outSizes[i] = compress_any(c, cp, tmp.data(), tmp.size(), srcs[i], sizes[i]); }
+        const CallParams& cpi = params_of(i);
+        if (dsts) outSizes[i] = compress_device(c, cpi, dsts[i], caps[i], srcs[i], sizes[i]);
+        else { tmp.resize(ZSTD_compressBound(sizes[i])); outSizes[i] = compress_any(c, cpi, tmp.data(), tmp.size(), srcs[i], sizes[i]); }
         ++alone;
     }
     c->lastChunks = 0;                                  // (ZSTDMI_debugGetChunk: no ordinary call to look at)
@@ -1920,6 +2009,51 @@ extern "C" size_t ZSTDMI_compressBatch(ZSTD_CCtx* c, const void* const* srcs, co
     return guarded([&] { return compress_batch_impl(c, srcs, srcSizes, n, dsts, dstCapacities, dstSizes); });
 }
 extern "C" int ZSTDMI_debugLastBatchAlone(const ZSTD_CCtx* c) { return c ? c->lastBatchAlone : -1; }
+extern "C" long long ZSTDMI_debugLastBatchPasses(const ZSTD_CCtx* c) { return c ? c->lastBatchPasses : -1; }
+extern "C" long long ZSTDMI_debugLastBatchSetChunks(const ZSTD_CCtx* c) { return c ? c->lastBatchSetChunks : -1; }
+
+// The batch with a CDict per entry (include/zstd_mi355x.h).  Entries that all name one CDict (or none) ARE ZSTD_CCtx_refCDict + the batch
+// above, private upload included; else compress_entries resolves per CDict, and nothing of the context's own dictionary is consulted.
+static size_t compress_batch_cdicts_impl(ZSTD_CCtx* c, const void* const* srcs, const size_t* srcSizes, size_t n, void* const* dsts, const size_t* dstCapacities,
+                                         size_t* dstSizes, const ZSTD_CDict* const* cdicts)
+{
+    if (!c) return ZERR(kErrGeneric);
+    c->lastRegionList = nullptr;
+    if (n == 0) { c->lastBatchAlone = 0; c->lastBatchPasses = 0; c->lastBatchSetChunks = 0; return 0; }
+    if (!srcs || !srcSizes || !dsts || !dstCapacities || !dstSizes || !cdicts) return ZERR(kErrGeneric);
+    size_t e = cctx_bind(c); if (isErr(e)) return e;
+    if (c->workers.size() > 1 || c->seekTable || c->pfx) return ZERR(kErrParameterUnsupported);
+    // one = every entry names the same CDict (or none); only = the one non-NULL CDict of a call that names no second one; away = a
+    // CDict on another device than the context's
+    bool one = true, several = false, away = false;
+    const ZSTD_CDict_s* only = nullptr;
+    for (size_t i = 0; i < n; i++) {
+        one = one && cdicts[i] == cdicts[0];
+        if (!cdicts[i]) continue;
+        away = away || cdicts[i]->device != c->device;
+        if (only && cdicts[i] != only) several = true;
+        only = cdicts[i];
+    }
+    if (one) return under_cdict(c, cdicts[0], [&] { return compress_batch_impl(c, srcs, srcSizes, n, dsts, dstCapacities, dstSizes); });
+    if (several && away) return ZERR(kErrParameterUnsupported);       // (a private upload per CDict is what the call exists to avoid)
+    c->lastBatchAlone = 0;
+    auto run = [&]() -> size_t {
+        const ZSTD_CDict_s* const was = c->cdict;
+        c->cdict = nullptr;
+        const CallParams cp = sticky_params(c);     // (the context's own level: each CDict's takes its place in compress_entries)
+        c->cdict = was;
+        return compress_entries(c, cp, (const u8* const*)srcs, srcSizes, n, (u8* const*)dsts, dstCapacities, dstSizes, nullptr, c->lastBatchAlone, nullptr, 0, cdicts);
+    };
+    if (!away) return run();
+    // one CDict that cannot be shared, beside entries without a dictionary: the context's private upload of it stands in while it is in
+    // force (under_cdict; dict_in_force), and the entries without one never ask for a dictionary
+    return under_cdict(c, only, [&]() -> size_t { const size_t e2 = cctx_sync_dictionary(c); return isErr(e2) ? e2 : run(); });
+}
+extern "C" size_t ZSTDMI_compressBatchCDicts(ZSTD_CCtx* c, const void* const* srcs, const size_t* srcSizes, size_t n, void* const* dsts, const size_t* dstCapacities,
+                                             size_t* dstSizes, const ZSTD_CDict* const* cdicts)
+{
+    return guarded([&] { return compress_batch_cdicts_impl(c, srcs, srcSizes, n, dsts, dstCapacities, dstSizes, cdicts); });
+}
 
 // ---- a pack: n device-resident entries into ONE seekable stream (ZSTDMI_compressPack, include/zstd_mi355x.h) ----
 // The entries are walked in order and cut into ROUNDS: maximal runs of entries compress_entries batches (entry_batched), at most
