@@ -379,8 +379,8 @@ size_t ZSTDMI_decompressDevice(ZSTD_DCtx* dctx, void* d_dst, size_t dstCapacity,
  * Decompress.  One lane per entry walks that entry's frames exactly as the single call's serial walk does (every frame, skippable
  * frames, trailing bytes, a dictID that is not the loaded one); the frames and blocks of all entries then go through the decoder ONCE,
  * with as many host synchronisations as a single call makes.  An entry's error is its first failing block's first error.  Entries
- * that hold a frame without a content size, and entries of more than 4 MiB compressed, are decoded by the single-call path one at a
- * time afterwards. */
+ * that hold a frame without a content size (unless ZSTDMI_DCtx_setBatchUnsized), and entries of more than 4 MiB compressed, are
+ * decoded by the single-call path one at a time afterwards. */
 size_t ZSTDMI_compressBatch(ZSTD_CCtx* cctx, const void* const* srcs, const size_t* srcSizes, size_t n,
                             void* const* dsts, const size_t* dstCapacities, size_t* dstSizes);
 size_t ZSTDMI_decompressBatch(ZSTD_DCtx* dctx, const void* const* srcs, const size_t* srcSizes, size_t n,
@@ -388,6 +388,20 @@ size_t ZSTDMI_decompressBatch(ZSTD_DCtx* dctx, const void* const* srcs, const si
 /* diagnostics: entries of the last batch call that did NOT take the batched pass (handed to the single-call path); -1 without a context */
 int ZSTDMI_debugLastBatchAlone(const ZSTD_CCtx* cctx);
 int ZSTDMI_debugLastBatchAloneD(const ZSTD_DCtx* dctx);
+/* ---- frames without a content size in the shared pass (what streaming encoders write; ZSTD_c_contentSizeFlag = 0) ----
+ * 0 = off (default): an entry holding a frame without a content size is decoded alone, after the shared pass (as before).
+ * 1 = such entries take the shared pass.  Sticky; touches no device.  NULL context or mode > 1: parameter_outOfBound
+ * (as ZSTDMI_DCtx_setOverlap answers).  Acts on ZSTDMI_decompressBatch and, through their shared core, on ZSTDMI_decompressRange(s).
+ * The contract does not change, only the path: dstSizes[i] and the bytes at dsts[i] are what ZSTDMI_decompressDevice gives for the
+ * entry alone — the regenerated size when it is at most dstCapacities[i] (which may be far below the frame's bound), dstSize_tooSmall
+ * when it is more, a failing block's error in front of dstSize_tooSmall — and nothing is written at or beyond dsts[i] +
+ * dstCapacities[i].  An entry's first frame starts at dsts[i] whatever its header says; the frames behind an unsized one are placed
+ * per entry, from the regenerated sizes, before any of their bytes is written.  The literal scratch of such an entry is bounded by its
+ * capacity, not by its frames' bounds.  Entries of more than 4 MiB compressed still go alone: the alone counters then count only those. */
+size_t    ZSTDMI_DCtx_setBatchUnsized(ZSTD_DCtx* dctx, unsigned mode);
+/* device bytes the last batch / range(s) call ASKED its work buffers for (frame and block lists, block keys, literal scratch,
+ * sequence records): what it requested, not what the context has retained from earlier calls; -1 without a context */
+long long ZSTDMI_debugLastBatchWorkspace(const ZSTD_DCtx* dctx);
 /* ---- a CDict per entry: many dictionaries, one compress pass (the compressor's side of ZSTD_d_refMultipleDDicts) ----
  * The arrays and pointers are those of ZSTDMI_compressBatch; cdicts is a host array of n entries, cdicts[i] == NULL: entry i has no
  * dictionary.  Per entry, dstSizes[i] (a size or an error code) and the bytes at dsts[i] are exactly what ZSTD_CCtx_refCDict(cctx,

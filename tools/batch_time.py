@@ -9,7 +9,13 @@ with history of the default settings — at the same kinds and levels.  Per poin
 Best of 3 after a warm-up call of the same shape; the host clock stops after the call's final synchronise (every call ends with one).
 The input is 16 MiB of generated data repeated (entries are independent, so the repeats are nobody's match).
 python tools/batch_time.py [MiB] [--dict-entropy] [--dict-row] [--frames-rows] [--measure-only] [--dict-index-rows] [--dict-index]
-                           [--level=N] [--dict-index-strategy=N] [--dict-index-chain]
+                           [--level=N] [--dict-index-strategy=N] [--dict-index-chain] [--unsized-rows] [--batch-unsized]
+  --unsized-rows : only the rows of ZSTDMI_DCtx_setBatchUnsized, decompression alone: text and Zipf entries of 4 KiB at level 3,
+                   (a) written with content sizes, one batch call; (b) written with ZSTD_c_contentSizeFlag = 0 and the window restated as
+                   the 2^19 a streaming encoder declares (each frame's bound: 128 KiB), the switch off — every entry goes alone: timed on
+                   the first 4096 entries and scaled as the loop column is —; (c) those with the switch on, one batch call; the stage
+                   times of (a) and (c) and what (c) asked its work buffers for.  Every entry is compared afterwards.
+  --batch-unsized : those rows with column (c) (without it the call is not made, so (a) and (b) also run on a library from before the switch)
   --dict-index-rows : only the rows of ZSTDMI_CCtx_setDictIndex, batch calls alone: 4 KiB text entries at level 1 with
                    tests/golden/train_default_text.dict, and the 1000 held-out JSON records of tests/golden/make_golden_train.py
                    tiled to the total with train_default_json.dict; the ratio, the batch call's ms and its stage times
@@ -36,10 +42,11 @@ FLAGS = [a for a in sys.argv[1:] if a.startswith("--")]
 ARGS = [a for a in sys.argv[1:] if not a.startswith("--")]
 VALUED = {f.split("=", 1)[0]: int(f.split("=", 1)[1]) for f in FLAGS if "=" in f}
 FLAGS = [f for f in FLAGS if "=" not in f]
-assert all(f in ("--dict-entropy", "--dict-row", "--frames-rows", "--measure-only", "--dict-index-rows", "--dict-index", "--dict-index-chain") for f in FLAGS), FLAGS
+assert all(f in ("--dict-entropy", "--dict-row", "--frames-rows", "--measure-only", "--dict-index-rows", "--dict-index", "--dict-index-chain", "--unsized-rows", "--batch-unsized") for f in FLAGS), FLAGS
 assert all(f in ("--level", "--dict-index-strategy") for f in VALUED), VALUED
 DICT_INDEX_ROWS, DICT_INDEX = "--dict-index-rows" in FLAGS, "--dict-index" in FLAGS
 INDEX_LEVEL, INDEX_STRATEGY, INDEX_CHAIN = VALUED.get("--level", 1), VALUED.get("--dict-index-strategy"), "--dict-index-chain" in FLAGS
+UNSIZED_ROWS, BATCH_UNSIZED = "--unsized-rows" in FLAGS, "--batch-unsized" in FLAGS
 DICT_ENTROPY, DICT_ROW, FRAMES_ROWS, MEASURE_ONLY = "--dict-entropy" in FLAGS, "--dict-row" in FLAGS, "--frames-rows" in FLAGS, "--measure-only" in FLAGS
 total = (int(ARGS[0]) if ARGS else 256) * MiB
 SAMPLE = 4096
@@ -126,8 +133,71 @@ def dict_index_rows():
         torch.cuda.empty_cache()
 
 
+def unsized_rows():
+    size, level = 4096, 3
+    n = total // size
+    cap = lib.ZSTD_compressBound(size)
+    offs = [i * size for i in range(n)]
+    coffs = [i * cap for i in range(n)]
+    print(f"{n} entries of 4 KiB at level {level}; ms per call of all entries (GB/s of content)", flush=True)
+    for kind in ("text", "zipf"):
+        src = torch.from_numpy(np.frombuffer(datagen.gen(kind, 16 * MiB, 5), dtype=np.uint8).copy()).cuda().repeat(total // (16 * MiB))
+        out = torch.empty(total, dtype=torch.uint8, device="cuda")
+        blobs = {}
+        for flag in (1, 0):
+            dst = torch.empty(n * cap + MiB, dtype=torch.uint8, device="cuda")
+            c = lib.ZSTD_createCCtx()
+            lib.ZSTD_CCtx_setParameter(c, 100, level); ok(lib.ZSTD_CCtx_setParameter(c, 200, flag))
+            got = (ctypes.c_size_t * n)()
+            ok(lib.ZSTDMI_compressBatch(c, ptrs(src.data_ptr(), offs), sizes([size] * n), n, ptrs(dst.data_ptr(), coffs), sizes([cap] * n), got))
+            assert not any(lib.ZSTD_isError(g) for g in got)
+            lib.ZSTD_freeCCtx(c)
+            if not flag:            # byte 5 is the window descriptor of a frame without a content size: 2^19
+                at = torch.tensor(coffs, dtype=torch.int64, device="cuda")
+                assert bool((dst[at + 4] & 0xE0).eq(0).all()), "a frame carries a content size"
+                dst[at + 5] = (19 - 10) << 3
+                torch.cuda.synchronize()
+            blobs[flag] = (dst, got, ptrs(dst.data_ptr(), coffs))
+        s_sz, back, o_ptr = sizes([size] * n), (ctypes.c_size_t * n)(), ptrs(out.data_ptr(), offs)
+
+        def run(d, flag, m=n):
+            dst, got, d_ptr = blobs[flag]
+            ok(lib.ZSTDMI_decompressBatch(d, d_ptr, got, m, o_ptr, s_sz, back))
+
+        def checked(d, flag, m=n):
+            out.zero_(); run(d, flag, m)
+            assert all(back[i] == size for i in range(m)) and bool(torch.equal(out[:m * size], src[:m * size]))
+
+        d = lib.ZSTD_createDCtx(); lib.ZSTDMI_DCtx_setProfiling(d, 1)
+        ta = best_of(lambda: run(d, 1)); checked(d, 1)
+        assert lib.ZSTDMI_debugLastBatchAloneD(d) == 0
+        sta = stage_times(lib.ZSTDMI_DCtx_getStageTimes, d)
+        lib.ZSTD_freeDCtx(d)
+        d = lib.ZSTD_createDCtx()
+        m = min(n, SAMPLE)
+        tb = best_of(lambda: run(d, 0, m)) * n / m; checked(d, 0, m)
+        assert lib.ZSTDMI_debugLastBatchAloneD(d) == m
+        lib.ZSTD_freeDCtx(d)
+        gbs = lambda t: total / t / 1e9
+        line = f"| {kind} 4 KiB L{level} | {n:6d} | (a) sized {ta * 1e3:7.2f} ({gbs(ta):6.1f}) | (b) unsized, switch off {tb * 1e3:9.1f} ({gbs(tb):6.3f}) |"
+        if BATCH_UNSIZED:
+            d = lib.ZSTD_createDCtx(); lib.ZSTDMI_DCtx_setProfiling(d, 1)
+            ok(lib.ZSTDMI_DCtx_setBatchUnsized(d, 1))
+            tc = best_of(lambda: run(d, 0)); checked(d, 0)
+            assert lib.ZSTDMI_debugLastBatchAloneD(d) == 0
+            stc, ws = stage_times(lib.ZSTDMI_DCtx_getStageTimes, d), lib.ZSTDMI_debugLastBatchWorkspace(d)
+            lib.ZSTD_freeDCtx(d)
+            line += f" (c) unsized, switch on {tc * 1e3:7.2f} ({gbs(tc):6.1f}) | workspace {ws / MiB:.1f} MiB |\n    (c) stages ms: {stc}"
+        print(line + f"\n    (a) stages ms: {sta}", flush=True)
+        del src, out, blobs
+        torch.cuda.empty_cache()
+
+
 if DICT_INDEX_ROWS:
     dict_index_rows()
+    sys.exit(0)
+if UNSIZED_ROWS:
+    unsized_rows()
     sys.exit(0)
 data = {k: torch.from_numpy(np.frombuffer(datagen.gen(k, 16 * MiB, 5), dtype=np.uint8).copy()).cuda().repeat(total // (16 * MiB)) for k in ("text", "zipf")}
 points = [(kind, size, level, None) for size in (4096, 16384, 65536) for kind in ("text", "zipf") for level in (1, 3)] + [("text", 4096, 3, DICT)]

@@ -121,6 +121,8 @@ SIGNATURES = {
     "ZSTDMI_debugLastBatchPasses": (ctypes.c_longlong, [c_void_p]),
     "ZSTDMI_debugLastBatchSetChunks": (ctypes.c_longlong, [c_void_p]),
     "ZSTDMI_debugLastBatchAloneD": (c_int, [c_void_p]),
+    "ZSTDMI_DCtx_setBatchUnsized": (c_size_t, [c_void_p, c_uint]),
+    "ZSTDMI_debugLastBatchWorkspace": (ctypes.c_longlong, [c_void_p]),
     "ZSTDMI_packBound": (c_size_t, [ctypes.POINTER(c_size_t), c_size_t]),
     "ZSTDMI_compressPack": (c_size_t, [c_void_p, c_void_p, c_size_t, ctypes.POINTER(c_void_p), ctypes.POINTER(c_size_t), c_size_t]),
     "ZSTDMI_debugLastPackAlone": (c_int, [c_void_p]),

@@ -18,9 +18,11 @@
 //                     repcodes by composing the blocks' transfer functions), regenerated size against the header's
 //                     (U/ZstdDecompress.cs:1177-1184).
 //   frame_rescan    : only when some frame carries no content size: output offsets of the frames from their regenerated sizes.
+//   batch_rescan    : the same per entry of a batch (ZSTDMI_DCtx_setBatchUnsized): one wave per entry that holds such a frame.
 #include "zmi_decode.h"
 #include "zmi_fse.h"
 #include "zmi_host.h"
+#include "zmi_batch_rescan.h"
 
 namespace zmi {
 
@@ -366,7 +368,12 @@ __global__ __launch_bounds__(256) void walk_emit_kernel(const u8* __restrict__ s
 // ------------------------------------------------------------------------------------------------
 // count: what frame_walk_serial_kernel's counting pass and the host's checks behind it make of the entry
 // kSet: as in frame_walk_serial_body; the frames found in the set are counted for the entries that are decoded here
-template <bool kSet>
+// kOpen (ZSTDMI_DCtx_setBatchUnsized): an entry that holds a frame without a content size is decoded here too.  Where its frames go
+// is settled by batch_rescan_kernel once their regenerated sizes are known, and only that kernel holds it to its capacity — the
+// bounds that stand for the sizes here (chain_step) usually exceed it.  Such an entry is marked `open` and counted, and `result`
+// carries the literal scratch it asks for: per frame the smaller of its content size (or bound) and the entry's capacity, since the
+// literals of an entry that fits cannot outnumber its output.  kOpen = false is the kernel as it always was.
+template <bool kSet, bool kOpen = false>
 __device__ __forceinline__ void batch_walk_count_body(const u8* __restrict__ src, const BatchEntryIn* __restrict__ in, BatchEntryOut* __restrict__ out, u32 nEntries,
                                                       u32 dictID, u64 aloneAbove, const DictSlot* __restrict__ slots, u32 nSet, u32* __restrict__ status)
 {
@@ -378,6 +385,7 @@ __device__ __forceinline__ void batch_walk_count_body(const u8* __restrict__ src
     const u64 end = E.srcOff + E.srcSize;
     const u32 maxFrames = (u32)((E.srcSize / 9 + 1) < (1u << 26) ? (E.srcSize / 9 + 1) : (1u << 26));
     u64 pos = E.srcOff, content = 0, nBlocks = 0; u32 n = 0, err = 0, nUnsized = 0, nInSet = 0;
+    u64 room = 0;
     while (end - pos >= 5) {
         ChainOut o;
         const u32 st = chain_step(src, end, pos, o);
@@ -392,12 +400,14 @@ __device__ __forceinline__ void batch_walk_count_body(const u8* __restrict__ src
         if (n >= maxFrames || nBlocks + o.nbBlocks > 0xFFFFFFF0ull) { err = kErrMemoryAllocation; break; }
         n++; nUnsized += o.unsized; nBlocks += o.nbBlocks;
         content += o.content; pos = o.next;
+        if constexpr (kOpen) room += o.content < E.dstCap ? o.content : E.dstCap;
     }
     if (!err && pos != end) err = kErrSrcSizeWrong;
     if (err) { r.state = kBatchDone; r.result = (u64)0 - (u64)err; }
-    else if (nUnsized) r.state = kBatchAlone;
-    else if (content > E.dstCap) { r.state = kBatchDone; r.result = (u64)0 - (u64)kErrDstSizeTooSmall; }
+    else if (nUnsized && !kOpen) r.state = kBatchAlone;
+    else if (!nUnsized && content > E.dstCap) { r.state = kBatchDone; r.result = (u64)0 - (u64)kErrDstSizeTooSmall; }
     else { r.state = kBatchDecode; r.result = content; r.nFrames = n; r.nBlocks = (u32)nBlocks; }
+    if constexpr (kOpen) { if (r.state == kBatchDecode && nUnsized) { r.open = 1; r.result = room; atomicAdd(status + kStOpenEntries, 1u); } }
     out[e] = r;
     if constexpr (kSet) { if (r.state == kBatchDecode && nInSet) atomicAdd(status + kStSetFrames, nInSet); }
 }
@@ -410,6 +420,12 @@ __global__ __launch_bounds__(64) void batch_walk_count_set_kernel(const u8* __re
                                                                   u64 aloneAbove, const DictSlot* __restrict__ slots, u32 nSet, u32* __restrict__ status)
 {
     batch_walk_count_body<true>(src, in, out, nEntries, 0, aloneAbove, slots, nSet, status);
+}
+template <bool kSet>
+__global__ __launch_bounds__(64) void batch_walk_count_open_kernel(const u8* __restrict__ src, const BatchEntryIn* __restrict__ in, BatchEntryOut* __restrict__ out, u32 nEntries,
+                                                                   u32 dictID, u64 aloneAbove, const DictSlot* __restrict__ slots, u32 nSet, u32* __restrict__ status)
+{
+    batch_walk_count_body<kSet, true>(src, in, out, nEntries, dictID, aloneAbove, slots, nSet, status);
 }
 
 // scan (single workgroup): every decoded entry's first frame, first block and literal-scratch offset; the totals go to the status
@@ -446,9 +462,16 @@ __global__ __launch_bounds__(256) void batch_scan_kernel(BatchEntryOut* __restri
 
 // emit: the same walk again, into the lists.  A frame's content goes to the entry's destination plus the frame's place inside the
 // entry; its literal scratch is the scratch prefix sum (in a single call both are the same number; here they are not)
-template <bool kSet>
+// kOpen: every frame's literal room goes to rooms[] (what the count summed: the scratch prefix advances by it), and in an open entry
+// every frame whose place is not final yet is marked kFrameOpen: an unsized frame, every frame behind one — sized ones included: the
+// dstOff they get here is computed from bounds —, and a frame the capacity does not admit (only batch_rescan refuses the entry, so that
+// a failing block's error still outranks dstSize_tooSmall).  What is left — sized frames in front of the first unsized one, inside the
+// capacity — is where it will stay.  An entry's first frame starts at the entry's destination whatever its header says, but an unsized
+// one has not been held to the capacity: FrameDesc::unsized keeps it from being written early (block_link).
+template <bool kSet, bool kOpen = false>
 __device__ __forceinline__ void batch_walk_emit_body(const u8* __restrict__ src, const BatchEntryIn* __restrict__ in, const BatchEntryOut* __restrict__ out, u32 nEntries,
-                                                     FrameDesc* __restrict__ frames, BlockDesc* __restrict__ blocks, const DictSlot* __restrict__ slots, u32 nSet)
+                                                     FrameDesc* __restrict__ frames, BlockDesc* __restrict__ blocks, const DictSlot* __restrict__ slots, u32 nSet,
+                                                     u64* __restrict__ rooms = nullptr)
 {
     const u32 e = blockIdx.x * 64 + threadIdx.x;
     if (e >= nEntries) return;
@@ -457,6 +480,7 @@ __device__ __forceinline__ void batch_walk_emit_body(const u8* __restrict__ src,
     const BatchEntryIn E = in[e];
     const u64 end = E.srcOff + E.srcSize;
     u64 pos = E.srcOff, dstOff = E.dstOff, scr = R.scratchOff; u32 idx = R.firstFrame, blk = R.firstBlock;
+    bool behind = false;                                        // (kOpen) an unsized frame lies in front
     while (end - pos >= 5 && idx < R.firstFrame + R.nFrames) {
         ChainOut o;
         const u32 st = emit_frame(src, end, pos, o, idx, blk, dstOff, frames, blocks);
@@ -464,7 +488,17 @@ __device__ __forceinline__ void batch_walk_emit_body(const u8* __restrict__ src,
         if (st == 0) {
             frames[idx].scratchOff = scr;
             if constexpr (kSet) { u32 inSet, wrong; frames[idx].dictSlot = dictset_select(slots, nSet, o.dictID, &inSet, &wrong); }     // (the count refused a wrong one)
-            idx++; blk += o.nbBlocks; dstOff += o.content; scr += o.content;
+            u64 room = o.content;
+            if constexpr (kOpen) {
+                if (R.open) {
+                    room = o.content < E.dstCap ? o.content : E.dstCap;
+                    const bool final = !behind && !o.unsized && dstOff - E.dstOff + o.content <= E.dstCap;
+                    if (!final) frames[idx].unsized = o.unsized | kFrameOpen;
+                    behind |= o.unsized != 0;
+                }
+                rooms[idx] = room;
+            }
+            idx++; blk += o.nbBlocks; dstOff += o.content; scr += room;
         }
         pos = o.next;
     }
@@ -478,6 +512,51 @@ __global__ __launch_bounds__(64) void batch_walk_emit_set_kernel(const u8* __res
                                                                  FrameDesc* __restrict__ frames, BlockDesc* __restrict__ blocks, const DictSlot* __restrict__ slots, u32 nSet)
 {
     batch_walk_emit_body<true>(src, in, out, nEntries, frames, blocks, slots, nSet);
+}
+template <bool kSet>
+__global__ __launch_bounds__(64) void batch_walk_emit_open_kernel(const u8* __restrict__ src, const BatchEntryIn* __restrict__ in, const BatchEntryOut* __restrict__ out, u32 nEntries,
+                                                                  FrameDesc* __restrict__ frames, BlockDesc* __restrict__ blocks, const DictSlot* __restrict__ slots, u32 nSet,
+                                                                  u64* __restrict__ rooms)
+{
+    batch_walk_emit_body<kSet, true>(src, in, out, nEntries, frames, blocks, slots, nSet, rooms);
+}
+
+// ------------------------------------------------------------------------------------------------
+// batch_rescan (ZSTDMI_DCtx_setBatchUnsized): behind block_offsets, in front of everything that writes into a destination
+// ------------------------------------------------------------------------------------------------
+// One wave per entry; an entry without an unsized frame is left at once (its places have been final since the walk).  The others: 64
+// frames a step, every lane one frame's regenerated size (block_offsets has put it into dstSize), the rule of zmi_batch_rescan.h:
+// dstOff = the entry's destination + the sizes in front.  An entry that does not fit its capacity — or that had a block without room in
+// the clamped literal scratch, which cannot fit — answers dstSize_tooSmall and every frame of it is marked bad, as is every frame of
+// an entry with a failed frame: place_literals, exec_matches, the origin path and the literal decoder pass over bad frames, so nothing
+// of such an entry is written behind this kernel.  A block's error, folded behind the run (batch_fold_kernel), replaces the answer.
+__global__ __launch_bounds__(64) void batch_rescan_kernel(const BatchEntryIn* __restrict__ in, BatchEntryOut* __restrict__ out, u32 nEntries, FrameDesc* __restrict__ frames)
+{
+    const u32 e = blockIdx.x, lane = threadIdx.x;
+    if (e >= nEntries) return;
+    if (uniform(out[e].state) != kBatchDecode || !uniform(out[e].open)) return;
+    const u32 first = uniform(out[e].firstFrame), n = uniform(out[e].nFrames);
+    const u64 entryOff = in[e].dstOff, cap = in[e].dstCap;
+    u64 carry = 0; bool anyBad = false, noRoom = false;
+    for (u32 k0 = 0; k0 < n; k0 += kRescanStep) {
+        const bool have = k0 + lane < n;
+        u64 mine = 0; u32 bad = 0, flags = 0;
+        if (have) { const FrameDesc& F = frames[first + k0 + lane]; mine = F.dstSize; bad = F.bad; flags = F.unsized; }
+        anyBad |= ballot(bad != 0) != 0; noRoom |= ballot((flags & kFrameNoRoom) != 0) != 0;
+        u64 incl = mine;
+#pragma unroll
+        for (u32 d = 1; d < kRescanStep; d <<= 1) incl = rescan_round(incl, __shfl_up(incl, d), lane, d);
+        const u64 before = rescan_before(carry, __shfl_up(incl, 1), lane);
+        if (have) frames[first + k0 + lane].dstOff = rescan_place(entryOff, before);
+        carry = rescan_add(carry, __shfl(incl, 63));
+    }
+    const bool fits = rescan_fits(carry, cap) && !noRoom;
+    if (!fits || anyBad) for (u32 k = lane; k < n; k += 64) frames[first + k].bad = 1;
+    if (lane == 0) out[e].result = fits ? carry : (u64)0 - (u64)kErrDstSizeTooSmall;
+}
+void launch_batch_rescan(const BatchEntryIn* in, BatchEntryOut* out, u32 nEntries, FrameDesc* frames, hipStream_t stream)
+{
+    hipLaunchKernelGGL(batch_rescan_kernel, dim3(nEntries), dim3(64), 0, stream, in, out, nEntries, frames);
 }
 
 // fold: an entry's error is the smallest key of its blocks — its first failing block's first error, what the single call reports
@@ -493,16 +572,20 @@ __global__ __launch_bounds__(64) void batch_fold_kernel(BatchEntryOut* __restric
 }
 
 void launch_batch_walk_count(const u8* src, const BatchEntryIn* in, BatchEntryOut* out, u32 nEntries, u32 dictID, u64 aloneAbove, u32* status, hipStream_t stream,
-                             const DictSlot* slots, u32 nSet)
+                             const DictSlot* slots, u32 nSet, bool open)
 {
-    if (slots) hipLaunchKernelGGL(batch_walk_count_set_kernel, dim3((nEntries + 63) / 64), dim3(64), 0, stream, src, in, out, nEntries, aloneAbove, slots, nSet, status);
+    if (open && slots) hipLaunchKernelGGL(batch_walk_count_open_kernel<true>, dim3((nEntries + 63) / 64), dim3(64), 0, stream, src, in, out, nEntries, 0u, aloneAbove, slots, nSet, status);
+    else if (open) hipLaunchKernelGGL(batch_walk_count_open_kernel<false>, dim3((nEntries + 63) / 64), dim3(64), 0, stream, src, in, out, nEntries, dictID, aloneAbove, (const DictSlot*)nullptr, 0u, status);
+    else if (slots) hipLaunchKernelGGL(batch_walk_count_set_kernel, dim3((nEntries + 63) / 64), dim3(64), 0, stream, src, in, out, nEntries, aloneAbove, slots, nSet, status);
     else hipLaunchKernelGGL(batch_walk_count_kernel, dim3((nEntries + 63) / 64), dim3(64), 0, stream, src, in, out, nEntries, dictID, aloneAbove);
     hipLaunchKernelGGL(batch_scan_kernel, dim3(1), dim3(256), 0, stream, out, nEntries, status);
 }
 void launch_batch_walk_emit(const u8* src, const BatchEntryIn* in, const BatchEntryOut* out, u32 nEntries, FrameDesc* frames, BlockDesc* blocks, hipStream_t stream,
-                            const DictSlot* slots, u32 nSet)
+                            const DictSlot* slots, u32 nSet, u64* rooms)
 {
-    if (slots) hipLaunchKernelGGL(batch_walk_emit_set_kernel, dim3((nEntries + 63) / 64), dim3(64), 0, stream, src, in, out, nEntries, frames, blocks, slots, nSet);
+    if (rooms && slots) hipLaunchKernelGGL(batch_walk_emit_open_kernel<true>, dim3((nEntries + 63) / 64), dim3(64), 0, stream, src, in, out, nEntries, frames, blocks, slots, nSet, rooms);
+    else if (rooms) hipLaunchKernelGGL(batch_walk_emit_open_kernel<false>, dim3((nEntries + 63) / 64), dim3(64), 0, stream, src, in, out, nEntries, frames, blocks, (const DictSlot*)nullptr, 0u, rooms);
+    else if (slots) hipLaunchKernelGGL(batch_walk_emit_set_kernel, dim3((nEntries + 63) / 64), dim3(64), 0, stream, src, in, out, nEntries, frames, blocks, slots, nSet);
     else hipLaunchKernelGGL(batch_walk_emit_kernel, dim3((nEntries + 63) / 64), dim3(64), 0, stream, src, in, out, nEntries, frames, blocks);
 }
 void launch_batch_fold(BatchEntryOut* out, u32 nEntries, const u64* keys, hipStream_t stream)
@@ -748,7 +831,22 @@ __global__ __launch_bounds__(256) void block_parse_kernel(const u8* __restrict__
 constexpr u32 kLinkSmall = 4;
 // kSet: "a formatted dictionary" is a property of the frame's own dictionary (slots[F.dictSlot]); a lane has a frame of its own here,
 // so haveDict is per lane.  (The kernel itself is the template: as a wrapper around an inlined body the parent's instance took one SGPR more.)
-template <bool kSet>
+// kOpen (a batch with entries that hold unsized frames, ZSTDMI_DCtx_setBatchUnsized): a frame's scratch is not dstSize long but as
+// long as the walk's rooms[] says (the status words name the array): for a frame of such an entry the smaller of dstSize and the
+// entry's capacity.  dstSize stays the bound: literals beyond IT are corruption.  Literals that fit the bound but not the room mean
+// that the entry does not fit its capacity (its output holds at least its literals): the block is sent to the scratch's dump area
+// (kStDumpLo), where its literals are decoded for their errors' sake and never read, and the frame is marked kFrameNoRoom, on which
+// batch_rescan answers dstSize_tooSmall for the entry unless a block's error outranks it.  kOpen = false is the kernel as it always was.
+// a block's litRel that makes scratch + scratchOff + litRel + frame x kLitSkew the dump area (offsets are sums modulo 2^64)
+__device__ __forceinline__ u64 dump_lit_rel(const u32* __restrict__ status, u64 scratchOff, u32 frame)
+{
+    return ((u64)status[kStDumpLo] | ((u64)status[kStDumpHi] << 32)) - scratchOff - (u64)frame * kLitSkew;
+}
+__device__ __forceinline__ const u64* lit_rooms(const u32* __restrict__ status)
+{
+    return reinterpret_cast<const u64*>((uintptr_t)((u64)status[kStRoomLo] | ((u64)status[kStRoomHi] << 32)));
+}
+template <bool kSet, bool kOpen = false>
 __global__ __launch_bounds__(64) void block_link_small_kernel(FrameDesc* __restrict__ frames, BlockDesc* __restrict__ blocks, u32 nFrames, u32 haveDict,
                                                               u32 earlyLiterals, u32* __restrict__ status, const DictSlot* __restrict__ slots)
 {
@@ -757,6 +855,8 @@ __global__ __launch_bounds__(64) void block_link_small_kernel(FrameDesc* __restr
     FrameDesc& F = frames[f];
     if (F.nbBlocks > kLinkSmall) return;                       // (a wave of block_link_kernel takes it)
     if constexpr (kSet) haveDict = slots[F.dictSlot].formatted;
+    u64 room = 0; u32 noRoom = 0;
+    if constexpr (kOpen) room = lit_rooms(status)[f];
     // a formatted dictionary: every frame starts from its Huffman table and its three FSE tables (ZSTD_decompressBegin_usingDict,
     // U/ZstdDecompress.cs:1956-1990); without one nothing is defined before the frame's first block defines it
     u32 lastHuf = haveDict ? kDictBlock : kNoBlock;
@@ -770,9 +870,12 @@ __global__ __launch_bounds__(64) void block_link_small_kernel(FrameDesc* __restr
         if (B.litType == 2) { lastHuf = bi; B.hufSrc = bi; }
         else if (B.litType == 3) { B.hufSrc = lastHuf; if (lastHuf == kNoBlock) err = kErrDictionaryCorrupted; }     // U/ZstdDecompressBlock.cs:197-207
         if (B.litType >= 2) {
+            bool dumped = false;
             if (B.litSize > F.dstSize - litAcc) { err = err ? err : (u32)kErrCorruption; B.litRel = 0; }
+            else if (kOpen && (litAcc > room || B.litSize > room - litAcc)) { B.litRel = dump_lit_rel(status, F.scratchOff, f); dumped = true; noRoom = 1; }
             else { B.litRel = litAcc; litAcc += B.litSize; }
-            B.litInPlace = (B.nbSeq == 0 && (!earlyLiterals || (k == 0 && !F.unsized))) ? 1u : 0u;
+            // (F.unsized: without a content size, or — a batch entry with such a frame — at a place that is not final yet)
+            B.litInPlace = (B.nbSeq == 0 && !dumped && (!earlyLiterals || (k == 0 && !F.unsized))) ? 1u : 0u;
         }
         if (B.nbSeq) {
             hasSeq = 1;
@@ -786,6 +889,7 @@ __global__ __launch_bounds__(64) void block_link_small_kernel(FrameDesc* __restr
         if (err) { B.err = err; report_error(status, bi, B.litType >= 2 && (err == kErrDictionaryCorrupted || B.litSize > F.dstSize) ? kStageLiterals : kStageSequences, err); }
     }
     F.hasSeq = hasSeq;
+    if constexpr (kOpen) { if (noRoom) F.unsized |= kFrameNoRoom; }
     if (litAcc) atomicAdd(reinterpret_cast<unsigned long long*>(status + kStLitLo), (unsigned long long)litAcc);
     if (hasSeq && F.dstSize >= (1u << 20) && F.dstSize < (1ull << 30))
         atomicAdd(reinterpret_cast<unsigned long long*>(status + kStBigBins) + highbit32((u32)(F.dstSize >> 20)), (unsigned long long)F.dstSize);
@@ -803,7 +907,8 @@ __device__ __forceinline__ u32 latest_before(u64 mask, u32 firstOfBatch, u32 car
 // every later stage passes over; what they themselves lack (a table defined before the oldest carried block) is no error.  A fragment
 // is one frame, linked by this kernel whatever its number of blocks.
 // kSet: haveDict is the frame's own dictionary's (one frame per wave: uniform)
-template <bool PH, bool kSet = false>
+// kOpen: as in block_link_small_kernel (a block behind one without room has none either: the prefix sum counts them all)
+template <bool PH, bool kSet = false, bool kOpen = false>
 __device__ __forceinline__ void block_link_body(FrameDesc* __restrict__ frames, BlockDesc* __restrict__ blocks, u32 nFrames, u32 haveDict,
                                                 u32 earlyLiterals, u32* __restrict__ status, u32 phantoms, const DictSlot* __restrict__ slots = nullptr)
 {
@@ -814,6 +919,8 @@ __device__ __forceinline__ void block_link_body(FrameDesc* __restrict__ frames, 
     const u32 first = uniform(F.firstBlock), nb = uniform(F.nbBlocks);
     if (!PH && nb <= kLinkSmall) return;                       // (a lane of block_link_small_kernel takes it)
     const u64 dstSize = F.dstSize;
+    u64 room = 0, dumpRel = 0; u32 noRoom = 0;
+    if constexpr (kOpen) { room = lit_rooms(status)[f]; dumpRel = dump_lit_rel(status, F.scratchOff, f); }
     // a formatted dictionary: every frame starts from its Huffman table and its three FSE tables (ZSTD_decompressBegin_usingDict,
     // U/ZstdDecompress.cs:1956-1990); without one nothing is defined before the frame's first block defines it
     u32 lastHuf = haveDict ? kDictBlock : kNoBlock;
@@ -844,7 +951,10 @@ __device__ __forceinline__ void block_link_body(FrameDesc* __restrict__ frames, 
 #pragma unroll
         for (int d = 1; d < 64; d <<= 1) { const u64 t = __shfl_up(incl, d); if ((int)lane >= d) incl += t; }
         u64 litRel = litAcc + incl - mine;
+        bool dumped = false;
         if (coded && litRel + mine > dstSize) { err = err ? err : (u32)kErrCorruption; litRel = 0; }
+        else if (kOpen && coded && litRel + mine > room) { litRel = dumpRel; dumped = true; }
+        if constexpr (kOpen) { if (ballot(dumped)) noRoom = 1; }
         litAcc += __shfl(incl, 63);
         // repeat-mode FSE tables: the latest table of that kind defined in front of the block (:1780-1786)
         const bool seqs = live && nbSeq != 0;
@@ -866,7 +976,7 @@ __device__ __forceinline__ void block_link_body(FrameDesc* __restrict__ frames, 
                 B.hufSrc = hufSrc; B.litRel = litRel;
                 // earlyLiterals: the literal decoder runs beside seq_decode, i.e. before block_offsets: only where the output offset is
                 // known by now — the first block of a frame with a content size — can it write the output itself
-                B.litInPlace = (nbSeq == 0 && (!earlyLiterals || (k0 + lane == 0 && !F.unsized))) ? 1u : 0u;
+                B.litInPlace = (nbSeq == 0 && !dumped && (!earlyLiterals || (k0 + lane == 0 && !F.unsized))) ? 1u : 0u;
             }
             if (seqs) { B.tblSrc[0] = src3[0]; B.tblSrc[1] = src3[1]; B.tblSrc[2] = src3[2]; }
             if (err) { B.err = err; report_error(status, bi, litType >= 2 && (err == kErrDictionaryCorrupted || litSize > dstSize) ? kStageLiterals : kStageSequences, err); }
@@ -874,6 +984,7 @@ __device__ __forceinline__ void block_link_body(FrameDesc* __restrict__ frames, 
     }
     if (lane == 0) {
         F.hasSeq = hasSeq;
+        if constexpr (kOpen) { if (noRoom) F.unsized |= kFrameNoRoom; }
         if (litAcc) atomicAdd(reinterpret_cast<unsigned long long*>(status + kStLitLo), (unsigned long long)litAcc);
         // long frames by size class: what the host decides the origin path from (decode_origin.hip); a frame without a content size counts with its bound
         if (hasSeq && dstSize >= (1u << 20) && dstSize < (1ull << 30))
@@ -889,6 +1000,12 @@ __global__ __launch_bounds__(64) void block_link_set_kernel(FrameDesc* __restric
                                                             u32 earlyLiterals, u32* __restrict__ status, const DictSlot* __restrict__ slots)
 {
     block_link_body<false, true>(frames, blocks, nFrames, 0, earlyLiterals, status, 0, slots);
+}
+template <bool kSet>
+__global__ __launch_bounds__(64) void block_link_open_kernel(FrameDesc* __restrict__ frames, BlockDesc* __restrict__ blocks, u32 nFrames, u32 haveDict,
+                                                             u32 earlyLiterals, u32* __restrict__ status, const DictSlot* __restrict__ slots)
+{
+    block_link_body<false, kSet, true>(frames, blocks, nFrames, haveDict, earlyLiterals, status, 0, slots);
 }
 __global__ __launch_bounds__(64) void block_link_stream_kernel(FrameDesc* __restrict__ frames, BlockDesc* __restrict__ blocks, u32 nFrames, u32 haveDict,
                                                                u32 earlyLiterals, u32* __restrict__ status, u32 phantoms)
@@ -944,9 +1061,20 @@ __global__ __launch_bounds__(1024) void seq_scan_kernel(BlockDesc* __restrict__ 
 }
 
 void launch_block_prepass(const u8* src, FrameDesc* frames, BlockDesc* blocks, u32 nFrames, u32 nBlocks, u32 haveDict, u32 earlyLiterals, u32* status, hipStream_t stream,
-                          u32 phantoms, const DictSlot* slots)
+                          u32 phantoms, const DictSlot* slots, bool open)
 {
     hipLaunchKernelGGL(block_parse_kernel, dim3((nBlocks + 255) / 256), dim3(256), 0, stream, src, blocks, nBlocks, status);
+    if (open) {                 // (a batch: never a fragment of a segmented stream)
+        if (slots) {
+            hipLaunchKernelGGL((block_link_small_kernel<true, true>), dim3((nFrames + 63) / 64), dim3(64), 0, stream, frames, blocks, nFrames, 0u, earlyLiterals, status, slots);
+            if (nBlocks > nFrames) hipLaunchKernelGGL(block_link_open_kernel<true>, dim3(nFrames), dim3(64), 0, stream, frames, blocks, nFrames, 0u, earlyLiterals, status, slots);
+        } else {
+            hipLaunchKernelGGL((block_link_small_kernel<false, true>), dim3((nFrames + 63) / 64), dim3(64), 0, stream, frames, blocks, nFrames, haveDict, earlyLiterals, status, (const DictSlot*)nullptr);
+            if (nBlocks > nFrames) hipLaunchKernelGGL(block_link_open_kernel<false>, dim3(nFrames), dim3(64), 0, stream, frames, blocks, nFrames, haveDict, earlyLiterals, status, (const DictSlot*)nullptr);
+        }
+        hipLaunchKernelGGL(seq_scan_kernel, dim3(1), dim3(1024), 0, stream, blocks, nBlocks, status);
+        return;
+    }
     if (slots) {                // (never a fragment of a segmented stream: the host refuses that combination)
         hipLaunchKernelGGL(block_link_small_kernel<true>, dim3((nFrames + 63) / 64), dim3(64), 0, stream, frames, blocks, nFrames, 0u, earlyLiterals, status, slots);
         if (nBlocks > nFrames) hipLaunchKernelGGL(block_link_set_kernel, dim3(nFrames), dim3(64), 0, stream, frames, blocks, nFrames, earlyLiterals, status, slots);
@@ -967,7 +1095,8 @@ void launch_block_prepass(const u8* src, FrameDesc* frames, BlockDesc* blocks, u
 // block_offsets: output offsets and starting repcodes of the blocks of a frame (one wave per frame, after seq_decode)
 // ------------------------------------------------------------------------------------------------
 // kSet: the repcodes a frame starts from are its own dictionary's (one frame per wave: the record's fields are wave-uniform)
-template <bool kSet>
+// kOpen (a batch with entries that hold unsized frames): FrameDesc::unsized carries flags beside "no content size" (kFrameOpen)
+template <bool kSet, bool kOpen = false>
 __device__ __forceinline__ void block_offsets_body(FrameDesc* __restrict__ frames, BlockDesc* __restrict__ blocks, u32 nFrames,
                                                    const DictInfo* __restrict__ di, u32* __restrict__ status, const DictSlot* __restrict__ slots)
 {
@@ -1019,10 +1148,11 @@ __device__ __forceinline__ void block_offsets_body(FrameDesc* __restrict__ frame
     }
     if (lane == 0) {
         FrameDesc& F = frames[f];
+        const u32 unsized = kOpen ? F.unsized & kFrameUnsized : F.unsized;
         if (bad) F.bad = 1;
-        else if (!F.unsized && acc != F.dstSize) {              // regenerated size must equal the header's (U/ZstdDecompress.cs:1177-1184)
+        else if (!unsized && acc != F.dstSize) {              // regenerated size must equal the header's (U/ZstdDecompress.cs:1177-1184)
             F.bad = 1; report_error(status, (u64)first + nb - 1, kStageFrameEnd, kErrCorruption);
-        } else if (F.unsized) {
+        } else if (unsized) {
             if (acc > F.dstSize) { F.bad = 1; report_error(status, (u64)first + nb - 1, kStageFrameEnd, kErrCorruption); }   // more than nbBlocks x blockSizeMax: no valid encoder
             else F.dstSize = acc;
         }
@@ -1037,6 +1167,12 @@ __global__ __launch_bounds__(64) void block_offsets_set_kernel(FrameDesc* __rest
                                                                u32* __restrict__ status, const DictSlot* __restrict__ slots)
 {
     block_offsets_body<true>(frames, blocks, nFrames, nullptr, status, slots);
+}
+template <bool kSet>
+__global__ __launch_bounds__(64) void block_offsets_open_kernel(FrameDesc* __restrict__ frames, BlockDesc* __restrict__ blocks, u32 nFrames,
+                                                                const DictInfo* __restrict__ di, u32* __restrict__ status, const DictSlot* __restrict__ slots)
+{
+    block_offsets_body<kSet, true>(frames, blocks, nFrames, di, status, slots);
 }
 
 // frames without a content size: the frames' output offsets from their regenerated sizes (single workgroup); the total goes to
@@ -1054,9 +1190,11 @@ __global__ __launch_bounds__(1024) void frame_rescan_kernel(FrameDesc* __restric
 }
 
 void launch_block_offsets(FrameDesc* frames, BlockDesc* blocks, u32 nFrames, const DictInfo* di, u32 rescan, u64 dstCapacity, u32* status, hipStream_t stream,
-                          const DictSlot* slots)
+                          const DictSlot* slots, bool open)
 {
-    if (slots) hipLaunchKernelGGL(block_offsets_set_kernel, dim3(nFrames), dim3(64), 0, stream, frames, blocks, nFrames, status, slots);
+    if (open && slots) hipLaunchKernelGGL(block_offsets_open_kernel<true>, dim3(nFrames), dim3(64), 0, stream, frames, blocks, nFrames, (const DictInfo*)nullptr, status, slots);
+    else if (open) hipLaunchKernelGGL(block_offsets_open_kernel<false>, dim3(nFrames), dim3(64), 0, stream, frames, blocks, nFrames, di, status, (const DictSlot*)nullptr);
+    else if (slots) hipLaunchKernelGGL(block_offsets_set_kernel, dim3(nFrames), dim3(64), 0, stream, frames, blocks, nFrames, status, slots);
     else hipLaunchKernelGGL(block_offsets_kernel, dim3(nFrames), dim3(64), 0, stream, frames, blocks, nFrames, di, status);
     if (rescan) hipLaunchKernelGGL(frame_rescan_kernel, dim3(1), dim3(1024), 0, stream, frames, nFrames, dstCapacity, status);
 }

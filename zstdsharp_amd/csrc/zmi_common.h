@@ -115,7 +115,9 @@ struct FrameDesc {      // one per frame found by the frame walk (U/ZstdDecompre
     u64 srcSize;        // compressed frame size
     u64 dstSize;        // content size; for a frame without one the bound nbBlocks x blockSizeMax until the regenerated size replaces it
     u32 firstBlock, nbBlocks;
-    u32 unsized;        // 1 = the header carries no content size
+    u32 unsized;        // bit 0 (kFrameUnsized) = the header carries no content size; bit 1 (kFrameOpen), a batch entry that holds such a
+                        // frame: this frame's place is not final when the lists are emitted — it is unsized, lies behind an unsized
+                        // one, or the entry's capacity has yet to admit it — so nothing may write its output before batch_rescan
     u32 checksum;       // 1 = a 4-byte XXH64 checksum follows the last block
     u32 bad;            // 1 = some stage failed in this frame (its error is in the status words): later stages leave it alone
     u32 hasSeq;         // 1 = at least one block holds sequences (the ordered executor has work in this frame)
@@ -127,6 +129,9 @@ struct FrameDesc {      // one per frame found by the frame walk (U/ZstdDecompre
 // XXH64 of a frame that is decoded in segments (decode_stream.hip): the state between two segments.  reset: acc = the four seeds
 // (P1 + P2, P2, 0, -P1), everything else zero (xxh_carry_reset, zstd_mi355x_dec.hip)
 struct XxhCarry { u64 acc[4]; u64 total; u32 tailLen; u32 hash; u8 tail[32]; };
+
+// (bit 2, set by block_link's open instances: some block of the frame found no room in the clamped literal scratch — the entry cannot fit)
+enum : u32 { kFrameUnsized = 1, kFrameOpen = 2, kFrameNoRoom = 4 };
 
 constexpr u32 kNoBlock   = 0xFFFFFFFFu;     // table source: nothing defined it (corruption, or the default where that is legal)
 constexpr u32 kDictBlock = 0xFFFFFFFEu;     // table source: the formatted dictionary
@@ -178,7 +183,9 @@ struct BatchEntryOut {
     u64 scratchOff;     // literal scratch of its first frame (prefix sum of the content sizes over the entries that are decoded)
     u32 firstFrame, firstBlock, nFrames, nBlocks;
     u32 state;          // kBatchDecode: its frames are in the lists; kBatchDone: `result` is final (header-stage error, dstSize_tooSmall);
-    u32 pad;            // kBatchAlone: the single-call path decodes it afterwards (a frame without a content size, a very large entry)
+    u32 open;           // kBatchAlone: the single-call path decodes it afterwards (a frame without a content size, a very large entry)
+                        // open (kBatchDecode under ZSTDMI_DCtx_setBatchUnsized): 1 = it holds a frame without a content size: `result` is the
+                        // literal scratch it asks for until batch_rescan_kernel puts its answer there
 };
 
 // A range of a seekable stream (ZSTDMI_decompressRange): what seek_select_kernel makes of the seek table and (offset, length), and
@@ -235,7 +242,14 @@ enum : u32 { kStFrames = 0, kStErr = 1, kStTotalLo = 2, kStTotalHi = 3, kStUsabl
              kStBigBins = 56,           // 12 x u64: content bytes of the frames with sequences by size class, bin k = [2^(20+k), 2^(21+k)), below 2^30
              kStDictTabBlocks = 80,     // blocks that copied a sequence table from a DDict's ready-made set (seq_decode_kernel's instance for it)
              kStSetFrames = 82,         // frames whose dictionary was found in the DDict set by dictID (the walks' set instances)
-             kStWords = 84 };
+             // a batch call under ZSTDMI_DCtx_setBatchUnsized (the open instances of the walk and of block_link):
+             kStOpenEntries = 84,       // entries in the lists that hold a frame without a content size
+             kStRoomLo = 85, kStRoomHi = 86,            // address of one u64 per frame: the room its literals have in the scratch
+             kStDumpLo = 87, kStDumpHi = 88,            // offset in the scratch of kLitDump bytes that every block without room decodes into
+             kStWords = 90 };
+// Literals of a block that has no room left in its frame's scratch (the room of an entry with unsized frames is clamped to the entry's
+// capacity) still have to be decoded — a damaged stream's error outranks dstSize_tooSmall — but nobody reads them
+constexpr u32 kLitDump = (128u << 10) + 512;
 constexpr u32 kOriginRounds = 36;
 
 // Stage timing (ZSTDMI_*_setProfiling): a launcher that issues several kernels marks the end of each on the context's timer, so

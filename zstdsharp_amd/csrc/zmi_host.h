@@ -98,9 +98,11 @@ void launch_frame_walk_emit(const u8* src, u64 srcSize, FrameDesc* frames, Block
 void launch_frame_walk_serial(const u8* src, u64 srcSize, FrameDesc* frames, BlockDesc* blocks, u32 maxFrames, u32* status, u32 dictID, u32 emit,
                               hipStream_t stream, const DictSlot* slots = nullptr, u32 nSet = 0);
 void launch_batch_walk_count(const u8* src, const BatchEntryIn* in, BatchEntryOut* out, u32 nEntries, u32 dictID, u64 aloneAbove, u32* status, hipStream_t stream,
-                             const DictSlot* slots = nullptr, u32 nSet = 0);
+                             const DictSlot* slots = nullptr, u32 nSet = 0, bool open = false);        // open: ZSTDMI_DCtx_setBatchUnsized
+// rooms (not null: the open instance): one u64 per frame, the room its literals have in the scratch
 void launch_batch_walk_emit(const u8* src, const BatchEntryIn* in, const BatchEntryOut* out, u32 nEntries, FrameDesc* frames, BlockDesc* blocks, hipStream_t stream,
-                            const DictSlot* slots = nullptr, u32 nSet = 0);
+                            const DictSlot* slots = nullptr, u32 nSet = 0, u64* rooms = nullptr);
+void launch_batch_rescan(const BatchEntryIn* in, BatchEntryOut* out, u32 nEntries, FrameDesc* frames, hipStream_t stream);
 void launch_batch_fold(BatchEntryOut* out, u32 nEntries, const u64* keys, hipStream_t stream);
 void launch_seek_select(const u8* tab, u64 tableBytes, u32 n, u32 stride, u64 srcSize, u64 offset, u64 length, u64* sum, hipStream_t stream);
 void launch_seek_emit(const u8* tab, u32 stride, u32 first, u32 nSel, u64 dFirst, u64 offset, u64 dstBias, u64 edgeBias, u64 slot1, u32 cutFirst, u32 cutLast,
@@ -120,7 +122,7 @@ void launch_seq_stats(const Seq* seqs, const u8* lits, const ChunkMeta* meta, u3
 void launch_dict_parse(const u8* dict, u32 dictSize, DictInfo* out, hipStream_t stream);
 void launch_dict_ctables(const u8* dict, u32 dictSize, const DictInfo* info, DictCTables* out, hipStream_t stream);
 void launch_block_prepass(const u8* src, FrameDesc* frames, BlockDesc* blocks, u32 nFrames, u32 nBlocks, u32 haveDict, u32 earlyLiterals, u32* status, hipStream_t stream,
-                          u32 phantoms = 0, const DictSlot* slots = nullptr);     // phantoms: decode_walk.hip block_link_body
+                          u32 phantoms = 0, const DictSlot* slots = nullptr, bool open = false);     // phantoms, open: decode_walk.hip block_link_body
 // dictTabs (null: none): a DDict's ready-made tables, which the kernel's instance for them copies where a block repeats the dictionary's
 void launch_seq_decode(const u8* src, const FrameDesc* frames, BlockDesc* blocks, u32 nBlocks, SeqRec* recs, u32* status,
                        const u8* dictFull, const DictInfo* di, const u32* dictTabs, hipStream_t stream, const DictSlot* slots = nullptr);
@@ -129,7 +131,7 @@ void launch_seq_decode(const u8* src, const FrameDesc* frames, BlockDesc* blocks
 constexpr u32 kDictTabLogs = 1280, kDictTabWords = 1284;
 void launch_dict_seq_tables(const u8* dictFull, const DictInfo* di, u32* tabs, hipStream_t stream);
 void launch_block_offsets(FrameDesc* frames, BlockDesc* blocks, u32 nFrames, const DictInfo* di, u32 rescan, u64 dstCapacity, u32* status, hipStream_t stream,
-                          const DictSlot* slots = nullptr);
+                          const DictSlot* slots = nullptr, bool open = false);
 void launch_decode_literals(const u8* src, u8* out, u8* scratch, const FrameDesc* frames, const BlockDesc* blocks, u32 nBlocks, u32* status,
                             u8* slowFlags, u32 mode, const u8* dictFull, const DictInfo* di, hipStream_t stream, StageHook hook,
                             const DictSlot* slots = nullptr);

@@ -20,6 +20,11 @@ struct ZSTD_DCtx_s {
     DevBuf frames, blocks, recs, status, scratch, walkWs, slowFlags, stageSrc, stageDst, origin, originList;
     DevBuf batchIn, batchOut, blockKeys;    // ZSTDMI_decompressBatch: the entries' table, what the batch walk made of them, one error key per block
     int lastBatchAlone = 0;     // entries of the last ZSTDMI_decompressBatch that were decoded by the single-call path (debug hook)
+    // ZSTDMI_DCtx_setBatchUnsized: 1 = an entry of a batch / range(s) call that holds a frame without a content size takes the shared
+    // pass (decode_entries) instead of going alone.  litRooms: one u64 per frame of such a pass, the room its literals have in the scratch
+    int batchUnsized = 0;
+    DevBuf litRooms;
+    long long lastBatchWs = 0;  // device bytes the last decode_entries run asked its work buffers for (ZSTDMI_debugLastBatchWorkspace)
     DevBuf seekTab, seekSum, edge;          // ZSTDMI_decompressRange: a host source's seek table, the summary words, the frames the range cuts
     int lastRangeFrames = 0; long long lastRangeStaged = 0;     // table entries the last range call decoded, bytes it copied host -> device (debug hooks)
     // ZSTDMI_decompressRanges: the pass's workspace (RangesWs), the ranges as the host states them / as ranges_select files them /
@@ -123,7 +128,7 @@ size_t ZSTD_freeDCtx(ZSTD_DCtx* d)
     if (d->deviceOk) {
         (void)hipSetDevice(d->device);
         if (d->ownStream) (void)hipStreamSynchronize(d->ownStream);
-        d->frames.release(); d->blocks.release(); d->recs.release(); d->status.release(); d->scratch.release(); d->walkWs.release(); d->slowFlags.release(); d->stageSrc.release(); d->stageDst.release(); d->dict.release(); d->dictInfoDev.release(); d->origin.release(); d->originList.release(); d->batchIn.release(); d->batchOut.release(); d->blockKeys.release(); d->seekTab.release(); d->seekSum.release(); d->edge.release(); d->pfxStage.release(); d->rangesWs.release(); d->rangesIn.release(); d->rangesRec.release(); d->rangesRes.release(); d->arena.release(); d->slotTab.release();
+        d->frames.release(); d->blocks.release(); d->recs.release(); d->status.release(); d->scratch.release(); d->walkWs.release(); d->slowFlags.release(); d->stageSrc.release(); d->stageDst.release(); d->dict.release(); d->dictInfoDev.release(); d->origin.release(); d->originList.release(); d->batchIn.release(); d->batchOut.release(); d->blockKeys.release(); d->litRooms.release(); d->seekTab.release(); d->seekSum.release(); d->edge.release(); d->pfxStage.release(); d->rangesWs.release(); d->rangesIn.release(); d->rangesRec.release(); d->rangesRes.release(); d->arena.release(); d->slotTab.release();
         d->hist[0].release(); d->hist[1].release(); d->segReps.release(); d->segXxh.release();
         d->timer.destroy();
         if (d->aux) { (void)hipStreamSynchronize(d->aux); (void)hipStreamDestroy(d->aux); }
@@ -383,6 +388,10 @@ static size_t status_read(ZSTD_DCtx* d, u32* st) { return dev_read(st, d->status
 static u64 st_u64(const u32* st, u32 lo, u32 hi) { return (u64)st[lo] | ((u64)st[hi] << 32); }
 
 // the work lists of a run over nFrames frames and nBlocks blocks with `total` bytes of content
+static size_t lists_bytes(u32 nFrames, u32 nBlocks, u64 total)
+{
+    return (size_t)nFrames * sizeof(FrameDesc) + (size_t)nBlocks * sizeof(BlockDesc) + 64 + (size_t)total + (size_t)nFrames * kLitSkew + 256 + (size_t)nBlocks + 64;
+}
 static bool ensure_lists(ZSTD_DCtx* d, u32 nFrames, u32 nBlocks, u64 total)
 {
     return d->frames.ensure((size_t)nFrames * sizeof(FrameDesc)) && d->blocks.ensure((size_t)nBlocks * sizeof(BlockDesc) + 64) &&
@@ -394,9 +403,13 @@ static bool ensure_lists(ZSTD_DCtx* d, u32 nFrames, u32 nBlocks, u64 total)
 // with the last status read (-> false: failed); st = the status words after it.  -> 0 or the error of the whole run.
 // `link` (a fragment of a segmented stream, decode_fragment): the first link->phantoms blocks only define tables, and the frame's
 // repcodes start from link->reps where that is not NULL.
+// `open` (a batch whose lists hold entries with unsized frames, decode_entries): block_link and block_offsets run their open instances,
+// and batch_rescan_kernel settles those entries' places behind block_offsets, in front of everything that writes into a destination
+// (the literal decoder beside seq_decode writes only where block_link found the place final).
 struct StreamLink { u32 phantoms; const DictInfo* reps; };
+struct OpenEntries { const BatchEntryIn* in; BatchEntryOut* out; u32 n; };
 static size_t decode_lists(ZSTD_DCtx* d, const DecodeDict& dd, u8* d_dst, const u8* d_src, u32 nFrames, u32 nBlocks, u32 nUnsized, size_t dstCapacity, u32* st, const std::function<bool()>& tail,
-                           const StreamLink* link = nullptr)
+                           const StreamLink* link = nullptr, const OpenEntries* open = nullptr)
 {
     hipStream_t s = d->stream;
     u32* status = (u32*)d->status.p;
@@ -409,8 +422,11 @@ static size_t decode_lists(ZSTD_DCtx* d, const DecodeDict& dd, u8* d_dst, const 
     // seq_decode on a stream of its own (`early`: block_link then lets it write only the outputs whose place is known by now).
     // Whether it does is decided once the pre-pass has counted both kinds of work (below).
     constexpr u32 kOverlapBlocks = 12288;
-    const bool early = d->overlapMode == 2 || (d->overlapMode == 0 && nBlocks <= kOverlapBlocks);
-    launch_block_prepass(d_src, frames, blocks, nFrames, nBlocks, fmt ? 1u : 0u, early ? 1u : 0u, status, s, link ? link->phantoms : 0u, slots);
+    // Not in a single call of several frames with an unsized one among them: a sized frame behind an unsized one has, until
+    // frame_rescan, a dstOff computed from the bound in front of it, and block_link (which knows a frame's header, not its
+    // neighbours) would let its first block be written there.  (A batch marks such frames itself: kFrameOpen.)
+    const bool early = !(nUnsized && nFrames > 1) && (d->overlapMode == 2 || (d->overlapMode == 0 && nBlocks <= kOverlapBlocks));
+    launch_block_prepass(d_src, frames, blocks, nFrames, nBlocks, fmt ? 1u : 0u, early ? 1u : 0u, status, s, link ? link->phantoms : 0u, slots, open != nullptr);
     { const size_t e = status_read(d, st); if (isErr(e)) return e; }
     d->timer.mark("block_prepass", s);
     const u64 nSeq = st_u64(st, kStSeqLo, kStSeqHi);
@@ -460,7 +476,8 @@ static size_t decode_lists(ZSTD_DCtx* d, const DecodeDict& dd, u8* d_dst, const 
         auxGuard.on = true;
     }
     launch_seq_decode(d_src, frames, blocks, nBlocks, recs, status, dictFull, dinfo, dd.seqTabs, s, slots);     d->timer.mark("seq_decode", s);
-    launch_block_offsets(frames, blocks, nFrames, link && link->reps ? link->reps : dinfo, nUnsized ? 1u : 0u, dstCapacity, status, s, slots);  d->timer.mark("block_offsets", s);
+    launch_block_offsets(frames, blocks, nFrames, link && link->reps ? link->reps : dinfo, nUnsized ? 1u : 0u, dstCapacity, status, s, slots, open != nullptr);  d->timer.mark("block_offsets", s);
+    if (open) { launch_batch_rescan(open->in, open->out, open->n, frames, s); d->timer.mark("batch_rescan", s); }
     if (auxGuard.on) { if (hipStreamWaitEvent(s, d->auxDone, 0) != hipSuccess) return ZERR(kErrGeneric); d->timer.mark("decode_literals", s); }     // (what of it seq_decode did not cover)
     else launch_decode_literals(d_src, d_dst, (u8*)d->scratch.p, frames, blocks, nBlocks, status, (u8*)d->slowFlags.p, d->litDecoder, dictFull, dinfo, s, d->timer.hook(), slots);
     launch_place_literals(d_src, d_dst, (const u8*)d->scratch.p, frames, blocks, nBlocks, recs, status, s);    d->timer.mark("place_literals", s);
@@ -545,7 +562,9 @@ static size_t decompress_device(ZSTD_DCtx* d, u8* d_dst, size_t dstCapacity, con
 // ones are filed per block (report_error, kStBlockKeysLo) and folded per entry.  The host synchronises as often as for one single
 // call.  An entry that holds a frame without a content size (where its output goes is known only after decoding: frame_rescan is
 // global by construction) or more than kBatchAloneAbove compressed bytes (one lane walks an entry's block headers) is decoded alone
-// afterwards by decompress_device, and counted.
+// afterwards by decompress_device, and counted.  Under ZSTDMI_DCtx_setBatchUnsized the former take the shared pass too: an entry's
+// first frame starts at its destination whatever its header says, and batch_rescan_kernel places the others per entry from the
+// regenerated sizes block_offsets has computed before a byte of output is written.
 constexpr u64 kBatchAloneAbove = (u64)4 << 20;
 // the batch's core over a device-resident entry table (d->batchIn, n entries; d->batchOut gets what the walk and the decoder make of
 // them): batch_walk_count -> batch_scan -> batch_walk_emit -> decode_lists -> batch_fold.  `readBack` enqueues the caller's copy of
@@ -559,7 +578,8 @@ static size_t decode_entries(ZSTD_DCtx* d, const DecodeDict& dd, const u8* srcBa
     const BatchEntryIn* dIn = (const BatchEntryIn*)d->batchIn.p; BatchEntryOut* dOut = (BatchEntryOut*)d->batchOut.p;
     u32 st[kStWords] = {};
     { const size_t e = status_reset(d); if (isErr(e)) return e; }
-    launch_batch_walk_count(srcBase, dIn, dOut, n, dd.dictID, kBatchAloneAbove, status, s, dd.slots, dd.nSet);
+    d->lastBatchWs = 0;
+    launch_batch_walk_count(srcBase, dIn, dOut, n, dd.dictID, kBatchAloneAbove, status, s, dd.slots, dd.nSet, d->batchUnsized != 0);
     if (!readBack() ||
         hipMemcpyAsync(st, status, sizeof st, hipMemcpyDeviceToHost, s) != hipSuccess) return ZERR(kErrGeneric);
     { const size_t e = stream_wait(s); if (isErr(e)) return e; }
@@ -567,20 +587,35 @@ static size_t decode_entries(ZSTD_DCtx* d, const DecodeDict& dd, const u8* srcBa
     if (dd.slots) d->lastSetFrames += st[kStSetFrames];
     const u32 nFrames = st[kStFrames], nBlocks = st[kStBlocks];
     const u64 total = st_u64(st, kStTotalLo, kStTotalHi);
-    u32 keyWords[2] = {0, 0};
+    // entries with unsized frames in the lists (ZSTDMI_DCtx_setBatchUnsized; none: the pass is the one it always was): `total` holds
+    // their clamped literal rooms, the dump area lies behind the frames' scratch, and the open instances find both through the status words
+    const bool open = st[kStOpenEntries] != 0;
+    const u64 dumpOff = total + (u64)nFrames * kLitSkew + 256, scratchBytes = open ? total + kLitDump : total;
+    const OpenEntries openEntries = { dIn, dOut, n };
+    u32 keyWords[2] = {0, 0}, openWords[4] = {0, 0, 0, 0};      // (sources of asynchronous copies: they live until decode_lists has synchronised)
     if (nFrames) {
-        if (!ensure_lists(d, nFrames, nBlocks, total) || !d->blockKeys.ensure((size_t)nBlocks * sizeof(u64) + 8)) return ZERR(kErrMemoryAllocation);
+        if (!ensure_lists(d, nFrames, nBlocks, scratchBytes) || !d->blockKeys.ensure((size_t)nBlocks * sizeof(u64) + 8)) return ZERR(kErrMemoryAllocation);
+        d->lastBatchWs += (long long)(lists_bytes(nFrames, nBlocks, scratchBytes) + (size_t)nBlocks * sizeof(u64) + 8);
+        if (open) {
+            if (!d->litRooms.ensure((size_t)nFrames * sizeof(u64))) return ZERR(kErrMemoryAllocation);
+            d->lastBatchWs += (long long)((size_t)nFrames * sizeof(u64));
+            const u64 rooms = (u64)(uintptr_t)d->litRooms.p;
+            openWords[0] = (u32)rooms; openWords[1] = (u32)(rooms >> 32); openWords[2] = (u32)dumpOff; openWords[3] = (u32)(dumpOff >> 32);
+            static_assert(kStRoomHi == kStRoomLo + 1 && kStDumpLo == kStRoomLo + 2 && kStDumpHi == kStRoomLo + 3, "one copy fills the four words");
+            if (hipMemcpyAsync(status + kStRoomLo, openWords, sizeof openWords, hipMemcpyHostToDevice, s) != hipSuccess) return ZERR(kErrGeneric);
+        }
         keyWords[0] = (u32)(uintptr_t)d->blockKeys.p; keyWords[1] = (u32)((u64)(uintptr_t)d->blockKeys.p >> 32);
         if (hipMemsetAsync(d->blockKeys.p, 0xFF, (size_t)nBlocks * sizeof(u64), s) != hipSuccess ||
             hipMemcpyAsync(status + kStBlockKeysLo, &keyWords[0], sizeof(u32), hipMemcpyHostToDevice, s) != hipSuccess ||
             hipMemcpyAsync(status + kStBlockKeysHi, &keyWords[1], sizeof(u32), hipMemcpyHostToDevice, s) != hipSuccess) return ZERR(kErrGeneric);
-        launch_batch_walk_emit(srcBase, dIn, dOut, n, (FrameDesc*)d->frames.p, (BlockDesc*)d->blocks.p, s, dd.slots, dd.nSet);
+        launch_batch_walk_emit(srcBase, dIn, dOut, n, (FrameDesc*)d->frames.p, (BlockDesc*)d->blocks.p, s, dd.slots, dd.nSet, open ? (u64*)d->litRooms.p : nullptr);
         d->timer.mark("batch_walk", s);
         const size_t e = decode_lists(d, dd, dstBase, srcBase, nFrames, nBlocks, 0, dstSpan, st, [&]() -> bool {
             launch_batch_fold(dOut, n, (const u64*)d->blockKeys.p, s);
             return readBack();
-        });
+        }, nullptr, open ? &openEntries : nullptr);
         if (isErr(e)) return e;
+        d->lastBatchWs += (long long)((st_u64(st, kStSeqLo, kStSeqHi) + 64) * sizeof(SeqRec));      // (what decode_lists asked d->recs for)
     }
     return 0;
 }
@@ -588,13 +623,13 @@ static size_t decode_entries(ZSTD_DCtx* d, const DecodeDict& dd, const u8* srcBa
 static size_t decompress_batch_impl(ZSTD_DCtx* d, const void* const* srcs, const size_t* srcSizes, size_t n, void* const* dsts, const size_t* dstCapacities, size_t* dstSizes)
 {
     if (!d) return ZERR(kErrGeneric);
-    if (n == 0) { d->lastBatchAlone = 0; return 0; }
+    if (n == 0) { d->lastBatchAlone = 0; d->lastBatchWs = 0; return 0; }
     if (!srcs || !srcSizes || !dsts || !dstCapacities || !dstSizes) return ZERR(kErrGeneric);
     if (n > 0xFFFFFFF0ull) return ZERR(kErrMemoryAllocation);
     size_t e = dctx_bind(d); if (isErr(e)) return e;
     if (d->workers.size() > 1 || d->pfx) return ZERR(kErrParameterUnsupported);      // (a pending ZSTD_DCtx_refPrefix serves one single call)
     e = set_check(d); if (isErr(e)) return e;
-    d->lastBatchAlone = 0;
+    d->lastBatchAlone = 0; d->lastBatchWs = 0;
     e = dctx_sync_dictionary(d); if (isErr(e)) return e;
     hipStream_t s = d->stream;
     DecodeDict dd = decode_dict(d);
@@ -700,7 +735,7 @@ static size_t decompress_range_impl(ZSTD_DCtx* d, void* dst, size_t dstCapacity,
     size_t e = dctx_bind(d); if (isErr(e)) return e;
     if (d->workers.size() > 1 || d->pfx) return ZERR(kErrParameterUnsupported);
     e = set_check(d); if (isErr(e)) return e;
-    d->lastRangeFrames = 0; d->lastRangeStaged = 0;
+    d->lastRangeFrames = 0; d->lastRangeStaged = 0; d->lastBatchWs = 0;
     hipStream_t s = d->stream;
     const bool dstDev = dst ? is_device_ptr(dst) : false;
     SeekTable t;
@@ -797,7 +832,7 @@ static size_t decompress_ranges_impl(ZSTD_DCtx* d, const void* src, size_t srcSi
     size_t e = dctx_bind(d); if (isErr(e)) return e;
     if (d->workers.size() > 1 || d->pfx) return ZERR(kErrParameterUnsupported);      // (a pending ZSTD_DCtx_refPrefix serves one single call)
     e = set_check(d); if (isErr(e)) return e;
-    d->lastRangesFrames = 0; d->lastRangesAlone = 0; d->lastRangesStaged = 0;
+    d->lastRangesFrames = 0; d->lastRangesAlone = 0; d->lastRangesStaged = 0; d->lastBatchWs = 0;
     hipStream_t s = d->stream;
     SeekTable t;
     e = open_seek_table(d, src, srcSize, &t, &d->lastRangesStaged); if (isErr(e)) return e;
@@ -1522,6 +1557,8 @@ size_t ZSTDMI_decompressBatch(ZSTD_DCtx* d, const void* const* srcs, const size_
     return guarded([&] { if (d) d->lastDictTabBlocks = d->lastSetFrames = 0; return decompress_batch_impl(d, srcs, srcSizes, n, dsts, dstCapacities, dstSizes); });
 }
 int ZSTDMI_debugLastBatchAloneD(const ZSTD_DCtx* d) { return d ? d->lastBatchAlone : -1; }
+size_t ZSTDMI_DCtx_setBatchUnsized(ZSTD_DCtx* d, unsigned mode) { if (!d || mode > 1) return ZERR(kErrParameterOutOfBound); d->batchUnsized = (int)mode; return 0; }
+long long ZSTDMI_debugLastBatchWorkspace(const ZSTD_DCtx* d) { return d ? d->lastBatchWs : -1; }
 size_t ZSTDMI_decompressRange(ZSTD_DCtx* d, void* dst, size_t dstCapacity, const void* src, size_t srcSize, unsigned long long offset, size_t length)
 {
     if (!d) return ZERR(kErrGeneric);

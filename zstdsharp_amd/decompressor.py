@@ -22,6 +22,7 @@ class Decompressor(_PrefixHolder):
         if not self.dctx:
             raise MemoryError("ZSTD_createDCtx")
         self._stream_segment = 0
+        self._batch_unsized = False
         self._ddict = None              # the DDict RefDDict holds
         self._ddict_set = {}            # ZSTD_d_refMultipleDDicts: dictID -> every DDict the context's set references (until Dispose)
         if device is not None:
@@ -50,6 +51,17 @@ class Decompressor(_PrefixHolder):
             raise ValueError("stream_segment must not be negative")
         ensure_zstd_success(self._lib, self._lib.ZSTDMI_DCtx_setStreamSegment(self.dctx, int(nbytes)))
         self._stream_segment = int(nbytes)
+
+    # ---- frames without a content size in the shared pass of decompress_batch / unwrap_range(s) (ZSTDMI_DCtx_setBatchUnsized); off by default ----
+    @property
+    def batch_unsized(self) -> bool:
+        return self._batch_unsized
+
+    @batch_unsized.setter
+    def batch_unsized(self, on):
+        self._ensure_not_disposed()
+        ensure_zstd_success(self._lib, self._lib.ZSTDMI_DCtx_setBatchUnsized(self.dctx, 1 if on else 0))
+        self._batch_unsized = bool(on)
 
     def LoadDictionary(self, dict_bytes):                     # S/Decompressor.cs:29-36
         self._ensure_not_disposed()
