@@ -498,6 +498,28 @@ size_t ZSTDMI_CCtx_setSeekTable(ZSTD_CCtx* cctx, unsigned mode);
  * ZSTDMI_debugCompressSamples and contexts with several device workers.  Without a dictionary, with a raw-content dictionary, behind
  * ZSTD_CCtx_refPrefix and in ZSTD_compressCCtx the switch changes nothing.  Every zstd decoder holding the dictionary reads the frames. */
 size_t ZSTDMI_CCtx_setDictEntropy(ZSTD_CCtx* cctx, unsigned mode);
+/* Carry entropy tables and repcodes from block to block inside a frame.  0 = off (the default: a context that never turns the switch
+ * on launches the kernels it launched and writes the bytes it wrote), 1 = on, any other mode: parameter_outOfBound; NULL context:
+ * GENERIC.  Sticky; the call touches no device.  On, the blocks of a multi-block frame are coded in order inside carry groups: 8
+ * consecutive blocks of one frame, aligned to multiples of 8 of the block's index in its frame (under ZSTDMI_CCtx_setSingleFrame: of
+ * its place in the one frame; a stream batch ends a group where the batch ends).  Behind a group's first block a block may write
+ * treeless literals (type 3) with the Huffman table of the latest block of the group that ended as a compressed block with a
+ * Compressed_Literals section — taken when it has a code for every literal that occurs and the section is no larger than the block's
+ * own; repeat mode (3) for each of LL / OF / ML where the block before described or repeated that table, every code of the block has
+ * a probability in it and it costs no more bits than the description plus the block's own table would; and repcodes seeded with what
+ * the block before left (a raw block leaves the decoder's history, its Huffman table and the tables it would have repeated as they
+ * were; the tables it would have described are not repeated behind it).  A group's first block writes neither type 3 nor mode 3, and
+ * starts from unknown repcodes unless it is the frame's first block.
+ * Honoured by ZSTD_compress2, ZSTDMI_compressDevice, ZSTDMI_compressBatch (bytes equal to the single call), ZSTDMI_compressPack,
+ * ZSTD_compressStream2, contexts with several device workers, the seek-table switch, long-distance matching, the long form of
+ * ZSTD_CCtx_refPrefix and ZSTDMI_CCtx_setSingleFrame (the bytes of a one-shot call do not depend on ZSTDMI_CCtx_setPassChunks).
+ * It changes nothing, byte for byte, where every block is a frame of its own (levels 1-2 at their default framing above 32 MiB,
+ * inputs of one block), under ZSTD_c_windowLog 10 .. 15, behind a loaded dictionary or a CDict (ZSTDMI_compressBatchCDicts included),
+ * in ZSTD_compressCCtx, in ZSTDMI_debugCompressSamples and the dictionary trainer.  Every zstd decoder reads the frames.
+ * ZSTDMI_debugLastCarryGroups: carry groups the last call walked (over all its passes and device workers); 0 when the switch took no
+ * effect; -1 without a context. */
+size_t ZSTDMI_CCtx_setEntropyCarry(ZSTD_CCtx* cctx, unsigned mode);
+long long ZSTDMI_debugLastCarryGroups(const ZSTD_CCtx* cctx);
 /* Index a dictionary once, when it is uploaded, and match against ALL of it (the reference digests a dictionary once, ZSTD_createCDict /
  * ZSTD_loadDictionaryContent, and probes its table beside the block's own, ZSTD_compressBlock_fast_dictMatchState).  0 = off (the
  * default: no existing output changes), 1 = on, any other mode: parameter_outOfBound; NULL context: GENERIC.  Sticky; the call touches

@@ -129,6 +129,8 @@ SIGNATURES = {
     "ZSTDMI_debugLastPackFrames": (ctypes.c_longlong, [c_void_p]),
     "ZSTDMI_CCtx_setSeekTable": (c_size_t, [c_void_p, c_uint]),
     "ZSTDMI_CCtx_setDictEntropy": (c_size_t, [c_void_p, c_uint]),
+    "ZSTDMI_CCtx_setEntropyCarry": (c_size_t, [c_void_p, c_uint]),
+    "ZSTDMI_debugLastCarryGroups": (ctypes.c_longlong, [c_void_p]),
     "ZSTDMI_CCtx_setDictIndex": (c_size_t, [c_void_p, c_uint]),
     "ZSTDMI_CCtx_setDictIndexStrategy": (c_size_t, [c_void_p, c_uint]),
     "ZSTDMI_CCtx_setDictIndexChain": (c_size_t, [c_void_p, c_uint]),

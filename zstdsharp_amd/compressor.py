@@ -71,6 +71,7 @@ class Compressor(_PrefixHolder):
         self._level = 0
         self._seek_table = False
         self._dict_entropy = False
+        self._entropy_carry = False
         self._dict_index = False
         self._dict_index_strategy = 1
         self._dict_index_chain = False
@@ -177,6 +178,18 @@ class Compressor(_PrefixHolder):
         self._ensure_not_disposed()
         ensure_zstd_success(self._lib, self._lib.ZSTDMI_CCtx_setDictEntropy(self.cctx, 1 if on else 0))
         self._dict_entropy = bool(on)
+
+    # ---- entropy state carried across blocks (ZSTDMI_CCtx_setEntropyCarry): later blocks of a frame may reuse the Huffman table, the FSE
+    # tables and the repcodes of the blocks before them; off by default ----
+    @property
+    def entropy_carry(self) -> bool:
+        return self._entropy_carry
+
+    @entropy_carry.setter
+    def entropy_carry(self, on):
+        self._ensure_not_disposed()
+        ensure_zstd_success(self._lib, self._lib.ZSTDMI_CCtx_setEntropyCarry(self.cctx, 1 if on else 0))
+        self._entropy_carry = bool(on)
 
     # ---- dictionary index (ZSTDMI_CCtx_setDictIndex): the whole dictionary indexed once at upload, nothing staged per chunk; off by default ----
     @property

@@ -38,13 +38,6 @@ __device__ unsigned long long g_hufStamps[16];
 
 struct Node { u32 count; u16 parent; u8 byte; u8 nbBits; };
 
-// hand-off from huf_hist_kernel to huf_tree_kernel, kept in the chunk's output slot (overwritten later by huf_encode)
-struct HufWork {
-    u16 hist[4][256];           // per-stream histograms
-    u32 sampleMax[2];           // largest count of the first / last 4 KiB (written only when the pre-check applies)
-};
-static_assert(sizeof(HufWork) <= kSlotStride, "hand-off fits the slot");
-
 struct alignas(16) HufTreeLds {
     Node nodes[513];
     u8  nbBits[256];

@@ -11,9 +11,12 @@
 // (U/ZstdCompress.cs:4792) and the single-segment frame header (U/ZstdCompress.cs:4817-4929).
 // The state chains are serial per block by construction (U/Fse.cs:41-49); the GPU gets its parallelism from the
 // 16 384 independent chunks per GiB, which is why this kernel keeps LDS small.
+// With ZSTDMI_CCtx_setEntropyCarry a wave walks a carry group of up to eight blocks of one frame in order instead (seq_encode_carry_kernel,
+// zmi_carry.h), and a block may reuse the Huffman table, the FSE tables and the repcodes the blocks before it left in the decoder.
 #include "zmi_device.h"
 #include "zmi_fse.h"
 #include "zmi_host.h"
+#include "zmi_carry.h"
 
 namespace zmi {
 
@@ -62,13 +65,26 @@ struct SeqTable { const u16* state; const SymTT* tt; u32 tableLog; };
 // below lazy, U/ZstdCompressSequences.cs:400-469); the table and the transforms are then copied from the record into the wave's
 // LDS arrays, nothing is described, and lastCountSize stays what the last COMPRESSED description left.  dPresent (bit s: the
 // dictionary's table gives symbol s a probability) is checked against the block's codes all the same: a `valid` table has them all.
-template <bool DICT>
+// CARRY (ZSTDMI_CCtx_setEntropyCarry, the carry instance below): the table the block before used is still in stateTable / tt.  With
+// prevOk (that block described or itself repeated it, and ended as a compressed block: the decoder holds it) and every code of this
+// block present in it (prevPresent), set_repeat is a candidate, and the cheaper of the two wins at every strategy: what the old table
+// spends on the block's codes (ZSTD_fseBitCost) against the description's bits plus what the table this block would build spends,
+// both priced by the same rule from the transforms (fse_bit_cost); the own side's transforms follow from the normalised counts before
+// any table is built, because a repeated table is simply not rebuilt.  *presentOut: the symbols of a described table.
+template <bool DICT, bool CARRY = false>
 __device__ __forceinline__ u32 build_seq_table(SeqWaveLds& W, u8* op, u32* count, u32 maxPossible, u32 FSELog, u32 nbSeq, u32 lastCode,
                                                const s16* defaultNorm, u32 defaultNormLog, u32 defaultMax, bool defaultAllowedByMax,
                                                u32 strategy, u16* stateTable, SymTT* tt, u32* typeOut, u32* tableLogOut, u32* lastCountSize, u32 lane,
-                                               const u16* __restrict__ dState, const SymTT* __restrict__ dTT, u32 dLog, u64 dPresent)
+                                               const u16* __restrict__ dState, const SymTT* __restrict__ dTT, u32 dLog, u64 dPresent,
+                                               bool prevOk = false, u32 prevLog = 0, u64 prevPresent = 0, u64* presentOut = nullptr)
 {
     u32 type = 0, max = 0, tableLog = 0, n = 0;
+    u32 myCount = 0, repeatBits = ~0u;          // CARRY: lane s holds the count of code s (before lane 0 takes the last code out); ~0: no candidate
+    if (CARRY) {
+        myCount = lane <= maxPossible ? count[lane] : 0u;
+        if (prevOk && ballot(myCount != 0 && !((prevPresent >> lane) & 1)) == 0)
+            repeatBits = wave_sum(myCount ? myCount * fse_bit_cost(tt[lane].deltaNbBits, prevLog) : 0u) >> 8;
+    }
     if (lane == 0) {
         u32 mostFrequent = 0; max = maxPossible;
         while (!count[max]) max--;
@@ -84,6 +100,7 @@ __device__ __forceinline__ u32 build_seq_table(SeqWaveLds& W, u8* op, u32* count
                 else if (nbSeq < dynamicFse_nbSeq_min || mostFrequent < (nbSeq >> (defaultNormLog - 1))) type = 0;
             }
         }
+        if (CARRY && type == 1 && repeatBits <= 8) type = 3;        // (set_rle costs its one byte)
         if (type == 1) {        // set_rle: FSE_buildCTable_rle
             stateTable[0] = 0; stateTable[1] = 0;
             tt[max].deltaNbBits = 0; tt[max].deltaFindState = 0;
@@ -92,8 +109,8 @@ __device__ __forceinline__ u32 build_seq_table(SeqWaveLds& W, u8* op, u32* count
         } else if (type == 0) { // set_basic
             for (u32 s = 0; s <= defaultMax; s++) W.norm[s] = defaultNorm[s];
             max = defaultMax; tableLog = defaultNormLog;
-        } else if (DICT && type == 3) {     // set_repeat
-            tableLog = dLog;
+        } else if ((DICT || CARRY) && type == 3) {     // set_repeat
+            tableLog = CARRY ? prevLog : dLog;
         } else {                // set_compressed
             u32 nbSeq_1 = nbSeq;
             tableLog = fse_optimal_table_log(FSELog, nbSeq, max, 2);
@@ -104,12 +121,19 @@ __device__ __forceinline__ u32 build_seq_table(SeqWaveLds& W, u8* op, u32* count
     }
     type = uniform(type); max = uniform(max); tableLog = uniform(tableLog); n = uniform(n);
     wave_lds_sync();
+    if (CARRY && repeatBits != ~0u && (type == 0 || type == 2)) {
+        const int nc = (myCount && lane <= max) ? (int)W.norm[lane] : 0;
+        const u32 p = nc > 0 ? (u32)nc : 1u;        // (-1: a low-probability symbol holds one state; a code of the block always has a probability)
+        const u32 ownBits = wave_sum(myCount ? myCount * fse_bit_cost(fse_delta_nb_bits(p, tableLog), tableLog) : 0u) >> 8;
+        if (repeatBits <= 8 * n + ownBits) { type = 3; n = 0; tableLog = prevLog; }
+    }
+    if (CARRY && type == 2) *presentOut = ballot(lane <= max && W.norm[lane] != 0);
     if (DICT && type == 3) {
         for (u32 i = lane; i < (1u << tableLog); i += 64) stateTable[i] = dState[i];
         if (lane <= maxPossible) tt[lane] = dTT[lane];
         wave_lds_sync();
     }
-    else if (type != 1) fse_build_ctable_wave(stateTable, tt, W.norm, max, tableLog, W.cumul, W.tableSymbol, lane);
+    else if (type != 1 && !(CARRY && type == 3)) fse_build_ctable_wave(stateTable, tt, W.norm, max, tableLog, W.cumul, W.tableSymbol, lane);
     *typeOut = type; *tableLogOut = tableLog;
     if (type == 2) *lastCountSize = n;
     return n;
@@ -123,24 +147,48 @@ __device__ __forceinline__ u32 build_seq_table(SeqWaveLds& W, u8* op, u32* count
 // SET (ZSTDMI_compressBatchCDicts, zmi_cdictset.h; on the DICT instance): a pass behind two or more dictionaries.  The header's dictID,
 // the repcodes in front of a frame and dct come per chunk from dictSlots[chunkSlot[c]] (a wave's chunk: scalar loads); a slot without
 // tables (raw content, no dictionary, the switch off) leaves its chunks what the instance without DICT makes of them.
-// The body stands behind two kernels, below: seq_encode_kernel<DICT, SF> with the arguments it always had, and seq_encode_set_kernel.
-template <bool DICT, bool SF, bool SET>
+// The body stands behind three kernels, below: seq_encode_kernel<DICT, SF> with the arguments it always had, seq_encode_set_kernel and
+// seq_encode_carry_kernel<SF>.
+// CARRY (ZSTDMI_CCtx_setEntropyCarry, zmi_carry.h; never behind a dictionary): a wave owns a carry group, not a chunk, and the kernel
+// calls the body once per block of the group, in order: chunk cCarry (liveCarry: the wave's group has such a block; all four waves of a
+// workgroup make the same number of calls and meet the same barriers).  `cs` is what the decoder holds after the group's blocks so
+// far; a block that leads its group (`leads`) resets it and writes nothing that relies on an earlier block.  Per block, in this order:
+//   1. treeless literals (litCarry: literals are compressed at all): the Huffman table of the latest block of the group that ended as a
+//      compressed block with a Compressed_Literals section (cs->hufSrc; raw blocks and raw / RLE literals in between leave the decoder's
+//      table alone) is taken when it has a code for every literal that occurs and the section it makes is no larger than the one
+//      huf_tree_kernel decided on; the cost is exact, from the per-stream histograms huf_hist_kernel left in the slot — which is why
+//      this comes before anything of the block is written there.  The block's record and its tables[] entry are set as
+//      huf_tree_kernel<true> sets them behind a dictionary, and huf_encode_kernel<true> writes literals type 3;
+//   2. the repcode recurrence is seeded with what the block before left (a raw block leaves the decoder's history as it was);
+//   3. each of the three tables may repeat the one in the wave's LDS arrays (build_seq_table<false, true>);
+//   4. after the raw / compressed decision: a compressed block's repcodes, described tables and Huffman table become the state; a raw
+//      block leaves repcodes, Huffman table and the tables it repeated, and the tables it rebuilt in LDS are no longer repeatable.
+struct CarryWave {
+    u32 rep[3];         // the repcodes (0: unknown — it equals no offset)
+    u32 hufSrc;         // the chunk whose tables[] entry holds the Huffman table in force; kNoBlock: none
+    u32 fseOk;          // bit t (LL, OF, ML): the wave's LDS arrays hold table t as the decoder does, and a block may repeat it
+    u32 fseLog[3]; u64 fsePresent[3];       // then: its tableLog; bit s: symbol s has a probability in it
+};
+template <bool DICT, bool SF, bool SET, bool CARRY = false>
 __device__ __forceinline__ void seq_encode_body(Seq* __restrict__ seqs, ChunkMeta* __restrict__ meta,
                                                 u8* __restrict__ slots, u32 nChunks, u32 strategy, const FrameHeaderSpec& fhArg, u32 resolveReps,
                                                 u32 initRep0, u32 initRep1, u32 initRep2, const FrameLayout& frames,
-                                                const DictCTables* __restrict__ dctArg, const CDictSlot* __restrict__ dictSlots, const u32* __restrict__ chunkSlot)
+                                                const DictCTables* __restrict__ dctArg, const CDictSlot* __restrict__ dictSlots, const u32* __restrict__ chunkSlot,
+                                                CarryWave* cs = nullptr, HufTable* __restrict__ tables = nullptr, u32 cCarry = 0, bool liveCarry = false,
+                                                bool leads = true, bool litCarry = false)
 {
     static_assert(!SET || (DICT && !SF), "the set form stands on the DICT instance");
+    static_assert(!CARRY || (!DICT && !SET), "behind a dictionary a frame has one block: nothing to carry");
     __shared__ SeqWaveLds Ws[4];
     __shared__ u32 sBatchSeq[4];          // sequences each of the four chunks sends through the state chains (0: none)
     __shared__ u32 sFinalState[4][3];
     const u32 lane = lane_id(), wave = uniform(wave_id());
-    const u32 c = blockIdx.x * 4 + wave;
-    const bool live = c < nChunks;        // (a wave without a chunk still meets the workgroup's barriers below)
+    const u32 c = CARRY ? cCarry : blockIdx.x * 4 + wave;
+    const bool live = CARRY ? liveCarry : c < nChunks;        // (a wave without a chunk still meets the workgroup's barriers below)
     SeqWaveLds& W = Ws[wave];
     ChunkMeta m = {};
-    if (live) m = meta_checked<false>(meta[c]);
-    const u32 nbSeq = m.nbSeq, n = m.srcSize;
+    if (live) { if (CARRY) m = meta_checked<true>(meta[c]); else m = meta_checked<false>(meta[c]); }
+    const u32 nbSeq = CARRY ? uniform(m.nbSeq) : m.nbSeq, n = CARRY ? uniform(m.srcSize) : m.srcSize;
     FrameHeaderSpec fh = fhArg; const DictCTables* __restrict__ dct = dctArg;
     if (SET) {
         const CDictSlot* __restrict__ const ds = dictSlots + (live ? chunkSlot[c] : 0u);
@@ -159,14 +207,56 @@ __device__ __forceinline__ void seq_encode_body(Seq* __restrict__ seqs, ChunkMet
     const u32 bf = at.block;                                  // (SF: first block or not)
     const u64 frameLen = at.frameLen; const bool lastBlock = at.last;
     if (bf) { initRep0 = 0; initRep1 = 0; initRep2 = 0; }
+    if (CARRY) {
+        if (leads) { cs->rep[0] = initRep0; cs->rep[1] = initRep1; cs->rep[2] = initRep2; cs->hufSrc = kNoBlock; cs->fseOk = 0; }
+        else { initRep0 = cs->rep[0]; initRep1 = cs->rep[1]; initRep2 = cs->rep[2]; }
+    }
     Seq* __restrict__ sq = seqs + (u64)c * kMaxSeq;
     u8* const slot = slots + (u64)c * kSlotStride;
     u8* const body = slot + m.fhSize + 3;
+    if (CARRY && live && litCarry && cs->hufSrc != kNoBlock && m.litSize > 63 && m.litMode != kLitTreeless) {
+        // (ZSTD_compressLiterals: 63 literals or fewer stay raw; the sizes below are those huf_tree_kernel computes for a table it reuses)
+        const HufWork* __restrict__ const hw = reinterpret_cast<const HufWork*>(slot);
+        const HufTable* __restrict__ const old = tables + cs->hufSrc;
+        const u32 litSize = m.litSize;
+        u32 bits[4] = { 0, 0, 0, 0 }; bool covered = true;
+#pragma unroll
+        for (u32 k = 0; k < 4; ++k) {
+            const u32 s = k * 64 + lane, nb = old->nbBits[s]; u32 any = 0;
+#pragma unroll
+            for (u32 w = 0; w < 4; ++w) { const u32 h = hw->hist[w][s]; bits[w] += h * nb; any |= h; }
+            covered &= ballot(any != 0 && nb == 0) == 0;
+        }
+        if (covered) {
+#pragma unroll
+            for (u32 w = 0; w < 4; ++w) bits[w] = wave_sum(bits[w]);
+            const bool own = m.litMode == kLitCompressed;       // (litSingle / lhSize stay what the block's own decision made them)
+            const u32 single = own ? (m.litSingle ? 1u : 0u) : (litSize < 256 ? 1u : 0u);
+            const u32 lhSize = own ? m.lhSize : 3 + (litSize >= 1024) + (litSize >= 16384);
+            u32 ss[4] = { 0, 0, 0, 0 }, cLit = 0; bool ok = true;
+            if (single) { ss[0] = ((bits[0] + bits[1] + bits[2] + bits[3]) >> 3) + 1; cLit = ss[0]; }
+            else {
+                cLit = 6; ok = litSize >= 12;
+#pragma unroll
+                for (u32 w = 0; w < 4; ++w) { ss[w] = (bits[w] >> 3) + 1; ok = ok && ss[w] <= 65535; cLit += ss[w]; }
+            }
+            // HUF_compressCTable_internal's and ZSTD_compressLiterals' "did it shrink" (ZSTD_minGain), then the exact comparison
+            ok = ok && cLit + 1 < litSize && cLit + (litSize >> 6) + 2 < litSize && lhSize + cLit <= m.litSectionSize;
+            if (ok) {
+                m.litMode = kLitTreeless; m.litSingle = single; m.lhSize = lhSize; m.hufHdrSize = 0; m.litSectionSize = lhSize + cLit;
+                m.streamSize[0] = ss[0]; m.streamSize[1] = ss[1]; m.streamSize[2] = ss[2]; m.streamSize[3] = ss[3];
+                HufTable* __restrict__ const T = tables + c;      // huf_encode_kernel reads the chunk's table as ever
+#pragma unroll
+                for (u32 k = 0; k < 4; ++k) { const u32 s = k * 64 + lane; T->nbBits[s] = old->nbBits[s]; T->code[s] = old->code[s]; }
+            }
+        }
+    }
 
 #ifdef ZMI_LZ_STAMPS
     unsigned long long stampAcc[8] = {0,0,0,0,0,0,0,0}; unsigned long long stampLast = __builtin_amdgcn_s_memtime();
 #endif
     for (u32 i = lane; i < 3 * 64; i += 64) (&W.count[0][0])[i] = 0;
+    u32 endRep0 = initRep0, endRep1 = initRep1, endRep2 = initRep2;       // CARRY: the history behind the block's last sequence
     if (resolveReps) {
         // The match finder stores raw offsets (distance + 3).  Turning them into repcodes is a serial state machine over
         // the sequences — the decoder's history rule (U/ZstdDecompressBlock.cs:2387-2443) run forward — so it lives
@@ -209,6 +299,7 @@ __device__ __forceinline__ void seq_encode_body(Seq* __restrict__ seqs, ChunkMet
             }
             if (i < nbSeq) sq[i].offBase = myCode;
         }
+        if (CARRY) { endRep0 = R0; endRep1 = R1; endRep2 = R2; }
     }
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
     __builtin_amdgcn_wave_barrier();
@@ -227,6 +318,7 @@ __device__ __forceinline__ void seq_encode_body(Seq* __restrict__ seqs, ChunkMet
     u8* op = body + m.litSectionSize;
     bool giveUp = n < 7;                 // ZSTD_buildSeqStore: blocks under MIN_CBLOCK_SIZE+header are never compressed
     u32 bodyTablesEnd = 0, typesOk = 0, tLLlog = 0, tOFlog = 0, tMLlog = 0, tLastCount = 0;
+    u32 carryTypes = 0; u64 carryPresent[3] = { 0, 0, 0 };      // CARRY: the three modes (LL | OF << 2 | ML << 4), the symbols of the tables described
     if (!giveUp) {
         const u32 hdr = nbSeq < 128 ? 1u : (nbSeq < 0x7F00 ? 2u : 3u);
         if (lane == 0) {
@@ -254,12 +346,22 @@ __device__ __forceinline__ void seq_encode_body(Seq* __restrict__ seqs, ChunkMet
             if (dLogOF > 8) dLogOF = 8;
             if (dLogML > 9) dLogML = 9;
         }
-        op += build_seq_table<DICT>(W, op, W.count[0], 35, 9, nbSeq, lastLL, cLL_defaultNorm, 6, 35, false, strategy, W.llState, W.llTT, &LLtype, &llLog, &lastCountSize, lane,
-                                    dLL, (DICT && (!SET || dct)) ? dct->llTT : nullptr, dLogLL, dHasLL);
-        op += build_seq_table<DICT>(W, op, W.count[1], 31, 8, nbSeq, lastOF, cOF_defaultNorm, 5, 28, true,  strategy, W.ofState, W.ofTT, &OFtype, &ofLog, &lastCountSize, lane,
-                                    dOF, (DICT && (!SET || dct)) ? dct->ofTT : nullptr, dLogOF, dHasOF);
-        op += build_seq_table<DICT>(W, op, W.count[2], 52, 9, nbSeq, lastML, cML_defaultNorm, 6, 52, false, strategy, W.mlState, W.mlTT, &MLtype, &mlLog, &lastCountSize, lane,
-                                    dML, (DICT && (!SET || dct)) ? dct->mlTT : nullptr, dLogML, dHasML);
+        if (CARRY) {        // each table against the one the block before left in the wave's arrays
+            op += build_seq_table<false, true>(W, op, W.count[0], 35, 9, nbSeq, lastLL, cLL_defaultNorm, 6, 35, false, strategy, W.llState, W.llTT, &LLtype, &llLog, &lastCountSize, lane,
+                                               nullptr, nullptr, 0, 0, (cs->fseOk & 1u) != 0, cs->fseLog[0], cs->fsePresent[0], &carryPresent[0]);
+            op += build_seq_table<false, true>(W, op, W.count[1], 31, 8, nbSeq, lastOF, cOF_defaultNorm, 5, 28, true,  strategy, W.ofState, W.ofTT, &OFtype, &ofLog, &lastCountSize, lane,
+                                               nullptr, nullptr, 0, 0, (cs->fseOk & 2u) != 0, cs->fseLog[1], cs->fsePresent[1], &carryPresent[1]);
+            op += build_seq_table<false, true>(W, op, W.count[2], 52, 9, nbSeq, lastML, cML_defaultNorm, 6, 52, false, strategy, W.mlState, W.mlTT, &MLtype, &mlLog, &lastCountSize, lane,
+                                               nullptr, nullptr, 0, 0, (cs->fseOk & 4u) != 0, cs->fseLog[2], cs->fsePresent[2], &carryPresent[2]);
+            carryTypes = LLtype | (OFtype << 2) | (MLtype << 4);
+        } else {
+            op += build_seq_table<DICT>(W, op, W.count[0], 35, 9, nbSeq, lastLL, cLL_defaultNorm, 6, 35, false, strategy, W.llState, W.llTT, &LLtype, &llLog, &lastCountSize, lane,
+                                        dLL, (DICT && (!SET || dct)) ? dct->llTT : nullptr, dLogLL, dHasLL);
+            op += build_seq_table<DICT>(W, op, W.count[1], 31, 8, nbSeq, lastOF, cOF_defaultNorm, 5, 28, true,  strategy, W.ofState, W.ofTT, &OFtype, &ofLog, &lastCountSize, lane,
+                                        dOF, (DICT && (!SET || dct)) ? dct->ofTT : nullptr, dLogOF, dHasOF);
+            op += build_seq_table<DICT>(W, op, W.count[2], 52, 9, nbSeq, lastML, cML_defaultNorm, 6, 52, false, strategy, W.mlState, W.mlTT, &MLtype, &mlLog, &lastCountSize, lane,
+                                        dML, (DICT && (!SET || dct)) ? dct->mlTT : nullptr, dLogML, dHasML);
+        }
         // lastCountSize must be the size of the LAST compressed table description (U/ZstdCompress.cs:3196-3224)
         if (lane == 0) *seqHead = (u8)((LLtype << 6) + (OFtype << 4) + (MLtype << 2));
 
@@ -408,7 +510,7 @@ __device__ __forceinline__ void seq_encode_body(Seq* __restrict__ seqs, ChunkMet
 #ifdef ZMI_LZ_STAMPS
     if (lane == 0) for (int i = 0; i < 8; i++) atomicAdd(&g_sencStamps[i], stampAcc[i]);
 #endif
-    if (lane != 0 || !live) return;
+    if (!CARRY && (lane != 0 || !live)) return;          // (CARRY: every lane takes the decision, which the wave's state follows)
     if (typesOk) {
         op = body + bodyTablesEnd + bitstreamSize;
         const u32 lastCountSize = tLastCount;
@@ -416,6 +518,26 @@ __device__ __forceinline__ void seq_encode_body(Seq* __restrict__ seqs, ChunkMet
     }
     u32 cSize = (u32)(op - body);
     if (!giveUp && cSize >= n - ((n >> 6) + 2)) giveUp = true;                      // ZSTD_minGain
+    if (CARRY) {
+        // what the decoder holds behind this block.  A raw block leaves it everything but the tables this wave rebuilt in LDS, which
+        // are no longer what the decoder would repeat; a block without sequences (typesOk 0) touches no table.
+        const bool raw = uniform(giveUp ? 1u : 0u) != 0;
+        if (typesOk) {
+            const u32 logs[3] = { tLLlog, tOFlog, tMLlog };
+#pragma unroll
+            for (u32 t = 0; t < 3; ++t) {
+                const u32 type = (carryTypes >> (2 * t)) & 3u;
+                if (type == 3) continue;
+                if (type == 2 && !raw) { cs->fseOk |= 1u << t; cs->fseLog[t] = logs[t]; cs->fsePresent[t] = carryPresent[t]; }
+                else cs->fseOk &= ~(1u << t);
+            }
+        }
+        if (!raw) {
+            cs->rep[0] = endRep0; cs->rep[1] = endRep1; cs->rep[2] = endRep2;
+            if (uniform(m.litMode) == kLitCompressed) cs->hufSrc = c;
+        }
+        if (lane != 0 || !live) return;
+    }
 
     // ---- frame header in front of the frame's first block: the bytes whose count the finder left in fhSize (zmi_frame.h) ----
     if (bf == 0) frame_header_write(fh, frameLen, slot);
@@ -446,12 +568,43 @@ __global__ __launch_bounds__(256) void seq_encode_set_kernel(Seq* __restrict__ s
     seq_encode_body<true, false, true>(seqs, meta, slots, nChunks, strategy, fh, resolveReps, 0, 0, 0, frames, nullptr, dictSlots, chunkSlot);
 }
 
+// The carry instance: wave w of workgroup b walks carry group 4 b + w block by block (zmi_carry.h says which chunks those are: plain
+// arithmetic, or, for a batch's table form, the host's leader list).  All four waves take as many steps as the longest of their four
+// groups; a wave whose group is shorter, or that has none, meets the barriers as a wave without a chunk does in the other instances.
+template <bool SF>
+__global__ __launch_bounds__(256) void seq_encode_carry_kernel(Seq* __restrict__ seqs, ChunkMeta* __restrict__ meta,
+                                                               u8* __restrict__ slots, u32 nChunks, u32 strategy, const FrameHeaderSpec fh,
+                                                               u32 initRep0, u32 initRep1, u32 initRep2, const FrameLayout frames, const SeqCarry carry)
+{
+    const u32 wave = uniform(wave_id());
+    CarrySpan mine = { 0u, 0u }; u32 steps = 0;
+    for (u32 w = 0; w < 4; ++w) {
+        const u32 g = blockIdx.x * 4 + w;
+        const CarrySpan sp = SF ? carry_span<kSingle>(frames, nChunks, nullptr, 0, g)
+                                : frames.form == kTable ? carry_span<kTable>(frames, nChunks, carry.leaders, carry.nGroups, g) : carry_span<kArith>(frames, nChunks, nullptr, 0, g);
+        if (w == wave) mine = sp;
+        steps = sp.count > steps ? sp.count : steps;
+    }
+    if (steps > kCarryGroup) steps = kCarryGroup;       // (a leader list never says more; nothing downstream relies on that)
+    CarryWave cs = {};
+    for (u32 step = 0; step < steps; ++step)
+        seq_encode_body<false, SF, false, true>(seqs, meta, slots, nChunks, strategy, fh, 1, initRep0, initRep1, initRep2, frames, nullptr, nullptr, nullptr,
+                                                &cs, carry.tables, mine.first + step, step < mine.count && mine.first + step < nChunks, step == 0, carry.rawLiterals == 0);
+}
+
 void launch_seq_encode(Seq* seqs, ChunkMeta* meta, u8* slots, u32 nChunks, u32 strategy, const FrameHeaderSpec& header, u32 resolveReps,
                        const u32* initReps, const FrameLayout& frames, hipStream_t stream, const DictCTables* dct,
-                       const CDictSlot* dictSlots, const u32* chunkSlot)
+                       const CDictSlot* dictSlots, const u32* chunkSlot, const SeqCarry* carry)
 {
     assert((!dct && !dictSlots) || frames.form != kSingle);
     assert(!dictSlots == !chunkSlot && (!dictSlots || !frames.frameBlocks));
+    if (carry) {
+        assert(!dct && !dictSlots && frames.frameBlocks && resolveReps && carry->nGroups);
+        const auto kernel = frames.form == kSingle ? seq_encode_carry_kernel<true> : seq_encode_carry_kernel<false>;
+        hipLaunchKernelGGL(kernel, dim3((carry->nGroups + 3) / 4), dim3(256), 0, stream, seqs, meta, slots, nChunks, strategy, header,
+                           initReps[0], initReps[1], initReps[2], frames, *carry);
+        return;
+    }
     if (dictSlots) {
         hipLaunchKernelGGL(seq_encode_set_kernel, dim3((nChunks + 3) / 4), dim3(256), 0, stream, seqs, meta, slots, nChunks, strategy, header, resolveReps, frames, dictSlots, chunkSlot);
         return;

@@ -73,4 +73,12 @@ __device__ __forceinline__ ChunkMeta meta_checked(ChunkMeta m)
     return m;
 }
 
+// hand-off from huf_hist_kernel to huf_tree_kernel, kept in the chunk's output slot (overwritten later by seq_encode and huf_encode;
+// seq_encode's carry instance reads the histograms once more before it writes anything of the block there)
+struct HufWork {
+    u16 hist[4][256];           // per-stream histograms
+    u32 sampleMax[2];           // largest count of the first / last 4 KiB (written only when the pre-check applies)
+};
+static_assert(sizeof(HufWork) <= kSlotStride, "hand-off fits the slot");
+
 } // namespace zmi

@@ -205,6 +205,24 @@ __device__ __forceinline__ void fse_build_ctable_wave(u16* stateTable, SymTT* tt
     wave_lds_sync();
 }
 
+// What a table spends on one occurrence of a symbol, in 1/256 bit, from the symbol's transform alone (FSE_bitCost with accuracyLog 8):
+// the symbol's states take minNbBits or one bit more, and the share of each follows from where deltaNbBits lies below the threshold.
+// A symbol without a probability comes out at tableLog + 1 bits (fse_build_ctable_wave files that transform for it).
+__device__ __forceinline__ u32 fse_bit_cost(u32 deltaNbBits, u32 tableLog)
+{
+    const u32 minNbBits = deltaNbBits >> 16, threshold = (minNbBits + 1) << 16, tableSize = 1u << tableLog;
+    const u32 deltaFromThreshold = threshold - (deltaNbBits + tableSize);
+    const u32 normalizedDelta = (deltaFromThreshold << 8) >> tableLog;
+    return ((minNbBits + 1) << 8) - normalizedDelta;
+}
+// the deltaNbBits fse_build_ctable_wave files for a symbol of normalised count p >= 1 (-1 counts as 1) in a table of tableLog
+__device__ __forceinline__ u32 fse_delta_nb_bits(u32 p, u32 tableLog)
+{
+    if (p <= 1) return (tableLog << 16) - (1u << tableLog);
+    const u32 maxBitsOut = tableLog - highbit32(p - 1);
+    return (maxBitsOut << 16) - (p << maxBitsOut);
+}
+
 __device__ __forceinline__ u32 fse_init_state2(const u16* stateTable, const SymTT* tt, u32 symbol)
 {
     const SymTT t = tt[symbol];

@@ -62,9 +62,15 @@ void launch_huf_build(const u8* lits, ChunkMeta* meta, HufTable* tables, u8* slo
                       hipStream_t stream, StageHook hook, const DictCTables* dct = nullptr, const CDictSlot* dictSlots = nullptr, const u32* chunkSlot = nullptr);
 void launch_huf_encode(const u8* lits, const ChunkMeta* meta, const HufTable* tables, u8* slots, u8* dst, const u64* offsets, u64 dstCapacity,
                        u32 nChunks, const u8* src, u32 chunkBytes, hipStream_t stream, bool dictEntropy = false);
+// carry (null: off; ZSTDMI_CCtx_setEntropyCarry, zmi_carry.h; multi-block frames without dictionary tables only): seq_encode's carry
+// instance walks the pass's nGroups carry groups block by block.  tables: the pass's Huffman tables (a block that reuses an earlier
+// block's gets a copy in its own entry, and huf_encode must then be launched with dictEntropy = true, the instance that writes
+// literals type 3); leaders: for frames.form == kTable, nGroups + 1 chunk indices (carry_leaders_table), else null; rawLiterals: the
+// call compresses no literals
+struct SeqCarry { HufTable* tables; const u32* leaders; u32 nGroups, rawLiterals; };
 void launch_seq_encode(Seq* seqs, ChunkMeta* meta, u8* slots, u32 nChunks, u32 strategy, const FrameHeaderSpec& header, u32 resolveReps,
                        const u32* initReps, const FrameLayout& frames, hipStream_t stream, const DictCTables* dct = nullptr,
-                       const CDictSlot* dictSlots = nullptr, const u32* chunkSlot = nullptr);
+                       const CDictSlot* dictSlots = nullptr, const u32* chunkSlot = nullptr, const SeqCarry* carry = nullptr);
 void launch_scan_sizes(const ChunkMeta* meta, u32 nChunks, u64* offsets, u64* total, hipStream_t stream);
 void launch_gather(const u8* src, u64 srcSize, const u8* slots, const ChunkMeta* meta, const u64* offsets, u8* dst, u64 dstCapacity,
                    u32 nChunks, u32 chunkBytes, hipStream_t stream);

@@ -6,6 +6,7 @@
 // ZSTD_error_init_missing, loudly.
 #include "zmi_cparams.h"
 #include "zmi_host.h"
+#include "zmi_carry.h"
 #include <unordered_map>
 
 // ======================================================================================================
@@ -58,6 +59,10 @@ struct ZSTD_CCtx_s {
     // shared, else `own` filled from the CDict's host bytes (cctx_adopt_cdict).  dictUploads: uploads of `own` (ZSTDMI_debugDictUploads)
     DictDigest own; const ZSTD_CDict_s* cdict = nullptr; bool dictDirty = false; long long dictUploads = 0;
     int dictEntropy = 0;        // ZSTDMI_CCtx_setDictEntropy (sticky)
+    // ZSTDMI_CCtx_setEntropyCarry (sticky): the blocks of a multi-block frame are coded in order inside carry groups (zmi_carry.h) and
+    // may reuse the Huffman table, the FSE tables and the repcodes of the blocks before them (carry_active says where).
+    // lastCarryGroups: groups the carry instance walked in the last call (ZSTDMI_debugLastCarryGroups)
+    int entropyCarry = 0; long long lastCarryGroups = 0;
     // ZSTDMI_CCtx_setDictIndex (sticky): the dictionary's content — its last dict_index_max() bytes — stays whole on the device with a
     // hash index over it, built once per upload (lz_fast.hip), and the fast strategy's chunks look candidates up there instead of
     // staging a tail of it.  dictWide = those bytes of a raw-content dictionary (kept at every load, so the switch may come later; a
@@ -148,6 +153,7 @@ struct CallParams {
     int dictIndexStrategy = 1;          // ... at strategies up to this one (ZSTDMI_CCtx_setDictIndexStrategy)
     bool dictIndexChain = false;        // ... and where the call resolves to the chain finder (ZSTDMI_CCtx_setDictIndexChain)
     bool dictEntropy = false;           // code with a formatted dictionary's entropy tables (ZSTDMI_CCtx_setDictEntropy; ZSTD_compressCCtx uses no dictionary)
+    bool entropyCarry = false;          // carry entropy tables and repcodes from block to block (ZSTDMI_CCtx_setEntropyCarry; ZSTD_compressCCtx: never, level-only parameters)
     const u8* pfx = nullptr; size_t pfxSize = 0;    // the long form of a referenced prefix (compress_prefixed): device bytes in front of the ONE frame
     bool single = false;                // one frame per call (ZSTDMI_CCtx_setSingleFrame; ZSTD_compressCCtx: never, level-only parameters)
     bool sliding = false;               // ... whose long-distance window slides with it (ZSTDMI_CCtx_setSlidingLdm; takes effect where sliding_active says)
@@ -161,6 +167,7 @@ static CallParams sticky_params(const ZSTD_CCtx* c)
     p.strategy = c->strategy; p.targetLength = c->targetLength; p.windowLog = c->windowLog; p.searchLog = c->searchLog; p.minMatch = c->minMatch; p.chainLog = c->chainLog; p.useDict = true;
     p.seek = c->seekTable != 0;
     p.dictEntropy = c->dictEntropy != 0;
+    p.entropyCarry = c->entropyCarry != 0;
     p.dictIndex = c->dictIndex != 0; p.dictIndexStrategy = c->dictIndexStrategy; p.dictIndexChain = c->dictIndexChain != 0;
     p.single = c->singleFrame != 0; p.sliding = c->slidingLdm != 0;
     p.ldm = c->ldm; p.ldmHashLog = c->ldmHashLog; p.ldmMinMatch = c->ldmMinMatch; p.ldmBucketSizeLog = c->ldmBucketSizeLog; p.ldmHashRateLog = c->ldmHashRateLog;
@@ -514,6 +521,15 @@ static LzLaunch pass_lz(ZSTD_CCtx* c, const LaunchState& L, const Framing& fr, c
     a.stream = c->stream; a.hook = c->timer.hook();
     return a;
 }
+// ZSTDMI_CCtx_setEntropyCarry takes effect in a pass whose chunks share frames and see no dictionary: not where every chunk is a frame
+// of its own, not where the blocks of a frame are independent windows (ZSTD_c_windowLog 10 .. 15), not behind a loaded dictionary or
+// a CDict of any kind (such calls write what they wrote, byte for byte)
+static bool carry_active(const ZSTD_CCtx* c, const CallParams& cp, const Framing& fr, const LaunchState& ls)
+{
+    if (!cp.entropyCarry || !fr.frameBlocks || ls.independent || ls.dct || fr.prefixLen || fr.dictIndex) return false;
+    const DictDigest& g = dict_in_force(c);
+    return !(cp.useDict && (g.dictFormatted || !g.dictHost.empty()));
+}
 // a pass is over: its stage times into the call's, which are sums over its passes (inputs above 1 GiB take several)
 static void add_stage_times(ZSTD_CCtx* c, bool& first)
 {
@@ -561,6 +577,10 @@ static size_t compress_range(ZSTD_CCtx* c, const CallParams& cp, u8* d_dst, size
     u32 passChunks = (u32)(totalChunks < c->passChunks ? totalChunks : c->passChunks);
     if (fr.ldm) { const u32 fit = (u32)(((u64)1 << 31) / chunkBytes), most = fr.slideLog ? fit : whole_frame_chunks(fit, frameBlocks); if (passChunks > most) passChunks = most; }    // (ldm.hip: u32 offsets in a pass; a sliding window adds at most 2^28 in front)
     if (frameBlocks && !fr.single && passChunks < totalChunks) { passChunks = whole_frame_chunks(passChunks, frameBlocks); if (!passChunks) passChunks = frameBlocks; }     // frames never straddle passes
+    // carried entropy state: a one-shot call's passes of the one frame are whole carry groups, so that the bytes do not depend on
+    // ZSTDMI_CCtx_setPassChunks (a stream's batch ends a group where it ends)
+    const bool carry = carry_active(c, cp, fr, ls);
+    if (carry && fr.single && passChunks < totalChunks) passChunks = carry_pass_chunks(passChunks);
     if (!cctx_workspace(c, passChunks)) return ZERR(kErrMemoryAllocation);
     if (ls.regionParse && !cctx_cand_workspace(c, passChunks, ls.hcChains)) return ZERR(kErrMemoryAllocation);
     if (ls.regionParse && fr.dictIndex && !cctx_dist_workspace(c, passChunks)) return ZERR(kErrMemoryAllocation);
@@ -607,7 +627,9 @@ static size_t compress_range(ZSTD_CCtx* c, const CallParams& cp, u8* d_dst, size
             if (ends) launch_xxh_carry_file((const XxhCarry*)c->sfXxh.p, meta + (nChunks - 1), s);
             c->timer.mark("xxh64", s);
         } else if (cp.checksumFlag) { launch_xxh64(src, meta, nChunks, frames, s);             c->timer.mark("xxh64", s); }
-        launch_seq_encode(seqs, meta, slots, nChunks, ls.strategy, ls.header, 1, ls.initReps, frames, s, dct);   c->timer.mark("seq_encode", s);
+        SeqCarry sc = { tables, nullptr, 0, rs.rawLiterals };
+        if (carry) { sc.nGroups = fr.single ? carry_groups_single(nChunks, frames.at, chunkBytes) : carry_groups_arith(nChunks, frameBlocks); c->lastCarryGroups += sc.nGroups; }
+        launch_seq_encode(seqs, meta, slots, nChunks, ls.strategy, ls.header, 1, ls.initReps, frames, s, dct, nullptr, nullptr, carry ? &sc : nullptr);   c->timer.mark("seq_encode", s);
         launch_scan_sizes(meta, nChunks, offsets, total, s);                       c->timer.mark("scan", s);
         if (c->seekOn) {        // the pass's frames into the call's seek table
             const u32 nFrames = (nChunks + (frameBlocks ? frameBlocks : 1u) - 1) / (frameBlocks ? frameBlocks : 1u);
@@ -617,7 +639,7 @@ static size_t compress_range(ZSTD_CCtx* c, const CallParams& cp, u8* d_dst, size
         }
         const size_t room = dstCapacity > produced ? dstCapacity - produced : 0;
         // the literals section (most of the output) is encoded straight into its final place; gather moves the rest
-        launch_huf_encode(lits, meta, tables, slots, d_dst + produced, offsets, room, nChunks, src, chunkBytes, s, dct != nullptr);   c->timer.mark("huf_encode", s);
+        launch_huf_encode(lits, meta, tables, slots, d_dst + produced, offsets, room, nChunks, src, chunkBytes, s, dct != nullptr || carry);   c->timer.mark("huf_encode", s);
         launch_gather(src, n, slots, meta, offsets, d_dst + produced, room, nChunks, chunkBytes, s);      c->timer.mark("gather", s);
         u64 passTotal = 0;
         if (hipMemcpyAsync(&passTotal, total, sizeof(u64), hipMemcpyDeviceToHost, s) != hipSuccess) return ZERR(kErrGeneric);
@@ -1019,7 +1041,7 @@ size_t ZSTD_compressBound(size_t n) { return n + (n >> 8) + (n < (128u << 10) ? 
 static size_t ZSTDMI_compressDevice_impl(ZSTD_CCtx* c, void* d_dst, size_t dstCapacity, const void* d_src, size_t srcSize)
 {
     size_t e = cctx_bind(c); if (isErr(e)) return e;
-    c->lastRegionList = nullptr;
+    c->lastRegionList = nullptr; c->lastCarryGroups = 0;
     if (srcSize && !d_src) return ZERR(kErrSrcSizeWrong);
     if (!d_dst && dstCapacity) return ZERR(kErrDstBufferNull);
     if (!d_dst) return ZERR(kErrDstSizeTooSmall);
@@ -1033,6 +1055,7 @@ static size_t compress_any(ZSTD_CCtx* c, const CallParams& cp, void* dst, size_t
 {
     size_t e = cctx_bind(c); if (isErr(e)) return e;
     c->lastRegionList = nullptr;        // (ZSTDMI_debugLastRegionChunks speaks of this call from here on)
+    c->lastCarryGroups = 0;             // (and ZSTDMI_debugLastCarryGroups)
     if (srcSize && !src) return ZERR(kErrSrcSizeWrong);
     if (!dst) return ZERR(kErrDstSizeTooSmall);
     if (c->workers.size() > 1 && cp.seek) return ZERR(kErrParameterUnsupported);
@@ -1071,7 +1094,7 @@ static size_t compress_prefixed(ZSTD_CCtx* c, void* dst, size_t dstCapacity, con
     const void* const pfx = c->pfx; const size_t pfxSize = c->pfxSize;
     c->pfx = nullptr; c->pfxSize = 0;       // consumed, whatever this call returns (the reference consumes it at frame start)
     size_t e = cctx_bind(c); if (isErr(e)) return e;
-    c->lastRegionList = nullptr;
+    c->lastRegionList = nullptr; c->lastCarryGroups = 0;
     CallParams cp = sticky_params(c);
     auto plain = [&]() { return deviceCall ? ZSTDMI_compressDevice_impl(c, dst, dstCapacity, src, srcSize) : compress_any(c, cp, dst, dstCapacity, src, srcSize); };
     if (pfxSize < 8) return plain();
@@ -1267,13 +1290,14 @@ static size_t compress_multi(ZSTD_CCtx* c, const CallParams& cp, void* dst, size
     { const size_t e = check_call_params(cp); if (isErr(e)) return e; }
     { const size_t e = check_ldm_dict(c, cp, srcSize); if (isErr(e)) return e; }
     const size_t W = c->workers.size();
-    for (ZSTD_CCtx* w : c->workers) w->lastRegionList = nullptr;
+    for (ZSTD_CCtx* w : c->workers) { w->lastRegionList = nullptr; w->lastCarryGroups = 0; }
     bool ok = true;
     // the workers run with the parent's settings and dictionary
     if (cp.useDict) { const size_t e = cctx_sync_dictionary(c); if (isErr(e)) return e; }
     for (ZSTD_CCtx* w : c->workers) {
         w->historyBytes = c->historyBytes; w->frameBytes = c->frameBytes; w->parser = c->parser; w->passChunks = c->passChunks; w->timer.enabled = c->timer.enabled;
         w->dictEntropy = c->dictEntropy;        // (before the dictionary: a worker builds the tables when it uploads its copy)
+        w->entropyCarry = c->entropyCarry;
         w->dictIndex = c->dictIndex; w->dictIndexStrategy = c->dictIndexStrategy; w->dictIndexChain = c->dictIndexChain;       // (and the index, as far up the strategies as the parent's)
         if (w->dictGen != c->dictGen) {
             w->own.dictHost = c->own.dictHost; w->own.dictFull = c->own.dictFull; w->own.dictWide = c->own.dictWide; w->own.dictFormatted = c->own.dictFormatted; w->own.info = c->own.info; w->dictDirty = true; w->dictGen = c->dictGen;
@@ -1439,6 +1463,7 @@ static size_t cstream_compress_single(ZSTD_CCtx* c, size_t n, bool ending)
     if (tail && hipMemcpyAsync(d_src - tail, c->sTail.data(), tail, hipMemcpyHostToDevice, c->stream) != hipSuccess) return ZERR(kErrGeneric);
     if (hipMemcpyAsync(d_src, c->sIn.data(), n, hipMemcpyHostToDevice, c->stream) != hipSuccess) return ZERR(kErrGeneric);
     bool first = true;
+    c->lastCarryGroups = 0;
     const size_t r = compress_range(c, cp, (u8*)c->stageDst.p, cap, d_src, n, kStreamParamSize, first);
     if (isErr(r)) return r;
     const size_t at = c->sOut.size();
@@ -1492,6 +1517,7 @@ static size_t cstream_compress_sliding(ZSTD_CCtx* c, size_t n, bool ending)
         u8* const d_src = w + c->sWinFill;
         if (hipMemcpyAsync(d_src, c->sIn.data(), m, hipMemcpyHostToDevice, c->stream) != hipSuccess) return ZERR(kErrGeneric);
         bool first = true;
+        c->lastCarryGroups = 0;
         const size_t r = compress_range(c, cp, (u8*)c->stageDst.p, cap, d_src, m, kStreamParamSize, first);
         if (isErr(r)) return r;
         const size_t at = c->sOut.size();
@@ -1593,6 +1619,16 @@ size_t ZSTDMI_CCtx_setDictEntropy(ZSTD_CCtx* c, unsigned mode)
     c->dictEntropy = (int)mode;
     return 0;
 }
+// (no device is touched: the switch is read by the next call, carry_active)
+size_t ZSTDMI_CCtx_setEntropyCarry(ZSTD_CCtx* c, unsigned mode) { if (!c) return ZERR(kErrGeneric); if (mode > 1) return ZERR(kErrParameterOutOfBound); c->entropyCarry = (int)mode; return 0; }
+long long ZSTDMI_debugLastCarryGroups(const ZSTD_CCtx* c)
+{
+    if (!c) return -1;
+    if (c->workers.size() <= 1) return c->lastCarryGroups;
+    long long n = 0;
+    for (const ZSTD_CCtx* w : c->workers) n += w->lastCarryGroups;
+    return n;
+}
 // (no device is touched: a loaded dictionary is marked for another upload, which builds — or no longer builds — its index)
 size_t ZSTDMI_CCtx_setDictIndex(ZSTD_CCtx* c, unsigned mode)
 {
@@ -1688,20 +1724,28 @@ size_t ZSTDMI_debugEntropyBlock(ZSTD_CCtx* c, void* dst, size_t dstCapacity, con
 size_t ZSTDMI_debugPoisonedChunk(ZSTD_CCtx* c, unsigned nbSeq, unsigned litSize, unsigned srcSize, unsigned fill)
 {
     size_t e = cctx_bind(c); if (isErr(e)) return e;
-    if (!cctx_workspace(c, 1)) return ZERR(kErrMemoryAllocation);
     hipStream_t s = c->stream;
     // (with ZSTDMI_CCtx_setDictEntropy on and a formatted dictionary loaded, the instances that read its tables run)
     e = cctx_sync_dictionary(c); if (isErr(e)) return e;
     const DictCTables* const dct = call_dict_ctables(c, sticky_params(c));
-    ChunkMeta m = {}; m.srcSize = srcSize; m.nbSeq = nbSeq; m.litSize = litSize; m.fhSize = frame_header_bytes(FrameHeaderSpec{}, srcSize < kChunkSize ? srcSize : kChunkSize);
-    (void)hipMemsetAsync(c->seqs.p, (int)(fill & 0xFF), (size_t)kMaxSeq * sizeof(Seq), s);
-    (void)hipMemsetAsync(c->lits.p, (int)(fill & 0xFF), kLitStride, s);
-    (void)hipMemcpyAsync(c->meta.p, &m, sizeof m, hipMemcpyHostToDevice, s);
-    launch_huf_build((u8*)c->lits.p, (ChunkMeta*)c->meta.p, (HufTable*)c->tables.p, (u8*)c->slots.p, 1, 0, (const u8*)c->lits.p, layout_arith(kChunkSize, 0, 0), s, StageHook(), dct);
-    launch_huf_encode((u8*)c->lits.p, (ChunkMeta*)c->meta.p, (HufTable*)c->tables.p, (u8*)c->slots.p, nullptr, nullptr, 0, 1, (const u8*)c->lits.p, kChunkSize, s, dct != nullptr);
-    { const u32 plainReps[3] = { 1, 4, 8 };
-      launch_seq_encode((Seq*)c->seqs.p, (ChunkMeta*)c->meta.p, (u8*)c->slots.p, 1, 1, FrameHeaderSpec{}, 1, plainReps, layout_arith(kChunkSize, 0, srcSize < kChunkSize ? srcSize : kChunkSize), s, dct); }
-    if (isErr(dev_read(&m, c->meta.p, sizeof m, s))) return ZERR(kErrGeneric);
+    // (with ZSTDMI_CCtx_setEntropyCarry on, and no such tables, the record is filed twice, as the two blocks of one frame in the
+    //  pipeline's order, and seq_encode's carry instance codes the second behind what the first left: the answer is the second's)
+    const bool carry = c->entropyCarry && !dct;
+    const u32 nRec = carry ? 2u : 1u;
+    if (!cctx_workspace(c, nRec)) return ZERR(kErrMemoryAllocation);
+    const u32 blockSize = srcSize < kChunkSize ? srcSize : kChunkSize;
+    ChunkMeta m = {}; m.srcSize = srcSize; m.nbSeq = nbSeq; m.litSize = litSize; m.fhSize = frame_header_bytes(FrameHeaderSpec{}, blockSize);
+    (void)hipMemsetAsync(c->seqs.p, (int)(fill & 0xFF), (size_t)nRec * kMaxSeq * sizeof(Seq), s);
+    (void)hipMemsetAsync(c->lits.p, (int)(fill & 0xFF), (size_t)nRec * kLitStride, s);
+    for (u32 r = 0; r < nRec; ++r) (void)hipMemcpyAsync((ChunkMeta*)c->meta.p + r, &m, sizeof m, hipMemcpyHostToDevice, s);
+    const FrameLayout frames = carry ? layout_arith(kChunkSize, 2, (u64)kChunkSize + blockSize) : layout_arith(kChunkSize, 0, blockSize);
+    const u32 plainReps[3] = { 1, 4, 8 };
+    const SeqCarry sc = { (HufTable*)c->tables.p, nullptr, 1, 0 };
+    launch_huf_build((u8*)c->lits.p, (ChunkMeta*)c->meta.p, (HufTable*)c->tables.p, (u8*)c->slots.p, nRec, 0, (const u8*)c->lits.p, layout_arith(kChunkSize, 0, 0), s, StageHook(), dct);
+    if (!carry) launch_huf_encode((u8*)c->lits.p, (ChunkMeta*)c->meta.p, (HufTable*)c->tables.p, (u8*)c->slots.p, nullptr, nullptr, 0, 1, (const u8*)c->lits.p, kChunkSize, s, dct != nullptr);
+    launch_seq_encode((Seq*)c->seqs.p, (ChunkMeta*)c->meta.p, (u8*)c->slots.p, nRec, 1, FrameHeaderSpec{}, 1, plainReps, frames, s, dct, nullptr, nullptr, carry ? &sc : nullptr);
+    if (carry) launch_huf_encode((u8*)c->lits.p, (ChunkMeta*)c->meta.p, (HufTable*)c->tables.p, (u8*)c->slots.p, nullptr, nullptr, 0, nRec, (const u8*)c->lits.p, kChunkSize, s, true);
+    if (isErr(dev_read(&m, (ChunkMeta*)c->meta.p + (nRec - 1), sizeof m, s))) return ZERR(kErrGeneric);
     c->lastChunks = 0;
     return m.outSize;
 }
@@ -1870,7 +1914,11 @@ static size_t compress_entries(ZSTD_CCtx* c, const CallParams& cp, const u8* con
             if (set) for (const CDictSlot& r : slotTab) if (r.dct) dct = r.dct;     // (any: "some slot has tables")
             const size_t atChunkSlot = atSeek + (seekIdx ? (size_t)nEnt * 4 : 0);
             const size_t atSlots = (atChunkSlot + (set ? (size_t)nCh * 4 : 0) + 7) & ~(size_t)7;
-            const size_t tabBytes = (atSlots + (set ? slotTab.size() * sizeof(CDictSlot) : 0) + 7) & ~(size_t)7;
+            // carried entropy state (entries of more than one block): | leaders[nCh + 1] (u32), the chunks that lead a carry group
+            // (zmi_carry.h), so that an entry's bytes are the single call's
+            const bool carry = carry_active(c, params_of(g.members[m0]), fr, ls);
+            const size_t atLead = (atSlots + (set ? slotTab.size() * sizeof(CDictSlot) : 0) + 7) & ~(size_t)7;
+            const size_t tabBytes = (atLead + (carry ? ((size_t)nCh + 1) * 4 : 0) + 7) & ~(size_t)7;
             tab.assign(tabBytes, 0);
             if (set) { memcpy(tab.data() + atChunkSlot, chunkSlot.data(), (size_t)nCh * 4); memcpy(tab.data() + atSlots, slotTab.data(), slotTab.size() * sizeof(CDictSlot)); }
             u64* const hFrom = (u64*)tab.data(); u64* const hDst = (u64*)(tab.data() + atDst); u64* const hCap = (u64*)(tab.data() + atCap);
@@ -1901,6 +1949,8 @@ static size_t compress_entries(ZSTD_CCtx* c, const CallParams& cp, const u8* con
                 }
             }
             hFirst[nEnt] = ck;
+            SeqCarry sc = { (HufTable*)nullptr, nullptr, 0, rs.rawLiterals };
+            if (carry) { sc.nGroups = carry_leaders_table(hFrame, nCh, (u32*)(tab.data() + atLead)); c->lastCarryGroups += sc.nGroups; }
             if (!cctx_workspace(c, nCh) || (regionParse && !cctx_cand_workspace(c, nCh, hcChains)) || (regionParse && g.fr.dictIndex && !cctx_dist_workspace(c, nCh)) || !c->batchStage.ensure((u64)nCh * cb + 64) ||
                 !c->batchTab.ensure(tabBytes + (size_t)nEnt * 8)) return ZERR(kErrMemoryAllocation);
             u8* const dTab = (u8*)c->batchTab.p;
@@ -1925,7 +1975,8 @@ static size_t compress_entries(ZSTD_CCtx* c, const CallParams& cp, const u8* con
             launch_lz(lz);
             launch_huf_build(lits, meta, tables, slots, nCh, rs.rawLiterals, stage, frames, s, c->timer.hook(), dct, dSlots, dChunkSlot);
             if (cp.checksumFlag) { launch_xxh64(stage, meta, nCh, frames, s, dLen);        c->timer.mark("xxh64", s); }
-            launch_seq_encode(seqs, meta, slots, nCh, ls.strategy, ls.header, 1, ls.initReps, frames, s, dct, dSlots, dChunkSlot);
+            sc.tables = tables; sc.leaders = (const u32*)(dTab + atLead);
+            launch_seq_encode(seqs, meta, slots, nCh, ls.strategy, ls.header, 1, ls.initReps, frames, s, dct, dSlots, dChunkSlot, carry ? &sc : nullptr);
             c->timer.mark("seq_encode", s);
             c->lastBatchPasses++; if (set) c->lastBatchSetChunks += nCh;
             if (d_stats) launch_seq_stats(seqs, lits, meta, nCh, stage, cb, d_stats, s);
@@ -1936,7 +1987,7 @@ static size_t compress_entries(ZSTD_CCtx* c, const CallParams& cp, const u8* con
                 c->timer.mark("pack_entries", s);
             }
             if (dsts) {
-                launch_huf_encode(lits, meta, tables, slots, base, offsets, span, nCh, stage, cb, s, dct != nullptr);     c->timer.mark("huf_encode", s);
+                launch_huf_encode(lits, meta, tables, slots, base, offsets, span, nCh, stage, cb, s, dct != nullptr || carry);     c->timer.mark("huf_encode", s);
                 launch_gather(stage, stagedBytes, slots, meta, offsets, base, span, nCh, cb, s);          c->timer.mark("gather", s);
             }
             got.resize(nEnt);
@@ -1963,8 +2014,9 @@ namespace zmi {
 size_t compress_samples(ZSTD_CCtx* c, const u8* src, const u64* offs, const size_t* sizes, size_t n, size_t* outSizes, u32* stats)
 {
     size_t e = cctx_bind(c); if (isErr(e)) return e;
-    c->lastRegionList = nullptr;
+    c->lastRegionList = nullptr; c->lastCarryGroups = 0;
     CallParams cp = sticky_params(c); cp.seek = false;
+    cp.entropyCarry = false;        // (sizes and statistics of the samples are those of the default coding, whatever the context's switch says)
     e = cctx_sync_dictionary(c); if (isErr(e)) return e;
     hipStream_t s = c->stream;
     u64 maxEnd = 0;
@@ -1992,7 +2044,7 @@ size_t compress_samples(ZSTD_CCtx* c, const u8* src, const u64* offs, const size
 static size_t compress_batch_impl(ZSTD_CCtx* c, const void* const* srcs, const size_t* srcSizes, size_t n, void* const* dsts, const size_t* dstCapacities, size_t* dstSizes)
 {
     if (!c) return ZERR(kErrGeneric);
-    c->lastRegionList = nullptr;
+    c->lastRegionList = nullptr; c->lastCarryGroups = 0;
     if (n == 0) { c->lastBatchAlone = 0; return 0; }
     if (!srcs || !srcSizes || !dsts || !dstCapacities || !dstSizes) return ZERR(kErrGeneric);
     size_t e = cctx_bind(c); if (isErr(e)) return e;
@@ -2018,7 +2070,7 @@ static size_t compress_batch_cdicts_impl(ZSTD_CCtx* c, const void* const* srcs, 
                                          size_t* dstSizes, const ZSTD_CDict* const* cdicts)
 {
     if (!c) return ZERR(kErrGeneric);
-    c->lastRegionList = nullptr;
+    c->lastRegionList = nullptr; c->lastCarryGroups = 0;
     if (n == 0) { c->lastBatchAlone = 0; c->lastBatchPasses = 0; c->lastBatchSetChunks = 0; return 0; }
     if (!srcs || !srcSizes || !dsts || !dstCapacities || !dstSizes || !cdicts) return ZERR(kErrGeneric);
     size_t e = cctx_bind(c); if (isErr(e)) return e;
@@ -2096,7 +2148,7 @@ static size_t compress_pack_impl(ZSTD_CCtx* c, u8* d_dst, size_t dstCapacity, co
 {
     if (!c || (n && (!srcs || !sizes))) return ZERR(kErrGeneric);
     size_t e = cctx_bind(c); if (isErr(e)) return e;
-    c->lastRegionList = nullptr;
+    c->lastRegionList = nullptr; c->lastCarryGroups = 0;
     if (c->workers.size() > 1 || c->pfx) return ZERR(kErrParameterUnsupported);
     c->lastPackAlone = 0; c->lastPackFrames = 0;
     CallParams cp = sticky_params(c); cp.seek = false;      // (the context's own switch is not consulted)
