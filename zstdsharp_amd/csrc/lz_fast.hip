@@ -1078,6 +1078,15 @@ __global__ __launch_bounds__(1024) void lz_kernel(const LzArgs a)
 #endif
 
     // ---- stage the chunk: 16 B per lane when the source is 16-byte aligned ----
+    // tidS: the thread index as this section sees it.  Every address below depends on the thread index alone, so the compiler computed
+    // them once in front of the chunk loop and kept them in registers through the tile loop, which runs at the 128-register cap: the
+    // allocator paid with the longest-lived values it had, the prefetched chunk — pf0 went to scratch right behind its load, so every
+    // chunk began with s_waitcnt vmcnt(0) on one HBM access before the other three were even issued (13 spilled registers, 40 bytes
+    // of scratch).  Behind an empty statement the value is opaque, the addresses are this section's own, and the four loads of the
+    // prefetch leave back to back (3 spilled registers, 16 bytes of scratch, none of them the prefetch's).  The instances without
+    // the prefetch keep the plain index and their code.
+    u32 tidS = tid;
+    if constexpr (kPrefetch) asm volatile("" : "+v"(tidS));
     if (DICT && frameBlocks && !indep && ((((uintptr_t)prefix) | lowLimit) & 15) == 0) {
         // cross-chunk history: the history and the block are ONE contiguous piece of the input (at most 64 KiB): four 16-byte
         // pieces per thread, all loads in flight before the first store (pieces past the end re-read piece 0 and are not stored)
@@ -1085,38 +1094,38 @@ __global__ __launch_bounds__(1024) void lz_kernel(const LzArgs a)
         uint4* l4 = reinterpret_cast<uint4*>(L.in + lowLimit);
         const u32 bytes = prefixLen + nData, full = bytes >> 4;
         uint4 v0, v1, v2, v3;
-        const u32 i0 = tid, i1 = tid + kTile, i2 = tid + 2 * kTile, i3 = tid + 3 * kTile;
+        const u32 i0 = tidS, i1 = tidS + kTile, i2 = tidS + 2 * kTile, i3 = tidS + 3 * kTile;
         v0 = in4[i0 < full ? i0 : 0]; v1 = in4[i1 < full ? i1 : 0]; v2 = in4[i2 < full ? i2 : 0]; v3 = in4[i3 < full ? i3 : 0];
         if (i0 < full) l4[i0] = v0;
         if (i1 < full) l4[i1] = v1;
         if (i2 < full) l4[i2] = v2;
         if (i3 < full) l4[i3] = v3;
-        for (u32 i = (full << 4) + tid; i < bytes; i += kTile) L.in[lowLimit + i] = prefix[i];
-        for (u32 i = tid; i < lowLimit; i += kTile) L.in[i] = 0;
+        for (u32 i = (full << 4) + tidS; i < bytes; i += kTile) L.in[lowLimit + i] = prefix[i];
+        for (u32 i = tidS; i < lowLimit; i += kTile) L.in[i] = 0;
     } else {
     if (kPrefetch && pfValid) {                            // (uniform) a full aligned chunk, already in registers
         uint4* l4 = reinterpret_cast<uint4*>(L.in);
-        l4[tid] = pf0; l4[tid + kTile] = pf1; l4[tid + 2 * kTile] = pf2; l4[tid + 3 * kTile] = pf3;
+        l4[tidS] = pf0; l4[tidS + kTile] = pf1; l4[tidS + 2 * kTile] = pf2; l4[tidS + 3 * kTile] = pf3;
     } else if ((((uintptr_t)in) & 15) == 0) {
         const uint4* in4 = reinterpret_cast<const uint4*>(in);
         uint4* l4 = reinterpret_cast<uint4*>(L.in + hist);
         const u32 full = nData >> 4;
         if (full) {                                 // a full chunk is four 16-byte pieces per thread: all loads in flight, then the stores
             uint4 v0, v1, v2, v3;                   // (pieces past the end re-read piece 0 and are not stored)
-            const u32 i0 = tid, i1 = tid + kTile, i2 = tid + 2 * kTile, i3 = tid + 3 * kTile;
+            const u32 i0 = tidS, i1 = tidS + kTile, i2 = tidS + 2 * kTile, i3 = tidS + 3 * kTile;
             v0 = in4[i0 < full ? i0 : 0]; v1 = in4[i1 < full ? i1 : 0]; v2 = in4[i2 < full ? i2 : 0]; v3 = in4[i3 < full ? i3 : 0];
             if (i0 < full) l4[i0] = v0;
             if (i1 < full) l4[i1] = v1;
             if (i2 < full) l4[i2] = v2;
             if (i3 < full) l4[i3] = v3;
         }
-        for (u32 i = (full << 4) + tid; i < nData; i += kTile) L.in[hist + i] = in[i];
+        for (u32 i = (full << 4) + tidS; i < nData; i += kTile) L.in[hist + i] = in[i];
     } else {
-        for (u32 i = tid; i < nData; i += kTile) L.in[hist + i] = in[i];
+        for (u32 i = tidS; i < nData; i += kTile) L.in[hist + i] = in[i];
     }
-    if (DICT) for (u32 i = tid; i < hist; i += kTile) L.in[i] = i >= lowLimit ? prefix[i - lowLimit] : (u8)0;
+    if (DICT) for (u32 i = tidS; i < hist; i += kTile) L.in[i] = i >= lowLimit ? prefix[i - lowLimit] : (u8)0;
     }
-    for (u32 i = n + tid; i < kChunkSize + kInPad; i += kTile) L.in[i] = 0;
+    for (u32 i = n + tidS; i < kChunkSize + kInPad; i += kTile) L.in[i] = 0;
     u32* const endOf = reinterpret_cast<u32*>(L.jumpB);
     u32* const table = L.tabMem;                           // fast
     u32* const first = L.tabMem + (1u << kHashLog);
@@ -1128,12 +1137,12 @@ __global__ __launch_bounds__(1024) void lz_kernel(const LzArgs a)
         uint4* const t4 = reinterpret_cast<uint4*>(L.tabMem);
         const uint4 z = {0u, 0u, 0u, 0u}, f = {~0u, ~0u, ~0u, ~0u};
 #pragma unroll
-        for (u32 k = 0; k < 2; ++k) { t4[tid + k * kTile] = MODE == 0 ? z : f; t4[2 * kTile + tid + k * kTile] = MODE == 0 ? f : z; }
+        for (u32 k = 0; k < 2; ++k) { t4[tidS + k * kTile] = MODE == 0 ? z : f; t4[2 * kTile + tidS + k * kTile] = MODE == 0 ? f : z; }
     }
-    if (tid == 0) { L.nzWords[0] = 0; L.nzWords[1] = 0; L.nzWords[2] = 0; L.matchCount[0] = 0; L.matchCount[1] = 0; L.matchCount[2] = 0; }
+    if (tidS == 0) { L.nzWords[0] = 0; L.nzWords[1] = 0; L.nzWords[2] = 0; L.matchCount[0] = 0; L.matchCount[1] = 0; L.matchCount[2] = 0; }
     pfValid = false;
     cNext = c + gridDim.x;
-    if (claiming && tid == 0) { L.claim = claimed; claimed = atomicAdd(claimCtr, 1u) + gridDim.x; }
+    if (claiming && tidS == 0) { L.claim = claimed; claimed = atomicAdd(claimCtr, 1u) + gridDim.x; }
     __syncthreads();
     if (claiming) cNext = L.claim;
     if (kPrefetch) {
@@ -1142,7 +1151,7 @@ __global__ __launch_bounds__(1024) void lz_kernel(const LzArgs a)
         // (a batch's short chunk is staged directly: the zero fill behind its data must not meet the prefetched stores)
         if (cN < nChunks && srcSize - (u64)cN * kChunkSize >= kChunkSize && (((uintptr_t)inN) & 15) == 0 && (!chunkLens || chunkLens[cN] >= kChunkSize)) {      // uniform
             const uint4* n4 = reinterpret_cast<const uint4*>(inN);
-            pf0 = n4[tid]; pf1 = n4[tid + kTile]; pf2 = n4[tid + 2 * kTile]; pf3 = n4[tid + 3 * kTile];
+            pf0 = n4[tidS]; pf1 = n4[tidS + kTile]; pf2 = n4[tidS + 2 * kTile]; pf3 = n4[tidS + 3 * kTile];
             pfValid = true;
         }
     }
