@@ -428,6 +428,47 @@ size_t ZSTDMI_compressBatchCDicts(ZSTD_CCtx* cctx, const void* const* srcs, cons
                                   const ZSTD_CDict* const* cdicts);
 long long ZSTDMI_debugLastBatchPasses(const ZSTD_CCtx* cctx);     /* passes through the pipeline the last batch call made (either entry point; entries that went alone are ZSTDMI_debugLastBatchAlone's); -1 without a context */
 long long ZSTDMI_debugLastBatchSetChunks(const ZSTD_CCtx* cctx);  /* chunks of the last batch call that ran in set instances; 0 whenever the single-dictionary kernels ran; -1 without a context */
+/* ---- a batch enqueued from the device: descriptors in HBM, no host round trip ----
+ * ZSTDMI_compressBatch reads its five arrays on the host and waits for the sizes.  These two calls split that: the prepare does
+ * everything that needs the host (it may allocate, upload the dictionary and synchronise), the async call only enqueues.
+ * ZSTDMI_CCtx_prepareBatchAsync resolves the context's sticky parameters and the dictionary in force (loaded, ZSTD_CCtx_refCDict, the
+ * switches ZSTDMI_CCtx_setDictEntropy / setDictIndex / setDictIndexStrategy / setDictIndexChain) as ZSTDMI_compressBatch would for an
+ * entry of exactly srcSizeBound bytes, uploads the dictionary, and sizes every workspace a pass of maxEntries blocks needs.  It returns
+ * 0, or: GENERIC (NULL context), init_missing, memory_allocation, dictionary_corrupted, the error every single call would answer for
+ * the sticky parameters, and parameter_unsupported for what the one-block batched pass does not cover: a bound of 0; a bound that resolves
+ * to more than one block or to a multi-block frame (above 64 KiB; behind a staged dictionary tail above 64 KiB minus the tail rounded
+ * up to 4 KiB; under ZSTD_c_windowLog 10 .. 15 above one window); several device workers; the seek-table switch; a pending
+ * ZSTD_CCtx_refPrefix (which stays pending); maxEntries above the pass limit (ZSTDMI_CCtx_setPassChunks, at most 16384).  A refused or
+ * failed prepare leaves the context without a valid one.
+ * ZSTDMI_compressBatchAsync: all five arrays and everything they point to are DEVICE memory.  The call makes no device allocation, no
+ * host wait, no copy between host and device and no host read of the arrays; it enqueues kernels on the context's stream
+ * (ZSTDMI_CCtx_setStream) and returns: 0 once enqueued (n == 0: 0, nothing is touched); GENERIC for a NULL context, or a NULL array with
+ * n > 0; stage_wrong if there is no valid prepare, n > maxEntries, or a parameter, dictionary, CDict reference or switch changed since
+ * the prepare (any setter invalidates it, whatever value it sets; only a generation counter is compared).  Stage timing
+ * (ZSTDMI_CCtx_setProfiling) is off for the length of the call.
+ * The arrays, the sources and the destinations must stay valid and unchanged until the stream has passed the work, and so must a
+ * referenced CDict; d_dstSizes and the destinations hold their results from then on.  Work is in flight when the call returns: the
+ * context waits for it by itself wherever it frees or regrows one of its buffers (ZSTD_freeCCtx, a later call that needs more room,
+ * ZSTDMI_CCtx_setStream to another stream, ZSTD_CCtx_loadDictionary, ZSTD_CCtx_refCDict, a dictionary's re-upload); a later call on the
+ * same stream is ordered by the stream.  Capturing the call into a hipGraph is neither claimed nor tested.
+ * Per entry, d_dstSizes[i] is the compressed size or a zstd error code, with the convention of ZSTDMI_compressBatch: srcSize_wrong when
+ * d_srcSizes[i] > srcSizeBound, or when the source is NULL with a non-zero size; dstBuffer_null (capacity > 0) or dstSize_tooSmall
+ * (capacity 0) for a NULL destination; dstSize_tooSmall, with nothing written, when the result exceeds the capacity.  A size of 0 writes
+ * the empty frame the single call writes under these parameters.  One entry's failure changes nothing of another's.  Nothing is
+ * written at or beyond d_dsts[i] + d_dstCapacities[i].
+ * Bytes.  Every entry is compressed with the framing and parameters that srcSizeBound resolves to.  Every result is a complete zstd
+ * stream that decodes on its own.  For an entry whose own size resolves to the same framing and parameters as the bound, the bytes are
+ * exactly those of ZSTDMI_compressBatch.  The level tables change at 16 KiB, 128 KiB and 256 KiB.  A staged dictionary tail changes
+ * with the size (up to 60 KiB of it in front of an entry that fits one block behind it, else 32 KiB).  An entry in another tier is
+ * valid but may differ from the synchronous call's bytes.  It is the price of the host never seeing a size. */
+size_t ZSTDMI_CCtx_prepareBatchAsync(ZSTD_CCtx* cctx, size_t maxEntries, size_t srcSizeBound);
+size_t ZSTDMI_compressBatchAsync(ZSTD_CCtx* cctx, const void* const* d_srcs, const size_t* d_srcSizes, size_t n,
+                                 void* const* d_dsts, const size_t* d_dstCapacities, size_t* d_dstSizes);
+/* diagnostics: blocking waits the compressor's host code has made for this context (stream waits, read-backs, blocking copies, the
+ * wait behind an enqueued batch), and growths of its device buffers, since it was created; -1 without a context.  Neither moves
+ * across ZSTDMI_compressBatchAsync. */
+long long ZSTDMI_debugHostWaits(const ZSTD_CCtx* cctx);
+long long ZSTDMI_debugDeviceAllocs(const ZSTD_CCtx* cctx);
 
 /* Packs: n device buffers into ONE contiguous, standard seekable stream whose frames end exactly at the entries' boundaries — the write
  * side of ZSTDMI_decompressRanges.  srcs and srcSizes are host arrays; srcs[i] and d_dst are device pointers as for ZSTDMI_compressBatch,

@@ -9,7 +9,12 @@ with history of the default settings — at the same kinds and levels.  Per poin
 Best of 3 after a warm-up call of the same shape; the host clock stops after the call's final synchronise (every call ends with one).
 The input is 16 MiB of generated data repeated (entries are independent, so the repeats are nobody's match).
 python tools/batch_time.py [MiB] [--dict-entropy] [--dict-row] [--frames-rows] [--measure-only] [--dict-index-rows] [--dict-index]
-                           [--level=N] [--dict-index-strategy=N] [--dict-index-chain] [--unsized-rows] [--batch-unsized]
+                           [--level=N] [--dict-index-strategy=N] [--dict-index-chain] [--unsized-rows] [--batch-unsized] [--async]
+  --async        : only the rows of ZSTDMI_compressBatchAsync: text entries of 4 KiB at levels 1 and 3, the descriptors as CUDA tensors.
+                   One ZSTDMI_CCtx_prepareBatchAsync for a pass of 16 384 entries (the pass limit), then per measurement one async call
+                   per 16 384 entries back to back on the context's stream: (a) until the last call has returned, (b) until a following
+                   hipStreamSynchronize (torch.cuda.synchronize) has returned, and (c) the synchronous ZSTDMI_compressBatch of the same
+                   entries in the same session, its final wait included.  The bytes of both are compared afterwards.
   --unsized-rows : only the rows of ZSTDMI_DCtx_setBatchUnsized, decompression alone: text and Zipf entries of 4 KiB at level 3,
                    (a) written with content sizes, one batch call; (b) written with ZSTD_c_contentSizeFlag = 0 and the window restated as
                    the 2^19 a streaming encoder declares (each frame's bound: 128 KiB), the switch off — every entry goes alone: timed on
@@ -42,7 +47,7 @@ FLAGS = [a for a in sys.argv[1:] if a.startswith("--")]
 ARGS = [a for a in sys.argv[1:] if not a.startswith("--")]
 VALUED = {f.split("=", 1)[0]: int(f.split("=", 1)[1]) for f in FLAGS if "=" in f}
 FLAGS = [f for f in FLAGS if "=" not in f]
-assert all(f in ("--dict-entropy", "--dict-row", "--frames-rows", "--measure-only", "--dict-index-rows", "--dict-index", "--dict-index-chain", "--unsized-rows", "--batch-unsized") for f in FLAGS), FLAGS
+assert all(f in ("--dict-entropy", "--dict-row", "--frames-rows", "--measure-only", "--dict-index-rows", "--dict-index", "--dict-index-chain", "--unsized-rows", "--batch-unsized", "--async") for f in FLAGS), FLAGS
 assert all(f in ("--level", "--dict-index-strategy") for f in VALUED), VALUED
 DICT_INDEX_ROWS, DICT_INDEX = "--dict-index-rows" in FLAGS, "--dict-index" in FLAGS
 INDEX_LEVEL, INDEX_STRATEGY, INDEX_CHAIN = VALUED.get("--level", 1), VALUED.get("--dict-index-strategy"), "--dict-index-chain" in FLAGS
@@ -193,6 +198,57 @@ def unsized_rows():
         torch.cuda.empty_cache()
 
 
+def async_rows():
+    size, pass_entries = 4096, 16384
+    n = total // size
+    cap = lib.ZSTD_compressBound(size)
+    src = torch.from_numpy(np.frombuffer(datagen.gen("text", 16 * MiB, 5), dtype=np.uint8).copy()).cuda().repeat(total // (16 * MiB))
+    idx = torch.arange(n, dtype=torch.int64, device="cuda")
+    print(f"{n} text entries of 4 KiB; ms for all entries (GB/s of content)", flush=True)
+    for level in (1, 3):
+        dst_a = torch.zeros(n * cap + MiB, dtype=torch.uint8, device="cuda")
+        dst_s = torch.zeros(n * cap + MiB, dtype=torch.uint8, device="cuda")
+        c, cs = lib.ZSTD_createCCtx(), lib.ZSTD_createCCtx()
+        for x in (c, cs):
+            lib.ZSTD_CCtx_setParameter(x, 100, level)
+        ok(lib.ZSTDMI_CCtx_prepareBatchAsync(c, pass_entries, size))
+        ok(lib.ZSTDMI_CCtx_setStream(c, torch.cuda.current_stream().cuda_stream or 1))      # (1: hipStreamLegacy, torch's default stream)
+        srcs, dsts = src.data_ptr() + idx * size, dst_a.data_ptr() + idx * cap
+        szs, caps = torch.full((n,), size, dtype=torch.int64, device="cuda"), torch.full((n,), cap, dtype=torch.int64, device="cuda")
+        out = torch.empty(n, dtype=torch.int64, device="cuda")
+        returned = [0.0]
+
+        def enqueue():
+            t0 = time.perf_counter()
+            for at in range(0, n, pass_entries):
+                m = min(pass_entries, n - at)
+                ok(lib.ZSTDMI_compressBatchAsync(c, srcs.data_ptr() + 8 * at, szs.data_ptr() + 8 * at, m, dsts.data_ptr() + 8 * at, caps.data_ptr() + 8 * at, out.data_ptr() + 8 * at))
+            returned[0] = time.perf_counter() - t0
+            torch.cuda.synchronize()
+
+        waits = lib.ZSTDMI_debugHostWaits(c)
+        ret, done = 1e9, 1e9
+        enqueue()
+        for _ in range(3):
+            torch.cuda.synchronize(); t0 = time.perf_counter()
+            enqueue()
+            done = min(done, time.perf_counter() - t0); ret = min(ret, returned[0])
+        assert lib.ZSTDMI_debugHostWaits(c) == waits
+        s_ptr, d_ptr = ptrs(src.data_ptr(), [i * size for i in range(n)]), ptrs(dst_s.data_ptr(), [i * cap for i in range(n)])
+        s_sz, d_cap, got = sizes([size] * n), sizes([cap] * n), (ctypes.c_size_t * n)()
+        sync = best_of(lambda: ok(lib.ZSTDMI_compressBatch(cs, s_ptr, s_sz, n, d_ptr, d_cap, got)))
+        assert out.cpu().tolist() == list(got) and bool(torch.equal(dst_a, dst_s))
+        gbs = lambda t: total / t / 1e9
+        print(f"| text 4 KiB L{level} | {n:6d} | ratio {sum(got) / total:.3f} | (a) async calls returned {ret * 1e3:7.2f} | (b) ... and the stream drained {done * 1e3:7.2f} ({gbs(done):6.1f}) "
+              f"| (c) synchronous batch {sync * 1e3:7.2f} ({gbs(sync):6.1f}) |", flush=True)
+        lib.ZSTD_freeCCtx(c); lib.ZSTD_freeCCtx(cs)
+        del dst_a, dst_s
+        torch.cuda.empty_cache()
+
+
+if "--async" in FLAGS:
+    async_rows()
+    sys.exit(0)
 if DICT_INDEX_ROWS:
     dict_index_rows()
     sys.exit(0)

@@ -117,6 +117,11 @@ SIGNATURES = {
                                           ctypes.POINTER(c_void_p), ctypes.POINTER(c_size_t), ctypes.POINTER(c_size_t)]),
     "ZSTDMI_compressBatchCDicts": (c_size_t, [c_void_p, ctypes.POINTER(c_void_p), ctypes.POINTER(c_size_t), c_size_t,
                                               ctypes.POINTER(c_void_p), ctypes.POINTER(c_size_t), ctypes.POINTER(c_size_t), ctypes.POINTER(c_void_p)]),
+    "ZSTDMI_CCtx_prepareBatchAsync": (c_size_t, [c_void_p, c_size_t, c_size_t]),
+    # (the five arrays are device memory: plain addresses)
+    "ZSTDMI_compressBatchAsync": (c_size_t, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
+    "ZSTDMI_debugHostWaits": (ctypes.c_longlong, [c_void_p]),
+    "ZSTDMI_debugDeviceAllocs": (ctypes.c_longlong, [c_void_p]),
     "ZSTDMI_debugLastBatchAlone": (c_int, [c_void_p]),
     "ZSTDMI_debugLastBatchPasses": (ctypes.c_longlong, [c_void_p]),
     "ZSTDMI_debugLastBatchSetChunks": (ctypes.c_longlong, [c_void_p]),

@@ -11,6 +11,9 @@ from . import _ffi
 from .errors import ZstdException, get_error_code, is_error
 
 
+_HIP_STREAM_LEGACY = 1       # hipStreamLegacy (hip_runtime_api.h): the null stream, named explicitly
+
+
 def _pointer_array(values):
     return (ctypes.c_void_p * len(values))(*values)
 
@@ -110,6 +113,35 @@ def compress_batch(compressor, items, cdicts=None):
     out = _run(torch, lib, call, compressor.cctx, device, srcs, sizes, [lib.ZSTD_compressBound(x) for x in sizes], tensors)
     del keep, cdicts
     return out
+
+
+def compress_batch_async(compressor, srcs, sizes, dsts, caps, out_sizes=None):
+    """ZSTDMI_compressBatchAsync after Compressor.PrepareBatchAsync: srcs, sizes, dsts, caps are contiguous CUDA int64 tensors of n
+    entries each (pointers as integers, e.g. base.data_ptr() + offsets computed on the device) -> out_sizes, a CUDA int64 tensor: entry
+    i's compressed size, or its zstd error code as a negative value (-70 dstSize_tooSmall, -72 srcSize_wrong, -74 dstBuffer_null).
+    The work is enqueued on torch.cuda.current_stream() and the call returns: nothing is synchronised and nothing is copied to the
+    host, so out_sizes and the destinations are for work queued on that stream behind it.  The tensors, the sources and the
+    destinations must stay alive and unchanged until that stream has passed the work.  Raises ZstdException for the whole call's
+    error (stage_wrong: no valid PrepareBatchAsync, more entries than it was prepared for, or a parameter changed since)."""
+    import torch
+    compressor._ensure_not_disposed()
+    lib = compressor._lib
+    n = sizes.numel()
+    if out_sizes is None:
+        out_sizes = torch.empty(n, dtype=torch.int64, device=sizes.device)
+    for name, t in (("srcs", srcs), ("sizes", sizes), ("dsts", dsts), ("caps", caps), ("out_sizes", out_sizes)):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int64 and t.is_contiguous() and t.numel() == n):
+            raise TypeError(f"{name}: expected a contiguous CUDA int64 tensor of {n} entries")
+    if n == 0:
+        return out_sizes
+    stream = torch.cuda.current_stream(sizes.device)
+    # (torch's default stream is the null stream, which ZSTDMI_CCtx_setStream reads as "the context's own": hipStreamLegacy names it)
+    r = lib.ZSTDMI_CCtx_setStream(compressor.cctx, stream.cuda_stream or _HIP_STREAM_LEGACY)
+    if not is_error(r):
+        r = lib.ZSTDMI_compressBatchAsync(compressor.cctx, srcs.data_ptr(), sizes.data_ptr(), n, dsts.data_ptr(), caps.data_ptr(), out_sizes.data_ptr())
+    if is_error(r):
+        raise ZstdException(get_error_code(r), lib.ZSTD_getErrorName(r).decode())
+    return out_sizes
 
 
 def compress_pack(compressor, items):

@@ -246,6 +246,17 @@ class Compressor(_PrefixHolder):
         ensure_zstd_success(self._lib, self._lib.ZSTDMI_CCtx_setSlidingLdm(self.cctx, 1 if on else 0))
         self._sliding_ldm = bool(on)
 
+    # ---- batches enqueued from the device (ZSTDMI_CCtx_prepareBatchAsync; batch.compress_batch_async runs them) ----
+    def PrepareBatchAsync(self, max_entries: int, src_size_bound: int):
+        """Everything compress_batch_async needs the host for, once: resolves this object's parameters and dictionary for an entry of
+        src_size_bound bytes, uploads the dictionary and sizes the workspaces for max_entries entries.  Any later SetParameter,
+        LoadDictionary, RefCDict or switch invalidates it.  Raises ZstdException (parameter_unsupported) for what the one-block pass does
+        not cover."""
+        self._ensure_not_disposed()
+        ensure_zstd_success(self._lib, self._lib.ZSTDMI_CCtx_prepareBatchAsync(self.cctx, int(max_entries), int(src_size_bound)))
+
+    prepare_batch_async = PrepareBatchAsync
+
     # ---- Wrap (S/Compressor.cs:78-96) ----
     def Wrap(self, src, dest=None, offset: int = 0):
         """Wrap(src) -> bytes;  Wrap(src, dest[, offset]) -> number of bytes written into dest."""

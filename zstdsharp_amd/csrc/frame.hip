@@ -98,6 +98,62 @@ __global__ __launch_bounds__(256) void batch_place_kernel(const ChunkMeta* __res
     entSize[e] = fits ? sum : (u64)0 - (u64)kErrDstSizeTooSmall;
 }
 
+// ---- a batch whose descriptors lie in HBM (ZSTDMI_compressBatchAsync): the plan and the placement, no host in between ----
+// plan: entry e is chunk e.  The caller's arrays are read here, once, and checked as compress_entries checks them on the host; what the
+// stages read comes out in their layout: from[e], len[e], entFirst[e] = e (and entFirst[n] = n), entDst[e] = the destination's offset
+// from kAsyncBase, entCap[e].  verdict[e]: kAsyncGood, kAsyncEmpty (size 0: the placement writes the empty frame), or the error code
+// the entry answers.  The stages have never seen an empty or an oversize chunk, so every entry that is not kAsyncGood becomes the one
+// byte at `dummy` (context memory); the placement overrides whatever that chunk compressed to.  One lane per entry.
+__global__ __launch_bounds__(256) void batch_plan_kernel(const void* const* __restrict__ srcs, const size_t* __restrict__ sizes,
+                                                         void* const* __restrict__ dsts, const size_t* __restrict__ caps, u32 n, u64 bound,
+                                                         u32 emptyLen, const u8* __restrict__ dummy, u64* __restrict__ from,
+                                                         u64* __restrict__ entDst, u64* __restrict__ entCap, u32* __restrict__ len,
+                                                         u32* __restrict__ entFirst, u32* __restrict__ verdict)
+{
+    const u32 e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= n) return;
+    const u64 S = (u64)sizes[e], cap = (u64)caps[e];
+    const u64 src = (u64)(uintptr_t)srcs[e], dst = (u64)(uintptr_t)dsts[e];
+    u32 v = kAsyncGood;
+    if (S > bound || (S && !src)) v = kErrSrcSizeWrong;
+    else if (dst < kAsyncBase) v = cap ? kErrDstBufferNull : kErrDstSizeTooSmall;        // (null; no device address lies below kAsyncBase)
+    else if (!S) v = cap < emptyLen ? (u32)kErrDstSizeTooSmall : (u32)kAsyncEmpty;
+    const bool good = v == kAsyncGood;
+    from[e] = good ? src : (u64)(uintptr_t)dummy;
+    len[e] = good ? (u32)S : 1u;
+    entDst[e] = dst >= kAsyncBase ? dst - kAsyncBase : 0;
+    entCap[e] = cap;
+    entFirst[e] = e;
+    if (e == n - 1) entFirst[n] = n;
+    verdict[e] = v;
+}
+
+// place (batch_place_kernel's part for such a batch): entry e = chunk e; its size or its error code goes straight into the caller's
+// column.  A good entry that fits lies at entDst[e]; everything else gets the offset kAsyncSpan, which fails huf_encode's and gather's
+// capacity comparison (off + outSize > kAsyncSpan), so nothing of it is written.  An empty entry's frame — the bytes the single call
+// writes under the call's parameters, a launch constant — is written here (the plan compared it with the capacity).  One lane per entry.
+__global__ __launch_bounds__(256) void batch_place_async_kernel(const ChunkMeta* __restrict__ meta, u32 n, const u64* __restrict__ entDst,
+                                                                const u64* __restrict__ entCap, const u32* __restrict__ verdict,
+                                                                const AsyncEmptyFrame empty, u64* __restrict__ offsets, size_t* __restrict__ dstSizes)
+{
+    const u32 e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= n) return;
+    const u32 v = verdict[e];
+    const u64 out = meta[e].outSize;
+    u64 at = kAsyncSpan, answer;
+    if (v == kAsyncGood) {
+        const bool fits = out <= entCap[e];
+        if (fits) at = entDst[e];
+        answer = fits ? out : (u64)0 - (u64)kErrDstSizeTooSmall;
+    } else if (v == kAsyncEmpty) {
+        u8* const d = reinterpret_cast<u8*>((uintptr_t)(entDst[e] + kAsyncBase));
+        for (u32 i = 0; i < empty.len; ++i) d[i] = empty.bytes[i];
+        answer = empty.len;
+    } else answer = (u64)0 - (u64)v;
+    offsets[e] = at;
+    dstSizes[e] = (size_t)answer;
+}
+
 // ---- seek table (ZSTDMI_CCtx_setSeekTable; the zstd seekable format) ----
 // entries: one (compressed size, content size) pair per frame of the pass, from the scan's offsets.  A frame is frameBlocks chunks
 // (the pass's last one may be shorter); the sizes are below 2^32 by construction (a frame holds at most 512 MiB of content).
@@ -398,6 +454,18 @@ void launch_batch_place(const ChunkMeta* meta, u32 nEntries, const u32* entFirst
                         hipStream_t stream)
 {
     hipLaunchKernelGGL(batch_place_kernel, dim3((nEntries + 255) / 256), dim3(256), 0, stream, meta, nEntries, entFirst, entDst, entCap, span, offsets, entSize);
+}
+void launch_batch_plan(const void* const* srcs, const size_t* sizes, void* const* dsts, const size_t* caps, u32 n, u64 bound, u32 emptyLen, const u8* dummy,
+                       u64* from, u64* entDst, u64* entCap, u32* len, u32* entFirst, u32* verdict, hipStream_t stream)
+{
+    hipLaunchKernelGGL(batch_plan_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, srcs, sizes, dsts, caps, n, bound, emptyLen, dummy, from, entDst, entCap, len,
+                       entFirst, verdict);
+}
+void launch_batch_place_async(const ChunkMeta* meta, u32 n, const u64* entDst, const u64* entCap, const u32* verdict, AsyncEmptyFrame empty,
+                              u64* offsets, size_t* dstSizes, hipStream_t stream)
+{
+    assert(empty.len <= sizeof empty.bytes);
+    hipLaunchKernelGGL(batch_place_async_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, meta, n, entDst, entCap, verdict, empty, offsets, dstSizes);
 }
 
 } // namespace zmi

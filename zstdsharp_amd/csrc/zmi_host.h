@@ -78,6 +78,19 @@ void launch_xxh64(const u8* src, ChunkMeta* meta, u32 nChunks, const FrameLayout
 void launch_batch_stage(const u64* from, const u32* len, u8* stage, u32 nChunks, u32 chunkBytes, hipStream_t stream);
 void launch_batch_place(const ChunkMeta* meta, u32 nEntries, const u32* entFirst, const u64* entDst, const u64* entCap, u64 span, u64* offsets, u64* entSize,
                         hipStream_t stream);
+// a batch whose descriptors lie in HBM (ZSTDMI_compressBatchAsync, frame.hip).  plan: the caller's four arrays into the pass's table in the
+// layout the stages read (one chunk per entry), entDst as an offset from kAsyncBase, and a verdict per entry (AsyncVerdict); an entry
+// that runs no pass becomes one byte read from `dummy`.  place: sizes and statuses straight into the caller's column, the empty frame
+// (by value) for entries of size 0, the offset kAsyncSpan for every entry that writes nothing.
+// kAsyncBase: the "base pointer" huf_encode and gather get with absolute addresses (not null: a null dst is huf_encode's test hook);
+// kAsyncSpan: their dstCapacity — above every device address, far from wrapping when a frame's size is added
+constexpr u64 kAsyncBase = 4096, kAsyncSpan = (u64)1 << 62;
+enum AsyncVerdict : u32 { kAsyncGood = 0, kAsyncEmpty = 0xFFFFFFFFu };      // (else: the zstd error code the entry answers)
+struct AsyncEmptyFrame { u8 bytes[16]; u32 len; };
+void launch_batch_plan(const void* const* srcs, const size_t* sizes, void* const* dsts, const size_t* caps, u32 n, u64 bound, u32 emptyLen, const u8* dummy,
+                       u64* from, u64* entDst, u64* entCap, u32* len, u32* entFirst, u32* verdict, hipStream_t stream);
+void launch_batch_place_async(const ChunkMeta* meta, u32 n, const u64* entDst, const u64* entCap, const u32* verdict, AsyncEmptyFrame empty,
+                              u64* offsets, size_t* dstSizes, hipStream_t stream);
 void launch_seek_entries(const u64* offsets, const u64* total, u32 nChunks, const FrameLayout& frames, u32* entries, hipStream_t stream);
 void launch_seek_table(const u32* entries, u32 n, u8* dst, hipStream_t stream);
 // a pack (ZSTDMI_compressPack, frame.hip): a batched pass's seek-table rows per entry (entSeek[e] = the row of entry e's first frame, rows
@@ -172,8 +185,17 @@ using namespace zmi;
 #define ZERR(code) ((size_t)0 - (size_t)(code))
 static inline bool isErr(size_t c) { return c > ZERR(kErrMaxCode); }
 // No C++ exception may cross the C ABI (the caller is P/Invoke): host-side container growth is the only thing that throws here.
+// Host-side tallies of one compression context (ZSTDMI_debugHostWaits / ZSTDMI_debugDeviceAllocs): blocking waits its host code made and
+// growths of its device buffers.  Its buffers name it (DevBuf::owner); a wait is counted for the tally this thread's ABI call bound
+// (tl_waits: set by cctx_bind inside guarded(), which puts the caller's back), so that stream_wait and dev_read count without an argument.
+// beforeFree: what must happen before any of its buffers is freed (the compressor: cctx_async_drain, the wait behind an enqueued batch)
+struct HostTally { long long waits = 0, allocs = 0; void (*beforeFree)(void*) = nullptr; void* self = nullptr; };
+static thread_local long long* tl_waits = nullptr;
+static thread_local bool tl_guarded = false;
+static inline void count_wait() { if (tl_waits) ++*tl_waits; }
 template <class F> static size_t guarded(F f)
 {
+    struct Keep { long long* was = tl_waits; bool in = tl_guarded; Keep() { tl_guarded = true; } ~Keep() { tl_waits = was; tl_guarded = in; } } keep;
     try { return f(); }
     catch (const std::bad_alloc&) { return ZERR(kErrMemoryAllocation); }
     catch (...) { return ZERR(kErrGeneric); }
@@ -185,15 +207,18 @@ constexpr int kMaxStages = 24;
 
 struct DevBuf {
     void* p = nullptr; size_t cap = 0;
+    HostTally* owner = nullptr;     // (a compression context's buffers: see HostTally)
+    void drop() { if (!p) return; if (owner && owner->beforeFree) owner->beforeFree(owner->self); (void)hipFree(p); p = nullptr; cap = 0; }
     bool ensure(size_t n)
     {
         if (n <= cap) return true;
-        if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
+        if (owner) owner->allocs++;
+        drop();
         size_t want = n + (n >> 3) + 4096;
         if (hipMalloc(&p, want) != hipSuccess) { p = nullptr; if (hipMalloc(&p, n) != hipSuccess) { p = nullptr; return false; } want = n; }
         cap = want; return true;
     }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+    void release() { drop(); }
 };
 
 struct StageTimer {
@@ -268,6 +293,7 @@ static size_t copy_any(void* dst, const void* src, size_t n, hipStream_t s)
 // wait for everything enqueued on s -> 0 or generic (the failed wait's error is taken off the runtime's record)
 static size_t stream_wait(hipStream_t s)
 {
+    count_wait();
     if (hipStreamSynchronize(s) != hipSuccess) { (void)hipGetLastError(); return ZERR(kErrGeneric); }
     return 0;
 }

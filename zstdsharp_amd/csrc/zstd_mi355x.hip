@@ -104,6 +104,13 @@ struct ZSTD_CCtx_s {
     // them, and every batch is appended there (cstream_compress_sliding)
     int slidingLdm = 0;
     bool sSliding = false; int sSlideLog = 0; DevBuf sWin; size_t sWinFill = 0;
+    // ZSTDMI_CCtx_prepareBatchAsync / ZSTDMI_compressBatchAsync: what the prepare resolved (asyncPrep, valid while cctx_gen() is what it
+    // was then; paramGen: bumped by every setter, as dictGen is by every change of the dictionary in force), and the event recorded
+    // behind the last enqueued pass (asyncPending: not yet waited for).  cctx_async_drain is the one place that waits for it; every
+    // buffer of the context names `tally`, so that no growth or release frees memory an enqueued pass still uses, and counts there.
+    HostTally tally; u64 paramGen = 0;
+    struct AsyncPrep* asyncPrep = nullptr; hipEvent_t asyncEv = nullptr; bool asyncPending = false;
+    ZSTD_CCtx_s();
 };
 // History per chunk lives in LDS beside the chunk: up to 32 KiB of dictionary in front of 32 KiB chunks, or up to 60 KiB when
 // the whole input fits behind it in one chunk (small records, the usual dictionary case).
@@ -138,7 +145,29 @@ static u32 digest_index_len(const DictDigest& g)
 static u32 dict_index_len(const ZSTD_CCtx* c) { return c->dictIndex ? digest_index_len(dict_in_force(c)) : 0u; }
 
 static size_t cctx_sync_dictionary(ZSTD_CCtx* c);
-static size_t cctx_bind(ZSTD_CCtx* c) { return ctx_bind(c); }
+// (inside an ABI call's guarded(): the waits of this thread count for this context from here on, see HostTally)
+static size_t cctx_bind(ZSTD_CCtx* c) { if (c && tl_guarded) tl_waits = &c->tally.waits; return ctx_bind(c); }
+// The lifetime rule of an enqueued batch (ZSTDMI_compressBatchAsync), in one place: wait for the event behind the last enqueued pass.
+// Called before anything the pass may still read or write is freed or handed to another stream — by every DevBuf of the context
+// before it frees (HostTally::beforeFree: growth and release alike), and by ZSTD_freeCCtx, ZSTDMI_CCtx_setStream,
+// ZSTD_CCtx_loadDictionary, ZSTD_CCtx_refCDict and a digest's re-upload directly.  A later call on the same stream is ordered by the stream.
+static void cctx_async_drain(ZSTD_CCtx* c)
+{
+    if (!c->asyncPending) return;
+    c->asyncPending = false;
+    c->tally.waits++;
+    if (hipEventSynchronize(c->asyncEv) != hipSuccess) (void)hipGetLastError();
+}
+// a blocking copy, counted as the wait it is
+static hipError_t host_memcpy(void* dst, const void* src, size_t n, hipMemcpyKind kind) { count_wait(); return hipMemcpy(dst, src, n, kind); }
+static u64 cctx_gen(const ZSTD_CCtx* c) { return c->paramGen + c->dictGen; }
+ZSTD_CCtx_s::ZSTD_CCtx_s()
+{
+    tally.self = this; tally.beforeFree = [](void* self) { cctx_async_drain((ZSTD_CCtx_s*)self); };
+    for (DevBuf* b : { &seqs, &lits, &meta, &tables, &slots, &offsets, &total, &cand, &probe, &stageSrc, &stageDst, &ldmSmall, &ldmBig, &dixDist, &gatherIn, &gatherOut,
+                       &batchStage, &batchTab, &packArena, &packTab, &seekEntries, &seekSort, &pfxStage, &sfXxh, &sWin,
+                       &own.dict, &own.dictFullDev, &own.dictInfoDev, &own.dictCTabDev, &own.dictWideDev, &own.dictIdxDev }) b->owner = &tally;
+}
 
 // The parameters one compression call runs with: the context's sticky ones (ZSTD_compress2, ZSTD_compressStream2) or, for
 // ZSTD_compressCCtx, the level alone with default frame parameters and no dictionary (U/ZstdCompress.cs:5751-5776:
@@ -266,6 +295,7 @@ static size_t digest_upload(DictDigest& g, hipStream_t s, bool entropy, bool ind
 static size_t cctx_sync_dictionary(ZSTD_CCtx* c)
 {
     if (cdict_shared(c) || !c->dictDirty) return 0;
+    cctx_async_drain(c);        // (a re-upload writes what an enqueued batch may still read)
     if (c->own.dictFormatted || !c->own.dictHost.empty()) c->dictUploads++;
     const size_t e = digest_upload(c->own, c->stream, c->dictEntropy != 0, c->dictIndex != 0, c->dictIndexStrategy >= 2 || c->dictIndexChain);
     if (isErr(e) && e != ZERR(kErrDictionaryCorrupted)) return e;
@@ -454,6 +484,11 @@ static Framing resolve_framing(const ZSTD_CCtx* c, const CallParams& cp, size_t 
     return f;
 }
 
+// What ZSTDMI_CCtx_prepareBatchAsync resolved: the parameters and the framing of an entry of exactly `bound` bytes — one chunk, one
+// single-block frame —, the empty frame under those parameters, and the generation it holds for.  No device pointer is kept: the launch
+// state is derived again per call (launch_state, host arithmetic), and the buffers, which only ever grow, are asked where they are.
+struct AsyncPrep { u64 gen; u32 maxEntries; size_t bound; CallParams cp; Framing fr; AsyncEmptyFrame empty; };
+
 // What the kernels of a pass are launched with for a framing: derived in one place for the single call (compress_range) and the
 // batch (compress_entries), whose bytes must be the same.
 struct LaunchState {
@@ -538,6 +573,16 @@ static void add_stage_times(ZSTD_CCtx* c, bool& first)
     first = false;
 }
 
+// ZSTD_writeEpilogue on an empty frame: header (FCS=0, single segment) + empty raw last block [+ checksum] -> its 9 .. 13 bytes into f
+static size_t empty_frame_write(const CallParams& cp, u8* f)
+{
+    FrameHeaderSpec h = {}; h.checksum = cp.checksumFlag ? 1 : 0; h.noContentSize = cp.contentSizeFlag ? 0 : 1;
+    if (h.noContentSize && cp.windowLog >= 10) h.windowLog = (u8)cp.windowLog;     // (the window descriptor states the caller's window)
+    size_t n = frame_header_write(h, 0, f);
+    f[n++] = 1; f[n++] = 0; f[n++] = 0;
+    if (cp.checksumFlag) { f[n++] = 0x99; f[n++] = 0xE9; f[n++] = 0xD8; f[n++] = 0x51; }   // XXH64("") low 32 bits = 0x51D8E999
+    return n;
+}
 // the compress pipeline over device-resident buffers: one range of the input with one set of parameters (see compress_device)
 // paramSize: the size the parameters are resolved for — the whole range's, of which [d_src, d_src + srcSize) may be a frame-aligned
 // part (a device worker's share of the range, compress_multi): what is written for a stretch of frames depends on nothing else
@@ -547,15 +592,11 @@ static size_t compress_range(ZSTD_CCtx* c, const CallParams& cp, u8* d_dst, size
 {
     hipStream_t s = c->stream;
     c->lastRegionList = nullptr;
-    if (srcSize == 0) {     // ZSTD_writeEpilogue on an empty frame: header (FCS=0, single segment) + empty raw last block
-        FrameHeaderSpec h = {}; h.checksum = cp.checksumFlag ? 1 : 0; h.noContentSize = cp.contentSizeFlag ? 0 : 1;
-        if (h.noContentSize && cp.windowLog >= 10) h.windowLog = (u8)cp.windowLog;     // (the window descriptor states the caller's window)
-        u8 f[18 + 3 + 4]; size_t n = frame_header_write(h, 0, f);
-        f[n++] = 1; f[n++] = 0; f[n++] = 0;
-        if (cp.checksumFlag) { f[n++] = 0x99; f[n++] = 0xE9; f[n++] = 0xD8; f[n++] = 0x51; }   // XXH64("") low 32 bits = 0x51D8E999
+    if (srcSize == 0) {     // (empty_frame_write)
+        u8 f[18 + 3 + 4]; const size_t n = empty_frame_write(cp, f);
         if (dstCapacity < n) return ZERR(kErrDstSizeTooSmall);
         if (hipMemcpyAsync(d_dst, f, n, hipMemcpyHostToDevice, s) != hipSuccess) return ZERR(kErrGeneric);
-        (void)hipStreamSynchronize(s);       // (deliberately not stream_wait: a failed wait is ignored here)
+        count_wait(); (void)hipStreamSynchronize(s);       // (deliberately not stream_wait: a failed wait is ignored here)
         return n;
     }
     if (cp.useDict) { const size_t e = cctx_sync_dictionary(c); if (isErr(e)) return e; }
@@ -889,14 +930,18 @@ size_t ZSTD_freeCCtx(ZSTD_CCtx* c)
     if (!c) return 0;
     for (ZSTD_CCtx* w : c->workers) (void)ZSTD_freeCCtx(w);
     c->workers.clear();
+    if (tl_waits == &c->tally.waits) tl_waits = nullptr;
     if (c->deviceOk) {
         (void)hipSetDevice(c->device);
+        cctx_async_drain(c);        // (an enqueued batch may run on a stream that is not the context's own)
+        if (c->asyncEv) (void)hipEventDestroy(c->asyncEv);
         if (c->ownStream) (void)hipStreamSynchronize(c->ownStream);
         c->seqs.release(); c->lits.release(); c->meta.release(); c->tables.release(); c->slots.release(); c->cand.release(); c->lastRegionList = nullptr; c->dixDist.release(); c->probe.release();
         c->gatherIn.release(); c->gatherOut.release(); c->batchStage.release(); c->batchTab.release(); c->packArena.release(); c->packTab.release(); c->ldmSmall.release(); c->ldmBig.release(); c->offsets.release(); c->total.release(); c->seekEntries.release(); c->seekSort.release(); c->stageSrc.release(); c->stageDst.release(); c->pfxStage.release(); c->sfXxh.release(); c->sWin.release(); c->own.release();
         c->timer.destroy();
         if (c->ownStream) (void)hipStreamDestroy(c->ownStream);
     }
+    delete c->asyncPrep;
     delete c;
     return 0;
 }
@@ -908,6 +953,7 @@ int ZSTD_defaultCLevel(void) { return 3; }
 size_t ZSTD_CCtx_setParameter(ZSTD_CCtx* c, int param, int value)
 {
     if (!c) return ZERR(kErrGeneric);
+    c->paramGen++;
     switch (param) {
     case ZSTD_c_compressionLevel:           // clamped, 0 means default (U/ZstdCompress.cs:886-905)
         if (value < ZSTD_minCLevel()) value = ZSTD_minCLevel();
@@ -1000,7 +1046,9 @@ static size_t ZSTD_CCtx_loadDictionary_impl(ZSTD_CCtx* c, const void* dict, size
 {
     if (!c) return ZERR(kErrGeneric);
     if (!c->sIn.empty() || c->sEnding) return ZERR(kErrStageWrong);        /* not in the middle of a streaming frame session, U/ZstdCompress.cs:1273 */
+    if (tl_guarded) tl_waits = &c->tally.waits;
     c->dictGen++;
+    if (c->deviceOk && hipSetDevice(c->device) == hipSuccess) cctx_async_drain(c);
     c->pfx = nullptr; c->pfxSize = 0;       // (a pending prefix is cancelled: ZSTD_clearAllDicts)
     c->cdict = nullptr;                     // (and a referenced CDict)
     c->own.dictFormatted = false; c->own.dictFull.clear(); c->own.dictWide.clear();
@@ -1008,12 +1056,12 @@ static size_t ZSTD_CCtx_loadDictionary_impl(ZSTD_CCtx* c, const void* dict, size
     if (dictSize > (size_t)1 << 30) return ZERR(kErrParameterUnsupported);
     u8 head[8] = {};
     const bool dev = is_device_ptr(dict);
-    if (dev) { if (hipMemcpy(head, dict, dictSize < 8 ? dictSize : 8, hipMemcpyDeviceToHost) != hipSuccess) return ZERR(kErrGeneric); }
+    if (dev) { if (host_memcpy(head, dict, dictSize < 8 ? dictSize : 8, hipMemcpyDeviceToHost) != hipSuccess) return ZERR(kErrGeneric); }
     else memcpy(head, dict, dictSize < 8 ? dictSize : 8);
     if (is_formatted_dictionary(head, dictSize)) {
         // ZSTD_loadZstdDictionary, U/ZstdCompress.cs:5402-5463: dictID + repcodes + content are used (see ZSTD_CCtx_s::dictHost)
         std::vector<u8> full(dictSize);
-        if (dev) { if (hipMemcpy(full.data(), dict, dictSize, hipMemcpyDeviceToHost) != hipSuccess) return ZERR(kErrGeneric); }
+        if (dev) { if (host_memcpy(full.data(), dict, dictSize, hipMemcpyDeviceToHost) != hipSuccess) return ZERR(kErrGeneric); }
         else memcpy(full.data(), dict, dictSize);
         c->own.dictFull.swap(full); c->own.dictHost.clear(); c->own.dictFormatted = true; c->dictDirty = true;
         if (!isErr(cctx_bind(c))) return cctx_sync_dictionary(c);          // validated now when a device is there, else at first use
@@ -1022,13 +1070,13 @@ static size_t ZSTD_CCtx_loadDictionary_impl(ZSTD_CCtx* c, const void* dict, size
     const size_t keep = dictSize < kDictKeep ? dictSize : kDictKeep;
     std::vector<u8> h(dictSize < 8 ? dictSize : keep);
     const u8* tail = (const u8*)dict + (dictSize - h.size());
-    if (dev) { if (hipMemcpy(h.data(), tail, h.size(), hipMemcpyDeviceToHost) != hipSuccess) return ZERR(kErrGeneric); }
+    if (dev) { if (host_memcpy(h.data(), tail, h.size(), hipMemcpyDeviceToHost) != hipSuccess) return ZERR(kErrGeneric); }
     else memcpy(h.data(), tail, h.size());
     c->own.dictHost.swap(h);
     if (dictSize >= 8) {        // what an index would cover (ZSTDMI_CCtx_setDictIndex, before or after this load)
         std::vector<u8> wide(dictSize < dict_index_max() ? dictSize : dict_index_max());
         const u8* from = (const u8*)dict + (dictSize - wide.size());
-        if (dev) { if (hipMemcpy(wide.data(), from, wide.size(), hipMemcpyDeviceToHost) != hipSuccess) return ZERR(kErrGeneric); }
+        if (dev) { if (host_memcpy(wide.data(), from, wide.size(), hipMemcpyDeviceToHost) != hipSuccess) return ZERR(kErrGeneric); }
         else memcpy(wide.data(), from, wide.size());
         c->own.dictWide.swap(wide);
     }
@@ -1079,6 +1127,7 @@ static size_t compress_any(ZSTD_CCtx* c, const CallParams& cp, void* dst, size_t
     if (isErr(r)) return r;
     if (!dstDev) {
         if (hipMemcpyAsync(dst, d_dst, r, hipMemcpyDeviceToHost, c->stream) != hipSuccess) return ZERR(kErrGeneric);
+        count_wait();
         if (hipStreamSynchronize(c->stream) != hipSuccess) return ZERR(kErrGeneric);      // (deliberately not stream_wait: no hipGetLastError behind this wait)
     }
     return r;
@@ -1105,7 +1154,7 @@ static size_t compress_prefixed(ZSTD_CCtx* c, void* dst, size_t dstCapacity, con
     if (pfxSize <= kChunkSize && (size_t)round_tile(pfxSize) + srcSize <= kChunkSize) {
         const size_t keep = pfxSize < kDictKeep ? pfxSize : kDictKeep;
         std::vector<u8> h(keep);
-        if (hipMemcpy(h.data(), (const u8*)pfx + (pfxSize - keep), keep, hipMemcpyDefault) != hipSuccess) { (void)hipGetLastError(); return ZERR(kErrGeneric); }
+        if (host_memcpy(h.data(), (const u8*)pfx + (pfxSize - keep), keep, hipMemcpyDefault) != hipSuccess) { (void)hipGetLastError(); return ZERR(kErrGeneric); }
         c->own.dictHost.swap(h); c->own.dictFormatted = false; c->dictDirty = true; c->dictGen++;
         const size_t r = plain();
         c->own.dictHost.clear(); c->dictDirty = true; c->dictGen++;
@@ -1164,7 +1213,7 @@ static ZSTD_CDict* create_cdict(const void* dict, size_t dictSize, int level, in
     hipStream_t s = nullptr;
     try {       // (host containers may throw: nothing of a half-made CDict is left behind)
         std::vector<u8> bytes(dictSize);
-        if (dictSize && hipMemcpy(bytes.data(), dict, dictSize, hipMemcpyDefault) != hipSuccess) { (void)hipGetLastError(); ok = false; }
+        if (dictSize && host_memcpy(bytes.data(), dict, dictSize, hipMemcpyDefault) != hipSuccess) { (void)hipGetLastError(); ok = false; }
         if (ok) digest_set_bytes(cd->dg, bytes.data(), dictSize);
         // whole, on a stream of its own, waited for: every table any switch of a context can ask for
         if (ok && hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); s = nullptr; ok = false; }
@@ -1202,6 +1251,7 @@ size_t ZSTD_CCtx_refCDict(ZSTD_CCtx* c, const ZSTD_CDict* cdict)
     if (!c) return ZERR(kErrGeneric);
     if (!c->sIn.empty() || c->sEnding) return ZERR(kErrStageWrong);
     return guarded([&]() -> size_t {
+        cctx_async_drain(c);
         c->pfx = nullptr; c->pfxSize = 0;       // ZSTD_clearAllDicts: a loaded dictionary and a pending prefix are gone
         c->cdict = cdict;
         cctx_adopt_cdict(c);
@@ -1588,27 +1638,32 @@ static size_t ZSTD_compressStream2_impl(ZSTD_CCtx* c, ZSTD_outBuffer* output, ZS
 // ---------------- extensions ----------------
 int ZSTDMI_deviceCount(void) { return device_count(); }
 // (a referenced CDict is shared or copied by where the context runs: cctx_adopt_cdict)
-size_t ZSTDMI_CCtx_setDevice(ZSTD_CCtx* c, int device) { const size_t e = ctx_set_device(c, device); if (c && c->cdict) (void)guarded([&]() -> size_t { cctx_adopt_cdict(c); return 0; }); return e; }
+size_t ZSTDMI_CCtx_setDevice(ZSTD_CCtx* c, int device) { if (c) c->paramGen++; const size_t e = ctx_set_device(c, device); if (c && c->cdict) (void)guarded([&]() -> size_t { cctx_adopt_cdict(c); return 0; }); return e; }
 size_t ZSTDMI_CCtx_setDevices(ZSTD_CCtx* c, const int* devices, int n)
 {
+    if (c) c->paramGen++;
     const size_t e = ctx_set_devices(c, devices, n, ZSTD_createCCtx, ZSTD_freeCCtx);
     if (c && c->cdict) (void)guarded([&]() -> size_t { cctx_adopt_cdict(c); return 0; });
     return e;
 }
-size_t ZSTDMI_CCtx_setStream(ZSTD_CCtx* c, void* st) { return ctx_set_stream(c, st, cctx_bind); }
-size_t ZSTDMI_CCtx_setPassChunks(ZSTD_CCtx* c, unsigned chunks) { if (!c || chunks == 0 || chunks > (1u << 20)) return ZERR(kErrParameterOutOfBound); c->passChunks = chunks; return 0; }
+size_t ZSTDMI_CCtx_setStream(ZSTD_CCtx* c, void* st)
+{
+    if (c && (st ? (hipStream_t)st : c->ownStream) != c->stream) cctx_async_drain(c);     // (the new stream is not ordered behind an enqueued batch)
+    return ctx_set_stream(c, st, cctx_bind);
+}
+size_t ZSTDMI_CCtx_setPassChunks(ZSTD_CCtx* c, unsigned chunks) { if (!c || chunks == 0 || chunks > (1u << 20)) return ZERR(kErrParameterOutOfBound); c->passChunks = chunks; c->paramGen++; return 0; }
 // bytes: 0 = independent 64 KiB frames; > 0 = cross-chunk history of that many bytes per block (rounded to 4 KiB, at most 48 KiB);
 // < 0 = by level.  frameBytes: content of one multi-block frame (64 KiB .. 16 MiB), 0 = keep.
 size_t ZSTDMI_CCtx_setHistory(ZSTD_CCtx* c, int bytes, unsigned frameBytes)
 {
     if (!c || bytes > (48 << 10) || (frameBytes && (frameBytes < kChunkSize || frameBytes > (16u << 20)))) return ZERR(kErrParameterOutOfBound);
-    c->historyBytes = bytes; if (frameBytes) c->frameBytes = frameBytes; return 0;
+    c->historyBytes = bytes; if (frameBytes) c->frameBytes = frameBytes; c->paramGen++; return 0;
 }
-size_t ZSTDMI_CCtx_setSeekTable(ZSTD_CCtx* c, unsigned mode) { if (!c) return ZERR(kErrGeneric); if (mode > 1) return ZERR(kErrParameterOutOfBound); c->seekTable = (int)mode; return 0; }
+size_t ZSTDMI_CCtx_setSeekTable(ZSTD_CCtx* c, unsigned mode) { if (!c) return ZERR(kErrGeneric); if (mode > 1) return ZERR(kErrParameterOutOfBound); c->seekTable = (int)mode; c->paramGen++; return 0; }
 // (no device is touched; what the switch cannot be combined with is refused by the call that would have to do it: check_single_frame)
-size_t ZSTDMI_CCtx_setSingleFrame(ZSTD_CCtx* c, unsigned mode) { if (!c) return ZERR(kErrGeneric); if (mode > 1) return ZERR(kErrParameterOutOfBound); c->singleFrame = (int)mode; return 0; }
+size_t ZSTDMI_CCtx_setSingleFrame(ZSTD_CCtx* c, unsigned mode) { if (!c) return ZERR(kErrGeneric); if (mode > 1) return ZERR(kErrParameterOutOfBound); c->singleFrame = (int)mode; c->paramGen++; return 0; }
 // (no device is touched; where the switch takes effect: sliding_active, and what it cannot be combined with: check_single_frame)
-size_t ZSTDMI_CCtx_setSlidingLdm(ZSTD_CCtx* c, unsigned mode) { if (!c) return ZERR(kErrGeneric); if (mode > 1) return ZERR(kErrParameterOutOfBound); c->slidingLdm = (int)mode; return 0; }
+size_t ZSTDMI_CCtx_setSlidingLdm(ZSTD_CCtx* c, unsigned mode) { if (!c) return ZERR(kErrGeneric); if (mode > 1) return ZERR(kErrParameterOutOfBound); c->slidingLdm = (int)mode; c->paramGen++; return 0; }
 size_t ZSTDMI_seekTableBound(size_t srcSize) { return seek_table_bound(srcSize); }
 // (no device is touched: a loaded formatted dictionary is marked for another upload, which builds — or no longer builds — its tables)
 size_t ZSTDMI_CCtx_setDictEntropy(ZSTD_CCtx* c, unsigned mode)
@@ -1616,11 +1671,11 @@ size_t ZSTDMI_CCtx_setDictEntropy(ZSTD_CCtx* c, unsigned mode)
     if (!c) return ZERR(kErrGeneric);
     if (mode > 1) return ZERR(kErrParameterOutOfBound);
     if (c->dictEntropy != (int)mode && c->own.dictFormatted) { c->dictDirty = true; c->dictGen++; }
-    c->dictEntropy = (int)mode;
+    c->dictEntropy = (int)mode; c->paramGen++;
     return 0;
 }
 // (no device is touched: the switch is read by the next call, carry_active)
-size_t ZSTDMI_CCtx_setEntropyCarry(ZSTD_CCtx* c, unsigned mode) { if (!c) return ZERR(kErrGeneric); if (mode > 1) return ZERR(kErrParameterOutOfBound); c->entropyCarry = (int)mode; return 0; }
+size_t ZSTDMI_CCtx_setEntropyCarry(ZSTD_CCtx* c, unsigned mode) { if (!c) return ZERR(kErrGeneric); if (mode > 1) return ZERR(kErrParameterOutOfBound); c->entropyCarry = (int)mode; c->paramGen++; return 0; }
 long long ZSTDMI_debugLastCarryGroups(const ZSTD_CCtx* c)
 {
     if (!c) return -1;
@@ -1635,7 +1690,7 @@ size_t ZSTDMI_CCtx_setDictIndex(ZSTD_CCtx* c, unsigned mode)
     if (!c) return ZERR(kErrGeneric);
     if (mode > 1) return ZERR(kErrParameterOutOfBound);
     if (c->dictIndex != (int)mode && (c->own.dictFormatted || !c->own.dictWide.empty())) { c->dictDirty = true; c->dictGen++; }
-    c->dictIndex = (int)mode;
+    c->dictIndex = (int)mode; c->paramGen++;
     return 0;
 }
 // (no device is touched: with the index on, a loaded dictionary is marked for another upload, which builds — or no longer builds —
@@ -1645,7 +1700,7 @@ size_t ZSTDMI_CCtx_setDictIndexStrategy(ZSTD_CCtx* c, unsigned maxStrategy)
     if (!c) return ZERR(kErrGeneric);
     if (maxStrategy < 1 || maxStrategy > 2) return ZERR(kErrParameterOutOfBound);
     if (c->dictIndexStrategy != (int)maxStrategy && c->dictIndex && (c->own.dictFormatted || !c->own.dictWide.empty())) { c->dictDirty = true; c->dictGen++; }
-    c->dictIndexStrategy = (int)maxStrategy;
+    c->dictIndexStrategy = (int)maxStrategy; c->paramGen++;
     return 0;
 }
 // (no device is touched: with the index on, a loaded dictionary is marked for another upload, which builds — or, where
@@ -1655,7 +1710,7 @@ size_t ZSTDMI_CCtx_setDictIndexChain(ZSTD_CCtx* c, unsigned mode)
     if (!c) return ZERR(kErrGeneric);
     if (mode > 1) return ZERR(kErrParameterOutOfBound);
     if (c->dictIndexChain != (int)mode && c->dictIndex && (c->own.dictFormatted || !c->own.dictWide.empty())) { c->dictDirty = true; c->dictGen++; }
-    c->dictIndexChain = (int)mode;
+    c->dictIndexChain = (int)mode; c->paramGen++;
     return 0;
 }
 // chunks the last pass of the last compress call handed to lz_region_kernel: its work list's count, read back here
@@ -1667,12 +1722,12 @@ long long ZSTDMI_debugLastRegionChunks(const ZSTD_CCtx* c)
     int before = 0;
     if (hipGetDevice(&before) != hipSuccess || hipSetDevice(w->device) != hipSuccess) { (void)hipGetLastError(); return 0; }
     u32 count = 0;
-    if (hipStreamSynchronize(w->stream) != hipSuccess || hipMemcpy(&count, w->lastRegionList, sizeof count, hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); count = 0; }
+    if (hipStreamSynchronize(w->stream) != hipSuccess || host_memcpy(&count, w->lastRegionList, sizeof count, hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); count = 0; }
     (void)hipSetDevice(before);         // (a hook leaves the caller's current device where it was)
     return (long long)count;
 }
 long long ZSTDMI_debugDictIndexed(const ZSTD_CCtx* c) { return c ? (long long)dict_index_len(c) : -1; }
-size_t ZSTDMI_CCtx_setParser(ZSTD_CCtx* c, unsigned mode) { if (!c || mode > 1) return ZERR(kErrParameterOutOfBound); c->parser = mode; return 0; }
+size_t ZSTDMI_CCtx_setParser(ZSTD_CCtx* c, unsigned mode) { if (!c || mode > 1) return ZERR(kErrParameterOutOfBound); c->parser = mode; c->paramGen++; return 0; }
 size_t ZSTDMI_CCtx_setProfiling(ZSTD_CCtx* c, int en) { if (!c) return ZERR(kErrGeneric); c->timer.enabled = en != 0; return 0; }
 int ZSTDMI_CCtx_getStageTimes(const ZSTD_CCtx* c, float* ms, const char** names, int cap)
 {
@@ -1687,12 +1742,12 @@ size_t ZSTDMI_debugGetChunk(ZSTD_CCtx* c, size_t chunkIdx, ZSTDMI_Seq* seqs, siz
     size_t e = cctx_bind(c); if (isErr(e)) return e;
     if (chunkIdx >= c->lastChunks) return ZERR(kErrParameterOutOfBound);
     ChunkMeta m;
-    if (hipMemcpy(&m, (ChunkMeta*)c->meta.p + chunkIdx, sizeof m, hipMemcpyDeviceToHost) != hipSuccess) return ZERR(kErrGeneric);
+    if (host_memcpy(&m, (ChunkMeta*)c->meta.p + chunkIdx, sizeof m, hipMemcpyDeviceToHost) != hipSuccess) return ZERR(kErrGeneric);
     *nbSeq = m.nbSeq; *litSize = m.litSize;
     const size_t ns = m.nbSeq < seqCap ? m.nbSeq : seqCap, nl = m.litSize < litCap ? m.litSize : litCap;
-    if (ns && hipMemcpy(seqs, (Seq*)c->seqs.p + chunkIdx * kMaxSeq, ns * sizeof(Seq), hipMemcpyDeviceToHost) != hipSuccess) return ZERR(kErrGeneric);
+    if (ns && host_memcpy(seqs, (Seq*)c->seqs.p + chunkIdx * kMaxSeq, ns * sizeof(Seq), hipMemcpyDeviceToHost) != hipSuccess) return ZERR(kErrGeneric);
     const u8* litDev = m.litFromSrc ? c->lastSrc + chunkIdx * (size_t)c->lastChunkBytes : (const u8*)c->lits.p + chunkIdx * kLitStride;
-    if (nl && (!litDev || hipMemcpy(lits, litDev, nl, hipMemcpyDeviceToHost) != hipSuccess)) return ZERR(kErrGeneric);
+    if (nl && (!litDev || host_memcpy(lits, litDev, nl, hipMemcpyDeviceToHost) != hipSuccess)) return ZERR(kErrGeneric);
     return 0;
 }
 
@@ -1716,7 +1771,7 @@ size_t ZSTDMI_debugEntropyBlock(ZSTD_CCtx* c, void* dst, size_t dstCapacity, con
     if (isErr(dev_read(&m, c->meta.p, sizeof m, s))) return ZERR(kErrGeneric);
     if (m.blockType != 2) return 0;
     if (m.bodySize > dstCapacity) return ZERR(kErrDstSizeTooSmall);
-    if (hipMemcpy(dst, (u8*)c->slots.p + m.fhSize + 3, m.bodySize, hipMemcpyDeviceToHost) != hipSuccess) return ZERR(kErrGeneric);
+    if (host_memcpy(dst, (u8*)c->slots.p + m.fhSize + 3, m.bodySize, hipMemcpyDeviceToHost) != hipSuccess) return ZERR(kErrGeneric);
     c->lastChunks = 1;
     return m.bodySize;
 }
@@ -2032,7 +2087,7 @@ size_t compress_samples(ZSTD_CCtx* c, const u8* src, const u64* offs, const size
     if (isErr(e)) return e;
     if (stats) {
         std::vector<u32> h(377);
-        if (hipMemcpyAsync(h.data(), dStats.p, 377 * 4, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) { (void)hipGetLastError(); return ZERR(kErrGeneric); }
+        if (hipMemcpyAsync(h.data(), dStats.p, 377 * 4, hipMemcpyDeviceToHost, s) != hipSuccess || (count_wait(), hipStreamSynchronize(s)) != hipSuccess) { (void)hipGetLastError(); return ZERR(kErrGeneric); }
         // (deliberately not dev_read: a failed copy, too, is followed by hipGetLastError here)
         for (u32 i = 0; i < 377; i++) stats[i] += h[i];
     }
@@ -2063,6 +2118,97 @@ extern "C" size_t ZSTDMI_compressBatch(ZSTD_CCtx* c, const void* const* srcs, co
 extern "C" int ZSTDMI_debugLastBatchAlone(const ZSTD_CCtx* c) { return c ? c->lastBatchAlone : -1; }
 extern "C" long long ZSTDMI_debugLastBatchPasses(const ZSTD_CCtx* c) { return c ? c->lastBatchPasses : -1; }
 extern "C" long long ZSTDMI_debugLastBatchSetChunks(const ZSTD_CCtx* c) { return c ? c->lastBatchSetChunks : -1; }
+
+// ---------------- a batch enqueued from the device (include/zstd_mi355x.h) ----------------
+// the pass's table for n entries: from | entDst | entCap (u64) | len | entFirst[n + 1] | verdict (u32) | the byte an ineligible entry reads
+struct AsyncTab { size_t atDst, atCap, atLen, atFirst, atVerdict, atDummy, bytes; };
+static AsyncTab async_tab(u32 n)
+{
+    AsyncTab t;
+    t.atDst = (size_t)n * 8; t.atCap = t.atDst + (size_t)n * 8; t.atLen = t.atCap + (size_t)n * 8; t.atFirst = t.atLen + (size_t)n * 4;
+    t.atVerdict = t.atFirst + ((size_t)n + 1) * 4; t.atDummy = (t.atVerdict + (size_t)n * 4 + 7) & ~(size_t)7; t.bytes = t.atDummy + 8;
+    return t;
+}
+static size_t prepare_batch_async_impl(ZSTD_CCtx* c, size_t maxEntries, size_t bound)
+{
+    if (!c) return ZERR(kErrGeneric);
+    delete c->asyncPrep; c->asyncPrep = nullptr;
+    // what the one-block batched pass does not cover, as far as the host alone can tell
+    if (!bound || bound > kChunkSize || c->workers.size() > 1 || c->seekTable || c->pfx || maxEntries > batch_pass_limit(c)) return ZERR(kErrParameterUnsupported);
+    const CallParams cp = sticky_params(c);
+    size_t e = check_call_params(cp); if (isErr(e)) return e;
+    e = cctx_bind(c); if (isErr(e)) return e;
+    e = cctx_sync_dictionary(c); if (isErr(e)) return e;
+    // (a formatted dictionary's tail is known once it has been validated, so the framing is resolved behind the upload)
+    const Framing fr = resolve_framing(c, cp, bound);
+    if (bound > fr.chunkBytes || fr.frameBlocks || !entry_batched(c, cp, bound, fr, batch_pass_limit(c), call_dict_ctables(c, cp) != nullptr, false))
+        return ZERR(kErrParameterUnsupported);
+    const LaunchState ls = launch_state(c, cp, fr);
+    const u32 nCh = maxEntries ? (u32)maxEntries : 1u;
+    if (!cctx_workspace(c, nCh) || (ls.regionParse && !cctx_cand_workspace(c, nCh, ls.hcChains)) || (ls.regionParse && fr.dictIndex && !cctx_dist_workspace(c, nCh)) ||
+        !c->batchStage.ensure((u64)nCh * fr.chunkBytes + 64) || !c->batchTab.ensure(async_tab(nCh).bytes)) return ZERR(kErrMemoryAllocation);
+    if (!c->asyncEv && hipEventCreateWithFlags(&c->asyncEv, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); c->asyncEv = nullptr; return ZERR(kErrMemoryAllocation); }
+    AsyncPrep* const P = new AsyncPrep{ cctx_gen(c), (u32)maxEntries, bound, cp, fr, {} };
+    u8 f[18 + 3 + 4]; const size_t n = empty_frame_write(cp, f);
+    assert(n <= sizeof P->empty.bytes);
+    memcpy(P->empty.bytes, f, n); P->empty.len = (u32)n;
+    c->asyncPrep = P;
+    return 0;
+}
+// One pass of compress_entries between its table upload and its read-back, with the plan kernel in the place of the first and the
+// caller's column in the place of the second: kernels (and the finder's two 4-byte hipMemsetAsync) only.
+static size_t compress_batch_async_impl(ZSTD_CCtx* c, const void* const* d_srcs, const size_t* d_srcSizes, size_t n, void* const* d_dsts,
+                                        const size_t* d_dstCapacities, size_t* d_dstSizes)
+{
+    if (!c) return ZERR(kErrGeneric);
+    if (n == 0) return 0;
+    if (!d_srcs || !d_srcSizes || !d_dsts || !d_dstCapacities || !d_dstSizes) return ZERR(kErrGeneric);
+    const AsyncPrep* const P = c->asyncPrep;
+    if (!P || P->gen != cctx_gen(c) || n > P->maxEntries || (c->dictDirty && !cdict_shared(c)) || !c->deviceOk) return ZERR(kErrStageWrong);
+    size_t e = cctx_bind(c); if (isErr(e)) return e;
+    struct TimerOff { StageTimer& t; bool was; ~TimerOff() { t.enabled = was; } } timerOff{c->timer, c->timer.enabled};
+    c->timer.enabled = false;       // (stage events belong to calls that wait for them)
+    c->lastRegionList = nullptr; c->lastCarryGroups = 0; c->lastBatchAlone = 0; c->lastBatchPasses = 1; c->lastBatchSetChunks = 0; c->lastChunks = 0;
+    hipStream_t s = c->stream;
+    const Framing& fr = P->fr;
+    const LaunchState ls = launch_state(c, P->cp, fr);
+    const u32 nCh = (u32)n, cb = fr.chunkBytes;
+    const AsyncTab t = async_tab(nCh);
+    u8* const dTab = (u8*)c->batchTab.p;
+    u64* const dFrom = (u64*)dTab; u64* const dDst = (u64*)(dTab + t.atDst); u64* const dCap = (u64*)(dTab + t.atCap);
+    u32* const dLen = (u32*)(dTab + t.atLen); u32* const dFirst = (u32*)(dTab + t.atFirst); u32* const dVerdict = (u32*)(dTab + t.atVerdict);
+    const u8* stage = (const u8*)c->batchStage.p;
+    Seq* seqs = (Seq*)c->seqs.p; u8* lits = (u8*)c->lits.p; ChunkMeta* meta = (ChunkMeta*)c->meta.p;
+    HufTable* tables = (HufTable*)c->tables.p; u8* slots = (u8*)c->slots.p; u64* offsets = (u64*)c->offsets.p;
+    const u64 stagedBytes = (u64)nCh * cb;
+    launch_batch_plan(d_srcs, d_srcSizes, d_dsts, d_dstCapacities, nCh, P->bound, P->empty.len, dTab + t.atDummy, dFrom, dDst, dCap, dLen, dFirst, dVerdict, s);
+    launch_batch_stage(dFrom, dLen, (u8*)c->batchStage.p, nCh, cb, s);
+    const FrameLayout frames = layout_arith(cb, 0, stagedBytes);
+    launch_lz(pass_lz(c, ls, fr, stage, stagedBytes, nCh, nCh, frames, dLen));
+    launch_huf_build(lits, meta, tables, slots, nCh, fr.rs.rawLiterals, stage, frames, s, c->timer.hook(), ls.dct);
+    if (P->cp.checksumFlag) launch_xxh64(stage, meta, nCh, frames, s, dLen);
+    launch_seq_encode(seqs, meta, slots, nCh, ls.strategy, ls.header, 1, ls.initReps, frames, s, ls.dct);
+    launch_batch_place_async(meta, nCh, dDst, dCap, dVerdict, P->empty, offsets, d_dstSizes, s);
+    launch_huf_encode(lits, meta, tables, slots, (u8*)(uintptr_t)kAsyncBase, offsets, kAsyncSpan, nCh, stage, cb, s, ls.dct != nullptr);
+    launch_gather(stage, stagedBytes, slots, meta, offsets, (u8*)(uintptr_t)kAsyncBase, kAsyncSpan, nCh, cb, s);
+    if (hipEventRecord(c->asyncEv, s) != hipSuccess) {      // (without the event nothing may stay in flight)
+        (void)hipGetLastError();
+        return stream_wait(s);
+    }
+    c->asyncPending = true;
+    return 0;
+}
+extern "C" size_t ZSTDMI_CCtx_prepareBatchAsync(ZSTD_CCtx* c, size_t maxEntries, size_t srcSizeBound)
+{
+    return guarded([&] { return prepare_batch_async_impl(c, maxEntries, srcSizeBound); });
+}
+extern "C" size_t ZSTDMI_compressBatchAsync(ZSTD_CCtx* c, const void* const* d_srcs, const size_t* d_srcSizes, size_t n, void* const* d_dsts,
+                                            const size_t* d_dstCapacities, size_t* d_dstSizes)
+{
+    return guarded([&] { return compress_batch_async_impl(c, d_srcs, d_srcSizes, n, d_dsts, d_dstCapacities, d_dstSizes); });
+}
+extern "C" long long ZSTDMI_debugHostWaits(const ZSTD_CCtx* c) { return c ? c->tally.waits : -1; }
+extern "C" long long ZSTDMI_debugDeviceAllocs(const ZSTD_CCtx* c) { return c ? c->tally.allocs : -1; }
 
 // The batch with a CDict per entry (include/zstd_mi355x.h).  Entries that all name one CDict (or none) ARE ZSTD_CCtx_refCDict + the batch
 // above, private upload included; else compress_entries resolves per CDict, and nothing of the context's own dictionary is consulted.
