@@ -469,6 +469,65 @@ size_t ZSTDMI_compressBatchAsync(ZSTD_CCtx* cctx, const void* const* d_srcs, con
  * across ZSTDMI_compressBatchAsync. */
 long long ZSTDMI_debugHostWaits(const ZSTD_CCtx* cctx);
 long long ZSTDMI_debugDeviceAllocs(const ZSTD_CCtx* cctx);
+/* ---- the decompress counterpart: a batch decoded with no host round trip ----
+ * ZSTDMI_decompressBatch stops the host at least three times a call: to size the frame and block lists, to size the sequence records,
+ * and to read the answers.  Here the caller states limits ONCE, the prepare sizes every work buffer from them, and the async call only
+ * enqueues kernels that take their counts from device memory, over grids sized from the limits.
+ * The limits (ZSTDMI_DBatchLimits).  maxEntries, srcSizeBound and maxContent must be stated; the other three have defaults (0), which
+ * are conveniences, not measurements:
+ *   maxBlocks    = maxFrames + maxContent / 16384 covers every stream THIS library writes (its smallest non-final block is 16 KiB);
+ *                  a foreign stream may hold more, smaller blocks;
+ *   maxSequences = maxContent / 3 + 64 is exact for valid input — a sequence regenerates at least 3 bytes — and a record costs 8 bytes,
+ *                  so a caller who knows the data lowers it.
+ * ZSTDMI_batchAsyncWorkspaceD: the device bytes the prepare will ask its work buffers for under these limits (host arithmetic only;
+ * 0 for NULL or limits the prepare refuses as out of bound); monotone in every field.
+ * ZSTDMI_DCtx_prepareBatchAsync does everything that needs the host: binds the device, uploads and validates the dictionary in force
+ * (loaded, ZSTD_DCtx_refDDict, the ZSTD_d_refMultipleDDicts set) and allocates.  It returns 0, or: GENERIC (NULL context or limits);
+ * parameter_outOfBound for a zero maxEntries or maxContent, a srcSizeBound of 0 or above 4 MiB, or limits beyond the lists' index range
+ * (2^26 frames, 0xFFFFFFF0 blocks); parameter_unsupported for several device workers, a pending ZSTD_DCtx_refPrefix (which stays
+ * pending), ZSTDMI_DCtx_setLongFrames(2), and a DDict set that cannot serve a batch; init_missing, memory_allocation,
+ * dictionary_corrupted.  Refusals that need no device are answered before one is looked for.  A refused or failed prepare leaves the
+ * context without a valid one.
+ * ZSTDMI_decompressBatchAsync: all five arrays and everything they point to are DEVICE memory.  The call makes no device allocation, no
+ * host wait, no copy between host and device and no host read of the arrays; it enqueues on the context's stream
+ * (ZSTDMI_DCtx_setStream) and returns: 0 once enqueued (n == 0: 0, nothing is touched); GENERIC for a NULL context, or a NULL array with
+ * n > 0; stage_wrong if there is no valid prepare, n > maxEntries, or a parameter, the dictionary, a DDict reference or the device
+ * changed since the prepare (any setter but ZSTDMI_DCtx_setStream invalidates it, whatever value it sets: only a generation counter is
+ * compared).  Stage timing (ZSTDMI_DCtx_setProfiling) is off for the length of the call, and ZSTDMI_debugLastBatchAloneD,
+ * ZSTDMI_debugLastBatchWorkspace, ZSTDMI_debugLastDictTableBlocks and ZSTDMI_debugLastSetFrames are NOT updated by it.
+ * Per entry, d_dstSizes[i] and the bytes at d_dsts[i] are exactly what ZSTDMI_decompressBatch gives on a context with
+ * ZSTDMI_DCtx_setBatchUnsized(1), with four exceptions:
+ *   1. d_srcSizes[i] > srcSizeBound answers srcSize_wrong — and so does an error code that ZSTDMI_compressBatchAsync left in the column,
+ *      which reads as a huge size;
+ *   2. an entry refused by a limit answers workSpace_tooSmall, whatever else is wrong with it.  The rule: over the entries that pass the
+ *      header walk, in entry order, entry i is refused iff the inclusive sum over the entries 0 .. i of frames, of blocks or of
+ *      literal-scratch bytes (a frame's content size; its bound clamped to the capacity for a frame without one) exceeds maxFrames,
+ *      maxBlocks or maxContent — so every decodable entry behind a refused one is refused too.  A block whose sequence records would
+ *      end beyond maxSequences (counted over the admitted blocks in list order) fails its entry the same way;
+ *   3. frames without a content size always take the shared pass (ZSTDMI_DCtx_setBatchUnsized is not consulted);
+ *   4. every long frame takes the ordered walk; the origin path (ZSTDMI_DCtx_setLongFrames) is never chosen.  The bytes are the same.
+ * One entry's failure changes nothing of another's.  Nothing is written at or beyond d_dsts[i] + d_dstCapacities[i].
+ * The arrays, the sources, the destinations and a referenced DDict must stay valid and unchanged until the stream has passed the
+ * work.  Work is in flight when the call returns: the context waits for it by itself wherever it frees or regrows one of its buffers
+ * (ZSTD_freeDCtx, a later call that needs more room), in ZSTDMI_DCtx_setStream to another stream, ZSTD_DCtx_loadDictionary,
+ * ZSTD_DCtx_refDDict, ZSTD_DCtx_refPrefix and a dictionary's or DDict set's re-upload; a later call on the same stream is ordered by
+ * the stream.  Capturing the call into a hipGraph is neither claimed nor tested. */
+typedef struct {
+    size_t maxEntries;     /* entries per call, > 0 */
+    size_t srcSizeBound;   /* compressed bytes of one entry, 1 .. 4 MiB */
+    size_t maxContent;     /* regenerated bytes of one call, all entries together, > 0: sizes the literal scratch */
+    size_t maxFrames;      /* frames of one call; 0 = maxEntries */
+    size_t maxBlocks;      /* blocks of one call; 0 = maxFrames + maxContent / 16384 */
+    size_t maxSequences;   /* sequence records of one call; 0 = maxContent / 3 + 64 */
+} ZSTDMI_DBatchLimits;
+size_t ZSTDMI_batchAsyncWorkspaceD(const ZSTDMI_DBatchLimits* limits);
+size_t ZSTDMI_DCtx_prepareBatchAsync(ZSTD_DCtx* dctx, const ZSTDMI_DBatchLimits* limits);
+size_t ZSTDMI_decompressBatchAsync(ZSTD_DCtx* dctx, const void* const* d_srcs, const size_t* d_srcSizes, size_t n,
+                                   void* const* d_dsts, const size_t* d_dstCapacities, size_t* d_dstSizes);
+/* diagnostics, as ZSTDMI_debugHostWaits / ZSTDMI_debugDeviceAllocs: blocking waits the decoder's host code has made for this context and
+ * growths of its device buffers since it was created; -1 without a context.  Neither moves across ZSTDMI_decompressBatchAsync. */
+long long ZSTDMI_debugHostWaitsD(const ZSTD_DCtx* dctx);
+long long ZSTDMI_debugDeviceAllocsD(const ZSTD_DCtx* dctx);
 
 /* Packs: n device buffers into ONE contiguous, standard seekable stream whose frames end exactly at the entries' boundaries — the write
  * side of ZSTDMI_decompressRanges.  srcs and srcSizes are host arrays; srcs[i] and d_dst are device pointers as for ZSTDMI_compressBatch,

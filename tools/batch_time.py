@@ -15,6 +15,9 @@ python tools/batch_time.py [MiB] [--dict-entropy] [--dict-row] [--frames-rows] [
                    per 16 384 entries back to back on the context's stream: (a) until the last call has returned, (b) until a following
                    hipStreamSynchronize (torch.cuda.synchronize) has returned, and (c) the synchronous ZSTDMI_compressBatch of the same
                    entries in the same session, its final wait included.  The bytes of both are compared afterwards.
+                   Then the decode rows (ZSTDMI_decompressBatchAsync) over those frames: one ZSTDMI_DCtx_prepareBatchAsync per row with
+                   limits of 1x, 4x and 16x what the call holds, all entries in one async call per measurement, the same (a), (b), and
+                   (c) ZSTDMI_decompressBatch in the same session; every entry's size and bytes are compared afterwards.
   --unsized-rows : only the rows of ZSTDMI_DCtx_setBatchUnsized, decompression alone: text and Zipf entries of 4 KiB at level 3,
                    (a) written with content sizes, one batch call; (b) written with ZSTD_c_contentSizeFlag = 0 and the window restated as
                    the 2^19 a streaming encoder declares (each frame's bound: 128 KiB), the switch off — every entry goes alone: timed on
@@ -242,8 +245,57 @@ def async_rows():
         print(f"| text 4 KiB L{level} | {n:6d} | ratio {sum(got) / total:.3f} | (a) async calls returned {ret * 1e3:7.2f} | (b) ... and the stream drained {done * 1e3:7.2f} ({gbs(done):6.1f}) "
               f"| (c) synchronous batch {sync * 1e3:7.2f} ({gbs(sync):6.1f}) |", flush=True)
         lib.ZSTD_freeCCtx(c); lib.ZSTD_freeCCtx(cs)
-        del dst_a, dst_s
+        del dst_a
+        async_decode_rows(level, n, size, cap, src, dst_s, got)
+        del dst_s
         torch.cuda.empty_cache()
+
+
+def async_decode_rows(level, n, size, cap, src, comp, got):
+    """the decode rows of --async: the frames the synchronous compress batch has just written, all entries in ONE ZSTDMI_decompressBatchAsync
+    call per measurement, under limits of 1x, 4x and 16x what the call holds (n frames, n blocks, the content; sequence records: the
+    default maxContent / 3 + 64 of that content), against ZSTDMI_decompressBatch of the same build"""
+    idx = torch.arange(n, dtype=torch.int64, device="cuda")
+    out_a = torch.zeros(n * size, dtype=torch.uint8, device="cuda")
+    out_s = torch.zeros(n * size, dtype=torch.uint8, device="cuda")
+    srcs, dsts = comp.data_ptr() + idx * cap, out_a.data_ptr() + idx * size
+    szs = torch.tensor(list(got), dtype=torch.int64, device="cuda")
+    caps = torch.full((n,), size, dtype=torch.int64, device="cuda")
+    back = torch.empty(n, dtype=torch.int64, device="cuda")
+    gbs = lambda t: n * size / t / 1e9
+    ds = lib.ZSTD_createDCtx()
+    c_ptr, o_ptr = ptrs(comp.data_ptr(), [i * cap for i in range(n)]), ptrs(out_s.data_ptr(), [i * size for i in range(n)])
+    o_cap, back_s = sizes([size] * n), (ctypes.c_size_t * n)()
+    sync = best_of(lambda: ok(lib.ZSTDMI_decompressBatch(ds, c_ptr, got, n, o_ptr, o_cap, back_s)))
+    assert all(b == size for b in back_s) and bool(torch.equal(out_s, src[:n * size]))
+    lib.ZSTD_freeDCtx(ds)
+    for k in (1, 4, 16):
+        d = lib.ZSTD_createDCtx()
+        content = k * n * size
+        lim = z._ffi.DBatchLimits(n, cap, content, k * n, k * n, content // 3 + 64)
+        ok(lib.ZSTDMI_DCtx_prepareBatchAsync(d, ctypes.byref(lim)))
+        ok(lib.ZSTDMI_DCtx_setStream(d, torch.cuda.current_stream().cuda_stream or 1))
+        returned = [0.0]
+
+        def enqueue():
+            t0 = time.perf_counter()
+            ok(lib.ZSTDMI_decompressBatchAsync(d, srcs.data_ptr(), szs.data_ptr(), n, dsts.data_ptr(), caps.data_ptr(), back.data_ptr()))
+            returned[0] = time.perf_counter() - t0
+            torch.cuda.synchronize()
+
+        waits = lib.ZSTDMI_debugHostWaitsD(d)
+        ret, done = 1e9, 1e9
+        enqueue()
+        for _ in range(3):
+            out_a.zero_(); torch.cuda.synchronize(); t0 = time.perf_counter()
+            enqueue()
+            done = min(done, time.perf_counter() - t0); ret = min(ret, returned[0])
+        assert lib.ZSTDMI_debugHostWaitsD(d) == waits
+        assert bool((back == size).all()) and bool(torch.equal(out_a, src[:n * size]))
+        print(f"| decode text 4 KiB L{level} | {n:6d} | limits {k:2d}x ({lib.ZSTDMI_batchAsyncWorkspaceD(ctypes.byref(lim)) / MiB:8.1f} MiB) | (a) async call returned {ret * 1e3:7.2f} "
+              f"| (b) ... and the stream drained {done * 1e3:7.2f} ({gbs(done):6.1f}) | (c) synchronous batch {sync * 1e3:7.2f} ({gbs(sync):6.1f}) |", flush=True)
+        lib.ZSTD_freeDCtx(d)
+    del out_a, out_s
 
 
 if "--async" in FLAGS:

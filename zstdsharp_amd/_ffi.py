@@ -31,6 +31,12 @@ class ZSTDMI_Seq(ctypes.Structure):
     _fields_ = [("offBase", ctypes.c_uint32), ("litLength", ctypes.c_uint16), ("mlBase", ctypes.c_uint16)]
 
 
+class DBatchLimits(ctypes.Structure):
+    """ZSTDMI_DBatchLimits: what one ZSTDMI_decompressBatchAsync call may hold at most (0 in the last three = the default)."""
+    _fields_ = [("maxEntries", c_size_t), ("srcSizeBound", c_size_t), ("maxContent", c_size_t), ("maxFrames", c_size_t),
+                ("maxBlocks", c_size_t), ("maxSequences", c_size_t)]
+
+
 # name -> (restype, argtypes); every symbol include/zstd_mi355x.h declares
 SIGNATURES = {
     "ZSTD_createCCtx": (c_void_p, []),
@@ -122,6 +128,11 @@ SIGNATURES = {
     "ZSTDMI_compressBatchAsync": (c_size_t, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
     "ZSTDMI_debugHostWaits": (ctypes.c_longlong, [c_void_p]),
     "ZSTDMI_debugDeviceAllocs": (ctypes.c_longlong, [c_void_p]),
+    "ZSTDMI_batchAsyncWorkspaceD": (c_size_t, [ctypes.POINTER(DBatchLimits)]),
+    "ZSTDMI_DCtx_prepareBatchAsync": (c_size_t, [c_void_p, ctypes.POINTER(DBatchLimits)]),
+    "ZSTDMI_decompressBatchAsync": (c_size_t, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
+    "ZSTDMI_debugHostWaitsD": (ctypes.c_longlong, [c_void_p]),
+    "ZSTDMI_debugDeviceAllocsD": (ctypes.c_longlong, [c_void_p]),
     "ZSTDMI_debugLastBatchAlone": (c_int, [c_void_p]),
     "ZSTDMI_debugLastBatchPasses": (ctypes.c_longlong, [c_void_p]),
     "ZSTDMI_debugLastBatchSetChunks": (ctypes.c_longlong, [c_void_p]),

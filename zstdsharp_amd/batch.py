@@ -144,6 +144,35 @@ def compress_batch_async(compressor, srcs, sizes, dsts, caps, out_sizes=None):
     return out_sizes
 
 
+def decompress_batch_async(decompressor, srcs, sizes, dsts, caps, out_sizes=None):
+    """ZSTDMI_decompressBatchAsync after Decompressor.PrepareBatchAsync: srcs, sizes, dsts, caps are contiguous CUDA int64 tensors of n
+    entries each (pointers as integers; `sizes` may be the out_sizes tensor compress_batch_async has just written) -> out_sizes, a CUDA
+    int64 tensor: entry i's content size, or its zstd error code as a negative value (what decompress_batch raises for it; -72
+    srcSize_wrong also for a size above the prepared bound, which is what a negative size reads as; -66 workSpace_tooSmall for an entry
+    beyond a prepared limit).  The work is enqueued on torch.cuda.current_stream() and the call returns: nothing is synchronised and
+    nothing is copied to the host.  The tensors, the sources and the destinations must stay alive and unchanged until that stream has
+    passed the work.  Raises ZstdException for the whole call's error (stage_wrong: no valid PrepareBatchAsync, more entries than it
+    was prepared for, or a parameter or the dictionary changed since)."""
+    import torch
+    decompressor._ensure_not_disposed()
+    lib = decompressor._lib
+    n = sizes.numel()
+    if out_sizes is None:
+        out_sizes = torch.empty(n, dtype=torch.int64, device=sizes.device)
+    for name, t in (("srcs", srcs), ("sizes", sizes), ("dsts", dsts), ("caps", caps), ("out_sizes", out_sizes)):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int64 and t.is_contiguous() and t.numel() == n):
+            raise TypeError(f"{name}: expected a contiguous CUDA int64 tensor of {n} entries")
+    if n == 0:
+        return out_sizes
+    stream = torch.cuda.current_stream(sizes.device)
+    r = lib.ZSTDMI_DCtx_setStream(decompressor.dctx, stream.cuda_stream or _HIP_STREAM_LEGACY)
+    if not is_error(r):
+        r = lib.ZSTDMI_decompressBatchAsync(decompressor.dctx, srcs.data_ptr(), sizes.data_ptr(), n, dsts.data_ptr(), caps.data_ptr(), out_sizes.data_ptr())
+    if is_error(r):
+        raise ZstdException(get_error_code(r), lib.ZSTD_getErrorName(r).decode())
+    return out_sizes
+
+
 def compress_pack(compressor, items):
     """items as for compress_batch -> ONE seekable stream (ZSTDMI_compressPack): item i's frames as Compressor.Wrap writes them for it
     alone, one item's behind the other's, and one seek table behind the last (read_seek_table reads it).  Bytes-like items -> bytes;

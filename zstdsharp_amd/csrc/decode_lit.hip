@@ -953,21 +953,80 @@ __global__ __launch_bounds__(256) void decode_literals_sync_set_kernel(const u8*
 //   compact  (4 lanes per block, 2 KiB table + pair table): 64 blocks per CU; a round of 16 384 blocks takes 1.8-2.7 ms;
 //   selfsync (256 lanes per block): 0.15 ms up to 256 blocks, 0.25 ms per 1000 blocks beyond.
 // mode: 0 = choose by block count, 1 = serial, 2 = self-synchronising, 3 = compact.
+static u32 literal_decoder_for(u32 nBlocks)
+{
+    static int cus[64] = {};                     // per device
+    int dev = 0; (void)hipGetDevice(&dev);
+    if (!cus[dev & 63]) { int n = 0; (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev); cus[dev & 63] = n > 0 ? n : 256; }
+    const u32 roundS = (u32)cus[dev & 63] * 32u, roundC = roundS * 2u;
+    if (nBlocks <= roundS * 3u / 4u) return 2;
+    const float tS = (float)((nBlocks + roundS - 1) / roundS) * 1.7f, tC = (float)((nBlocks + roundC - 1) / roundC) * 2.7f;
+    return tC < tS ? 3u : 1u;
+}
+
+// The four bodies with the number of blocks from the status words (ZSTDMI_decompressBatchAsync): grids over the caller's limit, the
+// workgroups (quads) beyond the call's blocks leave at once.  slowFlags is written and read below the call's count only.
+template <bool kSet>
+__global__ __launch_bounds__(64) void decode_literals_slow_d_kernel(const u8* __restrict__ src, u8* __restrict__ out, u8* __restrict__ scratch,
+                                                                    const FrameDesc* __restrict__ frames, const BlockDesc* __restrict__ blocks,
+                                                                    u32* __restrict__ status, const u8* __restrict__ slowFlags, const u8* __restrict__ dictFull,
+                                                                    const DictInfo* __restrict__ di, const DictSlot* __restrict__ slots)
+{
+    decode_literals_slow_body<kSet>(src, out, scratch, frames, blocks, status[kStBlocks], status, slowFlags, dictFull, di, slots);
+}
+template <bool kSet>
+__global__ __launch_bounds__(64) void decode_literals_compact_d_kernel(const u8* __restrict__ src, u8* __restrict__ out, u8* __restrict__ scratch,
+                                                                       const FrameDesc* __restrict__ frames, const BlockDesc* __restrict__ blocks,
+                                                                       u32* __restrict__ status, u8* __restrict__ slowFlags, const u8* __restrict__ dictFull,
+                                                                       const DictInfo* __restrict__ di, const DictSlot* __restrict__ slots)
+{
+    decode_literals_compact_body<kSet>(src, out, scratch, frames, blocks, status[kStBlocks], status, slowFlags, dictFull, di, slots);
+}
+template <bool kSet>
+__global__ __launch_bounds__(64) void decode_literals_d_kernel(const u8* __restrict__ src, u8* __restrict__ out, u8* __restrict__ scratch,
+                                                               const FrameDesc* __restrict__ frames, const BlockDesc* __restrict__ blocks,
+                                                               u32* __restrict__ status, u8* __restrict__ slowFlags, const u8* __restrict__ dictFull,
+                                                               const DictInfo* __restrict__ di, const DictSlot* __restrict__ slots)
+{
+    decode_literals_body<kSet>(src, out, scratch, frames, blocks, status[kStBlocks], status, slowFlags, dictFull, di, slots);
+}
+template <bool kSet>
+__global__ __launch_bounds__(256) void decode_literals_sync_d_kernel(const u8* __restrict__ src, u8* __restrict__ out, u8* __restrict__ scratch,
+                                                                     const FrameDesc* __restrict__ frames, const BlockDesc* __restrict__ blocks,
+                                                                     u32* __restrict__ status, const u8* __restrict__ dictFull, const DictInfo* __restrict__ di,
+                                                                     const DictSlot* __restrict__ slots)
+{
+    decode_literals_sync_body<kSet>(src, out, scratch, frames, blocks, status[kStBlocks], status, dictFull, di, slots);
+}
+template <bool kSet>
+static void launch_decode_literals_dev(const u8* src, u8* out, u8* scratch, const FrameDesc* frames, const BlockDesc* blocks, u32 capBlocks, u32* status,
+                                       u8* slowFlags, u32 mode, const u8* dictFull, const DictInfo* di, hipStream_t stream, const DictSlot* slots)
+{
+    if (mode == 2) {
+        static bool attrSet[64] = {};               // per device
+        int dev = 0; (void)hipGetDevice(&dev);
+        if (!attrSet[dev & 63]) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(decode_literals_sync_d_kernel<kSet>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(SyncLds)); attrSet[dev & 63] = true; }
+        hipLaunchKernelGGL(decode_literals_sync_d_kernel<kSet>, dim3(capBlocks), dim3(256), sizeof(SyncLds), stream, src, out, scratch, frames, blocks, status, dictFull, di, slots);
+        return;
+    }
+    if (mode == 3) hipLaunchKernelGGL(decode_literals_compact_d_kernel<kSet>, dim3((capBlocks + kQuadsC - 1) / kQuadsC), dim3(64), 0, stream, src, out, scratch, frames, blocks, status, slowFlags, dictFull, di, slots);
+    else           hipLaunchKernelGGL(decode_literals_d_kernel<kSet>, dim3((capBlocks + kQuads - 1) / kQuads), dim3(64), 0, stream, src, out, scratch, frames, blocks, status, slowFlags, dictFull, di, slots);
+    hipLaunchKernelGGL(decode_literals_slow_d_kernel<kSet>, dim3(capBlocks), dim3(64), 0, stream, src, out, scratch, frames, blocks, status, (const u8*)slowFlags, dictFull, di, slots);
+}
+// mode 0: by the caller's limit for the blocks — the grid's size, the only count the host has
+void launch_decode_literals_d(const u8* src, u8* out, u8* scratch, const FrameDesc* frames, const BlockDesc* blocks, u32 capBlocks, u32* status,
+                              u8* slowFlags, u32 mode, const u8* dictFull, const DictInfo* di, hipStream_t stream, const DictSlot* slots)
+{
+    if (mode == 0) mode = literal_decoder_for(capBlocks);
+    if (slots) launch_decode_literals_dev<true>(src, out, scratch, frames, blocks, capBlocks, status, slowFlags, mode, nullptr, nullptr, stream, slots);
+    else launch_decode_literals_dev<false>(src, out, scratch, frames, blocks, capBlocks, status, slowFlags, mode, dictFull, di, stream, nullptr);
+}
+
 void launch_decode_literals(const u8* src, u8* out, u8* scratch, const FrameDesc* frames, const BlockDesc* blocks, u32 nBlocks, u32* status,
                             u8* slowFlags, u32 mode, const u8* dictFull, const DictInfo* di, hipStream_t stream, StageHook hook,
                             const DictSlot* slots)
 {
-    if (mode == 0) {
-        static int cus[64] = {};                     // per device
-        int dev = 0; (void)hipGetDevice(&dev);
-        if (!cus[dev & 63]) { int n = 0; (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev); cus[dev & 63] = n > 0 ? n : 256; }
-        const u32 roundS = (u32)cus[dev & 63] * 32u, roundC = roundS * 2u;
-        if (nBlocks <= roundS * 3u / 4u) mode = 2;
-        else {
-            const float tS = (float)((nBlocks + roundS - 1) / roundS) * 1.7f, tC = (float)((nBlocks + roundC - 1) / roundC) * 2.7f;
-            mode = tC < tS ? 3u : 1u;
-        }
-    }
+    if (mode == 0) mode = literal_decoder_for(nBlocks);
     if (mode == 2) {
         static bool attrSet[64] = {};               // per device
         int dev = 0; (void)hipGetDevice(&dev);

@@ -460,6 +460,35 @@ __global__ __launch_bounds__(256) void seq_decode_set_kernel(const u8* __restric
     seq_decode_body<true, true>(src, frames, blocks, nBlocks, recs, status, nullptr, nullptr, nullptr, slots);
 }
 
+// The three instances again with the number of blocks from the status words (ZSTDMI_decompressBatchAsync: the grid covers the caller's
+// limit, the workgroups beyond the call's blocks find no block and leave).  recs holds as many records as the caller's limit for them:
+// seq_scan's cap instance has failed every block whose records would end beyond it, and a failed block decodes none.
+__global__ __launch_bounds__(256) void seq_decode_d_kernel(const u8* __restrict__ src, const FrameDesc* __restrict__ frames, BlockDesc* __restrict__ blocks,
+                                                           SeqRec* __restrict__ recs, u32* __restrict__ status,
+                                                           const u8* __restrict__ dictFull, const DictInfo* __restrict__ di)
+{
+    seq_decode_body<false>(src, frames, blocks, status[kStBlocks], recs, status, dictFull, di, nullptr);
+}
+__global__ __launch_bounds__(256) void seq_decode_ready_d_kernel(const u8* __restrict__ src, const FrameDesc* __restrict__ frames, BlockDesc* __restrict__ blocks,
+                                                                 SeqRec* __restrict__ recs, u32* __restrict__ status,
+                                                                 const u8* __restrict__ dictFull, const DictInfo* __restrict__ di, const u32* __restrict__ dictTabs)
+{
+    seq_decode_body<true>(src, frames, blocks, status[kStBlocks], recs, status, dictFull, di, dictTabs);
+}
+__global__ __launch_bounds__(256) void seq_decode_set_d_kernel(const u8* __restrict__ src, const FrameDesc* __restrict__ frames, BlockDesc* __restrict__ blocks,
+                                                               SeqRec* __restrict__ recs, u32* __restrict__ status, const DictSlot* __restrict__ slots)
+{
+    seq_decode_body<true, true>(src, frames, blocks, status[kStBlocks], recs, status, nullptr, nullptr, nullptr, slots);
+}
+void launch_seq_decode_d(const u8* src, const FrameDesc* frames, BlockDesc* blocks, u32 capBlocks, SeqRec* recs, u32* status,
+                         const u8* dictFull, const DictInfo* di, const u32* dictTabs, hipStream_t stream, const DictSlot* slots)
+{
+    const dim3 grid((capBlocks + kPack - 1) / kPack);
+    if (slots) hipLaunchKernelGGL(seq_decode_set_d_kernel, grid, dim3(256), 0, stream, src, frames, blocks, recs, status, slots);
+    else if (dictTabs) hipLaunchKernelGGL(seq_decode_ready_d_kernel, grid, dim3(256), 0, stream, src, frames, blocks, recs, status, dictFull, di, dictTabs);
+    else          hipLaunchKernelGGL(seq_decode_d_kernel, grid, dim3(256), 0, stream, src, frames, blocks, recs, status, dictFull, di);
+}
+
 void launch_seq_decode(const u8* src, const FrameDesc* frames, BlockDesc* blocks, u32 nBlocks, SeqRec* recs, u32* status,
                        const u8* dictFull, const DictInfo* di, const u32* dictTabs, hipStream_t stream, const DictSlot* slots)
 {
@@ -499,12 +528,14 @@ void launch_dict_seq_tables(const u8* dictFull, const DictInfo* di, u32* tabs, h
 // ------------------------------------------------------------------------------------------------
 // place_literals: everything that is not a match goes to its final place; one wave per block
 // ------------------------------------------------------------------------------------------------
+// (kDev: list_count, zmi_decode.h — the kernel itself is the template, so that kDev = false stays the kernel it always was)
+template <bool kDev = false>
 __global__ __launch_bounds__(64) void place_literals_kernel(const u8* __restrict__ src, u8* __restrict__ out, const u8* __restrict__ scratch,
                                                             const FrameDesc* __restrict__ frames, const BlockDesc* __restrict__ blocks, u32 nBlocks,
                                                             const SeqRec* __restrict__ recs, const u32* __restrict__ status)
 {
     const u32 bi = blockIdx.x, lane = threadIdx.x;
-    if (bi >= nBlocks || status[kStErr]) return;
+    if (bi >= list_count<kDev>(nBlocks, status, kStBlocks) || status[kStErr]) return;
     const BlockDesc& B = blocks[bi];
     const FrameDesc& F = frames[B.frame];
     if (F.bad || B.err) return;
@@ -589,7 +620,12 @@ __global__ __launch_bounds__(64) void place_literals_kernel(const u8* __restrict
 void launch_place_literals(const u8* src, u8* out, const u8* scratch, const FrameDesc* frames, const BlockDesc* blocks, u32 nBlocks,
                            const SeqRec* recs, const u32* status, hipStream_t stream)
 {
-    hipLaunchKernelGGL(place_literals_kernel, dim3(nBlocks), dim3(64), 0, stream, src, out, scratch, frames, blocks, nBlocks, recs, status);
+    hipLaunchKernelGGL(place_literals_kernel<>, dim3(nBlocks), dim3(64), 0, stream, src, out, scratch, frames, blocks, nBlocks, recs, status);
+}
+void launch_place_literals_d(const u8* src, u8* out, const u8* scratch, const FrameDesc* frames, const BlockDesc* blocks, u32 capBlocks,
+                             const SeqRec* recs, const u32* status, hipStream_t stream)
+{
+    hipLaunchKernelGGL(place_literals_kernel<true>, dim3(capBlocks), dim3(64), 0, stream, src, out, scratch, frames, blocks, 0u, recs, status);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -600,13 +636,14 @@ void launch_place_literals(const u8* src, u8* out, const u8* scratch, const Fram
 // no longer per launch.  kSet = false is the kernel as it always was.  (The kernels themselves are the templates, not wrappers around
 // an inlined body: inlining turns the arguments' __restrict__ into scoped metadata, and the register allocation of the parent's
 // instances moved with it.)
-template <bool kSet>
+// kDev (ZSTDMI_decompressBatchAsync): the number of frames comes from the status words (list_count, zmi_decode.h)
+template <bool kSet, bool kDev = false>
 __global__ __launch_bounds__(64) void exec_matches_kernel(const u8* __restrict__ src, u8* __restrict__ out, const FrameDesc* __restrict__ frames,
                                                           const BlockDesc* __restrict__ blocks, u32 nFrames, const SeqRec* __restrict__ recs,
                                                           u32* __restrict__ status, const u8* __restrict__ dictArg, const u32 dictSizeArg)
 {
     const u32 f = blockIdx.x, lane = threadIdx.x;
-    if (f >= nFrames || status[kStErr]) return;
+    if (f >= list_count<kDev>(nFrames, status, kStFrames) || status[kStErr]) return;
     const FrameDesc& F = frames[f];
     if (F.bad || !(F.hasSeq || F.checksum)) return;
     const u8* __restrict__ dict = dictArg; u32 dictSize = dictSizeArg;
@@ -758,7 +795,7 @@ __global__ __launch_bounds__(64) void exec_matches_kernel(const u8* __restrict__
 // touches (an index interval, found by binary search over the batch's bounds in LDS), a round runs every match whose interval is
 // complete.  The done bits are double-buffered by round parity, so one barrier per round is enough.
 // ------------------------------------------------------------------------------------------------
-template <int W, bool kSet = false>
+template <int W, bool kSet = false, bool kDev = false>
 __global__ __launch_bounds__(64 * W) void exec_matches_wide_kernel(const u8* __restrict__ src, u8* __restrict__ out, const FrameDesc* __restrict__ frames,
                                                                    const BlockDesc* __restrict__ blocks, u32 nFrames, const SeqRec* __restrict__ recs,
                                                                    u32* __restrict__ status, const u8* __restrict__ dictArg, const u32 dictSizeArg)
@@ -769,7 +806,7 @@ __global__ __launch_bounds__(64 * W) void exec_matches_wide_kernel(const u8* __r
     __shared__ u32 waveSum[W];
     __shared__ u32 errFlag;
     const u32 f = blockIdx.x, tid = threadIdx.x, lane = tid & 63u, wave = uniform(tid >> 6);
-    if (f >= nFrames || status[kStErr]) return;
+    if (f >= list_count<kDev>(nFrames, status, kStFrames) || status[kStErr]) return;
     const FrameDesc& F = frames[f];
     if (F.bad || !(F.hasSeq || F.checksum)) return;
     const u8* __restrict__ dict = dictArg; u32 dictSize = dictSizeArg;
@@ -951,6 +988,26 @@ void launch_exec_matches(const u8* src, u8* out, const FrameDesc* frames, const 
     // dict: a raw-content dictionary (or a formatted one's content) = history in front of EVERY frame (ZSTD_refDictContent,
     // U/ZstdDecompress.cs:1758-1771); may be null
     hipLaunchKernelGGL(exec_matches_kernel<false>, dim3(nFrames), dim3(64), 0, stream, src, out, frames, blocks, nFrames, recs, status, dict, dict ? dictSize : 0u);
+}
+// the same instances with the number of frames from the status words, over a grid of the caller's limit (ZSTDMI_decompressBatchAsync)
+template <bool kSet>
+static void launch_exec_matches_dev(const u8* src, u8* out, const FrameDesc* frames, const BlockDesc* blocks, u32 capFrames, const SeqRec* recs, u32* status,
+                                    const u8* dict, u32 ds, hipStream_t stream, int wide)
+{
+    switch (wide) {
+    case 16: hipLaunchKernelGGL((exec_matches_wide_kernel<16, kSet, true>), dim3(capFrames), dim3(1024), 0, stream, src, out, frames, blocks, 0u, recs, status, dict, ds); return;
+    case 8:  hipLaunchKernelGGL((exec_matches_wide_kernel<8, kSet, true>),  dim3(capFrames), dim3(512),  0, stream, src, out, frames, blocks, 0u, recs, status, dict, ds); return;
+    case 4:  hipLaunchKernelGGL((exec_matches_wide_kernel<4, kSet, true>),  dim3(capFrames), dim3(256),  0, stream, src, out, frames, blocks, 0u, recs, status, dict, ds); return;
+    case 2:  hipLaunchKernelGGL((exec_matches_wide_kernel<2, kSet, true>),  dim3(capFrames), dim3(128),  0, stream, src, out, frames, blocks, 0u, recs, status, dict, ds); return;
+    default: break;
+    }
+    hipLaunchKernelGGL((exec_matches_kernel<kSet, true>), dim3(capFrames), dim3(64), 0, stream, src, out, frames, blocks, 0u, recs, status, dict, ds);
+}
+void launch_exec_matches_d(const u8* src, u8* out, const FrameDesc* frames, const BlockDesc* blocks, u32 capFrames, const SeqRec* recs, u32* status,
+                           const u8* dict, u32 dictSize, hipStream_t stream, int wide, const DictSlot* slots)
+{
+    if (slots) launch_exec_matches_dev<true>(src, out, frames, blocks, capFrames, recs, status, reinterpret_cast<const u8*>(slots), 0u, stream, wide);
+    else launch_exec_matches_dev<false>(src, out, frames, blocks, capFrames, recs, status, dict, dict ? dictSize : 0u, stream, wide);
 }
 
 } // namespace zmi

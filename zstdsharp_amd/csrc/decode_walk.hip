@@ -430,11 +430,20 @@ __global__ __launch_bounds__(64) void batch_walk_count_open_kernel(const u8* __r
 
 // scan (single workgroup): every decoded entry's first frame, first block and literal-scratch offset; the totals go to the status
 // words the single call's walk fills (a total beyond the lists' index range: memory_allocation for the whole call)
+// kCap (ZSTDMI_decompressBatchAsync: the work buffers were sized once, from the caller's limits in the status words kStCap*): entry i is
+// refused — workSpace_tooSmall, nothing of it in the lists — iff the INCLUSIVE sum over the entries 0 .. i of frames, blocks or
+// literal-scratch bytes exceeds its limit.  The sums run over every entry the walk marked kBatchDecode, refused ones included, so every
+// decodable entry behind a refused one is refused too, the admitted ones are a prefix whose places are the exclusive sums as always,
+// and the counts filed are the largest inclusive sums inside the limits.  (The kernel itself is the template: kCap = false is the kernel
+// as it always was, argument list included — which is why the limits ride in the status words.)
+template <bool kCap = false>
 __global__ __launch_bounds__(256) void batch_scan_kernel(BatchEntryOut* __restrict__ out, u32 nEntries, u32* __restrict__ status)
 {
     __shared__ u64 shF[4], shB[4], shC[4];
     const u32 tid = threadIdx.x, lane = lane_id(), wave = wave_id();
     u64 carryF = 0, carryB = 0, carryC = 0;
+    u64 capF = 0, capB = 0, capC = 0, admF = 0, admB = 0, admC = 0;
+    if constexpr (kCap) { capF = status[kStCapFrames]; capB = status[kStCapBlocks]; capC = (u64)status[kStCapContentLo] | ((u64)status[kStCapContentHi] << 32); }
     for (u32 base = 0; base < nEntries; base += 256) {
         const u32 i = base + tid;
         u64 f = 0, b = 0, c = 0;
@@ -452,7 +461,24 @@ __global__ __launch_bounds__(256) void batch_scan_kernel(BatchEntryOut* __restri
         if (i < nEntries) { out[i].firstFrame = (u32)(bf + fi - f); out[i].firstBlock = (u32)(bb + bi - b); out[i].scratchOff = bc + ci - c; }
         carryF += af; carryB += ab; carryC += ac;
         __syncthreads();
+        if constexpr (kCap) {
+            const u64 inF = bf + fi, inB = bb + bi, inC = bc + ci;
+            const bool within = inF <= capF && inB <= capB && inC <= capC;
+            if (!within && i < nEntries && out[i].state == kBatchDecode) { out[i].state = kBatchDone; out[i].open = 0; out[i].result = (u64)0 - (u64)kErrWorkSpaceTooSmall; }
+            // the largest inclusive sums inside the limits (each sum is monotone in the entry order): through the three arrays once more
+            u64 mF = within ? inF : 0, mB = within ? inB : 0, mC = within ? inC : 0;
+#pragma unroll
+            for (int d = 1; d < 64; d <<= 1) {
+                const u64 tf = __shfl_xor(mF, d), tb = __shfl_xor(mB, d), tc = __shfl_xor(mC, d);
+                mF = tf > mF ? tf : mF; mB = tb > mB ? tb : mB; mC = tc > mC ? tc : mC;
+            }
+            if (lane == 0) { shF[wave] = mF; shB[wave] = mB; shC[wave] = mC; }
+            __syncthreads();
+            for (u32 w = 0; w < 4; ++w) { admF = shF[w] > admF ? shF[w] : admF; admB = shB[w] > admB ? shB[w] : admB; admC = shC[w] > admC ? shC[w] : admC; }
+            __syncthreads();
+        }
     }
+    if constexpr (kCap) { carryF = admF; carryB = admB; carryC = admC; }
     if (tid == 0) {
         const bool tooMany = carryF > (1u << 26) || carryB > 0xFFFFFFF0ull;
         status[kStFrames] = tooMany ? 0u : (u32)carryF; status[kStBlocks] = tooMany ? 0u : (u32)carryB; status[kStErr] = tooMany ? (u32)kErrMemoryAllocation : 0u;
@@ -572,13 +598,83 @@ __global__ __launch_bounds__(64) void batch_fold_kernel(BatchEntryOut* __restric
 }
 
 void launch_batch_walk_count(const u8* src, const BatchEntryIn* in, BatchEntryOut* out, u32 nEntries, u32 dictID, u64 aloneAbove, u32* status, hipStream_t stream,
-                             const DictSlot* slots, u32 nSet, bool open)
+                             const DictSlot* slots, u32 nSet, bool open, bool caps)
 {
     if (open && slots) hipLaunchKernelGGL(batch_walk_count_open_kernel<true>, dim3((nEntries + 63) / 64), dim3(64), 0, stream, src, in, out, nEntries, 0u, aloneAbove, slots, nSet, status);
     else if (open) hipLaunchKernelGGL(batch_walk_count_open_kernel<false>, dim3((nEntries + 63) / 64), dim3(64), 0, stream, src, in, out, nEntries, dictID, aloneAbove, (const DictSlot*)nullptr, 0u, status);
     else if (slots) hipLaunchKernelGGL(batch_walk_count_set_kernel, dim3((nEntries + 63) / 64), dim3(64), 0, stream, src, in, out, nEntries, aloneAbove, slots, nSet, status);
     else hipLaunchKernelGGL(batch_walk_count_kernel, dim3((nEntries + 63) / 64), dim3(64), 0, stream, src, in, out, nEntries, dictID, aloneAbove);
-    hipLaunchKernelGGL(batch_scan_kernel, dim3(1), dim3(256), 0, stream, out, nEntries, status);
+    if (caps) hipLaunchKernelGGL(batch_scan_kernel<true>, dim3(1), dim3(256), 0, stream, out, nEntries, status);
+    else hipLaunchKernelGGL(batch_scan_kernel<>, dim3(1), dim3(256), 0, stream, out, nEntries, status);
+}
+
+// ------------------------------------------------------------------------------------------------
+// a batch enqueued from the device (ZSTDMI_decompressBatchAsync): what the host's loops over the entries and its small
+// host -> device copies do in ZSTDMI_decompressBatch, as kernels
+// ------------------------------------------------------------------------------------------------
+// plan, one lane per entry: the caller's four arrays -> BatchEntryIn.  The bases are constants: sources and destinations are offsets
+// from kAsyncBase (zmi_host.h; no decoder kernel treats a null base specially, but a base that is a valid non-null constant keeps
+// every `base + offset` an ordinary address computation), so an offset is the device address minus kAsyncBase.  An entry that never
+// reaches the walk gets its verdict here, in decompress_batch_impl's order — a size above `bound` (which includes an error code another
+// call left in the sizes column), then a size without a source, both srcSize_wrong — and walks as an empty entry.  A null destination
+// has no room, as in the host's loop.
+__global__ __launch_bounds__(64) void batch_plan_d_kernel(const void* const* __restrict__ srcs, const size_t* __restrict__ sizes, void* const* __restrict__ dsts,
+                                                          const size_t* __restrict__ caps, u32 n, u64 bound, BatchEntryIn* __restrict__ in, u32* __restrict__ verdict)
+{
+    const u32 e = blockIdx.x * 64 + threadIdx.x;
+    if (e >= n) return;
+    const u64 src = (u64)(uintptr_t)srcs[e], size = (u64)sizes[e], dst = (u64)(uintptr_t)dsts[e], cap = (u64)caps[e];
+    const u32 v = (size > bound || (size && !src)) ? (u32)kErrSrcSizeWrong : 0u;
+    const bool walk = !v && size != 0;
+    BatchEntryIn E;
+    E.srcOff = walk ? src - kAsyncBase : 0; E.srcSize = walk ? size : 0;
+    E.dstOff = dst ? dst - kAsyncBase : 0; E.dstCap = dst ? cap : 0;
+    in[e] = E; verdict[e] = v;
+}
+// init, one wave: the status words as status_reset leaves them, and what the host copies into them behind it: the block keys' address,
+// the literal rooms' address and the dump area's offset, the caller's limits
+__global__ __launch_bounds__(64) void batch_init_d_kernel(u32* __restrict__ status, u64 blockKeys, u64 rooms, u64 dumpOff, u32 capFrames, u32 capBlocks, u64 capContent, u64 capSeq)
+{
+    for (u32 w = threadIdx.x; w < kStWords; w += 64) {
+        u32 v = 0;
+        switch (w) {
+        case kStErrKeyLo: case kStErrKeyHi: v = 0xFFFFFFFFu; break;
+        case kStBlockKeysLo: v = (u32)blockKeys; break;
+        case kStBlockKeysHi: v = (u32)(blockKeys >> 32); break;
+        case kStRoomLo: v = (u32)rooms; break;
+        case kStRoomHi: v = (u32)(rooms >> 32); break;
+        case kStDumpLo: v = (u32)dumpOff; break;
+        case kStDumpHi: v = (u32)(dumpOff >> 32); break;
+        case kStCapFrames: v = capFrames; break;
+        case kStCapBlocks: v = capBlocks; break;
+        case kStCapContentLo: v = (u32)capContent; break;
+        case kStCapContentHi: v = (u32)(capContent >> 32); break;
+        case kStCapSeqLo: v = (u32)capSeq; break;
+        case kStCapSeqHi: v = (u32)(capSeq >> 32); break;
+        default: break;
+        }
+        status[w] = v;
+    }
+}
+// finish, one lane per entry: the caller's sizes column from the plan's verdict or the entry's answer
+__global__ __launch_bounds__(64) void batch_finish_d_kernel(const BatchEntryOut* __restrict__ out, const u32* __restrict__ verdict, u32 n, size_t* __restrict__ dstSizes)
+{
+    const u32 e = blockIdx.x * 64 + threadIdx.x;
+    if (e >= n) return;
+    const u32 v = verdict[e];
+    dstSizes[e] = v ? (size_t)((u64)0 - (u64)v) : (size_t)out[e].result;
+}
+void launch_batch_plan_d(const void* const* srcs, const size_t* sizes, void* const* dsts, const size_t* caps, u32 n, u64 bound, BatchEntryIn* in, u32* verdict, hipStream_t stream)
+{
+    hipLaunchKernelGGL(batch_plan_d_kernel, dim3((n + 63) / 64), dim3(64), 0, stream, srcs, sizes, dsts, caps, n, bound, in, verdict);
+}
+void launch_batch_init_d(u32* status, const u64* blockKeys, const u64* rooms, u64 dumpOff, const BatchLimitsD& lim, hipStream_t stream)
+{
+    hipLaunchKernelGGL(batch_init_d_kernel, dim3(1), dim3(64), 0, stream, status, (u64)(uintptr_t)blockKeys, (u64)(uintptr_t)rooms, dumpOff, lim.frames, lim.blocks, lim.content, lim.sequences);
+}
+void launch_batch_finish_d(const BatchEntryOut* out, const u32* verdict, u32 n, size_t* dstSizes, hipStream_t stream)
+{
+    hipLaunchKernelGGL(batch_finish_d_kernel, dim3((n + 63) / 64), dim3(64), 0, stream, out, verdict, n, dstSizes);
 }
 void launch_batch_walk_emit(const u8* src, const BatchEntryIn* in, const BatchEntryOut* out, u32 nEntries, FrameDesc* frames, BlockDesc* blocks, hipStream_t stream,
                             const DictSlot* slots, u32 nSet, u64* rooms)
@@ -777,10 +873,12 @@ void launch_frame_walk_serial(const u8* src, u64 srcSize, FrameDesc* frames, Blo
 // ------------------------------------------------------------------------------------------------
 // block_parse: the two section headers of every compressed block, one lane per block
 // ------------------------------------------------------------------------------------------------
+// (kDev: list_count, zmi_decode.h — the kernel itself is the template, so that kDev = false stays the kernel it always was)
+template <bool kDev = false>
 __global__ __launch_bounds__(256) void block_parse_kernel(const u8* __restrict__ src, BlockDesc* __restrict__ blocks, u32 nBlocks, u32* __restrict__ status)
 {
     const u32 bi = blockIdx.x * 256 + threadIdx.x;
-    if (bi >= nBlocks) return;
+    if (bi >= list_count<kDev>(nBlocks, status, kStBlocks)) return;
     BlockDesc& B = blocks[bi];
     if (B.type != 2) return;
     const u32 bsz = B.bsz;
@@ -846,12 +944,12 @@ __device__ __forceinline__ const u64* lit_rooms(const u32* __restrict__ status)
 {
     return reinterpret_cast<const u64*>((uintptr_t)((u64)status[kStRoomLo] | ((u64)status[kStRoomHi] << 32)));
 }
-template <bool kSet, bool kOpen = false>
+template <bool kSet, bool kOpen = false, bool kDev = false>
 __global__ __launch_bounds__(64) void block_link_small_kernel(FrameDesc* __restrict__ frames, BlockDesc* __restrict__ blocks, u32 nFrames, u32 haveDict,
                                                               u32 earlyLiterals, u32* __restrict__ status, const DictSlot* __restrict__ slots)
 {
     const u32 f = blockIdx.x * 64 + threadIdx.x;
-    if (f >= nFrames) return;
+    if (f >= list_count<kDev>(nFrames, status, kStFrames)) return;
     FrameDesc& F = frames[f];
     if (F.nbBlocks > kLinkSmall) return;                       // (a wave of block_link_kernel takes it)
     if constexpr (kSet) haveDict = slots[F.dictSlot].formatted;
@@ -1007,6 +1105,13 @@ __global__ __launch_bounds__(64) void block_link_open_kernel(FrameDesc* __restri
 {
     block_link_body<false, kSet, true>(frames, blocks, nFrames, haveDict, earlyLiterals, status, 0, slots);
 }
+// (the open instance with the number of frames from the status words: ZSTDMI_decompressBatchAsync)
+template <bool kSet>
+__global__ __launch_bounds__(64) void block_link_open_d_kernel(FrameDesc* __restrict__ frames, BlockDesc* __restrict__ blocks, u32 haveDict,
+                                                               u32 earlyLiterals, u32* __restrict__ status, const DictSlot* __restrict__ slots)
+{
+    block_link_body<false, kSet, true>(frames, blocks, status[kStFrames], haveDict, earlyLiterals, status, 0, slots);
+}
 __global__ __launch_bounds__(64) void block_link_stream_kernel(FrameDesc* __restrict__ frames, BlockDesc* __restrict__ blocks, u32 nFrames, u32 haveDict,
                                                                u32 earlyLiterals, u32* __restrict__ status, u32 phantoms)
 {
@@ -1051,19 +1156,36 @@ __device__ __forceinline__ u64 workgroup_scan(u32 n, u64 (*shW)[16], Load load, 
     return carry;
 }
 
+// kDev (ZSTDMI_decompressBatchAsync): the number of blocks comes from the status words, and so does the limit the caller set for the
+// sequence records (kStCapSeq*: the record buffer was sized from it, once).  A block with sequences whose records would end beyond the
+// limit fails with workSpace_tooSmall: its err keeps every later stage off it, and its key — block and stage fields zero, so that it
+// outranks whatever else the entry's blocks report — folds into the entry's answer (batch_fold).  The sums run over such blocks too:
+// every block with sequences behind one is refused as well.
+template <bool kDev = false>
 __global__ __launch_bounds__(1024) void seq_scan_kernel(BlockDesc* __restrict__ blocks, u32 nBlocks, u32* __restrict__ status)
 {
     __shared__ u64 shW[2][16];
+    u64 capSeq = 0; unsigned long long* keys = nullptr;
+    if constexpr (kDev) {
+        nBlocks = status[kStBlocks]; capSeq = (u64)status[kStCapSeqLo] | ((u64)status[kStCapSeqHi] << 32);
+        keys = reinterpret_cast<unsigned long long*>((uintptr_t)((u64)status[kStBlockKeysLo] | ((u64)status[kStBlockKeysHi] << 32)));
+    }
     const u64 total = workgroup_scan(nBlocks, shW,
         [&](u32 i) -> u64 { const BlockDesc& B = blocks[i]; return (B.type == 2 && !B.err) ? B.nbSeq : 0u; },
-        [&](u32 i, u64 before) { blocks[i].seqBase = before; });
+        [&](u32 i, u64 before) {
+            blocks[i].seqBase = before;
+            if constexpr (kDev) {
+                BlockDesc& B = blocks[i];
+                if (B.type == 2 && !B.err && B.nbSeq && before + B.nbSeq > capSeq) { B.err = kErrWorkSpaceTooSmall; atomicMin(keys + i, (unsigned long long)kErrWorkSpaceTooSmall); }
+            }
+        });
     if (threadIdx.x == 0) { status[kStSeqLo] = (u32)total; status[kStSeqHi] = (u32)(total >> 32); }
 }
 
 void launch_block_prepass(const u8* src, FrameDesc* frames, BlockDesc* blocks, u32 nFrames, u32 nBlocks, u32 haveDict, u32 earlyLiterals, u32* status, hipStream_t stream,
                           u32 phantoms, const DictSlot* slots, bool open)
 {
-    hipLaunchKernelGGL(block_parse_kernel, dim3((nBlocks + 255) / 256), dim3(256), 0, stream, src, blocks, nBlocks, status);
+    hipLaunchKernelGGL(block_parse_kernel<>, dim3((nBlocks + 255) / 256), dim3(256), 0, stream, src, blocks, nBlocks, status);
     if (open) {                 // (a batch: never a fragment of a segmented stream)
         if (slots) {
             hipLaunchKernelGGL((block_link_small_kernel<true, true>), dim3((nFrames + 63) / 64), dim3(64), 0, stream, frames, blocks, nFrames, 0u, earlyLiterals, status, slots);
@@ -1072,23 +1194,38 @@ void launch_block_prepass(const u8* src, FrameDesc* frames, BlockDesc* blocks, u
             hipLaunchKernelGGL((block_link_small_kernel<false, true>), dim3((nFrames + 63) / 64), dim3(64), 0, stream, frames, blocks, nFrames, haveDict, earlyLiterals, status, (const DictSlot*)nullptr);
             if (nBlocks > nFrames) hipLaunchKernelGGL(block_link_open_kernel<false>, dim3(nFrames), dim3(64), 0, stream, frames, blocks, nFrames, haveDict, earlyLiterals, status, (const DictSlot*)nullptr);
         }
-        hipLaunchKernelGGL(seq_scan_kernel, dim3(1), dim3(1024), 0, stream, blocks, nBlocks, status);
+        hipLaunchKernelGGL(seq_scan_kernel<>, dim3(1), dim3(1024), 0, stream, blocks, nBlocks, status);
         return;
     }
     if (slots) {                // (never a fragment of a segmented stream: the host refuses that combination)
         hipLaunchKernelGGL(block_link_small_kernel<true>, dim3((nFrames + 63) / 64), dim3(64), 0, stream, frames, blocks, nFrames, 0u, earlyLiterals, status, slots);
         if (nBlocks > nFrames) hipLaunchKernelGGL(block_link_set_kernel, dim3(nFrames), dim3(64), 0, stream, frames, blocks, nFrames, earlyLiterals, status, slots);
-        hipLaunchKernelGGL(seq_scan_kernel, dim3(1), dim3(1024), 0, stream, blocks, nBlocks, status);
+        hipLaunchKernelGGL(seq_scan_kernel<>, dim3(1), dim3(1024), 0, stream, blocks, nBlocks, status);
         return;
     }
     if (phantoms) {             // a fragment of a segmented stream: one frame whose first blocks are carried definers
         hipLaunchKernelGGL(block_link_stream_kernel, dim3(nFrames), dim3(64), 0, stream, frames, blocks, nFrames, haveDict, earlyLiterals, status, phantoms);
-        hipLaunchKernelGGL(seq_scan_kernel, dim3(1), dim3(1024), 0, stream, blocks, nBlocks, status);
+        hipLaunchKernelGGL(seq_scan_kernel<>, dim3(1), dim3(1024), 0, stream, blocks, nBlocks, status);
         return;
     }
     hipLaunchKernelGGL(block_link_small_kernel<false>, dim3((nFrames + 63) / 64), dim3(64), 0, stream, frames, blocks, nFrames, haveDict, earlyLiterals, status, (const DictSlot*)nullptr);
     if (nBlocks > nFrames) hipLaunchKernelGGL(block_link_kernel, dim3(nFrames), dim3(64), 0, stream, frames, blocks, nFrames, haveDict, earlyLiterals, status);      // (some frame has several blocks)
-    hipLaunchKernelGGL(seq_scan_kernel, dim3(1), dim3(1024), 0, stream, blocks, nBlocks, status);
+    hipLaunchKernelGGL(seq_scan_kernel<>, dim3(1), dim3(1024), 0, stream, blocks, nBlocks, status);
+}
+
+// the pre-pass of a batch enqueued from the device: the open instances, the counts from the status words, grids over the caller's limits
+// (block_link_open always runs: whether some frame has more than kLinkSmall blocks is not known here)
+void launch_block_prepass_d(const u8* src, FrameDesc* frames, BlockDesc* blocks, u32 capFrames, u32 capBlocks, u32 haveDict, u32* status, hipStream_t stream, const DictSlot* slots)
+{
+    hipLaunchKernelGGL(block_parse_kernel<true>, dim3((capBlocks + 255) / 256), dim3(256), 0, stream, src, blocks, 0u, status);
+    if (slots) {
+        hipLaunchKernelGGL((block_link_small_kernel<true, true, true>), dim3((capFrames + 63) / 64), dim3(64), 0, stream, frames, blocks, 0u, 0u, 0u, status, slots);
+        hipLaunchKernelGGL(block_link_open_d_kernel<true>, dim3(capFrames), dim3(64), 0, stream, frames, blocks, 0u, 0u, status, slots);
+    } else {
+        hipLaunchKernelGGL((block_link_small_kernel<false, true, true>), dim3((capFrames + 63) / 64), dim3(64), 0, stream, frames, blocks, 0u, haveDict, 0u, status, (const DictSlot*)nullptr);
+        hipLaunchKernelGGL(block_link_open_d_kernel<false>, dim3(capFrames), dim3(64), 0, stream, frames, blocks, haveDict, 0u, status, (const DictSlot*)nullptr);
+    }
+    hipLaunchKernelGGL(seq_scan_kernel<true>, dim3(1), dim3(1024), 0, stream, blocks, 0u, status);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1175,6 +1312,13 @@ __global__ __launch_bounds__(64) void block_offsets_open_kernel(FrameDesc* __res
     block_offsets_body<kSet, true>(frames, blocks, nFrames, di, status, slots);
 }
 
+template <bool kSet>
+__global__ __launch_bounds__(64) void block_offsets_open_d_kernel(FrameDesc* __restrict__ frames, BlockDesc* __restrict__ blocks,
+                                                                  const DictInfo* __restrict__ di, u32* __restrict__ status, const DictSlot* __restrict__ slots)
+{
+    block_offsets_body<kSet, true>(frames, blocks, status[kStFrames], di, status, slots);
+}
+
 // frames without a content size: the frames' output offsets from their regenerated sizes (single workgroup); the total goes to
 // status, and a total beyond the destination's capacity stops everything behind this kernel
 __global__ __launch_bounds__(1024) void frame_rescan_kernel(FrameDesc* __restrict__ frames, u32 nFrames, u64 dstCapacity, u32* __restrict__ status)
@@ -1197,6 +1341,12 @@ void launch_block_offsets(FrameDesc* frames, BlockDesc* blocks, u32 nFrames, con
     else if (slots) hipLaunchKernelGGL(block_offsets_set_kernel, dim3(nFrames), dim3(64), 0, stream, frames, blocks, nFrames, status, slots);
     else hipLaunchKernelGGL(block_offsets_kernel, dim3(nFrames), dim3(64), 0, stream, frames, blocks, nFrames, di, status);
     if (rescan) hipLaunchKernelGGL(frame_rescan_kernel, dim3(1), dim3(1024), 0, stream, frames, nFrames, dstCapacity, status);
+}
+
+void launch_block_offsets_d(FrameDesc* frames, BlockDesc* blocks, u32 capFrames, const DictInfo* di, u32* status, hipStream_t stream, const DictSlot* slots)
+{
+    if (slots) hipLaunchKernelGGL(block_offsets_open_d_kernel<true>, dim3(capFrames), dim3(64), 0, stream, frames, blocks, (const DictInfo*)nullptr, status, slots);
+    else hipLaunchKernelGGL(block_offsets_open_d_kernel<false>, dim3(capFrames), dim3(64), 0, stream, frames, blocks, di, status, (const DictSlot*)nullptr);
 }
 
 // ZSTD_loadDEntropy's checks (U/ZstdDecompress.cs:1773-1875) on one lane: where the Huffman description and the three NCounts

@@ -246,7 +246,10 @@ enum : u32 { kStFrames = 0, kStErr = 1, kStTotalLo = 2, kStTotalHi = 3, kStUsabl
              kStOpenEntries = 84,       // entries in the lists that hold a frame without a content size
              kStRoomLo = 85, kStRoomHi = 86,            // address of one u64 per frame: the room its literals have in the scratch
              kStDumpLo = 87, kStDumpHi = 88,            // offset in the scratch of kLitDump bytes that every block without room decodes into
-             kStWords = 90 };
+             // a batch enqueued from the device (ZSTDMI_decompressBatchAsync): the caller's limits, filed by batch_init_d_kernel for the
+             // scans' cap instances (batch_scan: frames, blocks, literal-scratch bytes; seq_scan: sequence records)
+             kStCapFrames = 90, kStCapBlocks = 91, kStCapContentLo = 92, kStCapContentHi = 93, kStCapSeqLo = 94, kStCapSeqHi = 95,
+             kStWords = 96 };
 // Literals of a block that has no room left in its frame's scratch (the room of an entry with unsized frames is clamped to the entry's
 // capacity) still have to be decoded — a damaged stream's error outranks dstSize_tooSmall — but nobody reads them
 constexpr u32 kLitDump = (128u << 10) + 512;

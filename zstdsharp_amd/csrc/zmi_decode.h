@@ -19,6 +19,15 @@ __device__ __forceinline__ void report_error(u32* status, u64 blockIdx, u32 stag
     if (perBlock) atomicMin(reinterpret_cast<unsigned long long*>(perBlock) + blockIdx, key);
 }
 
+// A work list's length as a stage's kernel takes it: the launch argument, or — kDev, the instances ZSTDMI_decompressBatchAsync launches
+// over a grid sized from the caller's limits, where the host never learns the counts — the status word the batch scan filed (kStFrames,
+// kStBlocks); the surplus workgroups leave at once.  kDev = false reads nothing and is the kernel as it always was.
+template <bool kDev>
+__device__ __forceinline__ u32 list_count(u32 arg, const u32* __restrict__ status, u32 word)
+{
+    if constexpr (kDev) return status[word]; else return arg;
+}
+
 struct FrameHeader { u64 contentSize; u64 windowSize; u32 headerSize; u32 checksum; u32 dictID; u32 err; };
 
 __device__ inline FrameHeader parse_frame_header(const u8* p, u64 avail)

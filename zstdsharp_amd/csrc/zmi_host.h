@@ -117,12 +117,32 @@ void launch_frame_walk_emit(const u8* src, u64 srcSize, FrameDesc* frames, Block
 void launch_frame_walk_serial(const u8* src, u64 srcSize, FrameDesc* frames, BlockDesc* blocks, u32 maxFrames, u32* status, u32 dictID, u32 emit,
                               hipStream_t stream, const DictSlot* slots = nullptr, u32 nSet = 0);
 void launch_batch_walk_count(const u8* src, const BatchEntryIn* in, BatchEntryOut* out, u32 nEntries, u32 dictID, u64 aloneAbove, u32* status, hipStream_t stream,
-                             const DictSlot* slots = nullptr, u32 nSet = 0, bool open = false);        // open: ZSTDMI_DCtx_setBatchUnsized
+                             const DictSlot* slots = nullptr, u32 nSet = 0, bool open = false,         // open: ZSTDMI_DCtx_setBatchUnsized
+                             bool caps = false);       // caps: batch_scan's instance that holds the entries to the limits in the status words
 // rooms (not null: the open instance): one u64 per frame, the room its literals have in the scratch
 void launch_batch_walk_emit(const u8* src, const BatchEntryIn* in, const BatchEntryOut* out, u32 nEntries, FrameDesc* frames, BlockDesc* blocks, hipStream_t stream,
                             const DictSlot* slots = nullptr, u32 nSet = 0, u64* rooms = nullptr);
 void launch_batch_rescan(const BatchEntryIn* in, BatchEntryOut* out, u32 nEntries, FrameDesc* frames, hipStream_t stream);
 void launch_batch_fold(BatchEntryOut* out, u32 nEntries, const u64* keys, hipStream_t stream);
+// A batch whose descriptors lie in HBM (ZSTDMI_decompressBatchAsync).  The host knows the number of entries and the
+// caller's limits, never the call's frames, blocks or sequences: those stay in the status words.  plan / init / finish stand in for the
+// host's loops over the entries and its small copies (decode_walk.hip); every launch_*_d below starts a stage's open instances that
+// take their count from the status words, over a grid sized from the limit (capFrames, capBlocks), never on a second stream.
+// batch_walk_count / _emit, batch_rescan and batch_fold run one lane or wave per ENTRY and serve as they are.
+struct BatchLimitsD { u32 frames, blocks; u64 content, sequences; };
+void launch_batch_plan_d(const void* const* srcs, const size_t* sizes, void* const* dsts, const size_t* caps, u32 n, u64 bound, BatchEntryIn* in, u32* verdict, hipStream_t stream);
+void launch_batch_init_d(u32* status, const u64* blockKeys, const u64* rooms, u64 dumpOff, const BatchLimitsD& lim, hipStream_t stream);
+void launch_batch_finish_d(const BatchEntryOut* out, const u32* verdict, u32 n, size_t* dstSizes, hipStream_t stream);
+void launch_block_prepass_d(const u8* src, FrameDesc* frames, BlockDesc* blocks, u32 capFrames, u32 capBlocks, u32 haveDict, u32* status, hipStream_t stream, const DictSlot* slots);
+void launch_seq_decode_d(const u8* src, const FrameDesc* frames, BlockDesc* blocks, u32 capBlocks, SeqRec* recs, u32* status,
+                         const u8* dictFull, const DictInfo* di, const u32* dictTabs, hipStream_t stream, const DictSlot* slots);
+void launch_block_offsets_d(FrameDesc* frames, BlockDesc* blocks, u32 capFrames, const DictInfo* di, u32* status, hipStream_t stream, const DictSlot* slots);
+void launch_decode_literals_d(const u8* src, u8* out, u8* scratch, const FrameDesc* frames, const BlockDesc* blocks, u32 capBlocks, u32* status,
+                              u8* slowFlags, u32 mode, const u8* dictFull, const DictInfo* di, hipStream_t stream, const DictSlot* slots);
+void launch_place_literals_d(const u8* src, u8* out, const u8* scratch, const FrameDesc* frames, const BlockDesc* blocks, u32 capBlocks,
+                             const SeqRec* recs, const u32* status, hipStream_t stream);
+void launch_exec_matches_d(const u8* src, u8* out, const FrameDesc* frames, const BlockDesc* blocks, u32 capFrames, const SeqRec* recs, u32* status,
+                           const u8* dict, u32 dictSize, hipStream_t stream, int wide, const DictSlot* slots);
 void launch_seek_select(const u8* tab, u64 tableBytes, u32 n, u32 stride, u64 srcSize, u64 offset, u64 length, u64* sum, hipStream_t stream);
 void launch_seek_emit(const u8* tab, u32 stride, u32 first, u32 nSel, u64 dFirst, u64 offset, u64 dstBias, u64 edgeBias, u64 slot1, u32 cutFirst, u32 cutLast,
                       BatchEntryIn* out, hipStream_t stream);
@@ -185,10 +205,11 @@ using namespace zmi;
 #define ZERR(code) ((size_t)0 - (size_t)(code))
 static inline bool isErr(size_t c) { return c > ZERR(kErrMaxCode); }
 // No C++ exception may cross the C ABI (the caller is P/Invoke): host-side container growth is the only thing that throws here.
-// Host-side tallies of one compression context (ZSTDMI_debugHostWaits / ZSTDMI_debugDeviceAllocs): blocking waits its host code made and
-// growths of its device buffers.  Its buffers name it (DevBuf::owner); a wait is counted for the tally this thread's ABI call bound
-// (tl_waits: set by cctx_bind inside guarded(), which puts the caller's back), so that stream_wait and dev_read count without an argument.
-// beforeFree: what must happen before any of its buffers is freed (the compressor: cctx_async_drain, the wait behind an enqueued batch)
+// Host-side tallies of one context (ZSTDMI_debugHostWaits / ZSTDMI_debugDeviceAllocs, and the decoder's with a D behind the name): blocking
+// waits its host code made and growths of its device buffers.  Its buffers name it (DevBuf::owner); a wait is counted for the tally this
+// thread's ABI call bound (tl_waits: set by cctx_bind / dctx_bind inside guarded(), which puts the caller's back), so that stream_wait and
+// dev_read count without an argument.
+// beforeFree: what must happen before any of its buffers is freed (cctx_async_drain / dctx_async_drain: the wait behind an enqueued batch)
 struct HostTally { long long waits = 0, allocs = 0; void (*beforeFree)(void*) = nullptr; void* self = nullptr; };
 static thread_local long long* tl_waits = nullptr;
 static thread_local bool tl_guarded = false;
@@ -207,7 +228,7 @@ constexpr int kMaxStages = 24;
 
 struct DevBuf {
     void* p = nullptr; size_t cap = 0;
-    HostTally* owner = nullptr;     // (a compression context's buffers: see HostTally)
+    HostTally* owner = nullptr;     // (a context's buffers: see HostTally)
     void drop() { if (!p) return; if (owner && owner->beforeFree) owner->beforeFree(owner->self); (void)hipFree(p); p = nullptr; cap = 0; }
     bool ensure(size_t n)
     {

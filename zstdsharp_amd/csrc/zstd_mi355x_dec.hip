@@ -85,7 +85,38 @@ struct ZSTD_DCtx_s {
     // ZSTD_DCtx_refPrefix: the caller's bytes (host or device), referenced until the next ZSTD_decompressDCtx / ZSTDMI_decompressDevice
     // has consumed them.  pfxDev: the prefix as that call's kernels read it (the caller's device pointer, or pfxStage for a host prefix)
     const void* pfx = nullptr; size_t pfxSize = 0; DevBuf pfxStage; const u8* pfxDev = nullptr;
+    // ZSTDMI_DCtx_prepareBatchAsync / ZSTDMI_decompressBatchAsync: what the prepare resolved (asyncPrep: host state only,
+    // valid while dctx_gen() is what it was then; paramGen: bumped by every setter whatever it sets), the plan's verdicts, and the event
+    // recorded behind the last enqueued call (asyncPending: not yet waited for).  dctx_async_drain is the one place that waits for it;
+    // every buffer of the context names `tally`, so that no growth or release frees memory an enqueued call still uses, and counts there.
+    HostTally tally; u64 paramGen = 0;
+    struct DAsyncPrep* asyncPrep = nullptr; hipEvent_t asyncEv = nullptr; bool asyncPending = false;
+    DevBuf asyncVerdict;
+    ZSTD_DCtx_s();
 };
+// what ZSTDMI_DCtx_prepareBatchAsync resolved: the limits with their defaults filled in, and where the dump area lies in the scratch
+struct DAsyncPrep { u64 gen; size_t maxEntries; u64 bound; BatchLimitsD lim; u64 dumpOff; };
+static void dctx_async_drain(ZSTD_DCtx* d);
+ZSTD_DCtx_s::ZSTD_DCtx_s()
+{
+    tally.self = this; tally.beforeFree = [](void* self) { dctx_async_drain((ZSTD_DCtx_s*)self); };
+    for (DevBuf* b : { &frames, &blocks, &recs, &status, &scratch, &walkWs, &slowFlags, &stageSrc, &stageDst, &origin, &originList, &batchIn, &batchOut, &blockKeys, &litRooms,
+                       &seekTab, &seekSum, &edge, &rangesWs, &rangesIn, &rangesRec, &rangesRes, &arena, &hist[0], &hist[1], &segReps, &segXxh, &dict, &dictInfoDev, &slotTab,
+                       &pfxStage, &asyncVerdict }) b->owner = &tally;
+}
+// The lifetime rule of an enqueued batch (ZSTDMI_decompressBatchAsync), in one place: wait for the event behind the last enqueued call.
+// Called by every DevBuf of the context before it frees (HostTally::beforeFree: growth and release alike), by ZSTD_freeDCtx, by
+// ZSTDMI_DCtx_setStream to another stream, by ZSTD_DCtx_loadDictionary and ZSTD_DCtx_refDDict, and in front of a re-upload of the
+// dictionary or of the DDict set's slot table (the device must be current).
+static void dctx_async_drain(ZSTD_DCtx* d)
+{
+    if (!d->asyncPending) return;
+    d->asyncPending = false;
+    d->tally.waits++;
+    if (hipEventSynchronize(d->asyncEv) != hipSuccess) (void)hipGetLastError();
+}
+// moves whenever a prepare may have become stale: a setter, the dictionary in force, the DDict set or the device
+static u64 dctx_gen(const ZSTD_DCtx* d) { return d->paramGen + d->dictGen + d->setGen; }
 
 // ZSTD_createDDict: a dictionary uploaded, validated and digested once on `device`, immutable afterwards (any number of contexts and
 // threads read it without a lock): the bytes with 64 readable ones behind them, DictInfo, and for a formatted dictionary its three
@@ -108,8 +139,10 @@ static size_t set_check(ZSTD_DCtx* d, bool segmented = false)
 }
 
 static size_t dctx_sync_dictionary(ZSTD_DCtx* d);
+// (inside an ABI call's guarded(): the waits of this thread count for this context from here on, see HostTally)
 static size_t dctx_bind(ZSTD_DCtx* d)
 {
+    if (d && tl_guarded) tl_waits = &d->tally.waits;
     const size_t e = ctx_bind(d); if (isErr(e)) return e;
     if (!d->aux && hipStreamCreateWithFlags(&d->aux, hipStreamNonBlocking) != hipSuccess) return ZERR(kErrMemoryAllocation);
     if (!d->auxDone && hipEventCreateWithFlags(&d->auxDone, hipEventDisableTiming) != hipSuccess) return ZERR(kErrMemoryAllocation);
@@ -125,8 +158,12 @@ size_t ZSTD_freeDCtx(ZSTD_DCtx* d)
     if (!d) return 0;
     for (ZSTD_DCtx* w : d->workers) (void)ZSTD_freeDCtx(w);
     d->workers.clear();
+    if (tl_waits == &d->tally.waits) tl_waits = nullptr;
     if (d->deviceOk) {
         (void)hipSetDevice(d->device);
+        dctx_async_drain(d);        // (an enqueued batch may run on a stream that is not the context's own)
+        if (d->asyncEv) (void)hipEventDestroy(d->asyncEv);
+        d->asyncVerdict.release();
         if (d->ownStream) (void)hipStreamSynchronize(d->ownStream);
         d->frames.release(); d->blocks.release(); d->recs.release(); d->status.release(); d->scratch.release(); d->walkWs.release(); d->slowFlags.release(); d->stageSrc.release(); d->stageDst.release(); d->dict.release(); d->dictInfoDev.release(); d->origin.release(); d->originList.release(); d->batchIn.release(); d->batchOut.release(); d->blockKeys.release(); d->litRooms.release(); d->seekTab.release(); d->seekSum.release(); d->edge.release(); d->pfxStage.release(); d->rangesWs.release(); d->rangesIn.release(); d->rangesRec.release(); d->rangesRes.release(); d->arena.release(); d->slotTab.release();
         d->hist[0].release(); d->hist[1].release(); d->segReps.release(); d->segXxh.release();
@@ -135,12 +172,14 @@ size_t ZSTD_freeDCtx(ZSTD_DCtx* d)
         if (d->auxDone) (void)hipEventDestroy(d->auxDone);
         if (d->ownStream) (void)hipStreamDestroy(d->ownStream);
     }
+    delete d->asyncPrep;
     delete d;
     return 0;
 }
 size_t ZSTD_DCtx_setParameter(ZSTD_DCtx* d, int param, int value)
 {
     if (!d) return ZERR(kErrGeneric);
+    d->paramGen++;
     if (param == ZSTD_d_windowLogMax) { if (value != 0 && (value < 10 || value > 31)) return ZERR(kErrParameterOutOfBound); d->windowLogMax = value ? value : 27; return 0; }
     if (param == ZSTD_d_refMultipleDDicts) {        // sticky; the set itself stays as it is (U/ZstdDecompress.cs:2441-2447)
         if (value != ZSTD_rmd_refSingleDDict && value != ZSTD_rmd_refMultipleDDicts) return ZERR(kErrParameterOutOfBound);
@@ -162,6 +201,8 @@ size_t ZSTD_DCtx_getParameter(ZSTD_DCtx* d, int param, int* value)
 static size_t ZSTD_DCtx_loadDictionary_impl(ZSTD_DCtx* d, const void* dict, size_t dictSize)
 {
     if (!d) return ZERR(kErrGeneric);
+    if (tl_guarded) tl_waits = &d->tally.waits;
+    if (d->deviceOk && hipSetDevice(d->device) == hipSuccess) dctx_async_drain(d);      // (an enqueued batch reads the dictionary it was prepared behind)
     d->dictGen++;
     d->pfx = nullptr; d->pfxSize = 0;       // (a pending prefix is cancelled: ZSTD_clearAllDicts)
     d->ddict = nullptr;                     // (and a referenced DDict)
@@ -296,6 +337,7 @@ static unsigned long long ZSTD_getFrameContentSize_impl(const void* src, size_t 
 static size_t dctx_sync_dictionary(ZSTD_DCtx* d)
 {
     if (ddict_shared(d) || !d->dictDirty) return 0;     // (a shared DDict is on the device already)
+    dctx_async_drain(d);        // (a re-upload writes what an enqueued batch may still read)
     hipStream_t s = d->stream;
     if (!d->dictHost.empty()) {
         d->dictUploads++;
@@ -366,6 +408,7 @@ static size_t dctx_sync_slots(ZSTD_DCtx* d, DecodeDict& dd)
     dd.slots = nullptr; dd.nSet = 0;
     if (!set_active(d) || d->pfxDev) return 0;
     if (d->slotGen != d->setGen) {
+        dctx_async_drain(d);    // (as for the dictionary)
         if (!d->ddictSet.image(d->slotHost, d->ddict, fill_slot)) return ZERR(kErrMemoryAllocation);
         if (!d->slotTab.ensure(d->slotHost.size() * sizeof(DictSlot) + 64)) return ZERR(kErrMemoryAllocation);
         if (hipMemcpyAsync(d->slotTab.p, d->slotHost.data(), d->slotHost.size() * sizeof(DictSlot), hipMemcpyHostToDevice, d->stream) != hipSuccess) return ZERR(kErrGeneric);
@@ -669,6 +712,107 @@ static size_t decompress_batch_impl(ZSTD_DCtx* d, const void* const* srcs, const
         dstSizes[i] = decompress_device(d, (u8*)dsts[i], dstCapacities[i], (const u8*)srcs[i], srcSizes[i]);
         d->lastBatchAlone++;
     }
+    return 0;
+}
+
+// ---- a batch enqueued from the device (ZSTDMI_DCtx_prepareBatchAsync / ZSTDMI_decompressBatchAsync) ----
+// decode_entries stops the host three times — to size the lists, to size the records, to read the answers — and copies a handful of
+// words to the device in between.  Here the caller states limits once, the prepare sizes every work buffer from them, and a call is
+// kernels only: the plan kernel reads the caller's arrays, the init kernel fills the status words, the scans hold the entries and the
+// blocks to the limits (batch_scan_kernel<true>, seq_scan_kernel<true>), every stage takes its count from the status words over a
+// grid sized from the limit, and the finish kernel writes the caller's sizes column.
+// the limits with their defaults filled in -> false: a zero where none is allowed, or a limit beyond the lists' index range
+static bool dbatch_limits(const ZSTDMI_DBatchLimits* L, size_t& maxEntries, u64& bound, BatchLimitsD& lim)
+{
+    if (!L->maxEntries || L->maxEntries > 0xFFFFFFF0ull || !L->maxContent || L->maxContent > ((u64)1 << 48) || !L->srcSizeBound || L->srcSizeBound > kBatchAloneAbove) return false;
+    const u64 frames = L->maxFrames ? L->maxFrames : L->maxEntries;
+    if (frames > ((u64)1 << 26)) return false;
+    const u64 blocks = L->maxBlocks ? L->maxBlocks : frames + L->maxContent / 16384;
+    if (blocks > 0xFFFFFFF0ull) return false;
+    const u64 seqs = L->maxSequences ? L->maxSequences : L->maxContent / 3 + 64;
+    if (seqs > ((u64)1 << 48)) return false;
+    maxEntries = L->maxEntries; bound = L->srcSizeBound;
+    lim.frames = (u32)frames; lim.blocks = (u32)blocks; lim.content = L->maxContent; lim.sequences = seqs;
+    return true;
+}
+// the work buffers of a call at the limits, in the order the prepare asks for them
+struct DAsyncBytes { size_t batchIn, batchOut, verdict, frames, blocks, scratch, slowFlags, blockKeys, litRooms, recs, status; };
+static DAsyncBytes dbatch_bytes(size_t maxEntries, const BatchLimitsD& lim)
+{
+    DAsyncBytes b;
+    b.batchIn = maxEntries * sizeof(BatchEntryIn); b.batchOut = maxEntries * sizeof(BatchEntryOut); b.verdict = maxEntries * sizeof(u32);
+    b.frames = (size_t)lim.frames * sizeof(FrameDesc); b.blocks = (size_t)lim.blocks * sizeof(BlockDesc) + 64;
+    b.scratch = (size_t)lim.content + kLitDump + (size_t)lim.frames * kLitSkew + 256;        // (the dump area behind the frames' scratch, as decode_entries lays it out)
+    b.slowFlags = (size_t)lim.blocks + 64; b.blockKeys = (size_t)lim.blocks * sizeof(u64) + 8; b.litRooms = (size_t)lim.frames * sizeof(u64);
+    b.recs = (size_t)(lim.sequences + 64) * sizeof(SeqRec); b.status = kStWords * sizeof(u32);
+    return b;
+}
+static size_t prepare_batch_async_d_impl(ZSTD_DCtx* d, const ZSTDMI_DBatchLimits* limits)
+{
+    if (!d || !limits) return ZERR(kErrGeneric);
+    delete d->asyncPrep; d->asyncPrep = nullptr;
+    size_t maxEntries; u64 bound; BatchLimitsD lim;
+    if (!dbatch_limits(limits, maxEntries, bound, lim)) return ZERR(kErrParameterOutOfBound);
+    // what the shared pass does not cover, as far as the host alone can tell (a pending prefix stays pending)
+    if (d->workers.size() > 1 || d->pfx || d->originMode == 2) return ZERR(kErrParameterUnsupported);
+    size_t e = set_check(d); if (isErr(e)) return e;
+    e = dctx_bind(d); if (isErr(e)) return e;
+    e = dctx_sync_dictionary(d); if (isErr(e)) return e;
+    DecodeDict dd = decode_dict(d);
+    e = dctx_sync_slots(d, dd); if (isErr(e)) return e;
+    const DAsyncBytes b = dbatch_bytes(maxEntries, lim);
+    if (!d->batchIn.ensure(b.batchIn) || !d->batchOut.ensure(b.batchOut) || !d->asyncVerdict.ensure(b.verdict) || !d->frames.ensure(b.frames) || !d->blocks.ensure(b.blocks) ||
+        !d->scratch.ensure(b.scratch) || !d->slowFlags.ensure(b.slowFlags) || !d->blockKeys.ensure(b.blockKeys) || !d->litRooms.ensure(b.litRooms) || !d->recs.ensure(b.recs) ||
+        !d->status.ensure(b.status)) { (void)hipGetLastError(); return ZERR(kErrMemoryAllocation); }
+    if (!d->asyncEv && hipEventCreateWithFlags(&d->asyncEv, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); d->asyncEv = nullptr; return ZERR(kErrMemoryAllocation); }
+    d->asyncPrep = new DAsyncPrep{ dctx_gen(d), maxEntries, bound, lim, lim.content + (u64)lim.frames * kLitSkew + 256 };
+    return 0;
+}
+// decode_entries between its table upload and its read-back, kernels only (and one hipMemsetAsync over the block keys)
+static size_t decompress_batch_async_impl(ZSTD_DCtx* d, const void* const* d_srcs, const size_t* d_srcSizes, size_t n, void* const* d_dsts,
+                                          const size_t* d_dstCapacities, size_t* d_dstSizes)
+{
+    if (!d) return ZERR(kErrGeneric);
+    if (n == 0) return 0;
+    if (!d_srcs || !d_srcSizes || !d_dsts || !d_dstCapacities || !d_dstSizes) return ZERR(kErrGeneric);
+    const DAsyncPrep* const P = d->asyncPrep;
+    if (!P || P->gen != dctx_gen(d) || n > P->maxEntries || !d->deviceOk || (d->dictDirty && !ddict_shared(d)) || (set_active(d) && d->slotGen != d->setGen)) return ZERR(kErrStageWrong);
+    size_t e = dctx_bind(d); if (isErr(e)) return e;
+    struct TimerOff { StageTimer& t; bool was; ~TimerOff() { t.enabled = was; } } timerOff{d->timer, d->timer.enabled};
+    d->timer.enabled = false;       // (stage events belong to calls that wait for them)
+    hipStream_t s = d->stream;
+    DecodeDict dd = decode_dict(d);
+    e = dctx_sync_slots(d, dd); if (isErr(e)) return e;       // (the table is current: nothing is uploaded)
+    const BatchLimitsD& lim = P->lim;
+    const u32 nE = (u32)n;
+    BatchEntryIn* const dIn = (BatchEntryIn*)d->batchIn.p; BatchEntryOut* const dOut = (BatchEntryOut*)d->batchOut.p; u32* const verdict = (u32*)d->asyncVerdict.p;
+    FrameDesc* const frames = (FrameDesc*)d->frames.p; BlockDesc* const blocks = (BlockDesc*)d->blocks.p; SeqRec* const recs = (SeqRec*)d->recs.p;
+    u32* const status = (u32*)d->status.p; u64* const keys = (u64*)d->blockKeys.p; u64* const rooms = (u64*)d->litRooms.p;
+    u8* const scratch = (u8*)d->scratch.p; u8* const slowFlags = (u8*)d->slowFlags.p;
+    // the bases are constants: the plan kernel states every source and destination as an offset from kAsyncBase
+    const u8* const srcBase = (const u8*)(uintptr_t)kAsyncBase; u8* const dstBase = (u8*)(uintptr_t)kAsyncBase;
+    launch_batch_init_d(status, keys, rooms, P->dumpOff, lim, s);
+    launch_batch_plan_d(d_srcs, d_srcSizes, d_dsts, d_dstCapacities, nE, P->bound, dIn, verdict, s);
+    if (hipMemsetAsync(keys, 0xFF, (size_t)lim.blocks * sizeof(u64), s) != hipSuccess) { (void)hipGetLastError(); return ZERR(kErrGeneric); }
+    // (frames without a content size always take the shared pass: there is no single-call path to hand them to)
+    launch_batch_walk_count(srcBase, dIn, dOut, nE, dd.dictID, kBatchAloneAbove, status, s, dd.slots, dd.nSet, true, true);
+    launch_batch_walk_emit(srcBase, dIn, dOut, nE, frames, blocks, s, dd.slots, dd.nSet, rooms);
+    launch_block_prepass_d(srcBase, frames, blocks, lim.frames, lim.blocks, dd.fmt ? 1u : 0u, status, s, dd.slots);
+    launch_seq_decode_d(srcBase, frames, blocks, lim.blocks, recs, status, dd.dictFull, dd.dinfo, dd.seqTabs, s, dd.slots);
+    launch_block_offsets_d(frames, blocks, lim.frames, dd.dinfo, status, s, dd.slots);
+    launch_batch_rescan(dIn, dOut, nE, frames, s);
+    launch_decode_literals_d(srcBase, dstBase, scratch, frames, blocks, lim.blocks, status, slowFlags, d->litDecoder, dd.dictFull, dd.dinfo, s, dd.slots);
+    launch_place_literals_d(srcBase, dstBase, scratch, frames, blocks, lim.blocks, recs, status, s);
+    // (every long frame takes the ordered walk; its waves per frame by the setter, else by the limit for the frames)
+    const int execWaves = d->execWaves ? d->execWaves : lim.frames <= 256 ? 16 : lim.frames <= 512 ? 8 : lim.frames <= 1024 ? 4 : lim.frames <= 2048 ? 2 : 1;
+    launch_exec_matches_d(srcBase, dstBase, frames, blocks, lim.frames, recs, status, dd.dictContent, dd.dictContentSize, s, execWaves, dd.slots);
+    launch_batch_fold(dOut, nE, keys, s);
+    launch_batch_finish_d(dOut, verdict, nE, d_dstSizes, s);
+    if (hipEventRecord(d->asyncEv, s) != hipSuccess) {      // (without the event nothing may stay in flight)
+        (void)hipGetLastError();
+        return stream_wait(s);
+    }
+    d->asyncPending = true;
     return 0;
 }
 
@@ -1456,6 +1600,8 @@ size_t ZSTD_DCtx_refDDict(ZSTD_DCtx* d, const ZSTD_DDict* ddict)
 {
     if (!d) return ZERR(kErrGeneric);
     return guarded([&]() -> size_t {
+        tl_waits = &d->tally.waits;
+        if (d->deviceOk && hipSetDevice(d->device) == hipSuccess) dctx_async_drain(d);      // (an enqueued batch reads the DDict it was prepared behind)
         // ZSTD_d_refMultipleDDicts: the DDict also joins the set, replacing an entry of equal dictID (U/ZstdDecompress.cs:2319-2333); a set
         // that cannot take it leaves the context as it was.  NULL clears the current DDict only (ZSTD_clearDict).  No device is touched.
         if (ddict && d->refMultiple && !d->ddictSet.insert(ZSTD_getDictID_fromDDict(ddict), ddict)) return ZERR(kErrMemoryAllocation);
@@ -1506,29 +1652,34 @@ unsigned ZSTD_getDictID_fromFrame(const void* src, size_t srcSize) { return dict
 
 // ---------------- extensions ----------------
 // (a referenced DDict is shared or copied by where the context runs: dctx_adopt_ddict)
-size_t ZSTDMI_DCtx_setDevice(ZSTD_DCtx* d, int device) { const size_t e = ctx_set_device(d, device); if (d) d->setGen++; if (d && d->ddict) (void)guarded([&]() -> size_t { dctx_adopt_ddict(d); return 0; }); return e; }
+size_t ZSTDMI_DCtx_setDevice(ZSTD_DCtx* d, int device) { if (d) d->paramGen++; const size_t e = ctx_set_device(d, device); if (d) d->setGen++; if (d && d->ddict) (void)guarded([&]() -> size_t { dctx_adopt_ddict(d); return 0; }); return e; }
 size_t ZSTDMI_DCtx_setDevices(ZSTD_DCtx* d, const int* devices, int n)
 {
+    if (d) d->paramGen++;
     const size_t e = ctx_set_devices(d, devices, n, ZSTD_createDCtx, ZSTD_freeDCtx);
     if (d) d->setGen++;
     if (d && d->ddict) (void)guarded([&]() -> size_t { dctx_adopt_ddict(d); return 0; });
     return e;
 }
-size_t ZSTDMI_DCtx_setStream(ZSTD_DCtx* d, void* st) { return ctx_set_stream(d, st, dctx_bind); }
+size_t ZSTDMI_DCtx_setStream(ZSTD_DCtx* d, void* st)
+{
+    if (d && d->deviceOk && (st ? (hipStream_t)st : d->ownStream) != d->stream && hipSetDevice(d->device) == hipSuccess) dctx_async_drain(d);    // (the new stream is not ordered behind an enqueued batch)
+    return ctx_set_stream(d, st, dctx_bind);
+}
 size_t ZSTDMI_DCtx_setStreamSegment(ZSTD_DCtx* d, size_t bytes)
 {
     if (!d) return ZERR(kErrGeneric);
-    d->segBytes = bytes; d->streamSegments = 0; d->streamPeakInput = 0;
+    d->segBytes = bytes; d->streamSegments = 0; d->streamPeakInput = 0; d->paramGen++;
     return 0;
 }
 long long ZSTDMI_debugStreamPeakInput(const ZSTD_DCtx* d) { return d ? d->streamPeakInput : -1; }
 int ZSTDMI_debugStreamSegments(const ZSTD_DCtx* d) { return d ? d->streamSegments : -1; }
 int ZSTDMI_debugLastWalkSerial(const ZSTD_DCtx* d) { return d ? (int)d->lastWalkSerial : -1; }
-size_t ZSTDMI_DCtx_setExecWaves(ZSTD_DCtx* d, unsigned waves) { if (!d || (waves != 0 && waves != 1 && waves != 2 && waves != 4 && waves != 8 && waves != 16)) return ZERR(kErrParameterOutOfBound); d->execWaves = (int)waves; return 0; }
-size_t ZSTDMI_DCtx_setOverlap(ZSTD_DCtx* d, unsigned mode) { if (!d || mode > 2) return ZERR(kErrParameterOutOfBound); d->overlapMode = (int)mode; return 0; }
-size_t ZSTDMI_DCtx_setLongFrames(ZSTD_DCtx* d, unsigned mode) { if (!d || mode > 2) return ZERR(kErrParameterOutOfBound); d->originMode = (int)mode; return 0; }
-size_t ZSTDMI_DCtx_setLiteralDecoder(ZSTD_DCtx* d, unsigned mode) { if (!d || mode > 3) return ZERR(kErrParameterOutOfBound); d->litDecoder = mode; return 0; }
-size_t ZSTDMI_DCtx_setProfiling(ZSTD_DCtx* d, int en) { if (!d) return ZERR(kErrGeneric); d->timer.enabled = en != 0; return 0; }
+size_t ZSTDMI_DCtx_setExecWaves(ZSTD_DCtx* d, unsigned waves) { if (!d || (waves != 0 && waves != 1 && waves != 2 && waves != 4 && waves != 8 && waves != 16)) return ZERR(kErrParameterOutOfBound); d->execWaves = (int)waves; d->paramGen++; return 0; }
+size_t ZSTDMI_DCtx_setOverlap(ZSTD_DCtx* d, unsigned mode) { if (!d || mode > 2) return ZERR(kErrParameterOutOfBound); d->overlapMode = (int)mode; d->paramGen++; return 0; }
+size_t ZSTDMI_DCtx_setLongFrames(ZSTD_DCtx* d, unsigned mode) { if (!d || mode > 2) return ZERR(kErrParameterOutOfBound); d->originMode = (int)mode; d->paramGen++; return 0; }
+size_t ZSTDMI_DCtx_setLiteralDecoder(ZSTD_DCtx* d, unsigned mode) { if (!d || mode > 3) return ZERR(kErrParameterOutOfBound); d->litDecoder = mode; d->paramGen++; return 0; }
+size_t ZSTDMI_DCtx_setProfiling(ZSTD_DCtx* d, int en) { if (!d) return ZERR(kErrGeneric); d->timer.enabled = en != 0; d->paramGen++; return 0; }
 int ZSTDMI_DCtx_getStageTimes(const ZSTD_DCtx* d, float* ms, const char** names, int cap)
 {
     if (!d) return 0;
@@ -1544,6 +1695,7 @@ size_t ZSTD_DCtx_refPrefix(ZSTD_DCtx* d, const void* prefix, size_t prefixSize)
     if (!d) return ZERR(kErrGeneric);
     if (prefix && prefixSize > (size_t)1 << 30) return ZERR(kErrParameterUnsupported);
     // ZSTD_clearAllDicts: a loaded dictionary, a referenced DDict and an earlier prefix are gone
+    if (d->deviceOk && hipSetDevice(d->device) == hipSuccess) dctx_async_drain(d);
     d->ddict = nullptr;
     d->dictGen++; d->dictHost.clear(); d->dictFormatted = false; d->dictDirty = true;
     d->pfx = nullptr; d->pfxSize = 0;
@@ -1556,8 +1708,22 @@ size_t ZSTDMI_decompressBatch(ZSTD_DCtx* d, const void* const* srcs, const size_
 {
     return guarded([&] { if (d) d->lastDictTabBlocks = d->lastSetFrames = 0; return decompress_batch_impl(d, srcs, srcSizes, n, dsts, dstCapacities, dstSizes); });
 }
+size_t ZSTDMI_batchAsyncWorkspaceD(const ZSTDMI_DBatchLimits* limits)
+{
+    size_t maxEntries; u64 bound; BatchLimitsD lim;
+    if (!limits || !dbatch_limits(limits, maxEntries, bound, lim)) return 0;
+    const DAsyncBytes b = dbatch_bytes(maxEntries, lim);
+    return b.batchIn + b.batchOut + b.verdict + b.frames + b.blocks + b.scratch + b.slowFlags + b.blockKeys + b.litRooms + b.recs + b.status;
+}
+size_t ZSTDMI_DCtx_prepareBatchAsync(ZSTD_DCtx* d, const ZSTDMI_DBatchLimits* limits) { return guarded([&] { return prepare_batch_async_d_impl(d, limits); }); }
+size_t ZSTDMI_decompressBatchAsync(ZSTD_DCtx* d, const void* const* d_srcs, const size_t* d_srcSizes, size_t n, void* const* d_dsts, const size_t* d_dstCapacities, size_t* d_dstSizes)
+{
+    return guarded([&] { return decompress_batch_async_impl(d, d_srcs, d_srcSizes, n, d_dsts, d_dstCapacities, d_dstSizes); });
+}
+long long ZSTDMI_debugHostWaitsD(const ZSTD_DCtx* d) { return d ? d->tally.waits : -1; }
+long long ZSTDMI_debugDeviceAllocsD(const ZSTD_DCtx* d) { return d ? d->tally.allocs : -1; }
 int ZSTDMI_debugLastBatchAloneD(const ZSTD_DCtx* d) { return d ? d->lastBatchAlone : -1; }
-size_t ZSTDMI_DCtx_setBatchUnsized(ZSTD_DCtx* d, unsigned mode) { if (!d || mode > 1) return ZERR(kErrParameterOutOfBound); d->batchUnsized = (int)mode; return 0; }
+size_t ZSTDMI_DCtx_setBatchUnsized(ZSTD_DCtx* d, unsigned mode) { if (!d || mode > 1) return ZERR(kErrParameterOutOfBound); d->batchUnsized = (int)mode; d->paramGen++; return 0; }
 long long ZSTDMI_debugLastBatchWorkspace(const ZSTD_DCtx* d) { return d ? d->lastBatchWs : -1; }
 size_t ZSTDMI_decompressRange(ZSTD_DCtx* d, void* dst, size_t dstCapacity, const void* src, size_t srcSize, unsigned long long offset, size_t length)
 {

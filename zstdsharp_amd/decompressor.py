@@ -63,6 +63,21 @@ class Decompressor(_PrefixHolder):
         ensure_zstd_success(self._lib, self._lib.ZSTDMI_DCtx_setBatchUnsized(self.dctx, 1 if on else 0))
         self._batch_unsized = bool(on)
 
+    # ---- batches enqueued from the device (ZSTDMI_DCtx_prepareBatchAsync; batch.decompress_batch_async runs them) ----
+    def PrepareBatchAsync(self, max_entries: int, src_size_bound: int, max_content: int, max_frames: int = 0, max_blocks: int = 0,
+                          max_sequences: int = 0):
+        """Everything decompress_batch_async needs the host for, once: binds the device, uploads the dictionary in force (loaded,
+        RefDDict, the ZSTD_d_refMultipleDDicts set) and sizes every work buffer for calls of at most max_entries entries of at most
+        src_size_bound compressed bytes each (1 .. 4 MiB) that regenerate at most max_content bytes together.  max_frames (0 =
+        max_entries), max_blocks (0 = max_frames + max_content / 16384, enough for every stream this library writes) and max_sequences
+        (0 = max_content / 3 + 64, exact for valid input) bound the call's frames, blocks and sequence records; an entry beyond a limit
+        answers workSpace_tooSmall (-66).  Any later setter, LoadDictionary, RefDDict or RefPrefix invalidates the prepare."""
+        self._ensure_not_disposed()
+        lim = _ffi.DBatchLimits(int(max_entries), int(src_size_bound), int(max_content), int(max_frames), int(max_blocks), int(max_sequences))
+        ensure_zstd_success(self._lib, self._lib.ZSTDMI_DCtx_prepareBatchAsync(self.dctx, ctypes.byref(lim)))
+
+    prepare_batch_async = PrepareBatchAsync
+
     def LoadDictionary(self, dict_bytes):                     # S/Decompressor.cs:29-36
         self._ensure_not_disposed()
         addr, n, keep = _as_buffer(dict_bytes if dict_bytes is not None else b"")
