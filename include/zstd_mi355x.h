@@ -464,6 +464,47 @@ long long ZSTDMI_debugLastBatchSetChunks(const ZSTD_CCtx* cctx);  /* chunks of t
 size_t ZSTDMI_CCtx_prepareBatchAsync(ZSTD_CCtx* cctx, size_t maxEntries, size_t srcSizeBound);
 size_t ZSTDMI_compressBatchAsync(ZSTD_CCtx* cctx, const void* const* d_srcs, const size_t* d_srcSizes, size_t n,
                                  void* const* d_dsts, const size_t* d_dstCapacities, size_t* d_dstSizes);
+/* ---- entries of several blocks: the second prepare ----
+ * ZSTDMI_CCtx_prepareBatchAsyncLimits is the prepare above for a bound of up to 4 MiB - 1, shaped like the decoder's limits; the call
+ * itself is ZSTDMI_compressBatchAsync, which serves whichever prepare is valid.  A context holds one prepare; a later one of either
+ * kind replaces it.  ZSTDMI_CCtx_prepareBatchAsync keeps its behaviour exactly, its refusal of a bound above one block included.
+ * The prepare resolves parameters, dictionary and framing for an entry of exactly srcSizeBound bytes, as ZSTDMI_compressBatch would,
+ * and accepts the bound wherever that call would put such an entry into a shared pass: blocks behind LDS history in multi-block frames
+ * (16 KiB blocks in 64 KiB frames at levels 1-2, 48 / 32 KiB blocks in frames of 240-256 KiB at levels >= 3,
+ * ZSTDMI_CCtx_setHistory(h > 0) above level 2, ZSTD_c_windowLog >= 16), and independent frames behind a dictionary (staged tail, the
+ * dictionary index at each of its settings, a referenced CDict, dictionary entropy tables).  A chunk is one block.  The entries of a
+ * call are cut into chunks ON THE DEVICE: the host computes every grid from n and the limits, min(maxChunks, n * ceil(srcSizeBound /
+ * chunkBytes)) chunk slots, and reads no count back; a slot the call does not fill compresses one idle byte that is placed nowhere.
+ * Workspaces are sized for maxChunks chunks (about 200 KiB of device memory each).  A bound that resolves to one block in a
+ * single-block frame, with maxChunks 0 or >= maxEntries, gives exactly the state of ZSTDMI_CCtx_prepareBatchAsync (maxChunks =
+ * maxEntries) and the call launches what it launches behind that prepare.
+ * Returns 0, or: GENERIC (NULL context or limits); parameter_outOfBound for maxEntries 0 or above the pass limit
+ * (ZSTDMI_CCtx_setPassChunks, at most 16384), a bound of 0 or >= 4 MiB, maxChunks above the pass limit or (checked behind the framing,
+ * so behind the device) below the chunks one entry of the bound needs, a non-zero reserved field; parameter_unsupported for several
+ * device workers, the seek-table switch, a pending ZSTD_CCtx_refPrefix (which stays pending) — these, and every out-of-bound answer but the
+ * one behind the framing, are given before a device is looked for — and for everything ZSTDMI_compressBatch would compress alone at that size: long-distance matching,
+ * ZSTDMI_CCtx_setSingleFrame, ZSTD_c_windowLog 10 .. 15 above one window, the fast strategy's full 64 KiB blocks with far candidates
+ * (level 1-2 with ZSTDMI_CCtx_setHistory(h > 0) or ZSTD_c_windowLog > 16), dictionary entropy tables in multi-block frames, more than
+ * 256 chunks per entry; and for ZSTDMI_CCtx_setEntropyCarry(1) where it would take effect (multi-block frames without a dictionary:
+ * its group count is a host launch argument); else the errors of the first prepare.  A refused prepare leaves the context without one.
+ * Per entry, d_dstSizes[i] is as above with this bound, and one answer more, by the decoder's rule: workSpace_tooSmall.  Count the
+ * entries that pass their argument checks and are not empty, in entry order: entry i is refused iff the sum of ceil(size / chunkBytes)
+ * over those entries up to and including i exceeds maxChunks, so every good entry behind a refused one is refused too; failed and empty
+ * entries count for nothing and keep their own answers.  Nothing of a refused entry is written.
+ * Bytes: the tier rule above, unchanged.  Every entry is cut with the bound's framing: an entry of 40 KiB under a level-1 bound of
+ * 256 KiB becomes three 16 KiB blocks in one frame, not one 40 KiB block.  Valid, decodes on its own, and equal to
+ * ZSTDMI_compressBatch's bytes exactly where the entry's own size resolves to the bound's framing and launch parameters.
+ * ZSTDMI_CCtx_getBatchAsyncPlan: what the valid prepare (of either kind) resolved, so that a caller can size maxChunks and its
+ * destinations: chunkBytes, frameBlocks (0: every chunk a frame of its own) and maxChunks, each through a pointer that may be NULL.
+ * Returns 0; GENERIC for a NULL context; stage_wrong without a valid prepare. */
+typedef struct {
+    size_t maxEntries;    /* entries per call, > 0 */
+    size_t srcSizeBound;  /* bytes of one entry, 1 .. 4 MiB - 1 */
+    size_t maxChunks;     /* blocks of one call, all entries together; 0 = min(maxEntries * ceil(srcSizeBound / chunkBytes), pass limit) */
+    size_t reserved[3];   /* must be 0 */
+} ZSTDMI_CBatchLimits;
+size_t ZSTDMI_CCtx_prepareBatchAsyncLimits(ZSTD_CCtx* cctx, const ZSTDMI_CBatchLimits* limits);
+size_t ZSTDMI_CCtx_getBatchAsyncPlan(const ZSTD_CCtx* cctx, size_t* chunkBytes, size_t* frameBlocks, size_t* maxChunks);
 /* diagnostics: blocking waits the compressor's host code has made for this context (stream waits, read-backs, blocking copies, the
  * wait behind an enqueued batch), and growths of its device buffers, since it was created; -1 without a context.  Neither moves
  * across ZSTDMI_compressBatchAsync. */

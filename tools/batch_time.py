@@ -18,6 +18,9 @@ python tools/batch_time.py [MiB] [--dict-entropy] [--dict-row] [--frames-rows] [
                    Then the decode rows (ZSTDMI_decompressBatchAsync) over those frames: one ZSTDMI_DCtx_prepareBatchAsync per row with
                    limits of 1x, 4x and 16x what the call holds, all entries in one async call per measurement, the same (a), (b), and
                    (c) ZSTDMI_decompressBatch in the same session; every entry's size and bytes are compared afterwards.
+                   Then the rows of ZSTDMI_CCtx_prepareBatchAsyncLimits: text entries of 256 KiB at levels 1 and 3, the same (a), (b),
+                   (c): all entries in one async call; 256 entries per call with a grid of exactly the chunk slots the entries fill;
+                   and 256 per call with four times as many slots (a bound of 1 MiB), the price of surplus slots.
   --unsized-rows : only the rows of ZSTDMI_DCtx_setBatchUnsized, decompression alone: text and Zipf entries of 4 KiB at level 3,
                    (a) written with content sizes, one batch call; (b) written with ZSTD_c_contentSizeFlag = 0 and the window restated as
                    the 2^19 a streaming encoder declares (each frame's bound: 128 KiB), the switch off — every entry goes alone: timed on
@@ -298,8 +301,75 @@ def async_decode_rows(level, n, size, cap, src, comp, got):
     del out_a, out_s
 
 
+def async_frames_rows():
+    """the rows of ZSTDMI_CCtx_prepareBatchAsyncLimits: text entries of 256 KiB, all in one async call, then 256 per call back to back.
+    A call's grid is min(maxChunks, n * ceil(bound / chunkBytes)) chunk slots, so surplus slots come from a bound above the entries:
+    the 1x rows prepare the entries' own size (every slot filled; bytes compared with the synchronous batch), the 4x row a bound of
+    1 MiB (four slots launched per slot filled, which fits the pass limit at 256 entries per call; another tier, so only sizes and
+    ratio are compared)."""
+    size = 256 << 10
+    n = total // size
+    src = torch.from_numpy(np.frombuffer(datagen.gen("text", 16 * MiB, 5), dtype=np.uint8).copy()).cuda().repeat(total // (16 * MiB))
+    idx = torch.arange(n, dtype=torch.int64, device="cuda")
+    cap = lib.ZSTD_compressBound(size)
+    print(f"{n} text entries of 256 KiB; ms for all entries (GB/s of content)", flush=True)
+    for level in (1, 3):
+        dst_s = torch.zeros(n * cap + MiB, dtype=torch.uint8, device="cuda")
+        cs = lib.ZSTD_createCCtx()
+        lib.ZSTD_CCtx_setParameter(cs, 100, level)
+        s_ptr, d_ptr = ptrs(src.data_ptr(), [i * size for i in range(n)]), ptrs(dst_s.data_ptr(), [i * cap for i in range(n)])
+        s_sz, d_cap, got = sizes([size] * n), sizes([cap] * n), (ctypes.c_size_t * n)()
+        sync = best_of(lambda: ok(lib.ZSTDMI_compressBatch(cs, s_ptr, s_sz, n, d_ptr, d_cap, got)))
+        assert lib.ZSTDMI_debugLastBatchAlone(cs) == 0
+        lib.ZSTD_freeCCtx(cs)
+        for per_call, k in ((n, 1), (256, 1), (256, 4)):
+            dst_a = torch.zeros(n * cap + MiB, dtype=torch.uint8, device="cuda")
+            c = lib.ZSTD_createCCtx()
+            lib.ZSTD_CCtx_setParameter(c, 100, level)
+            lim = z._ffi.CBatchLimits(per_call, size * k, 0)
+            ok(lib.ZSTDMI_CCtx_prepareBatchAsyncLimits(c, ctypes.byref(lim)))
+            cb, fb, mc = ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_size_t()
+            ok(lib.ZSTDMI_CCtx_getBatchAsyncPlan(c, ctypes.byref(cb), ctypes.byref(fb), ctypes.byref(mc)))
+            ok(lib.ZSTDMI_CCtx_setStream(c, torch.cuda.current_stream().cuda_stream or 1))
+            srcs, dsts = src.data_ptr() + idx * size, dst_a.data_ptr() + idx * cap
+            szs, caps = torch.full((n,), size, dtype=torch.int64, device="cuda"), torch.full((n,), cap, dtype=torch.int64, device="cuda")
+            out = torch.empty(n, dtype=torch.int64, device="cuda")
+            returned = [0.0]
+
+            def enqueue():
+                t0 = time.perf_counter()
+                for at in range(0, n, per_call):
+                    m = min(per_call, n - at)
+                    ok(lib.ZSTDMI_compressBatchAsync(c, srcs.data_ptr() + 8 * at, szs.data_ptr() + 8 * at, m, dsts.data_ptr() + 8 * at, caps.data_ptr() + 8 * at, out.data_ptr() + 8 * at))
+                returned[0] = time.perf_counter() - t0
+                torch.cuda.synchronize()
+
+            waits = lib.ZSTDMI_debugHostWaits(c)
+            ret, done = 1e9, 1e9
+            enqueue()
+            for _ in range(3):
+                torch.cuda.synchronize(); t0 = time.perf_counter()
+                enqueue()
+                done = min(done, time.perf_counter() - t0); ret = min(ret, returned[0])
+            assert lib.ZSTDMI_debugHostWaits(c) == waits
+            sizes_a = out.cpu().tolist()
+            assert all(0 < s <= cap for s in sizes_a)
+            if k == 1:
+                assert sizes_a == list(got) and bool(torch.equal(dst_a, dst_s))
+            gbs = lambda t: total / t / 1e9
+            filled = -(-size // cb.value)
+            print(f"| text 256 KiB L{level} | {n:5d} | {per_call:4d} per call, bound {size * k // 1024:4d} KiB: {mc.value} slots of {cb.value} B per call, {per_call * filled} filled | ratio {sum(sizes_a) / total:.3f} "
+                  f"| (a) async calls returned {ret * 1e3:7.2f} | (b) ... and the stream drained {done * 1e3:7.2f} ({gbs(done):6.1f}) | (c) synchronous batch {sync * 1e3:7.2f} ({gbs(sync):6.1f}), ratio {sum(got) / total:.3f} |", flush=True)
+            lib.ZSTD_freeCCtx(c)
+            del dst_a
+            torch.cuda.empty_cache()
+        del dst_s
+        torch.cuda.empty_cache()
+
+
 if "--async" in FLAGS:
     async_rows()
+    async_frames_rows()
     sys.exit(0)
 if DICT_INDEX_ROWS:
     dict_index_rows()

@@ -37,6 +37,11 @@ class DBatchLimits(ctypes.Structure):
                 ("maxBlocks", c_size_t), ("maxSequences", c_size_t)]
 
 
+class CBatchLimits(ctypes.Structure):
+    """ZSTDMI_CBatchLimits: what one ZSTDMI_compressBatchAsync call may hold at most (maxChunks 0 = the default; reserved = 0)."""
+    _fields_ = [("maxEntries", c_size_t), ("srcSizeBound", c_size_t), ("maxChunks", c_size_t), ("reserved", c_size_t * 3)]
+
+
 # name -> (restype, argtypes); every symbol include/zstd_mi355x.h declares
 SIGNATURES = {
     "ZSTD_createCCtx": (c_void_p, []),
@@ -126,6 +131,8 @@ SIGNATURES = {
     "ZSTDMI_CCtx_prepareBatchAsync": (c_size_t, [c_void_p, c_size_t, c_size_t]),
     # (the five arrays are device memory: plain addresses)
     "ZSTDMI_compressBatchAsync": (c_size_t, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
+    "ZSTDMI_CCtx_prepareBatchAsyncLimits": (c_size_t, [c_void_p, ctypes.POINTER(CBatchLimits)]),
+    "ZSTDMI_CCtx_getBatchAsyncPlan": (c_size_t, [c_void_p, ctypes.POINTER(c_size_t), ctypes.POINTER(c_size_t), ctypes.POINTER(c_size_t)]),
     "ZSTDMI_debugHostWaits": (ctypes.c_longlong, [c_void_p]),
     "ZSTDMI_debugDeviceAllocs": (ctypes.c_longlong, [c_void_p]),
     "ZSTDMI_batchAsyncWorkspaceD": (c_size_t, [ctypes.POINTER(DBatchLimits)]),

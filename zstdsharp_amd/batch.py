@@ -116,9 +116,10 @@ def compress_batch(compressor, items, cdicts=None):
 
 
 def compress_batch_async(compressor, srcs, sizes, dsts, caps, out_sizes=None):
-    """ZSTDMI_compressBatchAsync after Compressor.PrepareBatchAsync: srcs, sizes, dsts, caps are contiguous CUDA int64 tensors of n
-    entries each (pointers as integers, e.g. base.data_ptr() + offsets computed on the device) -> out_sizes, a CUDA int64 tensor: entry
-    i's compressed size, or its zstd error code as a negative value (-70 dstSize_tooSmall, -72 srcSize_wrong, -74 dstBuffer_null).
+    """ZSTDMI_compressBatchAsync after Compressor.PrepareBatchAsync or PrepareBatchAsyncLimits: srcs, sizes, dsts, caps are contiguous
+    CUDA int64 tensors of n entries each (pointers as integers, e.g. base.data_ptr() + offsets computed on the device) -> out_sizes, a CUDA int64 tensor: entry
+    i's compressed size, or its zstd error code as a negative value (-70 dstSize_tooSmall, -72 srcSize_wrong, -74 dstBuffer_null; after
+    Compressor.PrepareBatchAsyncLimits also -66 workSpace_tooSmall for an entry beyond the prepared max_chunks).
     The work is enqueued on torch.cuda.current_stream() and the call returns: nothing is synchronised and nothing is copied to the
     host, so out_sizes and the destinations are for work queued on that stream behind it.  The tensors, the sources and the
     destinations must stay alive and unchanged until that stream has passed the work.  Raises ZstdException for the whole call's

@@ -255,7 +255,25 @@ class Compressor(_PrefixHolder):
         self._ensure_not_disposed()
         ensure_zstd_success(self._lib, self._lib.ZSTDMI_CCtx_prepareBatchAsync(self.cctx, int(max_entries), int(src_size_bound)))
 
-    prepare_batch_async = PrepareBatchAsync
+    def PrepareBatchAsyncLimits(self, max_entries: int, src_size_bound: int, max_chunks: int = 0):
+        """ZSTDMI_CCtx_prepareBatchAsyncLimits: PrepareBatchAsync for entries of up to 4 MiB - 1 bytes, cut into blocks on the device.
+        max_chunks: the blocks one call may hold, all entries together (0 = max_entries entries of the bound, at most the pass limit);
+        entries beyond it answer -66 (workSpace_tooSmall).  Replaces an earlier prepare of either kind.  Raises ZstdException
+        (parameter_outOfBound, parameter_unsupported) as the header states."""
+        self._ensure_not_disposed()
+        lim = _ffi.CBatchLimits(int(max_entries), int(src_size_bound), int(max_chunks))
+        ensure_zstd_success(self._lib, self._lib.ZSTDMI_CCtx_prepareBatchAsyncLimits(self.cctx, ctypes.byref(lim)))
+
+    @property
+    def batch_async_plan(self):
+        """ZSTDMI_CCtx_getBatchAsyncPlan -> (chunk_bytes, frame_blocks, max_chunks) of the valid prepare; ZstdException (stage_wrong)
+        without one."""
+        self._ensure_not_disposed()
+        cb, fb, mc = ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_size_t(0)
+        ensure_zstd_success(self._lib, self._lib.ZSTDMI_CCtx_getBatchAsyncPlan(self.cctx, ctypes.byref(cb), ctypes.byref(fb), ctypes.byref(mc)))
+        return cb.value, fb.value, mc.value
+
+    prepare_batch_async, prepare_batch_async_limits = PrepareBatchAsync, PrepareBatchAsyncLimits
 
     # ---- Wrap (S/Compressor.cs:78-96) ----
     def Wrap(self, src, dest=None, offset: int = 0):

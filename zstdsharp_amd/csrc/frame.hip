@@ -114,10 +114,7 @@ __global__ __launch_bounds__(256) void batch_plan_kernel(const void* const* __re
     if (e >= n) return;
     const u64 S = (u64)sizes[e], cap = (u64)caps[e];
     const u64 src = (u64)(uintptr_t)srcs[e], dst = (u64)(uintptr_t)dsts[e];
-    u32 v = kAsyncGood;
-    if (S > bound || (S && !src)) v = kErrSrcSizeWrong;
-    else if (dst < kAsyncBase) v = cap ? kErrDstBufferNull : kErrDstSizeTooSmall;        // (null; no device address lies below kAsyncBase)
-    else if (!S) v = cap < emptyLen ? (u32)kErrDstSizeTooSmall : (u32)kAsyncEmpty;
+    const u32 v = plan_verdict(src, S, dst, cap, bound, emptyLen);          // (zmi_batch_plan.h)
     const bool good = v == kAsyncGood;
     from[e] = good ? src : (u64)(uintptr_t)dummy;
     len[e] = good ? (u32)S : 1u;
@@ -151,6 +148,110 @@ __global__ __launch_bounds__(256) void batch_place_async_kernel(const ChunkMeta*
         answer = empty.len;
     } else answer = (u64)0 - (u64)v;
     offsets[e] = at;
+    dstSizes[e] = (size_t)answer;
+}
+
+// ---- the same batch with entries of several chunks (ZSTDMI_CCtx_prepareBatchAsyncLimits): the host knows the number of entries and a
+// chunk limit, never a size; the arithmetic is zmi_batch_plan.h's, which tests/host/batch_plan_harness.cpp holds against the host loop ----
+// plan, entries -> chunk ranges.  ONE workgroup of 1024 lanes, 16 consecutive entries per lane (n <= 16384, the pass limit): a lane's
+// verdicts and chunk counts stay in registers; the lanes' sums are scanned by wave (cross-lane shifts), the wave totals go through LDS.
+// The lane that holds the first refused entry (plan_refused) publishes its exclusive sum, the cut: every entFirst is held to it, so
+// refused, failed and empty entries own no chunk.  The caller's arrays are read here, once; the other two kernels read the copies.
+constexpr u32 kPlanPerLane = 16;
+__global__ __launch_bounds__(1024) void batch_plan_entries_kernel(const void* const* __restrict__ srcs, const size_t* __restrict__ sizes,
+                                                                  void* const* __restrict__ dsts, const size_t* __restrict__ caps, u32 n, u64 bound,
+                                                                  u32 emptyLen, u32 chunkBytes, u32 maxChunks, const AsyncEntryTab tab)
+{
+    __shared__ u32 waveSum[16];
+    __shared__ u32 cutAt;
+    const u32 tid = threadIdx.x, lane = lane_id(), wave = wave_id(), e0 = tid * kPlanPerLane;
+    if (tid == 0) cutAt = kPlanNoCut;
+    u32 cnt[kPlanPerLane], verdict[kPlanPerLane], mine = 0;
+#pragma unroll
+    for (u32 k = 0; k < kPlanPerLane; ++k) {
+        const u32 e = e0 + k;
+        cnt[k] = 0; verdict[k] = kAsyncEmpty;
+        if (e < n) {
+            const u64 S = (u64)sizes[e], cap = (u64)caps[e];
+            const u64 src = (u64)(uintptr_t)srcs[e], dst = (u64)(uintptr_t)dsts[e];
+            verdict[k] = plan_verdict(src, S, dst, cap, bound, emptyLen);
+            cnt[k] = plan_chunks(verdict[k], S, chunkBytes);
+            tab.src[e] = src; tab.size[e] = S; tab.cap[e] = cap;
+            tab.dst[e] = dst >= kAsyncBase ? dst - kAsyncBase : 0;
+        }
+        mine += cnt[k];
+    }
+    const u32 incl = wave_scan_incl(mine);
+    if (lane == 63) waveSum[wave] = incl;
+    __syncthreads();
+    u32 before = 0, all = 0;
+#pragma unroll
+    for (u32 k = 0; k < 16; k++) { const u32 s = waveSum[k]; all += s; if (k < wave) before += s; }
+    const u32 first = before + incl - mine;             // the exclusive sum in front of this lane's entries
+    u32 run = first;
+#pragma unroll
+    for (u32 k = 0; k < kPlanPerLane; ++k) {
+        if (plan_is_cut(run, cnt[k], maxChunks)) cutAt = run;     // (one entry at most)
+        run += cnt[k];
+    }
+    __syncthreads();
+    const u32 cut = cutAt;
+    run = first;
+#pragma unroll
+    for (u32 k = 0; k < kPlanPerLane; ++k) {
+        const u32 e = e0 + k;
+        if (e < n) {
+            tab.first[e] = plan_first(run, cut);
+            tab.verdict[e] = plan_limited(verdict[k], run, cnt[k], maxChunks);
+        }
+        run += cnt[k];
+    }
+    if (tid == 0) tab.first[n] = plan_first(all, cut);
+}
+
+// plan, chunks: one lane per chunk slot of the grid.  A slot below the call's total finds its entry by a binary search in entFirst and
+// writes what the stages read for that chunk; a slot at or beyond it becomes what an ineligible entry is in batch_plan_kernel: one byte
+// read from `dummy`, a frame of its own (the placement gives it the offset kAsyncSpan).  frame: null where every chunk is a frame.
+__global__ __launch_bounds__(256) void batch_plan_chunks_kernel(const AsyncEntryTab tab, u32 n, u32 nLaunch, u32 chunkBytes, u32 frameBlocks,
+                                                                const u8* __restrict__ dummy, u64* __restrict__ from, u32* __restrict__ len,
+                                                                u32* __restrict__ frame)
+{
+    const u32 c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= nLaunch) return;
+    PlanChunk r = plan_chunk_idle((u64)(uintptr_t)dummy);
+    if (c < tab.first[n]) {
+        const u32 e = plan_owner(tab.first, n, c);
+        r = plan_chunk(tab.src[e], tab.size[e], c - tab.first[e], chunkBytes, frameBlocks);
+    }
+    from[c] = r.from;
+    len[c] = r.len;
+    if (frame) frame[c] = r.frameWord;
+}
+
+// place (batch_place_async_kernel for entries of several chunks): entry e's frames lie one behind the other from its destination; their
+// sum is compared with the capacity, and the size or the error goes straight into the caller's column.  Every chunk of an entry that
+// writes nothing, and every idle slot, gets the offset kAsyncSpan.  One lane per entry; the idle slots are dealt to the grid's lanes.
+__global__ __launch_bounds__(256) void batch_place_async_frames_kernel(const ChunkMeta* __restrict__ meta, u32 n, u32 nLaunch, const AsyncEntryTab tab,
+                                                                       const AsyncEmptyFrame empty, u64* __restrict__ offsets, size_t* __restrict__ dstSizes)
+{
+    const u32 e = blockIdx.x * 256 + threadIdx.x;
+    for (u32 c = tab.first[n] + e; c < nLaunch; c += gridDim.x * 256) offsets[c] = kAsyncSpan;
+    if (e >= n) return;
+    const u32 v = tab.verdict[e];
+    u64 answer;
+    if (v == kAsyncGood) {
+        const u32 c0 = tab.first[e], c1 = tab.first[e + 1];
+        u64 sum = 0;
+        for (u32 c = c0; c < c1; ++c) sum += meta[c].outSize;
+        const bool fits = sum <= tab.cap[e];
+        u64 at = tab.dst[e];
+        for (u32 c = c0; c < c1; ++c) { offsets[c] = fits ? at : kAsyncSpan; at += meta[c].outSize; }
+        answer = fits ? sum : (u64)0 - (u64)kErrDstSizeTooSmall;
+    } else if (v == kAsyncEmpty) {
+        u8* const d = reinterpret_cast<u8*>((uintptr_t)(tab.dst[e] + kAsyncBase));
+        for (u32 i = 0; i < empty.len; ++i) d[i] = empty.bytes[i];
+        answer = empty.len;
+    } else answer = (u64)0 - (u64)v;
     dstSizes[e] = (size_t)answer;
 }
 
@@ -466,6 +567,24 @@ void launch_batch_place_async(const ChunkMeta* meta, u32 n, const u64* entDst, c
 {
     assert(empty.len <= sizeof empty.bytes);
     hipLaunchKernelGGL(batch_place_async_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, meta, n, entDst, entCap, verdict, empty, offsets, dstSizes);
+}
+void launch_batch_plan_entries(const void* const* srcs, const size_t* sizes, void* const* dsts, const size_t* caps, u32 n, u64 bound, u32 emptyLen,
+                               u32 chunkBytes, u32 maxChunks, const AsyncEntryTab& tab, hipStream_t stream)
+{
+    assert(n && n <= 1024 * kPlanPerLane && bound <= kAsyncBoundMax && chunkBytes);
+    hipLaunchKernelGGL(batch_plan_entries_kernel, dim3(1), dim3(1024), 0, stream, srcs, sizes, dsts, caps, n, bound, emptyLen, chunkBytes, maxChunks, tab);
+}
+void launch_batch_plan_chunks(const AsyncEntryTab& tab, u32 n, u32 nLaunch, u32 chunkBytes, u32 frameBlocks, const u8* dummy, u64* from, u32* len, u32* frame,
+                              hipStream_t stream)
+{
+    assert(!frameBlocks == !frame);
+    hipLaunchKernelGGL(batch_plan_chunks_kernel, dim3((nLaunch + 255) / 256), dim3(256), 0, stream, tab, n, nLaunch, chunkBytes, frameBlocks, dummy, from, len, frame);
+}
+void launch_batch_place_async_frames(const ChunkMeta* meta, u32 n, u32 nLaunch, const AsyncEntryTab& tab, AsyncEmptyFrame empty, u64* offsets, size_t* dstSizes,
+                                     hipStream_t stream)
+{
+    assert(empty.len <= sizeof empty.bytes);
+    hipLaunchKernelGGL(batch_place_async_frames_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, meta, n, nLaunch, tab, empty, offsets, dstSizes);
 }
 
 } // namespace zmi

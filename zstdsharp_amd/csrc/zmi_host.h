@@ -11,6 +11,7 @@
 #include <new>
 #include "zmi_common.h"
 #include "zmi_frame.h"
+#include "zmi_batch_plan.h"
 #include "zmi_dictset.h"
 #include "zmi_cdictset.h"
 #include "../../include/zstd_mi355x.h"
@@ -82,15 +83,23 @@ void launch_batch_place(const ChunkMeta* meta, u32 nEntries, const u32* entFirst
 // layout the stages read (one chunk per entry), entDst as an offset from kAsyncBase, and a verdict per entry (AsyncVerdict); an entry
 // that runs no pass becomes one byte read from `dummy`.  place: sizes and statuses straight into the caller's column, the empty frame
 // (by value) for entries of size 0, the offset kAsyncSpan for every entry that writes nothing.
-// kAsyncBase: the "base pointer" huf_encode and gather get with absolute addresses (not null: a null dst is huf_encode's test hook);
-// kAsyncSpan: their dstCapacity — above every device address, far from wrapping when a frame's size is added
-constexpr u64 kAsyncBase = 4096, kAsyncSpan = (u64)1 << 62;
-enum AsyncVerdict : u32 { kAsyncGood = 0, kAsyncEmpty = 0xFFFFFFFFu };      // (else: the zstd error code the entry answers)
+// (kAsyncBase, kAsyncSpan, AsyncVerdict: zmi_batch_plan.h)
 struct AsyncEmptyFrame { u8 bytes[16]; u32 len; };
 void launch_batch_plan(const void* const* srcs, const size_t* sizes, void* const* dsts, const size_t* caps, u32 n, u64 bound, u32 emptyLen, const u8* dummy,
                        u64* from, u64* entDst, u64* entCap, u32* len, u32* entFirst, u32* verdict, hipStream_t stream);
 void launch_batch_place_async(const ChunkMeta* meta, u32 n, const u64* entDst, const u64* entCap, const u32* verdict, AsyncEmptyFrame empty,
                               u64* offsets, size_t* dstSizes, hipStream_t stream);
+// entries of several chunks (ZSTDMI_CCtx_prepareBatchAsyncLimits; the arithmetic is zmi_batch_plan.h's).  The entry table: what the
+// plan keeps per entry, and the grid's chunk slots.  plan_entries: verdicts (workSpace_tooSmall by the chunk limit included), the
+// entries' first chunks entFirst[0 .. n] by a scan, the caller's arrays copied.  plan_chunks: from / len / frame (null: every chunk a
+// frame of its own) for the nLaunch chunk slots, those at or beyond entFirst[n] idle.  place: each entry's frames one behind the other.
+struct AsyncEntryTab { u64* src; u64* size; u64* dst; u64* cap; u32* first; u32* verdict; };
+void launch_batch_plan_entries(const void* const* srcs, const size_t* sizes, void* const* dsts, const size_t* caps, u32 n, u64 bound, u32 emptyLen,
+                               u32 chunkBytes, u32 maxChunks, const AsyncEntryTab& tab, hipStream_t stream);
+void launch_batch_plan_chunks(const AsyncEntryTab& tab, u32 n, u32 nLaunch, u32 chunkBytes, u32 frameBlocks, const u8* dummy, u64* from, u32* len, u32* frame,
+                              hipStream_t stream);
+void launch_batch_place_async_frames(const ChunkMeta* meta, u32 n, u32 nLaunch, const AsyncEntryTab& tab, AsyncEmptyFrame empty, u64* offsets, size_t* dstSizes,
+                                     hipStream_t stream);
 void launch_seek_entries(const u64* offsets, const u64* total, u32 nChunks, const FrameLayout& frames, u32* entries, hipStream_t stream);
 void launch_seek_table(const u32* entries, u32 n, u8* dst, hipStream_t stream);
 // a pack (ZSTDMI_compressPack, frame.hip): a batched pass's seek-table rows per entry (entSeek[e] = the row of entry e's first frame, rows

@@ -487,7 +487,9 @@ static Framing resolve_framing(const ZSTD_CCtx* c, const CallParams& cp, size_t 
 // What ZSTDMI_CCtx_prepareBatchAsync resolved: the parameters and the framing of an entry of exactly `bound` bytes — one chunk, one
 // single-block frame —, the empty frame under those parameters, and the generation it holds for.  No device pointer is kept: the launch
 // state is derived again per call (launch_state, host arithmetic), and the buffers, which only ever grow, are asked where they are.
-struct AsyncPrep { u64 gen; u32 maxEntries; size_t bound; CallParams cp; Framing fr; AsyncEmptyFrame empty; };
+// maxChunks: the chunks one call may hold (the one-block prepare: maxEntries).  planned (ZSTDMI_CCtx_prepareBatchAsyncLimits for entries of
+// several chunks, or with a chunk limit below maxEntries): the call cuts the entries into chunks on the device (zmi_batch_plan.h).
+struct AsyncPrep { u64 gen; u32 maxEntries; size_t bound; CallParams cp; Framing fr; AsyncEmptyFrame empty; u32 maxChunks = 0; bool planned = false; };
 
 // What the kernels of a pass are launched with for a framing: derived in one place for the single call (compress_range) and the
 // batch (compress_entries), whose bytes must be the same.
@@ -2152,8 +2154,110 @@ static size_t prepare_batch_async_impl(ZSTD_CCtx* c, size_t maxEntries, size_t b
     u8 f[18 + 3 + 4]; const size_t n = empty_frame_write(cp, f);
     assert(n <= sizeof P->empty.bytes);
     memcpy(P->empty.bytes, f, n); P->empty.len = (u32)n;
+    P->maxChunks = (u32)maxEntries;
     c->asyncPrep = P;
     return 0;
+}
+// The pass's table of a planned call, laid out once for the prepared limits (nEnt entries, nCh chunks):
+// from[nCh] | src | size | dst | cap [nEnt] (u64) | len[nCh] | frame[nCh] | first[nEnt + 1] | verdict[nEnt] (u32) | the idle slots' byte
+struct AsyncPlanTab { size_t atSrc, atSize, atDst, atCap, atLen, atFrame, atFirst, atVerdict, atDummy, bytes; };
+static AsyncPlanTab async_plan_tab(u32 nEnt, u32 nCh)
+{
+    AsyncPlanTab t;
+    t.atSrc = (size_t)nCh * 8; t.atSize = t.atSrc + (size_t)nEnt * 8; t.atDst = t.atSize + (size_t)nEnt * 8; t.atCap = t.atDst + (size_t)nEnt * 8;
+    t.atLen = t.atCap + (size_t)nEnt * 8; t.atFrame = t.atLen + (size_t)nCh * 4; t.atFirst = t.atFrame + (size_t)nCh * 4;
+    t.atVerdict = t.atFirst + ((size_t)nEnt + 1) * 4; t.atDummy = (t.atVerdict + (size_t)nEnt * 4 + 7) & ~(size_t)7; t.bytes = t.atDummy + 8;
+    return t;
+}
+static u32 chunks_of(size_t bytes, u32 chunkBytes) { return (u32)((bytes + chunkBytes - 1) / chunkBytes); }
+// ZSTDMI_CCtx_prepareBatchAsyncLimits: the prepare above for a bound of any number of chunks that compress_entries would batch
+static size_t prepare_batch_async_limits_impl(ZSTD_CCtx* c, const ZSTDMI_CBatchLimits* L)
+{
+    if (!c || !L) return ZERR(kErrGeneric);
+    delete c->asyncPrep; c->asyncPrep = nullptr;
+    const u32 passLimit = batch_pass_limit(c);
+    const size_t bound = L->srcSizeBound;
+    if (!L->maxEntries || L->maxEntries > passLimit || !bound || bound > kAsyncBoundMax || L->maxChunks > passLimit ||
+        L->reserved[0] || L->reserved[1] || L->reserved[2]) return ZERR(kErrParameterOutOfBound);
+    if (c->workers.size() > 1 || c->seekTable || c->pfx) return ZERR(kErrParameterUnsupported);
+    const CallParams cp = sticky_params(c);
+    size_t e = check_call_params(cp); if (isErr(e)) return e;
+    e = cctx_bind(c); if (isErr(e)) return e;
+    e = cctx_sync_dictionary(c); if (isErr(e)) return e;
+    const Framing fr = resolve_framing(c, cp, bound);
+    if (!entry_batched(c, cp, bound, fr, passLimit, call_dict_ctables(c, cp) != nullptr, false)) return ZERR(kErrParameterUnsupported);
+    const LaunchState ls = launch_state(c, cp, fr);
+    if (carry_active(c, cp, fr, ls)) return ZERR(kErrParameterUnsupported);       // (its group count is a host launch argument)
+    const u32 perEntry = chunks_of(bound, fr.chunkBytes);
+    if (L->maxChunks && L->maxChunks < perEntry) return ZERR(kErrParameterOutOfBound);
+    const u64 most = (u64)L->maxEntries * perEntry;
+    const u32 maxChunks = L->maxChunks ? (u32)L->maxChunks : (u32)(most < passLimit ? most : passLimit);
+    // one block in a single-block frame and room for every entry: the one-block prepare's state, and so its launches
+    if (perEntry == 1 && !fr.frameBlocks && maxChunks >= L->maxEntries) return prepare_batch_async_impl(c, L->maxEntries, bound);
+    const u32 nCh = maxChunks;
+    if (!cctx_workspace(c, nCh) || (ls.regionParse && !cctx_cand_workspace(c, nCh, ls.hcChains)) || (ls.regionParse && fr.dictIndex && !cctx_dist_workspace(c, nCh)) ||
+        !c->batchStage.ensure((u64)nCh * fr.chunkBytes + 64) || !c->batchTab.ensure(async_plan_tab((u32)L->maxEntries, nCh).bytes)) return ZERR(kErrMemoryAllocation);
+    if (!c->asyncEv && hipEventCreateWithFlags(&c->asyncEv, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); c->asyncEv = nullptr; return ZERR(kErrMemoryAllocation); }
+    AsyncPrep* const P = new AsyncPrep{ cctx_gen(c), (u32)L->maxEntries, bound, cp, fr, {} };
+    u8 f[18 + 3 + 4]; const size_t n = empty_frame_write(cp, f);
+    assert(n <= sizeof P->empty.bytes);
+    memcpy(P->empty.bytes, f, n); P->empty.len = (u32)n;
+    P->maxChunks = maxChunks; P->planned = true;
+    c->asyncPrep = P;
+    return 0;
+}
+static size_t batch_async_plan_impl(const ZSTD_CCtx* c, size_t* chunkBytes, size_t* frameBlocks, size_t* maxChunks)
+{
+    if (!c) return ZERR(kErrGeneric);
+    const AsyncPrep* const P = c->asyncPrep;
+    if (!P || P->gen != cctx_gen(c)) return ZERR(kErrStageWrong);
+    if (chunkBytes) *chunkBytes = P->fr.chunkBytes;
+    if (frameBlocks) *frameBlocks = P->fr.frameBlocks;
+    if (maxChunks) *maxChunks = P->maxChunks;
+    return 0;
+}
+// the event behind an enqueued pass (cctx_async_drain waits for it)
+static size_t async_enqueued(ZSTD_CCtx* c, hipStream_t s)
+{
+    if (hipEventRecord(c->asyncEv, s) != hipSuccess) {      // (without the event nothing may stay in flight)
+        (void)hipGetLastError();
+        return stream_wait(s);
+    }
+    c->asyncPending = true;
+    return 0;
+}
+// A planned call: compress_entries' table-form pass (its frames from chunk_frame_word; independent frames where the framing has no
+// frameBlocks) with the two plan kernels in the place of the host loop and the upload.  Every grid is nLaunch chunk slots, host
+// arithmetic on the entry count and the prepared limits; slots beyond the call's chunks compress one idle byte that is placed nowhere.
+static size_t compress_batch_async_planned(ZSTD_CCtx* c, const AsyncPrep* P, const void* const* d_srcs, const size_t* d_srcSizes, u32 n, void* const* d_dsts,
+                                           const size_t* d_dstCapacities, size_t* d_dstSizes)
+{
+    hipStream_t s = c->stream;
+    const Framing& fr = P->fr;
+    const LaunchState ls = launch_state(c, P->cp, fr);
+    const u32 cb = fr.chunkBytes, frameBlocks = fr.frameBlocks;
+    const u64 most = (u64)n * chunks_of(P->bound, cb);
+    const u32 nCh = (u32)(most < P->maxChunks ? most : P->maxChunks);
+    const AsyncPlanTab t = async_plan_tab(P->maxEntries, P->maxChunks);
+    u8* const dTab = (u8*)c->batchTab.p;
+    u64* const dFrom = (u64*)dTab; u32* const dLen = (u32*)(dTab + t.atLen); u32* const dFrame = frameBlocks ? (u32*)(dTab + t.atFrame) : nullptr;
+    const AsyncEntryTab et = { (u64*)(dTab + t.atSrc), (u64*)(dTab + t.atSize), (u64*)(dTab + t.atDst), (u64*)(dTab + t.atCap), (u32*)(dTab + t.atFirst), (u32*)(dTab + t.atVerdict) };
+    const u8* stage = (const u8*)c->batchStage.p;
+    Seq* seqs = (Seq*)c->seqs.p; u8* lits = (u8*)c->lits.p; ChunkMeta* meta = (ChunkMeta*)c->meta.p;
+    HufTable* tables = (HufTable*)c->tables.p; u8* slots = (u8*)c->slots.p; u64* offsets = (u64*)c->offsets.p;
+    const u64 stagedBytes = (u64)nCh * cb;
+    launch_batch_plan_entries(d_srcs, d_srcSizes, d_dsts, d_dstCapacities, n, P->bound, P->empty.len, cb, P->maxChunks, et, s);
+    launch_batch_plan_chunks(et, n, nCh, cb, frameBlocks, dTab + t.atDummy, dFrom, dLen, dFrame, s);
+    launch_batch_stage(dFrom, dLen, (u8*)c->batchStage.p, nCh, cb, s);
+    const FrameLayout frames = dFrame ? layout_table(cb, frameBlocks, dFrame) : layout_arith(cb, 0, stagedBytes);
+    launch_lz(pass_lz(c, ls, fr, stage, stagedBytes, nCh, nCh, frames, dLen));
+    launch_huf_build(lits, meta, tables, slots, nCh, fr.rs.rawLiterals, stage, frames, s, c->timer.hook(), ls.dct);
+    if (P->cp.checksumFlag) launch_xxh64(stage, meta, nCh, frames, s, dLen);
+    launch_seq_encode(seqs, meta, slots, nCh, ls.strategy, ls.header, 1, ls.initReps, frames, s, ls.dct);
+    launch_batch_place_async_frames(meta, n, nCh, et, P->empty, offsets, d_dstSizes, s);
+    launch_huf_encode(lits, meta, tables, slots, (u8*)(uintptr_t)kAsyncBase, offsets, kAsyncSpan, nCh, stage, cb, s, ls.dct != nullptr);
+    launch_gather(stage, stagedBytes, slots, meta, offsets, (u8*)(uintptr_t)kAsyncBase, kAsyncSpan, nCh, cb, s);
+    return async_enqueued(c, s);
 }
 // One pass of compress_entries between its table upload and its read-back, with the plan kernel in the place of the first and the
 // caller's column in the place of the second: kernels (and the finder's two 4-byte hipMemsetAsync) only.
@@ -2170,6 +2274,7 @@ static size_t compress_batch_async_impl(ZSTD_CCtx* c, const void* const* d_srcs,
     c->timer.enabled = false;       // (stage events belong to calls that wait for them)
     c->lastRegionList = nullptr; c->lastCarryGroups = 0; c->lastBatchAlone = 0; c->lastBatchPasses = 1; c->lastBatchSetChunks = 0; c->lastChunks = 0;
     hipStream_t s = c->stream;
+    if (P->planned) return compress_batch_async_planned(c, P, d_srcs, d_srcSizes, (u32)n, d_dsts, d_dstCapacities, d_dstSizes);
     const Framing& fr = P->fr;
     const LaunchState ls = launch_state(c, P->cp, fr);
     const u32 nCh = (u32)n, cb = fr.chunkBytes;
@@ -2191,12 +2296,15 @@ static size_t compress_batch_async_impl(ZSTD_CCtx* c, const void* const* d_srcs,
     launch_batch_place_async(meta, nCh, dDst, dCap, dVerdict, P->empty, offsets, d_dstSizes, s);
     launch_huf_encode(lits, meta, tables, slots, (u8*)(uintptr_t)kAsyncBase, offsets, kAsyncSpan, nCh, stage, cb, s, ls.dct != nullptr);
     launch_gather(stage, stagedBytes, slots, meta, offsets, (u8*)(uintptr_t)kAsyncBase, kAsyncSpan, nCh, cb, s);
-    if (hipEventRecord(c->asyncEv, s) != hipSuccess) {      // (without the event nothing may stay in flight)
-        (void)hipGetLastError();
-        return stream_wait(s);
-    }
-    c->asyncPending = true;
-    return 0;
+    return async_enqueued(c, s);
+}
+extern "C" size_t ZSTDMI_CCtx_prepareBatchAsyncLimits(ZSTD_CCtx* c, const ZSTDMI_CBatchLimits* limits)
+{
+    return guarded([&] { return prepare_batch_async_limits_impl(c, limits); });
+}
+extern "C" size_t ZSTDMI_CCtx_getBatchAsyncPlan(const ZSTD_CCtx* c, size_t* chunkBytes, size_t* frameBlocks, size_t* maxChunks)
+{
+    return guarded([&] { return batch_async_plan_impl(c, chunkBytes, frameBlocks, maxChunks); });
 }
 extern "C" size_t ZSTDMI_CCtx_prepareBatchAsync(ZSTD_CCtx* c, size_t maxEntries, size_t srcSizeBound)
 {
