@@ -824,6 +824,11 @@ size_t ZSTDMI_debugGetChunk(ZSTD_CCtx* cctx, size_t chunkIdx, ZSTDMI_Seq* seqs, 
  * (0 = "store raw", the reference's ZSTD_entropyCompressSeqStore convention) */
 size_t ZSTDMI_debugEntropyBlock(ZSTD_CCtx* cctx, void* dst, size_t dstCapacity, const ZSTDMI_Seq* seqs, size_t nbSeq,
                                 const void* lits, size_t litSize, size_t srcSize);
+/* the same with offsets as the match finders store them: offBase = distance + 3 in every sequence (4 at least), turned into repcodes
+ * by the sequence encoder against the history rep[0..2] (0 = unknown, as in front of a later block of a frame: it equals no offset).
+ * After either call ZSTDMI_debugGetChunk(cctx, 0, ...) returns the seqStore as it was coded, "store raw" verdicts included */
+size_t ZSTDMI_debugEntropyBlockRaw(ZSTD_CCtx* cctx, void* dst, size_t dstCapacity, const ZSTDMI_Seq* seqs, size_t nbSeq,
+                                   const void* lits, size_t litSize, size_t srcSize, const unsigned rep[3]);
 /* the entropy stage of ONE chunk whose ChunkMeta is taken as given, WITHOUT the host's range checks, over a seqStore filled with the
  * byte `fill`: what a faulty match finder would hand over.  The kernels must bound every size themselves (meta_checked, the
  * bitstream room): returns the bytes the chunk's frame would take, never faults.  tests/test_gpu_boundary.py */

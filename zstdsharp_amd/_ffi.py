@@ -183,6 +183,8 @@ SIGNATURES = {
     "ZSTDMI_debugPoisonedChunk": (c_size_t, [c_void_p, c_uint, c_uint, c_uint, c_uint]),
     "ZSTDMI_debugEntropyBlock": (c_size_t, [c_void_p, c_void_p, c_size_t, ctypes.POINTER(ZSTDMI_Seq), c_size_t,
                                             c_void_p, c_size_t, c_size_t]),
+    "ZSTDMI_debugEntropyBlockRaw": (c_size_t, [c_void_p, c_void_p, c_size_t, ctypes.POINTER(ZSTDMI_Seq), c_size_t,
+                                               c_void_p, c_size_t, c_size_t, ctypes.POINTER(c_uint)]),
 }
 
 _lib = None

@@ -1753,8 +1753,11 @@ size_t ZSTDMI_debugGetChunk(ZSTD_CCtx* c, size_t chunkIdx, ZSTDMI_Seq* seqs, siz
     return 0;
 }
 
-size_t ZSTDMI_debugEntropyBlock(ZSTD_CCtx* c, void* dst, size_t dstCapacity, const ZSTDMI_Seq* seqs, size_t nbSeq,
-                                const void* lits, size_t litSize, size_t srcSize)
+// one caller-supplied seqStore through huf_build / huf_encode / seq_encode.  resolveReps 0: offBase holds repcodes already, as the block
+// codes them; 1: offBase is distance + 3 throughout and seq_encode resolves it against `reps`, as behind the match finders.  Either way
+// the record is chunk 0 of the context's last call afterwards (ZSTDMI_debugGetChunk reads the codes seq_encode left), raw verdict or not.
+static size_t debug_entropy_block(ZSTD_CCtx* c, void* dst, size_t dstCapacity, const ZSTDMI_Seq* seqs, size_t nbSeq,
+                                  const void* lits, size_t litSize, size_t srcSize, u32 resolveReps, const u32* reps)
 {
     size_t e = cctx_bind(c); if (isErr(e)) return e;
     if (nbSeq > kMaxSeq || litSize > kChunkSize || srcSize > kChunkSize) return ZERR(kErrParameterOutOfBound);
@@ -1767,15 +1770,28 @@ size_t ZSTDMI_debugEntropyBlock(ZSTD_CCtx* c, void* dst, size_t dstCapacity, con
     (void)hipMemcpyAsync(c->meta.p, &m, sizeof m, hipMemcpyHostToDevice, s);
     launch_huf_build((u8*)c->lits.p, (ChunkMeta*)c->meta.p, (HufTable*)c->tables.p, (u8*)c->slots.p, 1, 0, nullptr, layout_arith(0, 0, 0), s, StageHook());
     launch_huf_encode((u8*)c->lits.p, (ChunkMeta*)c->meta.p, (HufTable*)c->tables.p, (u8*)c->slots.p, nullptr, nullptr, 0, 1, nullptr, 0, s);
-    { const u32 plainReps[3] = { 1, 4, 8 };
-      const Resolved rs = resolve_call(sticky_params(c), srcSize, kChunkSize);
-      launch_seq_encode((Seq*)c->seqs.p, (ChunkMeta*)c->meta.p, (u8*)c->slots.p, 1, rs.cp.strategy < kStratGreedy ? rs.cp.strategy : (u32)kStratGreedy, FrameHeaderSpec{}, 0, plainReps, layout_arith(kChunkSize, 0, 0), s); }
+    { const Resolved rs = resolve_call(sticky_params(c), srcSize, kChunkSize);
+      launch_seq_encode((Seq*)c->seqs.p, (ChunkMeta*)c->meta.p, (u8*)c->slots.p, 1, rs.cp.strategy < kStratGreedy ? rs.cp.strategy : (u32)kStratGreedy, FrameHeaderSpec{}, resolveReps, reps, layout_arith(kChunkSize, 0, 0), s); }
     if (isErr(dev_read(&m, c->meta.p, sizeof m, s))) return ZERR(kErrGeneric);
+    c->lastChunks = 1;
     if (m.blockType != 2) return 0;
     if (m.bodySize > dstCapacity) return ZERR(kErrDstSizeTooSmall);
     if (host_memcpy(dst, (u8*)c->slots.p + m.fhSize + 3, m.bodySize, hipMemcpyDeviceToHost) != hipSuccess) return ZERR(kErrGeneric);
-    c->lastChunks = 1;
     return m.bodySize;
+}
+size_t ZSTDMI_debugEntropyBlock(ZSTD_CCtx* c, void* dst, size_t dstCapacity, const ZSTDMI_Seq* seqs, size_t nbSeq,
+                                const void* lits, size_t litSize, size_t srcSize)
+{
+    const u32 plainReps[3] = { 1, 4, 8 };
+    return debug_entropy_block(c, dst, dstCapacity, seqs, nbSeq, lits, litSize, srcSize, 0, plainReps);
+}
+size_t ZSTDMI_debugEntropyBlockRaw(ZSTD_CCtx* c, void* dst, size_t dstCapacity, const ZSTDMI_Seq* seqs, size_t nbSeq,
+                                   const void* lits, size_t litSize, size_t srcSize, const unsigned rep[3])
+{
+    if (!rep) return ZERR(kErrGeneric);
+    for (size_t i = 0; i < nbSeq && i < kMaxSeq; ++i) if (seqs[i].offBase < 4) return ZERR(kErrParameterOutOfBound);     // (distance + 3, distance >= 1)
+    const u32 reps[3] = { rep[0], rep[1], rep[2] };
+    return debug_entropy_block(c, dst, dstCapacity, seqs, nbSeq, lits, litSize, srcSize, 1, reps);
 }
 
 size_t ZSTDMI_debugPoisonedChunk(ZSTD_CCtx* c, unsigned nbSeq, unsigned litSize, unsigned srcSize, unsigned fill)
