@@ -788,6 +788,70 @@ int ZSTDMI_debugLastRangesFrames(const ZSTD_DCtx* dctx);
 int ZSTDMI_debugLastRangesAlone(const ZSTD_DCtx* dctx);
 long long ZSTDMI_debugLastRangesStaged(const ZSTD_DCtx* dctx);
 
+/* ---- gather reads enqueued from the device: ZSTDMI_decompressRanges with no host round trip ----
+ * ZSTDMI_decompressRanges stops the host at least three times a call (the table's footer, the plan's summary that sizes the arena, the
+ * answers), takes its five arrays as host memory and indexes the whole seek table again on every call.  Here ONE seekable stream in
+ * device memory is prepared once — footer read, table indexed and validated, every work buffer sized from limits — and a call only
+ * enqueues kernels over the caller's device arrays.
+ * The limits (ZSTDMI_DRangesLimits).  maxRanges, maxRangeBytes and maxContent must be stated; the other three have defaults (0):
+ * maxFrames = the table's entry count N, and maxBlocks / maxSequences as for ZSTDMI_DBatchLimits above, with the same caveats.
+ * ZSTDMI_rangesAsyncWorkspaceD: the device bytes the prepare will ask its buffers for under these limits and a table of tableEntries
+ * entries (host arithmetic only; 0 for NULL or what the prepare refuses as out of bound); monotone in every field and in tableEntries.
+ * ZSTDMI_DCtx_prepareRangesAsync(dctx, d_src, srcSize, limits) does everything that needs the host, once: binds the device, uploads
+ * and validates the dictionary in force (loaded, ZSTD_DCtx_refDDict, the ZSTD_d_refMultipleDDicts set), reads the 9-byte footer, indexes
+ * the table into buffers of its own — a synchronous ZSTDMI_decompressRange[s] on the same context between async calls neither disturbs
+ * nor invalidates the prepared index —, reads the index's summary back and allocates.  It returns 0, or: GENERIC (NULL context or
+ * limits); parameter_outOfBound for a zero maxRanges or maxContent, a maxRangeBytes of 0 or above 4 MiB, or limits beyond the lists'
+ * index range (those of ZSTDMI_DCtx_prepareBatchAsync; with maxFrames 0, N counts); parameter_unsupported for a host d_src, several
+ * device workers, a pending ZSTD_DCtx_refPrefix (which stays pending), ZSTDMI_DCtx_setLongFrames(2) and a DDict set that cannot serve
+ * a batch; the table's error with the code ZSTDMI_decompressRanges gives for the same stream (no footer magic or a wrong skippable
+ * header: prefix_unknown; reserved descriptor bits, more than 2^27 entries or sizes that do not add up: corruption_detected);
+ * init_missing, memory_allocation, dictionary_corrupted.  Refusals that need no device are answered before one is looked for.
+ * A context holds ONE async prepare of either kind: this one and ZSTDMI_DCtx_prepareBatchAsync replace each other, and the call whose
+ * prepare was replaced answers stage_wrong.  A refused or failed prepare leaves none.  The stream's bytes must stay valid and
+ * unchanged until the next prepare or ZSTD_freeDCtx.
+ * ZSTDMI_DCtx_getRangesAsyncPlan: what the valid prepare found — the table's entry count and the stream's content bytes (either
+ * pointer may be NULL) -> 0; GENERIC for a NULL context, stage_wrong without a valid prepare.
+ * ZSTDMI_decompressRangesAsync: all five arrays and everything they point to are DEVICE memory.  The call makes no device allocation,
+ * no host wait, no copy between host and device and no host read of the arrays; it enqueues on the context's stream
+ * (ZSTDMI_DCtx_setStream) and returns: 0 once enqueued (n == 0: 0, nothing is touched); GENERIC for a NULL context, or a NULL array with
+ * n > 0; stage_wrong if there is no valid prepare, n > maxRanges, or a parameter, the dictionary, a DDict reference or the device
+ * changed since the prepare (any setter but ZSTDMI_DCtx_setStream, ZSTD_DCtx_loadDictionary, ZSTD_DCtx_refDDict, ZSTD_DCtx_refPrefix:
+ * only a generation counter is compared).  ZSTDMI_debugHostWaitsD and ZSTDMI_debugDeviceAllocsD do not move across it; stage timing
+ * is off for the length of the call; the ZSTDMI_debugLastRanges* counters are NOT updated by it.
+ * Per range, d_dstSizes[i] and the bytes at d_dsts[i] are exactly those of ZSTDMI_decompressRanges on a second context with the same
+ * setup — min(length, max(total - offset, 0)) bytes; 0 for an empty range (d_dsts[i] may then be NULL); dstSize_tooSmall for more
+ * than the capacity, then dstBuffer_null for a NULL destination, in that order; ranges may overlap, repeat and come in any order;
+ * every touched frame is decoded once; a frame that fails fails every range that meets it, with the code of the lowest-indexed
+ * failing frame it meets, nothing of such a range is written and the other ranges are served — with three exceptions:
+ *   1. a range that would return more than maxRangeBytes answers workSpace_tooSmall and touches no frame (maxRangeBytes sizes the
+ *      gather's grid; the synchronous call hands such a range to the single-range path);
+ *   2. the limits.  Take the table entries with content that some served range meets, in table order: entry j is refused iff the
+ *      number of those entries up to and including j exceeds maxFrames, or the sum of their table content sizes exceeds maxContent,
+ *      or the sum of their blocks exceeds maxBlocks (and, should an entry hold more frames than one, their frames maxFrames).
+ *      Sequence records beyond maxSequences fail as in ZSTDMI_decompressBatchAsync.  A range that meets a refused entry answers
+ *      workSpace_tooSmall; ranges that meet only admitted entries are byte for byte what they are without the cut.  No arena byte
+ *      beyond maxContent is ever written, whatever the frames' own headers say;
+ *   3. there is no single-call path: a touched frame of more than 4 MiB compressed fails its ranges with srcSize_wrong, frames
+ *      without a content size take the shared pass, and every long frame takes the ordered walk.
+ * Nothing is written at or beyond d_dsts[i] + d_dstCapacities[i].  The arrays, the stream, the destinations and a referenced DDict
+ * must stay valid and unchanged until the stream has passed the work; the context waits for work in flight by itself where
+ * ZSTDMI_decompressBatchAsync's does.  Every call still scans the N-entry table (its cost follows N, not the touched frames).
+ * Capturing the call into a hipGraph is neither claimed nor tested. */
+typedef struct {
+    size_t maxRanges;      /* ranges per call, > 0 */
+    size_t maxRangeBytes;  /* returned bytes of one range, 1 .. 4 MiB: sizes the gather's grid */
+    size_t maxContent;     /* content bytes of all frames one call touches, > 0: sizes the arena and the literal scratch */
+    size_t maxFrames;      /* distinct frames one call touches; 0 = the table's entry count */
+    size_t maxBlocks;      /* 0 = maxFrames + maxContent / 16384 */
+    size_t maxSequences;   /* 0 = maxContent / 3 + 64 */
+} ZSTDMI_DRangesLimits;
+size_t ZSTDMI_rangesAsyncWorkspaceD(const ZSTDMI_DRangesLimits* limits, size_t tableEntries);
+size_t ZSTDMI_DCtx_prepareRangesAsync(ZSTD_DCtx* dctx, const void* d_src, size_t srcSize, const ZSTDMI_DRangesLimits* limits);
+size_t ZSTDMI_DCtx_getRangesAsyncPlan(const ZSTD_DCtx* dctx, size_t* tableEntries, unsigned long long* totalContent);
+size_t ZSTDMI_decompressRangesAsync(ZSTD_DCtx* dctx, const unsigned long long* d_offsets, const size_t* d_lengths, size_t n,
+                                    void* const* d_dsts, const size_t* d_dstCapacities, size_t* d_dstSizes);
+
 /* Segmented stream decoding: ZSTD_decompressStream decodes a frame that is still arriving in SEGMENTS — runs of whole blocks —
  * instead of collecting the whole frame first.  bytes == 0 (the default): off, ZSTD_decompressStream behaves exactly as without this
  * call.  Otherwise `bytes` is the compressed size at which a segment is cut: whenever the frame in progress has at least that many

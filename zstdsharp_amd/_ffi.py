@@ -37,6 +37,12 @@ class DBatchLimits(ctypes.Structure):
                 ("maxBlocks", c_size_t), ("maxSequences", c_size_t)]
 
 
+class DRangesLimits(ctypes.Structure):
+    """ZSTDMI_DRangesLimits: what one ZSTDMI_decompressRangesAsync call may hold at most (0 in the last three = the default)."""
+    _fields_ = [("maxRanges", c_size_t), ("maxRangeBytes", c_size_t), ("maxContent", c_size_t), ("maxFrames", c_size_t),
+                ("maxBlocks", c_size_t), ("maxSequences", c_size_t)]
+
+
 class CBatchLimits(ctypes.Structure):
     """ZSTDMI_CBatchLimits: what one ZSTDMI_compressBatchAsync call may hold at most (maxChunks 0 = the default; reserved = 0)."""
     _fields_ = [("maxEntries", c_size_t), ("srcSizeBound", c_size_t), ("maxChunks", c_size_t), ("reserved", c_size_t * 3)]
@@ -167,6 +173,11 @@ SIGNATURES = {
     "ZSTDMI_debugLastRangeStaged": (ctypes.c_longlong, [c_void_p]),
     "ZSTDMI_decompressRanges": (c_size_t, [c_void_p, c_void_p, c_size_t, ctypes.POINTER(c_ull), ctypes.POINTER(c_size_t), c_size_t,
                                            ctypes.POINTER(c_void_p), ctypes.POINTER(c_size_t), ctypes.POINTER(c_size_t)]),
+    "ZSTDMI_rangesAsyncWorkspaceD": (c_size_t, [ctypes.POINTER(DRangesLimits), c_size_t]),
+    "ZSTDMI_DCtx_prepareRangesAsync": (c_size_t, [c_void_p, c_void_p, c_size_t, ctypes.POINTER(DRangesLimits)]),
+    "ZSTDMI_DCtx_getRangesAsyncPlan": (c_size_t, [c_void_p, ctypes.POINTER(c_size_t), ctypes.POINTER(c_ull)]),
+    # (the five arrays are device memory: plain addresses)
+    "ZSTDMI_decompressRangesAsync": (c_size_t, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
     "ZSTDMI_debugLastRangesFrames": (c_int, [c_void_p]),
     "ZSTDMI_debugLastRangesAlone": (c_int, [c_void_p]),
     "ZSTDMI_debugLastRangesStaged": (ctypes.c_longlong, [c_void_p]),

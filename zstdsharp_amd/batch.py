@@ -174,6 +174,36 @@ def decompress_batch_async(decompressor, srcs, sizes, dsts, caps, out_sizes=None
     return out_sizes
 
 
+def decompress_ranges_async(decompressor, offsets, lengths, dsts, caps, out_sizes=None):
+    """ZSTDMI_decompressRangesAsync after Decompressor.PrepareRangesAsync: offsets, lengths, dsts, caps are contiguous CUDA int64
+    tensors of n ranges each of the prepared stream's content (dsts: pointers as integers, 0 = none; all of them e.g. computed on the
+    device from an index tensor) -> out_sizes, a CUDA int64 tensor: the bytes range i returned, or its zstd error code as a negative
+    value (what unwrap_ranges raises for it; -66 workSpace_tooSmall for a range longer than the prepared max_range_bytes or one that
+    meets a frame beyond a prepared limit; -72 srcSize_wrong for one that meets a frame of more than 4 MiB compressed).  The work is
+    enqueued on torch.cuda.current_stream() and the call returns: nothing is synchronised and nothing is copied to the host.  The
+    tensors and the destinations must stay alive and unchanged until that stream has passed the work.  Raises ZstdException for the
+    whole call's error (stage_wrong: no valid PrepareRangesAsync, more ranges than it was prepared for, or a parameter or the
+    dictionary changed since)."""
+    import torch
+    decompressor._ensure_not_disposed()
+    lib = decompressor._lib
+    n = offsets.numel()
+    if out_sizes is None:
+        out_sizes = torch.empty(n, dtype=torch.int64, device=offsets.device)
+    for name, t in (("offsets", offsets), ("lengths", lengths), ("dsts", dsts), ("caps", caps), ("out_sizes", out_sizes)):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int64 and t.is_contiguous() and t.numel() == n):
+            raise TypeError(f"{name}: expected a contiguous CUDA int64 tensor of {n} entries")
+    if n == 0:
+        return out_sizes
+    stream = torch.cuda.current_stream(offsets.device)
+    r = lib.ZSTDMI_DCtx_setStream(decompressor.dctx, stream.cuda_stream or _HIP_STREAM_LEGACY)
+    if not is_error(r):
+        r = lib.ZSTDMI_decompressRangesAsync(decompressor.dctx, offsets.data_ptr(), lengths.data_ptr(), n, dsts.data_ptr(), caps.data_ptr(), out_sizes.data_ptr())
+    if is_error(r):
+        raise ZstdException(get_error_code(r), lib.ZSTD_getErrorName(r).decode())
+    return out_sizes
+
+
 def compress_pack(compressor, items):
     """items as for compress_batch -> ONE seekable stream (ZSTDMI_compressPack): item i's frames as Compressor.Wrap writes them for it
     alone, one item's behind the other's, and one seek table behind the last (read_seek_table reads it).  Bytes-like items -> bytes;

@@ -10,6 +10,8 @@
 //                    the compacted source.  Writes the batch walk's table, and the runs of touched entries for a host source.
 //   ranges_gather  : per served range: every met entry decoded to the size its table entry names, or nothing is copied; then its
 //                    bytes from the arena slots to its destination, one workgroup per 64 KiB slice of its output.
+//   ranges_select_d, ranges_plan_d : the select and the plan's emit of ZSTDMI_decompressRangesAsync: the caller's
+//                    arrays lie in device memory, the index is a prepare's, the decode table has a fixed number of rows.
 #include "zmi_device.h"
 #include "zmi_host.h"
 
@@ -301,6 +303,81 @@ __global__ __launch_bounds__(256) void ranges_gather_kernel(const RangeIn* __res
 }
 
 // ------------------------------------------------------------------------------------------------
+// ranges enqueued from the device (ZSTDMI_decompressRangesAsync): the select and the plan's last step over the caller's
+// device arrays and a prepared index.  The scans between them, seek_index at the prepare and the gather are the kernels above.
+// ------------------------------------------------------------------------------------------------
+// select, one lane per range: the caller's four arrays -> RangeIn / RangeRec rows, ranges_select_kernel's answers in its order; where
+// that kernel decides "alone", a range that would return more than maxRangeBytes (which sized the gather's grid) answers
+// workSpace_tooSmall and marks nothing.  The difference array is zero when this runs: the index persists, the marks are the call's.
+__global__ __launch_bounds__(256) void ranges_select_d_kernel(const unsigned long long* __restrict__ offsets, const size_t* __restrict__ lengths,
+                                                              void* const* __restrict__ dsts, const size_t* __restrict__ caps, u32 nRanges, u64 maxRangeBytes,
+                                                              RangeIn* __restrict__ in, RangeRec* __restrict__ recs, const u64* __restrict__ dOff, u32 n,
+                                                              u32* __restrict__ diff)
+{
+    const u32 r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= nRanges) return;
+    RangeIn R;
+    R.offset = offsets[r]; R.length = (u64)lengths[r]; R.dstCap = (u64)caps[r]; R.dst = (u64)(uintptr_t)dsts[r];
+    const u64 total = dOff[n];
+    const u64 ret = R.offset < total ? (R.length < total - R.offset ? R.length : total - R.offset) : 0;
+    RangeRec rec = {};
+    if (ret > R.dstCap) rec.result = (u64)0 - (u64)kErrDstSizeTooSmall;
+    else if (!ret) rec.result = 0;
+    else if (!R.dst) rec.result = (u64)0 - (u64)kErrDstBufferNull;
+    else if (ret > maxRangeBytes) rec.result = (u64)0 - (u64)kErrWorkSpaceTooSmall;
+    else {
+        rec.result = ret; rec.state = kRangeServed;
+        rec.first = upper_bound(dOff, n + 1, R.offset) - 1;
+        rec.last = upper_bound(dOff, n + 1, R.offset + ret - 1) - 1;
+        atomicAdd(&diff[rec.first], 1u);
+        atomicAdd(&diff[rec.last + 1], 0xFFFFFFFFu);
+    }
+    in[r] = R; recs[r] = rec;
+}
+
+// emit (behind ranges_cover_sum, ranges_plan_sum and their carries, as ranges_plan_kernel): the decode core's table has nRows rows, a
+// host constant.  Touched entry number k, in table order, is refused iff k + 1 exceeds maxFrames or its arena slot, the exclusive sum
+// of the touched entries' table content sizes, would end beyond maxContent: both sums only grow, so the admitted entries are a prefix
+// and none of their slots reaches beyond the arena whatever the frames' own headers say.  An admitted entry fills row k — its source
+// and its slot as offsets from kAsyncBase, the base the core's kernels get —; every row nothing fills is an empty entry (srcSize 0),
+// which walks as batch_plan_d_kernel's and costs no frame, block or byte.  A refused entry, and one of more than aloneAbove
+// compressed bytes (there is no single-call path), points the gather at one of two verdict rows behind the table (rows nRows and
+// nRows + 1: workSpace_tooSmall, srcSize_wrong), so ranges_gather_kernel fails their ranges as it fails any entry's.
+__global__ __launch_bounds__(1024) void ranges_plan_d_kernel(const u8* __restrict__ tab, u32 n, u32 stride, u32 nTiles, RangesWs ws, u64 streamOff, u64 arenaOff,
+                                                             u32 maxFrames, u64 maxContent, u64 aloneAbove, u32 nRows, BatchEntryIn* __restrict__ rows,
+                                                             BatchEntryOut* __restrict__ verdicts)
+{
+    __shared__ u64 sh[4 * kScanSh];
+    __shared__ u32 shTouched[kRangesTile];
+    const u32 i = blockIdx.x * kRangesTile + threadIdx.x;
+    const PlanEntry e = plan_entry(tab, n, stride, ws.diff, ws.tileCover, sh, shTouched);
+    u64 v[4] = {e.touched, e.touched ? e.d : 0, e.touched ? e.c : 0, e.start}, ex[4], all[4];
+    block_scan<4>(v, ex, all, sh);
+    const u64* carry = ws.tilePlan + (u64)blockIdx.x * 4;
+    const u64 k = carry[0] + ex[0], slot = carry[1] + ex[1];
+    const u64* tot = ws.tilePlan + (u64)nTiles * 4;
+    u32 idx = kNoEntry;
+    if (e.touched) {
+        const bool refused = k + 1 > maxFrames || slot + e.d > maxContent;
+        idx = refused ? nRows : e.c > aloneAbove ? nRows + 1 : (u32)k;
+        if (k < nRows) {
+            BatchEntryIn b = {};
+            if (idx == (u32)k) { b.srcOff = streamOff + ws.cOff[i]; b.srcSize = e.c; b.dstOff = arenaOff + slot; b.dstCap = e.d; }
+            rows[k] = b;
+        }
+    }
+    if (i < n) { ws.slot[i] = slot; ws.decIdx[i] = idx; }
+    if ((u64)i >= tot[0] && i < nRows) rows[i] = BatchEntryIn{};
+    if (i == 0) {
+        BatchEntryOut o = {};
+        o.state = kBatchDone;
+        o.result = (u64)0 - (u64)kErrWorkSpaceTooSmall; verdicts[0] = o;
+        o.result = (u64)0 - (u64)kErrSrcSizeWrong; verdicts[1] = o;
+        ws.sum[kRgTouched] = tot[0]; ws.sum[kRgArena] = tot[1]; ws.sum[kRgCompact] = tot[2]; ws.sum[kRgRuns] = tot[3];
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------------
 static inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -354,6 +431,26 @@ void launch_ranges_gather(const RangeIn* in, const RangeRec* recs, u64* res, u32
         hipLaunchKernelGGL(ranges_gather_kernel, dim3(count, nSlices ? nSlices : 1), dim3(256), 0, stream, in + base, recs + base, res + base, ws.dOff, ws.slot,
                            ws.decIdx, out, arena);
     }
+}
+
+// an enqueued call (ZSTDMI_decompressRangesAsync): the select over the caller's arrays; the plan's scans as launch_ranges_plan runs them,
+// then the emit into the decode core's nRows rows (the two verdict rows lie behind row nRows - 1 of `out`)
+void launch_ranges_select_d(const unsigned long long* offsets, const size_t* lengths, void* const* dsts, const size_t* caps, u32 nRanges, u64 maxRangeBytes,
+                            RangeIn* in, RangeRec* recs, u32 n, const RangesWs& ws, hipStream_t stream)
+{
+    hipLaunchKernelGGL(ranges_select_d_kernel, dim3((nRanges + 255) / 256), dim3(256), 0, stream, offsets, lengths, dsts, caps, nRanges, maxRangeBytes, in, recs,
+                       ws.dOff, n, ws.diff);
+}
+void launch_ranges_plan_d(const u8* tab, u32 n, u32 stride, const RangesWs& ws, u64 streamOff, u64 arenaOff, u32 maxFrames, u64 maxContent, u64 aloneAbove,
+                          u32 nRows, BatchEntryIn* rows, BatchEntryOut* out, hipStream_t stream)
+{
+    const u32 T = n / kRangesTile + 1;
+    hipLaunchKernelGGL(ranges_cover_sum_kernel, dim3(T), dim3(1024), 0, stream, ws.diff, n, ws.tileCover);
+    hipLaunchKernelGGL(tile_carry_kernel<1>, dim3(1), dim3(1024), 0, stream, ws.tileCover, T);
+    hipLaunchKernelGGL(ranges_plan_sum_kernel, dim3(T), dim3(1024), 0, stream, tab, n, stride, ws.diff, ws.tileCover, ws.tilePlan);
+    hipLaunchKernelGGL(tile_carry_kernel<4>, dim3(1), dim3(1024), 0, stream, ws.tilePlan, T);
+    hipLaunchKernelGGL(ranges_plan_d_kernel, dim3(T), dim3(1024), 0, stream, tab, n, stride, T, ws, streamOff, arenaOff, maxFrames, maxContent, aloneAbove, nRows,
+                       rows, out + nRows);
 }
 
 } // namespace zmi

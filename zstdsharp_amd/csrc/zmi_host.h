@@ -166,6 +166,11 @@ void launch_ranges_plan(const u8* tab, u32 n, u32 stride, u32 srcDev, const Rang
 void launch_ranges_alone(const BatchEntryOut* out, u32 nEntries, const RangesWs& ws, hipStream_t stream);
 void launch_ranges_gather(const RangeIn* in, const RangeRec* recs, u64* res, u32 nRanges, u32 nSlices, const RangesWs& ws, const BatchEntryOut* out,
                           const u8* arena, hipStream_t stream);
+// ranges enqueued from the device over a prepared index (ZSTDMI_decompressRangesAsync)
+void launch_ranges_select_d(const unsigned long long* offsets, const size_t* lengths, void* const* dsts, const size_t* caps, u32 nRanges, u64 maxRangeBytes,
+                            RangeIn* in, RangeRec* recs, u32 n, const RangesWs& ws, hipStream_t stream);
+void launch_ranges_plan_d(const u8* tab, u32 n, u32 stride, const RangesWs& ws, u64 streamOff, u64 arenaOff, u32 maxFrames, u64 maxContent, u64 aloneAbove,
+                          u32 nRows, BatchEntryIn* rows, BatchEntryOut* out, hipStream_t stream);
 void launch_seq_stats(const Seq* seqs, const u8* lits, const ChunkMeta* meta, u32 nChunks, const u8* src, u32 chunkBytes, u32* stats, hipStream_t stream);
 void launch_dict_parse(const u8* dict, u32 dictSize, DictInfo* out, hipStream_t stream);
 void launch_dict_ctables(const u8* dict, u32 dictSize, const DictInfo* info, DictCTables* out, hipStream_t stream);

@@ -92,17 +92,26 @@ struct ZSTD_DCtx_s {
     HostTally tally; u64 paramGen = 0;
     struct DAsyncPrep* asyncPrep = nullptr; hipEvent_t asyncEv = nullptr; bool asyncPending = false;
     DevBuf asyncVerdict;
+    // ZSTDMI_DCtx_prepareRangesAsync / ZSTDMI_decompressRangesAsync: the other kind of prepare — a context holds one of
+    // the two, dctx_drop_prepares is what every prepare begins with — and the prepared stream's index, a RangesWs of its own: the
+    // synchronous range calls index into rangesWs on every call and must not disturb this one
+    struct DRangesPrep* rangesPrep = nullptr;
+    DevBuf rangesAsyncWs;
     ZSTD_DCtx_s();
 };
 // what ZSTDMI_DCtx_prepareBatchAsync resolved: the limits with their defaults filled in, and where the dump area lies in the scratch
 struct DAsyncPrep { u64 gen; size_t maxEntries; u64 bound; BatchLimitsD lim; u64 dumpOff; };
+// what ZSTDMI_DCtx_prepareRangesAsync resolved: the same, the stream (the caller keeps its bytes), its table as the footer and
+// seek_index state it, and the rows of the decode core's table
+struct DRangesPrep { u64 gen; size_t maxRanges; u64 maxRangeBytes; BatchLimitsD lim; u64 dumpOff; const u8* src; const u8* tab; u32 n, stride; u64 total; u32 nRows; };
+static void dctx_drop_prepares(ZSTD_DCtx* d) { delete d->asyncPrep; d->asyncPrep = nullptr; delete d->rangesPrep; d->rangesPrep = nullptr; }
 static void dctx_async_drain(ZSTD_DCtx* d);
 ZSTD_DCtx_s::ZSTD_DCtx_s()
 {
     tally.self = this; tally.beforeFree = [](void* self) { dctx_async_drain((ZSTD_DCtx_s*)self); };
     for (DevBuf* b : { &frames, &blocks, &recs, &status, &scratch, &walkWs, &slowFlags, &stageSrc, &stageDst, &origin, &originList, &batchIn, &batchOut, &blockKeys, &litRooms,
                        &seekTab, &seekSum, &edge, &rangesWs, &rangesIn, &rangesRec, &rangesRes, &arena, &hist[0], &hist[1], &segReps, &segXxh, &dict, &dictInfoDev, &slotTab,
-                       &pfxStage, &asyncVerdict }) b->owner = &tally;
+                       &pfxStage, &asyncVerdict, &rangesAsyncWs }) b->owner = &tally;
 }
 // The lifetime rule of an enqueued batch (ZSTDMI_decompressBatchAsync), in one place: wait for the event behind the last enqueued call.
 // Called by every DevBuf of the context before it frees (HostTally::beforeFree: growth and release alike), by ZSTD_freeDCtx, by
@@ -163,7 +172,7 @@ size_t ZSTD_freeDCtx(ZSTD_DCtx* d)
         (void)hipSetDevice(d->device);
         dctx_async_drain(d);        // (an enqueued batch may run on a stream that is not the context's own)
         if (d->asyncEv) (void)hipEventDestroy(d->asyncEv);
-        d->asyncVerdict.release();
+        d->asyncVerdict.release(); d->rangesAsyncWs.release();
         if (d->ownStream) (void)hipStreamSynchronize(d->ownStream);
         d->frames.release(); d->blocks.release(); d->recs.release(); d->status.release(); d->scratch.release(); d->walkWs.release(); d->slowFlags.release(); d->stageSrc.release(); d->stageDst.release(); d->dict.release(); d->dictInfoDev.release(); d->origin.release(); d->originList.release(); d->batchIn.release(); d->batchOut.release(); d->blockKeys.release(); d->litRooms.release(); d->seekTab.release(); d->seekSum.release(); d->edge.release(); d->pfxStage.release(); d->rangesWs.release(); d->rangesIn.release(); d->rangesRec.release(); d->rangesRes.release(); d->arena.release(); d->slotTab.release();
         d->hist[0].release(); d->hist[1].release(); d->segReps.release(); d->segXxh.release();
@@ -172,7 +181,7 @@ size_t ZSTD_freeDCtx(ZSTD_DCtx* d)
         if (d->auxDone) (void)hipEventDestroy(d->auxDone);
         if (d->ownStream) (void)hipStreamDestroy(d->ownStream);
     }
-    delete d->asyncPrep;
+    dctx_drop_prepares(d);
     delete d;
     return 0;
 }
@@ -750,7 +759,7 @@ static DAsyncBytes dbatch_bytes(size_t maxEntries, const BatchLimitsD& lim)
 static size_t prepare_batch_async_d_impl(ZSTD_DCtx* d, const ZSTDMI_DBatchLimits* limits)
 {
     if (!d || !limits) return ZERR(kErrGeneric);
-    delete d->asyncPrep; d->asyncPrep = nullptr;
+    dctx_drop_prepares(d);
     size_t maxEntries; u64 bound; BatchLimitsD lim;
     if (!dbatch_limits(limits, maxEntries, bound, lim)) return ZERR(kErrParameterOutOfBound);
     // what the shared pass does not cover, as far as the host alone can tell (a pending prefix stays pending)
@@ -768,31 +777,21 @@ static size_t prepare_batch_async_d_impl(ZSTD_DCtx* d, const ZSTDMI_DBatchLimits
     d->asyncPrep = new DAsyncPrep{ dctx_gen(d), maxEntries, bound, lim, lim.content + (u64)lim.frames * kLitSkew + 256 };
     return 0;
 }
-// decode_entries between its table upload and its read-back, kernels only (and one hipMemsetAsync over the block keys)
-static size_t decompress_batch_async_impl(ZSTD_DCtx* d, const void* const* d_srcs, const size_t* d_srcSizes, size_t n, void* const* d_dsts,
-                                          const size_t* d_dstCapacities, size_t* d_dstSizes)
+// The decode core of an enqueued call, shared by ZSTDMI_decompressBatchAsync and ZSTDMI_decompressRangesAsync: decode_entries between
+// its table upload and its read-back, kernels only (and one hipMemsetAsync over the block keys), over nE rows of d->batchIn whose
+// sources and destinations are offsets from kAsyncBase.  `plan` enqueues whatever fills those rows (-> false: failed); it runs behind
+// the init kernel, where the batch's plan kernel has always run.  Behind the core, d->batchOut holds every row's answer.
+static size_t decode_core_d(ZSTD_DCtx* d, const DecodeDict& dd, const BatchLimitsD& lim, u64 dumpOff, u32 nE, const std::function<bool()>& plan)
 {
-    if (!d) return ZERR(kErrGeneric);
-    if (n == 0) return 0;
-    if (!d_srcs || !d_srcSizes || !d_dsts || !d_dstCapacities || !d_dstSizes) return ZERR(kErrGeneric);
-    const DAsyncPrep* const P = d->asyncPrep;
-    if (!P || P->gen != dctx_gen(d) || n > P->maxEntries || !d->deviceOk || (d->dictDirty && !ddict_shared(d)) || (set_active(d) && d->slotGen != d->setGen)) return ZERR(kErrStageWrong);
-    size_t e = dctx_bind(d); if (isErr(e)) return e;
-    struct TimerOff { StageTimer& t; bool was; ~TimerOff() { t.enabled = was; } } timerOff{d->timer, d->timer.enabled};
-    d->timer.enabled = false;       // (stage events belong to calls that wait for them)
     hipStream_t s = d->stream;
-    DecodeDict dd = decode_dict(d);
-    e = dctx_sync_slots(d, dd); if (isErr(e)) return e;       // (the table is current: nothing is uploaded)
-    const BatchLimitsD& lim = P->lim;
-    const u32 nE = (u32)n;
-    BatchEntryIn* const dIn = (BatchEntryIn*)d->batchIn.p; BatchEntryOut* const dOut = (BatchEntryOut*)d->batchOut.p; u32* const verdict = (u32*)d->asyncVerdict.p;
+    BatchEntryIn* const dIn = (BatchEntryIn*)d->batchIn.p; BatchEntryOut* const dOut = (BatchEntryOut*)d->batchOut.p;
     FrameDesc* const frames = (FrameDesc*)d->frames.p; BlockDesc* const blocks = (BlockDesc*)d->blocks.p; SeqRec* const recs = (SeqRec*)d->recs.p;
     u32* const status = (u32*)d->status.p; u64* const keys = (u64*)d->blockKeys.p; u64* const rooms = (u64*)d->litRooms.p;
     u8* const scratch = (u8*)d->scratch.p; u8* const slowFlags = (u8*)d->slowFlags.p;
-    // the bases are constants: the plan kernel states every source and destination as an offset from kAsyncBase
+    // the bases are constants: the plan states every source and destination as an offset from kAsyncBase
     const u8* const srcBase = (const u8*)(uintptr_t)kAsyncBase; u8* const dstBase = (u8*)(uintptr_t)kAsyncBase;
-    launch_batch_init_d(status, keys, rooms, P->dumpOff, lim, s);
-    launch_batch_plan_d(d_srcs, d_srcSizes, d_dsts, d_dstCapacities, nE, P->bound, dIn, verdict, s);
+    launch_batch_init_d(status, keys, rooms, dumpOff, lim, s);
+    if (!plan()) { (void)hipGetLastError(); return ZERR(kErrGeneric); }
     if (hipMemsetAsync(keys, 0xFF, (size_t)lim.blocks * sizeof(u64), s) != hipSuccess) { (void)hipGetLastError(); return ZERR(kErrGeneric); }
     // (frames without a content size always take the shared pass: there is no single-call path to hand them to)
     launch_batch_walk_count(srcBase, dIn, dOut, nE, dd.dictID, kBatchAloneAbove, status, s, dd.slots, dd.nSet, true, true);
@@ -807,13 +806,41 @@ static size_t decompress_batch_async_impl(ZSTD_DCtx* d, const void* const* d_src
     const int execWaves = d->execWaves ? d->execWaves : lim.frames <= 256 ? 16 : lim.frames <= 512 ? 8 : lim.frames <= 1024 ? 4 : lim.frames <= 2048 ? 2 : 1;
     launch_exec_matches_d(srcBase, dstBase, frames, blocks, lim.frames, recs, status, dd.dictContent, dd.dictContentSize, s, execWaves, dd.slots);
     launch_batch_fold(dOut, nE, keys, s);
-    launch_batch_finish_d(dOut, verdict, nE, d_dstSizes, s);
-    if (hipEventRecord(d->asyncEv, s) != hipSuccess) {      // (without the event nothing may stay in flight)
+    return 0;
+}
+// the event behind an enqueued call (without the event nothing may stay in flight)
+static size_t dctx_async_record(ZSTD_DCtx* d)
+{
+    if (hipEventRecord(d->asyncEv, d->stream) != hipSuccess) {
         (void)hipGetLastError();
-        return stream_wait(s);
+        return stream_wait(d->stream);
     }
     d->asyncPending = true;
     return 0;
+}
+static size_t decompress_batch_async_impl(ZSTD_DCtx* d, const void* const* d_srcs, const size_t* d_srcSizes, size_t n, void* const* d_dsts,
+                                          const size_t* d_dstCapacities, size_t* d_dstSizes)
+{
+    if (!d) return ZERR(kErrGeneric);
+    if (n == 0) return 0;
+    if (!d_srcs || !d_srcSizes || !d_dsts || !d_dstCapacities || !d_dstSizes) return ZERR(kErrGeneric);
+    const DAsyncPrep* const P = d->asyncPrep;
+    if (!P || P->gen != dctx_gen(d) || n > P->maxEntries || !d->deviceOk || (d->dictDirty && !ddict_shared(d)) || (set_active(d) && d->slotGen != d->setGen)) return ZERR(kErrStageWrong);
+    size_t e = dctx_bind(d); if (isErr(e)) return e;
+    struct TimerOff { StageTimer& t; bool was; ~TimerOff() { t.enabled = was; } } timerOff{d->timer, d->timer.enabled};
+    d->timer.enabled = false;       // (stage events belong to calls that wait for them)
+    hipStream_t s = d->stream;
+    DecodeDict dd = decode_dict(d);
+    e = dctx_sync_slots(d, dd); if (isErr(e)) return e;       // (the table is current: nothing is uploaded)
+    const u32 nE = (u32)n;
+    u32* const verdict = (u32*)d->asyncVerdict.p;
+    e = decode_core_d(d, dd, P->lim, P->dumpOff, nE, [&]() -> bool {
+        launch_batch_plan_d(d_srcs, d_srcSizes, d_dsts, d_dstCapacities, nE, P->bound, (BatchEntryIn*)d->batchIn.p, verdict, s);
+        return true;
+    });
+    if (isErr(e)) return e;
+    launch_batch_finish_d((const BatchEntryOut*)d->batchOut.p, verdict, nE, d_dstSizes, s);
+    return dctx_async_record(d);
 }
 
 // ---- a byte range of a seekable stream (ZSTDMI_decompressRange) ----
@@ -1054,6 +1081,116 @@ static size_t decompress_ranges_impl(ZSTD_DCtx* d, const void* src, size_t srcSi
     }
     d->lastRangesAlone = alone; d->lastRangesStaged = staged + stagedAlone;
     return 0;
+}
+
+// ---- gather reads enqueued from the device (ZSTDMI_DCtx_prepareRangesAsync / ZSTDMI_decompressRangesAsync) ----
+// decompress_ranges_impl stops the host for the footer, for the plan's summary (to size the arena) and for the answers, and indexes
+// the table on every call.  Here the prepare reads the footer and runs seek_index once, into an index of its own, and sizes the arena
+// and the decode core's buffers from the caller's limits; a call is the per-call reset of the marks, the select over the caller's
+// device arrays, the plan over N entries (a host constant now), the decode core above over min(N, maxFrames) rows, and the gather over
+// a grid sized from maxRangeBytes, which writes the caller's sizes column.
+// the limits with their defaults filled in for a table of tableEntries entries -> false: a zero where none is allowed, a range
+// bound above what the gather serves, or a limit beyond the lists' index range (dbatch_limits' range)
+static bool dranges_limits(const ZSTDMI_DRangesLimits* L, u64 tableEntries, BatchLimitsD& lim, u32& nRows)
+{
+    if (!L->maxRanges || L->maxRanges > 0xFFFFFFF0ull || !L->maxRangeBytes || L->maxRangeBytes > kRangesAloneAbove || !L->maxContent || L->maxContent > ((u64)1 << 48)) return false;
+    if (tableEntries > ((u64)1 << 27)) return false;
+    u64 frames = L->maxFrames ? L->maxFrames : tableEntries;
+    if (!frames) frames = 1;            // (an empty table: the core still runs, over one empty row)
+    if (frames > ((u64)1 << 26)) return false;
+    const u64 blocks = L->maxBlocks ? L->maxBlocks : frames + L->maxContent / 16384;
+    if (blocks > 0xFFFFFFF0ull) return false;
+    const u64 seqs = L->maxSequences ? L->maxSequences : L->maxContent / 3 + 64;
+    if (seqs > ((u64)1 << 48)) return false;
+    lim.frames = (u32)frames; lim.blocks = (u32)blocks; lim.content = L->maxContent; lim.sequences = seqs;
+    nRows = (u32)(tableEntries < frames ? tableEntries : frames);
+    if (!nRows) nRows = 1;
+    return true;
+}
+// the buffers of a call at the limits: the index, the ranges' rows, the arena, and the decode core's (two verdict rows behind its table)
+struct DRangesBytes { size_t index, rangesIn, rangesRec, arena; DAsyncBytes core; };
+static DRangesBytes dranges_bytes(size_t maxRanges, u32 tableEntries, u32 nRows, const BatchLimitsD& lim)
+{
+    DRangesBytes b;
+    b.index = ranges_ws_bytes(tableEntries); b.rangesIn = maxRanges * sizeof(RangeIn); b.rangesRec = maxRanges * sizeof(RangeRec);
+    b.arena = (size_t)lim.content + 64;
+    b.core = dbatch_bytes(nRows, lim);
+    b.core.batchOut += 2 * sizeof(BatchEntryOut); b.core.verdict = 0;
+    return b;
+}
+static size_t prepare_ranges_async_impl(ZSTD_DCtx* d, const void* d_src, size_t srcSize, const ZSTDMI_DRangesLimits* limits)
+{
+    if (!d || !limits) return ZERR(kErrGeneric);
+    dctx_drop_prepares(d);
+    BatchLimitsD lim; u32 nRows;
+    if (!dranges_limits(limits, 0, lim, nRows)) return ZERR(kErrParameterOutOfBound);
+    // what the pass does not cover, as far as the host alone can tell (a pending prefix stays pending)
+    if (d->workers.size() > 1 || d->pfx || d->originMode == 2) return ZERR(kErrParameterUnsupported);
+    size_t e = set_check(d); if (isErr(e)) return e;
+    e = dctx_bind(d); if (isErr(e)) return e;
+    if (d_src && !is_device_ptr(d_src)) return ZERR(kErrParameterUnsupported);
+    hipStream_t s = d->stream;
+    u32 N, stride; u64 tableBytes;
+    e = read_seek_footer(d, d_src, srcSize, true, N, stride, tableBytes); if (isErr(e)) return e;
+    e = dctx_sync_dictionary(d); if (isErr(e)) return e;
+    DecodeDict dd = decode_dict(d);
+    e = dctx_sync_slots(d, dd); if (isErr(e)) return e;
+    if (!dranges_limits(limits, N, lim, nRows)) return ZERR(kErrParameterOutOfBound);      // (maxFrames 0 = N: known only now)
+    const DRangesBytes b = dranges_bytes(limits->maxRanges, N, nRows, lim);
+    if (!d->rangesAsyncWs.ensure(b.index)) { (void)hipGetLastError(); return ZERR(kErrMemoryAllocation); }
+    const RangesWs ws = ranges_ws((u8*)d->rangesAsyncWs.p, N);
+    const u8* const tab = (const u8*)d_src + (srcSize - tableBytes);
+    launch_seek_index(tab, tableBytes, N, stride, srcSize, ws, s);
+    u64 sm[kRgWords] = {};
+    e = dev_read(sm, ws.sum, sizeof sm, s); if (isErr(e)) return e;
+    if (sm[kRgErr]) return ZERR((u32)sm[kRgErr]);
+    if (!d->rangesIn.ensure(b.rangesIn) || !d->rangesRec.ensure(b.rangesRec) || !d->arena.ensure(b.arena) || !d->batchIn.ensure(b.core.batchIn) ||
+        !d->batchOut.ensure(b.core.batchOut) || !d->frames.ensure(b.core.frames) || !d->blocks.ensure(b.core.blocks) || !d->scratch.ensure(b.core.scratch) ||
+        !d->slowFlags.ensure(b.core.slowFlags) || !d->blockKeys.ensure(b.core.blockKeys) || !d->litRooms.ensure(b.core.litRooms) || !d->recs.ensure(b.core.recs) ||
+        !d->status.ensure(b.core.status)) { (void)hipGetLastError(); return ZERR(kErrMemoryAllocation); }
+    if (!d->asyncEv && hipEventCreateWithFlags(&d->asyncEv, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); d->asyncEv = nullptr; return ZERR(kErrMemoryAllocation); }
+    d->rangesPrep = new DRangesPrep{ dctx_gen(d), limits->maxRanges, limits->maxRangeBytes, lim, lim.content + (u64)lim.frames * kLitSkew + 256,
+                                     (const u8*)d_src, tab, N, stride, sm[kRgTotal], nRows };
+    return 0;
+}
+// the prepare that is valid now, or null
+static const DRangesPrep* ranges_prep(const ZSTD_DCtx* d)
+{
+    const DRangesPrep* const P = d->rangesPrep;
+    if (!P || P->gen != dctx_gen(d) || !d->deviceOk || (d->dictDirty && !ddict_shared(d)) || (set_active(d) && d->slotGen != d->setGen)) return nullptr;
+    return P;
+}
+static size_t decompress_ranges_async_impl(ZSTD_DCtx* d, const unsigned long long* d_offsets, const size_t* d_lengths, size_t n, void* const* d_dsts,
+                                           const size_t* d_dstCapacities, size_t* d_dstSizes)
+{
+    if (!d) return ZERR(kErrGeneric);
+    if (n == 0) return 0;
+    if (!d_offsets || !d_lengths || !d_dsts || !d_dstCapacities || !d_dstSizes) return ZERR(kErrGeneric);
+    const DRangesPrep* const P = ranges_prep(d);
+    if (!P || n > P->maxRanges) return ZERR(kErrStageWrong);
+    size_t e = dctx_bind(d); if (isErr(e)) return e;
+    struct TimerOff { StageTimer& t; bool was; ~TimerOff() { t.enabled = was; } } timerOff{d->timer, d->timer.enabled};
+    d->timer.enabled = false;       // (stage events belong to calls that wait for them)
+    hipStream_t s = d->stream;
+    DecodeDict dd = decode_dict(d);
+    e = dctx_sync_slots(d, dd); if (isErr(e)) return e;       // (the table is current: nothing is uploaded)
+    const u32 nR = (u32)n, N = P->n;
+    const RangesWs ws = ranges_ws((u8*)d->rangesAsyncWs.p, N);
+    RangeIn* const dRanges = (RangeIn*)d->rangesIn.p; RangeRec* const dRecs = (RangeRec*)d->rangesRec.p;
+    e = decode_core_d(d, dd, P->lim, P->dumpOff, P->nRows, [&]() -> bool {
+        // the index persists from the prepare, the marks and the plan's summary are this call's
+        if (hipMemsetAsync(ws.diff, 0, ((size_t)N + 1) * sizeof(u32), s) != hipSuccess ||
+            hipMemsetAsync(ws.sum + kRgTouched, 0, (kRgWords - kRgTouched) * sizeof(u64), s) != hipSuccess) return false;
+        launch_ranges_select_d(d_offsets, d_lengths, d_dsts, d_dstCapacities, nR, P->maxRangeBytes, dRanges, dRecs, N, ws, s);
+        launch_ranges_plan_d(P->tab, N, P->stride, ws, (u64)(uintptr_t)P->src - kAsyncBase, (u64)(uintptr_t)d->arena.p - kAsyncBase, P->lim.frames, P->lim.content,
+                             kBatchAloneAbove, P->nRows, (BatchEntryIn*)d->batchIn.p, (BatchEntryOut*)d->batchOut.p, s);
+        return true;
+    });
+    if (isErr(e)) return e;
+    static_assert(sizeof(size_t) == sizeof(u64), "the gather writes the caller's sizes column");
+    launch_ranges_gather(dRanges, dRecs, (u64*)d_dstSizes, nR, (u32)((P->maxRangeBytes + kGatherSlice - 1) / kGatherSlice), ws, (const BatchEntryOut*)d->batchOut.p,
+                         (const u8*)d->arena.p, s);
+    return dctx_async_record(d);
 }
 
 static size_t decompress_multi(ZSTD_DCtx* d, void* dst, size_t dstCapacity, const void* src, size_t srcSize);
@@ -1736,6 +1873,32 @@ size_t ZSTDMI_decompressRanges(ZSTD_DCtx* d, const void* src, size_t srcSize, co
                                void* const* dsts, const size_t* dstCapacities, size_t* dstSizes)
 {
     return guarded([&] { if (d) d->lastDictTabBlocks = d->lastSetFrames = 0; return decompress_ranges_impl(d, src, srcSize, offsets, lengths, n, dsts, dstCapacities, dstSizes); });
+}
+size_t ZSTDMI_rangesAsyncWorkspaceD(const ZSTDMI_DRangesLimits* limits, size_t tableEntries)
+{
+    BatchLimitsD lim; u32 nRows;
+    if (!limits || !dranges_limits(limits, tableEntries, lim, nRows)) return 0;
+    const DRangesBytes b = dranges_bytes(limits->maxRanges, (u32)tableEntries, nRows, lim);
+    return b.index + b.rangesIn + b.rangesRec + b.arena + b.core.batchIn + b.core.batchOut + b.core.frames + b.core.blocks + b.core.scratch + b.core.slowFlags +
+           b.core.blockKeys + b.core.litRooms + b.core.recs + b.core.status;
+}
+size_t ZSTDMI_DCtx_prepareRangesAsync(ZSTD_DCtx* d, const void* d_src, size_t srcSize, const ZSTDMI_DRangesLimits* limits)
+{
+    return guarded([&] { return prepare_ranges_async_impl(d, d_src, srcSize, limits); });
+}
+size_t ZSTDMI_DCtx_getRangesAsyncPlan(const ZSTD_DCtx* d, size_t* tableEntries, unsigned long long* totalContent)
+{
+    if (!d) return ZERR(kErrGeneric);
+    const DRangesPrep* const P = ranges_prep(d);
+    if (!P) return ZERR(kErrStageWrong);
+    if (tableEntries) *tableEntries = P->n;
+    if (totalContent) *totalContent = P->total;
+    return 0;
+}
+size_t ZSTDMI_decompressRangesAsync(ZSTD_DCtx* d, const unsigned long long* d_offsets, const size_t* d_lengths, size_t n, void* const* d_dsts,
+                                    const size_t* d_dstCapacities, size_t* d_dstSizes)
+{
+    return guarded([&] { return decompress_ranges_async_impl(d, d_offsets, d_lengths, n, d_dsts, d_dstCapacities, d_dstSizes); });
 }
 int ZSTDMI_debugLastRangesFrames(const ZSTD_DCtx* d) { return d ? d->lastRangesFrames : -1; }
 int ZSTDMI_debugLastRangesAlone(const ZSTD_DCtx* d) { return d ? d->lastRangesAlone : -1; }

@@ -25,6 +25,7 @@ class Decompressor(_PrefixHolder):
         self._batch_unsized = False
         self._ddict = None              # the DDict RefDDict holds
         self._ddict_set = {}            # ZSTD_d_refMultipleDDicts: dictID -> every DDict the context's set references (until Dispose)
+        self._ranges_stream = None      # the tensor PrepareRangesAsync opened
         if device is not None:
             ensure_zstd_success(self._lib, self._lib.ZSTDMI_DCtx_setDevice(self.dctx, device))
 
@@ -77,6 +78,38 @@ class Decompressor(_PrefixHolder):
         ensure_zstd_success(self._lib, self._lib.ZSTDMI_DCtx_prepareBatchAsync(self.dctx, ctypes.byref(lim)))
 
     prepare_batch_async = PrepareBatchAsync
+
+    # ---- gather reads enqueued from the device (ZSTDMI_DCtx_prepareRangesAsync; batch.decompress_ranges_async runs them) ----
+    def PrepareRangesAsync(self, stream_tensor, max_ranges: int, max_range_bytes: int, max_content: int, max_frames: int = 0, max_blocks: int = 0,
+                           max_sequences: int = 0):
+        """Everything decompress_ranges_async needs the host for, once, for ONE seekable stream (a contiguous CUDA uint8 tensor, kept
+        referenced here until the next prepare or Dispose; its bytes must not change): binds the device, uploads the dictionary in
+        force, reads and indexes the stream's seek table (a damaged table raises here, with unwrap_ranges' code) and sizes every work
+        buffer for calls of at most max_ranges ranges of at most max_range_bytes returned bytes each (1 .. 4 MiB) that touch frames of
+        at most max_content bytes of content together.  max_frames (0 = the table's entry count), max_blocks and max_sequences (0 =
+        PrepareBatchAsync's defaults) bound the touched frames, their blocks and sequence records; a range beyond a limit answers
+        workSpace_tooSmall (-66).  Replaces a PrepareBatchAsync and is replaced by one; any later setter, LoadDictionary, RefDDict or
+        RefPrefix invalidates it."""
+        self._ensure_not_disposed()
+        import torch
+        self._ranges_stream = None
+        t = stream_tensor
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous()):
+            raise TypeError("expected a contiguous CUDA uint8 tensor")
+        lim = _ffi.DRangesLimits(int(max_ranges), int(max_range_bytes), int(max_content), int(max_frames), int(max_blocks), int(max_sequences))
+        torch.cuda.synchronize(t.device)        # (the prepare reads the stream on the context's stream)
+        ensure_zstd_success(self._lib, self._lib.ZSTDMI_DCtx_prepareRangesAsync(self.dctx, t.data_ptr() if t.numel() else None, t.numel(), ctypes.byref(lim)))
+        self._ranges_stream = t
+
+    prepare_ranges_async = PrepareRangesAsync
+
+    @property
+    def ranges_async_plan(self):
+        """(table_entries, total_content) of the stream the valid PrepareRangesAsync opened (ZSTDMI_DCtx_getRangesAsyncPlan)."""
+        self._ensure_not_disposed()
+        n, total = ctypes.c_size_t(0), ctypes.c_ulonglong(0)
+        ensure_zstd_success(self._lib, self._lib.ZSTDMI_DCtx_getRangesAsyncPlan(self.dctx, ctypes.byref(n), ctypes.byref(total)))
+        return n.value, total.value
 
     def LoadDictionary(self, dict_bytes):                     # S/Decompressor.cs:29-36
         self._ensure_not_disposed()
@@ -249,6 +282,7 @@ class Decompressor(_PrefixHolder):
             self.dctx = None
             self._ddict = None
             self._ddict_set = {}        # (the set went with the context: its DDicts are the caller's again)
+            self._ranges_stream = None  # (freeing the context waited for its work in flight)
 
     dispose = close = Dispose
 
