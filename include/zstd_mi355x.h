@@ -603,6 +603,42 @@ size_t ZSTDMI_compressPack(ZSTD_CCtx* cctx, void* d_dst, size_t dstCapacity,
 /* diagnostics of the last ZSTDMI_compressPack: entries the single-call path took; entries of the table written; -1 without a context */
 int       ZSTDMI_debugLastPackAlone(const ZSTD_CCtx* cctx);
 long long ZSTDMI_debugLastPackFrames(const ZSTD_CCtx* cctx);
+/* ---- a pack enqueued from the device: a seekable stream with no host round trip ----
+ * ZSTDMI_compressPack takes host arrays and stops the host per round.  ZSTDMI_compressPackAsync is the pack for a pipeline whose record
+ * lengths were made by a kernel: it serves whichever of ZSTDMI_CCtx_prepareBatchAsync / ZSTDMI_CCtx_prepareBatchAsyncLimits is valid
+ * (there is no prepare of its own; their refusals stand, and both size what the pack needs), and the work of one prepare serves
+ * ZSTDMI_compressBatchAsync and this call in any order.  The stream is what ZSTDMI_DCtx_prepareRangesAsync / ZSTDMI_decompressRangesAsync read.
+ * d_srcs, d_srcSizes, d_packSize, d_entryEnds (may be NULL) and what they point to are DEVICE memory; d_dst is a device pointer at any
+ * alignment that overlaps no source; dstCapacity is a host scalar.  The call makes no device allocation, no host wait, no copy between
+ * host and device and no host read of the arrays; it enqueues on the context's stream (ZSTDMI_CCtx_setStream) and returns: 0 once
+ * enqueued; GENERIC for a NULL context, a NULL d_packSize, or a NULL array with n > 0; dstBuffer_null for a NULL d_dst with a non-zero
+ * capacity and dstSize_tooSmall for one with capacity 0 (as ZSTDMI_compressPack); stage_wrong under the conditions of
+ * ZSTDMI_compressBatchAsync (no valid prepare, n > maxEntries, anything changed since the prepare).  n == 0 with a valid prepare enqueues
+ * the 17-byte empty table and *d_packSize = 17 (dstSize_tooSmall below 17 bytes of capacity).
+ * The stream.  For i = 0 .. n - 1 in order, exactly the bytes ZSTDMI_compressBatchAsync writes for entry i under the same prepare (an
+ * entry of size 0: the one empty frame), one entry behind the other without a gap; behind the last frame ONE seek table in the format of
+ * "Seekable streams" below (8-byte rows, descriptor 0), one row per frame in stream order: (the frame's bytes, its content size) — an
+ * empty entry's row is (empty-frame length, 0), and frames written with ZSTD_c_contentSizeFlag = 0 have their true content size there.
+ * So a call whose entries all resolve to the bound's framing and parameters (the tier rule above) writes byte for byte what
+ * ZSTDMI_compressPack writes for the same entries on a context with the same setup; entries of other tiers give a valid seekable stream
+ * that may differ in bytes.  *d_packSize is the bytes written, frames plus table; d_entryEnds[i] the offset in the stream at which entry
+ * i's frames end, so entry i occupies [d_entryEnds[i - 1], d_entryEnds[i]) with 0 for d_entryEnds[-1].
+ * A pack is one stream, so a failure fails the whole call: *d_packSize is then ONE error code — the answer of the lowest-indexed entry
+ * that fails (srcSize_wrong for a size above srcSizeBound or a NULL source with a size; workSpace_tooSmall by the maxChunks rule above),
+ * otherwise dstSize_tooSmall when frames plus table exceed dstCapacity — nothing at all is written to [d_dst, d_dst + dstCapacity), and
+ * d_entryEnds is not written.  In every case nothing is written outside [d_dst, d_dst + dstCapacity).
+ * ZSTDMI_CCtx_packAsyncBound: host arithmetic on the valid prepare, 17 + n * (ZSTD_compressBound(srcSizeBound) + 8 * F), F = the frames
+ * one entry of srcSizeBound bytes has under the prepared framing (ceil(chunks / frameBlocks); the chunk count where frameBlocks is 0; at
+ * least 1).  A call of n entries with that much room never answers dstSize_tooSmall.  GENERIC for a NULL context, stage_wrong without a
+ * valid prepare, srcSize_wrong if the sum overflows; it touches no device.
+ * ZSTDMI_debugLastPackAlone / ZSTDMI_debugLastPackFrames are NOT updated; ZSTDMI_debugHostWaits / ZSTDMI_debugDeviceAllocs do not move
+ * across the call; stage timing is off for it.  Lifetime: the rules of ZSTDMI_compressBatchAsync (arrays, sources and destination valid
+ * and unchanged until the stream has passed the work; the context waits by itself wherever it frees or regrows a buffer).  Capturing the
+ * call into a hipGraph is neither claimed nor tested.  Out of scope: packs of more than one pass, appending to a pack. */
+size_t ZSTDMI_CCtx_packAsyncBound(const ZSTD_CCtx* cctx, size_t n);
+size_t ZSTDMI_compressPackAsync(ZSTD_CCtx* cctx, void* d_dst, size_t dstCapacity,
+                                const void* const* d_srcs, const size_t* d_srcSizes, size_t n,
+                                size_t* d_packSize, size_t* d_entryEnds /* may be NULL */);
 
 /* Seekable streams (the zstd seekable format, v0.1.0): random access at the granularity of the frame.
  * Every stream this library writes is a run of independent frames (64 KiB of content at levels 1-2, 240-256 KiB at levels >= 3, 32 KiB

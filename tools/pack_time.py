@@ -10,10 +10,15 @@ tests/golden/make_golden_train.py tiled to the total with train_default_json.dic
   (d) read   : 4096 random records read back with one ZSTDMI_decompressRanges call
 Best of 3 after a warm-up call of the same shape; the host clock stops after the final synchronise.  Every pack is compared with (b)'s
 stream byte for byte and decoded back to the input.  The text is 16 MiB of generated data repeated (entries are independent).
-python tools/pack_time.py [MiB] [--json-only] [--sorted]
+python tools/pack_time.py [MiB] [--json-only] [--sorted] [--async]
   --json-only : the JSON row alone
   --sorted    : the JSON row with its records ordered by size, every record repeated in place instead of the list being tiled: a round
-                then holds one class of resolved parameters, as a pass of the batch does (which sorts the whole call by class)"""
+                then holds one class of resolved parameters, as a pass of the batch does (which sorts the whole call by class)
+  --async     : ZSTDMI_compressPackAsync instead (README "Packs enqueued from the device"): text entries of 4 KiB in packs of 16 384 and
+                of 256 KiB in packs of 1024, levels 1 and 3, every pack a stream of its own behind one prepare.  Per row, best of 3
+                after a warm-up: (a) the time until the async calls have returned, (b) until the stream has drained, (c)
+                ZSTDMI_compressPack of the same entries on a second context of the same build, all three repetitions shown.  The
+                streams are compared byte for byte afterwards (every entry is in the bound's tier)."""
 import ctypes, sys, os, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
@@ -26,7 +31,7 @@ lib = z._ffi.load()
 MiB = 1 << 20
 FLAGS = [a for a in sys.argv[1:] if a.startswith("--")]
 ARGS = [a for a in sys.argv[1:] if not a.startswith("--")]
-assert all(f in ("--json-only", "--sorted") for f in FLAGS), FLAGS
+assert all(f in ("--json-only", "--sorted", "--async") for f in FLAGS), FLAGS
 total = (int(ARGS[0]) if ARGS else 256) * MiB
 
 
@@ -72,6 +77,70 @@ def rows():
     yield "json records L1 dict+index", blob * reps, [len(r) for r in recs] * reps, 1, open(os.path.join(GOLDEN, "train_default_json.dict"), "rb").read()
 
 
+def async_rows():
+    text = datagen.gen("text", 16 * MiB, 5) * (total // (16 * MiB))
+    src = torch.from_numpy(np.frombuffer(text, dtype=np.uint8).copy()).cuda()
+    print(f"{total // MiB} MiB per row; ms (GB/s of content); (c) = ZSTDMI_compressPack, the yardstick", flush=True)
+    for size, per_pack in ((4096, 16384), (256 * 1024, 1024)):
+        for level in (1, 3):
+            n = total // size
+            packs = [(i, min(per_pack, n - i)) for i in range(0, n, per_pack)]
+            offs = np.arange(n, dtype=np.uint64) * np.uint64(size)
+            ptrs_np, szs_np = offs + np.uint64(src.data_ptr()), np.full(n, size, dtype=np.uint64)
+            d_ptrs, d_szs = torch.from_numpy(ptrs_np.astype(np.int64)).cuda(), torch.from_numpy(szs_np.astype(np.int64)).cuda()
+            with z.Compressor(level) as c, z.Compressor(level) as ref:
+                if size <= 65536:
+                    c.PrepareBatchAsync(per_pack, size)
+                else:
+                    c.PrepareBatchAsyncLimits(per_pack, size)
+                room = c.pack_async_bound(per_pack)
+                dsts = [torch.empty(room, dtype=torch.uint8, device="cuda") for _ in packs]
+                outs = [torch.empty(1, dtype=torch.int64, device="cuda") for _ in packs]
+                want = [torch.empty(room, dtype=torch.uint8, device="cuda") for _ in packs]
+                h_ptr, h_sz = arr(ctypes.c_void_p, ptrs_np), arr(ctypes.c_size_t, szs_np)
+                step = ctypes.sizeof(ctypes.c_size_t)
+
+                def run_async():
+                    for (i, k), dst, out in zip(packs, dsts, outs):
+                        z.batch.compress_pack_async(c, d_ptrs[i:i + k], d_szs[i:i + k], dst, out_size=out)
+
+                run_async(); torch.cuda.synchronize()           # warm-up
+                ta = tb = 1e9
+                for _ in range(3):
+                    torch.cuda.synchronize(); t0 = time.perf_counter()
+                    run_async()
+                    t1 = time.perf_counter()
+                    torch.cuda.synchronize()
+                    ta, tb = min(ta, t1 - t0), min(tb, time.perf_counter() - t0)
+                got = [int(o.item()) for o in outs]
+                assert all(g > 0 for g in got), got
+                sync_size = [0] * len(packs)
+
+                def run_sync():
+                    for j, (i, k) in enumerate(packs):
+                        sync_size[j] = ok(lib.ZSTDMI_compressPack(ref.cctx, want[j].data_ptr(), room, ctypes.cast(ctypes.addressof(h_ptr) + i * step, ctypes.POINTER(ctypes.c_void_p)),
+                                                                 ctypes.cast(ctypes.addressof(h_sz) + i * step, ctypes.POINTER(ctypes.c_size_t)), k))
+
+                run_sync()
+                tc = []
+                for _ in range(3):
+                    torch.cuda.synchronize(); t0 = time.perf_counter()
+                    run_sync()
+                    torch.cuda.synchronize()
+                    tc.append(time.perf_counter() - t0)
+                same = all(g == w and bool(torch.equal(d[:g], x[:w])) for g, w, d, x in zip(got, sync_size, dsts, want))
+                gbs = lambda t: total / t / 1e9
+                print(f"| text {size // 1024:4d} KiB L{level} | {n:6d} entries in {len(packs)} packs | ratio {sum(got) / total:.4f} | (a) returned {ta * 1e3:7.2f} | "
+                      f"(b) drained {tb * 1e3:8.2f} ({gbs(tb):5.1f}) | (c) {min(tc) * 1e3:8.2f} ({gbs(min(tc)):5.1f}) of {' '.join(f'{t * 1e3:.2f}' for t in tc)} | "
+                      f"bytes {'equal' if same else 'DIFFER'} |", flush=True)
+                assert same, "the async pack's streams are not ZSTDMI_compressPack's"
+            del dsts, want
+            torch.cuda.empty_cache()
+
+
+if "--async" in FLAGS:
+    async_rows()
+    sys.exit(0)
 print(f"{total // MiB} MiB per row; ms per call (GB/s of content)", flush=True)
 for name, blob, szs, level, dic in rows():
     content = len(blob)

@@ -154,6 +154,8 @@ SIGNATURES = {
     "ZSTDMI_debugLastBatchWorkspace": (ctypes.c_longlong, [c_void_p]),
     "ZSTDMI_packBound": (c_size_t, [ctypes.POINTER(c_size_t), c_size_t]),
     "ZSTDMI_compressPack": (c_size_t, [c_void_p, c_void_p, c_size_t, ctypes.POINTER(c_void_p), ctypes.POINTER(c_size_t), c_size_t]),
+    "ZSTDMI_CCtx_packAsyncBound": (c_size_t, [c_void_p, c_size_t]),
+    "ZSTDMI_compressPackAsync": (c_size_t, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
     "ZSTDMI_debugLastPackAlone": (c_int, [c_void_p]),
     "ZSTDMI_debugLastPackFrames": (ctypes.c_longlong, [c_void_p]),
     "ZSTDMI_CCtx_setSeekTable": (c_size_t, [c_void_p, c_uint]),

@@ -230,6 +230,41 @@ def compress_pack(compressor, items):
     return out[:r] if tensors else out[:r].cpu().numpy().tobytes()
 
 
+def compress_pack_async(compressor, srcs, sizes, dst, out_size=None, entry_ends=None):
+    """ZSTDMI_compressPackAsync after Compressor.PrepareBatchAsync or PrepareBatchAsyncLimits: srcs, sizes are contiguous CUDA int64
+    tensors of n entries each (pointers as integers), dst a contiguous CUDA uint8 tensor whose numel() is the capacity
+    (Compressor.pack_async_bound(n) always suffices) -> out_size, a 1-element CUDA int64 tensor: the length of the seekable stream
+    written at dst — entry i's frames as compress_batch_async writes them, one entry's behind the other's, and one seek table — or
+    the ONE error of the call as a negative value (-72 srcSize_wrong, -66 workSpace_tooSmall: the lowest failing entry's answer; else
+    -70 dstSize_tooSmall), in which case nothing of dst has been written.  entry_ends (optional, a CUDA int64 tensor of n entries)
+    receives the offset at which each entry's frames end; it is left alone on an error.
+    The work is enqueued on torch.cuda.current_stream() and the call returns: nothing is synchronised and nothing is copied to the
+    host.  The tensors and the sources must stay alive and unchanged until that stream has passed the work.  Raises ZstdException for
+    the call's own error (stage_wrong: no valid prepare, more entries than it was prepared for, or a parameter changed since)."""
+    import torch
+    compressor._ensure_not_disposed()
+    lib = compressor._lib
+    n = sizes.numel() if isinstance(sizes, torch.Tensor) else -1
+    for name, t in (("srcs", srcs), ("sizes", sizes)) + ((("entry_ends", entry_ends),) if entry_ends is not None else ()):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int64 and t.is_contiguous() and t.numel() == n):
+            raise TypeError(f"{name}: expected a contiguous CUDA int64 tensor of {n} entries")
+    if not (isinstance(dst, torch.Tensor) and dst.is_cuda and dst.dtype == torch.uint8 and dst.is_contiguous()):
+        raise TypeError("dst: expected a contiguous CUDA uint8 tensor")
+    if out_size is None:
+        out_size = torch.empty(1, dtype=torch.int64, device=dst.device)
+    if not (isinstance(out_size, torch.Tensor) and out_size.is_cuda and out_size.dtype == torch.int64 and out_size.is_contiguous() and out_size.numel() == 1):
+        raise TypeError("out_size: expected a contiguous CUDA int64 tensor of 1 entry")
+    stream = torch.cuda.current_stream(dst.device)
+    # (torch's default stream is the null stream, which ZSTDMI_CCtx_setStream reads as "the context's own": hipStreamLegacy names it)
+    r = lib.ZSTDMI_CCtx_setStream(compressor.cctx, stream.cuda_stream or _HIP_STREAM_LEGACY)
+    if not is_error(r):
+        r = lib.ZSTDMI_compressPackAsync(compressor.cctx, dst.data_ptr() if dst.numel() else None, dst.numel(), srcs.data_ptr() if n else None,
+                                         sizes.data_ptr() if n else None, n, out_size.data_ptr(), entry_ends.data_ptr() if entry_ends is not None and n else None)
+    if is_error(r):
+        raise ZstdException(get_error_code(r), lib.ZSTD_getErrorName(r).decode())
+    return out_size
+
+
 def pack_ranges(sizes):
     """-> [(offset, length), ...] for Decompressor.unwrap_ranges: record i of a pack whose items had these sizes."""
     ranges, at = [], 0

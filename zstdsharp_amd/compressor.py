@@ -273,6 +273,12 @@ class Compressor(_PrefixHolder):
         ensure_zstd_success(self._lib, self._lib.ZSTDMI_CCtx_getBatchAsyncPlan(self.cctx, ctypes.byref(cb), ctypes.byref(fb), ctypes.byref(mc)))
         return cb.value, fb.value, mc.value
 
+    def pack_async_bound(self, n: int) -> int:
+        """ZSTDMI_CCtx_packAsyncBound: the room with which batch.compress_pack_async of n entries never answers dstSize_tooSmall under
+        the valid prepare (host arithmetic); ZstdException (stage_wrong) without one."""
+        self._ensure_not_disposed()
+        return ensure_zstd_success(self._lib, self._lib.ZSTDMI_CCtx_packAsyncBound(self.cctx, int(n)))
+
     prepare_batch_async, prepare_batch_async_limits = PrepareBatchAsync, PrepareBatchAsyncLimits
 
     # ---- Wrap (S/Compressor.cs:78-96) ----

@@ -157,7 +157,10 @@ __global__ __launch_bounds__(256) void batch_place_async_kernel(const ChunkMeta*
 // verdicts and chunk counts stay in registers; the lanes' sums are scanned by wave (cross-lane shifts), the wave totals go through LDS.
 // The lane that holds the first refused entry (plan_refused) publishes its exclusive sum, the cut: every entFirst is held to it, so
 // refused, failed and empty entries own no chunk.  The caller's arrays are read here, once; the other two kernels read the copies.
+// kPack (ZSTDMI_compressPackAsync): the entries share one destination, so dsts and caps are not read (null), the dst and cap columns
+// are not written, and the verdict is pack_verdict's.
 constexpr u32 kPlanPerLane = 16;
+template <bool kPack>
 __global__ __launch_bounds__(1024) void batch_plan_entries_kernel(const void* const* __restrict__ srcs, const size_t* __restrict__ sizes,
                                                                   void* const* __restrict__ dsts, const size_t* __restrict__ caps, u32 n, u64 bound,
                                                                   u32 emptyLen, u32 chunkBytes, u32 maxChunks, const AsyncEntryTab tab)
@@ -172,12 +175,16 @@ __global__ __launch_bounds__(1024) void batch_plan_entries_kernel(const void* co
         const u32 e = e0 + k;
         cnt[k] = 0; verdict[k] = kAsyncEmpty;
         if (e < n) {
-            const u64 S = (u64)sizes[e], cap = (u64)caps[e];
-            const u64 src = (u64)(uintptr_t)srcs[e], dst = (u64)(uintptr_t)dsts[e];
-            verdict[k] = plan_verdict(src, S, dst, cap, bound, emptyLen);
+            const u64 S = (u64)sizes[e], src = (u64)(uintptr_t)srcs[e];
+            tab.src[e] = src; tab.size[e] = S;
+            if constexpr (kPack) verdict[k] = pack_verdict(src, S, bound);
+            else {
+                const u64 cap = (u64)caps[e], dst = (u64)(uintptr_t)dsts[e];
+                verdict[k] = plan_verdict(src, S, dst, cap, bound, emptyLen);
+                tab.cap[e] = cap;
+                tab.dst[e] = dst >= kAsyncBase ? dst - kAsyncBase : 0;
+            }
             cnt[k] = plan_chunks(verdict[k], S, chunkBytes);
-            tab.src[e] = src; tab.size[e] = S; tab.cap[e] = cap;
-            tab.dst[e] = dst >= kAsyncBase ? dst - kAsyncBase : 0;
         }
         mine += cnt[k];
     }
@@ -271,20 +278,25 @@ __global__ __launch_bounds__(256) void seek_entries_kernel(const u64* __restrict
 }
 
 // table: skippable header | n entries of 8 bytes | footer, one byte per lane (dst has no alignment to speak of)
-__global__ __launch_bounds__(256) void seek_table_kernel(const u32* __restrict__ entries, u32 n, u8* __restrict__ dst)
+__device__ __forceinline__ u8 seek_table_byte(const u32* __restrict__ entries, u32 n, u64 i)       // byte i < 17 + 8 n of the table
 {
     const u64 bytes = 17 + 8 * (u64)n;
-    const u64 i = (u64)blockIdx.x * 256 + threadIdx.x;
-    if (i >= bytes) return;
     u32 word; u32 k;
     if (i < 8) { word = i < 4 ? 0x184D2A5Eu : (u32)(bytes - 8); k = (u32)i & 3; }
     else if (i < 8 + 8 * (u64)n) { word = entries[(i - 8) >> 2]; k = (u32)i & 3; }
     else {
         const u32 j = (u32)(i - 8 - 8 * (u64)n);        // footer: count (4) | descriptor 0 | magic (4)
-        if (j == 4) { dst[i] = 0; return; }
+        if (j == 4) return 0;
         word = j < 4 ? n : 0x8F92EAB1u; k = j < 4 ? j : j - 5;
     }
-    dst[i] = (u8)(word >> (8 * k));
+    return (u8)(word >> (8 * k));
+}
+__global__ __launch_bounds__(256) void seek_table_kernel(const u32* __restrict__ entries, u32 n, u8* __restrict__ dst)
+{
+    const u64 bytes = 17 + 8 * (u64)n;
+    const u64 i = (u64)blockIdx.x * 256 + threadIdx.x;
+    if (i >= bytes) return;
+    dst[i] = seek_table_byte(entries, n, i);
 }
 
 // ---- a pack (ZSTDMI_compressPack): n entries' frames side by side in ONE stream, one seek table behind them ----
@@ -376,6 +388,113 @@ __global__ __launch_bounds__(256) void pack_gather_kernel(const u8* __restrict__
         const u64 hi = n < lo + kPackSlice ? n : lo + kPackSlice;
         wave_copy(dst + a + lo, arena + s0 + lo, (u32)(hi - lo), lane);
     }
+}
+
+// ---- a pack enqueued from the device (ZSTDMI_compressPackAsync): the planned batch's pass with ONE destination ----
+// The sizes are known behind seq_encode, before huf_encode and gather move a byte, and both write to absolute addresses through
+// offsets[c]: so the placement below gives every chunk its final address in the stream, and there is no arena and no second copy.
+// place, entries: in the place of batch_place_async_frames.  ONE workgroup of 1024 lanes, 16 consecutive entries per lane
+// (batch_plan_entries_kernel's shape; n <= 16384).  A lane sums its entries' chunks (pack_bytes) and counts their frames (pack_frames)
+// into registers; the lanes' sums go through a 64-bit scan of bytes and a 32-bit scan of rows by wave, the wave totals through LDS, and
+// the lowest failing entry through a min reduction.  pack_answer is the one decision — the first failure's verdict, else frames plus
+// table against the capacity — and from it every lane writes its entries' place and first row (entAt, entRow: what the chunk kernel
+// reads), the empty frames byte by byte with their rows, and entryEnds; lane 0 writes *packSize and the state the other two kernels
+// read.  After a failure nothing but *packSize and that state is written.  n == 0: the decision alone (the empty table).
+__global__ __launch_bounds__(1024) void pack_place_async_kernel(const ChunkMeta* __restrict__ meta, u32 n, const AsyncEntryTab tab, u32 frameBlocks,
+                                                                const AsyncEmptyFrame empty, u8* __restrict__ dst, u64 cap, const PackAsyncTab pk,
+                                                                size_t* __restrict__ packSize, size_t* __restrict__ entryEnds)
+{
+    __shared__ u64 waveBytes[16];
+    __shared__ u32 waveRows[16], waveFail[16];
+    const u32 tid = threadIdx.x, lane = lane_id(), wave = wave_id(), e0 = tid * kPlanPerLane;
+    u64 bytes[kPlanPerLane], mine = 0;
+    u32 rows[kPlanPerLane], myRows = 0, fail = kPackNoFail, emptyMask = 0;
+#pragma unroll
+    for (u32 k = 0; k < kPlanPerLane; ++k) {
+        const u32 e = e0 + k;
+        bytes[k] = 0; rows[k] = 0;
+        if (e < n) {
+            const u32 v = tab.verdict[e], c0 = tab.first[e], c1 = tab.first[e + 1];
+            u64 sum = 0;
+            for (u32 c = c0; c < c1; ++c) sum += meta[c].outSize;
+            bytes[k] = pack_bytes(v, sum, empty.len);
+            rows[k] = pack_frames(v, c1 - c0, frameBlocks);
+            if (v == kAsyncEmpty) emptyMask |= 1u << k;
+            if (pack_fails(v) && fail == kPackNoFail) fail = e;
+        }
+        mine += bytes[k]; myRows += rows[k];
+    }
+    const u64 inclB = wave_scan_incl64(mine);
+    const u32 inclR = wave_scan_incl(myRows);
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) { const u32 t = __shfl_xor(fail, d); fail = t < fail ? t : fail; }
+    if (lane == 63) { waveBytes[wave] = inclB; waveRows[wave] = inclR; }
+    if (lane == 0) waveFail[wave] = fail;
+    __syncthreads();
+    u64 beforeB = 0, allB = 0;
+    u32 beforeR = 0, allR = 0, failAll = kPackNoFail;
+#pragma unroll
+    for (u32 k = 0; k < 16; k++) {
+        const u64 b = waveBytes[k]; const u32 r = waveRows[k], f = waveFail[k];
+        allB += b; allR += r; failAll = f < failAll ? f : failAll;
+        if (k < wave) { beforeB += b; beforeR += r; }
+    }
+    const u64 answer = pack_answer(failAll == kPackNoFail ? kPackNoFail : tab.verdict[failAll], allB, allR, cap);
+    const bool ok = pack_answer_ok(answer);
+    if (tid == 0) { *packSize = (size_t)answer; pk.state[kPackStateOk] = ok; pk.state[kPackStateTableAt] = allB; pk.state[kPackStateRows] = allR; }
+    if (!ok) return;
+    u64 at = beforeB + inclB - mine;
+    u32 row = beforeR + inclR - myRows;
+#pragma unroll
+    for (u32 k = 0; k < kPlanPerLane; ++k) {
+        const u32 e = e0 + k;
+        if (e < n) {
+            pk.entAt[e] = at; pk.entRow[e] = row;
+            if (emptyMask >> k & 1) {
+                for (u32 i = 0; i < empty.len; ++i) dst[at + i] = empty.bytes[i];
+                pk.rows[2 * (u64)row] = empty.len; pk.rows[2 * (u64)row + 1] = 0;
+            }
+            if (entryEnds) entryEnds[e] = (size_t)(at + bytes[k]);
+        }
+        at += bytes[k]; row += rows[k];
+    }
+}
+
+// place, chunks: one lane per chunk slot of the grid.  A slot below the call's total finds its entry (plan_owner) and gets its address:
+// the destination + the entry's place + the frame bytes of the entry's chunks in front of it; the lane of a frame's first chunk files
+// the frame's row (pack_entries_kernel's pair: the chunks' frame bytes, the chunks' lengths).  An idle slot, and every slot of a failed
+// pack, gets the offset kAsyncSpan.  A lane loops over chunks of its own entry only (at most 255).
+__global__ __launch_bounds__(256) void pack_place_chunks_kernel(const ChunkMeta* __restrict__ meta, u32 n, u32 nLaunch, const AsyncEntryTab tab,
+                                                                const u32* __restrict__ len, u32 frameBlocks, const u8* __restrict__ dst,
+                                                                const PackAsyncTab pk, u64* __restrict__ offsets)
+{
+    const u32 c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= nLaunch) return;
+    u64 off = kAsyncSpan;
+    if (pk.state[kPackStateOk] && c < tab.first[n]) {
+        const u32 e = plan_owner(tab.first, n, c), c0 = tab.first[e], k = c - c0;
+        u64 inner = 0;
+        for (u32 j = c0; j < c; ++j) inner += meta[j].outSize;
+        off = pack_chunk_at(true, (u64)(uintptr_t)dst, pk.entAt[e], inner);
+        if (pack_row_lead(k, frameBlocks)) {
+            const u32 c1 = tab.first[e + 1], fb = frameBlocks ? frameBlocks : 1u, row = pack_row(pk.entRow[e], k, frameBlocks);
+            u32 cSize = 0, dSize = 0;
+            for (u32 j = c; j < c + fb && j < c1; ++j) { cSize += meta[j].outSize; dSize += len[j]; }
+            pk.rows[2 * (u64)row] = cSize; pk.rows[2 * (u64)row + 1] = dSize;
+        }
+    }
+    offsets[c] = off;
+}
+
+// table: seek_table_kernel's byte-per-lane writer with the row count and the table's place read from the placement's state; the grid
+// covers the most rows the prepare admits.  Nothing is written for a failed pack.
+__global__ __launch_bounds__(256) void pack_table_async_kernel(const PackAsyncTab pk, u8* __restrict__ dst)
+{
+    if (!pk.state[kPackStateOk]) return;
+    const u32 n = (u32)pk.state[kPackStateRows];
+    const u64 i = (u64)blockIdx.x * 256 + threadIdx.x;
+    if (i >= 17 + 8 * (u64)n) return;
+    dst[pk.state[kPackStateTableAt] + i] = seek_table_byte(pk.rows, n, i);
 }
 
 // ---- XXH64 (seed 0): 4 lanes per chunk, one per accumulator ----
@@ -547,6 +666,18 @@ void launch_pack_gather(const u8* arena, const u64* slot, const u64* size, const
     hipLaunchKernelGGL(pack_gather_kernel, dim3((nEntries + kPackGroup - 1) / kPackGroup, nSlices ? nSlices : 1), dim3(256), 0, stream, arena, slot, size, at,
                        nEntries, dst, room);
 }
+void launch_pack_place_async(const ChunkMeta* meta, u32 n, u32 nLaunch, const AsyncEntryTab& tab, const u32* len, u32 frameBlocks, AsyncEmptyFrame empty, u8* dst,
+                             u64 cap, const PackAsyncTab& pk, u64* offsets, size_t* packSize, size_t* entryEnds, hipStream_t stream)
+{
+    assert(empty.len <= sizeof empty.bytes && n <= 1024 * kPlanPerLane);
+    hipLaunchKernelGGL(pack_place_async_kernel, dim3(1), dim3(1024), 0, stream, meta, n, tab, frameBlocks, empty, dst, cap, pk, packSize, entryEnds);
+    if (nLaunch) hipLaunchKernelGGL(pack_place_chunks_kernel, dim3((nLaunch + 255) / 256), dim3(256), 0, stream, meta, n, nLaunch, tab, len, frameBlocks, dst, pk, offsets);
+}
+void launch_pack_table_async(const PackAsyncTab& pk, u64 maxRows, u8* dst, hipStream_t stream)
+{
+    const u64 bytes = 17 + 8 * maxRows;
+    hipLaunchKernelGGL(pack_table_async_kernel, dim3((u32)((bytes + 255) / 256)), dim3(256), 0, stream, pk, dst);
+}
 void launch_batch_stage(const u64* from, const u32* len, u8* stage, u32 nChunks, u32 chunkBytes, hipStream_t stream)
 {
     hipLaunchKernelGGL(batch_stage_kernel, dim3(nChunks), dim3(256), 0, stream, from, len, stage, chunkBytes);
@@ -572,7 +703,13 @@ void launch_batch_plan_entries(const void* const* srcs, const size_t* sizes, voi
                                u32 chunkBytes, u32 maxChunks, const AsyncEntryTab& tab, hipStream_t stream)
 {
     assert(n && n <= 1024 * kPlanPerLane && bound <= kAsyncBoundMax && chunkBytes);
-    hipLaunchKernelGGL(batch_plan_entries_kernel, dim3(1), dim3(1024), 0, stream, srcs, sizes, dsts, caps, n, bound, emptyLen, chunkBytes, maxChunks, tab);
+    hipLaunchKernelGGL(batch_plan_entries_kernel<false>, dim3(1), dim3(1024), 0, stream, srcs, sizes, dsts, caps, n, bound, emptyLen, chunkBytes, maxChunks, tab);
+}
+void launch_pack_plan_entries(const void* const* srcs, const size_t* sizes, u32 n, u64 bound, u32 chunkBytes, u32 maxChunks, const AsyncEntryTab& tab, hipStream_t stream)
+{
+    assert(n && n <= 1024 * kPlanPerLane && bound <= kAsyncBoundMax && chunkBytes);
+    hipLaunchKernelGGL(batch_plan_entries_kernel<true>, dim3(1), dim3(1024), 0, stream, srcs, sizes, (void* const*)nullptr, (const size_t*)nullptr, n, bound, 0u, chunkBytes,
+                       maxChunks, tab);
 }
 void launch_batch_plan_chunks(const AsyncEntryTab& tab, u32 n, u32 nLaunch, u32 chunkBytes, u32 frameBlocks, const u8* dummy, u64* from, u32* len, u32* frame,
                               hipStream_t stream)

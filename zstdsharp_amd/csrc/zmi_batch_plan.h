@@ -2,7 +2,8 @@
 // entry answers for its arguments, how many chunks it is cut into, which entries a chunk limit refuses, which entry owns a chunk, and
 // what the stages read for that chunk.  It is compress_entries' host loop (zstd_mi355x.hip) in a form a lane can evaluate for one entry
 // or one chunk.  Plain integer code without a HIP header: frame.hip's plan kernels include it under hipcc,
-// tests/host/batch_plan_harness.cpp builds it for the CPU.
+// tests/host/batch_plan_harness.cpp builds it for the CPU.  Below it, what differs for a pack of the same entries into one destination
+// (ZSTDMI_compressPackAsync): tests/host/pack_plan_harness.cpp.
 #pragma once
 #include "zmi_common.h"
 #include "zmi_frame.h"
@@ -65,5 +66,35 @@ ZMI_HD PlanChunk plan_chunk(u64 src, u64 S, u32 k, u32 chunkBytes, u32 frameBloc
 }
 // a chunk slot at or beyond the call's total: one byte read from `dummy`, a frame of its own (the stages have never seen an empty chunk)
 ZMI_HD PlanChunk plan_chunk_idle(u64 dummy) { return PlanChunk{ dummy, 1u, chunk_frame_word(0u, 1u) }; }
+
+// ---- a pack (ZSTDMI_compressPackAsync): the same entries into ONE destination, densely, one seek table behind them ----
+// An entry has no destination of its own, so plan_verdict's dst and cap checks fall away: what is left of it.
+ZMI_HD u32 pack_verdict(u64 src, u64 S, u64 bound) { return (S > bound || (S && !src)) ? (u32)kErrSrcSizeWrong : S ? (u32)kAsyncGood : (u32)kAsyncEmpty; }
+// does the entry fail the pack?  (the verdict behind plan_limited: an error code, workSpace_tooSmall included)
+ZMI_HD bool pack_fails(u32 verdict) { return verdict != kAsyncGood && verdict != kAsyncEmpty; }
+// the entry's frames = its rows in the table: frameBlocks chunks to a frame (0: every chunk a frame), an empty entry the one empty frame
+ZMI_HD u32 pack_frames(u32 verdict, u32 cnt, u32 frameBlocks)
+{
+    const u32 fb = frameBlocks ? frameBlocks : 1u;
+    return verdict == kAsyncGood ? (cnt + fb - 1) / fb : verdict == kAsyncEmpty ? 1u : 0u;
+}
+// the entry's bytes in the stream: the sum of its chunks' frame bytes, or the empty frame
+ZMI_HD u64 pack_bytes(u32 verdict, u64 chunkSum, u32 emptyLen) { return verdict == kAsyncGood ? chunkSum : verdict == kAsyncEmpty ? (u64)emptyLen : 0; }
+constexpr u32 kPackNoFail = 0xFFFFFFFFu;
+constexpr u64 kSeekTableFixed = 17;         // skippable header (8) + footer (9)
+// the one decision: failVerdict = the verdict of the lowest failing entry (kPackNoFail: none), total = the frames' bytes, frames = the
+// rows.  The answer is the stream's length or the error code as a size_t holds it; nothing is written unless pack_answer_ok.
+ZMI_HD u64 pack_answer(u32 failVerdict, u64 total, u64 frames, u64 cap)
+{
+    if (failVerdict != kPackNoFail) return (u64)0 - (u64)failVerdict;
+    const u64 all = total + kSeekTableFixed + 8 * frames;
+    return all <= cap ? all : (u64)0 - (u64)kErrDstSizeTooSmall;
+}
+ZMI_HD bool pack_answer_ok(u64 answer) { return !(answer > (u64)0 - (u64)kErrMaxCode); }     // (ZSTD_isError's comparison)
+// chunk k of an entry: the table row of its frame, whether it is that frame's first chunk (the lane that files the row), and the
+// address huf_encode and gather are given for it: the destination's offset from kAsyncBase + the entry's place + the chunks in front
+ZMI_HD u32 pack_row(u32 entRow, u32 k, u32 frameBlocks) { return entRow + (frameBlocks ? k / frameBlocks : k); }
+ZMI_HD bool pack_row_lead(u32 k, u32 frameBlocks) { return frameBlocks ? k % frameBlocks == 0 : true; }
+ZMI_HD u64 pack_chunk_at(bool ok, u64 dst, u64 entAt, u64 inner) { return ok ? dst - kAsyncBase + entAt + inner : kAsyncSpan; }
 
 } // namespace zmi

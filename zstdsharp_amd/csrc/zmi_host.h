@@ -100,6 +100,17 @@ void launch_batch_plan_chunks(const AsyncEntryTab& tab, u32 n, u32 nLaunch, u32 
                               hipStream_t stream);
 void launch_batch_place_async_frames(const ChunkMeta* meta, u32 n, u32 nLaunch, const AsyncEntryTab& tab, AsyncEmptyFrame empty, u64* offsets, size_t* dstSizes,
                                      hipStream_t stream);
+// a pack of such entries (ZSTDMI_compressPackAsync): one destination, densely packed, one seek table behind the frames.  plan_entries
+// without the dst and cap columns (pack_verdict); the placement decides on the device whether frames plus table fit `cap` and writes
+// every chunk's final address into offsets (kAsyncSpan for all of them after a failure), the empty frames, the rows, *packSize and
+// entryEnds (may be null); the table kernel's grid covers maxRows rows and takes the count and the place from the state.
+// PackAsyncTab: context memory the prepare sized: entAt / entRow per entry, rows[2 * maxRows], state[kPackStateWords].
+enum PackState : u32 { kPackStateOk = 0, kPackStateTableAt = 1, kPackStateRows = 2, kPackStateWords = 4 };
+struct PackAsyncTab { u64* entAt; u32* entRow; u32* rows; u64* state; };
+void launch_pack_plan_entries(const void* const* srcs, const size_t* sizes, u32 n, u64 bound, u32 chunkBytes, u32 maxChunks, const AsyncEntryTab& tab, hipStream_t stream);
+void launch_pack_place_async(const ChunkMeta* meta, u32 n, u32 nLaunch, const AsyncEntryTab& tab, const u32* len, u32 frameBlocks, AsyncEmptyFrame empty, u8* dst,
+                             u64 cap, const PackAsyncTab& pk, u64* offsets, size_t* packSize, size_t* entryEnds, hipStream_t stream);
+void launch_pack_table_async(const PackAsyncTab& pk, u64 maxRows, u8* dst, hipStream_t stream);
 void launch_seek_entries(const u64* offsets, const u64* total, u32 nChunks, const FrameLayout& frames, u32* entries, hipStream_t stream);
 void launch_seek_table(const u32* entries, u32 n, u8* dst, hipStream_t stream);
 // a pack (ZSTDMI_compressPack, frame.hip): a batched pass's seek-table rows per entry (entSeek[e] = the row of entry e's first frame, rows

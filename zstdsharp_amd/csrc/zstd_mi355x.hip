@@ -86,6 +86,8 @@ struct ZSTD_CCtx_s {
     // ZSTDMI_compressPack: a round's frames in bound-sized slots before they are placed, and its placement table (compress_pack_impl);
     // entries the last pack handed to the single-call path and rows of the table it wrote (debug hooks)
     DevBuf packArena, packTab; int lastPackAlone = 0; long long lastPackFrames = 0;
+    // ZSTDMI_compressPackAsync: the placement's columns, rows and state, sized by the async prepares (pack_async_tab)
+    DevBuf packAsync;
     // ZSTDMI_CCtx_setSeekTable: one (compressed size, content size) pair per frame, filed on the device by every pass of a call
     // (seekOn: this call files them) at the running index seekCount; compress_device writes the table behind the frames from them
     int seekTable = 0; bool seekOn = false; u32 seekCount = 0;
@@ -165,7 +167,7 @@ ZSTD_CCtx_s::ZSTD_CCtx_s()
 {
     tally.self = this; tally.beforeFree = [](void* self) { cctx_async_drain((ZSTD_CCtx_s*)self); };
     for (DevBuf* b : { &seqs, &lits, &meta, &tables, &slots, &offsets, &total, &cand, &probe, &stageSrc, &stageDst, &ldmSmall, &ldmBig, &dixDist, &gatherIn, &gatherOut,
-                       &batchStage, &batchTab, &packArena, &packTab, &seekEntries, &seekSort, &pfxStage, &sfXxh, &sWin,
+                       &batchStage, &batchTab, &packArena, &packTab, &packAsync, &seekEntries, &seekSort, &pfxStage, &sfXxh, &sWin,
                        &own.dict, &own.dictFullDev, &own.dictInfoDev, &own.dictCTabDev, &own.dictWideDev, &own.dictIdxDev }) b->owner = &tally;
 }
 
@@ -939,7 +941,7 @@ size_t ZSTD_freeCCtx(ZSTD_CCtx* c)
         if (c->asyncEv) (void)hipEventDestroy(c->asyncEv);
         if (c->ownStream) (void)hipStreamSynchronize(c->ownStream);
         c->seqs.release(); c->lits.release(); c->meta.release(); c->tables.release(); c->slots.release(); c->cand.release(); c->lastRegionList = nullptr; c->dixDist.release(); c->probe.release();
-        c->gatherIn.release(); c->gatherOut.release(); c->batchStage.release(); c->batchTab.release(); c->packArena.release(); c->packTab.release(); c->ldmSmall.release(); c->ldmBig.release(); c->offsets.release(); c->total.release(); c->seekEntries.release(); c->seekSort.release(); c->stageSrc.release(); c->stageDst.release(); c->pfxStage.release(); c->sfXxh.release(); c->sWin.release(); c->own.release();
+        c->gatherIn.release(); c->gatherOut.release(); c->batchStage.release(); c->batchTab.release(); c->packArena.release(); c->packTab.release(); c->packAsync.release(); c->ldmSmall.release(); c->ldmBig.release(); c->offsets.release(); c->total.release(); c->seekEntries.release(); c->seekSort.release(); c->stageSrc.release(); c->stageDst.release(); c->pfxStage.release(); c->sfXxh.release(); c->sWin.release(); c->own.release();
         c->timer.destroy();
         if (c->ownStream) (void)hipStreamDestroy(c->ownStream);
     }
@@ -2147,6 +2149,33 @@ static AsyncTab async_tab(u32 n)
     t.atVerdict = t.atFirst + ((size_t)n + 1) * 4; t.atDummy = (t.atVerdict + (size_t)n * 4 + 7) & ~(size_t)7; t.bytes = t.atDummy + 8;
     return t;
 }
+// The pass's table of a planned call, laid out once for the prepared limits (nEnt entries, nCh chunks):
+// from[nCh] | src | size | dst | cap [nEnt] (u64) | len[nCh] | frame[nCh] | first[nEnt + 1] | verdict[nEnt] (u32) | the idle slots' byte
+struct AsyncPlanTab { size_t atSrc, atSize, atDst, atCap, atLen, atFrame, atFirst, atVerdict, atDummy, bytes; };
+static AsyncPlanTab async_plan_tab(u32 nEnt, u32 nCh)
+{
+    AsyncPlanTab t;
+    t.atSrc = (size_t)nCh * 8; t.atSize = t.atSrc + (size_t)nEnt * 8; t.atDst = t.atSize + (size_t)nEnt * 8; t.atCap = t.atDst + (size_t)nEnt * 8;
+    t.atLen = t.atCap + (size_t)nEnt * 8; t.atFrame = t.atLen + (size_t)nCh * 4; t.atFirst = t.atFrame + (size_t)nCh * 4;
+    t.atVerdict = t.atFirst + ((size_t)nEnt + 1) * 4; t.atDummy = (t.atVerdict + (size_t)nEnt * 4 + 7) & ~(size_t)7; t.bytes = t.atDummy + 8;
+    return t;
+}
+static u32 chunks_of(size_t bytes, u32 chunkBytes) { return (u32)((bytes + chunkBytes - 1) / chunkBytes); }
+// What a pack adds to either prepare (ZSTDMI_compressPackAsync): the placement's columns for nEnt entries of at most F frames each —
+// entAt[nEnt] | state (u64) | entRow[nEnt] | rows[2 * nEnt * F] (u32).  pack_frames_of: F for an entry of `bound` bytes under the framing.
+struct PackAsyncLayout { size_t atState, atRow, atRows, bytes; };
+static PackAsyncLayout pack_async_tab(u32 nEnt, u32 F)
+{
+    PackAsyncLayout t;
+    t.atState = (size_t)nEnt * 8; t.atRow = t.atState + kPackStateWords * 8; t.atRows = t.atRow + (((size_t)nEnt * 4 + 7) & ~(size_t)7);
+    t.bytes = t.atRows + (size_t)nEnt * F * 8 + 8;
+    return t;
+}
+static u32 pack_frames_of(size_t bound, const Framing& fr)
+{
+    const u32 chunks = chunks_of(bound, fr.chunkBytes), F = fr.frameBlocks ? (chunks + fr.frameBlocks - 1) / fr.frameBlocks : chunks;
+    return F ? F : 1u;
+}
 static size_t prepare_batch_async_impl(ZSTD_CCtx* c, size_t maxEntries, size_t bound)
 {
     if (!c) return ZERR(kErrGeneric);
@@ -2164,7 +2193,8 @@ static size_t prepare_batch_async_impl(ZSTD_CCtx* c, size_t maxEntries, size_t b
     const LaunchState ls = launch_state(c, cp, fr);
     const u32 nCh = maxEntries ? (u32)maxEntries : 1u;
     if (!cctx_workspace(c, nCh) || (ls.regionParse && !cctx_cand_workspace(c, nCh, ls.hcChains)) || (ls.regionParse && fr.dictIndex && !cctx_dist_workspace(c, nCh)) ||
-        !c->batchStage.ensure((u64)nCh * fr.chunkBytes + 64) || !c->batchTab.ensure(async_tab(nCh).bytes)) return ZERR(kErrMemoryAllocation);
+        !c->batchStage.ensure((u64)nCh * fr.chunkBytes + 64) || !c->batchTab.ensure(std::max(async_tab(nCh).bytes, async_plan_tab((u32)maxEntries, nCh).bytes)) ||
+        !c->packAsync.ensure(pack_async_tab((u32)maxEntries, pack_frames_of(bound, fr)).bytes)) return ZERR(kErrMemoryAllocation);      // (the pack runs the planned kernels)
     if (!c->asyncEv && hipEventCreateWithFlags(&c->asyncEv, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); c->asyncEv = nullptr; return ZERR(kErrMemoryAllocation); }
     AsyncPrep* const P = new AsyncPrep{ cctx_gen(c), (u32)maxEntries, bound, cp, fr, {} };
     u8 f[18 + 3 + 4]; const size_t n = empty_frame_write(cp, f);
@@ -2174,18 +2204,6 @@ static size_t prepare_batch_async_impl(ZSTD_CCtx* c, size_t maxEntries, size_t b
     c->asyncPrep = P;
     return 0;
 }
-// The pass's table of a planned call, laid out once for the prepared limits (nEnt entries, nCh chunks):
-// from[nCh] | src | size | dst | cap [nEnt] (u64) | len[nCh] | frame[nCh] | first[nEnt + 1] | verdict[nEnt] (u32) | the idle slots' byte
-struct AsyncPlanTab { size_t atSrc, atSize, atDst, atCap, atLen, atFrame, atFirst, atVerdict, atDummy, bytes; };
-static AsyncPlanTab async_plan_tab(u32 nEnt, u32 nCh)
-{
-    AsyncPlanTab t;
-    t.atSrc = (size_t)nCh * 8; t.atSize = t.atSrc + (size_t)nEnt * 8; t.atDst = t.atSize + (size_t)nEnt * 8; t.atCap = t.atDst + (size_t)nEnt * 8;
-    t.atLen = t.atCap + (size_t)nEnt * 8; t.atFrame = t.atLen + (size_t)nCh * 4; t.atFirst = t.atFrame + (size_t)nCh * 4;
-    t.atVerdict = t.atFirst + ((size_t)nEnt + 1) * 4; t.atDummy = (t.atVerdict + (size_t)nEnt * 4 + 7) & ~(size_t)7; t.bytes = t.atDummy + 8;
-    return t;
-}
-static u32 chunks_of(size_t bytes, u32 chunkBytes) { return (u32)((bytes + chunkBytes - 1) / chunkBytes); }
 // ZSTDMI_CCtx_prepareBatchAsyncLimits: the prepare above for a bound of any number of chunks that compress_entries would batch
 static size_t prepare_batch_async_limits_impl(ZSTD_CCtx* c, const ZSTDMI_CBatchLimits* L)
 {
@@ -2212,7 +2230,8 @@ static size_t prepare_batch_async_limits_impl(ZSTD_CCtx* c, const ZSTDMI_CBatchL
     if (perEntry == 1 && !fr.frameBlocks && maxChunks >= L->maxEntries) return prepare_batch_async_impl(c, L->maxEntries, bound);
     const u32 nCh = maxChunks;
     if (!cctx_workspace(c, nCh) || (ls.regionParse && !cctx_cand_workspace(c, nCh, ls.hcChains)) || (ls.regionParse && fr.dictIndex && !cctx_dist_workspace(c, nCh)) ||
-        !c->batchStage.ensure((u64)nCh * fr.chunkBytes + 64) || !c->batchTab.ensure(async_plan_tab((u32)L->maxEntries, nCh).bytes)) return ZERR(kErrMemoryAllocation);
+        !c->batchStage.ensure((u64)nCh * fr.chunkBytes + 64) || !c->batchTab.ensure(async_plan_tab((u32)L->maxEntries, nCh).bytes) ||
+        !c->packAsync.ensure(pack_async_tab((u32)L->maxEntries, pack_frames_of(bound, fr)).bytes)) return ZERR(kErrMemoryAllocation);
     if (!c->asyncEv && hipEventCreateWithFlags(&c->asyncEv, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); c->asyncEv = nullptr; return ZERR(kErrMemoryAllocation); }
     AsyncPrep* const P = new AsyncPrep{ cctx_gen(c), (u32)L->maxEntries, bound, cp, fr, {} };
     u8 f[18 + 3 + 4]; const size_t n = empty_frame_write(cp, f);
@@ -2330,6 +2349,73 @@ extern "C" size_t ZSTDMI_compressBatchAsync(ZSTD_CCtx* c, const void* const* d_s
                                             const size_t* d_dstCapacities, size_t* d_dstSizes)
 {
     return guarded([&] { return compress_batch_async_impl(c, d_srcs, d_srcSizes, n, d_dsts, d_dstCapacities, d_dstSizes); });
+}
+// ---- a pack enqueued from the device (ZSTDMI_compressPackAsync, include/zstd_mi355x.h) ----
+// compress_batch_async_planned's pass behind EITHER prepare (the one-block prepare is its case of one chunk per entry in frames of their
+// own; it sized the planned table for that), with the pack's plan and placement: no per-entry destination, one decision for the whole
+// stream, and the seek table behind the frames.  n == 0: the placement's decision and the table alone.
+static size_t pack_async_bound_impl(const ZSTD_CCtx* c, size_t n)
+{
+    if (!c) return ZERR(kErrGeneric);
+    const AsyncPrep* const P = c->asyncPrep;
+    if (!P || P->gen != cctx_gen(c)) return ZERR(kErrStageWrong);
+    const size_t per = ZSTD_compressBound(P->bound);
+    size_t each, all, sum;
+    if (isErr(per) || __builtin_add_overflow(per, (size_t)8 * pack_frames_of(P->bound, P->fr), &each) || __builtin_mul_overflow(each, n, &all) ||
+        __builtin_add_overflow(all, (size_t)17, &sum) || isErr(sum)) return ZERR(kErrSrcSizeWrong);
+    return sum;
+}
+static size_t compress_pack_async_impl(ZSTD_CCtx* c, u8* d_dst, size_t dstCapacity, const void* const* d_srcs, const size_t* d_srcSizes, size_t n,
+                                       size_t* d_packSize, size_t* d_entryEnds)
+{
+    if (!c || !d_packSize || (n && (!d_srcs || !d_srcSizes))) return ZERR(kErrGeneric);
+    if (!d_dst) return dstCapacity ? ZERR(kErrDstBufferNull) : ZERR(kErrDstSizeTooSmall);
+    const AsyncPrep* const P = c->asyncPrep;
+    if (!P || P->gen != cctx_gen(c) || n > P->maxEntries || (c->dictDirty && !cdict_shared(c)) || !c->deviceOk) return ZERR(kErrStageWrong);
+    size_t e = cctx_bind(c); if (isErr(e)) return e;
+    struct TimerOff { StageTimer& t; bool was; ~TimerOff() { t.enabled = was; } } timerOff{c->timer, c->timer.enabled};
+    c->timer.enabled = false;       // (stage events belong to calls that wait for them)
+    c->lastRegionList = nullptr; c->lastCarryGroups = 0; c->lastBatchAlone = 0; c->lastBatchPasses = n ? 1 : 0; c->lastBatchSetChunks = 0; c->lastChunks = 0;
+    hipStream_t s = c->stream;
+    const Framing& fr = P->fr;
+    const u32 cb = fr.chunkBytes, frameBlocks = fr.frameBlocks, F = pack_frames_of(P->bound, fr), nEnt = (u32)n;
+    const u64 most = (u64)nEnt * chunks_of(P->bound, cb);
+    const u32 nCh = (u32)(most < P->maxChunks ? most : P->maxChunks);
+    const AsyncPlanTab t = async_plan_tab(P->maxEntries, P->maxChunks);
+    const PackAsyncLayout pt = pack_async_tab(P->maxEntries, F);
+    u8* const dTab = (u8*)c->batchTab.p; u8* const dPack = (u8*)c->packAsync.p;
+    u64* const dFrom = (u64*)dTab; u32* const dLen = (u32*)(dTab + t.atLen); u32* const dFrame = frameBlocks ? (u32*)(dTab + t.atFrame) : nullptr;
+    const AsyncEntryTab et = { (u64*)(dTab + t.atSrc), (u64*)(dTab + t.atSize), (u64*)(dTab + t.atDst), (u64*)(dTab + t.atCap), (u32*)(dTab + t.atFirst), (u32*)(dTab + t.atVerdict) };
+    const PackAsyncTab pk = { (u64*)dPack, (u32*)(dPack + pt.atRow), (u32*)(dPack + pt.atRows), (u64*)(dPack + pt.atState) };
+    ChunkMeta* meta = (ChunkMeta*)c->meta.p; u64* offsets = (u64*)c->offsets.p;
+    if (!nCh) {
+        launch_pack_place_async(meta, 0, 0, et, dLen, frameBlocks, P->empty, d_dst, dstCapacity, pk, offsets, d_packSize, d_entryEnds, s);
+        launch_pack_table_async(pk, 0, d_dst, s);
+        return async_enqueued(c, s);
+    }
+    const LaunchState ls = launch_state(c, P->cp, fr);
+    const u8* stage = (const u8*)c->batchStage.p;
+    Seq* seqs = (Seq*)c->seqs.p; u8* lits = (u8*)c->lits.p; HufTable* tables = (HufTable*)c->tables.p; u8* slots = (u8*)c->slots.p;
+    const u64 stagedBytes = (u64)nCh * cb;
+    launch_pack_plan_entries(d_srcs, d_srcSizes, nEnt, P->bound, cb, P->maxChunks, et, s);
+    launch_batch_plan_chunks(et, nEnt, nCh, cb, frameBlocks, dTab + t.atDummy, dFrom, dLen, dFrame, s);
+    launch_batch_stage(dFrom, dLen, (u8*)c->batchStage.p, nCh, cb, s);
+    const FrameLayout frames = dFrame ? layout_table(cb, frameBlocks, dFrame) : layout_arith(cb, 0, stagedBytes);
+    launch_lz(pass_lz(c, ls, fr, stage, stagedBytes, nCh, nCh, frames, dLen));
+    launch_huf_build(lits, meta, tables, slots, nCh, fr.rs.rawLiterals, stage, frames, s, c->timer.hook(), ls.dct);
+    if (P->cp.checksumFlag) launch_xxh64(stage, meta, nCh, frames, s, dLen);
+    launch_seq_encode(seqs, meta, slots, nCh, ls.strategy, ls.header, 1, ls.initReps, frames, s, ls.dct);
+    launch_pack_place_async(meta, nEnt, nCh, et, dLen, frameBlocks, P->empty, d_dst, dstCapacity, pk, offsets, d_packSize, d_entryEnds, s);
+    launch_huf_encode(lits, meta, tables, slots, (u8*)(uintptr_t)kAsyncBase, offsets, kAsyncSpan, nCh, stage, cb, s, ls.dct != nullptr);
+    launch_gather(stage, stagedBytes, slots, meta, offsets, (u8*)(uintptr_t)kAsyncBase, kAsyncSpan, nCh, cb, s);
+    launch_pack_table_async(pk, (u64)nEnt * F, d_dst, s);
+    return async_enqueued(c, s);
+}
+extern "C" size_t ZSTDMI_CCtx_packAsyncBound(const ZSTD_CCtx* c, size_t n) { return pack_async_bound_impl(c, n); }
+extern "C" size_t ZSTDMI_compressPackAsync(ZSTD_CCtx* c, void* d_dst, size_t dstCapacity, const void* const* d_srcs, const size_t* d_srcSizes, size_t n,
+                                           size_t* d_packSize, size_t* d_entryEnds)
+{
+    return guarded([&] { return compress_pack_async_impl(c, (u8*)d_dst, dstCapacity, d_srcs, d_srcSizes, n, d_packSize, d_entryEnds); });
 }
 extern "C" long long ZSTDMI_debugHostWaits(const ZSTD_CCtx* c) { return c ? c->tally.waits : -1; }
 extern "C" long long ZSTDMI_debugDeviceAllocs(const ZSTD_CCtx* c) { return c ? c->tally.allocs : -1; }
