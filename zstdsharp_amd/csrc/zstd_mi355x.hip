@@ -118,6 +118,7 @@ struct ZSTD_CCtx_s {
 // the whole input fits behind it in one chunk (small records, the usual dictionary case).
 constexpr size_t kDictKeep = 60u << 10;
 static u32 round_tile(size_t n) { return (u32)((n + 4095) & ~(size_t)4095); }
+static size_t chunks_of(size_t bytes, u32 chunkBytes) { return (bytes + chunkBytes - 1) / chunkBytes; }     // (not narrowed: entry_batched compares it for any size)
 // A referenced CDict's device copies serve a context on the CDict's device that has no device workers (a worker uploads its own copy,
 // as of a loaded dictionary); everywhere else the context holds a private upload of the same bytes in `own`.
 static bool cdict_shared(const ZSTD_CCtx* c) { return c->cdict && c->cdict->device == c->device && c->workers.size() <= 1; }
@@ -486,12 +487,12 @@ static Framing resolve_framing(const ZSTD_CCtx* c, const CallParams& cp, size_t 
     return f;
 }
 
-// What ZSTDMI_CCtx_prepareBatchAsync resolved: the parameters and the framing of an entry of exactly `bound` bytes — one chunk, one
-// single-block frame —, the empty frame under those parameters, and the generation it holds for.  No device pointer is kept: the launch
-// state is derived again per call (launch_state, host arithmetic), and the buffers, which only ever grow, are asked where they are.
-// maxChunks: the chunks one call may hold (the one-block prepare: maxEntries).  planned (ZSTDMI_CCtx_prepareBatchAsyncLimits for entries of
-// several chunks, or with a chunk limit below maxEntries): the call cuts the entries into chunks on the device (zmi_batch_plan.h).
-struct AsyncPrep { u64 gen; u32 maxEntries; size_t bound; CallParams cp; Framing fr; AsyncEmptyFrame empty; u32 maxChunks = 0; bool planned = false; };
+// What either async prepare resolved: the parameters and the framing of an entry of exactly `bound` bytes (ZSTDMI_CCtx_prepareBatchAsync:
+// one chunk, one single-block frame), the empty frame under those parameters, and the generation it holds for.  No device pointer is
+// kept: the launch state is derived again per call (launch_state, host arithmetic), and the buffers, which only ever grow, are asked
+// where they are.  maxChunks: the chunks one call may hold (one chunk per entry: maxEntries).  planned (entries of several chunks, or
+// a chunk limit below maxEntries): the call cuts the entries into chunks on the device (zmi_batch_plan.h).
+struct AsyncPrep { u64 gen; u32 maxEntries; size_t bound; CallParams cp; Framing fr; AsyncEmptyFrame empty; u32 maxChunks; bool planned; };
 
 // What the kernels of a pass are launched with for a framing: derived in one place for the single call (compress_range) and the
 // batch (compress_entries), whose bytes must be the same.
@@ -569,6 +570,57 @@ static bool carry_active(const ZSTD_CCtx* c, const CallParams& cp, const Framing
     const DictDigest& g = dict_in_force(c);
     return !(cp.useDict && (g.dictFormatted || !g.dictHost.empty()));
 }
+// the workspace of a pass of nCh chunks: the stages' buffers, the candidate planes of a region parse, the distance plane of its
+// chain search behind an indexed dictionary.  staged_workspace: with the staging buffer and the table of a staged pass (below)
+static bool pass_workspace(ZSTD_CCtx* c, const LaunchState& ls, const Framing& fr, u32 nCh)
+{
+    return cctx_workspace(c, nCh) && (!ls.regionParse || cctx_cand_workspace(c, nCh, ls.hcChains)) && (!ls.regionParse || !fr.dictIndex || cctx_dist_workspace(c, nCh));
+}
+static bool staged_workspace(ZSTD_CCtx* c, const LaunchState& ls, const Framing& fr, u32 nCh, size_t tabBytes)
+{
+    return pass_workspace(c, ls, fr, nCh) && c->batchStage.ensure((u64)nCh * fr.chunkBytes + 64) && c->batchTab.ensure(tabBytes);
+}
+
+// ---- the staged pass: the table form of the pipeline over c->batchStage, stated once for compress_entries, compress_batch_async_impl
+// and compress_pack_async_impl, whose bytes must be the same.  staged_encode: batch_stage -> lz -> huf_build -> [xxh64] -> seq_encode,
+// which leaves every chunk's size in its ChunkMeta; the caller's own placement kernel then fills `offsets`; staged_write: huf_encode ->
+// gather, to base + offsets[chunk] below base + span.  The marks are compress_entries' stage times; an async call has the timer off.
+struct StagedPass {
+    u32 nCh, cb; FrameLayout frames;        // chunk slots of cb bytes in the staging buffer and each one's place in its frame
+    const u64* dFrom; const u32* dLen;      // (device) where each chunk is staged from, and its length
+    const DictCTables* dct;                 // a dictionary's entropy tables; in a set pass: those of any slot ("some slot has tables")
+    const CDictSlot* dSlots; const u32* dChunkSlot;     // a set pass (two or more CDicts): the slot table and each chunk's slot, else null
+    const SeqCarry* carry;                  // carried entropy state, else null
+    bool checksum;
+};
+// (multi-block frames: each chunk's place from the table dFrame; else every chunk a frame)
+static StagedPass staged_pass(u32 nCh, const Framing& fr, const u64* dFrom, const u32* dLen, const u32* dFrame, const DictCTables* dct, bool checksum)
+{
+    const FrameLayout frames = dFrame ? layout_table(fr.chunkBytes, fr.frameBlocks, dFrame) : layout_arith(fr.chunkBytes, 0, (u64)nCh * fr.chunkBytes);
+    return StagedPass{ nCh, fr.chunkBytes, frames, dFrom, dLen, dct, nullptr, nullptr, nullptr, checksum };
+}
+static void staged_encode(ZSTD_CCtx* c, const LaunchState& ls, const Framing& fr, const StagedPass& p)
+{
+    hipStream_t s = c->stream;
+    const u8* stage = (const u8*)c->batchStage.p; Seq* seqs = (Seq*)c->seqs.p; u8* lits = (u8*)c->lits.p; ChunkMeta* meta = (ChunkMeta*)c->meta.p; u8* slots = (u8*)c->slots.p;
+    launch_batch_stage(p.dFrom, p.dLen, (u8*)c->batchStage.p, p.nCh, p.cb, s);      c->timer.mark("batch_stage", s);
+    LzLaunch lz = pass_lz(c, ls, fr, stage, (u64)p.nCh * p.cb, p.nCh, p.nCh, p.frames, p.dLen);
+    // (a set pass: the finder's set instance — behind staged tails or behind indexes — takes each chunk's dictionary from its slot)
+    assert(!p.dSlots || fr.prefixLen || fr.dictIndex);
+    if (p.dSlots) { lz.slots = p.dSlots; lz.chunkSlot = p.dChunkSlot; lz.prefix = nullptr; }
+    launch_lz(lz);
+    launch_huf_build(lits, meta, (HufTable*)c->tables.p, slots, p.nCh, fr.rs.rawLiterals, stage, p.frames, s, c->timer.hook(), p.dct, p.dSlots, p.dChunkSlot);
+    if (p.checksum) { launch_xxh64(stage, meta, p.nCh, p.frames, s, p.dLen);        c->timer.mark("xxh64", s); }
+    launch_seq_encode(seqs, meta, slots, p.nCh, ls.strategy, ls.header, 1, ls.initReps, p.frames, s, p.dct, p.dSlots, p.dChunkSlot, p.carry);      c->timer.mark("seq_encode", s);
+}
+// (the literals' tables are in force — huf_encode's dictEntropy — behind a dictionary's tables and in a carry pass)
+static void staged_write(ZSTD_CCtx* c, const StagedPass& p, u8* base, u64 span)
+{
+    hipStream_t s = c->stream;
+    const u8* stage = (const u8*)c->batchStage.p; const ChunkMeta* meta = (const ChunkMeta*)c->meta.p; u8* slots = (u8*)c->slots.p; const u64* offsets = (const u64*)c->offsets.p;
+    launch_huf_encode((const u8*)c->lits.p, meta, (const HufTable*)c->tables.p, slots, base, offsets, span, p.nCh, stage, p.cb, s, p.dct || p.carry);      c->timer.mark("huf_encode", s);
+    launch_gather(stage, (u64)p.nCh * p.cb, slots, meta, offsets, base, span, p.nCh, p.cb, s);      c->timer.mark("gather", s);
+}
 // a pass is over: its stage times into the call's, which are sums over its passes (inputs above 1 GiB take several)
 static void add_stage_times(ZSTD_CCtx* c, bool& first)
 {
@@ -626,9 +678,7 @@ static size_t compress_range(ZSTD_CCtx* c, const CallParams& cp, u8* d_dst, size
     // ZSTDMI_CCtx_setPassChunks (a stream's batch ends a group where it ends)
     const bool carry = carry_active(c, cp, fr, ls);
     if (carry && fr.single && passChunks < totalChunks) passChunks = carry_pass_chunks(passChunks);
-    if (!cctx_workspace(c, passChunks)) return ZERR(kErrMemoryAllocation);
-    if (ls.regionParse && !cctx_cand_workspace(c, passChunks, ls.hcChains)) return ZERR(kErrMemoryAllocation);
-    if (ls.regionParse && fr.dictIndex && !cctx_dist_workspace(c, passChunks)) return ZERR(kErrMemoryAllocation);
+    if (!pass_workspace(c, ls, fr, passChunks)) return ZERR(kErrMemoryAllocation);
     size_t produced = 0;
     for (u64 c0 = 0; c0 < totalChunks; c0 += passChunks) {
         const u32 nChunks = (u32)((totalChunks - c0) < passChunks ? (totalChunks - c0) : passChunks);
@@ -1834,14 +1884,14 @@ size_t ZSTD_compressStream2(ZSTD_CCtx* c, ZSTD_outBuffer* output, ZSTD_inBuffer*
 // ---- a batch of independent entries, each compressed as the single call would compress it alone (ZSTDMI_compressBatch; the
 // dictionary trainer's inner loop, dict_train.hip) ----
 // Entries of one framing class (same dictionary prefix, chunk size, blocks per frame and resolved parameters) go through the pipeline
-// together: each chunk of an entry is staged at its own chunk boundary (batch_stage_kernel) and the finder and the checksum take its
+// together (staged_encode): each chunk of an entry is staged at its own chunk boundary (batch_stage_kernel) and the finder and the checksum take its
 // length from a per-chunk table (chunkLens).  Where every chunk is a frame of its own, what is written for it depends on nothing
 // beside it.  Multi-block frames behind LDS history (the small-call 16 KiB cut of levels 1-2, the 48 / 32 KiB blocks of the dual-hash
 // and chain finders) take a second column (chunkFrames): the block's index inside its frame and the frame's content size, which the
 // single call derives from its total size; all chunks of an entry but the last are full, so a block's history lies in front of it in
 // the staging buffer as it does in the entry.  With
 // destinations, batch_place_kernel gives every chunk its place as an offset from the lowest destination pointer and huf_encode and
-// gather write there directly; without (the trainer), only the sizes come back.  A pass holds whole entries, at most
+// gather write there directly (staged_write); without (the trainer), only the sizes come back.  A pass holds whole entries, at most
 // ZSTDMI_CCtx_setPassChunks chunks; per pass one table goes up and the entries' sizes come back in one copy.
 // An entry the class model does not cover — empty, windows below 64 KiB above one window, LDM above one block, more than one block under
 // ZSTDMI_CCtx_setSingleFrame (one frame per entry: a framing of its own), the fast strategy's
@@ -1870,13 +1920,13 @@ size_t ZSTD_compressStream2(ZSTD_CCtx* c, ZSTD_outBuffer* output, ZSTD_inBuffer*
 // its entries by it, and for ZSTDMI_compressPack, which cuts its rounds by it.
 static bool entry_batched(ZSTD_CCtx* c, const CallParams& cp, size_t S, const Framing& fr, u32 passLimit, bool dct, bool stats)
 {
-    bool batched = S && !fr.indepWindowLog && !fr.ldm && !fr.single && c->workers.size() <= 1 && (S + fr.chunkBytes - 1) / fr.chunkBytes <= passLimit;
+    bool batched = S && !fr.indepWindowLog && !fr.ldm && !fr.single && c->workers.size() <= 1 && chunks_of(S, fr.chunkBytes) <= passLimit;
     // multi-block frames: the blocks behind LDS history (chunks below 64 KiB; the full 64 KiB blocks with far candidates have no
     // table form, launch_lz), below 4 MiB and of at most 256 chunks (a block index and a frame size that fit chunk_frame_word);
     // with a dictionary's entropy tables (huf_tree_kernel<true> finds a frame's first block in the arithmetic form alone), or with sizes
     // only and statistics (the trainer's finalize step), as before: alone
     if (batched && fr.frameBlocks)
-        batched = S < (4u << 20) && (S + fr.chunkBytes - 1) / fr.chunkBytes <= 256 && fr.chunkBytes < kChunkSize && !dct && !stats;
+        batched = S < (4u << 20) && chunks_of(S, fr.chunkBytes) <= 256 && fr.chunkBytes < kChunkSize && !dct && !stats;
     if (batched && S >= (4u << 20)) { size_t err = 0; if (probe_group_bytes(c, cp, S, err) || isErr(err)) batched = false; }
     return batched;
 }
@@ -1945,14 +1995,12 @@ static size_t compress_entries(ZSTD_CCtx* c, const CallParams& cp, const u8* con
     std::vector<u32> chunkSlot, used; std::vector<CDictSlot> slotTab; std::vector<u8> slotDone;
     for (const Group& g : groups) {
         const u32 cb = g.fr.chunkBytes, frameBlocks = g.fr.frameBlocks;
-        const Resolved rs = g.fr.rs;
-        LaunchState ls = launch_state(c, params_of(g.members[0]), g.fr);
-        const bool regionParse = ls.regionParse, hcChains = ls.hcChains;
+        LaunchState ls = launch_state(c, params_of(g.members[0]), g.fr);      // (what sizes the workspace is the group's: same_launch_params)
         for (size_t m0 = 0; m0 < g.members.size(); ) {
             // the pass: whole entries, up to passLimit chunks
             size_t m1 = m0; u32 nCh = 0;
             while (m1 < g.members.size()) {
-                const u32 k = (u32)((sizes[g.members[m1]] + cb - 1) / cb);
+                const u32 k = (u32)chunks_of(sizes[g.members[m1]], cb);
                 if (nCh && nCh + k > passLimit) break;
                 nCh += k; ++m1;
             }
@@ -1967,7 +2015,7 @@ static size_t compress_entries(ZSTD_CCtx* c, const CallParams& cp, const u8* con
             Framing fr = g.fr;
             if (cdicts) {
                 chunkSlot.clear();
-                for (size_t m = m0; m < m1; ++m) chunkSlot.insert(chunkSlot.end(), (sizes[g.members[m]] + cb - 1) / cb, slotOf[g.members[m]]);
+                for (size_t m = m0; m < m1; ++m) chunkSlot.insert(chunkSlot.end(), chunks_of(sizes[g.members[m]], cb), slotOf[g.members[m]]);
                 if (!cdict_pass_image(chunkSlot, used)) return ZERR(kErrMemoryAllocation);
                 slotTab.assign(used.size(), CDictSlot{});
                 slotDone.assign(used.size(), 0);
@@ -2024,47 +2072,30 @@ static size_t compress_entries(ZSTD_CCtx* c, const CallParams& cp, const u8* con
                 }
             }
             hFirst[nEnt] = ck;
-            SeqCarry sc = { (HufTable*)nullptr, nullptr, 0, rs.rawLiterals };
-            if (carry) { sc.nGroups = carry_leaders_table(hFrame, nCh, (u32*)(tab.data() + atLead)); c->lastCarryGroups += sc.nGroups; }
-            if (!cctx_workspace(c, nCh) || (regionParse && !cctx_cand_workspace(c, nCh, hcChains)) || (regionParse && g.fr.dictIndex && !cctx_dist_workspace(c, nCh)) || !c->batchStage.ensure((u64)nCh * cb + 64) ||
-                !c->batchTab.ensure(tabBytes + (size_t)nEnt * 8)) return ZERR(kErrMemoryAllocation);
+            u32 carryGroups = 0;
+            if (carry) { carryGroups = carry_leaders_table(hFrame, nCh, (u32*)(tab.data() + atLead)); c->lastCarryGroups += carryGroups; }
+            if (!staged_workspace(c, ls, fr, nCh, tabBytes + (size_t)nEnt * 8)) return ZERR(kErrMemoryAllocation);
             u8* const dTab = (u8*)c->batchTab.p;
             const u32* const dLen = (const u32*)(dTab + atLen);
-            const u32* const dFrame = frameBlocks ? (const u32*)(dTab + atFrame) : nullptr;
             u64* const dGot = (u64*)(dTab + tabBytes);
             if (hipMemcpyAsync(dTab, tab.data(), tabBytes, hipMemcpyHostToDevice, s) != hipSuccess) return ZERR(kErrGeneric);
-            const u8* stage = (const u8*)c->batchStage.p;
-            Seq* seqs = (Seq*)c->seqs.p; u8* lits = (u8*)c->lits.p; ChunkMeta* meta = (ChunkMeta*)c->meta.p;
-            HufTable* tables = (HufTable*)c->tables.p; u8* slots = (u8*)c->slots.p; u64* offsets = (u64*)c->offsets.p;
-            const u64 stagedBytes = (u64)nCh * cb;
+            ChunkMeta* meta = (ChunkMeta*)c->meta.p;
+            // (dct: single-block frames only, see above)
+            StagedPass pass = staged_pass(nCh, fr, (const u64*)dTab, dLen, frameBlocks ? (const u32*)(dTab + atFrame) : nullptr, dct, cp.checksumFlag);
+            if (set) { pass.dSlots = (const CDictSlot*)(dTab + atSlots); pass.dChunkSlot = (const u32*)(dTab + atChunkSlot); }
+            const SeqCarry sc = { (HufTable*)c->tables.p, (const u32*)(dTab + atLead), carryGroups, fr.rs.rawLiterals };
+            if (carry) pass.carry = &sc;
             c->timer.begin(s);
-            launch_batch_stage((const u64*)dTab, dLen, (u8*)c->batchStage.p, nCh, cb, s);      c->timer.mark("batch_stage", s);
-            // (multi-block frames: each chunk's place from the table; else every chunk a frame.  dct: single-block frames only, see above)
-            const FrameLayout frames = dFrame ? layout_table(cb, frameBlocks, dFrame) : layout_arith(cb, 0, stagedBytes);
-            const CDictSlot* const dSlots = set ? (const CDictSlot*)(dTab + atSlots) : nullptr;
-            const u32* const dChunkSlot = set ? (const u32*)(dTab + atChunkSlot) : nullptr;
-            LzLaunch lz = pass_lz(c, ls, fr, stage, stagedBytes, nCh, nCh, frames, dLen);
-            // (a set pass: the finder's set instance — behind staged tails or behind indexes — takes each chunk's dictionary from its slot)
-            assert(!set || fr.prefixLen || fr.dictIndex);
-            if (set) { lz.slots = dSlots; lz.chunkSlot = dChunkSlot; lz.prefix = nullptr; }
-            launch_lz(lz);
-            launch_huf_build(lits, meta, tables, slots, nCh, rs.rawLiterals, stage, frames, s, c->timer.hook(), dct, dSlots, dChunkSlot);
-            if (cp.checksumFlag) { launch_xxh64(stage, meta, nCh, frames, s, dLen);        c->timer.mark("xxh64", s); }
-            sc.tables = tables; sc.leaders = (const u32*)(dTab + atLead);
-            launch_seq_encode(seqs, meta, slots, nCh, ls.strategy, ls.header, 1, ls.initReps, frames, s, dct, dSlots, dChunkSlot, carry ? &sc : nullptr);
-            c->timer.mark("seq_encode", s);
+            staged_encode(c, ls, fr, pass);
             c->lastBatchPasses++; if (set) c->lastBatchSetChunks += nCh;
-            if (d_stats) launch_seq_stats(seqs, lits, meta, nCh, stage, cb, d_stats, s);
-            launch_batch_place(meta, nEnt, (const u32*)(dTab + atFirst), (const u64*)(dTab + atDst), (const u64*)(dTab + atCap), span, offsets, dGot, s);
+            if (d_stats) launch_seq_stats((Seq*)c->seqs.p, (u8*)c->lits.p, meta, nCh, (const u8*)c->batchStage.p, cb, d_stats, s);
+            launch_batch_place(meta, nEnt, (const u32*)(dTab + atFirst), (const u64*)(dTab + atDst), (const u64*)(dTab + atCap), span, (u64*)c->offsets.p, dGot, s);
             c->timer.mark("batch_place", s);
             if (seekIdx) {
                 launch_pack_entries(meta, nEnt, (const u32*)(dTab + atFirst), dLen, frameBlocks, (const u32*)(dTab + atSeek), (u32*)c->seekEntries.p, seekCap, s);
                 c->timer.mark("pack_entries", s);
             }
-            if (dsts) {
-                launch_huf_encode(lits, meta, tables, slots, base, offsets, span, nCh, stage, cb, s, dct != nullptr || carry);     c->timer.mark("huf_encode", s);
-                launch_gather(stage, stagedBytes, slots, meta, offsets, base, span, nCh, cb, s);          c->timer.mark("gather", s);
-            }
+            if (dsts) staged_write(c, pass, base, span);
             got.resize(nEnt);
             if (isErr(dev_read(got.data(), dGot, (size_t)nEnt * 8, s))) return ZERR(kErrGeneric);
             add_stage_times(c, first);
@@ -2160,7 +2191,6 @@ static AsyncPlanTab async_plan_tab(u32 nEnt, u32 nCh)
     t.atVerdict = t.atFirst + ((size_t)nEnt + 1) * 4; t.atDummy = (t.atVerdict + (size_t)nEnt * 4 + 7) & ~(size_t)7; t.bytes = t.atDummy + 8;
     return t;
 }
-static u32 chunks_of(size_t bytes, u32 chunkBytes) { return (u32)((bytes + chunkBytes - 1) / chunkBytes); }
 // What a pack adds to either prepare (ZSTDMI_compressPackAsync): the placement's columns for nEnt entries of at most F frames each —
 // entAt[nEnt] | state (u64) | entRow[nEnt] | rows[2 * nEnt * F] (u32).  pack_frames_of: F for an entry of `bound` bytes under the framing.
 struct PackAsyncLayout { size_t atState, atRow, atRows, bytes; };
@@ -2176,33 +2206,49 @@ static u32 pack_frames_of(size_t bound, const Framing& fr)
     const u32 chunks = chunks_of(bound, fr.chunkBytes), F = fr.frameBlocks ? (chunks + fr.frameBlocks - 1) / fr.frameBlocks : chunks;
     return F ? F : 1u;
 }
-static size_t prepare_batch_async_impl(ZSTD_CCtx* c, size_t maxEntries, size_t bound)
+// Both async prepares behind their own device-free refusals, from the call's parameters to the AsyncPrep with its empty frame.
+// chunkLimit: the chunks a call may hold (0: every entry's, up to the pass limit).  oneBlock: ZSTDMI_CCtx_prepareBatchAsync, which
+// refuses what is not one chunk in a single-block frame.
+static size_t prepare_async_core(ZSTD_CCtx* c, size_t maxEntries, size_t bound, size_t chunkLimit, bool oneBlock)
 {
-    if (!c) return ZERR(kErrGeneric);
-    delete c->asyncPrep; c->asyncPrep = nullptr;
-    // what the one-block batched pass does not cover, as far as the host alone can tell
-    if (!bound || bound > kChunkSize || c->workers.size() > 1 || c->seekTable || c->pfx || maxEntries > batch_pass_limit(c)) return ZERR(kErrParameterUnsupported);
+    const u32 passLimit = batch_pass_limit(c);
     const CallParams cp = sticky_params(c);
     size_t e = check_call_params(cp); if (isErr(e)) return e;
     e = cctx_bind(c); if (isErr(e)) return e;
     e = cctx_sync_dictionary(c); if (isErr(e)) return e;
     // (a formatted dictionary's tail is known once it has been validated, so the framing is resolved behind the upload)
     const Framing fr = resolve_framing(c, cp, bound);
-    if (bound > fr.chunkBytes || fr.frameBlocks || !entry_batched(c, cp, bound, fr, batch_pass_limit(c), call_dict_ctables(c, cp) != nullptr, false))
+    if ((oneBlock && (bound > fr.chunkBytes || fr.frameBlocks)) || !entry_batched(c, cp, bound, fr, passLimit, call_dict_ctables(c, cp) != nullptr, false))
         return ZERR(kErrParameterUnsupported);
     const LaunchState ls = launch_state(c, cp, fr);
-    const u32 nCh = maxEntries ? (u32)maxEntries : 1u;
-    if (!cctx_workspace(c, nCh) || (ls.regionParse && !cctx_cand_workspace(c, nCh, ls.hcChains)) || (ls.regionParse && fr.dictIndex && !cctx_dist_workspace(c, nCh)) ||
-        !c->batchStage.ensure((u64)nCh * fr.chunkBytes + 64) || !c->batchTab.ensure(std::max(async_tab(nCh).bytes, async_plan_tab((u32)maxEntries, nCh).bytes)) ||
-        !c->packAsync.ensure(pack_async_tab((u32)maxEntries, pack_frames_of(bound, fr)).bytes)) return ZERR(kErrMemoryAllocation);      // (the pack runs the planned kernels)
+    if (carry_active(c, cp, fr, ls)) return ZERR(kErrParameterUnsupported);       // (its group count is a host launch argument)
+    const u32 perEntry = (u32)chunks_of(bound, fr.chunkBytes);
+    if (chunkLimit && chunkLimit < perEntry) return ZERR(kErrParameterOutOfBound);
+    const u64 most = (u64)maxEntries * perEntry;
+    u32 maxChunks = chunkLimit ? (u32)chunkLimit : (u32)(most < passLimit ? most : passLimit);
+    // one block in a single-block frame and room for every entry: entry e is chunk e (batch_plan_kernel), whichever prepare was called;
+    // the table is sized for the planned kernels too, which the pack runs
+    const bool planned = !(perEntry == 1 && !fr.frameBlocks && maxChunks >= maxEntries);
+    if (!planned) maxChunks = (u32)maxEntries;
+    const u32 nCh = maxChunks ? maxChunks : 1u;
+    const size_t tabBytes = async_plan_tab((u32)maxEntries, nCh).bytes;
+    if (!staged_workspace(c, ls, fr, nCh, planned ? tabBytes : std::max(async_tab(nCh).bytes, tabBytes)) ||
+        !c->packAsync.ensure(pack_async_tab((u32)maxEntries, pack_frames_of(bound, fr)).bytes)) return ZERR(kErrMemoryAllocation);
     if (!c->asyncEv && hipEventCreateWithFlags(&c->asyncEv, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); c->asyncEv = nullptr; return ZERR(kErrMemoryAllocation); }
-    AsyncPrep* const P = new AsyncPrep{ cctx_gen(c), (u32)maxEntries, bound, cp, fr, {} };
+    AsyncPrep* const P = new AsyncPrep{ cctx_gen(c), (u32)maxEntries, bound, cp, fr, {}, maxChunks, planned };
     u8 f[18 + 3 + 4]; const size_t n = empty_frame_write(cp, f);
     assert(n <= sizeof P->empty.bytes);
     memcpy(P->empty.bytes, f, n); P->empty.len = (u32)n;
-    P->maxChunks = (u32)maxEntries;
     c->asyncPrep = P;
     return 0;
+}
+static size_t prepare_batch_async_impl(ZSTD_CCtx* c, size_t maxEntries, size_t bound)
+{
+    if (!c) return ZERR(kErrGeneric);
+    delete c->asyncPrep; c->asyncPrep = nullptr;
+    // what the one-block batched pass does not cover, as far as the host alone can tell
+    if (!bound || bound > kChunkSize || c->workers.size() > 1 || c->seekTable || c->pfx || maxEntries > batch_pass_limit(c)) return ZERR(kErrParameterUnsupported);
+    return prepare_async_core(c, maxEntries, bound, maxEntries, true);
 }
 // ZSTDMI_CCtx_prepareBatchAsyncLimits: the prepare above for a bound of any number of chunks that compress_entries would batch
 static size_t prepare_batch_async_limits_impl(ZSTD_CCtx* c, const ZSTDMI_CBatchLimits* L)
@@ -2210,36 +2256,10 @@ static size_t prepare_batch_async_limits_impl(ZSTD_CCtx* c, const ZSTDMI_CBatchL
     if (!c || !L) return ZERR(kErrGeneric);
     delete c->asyncPrep; c->asyncPrep = nullptr;
     const u32 passLimit = batch_pass_limit(c);
-    const size_t bound = L->srcSizeBound;
-    if (!L->maxEntries || L->maxEntries > passLimit || !bound || bound > kAsyncBoundMax || L->maxChunks > passLimit ||
+    if (!L->maxEntries || L->maxEntries > passLimit || !L->srcSizeBound || L->srcSizeBound > kAsyncBoundMax || L->maxChunks > passLimit ||
         L->reserved[0] || L->reserved[1] || L->reserved[2]) return ZERR(kErrParameterOutOfBound);
     if (c->workers.size() > 1 || c->seekTable || c->pfx) return ZERR(kErrParameterUnsupported);
-    const CallParams cp = sticky_params(c);
-    size_t e = check_call_params(cp); if (isErr(e)) return e;
-    e = cctx_bind(c); if (isErr(e)) return e;
-    e = cctx_sync_dictionary(c); if (isErr(e)) return e;
-    const Framing fr = resolve_framing(c, cp, bound);
-    if (!entry_batched(c, cp, bound, fr, passLimit, call_dict_ctables(c, cp) != nullptr, false)) return ZERR(kErrParameterUnsupported);
-    const LaunchState ls = launch_state(c, cp, fr);
-    if (carry_active(c, cp, fr, ls)) return ZERR(kErrParameterUnsupported);       // (its group count is a host launch argument)
-    const u32 perEntry = chunks_of(bound, fr.chunkBytes);
-    if (L->maxChunks && L->maxChunks < perEntry) return ZERR(kErrParameterOutOfBound);
-    const u64 most = (u64)L->maxEntries * perEntry;
-    const u32 maxChunks = L->maxChunks ? (u32)L->maxChunks : (u32)(most < passLimit ? most : passLimit);
-    // one block in a single-block frame and room for every entry: the one-block prepare's state, and so its launches
-    if (perEntry == 1 && !fr.frameBlocks && maxChunks >= L->maxEntries) return prepare_batch_async_impl(c, L->maxEntries, bound);
-    const u32 nCh = maxChunks;
-    if (!cctx_workspace(c, nCh) || (ls.regionParse && !cctx_cand_workspace(c, nCh, ls.hcChains)) || (ls.regionParse && fr.dictIndex && !cctx_dist_workspace(c, nCh)) ||
-        !c->batchStage.ensure((u64)nCh * fr.chunkBytes + 64) || !c->batchTab.ensure(async_plan_tab((u32)L->maxEntries, nCh).bytes) ||
-        !c->packAsync.ensure(pack_async_tab((u32)L->maxEntries, pack_frames_of(bound, fr)).bytes)) return ZERR(kErrMemoryAllocation);
-    if (!c->asyncEv && hipEventCreateWithFlags(&c->asyncEv, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); c->asyncEv = nullptr; return ZERR(kErrMemoryAllocation); }
-    AsyncPrep* const P = new AsyncPrep{ cctx_gen(c), (u32)L->maxEntries, bound, cp, fr, {} };
-    u8 f[18 + 3 + 4]; const size_t n = empty_frame_write(cp, f);
-    assert(n <= sizeof P->empty.bytes);
-    memcpy(P->empty.bytes, f, n); P->empty.len = (u32)n;
-    P->maxChunks = maxChunks; P->planned = true;
-    c->asyncPrep = P;
-    return 0;
+    return prepare_async_core(c, L->maxEntries, L->srcSizeBound, L->maxChunks, false);
 }
 static size_t batch_async_plan_impl(const ZSTD_CCtx* c, size_t* chunkBytes, size_t* frameBlocks, size_t* maxChunks)
 {
@@ -2261,76 +2281,61 @@ static size_t async_enqueued(ZSTD_CCtx* c, hipStream_t s)
     c->asyncPending = true;
     return 0;
 }
-// A planned call: compress_entries' table-form pass (its frames from chunk_frame_word; independent frames where the framing has no
-// frameBlocks) with the two plan kernels in the place of the host loop and the upload.  Every grid is nLaunch chunk slots, host
-// arithmetic on the entry count and the prepared limits; slots beyond the call's chunks compress one idle byte that is placed nowhere.
-static size_t compress_batch_async_planned(ZSTD_CCtx* c, const AsyncPrep* P, const void* const* d_srcs, const size_t* d_srcSizes, u32 n, void* const* d_dsts,
-                                           const size_t* d_dstCapacities, size_t* d_dstSizes)
+// What an async call begins with: the prepare must hold for the context as it stands; then the device, the stage timer off for the
+// length of the call (AsyncCall puts it back) and the debug counters of a call of one pass.
+struct AsyncCall { StageTimer* timer = nullptr; bool was = false; ~AsyncCall() { if (timer) timer->enabled = was; } };
+static size_t async_begin(ZSTD_CCtx* c, size_t n, AsyncCall& call)
 {
-    hipStream_t s = c->stream;
-    const Framing& fr = P->fr;
-    const LaunchState ls = launch_state(c, P->cp, fr);
-    const u32 cb = fr.chunkBytes, frameBlocks = fr.frameBlocks;
-    const u64 most = (u64)n * chunks_of(P->bound, cb);
-    const u32 nCh = (u32)(most < P->maxChunks ? most : P->maxChunks);
-    const AsyncPlanTab t = async_plan_tab(P->maxEntries, P->maxChunks);
-    u8* const dTab = (u8*)c->batchTab.p;
-    u64* const dFrom = (u64*)dTab; u32* const dLen = (u32*)(dTab + t.atLen); u32* const dFrame = frameBlocks ? (u32*)(dTab + t.atFrame) : nullptr;
-    const AsyncEntryTab et = { (u64*)(dTab + t.atSrc), (u64*)(dTab + t.atSize), (u64*)(dTab + t.atDst), (u64*)(dTab + t.atCap), (u32*)(dTab + t.atFirst), (u32*)(dTab + t.atVerdict) };
-    const u8* stage = (const u8*)c->batchStage.p;
-    Seq* seqs = (Seq*)c->seqs.p; u8* lits = (u8*)c->lits.p; ChunkMeta* meta = (ChunkMeta*)c->meta.p;
-    HufTable* tables = (HufTable*)c->tables.p; u8* slots = (u8*)c->slots.p; u64* offsets = (u64*)c->offsets.p;
-    const u64 stagedBytes = (u64)nCh * cb;
-    launch_batch_plan_entries(d_srcs, d_srcSizes, d_dsts, d_dstCapacities, n, P->bound, P->empty.len, cb, P->maxChunks, et, s);
-    launch_batch_plan_chunks(et, n, nCh, cb, frameBlocks, dTab + t.atDummy, dFrom, dLen, dFrame, s);
-    launch_batch_stage(dFrom, dLen, (u8*)c->batchStage.p, nCh, cb, s);
-    const FrameLayout frames = dFrame ? layout_table(cb, frameBlocks, dFrame) : layout_arith(cb, 0, stagedBytes);
-    launch_lz(pass_lz(c, ls, fr, stage, stagedBytes, nCh, nCh, frames, dLen));
-    launch_huf_build(lits, meta, tables, slots, nCh, fr.rs.rawLiterals, stage, frames, s, c->timer.hook(), ls.dct);
-    if (P->cp.checksumFlag) launch_xxh64(stage, meta, nCh, frames, s, dLen);
-    launch_seq_encode(seqs, meta, slots, nCh, ls.strategy, ls.header, 1, ls.initReps, frames, s, ls.dct);
-    launch_batch_place_async_frames(meta, n, nCh, et, P->empty, offsets, d_dstSizes, s);
-    launch_huf_encode(lits, meta, tables, slots, (u8*)(uintptr_t)kAsyncBase, offsets, kAsyncSpan, nCh, stage, cb, s, ls.dct != nullptr);
-    launch_gather(stage, stagedBytes, slots, meta, offsets, (u8*)(uintptr_t)kAsyncBase, kAsyncSpan, nCh, cb, s);
-    return async_enqueued(c, s);
+    const AsyncPrep* const P = c->asyncPrep;
+    if (!P || P->gen != cctx_gen(c) || n > P->maxEntries || (c->dictDirty && !cdict_shared(c)) || !c->deviceOk) return ZERR(kErrStageWrong);
+    const size_t e = cctx_bind(c); if (isErr(e)) return e;
+    call.timer = &c->timer; call.was = c->timer.enabled;
+    c->timer.enabled = false;       // (stage events belong to calls that wait for them)
+    c->lastRegionList = nullptr; c->lastCarryGroups = 0; c->lastBatchAlone = 0; c->lastBatchPasses = n ? 1 : 0; c->lastBatchSetChunks = 0; c->lastChunks = 0;
+    return 0;
 }
-// One pass of compress_entries between its table upload and its read-back, with the plan kernel in the place of the first and the
-// caller's column in the place of the second: kernels (and the finder's two 4-byte hipMemsetAsync) only.
+// The table of a call of n entries as the kernels take it, and nCh, the chunk slots every grid of the call has: host arithmetic on the
+// entry count and the prepared limits; slots beyond the call's chunks compress one idle byte that is placed nowhere.  planned: the
+// layout of async_plan_tab; else async_tab's, one chunk per entry (no src and size columns, no frame words).
+struct AsyncPass { AsyncEntryTab et; u64* dFrom; u32* dLen; u32* dFrame; const u8* dummy; u32 nCh; };
+static AsyncPass async_pass(const ZSTD_CCtx* c, const AsyncPrep* P, u32 n, bool planned)
+{
+    u8* const dTab = (u8*)c->batchTab.p;
+    if (!planned) {
+        const AsyncTab a = async_tab(n);
+        return AsyncPass{ { nullptr, nullptr, (u64*)(dTab + a.atDst), (u64*)(dTab + a.atCap), (u32*)(dTab + a.atFirst), (u32*)(dTab + a.atVerdict) }, (u64*)dTab, (u32*)(dTab + a.atLen), nullptr, dTab + a.atDummy, n };
+    }
+    const AsyncPlanTab t = async_plan_tab(P->maxEntries, P->maxChunks);
+    const u64 most = (u64)n * chunks_of(P->bound, P->fr.chunkBytes);
+    return AsyncPass{ { (u64*)(dTab + t.atSrc), (u64*)(dTab + t.atSize), (u64*)(dTab + t.atDst), (u64*)(dTab + t.atCap), (u32*)(dTab + t.atFirst), (u32*)(dTab + t.atVerdict) },
+                      (u64*)dTab, (u32*)(dTab + t.atLen), P->fr.frameBlocks ? (u32*)(dTab + t.atFrame) : nullptr, dTab + t.atDummy, (u32)(most < P->maxChunks ? most : P->maxChunks) };
+}
+// One staged pass of compress_entries with a plan on the device in the place of the host loop and the upload, and the caller's column in
+// the place of the read-back: kernels (and the finder's two 4-byte hipMemsetAsync) only.  One chunk per entry: the plan and the
+// placement with a lane per entry; a planned call: the two plan kernels, frames from chunk_frame_word (independent frames where the
+// framing has no frameBlocks).
 static size_t compress_batch_async_impl(ZSTD_CCtx* c, const void* const* d_srcs, const size_t* d_srcSizes, size_t n, void* const* d_dsts,
                                         const size_t* d_dstCapacities, size_t* d_dstSizes)
 {
     if (!c) return ZERR(kErrGeneric);
     if (n == 0) return 0;
     if (!d_srcs || !d_srcSizes || !d_dsts || !d_dstCapacities || !d_dstSizes) return ZERR(kErrGeneric);
+    AsyncCall call;
+    const size_t e = async_begin(c, n, call); if (isErr(e)) return e;
     const AsyncPrep* const P = c->asyncPrep;
-    if (!P || P->gen != cctx_gen(c) || n > P->maxEntries || (c->dictDirty && !cdict_shared(c)) || !c->deviceOk) return ZERR(kErrStageWrong);
-    size_t e = cctx_bind(c); if (isErr(e)) return e;
-    struct TimerOff { StageTimer& t; bool was; ~TimerOff() { t.enabled = was; } } timerOff{c->timer, c->timer.enabled};
-    c->timer.enabled = false;       // (stage events belong to calls that wait for them)
-    c->lastRegionList = nullptr; c->lastCarryGroups = 0; c->lastBatchAlone = 0; c->lastBatchPasses = 1; c->lastBatchSetChunks = 0; c->lastChunks = 0;
     hipStream_t s = c->stream;
-    if (P->planned) return compress_batch_async_planned(c, P, d_srcs, d_srcSizes, (u32)n, d_dsts, d_dstCapacities, d_dstSizes);
     const Framing& fr = P->fr;
     const LaunchState ls = launch_state(c, P->cp, fr);
-    const u32 nCh = (u32)n, cb = fr.chunkBytes;
-    const AsyncTab t = async_tab(nCh);
-    u8* const dTab = (u8*)c->batchTab.p;
-    u64* const dFrom = (u64*)dTab; u64* const dDst = (u64*)(dTab + t.atDst); u64* const dCap = (u64*)(dTab + t.atCap);
-    u32* const dLen = (u32*)(dTab + t.atLen); u32* const dFirst = (u32*)(dTab + t.atFirst); u32* const dVerdict = (u32*)(dTab + t.atVerdict);
-    const u8* stage = (const u8*)c->batchStage.p;
-    Seq* seqs = (Seq*)c->seqs.p; u8* lits = (u8*)c->lits.p; ChunkMeta* meta = (ChunkMeta*)c->meta.p;
-    HufTable* tables = (HufTable*)c->tables.p; u8* slots = (u8*)c->slots.p; u64* offsets = (u64*)c->offsets.p;
-    const u64 stagedBytes = (u64)nCh * cb;
-    launch_batch_plan(d_srcs, d_srcSizes, d_dsts, d_dstCapacities, nCh, P->bound, P->empty.len, dTab + t.atDummy, dFrom, dDst, dCap, dLen, dFirst, dVerdict, s);
-    launch_batch_stage(dFrom, dLen, (u8*)c->batchStage.p, nCh, cb, s);
-    const FrameLayout frames = layout_arith(cb, 0, stagedBytes);
-    launch_lz(pass_lz(c, ls, fr, stage, stagedBytes, nCh, nCh, frames, dLen));
-    launch_huf_build(lits, meta, tables, slots, nCh, fr.rs.rawLiterals, stage, frames, s, c->timer.hook(), ls.dct);
-    if (P->cp.checksumFlag) launch_xxh64(stage, meta, nCh, frames, s, dLen);
-    launch_seq_encode(seqs, meta, slots, nCh, ls.strategy, ls.header, 1, ls.initReps, frames, s, ls.dct);
-    launch_batch_place_async(meta, nCh, dDst, dCap, dVerdict, P->empty, offsets, d_dstSizes, s);
-    launch_huf_encode(lits, meta, tables, slots, (u8*)(uintptr_t)kAsyncBase, offsets, kAsyncSpan, nCh, stage, cb, s, ls.dct != nullptr);
-    launch_gather(stage, stagedBytes, slots, meta, offsets, (u8*)(uintptr_t)kAsyncBase, kAsyncSpan, nCh, cb, s);
+    const AsyncPass t = async_pass(c, P, (u32)n, P->planned);
+    if (P->planned) {
+        launch_batch_plan_entries(d_srcs, d_srcSizes, d_dsts, d_dstCapacities, (u32)n, P->bound, P->empty.len, fr.chunkBytes, P->maxChunks, t.et, s);
+        launch_batch_plan_chunks(t.et, (u32)n, t.nCh, fr.chunkBytes, fr.frameBlocks, t.dummy, t.dFrom, t.dLen, t.dFrame, s);
+    } else launch_batch_plan(d_srcs, d_srcSizes, d_dsts, d_dstCapacities, t.nCh, P->bound, P->empty.len, t.dummy, t.dFrom, t.et.dst, t.et.cap, t.dLen, t.et.first, t.et.verdict, s);
+    const StagedPass pass = staged_pass(t.nCh, fr, t.dFrom, t.dLen, t.dFrame, ls.dct, P->cp.checksumFlag);
+    staged_encode(c, ls, fr, pass);
+    if (P->planned) launch_batch_place_async_frames((const ChunkMeta*)c->meta.p, (u32)n, t.nCh, t.et, P->empty, (u64*)c->offsets.p, d_dstSizes, s);
+    else launch_batch_place_async((const ChunkMeta*)c->meta.p, t.nCh, t.et.dst, t.et.cap, t.et.verdict, P->empty, (u64*)c->offsets.p, d_dstSizes, s);
+    staged_write(c, pass, (u8*)(uintptr_t)kAsyncBase, kAsyncSpan);
     return async_enqueued(c, s);
 }
 extern "C" size_t ZSTDMI_CCtx_prepareBatchAsyncLimits(ZSTD_CCtx* c, const ZSTDMI_CBatchLimits* limits)
@@ -2351,9 +2356,9 @@ extern "C" size_t ZSTDMI_compressBatchAsync(ZSTD_CCtx* c, const void* const* d_s
     return guarded([&] { return compress_batch_async_impl(c, d_srcs, d_srcSizes, n, d_dsts, d_dstCapacities, d_dstSizes); });
 }
 // ---- a pack enqueued from the device (ZSTDMI_compressPackAsync, include/zstd_mi355x.h) ----
-// compress_batch_async_planned's pass behind EITHER prepare (the one-block prepare is its case of one chunk per entry in frames of their
-// own; it sized the planned table for that), with the pack's plan and placement: no per-entry destination, one decision for the whole
-// stream, and the seek table behind the frames.  n == 0: the placement's decision and the table alone.
+// compress_batch_async_impl's planned pass behind EITHER prepare (one chunk per entry in frames of their own is a case of it;
+// prepare_async_core sized the planned table for that), with the pack's plan and placement: no per-entry destination, one decision
+// for the whole stream, and the seek table behind the frames.  n == 0: the placement's decision and the table alone.
 static size_t pack_async_bound_impl(const ZSTD_CCtx* c, size_t n)
 {
     if (!c) return ZERR(kErrGeneric);
@@ -2370,44 +2375,29 @@ static size_t compress_pack_async_impl(ZSTD_CCtx* c, u8* d_dst, size_t dstCapaci
 {
     if (!c || !d_packSize || (n && (!d_srcs || !d_srcSizes))) return ZERR(kErrGeneric);
     if (!d_dst) return dstCapacity ? ZERR(kErrDstBufferNull) : ZERR(kErrDstSizeTooSmall);
+    AsyncCall call;
+    const size_t e = async_begin(c, n, call); if (isErr(e)) return e;
     const AsyncPrep* const P = c->asyncPrep;
-    if (!P || P->gen != cctx_gen(c) || n > P->maxEntries || (c->dictDirty && !cdict_shared(c)) || !c->deviceOk) return ZERR(kErrStageWrong);
-    size_t e = cctx_bind(c); if (isErr(e)) return e;
-    struct TimerOff { StageTimer& t; bool was; ~TimerOff() { t.enabled = was; } } timerOff{c->timer, c->timer.enabled};
-    c->timer.enabled = false;       // (stage events belong to calls that wait for them)
-    c->lastRegionList = nullptr; c->lastCarryGroups = 0; c->lastBatchAlone = 0; c->lastBatchPasses = n ? 1 : 0; c->lastBatchSetChunks = 0; c->lastChunks = 0;
     hipStream_t s = c->stream;
     const Framing& fr = P->fr;
     const u32 cb = fr.chunkBytes, frameBlocks = fr.frameBlocks, F = pack_frames_of(P->bound, fr), nEnt = (u32)n;
-    const u64 most = (u64)nEnt * chunks_of(P->bound, cb);
-    const u32 nCh = (u32)(most < P->maxChunks ? most : P->maxChunks);
-    const AsyncPlanTab t = async_plan_tab(P->maxEntries, P->maxChunks);
+    const AsyncPass t = async_pass(c, P, nEnt, true);
     const PackAsyncLayout pt = pack_async_tab(P->maxEntries, F);
-    u8* const dTab = (u8*)c->batchTab.p; u8* const dPack = (u8*)c->packAsync.p;
-    u64* const dFrom = (u64*)dTab; u32* const dLen = (u32*)(dTab + t.atLen); u32* const dFrame = frameBlocks ? (u32*)(dTab + t.atFrame) : nullptr;
-    const AsyncEntryTab et = { (u64*)(dTab + t.atSrc), (u64*)(dTab + t.atSize), (u64*)(dTab + t.atDst), (u64*)(dTab + t.atCap), (u32*)(dTab + t.atFirst), (u32*)(dTab + t.atVerdict) };
+    u8* const dPack = (u8*)c->packAsync.p;
     const PackAsyncTab pk = { (u64*)dPack, (u32*)(dPack + pt.atRow), (u32*)(dPack + pt.atRows), (u64*)(dPack + pt.atState) };
     ChunkMeta* meta = (ChunkMeta*)c->meta.p; u64* offsets = (u64*)c->offsets.p;
-    if (!nCh) {
-        launch_pack_place_async(meta, 0, 0, et, dLen, frameBlocks, P->empty, d_dst, dstCapacity, pk, offsets, d_packSize, d_entryEnds, s);
+    if (!t.nCh) {
+        launch_pack_place_async(meta, 0, 0, t.et, t.dLen, frameBlocks, P->empty, d_dst, dstCapacity, pk, offsets, d_packSize, d_entryEnds, s);
         launch_pack_table_async(pk, 0, d_dst, s);
         return async_enqueued(c, s);
     }
     const LaunchState ls = launch_state(c, P->cp, fr);
-    const u8* stage = (const u8*)c->batchStage.p;
-    Seq* seqs = (Seq*)c->seqs.p; u8* lits = (u8*)c->lits.p; HufTable* tables = (HufTable*)c->tables.p; u8* slots = (u8*)c->slots.p;
-    const u64 stagedBytes = (u64)nCh * cb;
-    launch_pack_plan_entries(d_srcs, d_srcSizes, nEnt, P->bound, cb, P->maxChunks, et, s);
-    launch_batch_plan_chunks(et, nEnt, nCh, cb, frameBlocks, dTab + t.atDummy, dFrom, dLen, dFrame, s);
-    launch_batch_stage(dFrom, dLen, (u8*)c->batchStage.p, nCh, cb, s);
-    const FrameLayout frames = dFrame ? layout_table(cb, frameBlocks, dFrame) : layout_arith(cb, 0, stagedBytes);
-    launch_lz(pass_lz(c, ls, fr, stage, stagedBytes, nCh, nCh, frames, dLen));
-    launch_huf_build(lits, meta, tables, slots, nCh, fr.rs.rawLiterals, stage, frames, s, c->timer.hook(), ls.dct);
-    if (P->cp.checksumFlag) launch_xxh64(stage, meta, nCh, frames, s, dLen);
-    launch_seq_encode(seqs, meta, slots, nCh, ls.strategy, ls.header, 1, ls.initReps, frames, s, ls.dct);
-    launch_pack_place_async(meta, nEnt, nCh, et, dLen, frameBlocks, P->empty, d_dst, dstCapacity, pk, offsets, d_packSize, d_entryEnds, s);
-    launch_huf_encode(lits, meta, tables, slots, (u8*)(uintptr_t)kAsyncBase, offsets, kAsyncSpan, nCh, stage, cb, s, ls.dct != nullptr);
-    launch_gather(stage, stagedBytes, slots, meta, offsets, (u8*)(uintptr_t)kAsyncBase, kAsyncSpan, nCh, cb, s);
+    launch_pack_plan_entries(d_srcs, d_srcSizes, nEnt, P->bound, cb, P->maxChunks, t.et, s);
+    launch_batch_plan_chunks(t.et, nEnt, t.nCh, cb, frameBlocks, t.dummy, t.dFrom, t.dLen, t.dFrame, s);
+    const StagedPass pass = staged_pass(t.nCh, fr, t.dFrom, t.dLen, t.dFrame, ls.dct, P->cp.checksumFlag);
+    staged_encode(c, ls, fr, pass);
+    launch_pack_place_async(meta, nEnt, t.nCh, t.et, t.dLen, frameBlocks, P->empty, d_dst, dstCapacity, pk, offsets, d_packSize, d_entryEnds, s);
+    staged_write(c, pass, (u8*)(uintptr_t)kAsyncBase, kAsyncSpan);
     launch_pack_table_async(pk, (u64)nEnt * F, d_dst, s);
     return async_enqueued(c, s);
 }
@@ -2529,7 +2519,7 @@ static size_t compress_pack_impl(ZSTD_CCtx* c, u8* d_dst, size_t dstCapacity, co
             const Framing fr = S ? resolve_framing(c, cp, S) : Framing{};
             Kind k = { S && entry_batched(c, cp, S, fr, passLimit, dct != nullptr, false), 0, 0 };
             if (k.batched) {
-                k.chunks = (u32)((S + fr.chunkBytes - 1) / fr.chunkBytes);
+                k.chunks = (u32)chunks_of(S, fr.chunkBytes);
                 k.frames = fr.frameBlocks ? (k.chunks + fr.frameBlocks - 1) / fr.frameBlocks : k.chunks;
             } else {
                 e = check_ldm_dict(c, cp, S); if (isErr(e)) return e;
