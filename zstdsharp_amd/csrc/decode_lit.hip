@@ -1015,17 +1015,17 @@ static void launch_decode_literals_dev(const u8* src, u8* out, u8* scratch, cons
 }
 // mode 0: by the caller's limit for the blocks — the grid's size, the only count the host has
 void launch_decode_literals_d(const u8* src, u8* out, u8* scratch, const FrameDesc* frames, const BlockDesc* blocks, u32 capBlocks, u32* status,
-                              u8* slowFlags, u32 mode, const u8* dictFull, const DictInfo* di, hipStream_t stream, const DictSlot* slots)
+                              u8* slowFlags, u32 mode, const DecodeDict& dd, hipStream_t stream)
 {
     if (mode == 0) mode = literal_decoder_for(capBlocks);
-    if (slots) launch_decode_literals_dev<true>(src, out, scratch, frames, blocks, capBlocks, status, slowFlags, mode, nullptr, nullptr, stream, slots);
-    else launch_decode_literals_dev<false>(src, out, scratch, frames, blocks, capBlocks, status, slowFlags, mode, dictFull, di, stream, nullptr);
+    if (dd.slots) launch_decode_literals_dev<true>(src, out, scratch, frames, blocks, capBlocks, status, slowFlags, mode, nullptr, nullptr, stream, dd.slots);
+    else launch_decode_literals_dev<false>(src, out, scratch, frames, blocks, capBlocks, status, slowFlags, mode, dd.dictFull, dd.dinfo, stream, nullptr);
 }
 
 void launch_decode_literals(const u8* src, u8* out, u8* scratch, const FrameDesc* frames, const BlockDesc* blocks, u32 nBlocks, u32* status,
-                            u8* slowFlags, u32 mode, const u8* dictFull, const DictInfo* di, hipStream_t stream, StageHook hook,
-                            const DictSlot* slots)
+                            u8* slowFlags, u32 mode, const DecodeDict& dd, hipStream_t stream, StageHook hook)
 {
+    const DictSlot* const slots = dd.slots; const u8* const dictFull = dd.dictFull; const DictInfo* const di = dd.dinfo;
     if (mode == 0) mode = literal_decoder_for(nBlocks);
     if (mode == 2) {
         static bool attrSet[64] = {};               // per device

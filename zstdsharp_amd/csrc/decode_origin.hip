@@ -236,14 +236,14 @@ static dim3 origin_grid(u64 maxFrameBytes, u32 listCap)
 }
 // select + fill + init (queued behind block_offsets; the literals are not needed yet)
 void launch_origin_init(const FrameDesc* frames, const BlockDesc* blocks, const u32* list, u32 listCap, u64 maxFrameBytes, const SeqRec* recs, u32* status,
-                        u32* origin, u32 dictSize, hipStream_t stream, const DictSlot* slots)
+                        u32* origin, const DecodeDict& dd, hipStream_t stream)
 {
     const dim3 grid = origin_grid(maxFrameBytes, listCap), tb(256);
     u64 bw = (maxFrameBytes / (128u << 10) + 4) / 4;             // one wave per block of 128 KiB
     if (bw > 4096) bw = 4096;
     hipLaunchKernelGGL(origin_fill_kernel, grid, tb, 0, stream, frames, list, (const u32*)status, origin);
-    if (slots) hipLaunchKernelGGL(origin_init_set_kernel, dim3((u32)bw, listCap), tb, 0, stream, frames, blocks, list, recs, status, origin, slots);
-    else hipLaunchKernelGGL(origin_init_kernel, dim3((u32)bw, listCap), tb, 0, stream, frames, blocks, list, recs, status, origin, dictSize);
+    if (dd.slots) hipLaunchKernelGGL(origin_init_set_kernel, dim3((u32)bw, listCap), tb, 0, stream, frames, blocks, list, recs, status, origin, dd.slots);
+    else hipLaunchKernelGGL(origin_init_kernel, dim3((u32)bw, listCap), tb, 0, stream, frames, blocks, list, recs, status, origin, dd.dictContent ? dd.dictContentSize : 0u);
 }
 // rounds [r0, r1) of the pointer jumping; done: one word per 1024 origins, any contents before round 0
 void launch_origin_jump(const FrameDesc* frames, const u32* list, u32 listCap, u64 maxFrameBytes, u32* status, u32* origin, u32* done, u32 r0, u32 r1, hipStream_t stream)
@@ -251,11 +251,10 @@ void launch_origin_jump(const FrameDesc* frames, const u32* list, u32 listCap, u
     const dim3 grid = origin_grid(maxFrameBytes, listCap), tb(256);
     for (u32 r = r0; r < r1 && r < kOriginRounds; ++r) hipLaunchKernelGGL(origin_jump_kernel, grid, tb, 0, stream, frames, list, status, origin, done, r);
 }
-void launch_origin_gather(const FrameDesc* frames, const u32* list, u32 listCap, u64 maxFrameBytes, const u32* status, const u32* origin, u8* out, const u8* dict, hipStream_t stream,
-                          const DictSlot* slots)
+void launch_origin_gather(const FrameDesc* frames, const u32* list, u32 listCap, u64 maxFrameBytes, const u32* status, const u32* origin, u8* out, const DecodeDict& dd, hipStream_t stream)
 {
-    if (slots) hipLaunchKernelGGL(origin_gather_set_kernel, origin_grid(maxFrameBytes, listCap), dim3(256), 0, stream, frames, list, status, origin, out, slots);
-    else hipLaunchKernelGGL(origin_gather_kernel, origin_grid(maxFrameBytes, listCap), dim3(256), 0, stream, frames, list, status, origin, out, dict);
+    if (dd.slots) hipLaunchKernelGGL(origin_gather_set_kernel, origin_grid(maxFrameBytes, listCap), dim3(256), 0, stream, frames, list, status, origin, out, dd.slots);
+    else hipLaunchKernelGGL(origin_gather_kernel, origin_grid(maxFrameBytes, listCap), dim3(256), 0, stream, frames, list, status, origin, out, dd.dictContent);
 }
 
 } // namespace zmi

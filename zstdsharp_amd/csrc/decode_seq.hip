@@ -480,22 +480,20 @@ __global__ __launch_bounds__(256) void seq_decode_set_d_kernel(const u8* __restr
 {
     seq_decode_body<true, true>(src, frames, blocks, status[kStBlocks], recs, status, nullptr, nullptr, nullptr, slots);
 }
-void launch_seq_decode_d(const u8* src, const FrameDesc* frames, BlockDesc* blocks, u32 capBlocks, SeqRec* recs, u32* status,
-                         const u8* dictFull, const DictInfo* di, const u32* dictTabs, hipStream_t stream, const DictSlot* slots)
+void launch_seq_decode_d(const u8* src, const FrameDesc* frames, BlockDesc* blocks, u32 capBlocks, SeqRec* recs, u32* status, const DecodeDict& dd, hipStream_t stream)
 {
     const dim3 grid((capBlocks + kPack - 1) / kPack);
-    if (slots) hipLaunchKernelGGL(seq_decode_set_d_kernel, grid, dim3(256), 0, stream, src, frames, blocks, recs, status, slots);
-    else if (dictTabs) hipLaunchKernelGGL(seq_decode_ready_d_kernel, grid, dim3(256), 0, stream, src, frames, blocks, recs, status, dictFull, di, dictTabs);
-    else          hipLaunchKernelGGL(seq_decode_d_kernel, grid, dim3(256), 0, stream, src, frames, blocks, recs, status, dictFull, di);
+    if (dd.slots) hipLaunchKernelGGL(seq_decode_set_d_kernel, grid, dim3(256), 0, stream, src, frames, blocks, recs, status, dd.slots);
+    else if (dd.seqTabs) hipLaunchKernelGGL(seq_decode_ready_d_kernel, grid, dim3(256), 0, stream, src, frames, blocks, recs, status, dd.dictFull, dd.dinfo, dd.seqTabs);
+    else          hipLaunchKernelGGL(seq_decode_d_kernel, grid, dim3(256), 0, stream, src, frames, blocks, recs, status, dd.dictFull, dd.dinfo);
 }
 
-void launch_seq_decode(const u8* src, const FrameDesc* frames, BlockDesc* blocks, u32 nBlocks, SeqRec* recs, u32* status,
-                       const u8* dictFull, const DictInfo* di, const u32* dictTabs, hipStream_t stream, const DictSlot* slots)
+void launch_seq_decode(const u8* src, const FrameDesc* frames, BlockDesc* blocks, u32 nBlocks, SeqRec* recs, u32* status, const DecodeDict& dd, hipStream_t stream)
 {
     const dim3 grid((nBlocks + kPack - 1) / kPack);
-    if (slots) hipLaunchKernelGGL(seq_decode_set_kernel, grid, dim3(256), 0, stream, src, frames, blocks, nBlocks, recs, status, slots);
-    else if (dictTabs) hipLaunchKernelGGL(seq_decode_ready_kernel, grid, dim3(256), 0, stream, src, frames, blocks, nBlocks, recs, status, dictFull, di, dictTabs);
-    else          hipLaunchKernelGGL(seq_decode_kernel, grid, dim3(256), 0, stream, src, frames, blocks, nBlocks, recs, status, dictFull, di);
+    if (dd.slots) hipLaunchKernelGGL(seq_decode_set_kernel, grid, dim3(256), 0, stream, src, frames, blocks, nBlocks, recs, status, dd.slots);
+    else if (dd.seqTabs) hipLaunchKernelGGL(seq_decode_ready_kernel, grid, dim3(256), 0, stream, src, frames, blocks, nBlocks, recs, status, dd.dictFull, dd.dinfo, dd.seqTabs);
+    else          hipLaunchKernelGGL(seq_decode_kernel, grid, dim3(256), 0, stream, src, frames, blocks, nBlocks, recs, status, dd.dictFull, dd.dinfo);
 }
 
 // The dictionary's LL, OF and ML decoding tables, once (ZSTD_createDDict): wave t runs set_seq_table over the dictionary's description of
@@ -963,21 +961,23 @@ __global__ __launch_bounds__(64 * W) void exec_matches_wide_kernel(const u8* __r
 // 16 waves 2.4; 1024 frames: 6.8 / 5.5 / 4.3 / 5.7 / 7.3 at 1 / 2 / 4 / 8 / 16; 2048 frames: 8.3 / 6.5 / 8.0 at 1 / 2 / 4; 4096
 // frames: 9.8 / 12.3 at 1 / 2 — i.e. as many waves as keep frames x waves at about 4096 (the caller's rule, decompress_device)
 void launch_exec_matches(const u8* src, u8* out, const FrameDesc* frames, const BlockDesc* blocks, u32 nFrames, const SeqRec* recs, u32* status,
-                         const u8* dict, u32 dictSize, hipStream_t stream, int wide, const DictSlot* slots)
+                         const DecodeDict& dd, hipStream_t stream, int wide)
 {
-    if (slots) {                // the set instances: the slot table rides in the dictionary pointer's place
-        const u8* const tab = reinterpret_cast<const u8*>(slots);
+    // the set instances: the slot table rides in the dictionary pointer's place.  The others: a raw-content dictionary (or a formatted one's
+    // content) = history in front of EVERY frame (ZSTD_refDictContent, U/ZstdDecompress.cs:1758-1771); may be null
+    const u8* const dict = dd.slots ? reinterpret_cast<const u8*>(dd.slots) : dd.dictContent;
+    const u32 ds = !dd.slots && dd.dictContent ? dd.dictContentSize : 0u;
+    if (dd.slots) {
         switch (wide) {
-        case 16: hipLaunchKernelGGL((exec_matches_wide_kernel<16, true>), dim3(nFrames), dim3(1024), 0, stream, src, out, frames, blocks, nFrames, recs, status, tab, 0u); return;
-        case 8:  hipLaunchKernelGGL((exec_matches_wide_kernel<8, true>),  dim3(nFrames), dim3(512),  0, stream, src, out, frames, blocks, nFrames, recs, status, tab, 0u); return;
-        case 4:  hipLaunchKernelGGL((exec_matches_wide_kernel<4, true>),  dim3(nFrames), dim3(256),  0, stream, src, out, frames, blocks, nFrames, recs, status, tab, 0u); return;
-        case 2:  hipLaunchKernelGGL((exec_matches_wide_kernel<2, true>),  dim3(nFrames), dim3(128),  0, stream, src, out, frames, blocks, nFrames, recs, status, tab, 0u); return;
+        case 16: hipLaunchKernelGGL((exec_matches_wide_kernel<16, true>), dim3(nFrames), dim3(1024), 0, stream, src, out, frames, blocks, nFrames, recs, status, dict, ds); return;
+        case 8:  hipLaunchKernelGGL((exec_matches_wide_kernel<8, true>),  dim3(nFrames), dim3(512),  0, stream, src, out, frames, blocks, nFrames, recs, status, dict, ds); return;
+        case 4:  hipLaunchKernelGGL((exec_matches_wide_kernel<4, true>),  dim3(nFrames), dim3(256),  0, stream, src, out, frames, blocks, nFrames, recs, status, dict, ds); return;
+        case 2:  hipLaunchKernelGGL((exec_matches_wide_kernel<2, true>),  dim3(nFrames), dim3(128),  0, stream, src, out, frames, blocks, nFrames, recs, status, dict, ds); return;
         default: break;
         }
-        hipLaunchKernelGGL(exec_matches_kernel<true>, dim3(nFrames), dim3(64), 0, stream, src, out, frames, blocks, nFrames, recs, status, tab, 0u);
+        hipLaunchKernelGGL(exec_matches_kernel<true>, dim3(nFrames), dim3(64), 0, stream, src, out, frames, blocks, nFrames, recs, status, dict, ds);
         return;
     }
-    const u32 ds = dict ? dictSize : 0u;
     switch (wide) {
     case 16: hipLaunchKernelGGL(exec_matches_wide_kernel<16>, dim3(nFrames), dim3(1024), 0, stream, src, out, frames, blocks, nFrames, recs, status, dict, ds); return;
     case 8:  hipLaunchKernelGGL(exec_matches_wide_kernel<8>,  dim3(nFrames), dim3(512),  0, stream, src, out, frames, blocks, nFrames, recs, status, dict, ds); return;
@@ -985,9 +985,7 @@ void launch_exec_matches(const u8* src, u8* out, const FrameDesc* frames, const 
     case 2:  hipLaunchKernelGGL(exec_matches_wide_kernel<2>,  dim3(nFrames), dim3(128),  0, stream, src, out, frames, blocks, nFrames, recs, status, dict, ds); return;
     default: break;
     }
-    // dict: a raw-content dictionary (or a formatted one's content) = history in front of EVERY frame (ZSTD_refDictContent,
-    // U/ZstdDecompress.cs:1758-1771); may be null
-    hipLaunchKernelGGL(exec_matches_kernel<false>, dim3(nFrames), dim3(64), 0, stream, src, out, frames, blocks, nFrames, recs, status, dict, dict ? dictSize : 0u);
+    hipLaunchKernelGGL(exec_matches_kernel<false>, dim3(nFrames), dim3(64), 0, stream, src, out, frames, blocks, nFrames, recs, status, dict, ds);
 }
 // the same instances with the number of frames from the status words, over a grid of the caller's limit (ZSTDMI_decompressBatchAsync)
 template <bool kSet>
@@ -1004,10 +1002,10 @@ static void launch_exec_matches_dev(const u8* src, u8* out, const FrameDesc* fra
     hipLaunchKernelGGL((exec_matches_kernel<kSet, true>), dim3(capFrames), dim3(64), 0, stream, src, out, frames, blocks, 0u, recs, status, dict, ds);
 }
 void launch_exec_matches_d(const u8* src, u8* out, const FrameDesc* frames, const BlockDesc* blocks, u32 capFrames, const SeqRec* recs, u32* status,
-                           const u8* dict, u32 dictSize, hipStream_t stream, int wide, const DictSlot* slots)
+                           const DecodeDict& dd, hipStream_t stream, int wide)
 {
-    if (slots) launch_exec_matches_dev<true>(src, out, frames, blocks, capFrames, recs, status, reinterpret_cast<const u8*>(slots), 0u, stream, wide);
-    else launch_exec_matches_dev<false>(src, out, frames, blocks, capFrames, recs, status, dict, dict ? dictSize : 0u, stream, wide);
+    if (dd.slots) launch_exec_matches_dev<true>(src, out, frames, blocks, capFrames, recs, status, reinterpret_cast<const u8*>(dd.slots), 0u, stream, wide);
+    else launch_exec_matches_dev<false>(src, out, frames, blocks, capFrames, recs, status, dd.dictContent, dd.dictContent ? dd.dictContentSize : 0u, stream, wide);
 }
 
 } // namespace zmi

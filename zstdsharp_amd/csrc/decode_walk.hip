@@ -597,13 +597,15 @@ __global__ __launch_bounds__(64) void batch_fold_kernel(BatchEntryOut* __restric
     if (key != ~0ull) out[e].result = (u64)0 - (key & 0xFFFFull);
 }
 
-void launch_batch_walk_count(const u8* src, const BatchEntryIn* in, BatchEntryOut* out, u32 nEntries, u32 dictID, u64 aloneAbove, u32* status, hipStream_t stream,
-                             const DictSlot* slots, u32 nSet, bool open, bool caps)
+void launch_batch_walk_count(const u8* src, const BatchEntryIn* in, BatchEntryOut* out, u32 nEntries, const DecodeDict& dd, u64 aloneAbove, u32* status, hipStream_t stream,
+                             bool open, bool caps)
 {
-    if (open && slots) hipLaunchKernelGGL(batch_walk_count_open_kernel<true>, dim3((nEntries + 63) / 64), dim3(64), 0, stream, src, in, out, nEntries, 0u, aloneAbove, slots, nSet, status);
-    else if (open) hipLaunchKernelGGL(batch_walk_count_open_kernel<false>, dim3((nEntries + 63) / 64), dim3(64), 0, stream, src, in, out, nEntries, dictID, aloneAbove, (const DictSlot*)nullptr, 0u, status);
-    else if (slots) hipLaunchKernelGGL(batch_walk_count_set_kernel, dim3((nEntries + 63) / 64), dim3(64), 0, stream, src, in, out, nEntries, aloneAbove, slots, nSet, status);
-    else hipLaunchKernelGGL(batch_walk_count_kernel, dim3((nEntries + 63) / 64), dim3(64), 0, stream, src, in, out, nEntries, dictID, aloneAbove);
+    const DictSlot* const slots = dd.slots; const u32 nSet = dd.nSet, dictID = slots ? 0u : dd.dictID;      // (a set instance finds each frame's dictionary by its dictID)
+    const dim3 grid((nEntries + 63) / 64);
+    if (open && slots) hipLaunchKernelGGL(batch_walk_count_open_kernel<true>, grid, dim3(64), 0, stream, src, in, out, nEntries, dictID, aloneAbove, slots, nSet, status);
+    else if (open) hipLaunchKernelGGL(batch_walk_count_open_kernel<false>, grid, dim3(64), 0, stream, src, in, out, nEntries, dictID, aloneAbove, slots, nSet, status);
+    else if (slots) hipLaunchKernelGGL(batch_walk_count_set_kernel, grid, dim3(64), 0, stream, src, in, out, nEntries, aloneAbove, slots, nSet, status);
+    else hipLaunchKernelGGL(batch_walk_count_kernel, grid, dim3(64), 0, stream, src, in, out, nEntries, dictID, aloneAbove);
     if (caps) hipLaunchKernelGGL(batch_scan_kernel<true>, dim3(1), dim3(256), 0, stream, out, nEntries, status);
     else hipLaunchKernelGGL(batch_scan_kernel<>, dim3(1), dim3(256), 0, stream, out, nEntries, status);
 }
@@ -677,12 +679,14 @@ void launch_batch_finish_d(const BatchEntryOut* out, const u32* verdict, u32 n, 
     hipLaunchKernelGGL(batch_finish_d_kernel, dim3((n + 63) / 64), dim3(64), 0, stream, out, verdict, n, dstSizes);
 }
 void launch_batch_walk_emit(const u8* src, const BatchEntryIn* in, const BatchEntryOut* out, u32 nEntries, FrameDesc* frames, BlockDesc* blocks, hipStream_t stream,
-                            const DictSlot* slots, u32 nSet, u64* rooms)
+                            const DecodeDict& dd, u64* rooms)
 {
-    if (rooms && slots) hipLaunchKernelGGL(batch_walk_emit_open_kernel<true>, dim3((nEntries + 63) / 64), dim3(64), 0, stream, src, in, out, nEntries, frames, blocks, slots, nSet, rooms);
-    else if (rooms) hipLaunchKernelGGL(batch_walk_emit_open_kernel<false>, dim3((nEntries + 63) / 64), dim3(64), 0, stream, src, in, out, nEntries, frames, blocks, (const DictSlot*)nullptr, 0u, rooms);
-    else if (slots) hipLaunchKernelGGL(batch_walk_emit_set_kernel, dim3((nEntries + 63) / 64), dim3(64), 0, stream, src, in, out, nEntries, frames, blocks, slots, nSet);
-    else hipLaunchKernelGGL(batch_walk_emit_kernel, dim3((nEntries + 63) / 64), dim3(64), 0, stream, src, in, out, nEntries, frames, blocks);
+    const DictSlot* const slots = dd.slots; const u32 nSet = dd.nSet;
+    const dim3 grid((nEntries + 63) / 64);
+    if (rooms && slots) hipLaunchKernelGGL(batch_walk_emit_open_kernel<true>, grid, dim3(64), 0, stream, src, in, out, nEntries, frames, blocks, slots, nSet, rooms);
+    else if (rooms) hipLaunchKernelGGL(batch_walk_emit_open_kernel<false>, grid, dim3(64), 0, stream, src, in, out, nEntries, frames, blocks, slots, nSet, rooms);
+    else if (slots) hipLaunchKernelGGL(batch_walk_emit_set_kernel, grid, dim3(64), 0, stream, src, in, out, nEntries, frames, blocks, slots, nSet);
+    else hipLaunchKernelGGL(batch_walk_emit_kernel, grid, dim3(64), 0, stream, src, in, out, nEntries, frames, blocks);
 }
 void launch_batch_fold(BatchEntryOut* out, u32 nEntries, const u64* keys, hipStream_t stream)
 {
@@ -863,11 +867,10 @@ void launch_frame_walk_emit(const u8* src, u64 srcSize, FrameDesc* frames, Block
     const WalkWs w = walk_ws(walkWs, srcSize);
     hipLaunchKernelGGL(walk_emit_kernel, dim3((w.nSeg + 255) / 256), dim3(256), 0, stream, src, srcSize, w.segs, w.nSeg, w.frameBase, w.blockBase, w.dstBase, frames, blocks);
 }
-void launch_frame_walk_serial(const u8* src, u64 srcSize, FrameDesc* frames, BlockDesc* blocks, u32 maxFrames, u32* status, u32 dictID, u32 emit,
-                              hipStream_t stream, const DictSlot* slots, u32 nSet)
+void launch_frame_walk_serial(const u8* src, u64 srcSize, FrameDesc* frames, BlockDesc* blocks, u32 maxFrames, u32* status, const DecodeDict& dd, u32 emit, hipStream_t stream)
 {
-    if (slots) hipLaunchKernelGGL(frame_walk_serial_set_kernel, dim3(1), dim3(64), 0, stream, src, srcSize, frames, blocks, maxFrames, status, emit, slots, nSet);
-    else hipLaunchKernelGGL(frame_walk_serial_kernel, dim3(1), dim3(64), 0, stream, src, srcSize, frames, blocks, maxFrames, status, dictID, emit);
+    if (dd.slots) hipLaunchKernelGGL(frame_walk_serial_set_kernel, dim3(1), dim3(64), 0, stream, src, srcSize, frames, blocks, maxFrames, status, emit, dd.slots, dd.nSet);
+    else hipLaunchKernelGGL(frame_walk_serial_kernel, dim3(1), dim3(64), 0, stream, src, srcSize, frames, blocks, maxFrames, status, dd.dictID, emit);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1182,23 +1185,25 @@ __global__ __launch_bounds__(1024) void seq_scan_kernel(BlockDesc* __restrict__ 
     if (threadIdx.x == 0) { status[kStSeqLo] = (u32)total; status[kStSeqHi] = (u32)(total >> 32); }
 }
 
-void launch_block_prepass(const u8* src, FrameDesc* frames, BlockDesc* blocks, u32 nFrames, u32 nBlocks, u32 haveDict, u32 earlyLiterals, u32* status, hipStream_t stream,
-                          u32 phantoms, const DictSlot* slots, bool open)
+void launch_block_prepass(const u8* src, FrameDesc* frames, BlockDesc* blocks, u32 nFrames, u32 nBlocks, const DecodeDict& dd, u32 earlyLiterals, u32* status, hipStream_t stream,
+                          u32 phantoms, bool open)
 {
+    // (a set instance reads whether its frame has a formatted dictionary from the frame's slot)
+    const DictSlot* const slots = dd.slots; const u32 haveDict = !slots && dd.fmt ? 1u : 0u;
     hipLaunchKernelGGL(block_parse_kernel<>, dim3((nBlocks + 255) / 256), dim3(256), 0, stream, src, blocks, nBlocks, status);
     if (open) {                 // (a batch: never a fragment of a segmented stream)
         if (slots) {
-            hipLaunchKernelGGL((block_link_small_kernel<true, true>), dim3((nFrames + 63) / 64), dim3(64), 0, stream, frames, blocks, nFrames, 0u, earlyLiterals, status, slots);
-            if (nBlocks > nFrames) hipLaunchKernelGGL(block_link_open_kernel<true>, dim3(nFrames), dim3(64), 0, stream, frames, blocks, nFrames, 0u, earlyLiterals, status, slots);
+            hipLaunchKernelGGL((block_link_small_kernel<true, true>), dim3((nFrames + 63) / 64), dim3(64), 0, stream, frames, blocks, nFrames, haveDict, earlyLiterals, status, slots);
+            if (nBlocks > nFrames) hipLaunchKernelGGL(block_link_open_kernel<true>, dim3(nFrames), dim3(64), 0, stream, frames, blocks, nFrames, haveDict, earlyLiterals, status, slots);
         } else {
-            hipLaunchKernelGGL((block_link_small_kernel<false, true>), dim3((nFrames + 63) / 64), dim3(64), 0, stream, frames, blocks, nFrames, haveDict, earlyLiterals, status, (const DictSlot*)nullptr);
-            if (nBlocks > nFrames) hipLaunchKernelGGL(block_link_open_kernel<false>, dim3(nFrames), dim3(64), 0, stream, frames, blocks, nFrames, haveDict, earlyLiterals, status, (const DictSlot*)nullptr);
+            hipLaunchKernelGGL((block_link_small_kernel<false, true>), dim3((nFrames + 63) / 64), dim3(64), 0, stream, frames, blocks, nFrames, haveDict, earlyLiterals, status, slots);
+            if (nBlocks > nFrames) hipLaunchKernelGGL(block_link_open_kernel<false>, dim3(nFrames), dim3(64), 0, stream, frames, blocks, nFrames, haveDict, earlyLiterals, status, slots);
         }
         hipLaunchKernelGGL(seq_scan_kernel<>, dim3(1), dim3(1024), 0, stream, blocks, nBlocks, status);
         return;
     }
     if (slots) {                // (never a fragment of a segmented stream: the host refuses that combination)
-        hipLaunchKernelGGL(block_link_small_kernel<true>, dim3((nFrames + 63) / 64), dim3(64), 0, stream, frames, blocks, nFrames, 0u, earlyLiterals, status, slots);
+        hipLaunchKernelGGL(block_link_small_kernel<true>, dim3((nFrames + 63) / 64), dim3(64), 0, stream, frames, blocks, nFrames, haveDict, earlyLiterals, status, slots);
         if (nBlocks > nFrames) hipLaunchKernelGGL(block_link_set_kernel, dim3(nFrames), dim3(64), 0, stream, frames, blocks, nFrames, earlyLiterals, status, slots);
         hipLaunchKernelGGL(seq_scan_kernel<>, dim3(1), dim3(1024), 0, stream, blocks, nBlocks, status);
         return;
@@ -1208,22 +1213,23 @@ void launch_block_prepass(const u8* src, FrameDesc* frames, BlockDesc* blocks, u
         hipLaunchKernelGGL(seq_scan_kernel<>, dim3(1), dim3(1024), 0, stream, blocks, nBlocks, status);
         return;
     }
-    hipLaunchKernelGGL(block_link_small_kernel<false>, dim3((nFrames + 63) / 64), dim3(64), 0, stream, frames, blocks, nFrames, haveDict, earlyLiterals, status, (const DictSlot*)nullptr);
+    hipLaunchKernelGGL(block_link_small_kernel<false>, dim3((nFrames + 63) / 64), dim3(64), 0, stream, frames, blocks, nFrames, haveDict, earlyLiterals, status, slots);
     if (nBlocks > nFrames) hipLaunchKernelGGL(block_link_kernel, dim3(nFrames), dim3(64), 0, stream, frames, blocks, nFrames, haveDict, earlyLiterals, status);      // (some frame has several blocks)
     hipLaunchKernelGGL(seq_scan_kernel<>, dim3(1), dim3(1024), 0, stream, blocks, nBlocks, status);
 }
 
 // the pre-pass of a batch enqueued from the device: the open instances, the counts from the status words, grids over the caller's limits
 // (block_link_open always runs: whether some frame has more than kLinkSmall blocks is not known here)
-void launch_block_prepass_d(const u8* src, FrameDesc* frames, BlockDesc* blocks, u32 capFrames, u32 capBlocks, u32 haveDict, u32* status, hipStream_t stream, const DictSlot* slots)
+void launch_block_prepass_d(const u8* src, FrameDesc* frames, BlockDesc* blocks, u32 capFrames, u32 capBlocks, const DecodeDict& dd, u32* status, hipStream_t stream)
 {
+    const DictSlot* const slots = dd.slots; const u32 haveDict = !slots && dd.fmt ? 1u : 0u;        // (as launch_block_prepass)
     hipLaunchKernelGGL(block_parse_kernel<true>, dim3((capBlocks + 255) / 256), dim3(256), 0, stream, src, blocks, 0u, status);
     if (slots) {
-        hipLaunchKernelGGL((block_link_small_kernel<true, true, true>), dim3((capFrames + 63) / 64), dim3(64), 0, stream, frames, blocks, 0u, 0u, 0u, status, slots);
-        hipLaunchKernelGGL(block_link_open_d_kernel<true>, dim3(capFrames), dim3(64), 0, stream, frames, blocks, 0u, 0u, status, slots);
+        hipLaunchKernelGGL((block_link_small_kernel<true, true, true>), dim3((capFrames + 63) / 64), dim3(64), 0, stream, frames, blocks, 0u, haveDict, 0u, status, slots);
+        hipLaunchKernelGGL(block_link_open_d_kernel<true>, dim3(capFrames), dim3(64), 0, stream, frames, blocks, haveDict, 0u, status, slots);
     } else {
-        hipLaunchKernelGGL((block_link_small_kernel<false, true, true>), dim3((capFrames + 63) / 64), dim3(64), 0, stream, frames, blocks, 0u, haveDict, 0u, status, (const DictSlot*)nullptr);
-        hipLaunchKernelGGL(block_link_open_d_kernel<false>, dim3(capFrames), dim3(64), 0, stream, frames, blocks, haveDict, 0u, status, (const DictSlot*)nullptr);
+        hipLaunchKernelGGL((block_link_small_kernel<false, true, true>), dim3((capFrames + 63) / 64), dim3(64), 0, stream, frames, blocks, 0u, haveDict, 0u, status, slots);
+        hipLaunchKernelGGL(block_link_open_d_kernel<false>, dim3(capFrames), dim3(64), 0, stream, frames, blocks, haveDict, 0u, status, slots);
     }
     hipLaunchKernelGGL(seq_scan_kernel<true>, dim3(1), dim3(1024), 0, stream, blocks, 0u, status);
 }
@@ -1333,20 +1339,22 @@ __global__ __launch_bounds__(1024) void frame_rescan_kernel(FrameDesc* __restric
     }
 }
 
-void launch_block_offsets(FrameDesc* frames, BlockDesc* blocks, u32 nFrames, const DictInfo* di, u32 rescan, u64 dstCapacity, u32* status, hipStream_t stream,
-                          const DictSlot* slots, bool open)
+void launch_block_offsets(FrameDesc* frames, BlockDesc* blocks, u32 nFrames, const DecodeDict& dd, const DictInfo* reps, u32 rescan, u64 dstCapacity, u32* status, hipStream_t stream,
+                          bool open)
 {
-    if (open && slots) hipLaunchKernelGGL(block_offsets_open_kernel<true>, dim3(nFrames), dim3(64), 0, stream, frames, blocks, nFrames, (const DictInfo*)nullptr, status, slots);
-    else if (open) hipLaunchKernelGGL(block_offsets_open_kernel<false>, dim3(nFrames), dim3(64), 0, stream, frames, blocks, nFrames, di, status, (const DictSlot*)nullptr);
+    const DictSlot* const slots = dd.slots; const DictInfo* const di = slots ? nullptr : reps;      // (a set instance starts from its frame's slot)
+    if (open && slots) hipLaunchKernelGGL(block_offsets_open_kernel<true>, dim3(nFrames), dim3(64), 0, stream, frames, blocks, nFrames, di, status, slots);
+    else if (open) hipLaunchKernelGGL(block_offsets_open_kernel<false>, dim3(nFrames), dim3(64), 0, stream, frames, blocks, nFrames, di, status, slots);
     else if (slots) hipLaunchKernelGGL(block_offsets_set_kernel, dim3(nFrames), dim3(64), 0, stream, frames, blocks, nFrames, status, slots);
     else hipLaunchKernelGGL(block_offsets_kernel, dim3(nFrames), dim3(64), 0, stream, frames, blocks, nFrames, di, status);
     if (rescan) hipLaunchKernelGGL(frame_rescan_kernel, dim3(1), dim3(1024), 0, stream, frames, nFrames, dstCapacity, status);
 }
 
-void launch_block_offsets_d(FrameDesc* frames, BlockDesc* blocks, u32 capFrames, const DictInfo* di, u32* status, hipStream_t stream, const DictSlot* slots)
+void launch_block_offsets_d(FrameDesc* frames, BlockDesc* blocks, u32 capFrames, const DecodeDict& dd, u32* status, hipStream_t stream)
 {
-    if (slots) hipLaunchKernelGGL(block_offsets_open_d_kernel<true>, dim3(capFrames), dim3(64), 0, stream, frames, blocks, (const DictInfo*)nullptr, status, slots);
-    else hipLaunchKernelGGL(block_offsets_open_d_kernel<false>, dim3(capFrames), dim3(64), 0, stream, frames, blocks, di, status, (const DictSlot*)nullptr);
+    const DictSlot* const slots = dd.slots; const DictInfo* const di = slots ? nullptr : dd.dinfo;
+    if (slots) hipLaunchKernelGGL(block_offsets_open_d_kernel<true>, dim3(capFrames), dim3(64), 0, stream, frames, blocks, di, status, slots);
+    else hipLaunchKernelGGL(block_offsets_open_d_kernel<false>, dim3(capFrames), dim3(64), 0, stream, frames, blocks, di, status, slots);
 }
 
 // ZSTD_loadDEntropy's checks (U/ZstdDecompress.cs:1773-1875) on one lane: where the Huffman description and the three NCounts

@@ -127,21 +127,25 @@ void launch_ldm_count(const u8* src, u64 n, u64 frameSpan, const LdmLaunch& p, u
 u32* ldm_total_word(u8* small, u64 n);
 void launch_ldm_rest(const u8* src, u64 n, u32 nChunks, u32 chunkBytes, u64 frameSpan, const LdmLaunch& p, u32 nSplits, u8* small, u8* big,
                      Seq* seqs, u8* lits, ChunkMeta* meta, hipStream_t stream, StageHook hook, const LdmPrefix& pfx);
-// decoder (decode_walk.hip, decode_lit.hip, decode_seq.hip)
-// `slots` (null: off), where a launcher takes it: the slot table of a context's DDict set (ZSTD_d_refMultipleDDicts, zmi_dictset.h; nSet =
-// its records in front of the current DDict's).  The launcher then starts the stage's set instance, which reads every dictionary
-// argument per frame through FrameDesc::dictSlot; the single-dictionary arguments beside it are not read.
+// decoder (decode_walk.hip, decode_lit.hip, decode_seq.hip, decode_origin.hip)
+// The dictionary of a call as the stage launchers take it (the host's decode_dict, zstd_mi355x_dec.hip): formatted or raw content, the
+// whole dictionary and its parsed header (formatted only), the content that is history in front of every frame — a caller may put a
+// prefix or a stream's history there —, the dictID, and seqTabs: a DDict's ready-made sequence tables (null for a loaded dictionary).
+// slots (null: off): the slot table of the context's DDict set (ZSTD_d_refMultipleDDicts, zmi_dictset.h), nSet records sorted by dictID
+// and the current DDict's behind them.  A launcher then starts the stage's set instance, which reads every dictionary argument per
+// frame through FrameDesc::dictSlot and gets nulls for the single-dictionary arguments; the other fields describe the current DDict.
+struct DecodeDict { bool fmt; const u8* dictFull; const DictInfo* dinfo; const u8* dictContent; u32 dictContentSize, dictID; const u32* seqTabs;
+                    const DictSlot* slots; u32 nSet; };
 size_t decode_walk_workspace_bytes(u64 srcSize);
 void launch_frame_walk_count(const u8* src, u64 srcSize, u32 maxFrames, u32* status, u8* walkWs, hipStream_t stream);
 void launch_frame_walk_emit(const u8* src, u64 srcSize, FrameDesc* frames, BlockDesc* blocks, u8* walkWs, hipStream_t stream);
-void launch_frame_walk_serial(const u8* src, u64 srcSize, FrameDesc* frames, BlockDesc* blocks, u32 maxFrames, u32* status, u32 dictID, u32 emit,
-                              hipStream_t stream, const DictSlot* slots = nullptr, u32 nSet = 0);
-void launch_batch_walk_count(const u8* src, const BatchEntryIn* in, BatchEntryOut* out, u32 nEntries, u32 dictID, u64 aloneAbove, u32* status, hipStream_t stream,
-                             const DictSlot* slots = nullptr, u32 nSet = 0, bool open = false,         // open: ZSTDMI_DCtx_setBatchUnsized
-                             bool caps = false);       // caps: batch_scan's instance that holds the entries to the limits in the status words
+void launch_frame_walk_serial(const u8* src, u64 srcSize, FrameDesc* frames, BlockDesc* blocks, u32 maxFrames, u32* status, const DecodeDict& dd, u32 emit, hipStream_t stream);
+// open: ZSTDMI_DCtx_setBatchUnsized; caps: batch_scan's instance that holds the entries to the limits in the status words
+void launch_batch_walk_count(const u8* src, const BatchEntryIn* in, BatchEntryOut* out, u32 nEntries, const DecodeDict& dd, u64 aloneAbove, u32* status, hipStream_t stream,
+                             bool open = false, bool caps = false);
 // rooms (not null: the open instance): one u64 per frame, the room its literals have in the scratch
 void launch_batch_walk_emit(const u8* src, const BatchEntryIn* in, const BatchEntryOut* out, u32 nEntries, FrameDesc* frames, BlockDesc* blocks, hipStream_t stream,
-                            const DictSlot* slots = nullptr, u32 nSet = 0, u64* rooms = nullptr);
+                            const DecodeDict& dd, u64* rooms = nullptr);
 void launch_batch_rescan(const BatchEntryIn* in, BatchEntryOut* out, u32 nEntries, FrameDesc* frames, hipStream_t stream);
 void launch_batch_fold(BatchEntryOut* out, u32 nEntries, const u64* keys, hipStream_t stream);
 // A batch whose descriptors lie in HBM (ZSTDMI_decompressBatchAsync).  The host knows the number of entries and the
@@ -153,16 +157,15 @@ struct BatchLimitsD { u32 frames, blocks; u64 content, sequences; };
 void launch_batch_plan_d(const void* const* srcs, const size_t* sizes, void* const* dsts, const size_t* caps, u32 n, u64 bound, BatchEntryIn* in, u32* verdict, hipStream_t stream);
 void launch_batch_init_d(u32* status, const u64* blockKeys, const u64* rooms, u64 dumpOff, const BatchLimitsD& lim, hipStream_t stream);
 void launch_batch_finish_d(const BatchEntryOut* out, const u32* verdict, u32 n, size_t* dstSizes, hipStream_t stream);
-void launch_block_prepass_d(const u8* src, FrameDesc* frames, BlockDesc* blocks, u32 capFrames, u32 capBlocks, u32 haveDict, u32* status, hipStream_t stream, const DictSlot* slots);
-void launch_seq_decode_d(const u8* src, const FrameDesc* frames, BlockDesc* blocks, u32 capBlocks, SeqRec* recs, u32* status,
-                         const u8* dictFull, const DictInfo* di, const u32* dictTabs, hipStream_t stream, const DictSlot* slots);
-void launch_block_offsets_d(FrameDesc* frames, BlockDesc* blocks, u32 capFrames, const DictInfo* di, u32* status, hipStream_t stream, const DictSlot* slots);
+void launch_block_prepass_d(const u8* src, FrameDesc* frames, BlockDesc* blocks, u32 capFrames, u32 capBlocks, const DecodeDict& dd, u32* status, hipStream_t stream);
+void launch_seq_decode_d(const u8* src, const FrameDesc* frames, BlockDesc* blocks, u32 capBlocks, SeqRec* recs, u32* status, const DecodeDict& dd, hipStream_t stream);
+void launch_block_offsets_d(FrameDesc* frames, BlockDesc* blocks, u32 capFrames, const DecodeDict& dd, u32* status, hipStream_t stream);
 void launch_decode_literals_d(const u8* src, u8* out, u8* scratch, const FrameDesc* frames, const BlockDesc* blocks, u32 capBlocks, u32* status,
-                              u8* slowFlags, u32 mode, const u8* dictFull, const DictInfo* di, hipStream_t stream, const DictSlot* slots);
+                              u8* slowFlags, u32 mode, const DecodeDict& dd, hipStream_t stream);
 void launch_place_literals_d(const u8* src, u8* out, const u8* scratch, const FrameDesc* frames, const BlockDesc* blocks, u32 capBlocks,
                              const SeqRec* recs, const u32* status, hipStream_t stream);
 void launch_exec_matches_d(const u8* src, u8* out, const FrameDesc* frames, const BlockDesc* blocks, u32 capFrames, const SeqRec* recs, u32* status,
-                           const u8* dict, u32 dictSize, hipStream_t stream, int wide, const DictSlot* slots);
+                           const DecodeDict& dd, hipStream_t stream, int wide);
 void launch_seek_select(const u8* tab, u64 tableBytes, u32 n, u32 stride, u64 srcSize, u64 offset, u64 length, u64* sum, hipStream_t stream);
 void launch_seek_emit(const u8* tab, u32 stride, u32 first, u32 nSel, u64 dFirst, u64 offset, u64 dstBias, u64 edgeBias, u64 slot1, u32 cutFirst, u32 cutLast,
                       BatchEntryIn* out, hipStream_t stream);
@@ -185,20 +188,19 @@ void launch_ranges_plan_d(const u8* tab, u32 n, u32 stride, const RangesWs& ws, 
 void launch_seq_stats(const Seq* seqs, const u8* lits, const ChunkMeta* meta, u32 nChunks, const u8* src, u32 chunkBytes, u32* stats, hipStream_t stream);
 void launch_dict_parse(const u8* dict, u32 dictSize, DictInfo* out, hipStream_t stream);
 void launch_dict_ctables(const u8* dict, u32 dictSize, const DictInfo* info, DictCTables* out, hipStream_t stream);
-void launch_block_prepass(const u8* src, FrameDesc* frames, BlockDesc* blocks, u32 nFrames, u32 nBlocks, u32 haveDict, u32 earlyLiterals, u32* status, hipStream_t stream,
-                          u32 phantoms = 0, const DictSlot* slots = nullptr, bool open = false);     // phantoms, open: decode_walk.hip block_link_body
-// dictTabs (null: none): a DDict's ready-made tables, which the kernel's instance for them copies where a block repeats the dictionary's
-void launch_seq_decode(const u8* src, const FrameDesc* frames, BlockDesc* blocks, u32 nBlocks, SeqRec* recs, u32* status,
-                       const u8* dictFull, const DictInfo* di, const u32* dictTabs, hipStream_t stream, const DictSlot* slots = nullptr);
+void launch_block_prepass(const u8* src, FrameDesc* frames, BlockDesc* blocks, u32 nFrames, u32 nBlocks, const DecodeDict& dd, u32 earlyLiterals, u32* status, hipStream_t stream,
+                          u32 phantoms = 0, bool open = false);     // phantoms, open: decode_walk.hip block_link_body
+// (dd.seqTabs not null: the kernel's instance that copies a DDict's ready-made tables where a block repeats the dictionary's)
+void launch_seq_decode(const u8* src, const FrameDesc* frames, BlockDesc* blocks, u32 nBlocks, SeqRec* recs, u32* status, const DecodeDict& dd, hipStream_t stream);
 // A formatted dictionary's three sequence decoding tables, built once (ZSTD_createDDict): words [0, 1280) are the image seq_decode_kernel
 // holds per block in LDS (LL at 0, ML at 512, OF at 1024), words kDictTabLogs + 0 / 1 / 2 the LL / OF / ML table logs (all ones: corrupt)
 constexpr u32 kDictTabLogs = 1280, kDictTabWords = 1284;
 void launch_dict_seq_tables(const u8* dictFull, const DictInfo* di, u32* tabs, hipStream_t stream);
-void launch_block_offsets(FrameDesc* frames, BlockDesc* blocks, u32 nFrames, const DictInfo* di, u32 rescan, u64 dstCapacity, u32* status, hipStream_t stream,
-                          const DictSlot* slots = nullptr, bool open = false);
+// reps: the repcodes a frame starts from (dd.dinfo, or a segmented stream's carried triple)
+void launch_block_offsets(FrameDesc* frames, BlockDesc* blocks, u32 nFrames, const DecodeDict& dd, const DictInfo* reps, u32 rescan, u64 dstCapacity, u32* status, hipStream_t stream,
+                          bool open = false);
 void launch_decode_literals(const u8* src, u8* out, u8* scratch, const FrameDesc* frames, const BlockDesc* blocks, u32 nBlocks, u32* status,
-                            u8* slowFlags, u32 mode, const u8* dictFull, const DictInfo* di, hipStream_t stream, StageHook hook,
-                            const DictSlot* slots = nullptr);
+                            u8* slowFlags, u32 mode, const DecodeDict& dd, hipStream_t stream, StageHook hook);
 void launch_place_literals(const u8* src, u8* out, const u8* scratch, const FrameDesc* frames, const BlockDesc* blocks, u32 nBlocks,
                            const SeqRec* recs, const u32* status, hipStream_t stream);
 // a segmented stream's carried state (decode_stream.hip)
@@ -214,13 +216,12 @@ inline void xxh_carry_reset(XxhCarry* x)
     x->acc[0] = P1 + P2; x->acc[1] = P2; x->acc[2] = 0; x->acc[3] = 0 - P1;
 }
 void launch_exec_matches(const u8* src, u8* out, const FrameDesc* frames, const BlockDesc* blocks, u32 nFrames, const SeqRec* recs, u32* status,
-                         const u8* dict, u32 dictSize, hipStream_t stream, int wide, const DictSlot* slots = nullptr);
+                         const DecodeDict& dd, hipStream_t stream, int wide);
 void launch_origin_select(FrameDesc* frames, u32 nFrames, u64 minBytes, u32* list, u32 listCap, u64 originCap, u32* status, hipStream_t stream);
 void launch_origin_init(const FrameDesc* frames, const BlockDesc* blocks, const u32* list, u32 listCap, u64 maxFrameBytes, const SeqRec* recs, u32* status,
-                        u32* origin, u32 dictSize, hipStream_t stream, const DictSlot* slots = nullptr);
+                        u32* origin, const DecodeDict& dd, hipStream_t stream);
 void launch_origin_jump(const FrameDesc* frames, const u32* list, u32 listCap, u64 maxFrameBytes, u32* status, u32* origin, u32* done, u32 r0, u32 r1, hipStream_t stream);
-void launch_origin_gather(const FrameDesc* frames, const u32* list, u32 listCap, u64 maxFrameBytes, const u32* status, const u32* origin, u8* out, const u8* dict, hipStream_t stream,
-                          const DictSlot* slots = nullptr);
+void launch_origin_gather(const FrameDesc* frames, const u32* list, u32 listCap, u64 maxFrameBytes, const u32* status, const u32* origin, u8* out, const DecodeDict& dd, hipStream_t stream);
 // a batch of samples through the compressor, sizes (and sequence statistics) only (zstd_mi355x.hip; the dictionary trainer's inner loop)
 size_t compress_samples(ZSTD_CCtx* c, const u8* src, const u64* offs, const size_t* sizes, size_t n, size_t* outSizes, u32* stats);
 }

@@ -99,11 +99,11 @@ struct ZSTD_DCtx_s {
     DevBuf rangesAsyncWs;
     ZSTD_DCtx_s();
 };
-// what ZSTDMI_DCtx_prepareBatchAsync resolved: the limits with their defaults filled in, and where the dump area lies in the scratch
-struct DAsyncPrep { u64 gen; size_t maxEntries; u64 bound; BatchLimitsD lim; u64 dumpOff; };
-// what ZSTDMI_DCtx_prepareRangesAsync resolved: the same, the stream (the caller keeps its bytes), its table as the footer and
-// seek_index state it, and the rows of the decode core's table
-struct DRangesPrep { u64 gen; size_t maxRanges; u64 maxRangeBytes; BatchLimitsD lim; u64 dumpOff; const u8* src; const u8* tab; u32 n, stride; u64 total; u32 nRows; };
+// what either prepare resolved: dctx_gen() as it was then, and the limits with their defaults filled in (the decode core lays its lists out from them)
+struct DPrepCore { u64 gen; BatchLimitsD lim; };
+struct DAsyncPrep : DPrepCore { size_t maxEntries; u64 bound; };
+// (the stream too: the caller keeps its bytes; its table as the footer and seek_index state it; the rows of the decode core's table)
+struct DRangesPrep : DPrepCore { size_t maxRanges; u64 maxRangeBytes; const u8* src; const u8* tab; u32 n, stride; u64 total; u32 nRows; };
 static void dctx_drop_prepares(ZSTD_DCtx* d) { delete d->asyncPrep; d->asyncPrep = nullptr; delete d->rangesPrep; d->rangesPrep = nullptr; }
 static void dctx_async_drain(ZSTD_DCtx* d);
 ZSTD_DCtx_s::ZSTD_DCtx_s()
@@ -363,35 +363,28 @@ static size_t dctx_sync_dictionary(ZSTD_DCtx* d)
     return 0;
 }
 
-// the loaded dictionary as the decode kernels take it
-// seqTabs: a DDict's ready-made sequence tables (null for a loaded dictionary and for raw content)
-// slots (null: the single-dictionary kernels run): the context's DDict set as the kernels' set instances read it, nSet records sorted by
-// dictID and the current DDict's behind them (dctx_sync_slots); the other fields then describe the current DDict
-struct DecodeDict { bool fmt; const u8* dictFull; const DictInfo* dinfo; const u8* dictContent; u32 dictContentSize, dictID; const u32* seqTabs;
-                    const DictSlot* slots; u32 nSet; };
-static DecodeDict decode_dict(const ZSTD_DCtx* d)
+// the loaded dictionary as the decode kernels take it (DecodeDict, zmi_host.h; slots: dctx_sync_slots)
+// a dictionary as its owner holds it (a DDict, or the context's private copy): formatted or raw, its bytes on the host (0: none), the parsed
+// header there, the device copies.  dict_fields is the one place that derives the kernels' fields from it.
+struct DictView { bool formatted; size_t bytes; const DictInfo& info; const void* dev; const void* infoDev; const void* seqTabs; };
+static DictView ddict_view(const ZSTD_DDict_s& g) { return { g.formatted, g.host.size(), g.info, g.dict.p, g.dictInfoDev.p, g.seqTabs.p }; }
+static DecodeDict dict_fields(const DictView& v)
 {
     DecodeDict k;
     k.slots = nullptr; k.nSet = 0;
-    if (ddict_shared(d)) {
-        const ZSTD_DDict_s& g = *d->ddict;
-        k.fmt = g.formatted && !g.host.empty();
-        k.dictFull = k.fmt ? (const u8*)g.dict.p : nullptr;
-        k.dinfo = k.fmt ? (const DictInfo*)g.dictInfoDev.p : nullptr;
-        k.dictContent = g.host.empty() ? nullptr : (const u8*)g.dict.p + (k.fmt ? g.info.contentOff : 0u);
-        k.dictContentSize = g.host.empty() ? 0u : (k.fmt ? g.info.contentSize : (u32)g.host.size());
-        k.dictID = k.fmt ? g.info.dictID : 0u;
-        k.seqTabs = k.fmt ? (const u32*)g.seqTabs.p : nullptr;
-        return k;
-    }
-    k.seqTabs = nullptr;
-    k.fmt = d->dictFormatted && !d->dictHost.empty();
-    k.dictFull = k.fmt ? (const u8*)d->dict.p : nullptr;
-    k.dinfo = k.fmt ? (const DictInfo*)d->dictInfoDev.p : nullptr;
-    k.dictContent = d->dictHost.empty() ? nullptr : (const u8*)d->dict.p + (k.fmt ? d->info.contentOff : 0u);
-    k.dictContentSize = d->dictHost.empty() ? 0u : (k.fmt ? d->info.contentSize : (u32)d->dictHost.size());
-    k.dictID = k.fmt ? d->info.dictID : 0u;
+    k.fmt = v.formatted && v.bytes;
+    k.dictFull = k.fmt ? (const u8*)v.dev : nullptr;
+    k.dinfo = k.fmt ? (const DictInfo*)v.infoDev : nullptr;
+    k.dictContent = v.bytes ? (const u8*)v.dev + (k.fmt ? v.info.contentOff : 0u) : nullptr;
+    k.dictContentSize = v.bytes ? (k.fmt ? v.info.contentSize : (u32)v.bytes) : 0u;
+    k.dictID = k.fmt ? v.info.dictID : 0u;
+    k.seqTabs = k.fmt ? (const u32*)v.seqTabs : nullptr;
     return k;
+}
+static DecodeDict decode_dict(const ZSTD_DCtx* d)
+{
+    if (ddict_shared(d)) return dict_fields(ddict_view(*d->ddict));
+    return dict_fields(DictView{ d->dictFormatted, d->dictHost.size(), d->info, d->dict.p, d->dictInfoDev.p, nullptr });
 }
 
 // a DDict as a record of the slot table (what decode_dict says of a shared one)
@@ -399,13 +392,9 @@ static void fill_slot(const ZSTD_DDict_s* g, DictSlot& r)
 {
     r = DictSlot{};
     if (!g || g->host.empty()) return;
-    const bool fmt = g->formatted;
-    r.formatted = fmt ? 1u : 0u;
-    r.dictFull = fmt ? (const u8*)g->dict.p : nullptr;
-    r.content = (const u8*)g->dict.p + (fmt ? g->info.contentOff : 0u);
-    r.contentSize = fmt ? g->info.contentSize : (u32)g->host.size();
-    r.seqTabs = fmt ? (const u32*)g->seqTabs.p : nullptr;
-    if (!fmt) return;
+    const DecodeDict k = dict_fields(ddict_view(*g));
+    r.formatted = k.fmt ? 1u : 0u; r.dictFull = k.dictFull; r.content = k.dictContent; r.contentSize = k.dictContentSize; r.seqTabs = k.seqTabs;
+    if (!k.fmt) return;
     r.dictID = g->info.dictID;
     r.hufOff = g->info.hufOff; r.hufSize = g->info.hufSize; r.ofOff = g->info.ofOff; r.mlOff = g->info.mlOff; r.llOff = g->info.llOff; r.repOff = g->info.repOff;
     for (int i = 0; i < 3; ++i) r.rep[i] = g->info.rep[i];
@@ -427,6 +416,13 @@ static size_t dctx_sync_slots(ZSTD_DCtx* d, DecodeDict& dd)
     dd.slots = (const DictSlot*)d->slotTab.p; dd.nSet = (u32)d->ddictSet.size();
     return 0;
 }
+// the DecodeDict of a call: the dictionary uploaded where it is new, viewed as the kernels take it, the set's slot table behind it
+static size_t call_dict(ZSTD_DCtx* d, DecodeDict& dd)
+{
+    const size_t e = dctx_sync_dictionary(d); if (isErr(e)) return e;
+    dd = decode_dict(d);
+    return dctx_sync_slots(d, dd);
+}
 
 // the status words (d->status, kSt*): error key = "none" (all ones), everything else zero
 static size_t status_reset(ZSTD_DCtx* d)
@@ -439,16 +435,30 @@ static size_t status_reset(ZSTD_DCtx* d)
 static size_t status_read(ZSTD_DCtx* d, u32* st) { return dev_read(st, d->status.p, kStWords * sizeof(u32), d->stream); }
 static u64 st_u64(const u32* st, u32 lo, u32 hi) { return (u64)st[lo] | ((u64)st[hi] << 32); }
 
-// the work lists of a run over nFrames frames and nBlocks blocks with `total` bytes of content
-static size_t lists_bytes(u32 nFrames, u32 nBlocks, u64 total)
+// how a run ended (0: well): the first failing block's first error, then the run's own (unsized frames regenerated more than the destination holds)
+static size_t status_error(const u32* st)
 {
-    return (size_t)nFrames * sizeof(FrameDesc) + (size_t)nBlocks * sizeof(BlockDesc) + 64 + (size_t)total + (size_t)nFrames * kLitSkew + 256 + (size_t)nBlocks + 64;
+    if (st[kStErrKeyLo] != 0xFFFFFFFFu || st[kStErrKeyHi] != 0xFFFFFFFFu) return ZERR(st[kStErrKeyLo] & 0xFFFFu);
+    return st[kStErr] ? ZERR(st[kStErr]) : 0;
 }
-static bool ensure_lists(ZSTD_DCtx* d, u32 nFrames, u32 nBlocks, u64 total)
+
+// The work lists of a run over nFrames frames and nBlocks blocks with `content` bytes of literals, stated once: each buffer's bytes, and
+// where behind the frames' skewed literals the dump area of a pass with open entries lies (withDump: the scratch holds it; the open
+// kernel instances and batch_init_d_kernel find it through the status words).  blockKeys and litRooms are the batch's.
+struct ListsLayout { size_t frames, blocks, scratch, slowFlags, blockKeys, litRooms; u64 dumpOff; };
+static ListsLayout lists_layout(u32 nFrames, u32 nBlocks, u64 content, bool withDump)
 {
-    return d->frames.ensure((size_t)nFrames * sizeof(FrameDesc)) && d->blocks.ensure((size_t)nBlocks * sizeof(BlockDesc) + 64) &&
-           d->scratch.ensure((size_t)total + (size_t)nFrames * kLitSkew + 256) && d->slowFlags.ensure((size_t)nBlocks + 64);
+    ListsLayout l;
+    l.dumpOff = content + (u64)nFrames * kLitSkew + 256;
+    l.frames = (size_t)nFrames * sizeof(FrameDesc); l.blocks = (size_t)nBlocks * sizeof(BlockDesc) + 64;
+    l.scratch = (size_t)l.dumpOff + (withDump ? kLitDump : 0u);
+    l.slowFlags = (size_t)nBlocks + 64; l.blockKeys = (size_t)nBlocks * sizeof(u64) + 8; l.litRooms = (size_t)nFrames * sizeof(u64);
+    return l;
 }
+// (the four every run has)
+static bool ensure_lists(ZSTD_DCtx* d, const ListsLayout& l) { return d->frames.ensure(l.frames) && d->blocks.ensure(l.blocks) && d->scratch.ensure(l.scratch) && d->slowFlags.ensure(l.slowFlags); }
+// exec_matches' waves per frame: the setter's, else by the number of frames (64 x W sequences in flight per frame: measured on 1 - 4 MiB level-5 frames)
+static int exec_waves_for(const ZSTD_DCtx* d, u32 n) { return d->execWaves ? d->execWaves : n <= 256 ? 16 : n <= 512 ? 8 : n <= 1024 ? 4 : n <= 2048 ? 2 : 1; }
 
 // Everything behind the frame walk: the lists (d->frames, d->blocks; offsets relative to d_src and d_dst) through block_prepass,
 // seq_decode, block_offsets, the literal decoder, the origin path and exec_matches.  `tail` enqueues what the caller wants read back
@@ -466,9 +476,7 @@ static size_t decode_lists(ZSTD_DCtx* d, const DecodeDict& dd, u8* d_dst, const 
     hipStream_t s = d->stream;
     u32* status = (u32*)d->status.p;
     FrameDesc* frames = (FrameDesc*)d->frames.p; BlockDesc* blocks = (BlockDesc*)d->blocks.p;
-    const bool fmt = dd.fmt; const u8* const dictFull = dd.dictFull; const DictInfo* const dinfo = dd.dinfo;
-    const u8* const dictContent = dd.dictContent; const u32 dictContentSize = dd.dictContentSize;
-    const DictSlot* const slots = dd.slots;         // not null: every stage below runs its set instance and reads the dictionary per frame
+    // (dd.slots not null: every stage below runs its set instance and reads the dictionary per frame)
     // The literal decoder and seq_decode need nothing of each other (a block's Huffman streams and its FSE chains).  With few
     // blocks neither fills the chip — both are serial chains per block — so below kOverlapBlocks the literal decoder may run beside
     // seq_decode on a stream of its own (`early`: block_link then lets it write only the outputs whose place is known by now).
@@ -478,7 +486,7 @@ static size_t decode_lists(ZSTD_DCtx* d, const DecodeDict& dd, u8* d_dst, const 
     // frame_rescan, a dstOff computed from the bound in front of it, and block_link (which knows a frame's header, not its
     // neighbours) would let its first block be written there.  (A batch marks such frames itself: kFrameOpen.)
     const bool early = !(nUnsized && nFrames > 1) && (d->overlapMode == 2 || (d->overlapMode == 0 && nBlocks <= kOverlapBlocks));
-    launch_block_prepass(d_src, frames, blocks, nFrames, nBlocks, fmt ? 1u : 0u, early ? 1u : 0u, status, s, link ? link->phantoms : 0u, slots, open != nullptr);
+    launch_block_prepass(d_src, frames, blocks, nFrames, nBlocks, dd, early ? 1u : 0u, status, s, link ? link->phantoms : 0u, open != nullptr);
     { const size_t e = status_read(d, st); if (isErr(e)) return e; }
     d->timer.mark("block_prepass", s);
     const u64 nSeq = st_u64(st, kStSeqLo, kStSeqHi);
@@ -488,8 +496,7 @@ static size_t decode_lists(ZSTD_DCtx* d, const DecodeDict& dd, u8* d_dst, const 
     // own walk would outlast the sweep of every frame at least as long: the smallest size class 2^(20+k) with
     // 2^(20+k) / kWalkRate >= bytes(frames >= 2^(20+k)) / kSweepRate, from the per-class sums block_link filed.
     u64 originMin = 0, originBytes = 0, originLongest = 0; u32 originCap = 0;
-    // (the walk has 64 x W sequences in flight per frame, W waves by the number of frames: measured on 1 - 4 MiB level-5 frames)
-    const int execWaves = d->execWaves ? d->execWaves : nFrames <= 256 ? 16 : nFrames <= 512 ? 8 : nFrames <= 1024 ? 4 : nFrames <= 2048 ? 2 : 1;
+    const int execWaves = exec_waves_for(d, nFrames);
     if (d->originMode != 1) {
         const double kWalkRate = execWaves >= 16 ? 0.42e9 : execWaves == 8 ? 0.33e9 : execWaves == 4 ? 0.24e9 : execWaves == 2 ? 0.19e9 : 0.15e9;
         constexpr double kSweepRate = 20e9;
@@ -523,21 +530,21 @@ static size_t decode_lists(ZSTD_DCtx* d, const DecodeDict& dd, u8* d_dst, const 
     const bool beside = early && nSeq && (d->overlapMode == 2 || (litBytes >= 5 * nSeq && nSeq >= 64 * (u64)nBlocks));
     if (getenv("ZMI_DEBUG")) fprintf(stderr, "zmi: blocks %u seqs %llu coded literal bytes %llu early %d beside %d\n", nBlocks, (unsigned long long)nSeq, (unsigned long long)litBytes, (int)early, (int)beside);
     if (beside) {               // (the host has just waited for the pre-pass: everything the literal decoder reads is there)
-        launch_decode_literals(d_src, d_dst, (u8*)d->scratch.p, frames, blocks, nBlocks, status, (u8*)d->slowFlags.p, d->litDecoder, dictFull, dinfo, d->aux, StageHook(), slots);
+        launch_decode_literals(d_src, d_dst, (u8*)d->scratch.p, frames, blocks, nBlocks, status, (u8*)d->slowFlags.p, d->litDecoder, dd, d->aux, StageHook());
         if (hipEventRecord(d->auxDone, d->aux) != hipSuccess) return ZERR(kErrGeneric);
         auxGuard.on = true;
     }
-    launch_seq_decode(d_src, frames, blocks, nBlocks, recs, status, dictFull, dinfo, dd.seqTabs, s, slots);     d->timer.mark("seq_decode", s);
-    launch_block_offsets(frames, blocks, nFrames, link && link->reps ? link->reps : dinfo, nUnsized ? 1u : 0u, dstCapacity, status, s, slots, open != nullptr);  d->timer.mark("block_offsets", s);
+    launch_seq_decode(d_src, frames, blocks, nBlocks, recs, status, dd, s);     d->timer.mark("seq_decode", s);
+    launch_block_offsets(frames, blocks, nFrames, dd, link && link->reps ? link->reps : dd.dinfo, nUnsized ? 1u : 0u, dstCapacity, status, s, open != nullptr);  d->timer.mark("block_offsets", s);
     if (open) { launch_batch_rescan(open->in, open->out, open->n, frames, s); d->timer.mark("batch_rescan", s); }
     if (auxGuard.on) { if (hipStreamWaitEvent(s, d->auxDone, 0) != hipSuccess) return ZERR(kErrGeneric); d->timer.mark("decode_literals", s); }     // (what of it seq_decode did not cover)
-    else launch_decode_literals(d_src, d_dst, (u8*)d->scratch.p, frames, blocks, nBlocks, status, (u8*)d->slowFlags.p, d->litDecoder, dictFull, dinfo, s, d->timer.hook(), slots);
+    else launch_decode_literals(d_src, d_dst, (u8*)d->scratch.p, frames, blocks, nBlocks, status, (u8*)d->slowFlags.p, d->litDecoder, dd, s, d->timer.hook());
     launch_place_literals(d_src, d_dst, (const u8*)d->scratch.p, frames, blocks, nBlocks, recs, status, s);    d->timer.mark("place_literals", s);
     if (originMin) {
         const u64 entries = originBytes + 1024 * (u64)originCap, longest = originLongest;
         u32* const origin = (u32*)d->origin.p; const u32* const list = (const u32*)d->originList.p;
         launch_origin_select(frames, nFrames, originMin, (u32*)d->originList.p, originCap, entries, status, s);
-        launch_origin_init(frames, blocks, list, originCap, longest, recs, status, origin, dictContent ? dictContentSize : 0u, s, slots);    d->timer.mark("origin_init", s);
+        launch_origin_init(frames, blocks, list, originCap, longest, recs, status, origin, dd, s);    d->timer.mark("origin_init", s);
         // The rounds in groups of six, the host looking at the last one's verdict in between: ordinary data settles in about ten
         // rounds, and a round that only finds out that nothing is left still costs its launch (the kernels check the flag too).
         for (u32 r = 0; r < kOriginRounds; r += 6) {
@@ -548,9 +555,9 @@ static size_t decode_lists(ZSTD_DCtx* d, const DecodeDict& dd, u8* d_dst, const 
             if (!open) break;
         }
         d->timer.mark("origin_jump", s);
-        launch_origin_gather(frames, list, originCap, longest, status, origin, d_dst, dictContent, s, slots);    d->timer.mark("origin_gather", s);
+        launch_origin_gather(frames, list, originCap, longest, status, origin, d_dst, dd, s);    d->timer.mark("origin_gather", s);
     }
-    launch_exec_matches(d_src, d_dst, frames, blocks, nFrames, recs, status, dictContent, dictContentSize, s, execWaves, slots);  d->timer.mark("exec_matches", s);
+    launch_exec_matches(d_src, d_dst, frames, blocks, nFrames, recs, status, dd, s, execWaves);  d->timer.mark("exec_matches", s);
     if (!tail()) return ZERR(kErrGeneric);
     { const size_t e = status_read(d, st); if (isErr(e)) return e; }
     d->lastDictTabBlocks += st[kStDictTabBlocks];
@@ -569,11 +576,9 @@ static size_t decompress_device(ZSTD_DCtx* d, u8* d_dst, size_t dstCapacity, con
     const u32 maxFrames = (u32)((srcSize / 9 + 1) < (1u << 26) ? (srcSize / 9 + 1) : (1u << 26));
     if (!d->status.ensure(kStWords * sizeof(u32)) || !d->walkWs.ensure(decode_walk_workspace_bytes(srcSize))) return ZERR(kErrMemoryAllocation);
     u32* status = (u32*)d->status.p;
-    { const size_t e = dctx_sync_dictionary(d); if (isErr(e)) return e; }
-    DecodeDict dd = decode_dict(d);
+    DecodeDict dd;
+    { const size_t e = call_dict(d, dd); if (isErr(e)) return e; }
     if (d->pfxDev) { dd.dictContent = d->pfxDev; dd.dictContentSize = (u32)d->pfxSize; }      // ZSTD_DCtx_refPrefix: raw content, read where it lies
-    { const size_t e = dctx_sync_slots(d, dd); if (isErr(e)) return e; }
-    const u32 dictID = dd.dictID;
     d->timer.begin(s);
     { const size_t e = status_reset(d); if (isErr(e)) return e; }
     u32 st[kStWords] = {};
@@ -584,7 +589,7 @@ static size_t decompress_device(ZSTD_DCtx* d, u8* d_dst, size_t dstCapacity, con
     // (the parallel walk lists only frames that name no dictionary: all of them are the current DDict's, the single-dictionary kernels' case)
     if (!serialWalk) { dd.slots = nullptr; dd.nSet = 0; }
     if (serialWalk) {   // the segment links did not close: take the exact serial walk (it also yields the reference's error code)
-        launch_frame_walk_serial(d_src, srcSize, nullptr, nullptr, maxFrames, status, dictID, 0, s, dd.slots, dd.nSet);
+        launch_frame_walk_serial(d_src, srcSize, nullptr, nullptr, maxFrames, status, dd, 0, s);
         const size_t e = status_read(d, st); if (isErr(e)) return e;
         if (dd.slots) d->lastSetFrames += st[kStSetFrames];
     }
@@ -593,15 +598,14 @@ static size_t decompress_device(ZSTD_DCtx* d, u8* d_dst, size_t dstCapacity, con
     const u64 total = st_u64(st, kStTotalLo, kStTotalHi);       // content sizes (bounds for frames without one)
     if (!nUnsized && total > dstCapacity) return ZERR(kErrDstSizeTooSmall);
     if (nFrames == 0) { d->timer.finish(); return 0; }
-    if (!ensure_lists(d, nFrames, nBlocks, total)) return ZERR(kErrMemoryAllocation);
+    if (!ensure_lists(d, lists_layout(nFrames, nBlocks, total, false))) return ZERR(kErrMemoryAllocation);
     FrameDesc* frames = (FrameDesc*)d->frames.p; BlockDesc* blocks = (BlockDesc*)d->blocks.p;
-    if (serialWalk) launch_frame_walk_serial(d_src, srcSize, frames, blocks, maxFrames, status, dictID, 1, s, dd.slots, dd.nSet);
+    if (serialWalk) launch_frame_walk_serial(d_src, srcSize, frames, blocks, maxFrames, status, dd, 1, s);
     else            launch_frame_walk_emit(d_src, srcSize, frames, blocks, (u8*)d->walkWs.p, s);
     d->timer.mark("frame_walk", s);
     { const size_t e = decode_lists(d, dd, d_dst, d_src, nFrames, nBlocks, nUnsized, dstCapacity, st, [] { return true; }); if (isErr(e)) return e; }
     d->timer.finish();
-    if (st[kStErrKeyLo] != 0xFFFFFFFFu || st[kStErrKeyHi] != 0xFFFFFFFFu) return ZERR(st[kStErrKeyLo] & 0xFFFFu);   // the first failing block's first error
-    if (st[kStErr]) return ZERR(st[kStErr]);                  // regenerated sizes of unsized frames exceed the destination
+    { const size_t e = status_error(st); if (isErr(e)) return e; }
     if (nUnsized) return (size_t)st_u64(st, kStActualLo, kStActualHi);
     return (size_t)total;
 }
@@ -631,7 +635,7 @@ static size_t decode_entries(ZSTD_DCtx* d, const DecodeDict& dd, const u8* srcBa
     u32 st[kStWords] = {};
     { const size_t e = status_reset(d); if (isErr(e)) return e; }
     d->lastBatchWs = 0;
-    launch_batch_walk_count(srcBase, dIn, dOut, n, dd.dictID, kBatchAloneAbove, status, s, dd.slots, dd.nSet, d->batchUnsized != 0);
+    launch_batch_walk_count(srcBase, dIn, dOut, n, dd, kBatchAloneAbove, status, s, d->batchUnsized != 0);
     if (!readBack() ||
         hipMemcpyAsync(st, status, sizeof st, hipMemcpyDeviceToHost, s) != hipSuccess) return ZERR(kErrGeneric);
     { const size_t e = stream_wait(s); if (isErr(e)) return e; }
@@ -642,17 +646,17 @@ static size_t decode_entries(ZSTD_DCtx* d, const DecodeDict& dd, const u8* srcBa
     // entries with unsized frames in the lists (ZSTDMI_DCtx_setBatchUnsized; none: the pass is the one it always was): `total` holds
     // their clamped literal rooms, the dump area lies behind the frames' scratch, and the open instances find both through the status words
     const bool open = st[kStOpenEntries] != 0;
-    const u64 dumpOff = total + (u64)nFrames * kLitSkew + 256, scratchBytes = open ? total + kLitDump : total;
+    const ListsLayout l = lists_layout(nFrames, nBlocks, total, open);
     const OpenEntries openEntries = { dIn, dOut, n };
     u32 keyWords[2] = {0, 0}, openWords[4] = {0, 0, 0, 0};      // (sources of asynchronous copies: they live until decode_lists has synchronised)
     if (nFrames) {
-        if (!ensure_lists(d, nFrames, nBlocks, scratchBytes) || !d->blockKeys.ensure((size_t)nBlocks * sizeof(u64) + 8)) return ZERR(kErrMemoryAllocation);
-        d->lastBatchWs += (long long)(lists_bytes(nFrames, nBlocks, scratchBytes) + (size_t)nBlocks * sizeof(u64) + 8);
+        if (!ensure_lists(d, l) || !d->blockKeys.ensure(l.blockKeys)) return ZERR(kErrMemoryAllocation);
+        d->lastBatchWs += (long long)(l.frames + l.blocks + l.scratch + l.slowFlags + l.blockKeys);
         if (open) {
-            if (!d->litRooms.ensure((size_t)nFrames * sizeof(u64))) return ZERR(kErrMemoryAllocation);
-            d->lastBatchWs += (long long)((size_t)nFrames * sizeof(u64));
+            if (!d->litRooms.ensure(l.litRooms)) return ZERR(kErrMemoryAllocation);
+            d->lastBatchWs += (long long)l.litRooms;
             const u64 rooms = (u64)(uintptr_t)d->litRooms.p;
-            openWords[0] = (u32)rooms; openWords[1] = (u32)(rooms >> 32); openWords[2] = (u32)dumpOff; openWords[3] = (u32)(dumpOff >> 32);
+            openWords[0] = (u32)rooms; openWords[1] = (u32)(rooms >> 32); openWords[2] = (u32)l.dumpOff; openWords[3] = (u32)(l.dumpOff >> 32);
             static_assert(kStRoomHi == kStRoomLo + 1 && kStDumpLo == kStRoomLo + 2 && kStDumpHi == kStRoomLo + 3, "one copy fills the four words");
             if (hipMemcpyAsync(status + kStRoomLo, openWords, sizeof openWords, hipMemcpyHostToDevice, s) != hipSuccess) return ZERR(kErrGeneric);
         }
@@ -660,7 +664,7 @@ static size_t decode_entries(ZSTD_DCtx* d, const DecodeDict& dd, const u8* srcBa
         if (hipMemsetAsync(d->blockKeys.p, 0xFF, (size_t)nBlocks * sizeof(u64), s) != hipSuccess ||
             hipMemcpyAsync(status + kStBlockKeysLo, &keyWords[0], sizeof(u32), hipMemcpyHostToDevice, s) != hipSuccess ||
             hipMemcpyAsync(status + kStBlockKeysHi, &keyWords[1], sizeof(u32), hipMemcpyHostToDevice, s) != hipSuccess) return ZERR(kErrGeneric);
-        launch_batch_walk_emit(srcBase, dIn, dOut, n, (FrameDesc*)d->frames.p, (BlockDesc*)d->blocks.p, s, dd.slots, dd.nSet, open ? (u64*)d->litRooms.p : nullptr);
+        launch_batch_walk_emit(srcBase, dIn, dOut, n, (FrameDesc*)d->frames.p, (BlockDesc*)d->blocks.p, s, dd, open ? (u64*)d->litRooms.p : nullptr);
         d->timer.mark("batch_walk", s);
         const size_t e = decode_lists(d, dd, dstBase, srcBase, nFrames, nBlocks, 0, dstSpan, st, [&]() -> bool {
             launch_batch_fold(dOut, n, (const u64*)d->blockKeys.p, s);
@@ -682,10 +686,9 @@ static size_t decompress_batch_impl(ZSTD_DCtx* d, const void* const* srcs, const
     if (d->workers.size() > 1 || d->pfx) return ZERR(kErrParameterUnsupported);      // (a pending ZSTD_DCtx_refPrefix serves one single call)
     e = set_check(d); if (isErr(e)) return e;
     d->lastBatchAlone = 0; d->lastBatchWs = 0;
-    e = dctx_sync_dictionary(d); if (isErr(e)) return e;
     hipStream_t s = d->stream;
-    DecodeDict dd = decode_dict(d);
-    e = dctx_sync_slots(d, dd); if (isErr(e)) return e;
+    DecodeDict dd;
+    e = call_dict(d, dd); if (isErr(e)) return e;
     // one base pointer each: the lowest source, the lowest destination
     uintptr_t loS = ~(uintptr_t)0, loD = ~(uintptr_t)0, hiD = 0;
     for (size_t i = 0; i < n; i++) {
@@ -730,60 +733,84 @@ static size_t decompress_batch_impl(ZSTD_DCtx* d, const void* const* srcs, const
 // kernels only: the plan kernel reads the caller's arrays, the init kernel fills the status words, the scans hold the entries and the
 // blocks to the limits (batch_scan_kernel<true>, seq_scan_kernel<true>), every stage takes its count from the status words over a
 // grid sized from the limit, and the finish kernel writes the caller's sizes column.
-// the limits with their defaults filled in -> false: a zero where none is allowed, or a limit beyond the lists' index range
-static bool dbatch_limits(const ZSTDMI_DBatchLimits* L, size_t& maxEntries, u64& bound, BatchLimitsD& lim)
+// The limits rule of both prepares: content, and frames (framesDefault: what 0 stands for), blocks and sequences with their defaults
+// filled in -> false: no content, or a limit beyond the lists' index range
+static bool dcore_limits(u64 maxFrames, u64 maxBlocks, u64 maxSequences, u64 maxContent, u64 framesDefault, BatchLimitsD& lim)
 {
-    if (!L->maxEntries || L->maxEntries > 0xFFFFFFF0ull || !L->maxContent || L->maxContent > ((u64)1 << 48) || !L->srcSizeBound || L->srcSizeBound > kBatchAloneAbove) return false;
-    const u64 frames = L->maxFrames ? L->maxFrames : L->maxEntries;
-    if (frames > ((u64)1 << 26)) return false;
-    const u64 blocks = L->maxBlocks ? L->maxBlocks : frames + L->maxContent / 16384;
-    if (blocks > 0xFFFFFFF0ull) return false;
-    const u64 seqs = L->maxSequences ? L->maxSequences : L->maxContent / 3 + 64;
-    if (seqs > ((u64)1 << 48)) return false;
-    maxEntries = L->maxEntries; bound = L->srcSizeBound;
-    lim.frames = (u32)frames; lim.blocks = (u32)blocks; lim.content = L->maxContent; lim.sequences = seqs;
+    const u64 frames = maxFrames ? maxFrames : framesDefault;
+    if (!maxContent || maxContent > ((u64)1 << 48) || frames > ((u64)1 << 26)) return false;
+    const u64 blocks = maxBlocks ? maxBlocks : frames + maxContent / 16384, seqs = maxSequences ? maxSequences : maxContent / 3 + 64;
+    if (blocks > 0xFFFFFFF0ull || seqs > ((u64)1 << 48)) return false;
+    lim.frames = (u32)frames; lim.blocks = (u32)blocks; lim.content = maxContent; lim.sequences = seqs;
     return true;
 }
-// the work buffers of a call at the limits, in the order the prepare asks for them
-struct DAsyncBytes { size_t batchIn, batchOut, verdict, frames, blocks, scratch, slowFlags, blockKeys, litRooms, recs, status; };
-static DAsyncBytes dbatch_bytes(size_t maxEntries, const BatchLimitsD& lim)
+// the batch's own: entries and the bound of one entry's compressed bytes -> false: a zero where none is allowed, or the rule above
+static bool dbatch_limits(const ZSTDMI_DBatchLimits* L, size_t& maxEntries, u64& bound, BatchLimitsD& lim)
 {
-    DAsyncBytes b;
-    b.batchIn = maxEntries * sizeof(BatchEntryIn); b.batchOut = maxEntries * sizeof(BatchEntryOut); b.verdict = maxEntries * sizeof(u32);
-    b.frames = (size_t)lim.frames * sizeof(FrameDesc); b.blocks = (size_t)lim.blocks * sizeof(BlockDesc) + 64;
-    b.scratch = (size_t)lim.content + kLitDump + (size_t)lim.frames * kLitSkew + 256;        // (the dump area behind the frames' scratch, as decode_entries lays it out)
-    b.slowFlags = (size_t)lim.blocks + 64; b.blockKeys = (size_t)lim.blocks * sizeof(u64) + 8; b.litRooms = (size_t)lim.frames * sizeof(u64);
-    b.recs = (size_t)(lim.sequences + 64) * sizeof(SeqRec); b.status = kStWords * sizeof(u32);
-    return b;
+    if (!L->maxEntries || L->maxEntries > 0xFFFFFFF0ull || !L->srcSizeBound || L->srcSizeBound > kBatchAloneAbove) return false;
+    maxEntries = L->maxEntries; bound = L->srcSizeBound;
+    return dcore_limits(L->maxFrames, L->maxBlocks, L->maxSequences, L->maxContent, L->maxEntries, lim);
+}
+// One table of the work buffers of an enqueued call at the limits, in the order a prepare asks for them: a prepare ensures its entries, a
+// workspace entry point sums them.  dcore_needs: the decode core's, over `rows` table rows, outRows answers and verdictRows verdicts.
+struct BufNeeds {
+    struct { DevBuf ZSTD_DCtx_s::* buf; size_t bytes; } e[16]; int n = 0;
+    void add(DevBuf ZSTD_DCtx_s::* buf, size_t bytes) { e[n].buf = buf; e[n].bytes = bytes; n++; }
+    size_t sum() const { size_t t = 0; for (int i = 0; i < n; ++i) t += e[i].bytes; return t; }
+    bool ensure(ZSTD_DCtx* d, int from) const { for (int i = from; i < n; ++i) if (!(d->*e[i].buf).ensure(e[i].bytes)) return false; return true; }
+};
+static void dcore_needs(BufNeeds& t, size_t rows, size_t outRows, size_t verdictRows, const BatchLimitsD& lim)
+{
+    typedef ZSTD_DCtx_s D;
+    const ListsLayout l = lists_layout(lim.frames, lim.blocks, lim.content, true);
+    t.add(&D::batchIn, rows * sizeof(BatchEntryIn)); t.add(&D::batchOut, outRows * sizeof(BatchEntryOut)); t.add(&D::asyncVerdict, verdictRows * sizeof(u32));
+    t.add(&D::frames, l.frames); t.add(&D::blocks, l.blocks); t.add(&D::scratch, l.scratch); t.add(&D::slowFlags, l.slowFlags);
+    t.add(&D::blockKeys, l.blockKeys); t.add(&D::litRooms, l.litRooms);
+    t.add(&D::recs, (size_t)(lim.sequences + 64) * sizeof(SeqRec)); t.add(&D::status, kStWords * sizeof(u32));
+}
+static BufNeeds dbatch_needs(size_t maxEntries, const BatchLimitsD& lim) { BufNeeds t; dcore_needs(t, maxEntries, maxEntries, maxEntries, lim); return t; }
+// What both prepares do alike, in two steps (the ranges prepare reads the footer behind the bind and indexes the table in front of the core's
+// buffers).  The first, behind a prepare's own limits: what the pass does not cover, as far as the host alone can tell (a pending prefix stays pending).
+static size_t prepare_d_enter(ZSTD_DCtx* d)
+{
+    if (d->workers.size() > 1 || d->pfx || d->originMode == 2) return ZERR(kErrParameterUnsupported);
+    const size_t e = set_check(d); if (isErr(e)) return e;
+    return dctx_bind(d);
+}
+// the second: the table's buffers from entry `from` on, and the event behind an enqueued call
+static size_t prepare_d_buffers(ZSTD_DCtx* d, const BufNeeds& needs, int from)
+{
+    if (!needs.ensure(d, from)) { (void)hipGetLastError(); return ZERR(kErrMemoryAllocation); }
+    if (!d->asyncEv && hipEventCreateWithFlags(&d->asyncEv, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); d->asyncEv = nullptr; return ZERR(kErrMemoryAllocation); }
+    return 0;
 }
 static size_t prepare_batch_async_d_impl(ZSTD_DCtx* d, const ZSTDMI_DBatchLimits* limits)
 {
     if (!d || !limits) return ZERR(kErrGeneric);
     dctx_drop_prepares(d);
-    size_t maxEntries; u64 bound; BatchLimitsD lim;
+    size_t maxEntries; u64 bound; BatchLimitsD lim; DecodeDict dd;
     if (!dbatch_limits(limits, maxEntries, bound, lim)) return ZERR(kErrParameterOutOfBound);
-    // what the shared pass does not cover, as far as the host alone can tell (a pending prefix stays pending)
-    if (d->workers.size() > 1 || d->pfx || d->originMode == 2) return ZERR(kErrParameterUnsupported);
-    size_t e = set_check(d); if (isErr(e)) return e;
-    e = dctx_bind(d); if (isErr(e)) return e;
-    e = dctx_sync_dictionary(d); if (isErr(e)) return e;
-    DecodeDict dd = decode_dict(d);
-    e = dctx_sync_slots(d, dd); if (isErr(e)) return e;
-    const DAsyncBytes b = dbatch_bytes(maxEntries, lim);
-    if (!d->batchIn.ensure(b.batchIn) || !d->batchOut.ensure(b.batchOut) || !d->asyncVerdict.ensure(b.verdict) || !d->frames.ensure(b.frames) || !d->blocks.ensure(b.blocks) ||
-        !d->scratch.ensure(b.scratch) || !d->slowFlags.ensure(b.slowFlags) || !d->blockKeys.ensure(b.blockKeys) || !d->litRooms.ensure(b.litRooms) || !d->recs.ensure(b.recs) ||
-        !d->status.ensure(b.status)) { (void)hipGetLastError(); return ZERR(kErrMemoryAllocation); }
-    if (!d->asyncEv && hipEventCreateWithFlags(&d->asyncEv, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); d->asyncEv = nullptr; return ZERR(kErrMemoryAllocation); }
-    d->asyncPrep = new DAsyncPrep{ dctx_gen(d), maxEntries, bound, lim, lim.content + (u64)lim.frames * kLitSkew + 256 };
+    size_t e = prepare_d_enter(d); if (isErr(e)) return e;
+    e = call_dict(d, dd); if (isErr(e)) return e;
+    e = prepare_d_buffers(d, dbatch_needs(maxEntries, lim), 0); if (isErr(e)) return e;
+    d->asyncPrep = new DAsyncPrep{ { dctx_gen(d), lim }, maxEntries, bound };
     return 0;
 }
+// this prepare still holds for the context as it stands: nothing dctx_gen() covers moved, and neither the dictionary nor the slot table waits for an upload
+static bool prep_valid(const ZSTD_DCtx* d, const DPrepCore* P)
+{
+    return P && P->gen == dctx_gen(d) && d->deviceOk && !(d->dictDirty && !ddict_shared(d)) && !(set_active(d) && d->slotGen != d->setGen);
+}
+// an enqueued call's stage timer: off for the length of the call (stage events belong to calls that wait for them)
+struct TimerOff { StageTimer& t; const bool was; explicit TimerOff(StageTimer& timer) : t(timer), was(timer.enabled) { t.enabled = false; } ~TimerOff() { t.enabled = was; } };
 // The decode core of an enqueued call, shared by ZSTDMI_decompressBatchAsync and ZSTDMI_decompressRangesAsync: decode_entries between
 // its table upload and its read-back, kernels only (and one hipMemsetAsync over the block keys), over nE rows of d->batchIn whose
 // sources and destinations are offsets from kAsyncBase.  `plan` enqueues whatever fills those rows (-> false: failed); it runs behind
 // the init kernel, where the batch's plan kernel has always run.  Behind the core, d->batchOut holds every row's answer.
-static size_t decode_core_d(ZSTD_DCtx* d, const DecodeDict& dd, const BatchLimitsD& lim, u64 dumpOff, u32 nE, const std::function<bool()>& plan)
+static size_t decode_core_d(ZSTD_DCtx* d, const DecodeDict& dd, const BatchLimitsD& lim, u32 nE, const std::function<bool()>& plan)
 {
     hipStream_t s = d->stream;
+    const u64 dumpOff = lists_layout(lim.frames, lim.blocks, lim.content, true).dumpOff;
     BatchEntryIn* const dIn = (BatchEntryIn*)d->batchIn.p; BatchEntryOut* const dOut = (BatchEntryOut*)d->batchOut.p;
     FrameDesc* const frames = (FrameDesc*)d->frames.p; BlockDesc* const blocks = (BlockDesc*)d->blocks.p; SeqRec* const recs = (SeqRec*)d->recs.p;
     u32* const status = (u32*)d->status.p; u64* const keys = (u64*)d->blockKeys.p; u64* const rooms = (u64*)d->litRooms.p;
@@ -794,17 +821,16 @@ static size_t decode_core_d(ZSTD_DCtx* d, const DecodeDict& dd, const BatchLimit
     if (!plan()) { (void)hipGetLastError(); return ZERR(kErrGeneric); }
     if (hipMemsetAsync(keys, 0xFF, (size_t)lim.blocks * sizeof(u64), s) != hipSuccess) { (void)hipGetLastError(); return ZERR(kErrGeneric); }
     // (frames without a content size always take the shared pass: there is no single-call path to hand them to)
-    launch_batch_walk_count(srcBase, dIn, dOut, nE, dd.dictID, kBatchAloneAbove, status, s, dd.slots, dd.nSet, true, true);
-    launch_batch_walk_emit(srcBase, dIn, dOut, nE, frames, blocks, s, dd.slots, dd.nSet, rooms);
-    launch_block_prepass_d(srcBase, frames, blocks, lim.frames, lim.blocks, dd.fmt ? 1u : 0u, status, s, dd.slots);
-    launch_seq_decode_d(srcBase, frames, blocks, lim.blocks, recs, status, dd.dictFull, dd.dinfo, dd.seqTabs, s, dd.slots);
-    launch_block_offsets_d(frames, blocks, lim.frames, dd.dinfo, status, s, dd.slots);
+    launch_batch_walk_count(srcBase, dIn, dOut, nE, dd, kBatchAloneAbove, status, s, true, true);
+    launch_batch_walk_emit(srcBase, dIn, dOut, nE, frames, blocks, s, dd, rooms);
+    launch_block_prepass_d(srcBase, frames, blocks, lim.frames, lim.blocks, dd, status, s);
+    launch_seq_decode_d(srcBase, frames, blocks, lim.blocks, recs, status, dd, s);
+    launch_block_offsets_d(frames, blocks, lim.frames, dd, status, s);
     launch_batch_rescan(dIn, dOut, nE, frames, s);
-    launch_decode_literals_d(srcBase, dstBase, scratch, frames, blocks, lim.blocks, status, slowFlags, d->litDecoder, dd.dictFull, dd.dinfo, s, dd.slots);
+    launch_decode_literals_d(srcBase, dstBase, scratch, frames, blocks, lim.blocks, status, slowFlags, d->litDecoder, dd, s);
     launch_place_literals_d(srcBase, dstBase, scratch, frames, blocks, lim.blocks, recs, status, s);
     // (every long frame takes the ordered walk; its waves per frame by the setter, else by the limit for the frames)
-    const int execWaves = d->execWaves ? d->execWaves : lim.frames <= 256 ? 16 : lim.frames <= 512 ? 8 : lim.frames <= 1024 ? 4 : lim.frames <= 2048 ? 2 : 1;
-    launch_exec_matches_d(srcBase, dstBase, frames, blocks, lim.frames, recs, status, dd.dictContent, dd.dictContentSize, s, execWaves, dd.slots);
+    launch_exec_matches_d(srcBase, dstBase, frames, blocks, lim.frames, recs, status, dd, s, exec_waves_for(d, lim.frames));
     launch_batch_fold(dOut, nE, keys, s);
     return 0;
 }
@@ -825,16 +851,15 @@ static size_t decompress_batch_async_impl(ZSTD_DCtx* d, const void* const* d_src
     if (n == 0) return 0;
     if (!d_srcs || !d_srcSizes || !d_dsts || !d_dstCapacities || !d_dstSizes) return ZERR(kErrGeneric);
     const DAsyncPrep* const P = d->asyncPrep;
-    if (!P || P->gen != dctx_gen(d) || n > P->maxEntries || !d->deviceOk || (d->dictDirty && !ddict_shared(d)) || (set_active(d) && d->slotGen != d->setGen)) return ZERR(kErrStageWrong);
+    if (!prep_valid(d, P) || n > P->maxEntries) return ZERR(kErrStageWrong);
     size_t e = dctx_bind(d); if (isErr(e)) return e;
-    struct TimerOff { StageTimer& t; bool was; ~TimerOff() { t.enabled = was; } } timerOff{d->timer, d->timer.enabled};
-    d->timer.enabled = false;       // (stage events belong to calls that wait for them)
+    const TimerOff timerOff(d->timer);
     hipStream_t s = d->stream;
-    DecodeDict dd = decode_dict(d);
-    e = dctx_sync_slots(d, dd); if (isErr(e)) return e;       // (the table is current: nothing is uploaded)
+    DecodeDict dd;
+    e = call_dict(d, dd); if (isErr(e)) return e;       // (prep_valid: the dictionary and the table are current, nothing is uploaded)
     const u32 nE = (u32)n;
     u32* const verdict = (u32*)d->asyncVerdict.p;
-    e = decode_core_d(d, dd, P->lim, P->dumpOff, nE, [&]() -> bool {
+    e = decode_core_d(d, dd, P->lim, nE, [&]() -> bool {
         launch_batch_plan_d(d_srcs, d_srcSizes, d_dsts, d_dstCapacities, nE, P->bound, (BatchEntryIn*)d->batchIn.p, verdict, s);
         return true;
     });
@@ -876,8 +901,9 @@ static size_t read_seek_footer(ZSTD_DCtx* d, const void* src, size_t srcSize, bo
     if (tableBytes > srcSize) return ZERR(kErrCorruption);
     return 0;
 }
-// what a call on a seekable stream begins with: the footer, the dictionary, a host source's table staged (its bytes counted in *staged)
-static size_t open_seek_table(ZSTD_DCtx* d, const void* src, size_t srcSize, SeekTable* t, long long* staged)
+// what a call on a seekable stream begins with: the footer first, then the dictionary, a host source's table staged (its bytes counted
+// in *staged), and the call's DecodeDict with the slot table behind it
+static size_t open_seek_table(ZSTD_DCtx* d, const void* src, size_t srcSize, SeekTable* t, long long* staged, DecodeDict& dd)
 {
     t->srcDev = is_device_ptr(src);
     size_t e = read_seek_footer(d, src, srcSize, t->srcDev, t->n, t->stride, t->tableBytes); if (isErr(e)) return e;
@@ -888,7 +914,8 @@ static size_t open_seek_table(ZSTD_DCtx* d, const void* src, size_t srcSize, See
         if (hipMemcpyAsync(d->seekTab.p, t->tab, (size_t)t->tableBytes, hipMemcpyHostToDevice, d->stream) != hipSuccess) return ZERR(kErrGeneric);
         t->tab = (const u8*)d->seekTab.p; *staged += (long long)t->tableBytes;
     }
-    return 0;
+    dd = decode_dict(d);
+    return dctx_sync_slots(d, dd);
 }
 // what a range returns of a stream of `total` bytes of content when nothing fails
 static u64 range_returned(u64 offset, u64 length, u64 total) { return offset < total ? (length < total - offset ? length : total - offset) : 0; }
@@ -909,11 +936,9 @@ static size_t decompress_range_impl(ZSTD_DCtx* d, void* dst, size_t dstCapacity,
     d->lastRangeFrames = 0; d->lastRangeStaged = 0; d->lastBatchWs = 0;
     hipStream_t s = d->stream;
     const bool dstDev = dst ? is_device_ptr(dst) : false;
-    SeekTable t;
-    e = open_seek_table(d, src, srcSize, &t, &d->lastRangeStaged); if (isErr(e)) return e;
+    SeekTable t; DecodeDict dd;
+    e = open_seek_table(d, src, srcSize, &t, &d->lastRangeStaged, dd); if (isErr(e)) return e;
     const bool srcDev = t.srcDev;
-    DecodeDict dd = decode_dict(d);
-    e = dctx_sync_slots(d, dd); if (isErr(e)) return e;
     if (!d->seekSum.ensure(kSeekWords * sizeof(u64))) return ZERR(kErrMemoryAllocation);
     u64* const sum = (u64*)d->seekSum.p;
     d->timer.begin(s);
@@ -1005,11 +1030,9 @@ static size_t decompress_ranges_impl(ZSTD_DCtx* d, const void* src, size_t srcSi
     e = set_check(d); if (isErr(e)) return e;
     d->lastRangesFrames = 0; d->lastRangesAlone = 0; d->lastRangesStaged = 0; d->lastBatchWs = 0;
     hipStream_t s = d->stream;
-    SeekTable t;
-    e = open_seek_table(d, src, srcSize, &t, &d->lastRangesStaged); if (isErr(e)) return e;
+    SeekTable t; DecodeDict dd;
+    e = open_seek_table(d, src, srcSize, &t, &d->lastRangesStaged, dd); if (isErr(e)) return e;
     const bool srcDev = t.srcDev; const u32 N = t.n;
-    DecodeDict dd = decode_dict(d);
-    e = dctx_sync_slots(d, dd); if (isErr(e)) return e;
     const u32 nR = (u32)n;
     if (!d->rangesWs.ensure(ranges_ws_bytes(N)) || !d->batchIn.ensure((size_t)N * sizeof(BatchEntryIn) + 64) ||
         !d->rangesIn.ensure(n * sizeof(RangeIn)) || !d->rangesRec.ensure(n * sizeof(RangeRec)) || !d->rangesRes.ensure(n * sizeof(u64))) return ZERR(kErrMemoryAllocation);
@@ -1089,76 +1112,51 @@ static size_t decompress_ranges_impl(ZSTD_DCtx* d, const void* src, size_t srcSi
 // and the decode core's buffers from the caller's limits; a call is the per-call reset of the marks, the select over the caller's
 // device arrays, the plan over N entries (a host constant now), the decode core above over min(N, maxFrames) rows, and the gather over
 // a grid sized from maxRangeBytes, which writes the caller's sizes column.
-// the limits with their defaults filled in for a table of tableEntries entries -> false: a zero where none is allowed, a range
-// bound above what the gather serves, or a limit beyond the lists' index range (dbatch_limits' range)
+// the ranges' own limits for a table of tableEntries entries, and the rows of the decode core's table -> false: a zero where none is
+// allowed, a range bound above what the gather serves, a table beyond the format's, or dcore_limits' rule
 static bool dranges_limits(const ZSTDMI_DRangesLimits* L, u64 tableEntries, BatchLimitsD& lim, u32& nRows)
 {
-    if (!L->maxRanges || L->maxRanges > 0xFFFFFFF0ull || !L->maxRangeBytes || L->maxRangeBytes > kRangesAloneAbove || !L->maxContent || L->maxContent > ((u64)1 << 48)) return false;
-    if (tableEntries > ((u64)1 << 27)) return false;
-    u64 frames = L->maxFrames ? L->maxFrames : tableEntries;
-    if (!frames) frames = 1;            // (an empty table: the core still runs, over one empty row)
-    if (frames > ((u64)1 << 26)) return false;
-    const u64 blocks = L->maxBlocks ? L->maxBlocks : frames + L->maxContent / 16384;
-    if (blocks > 0xFFFFFFF0ull) return false;
-    const u64 seqs = L->maxSequences ? L->maxSequences : L->maxContent / 3 + 64;
-    if (seqs > ((u64)1 << 48)) return false;
-    lim.frames = (u32)frames; lim.blocks = (u32)blocks; lim.content = L->maxContent; lim.sequences = seqs;
-    nRows = (u32)(tableEntries < frames ? tableEntries : frames);
-    if (!nRows) nRows = 1;
+    if (!L->maxRanges || L->maxRanges > 0xFFFFFFF0ull || !L->maxRangeBytes || L->maxRangeBytes > kRangesAloneAbove || tableEntries > ((u64)1 << 27)) return false;
+    // (an empty table: the core still runs, over one empty row)
+    if (!dcore_limits(L->maxFrames, L->maxBlocks, L->maxSequences, L->maxContent, tableEntries ? tableEntries : 1, lim)) return false;
+    nRows = !tableEntries ? 1u : (u32)(tableEntries < lim.frames ? tableEntries : lim.frames);
     return true;
 }
-// the buffers of a call at the limits: the index, the ranges' rows, the arena, and the decode core's (two verdict rows behind its table)
-struct DRangesBytes { size_t index, rangesIn, rangesRec, arena; DAsyncBytes core; };
-static DRangesBytes dranges_bytes(size_t maxRanges, u32 tableEntries, u32 nRows, const BatchLimitsD& lim)
+// the buffers of a call at the limits: the index (first: seek_index runs into it before the others are asked for), the ranges' rows, the
+// arena, and the decode core's with two verdict rows behind its table and no verdict column
+static BufNeeds dranges_needs(size_t maxRanges, u32 tableEntries, u32 nRows, const BatchLimitsD& lim)
 {
-    DRangesBytes b;
-    b.index = ranges_ws_bytes(tableEntries); b.rangesIn = maxRanges * sizeof(RangeIn); b.rangesRec = maxRanges * sizeof(RangeRec);
-    b.arena = (size_t)lim.content + 64;
-    b.core = dbatch_bytes(nRows, lim);
-    b.core.batchOut += 2 * sizeof(BatchEntryOut); b.core.verdict = 0;
-    return b;
+    typedef ZSTD_DCtx_s D;
+    BufNeeds t;
+    t.add(&D::rangesAsyncWs, ranges_ws_bytes(tableEntries)); t.add(&D::rangesIn, maxRanges * sizeof(RangeIn)); t.add(&D::rangesRec, maxRanges * sizeof(RangeRec));
+    t.add(&D::arena, (size_t)lim.content + 64);
+    dcore_needs(t, nRows, (size_t)nRows + 2, 0, lim);
+    return t;
 }
 static size_t prepare_ranges_async_impl(ZSTD_DCtx* d, const void* d_src, size_t srcSize, const ZSTDMI_DRangesLimits* limits)
 {
     if (!d || !limits) return ZERR(kErrGeneric);
     dctx_drop_prepares(d);
-    BatchLimitsD lim; u32 nRows;
+    BatchLimitsD lim; u32 nRows; DecodeDict dd;
     if (!dranges_limits(limits, 0, lim, nRows)) return ZERR(kErrParameterOutOfBound);
-    // what the pass does not cover, as far as the host alone can tell (a pending prefix stays pending)
-    if (d->workers.size() > 1 || d->pfx || d->originMode == 2) return ZERR(kErrParameterUnsupported);
-    size_t e = set_check(d); if (isErr(e)) return e;
-    e = dctx_bind(d); if (isErr(e)) return e;
+    size_t e = prepare_d_enter(d); if (isErr(e)) return e;
     if (d_src && !is_device_ptr(d_src)) return ZERR(kErrParameterUnsupported);
     hipStream_t s = d->stream;
     u32 N, stride; u64 tableBytes;
     e = read_seek_footer(d, d_src, srcSize, true, N, stride, tableBytes); if (isErr(e)) return e;
-    e = dctx_sync_dictionary(d); if (isErr(e)) return e;
-    DecodeDict dd = decode_dict(d);
-    e = dctx_sync_slots(d, dd); if (isErr(e)) return e;
+    e = call_dict(d, dd); if (isErr(e)) return e;
     if (!dranges_limits(limits, N, lim, nRows)) return ZERR(kErrParameterOutOfBound);      // (maxFrames 0 = N: known only now)
-    const DRangesBytes b = dranges_bytes(limits->maxRanges, N, nRows, lim);
-    if (!d->rangesAsyncWs.ensure(b.index)) { (void)hipGetLastError(); return ZERR(kErrMemoryAllocation); }
+    const BufNeeds needs = dranges_needs(limits->maxRanges, N, nRows, lim);
+    if (!d->rangesAsyncWs.ensure(needs.e[0].bytes)) { (void)hipGetLastError(); return ZERR(kErrMemoryAllocation); }
     const RangesWs ws = ranges_ws((u8*)d->rangesAsyncWs.p, N);
     const u8* const tab = (const u8*)d_src + (srcSize - tableBytes);
     launch_seek_index(tab, tableBytes, N, stride, srcSize, ws, s);
     u64 sm[kRgWords] = {};
     e = dev_read(sm, ws.sum, sizeof sm, s); if (isErr(e)) return e;
     if (sm[kRgErr]) return ZERR((u32)sm[kRgErr]);
-    if (!d->rangesIn.ensure(b.rangesIn) || !d->rangesRec.ensure(b.rangesRec) || !d->arena.ensure(b.arena) || !d->batchIn.ensure(b.core.batchIn) ||
-        !d->batchOut.ensure(b.core.batchOut) || !d->frames.ensure(b.core.frames) || !d->blocks.ensure(b.core.blocks) || !d->scratch.ensure(b.core.scratch) ||
-        !d->slowFlags.ensure(b.core.slowFlags) || !d->blockKeys.ensure(b.core.blockKeys) || !d->litRooms.ensure(b.core.litRooms) || !d->recs.ensure(b.core.recs) ||
-        !d->status.ensure(b.core.status)) { (void)hipGetLastError(); return ZERR(kErrMemoryAllocation); }
-    if (!d->asyncEv && hipEventCreateWithFlags(&d->asyncEv, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); d->asyncEv = nullptr; return ZERR(kErrMemoryAllocation); }
-    d->rangesPrep = new DRangesPrep{ dctx_gen(d), limits->maxRanges, limits->maxRangeBytes, lim, lim.content + (u64)lim.frames * kLitSkew + 256,
-                                     (const u8*)d_src, tab, N, stride, sm[kRgTotal], nRows };
+    e = prepare_d_buffers(d, needs, 1); if (isErr(e)) return e;
+    d->rangesPrep = new DRangesPrep{ { dctx_gen(d), lim }, limits->maxRanges, limits->maxRangeBytes, (const u8*)d_src, tab, N, stride, sm[kRgTotal], nRows };
     return 0;
-}
-// the prepare that is valid now, or null
-static const DRangesPrep* ranges_prep(const ZSTD_DCtx* d)
-{
-    const DRangesPrep* const P = d->rangesPrep;
-    if (!P || P->gen != dctx_gen(d) || !d->deviceOk || (d->dictDirty && !ddict_shared(d)) || (set_active(d) && d->slotGen != d->setGen)) return nullptr;
-    return P;
 }
 static size_t decompress_ranges_async_impl(ZSTD_DCtx* d, const unsigned long long* d_offsets, const size_t* d_lengths, size_t n, void* const* d_dsts,
                                            const size_t* d_dstCapacities, size_t* d_dstSizes)
@@ -1166,18 +1164,17 @@ static size_t decompress_ranges_async_impl(ZSTD_DCtx* d, const unsigned long lon
     if (!d) return ZERR(kErrGeneric);
     if (n == 0) return 0;
     if (!d_offsets || !d_lengths || !d_dsts || !d_dstCapacities || !d_dstSizes) return ZERR(kErrGeneric);
-    const DRangesPrep* const P = ranges_prep(d);
-    if (!P || n > P->maxRanges) return ZERR(kErrStageWrong);
+    const DRangesPrep* const P = d->rangesPrep;
+    if (!prep_valid(d, P) || n > P->maxRanges) return ZERR(kErrStageWrong);
     size_t e = dctx_bind(d); if (isErr(e)) return e;
-    struct TimerOff { StageTimer& t; bool was; ~TimerOff() { t.enabled = was; } } timerOff{d->timer, d->timer.enabled};
-    d->timer.enabled = false;       // (stage events belong to calls that wait for them)
+    const TimerOff timerOff(d->timer);
     hipStream_t s = d->stream;
-    DecodeDict dd = decode_dict(d);
-    e = dctx_sync_slots(d, dd); if (isErr(e)) return e;       // (the table is current: nothing is uploaded)
+    DecodeDict dd;
+    e = call_dict(d, dd); if (isErr(e)) return e;       // (prep_valid: the dictionary and the table are current, nothing is uploaded)
     const u32 nR = (u32)n, N = P->n;
     const RangesWs ws = ranges_ws((u8*)d->rangesAsyncWs.p, N);
     RangeIn* const dRanges = (RangeIn*)d->rangesIn.p; RangeRec* const dRecs = (RangeRec*)d->rangesRec.p;
-    e = decode_core_d(d, dd, P->lim, P->dumpOff, P->nRows, [&]() -> bool {
+    e = decode_core_d(d, dd, P->lim, P->nRows, [&]() -> bool {
         // the index persists from the prepare, the marks and the plan's summary are this call's
         if (hipMemsetAsync(ws.diff, 0, ((size_t)N + 1) * sizeof(u32), s) != hipSuccess ||
             hipMemsetAsync(ws.sum + kRgTouched, 0, (kRgWords - kRgTouched) * sizeof(u64), s) != hipSuccess) return false;
@@ -1447,15 +1444,15 @@ static size_t decode_fragment(ZSTD_DCtx* d, u8* d_dst, size_t dstCapacity, const
     { const size_t e = status_reset(d); if (isErr(e)) return e; }
     u32 st[kStWords] = {};
     // (the exact serial walk: one frame, and it checks the dictID the fragment's header repeats)
-    launch_frame_walk_serial(d_src, srcSize, nullptr, nullptr, 1, status, dd.dictID, 0, s);
+    launch_frame_walk_serial(d_src, srcSize, nullptr, nullptr, 1, status, dd, 0, s);
     { const size_t e = status_read(d, st); if (isErr(e)) return e; }
     if (st[kStErr]) return ZERR(st[kStErr]);
     const u32 nFrames = st[kStFrames], nBlocks = st[kStBlocks];
     const u64 total = st_u64(st, kStTotalLo, kStTotalHi);
     if (nFrames != 1 || nBlocks <= phantoms || total > dstCapacity) return ZERR(kErrGeneric);       // (the host built it otherwise)
-    if (!ensure_lists(d, nFrames, nBlocks, total)) return ZERR(kErrMemoryAllocation);
+    if (!ensure_lists(d, lists_layout(nFrames, nBlocks, total, false))) return ZERR(kErrMemoryAllocation);
     FrameDesc* frames = (FrameDesc*)d->frames.p; BlockDesc* blocks = (BlockDesc*)d->blocks.p;
-    launch_frame_walk_serial(d_src, srcSize, frames, blocks, 1, status, dd.dictID, 1, s);
+    launch_frame_walk_serial(d_src, srcSize, frames, blocks, 1, status, dd, 1, s);
     d->timer.mark("frame_walk", s);
     const StreamLink link = { phantoms, g.first ? nullptr : (const DictInfo*)d->segReps.p };
     { const size_t e = decode_lists(d, dd, d_dst, d_src, nFrames, nBlocks, 1, dstCapacity, st, [&]() -> bool {
@@ -1464,8 +1461,7 @@ static size_t decode_fragment(ZSTD_DCtx* d, u8* d_dst, size_t dstCapacity, const
       }, &link);
       if (isErr(e)) return e; }
     d->timer.finish();
-    if (st[kStErrKeyLo] != 0xFFFFFFFFu || st[kStErrKeyHi] != 0xFFFFFFFFu) return ZERR(st[kStErrKeyLo] & 0xFFFFu);
-    if (st[kStErr]) return ZERR(st[kStErr]);
+    { const size_t e = status_error(st); if (isErr(e)) return e; }
     return (size_t)st_u64(st, kStActualLo, kStActualHi);
 }
 
@@ -1848,9 +1844,7 @@ size_t ZSTDMI_decompressBatch(ZSTD_DCtx* d, const void* const* srcs, const size_
 size_t ZSTDMI_batchAsyncWorkspaceD(const ZSTDMI_DBatchLimits* limits)
 {
     size_t maxEntries; u64 bound; BatchLimitsD lim;
-    if (!limits || !dbatch_limits(limits, maxEntries, bound, lim)) return 0;
-    const DAsyncBytes b = dbatch_bytes(maxEntries, lim);
-    return b.batchIn + b.batchOut + b.verdict + b.frames + b.blocks + b.scratch + b.slowFlags + b.blockKeys + b.litRooms + b.recs + b.status;
+    return limits && dbatch_limits(limits, maxEntries, bound, lim) ? dbatch_needs(maxEntries, lim).sum() : 0;
 }
 size_t ZSTDMI_DCtx_prepareBatchAsync(ZSTD_DCtx* d, const ZSTDMI_DBatchLimits* limits) { return guarded([&] { return prepare_batch_async_d_impl(d, limits); }); }
 size_t ZSTDMI_decompressBatchAsync(ZSTD_DCtx* d, const void* const* d_srcs, const size_t* d_srcSizes, size_t n, void* const* d_dsts, const size_t* d_dstCapacities, size_t* d_dstSizes)
@@ -1877,10 +1871,7 @@ size_t ZSTDMI_decompressRanges(ZSTD_DCtx* d, const void* src, size_t srcSize, co
 size_t ZSTDMI_rangesAsyncWorkspaceD(const ZSTDMI_DRangesLimits* limits, size_t tableEntries)
 {
     BatchLimitsD lim; u32 nRows;
-    if (!limits || !dranges_limits(limits, tableEntries, lim, nRows)) return 0;
-    const DRangesBytes b = dranges_bytes(limits->maxRanges, (u32)tableEntries, nRows, lim);
-    return b.index + b.rangesIn + b.rangesRec + b.arena + b.core.batchIn + b.core.batchOut + b.core.frames + b.core.blocks + b.core.scratch + b.core.slowFlags +
-           b.core.blockKeys + b.core.litRooms + b.core.recs + b.core.status;
+    return limits && dranges_limits(limits, tableEntries, lim, nRows) ? dranges_needs(limits->maxRanges, (u32)tableEntries, nRows, lim).sum() : 0;
 }
 size_t ZSTDMI_DCtx_prepareRangesAsync(ZSTD_DCtx* d, const void* d_src, size_t srcSize, const ZSTDMI_DRangesLimits* limits)
 {
@@ -1889,8 +1880,8 @@ size_t ZSTDMI_DCtx_prepareRangesAsync(ZSTD_DCtx* d, const void* d_src, size_t sr
 size_t ZSTDMI_DCtx_getRangesAsyncPlan(const ZSTD_DCtx* d, size_t* tableEntries, unsigned long long* totalContent)
 {
     if (!d) return ZERR(kErrGeneric);
-    const DRangesPrep* const P = ranges_prep(d);
-    if (!P) return ZERR(kErrStageWrong);
+    const DRangesPrep* const P = d->rangesPrep;
+    if (!prep_valid(d, P)) return ZERR(kErrStageWrong);
     if (tableEntries) *tableEntries = P->n;
     if (totalContent) *totalContent = P->total;
     return 0;
