@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 import datagen
+import forge_cases
 import zstd_forge as forge
 import zstdsharp_amd as z
 from zstdsharp_amd.batch import compress_batch_async, decompress_batch_async
@@ -430,6 +431,63 @@ def test_dictionaries(gpu_lib, setup):
     assert want == data
     with prepared(32, 4096, 1 << 16, setup=configure) as d:
         lay = DLayout(blobs, caps)
+        assert_same(lay.run_async(d), want)
+        lay.assert_canaries()
+    for dd in keep:
+        dd.Dispose()
+
+
+def first_block_literals(blob):
+    """-> the literals-section type (2: Huffman with a tree, 3: treeless) of a sized frame's first block; None: not a compressed block"""
+    fhd = blob[4]
+    single, fcs, did = (fhd >> 5) & 1, fhd >> 6, (0, 1, 2, 4)[fhd & 3]
+    at = 5 + (0 if single else 1) + did + ((1 if single else 0) if fcs == 0 else 1 << fcs)
+    bh = int.from_bytes(blob[at:at + 3], "little")
+    return blob[at + 3] & 3 if (bh >> 1) & 3 == 2 else None
+
+
+@functools.lru_cache(maxsize=None)
+def set_mix():
+    """-> (blobs, contents): six frames of 2 .. 4 KiB of text that name two dictionaries in turn, each with Huffman literals and
+    sequences, and in their middle a forged frame of FIVE blocks without a dictID (the current DDict's) — more blocks than a lane of
+    block_link_small takes, so the frame is a wave's of block_link — whose last block repeats its first block's Huffman table"""
+    names = ("trained_16k.dict", "train_default_json.dict")
+    data = [data_of("text", 2000 + 411 * i, 90 + i) for i in range(6)]
+    blobs = [wrap(x, level=3 if i % 2 else 1, dictionary=names[i % 2]) for i, x in enumerate(data)]
+    assert len({z.get_dict_id_from_frame(b) for b in blobs}) == 2
+    assert all(first_block_literals(b) in (2, 3) and frame_counts(b)[3] > 0 for b in blobs)
+    five, content = next(c[2] for c in forge_cases.CASES if c[0] == "huf_treeless_gap_s4")()
+    assert frame_counts(five)[1] == 5
+    return tuple(blobs[:3] + [five] + blobs[3:]), tuple(data[:3] + [content] + data[3:])
+
+
+@functools.lru_cache(maxsize=None)
+def set_mix_expected():
+    blobs, content = set_mix()
+    keep = [z.DDict(golden_bytes(n)) for n in ("trained_16k.dict", "train_default_json.dict")]
+    with sync_context(lambda d: _ref_set(d, keep)) as d:
+        want = DLayout(blobs, [len(x) for x in content], seed=7).run_sync(d)
+    for dd in keep:
+        dd.Dispose()
+    assert want == list(content)
+    return tuple(want)
+
+
+def _ref_set(d, ddicts):
+    d.SetParameter(z.ZSTD_d_refMultipleDDicts, 1)
+    for dd in ddicts:
+        d.RefDDict(dd)
+
+
+@pytest.mark.parametrize("lit", [1, 2, 3])
+def test_a_ddict_set_under_every_literal_decoder(gpu_lib, lit):
+    """the set instances that take their counts from the status words, each literal decoder forced: what the synchronous batch gives,
+    which is the data (and, for the forged frame, what zstd_forge's own executor regenerates)"""
+    blobs, content = set_mix()
+    want = set_mix_expected()
+    keep = [z.DDict(golden_bytes(n)) for n in ("trained_16k.dict", "train_default_json.dict")]
+    with prepared(8, 4096, 1 << 16, setup=lambda d: _ref_set(d, keep), lit=lit) as d:
+        lay = DLayout(blobs, [len(x) for x in content])
         assert_same(lay.run_async(d), want)
         lay.assert_canaries()
     for dd in keep:

@@ -418,14 +418,17 @@ def test_ddict_set(gpu_lib):
     blobs = [widen(b) if i % 2 else b for i, b in enumerate(blobs)]
     expect = list(records)
     blobs[13] = unsized_frames(records[13], dictionary="train_default_zipf.dict"); expect[13] = WRONG_DICT
-    caps = [len(r) for r in records]
+    # a forged frame of five blocks without a dictID (the current DDict's): more blocks than frames, so block_link's set instance runs too
+    five, five_content = next(c[2] for c in forge_cases.CASES if c[0] == "huf_treeless_gap_s4")()
+    blobs.append(five); expect.append(five_content)
+    caps = [len(r) for r in records] + [len(five_content)]
     dds = [z.DDict(dic(name)) for name in SET_DICTS]
     ref = context(gpu_lib, ddict_set=dds)
     want = single_decodes(gpu_lib, ref.dctx, blobs, caps)
     d = context(gpu_lib, ddict_set=dds)
     b = Batch(gpu_lib, blobs, caps, seed=23)
     assert b.run(d.dctx) == 0
-    for i in range(30):
+    for i in range(31):
         assert b.result(i) == want[i] == expect[i], i
     b.assert_guards_untouched()
     assert gpu_lib.ZSTDMI_debugLastBatchAloneD(d.dctx) == 0

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import datagen
+import forge_cases
 import oracle_lib
 import zstdsharp_amd as z
 from zstdsharp_amd.errors import ZSTD_ErrorCode, get_error_code, is_error
@@ -370,6 +371,19 @@ def test_using_ddict_ignores_the_set(gpu_lib, ddicts):
         assert d.GetParameter(z.ZSTD_d_refMultipleDDicts) == 1
         assert raw_call(gpu_lib, d, fa + fb, len(da) + len(db)) == (len(da) + len(db), da + db), "the set is as it was found"
         assert gpu_lib.ZSTDMI_debugLastSetFrames(d.dctx) == 2
+        d.RefDDict(None)
+
+
+def test_a_frame_of_five_blocks_between_set_frames(gpu_lib, ddicts):
+    """more blocks than a lane of block_link_small takes: block_link's set instance links them.  The frame is forged, has no dictID (the
+    current DDict's) and repeats its first block's Huffman table in its last; its content is what zstd_forge's own executor regenerates"""
+    five, content = next(c[2] for c in forge_cases.CASES if c[0] == "huf_treeless_gap_s4")()
+    data, frame, k = records()[0]
+    with set_context([ddicts[FIVE[k]], ddicts[FIVE[(k + 1) % 5]]]) as d:
+        stream, expect = frame + five + frame, data + content + data
+        assert raw_call(gpu_lib, d, stream, len(expect)) == (len(expect), expect)
+        assert gpu_lib.ZSTDMI_debugLastSetFrames(d.dctx) == 2
+        assert batch_raw(gpu_lib, d, [frame, five, frame], [len(data), len(content), len(data)]) == [(len(data), data), (len(content), content), (len(data), data)]
         d.RefDDict(None)
 
 

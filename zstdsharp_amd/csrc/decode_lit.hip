@@ -223,18 +223,17 @@ __device__ __forceinline__ void decode_literals_slow_body(const u8* __restrict__
     } while (false);
     if (err && lane == 0) report_error(status, bi, kStageLiterals, err);
 }
+// (the entry point of the four literal kernels: modes as template parameters, zmi_decode.h.  kSet reads slots and gets nulls for the one
+// dictionary; kDev — ZSTDMI_decompressBatchAsync — takes the number of blocks from the status words over a grid of the caller's limit:
+// the workgroups (quads) beyond the call's blocks leave at once, slowFlags is written and read below the call's count only.)
+template <bool kSet, bool kDev>
 __global__ __launch_bounds__(64) void decode_literals_slow_kernel(const u8* __restrict__ src, u8* __restrict__ out, u8* __restrict__ scratch,
                                                                   const FrameDesc* __restrict__ frames, const BlockDesc* __restrict__ blocks, u32 nBlocks,
                                                                   u32* __restrict__ status, const u8* __restrict__ slowFlags, const u8* __restrict__ dictFull,
-                                                                  const DictInfo* __restrict__ di)
+                                                                  const DictInfo* __restrict__ di, const DictSlot* __restrict__ slots)
 {
-    decode_literals_slow_body<false>(src, out, scratch, frames, blocks, nBlocks, status, slowFlags, dictFull, di, nullptr);
-}
-__global__ __launch_bounds__(64) void decode_literals_slow_set_kernel(const u8* __restrict__ src, u8* __restrict__ out, u8* __restrict__ scratch,
-                                                                      const FrameDesc* __restrict__ frames, const BlockDesc* __restrict__ blocks, u32 nBlocks,
-                                                                      u32* __restrict__ status, const u8* __restrict__ slowFlags, const DictSlot* __restrict__ slots)
-{
-    decode_literals_slow_body<true>(src, out, scratch, frames, blocks, nBlocks, status, slowFlags, nullptr, nullptr, slots);
+    decode_literals_slow_body<kSet>(src, out, scratch, frames, blocks, list_count<kDev>(nBlocks, status, kStBlocks), status, slowFlags,
+                                    kSet ? nullptr : dictFull, kSet ? nullptr : di, kSet ? slots : nullptr);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -593,18 +592,14 @@ __device__ __forceinline__ void decode_literals_compact_body(const u8* __restric
         else if (err) report_error(status, bi, kStageLiterals, err);
     }
 }
+template <bool kSet, bool kDev>
 __global__ __launch_bounds__(64) void decode_literals_compact_kernel(const u8* __restrict__ src, u8* __restrict__ out, u8* __restrict__ scratch,
                                                                      const FrameDesc* __restrict__ frames, const BlockDesc* __restrict__ blocks, u32 nBlocks,
                                                                      u32* __restrict__ status, u8* __restrict__ slowFlags, const u8* __restrict__ dictFull,
-                                                                     const DictInfo* __restrict__ di)
+                                                                     const DictInfo* __restrict__ di, const DictSlot* __restrict__ slots)
 {
-    decode_literals_compact_body<false>(src, out, scratch, frames, blocks, nBlocks, status, slowFlags, dictFull, di, nullptr);
-}
-__global__ __launch_bounds__(64) void decode_literals_compact_set_kernel(const u8* __restrict__ src, u8* __restrict__ out, u8* __restrict__ scratch,
-                                                                         const FrameDesc* __restrict__ frames, const BlockDesc* __restrict__ blocks, u32 nBlocks,
-                                                                         u32* __restrict__ status, u8* __restrict__ slowFlags, const DictSlot* __restrict__ slots)
-{
-    decode_literals_compact_body<true>(src, out, scratch, frames, blocks, nBlocks, status, slowFlags, nullptr, nullptr, slots);
+    decode_literals_compact_body<kSet>(src, out, scratch, frames, blocks, list_count<kDev>(nBlocks, status, kStBlocks), status, slowFlags,
+                                       kSet ? nullptr : dictFull, kSet ? nullptr : di, kSet ? slots : nullptr);
 }
 
 template <bool kSet>
@@ -628,18 +623,14 @@ __device__ __forceinline__ void decode_literals_body(const u8* __restrict__ src,
         else if (err) report_error(status, bi, kStageLiterals, err);
     }
 }
+template <bool kSet, bool kDev>
 __global__ __launch_bounds__(64) void decode_literals_kernel(const u8* __restrict__ src, u8* __restrict__ out, u8* __restrict__ scratch,
                                                              const FrameDesc* __restrict__ frames, const BlockDesc* __restrict__ blocks, u32 nBlocks,
                                                              u32* __restrict__ status, u8* __restrict__ slowFlags, const u8* __restrict__ dictFull,
-                                                             const DictInfo* __restrict__ di)
+                                                             const DictInfo* __restrict__ di, const DictSlot* __restrict__ slots)
 {
-    decode_literals_body<false>(src, out, scratch, frames, blocks, nBlocks, status, slowFlags, dictFull, di, nullptr);
-}
-__global__ __launch_bounds__(64) void decode_literals_set_kernel(const u8* __restrict__ src, u8* __restrict__ out, u8* __restrict__ scratch,
-                                                                 const FrameDesc* __restrict__ frames, const BlockDesc* __restrict__ blocks, u32 nBlocks,
-                                                                 u32* __restrict__ status, u8* __restrict__ slowFlags, const DictSlot* __restrict__ slots)
-{
-    decode_literals_body<true>(src, out, scratch, frames, blocks, nBlocks, status, slowFlags, nullptr, nullptr, slots);
+    decode_literals_body<kSet>(src, out, scratch, frames, blocks, list_count<kDev>(nBlocks, status, kStBlocks), status, slowFlags,
+                               kSet ? nullptr : dictFull, kSet ? nullptr : di, kSet ? slots : nullptr);
 }
 
 // =====================================================================================================================
@@ -935,17 +926,14 @@ __device__ __forceinline__ void decode_literals_sync_body(const u8* __restrict__
     const u32 err = sync_decode_literals(L, J, tid);
     if (err && tid == 0) report_error(status, bi, kStageLiterals, err);
 }
+template <bool kSet, bool kDev>
 __global__ __launch_bounds__(256) void decode_literals_sync_kernel(const u8* __restrict__ src, u8* __restrict__ out, u8* __restrict__ scratch,
                                                                    const FrameDesc* __restrict__ frames, const BlockDesc* __restrict__ blocks, u32 nBlocks,
-                                                                   u32* __restrict__ status, const u8* __restrict__ dictFull, const DictInfo* __restrict__ di)
+                                                                   u32* __restrict__ status, const u8* __restrict__ dictFull, const DictInfo* __restrict__ di,
+                                                                   const DictSlot* __restrict__ slots)
 {
-    decode_literals_sync_body<false>(src, out, scratch, frames, blocks, nBlocks, status, dictFull, di, nullptr);
-}
-__global__ __launch_bounds__(256) void decode_literals_sync_set_kernel(const u8* __restrict__ src, u8* __restrict__ out, u8* __restrict__ scratch,
-                                                                       const FrameDesc* __restrict__ frames, const BlockDesc* __restrict__ blocks, u32 nBlocks,
-                                                                       u32* __restrict__ status, const DictSlot* __restrict__ slots)
-{
-    decode_literals_sync_body<true>(src, out, scratch, frames, blocks, nBlocks, status, nullptr, nullptr, slots);
+    decode_literals_sync_body<kSet>(src, out, scratch, frames, blocks, list_count<kDev>(nBlocks, status, kStBlocks), status,
+                                    kSet ? nullptr : dictFull, kSet ? nullptr : di, kSet ? slots : nullptr);
 }
 
 // Three literal decoders (tools/lit_decoder_crossover.py, MI355X, 64 KiB Zipf frames):
@@ -964,95 +952,39 @@ static u32 literal_decoder_for(u32 nBlocks)
     return tC < tS ? 3u : 1u;
 }
 
-// The four bodies with the number of blocks from the status words (ZSTDMI_decompressBatchAsync): grids over the caller's limit, the
-// workgroups (quads) beyond the call's blocks leave at once.  slowFlags is written and read below the call's count only.
-template <bool kSet>
-__global__ __launch_bounds__(64) void decode_literals_slow_d_kernel(const u8* __restrict__ src, u8* __restrict__ out, u8* __restrict__ scratch,
-                                                                    const FrameDesc* __restrict__ frames, const BlockDesc* __restrict__ blocks,
-                                                                    u32* __restrict__ status, const u8* __restrict__ slowFlags, const u8* __restrict__ dictFull,
-                                                                    const DictInfo* __restrict__ di, const DictSlot* __restrict__ slots)
+// One core for both launchers: `count` is the number of blocks, or — dev, ZSTDMI_decompressBatchAsync — the caller's limit for them, which
+// sizes the grids and, under mode 0, picks the decoder (the only count the host has there); the instances then read the count itself.
+static void launch_literals(const u8* src, u8* out, u8* scratch, const FrameDesc* frames, const BlockDesc* blocks, u32 count, u32* status,
+                            u8* slowFlags, u32 mode, const DecodeDict& dd, bool dev, hipStream_t stream, StageHook hook)
 {
-    decode_literals_slow_body<kSet>(src, out, scratch, frames, blocks, status[kStBlocks], status, slowFlags, dictFull, di, slots);
+    if (mode == 0) mode = literal_decoder_for(count);
+    with_flags([&](auto set, auto d) {
+        if (mode == 2) {
+            // per device, and per instance: a generic lambda's operator() is a template, so each (set, d) has its own function with its
+            // own statics, as each of the former launch sites had its own latch
+            static bool attrSet[64] = {};
+            int device = 0; (void)hipGetDevice(&device);
+            if (!attrSet[device & 63]) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(decode_literals_sync_kernel<set(), d()>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(SyncLds)); attrSet[device & 63] = true; }
+            hipLaunchKernelGGL((decode_literals_sync_kernel<set(), d()>), dim3(count), dim3(256), sizeof(SyncLds), stream, src, out, scratch, frames, blocks, count, status, dd.dictFull, dd.dinfo, dd.slots);
+            hook("decode_literals");
+            return;
+        }
+        if (mode == 3) hipLaunchKernelGGL((decode_literals_compact_kernel<set(), d()>), dim3((count + kQuadsC - 1) / kQuadsC), dim3(64), 0, stream, src, out, scratch, frames, blocks, count, status, slowFlags, dd.dictFull, dd.dinfo, dd.slots);
+        else           hipLaunchKernelGGL((decode_literals_kernel<set(), d()>), dim3((count + kQuads - 1) / kQuads), dim3(64), 0, stream, src, out, scratch, frames, blocks, count, status, slowFlags, dd.dictFull, dd.dinfo, dd.slots);
+        hook("decode_literals");
+        hipLaunchKernelGGL((decode_literals_slow_kernel<set(), d()>), dim3(count), dim3(64), 0, stream, src, out, scratch, frames, blocks, count, status, (const u8*)slowFlags, dd.dictFull, dd.dinfo, dd.slots);
+        hook("decode_literals_slow");
+    }, dd.slots != nullptr, dev);
 }
-template <bool kSet>
-__global__ __launch_bounds__(64) void decode_literals_compact_d_kernel(const u8* __restrict__ src, u8* __restrict__ out, u8* __restrict__ scratch,
-                                                                       const FrameDesc* __restrict__ frames, const BlockDesc* __restrict__ blocks,
-                                                                       u32* __restrict__ status, u8* __restrict__ slowFlags, const u8* __restrict__ dictFull,
-                                                                       const DictInfo* __restrict__ di, const DictSlot* __restrict__ slots)
-{
-    decode_literals_compact_body<kSet>(src, out, scratch, frames, blocks, status[kStBlocks], status, slowFlags, dictFull, di, slots);
-}
-template <bool kSet>
-__global__ __launch_bounds__(64) void decode_literals_d_kernel(const u8* __restrict__ src, u8* __restrict__ out, u8* __restrict__ scratch,
-                                                               const FrameDesc* __restrict__ frames, const BlockDesc* __restrict__ blocks,
-                                                               u32* __restrict__ status, u8* __restrict__ slowFlags, const u8* __restrict__ dictFull,
-                                                               const DictInfo* __restrict__ di, const DictSlot* __restrict__ slots)
-{
-    decode_literals_body<kSet>(src, out, scratch, frames, blocks, status[kStBlocks], status, slowFlags, dictFull, di, slots);
-}
-template <bool kSet>
-__global__ __launch_bounds__(256) void decode_literals_sync_d_kernel(const u8* __restrict__ src, u8* __restrict__ out, u8* __restrict__ scratch,
-                                                                     const FrameDesc* __restrict__ frames, const BlockDesc* __restrict__ blocks,
-                                                                     u32* __restrict__ status, const u8* __restrict__ dictFull, const DictInfo* __restrict__ di,
-                                                                     const DictSlot* __restrict__ slots)
-{
-    decode_literals_sync_body<kSet>(src, out, scratch, frames, blocks, status[kStBlocks], status, dictFull, di, slots);
-}
-template <bool kSet>
-static void launch_decode_literals_dev(const u8* src, u8* out, u8* scratch, const FrameDesc* frames, const BlockDesc* blocks, u32 capBlocks, u32* status,
-                                       u8* slowFlags, u32 mode, const u8* dictFull, const DictInfo* di, hipStream_t stream, const DictSlot* slots)
-{
-    if (mode == 2) {
-        static bool attrSet[64] = {};               // per device
-        int dev = 0; (void)hipGetDevice(&dev);
-        if (!attrSet[dev & 63]) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(decode_literals_sync_d_kernel<kSet>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(SyncLds)); attrSet[dev & 63] = true; }
-        hipLaunchKernelGGL(decode_literals_sync_d_kernel<kSet>, dim3(capBlocks), dim3(256), sizeof(SyncLds), stream, src, out, scratch, frames, blocks, status, dictFull, di, slots);
-        return;
-    }
-    if (mode == 3) hipLaunchKernelGGL(decode_literals_compact_d_kernel<kSet>, dim3((capBlocks + kQuadsC - 1) / kQuadsC), dim3(64), 0, stream, src, out, scratch, frames, blocks, status, slowFlags, dictFull, di, slots);
-    else           hipLaunchKernelGGL(decode_literals_d_kernel<kSet>, dim3((capBlocks + kQuads - 1) / kQuads), dim3(64), 0, stream, src, out, scratch, frames, blocks, status, slowFlags, dictFull, di, slots);
-    hipLaunchKernelGGL(decode_literals_slow_d_kernel<kSet>, dim3(capBlocks), dim3(64), 0, stream, src, out, scratch, frames, blocks, status, (const u8*)slowFlags, dictFull, di, slots);
-}
-// mode 0: by the caller's limit for the blocks — the grid's size, the only count the host has
 void launch_decode_literals_d(const u8* src, u8* out, u8* scratch, const FrameDesc* frames, const BlockDesc* blocks, u32 capBlocks, u32* status,
                               u8* slowFlags, u32 mode, const DecodeDict& dd, hipStream_t stream)
 {
-    if (mode == 0) mode = literal_decoder_for(capBlocks);
-    if (dd.slots) launch_decode_literals_dev<true>(src, out, scratch, frames, blocks, capBlocks, status, slowFlags, mode, nullptr, nullptr, stream, dd.slots);
-    else launch_decode_literals_dev<false>(src, out, scratch, frames, blocks, capBlocks, status, slowFlags, mode, dd.dictFull, dd.dinfo, stream, nullptr);
+    launch_literals(src, out, scratch, frames, blocks, capBlocks, status, slowFlags, mode, dd, true, stream, StageHook());
 }
-
 void launch_decode_literals(const u8* src, u8* out, u8* scratch, const FrameDesc* frames, const BlockDesc* blocks, u32 nBlocks, u32* status,
                             u8* slowFlags, u32 mode, const DecodeDict& dd, hipStream_t stream, StageHook hook)
 {
-    const DictSlot* const slots = dd.slots; const u8* const dictFull = dd.dictFull; const DictInfo* const di = dd.dinfo;
-    if (mode == 0) mode = literal_decoder_for(nBlocks);
-    if (mode == 2) {
-        static bool attrSet[64] = {};               // per device
-        int dev = 0; (void)hipGetDevice(&dev);
-        if (!attrSet[dev & 63]) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(decode_literals_sync_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(SyncLds)); attrSet[dev & 63] = true; }
-        if (slots) {
-            static bool attrSetS[64] = {};
-            if (!attrSetS[dev & 63]) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(decode_literals_sync_set_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(SyncLds)); attrSetS[dev & 63] = true; }
-            hipLaunchKernelGGL(decode_literals_sync_set_kernel, dim3(nBlocks), dim3(256), sizeof(SyncLds), stream, src, out, scratch, frames, blocks, nBlocks, status, slots);
-        } else
-        hipLaunchKernelGGL(decode_literals_sync_kernel, dim3(nBlocks), dim3(256), sizeof(SyncLds), stream, src, out, scratch, frames, blocks, nBlocks, status, dictFull, di);
-        hook("decode_literals");
-        return;
-    }
-    if (slots) {
-        if (mode == 3) hipLaunchKernelGGL(decode_literals_compact_set_kernel, dim3((nBlocks + kQuadsC - 1) / kQuadsC), dim3(64), 0, stream, src, out, scratch, frames, blocks, nBlocks, status, slowFlags, slots);
-        else           hipLaunchKernelGGL(decode_literals_set_kernel, dim3((nBlocks + kQuads - 1) / kQuads), dim3(64), 0, stream, src, out, scratch, frames, blocks, nBlocks, status, slowFlags, slots);
-        hook("decode_literals");
-        hipLaunchKernelGGL(decode_literals_slow_set_kernel, dim3(nBlocks), dim3(64), 0, stream, src, out, scratch, frames, blocks, nBlocks, status, (const u8*)slowFlags, slots);
-        hook("decode_literals_slow");
-        return;
-    }
-    if (mode == 3) hipLaunchKernelGGL(decode_literals_compact_kernel, dim3((nBlocks + kQuadsC - 1) / kQuadsC), dim3(64), 0, stream, src, out, scratch, frames, blocks, nBlocks, status, slowFlags, dictFull, di);
-    else           hipLaunchKernelGGL(decode_literals_kernel, dim3((nBlocks + kQuads - 1) / kQuads), dim3(64), 0, stream, src, out, scratch, frames, blocks, nBlocks, status, slowFlags, dictFull, di);
-    hook("decode_literals");
-    hipLaunchKernelGGL(decode_literals_slow_kernel, dim3(nBlocks), dim3(64), 0, stream, src, out, scratch, frames, blocks, nBlocks, status, (const u8*)slowFlags, dictFull, di);
-    hook("decode_literals_slow");
+    launch_literals(src, out, scratch, frames, blocks, nBlocks, status, slowFlags, mode, dd, false, stream, hook);
 }
 
 } // namespace zmi

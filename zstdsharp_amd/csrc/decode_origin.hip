@@ -109,16 +109,12 @@ __device__ __forceinline__ void origin_init_body(const FrameDesc* __restrict__ f
         }
     }
 }
+template <bool kSet>
 __global__ __launch_bounds__(256) void origin_init_kernel(const FrameDesc* __restrict__ frames, const BlockDesc* __restrict__ blocks, const u32* __restrict__ list,
-                                                          const SeqRec* __restrict__ recs, u32* __restrict__ status, u32* __restrict__ origin, const u32 dictSize)
+                                                          const SeqRec* __restrict__ recs, u32* __restrict__ status, u32* __restrict__ origin, const u32 dictSize,
+                                                          const DictSlot* __restrict__ slots)
 {
-    origin_init_body<false>(frames, blocks, list, recs, status, origin, dictSize, nullptr);
-}
-__global__ __launch_bounds__(256) void origin_init_set_kernel(const FrameDesc* __restrict__ frames, const BlockDesc* __restrict__ blocks, const u32* __restrict__ list,
-                                                              const SeqRec* __restrict__ recs, u32* __restrict__ status, u32* __restrict__ origin,
-                                                              const DictSlot* __restrict__ slots)
-{
-    origin_init_body<true>(frames, blocks, list, recs, status, origin, 0, slots);
+    origin_init_body<kSet>(frames, blocks, list, recs, status, origin, kSet ? 0 : dictSize, kSet ? slots : nullptr);
 }
 
 // one round of origin[i] = origin[origin[i]]; four entries per thread, 1024 per workgroup and step = one REGION.
@@ -205,15 +201,12 @@ __device__ __forceinline__ void origin_gather_body(const FrameDesc* __restrict__
         }
     }
 }
+template <bool kSet>
 __global__ __launch_bounds__(256) void origin_gather_kernel(const FrameDesc* __restrict__ frames, const u32* __restrict__ list, const u32* __restrict__ status,
-                                                            const u32* __restrict__ origin, u8* __restrict__ out, const u8* __restrict__ dict)
+                                                            const u32* __restrict__ origin, u8* __restrict__ out, const u8* __restrict__ dict,
+                                                            const DictSlot* __restrict__ slots)
 {
-    origin_gather_body<false>(frames, list, status, origin, out, dict, nullptr);
-}
-__global__ __launch_bounds__(256) void origin_gather_set_kernel(const FrameDesc* __restrict__ frames, const u32* __restrict__ list, const u32* __restrict__ status,
-                                                                const u32* __restrict__ origin, u8* __restrict__ out, const DictSlot* __restrict__ slots)
-{
-    origin_gather_body<true>(frames, list, status, origin, out, nullptr, slots);
+    origin_gather_body<kSet>(frames, list, status, origin, out, kSet ? nullptr : dict, kSet ? slots : nullptr);
 }
 
 void launch_origin_select(FrameDesc* frames, u32 nFrames, u64 minBytes, u32* list, u32 listCap, u64 originCap, u32* status, hipStream_t stream)
@@ -242,8 +235,9 @@ void launch_origin_init(const FrameDesc* frames, const BlockDesc* blocks, const 
     u64 bw = (maxFrameBytes / (128u << 10) + 4) / 4;             // one wave per block of 128 KiB
     if (bw > 4096) bw = 4096;
     hipLaunchKernelGGL(origin_fill_kernel, grid, tb, 0, stream, frames, list, (const u32*)status, origin);
-    if (dd.slots) hipLaunchKernelGGL(origin_init_set_kernel, dim3((u32)bw, listCap), tb, 0, stream, frames, blocks, list, recs, status, origin, dd.slots);
-    else hipLaunchKernelGGL(origin_init_kernel, dim3((u32)bw, listCap), tb, 0, stream, frames, blocks, list, recs, status, origin, dd.dictContent ? dd.dictContentSize : 0u);
+    with_flags([&](auto set) {
+        hipLaunchKernelGGL(origin_init_kernel<set()>, dim3((u32)bw, listCap), tb, 0, stream, frames, blocks, list, recs, status, origin, dd.dictContent ? dd.dictContentSize : 0u, dd.slots);
+    }, dd.slots != nullptr);
 }
 // rounds [r0, r1) of the pointer jumping; done: one word per 1024 origins, any contents before round 0
 void launch_origin_jump(const FrameDesc* frames, const u32* list, u32 listCap, u64 maxFrameBytes, u32* status, u32* origin, u32* done, u32 r0, u32 r1, hipStream_t stream)
@@ -253,8 +247,9 @@ void launch_origin_jump(const FrameDesc* frames, const u32* list, u32 listCap, u
 }
 void launch_origin_gather(const FrameDesc* frames, const u32* list, u32 listCap, u64 maxFrameBytes, const u32* status, const u32* origin, u8* out, const DecodeDict& dd, hipStream_t stream)
 {
-    if (dd.slots) hipLaunchKernelGGL(origin_gather_set_kernel, origin_grid(maxFrameBytes, listCap), dim3(256), 0, stream, frames, list, status, origin, out, dd.slots);
-    else hipLaunchKernelGGL(origin_gather_kernel, origin_grid(maxFrameBytes, listCap), dim3(256), 0, stream, frames, list, status, origin, out, dd.dictContent);
+    with_flags([&](auto set) {
+        hipLaunchKernelGGL(origin_gather_kernel<set()>, origin_grid(maxFrameBytes, listCap), dim3(256), 0, stream, frames, list, status, origin, out, dd.dictContent, dd.slots);
+    }, dd.slots != nullptr);
 }
 
 } // namespace zmi

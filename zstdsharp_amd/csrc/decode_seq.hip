@@ -442,6 +442,8 @@ __device__ __forceinline__ void seq_decode_body(const u8* __restrict__ src, cons
 #endif
 }
 
+// (seq_decode keeps one wrapper per mode: as one template its instances were the same instruction streams, but the seq_decode stage of
+// 64 KiB level-5 frames measured 1 - 2 % slower, and with the wrappers this file's device code is what it was)
 __global__ __launch_bounds__(256) void seq_decode_kernel(const u8* __restrict__ src, const FrameDesc* __restrict__ frames, BlockDesc* __restrict__ blocks,
                                                          u32 nBlocks, SeqRec* __restrict__ recs, u32* __restrict__ status,
                                                          const u8* __restrict__ dictFull, const DictInfo* __restrict__ di)
@@ -960,52 +962,34 @@ __global__ __launch_bounds__(64 * W) void exec_matches_wide_kernel(const u8* __r
 // wide: waves per frame.  Measured on 1 MiB level-5 frames (exec_matches, ms; tools/exec_waves_time.py): 256 frames: 1 wave 5.0,
 // 16 waves 2.4; 1024 frames: 6.8 / 5.5 / 4.3 / 5.7 / 7.3 at 1 / 2 / 4 / 8 / 16; 2048 frames: 8.3 / 6.5 / 8.0 at 1 / 2 / 4; 4096
 // frames: 9.8 / 12.3 at 1 / 2 — i.e. as many waves as keep frames x waves at about 4096 (the caller's rule, decompress_device)
-void launch_exec_matches(const u8* src, u8* out, const FrameDesc* frames, const BlockDesc* blocks, u32 nFrames, const SeqRec* recs, u32* status,
-                         const DecodeDict& dd, hipStream_t stream, int wide)
+static void launch_exec(const u8* src, u8* out, const FrameDesc* frames, const BlockDesc* blocks, u32 count, const SeqRec* recs, u32* status,
+                        const DecodeDict& dd, bool dev, hipStream_t stream, int wide)
 {
     // the set instances: the slot table rides in the dictionary pointer's place.  The others: a raw-content dictionary (or a formatted one's
     // content) = history in front of EVERY frame (ZSTD_refDictContent, U/ZstdDecompress.cs:1758-1771); may be null
     const u8* const dict = dd.slots ? reinterpret_cast<const u8*>(dd.slots) : dd.dictContent;
     const u32 ds = !dd.slots && dd.dictContent ? dd.dictContentSize : 0u;
-    if (dd.slots) {
+    const u32 nFrames = dev ? 0u : count;                       // (a kDev instance reads the count from the status words)
+    with_flags([&](auto set, auto d) {
         switch (wide) {
-        case 16: hipLaunchKernelGGL((exec_matches_wide_kernel<16, true>), dim3(nFrames), dim3(1024), 0, stream, src, out, frames, blocks, nFrames, recs, status, dict, ds); return;
-        case 8:  hipLaunchKernelGGL((exec_matches_wide_kernel<8, true>),  dim3(nFrames), dim3(512),  0, stream, src, out, frames, blocks, nFrames, recs, status, dict, ds); return;
-        case 4:  hipLaunchKernelGGL((exec_matches_wide_kernel<4, true>),  dim3(nFrames), dim3(256),  0, stream, src, out, frames, blocks, nFrames, recs, status, dict, ds); return;
-        case 2:  hipLaunchKernelGGL((exec_matches_wide_kernel<2, true>),  dim3(nFrames), dim3(128),  0, stream, src, out, frames, blocks, nFrames, recs, status, dict, ds); return;
-        default: break;
+        case 16: hipLaunchKernelGGL((exec_matches_wide_kernel<16, set(), d()>), dim3(count), dim3(1024), 0, stream, src, out, frames, blocks, nFrames, recs, status, dict, ds); return;
+        case 8:  hipLaunchKernelGGL((exec_matches_wide_kernel<8, set(), d()>),  dim3(count), dim3(512),  0, stream, src, out, frames, blocks, nFrames, recs, status, dict, ds); return;
+        case 4:  hipLaunchKernelGGL((exec_matches_wide_kernel<4, set(), d()>),  dim3(count), dim3(256),  0, stream, src, out, frames, blocks, nFrames, recs, status, dict, ds); return;
+        case 2:  hipLaunchKernelGGL((exec_matches_wide_kernel<2, set(), d()>),  dim3(count), dim3(128),  0, stream, src, out, frames, blocks, nFrames, recs, status, dict, ds); return;
+        default: hipLaunchKernelGGL((exec_matches_kernel<set(), d()>), dim3(count), dim3(64), 0, stream, src, out, frames, blocks, nFrames, recs, status, dict, ds);
         }
-        hipLaunchKernelGGL(exec_matches_kernel<true>, dim3(nFrames), dim3(64), 0, stream, src, out, frames, blocks, nFrames, recs, status, dict, ds);
-        return;
-    }
-    switch (wide) {
-    case 16: hipLaunchKernelGGL(exec_matches_wide_kernel<16>, dim3(nFrames), dim3(1024), 0, stream, src, out, frames, blocks, nFrames, recs, status, dict, ds); return;
-    case 8:  hipLaunchKernelGGL(exec_matches_wide_kernel<8>,  dim3(nFrames), dim3(512),  0, stream, src, out, frames, blocks, nFrames, recs, status, dict, ds); return;
-    case 4:  hipLaunchKernelGGL(exec_matches_wide_kernel<4>,  dim3(nFrames), dim3(256),  0, stream, src, out, frames, blocks, nFrames, recs, status, dict, ds); return;
-    case 2:  hipLaunchKernelGGL(exec_matches_wide_kernel<2>,  dim3(nFrames), dim3(128),  0, stream, src, out, frames, blocks, nFrames, recs, status, dict, ds); return;
-    default: break;
-    }
-    hipLaunchKernelGGL(exec_matches_kernel<false>, dim3(nFrames), dim3(64), 0, stream, src, out, frames, blocks, nFrames, recs, status, dict, ds);
+    }, dd.slots != nullptr, dev);
+}
+void launch_exec_matches(const u8* src, u8* out, const FrameDesc* frames, const BlockDesc* blocks, u32 nFrames, const SeqRec* recs, u32* status,
+                         const DecodeDict& dd, hipStream_t stream, int wide)
+{
+    launch_exec(src, out, frames, blocks, nFrames, recs, status, dd, false, stream, wide);
 }
 // the same instances with the number of frames from the status words, over a grid of the caller's limit (ZSTDMI_decompressBatchAsync)
-template <bool kSet>
-static void launch_exec_matches_dev(const u8* src, u8* out, const FrameDesc* frames, const BlockDesc* blocks, u32 capFrames, const SeqRec* recs, u32* status,
-                                    const u8* dict, u32 ds, hipStream_t stream, int wide)
-{
-    switch (wide) {
-    case 16: hipLaunchKernelGGL((exec_matches_wide_kernel<16, kSet, true>), dim3(capFrames), dim3(1024), 0, stream, src, out, frames, blocks, 0u, recs, status, dict, ds); return;
-    case 8:  hipLaunchKernelGGL((exec_matches_wide_kernel<8, kSet, true>),  dim3(capFrames), dim3(512),  0, stream, src, out, frames, blocks, 0u, recs, status, dict, ds); return;
-    case 4:  hipLaunchKernelGGL((exec_matches_wide_kernel<4, kSet, true>),  dim3(capFrames), dim3(256),  0, stream, src, out, frames, blocks, 0u, recs, status, dict, ds); return;
-    case 2:  hipLaunchKernelGGL((exec_matches_wide_kernel<2, kSet, true>),  dim3(capFrames), dim3(128),  0, stream, src, out, frames, blocks, 0u, recs, status, dict, ds); return;
-    default: break;
-    }
-    hipLaunchKernelGGL((exec_matches_kernel<kSet, true>), dim3(capFrames), dim3(64), 0, stream, src, out, frames, blocks, 0u, recs, status, dict, ds);
-}
 void launch_exec_matches_d(const u8* src, u8* out, const FrameDesc* frames, const BlockDesc* blocks, u32 capFrames, const SeqRec* recs, u32* status,
                            const DecodeDict& dd, hipStream_t stream, int wide)
 {
-    if (dd.slots) launch_exec_matches_dev<true>(src, out, frames, blocks, capFrames, recs, status, reinterpret_cast<const u8*>(dd.slots), 0u, stream, wide);
-    else launch_exec_matches_dev<false>(src, out, frames, blocks, capFrames, recs, status, dd.dictContent, dd.dictContent ? dd.dictContentSize : 0u, stream, wide);
+    launch_exec(src, out, frames, blocks, capFrames, recs, status, dd, true, stream, wide);
 }
 
 } // namespace zmi

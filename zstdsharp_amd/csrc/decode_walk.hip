@@ -127,15 +127,11 @@ __device__ __forceinline__ void frame_walk_serial_body(const u8* __restrict__ sr
     status[kStUnsized] = nUnsized; status[kStBlocks] = (u32)nBlocks;
     if constexpr (kSet) status[kStSetFrames] = err ? 0u : nInSet;
 }
+template <bool kSet>
 __global__ void frame_walk_serial_kernel(const u8* __restrict__ src, u64 srcSize, FrameDesc* __restrict__ frames, BlockDesc* __restrict__ blocks,
-                                         u32 maxFrames, u32* __restrict__ status, u32 dictID, u32 emit)
+                                         u32 maxFrames, u32* __restrict__ status, u32 dictID, u32 emit, const DictSlot* __restrict__ slots, u32 nSet)
 {
-    frame_walk_serial_body<false>(src, srcSize, frames, blocks, maxFrames, status, dictID, emit, nullptr, 0);
-}
-__global__ void frame_walk_serial_set_kernel(const u8* __restrict__ src, u64 srcSize, FrameDesc* __restrict__ frames, BlockDesc* __restrict__ blocks,
-                                             u32 maxFrames, u32* __restrict__ status, u32 emit, const DictSlot* __restrict__ slots, u32 nSet)
-{
-    frame_walk_serial_body<true>(src, srcSize, frames, blocks, maxFrames, status, 0, emit, slots, nSet);
+    frame_walk_serial_body<kSet>(src, srcSize, frames, blocks, maxFrames, status, kSet ? 0 : dictID, emit, kSet ? slots : nullptr, kSet ? nSet : 0);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -411,21 +407,11 @@ __device__ __forceinline__ void batch_walk_count_body(const u8* __restrict__ src
     out[e] = r;
     if constexpr (kSet) { if (r.state == kBatchDecode && nInSet) atomicAdd(status + kStSetFrames, nInSet); }
 }
+template <bool kSet, bool kOpen>
 __global__ __launch_bounds__(64) void batch_walk_count_kernel(const u8* __restrict__ src, const BatchEntryIn* __restrict__ in, BatchEntryOut* __restrict__ out, u32 nEntries,
-                                                              u32 dictID, u64 aloneAbove)
+                                                              u32 dictID, u64 aloneAbove, const DictSlot* __restrict__ slots, u32 nSet, u32* __restrict__ status)
 {
-    batch_walk_count_body<false>(src, in, out, nEntries, dictID, aloneAbove, nullptr, 0, nullptr);
-}
-__global__ __launch_bounds__(64) void batch_walk_count_set_kernel(const u8* __restrict__ src, const BatchEntryIn* __restrict__ in, BatchEntryOut* __restrict__ out, u32 nEntries,
-                                                                  u64 aloneAbove, const DictSlot* __restrict__ slots, u32 nSet, u32* __restrict__ status)
-{
-    batch_walk_count_body<true>(src, in, out, nEntries, 0, aloneAbove, slots, nSet, status);
-}
-template <bool kSet>
-__global__ __launch_bounds__(64) void batch_walk_count_open_kernel(const u8* __restrict__ src, const BatchEntryIn* __restrict__ in, BatchEntryOut* __restrict__ out, u32 nEntries,
-                                                                   u32 dictID, u64 aloneAbove, const DictSlot* __restrict__ slots, u32 nSet, u32* __restrict__ status)
-{
-    batch_walk_count_body<kSet, true>(src, in, out, nEntries, dictID, aloneAbove, slots, nSet, status);
+    batch_walk_count_body<kSet, kOpen>(src, in, out, nEntries, kSet ? 0 : dictID, aloneAbove, kSet ? slots : nullptr, kSet ? nSet : 0, kSet || kOpen ? status : nullptr);
 }
 
 // scan (single workgroup): every decoded entry's first frame, first block and literal-scratch offset; the totals go to the status
@@ -529,22 +515,12 @@ __device__ __forceinline__ void batch_walk_emit_body(const u8* __restrict__ src,
         pos = o.next;
     }
 }
+template <bool kSet, bool kOpen>
 __global__ __launch_bounds__(64) void batch_walk_emit_kernel(const u8* __restrict__ src, const BatchEntryIn* __restrict__ in, const BatchEntryOut* __restrict__ out, u32 nEntries,
-                                                             FrameDesc* __restrict__ frames, BlockDesc* __restrict__ blocks)
+                                                             FrameDesc* __restrict__ frames, BlockDesc* __restrict__ blocks, const DictSlot* __restrict__ slots, u32 nSet,
+                                                             u64* __restrict__ rooms)
 {
-    batch_walk_emit_body<false>(src, in, out, nEntries, frames, blocks, nullptr, 0);
-}
-__global__ __launch_bounds__(64) void batch_walk_emit_set_kernel(const u8* __restrict__ src, const BatchEntryIn* __restrict__ in, const BatchEntryOut* __restrict__ out, u32 nEntries,
-                                                                 FrameDesc* __restrict__ frames, BlockDesc* __restrict__ blocks, const DictSlot* __restrict__ slots, u32 nSet)
-{
-    batch_walk_emit_body<true>(src, in, out, nEntries, frames, blocks, slots, nSet);
-}
-template <bool kSet>
-__global__ __launch_bounds__(64) void batch_walk_emit_open_kernel(const u8* __restrict__ src, const BatchEntryIn* __restrict__ in, const BatchEntryOut* __restrict__ out, u32 nEntries,
-                                                                  FrameDesc* __restrict__ frames, BlockDesc* __restrict__ blocks, const DictSlot* __restrict__ slots, u32 nSet,
-                                                                  u64* __restrict__ rooms)
-{
-    batch_walk_emit_body<kSet, true>(src, in, out, nEntries, frames, blocks, slots, nSet, rooms);
+    batch_walk_emit_body<kSet, kOpen>(src, in, out, nEntries, frames, blocks, kSet ? slots : nullptr, kSet ? nSet : 0, kOpen ? rooms : nullptr);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -600,12 +576,10 @@ __global__ __launch_bounds__(64) void batch_fold_kernel(BatchEntryOut* __restric
 void launch_batch_walk_count(const u8* src, const BatchEntryIn* in, BatchEntryOut* out, u32 nEntries, const DecodeDict& dd, u64 aloneAbove, u32* status, hipStream_t stream,
                              bool open, bool caps)
 {
-    const DictSlot* const slots = dd.slots; const u32 nSet = dd.nSet, dictID = slots ? 0u : dd.dictID;      // (a set instance finds each frame's dictionary by its dictID)
-    const dim3 grid((nEntries + 63) / 64);
-    if (open && slots) hipLaunchKernelGGL(batch_walk_count_open_kernel<true>, grid, dim3(64), 0, stream, src, in, out, nEntries, dictID, aloneAbove, slots, nSet, status);
-    else if (open) hipLaunchKernelGGL(batch_walk_count_open_kernel<false>, grid, dim3(64), 0, stream, src, in, out, nEntries, dictID, aloneAbove, slots, nSet, status);
-    else if (slots) hipLaunchKernelGGL(batch_walk_count_set_kernel, grid, dim3(64), 0, stream, src, in, out, nEntries, aloneAbove, slots, nSet, status);
-    else hipLaunchKernelGGL(batch_walk_count_kernel, grid, dim3(64), 0, stream, src, in, out, nEntries, dictID, aloneAbove);
+    // (a set instance finds each frame's dictionary by its dictID)
+    with_flags([&](auto set, auto op) {
+        hipLaunchKernelGGL((batch_walk_count_kernel<set(), op()>), dim3((nEntries + 63) / 64), dim3(64), 0, stream, src, in, out, nEntries, dd.dictID, aloneAbove, dd.slots, dd.nSet, status);
+    }, dd.slots != nullptr, open);
     if (caps) hipLaunchKernelGGL(batch_scan_kernel<true>, dim3(1), dim3(256), 0, stream, out, nEntries, status);
     else hipLaunchKernelGGL(batch_scan_kernel<>, dim3(1), dim3(256), 0, stream, out, nEntries, status);
 }
@@ -681,12 +655,9 @@ void launch_batch_finish_d(const BatchEntryOut* out, const u32* verdict, u32 n, 
 void launch_batch_walk_emit(const u8* src, const BatchEntryIn* in, const BatchEntryOut* out, u32 nEntries, FrameDesc* frames, BlockDesc* blocks, hipStream_t stream,
                             const DecodeDict& dd, u64* rooms)
 {
-    const DictSlot* const slots = dd.slots; const u32 nSet = dd.nSet;
-    const dim3 grid((nEntries + 63) / 64);
-    if (rooms && slots) hipLaunchKernelGGL(batch_walk_emit_open_kernel<true>, grid, dim3(64), 0, stream, src, in, out, nEntries, frames, blocks, slots, nSet, rooms);
-    else if (rooms) hipLaunchKernelGGL(batch_walk_emit_open_kernel<false>, grid, dim3(64), 0, stream, src, in, out, nEntries, frames, blocks, slots, nSet, rooms);
-    else if (slots) hipLaunchKernelGGL(batch_walk_emit_set_kernel, grid, dim3(64), 0, stream, src, in, out, nEntries, frames, blocks, slots, nSet);
-    else hipLaunchKernelGGL(batch_walk_emit_kernel, grid, dim3(64), 0, stream, src, in, out, nEntries, frames, blocks);
+    with_flags([&](auto set, auto op) {          // (rooms: the open instances)
+        hipLaunchKernelGGL((batch_walk_emit_kernel<set(), op()>), dim3((nEntries + 63) / 64), dim3(64), 0, stream, src, in, out, nEntries, frames, blocks, dd.slots, dd.nSet, rooms);
+    }, dd.slots != nullptr, rooms != nullptr);
 }
 void launch_batch_fold(BatchEntryOut* out, u32 nEntries, const u64* keys, hipStream_t stream)
 {
@@ -869,8 +840,9 @@ void launch_frame_walk_emit(const u8* src, u64 srcSize, FrameDesc* frames, Block
 }
 void launch_frame_walk_serial(const u8* src, u64 srcSize, FrameDesc* frames, BlockDesc* blocks, u32 maxFrames, u32* status, const DecodeDict& dd, u32 emit, hipStream_t stream)
 {
-    if (dd.slots) hipLaunchKernelGGL(frame_walk_serial_set_kernel, dim3(1), dim3(64), 0, stream, src, srcSize, frames, blocks, maxFrames, status, emit, dd.slots, dd.nSet);
-    else hipLaunchKernelGGL(frame_walk_serial_kernel, dim3(1), dim3(64), 0, stream, src, srcSize, frames, blocks, maxFrames, status, dd.dictID, emit);
+    with_flags([&](auto set) {
+        hipLaunchKernelGGL(frame_walk_serial_kernel<set()>, dim3(1), dim3(64), 0, stream, src, srcSize, frames, blocks, maxFrames, status, dd.dictID, emit, dd.slots, dd.nSet);
+    }, dd.slots != nullptr);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1092,33 +1064,14 @@ __device__ __forceinline__ void block_link_body(FrameDesc* __restrict__ frames, 
             atomicAdd(reinterpret_cast<unsigned long long*>(status + kStBigBins) + highbit32((u32)(dstSize >> 20)), (unsigned long long)dstSize);
     }
 }
+// (kStream: a fragment of a segmented stream, whose first `phantoms` blocks are carried definers — never a set, open or kDev instance)
+template <bool kSet, bool kOpen, bool kDev, bool kStream>
 __global__ __launch_bounds__(64) void block_link_kernel(FrameDesc* __restrict__ frames, BlockDesc* __restrict__ blocks, u32 nFrames, u32 haveDict,
-                                                        u32 earlyLiterals, u32* __restrict__ status)
+                                                        u32 earlyLiterals, u32* __restrict__ status, u32 phantoms, const DictSlot* __restrict__ slots)
 {
-    block_link_body<false>(frames, blocks, nFrames, haveDict, earlyLiterals, status, 0);
-}
-__global__ __launch_bounds__(64) void block_link_set_kernel(FrameDesc* __restrict__ frames, BlockDesc* __restrict__ blocks, u32 nFrames,
-                                                            u32 earlyLiterals, u32* __restrict__ status, const DictSlot* __restrict__ slots)
-{
-    block_link_body<false, true>(frames, blocks, nFrames, 0, earlyLiterals, status, 0, slots);
-}
-template <bool kSet>
-__global__ __launch_bounds__(64) void block_link_open_kernel(FrameDesc* __restrict__ frames, BlockDesc* __restrict__ blocks, u32 nFrames, u32 haveDict,
-                                                             u32 earlyLiterals, u32* __restrict__ status, const DictSlot* __restrict__ slots)
-{
-    block_link_body<false, kSet, true>(frames, blocks, nFrames, haveDict, earlyLiterals, status, 0, slots);
-}
-// (the open instance with the number of frames from the status words: ZSTDMI_decompressBatchAsync)
-template <bool kSet>
-__global__ __launch_bounds__(64) void block_link_open_d_kernel(FrameDesc* __restrict__ frames, BlockDesc* __restrict__ blocks, u32 haveDict,
-                                                               u32 earlyLiterals, u32* __restrict__ status, const DictSlot* __restrict__ slots)
-{
-    block_link_body<false, kSet, true>(frames, blocks, status[kStFrames], haveDict, earlyLiterals, status, 0, slots);
-}
-__global__ __launch_bounds__(64) void block_link_stream_kernel(FrameDesc* __restrict__ frames, BlockDesc* __restrict__ blocks, u32 nFrames, u32 haveDict,
-                                                               u32 earlyLiterals, u32* __restrict__ status, u32 phantoms)
-{
-    block_link_body<true>(frames, blocks, nFrames, haveDict, earlyLiterals, status, phantoms);
+    static_assert(!kStream || !(kSet || kOpen || kDev), "a stream fragment has one dictionary and a content size");
+    block_link_body<kStream, kSet, kOpen>(frames, blocks, list_count<kDev>(nFrames, status, kStFrames), kSet ? 0 : haveDict, earlyLiterals, status,
+                                          kStream ? phantoms : 0, kSet ? slots : nullptr);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1191,30 +1144,13 @@ void launch_block_prepass(const u8* src, FrameDesc* frames, BlockDesc* blocks, u
     // (a set instance reads whether its frame has a formatted dictionary from the frame's slot)
     const DictSlot* const slots = dd.slots; const u32 haveDict = !slots && dd.fmt ? 1u : 0u;
     hipLaunchKernelGGL(block_parse_kernel<>, dim3((nBlocks + 255) / 256), dim3(256), 0, stream, src, blocks, nBlocks, status);
-    if (open) {                 // (a batch: never a fragment of a segmented stream)
-        if (slots) {
-            hipLaunchKernelGGL((block_link_small_kernel<true, true>), dim3((nFrames + 63) / 64), dim3(64), 0, stream, frames, blocks, nFrames, haveDict, earlyLiterals, status, slots);
-            if (nBlocks > nFrames) hipLaunchKernelGGL(block_link_open_kernel<true>, dim3(nFrames), dim3(64), 0, stream, frames, blocks, nFrames, haveDict, earlyLiterals, status, slots);
-        } else {
-            hipLaunchKernelGGL((block_link_small_kernel<false, true>), dim3((nFrames + 63) / 64), dim3(64), 0, stream, frames, blocks, nFrames, haveDict, earlyLiterals, status, slots);
-            if (nBlocks > nFrames) hipLaunchKernelGGL(block_link_open_kernel<false>, dim3(nFrames), dim3(64), 0, stream, frames, blocks, nFrames, haveDict, earlyLiterals, status, slots);
-        }
-        hipLaunchKernelGGL(seq_scan_kernel<>, dim3(1), dim3(1024), 0, stream, blocks, nBlocks, status);
-        return;
-    }
-    if (slots) {                // (never a fragment of a segmented stream: the host refuses that combination)
-        hipLaunchKernelGGL(block_link_small_kernel<true>, dim3((nFrames + 63) / 64), dim3(64), 0, stream, frames, blocks, nFrames, haveDict, earlyLiterals, status, slots);
-        if (nBlocks > nFrames) hipLaunchKernelGGL(block_link_set_kernel, dim3(nFrames), dim3(64), 0, stream, frames, blocks, nFrames, earlyLiterals, status, slots);
-        hipLaunchKernelGGL(seq_scan_kernel<>, dim3(1), dim3(1024), 0, stream, blocks, nBlocks, status);
-        return;
-    }
-    if (phantoms) {             // a fragment of a segmented stream: one frame whose first blocks are carried definers
-        hipLaunchKernelGGL(block_link_stream_kernel, dim3(nFrames), dim3(64), 0, stream, frames, blocks, nFrames, haveDict, earlyLiterals, status, phantoms);
-        hipLaunchKernelGGL(seq_scan_kernel<>, dim3(1), dim3(1024), 0, stream, blocks, nBlocks, status);
-        return;
-    }
-    hipLaunchKernelGGL(block_link_small_kernel<false>, dim3((nFrames + 63) / 64), dim3(64), 0, stream, frames, blocks, nFrames, haveDict, earlyLiterals, status, slots);
-    if (nBlocks > nFrames) hipLaunchKernelGGL(block_link_kernel, dim3(nFrames), dim3(64), 0, stream, frames, blocks, nFrames, haveDict, earlyLiterals, status);      // (some frame has several blocks)
+    // a fragment of a segmented stream: one frame whose first blocks are carried definers (never a batch, and the host refuses it with a set)
+    if (phantoms && !open && !slots) hipLaunchKernelGGL((block_link_kernel<false, false, false, true>), dim3(nFrames), dim3(64), 0, stream, frames, blocks, nFrames, haveDict, earlyLiterals, status, phantoms, slots);
+    else with_flags([&](auto set, auto op) {
+        hipLaunchKernelGGL((block_link_small_kernel<set(), op()>), dim3((nFrames + 63) / 64), dim3(64), 0, stream, frames, blocks, nFrames, haveDict, earlyLiterals, status, slots);
+        if (nBlocks > nFrames)          // (some frame has several blocks)
+            hipLaunchKernelGGL((block_link_kernel<set(), op(), false, false>), dim3(nFrames), dim3(64), 0, stream, frames, blocks, nFrames, haveDict, earlyLiterals, status, 0u, slots);
+    }, slots != nullptr, open);
     hipLaunchKernelGGL(seq_scan_kernel<>, dim3(1), dim3(1024), 0, stream, blocks, nBlocks, status);
 }
 
@@ -1224,13 +1160,10 @@ void launch_block_prepass_d(const u8* src, FrameDesc* frames, BlockDesc* blocks,
 {
     const DictSlot* const slots = dd.slots; const u32 haveDict = !slots && dd.fmt ? 1u : 0u;        // (as launch_block_prepass)
     hipLaunchKernelGGL(block_parse_kernel<true>, dim3((capBlocks + 255) / 256), dim3(256), 0, stream, src, blocks, 0u, status);
-    if (slots) {
-        hipLaunchKernelGGL((block_link_small_kernel<true, true, true>), dim3((capFrames + 63) / 64), dim3(64), 0, stream, frames, blocks, 0u, haveDict, 0u, status, slots);
-        hipLaunchKernelGGL(block_link_open_d_kernel<true>, dim3(capFrames), dim3(64), 0, stream, frames, blocks, haveDict, 0u, status, slots);
-    } else {
-        hipLaunchKernelGGL((block_link_small_kernel<false, true, true>), dim3((capFrames + 63) / 64), dim3(64), 0, stream, frames, blocks, 0u, haveDict, 0u, status, slots);
-        hipLaunchKernelGGL(block_link_open_d_kernel<false>, dim3(capFrames), dim3(64), 0, stream, frames, blocks, haveDict, 0u, status, slots);
-    }
+    with_flags([&](auto set) {
+        hipLaunchKernelGGL((block_link_small_kernel<set(), true, true>), dim3((capFrames + 63) / 64), dim3(64), 0, stream, frames, blocks, 0u, haveDict, 0u, status, slots);
+        hipLaunchKernelGGL((block_link_kernel<set(), true, true, false>), dim3(capFrames), dim3(64), 0, stream, frames, blocks, 0u, haveDict, 0u, status, 0u, slots);
+    }, slots != nullptr);
     hipLaunchKernelGGL(seq_scan_kernel<true>, dim3(1), dim3(1024), 0, stream, blocks, 0u, status);
 }
 
@@ -1301,28 +1234,12 @@ __device__ __forceinline__ void block_offsets_body(FrameDesc* __restrict__ frame
         }
     }
 }
+template <bool kSet, bool kOpen, bool kDev>
 __global__ __launch_bounds__(64) void block_offsets_kernel(FrameDesc* __restrict__ frames, BlockDesc* __restrict__ blocks, u32 nFrames,
-                                                           const DictInfo* __restrict__ di, u32* __restrict__ status)
+                                                           const DictInfo* __restrict__ di, u32* __restrict__ status, const DictSlot* __restrict__ slots)
 {
-    block_offsets_body<false>(frames, blocks, nFrames, di, status, nullptr);
-}
-__global__ __launch_bounds__(64) void block_offsets_set_kernel(FrameDesc* __restrict__ frames, BlockDesc* __restrict__ blocks, u32 nFrames,
-                                                               u32* __restrict__ status, const DictSlot* __restrict__ slots)
-{
-    block_offsets_body<true>(frames, blocks, nFrames, nullptr, status, slots);
-}
-template <bool kSet>
-__global__ __launch_bounds__(64) void block_offsets_open_kernel(FrameDesc* __restrict__ frames, BlockDesc* __restrict__ blocks, u32 nFrames,
-                                                                const DictInfo* __restrict__ di, u32* __restrict__ status, const DictSlot* __restrict__ slots)
-{
-    block_offsets_body<kSet, true>(frames, blocks, nFrames, di, status, slots);
-}
-
-template <bool kSet>
-__global__ __launch_bounds__(64) void block_offsets_open_d_kernel(FrameDesc* __restrict__ frames, BlockDesc* __restrict__ blocks,
-                                                                  const DictInfo* __restrict__ di, u32* __restrict__ status, const DictSlot* __restrict__ slots)
-{
-    block_offsets_body<kSet, true>(frames, blocks, status[kStFrames], di, status, slots);
+    static_assert(kOpen || !kDev, "a batch enqueued from the device runs the open instances");
+    block_offsets_body<kSet, kOpen>(frames, blocks, list_count<kDev>(nFrames, status, kStFrames), kSet ? nullptr : di, status, kSet ? slots : nullptr);
 }
 
 // frames without a content size: the frames' output offsets from their regenerated sizes (single workgroup); the total goes to
@@ -1342,19 +1259,18 @@ __global__ __launch_bounds__(1024) void frame_rescan_kernel(FrameDesc* __restric
 void launch_block_offsets(FrameDesc* frames, BlockDesc* blocks, u32 nFrames, const DecodeDict& dd, const DictInfo* reps, u32 rescan, u64 dstCapacity, u32* status, hipStream_t stream,
                           bool open)
 {
-    const DictSlot* const slots = dd.slots; const DictInfo* const di = slots ? nullptr : reps;      // (a set instance starts from its frame's slot)
-    if (open && slots) hipLaunchKernelGGL(block_offsets_open_kernel<true>, dim3(nFrames), dim3(64), 0, stream, frames, blocks, nFrames, di, status, slots);
-    else if (open) hipLaunchKernelGGL(block_offsets_open_kernel<false>, dim3(nFrames), dim3(64), 0, stream, frames, blocks, nFrames, di, status, slots);
-    else if (slots) hipLaunchKernelGGL(block_offsets_set_kernel, dim3(nFrames), dim3(64), 0, stream, frames, blocks, nFrames, status, slots);
-    else hipLaunchKernelGGL(block_offsets_kernel, dim3(nFrames), dim3(64), 0, stream, frames, blocks, nFrames, di, status);
+    // (a set instance starts from its frame's slot)
+    with_flags([&](auto set, auto op) {
+        hipLaunchKernelGGL((block_offsets_kernel<set(), op(), false>), dim3(nFrames), dim3(64), 0, stream, frames, blocks, nFrames, reps, status, dd.slots);
+    }, dd.slots != nullptr, open);
     if (rescan) hipLaunchKernelGGL(frame_rescan_kernel, dim3(1), dim3(1024), 0, stream, frames, nFrames, dstCapacity, status);
 }
 
 void launch_block_offsets_d(FrameDesc* frames, BlockDesc* blocks, u32 capFrames, const DecodeDict& dd, u32* status, hipStream_t stream)
 {
-    const DictSlot* const slots = dd.slots; const DictInfo* const di = slots ? nullptr : dd.dinfo;
-    if (slots) hipLaunchKernelGGL(block_offsets_open_d_kernel<true>, dim3(capFrames), dim3(64), 0, stream, frames, blocks, di, status, slots);
-    else hipLaunchKernelGGL(block_offsets_open_d_kernel<false>, dim3(capFrames), dim3(64), 0, stream, frames, blocks, di, status, slots);
+    with_flags([&](auto set) {
+        hipLaunchKernelGGL((block_offsets_kernel<set(), true, true>), dim3(capFrames), dim3(64), 0, stream, frames, blocks, 0u, dd.dinfo, status, dd.slots);
+    }, dd.slots != nullptr);
 }
 
 // ZSTD_loadDEntropy's checks (U/ZstdDecompress.cs:1773-1875) on one lane: where the Huffman description and the three NCounts

@@ -19,6 +19,13 @@ __device__ __forceinline__ void report_error(u32* status, u64 blockIdx, u32 stag
     if (perBlock) atomicMin(reinterpret_cast<unsigned long long*>(perBlock) + blockIdx, key);
 }
 
+// The convention of the decoder's stage kernels: a stage has ONE __global__ entry point, a template whose parameters are the modes the
+// stage runs in — kSet (a set of DDicts: slots[F.dictSlot] instead of the one dictionary), kOpen (frames without a content size in the
+// batch pass), kDev (below), kStream (block_link) — and whose argument list is the union of what the modes take.
+// What a mode does not take reaches the body as a compile-time constant (kSet ? nullptr : dictFull), so an instance holds no load or
+// branch for it; the launcher names the instance from the call's DecodeDict and flags (with_flags, zmi_host.h), and only instances a
+// launcher names are compiled.  Where the kernel is a wrapper around an inlined *_body, the body stays as it is.  One family keeps a
+// wrapper per mode, seq_decode (decode_seq.hip): as a template its stage measured slower.
 // A work list's length as a stage's kernel takes it: the launch argument, or — kDev, the instances ZSTDMI_decompressBatchAsync launches
 // over a grid sized from the caller's limits, where the host never learns the counts — the status word the batch scan filed (kStFrames,
 // kStBlocks); the surplus workgroups leave at once.  kDev = false reads nothing and is the kernel as it always was.

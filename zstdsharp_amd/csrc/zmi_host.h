@@ -9,6 +9,7 @@
 #include <vector>
 #include <thread>
 #include <new>
+#include <type_traits>
 #include "zmi_common.h"
 #include "zmi_frame.h"
 #include "zmi_batch_plan.h"
@@ -136,6 +137,16 @@ void launch_ldm_rest(const u8* src, u64 n, u32 nChunks, u32 chunkBytes, u64 fram
 // frame through FrameDesc::dictSlot and gets nulls for the single-dictionary arguments; the other fields describe the current DDict.
 struct DecodeDict { bool fmt; const u8* dictFull; const DictInfo* dinfo; const u8* dictContent; u32 dictContentSize, dictID; const u32* seqTabs;
                     const DictSlot* slots; u32 nSet; };
+// Run-time flags -> the template arguments of a stage's one entry point (zmi_decode.h): with_flags(f, a, b, ...) calls
+// f(std::bool_constant<a>(), std::bool_constant<b>(), ...), and f — a generic lambda, [&](auto set, auto dev) — names the instance as
+// kernel<set(), dev()>.  f is instantiated for every combination of the flags: one the family does not have is excluded inside f with
+// if constexpr, so that its instance is never compiled.
+template <class F> inline void with_flags(F&& f) { f(); }
+template <class F, class... Bs> inline void with_flags(F&& f, bool b, Bs... rest)
+{
+    if (b) with_flags([&](auto... cs) { f(std::true_type(), cs...); }, rest...);
+    else   with_flags([&](auto... cs) { f(std::false_type(), cs...); }, rest...);
+}
 size_t decode_walk_workspace_bytes(u64 srcSize);
 void launch_frame_walk_count(const u8* src, u64 srcSize, u32 maxFrames, u32* status, u8* walkWs, hipStream_t stream);
 void launch_frame_walk_emit(const u8* src, u64 srcSize, FrameDesc* frames, BlockDesc* blocks, u8* walkWs, hipStream_t stream);
