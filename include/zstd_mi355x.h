@@ -91,8 +91,8 @@ size_t     ZSTD_CCtx_loadDictionary(ZSTD_CCtx* cctx, const void* dict, size_t di
  *                      the level.  The block finders see no prefix; the long-distance stage indexes prefix and source as one window and
  *                      runs unless ZSTD_c_enableLongDistanceMatching is ZSTD_ps_disable (ZSTD_ps_auto means ON here); its parameters
  *                      left at 0 derive from windowLog = ceil_log2(prefixSize + srcSize), at least 17.
- * The long form refuses with parameter_unsupported, before any byte is read: ZSTD_ps_disable, prefixSize + srcSize > 512 MiB (the
- * decoder's offset record), a source of more than one pass (ZSTDMI_CCtx_setPassChunks), ZSTD_c_contentSizeFlag = 0, and a set
+ * The long form refuses with parameter_unsupported, before any byte is read: ZSTD_ps_disable, prefixSize + srcSize > 512 MiB (with
+ * ZSTDMI_CCtx_setFarOffsets on: > 2^31), a source of more than one pass (ZSTDMI_CCtx_setPassChunks), ZSTD_c_contentSizeFlag = 0, and a set
  * ZSTD_c_windowLog below ceil_log2(prefixSize + srcSize).  The bytes written depend on the prefix's and the source's bytes alone. */
 size_t     ZSTD_CCtx_refPrefix(ZSTD_CCtx* cctx, const void* prefix, size_t prefixSize);
 /* S/Compressor.cs:73-76 -> U/ZstdCompress.cs:19-22 */
@@ -348,6 +348,18 @@ size_t ZSTDMI_DCtx_setExecWaves(ZSTD_DCtx* dctx, unsigned waves);
 /* diagnostic: 1 if the last decompress call listed its frames with the exact serial walk (frames naming a dictionary, frames
  * without a content size, damaged input) instead of the parallel one, 0 if not, -1 without a context */
 int ZSTDMI_debugLastWalkSerial(const ZSTD_DCtx* dctx);
+/* Offsets of 2^29 and more (what zstd --long=30 / 31 or --patch-from writes for a large file).  The decoder's 8-byte sequence record
+ * names 2^29 - 1 bytes of distance; a far-capable frame — content size (without one: its bound) plus the dictionary or prefix content
+ * in front of it is 2^29 or more — gets a side plane of 4 bytes per sequence for the rest, and every offset the format can state is
+ * decoded: by ZSTD_decompressDCtx, ZSTDMI_decompressDevice, ZSTD_decompress_usingDDict, with a loaded dictionary, a DDict or a
+ * referenced prefix, by ZSTD_decompressStream without segments (ZSTD_d_windowLogMax still holds), at every setExecWaves width and on
+ * the origin path of frames below 1 GiB (larger frames keep the ordered walk).  An offset beyond position + dictionary in such a
+ * frame is corruption_detected; a frame that cannot reach that far keeps frameParameter_windowTooLarge for an offset of 2^29 or
+ * more.  A call without a far-capable frame allocates no plane and launches the kernels it always did.  ZSTDMI_decompressBatch (and
+ * Async), ZSTDMI_decompressRange(s) (and Async) and a segmented ZSTD_decompressStream (ZSTDMI_DCtx_setStreamSegment) keep the
+ * refusal: frameParameter_windowTooLarge for a frame that uses such an offset.
+ * diagnostic: 1 if the last single decompress call had a far plane, 0 if not, -1 without a context */
+int ZSTDMI_debugLastFarPlane(const ZSTD_DCtx* dctx);
 
 /* same contracts as ZSTD_compress2 / ZSTD_decompressDCtx, but src and dst MUST be device pointers (no staging) */
 size_t ZSTDMI_compressDevice(ZSTD_CCtx* cctx, void* d_dst, size_t dstCapacity, const void* d_src, size_t srcSize);
@@ -786,10 +798,22 @@ size_t ZSTDMI_CCtx_setSingleFrame(ZSTD_CCtx* cctx, unsigned mode);
  * A call reads them in place in its own source; a session keeps them on the device: it holds 2^wl bytes + one batch + 4 MiB there from
  * its first batch to its end.  The same input, parameters, pass size and flush positions give the same bytes; other than plain
  * single-frame output, the bytes MAY change with ZSTDMI_CCtx_setPassChunks and with where batches end (a step's index is its window's).
- * parameter_unsupported at the consuming call: ZSTD_c_windowLog 29 .. 31 (the decoder's offset record holds 29 bits), and what
+ * parameter_unsupported at the consuming call: ZSTD_c_windowLog 29 .. 31 (with ZSTDMI_CCtx_setFarOffsets on: 31 alone), and what
  * ZSTDMI_CCtx_setSingleFrame refuses otherwise.  ZSTDMI_compressBatch / ZSTDMI_compressPack: such an entry goes through the single-call
  * path.  Cost: every step indexes its window again ((2^wl + n) of stage work for n bytes).  Figures: README "Sliding long-distance window". */
 size_t ZSTDMI_CCtx_setSlidingLdm(ZSTD_CCtx* cctx, unsigned mode);
+/* Offsets of 2^29 and more on the compress side: delta frames beyond 512 MiB.  0 = off (the default), 1 = on, any other mode:
+ * parameter_outOfBound; NULL context: GENERIC.  Sticky; the call touches no device; device workers take it with the call's parameters.
+ * Off: every byte and every refusal is what it always was.  On:
+ *   - the long form of ZSTD_CCtx_refPrefix accepts prefixSize + srcSize up to 2^31 (the prefix stays at most 1 GiB, the source at most
+ *     one pass); its window is ceil_log2(prefixSize + srcSize), up to 31;
+ *   - ZSTDMI_CCtx_setSlidingLdm accepts ZSTD_c_windowLog 29 and 30 (a pass is held to 2^31 bytes, so that window + pass stay inside the
+ *     long-distance stage's 32-bit pass coordinate); 31 stays refused.
+ * Aligned long-distance frames keep their 512 MiB cap in either mode, and a call that the switch does not touch writes the bytes of
+ * the switch off.  Such frames state offset codes 29 and 30, for which the format has no predefined table: their offset table is
+ * always described or RLE.  They decode with this library's single calls (ZSTDMI_debugLastFarPlane), with the oracle and with libzstd;
+ * ZSTDMI_decompressBatch, the range calls and a segmented stream refuse them (frameParameter_windowTooLarge). */
+size_t ZSTDMI_CCtx_setFarOffsets(ZSTD_CCtx* cctx, unsigned mode);
 size_t ZSTDMI_seekTableBound(size_t srcSize);
 size_t ZSTDMI_decompressRange(ZSTD_DCtx* dctx, void* dst, size_t dstCapacity, const void* src, size_t srcSize,
                               unsigned long long offset, size_t length);

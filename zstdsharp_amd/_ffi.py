@@ -125,6 +125,7 @@ SIGNATURES = {
     "ZSTDMI_DCtx_setOverlap": (c_size_t, [c_void_p, c_uint]),
     "ZSTDMI_DCtx_setExecWaves": (c_size_t, [c_void_p, c_uint]),
     "ZSTDMI_debugLastWalkSerial": (c_int, [c_void_p]),
+    "ZSTDMI_debugLastFarPlane": (c_int, [c_void_p]),
     "ZSTDMI_CCtx_setParser": (c_size_t, [c_void_p, c_uint]),
     "ZSTDMI_compressDevice": (c_size_t, [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t]),
     "ZSTDMI_decompressDevice": (c_size_t, [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t]),
@@ -169,6 +170,7 @@ SIGNATURES = {
     "ZSTDMI_debugDictIndexed": (ctypes.c_longlong, [c_void_p]),
     "ZSTDMI_CCtx_setSingleFrame": (c_size_t, [c_void_p, c_uint]),
     "ZSTDMI_CCtx_setSlidingLdm": (c_size_t, [c_void_p, c_uint]),
+    "ZSTDMI_CCtx_setFarOffsets": (c_size_t, [c_void_p, c_uint]),
     "ZSTDMI_seekTableBound": (c_size_t, [c_size_t]),
     "ZSTDMI_decompressRange": (c_size_t, [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_ull, c_size_t]),
     "ZSTDMI_debugLastRangeFrames": (c_int, [c_void_p]),

@@ -77,6 +77,7 @@ class Compressor(_PrefixHolder):
         self._dict_index_chain = False
         self._single_frame = False
         self._sliding_ldm = False
+        self._far_offsets = False
         self._cdict = None              # the CDict RefCDict holds
         self.Level = level if level else self.DefaultCompressionLevel
 
@@ -245,6 +246,17 @@ class Compressor(_PrefixHolder):
         self._ensure_not_disposed()
         ensure_zstd_success(self._lib, self._lib.ZSTDMI_CCtx_setSlidingLdm(self.cctx, 1 if on else 0))
         self._sliding_ldm = bool(on)
+
+    # ---- offsets of 2^29 and more: RefPrefix up to prefix + source = 2^31, sliding_ldm at windowLog 29 and 30 (ZSTDMI_CCtx_setFarOffsets); off by default ----
+    @property
+    def far_offsets(self) -> bool:
+        return self._far_offsets
+
+    @far_offsets.setter
+    def far_offsets(self, on):
+        self._ensure_not_disposed()
+        ensure_zstd_success(self._lib, self._lib.ZSTDMI_CCtx_setFarOffsets(self.cctx, 1 if on else 0))
+        self._far_offsets = bool(on)
 
     # ---- batches enqueued from the device (ZSTDMI_CCtx_prepareBatchAsync; batch.compress_batch_async runs them) ----
     def PrepareBatchAsync(self, max_entries: int, src_size_bound: int):

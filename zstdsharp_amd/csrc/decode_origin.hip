@@ -61,10 +61,12 @@ __global__ __launch_bounds__(256) void origin_fill_kernel(const FrameDesc* __res
 // the match bytes' first origins: one wave per block, 64 sequences at a time, the batch's match bytes dealt to the lanes in order
 // kSet (ZSTD_d_refMultipleDDicts with two or more DDicts in the set): the dictionary in front of the frame is its own,
 // slots[F.dictSlot]; a workgroup has one frame (blockIdx.y), so dictSize is uniform for it
-template <bool kSet>
+// kFar (a call with a far-capable frame): farPlane holds the offsets of the records that carry kRecFar (seq_batch, zmi_decode.h); a frame
+// on this path is below 1 GiB, so a far offset it may use still names a position, or a dictionary index, below 2^31
+template <bool kSet, bool kFar = false>
 __device__ __forceinline__ void origin_init_body(const FrameDesc* __restrict__ frames, const BlockDesc* __restrict__ blocks, const u32* __restrict__ list,
                                                  const SeqRec* __restrict__ recs, u32* __restrict__ status, u32* __restrict__ origin, u32 dictSize,
-                                                 const DictSlot* __restrict__ slots)
+                                                 const DictSlot* __restrict__ slots, const u32* __restrict__ farPlane = nullptr)
 {
     if (blockIdx.y >= status[kStOriginFrames]) return;
     const FrameDesc& F = frames[list[blockIdx.y]];
@@ -87,7 +89,8 @@ __device__ __forceinline__ void origin_init_body(const FrameDesc* __restrict__ f
             const SeqRec r = rNext;
             if (base + 64 + lane < nbSeq) rNext = rec[base + 64 + lane];
             SeqLane q;
-            outBase = seq_batch(r, have, in0, in1, in2, outBase, q);
+            if constexpr (kFar) outBase = seq_batch<true>(r, have, in0, in1, in2, outBase, q, farPlane + B.seqBase + base + lane);
+            else outBase = seq_batch(r, have, in0, in1, in2, outBase, q);
             const u32 d = bRel + q.pos + q.ll;                   // frame position of my match
             // offset beyond everything in front of the match (+ the dictionary): corruption (:2218-2223)
             if (ballot(have && ((u64)q.off > (u64)d + dictSize || q.off == 0))) { if (lane == 0) report_error(status, (u64)first + k, kStageExec, kErrCorruption); break; }
@@ -115,6 +118,13 @@ __global__ __launch_bounds__(256) void origin_init_kernel(const FrameDesc* __res
                                                           const DictSlot* __restrict__ slots)
 {
     origin_init_body<kSet>(frames, blocks, list, recs, status, origin, kSet ? 0 : dictSize, kSet ? slots : nullptr);
+}
+template <bool kSet>
+__global__ __launch_bounds__(256) void origin_init_far_kernel(const FrameDesc* __restrict__ frames, const BlockDesc* __restrict__ blocks, const u32* __restrict__ list,
+                                                              const SeqRec* __restrict__ recs, u32* __restrict__ status, u32* __restrict__ origin, const u32 dictSize,
+                                                              const DictSlot* __restrict__ slots, const u32* __restrict__ farPlane)
+{
+    origin_init_body<kSet, true>(frames, blocks, list, recs, status, origin, kSet ? 0 : dictSize, kSet ? slots : nullptr, farPlane);
 }
 
 // one round of origin[i] = origin[origin[i]]; four entries per thread, 1024 per workgroup and step = one REGION.
@@ -229,14 +239,15 @@ static dim3 origin_grid(u64 maxFrameBytes, u32 listCap)
 }
 // select + fill + init (queued behind block_offsets; the literals are not needed yet)
 void launch_origin_init(const FrameDesc* frames, const BlockDesc* blocks, const u32* list, u32 listCap, u64 maxFrameBytes, const SeqRec* recs, u32* status,
-                        u32* origin, const DecodeDict& dd, hipStream_t stream)
+                        u32* origin, const DecodeDict& dd, hipStream_t stream, const u32* far)
 {
     const dim3 grid = origin_grid(maxFrameBytes, listCap), tb(256);
     u64 bw = (maxFrameBytes / (128u << 10) + 4) / 4;             // one wave per block of 128 KiB
     if (bw > 4096) bw = 4096;
     hipLaunchKernelGGL(origin_fill_kernel, grid, tb, 0, stream, frames, list, (const u32*)status, origin);
     with_flags([&](auto set) {
-        hipLaunchKernelGGL(origin_init_kernel<set()>, dim3((u32)bw, listCap), tb, 0, stream, frames, blocks, list, recs, status, origin, dd.dictContent ? dd.dictContentSize : 0u, dd.slots);
+        if (far) hipLaunchKernelGGL(origin_init_far_kernel<set()>, dim3((u32)bw, listCap), tb, 0, stream, frames, blocks, list, recs, status, origin, dd.dictContent ? dd.dictContentSize : 0u, dd.slots, far);
+        else hipLaunchKernelGGL(origin_init_kernel<set()>, dim3((u32)bw, listCap), tb, 0, stream, frames, blocks, list, recs, status, origin, dd.dictContent ? dd.dictContentSize : 0u, dd.slots);
     }, dd.slots != nullptr);
 }
 // rounds [r0, r1) of the pointer jumping; done: one word per 1024 origins, any contents before round 0

@@ -179,9 +179,13 @@ __device__ __forceinline__ u32 stream_field(const u8* s, s32 size, s32 p, u32 nb
 
 // phase C for one block: records `buf` of its sequences [base, base + 64) -> SeqRecs; the block's running state (symbolic repcodes,
 // output and literal totals, error) is wave-uniform and lives in the caller's registers
+// kFar (the far instances, launched only for a call that has a far-capable frame): an offset above kRecOffMax — stated, or the repeat of
+// one that this batch resolves — goes to the block's words of the far plane and leaves the mark kRecFar in its record, where the block's
+// own frame can reach that far back (farOk); a frame that cannot keeps the refusal.  kFar = false is the function as it always was.
 struct SlotState { RepSlot s0, s1, s2; u32 outBase, litUsed, err; };
+template <bool kFar = false>
 __device__ __forceinline__ void seq_fields_batch(const SeqLds& L, u32 buf, u32 sl, u32 base, u32 nbSeq, const u8* sp, s32 size, u32 litSize,
-                                                 SeqRec* __restrict__ rec, SlotState& S, u32 lane)
+                                                 SeqRec* __restrict__ rec, SlotState& S, u32 lane, u32* __restrict__ far = nullptr, bool farOk = false)
 {
     const u32 cnt = nbSeq - base < 64 ? nbSeq - base : 64;
     const u32* const T = L.tab[sl];
@@ -228,6 +232,11 @@ __device__ __forceinline__ void seq_fields_batch(const SeqLds& L, u32 buf, u32 s
     const u32 totalOut = wave_sum(ll + ml), totalLit = wave_sum(ll);
     if (totalLit > litSize - S.litUsed) { S.err = kErrCorruption; return; }
     if (totalOut > 0xFFFFFFFFu - S.outBase - litSize) { S.err = kErrCorruption; return; }     // (no valid block regenerates 4 GiB)
+    if constexpr (kFar) {
+        const bool isFar = have && !tag && off > kRecOffMax;
+        if (ballot(isFar) && !farOk) { S.err = kErrWindowTooLarge; return; }
+        if (isFar) { far[base + lane] = off; off = kRecFar; }
+    } else
     if (ballot(have && !tag && off > kRecOffMax)) { S.err = kErrWindowTooLarge; return; }      // beyond what a record holds (windows above 512 MiB)
     if (have) rec[base + lane] = rec_pack(ll, ml, off, tag);
     S.s0 = s0; S.s1 = s1; S.s2 = s2; S.outBase += totalOut; S.litUsed += totalLit;
@@ -240,11 +249,13 @@ __device__ __forceinline__ void seq_fields_batch(const SeqLds& L, u32 buf, u32 s
 // kSet (with kReady; ZSTD_d_refMultipleDDicts with two or more DDicts in the set): the dictionary is the one of the block's own frame,
 // slots[frames[B.frame].dictSlot].  Phase A gives a wave ONE (block, table) task at a time, so what it reads of the record is
 // wave-uniform per task although the workgroup's kPack blocks may sit behind kPack dictionaries; phases B and C read no dictionary.
-template <bool kReady, bool kSet = false>
+// kFar (a call with a far-capable frame): farPlane holds one word per record, and a block may state a far offset when its own frame's
+// content plus the dictionary's (dictSize; kSet: its slot's) exceeds kRecOffMax.  Launched for no other call: kFar = false has no plane.
+template <bool kReady, bool kSet = false, bool kFar = false>
 __device__ __forceinline__ void seq_decode_body(const u8* __restrict__ src, const FrameDesc* __restrict__ frames, BlockDesc* __restrict__ blocks,
                                                 u32 nBlocks, SeqRec* __restrict__ recs, u32* __restrict__ status,
                                                 const u8* __restrict__ dictFull, const DictInfo* __restrict__ di, const u32* __restrict__ dictTabs,
-                                                const DictSlot* __restrict__ slots = nullptr)
+                                                const DictSlot* __restrict__ slots = nullptr, u32* __restrict__ farPlane = nullptr, u32 dictSize = 0)
 {
     __shared__ SeqLds L;
     const u32 lane = lane_id(), wave = uniform(wave_id()), b0 = blockIdx.x * kPack;
@@ -340,6 +351,18 @@ __device__ __forceinline__ void seq_decode_body(const u8* __restrict__ src, cons
     const u32 litA = read_lane(mLitSize, slA), litB = read_lane(mLitSize, slB);
     SeqRec* __restrict__ const recA = recs + read_lane64(mSeqBase, slA);
     SeqRec* __restrict__ const recB = recs + read_lane64(mSeqBase, slB);
+    u32* farA = nullptr; u32* farB = nullptr; bool farOkA = false, farOkB = false;
+    if constexpr (kFar) {
+        u32 mFarOk = 0;
+        if (lane < kPack && b0 + lane < nBlocks) {
+            const FrameDesc& F = frames[MB.frame];
+            u32 ds = dictSize;
+            if constexpr (kSet) { const DictSlot& D = slots[F.dictSlot]; ds = D.content ? D.contentSize : 0u; }
+            mFarOk = F.dstSize + ds > kRecOffMax ? 1u : 0u;
+        }
+        farA = farPlane + read_lane64(mSeqBase, slA); farB = farPlane + read_lane64(mSeqBase, slB);
+        farOkA = read_lane(mFarOk, slA) != 0; farOkB = read_lane(mFarOk, slB) != 0;
+    }
     const u32* const mT = L.tab[lane < kPack ? lane : 0];
     // ---- the top 2 KiB of every stream into its ring (zeros outside the stream) ----
     s32 loA = 0, loB = 0;                                           // helper waves: lowest staged byte of their blocks (multiples of 4)
@@ -404,8 +427,8 @@ __device__ __forceinline__ void seq_decode_body(const u8* __restrict__ src, cons
             // ---- phase C for the previous 64 sequences of this wave's blocks ----
             if (bt) {
                 const u32 pbase = base - 64, buf = (bt - 1) & 1;
-                if (pbase < nbA && !SA.err) seq_fields_batch(L, buf, slA, pbase, nbA, spA, sizeA, litA, recA, SA, lane);
-                if (pbase < nbB && !SB.err) seq_fields_batch(L, buf, slB, pbase, nbB, spB, sizeB, litB, recB, SB, lane);
+                if (pbase < nbA && !SA.err) seq_fields_batch<kFar>(L, buf, slA, pbase, nbA, spA, sizeA, litA, recA, SA, lane, farA, farOkA);
+                if (pbase < nbB && !SB.err) seq_fields_batch<kFar>(L, buf, slB, pbase, nbB, spB, sizeB, litB, recB, SB, lane, farB, farOkB);
             }
             // ---- their streams: stage down to 2 KiB below where the chain stands now.  What that overwrites in the ring lies 16
             // bytes or more above the chain's position (dead: it only moves down); a batch consumes at most 712 bytes and the
@@ -490,9 +513,27 @@ void launch_seq_decode_d(const u8* src, const FrameDesc* frames, BlockDesc* bloc
     else          hipLaunchKernelGGL(seq_decode_d_kernel, grid, dim3(256), 0, stream, src, frames, blocks, recs, status, dd.dictFull, dd.dinfo);
 }
 
-void launch_seq_decode(const u8* src, const FrameDesc* frames, BlockDesc* blocks, u32 nBlocks, SeqRec* recs, u32* status, const DecodeDict& dd, hipStream_t stream)
+// The far instances (a call with a far-capable frame; seq_decode_body): one entry point for the three modes, each taking what it reads
+template <bool kReady, bool kSet>
+__global__ __launch_bounds__(256) void seq_decode_far_kernel(const u8* __restrict__ src, const FrameDesc* __restrict__ frames, BlockDesc* __restrict__ blocks,
+                                                             u32 nBlocks, SeqRec* __restrict__ recs, u32* __restrict__ status,
+                                                             const u8* __restrict__ dictFull, const DictInfo* __restrict__ di, const u32* __restrict__ dictTabs,
+                                                             const DictSlot* __restrict__ slots, u32* __restrict__ farPlane, const u32 dictSize)
+{
+    seq_decode_body<kReady, kSet, true>(src, frames, blocks, nBlocks, recs, status, kSet ? nullptr : dictFull, kSet ? nullptr : di,
+                                        kReady && !kSet ? dictTabs : nullptr, kSet ? slots : nullptr, farPlane, kSet ? 0u : dictSize);
+}
+
+void launch_seq_decode(const u8* src, const FrameDesc* frames, BlockDesc* blocks, u32 nBlocks, SeqRec* recs, u32* status, const DecodeDict& dd, hipStream_t stream, u32* far)
 {
     const dim3 grid((nBlocks + kPack - 1) / kPack);
+    if (far) {
+        const u32 ds = dd.dictContent ? dd.dictContentSize : 0u;
+        if (dd.slots) hipLaunchKernelGGL((seq_decode_far_kernel<true, true>), grid, dim3(256), 0, stream, src, frames, blocks, nBlocks, recs, status, dd.dictFull, dd.dinfo, dd.seqTabs, dd.slots, far, ds);
+        else if (dd.seqTabs) hipLaunchKernelGGL((seq_decode_far_kernel<true, false>), grid, dim3(256), 0, stream, src, frames, blocks, nBlocks, recs, status, dd.dictFull, dd.dinfo, dd.seqTabs, dd.slots, far, ds);
+        else          hipLaunchKernelGGL((seq_decode_far_kernel<false, false>), grid, dim3(256), 0, stream, src, frames, blocks, nBlocks, recs, status, dd.dictFull, dd.dinfo, dd.seqTabs, dd.slots, far, ds);
+        return;
+    }
     if (dd.slots) hipLaunchKernelGGL(seq_decode_set_kernel, grid, dim3(256), 0, stream, src, frames, blocks, nBlocks, recs, status, dd.slots);
     else if (dd.seqTabs) hipLaunchKernelGGL(seq_decode_ready_kernel, grid, dim3(256), 0, stream, src, frames, blocks, nBlocks, recs, status, dd.dictFull, dd.dinfo, dd.seqTabs);
     else          hipLaunchKernelGGL(seq_decode_kernel, grid, dim3(256), 0, stream, src, frames, blocks, nBlocks, recs, status, dd.dictFull, dd.dinfo);
@@ -637,10 +678,13 @@ void launch_place_literals_d(const u8* src, u8* out, const u8* scratch, const Fr
 // an inlined body: inlining turns the arguments' __restrict__ into scoped metadata, and the register allocation of the parent's
 // instances moved with it.)
 // kDev (ZSTDMI_decompressBatchAsync): the number of frames comes from the status words (list_count, zmi_decode.h)
-template <bool kSet, bool kDev = false>
+// kFar (a call with a far-capable frame, never with kDev): farPlane holds the offsets of the records that carry kRecFar (seq_batch).  No
+// other instance reads the argument.  Far or near, an offset is held against position + dictionary before a byte is read through it.
+template <bool kSet, bool kDev = false, bool kFar = false>
 __global__ __launch_bounds__(64) void exec_matches_kernel(const u8* __restrict__ src, u8* __restrict__ out, const FrameDesc* __restrict__ frames,
                                                           const BlockDesc* __restrict__ blocks, u32 nFrames, const SeqRec* __restrict__ recs,
-                                                          u32* __restrict__ status, const u8* __restrict__ dictArg, const u32 dictSizeArg)
+                                                          u32* __restrict__ status, const u8* __restrict__ dictArg, const u32 dictSizeArg,
+                                                          const u32* __restrict__ farPlane)
 {
     const u32 f = blockIdx.x, lane = threadIdx.x;
     if (f >= list_count<kDev>(nFrames, status, kStFrames) || status[kStErr]) return;
@@ -677,7 +721,8 @@ __global__ __launch_bounds__(64) void exec_matches_kernel(const u8* __restrict__
             const SeqRec r = rNext;
             if (base + 64 + lane < nbSeq) rNext = rec[base + 64 + lane];
             SeqLane q;
-            outBase = seq_batch(r, have, in0, in1, in2, outBase, q);
+            if constexpr (kFar) outBase = seq_batch<true>(r, have, in0, in1, in2, outBase, q, farPlane + B.seqBase + base + lane);
+            else outBase = seq_batch(r, have, in0, in1, in2, outBase, q);
             const u32 ll = q.ll, ml = q.ml, pos = q.pos, off = q.off;
             ZMI_SSTAMP(0);
             const u32 dMatch = pos + ll;                          // block-relative start of my match
@@ -795,10 +840,11 @@ __global__ __launch_bounds__(64) void exec_matches_kernel(const u8* __restrict__
 // touches (an index interval, found by binary search over the batch's bounds in LDS), a round runs every match whose interval is
 // complete.  The done bits are double-buffered by round parity, so one barrier per round is enough.
 // ------------------------------------------------------------------------------------------------
-template <int W, bool kSet = false, bool kDev = false>
+template <int W, bool kSet = false, bool kDev = false, bool kFar = false>
 __global__ __launch_bounds__(64 * W) void exec_matches_wide_kernel(const u8* __restrict__ src, u8* __restrict__ out, const FrameDesc* __restrict__ frames,
                                                                    const BlockDesc* __restrict__ blocks, u32 nFrames, const SeqRec* __restrict__ recs,
-                                                                   u32* __restrict__ status, const u8* __restrict__ dictArg, const u32 dictSizeArg)
+                                                                   u32* __restrict__ status, const u8* __restrict__ dictArg, const u32 dictSizeArg,
+                                                                   const u32* __restrict__ farPlane)
 {
     constexpr u32 kB = 64u * W;                                  // sequences per batch
     __shared__ u32 endOfOut[kB], startOfOut[kB];                 // block-relative bounds of the batch's match outputs (monotone; 0xFFFFFFFF: no sequence)
@@ -840,6 +886,7 @@ __global__ __launch_bounds__(64 * W) void exec_matches_wide_kernel(const u8* __r
             if (have) {
                 u32 tag; rec_unpack(r, ll, ml, off, tag);
                 if (tag) { const u32 in = tag == 1 ? in0 : tag == 2 ? in1 : in2; off = in > off ? in - off : 1u; }
+                if constexpr (kFar) { if (!tag && (off & kRecFar)) off = farPlane[B.seqBase + base + tid]; }
             }
             const u32 incl = wave_scan_incl(ll + ml);
             if (lane == 63) waveSum[wave] = incl;
@@ -963,27 +1010,29 @@ __global__ __launch_bounds__(64 * W) void exec_matches_wide_kernel(const u8* __r
 // 16 waves 2.4; 1024 frames: 6.8 / 5.5 / 4.3 / 5.7 / 7.3 at 1 / 2 / 4 / 8 / 16; 2048 frames: 8.3 / 6.5 / 8.0 at 1 / 2 / 4; 4096
 // frames: 9.8 / 12.3 at 1 / 2 — i.e. as many waves as keep frames x waves at about 4096 (the caller's rule, decompress_device)
 static void launch_exec(const u8* src, u8* out, const FrameDesc* frames, const BlockDesc* blocks, u32 count, const SeqRec* recs, u32* status,
-                        const DecodeDict& dd, bool dev, hipStream_t stream, int wide)
+                        const DecodeDict& dd, bool dev, hipStream_t stream, int wide, const u32* farPlane = nullptr)
 {
     // the set instances: the slot table rides in the dictionary pointer's place.  The others: a raw-content dictionary (or a formatted one's
     // content) = history in front of EVERY frame (ZSTD_refDictContent, U/ZstdDecompress.cs:1758-1771); may be null
     const u8* const dict = dd.slots ? reinterpret_cast<const u8*>(dd.slots) : dd.dictContent;
     const u32 ds = !dd.slots && dd.dictContent ? dd.dictContentSize : 0u;
     const u32 nFrames = dev ? 0u : count;                       // (a kDev instance reads the count from the status words)
-    with_flags([&](auto set, auto d) {
+    with_flags([&](auto set, auto d, auto far) {
+        if constexpr (d() && far()) return;                     // (a batch enqueued from the device has no far plane)
+        else
         switch (wide) {
-        case 16: hipLaunchKernelGGL((exec_matches_wide_kernel<16, set(), d()>), dim3(count), dim3(1024), 0, stream, src, out, frames, blocks, nFrames, recs, status, dict, ds); return;
-        case 8:  hipLaunchKernelGGL((exec_matches_wide_kernel<8, set(), d()>),  dim3(count), dim3(512),  0, stream, src, out, frames, blocks, nFrames, recs, status, dict, ds); return;
-        case 4:  hipLaunchKernelGGL((exec_matches_wide_kernel<4, set(), d()>),  dim3(count), dim3(256),  0, stream, src, out, frames, blocks, nFrames, recs, status, dict, ds); return;
-        case 2:  hipLaunchKernelGGL((exec_matches_wide_kernel<2, set(), d()>),  dim3(count), dim3(128),  0, stream, src, out, frames, blocks, nFrames, recs, status, dict, ds); return;
-        default: hipLaunchKernelGGL((exec_matches_kernel<set(), d()>), dim3(count), dim3(64), 0, stream, src, out, frames, blocks, nFrames, recs, status, dict, ds);
+        case 16: hipLaunchKernelGGL((exec_matches_wide_kernel<16, set(), d(), far()>), dim3(count), dim3(1024), 0, stream, src, out, frames, blocks, nFrames, recs, status, dict, ds, farPlane); return;
+        case 8:  hipLaunchKernelGGL((exec_matches_wide_kernel<8, set(), d(), far()>),  dim3(count), dim3(512),  0, stream, src, out, frames, blocks, nFrames, recs, status, dict, ds, farPlane); return;
+        case 4:  hipLaunchKernelGGL((exec_matches_wide_kernel<4, set(), d(), far()>),  dim3(count), dim3(256),  0, stream, src, out, frames, blocks, nFrames, recs, status, dict, ds, farPlane); return;
+        case 2:  hipLaunchKernelGGL((exec_matches_wide_kernel<2, set(), d(), far()>),  dim3(count), dim3(128),  0, stream, src, out, frames, blocks, nFrames, recs, status, dict, ds, farPlane); return;
+        default: hipLaunchKernelGGL((exec_matches_kernel<set(), d(), far()>), dim3(count), dim3(64), 0, stream, src, out, frames, blocks, nFrames, recs, status, dict, ds, farPlane);
         }
-    }, dd.slots != nullptr, dev);
+    }, dd.slots != nullptr, dev, farPlane != nullptr);
 }
 void launch_exec_matches(const u8* src, u8* out, const FrameDesc* frames, const BlockDesc* blocks, u32 nFrames, const SeqRec* recs, u32* status,
-                         const DecodeDict& dd, hipStream_t stream, int wide)
+                         const DecodeDict& dd, hipStream_t stream, int wide, const u32* far)
 {
-    launch_exec(src, out, frames, blocks, nFrames, recs, status, dd, false, stream, wide);
+    launch_exec(src, out, frames, blocks, nFrames, recs, status, dd, false, stream, wide, far);
 }
 // the same instances with the number of frames from the status words, over a grid of the caller's limit (ZSTDMI_decompressBatchAsync)
 void launch_exec_matches_d(const u8* src, u8* out, const FrameDesc* frames, const BlockDesc* blocks, u32 capFrames, const SeqRec* recs, u32* status,

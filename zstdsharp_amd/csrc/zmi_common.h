@@ -167,11 +167,16 @@ struct BlockDesc {
 // One decoded sequence (U/ZstdDecompressBlock.cs:2360-2484) as seq_decode leaves it for the executors, packed into 8 bytes:
 //   bits  0-16  litLength (<= 131071: LL_base[35] + 16 extra bits)
 //   bits 17-33  matchLength - 3 (<= 131071: ML_base[52] + 16 extra bits - 3)
-//   bits 34-63  bit 29 clear: the match offset (1 .. 2^29 - 1; a frame that reaches further back is refused with windowTooLarge);
-//               bit 29 set: a repcode left symbolic — bits 27-28 = i (1..3), bits 0-26 = d: the offset is max(repIn[i - 1] - d, 1)
+//   bits 34-63  bit 29 clear: the match offset (1 .. 2^29 - 1);
+//               bit 29 set, bits 27-28 = i (1..3): a repcode left symbolic — bits 0-26 = d: the offset is max(repIn[i - 1] - d, 1)
+//               bit 29 set, bits 27-28 = 0 (kRecFar): a far offset (2^29 and more, a repeat of one included) — its 32 bits are the
+//               record's word of the far plane, one u32 per record, which only a call with a far-capable frame has (a frame whose
+//               content plus dictionary or prefix content exceeds kRecOffMax: decompress_device).  Every other call passes no plane
+//               and refuses such an offset with windowTooLarge, as do the batch, range and segmented paths.
 // The output position is not stored: consumers walk a block's records in order and carry the running sum of litLength + matchLength.
 struct SeqRec { u32 lo, hi; };
 constexpr u32 kRecOffMax = (1u << 29) - 1;
+constexpr u32 kRecFar = 1u << 29;
 
 // A batch of independent entries (ZSTDMI_decompressBatch): what the host says of entry e, and what the batch walk finds in it.
 // Offsets are relative to one base pointer each for sources and destinations (the lowest of the call); the lists of all entries

@@ -498,13 +498,17 @@ __device__ __forceinline__ void rec_unpack(const SeqRec r, u32& ll, u32& ml, u32
 // one batch of up to 64 records of a block, one per lane, as the in-order consumers see it: lengths, the resolved offset, and the
 // block-relative position of the sequence's literals (`outBase` = the running sum before the batch; returns the sum after it).
 // `next` holds the batch's records (loaded one batch ahead by the caller).  Lanes >= cnt get ll = ml = 0.
+// kFar (a call with a far-capable frame, kRecFar in zmi_common.h): `far` is the lane's own word of the far plane, read only behind a
+// record that carries the mark; kFar = false reads nothing and is the function as it always was.
 struct SeqLane { u32 ll, ml, off, pos; };
-__device__ __forceinline__ u32 seq_batch(const SeqRec r, bool have, u32 in0, u32 in1, u32 in2, u32 outBase, SeqLane& q)
+template <bool kFar = false>
+__device__ __forceinline__ u32 seq_batch(const SeqRec r, bool have, u32 in0, u32 in1, u32 in2, u32 outBase, SeqLane& q, const u32* far = nullptr)
 {
     q.ll = 0; q.ml = 0; q.off = 1;
     if (have) {
         u32 tag; rec_unpack(r, q.ll, q.ml, q.off, tag);
         if (tag) { const u32 in = tag == 1 ? in0 : tag == 2 ? in1 : in2; q.off = in > q.off ? in - q.off : 1u; }
+        if constexpr (kFar) { if (!tag && (q.off & kRecFar)) q.off = *far; }
     }
     const u32 incl = wave_scan_incl(q.ll + q.ml);
     q.pos = outBase + incl - q.ll - q.ml;

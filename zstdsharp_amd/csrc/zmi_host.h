@@ -202,7 +202,10 @@ void launch_dict_ctables(const u8* dict, u32 dictSize, const DictInfo* info, Dic
 void launch_block_prepass(const u8* src, FrameDesc* frames, BlockDesc* blocks, u32 nFrames, u32 nBlocks, const DecodeDict& dd, u32 earlyLiterals, u32* status, hipStream_t stream,
                           u32 phantoms = 0, bool open = false);     // phantoms, open: decode_walk.hip block_link_body
 // (dd.seqTabs not null: the kernel's instance that copies a DDict's ready-made tables where a block repeats the dictionary's)
-void launch_seq_decode(const u8* src, const FrameDesc* frames, BlockDesc* blocks, u32 nBlocks, SeqRec* recs, u32* status, const DecodeDict& dd, hipStream_t stream);
+// far (here, in launch_exec_matches and in launch_origin_init; null: none): the far plane of a call with a far-capable frame, one u32 per
+// sequence record (kRecFar, zmi_common.h); the launcher then starts the stage's far instance
+void launch_seq_decode(const u8* src, const FrameDesc* frames, BlockDesc* blocks, u32 nBlocks, SeqRec* recs, u32* status, const DecodeDict& dd, hipStream_t stream,
+                       u32* far = nullptr);
 // A formatted dictionary's three sequence decoding tables, built once (ZSTD_createDDict): words [0, 1280) are the image seq_decode_kernel
 // holds per block in LDS (LL at 0, ML at 512, OF at 1024), words kDictTabLogs + 0 / 1 / 2 the LL / OF / ML table logs (all ones: corrupt)
 constexpr u32 kDictTabLogs = 1280, kDictTabWords = 1284;
@@ -227,10 +230,10 @@ inline void xxh_carry_reset(XxhCarry* x)
     x->acc[0] = P1 + P2; x->acc[1] = P2; x->acc[2] = 0; x->acc[3] = 0 - P1;
 }
 void launch_exec_matches(const u8* src, u8* out, const FrameDesc* frames, const BlockDesc* blocks, u32 nFrames, const SeqRec* recs, u32* status,
-                         const DecodeDict& dd, hipStream_t stream, int wide);
+                         const DecodeDict& dd, hipStream_t stream, int wide, const u32* far = nullptr);
 void launch_origin_select(FrameDesc* frames, u32 nFrames, u64 minBytes, u32* list, u32 listCap, u64 originCap, u32* status, hipStream_t stream);
 void launch_origin_init(const FrameDesc* frames, const BlockDesc* blocks, const u32* list, u32 listCap, u64 maxFrameBytes, const SeqRec* recs, u32* status,
-                        u32* origin, const DecodeDict& dd, hipStream_t stream);
+                        u32* origin, const DecodeDict& dd, hipStream_t stream, const u32* far = nullptr);
 void launch_origin_jump(const FrameDesc* frames, const u32* list, u32 listCap, u64 maxFrameBytes, u32* status, u32* origin, u32* done, u32 r0, u32 r1, hipStream_t stream);
 void launch_origin_gather(const FrameDesc* frames, const u32* list, u32 listCap, u64 maxFrameBytes, const u32* status, const u32* origin, u8* out, const DecodeDict& dd, hipStream_t stream);
 // a batch of samples through the compressor, sizes (and sequence statistics) only (zstd_mi355x.hip; the dictionary trainer's inner loop)

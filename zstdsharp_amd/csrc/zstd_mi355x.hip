@@ -105,6 +105,9 @@ struct ZSTD_CCtx_s {
     // latest content on the device instead of sTail: sWin holds sWinFill bytes, the last min(sTotal, 2^sSlideLog) of the frame among
     // them, and every batch is appended there (cstream_compress_sliding)
     int slidingLdm = 0;
+    // ZSTDMI_CCtx_setFarOffsets (sticky): offsets of 2^29 and more may be written — a referenced prefix's long form up to prefix + source
+    // = 2^31, a sliding long-distance window of 2^29 or 2^30 (far_limit, check_single_frame).  Off: every refusal is what it was.
+    int farOffsets = 0;
     bool sSliding = false; int sSlideLog = 0; DevBuf sWin; size_t sWinFill = 0;
     // ZSTDMI_CCtx_prepareBatchAsync / ZSTDMI_compressBatchAsync: what the prepare resolved (asyncPrep, valid while cctx_gen() is what it
     // was then; paramGen: bumped by every setter, as dictGen is by every change of the dictionary in force), and the event recorded
@@ -188,6 +191,7 @@ struct CallParams {
     bool entropyCarry = false;          // carry entropy tables and repcodes from block to block (ZSTDMI_CCtx_setEntropyCarry; ZSTD_compressCCtx: never, level-only parameters)
     const u8* pfx = nullptr; size_t pfxSize = 0;    // the long form of a referenced prefix (compress_prefixed): device bytes in front of the ONE frame
     bool single = false;                // one frame per call (ZSTDMI_CCtx_setSingleFrame; ZSTD_compressCCtx: never, level-only parameters)
+    bool farOffsets = false;            // offsets of 2^29 and more may be written (ZSTDMI_CCtx_setFarOffsets; ZSTD_compressCCtx: never, level-only parameters)
     bool sliding = false;               // ... whose long-distance window slides with it (ZSTDMI_CCtx_setSlidingLdm; takes effect where sliding_active says)
     // a batch of a single-frame stream session (cstream_compress_single): streamAt bytes of the frame lie in front of it (the last
     // kStreamTail of them readable in front of the source), and the batch ends the frame or not
@@ -201,7 +205,7 @@ static CallParams sticky_params(const ZSTD_CCtx* c)
     p.dictEntropy = c->dictEntropy != 0;
     p.entropyCarry = c->entropyCarry != 0;
     p.dictIndex = c->dictIndex != 0; p.dictIndexStrategy = c->dictIndexStrategy; p.dictIndexChain = c->dictIndexChain != 0;
-    p.single = c->singleFrame != 0; p.sliding = c->slidingLdm != 0;
+    p.single = c->singleFrame != 0; p.sliding = c->slidingLdm != 0; p.farOffsets = c->farOffsets != 0;
     p.ldm = c->ldm; p.ldmHashLog = c->ldmHashLog; p.ldmMinMatch = c->ldmMinMatch; p.ldmBucketSizeLog = c->ldmBucketSizeLog; p.ldmHashRateLog = c->ldmHashRateLog;
     return p;
 }
@@ -329,7 +333,12 @@ struct Framing { u32 prefixLen, chunkBytes, frameBlocks; Resolved rs; u32 indepW
 // left at 0 follow from it as ZSTD_ldm_adjustParameters derives them (U/ZstdLdm.cs:187-212).  ZSTD_ps_auto and ZSTD_ps_disable
 // are off: the reference's auto rule (btopt and above with windowLog >= 27) is not adopted, so no level's output changes.
 constexpr int kLdmDefaultWindowLog = 27;
-constexpr u64 kLdmMaxFrame = (u64)512 << 20;        // every offset stays below the decoder's 2^29 record limit (kRecOffMax)
+constexpr u64 kLdmMaxFrame = (u64)512 << 20;        // every offset stays below 2^29, what the decoder's sequence record packs (kRecOffMax)
+// With ZSTDMI_CCtx_setFarOffsets on, what a referenced prefix and its source may span together, and the largest sliding window: ldm.hip's
+// positions are 32-bit in the pass's virtual coordinate (prefix or window rounded up to a tile, then the pass of at most 2^31 bytes),
+// so 2^30 + 2^31 is the most that stays inside it; a window of 2^31 would not.  Aligned long-distance frames keep kLdmMaxFrame.
+constexpr u64 kFarMaxSpan = (u64)1 << 31;
+constexpr int kSlideMaxLog = 28, kFarSlideMaxLog = 30;
 static int ldm_window_log(const CallParams& cp) { return cp.windowLog ? cp.windowLog : kLdmDefaultWindowLog; }
 static bool ldm_active(const CallParams& cp, size_t paramSize) { return cp.ldm == 1 && paramSize > kChunkSize && ldm_window_log(cp) >= 17; }
 // the window of a referenced prefix in front of srcSize bytes: ceil_log2(prefixSize + srcSize), at least 17
@@ -672,7 +681,7 @@ static size_t compress_range(ZSTD_CCtx* c, const CallParams& cp, u8* d_dst, size
     const DictCTables* const dct = ls.dct;
     const u64 totalChunks = (srcSize + chunkBytes - 1) / chunkBytes;
     u32 passChunks = (u32)(totalChunks < c->passChunks ? totalChunks : c->passChunks);
-    if (fr.ldm) { const u32 fit = (u32)(((u64)1 << 31) / chunkBytes), most = fr.slideLog ? fit : whole_frame_chunks(fit, frameBlocks); if (passChunks > most) passChunks = most; }    // (ldm.hip: u32 offsets in a pass; a sliding window adds at most 2^28 in front)
+    if (fr.ldm) { const u32 fit = (u32)(((u64)1 << 31) / chunkBytes), most = fr.slideLog ? fit : whole_frame_chunks(fit, frameBlocks); if (passChunks > most) passChunks = most; }    // (ldm.hip: u32 positions in a pass; a sliding window adds at most 2^30 in front, a prefix at most 2^30 + a tile: window + pass stay below 2^32)
     if (frameBlocks && !fr.single && passChunks < totalChunks) { passChunks = whole_frame_chunks(passChunks, frameBlocks); if (!passChunks) passChunks = frameBlocks; }     // frames never straddle passes
     // carried entropy state: a one-shot call's passes of the one frame are whole carry groups, so that the bytes do not depend on
     // ZSTDMI_CCtx_setPassChunks (a stream's batch ends a group where it ends)
@@ -828,8 +837,8 @@ static size_t check_single_frame(const ZSTD_CCtx* c, const CallParams& cp, size_
     if (cp.windowLog >= 10 && cp.windowLog < 18) return ZERR(kErrParameterUnsupported); // (the finders reach up to 2^18 back)
     if (cp.useDict && (dict_in_force(c).dictFormatted || dict_in_force(c).dictHost.size() >= 8)) return ZERR(kErrParameterUnsupported);   // (a dictionary's framing: a prefix in front of independent blocks)
     if (cp.stream ? cp.ldm == 1 : ldm_active(cp, srcSize)) {       // one LDM frame is one frame already (bytes unchanged); more than one is not,
-        if (cp.stream || srcSize > ldm_frame_span(c, cp, srcSize)) {  // unless the window slides (ZSTDMI_CCtx_setSlidingLdm): up to 2^28, the decoder's 29-bit offset record
-            if (!cp.sliding || ldm_window_log(cp) > 28) return ZERR(kErrParameterUnsupported);
+        if (cp.stream || srcSize > ldm_frame_span(c, cp, srcSize)) {  // unless the window slides (ZSTDMI_CCtx_setSlidingLdm): up to 2^28 (what a sequence record of the decoder packs), with ZSTDMI_CCtx_setFarOffsets up to 2^30
+            if (!cp.sliding || ldm_window_log(cp) > (cp.farOffsets ? kFarSlideMaxLog : kSlideMaxLog)) return ZERR(kErrParameterUnsupported);
         }
     }
     return 0;
@@ -1216,7 +1225,7 @@ static size_t compress_prefixed(ZSTD_CCtx* c, void* dst, size_t dstCapacity, con
     }
     { const size_t e2 = check_call_params(cp); if (isErr(e2)) return e2; }
     if (cp.ldm == ZSTD_ps_disable || !cp.contentSizeFlag) return ZERR(kErrParameterUnsupported);
-    if ((u64)pfxSize + srcSize > kLdmMaxFrame) return ZERR(kErrParameterUnsupported);       // (the decoder's 29-bit offset record)
+    if ((u64)pfxSize + srcSize > (cp.farOffsets ? kFarMaxSpan : kLdmMaxFrame)) return ZERR(kErrParameterUnsupported);       // (offsets of 2^29 and more: only with ZSTDMI_CCtx_setFarOffsets)
     if (cp.windowLog && cp.windowLog < 31 && ((u64)1 << cp.windowLog) < (u64)pfxSize + srcSize) return ZERR(kErrParameterUnsupported);
     cp.pfxSize = pfxSize;
     { const Framing fr = resolve_framing(c, cp, srcSize); if ((srcSize + fr.chunkBytes - 1) / fr.chunkBytes > c->passChunks) return ZERR(kErrParameterUnsupported); }
@@ -1402,6 +1411,7 @@ static size_t compress_multi(ZSTD_CCtx* c, const CallParams& cp, void* dst, size
         w->historyBytes = c->historyBytes; w->frameBytes = c->frameBytes; w->parser = c->parser; w->passChunks = c->passChunks; w->timer.enabled = c->timer.enabled;
         w->dictEntropy = c->dictEntropy;        // (before the dictionary: a worker builds the tables when it uploads its copy)
         w->entropyCarry = c->entropyCarry;
+        w->farOffsets = c->farOffsets;
         w->dictIndex = c->dictIndex; w->dictIndexStrategy = c->dictIndexStrategy; w->dictIndexChain = c->dictIndexChain;       // (and the index, as far up the strategies as the parent's)
         if (w->dictGen != c->dictGen) {
             w->own.dictHost = c->own.dictHost; w->own.dictFull = c->own.dictFull; w->own.dictWide = c->own.dictWide; w->own.dictFormatted = c->own.dictFormatted; w->own.info = c->own.info; w->dictDirty = true; w->dictGen = c->dictGen;
@@ -1717,6 +1727,7 @@ size_t ZSTDMI_CCtx_setSeekTable(ZSTD_CCtx* c, unsigned mode) { if (!c) return ZE
 // (no device is touched; what the switch cannot be combined with is refused by the call that would have to do it: check_single_frame)
 size_t ZSTDMI_CCtx_setSingleFrame(ZSTD_CCtx* c, unsigned mode) { if (!c) return ZERR(kErrGeneric); if (mode > 1) return ZERR(kErrParameterOutOfBound); c->singleFrame = (int)mode; c->paramGen++; return 0; }
 // (no device is touched; where the switch takes effect: sliding_active, and what it cannot be combined with: check_single_frame)
+size_t ZSTDMI_CCtx_setFarOffsets(ZSTD_CCtx* c, unsigned mode) { if (!c) return ZERR(kErrGeneric); if (mode > 1) return ZERR(kErrParameterOutOfBound); c->farOffsets = (int)mode; c->paramGen++; return 0; }
 size_t ZSTDMI_CCtx_setSlidingLdm(ZSTD_CCtx* c, unsigned mode) { if (!c) return ZERR(kErrGeneric); if (mode > 1) return ZERR(kErrParameterOutOfBound); c->slidingLdm = (int)mode; c->paramGen++; return 0; }
 size_t ZSTDMI_seekTableBound(size_t srcSize) { return seek_table_bound(srcSize); }
 // (no device is touched: a loaded formatted dictionary is marked for another upload, which builds — or no longer builds — its tables)

@@ -18,6 +18,8 @@ struct ZSTD_DCtx_s {
     bool lastWalkSerial = false; // the last call's frames were listed by the serial walk (ZSTDMI_debugLastWalkSerial)
     int execWaves = 0;          // ZSTDMI_DCtx_setExecWaves: waves per frame in exec_matches, 0 = by the number of frames
     DevBuf frames, blocks, recs, status, scratch, walkWs, slowFlags, stageSrc, stageDst, origin, originList;
+    DevBuf farPlane;            // one u32 per sequence record, only in a call with a far-capable frame (kRecFar, zmi_common.h; decompress_device)
+    int lastFarPlane = 0;       // the last decompress_device run had one (ZSTDMI_debugLastFarPlane)
     DevBuf batchIn, batchOut, blockKeys;    // ZSTDMI_decompressBatch: the entries' table, what the batch walk made of them, one error key per block
     int lastBatchAlone = 0;     // entries of the last ZSTDMI_decompressBatch that were decoded by the single-call path (debug hook)
     // ZSTDMI_DCtx_setBatchUnsized: 1 = an entry of a batch / range(s) call that holds a frame without a content size takes the shared
@@ -109,7 +111,7 @@ static void dctx_async_drain(ZSTD_DCtx* d);
 ZSTD_DCtx_s::ZSTD_DCtx_s()
 {
     tally.self = this; tally.beforeFree = [](void* self) { dctx_async_drain((ZSTD_DCtx_s*)self); };
-    for (DevBuf* b : { &frames, &blocks, &recs, &status, &scratch, &walkWs, &slowFlags, &stageSrc, &stageDst, &origin, &originList, &batchIn, &batchOut, &blockKeys, &litRooms,
+    for (DevBuf* b : { &frames, &blocks, &recs, &status, &scratch, &walkWs, &slowFlags, &stageSrc, &stageDst, &origin, &originList, &farPlane, &batchIn, &batchOut, &blockKeys, &litRooms,
                        &seekTab, &seekSum, &edge, &rangesWs, &rangesIn, &rangesRec, &rangesRes, &arena, &hist[0], &hist[1], &segReps, &segXxh, &dict, &dictInfoDev, &slotTab,
                        &pfxStage, &asyncVerdict, &rangesAsyncWs }) b->owner = &tally;
 }
@@ -174,7 +176,7 @@ size_t ZSTD_freeDCtx(ZSTD_DCtx* d)
         if (d->asyncEv) (void)hipEventDestroy(d->asyncEv);
         d->asyncVerdict.release(); d->rangesAsyncWs.release();
         if (d->ownStream) (void)hipStreamSynchronize(d->ownStream);
-        d->frames.release(); d->blocks.release(); d->recs.release(); d->status.release(); d->scratch.release(); d->walkWs.release(); d->slowFlags.release(); d->stageSrc.release(); d->stageDst.release(); d->dict.release(); d->dictInfoDev.release(); d->origin.release(); d->originList.release(); d->batchIn.release(); d->batchOut.release(); d->blockKeys.release(); d->litRooms.release(); d->seekTab.release(); d->seekSum.release(); d->edge.release(); d->pfxStage.release(); d->rangesWs.release(); d->rangesIn.release(); d->rangesRec.release(); d->rangesRes.release(); d->arena.release(); d->slotTab.release();
+        d->frames.release(); d->blocks.release(); d->recs.release(); d->status.release(); d->scratch.release(); d->walkWs.release(); d->slowFlags.release(); d->stageSrc.release(); d->stageDst.release(); d->dict.release(); d->dictInfoDev.release(); d->origin.release(); d->originList.release(); d->farPlane.release(); d->batchIn.release(); d->batchOut.release(); d->blockKeys.release(); d->litRooms.release(); d->seekTab.release(); d->seekSum.release(); d->edge.release(); d->pfxStage.release(); d->rangesWs.release(); d->rangesIn.release(); d->rangesRec.release(); d->rangesRes.release(); d->arena.release(); d->slotTab.release();
         d->hist[0].release(); d->hist[1].release(); d->segReps.release(); d->segXxh.release();
         d->timer.destroy();
         if (d->aux) { (void)hipStreamSynchronize(d->aux); (void)hipStreamDestroy(d->aux); }
@@ -468,10 +470,12 @@ static int exec_waves_for(const ZSTD_DCtx* d, u32 n) { return d->execWaves ? d->
 // `open` (a batch whose lists hold entries with unsized frames, decode_entries): block_link and block_offsets run their open instances,
 // and batch_rescan_kernel settles those entries' places behind block_offsets, in front of everything that writes into a destination
 // (the literal decoder beside seq_decode writes only where block_link found the place final).
+// `far` (decompress_device alone): some frame of the lists may reach further back than a record's 29 offset bits — seq_decode,
+// exec_matches and origin_init run their far instances over d->farPlane, one u32 per record (4 bytes per sequence of such a call).
 struct StreamLink { u32 phantoms; const DictInfo* reps; };
 struct OpenEntries { const BatchEntryIn* in; BatchEntryOut* out; u32 n; };
 static size_t decode_lists(ZSTD_DCtx* d, const DecodeDict& dd, u8* d_dst, const u8* d_src, u32 nFrames, u32 nBlocks, u32 nUnsized, size_t dstCapacity, u32* st, const std::function<bool()>& tail,
-                           const StreamLink* link = nullptr, const OpenEntries* open = nullptr)
+                           const StreamLink* link = nullptr, const OpenEntries* open = nullptr, bool far = false)
 {
     hipStream_t s = d->stream;
     u32* status = (u32*)d->status.p;
@@ -491,6 +495,8 @@ static size_t decode_lists(ZSTD_DCtx* d, const DecodeDict& dd, u8* d_dst, const 
     d->timer.mark("block_prepass", s);
     const u64 nSeq = st_u64(st, kStSeqLo, kStSeqHi);
     if (!d->recs.ensure((size_t)(nSeq + 64) * sizeof(SeqRec))) return ZERR(kErrMemoryAllocation);
+    if (far && !d->farPlane.ensure((size_t)(nSeq + 64) * sizeof(u32))) return ZERR(kErrMemoryAllocation);
+    u32* const farPlane = far ? (u32*)d->farPlane.p : nullptr;
     // Long frames (decode_origin.hip).  The ordered walk of exec_matches moves a frame at about kWalkRate, all frames at
     // once; the origin path sweeps the frames it is given at about kSweepRate together.  A frame belongs on the origin path when its
     // own walk would outlast the sweep of every frame at least as long: the smallest size class 2^(20+k) with
@@ -534,7 +540,7 @@ static size_t decode_lists(ZSTD_DCtx* d, const DecodeDict& dd, u8* d_dst, const 
         if (hipEventRecord(d->auxDone, d->aux) != hipSuccess) return ZERR(kErrGeneric);
         auxGuard.on = true;
     }
-    launch_seq_decode(d_src, frames, blocks, nBlocks, recs, status, dd, s);     d->timer.mark("seq_decode", s);
+    launch_seq_decode(d_src, frames, blocks, nBlocks, recs, status, dd, s, farPlane);     d->timer.mark("seq_decode", s);
     launch_block_offsets(frames, blocks, nFrames, dd, link && link->reps ? link->reps : dd.dinfo, nUnsized ? 1u : 0u, dstCapacity, status, s, open != nullptr);  d->timer.mark("block_offsets", s);
     if (open) { launch_batch_rescan(open->in, open->out, open->n, frames, s); d->timer.mark("batch_rescan", s); }
     if (auxGuard.on) { if (hipStreamWaitEvent(s, d->auxDone, 0) != hipSuccess) return ZERR(kErrGeneric); d->timer.mark("decode_literals", s); }     // (what of it seq_decode did not cover)
@@ -544,7 +550,7 @@ static size_t decode_lists(ZSTD_DCtx* d, const DecodeDict& dd, u8* d_dst, const 
         const u64 entries = originBytes + 1024 * (u64)originCap, longest = originLongest;
         u32* const origin = (u32*)d->origin.p; const u32* const list = (const u32*)d->originList.p;
         launch_origin_select(frames, nFrames, originMin, (u32*)d->originList.p, originCap, entries, status, s);
-        launch_origin_init(frames, blocks, list, originCap, longest, recs, status, origin, dd, s);    d->timer.mark("origin_init", s);
+        launch_origin_init(frames, blocks, list, originCap, longest, recs, status, origin, dd, s, farPlane);    d->timer.mark("origin_init", s);
         // The rounds in groups of six, the host looking at the last one's verdict in between: ordinary data settles in about ten
         // rounds, and a round that only finds out that nothing is left still costs its launch (the kernels check the flag too).
         for (u32 r = 0; r < kOriginRounds; r += 6) {
@@ -557,7 +563,7 @@ static size_t decode_lists(ZSTD_DCtx* d, const DecodeDict& dd, u8* d_dst, const 
         d->timer.mark("origin_jump", s);
         launch_origin_gather(frames, list, originCap, longest, status, origin, d_dst, dd, s);    d->timer.mark("origin_gather", s);
     }
-    launch_exec_matches(d_src, d_dst, frames, blocks, nFrames, recs, status, dd, s, execWaves);  d->timer.mark("exec_matches", s);
+    launch_exec_matches(d_src, d_dst, frames, blocks, nFrames, recs, status, dd, s, execWaves, farPlane);  d->timer.mark("exec_matches", s);
     if (!tail()) return ZERR(kErrGeneric);
     { const size_t e = status_read(d, st); if (isErr(e)) return e; }
     d->lastDictTabBlocks += st[kStDictTabBlocks];
@@ -568,7 +574,8 @@ static size_t decode_lists(ZSTD_DCtx* d, const DecodeDict& dd, u8* d_dst, const 
 // counting walk, sequence records after the block pre-pass); everything else is one launch sequence:
 //   walk (count) | walk (emit) -> block_parse -> block_link -> seq_scan | seq_decode -> block_offsets [-> frame_rescan]
 //   -> decode_literals -> place_literals -> exec_matches
-static size_t decompress_device(ZSTD_DCtx* d, u8* d_dst, size_t dstCapacity, const u8* d_src, size_t srcSize)
+// allowFar = false (an entry that a batch, range or ranges call left to this path): offsets above kRecOffMax keep the refusal those calls state
+static size_t decompress_device(ZSTD_DCtx* d, u8* d_dst, size_t dstCapacity, const u8* d_src, size_t srcSize, bool allowFar = true)
 {
     hipStream_t s = d->stream;
     if (srcSize == 0) return 0;
@@ -603,7 +610,14 @@ static size_t decompress_device(ZSTD_DCtx* d, u8* d_dst, size_t dstCapacity, con
     if (serialWalk) launch_frame_walk_serial(d_src, srcSize, frames, blocks, maxFrames, status, dd, 1, s);
     else            launch_frame_walk_emit(d_src, srcSize, frames, blocks, (u8*)d->walkWs.p, s);
     d->timer.mark("frame_walk", s);
-    { const size_t e = decode_lists(d, dd, d_dst, d_src, nFrames, nBlocks, nUnsized, dstCapacity, st, [] { return true; }); if (isErr(e)) return e; }
+    // A far-capable frame: its content (an unsized frame: its bound) plus the dictionary or prefix content in front of it exceeds what a
+    // record's offset bits name.  `total` is the sum over the call's frames and the dictionary the largest a frame can have, so the test
+    // errs toward the plane; seq_decode's far instance holds each block to its own frame's reach.
+    u64 dictReach = dd.dictContent ? dd.dictContentSize : 0u;
+    if (dd.slots) for (const DictSlot& r : d->slotHost) if (r.content && r.contentSize > dictReach) dictReach = r.contentSize;
+    const bool far = allowFar && total + dictReach > kRecOffMax;
+    d->lastFarPlane = far ? 1 : 0;
+    { const size_t e = decode_lists(d, dd, d_dst, d_src, nFrames, nBlocks, nUnsized, dstCapacity, st, [] { return true; }, nullptr, nullptr, far); if (isErr(e)) return e; }
     d->timer.finish();
     { const size_t e = status_error(st); if (isErr(e)) return e; }
     if (nUnsized) return (size_t)st_u64(st, kStActualLo, kStActualHi);
@@ -721,7 +735,7 @@ static size_t decompress_batch_impl(ZSTD_DCtx* d, const void* const* srcs, const
     }
     for (size_t i = 0; i < n; i++) {
         if ((srcSizes[i] && !srcs[i]) || hOut[i].state != kBatchAlone) continue;
-        dstSizes[i] = decompress_device(d, (u8*)dsts[i], dstCapacities[i], (const u8*)srcs[i], srcSizes[i]);
+        dstSizes[i] = decompress_device(d, (u8*)dsts[i], dstCapacities[i], (const u8*)srcs[i], srcSizes[i], false);
         d->lastBatchAlone++;
     }
     return 0;
@@ -983,7 +997,7 @@ static size_t decompress_range_impl(ZSTD_DCtx* d, void* dst, size_t dstCapacity,
         e = fetch_entries(d, nSel, hIn, hOut); if (isErr(e)) return e;
         for (u32 i = 0; i < nSel; ++i) {
             if (hOut[i].state != kBatchAlone) continue;
-            const size_t r = decompress_device(d, (u8*)lo + hIn[i].dstOff, (size_t)hIn[i].dstCap, srcBase + hIn[i].srcOff, (size_t)hIn[i].srcSize);
+            const size_t r = decompress_device(d, (u8*)lo + hIn[i].dstOff, (size_t)hIn[i].dstCap, srcBase + hIn[i].srcOff, (size_t)hIn[i].srcSize, false);
             if (isErr(r)) return r == ZERR(kErrDstSizeTooSmall) ? ZERR(kErrCorruption) : r;
             if (r != hIn[i].dstCap) return ZERR(kErrCorruption);
         }
@@ -1075,7 +1089,7 @@ static size_t decompress_ranges_impl(ZSTD_DCtx* d, const void* src, size_t srcSi
             const TimerPause pause(d->timer);       // (decompress_device times itself: the pass keeps its own stages)
             for (u32 i = 0; i < nTouched; ++i) {
                 if (eOut[i].state != kBatchAlone) continue;
-                eOut[i].result = (u64)decompress_device(d, (u8*)d->arena.p + eIn[i].dstOff, (size_t)eIn[i].dstCap, srcBase + eIn[i].srcOff, (size_t)eIn[i].srcSize);
+                eOut[i].result = (u64)decompress_device(d, (u8*)d->arena.p + eIn[i].dstOff, (size_t)eIn[i].dstCap, srcBase + eIn[i].srcOff, (size_t)eIn[i].srcSize, false);
                 if (hipMemcpyAsync((BatchEntryOut*)d->batchOut.p + i, &eOut[i], sizeof(BatchEntryOut), hipMemcpyHostToDevice, s) != hipSuccess) return ZERR(kErrGeneric);
             }
         }
@@ -1808,6 +1822,7 @@ size_t ZSTDMI_DCtx_setStreamSegment(ZSTD_DCtx* d, size_t bytes)
 long long ZSTDMI_debugStreamPeakInput(const ZSTD_DCtx* d) { return d ? d->streamPeakInput : -1; }
 int ZSTDMI_debugStreamSegments(const ZSTD_DCtx* d) { return d ? d->streamSegments : -1; }
 int ZSTDMI_debugLastWalkSerial(const ZSTD_DCtx* d) { return d ? (int)d->lastWalkSerial : -1; }
+int ZSTDMI_debugLastFarPlane(const ZSTD_DCtx* d) { return d ? d->lastFarPlane : -1; }
 size_t ZSTDMI_DCtx_setExecWaves(ZSTD_DCtx* d, unsigned waves) { if (!d || (waves != 0 && waves != 1 && waves != 2 && waves != 4 && waves != 8 && waves != 16)) return ZERR(kErrParameterOutOfBound); d->execWaves = (int)waves; d->paramGen++; return 0; }
 size_t ZSTDMI_DCtx_setOverlap(ZSTD_DCtx* d, unsigned mode) { if (!d || mode > 2) return ZERR(kErrParameterOutOfBound); d->overlapMode = (int)mode; d->paramGen++; return 0; }
 size_t ZSTDMI_DCtx_setLongFrames(ZSTD_DCtx* d, unsigned mode) { if (!d || mode > 2) return ZERR(kErrParameterOutOfBound); d->originMode = (int)mode; d->paramGen++; return 0; }
