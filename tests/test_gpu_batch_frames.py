@@ -239,6 +239,41 @@ def test_pass_boundaries(gpu_lib, oracle):
     c.Dispose()
 
 
+# (level, sizes, batched passes, entries alone) under ZSTDMI_CCtx_setPassChunks(4).  Level 3: chunks of 48 KiB in multi-block frames,
+# around one chunk, one pass and one chunk more than a pass.  Level 1: one chunk of 64 KiB up to 64 KiB, above it blocks of 16 KiB.
+# The counts are ZSTDMI_debugLastBatchPasses / ZSTDMI_debugLastBatchAlone as measured on an MI355X with the library of the commit
+# before compress_entries became a sequence of steps over zmi_batch_pass.h (2026-10-21): the cut and the groups are to stay as they were.
+_CB3 = 49152
+FOUR_CHUNK_PASSES = [
+    (3, (1, _CB3 - 1, _CB3, _CB3 + 1, 2 * _CB3, 3 * _CB3 + 1, 4 * _CB3, 4 * _CB3 + 1, 0), 5, 2),
+    (1, (65536, 70000, 1000), 2, 1),
+]
+
+
+@pytest.mark.parametrize("level,sizes,passes,alone", FOUR_CHUNK_PASSES, ids=["level3", "level1"])
+def test_passes_of_four_chunks(gpu_lib, oracle, level, sizes, passes, alone):
+    """passes of at most four chunks: every entry's bytes are the single call's, and the call makes the passes and leaves the entries
+    alone that it made and left before the host loop was cut into steps"""
+    entries = tuple(data_of(KINDS[i % len(KINDS)], n, n + 17) for i, n in enumerate(sizes))
+    ctxs = []
+    for _ in range(2):
+        c = make_compressor(level)
+        assert gpu_lib.ZSTDMI_CCtx_setPassChunks(c.cctx, 4) == 0
+        ctxs.append(c)
+    ref, c = ctxs
+    want = single_results(gpu_lib, ref.cctx, entries)
+    b = Batch(gpu_lib, entries, seed=7)
+    assert b.run(c.cctx) == 0
+    for i, e in enumerate(entries):
+        assert b.result(i) == want[i], (level, i, len(e), "differs from the single call")
+        assert oracle.decompress(want[i], len(e)) == e, (level, i, len(e))
+    b.assert_nothing_else_written()
+    got = (gpu_lib.ZSTDMI_debugLastBatchPasses(c.cctx), gpu_lib.ZSTDMI_debugLastBatchAlone(c.cctx))
+    print(f"four-chunk passes, level {level}: passes {got[0]} alone {got[1]}")
+    assert got == (passes, alone)
+    ref.Dispose(); c.Dispose()
+
+
 def far_candidates(lib, c):
     assert lib.ZSTDMI_CCtx_setHistory(c.cctx, 16384, 0) == 0
 

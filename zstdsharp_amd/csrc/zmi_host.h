@@ -13,6 +13,7 @@
 #include "zmi_common.h"
 #include "zmi_frame.h"
 #include "zmi_batch_plan.h"
+#include "zmi_batch_pass.h"
 #include "zmi_dictset.h"
 #include "zmi_cdictset.h"
 #include "../../include/zstd_mi355x.h"
@@ -105,8 +106,8 @@ void launch_batch_place_async_frames(const ChunkMeta* meta, u32 n, u32 nLaunch, 
 // without the dst and cap columns (pack_verdict); the placement decides on the device whether frames plus table fit `cap` and writes
 // every chunk's final address into offsets (kAsyncSpan for all of them after a failure), the empty frames, the rows, *packSize and
 // entryEnds (may be null); the table kernel's grid covers maxRows rows and takes the count and the place from the state.
-// PackAsyncTab: context memory the prepare sized: entAt / entRow per entry, rows[2 * maxRows], state[kPackStateWords].
-enum PackState : u32 { kPackStateOk = 0, kPackStateTableAt = 1, kPackStateRows = 2, kPackStateWords = 4 };
+// PackAsyncTab: context memory the prepare sized: entAt / entRow per entry, rows[2 * maxRows], state[kPackStateWords] (PackState and
+// the layout: zmi_batch_pass.h).
 struct PackAsyncTab { u64* entAt; u32* entRow; u32* rows; u64* state; };
 void launch_pack_plan_entries(const void* const* srcs, const size_t* sizes, u32 n, u64 bound, u32 chunkBytes, u32 maxChunks, const AsyncEntryTab& tab, hipStream_t stream);
 void launch_pack_place_async(const ChunkMeta* meta, u32 n, u32 nLaunch, const AsyncEntryTab& tab, const u32* len, u32 frameBlocks, AsyncEmptyFrame empty, u8* dst,

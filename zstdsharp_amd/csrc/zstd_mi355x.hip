@@ -212,7 +212,7 @@ static CallParams sticky_params(const ZSTD_CCtx* c)
 
 // What a call resolves to: the reference's cParams for (level, chunk size) with the explicitly set strategy /
 // targetLength on top (ZSTD_overrideCParams, U/ZstdCompress.cs:2096-2127), then the parts of them the kernels act on.
-struct Resolved { CParams cp; u32 finder, minStrideLog, rawLiterals; };
+// (struct Resolved: zmi_batch_pass.h, beside the batch's group key, which compares it)
 static Resolved resolve_call(const CallParams& p, size_t srcSize, u32 chunkBytes)
 {
     Resolved r;
@@ -1900,35 +1900,19 @@ size_t ZSTD_compressStream2(ZSTD_CCtx* c, ZSTD_outBuffer* output, ZSTD_inBuffer*
 // beside it.  Multi-block frames behind LDS history (the small-call 16 KiB cut of levels 1-2, the 48 / 32 KiB blocks of the dual-hash
 // and chain finders) take a second column (chunkFrames): the block's index inside its frame and the frame's content size, which the
 // single call derives from its total size; all chunks of an entry but the last are full, so a block's history lies in front of it in
-// the staging buffer as it does in the entry.  With
-// destinations, batch_place_kernel gives every chunk its place as an offset from the lowest destination pointer and huf_encode and
-// gather write there directly (staged_write); without (the trainer), only the sizes come back.  A pass holds whole entries, at most
-// ZSTDMI_CCtx_setPassChunks chunks; per pass one table goes up and the entries' sizes come back in one copy.
+// the staging buffer as it does in the entry.
+// compress_entries (below) is the sequence of the steps that follow: batch_classify sorts the entries into groups and the alone
+// list, a group is cut into passes (batch_pass_cut), batch_pass_image lays out and fills a pass's table (behind per-entry CDicts with
+// batch_slot_table's slots), batch_pass_run runs it, batch_alone_tail takes the rest.  The host decisions among them — the group key,
+// the cut, the table's layout and its fill — are zmi_batch_pass.h's, which tests/host/batch_plan_harness.cpp holds to account.
+//
+// entry_batched -> does an entry of S bytes (S > 0, framed as fr) share a batched pass?  One rule for compress_entries, which sorts
+// its entries by it, and for ZSTDMI_compressPack, which cuts its rounds by it.
 // An entry the class model does not cover — empty, windows below 64 KiB above one window, LDM above one block, more than one block under
 // ZSTDMI_CCtx_setSingleFrame (one frame per entry: a framing of its own), the fast strategy's
 // full 64 KiB blocks with far candidates (no per-chunk tables in that kernel), the sparse-input probe and multi-block frames of
 // 4 MiB and more, more chunks than a pass, several device workers — is compressed alone afterwards, in entry order, by the
-// single-call path, and counted in `alone`.
-// srcs[i]: device pointers.  dsts / caps: device pointers and their capacities, or null (sizes only).  outSizes[i] = the compressed
-// size of entry i (or its error).  d_stats (optional, device, 377 u32): seq_stats_kernel's counts of the batched chunks are added.
-// seekIdx (optional; ZSTDMI_compressPack): the row of c->seekEntries (seekCap rows) at which entry i's frames are filed, one
-// (compressed size, content size) pair per frame, by every pass from its ChunkMeta (pack_entries_kernel).
-// cdicts (optional; ZSTDMI_compressBatchCDicts): entry i is compressed behind cdicts[i] (null: without a dictionary) as after
-// ZSTD_CCtx_refCDict, all of them shareable by this context (on its device, no workers) — or a single one that is not, of which the
-// context holds its private upload (compress_batch_cdicts_impl).  `cp` then holds the context's parameters without
-// a reference; what the call runs with is resolved per distinct CDict, because its level is: CallParams here, LaunchState per pass.
-// For the length of a resolve or a launch the CDict is the context's reference (c->cdict), which is put back at the end.  Entries
-// share a group, and so a pass, by what has to be equal for their chunks to share a launch — chunk size (the staged tail in whole
-// 4 KiB tiles), blocks per frame, indexed or not, the resolved parameters the kernels act on (same_launch_params: a call without
-// `cdicts` keeps its classes by the whole of Resolved, and so its passes) — not by the dictionary nor by the tail's exact length.
-// (Only where nothing of the dictionary is staged or indexed — no dictionary, content below 8 bytes — the finder runs its plain
-// instance, which has no set form and takes the header's dictID bytes as launch constants: such entries group by CDict as well, and
-// never with staged or indexed ones, whatever else is equal: under ZSTD_c_windowLog 10 .. 15 both kinds have chunks of one window.)
-// A pass that holds two or more distinct CDicts uploads a slot table (zmi_cdictset.h) with each chunk's index into it and runs the
-// stages' set instances; a pass behind one is launched exactly as the call without `cdicts` launches it.
-//
-// entry_batched -> does an entry of S bytes (S > 0, framed as fr) share a batched pass?  One rule for compress_entries, which sorts
-// its entries by it, and for ZSTDMI_compressPack, which cuts its rounds by it.
+// single-call path, and counted in `alone` (batch_alone_tail).
 static bool entry_batched(ZSTD_CCtx* c, const CallParams& cp, size_t S, const Framing& fr, u32 passLimit, bool dct, bool stats)
 {
     bool batched = S && !fr.indepWindowLog && !fr.ldm && !fr.single && c->workers.size() <= 1 && chunks_of(S, fr.chunkBytes) <= passLimit;
@@ -1941,27 +1925,37 @@ static bool entry_batched(ZSTD_CCtx* c, const CallParams& cp, size_t S, const Fr
     if (batched && S >= (4u << 20)) { size_t err = 0; if (probe_group_bytes(c, cp, S, err) || isErr(err)) batched = false; }
     return batched;
 }
-// What of two entries' resolved parameters has to be equal for their chunks to share a launch: the parts the kernels act on (finder,
-// probing stride, raw literals, seq_encode's strategy constants, the chain search's depth).  The rest of a CParams — windowLog, hashLog
-// and chainLog, which ZSTD_adjustCParams shrinks with the entry's size — reaches no kernel.
-static bool same_launch_params(const Resolved& a, const Resolved& b)
-{
-    return a.finder == b.finder && a.minStrideLog == b.minStrideLog && a.rawLiterals == b.rawLiterals && a.cp.strategy == b.cp.strategy && a.cp.searchLog == b.cp.searchLog;
-}
 static u32 batch_pass_limit(const ZSTD_CCtx* c) { return c->passChunks < 16384 ? c->passChunks : 16384; }
-static size_t compress_entries(ZSTD_CCtx* c, const CallParams& cp, const u8* const* srcs, const size_t* sizes, size_t n,
-                               u8* const* dsts, const size_t* caps, size_t* outSizes, u32* d_stats, int& alone,
-                               const u32* seekIdx = nullptr, u32 seekCap = 0, const ZSTD_CDict_s* const* cdicts = nullptr)
-{
-    hipStream_t s = c->stream;
-    alone = 0;
-    c->lastRegionList = nullptr;        // (entries that go alone pass through compress_range, which notes its own)
-    c->lastBatchPasses = 0; c->lastBatchSetChunks = 0;
-    const u32 passLimit = batch_pass_limit(c);
+
+// What the steps of one compress_entries call share: its arguments, the per-entry CDicts, and the vectors every pass fills anew.
+// srcs[i]: device pointers.  dsts / caps: device pointers and their capacities, or null (sizes only).  outSizes[i] = the compressed
+// size of entry i (or its error).  d_stats (optional, device, 377 u32): seq_stats_kernel's counts of the batched chunks are added.
+// seekIdx (optional; ZSTDMI_compressPack): the row of c->seekEntries (seekCap rows) at which entry i's frames are filed, one
+// (compressed size, content size) pair per frame, by every pass from its ChunkMeta (pack_entries_kernel).
+// cdicts (optional; ZSTDMI_compressBatchCDicts): entry i is compressed behind cdicts[i] (null: without a dictionary) as after
+// ZSTD_CCtx_refCDict, all of them shareable by this context (on its device, no workers) — or a single one that is not, of which the
+// context holds its private upload (compress_batch_cdicts_impl).  `cp` then holds the context's parameters without
+// a reference; what the call runs with is resolved per distinct CDict, because its level is: CallParams here, LaunchState per pass.
+// For the length of a resolve or a launch the CDict is the context's reference (c->cdict), which is put back at the end.
+struct BatchCall {
+    ZSTD_CCtx* c; const CallParams& cp; const u8* const* srcs; const size_t* sizes; size_t n; u8* const* dsts; const size_t* caps; size_t* outSizes;
+    u32* d_stats; const u32* seekIdx; u32 seekCap; const ZSTD_CDict_s* const* cdicts;
+    const ZSTD_CDict_s* was;
     // per-entry CDicts: the distinct ones, each entry's index among them, and the parameters each of them makes of the context's
     std::vector<const void*> dicts; std::vector<u32> slotOf; std::vector<CallParams> cps; std::vector<size_t> slotErr;
-    struct Restore { ZSTD_CCtx* c; const ZSTD_CDict_s* was; ~Restore() { c->cdict = was; } } restore{c, c->cdict};
-    if (cdicts) {
+    // a pass's table on the host, its sizes as they come back, and the slot table of a pass behind per-entry CDicts
+    std::vector<u8> tab; std::vector<u64> got;
+    std::vector<u32> chunkSlot, used; std::vector<CDictSlot> slotTab; std::vector<u8> slotDone;
+    ~BatchCall() { c->cdict = was; }
+    // the parameters entry i runs with; with per-entry CDicts its CDict becomes the reference in force
+    const CallParams& params_of(size_t i)
+    {
+        if (!cdicts) return cp;
+        c->cdict = (const ZSTD_CDict_s*)dicts[slotOf[i]];
+        return cps[slotOf[i]];
+    }
+    size_t assign_cdicts()
+    {
         const int bad = cdict_slots_assign((const void* const*)cdicts, n, dicts, slotOf);
         if (bad) return bad == 1 ? ZERR(kErrParameterUnsupported) : ZERR(kErrMemoryAllocation);
         for (const void* d : dicts) {
@@ -1969,158 +1963,163 @@ static size_t compress_entries(ZSTD_CCtx* c, const CallParams& cp, const u8* con
             if (d) q.level = ((const ZSTD_CDict_s*)d)->level; else q.useDict = false;
             cps.push_back(q); slotErr.push_back(check_call_params(q));       // (what every single call behind this CDict would answer)
         }
+        return 0;
     }
-    // the parameters entry i runs with; with per-entry CDicts its CDict becomes the reference in force
-    auto params_of = [&](size_t i) -> const CallParams& {
-        if (!cdicts) return cp;
-        c->cdict = (const ZSTD_CDict_s*)dicts[slotOf[i]];
-        return cps[slotOf[i]];
-    };
-    // (cdicts: plain = nothing of the members' dictionaries is staged or indexed, and they all lie behind `slot`; tail = each member's prefixLen)
-    struct Group { Framing fr; u32 slot; bool plain; std::vector<size_t> members; std::vector<u32> tail; };
-    std::vector<Group> groups;
-    std::vector<size_t> aloneList;
-    for (size_t i = 0; i < n; i++) {
-        const size_t S = sizes[i];
-        if (dsts) {         // (the single call's argument checks)
-            if (S && !srcs[i]) { outSizes[i] = ZERR(kErrSrcSizeWrong); continue; }
-            if (!dsts[i]) { outSizes[i] = caps[i] ? ZERR(kErrDstBufferNull) : ZERR(kErrDstSizeTooSmall); continue; }
+};
+// Entries share a group, and so a pass, by same_group (zmi_batch_pass.h).  tail (per-entry CDicts): each member's prefixLen
+struct BatchGroup { Framing fr; u32 slot; std::vector<size_t> members; std::vector<u32> tail; };
+static BatchGroupKey group_key(const Framing& fr, u32 slot) { return BatchGroupKey{ fr.prefixLen, fr.chunkBytes, fr.frameBlocks, fr.dictIndex, fr.rs, slot }; }
+
+// Classify: the single call's argument checks, the entry's framing, and its place — a group, or the alone list
+static void batch_classify(BatchCall& b, u32 passLimit, std::vector<BatchGroup>& groups, std::vector<size_t>& aloneList)
+{
+    ZSTD_CCtx* c = b.c;
+    for (size_t i = 0; i < b.n; i++) {
+        const size_t S = b.sizes[i];
+        if (b.dsts) {         // (the single call's argument checks)
+            if (S && !b.srcs[i]) { b.outSizes[i] = ZERR(kErrSrcSizeWrong); continue; }
+            if (!b.dsts[i]) { b.outSizes[i] = b.caps[i] ? ZERR(kErrDstBufferNull) : ZERR(kErrDstSizeTooSmall); continue; }
         }
-        if (cdicts && isErr(slotErr[slotOf[i]])) { outSizes[i] = slotErr[slotOf[i]]; continue; }
-        const CallParams& cpi = params_of(i);
+        if (b.cdicts && isErr(b.slotErr[b.slotOf[i]])) { b.outSizes[i] = b.slotErr[b.slotOf[i]]; continue; }
+        const CallParams& cpi = b.params_of(i);
         const Framing fr = S ? resolve_framing(c, cpi, S) : Framing{};
-        if (!S || !entry_batched(c, cpi, S, fr, passLimit, call_dict_ctables(c, cpi) != nullptr, d_stats != nullptr)) { aloneList.push_back(i); continue; }
-        outSizes[i] = 0;
-        const u32 slot = cdicts ? slotOf[i] : 0u;
-        const bool plain = !fr.prefixLen && !fr.dictIndex;      // (the finder's plain instance: no set form)
-        Group* g = nullptr;
-        for (auto& x : groups)
-            if ((cdicts ? (x.plain == plain && (!plain || x.slot == slot)) : x.fr.prefixLen == fr.prefixLen) && x.fr.chunkBytes == fr.chunkBytes && x.fr.frameBlocks == fr.frameBlocks && x.fr.dictIndex == fr.dictIndex &&
-                (cdicts ? same_launch_params(x.fr.rs, fr.rs) : !memcmp(&x.fr.rs, &fr.rs, sizeof(Resolved)))) { g = &x; break; }
-        if (!g) { groups.push_back(Group{fr, slot, plain, {}, {}}); g = &groups.back(); }
+        if (!S || !entry_batched(c, cpi, S, fr, passLimit, call_dict_ctables(c, cpi) != nullptr, b.d_stats != nullptr)) { aloneList.push_back(i); continue; }
+        b.outSizes[i] = 0;
+        const u32 slot = b.cdicts ? b.slotOf[i] : 0u;
+        BatchGroup* g = nullptr;
+        for (auto& x : groups) if (same_group(group_key(x.fr, x.slot), group_key(fr, slot), b.cdicts != nullptr)) { g = &x; break; }
+        if (!g) { groups.push_back(BatchGroup{fr, slot, {}, {}}); g = &groups.back(); }
         g->members.push_back(i);
-        if (cdicts) g->tail.push_back(fr.prefixLen);
+        if (b.cdicts) g->tail.push_back(fr.prefixLen);
     }
+}
+
+// Slot table (per-entry CDicts): the launch state of the pass of members [m0, m1) of g is that of its dictionary, or, behind two or
+// more of them, the group's with a slot table (zmi_cdictset.h): each chunk's index into it (b.chunkSlot) and the slots (b.slotTab),
+// each from the first entry behind it.  The pass's state ls and its tail fr.prefixLen are its first entry's.
+static size_t batch_slot_table(BatchCall& b, const BatchGroup& g, size_t m0, size_t m1, Framing& fr, LaunchState& ls)
+{
+    b.chunkSlot.clear();
+    for (size_t m = m0; m < m1; ++m) b.chunkSlot.insert(b.chunkSlot.end(), chunks_of(b.sizes[g.members[m]], fr.chunkBytes), b.slotOf[g.members[m]]);
+    if (!cdict_pass_image(b.chunkSlot, b.used)) return ZERR(kErrMemoryAllocation);
+    b.slotTab.assign(b.used.size(), CDictSlot{});
+    b.slotDone.assign(b.used.size(), 0);
+    for (size_t m = m0; m < m1; ++m) {
+        const size_t i = g.members[m];
+        const size_t k = std::lower_bound(b.used.begin(), b.used.end(), b.slotOf[i]) - b.used.begin();
+        assert(!b.slotDone[k] || b.slotTab[k].tailLen == g.tail[m]);        // (one dictionary, one chunk size: one tail)
+        if (b.slotDone[k]) continue;
+        fr.prefixLen = g.tail[m];
+        const LaunchState lu = launch_state(b.c, b.params_of(i), fr);
+        b.slotTab[k] = CDictSlot{ lu.prefix, lu.dct, lu.dix, fr.prefixLen, lu.header.dictID, lu.header.dictIdBytes, { lu.initReps[0], lu.initReps[1], lu.initReps[2] } };
+        b.slotDone[k] = 1;
+        if (m == m0) ls = lu;
+    }
+    fr.prefixLen = g.tail[m0];
+    return 0;
+}
+
+// One pass: members [m0, m0 + nEnt) of its group, nCh chunks.  A pass that holds two or more distinct CDicts (set) uploads the slot
+// table and runs the stages' set instances; a pass behind one is launched exactly as the call without `cdicts` launches it.
+// carry: carried entropy state (entries of more than one block), the chunks that lead a carry group listed beside the table
+// (zmi_carry.h), so that an entry's bytes are the single call's.
+struct BatchPass {
+    size_t m0; u32 nEnt, nCh; Framing fr; LaunchState ls;
+    bool set, carry; u32 carryGroups; const DictCTables* dct;
+    BatchPassTab t; BatchPassSpan at;
+};
+// the pass's table on the host (b.tab): laid out by batch_pass_tab, filled by batch_pass_fill
+static size_t batch_pass_image(BatchCall& b, const BatchGroup& g, BatchPass& p)
+{
+    const size_t m1 = p.m0 + p.nEnt;
+    if (b.cdicts) { const size_t e = batch_slot_table(b, g, p.m0, m1, p.fr, p.ls); if (isErr(e)) return e; }
+    p.set = b.cdicts && b.used.size() >= 2;
+    p.dct = p.ls.dct;
+    if (p.set) for (const CDictSlot& r : b.slotTab) if (r.dct) p.dct = r.dct;     // (any: "some slot has tables")
+    p.carry = carry_active(b.c, b.params_of(g.members[p.m0]), p.fr, p.ls);
+    p.t = batch_pass_tab(p.nCh, p.nEnt, p.fr.frameBlocks != 0, b.seekIdx != nullptr, p.set ? (u32)b.slotTab.size() : 0u, p.carry);
+    b.tab.assign(p.t.bytes, 0);
+    const BatchPassCols h = batch_pass_cols(p.t, b.tab.data());
+    if (p.set) { memcpy(h.chunkSlot, b.chunkSlot.data(), (size_t)p.nCh * 4); memcpy(h.slots, b.slotTab.data(), b.slotTab.size() * sizeof(CDictSlot)); }
+    p.at = batch_pass_fill(BatchPassEntries{ g.members.data() + p.m0, p.nEnt, b.srcs, b.sizes, b.dsts, b.caps, b.seekIdx }, p.fr.chunkBytes, p.fr.frameBlocks, h);
+    p.carryGroups = 0;
+    if (p.carry) { p.carryGroups = carry_leaders_table(h.frame, p.nCh, h.leaders); b.c->lastCarryGroups += p.carryGroups; }
+    return 0;
+}
+// Run it: per pass one table goes up and the entries' sizes come back in one copy.  With destinations, batch_place_kernel gives every
+// chunk its place as an offset from the lowest destination pointer and huf_encode and gather write there directly (staged_write);
+// without (the trainer), only the sizes come back.
+static size_t batch_pass_run(BatchCall& b, const BatchGroup& g, const BatchPass& p, bool& first)
+{
+    ZSTD_CCtx* c = b.c;
+    hipStream_t s = c->stream;
+    if (!staged_workspace(c, p.ls, p.fr, p.nCh, p.t.bytes + (size_t)p.nEnt * 8)) return ZERR(kErrMemoryAllocation);
+    const BatchPassCols d = batch_pass_cols(p.t, (u8*)c->batchTab.p);
+    if (hipMemcpyAsync(c->batchTab.p, b.tab.data(), p.t.bytes, hipMemcpyHostToDevice, s) != hipSuccess) return ZERR(kErrGeneric);
+    ChunkMeta* meta = (ChunkMeta*)c->meta.p;
+    // (dct: single-block frames only, see entry_batched)
+    StagedPass pass = staged_pass(p.nCh, p.fr, d.from, d.len, d.frame, p.dct, b.cp.checksumFlag);
+    if (p.set) { pass.dSlots = d.slots; pass.dChunkSlot = d.chunkSlot; }
+    const SeqCarry sc = { (HufTable*)c->tables.p, d.leaders, p.carryGroups, p.fr.rs.rawLiterals };
+    if (p.carry) pass.carry = &sc;
+    c->timer.begin(s);
+    staged_encode(c, p.ls, p.fr, pass);
+    c->lastBatchPasses++; if (p.set) c->lastBatchSetChunks += p.nCh;
+    if (b.d_stats) launch_seq_stats((Seq*)c->seqs.p, (u8*)c->lits.p, meta, p.nCh, (const u8*)c->batchStage.p, p.fr.chunkBytes, b.d_stats, s);
+    launch_batch_place(meta, p.nEnt, d.entFirst, d.entDst, d.entCap, p.at.span, (u64*)c->offsets.p, d.got, s);
+    c->timer.mark("batch_place", s);
+    if (b.seekIdx) {
+        launch_pack_entries(meta, p.nEnt, d.entFirst, d.len, p.fr.frameBlocks, d.entSeek, (u32*)c->seekEntries.p, b.seekCap, s);
+        c->timer.mark("pack_entries", s);
+    }
+    if (b.dsts) staged_write(c, pass, (u8*)p.at.lo, p.at.span);
+    b.got.resize(p.nEnt);
+    if (isErr(dev_read(b.got.data(), d.got, (size_t)p.nEnt * 8, s))) return ZERR(kErrGeneric);
+    add_stage_times(c, first);
+    const size_t* const members = g.members.data() + p.m0;
+    for (u32 e = 0; e < p.nEnt; ++e) b.outSizes[members[e]] = (size_t)b.got[e];
+    return 0;
+}
+
+// Alone tail: what the class model does not cover, in entry order, by the single-call path
+static void batch_alone_tail(BatchCall& b, const std::vector<size_t>& aloneList, int& alone)
+{
+    std::vector<u8> tmp;
+    for (size_t i : aloneList) {
+        const CallParams& cpi = b.params_of(i);
+        if (b.dsts) b.outSizes[i] = compress_device(b.c, cpi, b.dsts[i], b.caps[i], b.srcs[i], b.sizes[i]);
+        else { tmp.resize(ZSTD_compressBound(b.sizes[i])); b.outSizes[i] = compress_any(b.c, cpi, tmp.data(), tmp.size(), b.srcs[i], b.sizes[i]); }
+        ++alone;
+    }
+}
+
+// A pass holds whole entries, at most ZSTDMI_CCtx_setPassChunks chunks (batch_pass_cut).
+static size_t compress_entries(ZSTD_CCtx* c, const CallParams& cp, const u8* const* srcs, const size_t* sizes, size_t n,
+                               u8* const* dsts, const size_t* caps, size_t* outSizes, u32* d_stats, int& alone,
+                               const u32* seekIdx = nullptr, u32 seekCap = 0, const ZSTD_CDict_s* const* cdicts = nullptr)
+{
+    alone = 0;
+    c->lastRegionList = nullptr;        // (entries that go alone pass through compress_range, which notes its own)
+    c->lastBatchPasses = 0; c->lastBatchSetChunks = 0;
+    const u32 passLimit = batch_pass_limit(c);
+    BatchCall b{ c, cp, srcs, sizes, n, dsts, caps, outSizes, d_stats, seekIdx, seekCap, cdicts, c->cdict };
+    if (cdicts) { const size_t e = b.assign_cdicts(); if (isErr(e)) return e; }
+    std::vector<BatchGroup> groups;
+    std::vector<size_t> aloneList;
+    batch_classify(b, passLimit, groups, aloneList);
     bool first = true;
-    std::vector<u8> tab; std::vector<u64> got;
-    std::vector<u32> chunkSlot, used; std::vector<CDictSlot> slotTab; std::vector<u8> slotDone;
-    for (const Group& g : groups) {
-        const u32 cb = g.fr.chunkBytes, frameBlocks = g.fr.frameBlocks;
-        LaunchState ls = launch_state(c, params_of(g.members[0]), g.fr);      // (what sizes the workspace is the group's: same_launch_params)
+    for (const BatchGroup& g : groups) {
+        const LaunchState ls = launch_state(c, b.params_of(g.members[0]), g.fr);      // (what sizes the workspace is the group's: same_launch_params)
         for (size_t m0 = 0; m0 < g.members.size(); ) {
-            // the pass: whole entries, up to passLimit chunks
-            size_t m1 = m0; u32 nCh = 0;
-            while (m1 < g.members.size()) {
-                const u32 k = (u32)chunks_of(sizes[g.members[m1]], cb);
-                if (nCh && nCh + k > passLimit) break;
-                nCh += k; ++m1;
-            }
-            const u32 nEnt = (u32)(m1 - m0);
-            // the pass's table, one upload: from[nCh] | entDst[nEnt] | entCap[nEnt] (u64) | len[nCh] | entFirst[nEnt + 1] | with multi-block frames frame[nCh] (u32);
-            // behind it the sizes that come back
-            const size_t atDst = (size_t)nCh * 8, atCap = atDst + (size_t)nEnt * 8, atLen = atCap + (size_t)nEnt * 8, atFirst = atLen + (size_t)nCh * 4;
-            const size_t atFrame = atFirst + ((size_t)nEnt + 1) * 4;
-            const size_t atSeek = atFrame + (frameBlocks ? (size_t)nCh * 4 : 0);        // (a pack: | entSeek[nEnt])
-            // per-entry CDicts: the pass's launch state is that of its dictionary, or, behind two or more of them, the group's with a
-            // slot table: | chunkSlot[nCh] (u32) | slots[used.size()] (CDictSlot)
-            Framing fr = g.fr;
-            if (cdicts) {
-                chunkSlot.clear();
-                for (size_t m = m0; m < m1; ++m) chunkSlot.insert(chunkSlot.end(), chunks_of(sizes[g.members[m]], cb), slotOf[g.members[m]]);
-                if (!cdict_pass_image(chunkSlot, used)) return ZERR(kErrMemoryAllocation);
-                slotTab.assign(used.size(), CDictSlot{});
-                slotDone.assign(used.size(), 0);
-                for (size_t m = m0; m < m1; ++m) {      // each slot from the first entry behind it; the pass's state is its first entry's
-                    const size_t i = g.members[m];
-                    const size_t k = std::lower_bound(used.begin(), used.end(), slotOf[i]) - used.begin();
-                    assert(!slotDone[k] || slotTab[k].tailLen == g.tail[m]);        // (one dictionary, one chunk size: one tail)
-                    if (slotDone[k]) continue;
-                    fr.prefixLen = g.tail[m];
-                    const LaunchState lu = launch_state(c, params_of(i), fr);
-                    slotTab[k] = CDictSlot{ lu.prefix, lu.dct, lu.dix, fr.prefixLen, lu.header.dictID, lu.header.dictIdBytes, { lu.initReps[0], lu.initReps[1], lu.initReps[2] } };
-                    slotDone[k] = 1;
-                    if (m == m0) ls = lu;
-                }
-                fr.prefixLen = g.tail[m0];
-            }
-            const bool set = cdicts && used.size() >= 2;
-            const DictCTables* dct = ls.dct;
-            if (set) for (const CDictSlot& r : slotTab) if (r.dct) dct = r.dct;     // (any: "some slot has tables")
-            const size_t atChunkSlot = atSeek + (seekIdx ? (size_t)nEnt * 4 : 0);
-            const size_t atSlots = (atChunkSlot + (set ? (size_t)nCh * 4 : 0) + 7) & ~(size_t)7;
-            // carried entropy state (entries of more than one block): | leaders[nCh + 1] (u32), the chunks that lead a carry group
-            // (zmi_carry.h), so that an entry's bytes are the single call's
-            const bool carry = carry_active(c, params_of(g.members[m0]), fr, ls);
-            const size_t atLead = (atSlots + (set ? slotTab.size() * sizeof(CDictSlot) : 0) + 7) & ~(size_t)7;
-            const size_t tabBytes = (atLead + (carry ? ((size_t)nCh + 1) * 4 : 0) + 7) & ~(size_t)7;
-            tab.assign(tabBytes, 0);
-            if (set) { memcpy(tab.data() + atChunkSlot, chunkSlot.data(), (size_t)nCh * 4); memcpy(tab.data() + atSlots, slotTab.data(), slotTab.size() * sizeof(CDictSlot)); }
-            u64* const hFrom = (u64*)tab.data(); u64* const hDst = (u64*)(tab.data() + atDst); u64* const hCap = (u64*)(tab.data() + atCap);
-            u32* const hLen = (u32*)(tab.data() + atLen); u32* const hFirst = (u32*)(tab.data() + atFirst); u32* const hFrame = (u32*)(tab.data() + atFrame);
-            uintptr_t lo = ~(uintptr_t)0, hi = 0;
-            if (dsts) for (size_t m = m0; m < m1; ++m) {
-                const size_t i = g.members[m];
-                const uintptr_t d = (uintptr_t)dsts[i];
-                lo = d < lo ? d : lo; hi = d + caps[i] > hi ? d + caps[i] : hi;
-            }
-            u8* const base = dsts ? (u8*)lo : nullptr;
-            const u64 span = dsts ? (u64)(hi - lo) : 0;
-            u32 ck = 0;
-            for (size_t m = m0; m < m1; ++m) {
-                const size_t i = g.members[m];
-                hFirst[m - m0] = ck;
-                if (seekIdx) ((u32*)(tab.data() + atSeek))[m - m0] = seekIdx[i];
-                hDst[m - m0] = dsts ? (u64)((uintptr_t)dsts[i] - lo) : 0;
-                hCap[m - m0] = dsts ? (u64)caps[i] : ~(u64)0;
-                const FrameLayout entry = layout_arith(cb, frameBlocks, sizes[i]);      // the entry as the single call frames it
-                for (u64 o = 0, k = 0; o < sizes[i]; o += cb, ++ck, ++k) {
-                    hFrom[ck] = (u64)(uintptr_t)(srcs[i] + o); hLen[ck] = (u32)(sizes[i] - o < cb ? sizes[i] - o : cb);
-                    if (frameBlocks) {
-                        const BlockPlace at = block_place<kArith>(entry, (u32)k);
-                        assert(at.block < kFrameWordBlocks && at.frameLen < kFrameWordLen);
-                        hFrame[ck] = chunk_frame_word(at.block, (u32)at.frameLen);
-                    }
-                }
-            }
-            hFirst[nEnt] = ck;
-            u32 carryGroups = 0;
-            if (carry) { carryGroups = carry_leaders_table(hFrame, nCh, (u32*)(tab.data() + atLead)); c->lastCarryGroups += carryGroups; }
-            if (!staged_workspace(c, ls, fr, nCh, tabBytes + (size_t)nEnt * 8)) return ZERR(kErrMemoryAllocation);
-            u8* const dTab = (u8*)c->batchTab.p;
-            const u32* const dLen = (const u32*)(dTab + atLen);
-            u64* const dGot = (u64*)(dTab + tabBytes);
-            if (hipMemcpyAsync(dTab, tab.data(), tabBytes, hipMemcpyHostToDevice, s) != hipSuccess) return ZERR(kErrGeneric);
-            ChunkMeta* meta = (ChunkMeta*)c->meta.p;
-            // (dct: single-block frames only, see above)
-            StagedPass pass = staged_pass(nCh, fr, (const u64*)dTab, dLen, frameBlocks ? (const u32*)(dTab + atFrame) : nullptr, dct, cp.checksumFlag);
-            if (set) { pass.dSlots = (const CDictSlot*)(dTab + atSlots); pass.dChunkSlot = (const u32*)(dTab + atChunkSlot); }
-            const SeqCarry sc = { (HufTable*)c->tables.p, (const u32*)(dTab + atLead), carryGroups, fr.rs.rawLiterals };
-            if (carry) pass.carry = &sc;
-            c->timer.begin(s);
-            staged_encode(c, ls, fr, pass);
-            c->lastBatchPasses++; if (set) c->lastBatchSetChunks += nCh;
-            if (d_stats) launch_seq_stats((Seq*)c->seqs.p, (u8*)c->lits.p, meta, nCh, (const u8*)c->batchStage.p, cb, d_stats, s);
-            launch_batch_place(meta, nEnt, (const u32*)(dTab + atFirst), (const u64*)(dTab + atDst), (const u64*)(dTab + atCap), span, (u64*)c->offsets.p, dGot, s);
-            c->timer.mark("batch_place", s);
-            if (seekIdx) {
-                launch_pack_entries(meta, nEnt, (const u32*)(dTab + atFirst), dLen, frameBlocks, (const u32*)(dTab + atSeek), (u32*)c->seekEntries.p, seekCap, s);
-                c->timer.mark("pack_entries", s);
-            }
-            if (dsts) staged_write(c, pass, base, span);
-            got.resize(nEnt);
-            if (isErr(dev_read(got.data(), dGot, (size_t)nEnt * 8, s))) return ZERR(kErrGeneric);
-            add_stage_times(c, first);
-            for (u32 e = 0; e < nEnt; ++e) outSizes[g.members[m0 + e]] = (size_t)got[e];
+            u32 nCh = 0;
+            const size_t m1 = batch_pass_cut(m0, g.members.size(), passLimit, [&](size_t m) { return (u32)chunks_of(sizes[g.members[m]], g.fr.chunkBytes); }, nCh);
+            BatchPass p = { m0, (u32)(m1 - m0), nCh, g.fr, ls };
+            size_t e = batch_pass_image(b, g, p); if (isErr(e)) return e;
+            e = batch_pass_run(b, g, p, first); if (isErr(e)) return e;
             m0 = m1;
         }
     }
-    std::vector<u8> tmp;
-    for (size_t i : aloneList) {
-        const CallParams& cpi = params_of(i);
-        if (dsts) outSizes[i] = compress_device(c, cpi, dsts[i], caps[i], srcs[i], sizes[i]);
-        else { tmp.resize(ZSTD_compressBound(sizes[i])); outSizes[i] = compress_any(c, cpi, tmp.data(), tmp.size(), srcs[i], sizes[i]); }
-        ++alone;
-    }
+    batch_alone_tail(b, aloneList, alone);
     c->lastChunks = 0;                                  // (ZSTDMI_debugGetChunk: no ordinary call to look at)
     return 0;
 }
@@ -2182,36 +2181,8 @@ extern "C" long long ZSTDMI_debugLastBatchPasses(const ZSTD_CCtx* c) { return c 
 extern "C" long long ZSTDMI_debugLastBatchSetChunks(const ZSTD_CCtx* c) { return c ? c->lastBatchSetChunks : -1; }
 
 // ---------------- a batch enqueued from the device (include/zstd_mi355x.h) ----------------
-// the pass's table for n entries: from | entDst | entCap (u64) | len | entFirst[n + 1] | verdict (u32) | the byte an ineligible entry reads
-struct AsyncTab { size_t atDst, atCap, atLen, atFirst, atVerdict, atDummy, bytes; };
-static AsyncTab async_tab(u32 n)
-{
-    AsyncTab t;
-    t.atDst = (size_t)n * 8; t.atCap = t.atDst + (size_t)n * 8; t.atLen = t.atCap + (size_t)n * 8; t.atFirst = t.atLen + (size_t)n * 4;
-    t.atVerdict = t.atFirst + ((size_t)n + 1) * 4; t.atDummy = (t.atVerdict + (size_t)n * 4 + 7) & ~(size_t)7; t.bytes = t.atDummy + 8;
-    return t;
-}
-// The pass's table of a planned call, laid out once for the prepared limits (nEnt entries, nCh chunks):
-// from[nCh] | src | size | dst | cap [nEnt] (u64) | len[nCh] | frame[nCh] | first[nEnt + 1] | verdict[nEnt] (u32) | the idle slots' byte
-struct AsyncPlanTab { size_t atSrc, atSize, atDst, atCap, atLen, atFrame, atFirst, atVerdict, atDummy, bytes; };
-static AsyncPlanTab async_plan_tab(u32 nEnt, u32 nCh)
-{
-    AsyncPlanTab t;
-    t.atSrc = (size_t)nCh * 8; t.atSize = t.atSrc + (size_t)nEnt * 8; t.atDst = t.atSize + (size_t)nEnt * 8; t.atCap = t.atDst + (size_t)nEnt * 8;
-    t.atLen = t.atCap + (size_t)nEnt * 8; t.atFrame = t.atLen + (size_t)nCh * 4; t.atFirst = t.atFrame + (size_t)nCh * 4;
-    t.atVerdict = t.atFirst + ((size_t)nEnt + 1) * 4; t.atDummy = (t.atVerdict + (size_t)nEnt * 4 + 7) & ~(size_t)7; t.bytes = t.atDummy + 8;
-    return t;
-}
-// What a pack adds to either prepare (ZSTDMI_compressPackAsync): the placement's columns for nEnt entries of at most F frames each —
-// entAt[nEnt] | state (u64) | entRow[nEnt] | rows[2 * nEnt * F] (u32).  pack_frames_of: F for an entry of `bound` bytes under the framing.
-struct PackAsyncLayout { size_t atState, atRow, atRows, bytes; };
-static PackAsyncLayout pack_async_tab(u32 nEnt, u32 F)
-{
-    PackAsyncLayout t;
-    t.atState = (size_t)nEnt * 8; t.atRow = t.atState + kPackStateWords * 8; t.atRows = t.atRow + (((size_t)nEnt * 4 + 7) & ~(size_t)7);
-    t.bytes = t.atRows + (size_t)nEnt * F * 8 + 8;
-    return t;
-}
+// (the pass's tables, async_tab and async_plan_tab, and what a pack adds to either prepare, pack_async_tab: zmi_batch_pass.h)
+// pack_frames_of: pack_async_tab's F for an entry of `bound` bytes under the framing.
 static u32 pack_frames_of(size_t bound, const Framing& fr)
 {
     const u32 chunks = chunks_of(bound, fr.chunkBytes), F = fr.frameBlocks ? (chunks + fr.frameBlocks - 1) / fr.frameBlocks : chunks;
@@ -2571,14 +2542,17 @@ static size_t compress_pack_impl(ZSTD_CCtx* c, u8* d_dst, size_t dstCapacity, co
             at += r; ++alone; ++i;
             continue;
         }
-        // a round: the batched entries [i, j), at most passLimit chunks
-        size_t j = i; u32 nCh = 0, nRows = 0; size_t arenaBytes = 0;
+        // a round: the batched entries [i, j), cut as compress_entries cuts a pass (batch_pass_cut) from the run of batched entries
+        // that begins at i
+        const size_t runEnd = batch_run_end(batched.data(), i, std::min(n, i + (size_t)passLimit));
+        u32 nCh = 0, nRows = 0; size_t arenaBytes = 0;
+        const size_t j = batch_pass_cut(i, runEnd, passLimit, [&](size_t k) { return chunks[k]; }, nCh);
         slotPtr.clear(); slotCap.clear(); seekIdx.clear(); tab.clear();
-        while (j < n && batched[j] && !(nCh && nCh + chunks[j] > passLimit)) {
+        for (size_t k = i; k < j; ++k) {
             tab.push_back(arenaBytes); seekIdx.push_back(nRows);
-            slotCap.push_back(ZSTD_compressBound(sizes[j]));
+            slotCap.push_back(ZSTD_compressBound(sizes[k]));
             arenaBytes += (slotCap.back() + 15) & ~(size_t)15;
-            nCh += chunks[j]; nRows += frames[j]; ++j;
+            nRows += frames[k];
         }
         const u32 nEnt = (u32)(j - i);
         tab.push_back(arenaBytes);                                  // slot[nEnt + 1] | size[nEnt] | at[nEnt] (device only)
