@@ -652,6 +652,55 @@ size_t ZSTDMI_compressPackAsync(ZSTD_CCtx* cctx, void* d_dst, size_t dstCapacity
                                 const void* const* d_srcs, const size_t* d_srcSizes, size_t n,
                                 size_t* d_packSize, size_t* d_entryEnds /* may be NULL */);
 
+/* Content-defined cuts: frames that end where the CONTENT says, so that the compressed streams of two inputs that differ by an insertion
+ * or a deletion share their frames again a few pieces behind the edit (what `zstd --rsyncable` is for: deduplicating and rsync-style
+ * stores of compressed data).  Without the switch every frame is cut by position and one inserted byte changes all frames behind it.
+ * The cut rule, version 1 — a FORMAT CONTRACT: stores depend on these cut points, a change to it is a new version.
+ *   Gear table.  gear[i] = splitmix64(i): z = (i + 1) * 0x9E3779B97F4A7C15; z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;
+ *     z = (z ^ (z >> 27)) * 0x94D049BB133111EB; gear[i] = z ^ (z >> 31), all mod 2^64 (the long-distance matcher's table).
+ *   Hash.  After byte p of the call's source, h(p) = sum over k = 0 .. min(p, 63) of gear[src[p - k]] << k (mod 2^64):
+ *     h = (h << 1) + gear[byte], started at 0 at the source's first byte.  h(p) depends on the last 64 bytes only, never on earlier cuts.
+ *   Candidate.  With bits = avgLog - 1, min = 1 << (avgLog - 2) and max = 65536, position p + 1 is a candidate end iff the top `bits`
+ *     bits of h(p) are zero.
+ *   Selection.  From a piece start s (first s = 0), the piece ends at the smallest candidate e with e - s >= min, if e - s <= max;
+ *     otherwise it ends at s + max.  The source's end ends the last piece, whatever its length.  An empty source has no piece.
+ *   Range.  avgLog is 12 to 16.
+ * ZSTDMI_CCtx_setContentCuts(avgLog): 0 = off (the default), 12 .. 16 = on; 1 .. 11 and above 16: parameter_outOfBound; NULL context:
+ * GENERIC.  Sticky; the call touches no device.
+ * Where it applies: ZSTD_compress2, ZSTDMI_compressDevice and ZSTD_compress_usingCDict, with host or device buffers.
+ * The bytes.  For the pieces 0 .. n - 1 of the rule, in order, the call writes exactly the frames ZSTDMI_compressDevice writes for that
+ * piece alone on the same context with the switch off — ZSTDMI_compressPack's contract (above), and its rounds —, one piece's behind the
+ * other's without a gap.  With ZSTDMI_CCtx_setSeekTable(1) the pack's ONE seek table follows the last frame: the stream is byte for byte
+ * ZSTDMI_compressPack of the pieces.  Without it no table is written (an empty source then writes nothing and returns 0).  Level,
+ * dictionary, CDict, ZSTDMI_CCtx_setDictEntropy / setDictIndex* / setEntropyCarry, checksum and content-size flags act per piece as they
+ * do in a pack (ZSTD_compress_usingCDict: the CDict's level and default frame parameters, as without the switch).  Every frame depends
+ * on its piece's bytes and the context's settings only.  ZSTDMI_debugLastPackAlone / ZSTDMI_debugLastPackFrames speak of a cut call as
+ * of a pack.
+ * Room.  ZSTDMI_contentCutsBound(srcSize, avgLog) touches no device: with P = srcSize / min + 1 it is
+ *     srcSize + (srcSize >> 8) + 64 * P + 17 + 8 * (srcSize / 4096 + P),
+ * at least ZSTDMI_packBound of any piece list the rule allows, the seek table included; a call with that much room never answers
+ * dstSize_tooSmall.  srcSize_wrong when it does not fit a size_t, parameter_outOfBound for an avgLog outside 12 .. 16.
+ * ZSTD_compressBound is too small here (a 1 KiB raw piece costs more than 4 extra bytes).  Nothing is written at or beyond dst + dstCapacity.
+ * Refused, never ignored — parameter_unsupported, before a byte is read, while the switch is on: ZSTD_compressStream2;
+ * ZSTDMI_compressBatch, ZSTDMI_compressBatchCDicts, ZSTDMI_compressPack and the enqueued calls with their prepares (ZSTDMI_CCtx_prepareBatchAsync /
+ * ...Limits, ZSTDMI_compressBatchAsync, ZSTDMI_compressPackAsync: their entries are the caller's cuts); ZSTDMI_debugCompressSamples; and in
+ * the calls it applies to: several device workers, a pending ZSTD_CCtx_refPrefix (it stays pending), ZSTDMI_CCtx_setSingleFrame,
+ * ZSTD_c_enableLongDistanceMatching = ZSTD_ps_enable, a set ZSTD_c_windowLog of 10 .. 15, srcSize above 2^32 - 1.  ZSTD_compressCCtx
+ * ignores the switch, as it ignores the other sticky switches.  ZSTD_c_rsyncable stays parameter_unsupported.  A source whose candidate
+ * list does not fit device memory (a hostile input can make it as long as the source) fails with memory_allocation: the list is never thinned.
+ * Off (the default, or on and off again): every call launches what it launched before and writes the same bytes.
+ * ZSTDMI_contentCuts is the chunker alone: the piece sizes of [d_src, d_src + srcSize) (device memory; host memory is staged) for
+ * avgLog, in order, into the HOST array pieceSizes[capacity], their number into *nPieces — also when capacity is too small, which
+ * answers dstSize_tooSmall and writes no size (srcSize / min + 1 entries always suffice).  The context's switch is not consulted.
+ * GENERIC for a NULL context, a NULL nPieces or a NULL array with a capacity; parameter_outOfBound / parameter_unsupported as above.
+ * ZSTDMI_debugLastContentCuts: pieces of the last call that was cut; 0 when none was; -1 without a context.
+ * Out of scope: cuts that carry across ZSTD_compressStream2 batches, cuts inside batch or pack entries, pieces above 64 KiB. */
+size_t ZSTDMI_CCtx_setContentCuts(ZSTD_CCtx* cctx, unsigned avgLog);
+size_t ZSTDMI_contentCutsBound(size_t srcSize, unsigned avgLog);
+size_t ZSTDMI_contentCuts(ZSTD_CCtx* cctx, const void* d_src, size_t srcSize, unsigned avgLog,
+                          size_t* pieceSizes, size_t capacity, size_t* nPieces);
+long long ZSTDMI_debugLastContentCuts(const ZSTD_CCtx* cctx);
+
 /* Seekable streams (the zstd seekable format, v0.1.0): random access at the granularity of the frame.
  * Every stream this library writes is a run of independent frames (64 KiB of content at levels 1-2, 240-256 KiB at levels >= 3, 32 KiB
  * or less behind a dictionary, one window under long-distance matching; ZSTDMI_CCtx_setHistory and ZSTD_c_windowLog change it).

@@ -159,6 +159,10 @@ SIGNATURES = {
     "ZSTDMI_compressPackAsync": (c_size_t, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
     "ZSTDMI_debugLastPackAlone": (c_int, [c_void_p]),
     "ZSTDMI_debugLastPackFrames": (ctypes.c_longlong, [c_void_p]),
+    "ZSTDMI_CCtx_setContentCuts": (c_size_t, [c_void_p, c_uint]),
+    "ZSTDMI_contentCutsBound": (c_size_t, [c_size_t, c_uint]),
+    "ZSTDMI_contentCuts": (c_size_t, [c_void_p, c_void_p, c_size_t, c_uint, ctypes.POINTER(c_size_t), c_size_t, ctypes.POINTER(c_size_t)]),
+    "ZSTDMI_debugLastContentCuts": (ctypes.c_longlong, [c_void_p]),
     "ZSTDMI_CCtx_setSeekTable": (c_size_t, [c_void_p, c_uint]),
     "ZSTDMI_CCtx_setDictEntropy": (c_size_t, [c_void_p, c_uint]),
     "ZSTDMI_CCtx_setEntropyCarry": (c_size_t, [c_void_p, c_uint]),

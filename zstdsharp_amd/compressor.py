@@ -78,6 +78,7 @@ class Compressor(_PrefixHolder):
         self._single_frame = False
         self._sliding_ldm = False
         self._far_offsets = False
+        self._content_cuts = 0
         self._cdict = None              # the CDict RefCDict holds
         self.Level = level if level else self.DefaultCompressionLevel
 
@@ -137,7 +138,7 @@ class Compressor(_PrefixHolder):
         self._ensure_not_disposed()
         cdict._ensure_not_disposed()
         saddr, sn, skeep = _as_buffer(src)
-        cap = self.GetCompressBound(sn)
+        cap = self._wrap_bound(sn) if self._content_cuts else self.GetCompressBound(sn)
         out = ctypes.create_string_buffer(max(cap, 1))
         n = ensure_zstd_success(self._lib, self._lib.ZSTD_compress_usingCDict(self.cctx, out, cap, saddr, sn, cdict.handle))
         return out.raw[:n]
@@ -258,6 +259,23 @@ class Compressor(_PrefixHolder):
         ensure_zstd_success(self._lib, self._lib.ZSTDMI_CCtx_setFarOffsets(self.cctx, 1 if on else 0))
         self._far_offsets = bool(on)
 
+    # ---- content-defined cuts (ZSTDMI_CCtx_setContentCuts): 0 = off (default), 12 .. 16 = Wrap cuts its source by content, avgLog ----
+    @property
+    def content_cuts(self) -> int:
+        return self._content_cuts
+
+    @content_cuts.setter
+    def content_cuts(self, avg_log):
+        self._ensure_not_disposed()
+        ensure_zstd_success(self._lib, self._lib.ZSTDMI_CCtx_setContentCuts(self.cctx, int(avg_log)))
+        self._content_cuts = int(avg_log)
+
+    def _wrap_bound(self, length: int) -> int:
+        """the room Wrap(src) without dest asks for: frames plus, where a switch adds one, the seek table"""
+        if self._content_cuts:
+            return ensure_zstd_success(self._lib, self._lib.ZSTDMI_contentCutsBound(length, self._content_cuts))
+        return self.GetCompressBound(length) + (self._lib.ZSTDMI_seekTableBound(length) if self._seek_table else 0)
+
     # ---- batches enqueued from the device (ZSTDMI_CCtx_prepareBatchAsync; batch.compress_batch_async runs them) ----
     def PrepareBatchAsync(self, max_entries: int, src_size_bound: int):
         """Everything compress_batch_async needs the host for, once: resolves this object's parameters and dictionary for an entry of
@@ -306,7 +324,7 @@ class Compressor(_PrefixHolder):
     def _wrap(self, src, dest, offset):
         saddr, sn, skeep = _as_buffer(src)
         if dest is None:
-            cap = self.GetCompressBound(sn) + (self._lib.ZSTDMI_seekTableBound(sn) if self._seek_table else 0)
+            cap = self._wrap_bound(sn)
             out = ctypes.create_string_buffer(max(cap, 1))
             n = ensure_zstd_success(self._lib, self._lib.ZSTD_compress2(self.cctx, out, cap, saddr, sn))
             return out.raw[:n]
@@ -355,3 +373,24 @@ class Compressor(_PrefixHolder):
             self.Dispose()
         except Exception:
             pass
+
+
+def content_cuts(compressor, data, avg_log: int):
+    """ZSTDMI_contentCuts: the chunker alone -> the list of piece sizes the cut rule (include/zstd_mi355x.h "Content-defined cuts") gives
+    `data` (bytes-like, or a contiguous CUDA uint8 tensor) at avg_log, in order; their sum is len(data).  The compressor lends its
+    device and stream; its content_cuts switch is not consulted."""
+    compressor._ensure_not_disposed()
+    lib = compressor._lib
+    if hasattr(data, "data_ptr"):
+        import torch
+        if not (data.is_cuda and data.dtype == torch.uint8 and data.is_contiguous()):
+            raise TypeError("expected a contiguous CUDA uint8 tensor")
+        torch.cuda.synchronize(data.device)
+        addr, n, keep = (data.data_ptr() if data.numel() else None), data.numel(), data
+    else:
+        addr, n, keep = _as_buffer(data)
+    cap = n // 1024 + 1         # (min is 1 KiB or more: never fewer entries than pieces)
+    sizes = (ctypes.c_size_t * cap)()
+    got = ctypes.c_size_t(0)
+    ensure_zstd_success(lib, lib.ZSTDMI_contentCuts(compressor.cctx, addr, n, int(avg_log), sizes, cap, ctypes.byref(got)))
+    return list(sizes[:got.value])

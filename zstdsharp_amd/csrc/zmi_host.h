@@ -16,6 +16,7 @@
 #include "zmi_batch_pass.h"
 #include "zmi_dictset.h"
 #include "zmi_cdictset.h"
+#include "zmi_cuts.h"
 #include "../../include/zstd_mi355x.h"
 
 namespace zmi {
@@ -129,6 +130,13 @@ void launch_ldm_count(const u8* src, u64 n, u64 frameSpan, const LdmLaunch& p, u
 u32* ldm_total_word(u8* small, u64 n);
 void launch_ldm_rest(const u8* src, u64 n, u32 nChunks, u32 chunkBytes, u64 frameSpan, const LdmLaunch& p, u32 nSplits, u8* small, u8* big,
                      Seq* seqs, u8* lits, ChunkMeta* meta, hipStream_t stream, StageHook hook, const LdmPrefix& pfx);
+// content-defined cuts (content_cuts.hip; the rule: zmi_cuts.h).  small: cut_small_bytes(n) bytes; the count leaves the candidates'
+// total in *cut_total_word, the emit writes that many ends in position order, the select 1 + cap words: the pieces, then their ends
+size_t cut_small_bytes(u64 n);
+u32* cut_total_word(u8* small, u64 n);
+void launch_cut_count(const u8* src, u64 n, u32 bits, u8* small, hipStream_t stream);
+void launch_cut_emit(const u8* src, u64 n, u32 bits, u8* small, u32* cand, hipStream_t stream);
+void launch_cut_select(const u32* cand, u32 nCand, u64 n, const CutRule& rule, u32* out, u32 cap, hipStream_t stream);
 // decoder (decode_walk.hip, decode_lit.hip, decode_seq.hip, decode_origin.hip)
 // The dictionary of a call as the stage launchers take it (the host's decode_dict, zstd_mi355x_dec.hip): formatted or raw content, the
 // whole dictionary and its parsed header (formatted only), the content that is history in front of every frame — a caller may put a

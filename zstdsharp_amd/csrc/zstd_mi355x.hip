@@ -114,6 +114,11 @@ struct ZSTD_CCtx_s {
     // behind the last enqueued pass (asyncPending: not yet waited for).  cctx_async_drain is the one place that waits for it; every
     // buffer of the context names `tally`, so that no growth or release frees memory an enqueued pass still uses, and counts there.
     HostTally tally; u64 paramGen = 0;
+    // ZSTDMI_CCtx_setContentCuts (sticky; 0 = off, else avgLog): the single calls cut their source by content (zmi_cuts.h) and write
+    // the pieces as a pack (compress_cut).  cutSmall / cutList / cutEnds: the mark's tile counts, the candidate list and the select's
+    // output (content_cuts.hip); lastContentCuts: pieces of the last call that was cut (ZSTDMI_debugLastContentCuts)
+    int contentCuts = 0; long long lastContentCuts = 0;
+    DevBuf cutSmall, cutList, cutEnds;
     struct AsyncPrep* asyncPrep = nullptr; hipEvent_t asyncEv = nullptr; bool asyncPending = false;
     ZSTD_CCtx_s();
 };
@@ -171,7 +176,7 @@ ZSTD_CCtx_s::ZSTD_CCtx_s()
 {
     tally.self = this; tally.beforeFree = [](void* self) { cctx_async_drain((ZSTD_CCtx_s*)self); };
     for (DevBuf* b : { &seqs, &lits, &meta, &tables, &slots, &offsets, &total, &cand, &probe, &stageSrc, &stageDst, &ldmSmall, &ldmBig, &dixDist, &gatherIn, &gatherOut,
-                       &batchStage, &batchTab, &packArena, &packTab, &packAsync, &seekEntries, &seekSort, &pfxStage, &sfXxh, &sWin,
+                       &batchStage, &batchTab, &packArena, &packTab, &packAsync, &seekEntries, &seekSort, &pfxStage, &sfXxh, &sWin, &cutSmall, &cutList, &cutEnds,
                        &own.dict, &own.dictFullDev, &own.dictInfoDev, &own.dictCTabDev, &own.dictWideDev, &own.dictIdxDev }) b->owner = &tally;
 }
 
@@ -854,6 +859,8 @@ static size_t check_call_params(const CallParams& cp)
 }
 
 static size_t compress_multi(ZSTD_CCtx* c, const CallParams& cp, void* dst, size_t dstCapacity, const void* src, size_t srcSize);
+// a single call under ZSTDMI_CCtx_setContentCuts (defined behind the pack, whose rounds it runs)
+static size_t compress_cut(ZSTD_CCtx* c, const CallParams& cp, void* dst, size_t dstCapacity, const void* src, size_t srcSize, bool deviceCall);
 
 // A plan of several ranges (a mixed input: stretches the level's finder is for, stretches without matches) as it stands is a run of
 // small passes — a handful of kernels over a few hundred chunks each, none of which fills the chip; side by side on several
@@ -1000,7 +1007,7 @@ size_t ZSTD_freeCCtx(ZSTD_CCtx* c)
         if (c->asyncEv) (void)hipEventDestroy(c->asyncEv);
         if (c->ownStream) (void)hipStreamSynchronize(c->ownStream);
         c->seqs.release(); c->lits.release(); c->meta.release(); c->tables.release(); c->slots.release(); c->cand.release(); c->lastRegionList = nullptr; c->dixDist.release(); c->probe.release();
-        c->gatherIn.release(); c->gatherOut.release(); c->batchStage.release(); c->batchTab.release(); c->packArena.release(); c->packTab.release(); c->packAsync.release(); c->ldmSmall.release(); c->ldmBig.release(); c->offsets.release(); c->total.release(); c->seekEntries.release(); c->seekSort.release(); c->stageSrc.release(); c->stageDst.release(); c->pfxStage.release(); c->sfXxh.release(); c->sWin.release(); c->own.release();
+        c->gatherIn.release(); c->gatherOut.release(); c->batchStage.release(); c->batchTab.release(); c->packArena.release(); c->packTab.release(); c->packAsync.release(); c->ldmSmall.release(); c->ldmBig.release(); c->offsets.release(); c->total.release(); c->seekEntries.release(); c->seekSort.release(); c->stageSrc.release(); c->stageDst.release(); c->pfxStage.release(); c->sfXxh.release(); c->sWin.release(); c->cutSmall.release(); c->cutList.release(); c->cutEnds.release(); c->own.release();
         c->timer.destroy();
         if (c->ownStream) (void)hipStreamDestroy(c->ownStream);
     }
@@ -1350,7 +1357,8 @@ size_t ZSTD_compress_usingCDict(ZSTD_CCtx* c, void* dst, size_t dstCapacity, con
     // steps aside for the call (where the CDict cannot be shared, its host fields do, and are uploaded again by their next use)
     CallParams p; p.level = cdict->level; p.useDict = true;
     p.dictEntropy = c->dictEntropy != 0; p.dictIndex = c->dictIndex != 0; p.dictIndexStrategy = c->dictIndexStrategy; p.dictIndexChain = c->dictIndexChain != 0;
-    return guarded([&]() -> size_t { return under_cdict(c, cdict, [&] { return compress_any(c, p, dst, dstCapacity, src, srcSize); }); });
+    return guarded([&]() -> size_t { return under_cdict(c, cdict, [&] { return c->contentCuts ? compress_cut(c, p, dst, dstCapacity, src, srcSize, false)
+                                                                                              : compress_any(c, p, dst, dstCapacity, src, srcSize); }); });
 }
 long long ZSTDMI_debugDictUploads(const ZSTD_CCtx* c)
 {
@@ -1362,12 +1370,14 @@ long long ZSTDMI_debugDictUploads(const ZSTD_CCtx* c)
 
 size_t ZSTDMI_compressDevice(ZSTD_CCtx* c, void* d_dst, size_t dstCapacity, const void* d_src, size_t srcSize)
 {
+    if (c && c->contentCuts) return guarded([&] { return compress_cut(c, sticky_params(c), d_dst, dstCapacity, d_src, srcSize, true); });     // (a pending prefix: refused there, and stays pending)
     if (c && c->pfx) return guarded([&] { return compress_prefixed(c, d_dst, dstCapacity, d_src, srcSize, true); });
     return guarded([&] { return ZSTDMI_compressDevice_impl(c, d_dst, dstCapacity, d_src, srcSize); });
 }
 size_t ZSTD_compress2(ZSTD_CCtx* c, void* dst, size_t dstCapacity, const void* src, size_t srcSize)
 {
     if (!c) return ZERR(kErrGeneric);
+    if (c->contentCuts) return guarded([&] { return compress_cut(c, sticky_params(c), dst, dstCapacity, src, srcSize, false); });
     if (c->pfx) return guarded([&] { return compress_prefixed(c, dst, dstCapacity, src, srcSize, false); });
     return guarded([&] { return compress_any(c, sticky_params(c), dst, dstCapacity, src, srcSize); });
 }
@@ -1664,6 +1674,7 @@ static size_t ZSTD_compressStream2_impl(ZSTD_CCtx* c, ZSTD_outBuffer* output, ZS
     if (input->pos > input->size) return ZERR(105);            // srcBuffer_wrong
     if ((unsigned)endOp > 2) return ZERR(kErrParameterOutOfBound);
     if (c->seekTable) return ZERR(kErrParameterUnsupported);   // (a table per batch of the session would not be one table of the stream)
+    if (c->contentCuts) return ZERR(kErrParameterUnsupported); // (cuts would have to carry across the session's batches)
     if (c->pfx) return ZERR(kErrParameterUnsupported);         // (a referenced prefix stands in front of ONE frame; a session writes one per batch)
     if (input->size > input->pos && !input->src) return ZERR(kErrSrcSizeWrong);
     if (output->size > output->pos && !output->dst) return ZERR(kErrDstBufferNull);
@@ -2160,6 +2171,7 @@ size_t compress_samples(ZSTD_CCtx* c, const u8* src, const u64* offs, const size
 static size_t compress_batch_impl(ZSTD_CCtx* c, const void* const* srcs, const size_t* srcSizes, size_t n, void* const* dsts, const size_t* dstCapacities, size_t* dstSizes)
 {
     if (!c) return ZERR(kErrGeneric);
+    if (c->contentCuts) return ZERR(kErrParameterUnsupported);       // (a batch's entries are the caller's cuts)
     c->lastRegionList = nullptr; c->lastCarryGroups = 0;
     if (n == 0) { c->lastBatchAlone = 0; return 0; }
     if (!srcs || !srcSizes || !dsts || !dstCapacities || !dstSizes) return ZERR(kErrGeneric);
@@ -2195,6 +2207,7 @@ static size_t prepare_async_core(ZSTD_CCtx* c, size_t maxEntries, size_t bound, 
 {
     const u32 passLimit = batch_pass_limit(c);
     const CallParams cp = sticky_params(c);
+    if (c->contentCuts) return ZERR(kErrParameterUnsupported);       // (the enqueued calls refuse the switch: nothing to prepare for)
     size_t e = check_call_params(cp); if (isErr(e)) return e;
     e = cctx_bind(c); if (isErr(e)) return e;
     e = cctx_sync_dictionary(c); if (isErr(e)) return e;
@@ -2300,6 +2313,7 @@ static size_t compress_batch_async_impl(ZSTD_CCtx* c, const void* const* d_srcs,
                                         const size_t* d_dstCapacities, size_t* d_dstSizes)
 {
     if (!c) return ZERR(kErrGeneric);
+    if (c->contentCuts) return ZERR(kErrParameterUnsupported);
     if (n == 0) return 0;
     if (!d_srcs || !d_srcSizes || !d_dsts || !d_dstCapacities || !d_dstSizes) return ZERR(kErrGeneric);
     AsyncCall call;
@@ -2356,6 +2370,7 @@ static size_t compress_pack_async_impl(ZSTD_CCtx* c, u8* d_dst, size_t dstCapaci
                                        size_t* d_packSize, size_t* d_entryEnds)
 {
     if (!c || !d_packSize || (n && (!d_srcs || !d_srcSizes))) return ZERR(kErrGeneric);
+    if (c->contentCuts) return ZERR(kErrParameterUnsupported);
     if (!d_dst) return dstCapacity ? ZERR(kErrDstBufferNull) : ZERR(kErrDstSizeTooSmall);
     AsyncCall call;
     const size_t e = async_begin(c, n, call); if (isErr(e)) return e;
@@ -2398,6 +2413,7 @@ static size_t compress_batch_cdicts_impl(ZSTD_CCtx* c, const void* const* srcs, 
                                          size_t* dstSizes, const ZSTD_CDict* const* cdicts)
 {
     if (!c) return ZERR(kErrGeneric);
+    if (c->contentCuts) return ZERR(kErrParameterUnsupported);
     c->lastRegionList = nullptr; c->lastCarryGroups = 0;
     if (n == 0) { c->lastBatchAlone = 0; c->lastBatchPasses = 0; c->lastBatchSetChunks = 0; return 0; }
     if (!srcs || !srcSizes || !dsts || !dstCapacities || !dstSizes || !cdicts) return ZERR(kErrGeneric);
@@ -2472,14 +2488,13 @@ struct PackStages {
     void file(ZSTD_CCtx* c) const { c->nStages = n; for (int i = 0; i < n; i++) { c->stageNames[i] = names[i]; c->stageMs[i] = ms[i]; } }
 };
 }
-static size_t compress_pack_impl(ZSTD_CCtx* c, u8* d_dst, size_t dstCapacity, const u8* const* srcs, const size_t* sizes, size_t n)
+// The pack's rounds for a bound context and the call's parameters (cp.seek off).  withTable = false: the frames alone, no table behind
+// them (a cut call without the seek-table switch, compress_cut); st: stage times the caller has gathered in front of the rounds.
+static size_t compress_pack_core(ZSTD_CCtx* c, const CallParams& cp, u8* d_dst, size_t dstCapacity, const u8* const* srcs, const size_t* sizes, size_t n,
+                                 bool withTable, PackStages st)
 {
-    if (!c || (n && (!srcs || !sizes))) return ZERR(kErrGeneric);
-    size_t e = cctx_bind(c); if (isErr(e)) return e;
-    c->lastRegionList = nullptr; c->lastCarryGroups = 0;
-    if (c->workers.size() > 1 || c->pfx) return ZERR(kErrParameterUnsupported);
+    size_t e = 0;
     c->lastPackAlone = 0; c->lastPackFrames = 0;
-    CallParams cp = sticky_params(c); cp.seek = false;      // (the context's own switch is not consulted)
     hipStream_t s = c->stream;
     // what the single call would refuse, for the lowest entry it refuses, before a byte is read
     for (size_t i = 0; i < n; i++) if (sizes[i] && !srcs[i]) return ZERR(kErrSrcSizeWrong);
@@ -2514,7 +2529,6 @@ static size_t compress_pack_impl(ZSTD_CCtx* c, u8* d_dst, size_t dstCapacity, co
     struct Off { ZSTD_CCtx* c; ~Off() { c->seekOn = false; c->seekCount = 0; } } off{c};
     std::vector<u32> table;             // the rows, two words each, in stream order
     std::vector<u8*> slotPtr; std::vector<size_t> slotCap, got; std::vector<u32> seekIdx; std::vector<u64> tab;
-    PackStages st;
     size_t at = 0;
     int alone = 0;
     for (size_t i = 0; i < n; ) {
@@ -2584,6 +2598,12 @@ static size_t compress_pack_impl(ZSTD_CCtx* c, u8* d_dst, size_t dstCapacity, co
     }
     const size_t nFrames = table.size() / 2;
     if (nFrames > kPackMaxFrames) return ZERR(kErrParameterUnsupported);
+    if (!withTable) {       // (every round and alone entry has been waited for)
+        st.file(c);
+        c->lastPackAlone = alone; c->lastPackFrames = (long long)nFrames;
+        c->lastChunks = 0;
+        return at;
+    }
     const size_t tableBytes = 17 + 8 * nFrames;
     if (tableBytes > dstCapacity - at) return ZERR(kErrDstSizeTooSmall);
     // the table behind the last frame: skippable header | rows | footer (include/zstd_mi355x.h "Seekable streams"), in one copy
@@ -2601,6 +2621,16 @@ static size_t compress_pack_impl(ZSTD_CCtx* c, u8* d_dst, size_t dstCapacity, co
     c->lastChunks = 0;
     return at + tableBytes;
 }
+static size_t compress_pack_impl(ZSTD_CCtx* c, u8* d_dst, size_t dstCapacity, const u8* const* srcs, const size_t* sizes, size_t n)
+{
+    if (!c || (n && (!srcs || !sizes))) return ZERR(kErrGeneric);
+    if (c->contentCuts) return ZERR(kErrParameterUnsupported);      // (a pack's entries are the caller's cuts)
+    size_t e = cctx_bind(c); if (isErr(e)) return e;
+    c->lastRegionList = nullptr; c->lastCarryGroups = 0;
+    if (c->workers.size() > 1 || c->pfx) return ZERR(kErrParameterUnsupported);
+    CallParams cp = sticky_params(c); cp.seek = false;      // (the context's own switch is not consulted)
+    return compress_pack_core(c, cp, d_dst, dstCapacity, srcs, sizes, n, true, PackStages());
+}
 extern "C" size_t ZSTDMI_packBound(const size_t* srcSizes, size_t n) { return pack_bound(srcSizes, n); }
 extern "C" size_t ZSTDMI_compressPack(ZSTD_CCtx* c, void* d_dst, size_t dstCapacity, const void* const* srcs, const size_t* srcSizes, size_t n)
 {
@@ -2609,9 +2639,133 @@ extern "C" size_t ZSTDMI_compressPack(ZSTD_CCtx* c, void* d_dst, size_t dstCapac
 extern "C" int ZSTDMI_debugLastPackAlone(const ZSTD_CCtx* c) { return c ? c->lastPackAlone : -1; }
 extern "C" long long ZSTDMI_debugLastPackFrames(const ZSTD_CCtx* c) { return c ? c->lastPackFrames : -1; }
 
+// ---- content-defined cuts (ZSTDMI_CCtx_setContentCuts, include/zstd_mi355x.h; the rule: zmi_cuts.h) ----
+// The pieces of [d_src, d_src + n) by the rule -> their sizes in order.  Two host synchronisations: the candidates' count, which sizes
+// the list, and the select's output (the piece count and the ends, one copy sized by the most pieces the rule allows).
+static size_t content_cut_sizes(ZSTD_CCtx* c, const u8* d_src, size_t n, unsigned avgLog, std::vector<size_t>& sizes, PackStages& st)
+{
+    sizes.clear();
+    if (!n) return 0;
+    if ((u64)n > kCutMaxSrc) return ZERR(kErrParameterUnsupported);
+    const CutRule rule = cut_rule(avgLog);
+    hipStream_t s = c->stream;
+    if (!c->cutSmall.ensure(cut_small_bytes(n))) return ZERR(kErrMemoryAllocation);
+    u8* const small = (u8*)c->cutSmall.p;
+    c->timer.begin(s);
+    launch_cut_count(d_src, n, rule.bits, small, s);
+    c->timer.mark("cut_mark", s);
+    u32 nCand = 0;
+    if (isErr(dev_read(&nCand, cut_total_word(small, n), sizeof nCand, s))) return ZERR(kErrGeneric);
+    st.add_timer(c);
+    // (a hostile input makes the list as long as the source: the call then fails here, the list is never thinned)
+    const u64 P = cut_max_pieces(n, rule);
+    if (!c->cutList.ensure((size_t)nCand * 4 + 64) || !c->cutEnds.ensure((size_t)(P + 1) * 4)) return ZERR(kErrMemoryAllocation);
+    c->timer.begin(s);
+    if (nCand) launch_cut_emit(d_src, n, rule.bits, small, (u32*)c->cutList.p, s);
+    c->timer.mark("cut_mark", s);
+    launch_cut_select((const u32*)c->cutList.p, nCand, n, rule, (u32*)c->cutEnds.p, (u32)P, s);
+    c->timer.mark("cut_select", s);
+    std::vector<u32> ends((size_t)P + 1);
+    if (isErr(dev_read(ends.data(), c->cutEnds.p, ends.size() * 4, s))) return ZERR(kErrGeneric);
+    st.add_timer(c);
+    const u64 np = ends[0];
+    if (np == 0 || np > P || ends[np] != n) return ZERR(kErrGeneric);
+    sizes.reserve(np);
+    u64 from = 0;
+    for (u64 i = 1; i <= np; ++i) {
+        if (ends[i] <= from || ends[i] - from > rule.max) return ZERR(kErrGeneric);
+        sizes.push_back((size_t)(ends[i] - from)); from = ends[i];
+    }
+    return 0;
+}
+// host memory in, device memory out: the call's source where the kernels can read it
+static size_t cut_stage_src(ZSTD_CCtx* c, const void* src, size_t srcSize, bool deviceCall, const u8*& d_src)
+{
+    d_src = (const u8*)src;
+    if (deviceCall || !srcSize || is_device_ptr(src)) return 0;
+    if (!c->stageSrc.ensure(srcSize + 64)) return ZERR(kErrMemoryAllocation);
+    if (hipMemcpyAsync(c->stageSrc.p, src, srcSize, hipMemcpyHostToDevice, c->stream) != hipSuccess) return ZERR(kErrGeneric);
+    d_src = (const u8*)c->stageSrc.p;
+    return 0;
+}
+// ZSTD_compress2 / ZSTDMI_compressDevice / ZSTD_compress_usingCDict with the switch on: the source cut by content, the pieces written as
+// ZSTDMI_compressPack writes them — with the seek-table switch its one table behind them, without it the frames alone.
+static size_t compress_cut(ZSTD_CCtx* c, const CallParams& cp0, void* dst, size_t dstCapacity, const void* src, size_t srcSize, bool deviceCall)
+{
+    // what the cut call cannot be, before a byte is read (a pending prefix stays pending)
+    if (c->workers.size() > 1 || c->pfx || cp0.single || cp0.ldm == ZSTD_ps_enable || (cp0.windowLog >= 10 && cp0.windowLog <= 15)) return ZERR(kErrParameterUnsupported);
+    if ((u64)srcSize > kCutMaxSrc) return ZERR(kErrParameterUnsupported);
+    size_t e = cctx_bind(c); if (isErr(e)) return e;
+    c->lastRegionList = nullptr; c->lastCarryGroups = 0;
+    if (srcSize && !src) return ZERR(kErrSrcSizeWrong);
+    if (!dst) return deviceCall && dstCapacity ? ZERR(kErrDstBufferNull) : ZERR(kErrDstSizeTooSmall);
+    CallParams cp = cp0; cp.seek = false;
+    const u8* d_src; e = cut_stage_src(c, src, srcSize, deviceCall, d_src); if (isErr(e)) return e;
+    const bool dstDev = deviceCall || is_device_ptr(dst);
+    u8* d_dst = (u8*)dst; size_t devCap = dstCapacity;
+    if (!dstDev) {
+        u64 worst = 0;
+        if (!cut_bound(srcSize, cut_rule((unsigned)c->contentCuts), &worst)) return ZERR(kErrSrcSizeWrong);
+        devCap = dstCapacity < worst ? dstCapacity : (size_t)worst;
+        if (!c->stageDst.ensure(devCap + 64)) return ZERR(kErrMemoryAllocation);
+        d_dst = (u8*)c->stageDst.p;
+    }
+    PackStages st;
+    std::vector<size_t> sizes;
+    e = content_cut_sizes(c, d_src, srcSize, (unsigned)c->contentCuts, sizes, st); if (isErr(e)) return e;
+    std::vector<const u8*> srcs(sizes.size());
+    { size_t at = 0; for (size_t i = 0; i < sizes.size(); i++) { srcs[i] = d_src + at; at += sizes[i]; } }
+    const size_t r = compress_pack_core(c, cp, d_dst, devCap, srcs.data(), sizes.data(), sizes.size(), cp0.seek, st);
+    if (isErr(r)) return r;
+    c->lastContentCuts = (long long)sizes.size();
+    if (!dstDev && r) {
+        if (hipMemcpyAsync(dst, d_dst, r, hipMemcpyDeviceToHost, c->stream) != hipSuccess) return ZERR(kErrGeneric);
+        if (isErr(stream_wait(c->stream))) return ZERR(kErrGeneric);
+    }
+    return r;
+}
+static size_t content_cuts_impl(ZSTD_CCtx* c, const void* src, size_t srcSize, unsigned avgLog, size_t* pieceSizes, size_t capacity, size_t* nPieces)
+{
+    if (!c || !nPieces || (capacity && !pieceSizes)) return ZERR(kErrGeneric);
+    *nPieces = 0;
+    if (!cut_avglog_ok(avgLog)) return ZERR(kErrParameterOutOfBound);
+    if ((u64)srcSize > kCutMaxSrc) return ZERR(kErrParameterUnsupported);
+    size_t e = cctx_bind(c); if (isErr(e)) return e;
+    if (srcSize && !src) return ZERR(kErrSrcSizeWrong);
+    const u8* d_src; e = cut_stage_src(c, src, srcSize, false, d_src); if (isErr(e)) return e;
+    PackStages st;
+    std::vector<size_t> sizes;
+    e = content_cut_sizes(c, d_src, srcSize, avgLog, sizes, st); if (isErr(e)) return e;
+    st.file(c);
+    *nPieces = sizes.size();
+    if (sizes.size() > capacity) return ZERR(kErrDstSizeTooSmall);
+    for (size_t i = 0; i < sizes.size(); i++) pieceSizes[i] = sizes[i];
+    return 0;
+}
+extern "C" size_t ZSTDMI_CCtx_setContentCuts(ZSTD_CCtx* c, unsigned avgLog)
+{
+    if (!c) return ZERR(kErrGeneric);
+    if (avgLog && !cut_avglog_ok(avgLog)) return ZERR(kErrParameterOutOfBound);
+    c->contentCuts = (int)avgLog; c->paramGen++;
+    return 0;
+}
+extern "C" size_t ZSTDMI_contentCutsBound(size_t srcSize, unsigned avgLog)
+{
+    if (!cut_avglog_ok(avgLog)) return ZERR(kErrParameterOutOfBound);
+    u64 b = 0;
+    if (!cut_bound(srcSize, cut_rule(avgLog), &b) || b > (u64)(size_t)-1 || isErr((size_t)b)) return ZERR(kErrSrcSizeWrong);
+    return (size_t)b;
+}
+extern "C" size_t ZSTDMI_contentCuts(ZSTD_CCtx* c, const void* d_src, size_t srcSize, unsigned avgLog, size_t* pieceSizes, size_t capacity, size_t* nPieces)
+{
+    return guarded([&] { return content_cuts_impl(c, d_src, srcSize, avgLog, pieceSizes, capacity, nPieces); });
+}
+extern "C" long long ZSTDMI_debugLastContentCuts(const ZSTD_CCtx* c) { return c ? c->lastContentCuts : -1; }
+
 extern "C" size_t ZSTDMI_debugCompressSamples(ZSTD_CCtx* c, const void* src, const size_t* sizes, size_t n, size_t* outSizes)
 {
     if (!c || (n && (!sizes || !outSizes))) return ZERR(kErrGeneric);
+    if (c->contentCuts) return ZERR(kErrParameterUnsupported);
     return guarded([&] {
         std::vector<u64> offs(n);
         u64 o = 0; for (size_t i = 0; i < n; i++) { offs[i] = o; o += sizes[i]; }
