@@ -1009,6 +1009,16 @@ size_t ZSTDMI_debugEntropyBlockRaw(ZSTD_CCtx* cctx, void* dst, size_t dstCapacit
  * alone with the context's parameters and dictionary, in one pass through the pipeline; outSizes[i] = sample i's compressed size */
 size_t ZSTDMI_debugCompressSamples(ZSTD_CCtx* cctx, const void* src, const size_t* sizes, size_t n, size_t* outSizes);
 size_t ZSTDMI_debugPoisonedChunk(ZSTD_CCtx* cctx, unsigned nbSeq, unsigned litSize, unsigned srcSize, unsigned fill);
+/* the record of the long-distance stage of the last pass of the context's last compress call (a context without device workers):
+ * *nSplits = its splits, and for the first min(cap, *nSplits) of them, in position order, the window's start pos[i] and the match
+ * found there (mLen[i] 0 = none; mStart[i] its first byte, mOff[i] its distance).  Every position is in the stage's own coordinate:
+ * the pass's byte i lies at *base + i and nothing lies below *vlo (both 0 without a referenced prefix or a sliding window).
+ * parameter_unsupported when that pass ran no long-distance stage.  tests/test_gpu_ldm_model.py */
+size_t ZSTDMI_debugLdmPass(ZSTD_CCtx* cctx, unsigned* pos, unsigned* mStart, unsigned* mLen, unsigned* mOff, size_t cap,
+                           size_t* nSplits, unsigned* base, unsigned* vlo);
+/* on != 0: the long-distance stage of the context's later calls runs up to its matches and merges nothing into the finder's
+ * sequences (the call still writes a valid stream, from those): ZSTDMI_debugGetChunk then shows what the merge would have been given */
+size_t ZSTDMI_debugLdmSkipMerge(ZSTD_CCtx* cctx, int on);
 
 #ifdef __cplusplus
 }

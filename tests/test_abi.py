@@ -23,6 +23,7 @@ def test_library_exports_every_declared_symbol():
     lib = ctypes.CDLL(_ffi.LIB_PATH)
     names = _declared_symbols()
     assert len(names) >= 44 and "ZDICT_isError" in names and "ZSTD_CStreamOutSize" in names
+    assert "ZSTDMI_debugGetChunk" in names and "ZSTDMI_debugLdmPass" in names and "ZSTDMI_debugLdmSkipMerge" in names
     for n in names:
         assert hasattr(lib, n), f"{n} declared in include/zstd_mi355x.h but not exported"
         assert n in _ffi.SIGNATURES, f"{n} has no ctypes signature"

@@ -29,7 +29,7 @@
 
 namespace zmi {
 
-constexpr u32 kLdmTile = 16384;         // bytes per workgroup of the split kernels (256 lanes x 64 positions); frames are multiples of it
+constexpr u32 kLdmTile = 16384;         // bytes per workgroup of the split kernels (256 lanes x 64 positions); a frame may start inside one
 constexpr u32 kLdmSegCap = 4;           // splits kept per 64 positions (the first four): the workspace holds at most one per 16 bytes
 constexpr u32 kSortTile = 4096;         // elements per workgroup of the radix sort (16 rounds of 256)
 static_assert(kLdmPrefixAlign == kLdmTile, "a referenced prefix ends on a tile boundary of the virtual coordinate");
@@ -71,7 +71,9 @@ __device__ __forceinline__ u32 block_excl_scan256(u32 v, u32* part, u32* tot)
 
 // Split points (ZSTD_ldm_gear_feed): after byte p, h = (h << 1) + gear[byte]; a split ends at p + 1 when (h & stopMask) == 0.  Bit k
 // of h depends on the last k + 1 bytes only and stopMask lies below bit 64, so every lane starts 64 bytes ahead of its 64 positions
-// (never before its frame's start).  A split's window [p + 1 - minMatch, p + 1) must lie in the frame.
+// (never before its frame's start, where h is 0).  A split's window [p + 1 - minMatch, p + 1) must lie in the frame.  The default
+// blocks (64, 48, 32 KiB) make a frame span a multiple of the tile; ZSTDMI_CCtx_setHistory can make it any multiple of 4 KiB, so the
+// frame is taken per lane and per position, not per tile.  Only the first kLdmSegCap splits of a lane's 64 positions are kept.
 // PFX: n, the tiles and every position are virtual (see the head of the file); the one frame starts at pfx.vlo.
 template <bool EMIT, bool PFX>
 __global__ __launch_bounds__(256) void ldm_split_kernel(const u8* __restrict__ src, u64 n, u64 frameSpan, u32 minMatch, u64 stopMask, u32 hb, const LdmPrefix pfx,
@@ -102,14 +104,18 @@ __global__ __launch_bounds__(256) void ldm_split_kernel(const u8* __restrict__ s
         }
         if (p0 < tEnd) {
             u64 h = 0;
-            const u64 wlo = p0 >= fStart + 64 ? p0 - 64 : fStart;
+            // the frame of this lane's positions: a frame span need not be a multiple of the tile (nor of 64), so it is the lane's
+            // own, and it moves on where a frame starts among the lane's 64 positions (the hash starts from 0 there)
+            u64 fS = PFX ? fStart : p0 / frameSpan * frameSpan;
+            const u64 wlo = p0 >= fS + 64 ? p0 - 64 : fS;
             for (u64 q = wlo; q < p0; ++q) h = (h << 1) + gear[buf[ldm_pad((u32)(64 + (s64)(q - t0)))]];
             const u32 cnt = (tEnd - p0) < 64 ? (u32)(tEnd - p0) : 64u;
             const u32 k0 = (PFX && p0 < fStart) ? ((fStart - p0) < 64 ? (u32)(fStart - p0) : 64u) : 0u;      // (nothing lies in front of the prefix)
             for (u32 k = k0; k < cnt && found < kLdmSegCap; ++k) {
-                h = (h << 1) + gear[buf[ldm_pad(64 + tid * 64 + k)]];
                 const u64 p = p0 + k;
-                if ((h & stopMask) == 0 && p + 1 >= fStart + minMatch) {
+                if (!PFX && p == fS + frameSpan) { fS = p; h = 0; }
+                h = (h << 1) + gear[buf[ldm_pad(64 + tid * 64 + k)]];
+                if ((h & stopMask) == 0 && p + 1 >= fS + minMatch) {
                     if (pass == 1) {
                         const u32 w = (u32)(p + 1 - minMatch), i = base + found;
                         const u64 x = w >= lo ? window_hash([&](u32 j) { return (u32)buf[ldm_pad((u32)(64 + (s64)(w + j - t0)))]; }, mm)
@@ -439,8 +445,8 @@ void launch_ldm_count(const u8* src, u64 n, u64 frameSpan, const LdmLaunch& p, u
 u32* ldm_total_word(u8* small, u64 n) { const u32 nTiles = (u32)((n + kLdmTile - 1) / kLdmTile); return (u32*)small + 2 * (nTiles + 16); }
 
 // everything after the count: emit, sort, match, merge (nSplits > 0).  nChunks: the source's blocks.
-void launch_ldm_rest(const u8* src, u64 n, u32 nChunks, u32 chunkBytes, u64 frameSpan, const LdmLaunch& p, u32 nSplits, u8* small, u8* big,
-                     Seq* seqs, u8* lits, ChunkMeta* meta, hipStream_t stream, StageHook hook, const LdmPrefix& pfx)
+LdmRecord launch_ldm_rest(const u8* src, u64 n, u32 nChunks, u32 chunkBytes, u64 frameSpan, const LdmLaunch& p, u32 nSplits, u8* small, u8* big,
+                          Seq* seqs, u8* lits, ChunkMeta* meta, hipStream_t stream, StageHook hook, const LdmPrefix& pfx, bool merge)
 {
     const u32 nTiles = (u32)((n + kLdmTile - 1) / kLdmTile);
     const u32* tileBase = (const u32*)small + nTiles + 16;
@@ -481,10 +487,13 @@ void launch_ldm_rest(const u8* src, u64 n, u32 nChunks, u32 chunkBytes, u64 fram
     else hipLaunchKernelGGL(ldm_match_kernel<false>, dim3((nChunks + 3) / 4), dim3(256), 0, stream, src, n, nChunks, chunkBytes, frameSpan, p.minMatch, p.bucketLog, pfx,
                             splitPos, splitCheck, keyA, valA, inv, nSplits, mStart, mLen, mOff);
     hook("ldm_match");
+    LdmRecord rec; rec.splitPos = splitPos; rec.mStart = mStart; rec.mLen = mLen; rec.mOff = mOff; rec.nSplits = nSplits;
+    if (!merge) return rec;
     const u32 waves = nChunks < kMergeWaves ? ((nChunks + 3) & ~3u) : kMergeWaves;
     hipLaunchKernelGGL(ldm_merge_kernel, dim3(waves / 4), dim3(256), 0, stream, src, pfx.pre ? n - pfx.base : n, nChunks, chunkBytes, pfx.pre ? pfx.base : 0u, splitPos, nSplits, mStart, mLen, mOff,
                        seqs, lits, meta, scratch, waves);
     hook("ldm_merge");
+    return rec;
 }
 
 } // namespace zmi

@@ -128,8 +128,11 @@ size_t ldm_small_bytes(u64 n);
 size_t ldm_big_bytes(u64 nSplits);
 void launch_ldm_count(const u8* src, u64 n, u64 frameSpan, const LdmLaunch& p, u8* small, hipStream_t stream, const LdmPrefix& pfx);
 u32* ldm_total_word(u8* small, u64 n);
-void launch_ldm_rest(const u8* src, u64 n, u32 nChunks, u32 chunkBytes, u64 frameSpan, const LdmLaunch& p, u32 nSplits, u8* small, u8* big,
-                     Seq* seqs, u8* lits, ChunkMeta* meta, hipStream_t stream, StageHook hook, const LdmPrefix& pfx);
+// where a pass's splits and their matches lie in `big` afterwards (ZSTDMI_debugLdmPass)
+struct LdmRecord { const u32* splitPos = nullptr; const u32* mStart = nullptr; const u32* mLen = nullptr; const u32* mOff = nullptr; u32 nSplits = 0; };
+// merge false (ZSTDMI_debugLdmSkipMerge): the stage ends behind ldm_match and the finder's sequence store stays as it is
+LdmRecord launch_ldm_rest(const u8* src, u64 n, u32 nChunks, u32 chunkBytes, u64 frameSpan, const LdmLaunch& p, u32 nSplits, u8* small, u8* big,
+                          Seq* seqs, u8* lits, ChunkMeta* meta, hipStream_t stream, StageHook hook, const LdmPrefix& pfx, bool merge = true);
 // content-defined cuts (content_cuts.hip; the rule: zmi_cuts.h).  small: cut_small_bytes(n) bytes; the count leaves the candidates'
 // total in *cut_total_word, the emit writes that many ends in position order, the select 1 + cap words: the pieces, then their ends
 size_t cut_small_bytes(u64 n);

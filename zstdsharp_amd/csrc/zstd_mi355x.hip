@@ -36,6 +36,8 @@ struct ZSTD_CCtx_s {
     hipStream_t ownStream = nullptr, stream = nullptr;
     DevBuf seqs, lits, meta, tables, slots, offsets, total, cand, probe, stageSrc, stageDst;
     DevBuf ldmSmall, ldmBig;    // long-distance matching's workspace (allocated by the first call that runs it)
+    LdmRecord ldmRec; u32 ldmRecBase = 0, ldmRecVlo = 0; bool ldmRecOk = false;     // the last pass's stage (ZSTDMI_debugLdmPass)
+    bool ldmSkipMerge = false;  // ZSTDMI_debugLdmSkipMerge
     u32 lastChunks = 0;         // chunks of the last pass (debug hook)
     const u8* lastSrc = nullptr; u32 lastChunkBytes = 0;     // its source (debug hook: chunks without sequences keep their literals there)
     u32 passChunks = 16384;     // chunks per pass: 1 GiB of input bounds the HBM workspace to ~4.2 GiB
@@ -722,11 +724,13 @@ static size_t compress_range(ZSTD_CCtx* c, const CallParams& cp, u8* d_dst, size
             u32 nSplits = 0;
             if (isErr(dev_read(&nSplits, ldm_total_word((u8*)c->ldmSmall.p, nL), sizeof(u32), s))) return ZERR(kErrGeneric);
             c->timer.mark("ldm_count", s);
+            c->ldmRec = LdmRecord(); c->ldmRecBase = lp.base; c->ldmRecVlo = lp.vlo; c->ldmRecOk = true;
             if (nSplits) {
                 if (!c->ldmBig.ensure(ldm_big_bytes(nSplits))) return ZERR(kErrMemoryAllocation);
-                launch_ldm_rest(src, nL, nChunks, chunkBytes, span, fr.ldmP, nSplits, (u8*)c->ldmSmall.p, (u8*)c->ldmBig.p, seqs, lits, meta, s, c->timer.hook(), lp);
+                c->ldmRec = launch_ldm_rest(src, nL, nChunks, chunkBytes, span, fr.ldmP, nSplits, (u8*)c->ldmSmall.p, (u8*)c->ldmBig.p, seqs, lits, meta, s, c->timer.hook(), lp,
+                                            !c->ldmSkipMerge);
             }
-        }
+        } else c->ldmRecOk = false;
         launch_huf_build(lits, meta, tables, slots, nChunks, rs.rawLiterals, src, frames, s, c->timer.hook(), dct);
         if (cp.checksumFlag && fr.single) {
             // XXH64 does not merge: the whole content is one serial chain, carried from pass to pass (and from batch to batch); the
@@ -1812,6 +1816,28 @@ int ZSTDMI_CCtx_getStageTimes(const ZSTD_CCtx* c, float* ms, const char** names,
     for (int i = 0; i < n; i++) { if (ms) ms[i] = c->stageMs[i]; if (names) names[i] = c->stageNames[i]; }
     return n;
 }
+
+size_t ZSTDMI_debugLdmPass(ZSTD_CCtx* c, unsigned* pos, unsigned* mStart, unsigned* mLen, unsigned* mOff, size_t cap, size_t* nSplits, unsigned* base, unsigned* vlo)
+{
+    size_t e = cctx_bind(c); if (isErr(e)) return e;
+    if (!nSplits || !base || !vlo) return ZERR(kErrGeneric);
+    if (c->workers.size() > 1 || !c->lastChunks || !c->ldmRecOk) return ZERR(kErrParameterUnsupported);
+    const LdmRecord& r = c->ldmRec;
+    *nSplits = r.nSplits; *base = c->ldmRecBase; *vlo = c->ldmRecVlo;
+    const size_t k = r.nSplits < cap ? r.nSplits : cap;
+    const struct { unsigned* to; const u32* from; } rows[4] = { { pos, r.splitPos }, { mStart, r.mStart }, { mLen, r.mLen }, { mOff, r.mOff } };
+    for (const auto& row : rows)
+        if (k && row.to && host_memcpy(row.to, row.from, k * sizeof(u32), hipMemcpyDeviceToHost) != hipSuccess) return ZERR(kErrGeneric);
+    // what lies in front of the pass is searched by no block: ldm_match writes nothing for those splits (they are candidates only)
+    if (k && c->ldmRecBase) {
+        std::vector<u32> p(k);
+        if (host_memcpy(p.data(), r.splitPos, k * sizeof(u32), hipMemcpyDeviceToHost) != hipSuccess) return ZERR(kErrGeneric);
+        const size_t front = (size_t)(std::lower_bound(p.begin(), p.end(), c->ldmRecBase) - p.begin());
+        for (unsigned* col : { mStart, mLen, mOff }) if (col) std::fill(col, col + front, 0u);
+    }
+    return 0;
+}
+size_t ZSTDMI_debugLdmSkipMerge(ZSTD_CCtx* c, int on) { if (!c) return ZERR(kErrGeneric); c->ldmSkipMerge = on != 0; return 0; }
 
 size_t ZSTDMI_debugGetChunk(ZSTD_CCtx* c, size_t chunkIdx, ZSTDMI_Seq* seqs, size_t seqCap, size_t* nbSeq, void* lits, size_t litCap, size_t* litSize)
 {
