@@ -269,9 +269,11 @@ constexpr u32 kScanRound = 1024 * kScanItems;
 constexpr u32 kLinkItems = 2;
 constexpr u32 kLinkRound = 1024 * kLinkItems;
 // single workgroup: link check + prefix sums.  status: frames, total, blocks; [kStUsable] = 1 when the parallel walk is usable
+// pinned (null: none): the host's pinned copy of the status words (zmi_host.h); the words written here are written there too, and they
+// are all the host reads of the counting walk
 __global__ __launch_bounds__(1024) void walk_link_kernel(const SegInfo* __restrict__ segs, u32 nSeg, u64 srcSize, u32 maxFrames,
                                                          u32* __restrict__ frameBase, u32* __restrict__ blockBase, u64* __restrict__ dstBase,
-                                                         u32* __restrict__ status)
+                                                         u32* __restrict__ status, u32* __restrict__ pinned)
 {
     __shared__ u64 sh64[2][16], shBlk[2][16], shExit[2][16]; __shared__ u32 sh32[2][16]; __shared__ s32 shLast[2][16]; __shared__ u32 bad;
     const u32 tid = threadIdx.x, lane = lane_id(), wave = wave_id();
@@ -337,6 +339,10 @@ __global__ __launch_bounds__(1024) void walk_link_kernel(const SegInfo* __restri
         if (carryCnt > maxFrames || carryBlk > 0xFFFFFFF0ull) usable = 0;
         status[kStFrames] = carryCnt; status[kStErr] = 0; status[kStTotalLo] = (u32)carryDst; status[kStTotalHi] = (u32)(carryDst >> 32);
         status[kStUsable] = usable; status[kStUnsized] = 0; status[kStBlocks] = (u32)carryBlk;
+        if (pinned) {
+            pinned[kStFrames] = carryCnt; pinned[kStErr] = 0; pinned[kStTotalLo] = (u32)carryDst; pinned[kStTotalHi] = (u32)(carryDst >> 32);
+            pinned[kStUsable] = usable; pinned[kStUnsized] = 0; pinned[kStBlocks] = (u32)carryBlk;
+        }
     }
 }
 
@@ -810,6 +816,20 @@ void launch_range_clip(u8* dst, const u8* edge, ClipJob j0, ClipJob j1, hipStrea
     hipLaunchKernelGGL(range_clip_kernel, dim3((u32)(want < 2048 ? want : 2048), 2), dim3(256), 0, stream, dst, edge, j0, j1);
 }
 
+// ---- the status words at both ends of a call: set by a store per word, handed to the host through its pinned block (zmi_host.h) ----
+__global__ __launch_bounds__(128) void status_reset_kernel(u32* __restrict__ status)
+{
+    const u32 w = threadIdx.x;
+    if (w < kStWords) status[w] = (w == kStErrKeyLo || w == kStErrKeyHi) ? 0xFFFFFFFFu : 0u;
+}
+__global__ __launch_bounds__(128) void status_mirror_kernel(const u32* __restrict__ status, u32* __restrict__ pinned)
+{
+    const u32 w = threadIdx.x;
+    if (w < kStWords) pinned[w] = status[w];
+}
+void launch_status_reset(u32* status, hipStream_t stream) { hipLaunchKernelGGL(status_reset_kernel, dim3(1), dim3(128), 0, stream, status); }
+void launch_status_mirror(const u32* status, u32* pinned, hipStream_t stream) { hipLaunchKernelGGL(status_mirror_kernel, dim3(1), dim3(128), 0, stream, status, pinned); }
+
 size_t decode_walk_workspace_bytes(u64 srcSize)
 {
     const u64 nSeg = (srcSize + (1ull << kSegLog) - 1) >> kSegLog;
@@ -827,11 +847,11 @@ static WalkWs walk_ws(u8* walkWs, u64 srcSize)
     return w;
 }
 // count: frames, blocks, content bytes -> status (the host then sizes the lists)
-void launch_frame_walk_count(const u8* src, u64 srcSize, u32 maxFrames, u32* status, u8* walkWs, hipStream_t stream)
+void launch_frame_walk_count(const u8* src, u64 srcSize, u32 maxFrames, u32* status, u8* walkWs, hipStream_t stream, u32* pinned)
 {
     const WalkWs w = walk_ws(walkWs, srcSize);
     hipLaunchKernelGGL(walk_segments_kernel, dim3(w.nSeg), dim3(64), 0, stream, src, srcSize, w.segs, w.nSeg);
-    hipLaunchKernelGGL(walk_link_kernel, dim3(1), dim3(1024), 0, stream, w.segs, w.nSeg, srcSize, maxFrames, w.frameBase, w.blockBase, w.dstBase, status);
+    hipLaunchKernelGGL(walk_link_kernel, dim3(1), dim3(1024), 0, stream, w.segs, w.nSeg, srcSize, maxFrames, w.frameBase, w.blockBase, w.dstBase, status, pinned);
 }
 void launch_frame_walk_emit(const u8* src, u64 srcSize, FrameDesc* frames, BlockDesc* blocks, u8* walkWs, hipStream_t stream)
 {
@@ -849,13 +869,16 @@ void launch_frame_walk_serial(const u8* src, u64 srcSize, FrameDesc* frames, Blo
 // block_parse: the two section headers of every compressed block, one lane per block
 // ------------------------------------------------------------------------------------------------
 // (kDev: list_count, zmi_decode.h — the kernel itself is the template, so that kDev = false stays the kernel it always was)
+// seqPlane (null: none; seq_scan_kernel): one u32 per block, the sequences it will file records for — nbSeq of a compressed block
+// without an error, else 0.  Every block's word is written here; block_link zeroes the word of a block it fails or makes a phantom.
 template <bool kDev = false>
-__global__ __launch_bounds__(256) void block_parse_kernel(const u8* __restrict__ src, BlockDesc* __restrict__ blocks, u32 nBlocks, u32* __restrict__ status)
+__global__ __launch_bounds__(256) void block_parse_kernel(const u8* __restrict__ src, BlockDesc* __restrict__ blocks, u32 nBlocks, u32* __restrict__ status,
+                                                          u32* __restrict__ seqPlane)
 {
     const u32 bi = blockIdx.x * 256 + threadIdx.x;
     if (bi >= list_count<kDev>(nBlocks, status, kStBlocks)) return;
     BlockDesc& B = blocks[bi];
-    if (B.type != 2) return;
+    if (B.type != 2) { if (seqPlane) seqPlane[bi] = 0; return; }
     const u32 bsz = B.bsz;
     u32 err = 0;
     do {
@@ -894,6 +917,7 @@ __global__ __launch_bounds__(256) void block_parse_kernel(const u8* __restrict__
         B.bitsOff = bp;
     } while (false);
     if (err) { B.err = err; report_error(status, bi, kStageParse, err); }
+    if (seqPlane) seqPlane[bi] = (err || B.err) ? 0u : B.nbSeq;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -921,7 +945,8 @@ __device__ __forceinline__ const u64* lit_rooms(const u32* __restrict__ status)
 }
 template <bool kSet, bool kOpen = false, bool kDev = false>
 __global__ __launch_bounds__(64) void block_link_small_kernel(FrameDesc* __restrict__ frames, BlockDesc* __restrict__ blocks, u32 nFrames, u32 haveDict,
-                                                              u32 earlyLiterals, u32* __restrict__ status, const DictSlot* __restrict__ slots)
+                                                              u32 earlyLiterals, u32* __restrict__ status, const DictSlot* __restrict__ slots,
+                                                              u32* __restrict__ seqPlane)
 {
     const u32 f = blockIdx.x * 64 + threadIdx.x;
     if (f >= list_count<kDev>(nFrames, status, kStFrames)) return;
@@ -959,7 +984,10 @@ __global__ __launch_bounds__(64) void block_link_small_kernel(FrameDesc* __restr
                 else { B.tblSrc[t] = bi; lastTbl[t] = bi; }
             }
         }
-        if (err) { B.err = err; report_error(status, bi, B.litType >= 2 && (err == kErrDictionaryCorrupted || B.litSize > F.dstSize) ? kStageLiterals : kStageSequences, err); }
+        if (err) {
+            B.err = err; report_error(status, bi, B.litType >= 2 && (err == kErrDictionaryCorrupted || B.litSize > F.dstSize) ? kStageLiterals : kStageSequences, err);
+            if (seqPlane) seqPlane[bi] = 0;     // (block_parse_kernel)
+        }
     }
     F.hasSeq = hasSeq;
     if constexpr (kOpen) { if (noRoom) F.unsized |= kFrameNoRoom; }
@@ -983,7 +1011,7 @@ __device__ __forceinline__ u32 latest_before(u64 mask, u32 firstOfBatch, u32 car
 // kOpen: as in block_link_small_kernel (a block behind one without room has none either: the prefix sum counts them all)
 template <bool PH, bool kSet = false, bool kOpen = false>
 __device__ __forceinline__ void block_link_body(FrameDesc* __restrict__ frames, BlockDesc* __restrict__ blocks, u32 nFrames, u32 haveDict,
-                                                u32 earlyLiterals, u32* __restrict__ status, u32 phantoms, const DictSlot* __restrict__ slots = nullptr)
+                                                u32 earlyLiterals, u32* __restrict__ status, u32 phantoms, const DictSlot* __restrict__ slots, u32* __restrict__ seqPlane)
 {
     const u32 f = blockIdx.x, lane = threadIdx.x;
     if (f >= nFrames) return;
@@ -1042,7 +1070,7 @@ __device__ __forceinline__ void block_link_body(FrameDesc* __restrict__ frames, 
             if (seqs && mode == 3) { src3[t] = latest_before(def, first + k0, last, lane); if (src3[t] == kNoBlock && !ph) err = err ? err : (u32)kErrCorruption; }
             if (def) last = first + k0 + (63u - (u32)__builtin_clzll(def));
         }
-        if (ph && have) { BlockDesc& B = blocks[bi]; B.type = 1; B.outSize = 0; B.nbSeq = 0; }
+        if (ph && have) { BlockDesc& B = blocks[bi]; B.type = 1; B.outSize = 0; B.nbSeq = 0; if (seqPlane) seqPlane[bi] = 0; }
         else if (live) {
             BlockDesc& B = blocks[bi];
             if (litType >= 2) {
@@ -1052,7 +1080,10 @@ __device__ __forceinline__ void block_link_body(FrameDesc* __restrict__ frames, 
                 B.litInPlace = (nbSeq == 0 && !dumped && (!earlyLiterals || (k0 + lane == 0 && !F.unsized))) ? 1u : 0u;
             }
             if (seqs) { B.tblSrc[0] = src3[0]; B.tblSrc[1] = src3[1]; B.tblSrc[2] = src3[2]; }
-            if (err) { B.err = err; report_error(status, bi, litType >= 2 && (err == kErrDictionaryCorrupted || litSize > dstSize) ? kStageLiterals : kStageSequences, err); }
+            if (err) {
+                B.err = err; report_error(status, bi, litType >= 2 && (err == kErrDictionaryCorrupted || litSize > dstSize) ? kStageLiterals : kStageSequences, err);
+                if (seqPlane) seqPlane[bi] = 0;     // (block_parse_kernel)
+            }
         }
     }
     if (lane == 0) {
@@ -1067,27 +1098,26 @@ __device__ __forceinline__ void block_link_body(FrameDesc* __restrict__ frames, 
 // (kStream: a fragment of a segmented stream, whose first `phantoms` blocks are carried definers — never a set, open or kDev instance)
 template <bool kSet, bool kOpen, bool kDev, bool kStream>
 __global__ __launch_bounds__(64) void block_link_kernel(FrameDesc* __restrict__ frames, BlockDesc* __restrict__ blocks, u32 nFrames, u32 haveDict,
-                                                        u32 earlyLiterals, u32* __restrict__ status, u32 phantoms, const DictSlot* __restrict__ slots)
+                                                        u32 earlyLiterals, u32* __restrict__ status, u32 phantoms, const DictSlot* __restrict__ slots,
+                                                        u32* __restrict__ seqPlane)
 {
     static_assert(!kStream || !(kSet || kOpen || kDev), "a stream fragment has one dictionary and a content size");
     block_link_body<kStream, kSet, kOpen>(frames, blocks, list_count<kDev>(nFrames, status, kStFrames), kSet ? 0 : haveDict, earlyLiterals, status,
-                                          kStream ? phantoms : 0, kSet ? slots : nullptr);
+                                          kStream ? phantoms : 0, kSet ? slots : nullptr, kDev ? nullptr : seqPlane);
 }
 
 // ------------------------------------------------------------------------------------------------
 // seq_scan: where every block's sequence records go (exclusive scan of nbSeq), single workgroup
 // ------------------------------------------------------------------------------------------------
-// exclusive scan over n items of a single workgroup: load(i) -> the item's value, store(i, sum of the items before it); -> the total
-template <class Load, class Store>
-__device__ __forceinline__ u64 workgroup_scan(u32 n, u64 (*shW)[16], Load load, Store store)
+// exclusive scan over n items of a single workgroup: fetch(i0, o) -> the values of the thread's kScanItems consecutive items from i0 on
+// (0 for an item at or beyond n), store(i, sum of the items before it); -> the total, in every thread
+template <class Fetch, class Store>
+__device__ __forceinline__ u64 workgroup_scan_items(u32 n, u64 (*shW)[16], Fetch fetchItems, Store store)
 {
     const u32 tid = threadIdx.x, lane = lane_id(), wave = wave_id();
     u64 carry = 0;
     u64 v[kScanItems], nx[kScanItems];
-    auto fetch = [&](u32 base, u64 (&o)[kScanItems]) {
-#pragma unroll
-        for (u32 j = 0; j < kScanItems; ++j) { const u32 i = base + tid * kScanItems + j; o[j] = i < n ? load(i) : 0; }
-    };
+    auto fetch = [&](u32 base, u64 (&o)[kScanItems]) { fetchItems(base + tid * kScanItems, o); };
     fetch(0, v);
     u32 par = 0;
     for (u32 base = 0; base < n; base += kScanRound, par ^= 1) {
@@ -1111,47 +1141,76 @@ __device__ __forceinline__ u64 workgroup_scan(u32 n, u64 (*shW)[16], Load load, 
     }
     return carry;
 }
+// (the items one by one: load(i) -> the item's value)
+template <class Load, class Store>
+__device__ __forceinline__ u64 workgroup_scan(u32 n, u64 (*shW)[16], Load load, Store store)
+{
+    return workgroup_scan_items(n, shW, [&](u32 i0, u64 (&o)[kScanItems]) {
+#pragma unroll
+        for (u32 j = 0; j < kScanItems; ++j) o[j] = i0 + j < n ? load(i0 + j) : 0;
+    }, store);
+}
 
 // kDev (ZSTDMI_decompressBatchAsync): the number of blocks comes from the status words, and so does the limit the caller set for the
 // sequence records (kStCapSeq*: the record buffer was sized from it, once).  A block with sequences whose records would end beyond the
 // limit fails with workSpace_tooSmall: its err keeps every later stage off it, and its key — block and stage fields zero, so that it
 // outranks whatever else the entry's blocks report — folds into the entry's answer (batch_fold).  The sums run over such blocks too:
 // every block with sequences behind one is refused as well.
+// kDev = false reads no BlockDesc: an item is a word of seqPlane (block_parse_kernel), the dense image of what the kDev instance
+// gathers at BlockDesc's stride, a cache line per item; a thread's four consecutive items are one 16-byte load (the plane is 16-byte
+// aligned and kScanItems is 4).  pinned (null: none): the host's pinned copy of the status words (zmi_host.h) — this kernel is the last
+// of the pre-pass to write them, so it hands all of them over and the host needs no copy behind it.
 template <bool kDev = false>
-__global__ __launch_bounds__(1024) void seq_scan_kernel(BlockDesc* __restrict__ blocks, u32 nBlocks, u32* __restrict__ status)
+__global__ __launch_bounds__(1024) void seq_scan_kernel(BlockDesc* __restrict__ blocks, u32 nBlocks, u32* __restrict__ status, const u32* __restrict__ seqPlane,
+                                                        u32* __restrict__ pinned)
 {
     __shared__ u64 shW[2][16];
-    u64 capSeq = 0; unsigned long long* keys = nullptr;
+    u64 total;
     if constexpr (kDev) {
-        nBlocks = status[kStBlocks]; capSeq = (u64)status[kStCapSeqLo] | ((u64)status[kStCapSeqHi] << 32);
-        keys = reinterpret_cast<unsigned long long*>((uintptr_t)((u64)status[kStBlockKeysLo] | ((u64)status[kStBlockKeysHi] << 32)));
-    }
-    const u64 total = workgroup_scan(nBlocks, shW,
-        [&](u32 i) -> u64 { const BlockDesc& B = blocks[i]; return (B.type == 2 && !B.err) ? B.nbSeq : 0u; },
-        [&](u32 i, u64 before) {
-            blocks[i].seqBase = before;
-            if constexpr (kDev) {
+        nBlocks = status[kStBlocks];
+        const u64 capSeq = (u64)status[kStCapSeqLo] | ((u64)status[kStCapSeqHi] << 32);
+        unsigned long long* const keys = reinterpret_cast<unsigned long long*>((uintptr_t)((u64)status[kStBlockKeysLo] | ((u64)status[kStBlockKeysHi] << 32)));
+        total = workgroup_scan(nBlocks, shW,
+            [&](u32 i) -> u64 { const BlockDesc& B = blocks[i]; return (B.type == 2 && !B.err) ? B.nbSeq : 0u; },
+            [&](u32 i, u64 before) {
                 BlockDesc& B = blocks[i];
+                B.seqBase = before;
                 if (B.type == 2 && !B.err && B.nbSeq && before + B.nbSeq > capSeq) { B.err = kErrWorkSpaceTooSmall; atomicMin(keys + i, (unsigned long long)kErrWorkSpaceTooSmall); }
-            }
-        });
+            });
+    } else {
+        static_assert(kScanItems == 4, "a thread's items are one uint4");
+        total = workgroup_scan_items(nBlocks, shW,
+            [&](u32 i0, u64 (&o)[kScanItems]) {
+                if (i0 + kScanItems <= nBlocks) { const uint4 q = *reinterpret_cast<const uint4*>(seqPlane + i0); o[0] = q.x; o[1] = q.y; o[2] = q.z; o[3] = q.w; }
+                else {
+#pragma unroll
+                    for (u32 j = 0; j < kScanItems; ++j) o[j] = i0 + j < nBlocks ? seqPlane[i0 + j] : 0u;
+                }
+            },
+            [&](u32 i, u64 before) { blocks[i].seqBase = before; });
+    }
     if (threadIdx.x == 0) { status[kStSeqLo] = (u32)total; status[kStSeqHi] = (u32)(total >> 32); }
+    if constexpr (!kDev) {
+        // (the total is the same in every thread; the other words were written by kernels in front of this one)
+        const u32 w = threadIdx.x;
+        if (pinned && w < kStWords) pinned[w] = w == kStSeqLo ? (u32)total : w == kStSeqHi ? (u32)(total >> 32) : status[w];
+    }
 }
 
 void launch_block_prepass(const u8* src, FrameDesc* frames, BlockDesc* blocks, u32 nFrames, u32 nBlocks, const DecodeDict& dd, u32 earlyLiterals, u32* status, hipStream_t stream,
-                          u32 phantoms, bool open)
+                          u32* seqPlane, u32* pinned, u32 phantoms, bool open)
 {
     // (a set instance reads whether its frame has a formatted dictionary from the frame's slot)
     const DictSlot* const slots = dd.slots; const u32 haveDict = !slots && dd.fmt ? 1u : 0u;
-    hipLaunchKernelGGL(block_parse_kernel<>, dim3((nBlocks + 255) / 256), dim3(256), 0, stream, src, blocks, nBlocks, status);
+    hipLaunchKernelGGL(block_parse_kernel<>, dim3((nBlocks + 255) / 256), dim3(256), 0, stream, src, blocks, nBlocks, status, seqPlane);
     // a fragment of a segmented stream: one frame whose first blocks are carried definers (never a batch, and the host refuses it with a set)
-    if (phantoms && !open && !slots) hipLaunchKernelGGL((block_link_kernel<false, false, false, true>), dim3(nFrames), dim3(64), 0, stream, frames, blocks, nFrames, haveDict, earlyLiterals, status, phantoms, slots);
+    if (phantoms && !open && !slots) hipLaunchKernelGGL((block_link_kernel<false, false, false, true>), dim3(nFrames), dim3(64), 0, stream, frames, blocks, nFrames, haveDict, earlyLiterals, status, phantoms, slots, seqPlane);
     else with_flags([&](auto set, auto op) {
-        hipLaunchKernelGGL((block_link_small_kernel<set(), op()>), dim3((nFrames + 63) / 64), dim3(64), 0, stream, frames, blocks, nFrames, haveDict, earlyLiterals, status, slots);
+        hipLaunchKernelGGL((block_link_small_kernel<set(), op()>), dim3((nFrames + 63) / 64), dim3(64), 0, stream, frames, blocks, nFrames, haveDict, earlyLiterals, status, slots, seqPlane);
         if (nBlocks > nFrames)          // (some frame has several blocks)
-            hipLaunchKernelGGL((block_link_kernel<set(), op(), false, false>), dim3(nFrames), dim3(64), 0, stream, frames, blocks, nFrames, haveDict, earlyLiterals, status, 0u, slots);
+            hipLaunchKernelGGL((block_link_kernel<set(), op(), false, false>), dim3(nFrames), dim3(64), 0, stream, frames, blocks, nFrames, haveDict, earlyLiterals, status, 0u, slots, seqPlane);
     }, slots != nullptr, open);
-    hipLaunchKernelGGL(seq_scan_kernel<>, dim3(1), dim3(1024), 0, stream, blocks, nBlocks, status);
+    hipLaunchKernelGGL(seq_scan_kernel<>, dim3(1), dim3(1024), 0, stream, blocks, nBlocks, status, (const u32*)seqPlane, pinned);
 }
 
 // the pre-pass of a batch enqueued from the device: the open instances, the counts from the status words, grids over the caller's limits
@@ -1159,12 +1218,12 @@ void launch_block_prepass(const u8* src, FrameDesc* frames, BlockDesc* blocks, u
 void launch_block_prepass_d(const u8* src, FrameDesc* frames, BlockDesc* blocks, u32 capFrames, u32 capBlocks, const DecodeDict& dd, u32* status, hipStream_t stream)
 {
     const DictSlot* const slots = dd.slots; const u32 haveDict = !slots && dd.fmt ? 1u : 0u;        // (as launch_block_prepass)
-    hipLaunchKernelGGL(block_parse_kernel<true>, dim3((capBlocks + 255) / 256), dim3(256), 0, stream, src, blocks, 0u, status);
+    hipLaunchKernelGGL(block_parse_kernel<true>, dim3((capBlocks + 255) / 256), dim3(256), 0, stream, src, blocks, 0u, status, (u32*)nullptr);
     with_flags([&](auto set) {
-        hipLaunchKernelGGL((block_link_small_kernel<set(), true, true>), dim3((capFrames + 63) / 64), dim3(64), 0, stream, frames, blocks, 0u, haveDict, 0u, status, slots);
-        hipLaunchKernelGGL((block_link_kernel<set(), true, true, false>), dim3(capFrames), dim3(64), 0, stream, frames, blocks, 0u, haveDict, 0u, status, 0u, slots);
+        hipLaunchKernelGGL((block_link_small_kernel<set(), true, true>), dim3((capFrames + 63) / 64), dim3(64), 0, stream, frames, blocks, 0u, haveDict, 0u, status, slots, (u32*)nullptr);
+        hipLaunchKernelGGL((block_link_kernel<set(), true, true, false>), dim3(capFrames), dim3(64), 0, stream, frames, blocks, 0u, haveDict, 0u, status, 0u, slots, (u32*)nullptr);
     }, slots != nullptr);
-    hipLaunchKernelGGL(seq_scan_kernel<true>, dim3(1), dim3(1024), 0, stream, blocks, 0u, status);
+    hipLaunchKernelGGL(seq_scan_kernel<true>, dim3(1), dim3(1024), 0, stream, blocks, 0u, status, (const u32*)nullptr, (u32*)nullptr);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1172,9 +1231,11 @@ void launch_block_prepass_d(const u8* src, FrameDesc* frames, BlockDesc* blocks,
 // ------------------------------------------------------------------------------------------------
 // kSet: the repcodes a frame starts from are its own dictionary's (one frame per wave: the record's fields are wave-uniform)
 // kOpen (a batch with entries that hold unsized frames): FrameDesc::unsized carries flags beside "no content size" (kFrameOpen)
+// sizePlane (null: none; a call that runs frame_rescan_kernel behind this one): one u64 per frame, its dstSize as this kernel leaves it
 template <bool kSet, bool kOpen = false>
 __device__ __forceinline__ void block_offsets_body(FrameDesc* __restrict__ frames, BlockDesc* __restrict__ blocks, u32 nFrames,
-                                                   const DictInfo* __restrict__ di, u32* __restrict__ status, const DictSlot* __restrict__ slots)
+                                                   const DictInfo* __restrict__ di, u32* __restrict__ status, const DictSlot* __restrict__ slots,
+                                                   u64* __restrict__ sizePlane)
 {
     const u32 f = blockIdx.x, lane = threadIdx.x;
     if (f >= nFrames) return;
@@ -1232,23 +1293,37 @@ __device__ __forceinline__ void block_offsets_body(FrameDesc* __restrict__ frame
             if (acc > F.dstSize) { F.bad = 1; report_error(status, (u64)first + nb - 1, kStageFrameEnd, kErrCorruption); }   // more than nbBlocks x blockSizeMax: no valid encoder
             else F.dstSize = acc;
         }
+        if (sizePlane) sizePlane[f] = F.dstSize;
     }
 }
 template <bool kSet, bool kOpen, bool kDev>
 __global__ __launch_bounds__(64) void block_offsets_kernel(FrameDesc* __restrict__ frames, BlockDesc* __restrict__ blocks, u32 nFrames,
-                                                           const DictInfo* __restrict__ di, u32* __restrict__ status, const DictSlot* __restrict__ slots)
+                                                           const DictInfo* __restrict__ di, u32* __restrict__ status, const DictSlot* __restrict__ slots,
+                                                           u64* __restrict__ sizePlane)
 {
     static_assert(kOpen || !kDev, "a batch enqueued from the device runs the open instances");
-    block_offsets_body<kSet, kOpen>(frames, blocks, list_count<kDev>(nFrames, status, kStFrames), kSet ? nullptr : di, status, kSet ? slots : nullptr);
+    block_offsets_body<kSet, kOpen>(frames, blocks, list_count<kDev>(nFrames, status, kStFrames), kSet ? nullptr : di, status, kSet ? slots : nullptr,
+                                    kOpen ? nullptr : sizePlane);
 }
 
 // frames without a content size: the frames' output offsets from their regenerated sizes (single workgroup); the total goes to
-// status, and a total beyond the destination's capacity stops everything behind this kernel
-__global__ __launch_bounds__(1024) void frame_rescan_kernel(FrameDesc* __restrict__ frames, u32 nFrames, u64 dstCapacity, u32* __restrict__ status)
+// status, and a total beyond the destination's capacity stops everything behind this kernel.  The sizes are read from sizePlane
+// (block_offsets_body), dense, a thread's four as two 16-byte loads, not at FrameDesc's stride.
+__global__ __launch_bounds__(1024) void frame_rescan_kernel(FrameDesc* __restrict__ frames, u32 nFrames, u64 dstCapacity, u32* __restrict__ status,
+                                                            const u64* __restrict__ sizePlane)
 {
     __shared__ u64 shW[2][16];
-    const u64 total = workgroup_scan(nFrames, shW,
-        [&](u32 i) -> u64 { return frames[i].dstSize; },
+    static_assert(kScanItems == 4, "a thread's items are two ulonglong2");
+    const u64 total = workgroup_scan_items(nFrames, shW,
+        [&](u32 i0, u64 (&o)[kScanItems]) {
+            if (i0 + kScanItems <= nFrames) {
+                const ulonglong2 a = *reinterpret_cast<const ulonglong2*>(sizePlane + i0), b = *reinterpret_cast<const ulonglong2*>(sizePlane + i0 + 2);
+                o[0] = a.x; o[1] = a.y; o[2] = b.x; o[3] = b.y;
+            } else {
+#pragma unroll
+                for (u32 j = 0; j < kScanItems; ++j) o[j] = i0 + j < nFrames ? sizePlane[i0 + j] : 0u;
+            }
+        },
         [&](u32 i, u64 before) { frames[i].dstOff = before; });
     if (threadIdx.x == 0) {
         status[kStActualLo] = (u32)total; status[kStActualHi] = (u32)(total >> 32);
@@ -1256,20 +1331,20 @@ __global__ __launch_bounds__(1024) void frame_rescan_kernel(FrameDesc* __restric
     }
 }
 
-void launch_block_offsets(FrameDesc* frames, BlockDesc* blocks, u32 nFrames, const DecodeDict& dd, const DictInfo* reps, u32 rescan, u64 dstCapacity, u32* status, hipStream_t stream,
+void launch_block_offsets(FrameDesc* frames, BlockDesc* blocks, u32 nFrames, const DecodeDict& dd, const DictInfo* reps, u64* sizePlane, u64 dstCapacity, u32* status, hipStream_t stream,
                           bool open)
 {
     // (a set instance starts from its frame's slot)
     with_flags([&](auto set, auto op) {
-        hipLaunchKernelGGL((block_offsets_kernel<set(), op(), false>), dim3(nFrames), dim3(64), 0, stream, frames, blocks, nFrames, reps, status, dd.slots);
+        hipLaunchKernelGGL((block_offsets_kernel<set(), op(), false>), dim3(nFrames), dim3(64), 0, stream, frames, blocks, nFrames, reps, status, dd.slots, sizePlane);
     }, dd.slots != nullptr, open);
-    if (rescan) hipLaunchKernelGGL(frame_rescan_kernel, dim3(1), dim3(1024), 0, stream, frames, nFrames, dstCapacity, status);
+    if (sizePlane) hipLaunchKernelGGL(frame_rescan_kernel, dim3(1), dim3(1024), 0, stream, frames, nFrames, dstCapacity, status, (const u64*)sizePlane);
 }
 
 void launch_block_offsets_d(FrameDesc* frames, BlockDesc* blocks, u32 capFrames, const DecodeDict& dd, u32* status, hipStream_t stream)
 {
     with_flags([&](auto set) {
-        hipLaunchKernelGGL((block_offsets_kernel<set(), true, true>), dim3(capFrames), dim3(64), 0, stream, frames, blocks, 0u, dd.dinfo, status, dd.slots);
+        hipLaunchKernelGGL((block_offsets_kernel<set(), true, true>), dim3(capFrames), dim3(64), 0, stream, frames, blocks, 0u, dd.dinfo, status, dd.slots, (u64*)nullptr);
     }, dd.slots != nullptr);
 }
 

@@ -7,8 +7,10 @@
 namespace zmi {
 
 // ---- exclusive scan of ChunkMeta::outSize (one workgroup; nChunks is at most a few hundred thousand) ----
+// pinned (null: none): the context's pinned block (PinBuf, zmi_host.h), where the host reads what it wants of the pass behind its wait:
+// word 0 the total, word 1 + i the offset of chunk marks.chunk[i]
 __global__ __launch_bounds__(1024) void scan_sizes_kernel(const ChunkMeta* __restrict__ meta, u32 nChunks,
-                                                          u64* __restrict__ offsets, u64* __restrict__ total)
+                                                          u64* __restrict__ offsets, u64* __restrict__ total, u64* __restrict__ pinned, PassMarks marks)
 {
     __shared__ u32 waveSum[16];
     const u32 tid = threadIdx.x, lane = lane_id(), wave = wave_id();
@@ -27,6 +29,10 @@ __global__ __launch_bounds__(1024) void scan_sizes_kernel(const ChunkMeta* __res
         __syncthreads();
     }
     if (tid == 0) *total = carry;
+    if (pinned) {       // (the last round's barrier stands between the offsets' stores and these loads)
+        if (tid == 0) pinned[0] = carry;
+        if (tid < marks.n && marks.chunk[tid] < nChunks) pinned[1 + tid] = offsets[marks.chunk[tid]];
+    }
 }
 
 // ---- gather: copy each chunk's frame from its slot (or, for stored blocks, header + source bytes) to dst ----
@@ -611,9 +617,9 @@ __global__ void xxh_carry_file_kernel(const XxhCarry* __restrict__ st, ChunkMeta
     if (threadIdx.x == 0 && blockIdx.x == 0) chunk->checksum = st->hash;
 }
 
-void launch_scan_sizes(const ChunkMeta* meta, u32 nChunks, u64* offsets, u64* total, hipStream_t stream)
+void launch_scan_sizes(const ChunkMeta* meta, u32 nChunks, u64* offsets, u64* total, hipStream_t stream, u64* pinned, const PassMarks& marks)
 {
-    hipLaunchKernelGGL(scan_sizes_kernel, dim3(1), dim3(1024), 0, stream, meta, nChunks, offsets, total);
+    hipLaunchKernelGGL(scan_sizes_kernel, dim3(1), dim3(1024), 0, stream, meta, nChunks, offsets, total, pinned, marks);
 }
 void launch_gather(const u8* src, u64 srcSize, const u8* slots, const ChunkMeta* meta, const u64* offsets, u8* dst, u64 dstCapacity,
                    u32 nChunks, u32 chunkBytes, hipStream_t stream)

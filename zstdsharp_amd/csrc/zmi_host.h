@@ -75,7 +75,11 @@ struct SeqCarry { HufTable* tables; const u32* leaders; u32 nGroups, rawLiterals
 void launch_seq_encode(Seq* seqs, ChunkMeta* meta, u8* slots, u32 nChunks, u32 strategy, const FrameHeaderSpec& header, u32 resolveReps,
                        const u32* initReps, const FrameLayout& frames, hipStream_t stream, const DictCTables* dct = nullptr,
                        const CDictSlot* dictSlots = nullptr, const u32* chunkSlot = nullptr, const SeqCarry* carry = nullptr);
-void launch_scan_sizes(const ChunkMeta* meta, u32 nChunks, u64* offsets, u64* total, hipStream_t stream);
+// pinned (null: none): kPassPinWords u64 of the context's pinned block: the pass's total and the offsets of up to kPassMarks marked
+// chunks (indices into the pass), stored there by the scan itself for the host to read behind its wait
+constexpr u32 kPassMarks = 16, kPassPinWords = 1 + kPassMarks;
+struct PassMarks { u32 n = 0; u32 chunk[kPassMarks] = {}; };
+void launch_scan_sizes(const ChunkMeta* meta, u32 nChunks, u64* offsets, u64* total, hipStream_t stream, u64* pinned = nullptr, const PassMarks& marks = PassMarks());
 void launch_gather(const u8* src, u64 srcSize, const u8* slots, const ChunkMeta* meta, const u64* offsets, u8* dst, u64 dstCapacity,
                    u32 nChunks, u32 chunkBytes, hipStream_t stream);
 void launch_xxh64(const u8* src, ChunkMeta* meta, u32 nChunks, const FrameLayout& frames, hipStream_t stream, const u32* chunkLens = nullptr);
@@ -159,8 +163,13 @@ template <class F, class... Bs> inline void with_flags(F&& f, bool b, Bs... rest
     if (b) with_flags([&](auto... cs) { f(std::true_type(), cs...); }, rest...);
     else   with_flags([&](auto... cs) { f(std::false_type(), cs...); }, rest...);
 }
+// the status words (kSt*, zmi_common.h) at the start of a call: error key "none" (all ones), everything else zero; and their copy into
+// the context's pinned block (PinBuf below), which the host reads behind its wait
+void launch_status_reset(u32* status, hipStream_t stream);
+void launch_status_mirror(const u32* status, u32* pinned, hipStream_t stream);
 size_t decode_walk_workspace_bytes(u64 srcSize);
-void launch_frame_walk_count(const u8* src, u64 srcSize, u32 maxFrames, u32* status, u8* walkWs, hipStream_t stream);
+// pinned (null: none): the context's pinned copy of the status words, which walk_link fills with the words it writes
+void launch_frame_walk_count(const u8* src, u64 srcSize, u32 maxFrames, u32* status, u8* walkWs, hipStream_t stream, u32* pinned = nullptr);
 void launch_frame_walk_emit(const u8* src, u64 srcSize, FrameDesc* frames, BlockDesc* blocks, u8* walkWs, hipStream_t stream);
 void launch_frame_walk_serial(const u8* src, u64 srcSize, FrameDesc* frames, BlockDesc* blocks, u32 maxFrames, u32* status, const DecodeDict& dd, u32 emit, hipStream_t stream);
 // open: ZSTDMI_DCtx_setBatchUnsized; caps: batch_scan's instance that holds the entries to the limits in the status words
@@ -211,8 +220,10 @@ void launch_ranges_plan_d(const u8* tab, u32 n, u32 stride, const RangesWs& ws, 
 void launch_seq_stats(const Seq* seqs, const u8* lits, const ChunkMeta* meta, u32 nChunks, const u8* src, u32 chunkBytes, u32* stats, hipStream_t stream);
 void launch_dict_parse(const u8* dict, u32 dictSize, DictInfo* out, hipStream_t stream);
 void launch_dict_ctables(const u8* dict, u32 dictSize, const DictInfo* info, DictCTables* out, hipStream_t stream);
+// seqPlane: nBlocks u32 (16-byte aligned, room for a multiple of four), what block_parse and block_link leave for seq_scan to sum;
+// pinned (null: none): the context's pinned copy of the status words, which seq_scan fills as the last kernel of the pre-pass
 void launch_block_prepass(const u8* src, FrameDesc* frames, BlockDesc* blocks, u32 nFrames, u32 nBlocks, const DecodeDict& dd, u32 earlyLiterals, u32* status, hipStream_t stream,
-                          u32 phantoms = 0, bool open = false);     // phantoms, open: decode_walk.hip block_link_body
+                          u32* seqPlane, u32* pinned, u32 phantoms = 0, bool open = false);     // phantoms, open: decode_walk.hip block_link_body
 // (dd.seqTabs not null: the kernel's instance that copies a DDict's ready-made tables where a block repeats the dictionary's)
 // far (here, in launch_exec_matches and in launch_origin_init; null: none): the far plane of a call with a far-capable frame, one u32 per
 // sequence record (kRecFar, zmi_common.h); the launcher then starts the stage's far instance
@@ -223,7 +234,9 @@ void launch_seq_decode(const u8* src, const FrameDesc* frames, BlockDesc* blocks
 constexpr u32 kDictTabLogs = 1280, kDictTabWords = 1284;
 void launch_dict_seq_tables(const u8* dictFull, const DictInfo* di, u32* tabs, hipStream_t stream);
 // reps: the repcodes a frame starts from (dd.dinfo, or a segmented stream's carried triple)
-void launch_block_offsets(FrameDesc* frames, BlockDesc* blocks, u32 nFrames, const DecodeDict& dd, const DictInfo* reps, u32 rescan, u64 dstCapacity, u32* status, hipStream_t stream,
+// sizePlane (null: no rescan; never with open): a call with frames without a content size — nFrames u64 (16-byte aligned, room for a multiple
+// of four) that block_offsets fills with the frames' regenerated sizes and frame_rescan, launched behind it, sums into their places
+void launch_block_offsets(FrameDesc* frames, BlockDesc* blocks, u32 nFrames, const DecodeDict& dd, const DictInfo* reps, u64* sizePlane, u64 dstCapacity, u32* status, hipStream_t stream,
                           bool open = false);
 void launch_decode_literals(const u8* src, u8* out, u8* scratch, const FrameDesc* frames, const BlockDesc* blocks, u32 nBlocks, u32* status,
                             u8* slowFlags, u32 mode, const DecodeDict& dd, hipStream_t stream, StageHook hook);
@@ -292,6 +305,24 @@ struct DevBuf {
         cap = want; return true;
     }
     void release() { drop(); }
+};
+
+// A context's small block of pinned, device-visible host memory: what the host wants of a call — the decoder's status words, the
+// compressor's per-pass total and mark offsets — is stored there by a kernel of the call's stream (ordinary vector stores) and read
+// behind the call's stream_wait, so that no copy from or to pageable memory, with the staging kernel and the wait of its own that the
+// runtime puts behind one, stands in a call.  Made once, at the context's first call that reads it (counted as an allocation), never grown.
+struct PinBuf {
+    void* p = nullptr;
+    HostTally* owner = nullptr;
+    bool ensure(size_t n)
+    {
+        if (p) return true;
+        if (owner) owner->allocs++;
+        if (hipHostMalloc(&p, n, hipHostMallocPortable | hipHostMallocMapped) != hipSuccess) { (void)hipGetLastError(); p = nullptr; return false; }
+        memset(p, 0, n);
+        return true;
+    }
+    void release() { if (p) (void)hipHostFree(p); p = nullptr; }
 };
 
 struct StageTimer {

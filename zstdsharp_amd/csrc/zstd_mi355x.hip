@@ -35,6 +35,7 @@ struct ZSTD_CCtx_s {
     int device = 0; bool deviceOk = false;
     hipStream_t ownStream = nullptr, stream = nullptr;
     DevBuf seqs, lits, meta, tables, slots, offsets, total, cand, probe, stageSrc, stageDst;
+    PinBuf pin;                 // what the host reads of a pass: its total and mark offsets (compress_range; launch_scan_sizes)
     DevBuf ldmSmall, ldmBig;    // long-distance matching's workspace (allocated by the first call that runs it)
     LdmRecord ldmRec; u32 ldmRecBase = 0, ldmRecVlo = 0; bool ldmRecOk = false;     // the last pass's stage (ZSTDMI_debugLdmPass)
     bool ldmSkipMerge = false;  // ZSTDMI_debugLdmSkipMerge
@@ -180,6 +181,7 @@ ZSTD_CCtx_s::ZSTD_CCtx_s()
     for (DevBuf* b : { &seqs, &lits, &meta, &tables, &slots, &offsets, &total, &cand, &probe, &stageSrc, &stageDst, &ldmSmall, &ldmBig, &dixDist, &gatherIn, &gatherOut,
                        &batchStage, &batchTab, &packArena, &packTab, &packAsync, &seekEntries, &seekSort, &pfxStage, &sfXxh, &sWin, &cutSmall, &cutList, &cutEnds,
                        &own.dict, &own.dictFullDev, &own.dictInfoDev, &own.dictCTabDev, &own.dictWideDev, &own.dictIdxDev }) b->owner = &tally;
+    pin.owner = &tally;
 }
 
 // The parameters one compression call runs with: the context's sticky ones (ZSTD_compress2, ZSTD_compressStream2) or, for
@@ -743,7 +745,19 @@ static size_t compress_range(ZSTD_CCtx* c, const CallParams& cp, u8* d_dst, size
         SeqCarry sc = { tables, nullptr, 0, rs.rawLiterals };
         if (carry) { sc.nGroups = fr.single ? carry_groups_single(nChunks, frames.at, chunkBytes) : carry_groups_arith(nChunks, frameBlocks); c->lastCarryGroups += sc.nGroups; }
         launch_seq_encode(seqs, meta, slots, nChunks, ls.strategy, ls.header, 1, ls.initReps, frames, s, dct, nullptr, nullptr, carry ? &sc : nullptr);   c->timer.mark("seq_encode", s);
-        launch_scan_sizes(meta, nChunks, offsets, total, s);                       c->timer.mark("scan", s);
+        // What the host wants of the pass — its total, and the output offsets of the chunks that start at the marked inputs — is stored
+        // in the context's pinned block by the scan itself (markIdx: which of markAt fall into this pass, at most kPassMarks of them; a
+        // pass with more marks reads them back one by one as it always did)
+        PassMarks pm; size_t markIdx[kPassMarks]; bool marksPinned = true;
+        if (markAt) for (size_t i = 0; i < markAt->size(); ++i) {
+            const u64 ck = (*markAt)[i] / chunkBytes;
+            if (ck < c0 || ck >= c0 + nChunks) continue;
+            if (pm.n == kPassMarks) { marksPinned = false; pm.n = 0; break; }
+            markIdx[pm.n] = i; pm.chunk[pm.n++] = (u32)(ck - c0);
+        }
+        if (!c->pin.ensure(kPassPinWords * sizeof(u64))) return ZERR(kErrMemoryAllocation);
+        u64* const pinned = (u64*)c->pin.p;
+        launch_scan_sizes(meta, nChunks, offsets, total, s, pinned, pm);           c->timer.mark("scan", s);
         if (c->seekOn) {        // the pass's frames into the call's seek table
             const u32 nFrames = (nChunks + (frameBlocks ? frameBlocks : 1u) - 1) / (frameBlocks ? frameBlocks : 1u);
             if (((size_t)c->seekCount + nFrames) * 8 > c->seekEntries.cap) return ZERR(kErrGeneric);
@@ -754,13 +768,13 @@ static size_t compress_range(ZSTD_CCtx* c, const CallParams& cp, u8* d_dst, size
         // the literals section (most of the output) is encoded straight into its final place; gather moves the rest
         launch_huf_encode(lits, meta, tables, slots, d_dst + produced, offsets, room, nChunks, src, chunkBytes, s, dct != nullptr || carry);   c->timer.mark("huf_encode", s);
         launch_gather(src, n, slots, meta, offsets, d_dst + produced, room, nChunks, chunkBytes, s);      c->timer.mark("gather", s);
-        u64 passTotal = 0;
-        if (hipMemcpyAsync(&passTotal, total, sizeof(u64), hipMemcpyDeviceToHost, s) != hipSuccess) return ZERR(kErrGeneric);
-        if (markAt) for (size_t i = 0; i < markAt->size(); ++i) {           // output offsets of the chunks that start at the marked inputs
+        if (markAt && !marksPinned) for (size_t i = 0; i < markAt->size(); ++i) {
             const u64 ck = (*markAt)[i] / chunkBytes;
             if (ck >= c0 && ck < c0 + nChunks && hipMemcpyAsync(&(*marks)[i], offsets + (ck - c0), sizeof(u64), hipMemcpyDeviceToHost, s) != hipSuccess) return ZERR(kErrGeneric);
         }
         if (isErr(stream_wait(s))) return ZERR(kErrGeneric);
+        const u64 passTotal = pinned[0];
+        for (u32 k = 0; k < pm.n; ++k) (*marks)[markIdx[k]] = pinned[1 + k];
         if (markAt) for (size_t i = 0; i < markAt->size(); ++i) { const u64 ck = (*markAt)[i] / chunkBytes; if (ck >= c0 && ck < c0 + nChunks) (*marks)[i] += produced; }
         add_stage_times(c, first);
         if (passTotal > room) return ZERR(kErrDstSizeTooSmall);
@@ -1011,7 +1025,7 @@ size_t ZSTD_freeCCtx(ZSTD_CCtx* c)
         if (c->asyncEv) (void)hipEventDestroy(c->asyncEv);
         if (c->ownStream) (void)hipStreamSynchronize(c->ownStream);
         c->seqs.release(); c->lits.release(); c->meta.release(); c->tables.release(); c->slots.release(); c->cand.release(); c->lastRegionList = nullptr; c->dixDist.release(); c->probe.release();
-        c->gatherIn.release(); c->gatherOut.release(); c->batchStage.release(); c->batchTab.release(); c->packArena.release(); c->packTab.release(); c->packAsync.release(); c->ldmSmall.release(); c->ldmBig.release(); c->offsets.release(); c->total.release(); c->seekEntries.release(); c->seekSort.release(); c->stageSrc.release(); c->stageDst.release(); c->pfxStage.release(); c->sfXxh.release(); c->sWin.release(); c->cutSmall.release(); c->cutList.release(); c->cutEnds.release(); c->own.release();
+        c->gatherIn.release(); c->gatherOut.release(); c->batchStage.release(); c->batchTab.release(); c->packArena.release(); c->packTab.release(); c->packAsync.release(); c->ldmSmall.release(); c->ldmBig.release(); c->offsets.release(); c->total.release(); c->seekEntries.release(); c->seekSort.release(); c->stageSrc.release(); c->stageDst.release(); c->pfxStage.release(); c->sfXxh.release(); c->sWin.release(); c->cutSmall.release(); c->cutList.release(); c->cutEnds.release(); c->own.release(); c->pin.release();
         c->timer.destroy();
         if (c->ownStream) (void)hipStreamDestroy(c->ownStream);
     }

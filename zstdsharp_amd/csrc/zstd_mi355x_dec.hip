@@ -18,6 +18,9 @@ struct ZSTD_DCtx_s {
     bool lastWalkSerial = false; // the last call's frames were listed by the serial walk (ZSTDMI_debugLastWalkSerial)
     int execWaves = 0;          // ZSTDMI_DCtx_setExecWaves: waves per frame in exec_matches, 0 = by the number of frames
     DevBuf frames, blocks, recs, status, scratch, walkWs, slowFlags, stageSrc, stageDst, origin, originList;
+    PinBuf pin;                 // the status words as the host reads them (status_read)
+    DevBuf seqPlane;            // one u32 per block: the sequences it files records for (block_prepass writes it, seq_scan sums it)
+    DevBuf sizePlane;           // one u64 per frame, only in a call with frames without a content size: their regenerated sizes (block_offsets writes it, frame_rescan sums it)
     DevBuf farPlane;            // one u32 per sequence record, only in a call with a far-capable frame (kRecFar, zmi_common.h; decompress_device)
     int lastFarPlane = 0;       // the last decompress_device run had one (ZSTDMI_debugLastFarPlane)
     DevBuf batchIn, batchOut, blockKeys;    // ZSTDMI_decompressBatch: the entries' table, what the batch walk made of them, one error key per block
@@ -113,7 +116,8 @@ ZSTD_DCtx_s::ZSTD_DCtx_s()
     tally.self = this; tally.beforeFree = [](void* self) { dctx_async_drain((ZSTD_DCtx_s*)self); };
     for (DevBuf* b : { &frames, &blocks, &recs, &status, &scratch, &walkWs, &slowFlags, &stageSrc, &stageDst, &origin, &originList, &farPlane, &batchIn, &batchOut, &blockKeys, &litRooms,
                        &seekTab, &seekSum, &edge, &rangesWs, &rangesIn, &rangesRec, &rangesRes, &arena, &hist[0], &hist[1], &segReps, &segXxh, &dict, &dictInfoDev, &slotTab,
-                       &pfxStage, &asyncVerdict, &rangesAsyncWs }) b->owner = &tally;
+                       &pfxStage, &asyncVerdict, &rangesAsyncWs, &seqPlane, &sizePlane }) b->owner = &tally;
+    pin.owner = &tally;
 }
 // The lifetime rule of an enqueued batch (ZSTDMI_decompressBatchAsync), in one place: wait for the event behind the last enqueued call.
 // Called by every DevBuf of the context before it frees (HostTally::beforeFree: growth and release alike), by ZSTD_freeDCtx, by
@@ -177,7 +181,7 @@ size_t ZSTD_freeDCtx(ZSTD_DCtx* d)
         d->asyncVerdict.release(); d->rangesAsyncWs.release();
         if (d->ownStream) (void)hipStreamSynchronize(d->ownStream);
         d->frames.release(); d->blocks.release(); d->recs.release(); d->status.release(); d->scratch.release(); d->walkWs.release(); d->slowFlags.release(); d->stageSrc.release(); d->stageDst.release(); d->dict.release(); d->dictInfoDev.release(); d->origin.release(); d->originList.release(); d->farPlane.release(); d->batchIn.release(); d->batchOut.release(); d->blockKeys.release(); d->litRooms.release(); d->seekTab.release(); d->seekSum.release(); d->edge.release(); d->pfxStage.release(); d->rangesWs.release(); d->rangesIn.release(); d->rangesRec.release(); d->rangesRes.release(); d->arena.release(); d->slotTab.release();
-        d->hist[0].release(); d->hist[1].release(); d->segReps.release(); d->segXxh.release();
+        d->hist[0].release(); d->hist[1].release(); d->segReps.release(); d->segXxh.release(); d->seqPlane.release(); d->sizePlane.release(); d->pin.release();
         d->timer.destroy();
         if (d->aux) { (void)hipStreamSynchronize(d->aux); (void)hipStreamDestroy(d->aux); }
         if (d->auxDone) (void)hipEventDestroy(d->auxDone);
@@ -426,15 +430,28 @@ static size_t call_dict(ZSTD_DCtx* d, DecodeDict& dd)
     return dctx_sync_slots(d, dd);
 }
 
-// the status words (d->status, kSt*): error key = "none" (all ones), everything else zero
+// the status words (d->status, kSt*): error key = "none" (all ones), everything else zero — stores of a one-wave kernel, no upload
 static size_t status_reset(ZSTD_DCtx* d)
 {
-    // (static: the source of an asynchronous copy outlives this function)
-    static const struct Init { u32 w[kStWords] = {}; Init() { w[kStErrKeyLo] = w[kStErrKeyHi] = 0xFFFFFFFFu; } } init;
-    if (hipMemcpyAsync(d->status.p, init.w, sizeof init.w, hipMemcpyHostToDevice, d->stream) != hipSuccess) return ZERR(kErrGeneric);
+    launch_status_reset((u32*)d->status.p, d->stream);
     return 0;
 }
-static size_t status_read(ZSTD_DCtx* d, u32* st) { return dev_read(st, d->status.p, kStWords * sizeof(u32), d->stream); }
+// The host's view of the status words: d->pin (PinBuf, zmi_host.h), kStWords words that a kernel of the call's stream fills — the
+// mirror kernel, or a single-workgroup stage that is the last to write the words the host wants next (walk_link, seq_scan: they get
+// the block as an argument) — and that the host copies out behind its wait.  status_wait: the wait and the copy alone.
+static bool status_pin(ZSTD_DCtx* d) { return d->pin.ensure(kStWords * sizeof(u32)); }
+static size_t status_wait(ZSTD_DCtx* d, u32* st)
+{
+    const size_t e = stream_wait(d->stream); if (isErr(e)) return e;
+    memcpy(st, d->pin.p, kStWords * sizeof(u32));
+    return 0;
+}
+static size_t status_read(ZSTD_DCtx* d, u32* st)
+{
+    if (!status_pin(d)) return ZERR(kErrMemoryAllocation);
+    launch_status_mirror((const u32*)d->status.p, (u32*)d->pin.p, d->stream);
+    return status_wait(d, st);
+}
 static u64 st_u64(const u32* st, u32 lo, u32 hi) { return (u64)st[lo] | ((u64)st[hi] << 32); }
 
 // how a run ended (0: well): the first failing block's first error, then the run's own (unsized frames regenerated more than the destination holds)
@@ -490,8 +507,10 @@ static size_t decode_lists(ZSTD_DCtx* d, const DecodeDict& dd, u8* d_dst, const 
     // frame_rescan, a dstOff computed from the bound in front of it, and block_link (which knows a frame's header, not its
     // neighbours) would let its first block be written there.  (A batch marks such frames itself: kFrameOpen.)
     const bool early = !(nUnsized && nFrames > 1) && (d->overlapMode == 2 || (d->overlapMode == 0 && nBlocks <= kOverlapBlocks));
-    launch_block_prepass(d_src, frames, blocks, nFrames, nBlocks, dd, early ? 1u : 0u, status, s, link ? link->phantoms : 0u, open != nullptr);
-    { const size_t e = status_read(d, st); if (isErr(e)) return e; }
+    if (!d->seqPlane.ensure((size_t)nBlocks * sizeof(u32) + 64) || !status_pin(d)) return ZERR(kErrMemoryAllocation);
+    if (nUnsized && !d->sizePlane.ensure((size_t)nFrames * sizeof(u64) + 64)) return ZERR(kErrMemoryAllocation);
+    launch_block_prepass(d_src, frames, blocks, nFrames, nBlocks, dd, early ? 1u : 0u, status, s, (u32*)d->seqPlane.p, (u32*)d->pin.p, link ? link->phantoms : 0u, open != nullptr);
+    { const size_t e = status_wait(d, st); if (isErr(e)) return e; }       // (seq_scan has filed the status words in the pinned block itself)
     d->timer.mark("block_prepass", s);
     const u64 nSeq = st_u64(st, kStSeqLo, kStSeqHi);
     if (!d->recs.ensure((size_t)(nSeq + 64) * sizeof(SeqRec))) return ZERR(kErrMemoryAllocation);
@@ -541,7 +560,7 @@ static size_t decode_lists(ZSTD_DCtx* d, const DecodeDict& dd, u8* d_dst, const 
         auxGuard.on = true;
     }
     launch_seq_decode(d_src, frames, blocks, nBlocks, recs, status, dd, s, farPlane);     d->timer.mark("seq_decode", s);
-    launch_block_offsets(frames, blocks, nFrames, dd, link && link->reps ? link->reps : dd.dinfo, nUnsized ? 1u : 0u, dstCapacity, status, s, open != nullptr);  d->timer.mark("block_offsets", s);
+    launch_block_offsets(frames, blocks, nFrames, dd, link && link->reps ? link->reps : dd.dinfo, nUnsized ? (u64*)d->sizePlane.p : nullptr, dstCapacity, status, s, open != nullptr);  d->timer.mark("block_offsets", s);
     if (open) { launch_batch_rescan(open->in, open->out, open->n, frames, s); d->timer.mark("batch_rescan", s); }
     if (auxGuard.on) { if (hipStreamWaitEvent(s, d->auxDone, 0) != hipSuccess) return ZERR(kErrGeneric); d->timer.mark("decode_literals", s); }     // (what of it seq_decode did not cover)
     else launch_decode_literals(d_src, d_dst, (u8*)d->scratch.p, frames, blocks, nBlocks, status, (u8*)d->slowFlags.p, d->litDecoder, dd, s, d->timer.hook());
@@ -571,7 +590,9 @@ static size_t decode_lists(ZSTD_DCtx* d, const DecodeDict& dd, u8* d_dst, const 
 }
 
 // The decompress pipeline over device-resident buffers.  Two host round trips size the work lists (frames + blocks after the
-// counting walk, sequence records after the block pre-pass); everything else is one launch sequence:
+// counting walk, sequence records after the block pre-pass); everything else is one launch sequence.  A round trip is a wait and a read
+// of the context's pinned block (status_wait): walk_link and seq_scan, the kernels in front of the two waits, file the status words
+// there themselves, and the mirror kernel does at the end of the call — no copy between device and pageable memory stands in a call.
 //   walk (count) | walk (emit) -> block_parse -> block_link -> seq_scan | seq_decode -> block_offsets [-> frame_rescan]
 //   -> decode_literals -> place_literals -> exec_matches
 // allowFar = false (an entry that a batch, range or ranges call left to this path): offsets above kRecOffMax keep the refusal those calls state
@@ -589,8 +610,9 @@ static size_t decompress_device(ZSTD_DCtx* d, u8* d_dst, size_t dstCapacity, con
     d->timer.begin(s);
     { const size_t e = status_reset(d); if (isErr(e)) return e; }
     u32 st[kStWords] = {};
-    launch_frame_walk_count(d_src, srcSize, maxFrames, status, (u8*)d->walkWs.p, s);
-    { const size_t e = status_read(d, st); if (isErr(e)) return e; }
+    if (!status_pin(d)) return ZERR(kErrMemoryAllocation);
+    launch_frame_walk_count(d_src, srcSize, maxFrames, status, (u8*)d->walkWs.p, s, (u32*)d->pin.p);
+    { const size_t e = status_wait(d, st); if (isErr(e)) return e; }      // (walk_link has filed its words in the pinned block itself)
     const bool serialWalk = !st[kStUsable];
     d->lastWalkSerial = serialWalk;
     // (the parallel walk lists only frames that name no dictionary: all of them are the current DDict's, the single-dictionary kernels' case)
