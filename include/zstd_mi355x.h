@@ -701,6 +701,43 @@ size_t ZSTDMI_contentCuts(ZSTD_CCtx* cctx, const void* d_src, size_t srcSize, un
                           size_t* pieceSizes, size_t capacity, size_t* nPieces);
 long long ZSTDMI_debugLastContentCuts(const ZSTD_CCtx* cctx);
 
+/* Piece digests: the step between cutting a device-resident buffer and compressing the pieces a store does not hold yet — the key of
+ * every piece, computed where the bytes are.  Two kinds: XXH64 (seed 0), the function of zstd's own frame checksum, as a cheap filter
+ * key; SHA-256 (FIPS 180-4), what content-addressed stores key on, as the identity.
+ * ZSTDMI_digestSize(kind): 8 for ZSTDMI_digest_xxh64, 32 for ZSTDMI_digest_sha256, 0 for any other kind; touches no device.
+ * ZSTDMI_digestPieces.  Piece i is the pieceSizes[i] bytes behind piece i - 1, the first at src.  The sizes' sum may be smaller than
+ * srcSize (the frames of a pack without its seek table), never larger; a piece may be empty or as long as the buffer.  src is device
+ * memory (host memory is staged, as ZSTDMI_contentCuts stages it) and may be larger than 4 GiB; pieceSizes and digests are HOST arrays.
+ * digests receives nPieces * ZSTDMI_digestSize(kind) bytes, piece after piece: XXH64 as the 8 bytes of the value in little-endian order
+ * — its first four bytes are exactly the checksum field zstd writes behind a frame of that content —, SHA-256 as the 32 bytes of
+ * FIPS 180-4 (hashlib.sha256(piece).digest()).
+ * Answers, in this order, all but the last two before a device is looked for: NULL context: GENERIC; NULL pieceSizes or NULL digests
+ * with nPieces > 0: GENERIC; a kind other than 1 or 2: parameter_outOfBound; nPieces == 0: 0, nothing touched;
+ * digestsCapacity < nPieces * size: dstSize_tooSmall, nothing written; a sum of sizes that overflows or exceeds srcSize: srcSize_wrong;
+ * NULL src with srcSize > 0: srcSize_wrong; several device workers (or 2^31 pieces and more): parameter_unsupported; then init_missing /
+ * memory_allocation as elsewhere, then 0.
+ * ZSTDMI_contentCutsDigests is ZSTDMI_contentCuts(cctx, src, srcSize, avgLog, ...) — its pieces, argument checks and answers — plus the
+ * digest of every piece: parameter_outOfBound for the kind comes right behind the one for avgLog; *nPieces is set also when capacity or
+ * digestsCapacity is too small, which answers dstSize_tooSmall and writes neither array.  The piece ends never leave the device between
+ * the selection and the digest kernel, and the call makes exactly the host waits ZSTDMI_contentCuts makes on the same input.
+ * Both calls use the context for its device, stream, workspaces and stage timer only (the digest stage is named digest_xxh64 /
+ * digest_sha256 under ZSTDMI_CCtx_setProfiling): they consult and change no sticky parameter, dictionary, CDict reference or
+ * content-cuts switch, neither consume nor refuse a pending ZSTD_CCtx_refPrefix, leave a valid ZSTDMI_CCtx_prepareBatchAsync valid and
+ * ZSTDMI_debugLastContentCuts as it was.
+ * Both functions are serial inside a piece: the call is fast for many pieces and a serial chain for one long piece (README "Piece digests").
+ * ZSTDMI_debugDigestModel: one digest of host memory on the CPU, by the same text the kernels run (zmi_digest.h); no device;
+ * parameter_outOfBound for a bad kind, GENERIC for a NULL digest or a NULL src with a size.
+ * Out of scope: device-array outputs and an enqueued form, other kinds and keyed hashes, digests computed inside the compress calls. */
+enum { ZSTDMI_digest_xxh64 = 1, ZSTDMI_digest_sha256 = 2 };
+size_t ZSTDMI_digestSize(unsigned kind);
+size_t ZSTDMI_digestPieces(ZSTD_CCtx* cctx, const void* src, size_t srcSize,
+                           const size_t* pieceSizes, size_t nPieces, unsigned kind,
+                           void* digests, size_t digestsCapacity);
+size_t ZSTDMI_contentCutsDigests(ZSTD_CCtx* cctx, const void* src, size_t srcSize, unsigned avgLog, unsigned kind,
+                                 size_t* pieceSizes, size_t capacity, size_t* nPieces,
+                                 void* digests, size_t digestsCapacity);
+size_t ZSTDMI_debugDigestModel(unsigned kind, const void* src, size_t srcSize, void* digest);
+
 /* Seekable streams (the zstd seekable format, v0.1.0): random access at the granularity of the frame.
  * Every stream this library writes is a run of independent frames (64 KiB of content at levels 1-2, 240-256 KiB at levels >= 3, 32 KiB
  * or less behind a dictionary, one window under long-distance matching; ZSTDMI_CCtx_setHistory and ZSTD_c_windowLog change it).

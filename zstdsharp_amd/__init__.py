@@ -5,7 +5,7 @@ ThrowHelper.cs): same member names in snake_case next to the original PascalCase
 error behaviour, over the C ABI in include/zstd_mi355x.h.
 """
 from .errors import ZstdException, ZSTD_ErrorCode
-from .compressor import Compressor, content_cuts
+from .compressor import Compressor, content_cuts, content_cuts_digests, piece_digests
 from .decompressor import Decompressor
 from .dictbuilder import DictBuilder
 from .decompressor import ZSTD_d_windowLogMax, ZSTD_d_refMultipleDDicts, ZSTD_rmd_refSingleDDict, ZSTD_rmd_refMultipleDDicts
@@ -15,4 +15,4 @@ from .batch import compress_batch, compress_batch_async, compress_pack, compress
 from .seekable import read_seek_table
 from .streams import CompressionStream, DecompressionStream, EndOfStreamException
 
-__all__ = ["Compressor", "Decompressor", "ZSTD_d_windowLogMax", "ZSTD_d_refMultipleDDicts", "ZSTD_rmd_refSingleDDict", "ZSTD_rmd_refMultipleDDicts", "DictBuilder", "CDict", "DDict", "get_dict_id_from_dict", "get_dict_id_from_frame", "CompressionStream", "DecompressionStream", "EndOfStreamException", "ZstdException", "ZSTD_ErrorCode", "compress_batch", "compress_batch_async", "compress_pack", "compress_pack_async", "decompress_batch", "decompress_batch_async", "decompress_ranges_async", "pack_ranges", "read_seek_table", "content_cuts", "_ffi"]
+__all__ = ["Compressor", "Decompressor", "ZSTD_d_windowLogMax", "ZSTD_d_refMultipleDDicts", "ZSTD_rmd_refSingleDDict", "ZSTD_rmd_refMultipleDDicts", "DictBuilder", "CDict", "DDict", "get_dict_id_from_dict", "get_dict_id_from_frame", "CompressionStream", "DecompressionStream", "EndOfStreamException", "ZstdException", "ZSTD_ErrorCode", "compress_batch", "compress_batch_async", "compress_pack", "compress_pack_async", "decompress_batch", "decompress_batch_async", "decompress_ranges_async", "pack_ranges", "read_seek_table", "content_cuts", "content_cuts_digests", "piece_digests", "_ffi"]

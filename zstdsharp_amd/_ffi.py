@@ -163,6 +163,11 @@ SIGNATURES = {
     "ZSTDMI_contentCutsBound": (c_size_t, [c_size_t, c_uint]),
     "ZSTDMI_contentCuts": (c_size_t, [c_void_p, c_void_p, c_size_t, c_uint, ctypes.POINTER(c_size_t), c_size_t, ctypes.POINTER(c_size_t)]),
     "ZSTDMI_debugLastContentCuts": (ctypes.c_longlong, [c_void_p]),
+    "ZSTDMI_digestSize": (c_size_t, [c_uint]),
+    "ZSTDMI_digestPieces": (c_size_t, [c_void_p, c_void_p, c_size_t, ctypes.POINTER(c_size_t), c_size_t, c_uint, c_void_p, c_size_t]),
+    "ZSTDMI_contentCutsDigests": (c_size_t, [c_void_p, c_void_p, c_size_t, c_uint, c_uint, ctypes.POINTER(c_size_t), c_size_t, ctypes.POINTER(c_size_t),
+                                             c_void_p, c_size_t]),
+    "ZSTDMI_debugDigestModel": (c_size_t, [c_uint, c_void_p, c_size_t, c_void_p]),
     "ZSTDMI_CCtx_setSeekTable": (c_size_t, [c_void_p, c_uint]),
     "ZSTDMI_CCtx_setDictEntropy": (c_size_t, [c_void_p, c_uint]),
     "ZSTDMI_CCtx_setEntropyCarry": (c_size_t, [c_void_p, c_uint]),

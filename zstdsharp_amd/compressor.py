@@ -375,22 +375,75 @@ class Compressor(_PrefixHolder):
             pass
 
 
+def _as_source(data):
+    """bytes-like or a contiguous CUDA uint8 tensor (what torch has queued for it finished) -> (address, length, keepalive)"""
+    if hasattr(data, "data_ptr"):
+        import torch
+        if not (data.is_cuda and data.dtype == torch.uint8 and data.is_contiguous()):
+            raise TypeError("expected a contiguous CUDA uint8 tensor")
+        torch.cuda.synchronize(data.device)
+        return (data.data_ptr() if data.numel() else None), data.numel(), data
+    return _as_buffer(data)
+
+
 def content_cuts(compressor, data, avg_log: int):
     """ZSTDMI_contentCuts: the chunker alone -> the list of piece sizes the cut rule (include/zstd_mi355x.h "Content-defined cuts") gives
     `data` (bytes-like, or a contiguous CUDA uint8 tensor) at avg_log, in order; their sum is len(data).  The compressor lends its
     device and stream; its content_cuts switch is not consulted."""
     compressor._ensure_not_disposed()
     lib = compressor._lib
-    if hasattr(data, "data_ptr"):
-        import torch
-        if not (data.is_cuda and data.dtype == torch.uint8 and data.is_contiguous()):
-            raise TypeError("expected a contiguous CUDA uint8 tensor")
-        torch.cuda.synchronize(data.device)
-        addr, n, keep = (data.data_ptr() if data.numel() else None), data.numel(), data
-    else:
-        addr, n, keep = _as_buffer(data)
+    addr, n, keep = _as_source(data)
     cap = n // 1024 + 1         # (min is 1 KiB or more: never fewer entries than pieces)
     sizes = (ctypes.c_size_t * cap)()
     got = ctypes.c_size_t(0)
     ensure_zstd_success(lib, lib.ZSTDMI_contentCuts(compressor.cctx, addr, n, int(avg_log), sizes, cap, ctypes.byref(got)))
     return list(sizes[:got.value])
+
+
+DIGEST_KINDS = {"xxh64": 1, "sha256": 2}
+
+
+def _digest_kind(kind) -> int:
+    if isinstance(kind, str):
+        if kind not in DIGEST_KINDS:
+            raise ValueError(f"digest kind {kind!r}: expected one of {sorted(DIGEST_KINDS)}")
+        return DIGEST_KINDS[kind]
+    return int(kind)
+
+
+def _split_digests(raw, count, each):
+    return [raw[i * each:(i + 1) * each] for i in range(count)]
+
+
+def piece_digests(compressor, data, sizes, kind="xxh64"):
+    """ZSTDMI_digestPieces: the digest of every piece of `data` (bytes-like, or a contiguous CUDA uint8 tensor) -> a list of bytes, one
+    per entry of `sizes`.  Piece i is the sizes[i] bytes behind piece i - 1; the sizes may add up to less than len(data), never to more.
+    kind: "xxh64" (8 bytes, the value little-endian: its first four are zstd's frame checksum field), "sha256" (32 bytes, as
+    hashlib.sha256(piece).digest()), or the ABI's integer.  The compressor lends its device and stream; none of its settings is
+    consulted or changed."""
+    compressor._ensure_not_disposed()
+    lib = compressor._lib
+    k = _digest_kind(kind)
+    each = lib.ZSTDMI_digestSize(k)
+    addr, n, keep = _as_source(data)
+    sizes = [int(x) for x in sizes]
+    arr = (ctypes.c_size_t * max(len(sizes), 1))(*sizes)
+    out = ctypes.create_string_buffer(max(len(sizes) * each, 1))
+    ensure_zstd_success(lib, lib.ZSTDMI_digestPieces(compressor.cctx, addr, n, arr, len(sizes), k, out, len(sizes) * each))
+    return _split_digests(out.raw, len(sizes), each)
+
+
+def content_cuts_digests(compressor, data, avg_log: int, kind="sha256"):
+    """ZSTDMI_contentCutsDigests: content_cuts(compressor, data, avg_log) and the digest of every piece in one call, with no host round
+    trip beyond the chunker's own -> (sizes, digests)."""
+    compressor._ensure_not_disposed()
+    lib = compressor._lib
+    k = _digest_kind(kind)
+    each = lib.ZSTDMI_digestSize(k)
+    addr, n, keep = _as_source(data)
+    cap = n // 1024 + 1         # (min is 1 KiB or more: never fewer entries than pieces)
+    sizes = (ctypes.c_size_t * cap)()
+    out = ctypes.create_string_buffer(max(cap * each, 1))
+    got = ctypes.c_size_t(0)
+    ensure_zstd_success(lib, lib.ZSTDMI_contentCutsDigests(compressor.cctx, addr, n, int(avg_log), k, sizes, cap, ctypes.byref(got), out, cap * each))
+    return list(sizes[:got.value]), _split_digests(out.raw, got.value, each)

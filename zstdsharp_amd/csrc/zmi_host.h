@@ -144,6 +144,11 @@ u32* cut_total_word(u8* small, u64 n);
 void launch_cut_count(const u8* src, u64 n, u32 bits, u8* small, hipStream_t stream);
 void launch_cut_emit(const u8* src, u64 n, u32 bits, u8* small, u32* cand, hipStream_t stream);
 void launch_cut_select(const u32* cand, u32 nCand, u64 n, const CutRule& rule, u32* out, u32 cap, hipStream_t stream);
+// piece digests (digest.hip; the functions: zmi_digest.h).  Where the pieces of [src, src + srcSize) lie: offs, n + 1 offsets from src
+// (device memory, ascending, the last at most srcSize), or — ends not null — launch_cut_select's output, of which the kernel takes the
+// count and the ends; n is then the most pieces there can be (the select's cap).  out: n digests side by side (device memory).
+struct DigestPieces { const u64* offs; const u32* ends; u64 n; u64 srcSize; };
+void launch_digest(unsigned kind, const u8* src, const DigestPieces& tab, u8* out, hipStream_t stream);
 // decoder (decode_walk.hip, decode_lit.hip, decode_seq.hip, decode_origin.hip)
 // The dictionary of a call as the stage launchers take it (the host's decode_dict, zstd_mi355x_dec.hip): formatted or raw content, the
 // whole dictionary and its parsed header (formatted only), the content that is history in front of every frame — a caller may put a

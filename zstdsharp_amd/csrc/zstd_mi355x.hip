@@ -7,6 +7,8 @@
 #include "zmi_cparams.h"
 #include "zmi_host.h"
 #include "zmi_carry.h"
+#include "zmi_digest.h"
+#include <memory>
 #include <unordered_map>
 
 // ======================================================================================================
@@ -122,6 +124,8 @@ struct ZSTD_CCtx_s {
     // output (content_cuts.hip); lastContentCuts: pieces of the last call that was cut (ZSTDMI_debugLastContentCuts)
     int contentCuts = 0; long long lastContentCuts = 0;
     DevBuf cutSmall, cutList, cutEnds;
+    // ZSTDMI_digestPieces / ZSTDMI_contentCutsDigests (digest.hip): the pieces' offsets and their digests on the device
+    DevBuf digOffs, digOut;
     struct AsyncPrep* asyncPrep = nullptr; hipEvent_t asyncEv = nullptr; bool asyncPending = false;
     ZSTD_CCtx_s();
 };
@@ -179,7 +183,7 @@ ZSTD_CCtx_s::ZSTD_CCtx_s()
 {
     tally.self = this; tally.beforeFree = [](void* self) { cctx_async_drain((ZSTD_CCtx_s*)self); };
     for (DevBuf* b : { &seqs, &lits, &meta, &tables, &slots, &offsets, &total, &cand, &probe, &stageSrc, &stageDst, &ldmSmall, &ldmBig, &dixDist, &gatherIn, &gatherOut,
-                       &batchStage, &batchTab, &packArena, &packTab, &packAsync, &seekEntries, &seekSort, &pfxStage, &sfXxh, &sWin, &cutSmall, &cutList, &cutEnds,
+                       &batchStage, &batchTab, &packArena, &packTab, &packAsync, &seekEntries, &seekSort, &pfxStage, &sfXxh, &sWin, &cutSmall, &cutList, &cutEnds, &digOffs, &digOut,
                        &own.dict, &own.dictFullDev, &own.dictInfoDev, &own.dictCTabDev, &own.dictWideDev, &own.dictIdxDev }) b->owner = &tally;
     pin.owner = &tally;
 }
@@ -1025,7 +1029,7 @@ size_t ZSTD_freeCCtx(ZSTD_CCtx* c)
         if (c->asyncEv) (void)hipEventDestroy(c->asyncEv);
         if (c->ownStream) (void)hipStreamSynchronize(c->ownStream);
         c->seqs.release(); c->lits.release(); c->meta.release(); c->tables.release(); c->slots.release(); c->cand.release(); c->lastRegionList = nullptr; c->dixDist.release(); c->probe.release();
-        c->gatherIn.release(); c->gatherOut.release(); c->batchStage.release(); c->batchTab.release(); c->packArena.release(); c->packTab.release(); c->packAsync.release(); c->ldmSmall.release(); c->ldmBig.release(); c->offsets.release(); c->total.release(); c->seekEntries.release(); c->seekSort.release(); c->stageSrc.release(); c->stageDst.release(); c->pfxStage.release(); c->sfXxh.release(); c->sWin.release(); c->cutSmall.release(); c->cutList.release(); c->cutEnds.release(); c->own.release(); c->pin.release();
+        c->gatherIn.release(); c->gatherOut.release(); c->batchStage.release(); c->batchTab.release(); c->packArena.release(); c->packTab.release(); c->packAsync.release(); c->ldmSmall.release(); c->ldmBig.release(); c->offsets.release(); c->total.release(); c->seekEntries.release(); c->seekSort.release(); c->stageSrc.release(); c->stageDst.release(); c->pfxStage.release(); c->sfXxh.release(); c->sWin.release(); c->cutSmall.release(); c->cutList.release(); c->cutEnds.release(); c->digOffs.release(); c->digOut.release(); c->own.release(); c->pin.release();
         c->timer.destroy();
         if (c->ownStream) (void)hipStreamDestroy(c->ownStream);
     }
@@ -2682,7 +2686,10 @@ extern "C" long long ZSTDMI_debugLastPackFrames(const ZSTD_CCtx* c) { return c ?
 // ---- content-defined cuts (ZSTDMI_CCtx_setContentCuts, include/zstd_mi355x.h; the rule: zmi_cuts.h) ----
 // The pieces of [d_src, d_src + n) by the rule -> their sizes in order.  Two host synchronisations: the candidates' count, which sizes
 // the list, and the select's output (the piece count and the ends, one copy sized by the most pieces the rule allows).
-static size_t content_cut_sizes(ZSTD_CCtx* c, const u8* d_src, size_t n, unsigned avgLog, std::vector<size_t>& sizes, PackStages& st)
+// dg (ZSTDMI_contentCutsDigests; null: none): the digest of every piece too — the kernel takes the ends where cut_select left them, over
+// a grid sized by the most pieces the rule allows, and its output rides behind the ends in front of the same wait.
+struct CutDigests { unsigned kind; std::unique_ptr<u8[]> bytes; };      // bytes: pieces x digest_size(kind), piece after piece
+static size_t content_cut_sizes(ZSTD_CCtx* c, const u8* d_src, size_t n, unsigned avgLog, std::vector<size_t>& sizes, PackStages& st, CutDigests* dg = nullptr)
 {
     sizes.clear();
     if (!n) return 0;
@@ -2700,11 +2707,18 @@ static size_t content_cut_sizes(ZSTD_CCtx* c, const u8* d_src, size_t n, unsigne
     // (a hostile input makes the list as long as the source: the call then fails here, the list is never thinned)
     const u64 P = cut_max_pieces(n, rule);
     if (!c->cutList.ensure((size_t)nCand * 4 + 64) || !c->cutEnds.ensure((size_t)(P + 1) * 4)) return ZERR(kErrMemoryAllocation);
+    const size_t dgBytes = dg ? (size_t)P * digest_size(dg->kind) : 0;
+    if (dg) { if (!c->digOut.ensure(dgBytes)) return ZERR(kErrMemoryAllocation); dg->bytes.reset(new u8[dgBytes]); }
     c->timer.begin(s);
     if (nCand) launch_cut_emit(d_src, n, rule.bits, small, (u32*)c->cutList.p, s);
     c->timer.mark("cut_mark", s);
     launch_cut_select((const u32*)c->cutList.p, nCand, n, rule, (u32*)c->cutEnds.p, (u32)P, s);
     c->timer.mark("cut_select", s);
+    if (dg) {
+        launch_digest(dg->kind, d_src, DigestPieces{ nullptr, (const u32*)c->cutEnds.p, P, n }, (u8*)c->digOut.p, s);
+        c->timer.mark(digest_stage_name(dg->kind), s);
+        if (hipMemcpyAsync(dg->bytes.get(), c->digOut.p, dgBytes, hipMemcpyDeviceToHost, s) != hipSuccess) return ZERR(kErrGeneric);
+    }
     std::vector<u32> ends((size_t)P + 1);
     if (isErr(dev_read(ends.data(), c->cutEnds.p, ends.size() * 4, s))) return ZERR(kErrGeneric);
     st.add_timer(c);
@@ -2764,22 +2778,57 @@ static size_t compress_cut(ZSTD_CCtx* c, const CallParams& cp0, void* dst, size_
     }
     return r;
 }
-static size_t content_cuts_impl(ZSTD_CCtx* c, const void* src, size_t srcSize, unsigned avgLog, size_t* pieceSizes, size_t capacity, size_t* nPieces)
+// kind 0: ZSTDMI_contentCuts; else ZSTDMI_contentCutsDigests, the same call with every piece's digest behind it
+static size_t content_cuts_impl(ZSTD_CCtx* c, const void* src, size_t srcSize, unsigned avgLog, size_t* pieceSizes, size_t capacity, size_t* nPieces,
+                                bool withDigests = false, unsigned kind = 0, void* digests = nullptr, size_t digestsCapacity = 0)
 {
-    if (!c || !nPieces || (capacity && !pieceSizes)) return ZERR(kErrGeneric);
+    if (!c || !nPieces || (capacity && !pieceSizes) || (withDigests && digestsCapacity && !digests)) return ZERR(kErrGeneric);
     *nPieces = 0;
     if (!cut_avglog_ok(avgLog)) return ZERR(kErrParameterOutOfBound);
+    if (withDigests && !digest_size(kind)) return ZERR(kErrParameterOutOfBound);
     if ((u64)srcSize > kCutMaxSrc) return ZERR(kErrParameterUnsupported);
     size_t e = cctx_bind(c); if (isErr(e)) return e;
     if (srcSize && !src) return ZERR(kErrSrcSizeWrong);
     const u8* d_src; e = cut_stage_src(c, src, srcSize, false, d_src); if (isErr(e)) return e;
     PackStages st;
     std::vector<size_t> sizes;
-    e = content_cut_sizes(c, d_src, srcSize, avgLog, sizes, st); if (isErr(e)) return e;
+    CutDigests dg{ kind, nullptr };
+    e = content_cut_sizes(c, d_src, srcSize, avgLog, sizes, st, withDigests ? &dg : nullptr); if (isErr(e)) return e;
     st.file(c);
     *nPieces = sizes.size();
-    if (sizes.size() > capacity) return ZERR(kErrDstSizeTooSmall);
+    const size_t dgBytes = sizes.size() * digest_size(kind);        // (at most srcSize / 1024 + 1 pieces of 32 bytes: no overflow)
+    if (sizes.size() > capacity || (withDigests && dgBytes > digestsCapacity)) return ZERR(kErrDstSizeTooSmall);
     for (size_t i = 0; i < sizes.size(); i++) pieceSizes[i] = sizes[i];
+    if (withDigests && dgBytes) memcpy(digests, dg.bytes.get(), dgBytes);
+    return 0;
+}
+// ZSTDMI_digestPieces: the answers in the header's order; the context lends its device, stream, workspaces and stage timer
+static size_t digest_pieces_impl(ZSTD_CCtx* c, const void* src, size_t srcSize, const size_t* pieceSizes, size_t nPieces, unsigned kind,
+                                 void* digests, size_t digestsCapacity)
+{
+    if (!c) return ZERR(kErrGeneric);
+    if (nPieces && (!pieceSizes || !digests)) return ZERR(kErrGeneric);
+    const size_t each = digest_size(kind);
+    if (!each) return ZERR(kErrParameterOutOfBound);
+    if (!nPieces) return 0;
+    size_t outBytes = 0;
+    if (__builtin_mul_overflow(nPieces, each, &outBytes) || outBytes > digestsCapacity) return ZERR(kErrDstSizeTooSmall);
+    { size_t sum = 0; for (size_t i = 0; i < nPieces; i++) if (__builtin_add_overflow(sum, pieceSizes[i], &sum) || sum > srcSize) return ZERR(kErrSrcSizeWrong); }
+    if (srcSize && !src) return ZERR(kErrSrcSizeWrong);
+    if (c->workers.size() > 1) return ZERR(kErrParameterUnsupported);
+    if ((u64)nPieces >= (1ull << 31)) return ZERR(kErrParameterUnsupported);       // (the grid's reach)
+    size_t e = cctx_bind(c); if (isErr(e)) return e;
+    const u8* d_src; e = cut_stage_src(c, src, srcSize, false, d_src); if (isErr(e)) return e;
+    std::vector<u64> offs(nPieces + 1);
+    { u64 at = 0; for (size_t i = 0; i < nPieces; i++) { offs[i] = at; at += pieceSizes[i]; } offs[nPieces] = at; }
+    hipStream_t s = c->stream;
+    if (!c->digOffs.ensure(offs.size() * sizeof(u64)) || !c->digOut.ensure(outBytes)) return ZERR(kErrMemoryAllocation);
+    if (hipMemcpyAsync(c->digOffs.p, offs.data(), offs.size() * sizeof(u64), hipMemcpyHostToDevice, s) != hipSuccess) return ZERR(kErrGeneric);
+    c->timer.begin(s);
+    launch_digest(kind, d_src, DigestPieces{ (const u64*)c->digOffs.p, nullptr, (u64)nPieces, (u64)srcSize }, (u8*)c->digOut.p, s);
+    c->timer.mark(digest_stage_name(kind), s);
+    if (isErr(dev_read(digests, c->digOut.p, outBytes, s))) return ZERR(kErrGeneric);
+    PackStages st; st.add_timer(c); st.file(c);
     return 0;
 }
 extern "C" size_t ZSTDMI_CCtx_setContentCuts(ZSTD_CCtx* c, unsigned avgLog)
@@ -2801,6 +2850,26 @@ extern "C" size_t ZSTDMI_contentCuts(ZSTD_CCtx* c, const void* d_src, size_t src
     return guarded([&] { return content_cuts_impl(c, d_src, srcSize, avgLog, pieceSizes, capacity, nPieces); });
 }
 extern "C" long long ZSTDMI_debugLastContentCuts(const ZSTD_CCtx* c) { return c ? c->lastContentCuts : -1; }
+
+// ---- piece digests (include/zstd_mi355x.h "Piece digests"; zmi_digest.h, digest.hip) ----
+extern "C" size_t ZSTDMI_digestSize(unsigned kind) { return digest_size(kind); }
+extern "C" size_t ZSTDMI_digestPieces(ZSTD_CCtx* c, const void* src, size_t srcSize, const size_t* pieceSizes, size_t nPieces, unsigned kind,
+                                      void* digests, size_t digestsCapacity)
+{
+    return guarded([&] { return digest_pieces_impl(c, src, srcSize, pieceSizes, nPieces, kind, digests, digestsCapacity); });
+}
+extern "C" size_t ZSTDMI_contentCutsDigests(ZSTD_CCtx* c, const void* src, size_t srcSize, unsigned avgLog, unsigned kind,
+                                            size_t* pieceSizes, size_t capacity, size_t* nPieces, void* digests, size_t digestsCapacity)
+{
+    return guarded([&] { return content_cuts_impl(c, src, srcSize, avgLog, pieceSizes, capacity, nPieces, true, kind, digests, digestsCapacity); });
+}
+extern "C" size_t ZSTDMI_debugDigestModel(unsigned kind, const void* src, size_t srcSize, void* digest)
+{
+    if (!digest_size(kind)) return ZERR(kErrParameterOutOfBound);
+    if (!digest || (srcSize && !src)) return ZERR(kErrGeneric);
+    (void)digest_serial(kind, (const u8*)src, srcSize, (u8*)digest);
+    return 0;
+}
 
 extern "C" size_t ZSTDMI_debugCompressSamples(ZSTD_CCtx* c, const void* src, const size_t* sizes, size_t n, size_t* outSizes)
 {
