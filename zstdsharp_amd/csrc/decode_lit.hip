@@ -12,6 +12,7 @@
 //   slow     : one wave per block, everything the others pass on (12-bit tables).
 #include "zmi_decode.h"
 #include "zmi_host.h"
+#include "zmi_lit_ahead.h"
 
 namespace zmi {
 
@@ -297,8 +298,27 @@ __device__ __forceinline__ bool huf_decode_stream_fs(const u32 tOff, const u32 n
         u64 lowHi = 0, lowLo = 0;
         auto load_low = [&]() {
             const s32 lp = ptr - 16;
+#ifdef ZMI_EXP_LIT_LOADFIX                   // ablation build (diagnostic, make variant DEFS=-DZMI_EXP_LIT_LOADFIX): every look-ahead
+            const u8* a = src; (void)lp;     // load reads the stream's first 16 bytes, a cache hit; same steps and stores, garbage symbols
+#else
             const u8* a = src + (lp > 0 ? lp : 0);
+#endif
             lowLo = readLE64(a); lowHi = readLE64(a + 8);
+        };
+        // Behind the eighth step's load_low of every second 64-symbol group: a 4-byte load ZMI_LIT_AHEAD bytes further down the
+        // stream, whose value nobody needs.  It brings that line into L2 before the exact loads get there, so that those hit (two
+        // groups move 92 bytes on average: nearly every 128-byte line is touched, once or twice; touching in every group, or only
+        // where the address enters a new line, measured slower: DESIGN 11).  A plain load, which the compiler counts in its vmcnt
+        // waits (a volatile one is waited for with vmcnt(0) right behind it).  The empty asm in front of the next touch is its only
+        // use: that keeps the load, and keeps its register claimed until then — a register free for reuse would be waited for in
+        // front of whatever reuses it.
+        u32 touched = 0;
+        auto touch = [&]() {
+#if defined(ZMI_LIT_AHEAD) && ZMI_LIT_AHEAD      // (zmi_lit_ahead.h; a build of this function without it — tests/host/lit_stream_harness.cpp — has no touch)
+            if (i & 64u) return;
+            asm volatile("" :: "v"(touched));
+            touched = *(const u32u*)(src + lit_touch_offset(ptr, (s32)srcSize, ZMI_LIT_AHEAD));
+#endif
         };
         auto fix_low = [&]() {           // bytes below the stream's start are zero (only the last steps of a stream get here)
             const s32 lp = ptr - 16;
@@ -348,6 +368,7 @@ __device__ __forceinline__ bool huf_decode_stream_fs(const u32 tOff, const u32 n
                 u32 d[16];
 #pragma unroll
                 for (u32 g = 0; g < 8; ++g) step(d[2 * g], d[2 * g + 1]);
+                touch();
                 // 4 x 4 transpose of 16-byte pieces over the quad's lanes: piece p of lane l <-> piece l of lane p
                 u32 b[16], c[16];
 #pragma unroll
@@ -364,11 +385,15 @@ __device__ __forceinline__ bool huf_decode_stream_fs(const u32 tOff, const u32 n
                         const u32 nb2 = (u32)__builtin_amdgcn_mov_dpp((int)b[4 * (p ^ 2u) + k], 0x4E, 0xF, 0xF, true);    // lane ^ 2's piece p ^ 2
                         c[4 * p + k] = (odd2 == (bool)(p & 2u)) ? b[4 * p + k] : nb2;
                     }
+#ifndef ZMI_EXP_LIT_NOSTORE                  // (ablation build, DEFS=-DZMI_EXP_LIT_NOSTORE, DESIGN 11: the same steps without the transposed stores)
 #pragma unroll
                 for (u32 p = 0; p < 4; ++p) {
                     u32u* o = (u32u*)(tbase + (size_t)p * seg + i);
                     o[0] = c[4 * p]; o[1] = c[4 * p + 1]; o[2] = c[4 * p + 2]; o[3] = c[4 * p + 3];
                 }
+#else
+                asm volatile("" :: "v"(c[0]), "v"(c[5]), "v"(c[10]), "v"(c[15]));
+#endif
                 i += 64;
             }
         }
@@ -376,11 +401,16 @@ __device__ __forceinline__ bool huf_decode_stream_fs(const u32 tOff, const u32 n
             u32 d[16];
 #pragma unroll
             for (u32 g = 0; g < 8; ++g) step(d[2 * g], d[2 * g + 1]);
+            touch();
             u32u* o = (u32u*)(out + i);
 #pragma unroll
             for (u32 g = 0; g < 16; ++g) o[g] = d[g];
             i += 64;
         }
+#if defined(ZMI_LIT_AHEAD) && ZMI_LIT_AHEAD
+        asm volatile("" :: "v"(touched));
+#endif
+        (void)touched;
         while (i + 8 <= n) {
             u32 d0, d1;
             step(d0, d1);
