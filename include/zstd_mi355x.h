@@ -727,7 +727,8 @@ long long ZSTDMI_debugLastContentCuts(const ZSTD_CCtx* cctx);
  * Both functions are serial inside a piece: the call is fast for many pieces and a serial chain for one long piece (README "Piece digests").
  * ZSTDMI_debugDigestModel: one digest of host memory on the CPU, by the same text the kernels run (zmi_digest.h); no device;
  * parameter_outOfBound for a bad kind, GENERIC for a NULL digest or a NULL src with a size.
- * Out of scope: device-array outputs and an enqueued form, other kinds and keyed hashes, digests computed inside the compress calls. */
+ * Device-array outputs and an enqueued form: ZSTDMI_contentCutsAsync below.
+ * Out of scope: other kinds and keyed hashes, digests computed inside the compress calls. */
 enum { ZSTDMI_digest_xxh64 = 1, ZSTDMI_digest_sha256 = 2 };
 size_t ZSTDMI_digestSize(unsigned kind);
 size_t ZSTDMI_digestPieces(ZSTD_CCtx* cctx, const void* src, size_t srcSize,
@@ -737,6 +738,68 @@ size_t ZSTDMI_contentCutsDigests(ZSTD_CCtx* cctx, const void* src, size_t srcSiz
                                  size_t* pieceSizes, size_t capacity, size_t* nPieces,
                                  void* digests, size_t digestsCapacity);
 size_t ZSTDMI_debugDigestModel(unsigned kind, const void* src, size_t srcSize, void* digest);
+
+/* Cuts and digests enqueued from the device: ZSTDMI_contentCutsDigests (or, with kind 0, ZSTDMI_contentCuts) as an enqueued call in the
+ * manner of ZSTDMI_compressBatchAsync — every result in device memory, no allocation, no host wait, no copy between host and device
+ * and no host read of any array inside the call.  Its sizes (size_t) and sources (pointers) are the d_srcSizes and d_srcs of
+ * ZSTDMI_compressBatchAsync and ZSTDMI_compressPackAsync as they stand.
+ * ZSTDMI_CCtx_prepareCutsAsync does everything that needs the host: it allocates one workspace of its own (never the synchronous
+ * calls' buffers) for sources up to srcSizeBound bytes cut at avgLog, with digests of `kind` (0: none) and room for maxCandidates
+ * candidate ends (0: four times the expected count, 4 * (srcSizeBound >> (avgLog - 1)) + 1024; held to 2^32 - 16).
+ * ZSTDMI_cutsAsyncWorkspace(limits): the bytes of that workspace, host arithmetic — with T = ceil(srcSizeBound / 16384), C = the
+ * candidate room, P = srcSizeBound / (1 << (avgLog - 2)) + 1, D = ZSTDMI_digestSize(kind), B = ceil((C + 2) / 1024) and r(x) = x rounded
+ * up to a multiple of 256:
+ *     r(8 (T + 16) + 256) + r(4 C + 64) + 4 r(4 (C + 2)) + r(C + 2) + 2 r(4 (B + 16)) + 256 + r(4 (P + 1)) + r(P D)
+ * — or the error the prepare would answer for the same limits before it looks for a device.
+ * The prepare consults no sticky parameter, dictionary, CDict or switch.  A context holds one cuts prepare, independent of the batch
+ * prepare: each leaves the other valid.  Compression-parameter setters, dictionary calls and the synchronous cut and digest calls leave
+ * it valid; a later ZSTDMI_CCtx_prepareCutsAsync replaces it (also when it fails); ZSTDMI_CCtx_setDevice and ZSTDMI_CCtx_setDevices drop it.
+ * Answers, all but the last group before a device is looked for: NULL context or NULL limits: GENERIC; srcSizeBound 0 or above 2^32 - 1,
+ * avgLog outside 12 .. 16, a kind above 2 or a non-zero reserved field: parameter_outOfBound; several device workers:
+ * parameter_unsupported; then init_missing / memory_allocation.
+ * ZSTDMI_CCtx_getCutsAsyncPlan: what the prepare resolved (any pointer may be NULL) — maxPieces = P above, the capacity no call on this
+ * prepare exceeds; the candidate room; the digest size.  stage_wrong without a prepare.
+ * ZSTDMI_contentCutsAsync.  Every d_ argument is device memory; srcSize, capacity (elements of d_pieceSizes and of d_pieceSrcs) and
+ * digestsCapacity (bytes) are host scalars.  It enqueues on the context's stream and returns 0, or — nothing enqueued — GENERIC (NULL
+ * context, NULL d_nPieces, NULL d_status, NULL d_pieceSizes with a capacity; then, behind stage_wrong, d_digests NULL with a prepared
+ * kind or not NULL without one), stage_wrong (no valid prepare), srcSize_wrong (srcSize above the bound, NULL d_src with a size).
+ * Device results: *d_status is 0 or one error code (as a size_t, ZSTD_isError's form).  On success *d_nPieces is the number of pieces
+ * the rule (version 1) gives for [d_src, d_src + srcSize), d_pieceSizes[i] their sizes in order, d_pieceSrcs[i] = d_src + start_i
+ * where that array is given, d_digests their digests in ZSTDMI_digestPieces' byte format.  srcSize == 0: status 0, 0 pieces, no array
+ * touched.  More pieces than capacity, or more digest bytes than digestsCapacity: dstSize_tooSmall, *d_nPieces the true count, no array
+ * element written.  More candidates than the prepared room: workSpace_tooSmall, *d_nPieces 0, no array element written (prepare with a
+ * larger maxCandidates; a list is never thinned).  Nothing is ever written outside the first *d_nPieces elements of each array.
+ * ZSTDMI_debugHostWaits and ZSTDMI_debugDeviceAllocs do not move across the call; no stage is timed.  Lifetime: ZSTDMI_compressBatchAsync's
+ * rules — the source and every array stay as they are until the stream has passed the work; the context's own buffers are guarded by
+ * the same event.  Capture into a hipGraph is neither claimed nor tested.
+ * The selection runs across the device (zmi_cut_rank.h): per candidate the candidate its piece would end at, the candidates the walk
+ * from position 0 reaches by pointer doubling, every reached candidate's ends at the index a scan gives it.  The synchronous calls keep
+ * their single-wave selection.  ZSTDMI_debugCutSelectParallel runs that selection alone over a HOST list of nCand ascending candidate
+ * ends of a source of n bytes (synchronous; buffers of its own): *nEnds = the pieces, ends[0 .. *nEnds) their ends when they fit cap,
+ * else dstSize_tooSmall; GENERIC for NULL arguments, parameter_outOfBound for avgLog, srcSize_wrong for n above 2^32 - 1 or nCand above n.
+ * ZSTDMI_debugCutsAsyncStages runs the stages of one call on the prepared workspace behind events and waits (a measuring hook, not an
+ * enqueued call): ms[0] = count and bounded emit, ms[1] = the selection, ms[2] = the digests, in milliseconds; GENERIC for a NULL
+ * argument, stage_wrong without a prepare, srcSize_wrong for a size of 0 or above the bound or a NULL source.
+ * Out of scope: a device-side entry count for ZSTDMI_compressBatchAsync / ZSTDMI_compressPackAsync (a caller reads the 8-byte count, or
+ * filters with a kernel of its own); switching the synchronous calls to the parallel selection; sources above 2^32 - 1; thinning of
+ * hostile candidate lists; balancing of uneven pieces in the digest kernels. */
+typedef struct {
+    size_t   srcSizeBound;   /* bytes of one call's source, 1 .. 2^32 - 1 */
+    unsigned avgLog;         /* 12 .. 16 */
+    unsigned kind;           /* 0 = no digests, ZSTDMI_digest_xxh64, ZSTDMI_digest_sha256 */
+    size_t   maxCandidates;  /* 0 = 4 * (srcSizeBound >> (avgLog - 1)) + 1024 */
+    size_t   reserved[3];    /* must be 0 */
+} ZSTDMI_CutLimits;
+size_t ZSTDMI_cutsAsyncWorkspace(const ZSTDMI_CutLimits* limits);
+size_t ZSTDMI_CCtx_prepareCutsAsync(ZSTD_CCtx* cctx, const ZSTDMI_CutLimits* limits);
+size_t ZSTDMI_CCtx_getCutsAsyncPlan(const ZSTD_CCtx* cctx, size_t* maxPieces, size_t* maxCandidates, size_t* digestSize);
+size_t ZSTDMI_contentCutsAsync(ZSTD_CCtx* cctx, const void* d_src, size_t srcSize,
+                               size_t* d_pieceSizes, const void** d_pieceSrcs, size_t capacity,
+                               void* d_digests, size_t digestsCapacity,
+                               size_t* d_nPieces, size_t* d_status);
+size_t ZSTDMI_debugCutSelectParallel(ZSTD_CCtx* cctx, const unsigned* cands, size_t nCand, unsigned long long n, unsigned avgLog,
+                                     unsigned* ends, size_t cap, size_t* nEnds);
+size_t ZSTDMI_debugCutsAsyncStages(ZSTD_CCtx* cctx, const void* d_src, size_t srcSize, float* ms);
 
 /* Seekable streams (the zstd seekable format, v0.1.0): random access at the granularity of the frame.
  * Every stream this library writes is a run of independent frames (64 KiB of content at levels 1-2, 240-256 KiB at levels >= 3, 32 KiB

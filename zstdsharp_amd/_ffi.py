@@ -48,6 +48,11 @@ class CBatchLimits(ctypes.Structure):
     _fields_ = [("maxEntries", c_size_t), ("srcSizeBound", c_size_t), ("maxChunks", c_size_t), ("reserved", c_size_t * 3)]
 
 
+class CutLimits(ctypes.Structure):
+    """ZSTDMI_CutLimits: what one ZSTDMI_contentCutsAsync call may hold at most (maxCandidates 0 = the default; reserved = 0)."""
+    _fields_ = [("srcSizeBound", c_size_t), ("avgLog", c_uint), ("kind", c_uint), ("maxCandidates", c_size_t), ("reserved", c_size_t * 3)]
+
+
 # name -> (restype, argtypes); every symbol include/zstd_mi355x.h declares
 SIGNATURES = {
     "ZSTD_createCCtx": (c_void_p, []),
@@ -168,6 +173,13 @@ SIGNATURES = {
     "ZSTDMI_contentCutsDigests": (c_size_t, [c_void_p, c_void_p, c_size_t, c_uint, c_uint, ctypes.POINTER(c_size_t), c_size_t, ctypes.POINTER(c_size_t),
                                              c_void_p, c_size_t]),
     "ZSTDMI_debugDigestModel": (c_size_t, [c_uint, c_void_p, c_size_t, c_void_p]),
+    "ZSTDMI_cutsAsyncWorkspace": (c_size_t, [ctypes.POINTER(CutLimits)]),
+    "ZSTDMI_CCtx_prepareCutsAsync": (c_size_t, [c_void_p, ctypes.POINTER(CutLimits)]),
+    "ZSTDMI_CCtx_getCutsAsyncPlan": (c_size_t, [c_void_p, ctypes.POINTER(c_size_t), ctypes.POINTER(c_size_t), ctypes.POINTER(c_size_t)]),
+    "ZSTDMI_contentCutsAsync": (c_size_t, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "ZSTDMI_debugCutsAsyncStages": (c_size_t, [c_void_p, c_void_p, c_size_t, ctypes.POINTER(ctypes.c_float)]),
+    "ZSTDMI_debugCutSelectParallel": (c_size_t, [c_void_p, ctypes.POINTER(c_uint), c_size_t, c_ull, c_uint, ctypes.POINTER(c_uint), c_size_t,
+                                                 ctypes.POINTER(c_size_t)]),
     "ZSTDMI_CCtx_setSeekTable": (c_size_t, [c_void_p, c_uint]),
     "ZSTDMI_CCtx_setDictEntropy": (c_size_t, [c_void_p, c_uint]),
     "ZSTDMI_CCtx_setEntropyCarry": (c_size_t, [c_void_p, c_uint]),

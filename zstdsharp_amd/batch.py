@@ -265,6 +265,51 @@ def compress_pack_async(compressor, srcs, sizes, dst, out_size=None, entry_ends=
     return out_size
 
 
+def content_cuts_async(compressor, src, sizes=None, srcs=None, digests=None):
+    """ZSTDMI_contentCutsAsync after Compressor.PrepareCutsAsync: the pieces of `src` (a contiguous CUDA uint8 tensor of at most the
+    prepared bound) by the cut rule, and their digests where the prepare asked for a kind, all in device memory ->
+    (n_pieces, status, sizes, srcs, digests): n_pieces and status 1-element CUDA int64 tensors (status 0, or the call's zstd error code
+    as a negative value: -70 dstSize_tooSmall — n_pieces is then still the true count —, -66 workSpace_tooSmall: more candidates than
+    the prepared room); sizes and srcs CUDA int64 tensors whose first n_pieces entries are the pieces' sizes and addresses — the
+    `sizes` and `srcs` compress_batch_async and compress_pack_async take —; digests a CUDA uint8 tensor, n_pieces digests side by side
+    (None without a kind).  Tensors not given are allocated from the plan (max_pieces entries); given ones state the capacity by their
+    numel().  The work is enqueued on torch.cuda.current_stream() and the call returns: nothing is synchronised and nothing is copied
+    to the host.  Every tensor and `src` must stay alive and unchanged until that stream has passed the work.  Raises ZstdException for
+    the call's own error (stage_wrong: no PrepareCutsAsync; srcSize_wrong: src above the bound)."""
+    import torch
+    compressor._ensure_not_disposed()
+    lib = compressor._lib
+    if not (isinstance(src, torch.Tensor) and src.is_cuda and src.dtype == torch.uint8 and src.is_contiguous()):
+        raise TypeError("src: expected a contiguous CUDA uint8 tensor")
+    max_pieces, _, each = compressor.cuts_async_plan()
+    dev = src.device
+    if sizes is None:
+        sizes = torch.empty(max_pieces, dtype=torch.int64, device=dev)
+    if srcs is None:
+        srcs = torch.empty(sizes.numel(), dtype=torch.int64, device=dev)
+    if digests is None and each:
+        digests = torch.empty(sizes.numel() * each, dtype=torch.uint8, device=dev)
+    for name, t in (("sizes", sizes), ("srcs", srcs)):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int64 and t.is_contiguous()):
+            raise TypeError(f"{name}: expected a contiguous CUDA int64 tensor")
+    if srcs.numel() != sizes.numel():
+        raise TypeError("srcs: expected as many entries as sizes")
+    if digests is not None and not (isinstance(digests, torch.Tensor) and digests.is_cuda and digests.dtype == torch.uint8 and digests.is_contiguous()):
+        raise TypeError("digests: expected a contiguous CUDA uint8 tensor")
+    n_pieces = torch.empty(1, dtype=torch.int64, device=dev)
+    status = torch.empty(1, dtype=torch.int64, device=dev)
+    stream = torch.cuda.current_stream(dev)
+    r = lib.ZSTDMI_CCtx_setStream(compressor.cctx, stream.cuda_stream or _HIP_STREAM_LEGACY)
+    if not is_error(r):
+        cap = sizes.numel()
+        r = lib.ZSTDMI_contentCutsAsync(compressor.cctx, src.data_ptr() if src.numel() else None, src.numel(), sizes.data_ptr() if cap else None,
+                                        srcs.data_ptr() if cap else None, cap, digests.data_ptr() if digests is not None else None,
+                                        digests.numel() if digests is not None else 0, n_pieces.data_ptr(), status.data_ptr())
+    if is_error(r):
+        raise ZstdException(get_error_code(r), lib.ZSTD_getErrorName(r).decode())
+    return n_pieces, status, sizes, srcs, digests
+
+
 def pack_ranges(sizes):
     """-> [(offset, length), ...] for Decompressor.unwrap_ranges: record i of a pack whose items had these sizes."""
     ranges, at = [], 0

@@ -311,6 +311,26 @@ class Compressor(_PrefixHolder):
 
     prepare_batch_async, prepare_batch_async_limits = PrepareBatchAsync, PrepareBatchAsyncLimits
 
+    # ---- cuts and digests enqueued from the device (ZSTDMI_CCtx_prepareCutsAsync; content_cuts_async runs them) ----
+    def PrepareCutsAsync(self, src_size_bound: int, avg_log: int, kind=None, max_candidates: int = 0):
+        """Everything content_cuts_async needs the host for, once: one workspace for sources of up to src_size_bound bytes (at most
+        2^32 - 1) cut at avg_log, with digests of `kind` (None: none; "xxh64" / "sha256" or the ABI's integer) and room for
+        max_candidates candidate ends (0: four times the expected count).  Independent of PrepareBatchAsync and of every parameter;
+        a later PrepareCutsAsync replaces it.  Raises ZstdException (parameter_outOfBound, parameter_unsupported) as the header states."""
+        self._ensure_not_disposed()
+        lim = _ffi.CutLimits(int(src_size_bound), int(avg_log), 0 if kind is None else _digest_kind(kind), int(max_candidates))
+        ensure_zstd_success(self._lib, self._lib.ZSTDMI_CCtx_prepareCutsAsync(self.cctx, ctypes.byref(lim)))
+
+    def cuts_async_plan(self):
+        """ZSTDMI_CCtx_getCutsAsyncPlan -> (max_pieces, max_candidates, digest_size) of the cuts prepare; ZstdException (stage_wrong)
+        without one."""
+        self._ensure_not_disposed()
+        mp, mc, ds = ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_size_t(0)
+        ensure_zstd_success(self._lib, self._lib.ZSTDMI_CCtx_getCutsAsyncPlan(self.cctx, ctypes.byref(mp), ctypes.byref(mc), ctypes.byref(ds)))
+        return mp.value, mc.value, ds.value
+
+    prepare_cuts_async = PrepareCutsAsync
+
     # ---- Wrap (S/Compressor.cs:78-96) ----
     def Wrap(self, src, dest=None, offset: int = 0):
         """Wrap(src) -> bytes;  Wrap(src, dest[, offset]) -> number of bytes written into dest."""

@@ -144,6 +144,30 @@ u32* cut_total_word(u8* small, u64 n);
 void launch_cut_count(const u8* src, u64 n, u32 bits, u8* small, hipStream_t stream);
 void launch_cut_emit(const u8* src, u64 n, u32 bits, u8* small, u32* cand, hipStream_t stream);
 void launch_cut_select(const u32* cand, u32 nCand, u64 n, const CutRule& rule, u32* out, u32 cap, hipStream_t stream);
+// cuts and digests enqueued from the device (content_cuts_async.hip; the selection: zmi_cut_rank.h).  One workspace the
+// prepare sizes (cuts_async_layout: include/zstd_mi355x.h states the arithmetic): the count's tiles, the list with room for maxCand
+// candidates, per node (maxCand + 2) the successor, two pointer planes, the forced count and the mark, the scan's block sums and bases,
+// 256 bytes of state (word 0: the pieces, word 1: the list passed its room), the ends (1 + maxPieces words) and the digests.
+constexpr u64 kCutsAsyncMaxCand = 0xFFFFFFF0ull;     // the most candidates a prepare makes room for (node indices are words)
+struct CutsAsyncLayout { size_t atSmall, atList, atSucc, atJumpA, atJumpB, atForced, atMark, atSum, atBase, atState, atEnds, atDigests, bytes; };
+CutsAsyncLayout cuts_async_layout(u64 bound, u64 maxCand, u64 maxPieces, u32 digestSize);
+struct CutRankWs { u32* succ; u32* jumpA; u32* jumpB; u32* forced; u8* mark; u32* blockSum; u32* blockBase; u32* state; };
+inline CutRankWs cut_rank_ws(u8* p, const CutsAsyncLayout& L)
+{
+    return CutRankWs{ (u32*)(p + L.atSucc), (u32*)(p + L.atJumpA), (u32*)(p + L.atJumpB), (u32*)(p + L.atForced), p + L.atMark, (u32*)(p + L.atSum), (u32*)(p + L.atBase), (u32*)(p + L.atState) };
+}
+// emit: launch_cut_emit that never stores at or beyond `room` and does nothing when the count passed it.  rank: the selection over the
+// list of *total candidates -> ends[0] = the pieces, ends[1 ..] their ends (at most cap), state as above.  finish: the caller's arrays
+// (all device memory) from the ends, the state and the workspace's digests; maxPieces: the most pieces n allows (the grid)
+void launch_cut_emit_bounded(const u8* src, u64 n, u32 bits, u8* small, u32* cand, u32 room, hipStream_t stream);
+void launch_cut_rank(const u32* cand, const u32* total, u32 room, u64 n, const CutRule& rule, const CutRankWs& ws, u32* ends, u32 cap, hipStream_t stream);
+struct CutsFinishArgs {
+    const u32* ends; const u32* state; u32 endsCap; const u8* src; u64 n, maxPieces;
+    size_t* sizes; const void** srcs; u64 capacity;
+    const u8* digestsWs; u8* digests; u64 digestsCapacity; u32 digestSize;
+    size_t* nPieces; size_t* status;
+};
+void launch_cuts_finish(const CutsFinishArgs& a, hipStream_t stream);
 // piece digests (digest.hip; the functions: zmi_digest.h).  Where the pieces of [src, src + srcSize) lie: offs, n + 1 offsets from src
 // (device memory, ascending, the last at most srcSize), or — ends not null — launch_cut_select's output, of which the kernel takes the
 // count and the ends; n is then the most pieces there can be (the select's cap).  out: n digests side by side (device memory).

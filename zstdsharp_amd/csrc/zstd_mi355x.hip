@@ -126,6 +126,9 @@ struct ZSTD_CCtx_s {
     DevBuf cutSmall, cutList, cutEnds;
     // ZSTDMI_digestPieces / ZSTDMI_contentCutsDigests (digest.hip): the pieces' offsets and their digests on the device
     DevBuf digOffs, digOut;
+    // ZSTDMI_CCtx_prepareCutsAsync / ZSTDMI_contentCutsAsync (content_cuts_async.hip): what the prepare resolved and its one
+    // workspace, which no other call touches.  Independent of asyncPrep and of every parameter; ZSTDMI_CCtx_setDevice / setDevices drop it.
+    struct CutsPrep* cutsPrep = nullptr; DevBuf cutsAsync;
     struct AsyncPrep* asyncPrep = nullptr; hipEvent_t asyncEv = nullptr; bool asyncPending = false;
     ZSTD_CCtx_s();
 };
@@ -179,11 +182,14 @@ static void cctx_async_drain(ZSTD_CCtx* c)
 // a blocking copy, counted as the wait it is
 static hipError_t host_memcpy(void* dst, const void* src, size_t n, hipMemcpyKind kind) { count_wait(); return hipMemcpy(dst, src, n, kind); }
 static u64 cctx_gen(const ZSTD_CCtx* c) { return c->paramGen + c->dictGen; }
+// a cuts prepare (ZSTDMI_CCtx_prepareCutsAsync): the limits as resolved, the most pieces they allow and where everything lies in cutsAsync
+struct CutsPrep { u64 bound; unsigned avgLog, kind; u32 maxCand; u64 maxPieces; u32 digestSize; CutsAsyncLayout lay; };
+static void cctx_drop_cuts_prepare(ZSTD_CCtx* c) { delete c->cutsPrep; c->cutsPrep = nullptr; }
 ZSTD_CCtx_s::ZSTD_CCtx_s()
 {
     tally.self = this; tally.beforeFree = [](void* self) { cctx_async_drain((ZSTD_CCtx_s*)self); };
     for (DevBuf* b : { &seqs, &lits, &meta, &tables, &slots, &offsets, &total, &cand, &probe, &stageSrc, &stageDst, &ldmSmall, &ldmBig, &dixDist, &gatherIn, &gatherOut,
-                       &batchStage, &batchTab, &packArena, &packTab, &packAsync, &seekEntries, &seekSort, &pfxStage, &sfXxh, &sWin, &cutSmall, &cutList, &cutEnds, &digOffs, &digOut,
+                       &batchStage, &batchTab, &packArena, &packTab, &packAsync, &seekEntries, &seekSort, &pfxStage, &sfXxh, &sWin, &cutSmall, &cutList, &cutEnds, &digOffs, &digOut, &cutsAsync,
                        &own.dict, &own.dictFullDev, &own.dictInfoDev, &own.dictCTabDev, &own.dictWideDev, &own.dictIdxDev }) b->owner = &tally;
     pin.owner = &tally;
 }
@@ -1029,11 +1035,12 @@ size_t ZSTD_freeCCtx(ZSTD_CCtx* c)
         if (c->asyncEv) (void)hipEventDestroy(c->asyncEv);
         if (c->ownStream) (void)hipStreamSynchronize(c->ownStream);
         c->seqs.release(); c->lits.release(); c->meta.release(); c->tables.release(); c->slots.release(); c->cand.release(); c->lastRegionList = nullptr; c->dixDist.release(); c->probe.release();
-        c->gatherIn.release(); c->gatherOut.release(); c->batchStage.release(); c->batchTab.release(); c->packArena.release(); c->packTab.release(); c->packAsync.release(); c->ldmSmall.release(); c->ldmBig.release(); c->offsets.release(); c->total.release(); c->seekEntries.release(); c->seekSort.release(); c->stageSrc.release(); c->stageDst.release(); c->pfxStage.release(); c->sfXxh.release(); c->sWin.release(); c->cutSmall.release(); c->cutList.release(); c->cutEnds.release(); c->digOffs.release(); c->digOut.release(); c->own.release(); c->pin.release();
+        c->gatherIn.release(); c->gatherOut.release(); c->batchStage.release(); c->batchTab.release(); c->packArena.release(); c->packTab.release(); c->packAsync.release(); c->ldmSmall.release(); c->ldmBig.release(); c->offsets.release(); c->total.release(); c->seekEntries.release(); c->seekSort.release(); c->stageSrc.release(); c->stageDst.release(); c->pfxStage.release(); c->sfXxh.release(); c->sWin.release(); c->cutSmall.release(); c->cutList.release(); c->cutEnds.release(); c->digOffs.release(); c->digOut.release(); c->cutsAsync.release(); c->own.release(); c->pin.release();
         c->timer.destroy();
         if (c->ownStream) (void)hipStreamDestroy(c->ownStream);
     }
     delete c->asyncPrep;
+    cctx_drop_cuts_prepare(c);
     delete c;
     return 0;
 }
@@ -1735,10 +1742,10 @@ static size_t ZSTD_compressStream2_impl(ZSTD_CCtx* c, ZSTD_outBuffer* output, ZS
 // ---------------- extensions ----------------
 int ZSTDMI_deviceCount(void) { return device_count(); }
 // (a referenced CDict is shared or copied by where the context runs: cctx_adopt_cdict)
-size_t ZSTDMI_CCtx_setDevice(ZSTD_CCtx* c, int device) { if (c) c->paramGen++; const size_t e = ctx_set_device(c, device); if (c && c->cdict) (void)guarded([&]() -> size_t { cctx_adopt_cdict(c); return 0; }); return e; }
+size_t ZSTDMI_CCtx_setDevice(ZSTD_CCtx* c, int device) { if (c) { c->paramGen++; cctx_drop_cuts_prepare(c); } const size_t e = ctx_set_device(c, device); if (c && c->cdict) (void)guarded([&]() -> size_t { cctx_adopt_cdict(c); return 0; }); return e; }
 size_t ZSTDMI_CCtx_setDevices(ZSTD_CCtx* c, const int* devices, int n)
 {
-    if (c) c->paramGen++;
+    if (c) { c->paramGen++; cctx_drop_cuts_prepare(c); }
     const size_t e = ctx_set_devices(c, devices, n, ZSTD_createCCtx, ZSTD_freeCCtx);
     if (c && c->cdict) (void)guarded([&]() -> size_t { cctx_adopt_cdict(c); return 0; });
     return e;
@@ -2869,6 +2876,156 @@ extern "C" size_t ZSTDMI_debugDigestModel(unsigned kind, const void* src, size_t
     if (!digest || (srcSize && !src)) return ZERR(kErrGeneric);
     (void)digest_serial(kind, (const u8*)src, srcSize, (u8*)digest);
     return 0;
+}
+
+// ---- cuts and digests enqueued from the device (include/zstd_mi355x.h "Cuts and digests enqueued from the device") ----
+// the limits as the prepare takes them: 0, or what both ZSTDMI_cutsAsyncWorkspace and the prepare answer before a device is looked for
+static size_t cuts_limits_resolve(const ZSTDMI_CutLimits* L, CutsPrep& P)
+{
+    if (!L) return ZERR(kErrGeneric);
+    if (!L->srcSizeBound || (u64)L->srcSizeBound > kCutMaxSrc || !cut_avglog_ok(L->avgLog) || L->kind > 2 || L->reserved[0] || L->reserved[1] || L->reserved[2])
+        return ZERR(kErrParameterOutOfBound);
+    const CutRule rule = cut_rule(L->avgLog);
+    u64 cand = L->maxCandidates ? (u64)L->maxCandidates : 4 * ((u64)L->srcSizeBound >> rule.bits) + 1024;
+    if (cand > kCutsAsyncMaxCand) cand = kCutsAsyncMaxCand;         // (node indices are words)
+    P.bound = L->srcSizeBound; P.avgLog = L->avgLog; P.kind = L->kind; P.maxCand = (u32)cand;
+    P.maxPieces = cut_max_pieces(P.bound, rule); P.digestSize = (u32)digest_size(L->kind);
+    P.lay = cuts_async_layout(P.bound, cand, P.maxPieces, P.digestSize);
+    return 0;
+}
+static size_t prepare_cuts_async_impl(ZSTD_CCtx* c, const ZSTDMI_CutLimits* L)
+{
+    if (!c || !L) return ZERR(kErrGeneric);
+    cctx_drop_cuts_prepare(c);
+    CutsPrep P;
+    size_t e = cuts_limits_resolve(L, P); if (isErr(e)) return e;
+    if (c->workers.size() > 1) return ZERR(kErrParameterUnsupported);
+    e = cctx_bind(c); if (isErr(e)) return e;
+    if (!c->cutsAsync.ensure(P.lay.bytes)) return ZERR(kErrMemoryAllocation);
+    if (!c->asyncEv && hipEventCreateWithFlags(&c->asyncEv, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); c->asyncEv = nullptr; return ZERR(kErrMemoryAllocation); }
+    c->cutsPrep = new CutsPrep(P);
+    return 0;
+}
+// Kernels only, on the context's stream: the synchronous call's count, the bounded emit, the parallel selection, the fused digest over
+// the ends where the selection left them, and the finish that files everything the caller reads.  The host knows srcSize and the
+// prepared limits and nothing else: every grid and the round count come from them.
+static size_t content_cuts_async_impl(ZSTD_CCtx* c, const u8* d_src, size_t srcSize, size_t* d_pieceSizes, const void** d_pieceSrcs, size_t capacity,
+                                      void* d_digests, size_t digestsCapacity, size_t* d_nPieces, size_t* d_status)
+{
+    if (!c || !d_nPieces || !d_status || (capacity && !d_pieceSizes)) return ZERR(kErrGeneric);
+    const CutsPrep* const P = c->cutsPrep;
+    if (!P || !c->deviceOk) return ZERR(kErrStageWrong);
+    if ((d_digests != nullptr) != (P->kind != 0)) return ZERR(kErrGeneric);
+    if ((u64)srcSize > P->bound || (srcSize && !d_src)) return ZERR(kErrSrcSizeWrong);
+    const size_t e = cctx_bind(c); if (isErr(e)) return e;
+    hipStream_t s = c->stream;
+    u8* const ws = (u8*)c->cutsAsync.p;
+    const CutsAsyncLayout& L = P->lay;
+    u32* const ends = (u32*)(ws + L.atEnds);
+    const CutRankWs rk = cut_rank_ws(ws, L);
+    const CutRule rule = cut_rule(P->avgLog);
+    const u64 n = srcSize, most = cut_max_pieces(n, rule);
+    if (n) {
+        u8* const small = ws + L.atSmall; u32* const list = (u32*)(ws + L.atList);
+        launch_cut_count(d_src, n, rule.bits, small, s);
+        launch_cut_emit_bounded(d_src, n, rule.bits, small, list, P->maxCand, s);
+        launch_cut_rank(list, cut_total_word(small, n), P->maxCand, n, rule, rk, ends, (u32)P->maxPieces, s);
+        if (P->kind) launch_digest(P->kind, d_src, DigestPieces{ nullptr, ends, most, n }, ws + L.atDigests, s);
+    }
+    launch_cuts_finish(CutsFinishArgs{ ends, rk.state, (u32)P->maxPieces, d_src, n, most, d_pieceSizes, d_pieceSrcs, capacity,
+                                       ws + L.atDigests, (u8*)d_digests, digestsCapacity, P->digestSize, d_nPieces, d_status }, s);
+    return async_enqueued(c, s);
+}
+// the selection alone over a host list (synchronous; buffers of its own, freed before it returns)
+static size_t debug_cut_select_parallel_impl(ZSTD_CCtx* c, const unsigned* cands, size_t nCand, unsigned long long n, unsigned avgLog, unsigned* outEnds, size_t cap, size_t* nEnds)
+{
+    if (!c || !nEnds || (nCand && !cands) || (cap && !outEnds)) return ZERR(kErrGeneric);
+    *nEnds = 0;
+    if (!cut_avglog_ok(avgLog)) return ZERR(kErrParameterOutOfBound);
+    if (n > kCutMaxSrc || (u64)nCand > n || (u64)nCand > kCutsAsyncMaxCand) return ZERR(kErrSrcSizeWrong);
+    size_t e = cctx_bind(c); if (isErr(e)) return e;
+    const CutRule rule = cut_rule(avgLog);
+    const u64 P = cut_max_pieces(n, rule);
+    const u32 room = (u32)nCand, endsCap = (u32)((u64)cap < P ? (u64)cap : P);
+    const CutsAsyncLayout L = cuts_async_layout(1, room, endsCap, 0);
+    DevBuf buf;
+    struct Free { DevBuf& b; ~Free() { b.release(); } } freeIt{ buf };
+    if (!buf.ensure(L.bytes)) return ZERR(kErrMemoryAllocation);
+    hipStream_t s = c->stream;
+    u8* const ws = (u8*)buf.p;
+    u32* const list = (u32*)(ws + L.atList); u32* const total = (u32*)(ws + L.atSmall); u32* const ends = (u32*)(ws + L.atEnds);
+    const CutRankWs rk = cut_rank_ws(ws, L);
+    if ((nCand && hipMemcpyAsync(list, cands, nCand * 4, hipMemcpyHostToDevice, s) != hipSuccess) ||
+        hipMemcpyAsync(total, &room, 4, hipMemcpyHostToDevice, s) != hipSuccess) return ZERR(kErrGeneric);
+    launch_cut_rank(list, total, room, n, rule, rk, ends, endsCap, s);
+    u32 state[2] = { 0, 0 };
+    if (isErr(dev_read(state, rk.state, sizeof state, s))) return ZERR(kErrGeneric);
+    *nEnds = state[0];
+    if (state[1]) return ZERR(kErrWorkSpaceTooSmall);
+    if (state[0] > cap) return ZERR(kErrDstSizeTooSmall);
+    if (state[0] && isErr(dev_read(outEnds, ends + 1, (size_t)state[0] * 4, s))) return ZERR(kErrGeneric);
+    return 0;
+}
+// the stages of one enqueued call on the prepared workspace, timed by events and waited for (tools/cuts_async_time.py): ms[0] = count and
+// bounded emit, ms[1] = the selection, ms[2] = the digests (0 without a kind).  The caller's arrays are not involved: no finish.
+static size_t debug_cuts_async_stages_impl(ZSTD_CCtx* c, const u8* d_src, size_t srcSize, float* ms)
+{
+    if (!c || !ms) return ZERR(kErrGeneric);
+    const CutsPrep* const P = c->cutsPrep;
+    if (!P || !c->deviceOk) return ZERR(kErrStageWrong);
+    if (!srcSize || (u64)srcSize > P->bound || !d_src) return ZERR(kErrSrcSizeWrong);
+    const size_t e = cctx_bind(c); if (isErr(e)) return e;
+    hipStream_t s = c->stream;
+    hipEvent_t ev[4] = {};
+    struct Free { hipEvent_t* ev; ~Free() { for (int i = 0; i < 4; i++) if (ev[i]) (void)hipEventDestroy(ev[i]); } } freeThem{ ev };
+    for (auto& x : ev) if (hipEventCreate(&x) != hipSuccess) { (void)hipGetLastError(); x = nullptr; return ZERR(kErrMemoryAllocation); }
+    u8* const ws = (u8*)c->cutsAsync.p;
+    const CutsAsyncLayout& L = P->lay;
+    u8* const small = ws + L.atSmall; u32* const list = (u32*)(ws + L.atList); u32* const ends = (u32*)(ws + L.atEnds);
+    const CutRule rule = cut_rule(P->avgLog);
+    const u64 n = srcSize;
+    (void)hipEventRecord(ev[0], s);
+    launch_cut_count(d_src, n, rule.bits, small, s);
+    launch_cut_emit_bounded(d_src, n, rule.bits, small, list, P->maxCand, s);
+    (void)hipEventRecord(ev[1], s);
+    launch_cut_rank(list, cut_total_word(small, n), P->maxCand, n, rule, cut_rank_ws(ws, L), ends, (u32)P->maxPieces, s);
+    (void)hipEventRecord(ev[2], s);
+    if (P->kind) launch_digest(P->kind, d_src, DigestPieces{ nullptr, ends, cut_max_pieces(n, rule), n }, ws + L.atDigests, s);
+    (void)hipEventRecord(ev[3], s);
+    if (isErr(stream_wait(s))) return ZERR(kErrGeneric);
+    for (int i = 0; i < 3; i++) { ms[i] = 0; (void)hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]); }
+    return 0;
+}
+extern "C" size_t ZSTDMI_debugCutsAsyncStages(ZSTD_CCtx* c, const void* d_src, size_t srcSize, float* ms)
+{
+    return guarded([&] { return debug_cuts_async_stages_impl(c, (const u8*)d_src, srcSize, ms); });
+}
+extern "C" size_t ZSTDMI_cutsAsyncWorkspace(const ZSTDMI_CutLimits* limits)
+{
+    CutsPrep P;
+    const size_t e = cuts_limits_resolve(limits, P);
+    return isErr(e) ? e : P.lay.bytes;
+}
+extern "C" size_t ZSTDMI_CCtx_prepareCutsAsync(ZSTD_CCtx* c, const ZSTDMI_CutLimits* limits) { return guarded([&] { return prepare_cuts_async_impl(c, limits); }); }
+extern "C" size_t ZSTDMI_CCtx_getCutsAsyncPlan(const ZSTD_CCtx* c, size_t* maxPieces, size_t* maxCandidates, size_t* digestSize)
+{
+    if (!c) return ZERR(kErrGeneric);
+    const CutsPrep* const P = c->cutsPrep;
+    if (!P) return ZERR(kErrStageWrong);
+    if (maxPieces) *maxPieces = (size_t)P->maxPieces;
+    if (maxCandidates) *maxCandidates = P->maxCand;
+    if (digestSize) *digestSize = P->digestSize;
+    return 0;
+}
+extern "C" size_t ZSTDMI_contentCutsAsync(ZSTD_CCtx* c, const void* d_src, size_t srcSize, size_t* d_pieceSizes, const void** d_pieceSrcs, size_t capacity,
+                                          void* d_digests, size_t digestsCapacity, size_t* d_nPieces, size_t* d_status)
+{
+    return guarded([&] { return content_cuts_async_impl(c, (const u8*)d_src, srcSize, d_pieceSizes, d_pieceSrcs, capacity, d_digests, digestsCapacity, d_nPieces, d_status); });
+}
+extern "C" size_t ZSTDMI_debugCutSelectParallel(ZSTD_CCtx* c, const unsigned* cands, size_t nCand, unsigned long long n, unsigned avgLog,
+                                                unsigned* ends, size_t cap, size_t* nEnds)
+{
+    return guarded([&] { return debug_cut_select_parallel_impl(c, cands, nCand, n, avgLog, ends, cap, nEnds); });
 }
 
 extern "C" size_t ZSTDMI_debugCompressSamples(ZSTD_CCtx* c, const void* src, const size_t* sizes, size_t n, size_t* outSizes)
