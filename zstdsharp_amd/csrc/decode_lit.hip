@@ -247,7 +247,8 @@ __global__ __launch_bounds__(64) void decode_literals_slow_kernel(const u8* __re
 //     e = lds[a]                   entry: low byte = 32 - nbBits, high byte = symbol
 //     w = alignbit(w, r, e)        v_alignbit_b32 takes its shift from the entry's low 5 bits as they are: {w, r} >> (32 - nbBits)
 // (r, q), the 64 bits behind the window, the output packing and the bit count follow off the chain.  After 8 symbols (at most
-// 88 of the 96 bits) the window is rebuilt from the byte stream, see the function body.
+// 88 bits) the window is rebuilt from the byte stream: in the general form at once, from 96 bits, in the steady form beside the
+// next two lookups, from 128, see the function body.
 // IDX = index bits of the table (tables of a smaller tableLog are replicated up to it).  PAIRS: tableLog = IDX + 1 is held in the
 // same table: the longest codes come in pairs sharing an IDX-bit prefix and own the first entries of the table (canonical order:
 // weight classes ascending); such an entry holds BOTH symbols (low byte: next bit 0, high byte: next bit 1), "index below the
@@ -274,18 +275,186 @@ __device__ __forceinline__ bool huf_decode_stream_fs(const u32 tOff, const u32 n
     constexpr u32 kMask = ((1u << IDX) - 1u) << 1;
     // one symbol out of the 96-bit window (w, r, q): returns it, advances the window, adds 32 - its bits to `spare`
     // (nPair2 = twice the number of pair entries: t, which carries the bit behind the index, is below it exactly for them)
+    // (the lookup in its parts — fetch: the table entry for the bits at the top of w; entry: the symbol in it, and e2, whose low
+    //  5 bits are 32 - its length; the steady form below issues a fetch, re-bases, then shifts two sets of window registers by e2)
+    auto fetch = [&](const u32 w) -> u32 { return ZMI_LDS_U16(tOff | ((w >> (31 - IDX)) & kMask)); };
+    auto entry = [&](const u32 w, const u32 e, u32& e2) -> u32 {
+        u32 sh = 8; e2 = e;
+        if (PAIRS) { const u32 t = w >> (31 - IDX); const bool isPair = t < nPair2; e2 = isPair ? 31u - IDX : e; sh = isPair ? (t & 1u) << 3 : 8u; }
+        return (e >> sh) & 0xFFu;
+    };
+    auto look = [&](const u32 w, u32& e2) -> u32 { return entry(w, fetch(w), e2); };
     auto sym1 = [&](u32& w, u32& r, u32& q, u32& spare) -> u32 {
-        const u32 t = w >> (31 - IDX);
-        const u32 e = ZMI_LDS_U16(tOff | (t & kMask));
-        u32 e2 = e, sh = 8;
-        if (PAIRS) { const bool isPair = t < nPair2; e2 = isPair ? 31u - IDX : e; sh = isPair ? (t & 1u) << 3 : 8u; }
+        u32 e2; const u32 sym = look(w, e2);
         w = __builtin_amdgcn_alignbit(w, r, e2);
         r = __builtin_amdgcn_alignbit(r, q, e2);
         q = __builtin_amdgcn_alignbit(q, 0u, e2);
         spare += e2 & 0xFFu;
-        return (e >> sh) & 0xFFu;
+        return sym;
     };
     if (srcSize >= 16) {
+        const u32 last = src[srcSize - 1];
+        if (!last) return false;
+        remaining = (s32)(srcSize - 1) * 8 + (s32)highbit32(last);
+        // Behind the eighth step's look-ahead load of every second 64-symbol group: a 4-byte load ZMI_LIT_AHEAD bytes further down
+        // the stream, whose value nobody needs.  It brings that line into L2 before the exact loads get there, so that those hit (two
+        // groups move 92 bytes on average: nearly every 128-byte line is touched, once or twice; touching in every group, or only
+        // where the address enters a new line, measured slower: DESIGN 11).  A plain load, which the compiler counts in its vmcnt
+        // waits (a volatile one is waited for with vmcnt(0) right behind it).  The empty asm in front of the next touch is its only
+        // use: that keeps the load, and keeps its register claimed until then — a register free for reuse would be waited for in
+        // front of whatever reuses it.  at = where the decoder stands in the stream (any offset near it; clamped into the stream).
+        u32 touched = 0;
+        auto touch = [&](const s32 at) {
+#if defined(ZMI_LIT_AHEAD) && ZMI_LIT_AHEAD      // (zmi_lit_ahead.h; a build of this function without it — tests/host/lit_stream_harness.cpp — has no touch)
+            if (i & 64u) return;
+            asm volatile("" :: "v"(touched));
+            touched = *(const u32u*)(src + lit_touch_offset(at, (s32)srcSize, ZMI_LIT_AHEAD));
+#endif
+            (void)at;
+        };
+        // the two ways a group of 64 symbols (16 dwords) leaves a lane
+        auto store_plain = [&](const u32 (&d)[16]) {
+            u32u* o = (u32u*)(out + i);
+#pragma unroll
+            for (u32 g = 0; g < 16; ++g) o[g] = d[g];
+        };
+        auto store_quad = [&](const u32 (&d)[16]) {
+            const bool odd1 = ql & 1u, odd2 = ql & 2u;
+            u8* const tbase = out - (size_t)ql * seg + 16u * ql;       // stream 0's base + this lane's 16-byte column
+            // 4 x 4 transpose of 16-byte pieces over the quad's lanes: piece p of lane l <-> piece l of lane p
+            u32 b[16], c[16];
+#pragma unroll
+            for (u32 p = 0; p < 4; ++p)
+#pragma unroll
+                for (u32 k = 0; k < 4; ++k) {
+                    const u32 nb1 = (u32)__builtin_amdgcn_mov_dpp((int)d[4 * (p ^ 1u) + k], 0xB1, 0xF, 0xF, true);    // lane ^ 1's piece p ^ 1
+                    b[4 * p + k] = (odd1 == (bool)(p & 1u)) ? d[4 * p + k] : nb1;
+                }
+#pragma unroll
+            for (u32 p = 0; p < 4; ++p)
+#pragma unroll
+                for (u32 k = 0; k < 4; ++k) {
+                    const u32 nb2 = (u32)__builtin_amdgcn_mov_dpp((int)b[4 * (p ^ 2u) + k], 0x4E, 0xF, 0xF, true);    // lane ^ 2's piece p ^ 2
+                    c[4 * p + k] = (odd2 == (bool)(p & 2u)) ? b[4 * p + k] : nb2;
+                }
+#ifndef ZMI_EXP_LIT_NOSTORE                  // (ablation build, DEFS=-DZMI_EXP_LIT_NOSTORE, DESIGN 11: the same steps without the transposed stores)
+#pragma unroll
+            for (u32 p = 0; p < 4; ++p) {
+                u32u* o = (u32u*)(tbase + (size_t)p * seg + i);
+                o[0] = c[4 * p]; o[1] = c[4 * p + 1]; o[2] = c[4 * p + 2]; o[3] = c[4 * p + 3];
+            }
+#else
+            asm volatile("" :: "v"(c[0]), "v"(c[5]), "v"(c[10]), "v"(c[15]));
+#endif
+        };
+#ifndef ZMI_EXP_LIT_NOSTEADY                 // (diagnostic build without the steady form, DEFS=-DZMI_EXP_LIT_NOSTEADY: every group in the general form)
+        // ---- The steady form: groups that stay clear of the stream's start, which is all but the last two or three of a stream.
+        // S = (s7 : ... : s0), 32 stream bytes as 8 little-endian dwords, s7 highest: (s7 .. s4) = bytes [sp, sp + 16) are kept
+        // from step to step, (s3 .. s0) = [sp - 16, sp) are the look-ahead load issued a step (8 symbols) ago.  P = how many
+        // bits below the top of S the next unread bit lies: 1 .. 32 at a step's start, at most 32 + 88 = 120 at its end.
+        // The re-base for a step, rebase_regs() and rebase_window(), (1) drops the M = (P - 1) / 32 <= 3 dwords used up — selects
+        // between registers, no shift: sp moves by 4 M bytes and P by 32 M, and is in 1 .. 32 again — (2) issues the next look-ahead
+        // load, and (3) builds the 128-bit window at P, one v_alignbit_b32 per dword by (32 - P) mod 32 (for P = 32 that is the
+        // lower dword, whole), into the SHADOW registers (w2, r2, q2, p2): all their 128 bits are stream bits, because S holds
+        // 128 bits below any P <= 32 + 96.  None of this is on the path from one lookup to the next.  It runs at the head of the
+        // NEXT step, behind that step's first fetch, and the lookups go on from w, the window of the step before, whose bits are the
+        // same stream bits as far as they reach (alignbit(x, 0, e) shifts zeros in below them).  The shadow is shifted along by the
+        // first two symbols' lengths and takes over behind the second: the third lookup's w is alignbit(w2, r2, e) in place of
+        // alignbit(w, r, e), the same single instruction behind the entry.  A window is whole where it is built and serves ten
+        // lookups: the last six of its own step and the first two of the next; how many of its bits are still exact at each of
+        // them, against the 11 a lookup reads (the longest code; with PAIRS the pair entries' constant length IDX + 1 = 11 is that
+        // same maximum), is counted in front of the step below.
+        // A step moves sp by at most 12 bytes and the load reads down to sp - 16: a group of 8 steps runs in this form only
+        // if sp >= 8 x 12 + 16 at its start, so that no address needs a clamp and no byte below the stream's start is asked for.
+        if (srcSize >= 128) {
+            s32 sp = (s32)srcSize - 16;
+            u32 s7, s6, s5, s4, s3 = 0, s2 = 0, s1 = 0, s0 = 0;
+            { const u64 lo = readLE64(src + sp), hi = readLE64(src + sp + 8); s4 = (u32)lo; s5 = (u32)(lo >> 32); s6 = (u32)hi; s7 = (u32)(hi >> 32); }
+            u32 P = 8u * srcSize - (u32)remaining;                     // 1 .. 8: the end mark and the zero bits above it
+            u32 w = 0, w2 = 0, r2 = 0, q2 = 0, p2 = 0;
+            auto sload = [&]() {
+#ifdef ZMI_EXP_LIT_LOADFIX
+                const u8* a = src;               // (ablation: as in load_low below)
+#else
+                const u8* a = src + (sp - 16);
+#endif
+                const u64 lo = readLE64(a), hi = readLE64(a + 8);
+                s0 = (u32)lo; s1 = (u32)(lo >> 32); s2 = (u32)hi; s3 = (u32)(hi >> 32);
+            };
+            u32 t3 = 0;
+            auto rebase_regs = [&](const u32 g) {                      // (1) and (2): the registers of S, sp, and the load
+#ifdef ZMI_EXP_LIT_NOREBASE                  // ablation build (diagnostic, DEFS=-DZMI_EXP_LIT_NOREBASE): the same lookups, loads and stores
+                const u32 M = 1u + (g & 1u); P = 32u + 32u * M;        // without the re-base arithmetic: 6 bytes a step, dword moves only
+#else
+                const u32 M = ((P - 1u) >> 5) & 3u; (void)g;           // (& 3: sp never moves by more than 12, whatever a table holds)
+#endif
+                const bool b0 = M & 1u, b1 = M & 2u;
+                const u32 u7 = b0 ? s6 : s7, u6 = b0 ? s5 : s6, u5 = b0 ? s4 : s5, u4 = b0 ? s3 : s4, u3 = b0 ? s2 : s3, u2 = b0 ? s1 : s2, u1 = b0 ? s0 : s1;
+                s7 = b1 ? u5 : u7; s6 = b1 ? u4 : u6; s5 = b1 ? u3 : u5; s4 = b1 ? u2 : u4; t3 = b1 ? u1 : u3;
+                P -= 32u * M; sp -= 4 * (s32)M;
+                sload();
+            };
+            auto rebase_window = [&]() {                               // (3): the window at P, which is now 1 .. 32
+                const u32 sh = 0u - P;                                 // (alignbit takes the low 5 bits of its count)
+                w2 = __builtin_amdgcn_alignbit(s7, s6, sh); r2 = __builtin_amdgcn_alignbit(s6, s5, sh);
+                q2 = __builtin_amdgcn_alignbit(s5, s4, sh); p2 = __builtin_amdgcn_alignbit(s4, t3, sh);
+            };
+            // Which registers a shift must still produce follows from how many lookups the window has left, 11 bits each at the most
+            // (a shift by len keeps exact what was exact below it, up to the registers kept; what alignbit(x, 0, e) shifts in is not):
+            //   built: 128 exact bits.  Behind the 1st symbol >= 117 (4 registers shifted), behind the 2nd the main registers take
+            //   over (w, r, q) = 96, of which the 8 lookups left (3rd .. 8th, and the next step's two) need 88; then 85 of 77 needed,
+            //   74 of 66; from the 5th symbol on q is read but not shifted: 63 of 55; from the 6th r takes zeros: 52 of 44, 41 of 33;
+            //   behind the 8th only w is kept: 30 of 22, and behind the next step's 1st 19, of which its 2nd lookup reads 11.
+            // So every lookup finds at least 11 exact bits at the top of w, 19 in the worst case (eleven-bit codes throughout).
+            auto ab = [&](const u32 hi, const u32 lo, const u32 e) -> u32 { return __builtin_amdgcn_alignbit(hi, lo, e); };
+            // one step = 8 symbols -> two dwords
+            auto sstep = [&](const u32 g, u32& word0, u32& word1) {
+                u32 e, sum, r, q, y[8];
+                const u32 e0 = fetch(w);         // the first lookup is on its way: the re-base for the step before runs behind it
+#if defined(ZMI_EXP_LIT_FENCE) && defined(__HIP_DEVICE_COMPILE__)     // (diagnostic build, DESIGN 11: pins the re-base behind the fetch in the schedule)
+                __builtin_amdgcn_sched_barrier(0);
+#endif
+                rebase_regs(g); rebase_window();
+                y[0] = entry(w, e0, e); sum = e;
+                w = ab(w, 0u, e);
+                w2 = ab(w2, r2, e); r2 = ab(r2, q2, e); q2 = ab(q2, p2, e); p2 = ab(p2, 0u, e);
+                y[1] = look(w, e); sum += e;
+                w = ab(w2, r2, e); r = ab(r2, q2, e); q = ab(q2, p2, e);
+                y[2] = look(w, e); sum += e; w = ab(w, r, e); r = ab(r, q, e); q = ab(q, 0u, e);
+                y[3] = look(w, e); sum += e; w = ab(w, r, e); r = ab(r, q, e); q = ab(q, 0u, e);
+                y[4] = look(w, e); sum += e; w = ab(w, r, e); r = ab(r, q, e);
+                y[5] = look(w, e); sum += e; w = ab(w, r, e); r = ab(r, 0u, e);
+                y[6] = look(w, e); sum += e; w = ab(w, r, e); r = ab(r, 0u, e);
+                y[7] = look(w, e); sum += e; w = ab(w, r, e);
+                word0 = y[0] | (y[1] << 8) | (y[2] << 16) | (y[3] << 24);
+                word1 = y[4] | (y[5] << 8) | (y[6] << 16) | (y[7] << 24);
+                P += 8u * 32u - (sum & 0xFFu);   // (e2's low byte is 32 - length, at most 31: eight of them do not carry out of it)
+            };
+            sload();
+            rebase_regs(0); rebase_window();     // (P <= 8: no dword dropped) the first window; the load is the same one again
+            w = w2;
+            while (i + 64 <= n) {
+                const bool quads = quadStore && i + 64 <= nQuad;       // the same on the 4 lanes of a quad, and so is i while it holds
+                u32 go = sp >= 8 * 12 + 16;
+                if (quads) {                                           // ... and so must the form be: the transposed stores need all 4 lanes
+                    go &= (u32)__builtin_amdgcn_mov_dpp((int)go, 0xB1, 0xF, 0xF, true);      // (a lane that is not here reads as 0)
+                    go &= (u32)__builtin_amdgcn_mov_dpp((int)go, 0x4E, 0xF, 0xF, true);
+                }
+                if (!go) break;
+                u32 d[16];
+#pragma unroll
+                for (u32 g = 0; g < 8; ++g) sstep(g, d[2 * g], d[2 * g + 1]);
+                touch(sp);
+                if (quads) store_quad(d); else store_plain(d);
+                i += 64;
+#ifdef ZMI_LIT_PATHS
+                ZMI_LIT_PATHS(0);
+#endif
+            }
+            remaining = 8 * (sp + 16) - (s32)P;
+        }
+#endif
+        // ---- The general form, for the groups left: those that may reach the stream's start.
         // The stream is read from its last byte down.  cont = stream bytes [ptr, ptr + 8); (lowHi, lowLo) = the 16 bytes below it,
         // [ptr - 8, ptr) and [ptr - 16, ptr - 8), loaded one step (8 symbols) ahead of their use; bytes below the stream's start
         // read as zero.  A step decodes 8 symbols (at most 88 bits) out of the 96 bits behind the `consumed` (<= 8) bits already
@@ -293,7 +462,7 @@ __device__ __forceinline__ bool huf_decode_stream_fs(const u32 tOff, const u32 n
         // starts at once — and issues the load that replaces (lowHi, lowLo) by the exact 16 bytes below the new cont.  The load
         // has 8 symbols' time to arrive (an L2 hit takes about 4 symbols' time), and between two store groups (64 symbols) it
         // is not behind any store: vmcnt counts loads and stores together, in order, so a load issued after a store waits for it.
-        s32 ptr = (s32)srcSize - 8;
+        s32 ptr = ((remaining + 7) >> 3) - 8;                          // the byte that holds the next bit is the top byte of cont
         u64 cont = readLE64(src + ptr);
         u64 lowHi = 0, lowLo = 0;
         auto load_low = [&]() {
@@ -304,21 +473,6 @@ __device__ __forceinline__ bool huf_decode_stream_fs(const u32 tOff, const u32 n
             const u8* a = src + (lp > 0 ? lp : 0);
 #endif
             lowLo = readLE64(a); lowHi = readLE64(a + 8);
-        };
-        // Behind the eighth step's load_low of every second 64-symbol group: a 4-byte load ZMI_LIT_AHEAD bytes further down the
-        // stream, whose value nobody needs.  It brings that line into L2 before the exact loads get there, so that those hit (two
-        // groups move 92 bytes on average: nearly every 128-byte line is touched, once or twice; touching in every group, or only
-        // where the address enters a new line, measured slower: DESIGN 11).  A plain load, which the compiler counts in its vmcnt
-        // waits (a volatile one is waited for with vmcnt(0) right behind it).  The empty asm in front of the next touch is its only
-        // use: that keeps the load, and keeps its register claimed until then — a register free for reuse would be waited for in
-        // front of whatever reuses it.
-        u32 touched = 0;
-        auto touch = [&]() {
-#if defined(ZMI_LIT_AHEAD) && ZMI_LIT_AHEAD      // (zmi_lit_ahead.h; a build of this function without it — tests/host/lit_stream_harness.cpp — has no touch)
-            if (i & 64u) return;
-            asm volatile("" :: "v"(touched));
-            touched = *(const u32u*)(src + lit_touch_offset(ptr, (s32)srcSize, ZMI_LIT_AHEAD));
-#endif
         };
         auto fix_low = [&]() {           // bytes below the stream's start are zero (only the last steps of a stream get here)
             const s32 lp = ptr - 16;
@@ -332,10 +486,7 @@ __device__ __forceinline__ bool huf_decode_stream_fs(const u32 tOff, const u32 n
             }
         };
         load_low();
-        const u32 last = (u32)(cont >> 56);
-        if (!last) return false;
-        remaining = (s32)(srcSize - 1) * 8 + (s32)highbit32(last);
-        u32 consumed = 64u - (u32)(remaining - 8 * ptr);               // 1 .. 8
+        u32 consumed = 64u - (u32)(remaining - 8 * ptr);               // 0 .. 7
         u32 hiTop;                                                     // the 4 bytes right below cont: all a window needs beyond cont
         {   // (computed on a copy: the registers themselves are fixed where they are used, in the first step's re-base)
             const u64 h0 = lowHi, l0 = lowLo;
@@ -349,6 +500,11 @@ __device__ __forceinline__ bool huf_decode_stream_fs(const u32 tOff, const u32 n
             u32 w = (u32)(top >> 32), r = (u32)(mid >> 32), q = (u32)mid, spare = 0;
             word0 = sym1(w, r, q, spare); word0 |= sym1(w, r, q, spare) << 8; word0 |= sym1(w, r, q, spare) << 16; word0 |= sym1(w, r, q, spare) << 24;
             word1 = sym1(w, r, q, spare); word1 |= sym1(w, r, q, spare) << 8; word1 |= sym1(w, r, q, spare) << 16; word1 |= sym1(w, r, q, spare) << 24;
+#ifdef ZMI_EXP_LIT_NOREBASE                  // ablation build (diagnostic, DEFS=-DZMI_EXP_LIT_NOREBASE): the same lookups, loads and stores
+            consumed = 3; cont = lowHi; hiTop = (u32)(lowLo >> 32); ptr -= 6;      // without the re-base arithmetic; garbage symbols; load_low clamps
+            load_low();
+            return;
+#endif
             consumed += 8u * 32u - spare;
             // re-base by k whole bytes out of the 24 bytes in registers (now exact: the load issued a step ago has arrived)
             fix_low();
@@ -361,51 +517,27 @@ __device__ __forceinline__ bool huf_decode_stream_fs(const u32 tOff, const u32 n
             ptr -= (s32)k; consumed &= 7u;
             load_low();
         };
-        if (quadStore) {
-            const bool odd1 = ql & 1u, odd2 = ql & 2u;
-            u8* const tbase = out - (size_t)ql * seg + 16u * ql;       // stream 0's base + this lane's 16-byte column
-            while (i + 64 <= nQuad) {
-                u32 d[16];
+        while (quadStore && i + 64 <= nQuad) {
+            u32 d[16];
 #pragma unroll
-                for (u32 g = 0; g < 8; ++g) step(d[2 * g], d[2 * g + 1]);
-                touch();
-                // 4 x 4 transpose of 16-byte pieces over the quad's lanes: piece p of lane l <-> piece l of lane p
-                u32 b[16], c[16];
-#pragma unroll
-                for (u32 p = 0; p < 4; ++p)
-#pragma unroll
-                    for (u32 k = 0; k < 4; ++k) {
-                        const u32 nb1 = (u32)__builtin_amdgcn_mov_dpp((int)d[4 * (p ^ 1u) + k], 0xB1, 0xF, 0xF, true);    // lane ^ 1's piece p ^ 1
-                        b[4 * p + k] = (odd1 == (bool)(p & 1u)) ? d[4 * p + k] : nb1;
-                    }
-#pragma unroll
-                for (u32 p = 0; p < 4; ++p)
-#pragma unroll
-                    for (u32 k = 0; k < 4; ++k) {
-                        const u32 nb2 = (u32)__builtin_amdgcn_mov_dpp((int)b[4 * (p ^ 2u) + k], 0x4E, 0xF, 0xF, true);    // lane ^ 2's piece p ^ 2
-                        c[4 * p + k] = (odd2 == (bool)(p & 2u)) ? b[4 * p + k] : nb2;
-                    }
-#ifndef ZMI_EXP_LIT_NOSTORE                  // (ablation build, DEFS=-DZMI_EXP_LIT_NOSTORE, DESIGN 11: the same steps without the transposed stores)
-#pragma unroll
-                for (u32 p = 0; p < 4; ++p) {
-                    u32u* o = (u32u*)(tbase + (size_t)p * seg + i);
-                    o[0] = c[4 * p]; o[1] = c[4 * p + 1]; o[2] = c[4 * p + 2]; o[3] = c[4 * p + 3];
-                }
-#else
-                asm volatile("" :: "v"(c[0]), "v"(c[5]), "v"(c[10]), "v"(c[15]));
+            for (u32 g = 0; g < 8; ++g) step(d[2 * g], d[2 * g + 1]);
+            touch(ptr);
+            store_quad(d);
+            i += 64;
+#ifdef ZMI_LIT_PATHS
+            ZMI_LIT_PATHS(1);
 #endif
-                i += 64;
-            }
         }
         while (i + 64 <= n) {
             u32 d[16];
 #pragma unroll
             for (u32 g = 0; g < 8; ++g) step(d[2 * g], d[2 * g + 1]);
-            touch();
-            u32u* o = (u32u*)(out + i);
-#pragma unroll
-            for (u32 g = 0; g < 16; ++g) o[g] = d[g];
+            touch(ptr);
+            store_plain(d);
             i += 64;
+#ifdef ZMI_LIT_PATHS
+            ZMI_LIT_PATHS(1);
+#endif
         }
 #if defined(ZMI_LIT_AHEAD) && ZMI_LIT_AHEAD
         asm volatile("" :: "v"(touched));
@@ -416,6 +548,9 @@ __device__ __forceinline__ bool huf_decode_stream_fs(const u32 tOff, const u32 n
             step(d0, d1);
             u32u* o = (u32u*)(out + i); o[0] = d0; o[1] = d1;
             i += 8;
+#ifdef ZMI_LIT_PATHS
+            ZMI_LIT_PATHS(1);
+#endif
         }
         remaining = 8 * ptr + 64 - (s32)consumed;
     } else {
@@ -425,6 +560,9 @@ __device__ __forceinline__ bool huf_decode_stream_fs(const u32 tOff, const u32 n
     }
     if (i < n && remaining > 0) {        // short stream, or the last symbols of a long one: plain bit reader
         BackBits bd; bd.base = src; bd.size = (s32)srcSize; bd.pos = remaining; bd.load_window(remaining);
+#ifdef ZMI_LIT_PATHS
+        ZMI_LIT_PATHS(2);
+#endif
         while (i < n) {
             u32 w = bd.peek(IDX + 1) << (31 - IDX), r = 0, q = 0, spare = 0;
             out[i++] = (u8)sym1(w, r, q, spare);
@@ -467,7 +605,7 @@ __device__ __forceinline__ void quad_symbol_starts(QuadLds& Q, u32 nbSymbols, u3
 // One block on the 4 lanes of a quad.  The job is computed redundantly by the 4 lanes (same loads, same values, so the quad's
 // control flow is uniform without any cross-lane traffic); only the weight decoding runs on the quad leader.
 // Returns an error code, or 0xFFFF to ask for the slow path (12-bit table).
-__device__ u32 quad_decode_literals(u16* __restrict__ huf, QuadLds& Q, const LitJob& J, const u32 ql)
+__device__ __forceinline__ u32 quad_decode_literals(u16* __restrict__ huf, QuadLds& Q, const LitJob& J, const u32 ql)
 {
     if (ql == 0) {
         QuadScratch sc;
@@ -530,7 +668,7 @@ struct CompactLds {             // (the tables live in their own LDS array, alig
 };
 
 // One block on the 4 lanes of a quad (compact tables).  Returns an error code, or 0xFFFF to ask for the slow path.
-__device__ u32 quad_decode_literals_c(u16* __restrict__ huf, CompactLds& Q, const LitJob& J, const u32 ql)
+__device__ __forceinline__ u32 quad_decode_literals_c(u16* __restrict__ huf, CompactLds& Q, const LitJob& J, const u32 ql)
 {
     u8* const weights = reinterpret_cast<u8*>(huf + 896);       // top 256 B of the table area until the fill
     if (ql == 0) {
@@ -977,7 +1115,7 @@ static u32 literal_decoder_for(u32 nBlocks)
     int dev = 0; (void)hipGetDevice(&dev);
     if (!cus[dev & 63]) { int n = 0; (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev); cus[dev & 63] = n > 0 ? n : 256; }
     const u32 roundS = (u32)cus[dev & 63] * 32u, roundC = roundS * 2u;
-    if (nBlocks <= roundS * 3u / 4u) return 2;
+    if (nBlocks < roundS / 2u) return 2;        // (below 4096 blocks on 256 CUs: 0.26 ms per 1024 blocks against the serial round's 1.0)
     const float tS = (float)((nBlocks + roundS - 1) / roundS) * 1.7f, tC = (float)((nBlocks + roundC - 1) / roundC) * 2.7f;
     return tC < tS ? 3u : 1u;
 }
