@@ -9,12 +9,13 @@ compare against.  Fields that make a frame INVALID can be asked for too (negativ
 Description (plain dicts / tuples, see tests/forge_cases.py for many examples):
 
   frame(blocks, single=None, fcs=None, fcs_value=None, window=None, did=0, checksum=False, reserved=False,
-        bad_checksum=False, valid=True)
+        bad_checksum=False, valid=True, history=b"", did_value=0)
       single   single-segment (the content size is the window); None = where no block is larger than the content, else a
                window descriptor that holds the content (also where an invalid description has no content size to state)
       fcs      content-size field in bytes: 0, 1, 2, 4, 8 or None = the smallest that holds the size (none under a window)
       window   the window descriptor byte (exponent << 3 | mantissa); needs single=False
-      did      size of a dictionary-ID field (0, 1, 2, 4); it holds 0
+      did      size of a dictionary-ID field (0, 1, 2, 4); it holds did_value (default 0)
+      history  bytes in front of the frame that offsets may reach (a dictionary's content, a prefix); not part of the content
 
   block:   {"t": "raw", "data": b"..."}          {"t": "rle", "byte": 65, "size": 1000}        {"t": "reserved"}
            {"t": "c", "lit": LIT, "seqs": [(litLength, offset_value, matchLength), ...],
@@ -434,10 +435,10 @@ def rep_step(rep, ll, ov):
     return off, ([off, rep[0], rep[1]] if idx >= 2 else [off, rep[0], rep[2]])
 
 
-def execute(blocks, sizes=None):
+def execute(blocks, sizes=None, history=b""):
     """the content a frame of these blocks regenerates (RFC 8878 3.1.1.4 and 3.1.1.5), or ForgeInvalid; `sizes`, a list, takes
-    the size each block regenerates"""
-    out = bytearray()
+    the size each block regenerates; `history` lies in front of the frame: offsets may reach into it, the content does not hold it"""
+    out = bytearray(history)
     rep = [1, 4, 8]
     for blk in blocks:
         t = blk["t"]
@@ -455,7 +456,7 @@ def execute(blocks, sizes=None):
                 lp += ll
                 off, rep = rep_step(rep, ll, ov)
                 if off > len(out):
-                    raise ForgeInvalid("offset reaches before the frame")
+                    raise ForgeInvalid("offset reaches before the frame and its history")
                 if off >= ml:
                     out += out[len(out) - off:len(out) - off + ml]
                 else:
@@ -468,7 +469,7 @@ def execute(blocks, sizes=None):
             raise ForgeInvalid("reserved block type")
         if sizes is not None:
             sizes.append(len(out) - start)
-    return bytes(out)
+    return bytes(out[len(history):])
 
 
 # ------------------------------------------------------------------------------------------------------------- frame
@@ -493,10 +494,10 @@ def block_bytes(blk, last, fs):
 
 
 def frame(blocks, single=None, fcs=None, fcs_value=None, window=None, did=0, checksum=False, reserved=False,
-          bad_checksum=False, valid=True):
+          bad_checksum=False, valid=True, history=b"", did_value=0):
     regen = []
     try:
-        content = execute(blocks, regen)
+        content = execute(blocks, regen, history)
     except ForgeInvalid:
         assert not valid, "the description is invalid but was declared valid"
         content = None
@@ -524,7 +525,7 @@ def frame(blocks, single=None, fcs=None, fcs_value=None, window=None, did=0, che
     out += bytes([(flag << 6) | (single << 5) | (reserved << 3) | (checksum << 2) | {0: 0, 1: 1, 2: 2, 4: 3}[did]])
     if not single:
         out += bytes([window])
-    out += bytes(did)
+    out += did_value.to_bytes(did, "little")
     if fcs:
         out += (size - 256 if fcs == 2 else size).to_bytes(fcs, "little")
     out += b"".join(body)
